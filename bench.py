@@ -121,7 +121,15 @@ def parse():
                     help="batch mode with --gpus > 1: after the weak line's own timed region, run `--mode rows --gather-minima` (ONE "
                          "SLSQP iteration's rows over the ranks, sparse minima all-gather: `scaling` strong) for C3 and for C4 in the "
                          "same processes and carry both in the line's `modes` -- one command, both curves (also OBTG_BENCH_ALL_MODES=1)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float64; "
+                         "at most 64 MB in all: a larger batch is cut to a fixed, seeded sample of its rows, named by "
+                         "DIR/sample_rows.npy; entries the library leaves undefined, NaN, are written as 0 beside the flag or "
+                         "status that marks them); the same arguments give the same inputs and the same sample")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------
@@ -324,6 +332,7 @@ def main():
             for wl in ("C3", "C4"):
                 a2 = copy.copy(args)
                 a2.mode, a2.workload, a2.gather_minima, a2.no_cpu, a2.batch = "rows", wl, "sparse", True, 0
+                a2.dump_outputs = None          # --dump-outputs: the weak line's own timed path
                 a2.steps = args.steps if wl == "C3" else max(3, min(args.steps, 10))
                 a2.warmup = args.warmup if wl == "C3" else max(1, min(args.warmup, 2))
                 l2 = step_bench(a2, env)
@@ -561,6 +570,18 @@ def step_bench(args, env):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     stats_timed = kstats()
+    if args.dump_outputs and rank == 0:
+        # the result buffers of the last timed step, as the step's caller receives them (rows of this rank; before anything
+        # below rewrites them)
+        outs = dict(temporal_sep=o_sep, speed=o_sp, ang_rate=o_an)
+        if use_gjk:
+            outs.update(gjk_flag=g_flag, gjk_dist=g_dist, gjk_p1=g_p1, gjk_p2=g_p2, gjk_status=g_stat)
+        dump = sample_batch(outs, first_row=row_begin)
+        if use_gjk:
+            # gjkNew's distance and closest points are defined where it separated the pair and its search ended (flag 1,
+            # status OK); the library leaves NaN in the others, written here as 0 -- gjk_flag and gjk_status say which
+            zero_undefined(dump, ("gjk_dist", "gjk_p1", "gjk_p2"), (dump["gjk_flag"] != 1) | (dump["gjk_status"] != 0))
+        dump_outputs(args.dump_outputs, dump)
     # sample rows of the buffers the last timed step left behind, for the parity check (before anything rewrites them)
     status_nonok = int((g_stat != 0).sum().item()) if use_gjk else 0
     snap = None
@@ -914,6 +935,59 @@ def step_bench(args, env):
     return None
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6
+_NPY_HEADER_BYTES = 128       # what np.save puts before the data of an array of these shapes
+
+
+def dump_sample_rows(n_rows, row_bytes, limit, seed=2024):
+    """--dump-outputs: None when all n_rows rows of row_bytes each fit in `limit` bytes, else the sorted row ids of a fixed,
+    seeded sample that does -- the first and the last row always among them."""
+    keep = int(limit // max(row_bytes, 1))
+    if keep >= n_rows:
+        return None
+    if keep < 2:
+        raise SystemExit("bench.py --dump-outputs: one row of %d bytes does not fit in %d" % (row_bytes, limit))
+    inner = np.random.default_rng(seed).choice(np.arange(1, n_rows - 1), size=keep - 2, replace=False)
+    return np.sort(np.concatenate(([0, n_rows - 1], inner))).astype(np.int64)
+
+
+def sample_batch(outs, first_row=0):
+    """--dump-outputs of a step's device buffers (name -> tensor, one row per batch row): host copies of every row when they fit,
+    else of the same seeded sample of rows from every buffer; "sample_rows" names the rows."""
+    import torch
+    outs = {k: v for k, v in outs.items() if v is not None}
+    B = next(iter(outs.values())).shape[0]
+    rows = dump_sample_rows(B, sum(8 * v[0].numel() for v in outs.values()),
+                            DUMP_LIMIT_BYTES - _NPY_HEADER_BYTES * (len(outs) + 1) - 8 * B)
+    if rows is not None:
+        outs = {k: v.index_select(0, torch.as_tensor(rows, device=v.device)) for k, v in outs.items()}
+    dump = {k: v.cpu().numpy() for k, v in outs.items()}
+    dump["sample_rows"] = first_row + (rows if rows is not None else np.arange(B))
+    return dump
+
+
+def zero_undefined(dump, names, undefined):
+    """--dump-outputs: 0 in the entries of dump[name] (first axes shaped like `undefined`) that the library leaves undefined (NaN)."""
+    for k in names:
+        dump[k] = np.where(undefined.reshape(undefined.shape + (1,) * (dump[k].ndim - undefined.ndim)), 0.0, dump[k])
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: name -> array as path/<name>.npy in float64 (integer results convert exactly); refuses to write more
+    than DUMP_LIMIT_BYTES in all, or a value that is not finite (the callers have replaced what the library leaves undefined:
+    any other NaN or inf is a wrong result)."""
+    out = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items() if v is not None}
+    bad = ["%s (%d values)" % (k, int((~np.isfinite(a)).sum())) for k, a in out.items() if not np.isfinite(a).all()]
+    if bad:
+        raise SystemExit("bench.py --dump-outputs: outputs that are not finite: %s" % ", ".join(bad))
+    total = sum(a.nbytes + _NPY_HEADER_BYTES for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def parity_snapshot(dev_out, B):
     """Host copies of a sample of rows of the step's device buffers: first, last, and rows of every residue
     mod 8 (consecutive rows of a launch go to the 8 XCDs round-robin)."""
@@ -1019,6 +1093,14 @@ def pairs_mode(args, ctx, dist, world, rank, dev, dY, B, max_sep, barrier, pa, p
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        # what the last timed step returned: the gathered separation minima (and gjkNew's dist / flag when gathered; else
+        # this rank's block of them)
+        g_dist, g_flag = (out[1], out[2]) if gather_gjk else ((hull._buf[0], hull._buf[1]) if hull is not None else (None, None))
+        dump = sample_batch(dict(temporal_sep_min=out[0], gjk_dist=g_dist, gjk_flag=g_flag))
+        if g_dist is not None:          # the distance is defined where gjkNew separated the pair (NaN elsewhere: written as 0)
+            zero_undefined(dump, ("gjk_dist",), dump["gjk_flag"] != 1)
+        dump_outputs(args.dump_outputs, dump)
     # proof of ranks: what the process group itself reports, and the device every rank ran on
     ranks_seen = dist.get_world_size() if use_dist else 1
     me = "%s #%d pid %d" % (torch.cuda.get_device_name(dev), dev.index if dev.index is not None else 0, os.getpid())
@@ -1162,6 +1244,7 @@ def mindist_line(args, cpu=True, legs=None, cpu_seconds=None):
     if cpu:
         from oracle import oracle as O
         O.build()
+    dump = {}
     for name, f in all_legs:
         if legs is not None and name not in legs:
             continue
@@ -1179,6 +1262,9 @@ def mindist_line(args, cpu=True, legs=None, cpu_seconds=None):
         for _ in range(reps):
             r = f()
         ms = 1e3 * (time.perf_counter() - t0) / reps
+        # the last timed call's results (--dump-outputs); a search stopped by a budget (status != OK) has no result: 0 there
+        dump.update(("%s_%s" % (name, k), v) for k, v in r.items())
+        zero_undefined(dump, ("%s_res" % name,), r["status"] != 0)
         kms, kcnt = ctx.kernel_stats().get("min_dist", (0.0, 0))
         ctx.set_profiling(False)
         nodes = int(r["nodes"].sum())
@@ -1251,12 +1337,16 @@ def mindist_line(args, cpu=True, legs=None, cpu_seconds=None):
         t0 = time.perf_counter()
         F = bo.spatialSeparationConstraints(x, robust=True)
         ms_f = 1e3 * (time.perf_counter() - t0)
+        dump["provider_constraints"] = F
+        dump["provider_jacobian"] = J
         out["provider_end_to_end"] = dict(
             ms_per_jacobian=round(ms, 2), first_ms=round(first_ms, 2), ms_per_constraint_evaluation=round(ms_f, 2),
             jacobian_shape=list(J.shape), nonzeros=int(np.count_nonzero(J)), finite=bool(np.isfinite(J).all() and np.isfinite(F).all()),
             what="BezOptimization.spatialSeparationJacobian(x, robust=True, column=0) at C5 size, host arrays in and out: plan of the ONE "
                  "call (114 000 searches), obtg_min_dist_robust, dense (4560 x 1152) matrix; and one spatialSeparationConstraints(x, robust=True); "
                  "what ONE SLSQP iteration of Examples/ComplexObstacles.py:49-63 costs through the provider instead of n_x + 1 sweeps")
+    if args.dump_outputs and dump and int(os.environ.get("RANK", "0")) == 0:     # (every leg: about 56 MB)
+        dump_outputs(args.dump_outputs, dump)
     head = out.get("jacobian_list") or out.get("reference_algorithm") or next(iter(out.values()))
     return {"metric": "spatial-separation (_minDist) evals/s, host buffers in and out", "value": (out.get("reference_algorithm") or head).get("evals_per_s"),
             "unit": "constraint-evals/s", "n_gpus": 1, "higher_is_better": True, "dtype": "f64", "data": "synthetic",
@@ -1293,6 +1383,8 @@ def c1_text_mode(args, rank):
     for _ in range(args.steps):
         F = step()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:      # the three closures' rows of the last timed step
+        dump_outputs(args.dump_outputs, {"temporal_sep": F[0], "speed": F[1], "ang_rate": F[2]})
     B = x.size + 1
     ms = 1e3 * elapsed / args.steps
     # the kernels behind it: HIP events on every launch of a replay

@@ -190,6 +190,30 @@ def test_bench_all_modes_two_ranks():
         assert abs(c1[k] - c2[k]) <= 1e-11 * abs(c1[k]), k
 
 
+def test_bench_dump_outputs_same_run_to_run(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's result buffers as finite float64 .npy files (gjkNew's distance 0
+    where its flag leaves it undefined), under 64 MB, the same files from two runs with the same arguments (seeded inputs), and
+    a sampled batch's rows named in sample_rows.npy."""
+    args = ["--gpus", "1", "--workload", "C3", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-variants"]
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    lines = [_bench(args + ["--dump-outputs", p]) for p in dirs]
+    assert lines[0]["steps"] == 3
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1]))
+    assert {"temporal_sep.npy", "speed.npy", "gjk_flag.npy", "gjk_dist.npy", "sample_rows.npy"} <= set(names)
+    assert sum(os.path.getsize(os.path.join(dirs[0], f)) for f in names) <= 64 * 10**6
+    for f in names:
+        a, b = np.load(os.path.join(dirs[0], f)), np.load(os.path.join(dirs[1], f))
+        assert a.dtype == np.float64 and np.isfinite(a).all() and np.array_equal(a, b), f
+    flag, dist = np.load(os.path.join(dirs[0], "gjk_flag.npy")), np.load(os.path.join(dirs[0], "gjk_dist.npy"))
+    assert (dist[flag != 1] == 0).all() and (dist[flag == 1] >= 0).all() and (flag == 0).any() and (dist[flag == 1] > 0).any()
+    rows = np.load(os.path.join(dirs[0], "sample_rows.npy"))
+    B = lines[0]["config"]["evals_per_step_per_gpu"]
+    assert rows[0] == 0 and rows[-1] == B - 1 and len(rows) < B            # C3's 1153 rows do not fit: a sample
+    assert np.load(os.path.join(dirs[0], "temporal_sep.npy")).shape[0] == len(rows) == np.load(os.path.join(dirs[0], "gjk_p1.npy")).shape[0]
+    assert np.isfinite(np.load(os.path.join(dirs[0], "speed.npy"))).all()
+
+
 def test_default_bench_line_keeps_the_contract():
     """`python bench.py` as the driver runs it (shortened): ONE JSON line with the contract's keys, the C3 workload as one
     launch per step, `roofline` and `cpu_baseline` objects complete, and the bench's own check of its device buffers

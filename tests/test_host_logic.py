@@ -288,3 +288,35 @@ def test_counter_files_carry_their_provenance_and_stale_ones_are_refused(tmp_pat
         assert _capi.source_hash(unit) == want[unit], unit
     assert _capi.source_hash("no such unit") is None
     assert _capi.libm_pow_matches() is True          # this image's glibc 2.35 is what csrc/libm_pow2.h restates (obtg_libm_pow_matches)
+
+
+def test_bench_dump_helpers_sample_and_cap(tmp_path):
+    """bench.py --dump-outputs: the row sample is fixed by its arguments (first and last row kept), a batch that fits is
+    written whole, every file is float64 (integer results exactly), and more than 64 MB, or a value that is not finite, is
+    refused rather than written."""
+    import importlib.util
+    import os
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(repo, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.dump_sample_rows(10, 100, 1000) is None
+    rows = bench.dump_sample_rows(1153, 552448, bench.DUMP_LIMIT_BYTES)
+    assert np.array_equal(rows, bench.dump_sample_rows(1153, 552448, bench.DUMP_LIMIT_BYTES))
+    assert rows[0] == 0 and rows[-1] == 1152 and len(np.unique(rows)) == len(rows) and len(rows) * 552448 <= bench.DUMP_LIMIT_BYTES
+    out = str(tmp_path / "dump")
+    bench.dump_outputs(out, {"flag": np.array([[1, -1], [0, 2]], dtype=np.int32), "dist": np.array([0.5, -0.0]), "none": None})
+    assert sorted(os.listdir(out)) == ["dist.npy", "flag.npy"]
+    flag = np.load(os.path.join(out, "flag.npy"))
+    assert flag.dtype == np.float64 and np.array_equal(flag, [[1, -1], [0, 2]])
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 8)})
+    assert not os.path.exists(str(tmp_path / "big"))
+    # what the library leaves undefined (NaN where gjkNew's flag / status says so) is written as 0; any other NaN is refused
+    dump = {"gjk_flag": np.array([[1, 0]]), "gjk_dist": np.array([[0.25, np.nan]]), "gjk_p1": np.array([[[1.0, 2.0, 0.0], [np.nan] * 3]])}
+    bench.zero_undefined(dump, ("gjk_dist", "gjk_p1"), dump["gjk_flag"] != 1)
+    assert np.array_equal(dump["gjk_dist"], [[0.25, 0.0]]) and np.array_equal(dump["gjk_p1"], [[[1.0, 2.0, 0.0], [0.0] * 3]])
+    bench.dump_outputs(str(tmp_path / "gjk"), dump)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "nan"), {"gjk_dist": np.array([[0.25, np.nan]])})
+    assert not os.path.exists(str(tmp_path / "nan"))

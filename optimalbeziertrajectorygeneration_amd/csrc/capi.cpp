@@ -1216,7 +1216,13 @@ int obtg_min_dist(obtg_ctx* c, const double* curves, int n_curves, int K, const 
     if (rc) return rc;
     if ((rc = h2d(c, m[1], pair_a, sizeof(int) * n_pairs))) return rc;
     if ((rc = h2d(c, m[2], pair_b, sizeof(int) * n_pairs))) return rc;
-    if ((rc = m[5].reserve(sizeof(double) * min_dist_stack_doubles(c, K, max_depth, n_pairs)))) return rc;
+    // 2-D curves arrive padded with a zero z row (bezier.py:1294-1308): then the planar gjkNew machine runs (the same bits)
+    bool planar = true;
+    for (int i = 0; i < n_curves && planar; ++i) {
+        const double* z = curves + ((size_t)i * 3 + 2) * K;
+        for (int j = 0; j < K; ++j) if (z[j] != 0.0 || std::signbit(z[j])) { planar = false; break; }      // (+0 only: a -0 would show in a returned closest point)
+    }
+    if ((rc = m[5].reserve(sizeof(double) * min_dist_stack_doubles(c, K, max_depth, n_pairs, planar)))) return rc;
     if ((rc = c->ws_out.reserve(sizeof(double) * 3 * (size_t)n_pairs))) return rc;
     if ((rc = m[3].reserve(sizeof(int) * 4 * (size_t)n_pairs))) return rc;
     // the order the worker waves take the pairs in: by the previous evaluation's node counts, longest search first, when
@@ -1238,12 +1244,6 @@ int obtg_min_dist(obtg_ctx* c, const double* curves, int n_curves, int K, const 
         std::stable_sort(qbuf.begin() + 1, qbuf.end(), [&](int a, int b) { return hn[a] > hn[b]; });
     }
     if ((rc = h2d(c, m[6], qbuf.data(), sizeof(int) * qbuf.size()))) return rc;
-    // 2-D curves arrive padded with a zero z row (bezier.py:1294-1308): then the planar gjkNew machine runs (the same bits)
-    bool planar = true;
-    for (int i = 0; i < n_curves && planar; ++i) {
-        const double* z = curves + ((size_t)i * 3 + 2) * K;
-        for (int j = 0; j < K; ++j) if (z[j] != 0.0 || std::signbit(z[j])) { planar = false; break; }      // (+0 only: a -0 would show in a returned closest point)
-    }
     rc = launch_min_dist(c, c->ws_in.as<double>(), K, m[1].as<int>(), m[2].as<int>(), n_pairs, eps, max_iter,
                          md_cap, max_depth, max_nodes, m[5].as<double>(), c->ws_out.as<double>(), m[3].as<int>(),
                          have ? m[6].as<int>() + 1 : nullptr, m[6].as<int>(), planar);

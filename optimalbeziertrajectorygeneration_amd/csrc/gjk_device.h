@@ -765,8 +765,11 @@ __device__ __forceinline__ void closest_from_simplex2(const Ctx<Mem>& g, const S
         r.c1 = V3{ a1.x, a1.y, 0.0 };
         r.c2 = V3{ a2.x, a2.y, 0.0 };
     } else {
-        r.c1 = V3{ (1 - t) * a1.x + t * o1.x, (1 - t) * a1.y + t * o1.y, 0.0 };
-        r.c2 = V3{ (1 - t) * a2.x + t * o2.x, (1 - t) * a2.y + t * o2.y, 0.0 };
+        // z: seg_result's (1 - t) * 0 + t * 0 as written -- 0 for t in [0, 1], NaN when t is NaN (an overflowing or vanishing
+        // segment), as the 3-D machine and the reference return it
+        const double z = (1 - t) * 0.0 + t * 0.0;
+        r.c1 = V3{ (1 - t) * a1.x + t * o1.x, (1 - t) * a1.y + t * o1.y, z };
+        r.c2 = V3{ (1 - t) * a2.x + t * o2.x, (1 - t) * a2.y + t * o2.y, z };
     }
 }
 

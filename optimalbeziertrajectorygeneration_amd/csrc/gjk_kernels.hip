@@ -4094,19 +4094,57 @@ static MdPlan md_plan(int K, int max_depth)
     return pl;
 }
 
-// doubles of frame stack obtg_min_dist has to provide: a stack per WORKER wave for the forms that run as workers on the queue
-// (either may be chosen at launch), a stack per pair only when neither fits and the one-lane form runs
-size_t min_dist_stack_doubles(const obtg_ctx* c, int K, int max_depth, int n_pairs)
+// The form obtg_min_dist runs for one call, with its grid, LDS and the frame stack it writes: the ONE place that decides, so that
+// min_dist_stack_doubles (the allocation) and launch_min_dist (the launch) cannot disagree.  The switches are read per call (the
+// tests flip them in-process): OBTG_MD_FORM=wave skips the quad form (the wave form where its LDS fits, else the one-lane form),
+// OBTG_MD_FORM=lane runs the one-lane form whatever fits; OBTG_MD_PLANAR=0 keeps planar curves on the 3-D machine; OBTG_MD_MANY
+// sets the pairs per worker from which a planar call counts as issue bound.
+enum MdForm { MD_QUAD_3D = 0, MD_QUAD_PLANAR_CHAIN, MD_QUAD_PLANAR_ISSUE, MD_WAVE, MD_LANE };
+struct MdLaunch {
+    MdForm form;
+    unsigned grid, block;
+    size_t lds;
+    size_t stack_doubles;          // the whole launch: a stack per worker wave (queue forms), a stack per pair (one-lane form)
+};
+static MdLaunch md_launch(const obtg_ctx* c, int K, int max_depth, int n_pairs, bool planar)
 {
     const MdPlan pl = md_plan(K, max_depth);
-    size_t need = 0;
-    if (pl.quad_ok) need = (size_t)min_dist_workers(c, n_pairs, pl.lds_q, OBTG_MD_MIN_WAVES_PLANAR) * max_depth * md_quad_frame(K);
-    if (pl.wave_ok) {
-        const size_t w = (size_t)min_dist_workers(c, n_pairs, pl.lds_w, OBTG_MD_MIN_WAVES) * max_depth * (6 * K + F_NSCAL);
-        if (w > need) need = w;
+    const char* env_form = getenv("OBTG_MD_FORM");
+    const bool want_wave = env_form && !strcmp(env_form, "wave"), want_lane = env_form && !strcmp(env_form, "lane");
+    MdLaunch L;
+    if (pl.quad_ok && !want_wave && !want_lane) {          // a 16-lane row per child: four gjkNew calls of a node's children in lockstep
+        const char* env_planar = getenv("OBTG_MD_PLANAR");
+        const bool no_planar = env_planar && env_planar[0] == '0';
+        const char* env_many = getenv("OBTG_MD_MANY");
+        const int many_env = env_many ? atoi(env_many) : 0;
+        const int w3 = min_dist_workers(c, n_pairs, pl.lds_q, OBTG_MD_MIN_WAVES_PLANAR), w2 = min_dist_workers(c, n_pairs, pl.lds_q, OBTG_MD_MIN_WAVES);
+        const bool many = (long)n_pairs >= (long)(many_env > 0 ? many_env : 8) * w3;
+        L.form = (planar && !no_planar) ? (many ? MD_QUAD_PLANAR_ISSUE : MD_QUAD_PLANAR_CHAIN) : MD_QUAD_3D;
+        L.grid = (unsigned)(L.form == MD_QUAD_PLANAR_ISSUE ? w3 : w2);
+        L.block = kWave;
+        L.lds = pl.lds_q;
+        L.stack_doubles = (size_t)L.grid * max_depth * md_quad_frame(K);
+    } else if (pl.wave_ok && !want_lane) {                 // one pair per wavefront at a time, the waves as workers on a queue
+        L.form = MD_WAVE;
+        L.grid = (unsigned)min_dist_workers(c, n_pairs, pl.lds_w, OBTG_MD_MIN_WAVES);
+        L.block = kWave;
+        L.lds = pl.lds_w;
+        L.stack_doubles = (size_t)L.grid * max_depth * (6 * K + F_NSCAL);
+    } else {                                               // one lane per pair, its frames in global memory only
+        L.form = MD_LANE;
+        L.grid = (unsigned)((n_pairs + 63) / 64);
+        L.block = 64;
+        L.lds = 0;
+        L.stack_doubles = (size_t)n_pairs * max_depth * (6 * K + F_NSCAL);
     }
-    if (!pl.quad_ok && !pl.wave_ok) need = (size_t)n_pairs * max_depth * (6 * K + F_NSCAL);
-    return need;
+    return L;
+}
+
+// doubles of frame stack obtg_min_dist has to provide for the form md_launch picks
+size_t min_dist_stack_doubles(const obtg_ctx* c, int K, int max_depth, int n_pairs, bool planar)
+{
+    if (n_pairs <= 0 || K < 2 || K > kMdMaxK || max_depth < 1) return 0;
+    return md_launch(c, K, max_depth, n_pairs, planar).stack_doubles;
 }
 
 int launch_min_dist(obtg_ctx* c, const double* d_curves, int K, const int* d_pa, const int* d_pb,
@@ -4118,20 +4156,13 @@ int launch_min_dist(obtg_ctx* c, const double* d_curves, int K, const int* d_pa,
     MdParams p{ d_curves, d_pa, d_pb, n_pairs, K, max_iter, md_cap, max_depth, max_nodes, eps, d_stack, d_res, d_info,
                 d_order, d_queue };
     ScopedKernelTimer t(c, OBTG_K_MIN_DIST);
-    const MdPlan pl = md_plan(K, max_depth);
-    const size_t lds_w = pl.lds_w, lds_q = pl.lds_q;
-    const char* env_form = getenv("OBTG_MD_FORM");          // "wave": a wavefront per gjkNew call (read per launch: the A/B test flips it)
-    const bool quad = pl.quad_ok && d_queue && !(env_form && !strcmp(env_form, "wave"));
-    if (quad) {                            // a 16-lane row per child: four gjkNew calls of a node's children in lockstep
+    const MdLaunch L = md_launch(c, K, max_depth, n_pairs, planar);
+    if (L.form != MD_LANE) {               // the queue forms: workers take the pairs from d_queue
+        if (!d_queue) return OBTG_ERR_ARG;
         OBTG_HIP(c, hipMemsetAsync(d_queue, 0, sizeof(int), c->stream));
-        // (both read per launch: the tests flip them in-process)
-        const char* env_planar = getenv("OBTG_MD_PLANAR");                       // "0": the 3-D machine on planar curves too (A/B runs)
-        const bool no_planar = env_planar && env_planar[0] == '0';
-        const char* env_many = getenv("OBTG_MD_MANY");                           // pairs per worker from which a call counts as issue bound
-        const int many_env = env_many ? atoi(env_many) : 0;
-        const int w3 = min_dist_workers(c, n_pairs, lds_q, OBTG_MD_MIN_WAVES_PLANAR), w2 = min_dist_workers(c, n_pairs, lds_q, OBTG_MD_MIN_WAVES);
-        const bool many = (long)n_pairs >= (long)(many_env > 0 ? many_env : 8) * w3;
-        const int form = (planar && !no_planar) ? (many ? 2 : 1) : 0;      // 0: the 3-D machine, 1: planar, chain bound, 2: planar, issue bound
+    }
+    if (L.form <= MD_QUAD_PLANAR_ISSUE) {
+        const int form = (int)L.form;      // 0: the 3-D machine, 1: planar, chain bound, 2: planar, issue bound
         void (*kern)(const MdParams) = form == 2 ? k_min_dist_quad<true, OBTG_MD_MIN_WAVES_PLANAR, 0>
                                                  : (form == 1 ? k_min_dist_quad<true, OBTG_MD_MIN_WAVES, 0> : k_min_dist_quad<false, OBTG_MD_MIN_WAVES, 0>);
         switch (K) {        // the counts with a build of their own
@@ -4144,12 +4175,11 @@ int launch_min_dist(obtg_ctx* c, const double* d_curves, int K, const int* d_pa,
 #undef OBTG_CASE
             default: break;
         }
-        hipLaunchKernelGGL(kern, dim3((unsigned)(form == 2 ? w3 : w2)), dim3(kWave), lds_q, c->stream, p);
-    } else if (pl.wave_ok && d_queue) {    // one pair per wavefront at a time, the waves as workers on a queue
-        OBTG_HIP(c, hipMemsetAsync(d_queue, 0, sizeof(int), c->stream));
-        hipLaunchKernelGGL(k_min_dist_wave, dim3((unsigned)min_dist_workers(c, n_pairs, lds_w, OBTG_MD_MIN_WAVES)), dim3(kWave), lds_w, c->stream, p);
-    } else
-        hipLaunchKernelGGL(k_min_dist, dim3((n_pairs + 63) / 64), dim3(64), 0, c->stream, p);
+        hipLaunchKernelGGL(kern, dim3(L.grid), dim3(L.block), L.lds, c->stream, p);
+    } else if (L.form == MD_WAVE)
+        hipLaunchKernelGGL(k_min_dist_wave, dim3(L.grid), dim3(L.block), L.lds, c->stream, p);
+    else
+        hipLaunchKernelGGL(k_min_dist, dim3(L.grid), dim3(L.block), 0, c->stream, p);
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;
 }
@@ -4456,6 +4486,10 @@ int launch_min_dist_robust(obtg_ctx* c, const double* d_curves, int K, const int
             default: break;
         }
     }
+    // any-count form: a node's 3 K-row sub-curves per lane in LDS, past the default 48 KB from K = 32 (51 200 B)
+    if (lds > 64 * 1024) return OBTG_ERR_UNSUPPORTED;
+    if (lds > 48 * 1024)
+        OBTG_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     ScopedKernelTimer t(c, OBTG_K_MIN_DIST);
     hipLaunchKernelGGL(kern, dim3((unsigned)n_pairs), dim3(kWave), lds, c->stream, p);
     OBTG_HIP(c, hipGetLastError());
@@ -4514,10 +4548,13 @@ int launch_min_dist2poly(obtg_ctx* c, const double* d_curves, int K, const doubl
     const size_t lds_w = sizeof(double) * ((size_t)6 * K + 8 * kMdMaxK + (size_t)max_depth * G_NSCAL);
     const size_t lds_q = sizeof(double) * ((size_t)2 * md2_quad_blob(K) + 48 + 8 * kMdShRow + 64 +
                                            (size_t)(max_depth < kMdScsLds ? max_depth : kMdScsLds) * G_NSCAL);
-    const char* env_form = getenv("OBTG_MD_FORM");          // "wave": a wavefront per gjkNew call (read per launch: the A/B test flips it)
+    // (read per launch: the tests flip them) "wave": no quad form -- the wave form where it fits; "lane": the one-lane form.  Every
+    // form fits the stack obtg_min_dist2poly provides: min_dist2poly_stack_doubles per pair, the larger of the frame forms.
+    const char* env_form = getenv("OBTG_MD_FORM");
+    const bool want_wave = env_form && !strcmp(env_form, "wave"), want_lane = env_form && !strcmp(env_form, "lane");
     const char* env_planar = getenv("OBTG_MD_PLANAR");                           // (A/B runs and tests; read per launch)
     const bool no_planar = env_planar && env_planar[0] == '0';
-    if (K <= kMdQuadMaxK && max_poly_K <= 16 && lds_q <= 48 * 1024 && !(env_form && !strcmp(env_form, "wave"))) {
+    if (K <= kMdQuadMaxK && max_poly_K <= 16 && lds_q <= 48 * 1024 && !want_wave && !want_lane) {
         // both children side by side
         const bool pl2 = planar && !no_planar;
         void (*kern)(const Md2Params) = pl2 ? k_min_dist2poly_quad<true, 0> : k_min_dist2poly_quad<false, 0>;
@@ -4529,7 +4566,7 @@ int launch_min_dist2poly(obtg_ctx* c, const double* d_curves, int K, const doubl
         }
         hipLaunchKernelGGL(kern, dim3((unsigned)n_pairs), dim3(kWave), lds_q, c->stream, p);
     }
-    else if (lds_w <= 48 * 1024 && max_poly_K <= kMdMaxK)      // one pair per wavefront
+    else if (lds_w <= 48 * 1024 && max_poly_K <= kMdMaxK && !want_lane)      // one pair per wavefront
         hipLaunchKernelGGL(k_min_dist2poly_wave, dim3((unsigned)n_pairs), dim3(kWave), lds_w, c->stream, p);
     else
         hipLaunchKernelGGL(k_min_dist2poly, dim3((n_pairs + 63) / 64), dim3(64), 0, c->stream, p);

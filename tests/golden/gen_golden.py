@@ -584,6 +584,72 @@ def gen_mindist_script():
     save("mindist_script.npz", **d)
 
 
+def _wide_poly(kv, planar, rng):
+    """kv vertices on a small ellipse somewhere in the swarm's square, jittered; planar (z = 0) or a point set in space."""
+    ang = np.sort(rng.uniform(0, 2 * np.pi, kv))
+    c = rng.uniform(10, 90, 2)
+    P = np.zeros((kv, 3))
+    P[:, 0] = c[0] + 6 * np.cos(ang) + rng.normal(0, 0.3, kv)
+    P[:, 1] = c[1] + 4 * np.sin(ang) + rng.normal(0, 0.3, kv)
+    if not planar:
+        P[:, 2] = rng.uniform(0, 30, kv)
+    return P
+
+
+def gen_mindist_wide():
+    """`_minDist` and `_minDist2Poly` at the shapes the device runs in its wave and one-lane forms: curves of 17..32 control points
+    (kMdMaxK = 32) and polygons of 20..64 vertices.  Per group `<g>_`: curves[n][3][K] (2-D ones with a zero z row), the pair
+    list, and the reference's status, result, gjkNew-call count (and closest point).  Mostly separated swarm curves -- the
+    reference takes seconds on crossing K = 32 pairs -- plus a few crossing pairs drawn in a small box, whose status (a timeout
+    among them) is recorded as it is."""
+    d = {}
+    sys.setrecursionlimit(1000)
+    md_groups, p_groups = [], []
+    for K in (17, 21, 25, 32):
+        for dim in (2, 3):
+            g = "md_K%d_d%d" % (K, dim)
+            nsw = 6
+            Y = synth.swarm_control_points(nsw, dim, K - 1, seed=100 * K + dim)
+            rng = np.random.default_rng(200 * K + dim)
+            box = rng.uniform(0, 10, size=(2 * dim, K))          # two curves in a small box: they cross
+            curves = np.zeros((nsw + 2, 3, K))
+            curves[:nsw, :dim, :] = Y.reshape(nsw, dim, K)
+            curves[nsw:, :dim, :] = box.reshape(2, dim, K)
+            pa, pb = synth.all_pairs(nsw)
+            sel = np.arange(0, len(pa), 2)                       # 8 of the 15 swarm pairs
+            pairs = [(int(pa[k]), int(pb[k])) for k in sel] + [(nsw, nsw + 1), (0, nsw)]
+            res, stat, calls = [], [], []
+            for (i, j) in pairs:
+                st, v, nc = run_mindist(bez.Bezier(curves[i, :dim].copy()), bez.Bezier(curves[j, :dim].copy()), budget=5.0)
+                res.append(v); stat.append(st); calls.append(nc)
+            d[g + "_curves"], d[g + "_pairs"] = curves, np.array(pairs, np.int32)
+            d[g + "_res"], d[g + "_status"], d[g + "_calls"] = np.array(res), np.array(stat, np.int32), np.array(calls, np.int32)
+            md_groups.append(g)
+            print("  %s: status %s, calls max %d" % (g, np.bincount(stat, minlength=3), max(calls)))
+    for K in (11, 21, 32):
+        for dim in (2, 3):
+            g = "p_K%d_d%d" % (K, dim)
+            nc_ = 3
+            Y = synth.swarm_control_points(nc_, dim, K - 1, seed=300 * K + dim)
+            curves = np.zeros((nc_, 3, K))
+            curves[:, :dim, :] = Y.reshape(nc_, dim, K)
+            rng = np.random.default_rng(400 * K + dim)
+            polys = [_wide_poly(kv, dim == 2, rng) for kv in (20, 32, 40, 64)]
+            pts, off = synth.pack_polys(polys)
+            pairs = [(i, q) for i in range(nc_) for q in range(len(polys))]
+            res, pt, stat, calls = [], [], [], []
+            for (i, q) in pairs:
+                st, v, p, nc = run_mindist2poly(bez.Bezier(curves[i, :dim].copy()), polys[q].copy(), budget=5.0)
+                res.append(v); pt.append(p); stat.append(st); calls.append(nc)
+            d[g + "_curves"], d[g + "_pts"], d[g + "_off"], d[g + "_pairs"] = curves, pts, off, np.array(pairs, np.int32)
+            d[g + "_res"], d[g + "_pt"] = np.array(res), np.array(pt)
+            d[g + "_status"], d[g + "_calls"] = np.array(stat, np.int32), np.array(calls, np.int32)
+            p_groups.append(g)
+            print("  %s: status %s, calls max %d" % (g, np.bincount(stat, minlength=3), max(calls)))
+    d["md_groups"], d["p_groups"] = np.array(md_groups), np.array(p_groups)
+    save("mindist_wide.npz", **d)
+
+
 # ========================================================================= C5
 def gen_c5():
     """BASELINE config 5 (ComplexObstacles.py-style): 64 vehicles + 32 curve obstacles, degree 10.

@@ -3,6 +3,8 @@ reference-generated golden fixtures.  Needs a real MI355X: `pytest -m gpu`.
 
 Bars (BASELINE.json north_star): float64 constraint values within 1e-9 relative
 (scale-aware, tests/util.py); GJK flags and support-index sequences BIT-EXACT."""
+import itertools
+
 import numpy as np
 import pytest
 
@@ -845,8 +847,8 @@ def test_min_dist_robust_register_form_is_the_lds_form(capi, synth, monkeypatch)
 def test_min_dist_quad_form_is_the_wave_form(capi, synth, monkeypatch):
     """obtg_min_dist, round 5: up to 16 control points a node's four children are evaluated together, a 16-lane row of the
     wavefront each, the four gjkNew state machines in lockstep (k_min_dist_quad); OBTG_MD_FORM=wave selects the form that
-    spends the wavefront on one call at a time (k_min_dist_wave, which also serves 17..32 points).  The walk is the same
-    walk: results, node counts, call counts, depths and statuses identical -- on the C5-sized pair list, on curves of
+    spends the wavefront on one call at a time (k_min_dist_wave, which also serves 17..32 points), OBTG_MD_FORM=lane the one
+    with a lane per pair and its frames in global memory (k_min_dist).  The walk is the same walk: results, node counts, call counts, depths and statuses identical -- on the C5-sized pair list, on curves of
     degree 1..15 in 2-D and 3-D, with a node budget that ends searches early, with a depth cap, and with a one-node budget."""
     cases = [(96, 2, 10, 1234), (30, 3, 3, 2), (20, 3, 5, 3), (14, 3, 8, 4), (12, 2, 12, 5), (10, 3, 15, 6), (24, 2, 7, 7),
              # control-point counts without an unrolled form (2, 3, 5, 7, 14, 15): the any-count splits and split parameters
@@ -866,9 +868,12 @@ def test_min_dist_quad_form_is_the_wave_form(capi, synth, monkeypatch):
             quad = ctx.min_dist(curves, pa, pb, **kw)
             monkeypatch.setenv("OBTG_MD_FORM", "wave")
             wave = ctx.min_dist(curves, pa, pb, **kw)
+            monkeypatch.setenv("OBTG_MD_FORM", "lane")
+            lane = ctx.min_dist(curves, pa, pb, **kw)
             monkeypatch.delenv("OBTG_MD_FORM")
             for key in ("res", "nodes", "gjk_calls", "depth", "status"):
                 assert np.array_equal(quad[key], wave[key], equal_nan=True), (n, kw, key)
+                assert np.array_equal(quad[key], lane[key], equal_nan=True), (n, kw, key, "one lane per pair")
 
 
 def test_min_dist_planar_builds_are_the_3d_machine(capi, synth, monkeypatch):
@@ -934,7 +939,8 @@ def test_min_dist_split_parameter_quotients_at_extreme_scales(capi, oracle, synt
     or vanish (NaN directions, NaN support values: `cur > maxd` semantics of the row reductions).  (Scaling by a power of two is
     exact, so at 2^+-100 t1 / t2 are those of the unscaled search.)"""
     ctx = capi.scratch_context()
-    for (ncurves, n, seed) in ((10, 10, 3), (8, 5, 4), (8, 15, 5)):
+    # (21 and 31 control points: the wave form, 8 * (12 K + 192 + 480) <= 8 352 B of LDS at max_depth 48)
+    for (ncurves, n, seed) in ((10, 10, 3), (8, 5, 4), (8, 15, 5), (6, 20, 9), (5, 30, 11)):
         Yc = synth.swarm_control_points(ncurves, 2, n, seed=seed)
         base = np.zeros((ncurves, 3, n + 1))
         base[:, :2, :] = Yc.reshape(ncurves, 2, n + 1)
@@ -959,7 +965,8 @@ def test_min_dist_split_parameter_quotients_at_extreme_scales(capi, oracle, synt
 
 def test_min_dist2poly_quad_form_is_the_wave_form(capi, synth, monkeypatch):
     """obtg_min_dist2poly, round 5: with at most 16 control points and polygons of at most 16 vertices a node's two children are
-    evaluated together, a 16-lane row each (k_min_dist2poly_quad); OBTG_MD_FORM=wave selects the wavefront-per-call form.  The
+    evaluated together, a 16-lane row each (k_min_dist2poly_quad); OBTG_MD_FORM=wave selects the wavefront-per-call form,
+    OBTG_MD_FORM=lane the lane-per-pair form (k_min_dist2poly).  The
     same walk: (alpha, t1, closest point), node counts, gjkNew-call counts, depths and statuses identical -- 2-D and 3-D curves of
     degree 1..15 against polygons of 3..16 vertices (planar ones, and point sets in space), under node, depth and gjkNew limits."""
     rng = np.random.default_rng(77)
@@ -986,9 +993,12 @@ def test_min_dist2poly_quad_form_is_the_wave_form(capi, synth, monkeypatch):
             quad = ctx.min_dist2poly(curves, ppts, poff, pc, pp, **kw)
             monkeypatch.setenv("OBTG_MD_FORM", "wave")
             wave = ctx.min_dist2poly(curves, ppts, poff, pc, pp, **kw)
+            monkeypatch.setenv("OBTG_MD_FORM", "lane")
+            lane = ctx.min_dist2poly(curves, ppts, poff, pc, pp, **kw)
             monkeypatch.delenv("OBTG_MD_FORM")
             for key in ("res", "nodes", "gjk_calls", "depth", "status"):
                 assert np.array_equal(quad[key], wave[key], equal_nan=True), (n, dim, kw, key)
+                assert np.array_equal(quad[key], lane[key], equal_nan=True), (n, dim, kw, key, "one lane per pair")
 
 
 def test_min_dist2poly_random_sets_identical_to_the_oracle(capi, oracle, synth):
@@ -1059,6 +1069,335 @@ def test_min_dist_random_sets_identical_to_the_oracle(capi, oracle, synth):
                 assert_identical(q["res"][k], o["res"], "set %d pair %d (dim %d, degree %d)" % (s, k, dim, n))
         n_pairs += len(pa)
     assert n_pairs > 9000
+
+
+# --------------------------------------------- _minDist / _minDist2Poly at 17..32 control points and 17..64 vertices
+# Which kernel a call runs is fixed by the LDS the walk asks for (launch_min_dist / launch_min_dist2poly): the wave forms hold
+# a frame's scalars for EVERY level in LDS, and the launch takes them only within the default 48 KB; past that, and for
+# polygons of more than 32 vertices, one lane per pair walks with its frames in global memory.  The tests below state the
+# arithmetic, so that the depths they use are seen to reach the kernel they are meant for.
+_LDS = 48 * 1024
+
+
+def _md_wave_lds(K, max_depth):             # k_min_dist_wave: [12 K] curves + [6 * 32] scratch + [max_depth][10] frame scalars
+    return 8 * (12 * K + 6 * 32 + 10 * max_depth)
+
+
+def _md2_wave_lds(K, max_depth):            # k_min_dist2poly_wave: [6 K] + [8 * 32] polygon and scratch + [max_depth][9]
+    return 8 * (6 * K + 8 * 32 + 9 * max_depth)
+
+
+def _md_form(K, max_depth):
+    return "quad" if K <= 16 else ("wave" if _md_wave_lds(K, max_depth) <= _LDS else "lane")
+
+
+def _md2_form(K, max_depth, poly_K):
+    if K <= 16 and poly_K <= 16:
+        return "quad"
+    return "wave" if _md2_wave_lds(K, max_depth) <= _LDS and poly_K <= 32 else "lane"
+
+
+# gjkNew's own limits, node budgets, a depth cap and a coarse eps (the limits of the quad-vs-wave tests)
+_MD_LIMITS = (dict(max_nodes=1), dict(max_nodes=37), dict(max_nodes=400), dict(max_nodes=1500),
+              dict(max_nodes=300, max_iter=1), dict(max_nodes=300, max_iter=3, md_cap=1), dict(max_nodes=300, md_cap=2),
+              dict(max_nodes=500, eps=1e-3))
+
+
+def _assert_md_same(got, o, k, what):
+    assert got["status"][k] == o["status"], what
+    if o["status"] == 0:
+        assert got["nodes"][k] == o["nodes"] and got["gjk_calls"][k] == o["gjk_calls"] and got["depth"][k] == o["depth"], what
+        assert_identical(got["res"][k], o["res"], what)
+
+
+def test_min_dist_wide_fixtures(capi, oracle, synth, golden_dir):
+    """mindist_wide.npz (the reference run on curves of 17, 21, 25 and 32 control points, and on polygons of 20..64 vertices)
+    through every form the device has for those shapes.  The wave forms at max_depth 400: a K = 32 `_minDist` walk asks
+    8 * (12 * 32 + 192 + 10 * 400) = 36 608 B of LDS, a K = 32 `_minDist2Poly` walk 8 * (6 * 32 + 256 + 9 * 400) = 32 384 B --
+    the latter only while the call's LARGEST polygon has at most 32 vertices (launch_min_dist2poly decides per call), so the
+    polygons of 20 and 32 vertices go in a call of their own and those of 40 and 64 in another (the one-lane form).  The
+    one-lane forms at max_depth 900, the reference's own recursion limit less the oracle's margin (76 608 B for `_minDist` at
+    K = 32).  Where the reference returned, status OK, gjkNew-call count, result and closest point identical to its; everywhere,
+    status and -- where the search ends -- node, call and depth counts and results identical to the oracle's at the same
+    limits."""
+    m = _load(golden_dir, "mindist_wide.npz")
+    ctx = capi.scratch_context()
+    n_ref = 0
+    n_form = {}
+    for depth in (400, 900):
+        for g in m["md_groups"]:
+            cur, pr = m[g + "_curves"], m[g + "_pairs"]
+            K = cur.shape[2]
+            form = _md_form(K, depth)
+            assert form == ("wave" if depth == 400 else "lane"), (g, depth)
+            r = ctx.min_dist(cur, pr[:, 0], pr[:, 1], max_depth=depth, max_nodes=300000)
+            for k, (i, j) in enumerate(pr):
+                o = oracle.min_dist(cur[i], cur[j], max_depth=depth, max_nodes=300000)
+                _assert_md_same(r, o, k, (g, depth, k))
+                n_form["md_" + form] = n_form.get("md_" + form, 0) + 1
+                if m[g + "_status"][k] == 0 and depth == 900:
+                    assert r["status"][k] == capi.MD_OK and r["gjk_calls"][k] == m[g + "_calls"][k], (g, k)
+                    assert_identical(r["res"][k], m[g + "_res"][k], "%s pair %d vs the reference" % (g, k))
+                    n_ref += 1
+        for g in m["p_groups"]:
+            cur, pts, off, pr = m[g + "_curves"], m[g + "_pts"], m[g + "_off"], m[g + "_pairs"]
+            K = cur.shape[2]
+            sizes = np.diff(off)
+            for small in (True, False):                    # one call per polygon class: the form follows the largest polygon
+                qs = [q for q in range(len(sizes)) if (sizes[q] <= 32) == small]
+                sub_pts, sub_off = synth.pack_polys([pts[off[q]:off[q + 1]] for q in qs])
+                sel = [k for k in range(len(pr)) if pr[k, 1] in qs]
+                pc = pr[sel, 0].astype(np.int32)
+                pp = np.array([qs.index(q) for q in pr[sel, 1]], np.int32)
+                form = _md2_form(K, depth, int(sizes[qs].max()))
+                assert form == ("wave" if depth == 400 and small else "lane"), (g, depth, small)
+                r = ctx.min_dist2poly(cur, sub_pts, sub_off, pc, pp, max_depth=depth, max_nodes=300000)
+                for kk, k in enumerate(sel):
+                    i, q = pr[k]
+                    o = oracle.min_dist2poly(cur[i], pts[off[q]:off[q + 1]], max_depth=depth, max_nodes=300000)
+                    _assert_md_same(r, o, kk, (g, depth, k))
+                    n_form["p_" + form] = n_form.get("p_" + form, 0) + 1
+                    if m[g + "_status"][k] == 0 and depth == 900:
+                        assert r["status"][kk] == capi.MD_OK and r["gjk_calls"][kk] == m[g + "_calls"][k], (g, k)
+                        assert_identical(r["res"][kk][:2], m[g + "_res"][k], "%s pair %d vs the reference" % (g, k))
+                        assert_identical(r["res"][kk][2:], m[g + "_pt"][k], "%s pair %d point vs the reference" % (g, k))
+                        n_ref += 1
+    assert n_ref == int(sum((m[g + "_status"] == 0).sum() for g in list(m["md_groups"]) + list(m["p_groups"])))
+    assert n_form["md_wave"] == n_form["md_lane"] == 80 and n_form["p_wave"] == 36 and n_form["p_lane"] == 108, n_form
+
+
+def _wide_curves(rng, synth, nc, dim, K, box, seed):
+    curves = np.zeros((nc, 3, K))
+    if box:                                                # drawn in a small box: many pairs cross
+        curves[:, :dim, :] = rng.uniform(0, 10, size=(nc, dim, K))
+    else:
+        curves[:, :dim, :] = synth.swarm_control_points(nc, dim, K - 1, seed=seed).reshape(nc, dim, K)
+    return curves
+
+
+def test_min_dist_wide_campaign_wave_and_lane_forms(capi, oracle, synth, monkeypatch):
+    """`_minDist` on random curve sets of 17..32 control points, 2-D and 3-D (swarm curves, and curves in a small box that cross),
+    at max_depth 64 -- the wave form, 8 * (12 K + 192 + 640) <= 11 264 B -- and at max_depth 900 -- the one-lane form, past 48 KB
+    from K = 1 on (73 536 B + 96 K) -- under node budgets 1 / 37 / 400 / 1500, gjkNew's limits (max_iter 1 and 3, md_cap 1 and
+    2), eps 1e-3, and a depth cap of 7 in both forms (the one-lane one forced with OBTG_MD_FORM=lane).  Status, and where the
+    search ends node, gjkNew-call and depth counts and (d, t1, t2), identical to the oracle's."""
+    ctx = capi.scratch_context()
+    rng = np.random.default_rng(1717)
+    n_cmp = {"wave": 0, "lane": 0}
+    for s in range(12):
+        dim = 2 + (s & 1)
+        K = [17, 32, 21, 32, 25, 19, 29, 32, 18, 23, 31, 32][s]
+        nc = 6
+        curves = _wide_curves(rng, synth, nc, dim, K, s % 4 == 3, 5000 + s)
+        pa, pb = synth.all_pairs(nc)
+        runs = [(dict(max_depth=64, **kw), None) for kw in _MD_LIMITS] + [(dict(max_depth=900, **kw), None) for kw in _MD_LIMITS]
+        runs += [(dict(max_depth=7, max_nodes=2000), None), (dict(max_depth=7, max_nodes=2000), "lane")]
+        for kw, force in runs:
+            form = force or _md_form(K, kw["max_depth"])
+            assert form == ("wave" if kw["max_depth"] < 900 and not force else "lane"), (K, kw)
+            if force:
+                monkeypatch.setenv("OBTG_MD_FORM", force)
+            got = ctx.min_dist(curves, pa, pb, **kw)
+            if force:
+                monkeypatch.delenv("OBTG_MD_FORM")
+            o = oracle.min_dist_pairs(curves, pa, pb, nthreads=4, **kw)
+            assert np.array_equal(got["status"], o["status"]), (s, K, dim, kw, force)
+            ended = o["status"] == 0
+            for key in ("nodes", "gjk_calls", "depth"):
+                assert np.array_equal(np.asarray(got[key])[ended], np.asarray(o[key])[ended]), (s, K, dim, kw, force, key)
+            assert np.array_equal(got["res"][ended], o["res"][ended]), (s, K, dim, kw, force)
+            n_cmp[form] += int(ended.sum())
+    assert n_cmp["wave"] > 250 and n_cmp["lane"] > 250, n_cmp
+
+
+def test_min_dist2poly_wide_campaign_wave_and_lane_forms(capi, oracle, synth, monkeypatch):
+    """`_minDist2Poly` beyond the quad form: curves of 17..32 control points against polygons of up to 16 vertices and against
+    polygons of 17..32 vertices, curves of up to 16 points against polygons of 17..32 vertices (all the wave form at max_depth 64,
+    8 * (6 K + 256 + 576) <= 8 192 B, chosen per call by the largest polygon in it), and
+    polygons of 33..64 vertices (the one-lane form at any depth); at max_depth 900 every one of them walks in the one-lane form
+    (8 * (6 K + 256 + 8100) > 48 KB).  2-D curves against planar polygons, 3-D curves against point sets in space; under the limits
+    of the `_minDist` campaign.  Status, and where the search ends node, call and depth counts, (alpha, t1) and the closest
+    point, identical to the oracle's."""
+    ctx = capi.scratch_context()
+    rng = np.random.default_rng(2323)
+    n_cmp = {"wave": 0, "lane": 0}
+    # (K, vertex counts of the polygons)
+    shapes = [(21, (5, 12, 16)), (32, (4, 16)), (11, (17, 24, 32)), (6, (20, 31)), (16, (33, 48, 64)), (27, (40, 64)),
+              (32, (32, 64)), (9, (64,)), (24, (20, 32)), (19, (17, 28)), (32, (6, 25, 32)), (17, (17,))]
+    for s, (K, kvs) in enumerate(shapes):
+        dim = 2 + (s & 1)
+        nc = 3
+        curves = _wide_curves(rng, synth, nc, dim, K, s % 4 == 2, 6000 + s)
+        polys = []
+        for kv in kvs:
+            ang = np.sort(rng.uniform(0, 2 * np.pi, kv))
+            c = rng.uniform(15, 85, 2)
+            P = np.zeros((kv, 3))
+            P[:, 0] = c[0] + 8 * np.cos(ang); P[:, 1] = c[1] + 5 * np.sin(ang)
+            if dim == 3:
+                P[:, 2] = rng.uniform(0, 40, kv)
+            polys.append(P)
+        ppts, poff = synth.pack_polys(polys)
+        pc = np.repeat(np.arange(nc), len(polys)).astype(np.int32)
+        pp = np.tile(np.arange(len(polys)), nc).astype(np.int32)
+        max_pk = max(kvs)
+        runs = [dict(max_depth=64, **kw) for kw in _MD_LIMITS] + [dict(max_depth=900, **kw) for kw in _MD_LIMITS]
+        runs += [dict(max_depth=7, max_nodes=2000)]
+        for kw in runs:
+            form = _md2_form(K, kw["max_depth"], max_pk)
+            assert form == ("lane" if kw["max_depth"] == 900 or max_pk > 32 else "wave"), (K, max_pk, kw)
+            got = ctx.min_dist2poly(curves, ppts, poff, pc, pp, **kw)
+            for k in range(len(pc)):
+                o = oracle.min_dist2poly(curves[pc[k]], polys[pp[k]], **kw)
+                _assert_md_same(got, o, k, (s, K, dim, kvs, kw, k))
+                n_cmp[form] += o["status"] == 0
+    assert n_cmp["wave"] > 250 and n_cmp["lane"] > 300, n_cmp
+
+
+def test_min_dist2poly_closest_points_at_extreme_scales(capi, oracle, synth, monkeypatch):
+    """`_minDist2Poly` on 2-D curves and planar polygons scaled by powers of two far outside and just inside [2^-300, 2^300]
+    (the exponents of test_min_dist_split_parameter_quotients_at_extreme_scales): the planar quad build, the same call on the 3-D
+    machine (OBTG_MD_PLANAR=0) and the oracle agree on status, and where the search ends on node, call and depth counts, (alpha,
+    t1) and the closest point's bits -- its z included: the planar closest point forms z as the 3-D machine does,
+    (1 - t) * 0 + t * 0, which is NaN when the segment parameter t is (overflowing or vanishing products).  No input here
+    reaches a NaN t in a search that ends (status OK): a NaN t makes the node's distance NaN, and such a node is never pruned.
+    Searches cut by the depth cap (max_depth 48, and 1: the cap at the first children) do return NaN points -- at 2^294 and
+    beyond, (NaN, NaN, NaN) in the oracle -- and the planar-vs-3-D comparison covers them (every pair's result, whatever the
+    status); on these inputs, though, the planar build reaches them through paths other than the segment formula --
+    test_min_dist2poly_planar_closest_point_z_when_t_is_nan takes the scales at which it does."""
+    ctx = capi.scratch_context()
+    for (nc, n, seed) in ((6, 10, 3), (6, 5, 4), (5, 15, 5)):
+        Yc = synth.swarm_control_points(nc, 2, n, seed=seed)
+        base = np.zeros((nc, 3, n + 1))
+        base[:, :2, :] = Yc.reshape(nc, 2, n + 1)
+        polys0 = synth.polygon_obstacles(4, seed=seed)
+        pc = np.repeat(np.arange(nc), len(polys0)).astype(np.int32)
+        pp = np.tile(np.arange(len(polys0)), nc).astype(np.int32)
+        for e, kw in itertools.product((0, -100, 100, -290, 290, -310, 310, -400, 400, -306, 294),
+                                       (dict(max_depth=48, max_nodes=600), dict(max_depth=1, max_nodes=600))):
+            curves = np.ldexp(base, e)
+            polys = [np.ldexp(P, e) for P in polys0]
+            ppts, poff = synth.pack_polys(polys)
+            assert _md2_form(n + 1, kw["max_depth"], max(len(P) for P in polys)) == "quad"
+            plan = ctx.min_dist2poly(curves, ppts, poff, pc, pp, **kw)
+            monkeypatch.setenv("OBTG_MD_PLANAR", "0")
+            space = ctx.min_dist2poly(curves, ppts, poff, pc, pp, **kw)
+            monkeypatch.delenv("OBTG_MD_PLANAR")
+            for key in ("res", "nodes", "gjk_calls", "depth", "status"):
+                assert np.array_equal(plan[key], space[key], equal_nan=True), (n, e, key)
+            for k in range(len(pc)):
+                o = oracle.min_dist2poly(curves[pc[k]], polys[pp[k]], **kw)
+                _assert_md_same(plan, o, k, (n, e, k))
+
+
+def test_min_dist2poly_planar_closest_point_z_when_t_is_nan(capi, oracle, synth, monkeypatch):
+    """The planar quad build's closest point when gjkNew's segment parameter t is NaN: 2-D curves and planar polygons scaled by
+    2^-600 .. 2^-1000 (every square and product of the segment formula underflows: t = -0 / 0) and by 2^480 .. 2^900 (they
+    overflow: t = -inf / inf).  Such a node's distance is NaN too, so it is never pruned; the searches end at the depth cap
+    (max_depth 48, and 1: the cap at the first children), which returns the last node's point.  closest_from_simplex2 forms z
+    as seg_result does, (1 - t) * 0 + t * 0 -- NaN here -- so the planar build and the 3-D machine (OBTG_MD_PLANAR=0) return the
+    same bits for every pair, whatever its status; statuses as the oracle's.  Some of those points must have a NaN z."""
+    ctx = capi.scratch_context()
+    n_nan_z = 0
+    for (nc, n, seed) in ((6, 10, 3), (6, 5, 4), (5, 15, 5)):
+        Yc = synth.swarm_control_points(nc, 2, n, seed=seed)
+        base = np.zeros((nc, 3, n + 1))
+        base[:, :2, :] = Yc.reshape(nc, 2, n + 1)
+        polys0 = synth.polygon_obstacles(4, seed=seed)
+        pc = np.repeat(np.arange(nc), len(polys0)).astype(np.int32)
+        pp = np.tile(np.arange(len(polys0)), nc).astype(np.int32)
+        for e, kw in itertools.product((-600, -800, -1000, 480, 600, 900),
+                                       (dict(max_depth=48, max_nodes=600), dict(max_depth=1, max_nodes=600))):
+            curves = np.ldexp(base, e)
+            polys = [np.ldexp(P, e) for P in polys0]
+            ppts, poff = synth.pack_polys(polys)
+            assert _md2_form(n + 1, kw["max_depth"], max(len(P) for P in polys)) == "quad"
+            plan = ctx.min_dist2poly(curves, ppts, poff, pc, pp, **kw)
+            monkeypatch.setenv("OBTG_MD_PLANAR", "0")
+            space = ctx.min_dist2poly(curves, ppts, poff, pc, pp, **kw)
+            monkeypatch.delenv("OBTG_MD_PLANAR")
+            for key in ("res", "nodes", "gjk_calls", "depth", "status"):
+                assert np.array_equal(plan[key], space[key], equal_nan=True), (n, e, kw, key)
+            for k in range(len(pc)):
+                o = oracle.min_dist2poly(curves[pc[k]], polys[pp[k]], **kw)
+                _assert_md_same(plan, o, k, (n, e, kw, k))
+            n_nan_z += int(np.isnan(space["res"][:, 4]).sum())
+    assert n_nan_z > 0
+
+
+def _bez_basis(n, ts):
+    from scipy.special import comb
+    k = np.arange(n + 1)
+    return comb(n, k)[None, :] * ts[:, None] ** k[None, :] * (1 - ts[:, None]) ** (n - k[None, :])
+
+
+@pytest.mark.parametrize("K", [17, 24, 32])
+def test_min_dist_robust_wide_finds_the_true_minimum(capi, synth, K):
+    """obtg_min_dist_robust at 17..32 control points -- only the any-count kernel k_min_dist_robust<0> serves them, whose LDS
+    (8 * (6 K + 64 * (3 K | 1)) B: 51 200 at K = 32) passes the default 48 KB -- against dense sampling of both curves and a
+    bounded local minimisation (the ground truth of test_min_dist_robust_finds_the_true_minimum), in 3-D."""
+    from scipy.optimize import minimize
+    N, n = 8, K - 1
+    Y = synth.swarm_control_points(N, 2, n, seed=K)
+    curves = np.zeros((N, 3, K))
+    curves[:, :2, :] = Y.reshape(N, 2, K)
+    curves[:, 2, :] = np.random.default_rng(K).normal(0, 3.0, size=(N, K))
+    pa, pb = np.triu_indices(N, 1)
+    ctx = capi.scratch_context()
+    r = ctx.min_dist_robust(curves, pa, pb, eps=1e-9, max_nodes=400000)
+    assert (r["status"] == capi.MD_OK).all(), np.bincount(r["status"])
+    ts = np.linspace(0, 1, 201)
+    samples = curves @ _bez_basis(n, ts).T                                        # [N][3][201]
+    point = lambda c, t: c @ _bez_basis(n, np.array([t]))[0]                      # noqa: E731
+    for q in range(0, len(pa), 2):
+        a, b = curves[pa[q]], curves[pb[q]]
+        D = np.linalg.norm(samples[pa[q]][:, :, None] - samples[pb[q]][:, None, :], axis=0)
+        i, j = np.unravel_index(np.argmin(D), D.shape)
+        f = lambda x: np.linalg.norm(point(a, x[0]) - point(b, x[1]))             # noqa: E731
+        best = min((minimize(f, [ts[i], ts[j]], bounds=[(0, 1), (0, 1)], method="L-BFGS-B", tol=1e-14).fun, D[i, j]))
+        got, t1, t2 = r["res"][q]
+        assert got <= best * (1 + 1e-7) + 1e-9, (K, q, got, best)
+        assert got >= best * (1 - 1e-5) - 1e-9, (K, q, got, best)
+        assert abs(f([t1, t2]) - got) <= 1e-9 * max(1.0, got)
+
+
+@pytest.mark.parametrize("K", [17, 24, 32])
+def test_min_dist2poly_robust_wide_finds_the_true_minimum(capi, synth, host_gjk, K):
+    """obtg_min_dist2poly_robust at 17..32 control points against polygons of 6, 20 and 40 vertices (LDS 8 * (3 K + 3 * 40 +
+    64 * (3 K | 1)) B: 51 392 at K = 32), against dense sampling of the curve with the host build of the true point-to-hull
+    distance, refined by a bounded scalar minimisation (the ground truth of test_min_dist2poly_robust)."""
+    import scipy.optimize as sop
+    N, n = 4, K - 1
+    Y = synth.swarm_control_points(N, 2, n, seed=K + 1)
+    curves = np.zeros((N, 3, K))
+    curves[:, :2, :] = Y.reshape(N, 2, K)
+    rng = np.random.default_rng(K)
+    polys = []
+    for kv in (6, 20, 40):
+        ang = np.sort(rng.uniform(0, 2 * np.pi, kv))
+        c = rng.uniform(20, 80, 2)
+        P = np.zeros((kv, 3))
+        P[:, 0] = c[0] + 8 * np.cos(ang); P[:, 1] = c[1] + 5 * np.sin(ang)
+        polys.append(P)
+    pts, off = synth.pack_polys(polys)
+    pc = np.repeat(np.arange(N), len(polys)).astype(np.int32)
+    pp = np.tile(np.arange(len(polys)), N).astype(np.int32)
+    ctx = capi.scratch_context()
+    r = ctx.min_dist2poly_robust(curves, pts, off, pc, pp, eps=1e-9)
+    assert (r["status"] == capi.MD_OK).all(), np.bincount(r["status"])
+    ts = np.linspace(0.0, 1.0, 401)
+    Bm = _bez_basis(n, ts)
+    for k in range(len(pc)):
+        c, poly = curves[pc[k]], polys[pp[k]]
+        f = lambda t: host_gjk(c @ _bez_basis(n, np.array([t]))[0], poly, eps=1e-12)["dist"]     # noqa: E731
+        vals = np.array([host_gjk(c @ Bm[i], poly, eps=1e-12)["dist"] for i in range(len(ts))])
+        i0 = int(vals.argmin())
+        lo, hi = ts[max(i0 - 1, 0)], ts[min(i0 + 1, len(ts) - 1)]
+        best = min(vals[i0], sop.minimize_scalar(f, bounds=(lo, hi), method="bounded", options={"xatol": 1e-12}).fun)
+        d = r["res"][k, 0]
+        assert d <= best * (1 + 1e-7) + 1e-9, (K, k, d, best)
+        assert d >= best * (1 - 1e-6) - 1e-9, (K, k, d, best)
+        assert abs(f(r["res"][k, 1]) - d) <= 1e-8 * max(1.0, d)
 
 
 @pytest.mark.parametrize("R", [0, 7])

@@ -210,6 +210,33 @@ def test_min_dist(oracle, golden_dir):
                   r["res"][2:], m["c3p_pt"][k])
 
 
+def test_min_dist_wide_shapes(oracle, golden_dir):
+    """mindist_wide.npz: `_minDist` on curves of 17, 21, 25 and 32 control points (2-D and 3-D; swarm pairs and crossing pairs
+    drawn in a small box) and `_minDist2Poly` on curves of 11, 21 and 32 points against polygons of 20, 32, 40 and 64 vertices
+    (planar ones, and point sets in space): the oracle returns the reference's bits, gjkNew-call counts and closest points."""
+    m = _load(golden_dir, "mindist_wide.npz")
+    n_ok = n_ok_p = 0
+    for g in m["md_groups"]:
+        cur, pairs = m[g + "_curves"], m[g + "_pairs"]
+        for k, (i, j) in enumerate(pairs):
+            r = oracle.min_dist(cur[i], cur[j], max_nodes=300000)
+            if m[g + "_status"][k] == 1 and r["status"] == oracle.MD_OK:
+                continue   # the generator's wall-clock budget fired on a finite (long) search
+            _check_md(oracle, m[g + "_status"][k], m[g + "_res"][k], m[g + "_calls"][k], r)
+            n_ok += m[g + "_status"][k] == 0
+    for g in m["p_groups"]:
+        cur, pts, off, pairs = m[g + "_curves"], m[g + "_pts"], m[g + "_off"], m[g + "_pairs"]
+        for k, (i, q) in enumerate(pairs):
+            r = oracle.min_dist2poly(cur[i], pts[off[q]:off[q + 1]], max_nodes=300000)
+            if m[g + "_status"][k] == 1 and r["status"] == oracle.MD_OK:
+                continue
+            _check_md(oracle, m[g + "_status"][k], m[g + "_res"][k], m[g + "_calls"][k], r, r["res"][2:], m[g + "_pt"][k])
+            n_ok_p += m[g + "_status"][k] == 0
+    # every pair the reference finished (60 curve pairs, 65 curve-polygon pairs) was compared
+    assert n_ok == sum(int((m[g + "_status"] == 0).sum()) for g in m["md_groups"]) == 60, n_ok
+    assert n_ok_p == sum(int((m[g + "_status"] == 0).sum()) for g in m["p_groups"]) == 65, n_ok_p
+
+
 def test_min_dist_on_the_example_scripts_inputs(oracle, golden_dir):
     """Examples/MinDistBez2Bez.py:42-84's five curves (every ordered pair) and three polygons through the reference
     (mindist_script.npz): the oracle returns the reference's numbers where the reference returns, a status elsewhere."""

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The reference's Example1 driver flow (Examples/Example1_DubinsCarTimeOptimal.py:94-148: two
 Dubins cars, degree 10, time-optimal, SLSQP) on the MI355X path.  Only the import lines differ
-from a reference driver; the second solve hands SLSQP the batched finite-difference Jacobians.
+from a reference driver; the second solve hands SLSQP the batched finite-difference Jacobians, and at DEG_ELEV 0 a
+third one the exact Jacobians (method='exact').
 
     python examples/example1_dubins_time_optimal.py
 """
@@ -49,6 +50,17 @@ def main():
         t2 = time.time()
         print('DEG_ELEV %3d: tf* = %.9f (nit %d, %.2f s with callbacks)   tf* = %.9f (nit %d, %.2f s with batched Jacobians)'
               % (elev, res.fun, res.nit, t1 - t0, res_j.fun, res_j.nit, t2 - t1))
+        if elev == 0:
+            # third solve: the exact Jacobians from the device (method='exact') instead of finite differences
+            cons_e = [dict(c) for c in cons]
+            cons_e[0]['jac'] = lambda x: bezopt.temporalSeparationJacobian(x, method='exact')
+            cons_e[1]['jac'] = lambda x: bezopt.maxSpeedJacobian(x, method='exact')
+            cons_e[2]['jac'] = lambda x: bezopt.maxAngularRateJacobian(x, method='exact')
+            cons_e[3]['jac'] = lambda x: np.eye(1, x.size, x.size - 1)
+            t2 = time.time()
+            res_e = sop.minimize(bezopt.objectiveFunction, x0=xGuess, method='SLSQP', constraints=cons_e,
+                                 jac=lambda x: bezopt.objectiveGradient(x, method='exact'), options={'maxiter': 250, 'disp': False})
+            print('              tf* = %.9f (nit %d, %.2f s with exact Jacobians)' % (res_e.fun, res_e.nit, time.time() - t2))
         cpts = bezopt.reshapeVector(res.x)
         curves = [bez.Bezier(cpts[i * dim:(i + 1) * dim]) for i in range(numVeh)]
         print('   end points:', [c.cpts[:, -1].tolist() for c in curves])

@@ -82,12 +82,15 @@ const char* obtg_strerror(int code);
  *   5  round 5: nothing changed meaning; new: obtg_abi_version, obtg_fast_kernels, obtg_ctx_ang_rate_order_in_effect, obtg_temporal_sep_active[_dev],
  *      obtg_comm_* and obtg_temporal_sep_min_gather_dev (the collective behind the C ABI); 9 control points (degree 8)
  *      joined the specialised counts.
- *   6  round 6: nothing changed meaning; new: obtg_source_hash, obtg_libm_pow_matches. */
-#define OBTG_ABI_VERSION 6
+ *   6  round 6: nothing changed meaning; new: obtg_source_hash, obtg_libm_pow_matches.
+ *   7  nothing changed meaning; new: the exact derivatives obtg_temporal_sep_jac[_dev], obtg_speed_jac[_dev],
+ *      obtg_ang_rate_jac[_dev], obtg_euclidean_grad, obtg_deriv_energy_grad and the kernel-stats id OBTG_K_JAC
+ *      (OBTG_K_COUNT moved from 8 to 9). */
+#define OBTG_ABI_VERSION 7
 int obtg_abi_version(void);
 
 /* Which sources this library was built from: the first 16 hex digits of a sha256 over a compile unit's source, the headers of
- * csrc/ and its compiler flags.  unit: "gjk_kernels", "bern_kernels", "capi", "tables", "comm", "libm_check", or "all" (NULL =
+ * csrc/ and its compiler flags.  unit: "gjk_kernels", "bern_kernels", "jac_kernels", "capi", "tables", "comm", "libm_check", or "all" (NULL =
  * "all"); NULL is returned for a name that is none of these.  Counter files under profiles/ record the hash of the kernels they
  * were taken on; bench.py drops a counter whose hash is not the running library's instead of reporting it as measured. */
 const char* obtg_source_hash(const char* unit);
@@ -478,12 +481,40 @@ int obtg_euclidean_obj(obtg_ctx*, const double* Y, int B, double* out /*[B]*/);
 int obtg_accel_obj(obtg_ctx*, const double* Y, const double* tf, int B, double* out /*[B]*/);
 int obtg_jerk_obj(obtg_ctx*, const double* Y, const double* tf, int B, double* out /*[B]*/);
 
+/* ---- exact derivatives (the `jac` SLSQP takes; no finite differences) ----------------------
+ * With n = deg, d = dim, R = deg_elev, L = 2n+R+1, La = 4(n+R)+1, P = C(N+M, 2); every block is batched over the B rows
+ * of Y like the value entry points, and the entries of a block are the partial derivatives with respect to the control
+ * points Y[v*d + c][i] of ONE vehicle, laid out [d][n+1] (c major).
+ * obtg_temporal_sep_jac: d/dP_a of obtg_temporal_sep's rows (optimization.py:311-346), out[B][P][L][d][n+1] for pair (a, b)
+ *   in lexicographic order.  The b side is the exact negation of the a side and is not stored; when b is a point obstacle
+ *   it has no variable, and a pair of two obstacles is all zeros.
+ * obtg_speed_jac: d/dP_v of obtg_speed's rows (optimization.py:349-422, diff's trailing elev(1) included), out[B][N][L][d][n+1],
+ *   the sign of is_max applied (bound^2 - v: negated); out_tf[B][N][L] (nullable) = d/dtf at fixed control points
+ *   (the rows scale as tf^-2).
+ * obtg_ang_rate_jac: dim 2, d/dP_v of obtg_ang_rate's rows (optimization.py:425-459, 578-611), out[B][N][La][2][n+1],
+ *   out_tf[B][N][La] (nullable).  Numerator and denominator are differentiated at degree 4n and elevated by 4R -- elevation
+ *   is exact, so these are the derivatives of the rows of every obtg_ctx_set_ang_rate_order.  A row whose quotient is not
+ *   finite (a vehicle at rest at a control point of |v|^2) gets NaN derivatives.  OBTG_ERR_UNSUPPORTED for n > 15 or
+ *   4R > 1000, and where the per-vehicle working set passes 64 KB of LDS (at n = 15: R > 177).
+ * obtg_euclidean_grad: gradient of obtg_euclidean_obj (optimization.py:462-489), out[B][N*d][n+1]; a zero-length
+ *   segment gives NaN at its two ends.
+ * obtg_deriv_energy_grad: gradient of obtg_accel_obj (order 2, optimization.py:503-519) / obtg_jerk_obj (order 3,
+ *   optimization.py:522-539), out[B][N*d][n+1], out_tf[B] (nullable) = d/dtf (the objective scales as tf^(-2 order)). */
+int obtg_temporal_sep_jac(obtg_ctx*, const double* Y, int B, double* out);
+int obtg_temporal_sep_jac_dev(obtg_ctx*, const double* dY, int B, double* d_out);
+int obtg_speed_jac(obtg_ctx*, const double* Y, const double* tf, int B, int is_max, double* out, double* out_tf);
+int obtg_speed_jac_dev(obtg_ctx*, const double* dY, const double* d_tf, int B, int is_max, double* d_out, double* d_out_tf);
+int obtg_ang_rate_jac(obtg_ctx*, const double* Y, const double* tf, int B, double* out, double* out_tf);
+int obtg_ang_rate_jac_dev(obtg_ctx*, const double* dY, const double* d_tf, int B, double* d_out, double* d_out_tf);
+int obtg_euclidean_grad(obtg_ctx*, const double* Y, int B, double* out);
+int obtg_deriv_energy_grad(obtg_ctx*, const double* Y, const double* tf, int B, int order, double* out, double* out_tf);
+
 /* ---- instrumentation -------------------------------------------------------------------
  * When enabled every kernel launch is bracketed by HIP events on the launch stream;
  * obtg_kernel_stats returns the accumulated device time and launch count per kernel id. */
 enum {
     OBTG_K_TEMPORAL_SEP = 0, OBTG_K_SPEED = 1, OBTG_K_ANG_RATE = 2, OBTG_K_GJK = 3,
-    OBTG_K_MIN_DIST = 4, OBTG_K_FD_BATCH = 5, OBTG_K_BERN = 6, OBTG_K_PAIR_SWEEP = 7, OBTG_K_COUNT = 8
+    OBTG_K_MIN_DIST = 4, OBTG_K_FD_BATCH = 5, OBTG_K_BERN = 6, OBTG_K_PAIR_SWEEP = 7, OBTG_K_JAC = 8, OBTG_K_COUNT = 9
 };
 /* on: 0 = off, 1 = every kernel, OBTG_PROFILE_ONLY(id) = only launches of that kernel id (two
  * events per launch drain the queue between kernels: 15 % of a 0.25 ms step when all three

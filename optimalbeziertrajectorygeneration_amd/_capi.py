@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("OBTG_LIB") or os.path.join(HERE, "libobtg_hip.so")   
 OK = 0
 ST_OK, ST_MD_CAP, ST_MAXITER, ST_CYCLE = 0, 1, 2, 3
 MD_OK, MD_NODE_CAP, MD_DEPTH_CAP, MD_GJK_CAP = 0, 1, 2, 3
-K_TEMPORAL_SEP, K_SPEED, K_ANG_RATE, K_GJK, K_MIN_DIST, K_FD_BATCH, K_BERN, K_PAIR_SWEEP, K_COUNT = range(9)
+K_TEMPORAL_SEP, K_SPEED, K_ANG_RATE, K_GJK, K_MIN_DIST, K_FD_BATCH, K_BERN, K_PAIR_SWEEP, K_JAC, K_COUNT = range(10)
 
 _lib = None
 
@@ -111,6 +111,14 @@ _SIGNATURES = {
     "obtg_euclidean_obj": (_i, [_vp, _vp, _i, _vp]),
     "obtg_accel_obj": (_i, [_vp, _vp, _vp, _i, _vp]),
     "obtg_jerk_obj": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "obtg_temporal_sep_jac": (_i, [_vp, _vp, _i, _vp]),
+    "obtg_temporal_sep_jac_dev": (_i, [_vp, _vp, _i, _vp]),
+    "obtg_speed_jac": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "obtg_speed_jac_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "obtg_ang_rate_jac": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "obtg_ang_rate_jac_dev": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "obtg_euclidean_grad": (_i, [_vp, _vp, _i, _vp]),
+    "obtg_deriv_energy_grad": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "obtg_set_profiling": (_i, [_vp, _i]),
     "obtg_set_profile_period": (_i, [_vp, _i]),
     "obtg_kernel_stats": (_i, [_vp, _i, C.POINTER(_d), C.POINTER(C.c_longlong)]),
@@ -557,6 +565,62 @@ class Context(object):
 
     def accel_obj(self, Y, tf):
         return self.deriv_energy_obj(Y, tf, 2)
+
+    # -- exact derivatives (include/obtg.h obtg_*_jac / *_grad): blocks per pair / vehicle, [..][d][deg + 1] per vehicle
+    def temporal_sep_jac(self, Y):
+        """d(temporal_sep rows)/d(first object's control points): [B][P][2n+R+1][d][n+1] (the second object's: the negation)."""
+        Y, B = self._rows(Y)
+        L, nc = 2 * self.deg + self.deg_elev + 1, self.deg + 1
+        out = np.empty((B, self.num_pairs, L, self.dim, nc))
+        self._check(self._lib.obtg_temporal_sep_jac(self._h, _ptr(Y), B, _ptr(out)), "obtg_temporal_sep_jac")
+        return out
+
+    def temporal_sep_jac_dev(self, dY, B, d_out):
+        self._check(self._lib.obtg_temporal_sep_jac_dev(self._h, _vp(dY), int(B), _vp(d_out)), "obtg_temporal_sep_jac_dev")
+
+    def speed_jac(self, Y, tf, is_max):
+        """(d rows / d own control points [B][N][2n+R+1][d][n+1], d rows / d tf [B][N][2n+R+1]) of speed(Y, tf, bound, is_max)."""
+        Y, B = self._rows(Y)
+        tf = self._tf(tf, B)
+        L, nc = 2 * self.deg + self.deg_elev + 1, self.deg + 1
+        out, out_tf = np.empty((B, self.n_veh, L, self.dim, nc)), np.empty((B, self.n_veh, L))
+        self._check(self._lib.obtg_speed_jac(self._h, _ptr(Y), _ptr(tf), B, int(bool(is_max)), _ptr(out), _ptr(out_tf)),
+                    "obtg_speed_jac")
+        return out, out_tf
+
+    def speed_jac_dev(self, dY, d_tf, B, is_max, d_out, d_out_tf=None):
+        self._check(self._lib.obtg_speed_jac_dev(self._h, _vp(dY), _vp(d_tf), int(B), int(bool(is_max)), _vp(d_out),
+                                                 _vp(d_out_tf)), "obtg_speed_jac_dev")
+
+    def ang_rate_jac(self, Y, tf):
+        """(d rows / d own control points [B][N][4(n+R)+1][2][n+1], d rows / d tf [B][N][4(n+R)+1]) of ang_rate; rows whose
+        value is not finite: NaN."""
+        Y, B = self._rows(Y)
+        tf = self._tf(tf, B)
+        La, nc = 4 * (self.deg + self.deg_elev) + 1, self.deg + 1
+        out, out_tf = np.empty((B, self.n_veh, La, 2, nc)), np.empty((B, self.n_veh, La))
+        self._check(self._lib.obtg_ang_rate_jac(self._h, _ptr(Y), _ptr(tf), B, _ptr(out), _ptr(out_tf)), "obtg_ang_rate_jac")
+        return out, out_tf
+
+    def ang_rate_jac_dev(self, dY, d_tf, B, d_out, d_out_tf=None):
+        self._check(self._lib.obtg_ang_rate_jac_dev(self._h, _vp(dY), _vp(d_tf), int(B), _vp(d_out), _vp(d_out_tf)),
+                    "obtg_ang_rate_jac_dev")
+
+    def euclidean_grad(self, Y):
+        """Gradient of euclidean_obj: [B][N d][n+1]."""
+        Y, B = self._rows(Y)
+        out = np.empty((B, self.n_veh * self.dim, self.deg + 1))
+        self._check(self._lib.obtg_euclidean_grad(self._h, _ptr(Y), B, _ptr(out)), "obtg_euclidean_grad")
+        return out
+
+    def deriv_energy_grad(self, Y, tf, order):
+        """Gradient of deriv_energy_obj (order 2 accel, 3 jerk): ([B][N d][n+1], d/dtf [B])."""
+        Y, B = self._rows(Y)
+        tf = self._tf(tf, B)
+        out, out_tf = np.empty((B, self.n_veh * self.dim, self.deg + 1)), np.empty(B)
+        self._check(self._lib.obtg_deriv_energy_grad(self._h, _ptr(Y), _ptr(tf), B, int(order), _ptr(out), _ptr(out_tf)),
+                    "obtg_deriv_energy_grad")
+        return out, out_tf
 
     # -- device-pointer sweeps (pointers are plain ints, e.g. torch.Tensor.data_ptr())
     def temporal_sep_dev(self, dY, B, max_sep, d_out, pair_begin=0, pair_count=None):

@@ -237,6 +237,7 @@ const char* obtg_abi_symbols(void)
         "obtg_ctx_set_fd_dedup\0obtg_ctx_set_gjk_history\0obtg_pair_sweep_dev\0obtg_constraint_sweep_dev\0obtg_constraint_sweep_fd_structured_dev\0obtg_constraint_sweep_fd_structured_rows_dev\0obtg_gjk_swarm_dev\0obtg_gjk_swarm\0obtg_min_dist\0obtg_min_dist_robust\0obtg_min_dist2poly\0obtg_min_dist2poly_robust\0obtg_gjk_true_pairs\0"
         "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_eval\0"
         "obtg_euclidean_obj\0obtg_accel_obj\0obtg_jerk_obj\0"
+        "obtg_temporal_sep_jac\0obtg_temporal_sep_jac_dev\0obtg_speed_jac\0obtg_speed_jac_dev\0obtg_ang_rate_jac\0obtg_ang_rate_jac_dev\0obtg_euclidean_grad\0obtg_deriv_energy_grad\0"
         "obtg_set_profiling\0obtg_set_profile_period\0obtg_kernel_stats\0obtg_reset_kernel_stats\0obtg_kernel_name\0";
     return syms;
 }
@@ -288,7 +289,7 @@ void obtg_ctx_destroy(obtg_ctx* c)
     (void)hipStreamSynchronize(c->stream);
     flush_pending_events(c);
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
-    DevBuf* bufs[] = { &c->d_pairs, &c->d_obs, &c->d_w2, &c->d_Tt, &c->d_Td, &c->d_Tf, &c->d_ang_dd, &c->d_ang_flags, &c->d_vp_off, &c->d_vp_idx, &c->d_ang_w2n, &c->d_ang_w22n, &c->d_ang_wn, &c->d_ang_T4, &c->d_ang_cv2,
+    DevBuf* bufs[] = { &c->d_pairs, &c->d_obs, &c->d_w2, &c->d_Tt, &c->d_Td, &c->d_Tf, &c->d_ang_dd, &c->d_ang_flags, &c->d_vp_off, &c->d_vp_idx, &c->d_ang_w2n, &c->d_ang_w22n, &c->d_ang_wn, &c->d_ang_T4, &c->d_ang_cv2, &c->d_jac,
                        &c->d_binrows, &c->d_tiles, &c->d_poly_pts, &c->d_poly_off, &c->d_hp_a, &c->d_hp_b, &c->d_tile_chunk_off, &c->d_tile_order, &c->d_tile_pslots,
                        &c->d_tile_cobj_off, &c->d_tile_cobjs, &c->d_tile_ij, &c->ws_in,
                        &c->ws_in2, &c->ws_out, &c->ws_fd };
@@ -1455,6 +1456,123 @@ int obtg_jerk_obj(obtg_ctx* c, const double* Y, const double* tf, int B, double*
     return host_deriv_obj(c, Y, tf, B, 3, out);
 }
 
+// ------------------------------------------------------------------ exact derivatives (jac_kernels.hip)
+int obtg_temporal_sep_jac_dev(obtg_ctx* c, const double* dY, int B, double* d_out)
+{
+    if (!check_ctx(c) || B < 0) return OBTG_ERR_ARG;
+    if (B == 0 || c->n_pairs == 0) return OBTG_OK;
+    if (!dY || !d_out) return OBTG_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    return launch_temporal_sep_jac(c, dY, B, d_out);
+}
+
+int obtg_temporal_sep_jac(obtg_ctx* c, const double* Y, int B, double* out)
+{
+    if (!check_ctx(c) || !Y || !out || B < 0) return OBTG_ERR_ARG;
+    if (B == 0 || c->n_pairs == 0) return OBTG_OK;
+    (void)hipSetDevice(c->device);
+    const size_t per = (size_t)c->n_pairs * (2 * c->deg + c->R + 1) * c->dim * (c->deg + 1);
+    int rc = h2d(c, c->ws_in, Y, sizeof(double) * ysize(c) * B);
+    if (rc) return rc;
+    if ((rc = c->ws_out.reserve(sizeof(double) * per * B))) return rc;
+    if ((rc = launch_temporal_sep_jac(c, c->ws_in.as<double>(), B, c->ws_out.as<double>()))) return rc;
+    return d2h(c, out, c->ws_out.p, sizeof(double) * per * B);
+}
+
+int obtg_speed_jac_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, int is_max, double* d_out, double* d_out_tf)
+{
+    if (!check_ctx(c) || B < 0) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    if (!dY || !d_tf || !d_out) return OBTG_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    return launch_speed_jac(c, dY, d_tf, B, is_max, d_out, d_out_tf);
+}
+
+// the per-vehicle families' host entry points: Y, tf in; [B][N][rows][d][n+1] and (nullable) [B][N][rows] out
+static int host_vehicle_jac(obtg_ctx* c, const double* Y, const double* tf, int B, int rows, double* out, double* out_tf,
+                            int (*launch)(obtg_ctx*, const double*, const double*, int, double*, double*, int), int arg)
+{
+    if (!check_ctx(c) || !Y || !tf || !out || B < 0) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    (void)hipSetDevice(c->device);
+    const size_t per = (size_t)c->n_veh * rows * c->dim * (c->deg + 1), per_tf = (size_t)c->n_veh * rows;
+    int rc = h2d(c, c->ws_in, Y, sizeof(double) * ysize(c) * B);
+    if (rc) return rc;
+    if ((rc = h2d(c, c->ws_in2, tf, sizeof(double) * B))) return rc;
+    if ((rc = c->ws_out.reserve(sizeof(double) * per * B))) return rc;
+    double* d_tfo = nullptr;
+    if (out_tf) {
+        if ((rc = c->ws_misc[5].reserve(sizeof(double) * per_tf * B))) return rc;
+        d_tfo = c->ws_misc[5].as<double>();
+    }
+    if ((rc = launch(c, c->ws_in.as<double>(), c->ws_in2.as<double>(), B, c->ws_out.as<double>(), d_tfo, arg))) return rc;
+    if (out_tf && (rc = d2h_copy(c, out_tf, d_tfo, sizeof(double) * per_tf * B))) return rc;
+    return d2h(c, out, c->ws_out.p, sizeof(double) * per * B);
+}
+
+static int speed_jac_launch(obtg_ctx* c, const double* dY, const double* d_tf, int B, double* d_out, double* d_out_tf, int is_max)
+{
+    return launch_speed_jac(c, dY, d_tf, B, is_max, d_out, d_out_tf);
+}
+
+static int ang_rate_jac_launch(obtg_ctx* c, const double* dY, const double* d_tf, int B, double* d_out, double* d_out_tf, int)
+{
+    return launch_ang_rate_jac(c, dY, d_tf, B, d_out, d_out_tf);
+}
+
+int obtg_speed_jac(obtg_ctx* c, const double* Y, const double* tf, int B, int is_max, double* out, double* out_tf)
+{
+    if (!check_ctx(c)) return OBTG_ERR_ARG;
+    return host_vehicle_jac(c, Y, tf, B, 2 * c->deg + c->R + 1, out, out_tf, speed_jac_launch, is_max);
+}
+
+int obtg_ang_rate_jac_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double* d_out, double* d_out_tf)
+{
+    if (!check_ctx(c) || B < 0 || c->dim != 2) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    if (!dY || !d_tf || !d_out) return OBTG_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    return launch_ang_rate_jac(c, dY, d_tf, B, d_out, d_out_tf);
+}
+
+int obtg_ang_rate_jac(obtg_ctx* c, const double* Y, const double* tf, int B, double* out, double* out_tf)
+{
+    if (!check_ctx(c) || c->dim != 2) return OBTG_ERR_ARG;
+    return host_vehicle_jac(c, Y, tf, B, 4 * (c->deg + c->R) + 1, out, out_tf, ang_rate_jac_launch, 0);
+}
+
+int obtg_euclidean_grad(obtg_ctx* c, const double* Y, int B, double* out)
+{
+    if (!check_ctx(c) || !Y || !out || B < 0) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    (void)hipSetDevice(c->device);
+    int rc = h2d(c, c->ws_in, Y, sizeof(double) * ysize(c) * B);
+    if (rc) return rc;
+    if ((rc = c->ws_out.reserve(sizeof(double) * ysize(c) * B))) return rc;
+    if ((rc = launch_euclidean_grad(c, c->ws_in.as<double>(), B, c->ws_out.as<double>()))) return rc;
+    return d2h(c, out, c->ws_out.p, sizeof(double) * ysize(c) * B);
+}
+
+int obtg_deriv_energy_grad(obtg_ctx* c, const double* Y, const double* tf, int B, int order, double* out, double* out_tf)
+{
+    if (!check_ctx(c) || !Y || !tf || !out || B < 0 || order < 1 || order > 4) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    (void)hipSetDevice(c->device);
+    int rc = h2d(c, c->ws_in, Y, sizeof(double) * ysize(c) * B);
+    if (rc) return rc;
+    if ((rc = h2d(c, c->ws_in2, tf, sizeof(double) * B))) return rc;
+    if ((rc = c->ws_out.reserve(sizeof(double) * ysize(c) * B))) return rc;
+    double* d_tfo = nullptr;
+    if (out_tf) {
+        if ((rc = c->ws_misc[5].reserve(sizeof(double) * B))) return rc;
+        d_tfo = c->ws_misc[5].as<double>();
+    }
+    if ((rc = launch_deriv_energy_grad(c, c->ws_in.as<double>(), c->ws_in2.as<double>(), B, order, c->ws_out.as<double>(), d_tfo)))
+        return rc;
+    if (out_tf && (rc = d2h_copy(c, out_tf, d_tfo, sizeof(double) * B))) return rc;
+    return d2h(c, out, c->ws_out.p, sizeof(double) * ysize(c) * B);
+}
+
 // ------------------------------------------------------------------ instrumentation
 int obtg_set_profiling(obtg_ctx* c, int on)
 {
@@ -1503,6 +1621,7 @@ const char* obtg_kernel_name(int id)
         case OBTG_K_FD_BATCH: return "fd_batch";
         case OBTG_K_BERN: return "bern";
         case OBTG_K_PAIR_SWEEP: return "pair_sweep";
+        case OBTG_K_JAC: return "jac";
         default: return "?";
     }
 }

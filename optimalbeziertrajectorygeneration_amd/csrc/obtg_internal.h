@@ -91,6 +91,11 @@ struct obtg_ctx {
     bool ang_exact = false;           // obtg_ctx_set_ang_rate_order(2): the default order, then the rows of near-stop vehicles again in
                                       // double-double (k_angrate_dd); tables and the flag list below, made on first use
     obtg::DevBuf d_ang_dd, d_ang_flags;
+    // exact Jacobians (jac_kernels.hip): G = elevation o folded product for (deg, R), its row sums, and for dim 2 the angular
+    // rate's product / elevation weights from offset jac_off_ang (-1: not this shape); made on first use, per R
+    obtg::DevBuf d_jac;
+    int jac_R = -1;
+    long long jac_off_ang = -1;
     obtg::DdTables ang_dd_off{};
     int ang_dd_R = -1;
     // obtg_ctx_set_second_speed_bound: every dynamics pass that writes speed rows also writes the other bound's rows
@@ -237,6 +242,13 @@ int launch_bern_mul(obtg_ctx* c, const double* d_a, const double* d_b, int rows,
 int launch_bern_normsq(obtg_ctx* c, const double* d_x, int d, int n, double* d_out);
 int launch_euclidean_obj(obtg_ctx* c, const double* dY, int B, double* d_out);
 int launch_deriv_energy_obj(obtg_ctx* c, const double* dY, const double* d_tf, double tf0, int B, int order, double* d_out);
+
+// ---------------------------------------------------------------- launchers (jac_kernels.hip): exact derivatives, layouts in obtg.h
+int launch_temporal_sep_jac(obtg_ctx* c, const double* dY, int B, double* d_out);
+int launch_speed_jac(obtg_ctx* c, const double* dY, const double* d_tf, int B, int is_max, double* d_out, double* d_out_tf);
+int launch_ang_rate_jac(obtg_ctx* c, const double* dY, const double* d_tf, int B, double* d_out, double* d_out_tf);
+int launch_euclidean_grad(obtg_ctx* c, const double* dY, int B, double* d_out);
+int launch_deriv_energy_grad(obtg_ctx* c, const double* dY, const double* d_tf, int B, int order, double* d_out, double* d_out_tf);
 
 // ---------------------------------------------------------------- launchers (gjk_kernels.hip)
 int launch_gjk_pairs(obtg_ctx* c, const double* d_soa, const int* d_off, const int* d_pa,

@@ -150,6 +150,11 @@ def _angularRateSqr(bezTraj):
     return bez.RationalBezier(quotient[None, :], (speed2 * speed2).cpts)
 
 
+def _check_method(method):
+    if method not in ('fd', 'exact'):
+        raise ValueError("method must be 'fd' or 'exact', not {!r}".format(method))
+
+
 # (key of BezOptimization.model, constructor keyword, container) -- optimization.py:49-63 defines the keys
 _MODEL_FIELDS = (
     ('numVeh', 'numVeh', None), ('dim', 'dimension', None), ('deg', 'degree', None), ('minGoal', 'minimizeGoal', None),
@@ -372,17 +377,30 @@ class BezOptimization(object):
     def jerkObjective(self, x):
         return float(self._serve('obj_jerk', x, lambda x_: self._ctx(False).deriv_energy_obj(self.reshapeVector(x_), self.model['tf'], 3)[:1])[0])
 
-    def objectiveGradient(self, x):
+    def objectiveGradient(self, x, method='fd'):
         """Gradient of `objectiveFunction` the way SciPy would difference it (2-point, abs_step = sqrt(eps)), but from ONE
         batched evaluation of the n_x + 1 rows instead of n_x + 1 callbacks: pass it as `jac=` to `minimize`.  (With
         the constraint Jacobians supplied, the objective's finite differences are what is left of the per-iteration
-        callback count: 17 983 of them in examples/example2_swarm_3d.py with 8 vehicles.)"""
+        callback count: 17 983 of them in examples/example2_swarm_3d.py with 8 vehicles.)
+        method='exact': the analytic gradient from the device (obtg_euclidean_grad / obtg_deriv_energy_grad) instead."""
+        _check_method(method)
         x = np.asarray(x, dtype=float)
         goal = self.model['minGoal'].lower()
         if goal == 'timeopt':
             g = np.zeros(x.size)
             g[-1] = 1.0
             return g
+        if method == 'exact':
+            Y0 = self.reshapeVectors(x[None])
+            c = self._ctx(False)
+            if goal == 'euclidean':
+                G = c.euclidean_grad(Y0)[0]
+            elif goal in ('accel', 'jerk'):
+                G = c.deriv_energy_grad(Y0, self.model['tf'], 2 if goal == 'accel' else 3)[0][0]
+            else:
+                self.objectiveFunction          # raises the reference's ValueError for an unknown goal
+            first = self._rv_parts()[1]
+            return G[:, first:first + self._numCols].ravel()
         X, dx = self._fd_rows(x)
         Y = self.reshapeVectors(X)
         c = self._ctx(False)
@@ -640,14 +658,20 @@ class BezOptimization(object):
                 F = c.ang_rate(Y, tf, self.model['maxAngRate'])
         return F, dx
 
-    def temporalSeparationJacobian(self, x, structured=True):
+    def temporalSeparationJacobian(self, x, structured=True, method='fd'):
         """d(temporalSeparationConstraints)/dx by SciPy-style forward differences.
 
         structured=True: a variable of vehicle v only moves the N-1 pairs
         that contain v, so only those pairs are re-evaluated (obtg_temporal_sep_fd) and the dense
         matrix is assembled from them; every entry equals the brute-force batch's
         (structured=False) bit for bit.  Variables that move every vehicle (tf with prescribed
-        speeds) and shapes outside the specialised kernels take the batch path."""
+        speeds) and shapes outside the specialised kernels take the batch path.
+
+        method='exact': the analytic Jacobian (obtg_temporal_sep_jac, one launch at x; `structured` is ignored).  With
+        separationRows 'min' / 'active' its rows are those of the control points the value kernels select at x."""
+        _check_method(method)
+        if method == 'exact':
+            return self._temporal_sep_jac_exact(x)
         if not structured or self.separationRows == 'active':
             # 'active': the forward differences of the order statistics themselves -- what SciPy builds from n_x + 1 calls
             # of the closure -- from one batched call (k values per pair and row leave the device, not 2n+R+1)
@@ -691,12 +715,15 @@ class BezOptimization(object):
             J[:, n_pts:] = ((Ft - F0[None]) / dx[n_pts:, None]).T
         return J
 
-    def _jac_vehicle(self, x, family, structured=True):
+    def _jac_vehicle(self, x, family, structured=True, method='fd'):
         """Per-vehicle families (speed, angular rate): the Jacobian is block diagonal -- a control
         point of vehicle v only moves v's own rows.  structured=True evaluates, per variable, that one
         vehicle (a compact batch on a one-vehicle context: n_x vehicle evaluations instead of
         n_x N); entries equal the brute-force batch's bit for bit.  A trailing tf moves everything and
-        takes the batch path."""
+        takes the batch path.  method='exact': the analytic blocks (obtg_speed_jac / obtg_ang_rate_jac, one launch at x)."""
+        _check_method(method)
+        if method == 'exact':
+            return self._jac_vehicle_exact(x, family)
         if not structured:
             return self._jac(x, family)
         x = np.asarray(x, dtype=float)
@@ -731,14 +758,85 @@ class BezOptimization(object):
             J[:, n_pts:] = ((Ft - F0[None]) / dx[n_pts:, None]).T
         return J
 
-    def maxSpeedJacobian(self, x, structured=True):
-        return self._jac_vehicle(x, 'vmax', structured)
+    def maxSpeedJacobian(self, x, structured=True, method='fd'):
+        return self._jac_vehicle(x, 'vmax', structured, method)
 
-    def minSpeedJacobian(self, x, structured=True):
-        return self._jac_vehicle(x, 'vmin', structured)
+    def minSpeedJacobian(self, x, structured=True, method='fd'):
+        return self._jac_vehicle(x, 'vmin', structured, method)
 
-    def maxAngularRateJacobian(self, x, structured=True):
-        return self._jac_vehicle(x, 'ang', structured)
+    def maxAngularRateJacobian(self, x, structured=True, method='fd'):
+        return self._jac_vehicle(x, 'ang', structured, method)
+
+    # ------------------------------------------------------------------ exact Jacobians (method='exact')
+    # The device returns d rows / d Y per pair or vehicle ([..][rows][dim][deg+1] blocks, include/obtg.h obtg_*_jac); the chain
+    # rule to x keeps the free columns, and for a time-optimal problem adds the tf column: the explicit d/dtf of the speed and
+    # angular-rate rows plus, with prescribed speeds, the rows' derivative along dY/dtf (columns 1 and -2, reshapeVectors).
+    def _dY_dtf(self):
+        """dY/dtf [numVeh*dim][deg+1]: nonzero in columns 1 and -2 when speeds are prescribed (p0 + (v0 tf / deg) (cos, sin))."""
+        template, _, headings = self._rv_parts()
+        D = np.zeros(template.shape)
+        if headings is not None:
+            deg = self.model['deg']
+            for col, (speed, _px, _py, c, s) in ((1, headings[0]), (-2, headings[1])):
+                D[0::2, col] = speed * c / deg
+                D[1::2, col] = speed * s / deg
+        return D
+
+    def _scatter_exact(self, blk, owner, sign, dtf=None):
+        """Dense J [K * rows][n_x] from blocks blk[K][rows][dim][deg+1]: block k is the derivative of its rows with respect to
+        the control points of vehicle owner[j][k], times sign[j] (j over the block's sides; owner >= numVeh: a point obstacle,
+        no variable).  dtf[K][rows]: the explicit d/dtf of the rows (time-optimal problems)."""
+        numVeh, dim, numCols = self.model['numVeh'], self.model['dim'], self._numCols
+        first = self._rv_parts()[1]
+        K, rows = blk.shape[:2]
+        free = blk[..., first:first + numCols].reshape(K, rows, dim * numCols)
+        J4 = np.zeros((K, rows, numVeh, dim * numCols))
+        kk = np.arange(K)
+        for own, sg in zip(owner, sign):
+            m = own < numVeh
+            J4[kk[m], :, own[m], :] += sg * free[m]
+        J = J4.reshape(K * rows, numVeh * dim * numCols)
+        if not self._timeopt():
+            return J
+        D = np.zeros((numVeh + 1, dim, blk.shape[3]))
+        D[:numVeh] = self._dY_dtf().reshape(numVeh, dim, -1)
+        Dk = sum(sg * D[np.minimum(own, numVeh)] for own, sg in zip(owner, sign))   # [K][dim][deg+1]
+        t = np.einsum('krci,kci->kr', blk, Dk)
+        if dtf is not None:
+            t = t + dtf
+        return np.hstack((J, t.reshape(-1, 1)))
+
+    def _temporal_sep_jac_exact(self, x):
+        x = np.asarray(x, dtype=float)
+        with_obs = self.pointObstacles is not None
+        ctx = self._ctx(with_obs)
+        n_obj = ctx.n_veh + ctx.n_obs
+        if n_obj < 2:
+            return np.zeros((0, x.size))
+        Y0 = self.reshapeVectors(x[None])
+        blk = ctx.temporal_sep_jac(Y0)[0]                                   # [P][2n+R+1][dim][deg+1]
+        P = blk.shape[0]
+        if self.separationRows in ('min', 'active'):
+            k = 1 if self.separationRows == 'min' else self._active_k()
+            idx = ctx.temporal_sep_active(Y0, self.model['maxSep'], k, with_index=True)[1][0].reshape(P, k)
+            blk = blk[np.arange(P)[:, None], idx]
+        pa, pb = np.triu_indices(n_obj, 1)
+        return self._scatter_exact(blk, (pa, pb), (1.0, -1.0))
+
+    def _jac_vehicle_exact(self, x, family):
+        x = np.asarray(x, dtype=float)
+        Y0 = self.reshapeVectors(x[None])
+        tf = float(self._tf_of(x))
+        c = self._ctx(False)
+        if family == 'ang':
+            if self.model['dim'] != 2:
+                raise ValueError('The input curve must be two dimensional,\n'
+                                 'instead it is {} dimensional'.format(self.model['dim']))
+            blk, dtf = c.ang_rate_jac(Y0, tf)
+        else:
+            blk, dtf = c.speed_jac(Y0, tf, family == 'vmax')
+        N = self.model['numVeh']
+        return self._scatter_exact(blk[0], (np.arange(N),), (1.0,), dtf[0])
 
     # ------------------------------------------------------------------ x <-> y
     def generateGuess(self, std=0, seed=None):

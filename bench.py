@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the constraint-evaluation hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3] [--full [--no-cpu]]
 
 Metric (BASELINE.json): constraint-evals/s.  One "constraint-eval" = one evaluation, for
 one optimisation vector x, of every constraint family of the configuration: the temporal
@@ -20,16 +20,22 @@ no data-path collective (each rank evaluates the FD batch of its own seeded swar
 scaling.  `--mode pairs` is the partitioned form: ONE batch, the pair lists split over the
 ranks, one RCCL all-gather of the per-pair minima.
 
-Output: ONE JSON line from rank 0 (contract in the task description) carrying also
+Output: ONE JSON line from rank 0 carrying also
   roofline     -- for the kernel that dominates the step's device time: algorithmic bytes
                   per launch / mean launch duration measured with HIP events on the
-                  launch stream inside the timed region, against the 8 TB/s HBM peak and
-                  against this box's measured copy / fill bandwidth;
-  kernels      -- the same figures for every kernel of the step;
+                  launch stream inside the timed region, against the 8 TB/s HBM peak
+                  (--full: and against this box's measured copy / fill bandwidth);
+  kernels      -- the same figures for the dominant kernel (--full: for every kernel of the step,
+                  from a replay of the steps after the timed region).
+
+A plain run sets up, spins the clocks up, warms up, times the K steps, writes --dump-outputs and
+prints the line.  Everything else is measured or checked only with --full:
   parity_check -- the device buffers of the last timed step against the CPU oracle on a sample
                   of rows (first, last, one per XCD residue);
   cpu_baseline -- the CPU oracle (oracle/, a C port of the reference path) timed on this
-                  box's host on a bounded sample of the same workload.
+                  box's host on a bounded sample of the same workload;
+  variants, strong_scaling_proxy, configs (every other BASELINE.json configuration, each a
+  child process), config.rows_structured, and the per-kernel replay above.
 """
 import argparse
 import json
@@ -56,7 +62,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--workload", default="C3", choices=["C2", "C2_file", "C3", "C4", "C5"])
     ap.add_argument("--batch", type=int, default=0, help="rows per step (default n_x + 1)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline and parity_check legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, also measure and check everything else: the per-kernel replay, "
+                         "measured HBM peaks, parity_check, cpu_baseline, variants, strong_scaling_proxy, configs and "
+                         "rows_structured (the --no-* options below trim this)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline and parity_check legs")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-gjk", action="store_true", help="Bernstein sweeps only")
     ap.add_argument("--event-period", type=int, default=0,
@@ -66,7 +76,7 @@ def parse():
                          "own); a timed launch still does not overlap its neighbours: every launch 0.1886 ms per step, every "
                          "4th 0.1865, none 0.1863 at C3")
     ap.add_argument("--no-variants", action="store_true",
-                    help="skip the `variants` legs after the timed region (history off, moving x, structured FD step): "
+                    help="--full: skip the `variants` legs after the timed region (history off, moving x, structured FD step): "
                          "profile runs, where their launches of the same kernel would blur its average")
     ap.add_argument("--fd-dedup", action="store_true",
                     help="reuse row 0's gjkNew results for bit-identical hull pairs (obtg_ctx_set_fd_dedup); "
@@ -104,14 +114,14 @@ def parse():
     ap.add_argument("--ang-order", default="fast", choices=["fast", "elevate_first", "reference", "exact"],
                     help="DEG_ELEV > 0: obtg_ctx_set_ang_rate_order (fast = the headline; exact = plus the double-double "
                          "recompute of near-stop vehicles' rows)")
-    ap.add_argument("--no-proxy", action="store_true", help="skip the strong_scaling_proxy leg of a 1-GPU batch-mode run")
+    ap.add_argument("--no-proxy", action="store_true", help="--full: skip the strong_scaling_proxy leg of a 1-GPU batch-mode run")
     ap.add_argument("--one-device", action="store_true",
                     help="rehearsal only: every rank uses device 0 (needs --backend gloo)")
     ap.add_argument("--mindist-legs", default=None,
                     help="--mode mindist: comma-separated legs to run (reference_algorithm, jacobian_list, robust, jacobian_list_robust, "
                          "curve_polygon_reference_algorithm, curve_polygon_robust); default all (profile runs pick the kernels they want)")
     ap.add_argument("--no-configs", action="store_true",
-                    help="1-GPU C3 batch-mode run: skip the `configs` block (every other BASELINE.json configuration measured by a "
+                    help="--full, 1-GPU C3 batch-mode run: skip the `configs` block (every other BASELINE.json configuration measured by a "
                          "child process of this run: C1_text, C2, C2_file, C4, C5, C5_mindist -- ms per step, the dominant kernel's "
                          "HIP-event duration, algorithmic bytes, fraction of the HBM peak, parity against the oracle on sampled rows)")
     ap.add_argument("--config-leg", action="store_true",
@@ -342,8 +352,8 @@ def main():
             if rank == 0 and line is not None:
                 line["modes"] = modes
         if rank == 0 and line is not None and line.get("value") is not None:
-            if (args.workload == "C3" and args.mode == "batch" and world == 1 and not args.no_configs and not args.config_leg
-                    and not args.no_cpu and not args.batch):
+            if (args.full and args.workload == "C3" and args.mode == "batch" and world == 1 and not args.no_configs
+                    and not args.config_leg and not args.no_cpu and not args.batch):
                 line["configs"] = config_legs(args)
             print(json.dumps(line))
             sys.stdout.flush()
@@ -585,17 +595,22 @@ def step_bench(args, env):
     # sample rows of the buffers the last timed step left behind, for the parity check (before anything rewrites them)
     status_nonok = int((g_stat != 0).sum().item()) if use_gjk else 0
     snap = None
-    if rank == 0 and not args.no_cpu and args.gpus == 1:
+    check_cpu = args.full and rank == 0 and not args.no_cpu and args.gpus == 1
+    if check_cpu:
         dev_out = dict(Y=dY, sep=o_sep, speed=o_sp, ang=o_an)
         if use_gjk:
             dev_out.update(flag=g_flag, dist=g_dist, p1=g_p1)
         snap = parity_snapshot(dev_out, B)
-    # the other kernels: the same steps once more with events on every launch, outside the timed region
-    prof(True)
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    stats = kstats()
+    if args.full:
+        # the other kernels: the same steps once more with events on every launch, outside the timed region
+        prof(True)
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        stats = kstats()
+    else:
+        # which kernels a step launches: the warm-up's events (every launch); figures for the dominant kernel only
+        stats = dict(wstats)
     stats[dom_name] = stats_timed[dom_name]
     prof(False)
 
@@ -652,7 +667,7 @@ def step_bench(args, env):
     nv = max(args.steps, 200)
     nv = max(20, min(nv, int(2000.0 / max(1e3 * elapsed / args.steps, 1e-3))))      # (a 26 ms step: 76 steps per run, not 500)
     can_structured = everything and o_an is not None and row_begin == 0
-    if use_view and use_gjk and args.mode == "batch" and not args.no_variants and not lean:
+    if args.full and use_view and use_gjk and args.mode == "batch" and not args.no_variants and not lean:
         variants = {}
         ctx.set_gjk_history(False)
         variants["history_off"] = entry(timed(nv, lambda i: step_at(d0.data_ptr())), B,
@@ -685,7 +700,7 @@ def step_bench(args, env):
                 structured()
                 torch.cuda.synchronize()
                 s_par = None
-                if rank == 0 and not args.no_cpu and args.gpus == 1:
+                if check_cpu:
                     s_snap = parity_snapshot(dict(Y=dY, sep=o_sep, speed=o_sp, ang=o_an, flag=g_flag, dist=g_dist, p1=g_p1), B)
                     s_par = parity_check(s_snap, N, d, n, R, statics, pa, pb, use_gjk, max_sep, vmax, wmax, tfv)
                     s_par = {k: s_par[k] for k in ("rows", "max_rel", "max_rel_elementwise", "flags_equal", "gjk_dist_max_rel", "ok")}
@@ -712,7 +727,8 @@ def step_bench(args, env):
     # the first ceil(B / G) rows of the same view, G = 1, 2, 4, 8 (the rows every rank of `--mode rows` would own, up to
     # which vehicle they perturb).  efficiency = t(B) / (G t(B / G)): the speed-up G GPUs would show over one, divided by
     # G, if nothing but the kernels' small-batch behaviour stood in the way (no collective on this path).
-    if use_view and use_gjk and args.mode == "batch" and world == 1 and not args.no_proxy and not args.no_variants and not lean:
+    if (args.full and use_view and use_gjk and args.mode == "batch" and world == 1 and not args.no_proxy and not args.no_variants
+            and not lean):
         proxy = {"rows": [], "what": "the step on the first ceil(B / G) rows of the view; efficiency = t(B) / (G t(B/G))"}
         base = {}
         for G in (1, 2, 4, 8):
@@ -760,9 +776,10 @@ def step_bench(args, env):
         # DEG_ELEV > 0: the separation rows and the speed / angular-rate rows share a launch (k_sep_dynamics_elev, booked as
         # "temporal_sep"): both families' bytes, the control points counted once
         by["temporal_sep"] += by["ang_rate"] - 8 * N * d * (n + 1)
+    launches_per_step = sum(1 for name in KNAMES if stats.get(name, (0.0, 0))[1] > 0)
     for name in KNAMES:
         ms, cnt = stats.get(name, (0.0, 0))
-        if cnt == 0:
+        if cnt == 0 or (name != dom_name and not args.full):
             continue
         avg_ms = ms / cnt
         gbs = B * by[name] / (avg_ms * 1e-3) / 1e9
@@ -799,20 +816,21 @@ def step_bench(args, env):
     if dom["kernel"] == "gjk":
         note = ("gjkNew sweep: VALU-issue bound by nature (PMC at C3: ~85 % VALU busy, LDS 34 %), reported against "
                 "HBM as the contract asks; see DESIGN.md 4.3")
-    copy_gbs, fill_gbs = measured_peaks(torch, dev) if not lean else (float("nan"), float("nan"))
+    peaks = args.full and not lean
+    copy_gbs, fill_gbs = measured_peaks(torch, dev) if peaks else (float("nan"), float("nan"))
     roofline = dict(bound=bound, kernel=dom["kernel"], achieved=dom["achieved_gbs"], peak=HBM_PEAK_GBS,
                     unit="GB/s", frac=dom["frac"], traffic=traffic, traffic_source=traffic_source, issue=issue,
                     bound_note=("achieved / peak / frac are the HBM figures the contract asks for; `bound` names the roof the "
                                 "counters say binds this launch (valu_issue: the launch fills a larger share of the chip's VALU "
                                 "issue slots than of the HBM peak -- DESIGN.md 4.7)"),
-                    peak_measured=round(copy_gbs, 1) if not lean else None,
-                    frac_measured=round(dom["achieved_gbs"] / copy_gbs, 5) if not lean else None,
-                    peak_measured_write_only=round(fill_gbs, 1) if not lean else None,
+                    peak_measured=round(copy_gbs, 1) if peaks else None,
+                    frac_measured=round(dom["achieved_gbs"] / copy_gbs, 5) if peaks else None,
+                    peak_measured_write_only=round(fill_gbs, 1) if peaks else None,
                     peak_measured_note="this box, torch copy_ (read+write bytes) / fill_ of 1 GiB, HIP events",
                     note=note, step_achieved=round(B * total_bytes / (ms_per_step * 1e-3) / 1e9, 2))
 
     cpu = cpu_np = parity = None
-    if rank == 0 and not args.no_cpu and args.gpus == 1:
+    if check_cpu:
         parity = parity_check(snap, N, d, n, R, statics, pa, pb, use_gjk, max_sep, vmax, wmax, tfv)
         parity["status_nonok"] = status_nonok
         cpu = cpu_baseline(args, N, d, n, R, Y, statics, pa, pb, use_gjk, max_sep, vmax, wmax, tfv)
@@ -843,7 +861,8 @@ def step_bench(args, env):
     # evaluates the unperturbed row, the source of its streams, and per row of its range only what that row's vehicle
     # touches): same barrier + MAX-over-ranks timing, the checksums over every rank's rows must be the brute-force ones
     rows_structured = None
-    if args.mode == "rows" and everything and o_an is not None and use_view and use_gjk and not args.no_variants and B > 0:
+    if (args.full and args.mode == "rows" and everything and o_an is not None and use_view and use_gjk and not args.no_variants
+            and B > 0):
         try:
             def structured_rows():
                 ctx.constraint_sweep_fd_structured_dev(d0.data_ptr(), 1, synth.FD_STEP, d_tf.data_ptr(), B, max_sep,
@@ -914,7 +933,7 @@ def step_bench(args, env):
                        "row_range_of_rank0": [row_begin, B] if args.mode == "rows" else None, "rows_structured": rows_structured,
                        "gather_minima": args.gather_minima if d_min is not None else None, "allgather_bytes": gather_bytes,
                        "gather_check": gather_check, "checksum": checksum,
-                       "launches_per_step": len(kernels), "streams": 2 if two_streams else 1, "stream": stream_note,
+                       "launches_per_step": launches_per_step, "streams": 2 if two_streams else 1, "stream": stream_note,
                        "ranks_seen": ranks_seen, "backend": (args.backend if use_dist else None), "devices": devices,
                        "gjk_status_note": status_note,
                        "evals_per_step_per_gpu": B, "alg_bytes_per_eval": total_bytes,
@@ -1207,7 +1226,7 @@ def mindist_mode(args, rank):
     legs = ("reference_algorithm", "jacobian_list", "curve_polygon_reference_algorithm", "provider_end_to_end") if args.config_leg else None
     if args.mindist_legs:
         legs = tuple(x.strip() for x in args.mindist_legs.split(",") if x.strip())
-    line = mindist_line(args, cpu=not args.no_cpu, legs=legs)
+    line = mindist_line(args, cpu=args.full and not args.no_cpu, legs=legs)
     if rank == 0:
         print(json.dumps(line))
         sys.stdout.flush()
@@ -1387,13 +1406,14 @@ def c1_text_mode(args, rank):
         dump_outputs(args.dump_outputs, {"temporal_sep": F[0], "speed": F[1], "ang_rate": F[2]})
     B = x.size + 1
     ms = 1e3 * elapsed / args.steps
-    # the kernels behind it: HIP events on every launch of a replay
-    ctxs = [bo._ctx(True), bo._ctx(False)]
+    # the kernels behind it (--full): HIP events on every launch of a replay
+    ctxs = [bo._ctx(True), bo._ctx(False)] if args.full else []
     for cx in ctxs:
         cx.set_profiling(True)
         cx.reset_kernel_stats()
-    for _ in range(args.steps):
-        step()
+    if ctxs:
+        for _ in range(args.steps):
+            step()
     kernels = []
     N, d, n, R, P, L = 1, 2, 10, 0, 10, 21
     by = {"temporal_sep": 8 * 5 * d * (n + 1) + 8 * P * L, "speed": 8 * N * d * (n + 1) + 8 * N * L,
@@ -1409,7 +1429,7 @@ def c1_text_mode(args, rank):
         cx.set_profiling(False)
     dom = max(kernels, key=lambda k: k["avg_ms"]) if kernels else None
     parity = cpu = None
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         from oracle import oracle as O
         O.build()
         X, _ = bo._fd_rows(x)
@@ -1452,7 +1472,7 @@ def c1_text_mode(args, rank):
                                "22-iteration solve (BASELINE.md 2)"},
             "roofline": (dict(bound="launch latency", kernel=dom["kernel"], achieved=dom["achieved_gbs"], peak=HBM_PEAK_GBS, unit="GB/s",
                               frac=dom["frac"], traffic=None) if dom else None),
-            "kernels": kernels, "parity_check": parity, "cpu_baseline": cpu}))
+            "kernels": kernels if args.full else None, "parity_check": parity, "cpu_baseline": cpu}))
         sys.stdout.flush()
     if parity is not None and not parity["ok"]:
         raise SystemExit("bench.py --mode c1text: the closures DISAGREE with the reference fixture / the oracle: %s" % json.dumps(parity))
@@ -1472,7 +1492,7 @@ def config_legs(args):
     out = {}
     t_all = time.perf_counter()
     for name, extra in legs:
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--config-leg", "--cpu-seconds", "2.5"] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--config-leg", "--cpu-seconds", "2.5"] + extra
         t0 = time.perf_counter()
         try:
             p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=150, text=True)

@@ -137,7 +137,7 @@ def test_bench_rows_mode_two_ranks_tile_the_iteration():
     # the same ranges through the structured step (obtg_constraint_sweep_fd_structured_rows_dev): bit-identical rows, so
     # the sums over all ranks' rows are the brute-force sums exactly
     assert one["config"]["rows_structured"] is None                        # (--no-variants)
-    args_v = [a for a in args if a != "--no-variants"]
+    args_v = [a for a in args if a != "--no-variants"] + ["--full"]
     for g in (1, 2, 3):
         line = _bench(["--gpus", str(g)] + (["--backend", "gloo", "--one-device"] if g > 1 else []) + args_v)
         rs = line["config"]["rows_structured"]
@@ -214,11 +214,31 @@ def test_bench_dump_outputs_same_run_to_run(tmp_path):
     assert np.isfinite(np.load(os.path.join(dirs[0], "speed.npy"))).all()
 
 
+def test_plain_bench_line_is_lean():
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: the headline line with the contract's keys, the
+    dominant kernel's roofline from the timed region's events, and nothing measured or checked beyond it."""
+    d = _bench(["--gpus", "1", "--steps", "12", "--warmup", "3"])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "roofline", "kernels"):
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == 12 and d["warmup"] == 3 and d["higher_is_better"] is True
+    assert d["unit"] == "constraint-evals/s" and d["dtype"] == "f64"
+    assert d["config"]["workload"].startswith("C3") and d["config"]["launches_per_step"] == 1
+    assert abs(d["value"] - d["config"]["evals_per_step_per_gpu"] / (d["ms_per_step"] * 1e-3)) < 2e-3 * d["value"]
+    r = d["roofline"]
+    assert r["kernel"] == "pair_sweep" and r["peak"] == 8000.0 and 0.2 < r["frac"] < 1.0 and r["peak_measured"] is None
+    assert [k["kernel"] for k in d["kernels"]] == ["pair_sweep"] and d["kernels"][0]["in_timed_region"] is True
+    assert d["kernels"][0]["launches"] == 12                 # events on every launch of the 12 timed steps, no replay
+    assert "configs" not in d
+    for k in ("parity_check", "cpu_baseline", "cpu_baseline_numpy", "variants", "strong_scaling_proxy"):
+        assert d[k] is None, k
+
+
 def test_default_bench_line_keeps_the_contract():
-    """`python bench.py` as the driver runs it (shortened): ONE JSON line with the contract's keys, the C3 workload as one
-    launch per step, `roofline` and `cpu_baseline` objects complete, and the bench's own check of its device buffers
-    against the oracle green."""
-    d = _bench(["--steps", "12", "--warmup", "3", "--cpu-seconds", "1.5"])
+    """`python bench.py --full` (shortened): ONE JSON line with the contract's keys, the C3 workload as one launch per
+    step, `roofline` and `cpu_baseline` objects complete, and the bench's own check of its device buffers against the
+    oracle green."""
+    d = _bench(["--full", "--steps", "12", "--warmup", "3", "--cpu-seconds", "1.5"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k

@@ -85,7 +85,8 @@ const char* obtg_strerror(int code);
  *   6  round 6: nothing changed meaning; new: obtg_source_hash, obtg_libm_pow_matches.
  *   7  nothing changed meaning; new: the exact derivatives obtg_temporal_sep_jac[_dev], obtg_speed_jac[_dev],
  *      obtg_ang_rate_jac[_dev], obtg_euclidean_grad, obtg_deriv_energy_grad and the kernel-stats id OBTG_K_JAC
- *      (OBTG_K_COUNT moved from 8 to 9). */
+ *      (OBTG_K_COUNT moved from 8 to 9).
+ *      Later, still 7: new: the collision checks obtg_coll_check, obtg_coll_check2poly (timed under OBTG_K_MIN_DIST). */
 #define OBTG_ABI_VERSION 7
 int obtg_abi_version(void);
 
@@ -455,6 +456,26 @@ int obtg_min_dist2poly(obtg_ctx*, const double* curves, int n_curves, int K,
                        const int* pair_curve, const int* pair_poly, int n_pairs,
                        double eps, int max_iter, int md_cap, int max_depth, int max_nodes,
                        double* res, int* info, int* status);
+/* ---- curve <-> curve / curve <-> polygon collision check --------------------------------
+ * Bezier.collCheck -> _collCheckBez2Bez (bezier.py:859-862, 1561-1614) and Bezier.collCheck2Poly ->
+ * _collCheckBez2Poly (bezier.py:864-867, 1617-1651): depth-first subdivision at 0.5 that asks gjkNew for its flag
+ * alone and stops at the first separated pair of hulls.  Layouts as obtg_min_dist / obtg_min_dist2poly; at most 16
+ * control points per curve and 16 vertices per polygon (more: OBTG_ERR_UNSUPPORTED).
+ * res[n_pairs] is the reference's return value: curve <-> curve 1 (hulls separated: no collision), -1 (its `cnt > 100`),
+ * 0.0 or the smallest end-point distance met on the way; curve <-> polygon 1 or 0.  `cnt > 100` is part of that value,
+ * not a status: there is no max_depth.  info[n_pairs][4] (nullable) = nodes visited (every one makes one gjkNew
+ * call), gjkNew calls, max depth (the reference's cnt, at most 100), status; status[n_pairs]: OBTG_MD_OK,
+ * OBTG_MD_NODE_CAP (max_nodes visited: the reference does not return in reasonable time) or OBTG_MD_GJK_CAP (an
+ * inner gjkNew that never returns: a proven cycle or md_cap rounds).  res is 0 beside a status other than OBTG_MD_OK. */
+int obtg_coll_check(obtg_ctx*, const double* curves, int n_curves, int K,
+                    const int* pair_a, const int* pair_b, int n_pairs,
+                    double eps, int max_iter, int md_cap, int max_nodes,
+                    double* res, int* info, int* status);
+int obtg_coll_check2poly(obtg_ctx*, const double* curves, int n_curves, int K,
+                         const double* pts, int n_pts, const int* poly_off, int n_poly,
+                         const int* pair_curve, const int* pair_poly, int n_pairs,
+                         int max_iter, int md_cap, int max_nodes,
+                         double* res, int* info, int* status);
 
 /* ---- single-curve Bernstein algebra (the Bezier object's methods, batched over rows) ----
  * obtg_bern_elev:   Bezier.elev(R)      bezier.py:469-495   in[rows][n+1]   -> out[rows][n+R+1]

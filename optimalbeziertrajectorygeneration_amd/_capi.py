@@ -102,6 +102,8 @@ _SIGNATURES = {
     "obtg_min_dist2poly": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _d, _i, _i, _i, _i, _vp, _vp, _vp]),
     "obtg_min_dist2poly_robust": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _d, _i, _vp, _vp, _vp]),
     "obtg_gjk_true_pairs": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_coll_check": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _d, _i, _i, _i, _vp, _vp, _vp]),
+    "obtg_coll_check2poly": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "obtg_bern_elev": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "obtg_bern_diff": (_i, [_vp, _vp, _i, _i, _d, _vp]),
     "obtg_bern_mul": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
@@ -871,6 +873,38 @@ class Context(object):
                                                         off.shape[0] - 1, _ptr(pc), _ptr(pp), n, float(eps), int(max_nodes),
                                                         _ptr(res), _ptr(info), _ptr(status)), "obtg_min_dist2poly_robust")
         return dict(res=res, nodes=info[:, 0], levels=info[:, 1], frontier=info[:, 2], status=status)
+
+    def coll_check(self, curves, pair_a, pair_b, eps=1e-9, max_iter=128, md_cap=4096, max_nodes=200000):
+        """_collCheckBez2Bez (bezier.py:1561-1614) on every pair (obtg_coll_check): res[n] is the reference's return value --
+        1 (no collision), -1 (its cnt > 100), 0.0 or the smallest end-point distance met -- where status is MD_OK (0 beside any
+        other status).  curves[n_curves][3][K], K <= 16."""
+        curves = _f64(curves)
+        n_curves, _, K = curves.shape
+        pa, pb = _i32(pair_a), _i32(pair_b)
+        n = pa.shape[0]
+        res = np.zeros(n)
+        info = np.zeros((n, 4), np.int32)
+        status = np.zeros(n, np.int32)
+        self._check(self._lib.obtg_coll_check(self._h, _ptr(curves), n_curves, K, _ptr(pa), _ptr(pb), n, float(eps), int(max_iter),
+                                              int(md_cap), int(max_nodes), _ptr(res), _ptr(info), _ptr(status)), "obtg_coll_check")
+        return dict(res=res, nodes=info[:, 0], gjk_calls=info[:, 1], depth=info[:, 2], status=status)
+
+    def coll_check2poly(self, curves, pts, off, pair_curve, pair_poly, max_iter=128, md_cap=4096, max_nodes=200000):
+        """_collCheckBez2Poly (bezier.py:1617-1651) on every (curve, polygon) pair (obtg_coll_check2poly): res[n] is 1 (no
+        collision) or 0 where status is MD_OK.  Polygons as in min_dist2poly, at most 16 vertices each; K <= 16."""
+        curves = _f64(curves)
+        n_curves, _, K = curves.shape
+        pts = _f64(pts).reshape(-1, 3)
+        off = _i32(off)
+        pc, pp = _i32(pair_curve), _i32(pair_poly)
+        n = pc.shape[0]
+        res = np.zeros(n)
+        info = np.zeros((n, 4), np.int32)
+        status = np.zeros(n, np.int32)
+        self._check(self._lib.obtg_coll_check2poly(self._h, _ptr(curves), n_curves, K, _ptr(pts), pts.shape[0], _ptr(off),
+                                                   off.shape[0] - 1, _ptr(pc), _ptr(pp), n, int(max_iter), int(md_cap),
+                                                   int(max_nodes), _ptr(res), _ptr(info), _ptr(status)), "obtg_coll_check2poly")
+        return dict(res=res, nodes=info[:, 0], gjk_calls=info[:, 1], depth=info[:, 2], status=status)
 
     def gjk_true_pairs(self, pts, off, pair_a, pair_b, eps=1e-10, max_iter=64):
         """True hull distances (obtg_gjk_true_pairs; not gjkNew).  status 0: converged with the certificate

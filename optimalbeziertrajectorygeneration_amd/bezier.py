@@ -251,15 +251,53 @@ class Bezier(BezierParams):
         res = r['res'][0]
         return (float(res[0]), float(res[1]), res[2:].copy())
 
+    # ---- collision checks (bezier.py:859-867)
+    def collCheck(self, otherCurve, max_nodes=4000000, robust=False):
+        """What the reference's `_collCheckBez2Bez` returns (bezier.py:1561-1614), step for step: 1 when no collision is
+        found -- so test `== 1` -- else -1 (its recursion counter passed 100), 0.0 or the smallest end-point distance met
+        on the way (a value below 1 does NOT mean that the curves touch).  A search the reference does not come back from
+        raises, as minDist does.  robust=True is NOT the reference's value: 1 when obtg_min_dist_robust's true minimum
+        distance is above its own "the curves touch" tolerance, 1e-9 x the largest coordinate, else 0."""
+        if self.dim < 2 or self.dim > 3 or otherCurve.dim < 2 or otherCurve.dim > 3:
+            raise ValueError('Both curves must be either 2D or 3D, not {}D and {}D.'.format(self.dim, otherCurve.dim))
+        if self.deg != otherCurve.deg:
+            raise ValueError('collCheck needs curves of equal degree here (got {} and {})'.format(self.deg, otherCurve.deg))
+        curves = np.stack([self._padded(), otherCurve._padded()])
+        if robust:
+            r = _ctx().min_dist_robust(curves, [0], [1], eps=1e-9, max_nodes=max_nodes)
+            if r['status'][0] != _capi.MD_OK:
+                raise RuntimeError('collCheck(robust): search budget exhausted (curves coincide over a stretch?)')
+            return 1 if r['res'][0][0] > 1e-9 * np.abs(curves).max() else 0
+        r = _ctx().coll_check(curves, [0], [1], max_nodes=max_nodes)
+        _raise_md(r['status'][0], 'collCheck')
+        v = float(r['res'][0])
+        return int(v) if v in (1.0, -1.0) else v
 
-def _raise_md(status):
+    def collCheck2Poly(self, poly, max_nodes=4000000, robust=False):
+        """What the reference's `_collCheckBez2Poly` returns (bezier.py:1617-1651), step for step: 1 when no collision is
+        found, else 0.  A search the reference does not come back from raises, as minDist2Poly does.  robust=True is NOT
+        the reference's value: 1 when obtg_min_dist2poly_robust's true minimum distance to the polygon's convex hull is
+        above 1e-9 x the largest coordinate, else 0."""
+        poly = np.asarray(poly, dtype=float)
+        if robust:
+            r = _ctx().min_dist2poly_robust(self._padded()[None], poly, [0, poly.shape[0]], [0], [0], eps=1e-9,
+                                            max_nodes=max_nodes)
+            if r['status'][0] != _capi.MD_OK:
+                raise RuntimeError('collCheck2Poly(robust): search budget exhausted')
+            return 1 if r['res'][0][0] > 1e-9 * max(np.abs(self.cpts).max(), np.abs(poly).max()) else 0
+        r = _ctx().coll_check2poly(self._padded()[None], poly, [0, poly.shape[0]], [0], [0], max_nodes=max_nodes)
+        _raise_md(r['status'][0], 'collCheck2Poly')
+        return int(r['res'][0])
+
+
+def _raise_md(status, what='minDist'):
     if status == _capi.MD_OK:
         return
     if status == _capi.MD_DEPTH_CAP:
-        raise RecursionError('minDist: subdivision deeper than max_depth (the reference overflows its stack here)')
+        raise RecursionError(what + ': subdivision deeper than max_depth (the reference overflows its stack here)')
     if status == _capi.MD_NODE_CAP:
-        raise RuntimeError('minDist: node budget exhausted (the reference does not return on this input)')
-    raise RuntimeError('minDist: an inner gjkNew did not converge (the reference loops forever here)')
+        raise RuntimeError(what + ': node budget exhausted (the reference does not return on this input)')
+    raise RuntimeError(what + ': an inner gjkNew did not converge (the reference loops forever here)')
 
 
 class RationalBezier(BezierParams):

@@ -234,7 +234,7 @@ const char* obtg_abi_symbols(void)
         "obtg_temporal_sep_fd\0obtg_temporal_sep_fd_dev\0obtg_one_vs_many_min\0obtg_one_vs_many_min_dev\0"
         "obtg_temporal_sep_dev\0obtg_temporal_sep_min_dev\0obtg_speed_dev\0obtg_ang_rate_dev\0obtg_dynamics_dev\0"
         "obtg_fd_batch_dev\0obtg_fd_view_begin\0obtg_fd_view_begin_rows\0obtg_fd_view_end\0obtg_fd_forms_on_the_fly\0obtg_pair_sweep_fd_dev\0obtg_dynamics_fd_dev\0obtg_gjk_pairs\0obtg_ctx_set_polygons\0obtg_ctx_set_hull_pairs\0"
-        "obtg_ctx_set_fd_dedup\0obtg_ctx_set_gjk_history\0obtg_pair_sweep_dev\0obtg_constraint_sweep_dev\0obtg_constraint_sweep_fd_structured_dev\0obtg_constraint_sweep_fd_structured_rows_dev\0obtg_gjk_swarm_dev\0obtg_gjk_swarm\0obtg_min_dist\0obtg_min_dist_robust\0obtg_min_dist2poly\0obtg_min_dist2poly_robust\0obtg_gjk_true_pairs\0"
+        "obtg_ctx_set_fd_dedup\0obtg_ctx_set_gjk_history\0obtg_pair_sweep_dev\0obtg_constraint_sweep_dev\0obtg_constraint_sweep_fd_structured_dev\0obtg_constraint_sweep_fd_structured_rows_dev\0obtg_gjk_swarm_dev\0obtg_gjk_swarm\0obtg_min_dist\0obtg_min_dist_robust\0obtg_min_dist2poly\0obtg_min_dist2poly_robust\0obtg_gjk_true_pairs\0obtg_coll_check\0obtg_coll_check2poly\0"
         "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_eval\0"
         "obtg_euclidean_obj\0obtg_accel_obj\0obtg_jerk_obj\0"
         "obtg_temporal_sep_jac\0obtg_temporal_sep_jac_dev\0obtg_speed_jac\0obtg_speed_jac_dev\0obtg_ang_rate_jac\0obtg_ang_rate_jac_dev\0obtg_euclidean_grad\0obtg_deriv_energy_grad\0"
@@ -1333,6 +1333,91 @@ int obtg_min_dist2poly(obtg_ctx* c, const double* curves, int n_curves, int K, c
     if ((rc = d2h_copy(c, hinfo.data(), m[3].p, sizeof(int) * 4 * n_pairs))) return rc;
     rc = d2h(c, res, c->ws_out.p, sizeof(double) * 5 * n_pairs);
     if (rc) return rc;
+    if (info) std::memcpy(info, hinfo.data(), sizeof(int) * 4 * n_pairs);
+    if (status) for (int k = 0; k < n_pairs; ++k) status[k] = hinfo[4 * k + 3];
+    return OBTG_OK;
+}
+
+// all-z-are-+0 test of curves[n_curves][3][K] (2-D curves arrive padded with a zero z row): then the planar gjkNew machine runs
+static bool curves_planar(const double* curves, int n_curves, int K)
+{
+    for (int i = 0; i < n_curves; ++i) {
+        const double* z = curves + ((size_t)i * 3 + 2) * K;
+        for (int j = 0; j < K; ++j) if (z[j] != 0.0 || std::signbit(z[j])) return false;
+    }
+    return true;
+}
+
+int obtg_coll_check(obtg_ctx* c, const double* curves, int n_curves, int K, const int* pair_a, const int* pair_b,
+                    int n_pairs, double eps, int max_iter, int md_cap, int max_nodes, double* res, int* info, int* status)
+{
+    if (!check_ctx(c) || !curves || n_curves < 1 || n_pairs < 0) return OBTG_ERR_ARG;
+    if (n_pairs > 0 && (!pair_a || !pair_b || !res)) return OBTG_ERR_ARG;
+    if (K < 2 || max_iter < 1 || md_cap < 1 || max_nodes < 1) return OBTG_ERR_ARG;
+    for (int k = 0; k < n_pairs; ++k)
+        if (pair_a[k] < 0 || pair_a[k] >= n_curves || pair_b[k] < 0 || pair_b[k] >= n_curves) return OBTG_ERR_ARG;
+    if (!coll_check_supported(K, 0)) return OBTG_ERR_UNSUPPORTED;
+    if (n_pairs == 0) return OBTG_OK;
+    (void)hipSetDevice(c->device);
+    DevBuf* m = c->ws_misc;
+    int rc = h2d(c, c->ws_in, curves, sizeof(double) * 3 * (size_t)K * n_curves);
+    if (rc) return rc;
+    if ((rc = h2d(c, m[1], pair_a, sizeof(int) * n_pairs))) return rc;
+    if ((rc = h2d(c, m[2], pair_b, sizeof(int) * n_pairs))) return rc;
+    const bool planar = curves_planar(curves, n_curves, K);
+    if ((rc = m[5].reserve(sizeof(double) * coll_check_stack_doubles(c, K, n_pairs, false, planar)))) return rc;
+    if ((rc = c->ws_out.reserve(sizeof(double) * (size_t)n_pairs))) return rc;
+    if ((rc = m[3].reserve(sizeof(int) * 4 * (size_t)n_pairs))) return rc;
+    if ((rc = m[6].reserve(sizeof(int)))) return rc;
+    rc = launch_coll_check(c, c->ws_in.as<double>(), K, m[1].as<int>(), m[2].as<int>(), n_pairs, eps, max_iter, md_cap,
+                           max_nodes, m[5].as<double>(), c->ws_out.as<double>(), m[3].as<int>(), m[6].as<int>(),
+                           planar);
+    if (rc) return rc;
+    std::vector<int> hinfo((size_t)4 * n_pairs);
+    if ((rc = d2h_copy(c, hinfo.data(), m[3].p, sizeof(int) * 4 * n_pairs))) return rc;
+    if ((rc = d2h(c, res, c->ws_out.p, sizeof(double) * n_pairs))) return rc;
+    if (info) std::memcpy(info, hinfo.data(), sizeof(int) * 4 * n_pairs);
+    if (status) for (int k = 0; k < n_pairs; ++k) status[k] = hinfo[4 * k + 3];
+    return OBTG_OK;
+}
+
+int obtg_coll_check2poly(obtg_ctx* c, const double* curves, int n_curves, int K, const double* pts, int n_pts,
+                         const int* poly_off, int n_poly, const int* pair_curve, const int* pair_poly, int n_pairs,
+                         int max_iter, int md_cap, int max_nodes, double* res, int* info, int* status)
+{
+    if (!check_ctx(c) || !curves || !pts || n_curves < 1 || n_pairs < 0) return OBTG_ERR_ARG;
+    if (n_pairs > 0 && (!pair_curve || !pair_poly || !res)) return OBTG_ERR_ARG;
+    if (K < 2 || max_iter < 1 || md_cap < 1 || max_nodes < 1) return OBTG_ERR_ARG;
+    int rc = check_polys(poly_off, n_poly, n_pts);
+    if (rc) return rc;
+    for (int k = 0; k < n_pairs; ++k)
+        if (pair_curve[k] < 0 || pair_curve[k] >= n_curves || pair_poly[k] < 0 || pair_poly[k] >= n_poly)
+            return OBTG_ERR_ARG;
+    int max_K = 0;
+    for (int a = 0; a < n_poly; ++a) max_K = std::max(max_K, poly_off[a + 1] - poly_off[a]);
+    if (!coll_check_supported(K, max_K)) return OBTG_ERR_UNSUPPORTED;
+    if (n_pairs == 0) return OBTG_OK;
+    (void)hipSetDevice(c->device);
+    DevBuf* m = c->ws_misc;
+    auto soa = to_soa(pts, poly_off, n_poly);
+    if ((rc = h2d(c, c->ws_in, curves, sizeof(double) * 3 * (size_t)K * n_curves))) return rc;
+    if ((rc = h2d(c, c->ws_in2, soa.data(), soa.size() * sizeof(double)))) return rc;
+    if ((rc = h2d(c, m[0], poly_off, sizeof(int) * (n_poly + 1)))) return rc;
+    if ((rc = h2d(c, m[1], pair_curve, sizeof(int) * n_pairs))) return rc;
+    if ((rc = h2d(c, m[2], pair_poly, sizeof(int) * n_pairs))) return rc;
+    bool planar = curves_planar(curves, n_curves, K);
+    for (int i = 0; i < n_pts && planar; ++i) if (pts[3 * (size_t)i + 2] != 0.0 || std::signbit(pts[3 * (size_t)i + 2])) planar = false;
+    if ((rc = m[5].reserve(sizeof(double) * coll_check_stack_doubles(c, K, n_pairs, true, planar)))) return rc;
+    if ((rc = c->ws_out.reserve(sizeof(double) * (size_t)n_pairs))) return rc;
+    if ((rc = m[3].reserve(sizeof(int) * 4 * (size_t)n_pairs))) return rc;
+    if ((rc = m[6].reserve(sizeof(int)))) return rc;
+    rc = launch_coll_check2poly(c, c->ws_in.as<double>(), K, c->ws_in2.as<double>(), m[0].as<int>(), m[1].as<int>(),
+                                m[2].as<int>(), n_pairs, max_iter, md_cap, max_nodes, m[5].as<double>(),
+                                c->ws_out.as<double>(), m[3].as<int>(), m[6].as<int>(), max_K, planar);
+    if (rc) return rc;
+    std::vector<int> hinfo((size_t)4 * n_pairs);
+    if ((rc = d2h_copy(c, hinfo.data(), m[3].p, sizeof(int) * 4 * n_pairs))) return rc;
+    if ((rc = d2h(c, res, c->ws_out.p, sizeof(double) * n_pairs))) return rc;
     if (info) std::memcpy(info, hinfo.data(), sizeof(int) * 4 * n_pairs);
     if (status) for (int k = 0; k < n_pairs; ++k) status[k] = hinfo[4 * k + 3];
     return OBTG_OK;

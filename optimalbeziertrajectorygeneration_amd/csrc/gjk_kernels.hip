@@ -24,6 +24,7 @@
 #include "gjk_device.h"
 #include "gjk_true.h"
 #include "obtg_internal.h"
+#include "md_device.h"
 // the Bernstein sweep body that k_pair_sweep runs beside the GJK workgroups: same contraction
 // setting as in bern_kernels.hip, so that both units produce the same arithmetic
 #pragma clang fp contract(fast)
@@ -1602,14 +1603,6 @@ __device__ double hull_param(const double* c, int K, const V3& cl)
     return np_sum(q, K);
 }
 
-__device__ __forceinline__ double norm_seq(double ax, double ay, double az, double bx, double by, double bz)
-{
-    const double dx = ax - bx, dy = ay - by, dz = az - bz;
-    double s = 0.0;
-    s += dx * dx; s += dy * dy; s += dz * dz;
-    return __builtin_sqrt(s);
-}
-
 // bezier.py:985-1027 deCasteljauSplit on one coordinate row; half = 0: left piece, 1: right piece
 // (the reference reverses the "right" list, bezier.py:563)
 __device__ void split_row(const double* src, int K, double t, int half, double* dst)
@@ -1788,15 +1781,6 @@ __device__ __forceinline__ void split_row_lds(const double* src, int K, double t
         for (int i = 0; i < sz - 1; ++i) work[i] = (1 - t) * work[i] + t * work[i + 1];
     }
     if (half == 0) dst[K - 1] = work[0]; else dst[0] = work[0];
-}
-
-// The lane above's value (lane 63: zero): one DPP move per half of the double, no LDS round trip.
-__device__ __forceinline__ double wave_next_lane(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, 0x130, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
 }
 
 // deCasteljauSplit (bezier.py:985-1027) of three coordinate rows at once, LEVEL-parallel: lane (r, i) = r * K + i holds
@@ -2082,7 +2066,6 @@ __global__ __launch_bounds__(64, OBTG_MD_MIN_WAVES) void k_min_dist_wave(const M
 enum { R_CAP = 0, R_LB, R_T1, R_T2, R_UB, R_AM, R_NREC };
 enum { Q_NSCAL = F_NSCAL };               // frame scalars: k_min_dist_wave's (F_STATE: the next child, 0..4)
 __host__ __device__ constexpr int md_quad_blob(int K) { return 12 * K + 4 * R_NREC; }
-constexpr int kMdQuadMaxK = 16;
 // The scalars of the frames below the walk's: the first kMdScsLds levels in LDS, deeper ones behind their frame's blob in the
 // global stack (round 6: at max_depth 128 the scalars were 10 of a worker's 15.4 KB of LDS and held a CU to ten workers;
 // a search that ends is a few levels deep, one that runs into the depth cap pays two global round trips per level below 32).
@@ -2091,45 +2074,6 @@ __host__ __device__ constexpr int md_quad_frame(int K) { return md_quad_blob(K) 
 // doubles of split-parameter scratch per 16-lane row: 2 x 16 used; 34 (not 32 = 64 banks) so that the four rows' broadcast
 // reads of the same element fall into four banks (PMC: a quarter of the LDS cycles were conflicts with 32)
 constexpr int kMdShRow = 34;
-
-// deCasteljauSplit of rows [row0, row0 + nrows) of a node's six coordinate rows (rows 0..2: curve 1 at t1, rows 3..5:
-// curve 2 at t2), BOTH pieces kept: as split_rows3_wave_t, where the left piece's point L is lane (r, 0)'s value at level L
-// and the right piece's point i is lane (r, i)'s value at level K - 1 - i -- never the same lane at the same level before
-// the last one, so a level is still one store per lane.
-template <int KC>
-__device__ __forceinline__ void split_both_t(const double* c1, const double* c2, int K, double t1, double t2, double* blob,
-                                             int row0, int nrows, double* dump)
-{
-    if (KC > 0) K = KC;
-    const int lane = threadIdx.x & 63;
-    const int rq = lane / K, il = lane - rq * K, row = row0 + rq;
-    const bool valid = rq < nrows;
-    const bool second = row >= 3;
-    const int r3 = second ? row - 3 : row;
-    double w = valid ? (second ? c2 : c1)[r3 * K + il] : 0.0;
-    const double t = second ? t2 : t1, u = 1 - t;
-    double* outL = blob + (second ? 6 * K : 0) + r3 * K;          // left piece's row; the right piece's is 3 K further
-    double* outR = outL + 3 * K + il;
-    const bool first = valid && il == 0;
-    const int my_level = valid ? K - 1 - il : -1;
-    double* mine = dump + lane;
-    auto level = [&](int L) {
-        double* a = first ? outL + L : (my_level == L ? outR : mine);
-        *a = w;
-        const double up = wave_next_lane(w);
-        w = u * w + t * up;
-    };
-    if constexpr (KC > 0) {
-#pragma unroll
-        for (int L = 0; L < KC - 1; ++L) level(L);
-    } else {
-        for (int L = 0; L < K - 1; ++L) level(L);
-    }
-    // the last level's value: point K - 1 of the left piece and point 0 of the right one
-    double* a = first ? outL + (K - 1) : mine;
-    double* b = first ? outR : mine;
-    *a = w; *b = w;
-}
 
 __device__ __forceinline__ void split_both(const double* c1, const double* c2, int K, double t1, double t2, double* blob,
                                            double* dump)

@@ -279,5 +279,16 @@ double square_as_python(double x);
 double cube_as_python(double x);       // x**3 likewise (bezier.py:1468: eps**3)
 size_t min_dist_stack_doubles(const obtg_ctx* c, int K, int max_depth, int n_pairs, bool planar);   // whole launch, the form launch_min_dist runs
 size_t min_dist2poly_stack_doubles(int K, int max_depth);
+int min_dist_workers(const obtg_ctx* c, int n_pairs, size_t lds_per_wave, int waves_per_simd);   // worker waves of the queue forms
+
+// ---------------------------------------------------------------- launchers (coll_kernels.hip): _collCheckBez2Bez / _collCheckBez2Poly
+bool coll_check_supported(int K, int max_poly_K);      // at most 16 control points per curve and 16 vertices per polygon
+size_t coll_check_stack_doubles(const obtg_ctx* c, int K, int n_pairs, bool poly, bool planar);      // whole launch: a frame stack per worker wave of the grid that `planar` launches
+int launch_coll_check(obtg_ctx* c, const double* d_curves, int K, const int* d_pa, const int* d_pb, int n_pairs, double eps,
+                      int max_iter, int md_cap, int max_nodes, double* d_stack, double* d_res, int* d_info, int* d_queue,
+                      bool planar);      // planar: every control point of every curve has z == +0 (the caller has looked)
+int launch_coll_check2poly(obtg_ctx* c, const double* d_curves, int K, const double* d_soa, const int* d_off, const int* d_pc,
+                           const int* d_pp, int n_pairs, int max_iter, int md_cap, int max_nodes, double* d_stack, double* d_res,
+                           int* d_info, int* d_queue, int max_poly_K, bool planar);      // planar: curves AND polygons
 
 }  // namespace obtg

@@ -86,12 +86,14 @@ const char* obtg_strerror(int code);
  *   7  nothing changed meaning; new: the exact derivatives obtg_temporal_sep_jac[_dev], obtg_speed_jac[_dev],
  *      obtg_ang_rate_jac[_dev], obtg_euclidean_grad, obtg_deriv_energy_grad and the kernel-stats id OBTG_K_JAC
  *      (OBTG_K_COUNT moved from 8 to 9).
- *      Later, still 7: new: the collision checks obtg_coll_check, obtg_coll_check2poly (timed under OBTG_K_MIN_DIST). */
+ *      Later, still 7: new: the collision checks obtg_coll_check, obtg_coll_check2poly (timed under OBTG_K_MIN_DIST).
+ *      Later, still 7: new: the true Bernstein extrema obtg_bern_extrema[_dev] (timed under OBTG_K_BERN) and
+ *      obtg_temporal_sep_true_min[_dev] (timed under OBTG_K_TEMPORAL_SEP). */
 #define OBTG_ABI_VERSION 7
 int obtg_abi_version(void);
 
 /* Which sources this library was built from: the first 16 hex digits of a sha256 over a compile unit's source, the headers of
- * csrc/ and its compiler flags.  unit: "gjk_kernels", "bern_kernels", "jac_kernels", "capi", "tables", "comm", "libm_check", or "all" (NULL =
+ * csrc/ and its compiler flags.  unit: "gjk_kernels", "bern_kernels", "jac_kernels", "coll_kernels", "extrema_kernels", "capi", "tables", "comm", "libm_check", or "all" (NULL =
  * "all"); NULL is returned for a name that is none of these.  Counter files under profiles/ record the hash of the kernels they
  * were taken on; bench.py drops a counter whose hash is not the running library's instead of reporting it as measured. */
 const char* obtg_source_hash(const char* unit);
@@ -476,6 +478,50 @@ int obtg_coll_check2poly(obtg_ctx*, const double* curves, int n_curves, int K,
                          const int* pair_curve, const int* pair_poly, int n_pairs,
                          int max_iter, int md_cap, int max_nodes,
                          double* res, int* info, int* status);
+
+/* ---- true extrema of Bernstein polynomials over [0, 1] ---------------------------------------
+ * What Bezier.min / Bezier.max are for (bezier.py:631-667, 727-763; Examples/3D_Plots.py:167-172 calls them) -- NOT the
+ * reference's recursion, which splits a child at a parameter outside the child's span (bezier.py:659-661 with 560-561)
+ * and returns values below the minimum or does not return.  A stated contract instead, like the `_robust` searches.
+ * c[M][K]: M independent rows of K Bernstein coefficients, 1 <= K <= 64 (41 is the separation polynomial of a degree-20
+ * curve); K > 64 is OBTG_ERR_ARG.  For the minimum (want_max = 0), with s = max |c_k| of the row and
+ * tol = max(eps_abs, eps_rel * s):
+ *   val[M]      the polynomial's value at t_star in [0, 1], as de Casteljau subdivision at 1/2 gives it in binary64;
+ *   bound[M]    a lower bound of the polynomial on [0, 1]: the smallest coefficient over the sub-curves the search kept.
+ *               bound <= min p <= val up to rounding, and with status OBTG_MD_OK val - bound <= tol;
+ *   nodes[M]    sub-curves examined (the row itself is 1).  If the row's smallest coefficient is its first or last one,
+ *               val IS that coefficient (same bits), t_star is 0 or 1 and nodes is 1;
+ *   status[M]   OBTG_MD_OK; OBTG_MD_NODE_CAP: max_nodes sub-curves examined without reaching tol; OBTG_MD_DEPTH_CAP: more
+ *               than 32 sub-curves waiting at once (the search is depth-first, so this is a depth of more than 32
+ *               bisections: only a tol below the rounding of the row, tol = 0 included, gets there).  val / bound are then
+ *               still a valid bracket, the best of both so far.
+ * want_max = 1 is, bit for bit, the negated result of the minimum of the negated row (bound is then an upper bound).
+ * A row with a non-finite coefficient: val, t_star, bound NaN, nodes 0, status OBTG_MD_OK.
+ * The search is depth-first bisection at 1/2 (every split a pair of averages per level).  A row's result depends on its
+ * coefficients alone: not on M, the other rows, its position or the launch; host and _dev entry give the same bits.
+ * t_star, bound, nodes are nullable (and status in the _dev form). */
+int obtg_bern_extrema(obtg_ctx*, const double* c /*[M][K]*/, int M, int K, int want_max,
+                      double eps_rel, double eps_abs, int max_nodes,
+                      double* val /*[M]*/, double* t_star /*[M], nullable*/, double* bound /*[M], nullable*/,
+                      int* nodes /*[M], nullable*/, int* status /*[M]*/);
+int obtg_bern_extrema_dev(obtg_ctx*, const double* d_c, int M, int K, int want_max, double eps_rel, double eps_abs,
+                          int max_nodes, double* d_val, double* d_t_star, double* d_bound, int* d_nodes, int* d_status);
+/* The tight continuous-time separation: for every row b and every pair of the context's N+M objects, in the order of
+ * obtg_temporal_sep, the MINIMUM over t in [0, 1] of ((v_i - v_j).normSquare())(t) - max_sep^2 (optimization.py:311-346
+ * bounds this polynomial from below by its control points; bezier.py:631-667 is the reference's sketch of the minimum).
+ * normSquare's (d/2) factor and Python's max_sep**2 are kept: the value is on the scale of every other separation row.
+ * DEG_ELEV does not enter -- elevation does not change the polynomial -- so the context's R is not read.  The 2n+1
+ * coefficients are formed by the device definition of obtg_temporal_sep's rows at R = 0, so out equals
+ * obtg_bern_extrema(eps_abs = 0) of those rows bit for bit, and a pair whose smallest coefficient is an end coefficient
+ * gives the bits of obtg_temporal_sep_min at R = 0.  out[B][P], t_star[B][P] (where the minimum is taken), status[B][P]
+ * as above.  Degrees with a specialised kernel (obtg_fast_kernels & 1) form the coefficients in registers: nothing but Y
+ * is read and 8 to 20 bytes per pair are written; other degrees up to 31 go through a workspace of obtg_temporal_sep's
+ * R = 0 rows (two launches; the context's DEG_ELEV and tables are not touched); beyond: OBTG_ERR_UNSUPPORTED.
+ * _dev: dY may be NULL inside an obtg_fd_view (the batch is then written once per view). */
+int obtg_temporal_sep_true_min(obtg_ctx*, const double* Y, int B, double max_sep, double eps_rel, int max_nodes,
+                               double* out /*[B][P]*/, double* t_star /*[B][P], nullable*/, int* status /*[B][P], nullable*/);
+int obtg_temporal_sep_true_min_dev(obtg_ctx*, const double* dY, int B, double max_sep, double eps_rel, int max_nodes,
+                                   double* d_out, double* d_t_star, int* d_status);
 
 /* ---- single-curve Bernstein algebra (the Bezier object's methods, batched over rows) ----
  * obtg_bern_elev:   Bezier.elev(R)      bezier.py:469-495   in[rows][n+1]   -> out[rows][n+R+1]

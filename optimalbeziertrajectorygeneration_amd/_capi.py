@@ -104,6 +104,10 @@ _SIGNATURES = {
     "obtg_gjk_true_pairs": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "obtg_coll_check": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _d, _i, _i, _i, _vp, _vp, _vp]),
     "obtg_coll_check2poly": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "obtg_bern_extrema": (_i, [_vp, _vp, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_bern_extrema_dev": (_i, [_vp, _vp, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_temporal_sep_true_min": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
+    "obtg_temporal_sep_true_min_dev": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
     "obtg_bern_elev": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "obtg_bern_diff": (_i, [_vp, _vp, _i, _i, _d, _vp]),
     "obtg_bern_mul": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
@@ -502,6 +506,44 @@ class Context(object):
         self._check(self._lib.obtg_temporal_sep_active(self._h, _ptr(Y), B, float(max_sep), int(k), _ptr(out), _ptr(idx)),
                     "obtg_temporal_sep_active")
         return (out, idx) if with_index else out
+
+    def temporal_sep_true_min(self, Y, max_sep, eps_rel=1e-9, max_nodes=100000):
+        """Per pair the true minimum over t in [0, 1] of the squared-separation polynomial minus max_sep^2
+        (obtg_temporal_sep_true_min; DEG_ELEV does not enter): dict(val[B][P], t_star[B][P] -- where it is taken --,
+        status[B][P] as MD_*).  val - (the search's lower bound) <= eps_rel x the pair's largest coefficient."""
+        Y, B = self._rows(Y)
+        out = pinned_empty((B, self.num_pairs))
+        t_star = np.empty((B, self.num_pairs))
+        status = np.zeros((B, self.num_pairs), np.int32)
+        self._check(self._lib.obtg_temporal_sep_true_min(self._h, _ptr(Y), B, float(max_sep), float(eps_rel), int(max_nodes),
+                                                         _ptr(out), _ptr(t_star), _ptr(status)), "obtg_temporal_sep_true_min")
+        return dict(val=out, t_star=t_star, status=status)
+
+    def temporal_sep_true_min_dev(self, dY, B, max_sep, d_out, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
+        self._check(self._lib.obtg_temporal_sep_true_min_dev(self._h, _vp(dY), B, float(max_sep), float(eps_rel), int(max_nodes),
+                                                             _vp(d_out), _vp(d_t_star), _vp(d_status)),
+                    "obtg_temporal_sep_true_min_dev")
+
+    def bern_extrema(self, c, want_max=False, eps_rel=1e-9, eps_abs=0.0, max_nodes=100000):
+        """True minimum (want_max: maximum) over [0, 1] of every row of Bernstein coefficients c[M][K], K <= 64
+        (obtg_bern_extrema): dict(val, t_star, bound, nodes, status) with bound <= min p <= val and, where status is MD_OK,
+        val - bound <= max(eps_abs, eps_rel * max |c_k|)."""
+        c = _f64(c)
+        if c.ndim == 1:
+            c = c[None]
+        M, K = c.shape
+        val, t_star, bound = np.empty(M), np.empty(M), np.empty(M)
+        nodes, status = np.zeros(M, np.int32), np.zeros(M, np.int32)
+        self._check(self._lib.obtg_bern_extrema(self._h, _ptr(c), M, K, int(bool(want_max)), float(eps_rel), float(eps_abs),
+                                                int(max_nodes), _ptr(val), _ptr(t_star), _ptr(bound), _ptr(nodes), _ptr(status)),
+                    "obtg_bern_extrema")
+        return dict(val=val, t_star=t_star, bound=bound, nodes=nodes, status=status)
+
+    def bern_extrema_dev(self, d_c, M, K, d_val, d_t_star=None, d_bound=None, d_nodes=None, d_status=None, want_max=False,
+                         eps_rel=1e-9, eps_abs=0.0, max_nodes=100000):
+        self._check(self._lib.obtg_bern_extrema_dev(self._h, _vp(d_c), int(M), int(K), int(bool(want_max)), float(eps_rel),
+                                                    float(eps_abs), int(max_nodes), _vp(d_val), _vp(d_t_star), _vp(d_bound),
+                                                    _vp(d_nodes), _vp(d_status)), "obtg_bern_extrema_dev")
 
     def temporal_sep_active_dev(self, dY, B, max_sep, k, d_out_val, d_out_idx=None, pair_begin=0, pair_count=None):
         if pair_count is None:

@@ -13,7 +13,12 @@ Differences from the reference, on purpose:
     exceptions instead of hanging;
   * plotting (`plot`, matplotlib) and temporal alignment of curves with different [t0, tf] are outside the
     accelerated path and are not provided; `curve` / `__call__` -- what the drivers' own
-    plotting code reads after a solve -- are (obtg_bern_eval).
+    plotting code reads after a solve -- are (obtg_bern_eval);
+  * `min` / `max` return the curve's true extremum within `tol` (obtg_bern_extrema: a certified subdivision search), not
+    what the reference's recursion returns (bezier.py:631-667, 727-763).  That recursion splits a child at
+    `minIdx / deg` taken as an absolute parameter, outside the child's span (bezier.py:659-661 with 560-561): on the
+    reference's own example c6 = Bezier([(0,1,2,3,4,5), (5,0,2,5,7,5)]) `c6.min(dim=1)` returns 1.7744000000000004 where
+    the minimum is 2.2606668630782703, and `c6.max(dim=1)` ends in RecursionError (true maximum 5.699106677492463).
 """
 import numpy as np
 
@@ -250,6 +255,23 @@ class Bezier(BezierParams):
         _raise_md(r['status'][0])
         res = r['res'][0]
         return (float(res[0]), float(res[1]), res[2:].copy())
+
+    # ---- extrema of one coordinate (bezier.py:631-667 min, 727-763 max)
+    def _extremum(self, dim, tol, want_max, what):
+        row = self.cpts[dim]                      # IndexError for a dimension the curve does not have, as in the reference
+        r = _ctx().bern_extrema(np.atleast_2d(row), want_max=want_max, eps_rel=0.0, eps_abs=float(tol))
+        _raise_md(r['status'][0], what)
+        return float(r['val'][0])
+
+    def min(self, dim=0, globMin=-np.inf, tol=1e-6):
+        """The minimum of coordinate `dim` over the curve, within the absolute tolerance `tol` above it (never below).
+        The reference's signature; `globMin` is its recursion plumbing, accepted and ignored.  See the module docstring:
+        this is the true minimum, which the reference's recursion is not."""
+        return self._extremum(dim, tol, False, 'min')
+
+    def max(self, dim=0, globMax=np.inf, tol=1e-6):
+        """The maximum of coordinate `dim` over the curve, within `tol` below it; `globMax` accepted and ignored."""
+        return self._extremum(dim, tol, True, 'max')
 
     # ---- collision checks (bezier.py:859-867)
     def collCheck(self, otherCurve, max_nodes=4000000, robust=False):

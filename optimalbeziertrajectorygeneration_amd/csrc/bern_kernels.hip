@@ -1105,10 +1105,11 @@ static bool fast_shape(const obtg_ctx* c)
     return nc_in_sep(nc) && (c->dim == 2 || c->dim == 3) && c->R <= 512;
 }
 
-static int gen_common(obtg_ctx* c, GenParams& g)
+static int gen_common(obtg_ctx* c, GenParams& g, int R = -1)      // R < 0: the context's DEG_ELEV
 {
     // make every binomial row resident BEFORE taking the base pointer
-    const int n = c->deg, R = c->R, m = n + R;
+    if (R < 0) R = c->R;
+    const int n = c->deg, m = n + R;
     int need[] = { n, 2 * n, R, 2 * n + R, m, 2 * m, 4 * m };
     for (int v : need) { int o = binrow_offset(c, v); if (o < 0) return o; }
     g.o_n = binrow_offset(c, n); g.o_2n = binrow_offset(c, 2 * n); g.o_R = binrow_offset(c, R);
@@ -1265,6 +1266,25 @@ int launch_temporal_sep(obtg_ctx* c, const double* dY, int B, double max_sep, in
     ScopedKernelTimer t(c, OBTG_K_TEMPORAL_SEP);
     hipLaunchKernelGGL(k_generic_normsq_elev<0>, dim3((unsigned)((size_t)B * pair_count)), dim3(kWave), lds,
                        c->stream, g);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
+// obtg_temporal_sep's rows AT R = 0 from the any-degree kernel, whatever the context's DEG_ELEV is (the route of
+// obtg_temporal_sep_true_min for degrees off the fast-kernel list): the launch a context with R = 0 makes, bit for bit; the
+// context is not touched
+int launch_temporal_sep_rows_r0_generic(obtg_ctx* c, const double* dY, int B, double max_sep, double* d_out)
+{
+    if (B <= 0 || c->n_pairs <= 0) return OBTG_OK;
+    if (2 * c->deg + 1 > kMaxGenericLen) return OBTG_ERR_UNSUPPORTED;
+    GenParams g{};
+    int rc = gen_common(c, g, 0);
+    if (rc) return rc;
+    g.Y = dY; g.out = d_out; g.item_begin = 0; g.item_count = c->n_pairs; g.B = B;
+    g.sign = 1.0; g.offset = 0.0 - square_as_python(max_sep); g.min_only = 0;
+    const size_t lds = sizeof(double) * ((size_t)2 * c->dim * (c->deg + 1) + 2 * c->deg + 1);
+    ScopedKernelTimer t(c, OBTG_K_TEMPORAL_SEP);
+    hipLaunchKernelGGL(k_generic_normsq_elev<0>, dim3((unsigned)((size_t)B * c->n_pairs)), dim3(kWave), lds, c->stream, g);
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;
 }

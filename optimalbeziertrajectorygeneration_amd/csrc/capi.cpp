@@ -235,6 +235,7 @@ const char* obtg_abi_symbols(void)
         "obtg_temporal_sep_dev\0obtg_temporal_sep_min_dev\0obtg_speed_dev\0obtg_ang_rate_dev\0obtg_dynamics_dev\0"
         "obtg_fd_batch_dev\0obtg_fd_view_begin\0obtg_fd_view_begin_rows\0obtg_fd_view_end\0obtg_fd_forms_on_the_fly\0obtg_pair_sweep_fd_dev\0obtg_dynamics_fd_dev\0obtg_gjk_pairs\0obtg_ctx_set_polygons\0obtg_ctx_set_hull_pairs\0"
         "obtg_ctx_set_fd_dedup\0obtg_ctx_set_gjk_history\0obtg_pair_sweep_dev\0obtg_constraint_sweep_dev\0obtg_constraint_sweep_fd_structured_dev\0obtg_constraint_sweep_fd_structured_rows_dev\0obtg_gjk_swarm_dev\0obtg_gjk_swarm\0obtg_min_dist\0obtg_min_dist_robust\0obtg_min_dist2poly\0obtg_min_dist2poly_robust\0obtg_gjk_true_pairs\0obtg_coll_check\0obtg_coll_check2poly\0"
+        "obtg_bern_extrema\0obtg_bern_extrema_dev\0obtg_temporal_sep_true_min\0obtg_temporal_sep_true_min_dev\0"
         "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_eval\0"
         "obtg_euclidean_obj\0obtg_accel_obj\0obtg_jerk_obj\0"
         "obtg_temporal_sep_jac\0obtg_temporal_sep_jac_dev\0obtg_speed_jac\0obtg_speed_jac_dev\0obtg_ang_rate_jac\0obtg_ang_rate_jac_dev\0obtg_euclidean_grad\0obtg_deriv_energy_grad\0"
@@ -1421,6 +1422,88 @@ int obtg_coll_check2poly(obtg_ctx* c, const double* curves, int n_curves, int K,
     if (info) std::memcpy(info, hinfo.data(), sizeof(int) * 4 * n_pairs);
     if (status) for (int k = 0; k < n_pairs; ++k) status[k] = hinfo[4 * k + 3];
     return OBTG_OK;
+}
+
+// ------------------------------------------------------------------ true Bernstein extrema (extrema_kernels.hip)
+int obtg_bern_extrema_dev(obtg_ctx* c, const double* d_c, int M, int K, int want_max, double eps_rel, double eps_abs,
+                          int max_nodes, double* d_val, double* d_t_star, double* d_bound, int* d_nodes, int* d_status)
+{
+    if (!check_ctx(c) || M < 0 || !bern_extrema_supported(K) || max_nodes < 1) return OBTG_ERR_ARG;
+    if (!(eps_rel >= 0.0) || !(eps_abs >= 0.0)) return OBTG_ERR_ARG;
+    if (M > 0 && (!d_c || !d_val)) return OBTG_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    return launch_bern_extrema(c, d_c, M, K, want_max != 0, eps_rel, eps_abs, max_nodes, d_val, d_t_star, d_bound, d_nodes,
+                               d_status);
+}
+
+int obtg_bern_extrema(obtg_ctx* c, const double* coef, int M, int K, int want_max, double eps_rel, double eps_abs,
+                      int max_nodes, double* val, double* t_star, double* bound, int* nodes, int* status)
+{
+    if (!check_ctx(c) || M < 0 || !bern_extrema_supported(K) || max_nodes < 1) return OBTG_ERR_ARG;
+    if (!(eps_rel >= 0.0) || !(eps_abs >= 0.0)) return OBTG_ERR_ARG;
+    if (M > 0 && (!coef || !val || !status)) return OBTG_ERR_ARG;
+    if (M == 0) return OBTG_OK;
+    (void)hipSetDevice(c->device);
+    const size_t m = (size_t)M;
+    int rc = h2d(c, c->ws_in, coef, sizeof(double) * m * K);
+    if (rc) return rc;
+    if ((rc = c->ws_out.reserve(sizeof(double) * 3 * m))) return rc;
+    DevBuf& di = c->ws_misc[3];
+    if ((rc = di.reserve(sizeof(int) * 2 * m))) return rc;
+    double* dv = c->ws_out.as<double>();
+    int* dn = di.as<int>();
+    if ((rc = launch_bern_extrema(c, c->ws_in.as<double>(), M, K, want_max != 0, eps_rel, eps_abs, max_nodes, dv, dv + m, dv + 2 * m,
+                                  dn, dn + m))) return rc;
+    if (t_star && (rc = d2h_copy(c, t_star, dv + m, sizeof(double) * m))) return rc;
+    if (bound && (rc = d2h_copy(c, bound, dv + 2 * m, sizeof(double) * m))) return rc;
+    if (nodes && (rc = d2h_copy(c, nodes, dn, sizeof(int) * m))) return rc;
+    if ((rc = d2h_copy(c, status, dn + m, sizeof(int) * m))) return rc;
+    return d2h(c, val, dv, sizeof(double) * m);
+}
+
+// the fused kernel where the shape has one; else obtg_temporal_sep's rows at R = 0 into a workspace and obtg_bern_extrema on them
+static int true_min_launch(obtg_ctx* c, const double* dY, int B, double max_sep, double eps_rel, int max_nodes, double* d_out,
+                           double* d_t, int* d_status)
+{
+    int rc = launch_temporal_sep_true_min(c, dY, B, max_sep, eps_rel, max_nodes, d_out, d_t, d_status);
+    if (rc != OBTG_ERR_UNSUPPORTED) return rc;
+    const int K = 2 * c->deg + 1;
+    if (!bern_extrema_supported(K)) return OBTG_ERR_UNSUPPORTED;
+    const long items = (long)B * c->n_pairs;
+    DevBuf& ws = c->ws_misc[7];
+    if ((rc = ws.reserve(sizeof(double) * (size_t)items * K))) return rc;
+    // DEG_ELEV does not enter: the any-degree kernel with R = 0 in its parameters, the context as it is
+    if ((rc = launch_temporal_sep_rows_r0_generic(c, dY, B, max_sep, ws.as<double>()))) return rc;
+    return launch_bern_extrema(c, ws.as<double>(), items, K, 0, eps_rel, 0.0, max_nodes, d_out, d_t, nullptr, nullptr, d_status,
+                               OBTG_K_TEMPORAL_SEP);
+}
+
+int obtg_temporal_sep_true_min_dev(obtg_ctx* c, const double* dY, int B, double max_sep, double eps_rel, int max_nodes,
+                                   double* d_out, double* d_t_star, int* d_status)
+{
+    if (!check_ctx(c) || !d_out || B < 0 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    return with_batch(c, dY, B, false, [&](const double* src) {
+        return true_min_launch(c, src, B, max_sep, eps_rel, max_nodes, d_out, d_t_star, d_status); });
+}
+
+int obtg_temporal_sep_true_min(obtg_ctx* c, const double* Y, int B, double max_sep, double eps_rel, int max_nodes,
+                               double* out, double* t_star, int* status)
+{
+    if (!check_ctx(c) || !Y || !out || B < 0 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
+    if (B == 0 || c->n_pairs == 0) return OBTG_OK;
+    (void)hipSetDevice(c->device);
+    const size_t n = (size_t)B * c->n_pairs;
+    int rc = h2d(c, c->ws_in, Y, sizeof(double) * ysize(c) * B, true);
+    if (rc) return rc;
+    if ((rc = c->ws_out.reserve(sizeof(double) * 2 * n))) return rc;
+    DevBuf& di = c->ws_misc[4];
+    if ((rc = di.reserve(sizeof(int) * n))) return rc;
+    double* dv = c->ws_out.as<double>();
+    if ((rc = true_min_launch(c, c->ws_in.as<double>(), B, max_sep, eps_rel, max_nodes, dv, dv + n, di.as<int>()))) return rc;
+    if (t_star && (rc = d2h_copy(c, t_star, dv + n, sizeof(double) * n))) return rc;
+    if (status && (rc = d2h_copy(c, status, di.p, sizeof(int) * n))) return rc;
+    return d2h(c, out, dv, sizeof(double) * n);
 }
 
 // ------------------------------------------------------------------ single-curve algebra

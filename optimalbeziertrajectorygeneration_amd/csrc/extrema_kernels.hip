@@ -1,0 +1,313 @@
+// True extrema of Bernstein polynomials over [0, 1] for gfx950 (MI355X): obtg_bern_extrema and the fused consumer
+// obtg_temporal_sep_true_min (include/obtg.h states the contract).
+//
+// What the reference has here is Bezier.min / Bezier.max (bezier.py:631-667, 727-763), a subdivision sketch that
+// extrapolates outside a child's span (bezier.py:659-661 with 560-561) and so returns values below the minimum or does
+// not return.  This unit is NOT that recursion: it is a certified search, val - bound <= tol, held to exact rationals.
+//
+// Search (wave_search): depth-first bisection at 1/2.  A sub-curve's smallest coefficient bounds it from below, the
+// end-point values met so far bound the minimum from above (U); a sub-curve with U - lower <= tol is a leaf.  Of two live
+// children the one with the smaller lower bound is followed, the other waits on a stack of kExStack frames in LDS.
+// Every split is a pair of averages per level -- 0.5 * a + 0.5 * b with contraction off -- so a row's result
+// depends on its coefficients alone.
+//
+// Kernel form: the first step (smallest coefficient at an end, or the end values within tol of it) is one LANE per row:
+// most rows of a constraint batch end there.  A row that needs the search gets the whole WAVE: lane k holds coefficient
+// k, a de Casteljau level is one DPP move of the lane above's value and one average (md_device.h wave_next_lane), the left
+// piece is lane 0's value level by level, the right piece what each lane holds when it stops.  No per-lane coefficient
+// arrays in the search (K is a run-time count up to 64), the stack is kExStack x (K + 3) doubles per wave.
+#include <algorithm>
+#include <cfloat>
+
+#include "obtg_internal.h"
+#include "md_device.h"
+#pragma clang fp contract(fast)
+#include "bern_device.h"
+#pragma clang fp contract(off)
+
+namespace obtg {
+
+constexpr int kExStack = 32;          // live sub-curves waiting per row; one more: OBTG_MD_DEPTH_CAP
+constexpr int kExMaxK = kWave;        // a row is a row of lanes
+constexpr int kExWaves = 2;           // waves per workgroup (K = 64: 34 KB of stacks)
+
+struct ExOut {
+    double val, t, bound;
+    int nodes, status;
+};
+
+__device__ __forceinline__ double ex_lane(double v, int src)      // src wave-uniform
+{
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src), hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double ex_lane0(double v)
+{
+    const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double ex_wave_min(double v)
+{
+#pragma unroll
+    for (int o = 32; o; o >>= 1) v = fmin(v, __shfl_xor(v, o));
+    return v;
+}
+
+// One row's scan, a coefficient at a time in index order: smallest value, largest magnitude, the two ends.
+struct ExScan {
+    double m = INFINITY, s = 0.0, c0 = 0.0, cl = 0.0;
+    bool bad = false;
+    __device__ __forceinline__ void put(double v, int k)
+    {
+        if (k == 0) c0 = v;
+        cl = v;
+        bad = bad || !(fabs(v) <= DBL_MAX);
+        m = fmin(m, v);
+        s = fmax(s, fabs(v));
+    }
+};
+
+// The first step of a row (node 1).  true: `o` is the row's answer; false: the search has to run (tol is set either way).
+__device__ __forceinline__ bool ex_first(const ExScan& sc, double eps_rel, double eps_abs, ExOut& o, double& tol)
+{
+    tol = fmax(eps_abs, eps_rel * sc.s);
+    o.status = OBTG_MD_OK;
+    if (sc.bad) { o.val = o.t = o.bound = __builtin_nan(""); o.nodes = 0; return true; }
+    o.nodes = 1;
+    o.bound = sc.m;
+    if (sc.c0 == sc.m) { o.val = sc.c0; o.t = 0.0; return true; }
+    if (sc.cl == sc.m) { o.val = sc.cl; o.t = 1.0; return true; }
+    if (sc.c0 <= sc.cl) { o.val = sc.c0; o.t = 0.0; } else { o.val = sc.cl; o.t = 1.0; }
+    return o.val - sc.m <= tol;
+}
+
+// The whole wave on ONE row (every lane must be here).  b: lane k < K holds coefficient k, the other lanes +inf.
+// stk: this wave's kExStack x (K + 3) doubles.  Every scalar below is the same in all lanes by construction.
+__device__ __forceinline__ ExOut wave_search(double b, const int K, const double tol, const double c0, const double cl,
+                                             const double m, const int max_nodes, double* stk)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const int pitch = K + 3;
+    double U, tU;
+    if (c0 <= cl) { U = c0; tU = 0.0; } else { U = cl; tU = 1.0; }
+    double bound = INFINITY, t0 = 0.0, w = 1.0, cur_lb = m;
+    int nodes = 1, sp = 0, status = OBTG_MD_OK;
+    for (;;) {
+        if (nodes + 2 > max_nodes) { status = OBTG_MD_NODE_CAP; bound = fmin(bound, cur_lb); break; }
+        // deCasteljau at 1/2, both pieces: left[r] is lane 0's value after level r, right[i] lane i's after level K - 1 - i
+        double left = b, lbL = ex_lane0(b), mid = lbL;
+        for (int r = 1; r < K; ++r) {
+            const double up = wave_next_lane(b);
+            if (lane <= K - 1 - r) b = 0.5 * b + 0.5 * up;      // (two exact scalings, one rounding: no overflow below DBL_MAX)
+            mid = ex_lane0(b);
+            if (lane == r) left = mid;
+            lbL = fmin(lbL, mid);
+        }
+        const double lbR = ex_wave_min(b);
+        const double hw = 0.5 * w, tm = t0 + hw;
+        nodes += 2;
+        if (mid < U) { U = mid; tU = tm; }
+        const bool aliveL = U - lbL > tol, aliveR = U - lbR > tol;
+        if (!aliveL) bound = fmin(bound, lbL);
+        if (!aliveR) bound = fmin(bound, lbR);
+        if (aliveL && aliveR) {
+            if (sp == kExStack) { status = OBTG_MD_DEPTH_CAP; bound = fmin(bound, fmin(lbL, lbR)); break; }
+            const bool go_left = lbL <= lbR;
+            double* f = stk + sp * pitch;
+            if (lane < K) f[lane] = go_left ? b : left;
+            if (lane == 0) { f[K] = go_left ? lbR : lbL; f[K + 1] = go_left ? tm : t0; f[K + 2] = hw; }
+            ++sp;
+            if (go_left) { b = left; cur_lb = lbL; } else { t0 = tm; cur_lb = lbR; }
+            w = hw;
+        } else if (aliveL) { b = left; cur_lb = lbL; w = hw; }
+        else if (aliveR) { t0 = tm; cur_lb = lbR; w = hw; }
+        else {
+            bool found = false;
+            wave_sync();
+            while (sp > 0) {
+                --sp;
+                const double* f = stk + sp * pitch;
+                const double plb = f[K];
+                if (U - plb > tol) {
+                    b = lane < K ? f[lane] : INFINITY;
+                    t0 = f[K + 1]; w = f[K + 2]; cur_lb = plb;
+                    found = true;
+                    break;
+                }
+                bound = fmin(bound, plb);
+            }
+            wave_sync();
+            if (!found) break;
+        }
+    }
+    if (status != OBTG_MD_OK) {            // what still waits is part of the bracket
+        wave_sync();
+        for (int i = 0; i < sp; ++i) bound = fmin(bound, stk[i * pitch + K]);
+        wave_sync();
+    }
+    ExOut o;
+    o.val = U; o.t = tU; o.bound = fmin(bound, U); o.nodes = nodes; o.status = status;
+    return o;
+}
+
+struct ExParams {
+    const double* __restrict__ c;      // [M][K]
+    double* __restrict__ val;          // [M]
+    double* __restrict__ t;            // [M] nullable
+    double* __restrict__ bound;        // [M] nullable
+    int* __restrict__ nodes;           // [M] nullable
+    int* __restrict__ status;          // [M] nullable
+    long M;
+    int K, want_max, max_nodes;
+    double eps_rel, eps_abs;
+};
+
+__device__ __forceinline__ void ex_store(const ExParams& p, long row, const ExOut& o, bool neg)
+{
+    p.val[row] = neg ? -o.val : o.val;
+    if (p.t) p.t[row] = o.t;
+    if (p.bound) p.bound[row] = neg ? -o.bound : o.bound;
+    if (p.nodes) p.nodes[row] = o.nodes;
+    if (p.status) p.status[row] = o.status;
+}
+
+__global__ __launch_bounds__(kExWaves * kWave) void k_bern_extrema(const ExParams p)
+{
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    double* stk = lds + (size_t)wave * kExStack * (p.K + 3);
+    const long row = ((long)blockIdx.x * kExWaves + wave) * kWave + lane;
+    const bool valid = row < p.M;
+    const long rr = valid ? row : p.M - 1;
+    const bool neg = p.want_max != 0;
+    const double* cr = p.c + rr * p.K;
+    ExScan sc;
+    for (int k = 0; k < p.K; ++k) { const double v = cr[k]; sc.put(neg ? -v : v, k); }
+    ExOut mine;
+    double tol;
+    const bool need = !ex_first(sc, p.eps_rel, p.eps_abs, mine, tol) && valid;
+    unsigned long long mask = __ballot(need);
+    while (mask) {
+        const int src = __ffsll((long long)mask) - 1;
+        mask &= mask - 1;
+        const long row0 = ((long)blockIdx.x * kExWaves + wave) * kWave;
+        const double* cs = p.c + (row0 + src) * p.K;
+        double b = INFINITY;
+        if (lane < p.K) { const double v = cs[lane]; b = neg ? -v : v; }
+        const ExOut o = wave_search(b, p.K, ex_lane(tol, src), ex_lane(sc.c0, src), ex_lane(sc.cl, src), ex_lane(sc.m, src),
+                                    p.max_nodes, stk);
+        if (lane == src) mine = o;
+    }
+    if (valid) ex_store(p, row, mine, neg);
+}
+
+// ---- fused: the separation polynomial of every (row, pair) formed in the lane (normsq_coeffs, the definition
+// obtg_temporal_sep's rows have at R = 0), then the same first step and the same search: the coefficients never reach memory
+struct TsepExParams {
+    const double* __restrict__ Y;      // [B][n_veh*DIM][NC]
+    const double* __restrict__ obs;    // [n_obj - n_veh][DIM]
+    const int2* __restrict__ pairs;    // [P]
+    const double* __restrict__ W2;
+    ExParams ex;                       // outputs [B][P]; c unused
+    int n_veh, P;
+    double sign, offset;
+};
+
+template <int NC, int DIM>
+__global__ __launch_bounds__(kExWaves * kWave) void k_tsep_true_min(const TsepExParams q)
+{
+    using S = NsShape<NC, DIM>;
+    constexpr int L = S::L;
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    double* stk = lds + (size_t)wave * kExStack * (L + 3);
+    const ExParams& p = q.ex;
+    const long item = ((long)blockIdx.x * kExWaves + wave) * kWave + lane;
+    const bool valid = item < p.M;
+    const long it = valid ? item : p.M - 1;
+    const int b = (int)(it / q.P), pr = (int)(it - (long)b * q.P);
+    const int2 ij = q.pairs[pr];
+    const double* Yrow = q.Y + (size_t)b * q.n_veh * S::VLEN;
+    double a[DIM][NC];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const double xi = ij.x < q.n_veh ? Yrow[(size_t)(ij.x * DIM + d) * NC + c] : q.obs[(ij.x - q.n_veh) * DIM + d];
+            const double xj = ij.y < q.n_veh ? Yrow[(size_t)(ij.y * DIM + d) * NC + c] : q.obs[(ij.y - q.n_veh) * DIM + d];
+            a[d][c] = xi - xj;
+        }
+    double cf[L];
+    normsq_coeffs<NC, DIM>(a, as_ctab(q.W2), cf);
+    ExScan sc;
+#pragma unroll
+    for (int k = 0; k < L; ++k) { cf[k] = fma(q.sign, cf[k], q.offset); sc.put(cf[k], k); }   // the R = 0 row's value (sign = 1)
+    ExOut mine;
+    double tol;
+    const bool need = !ex_first(sc, p.eps_rel, p.eps_abs, mine, tol) && valid;
+    unsigned long long mask = __ballot(need);
+    while (mask) {
+        const int src = __ffsll((long long)mask) - 1;
+        mask &= mask - 1;
+        double bb = INFINITY;
+#pragma unroll
+        for (int k = 0; k < L; ++k) { const double v = ex_lane(cf[k], src); if (lane == k) bb = v; }
+        const ExOut o = wave_search(bb, L, ex_lane(tol, src), ex_lane(sc.c0, src), ex_lane(sc.cl, src), ex_lane(sc.m, src),
+                                    p.max_nodes, stk);
+        if (lane == src) mine = o;
+    }
+    if (valid) ex_store(p, item, mine, false);
+}
+
+// =====================================================================================
+//  launchers
+// =====================================================================================
+bool bern_extrema_supported(int K) { return K >= 1 && K <= kExMaxK; }
+
+int launch_bern_extrema(obtg_ctx* c, const double* d_c, long M, int K, int want_max, double eps_rel, double eps_abs,
+                        int max_nodes, double* d_val, double* d_t, double* d_bound, int* d_nodes, int* d_status, int kernel_id)
+{
+    if (M <= 0) return OBTG_OK;
+    if (!bern_extrema_supported(K)) return OBTG_ERR_ARG;
+    ExParams p{};
+    p.c = d_c; p.val = d_val; p.t = d_t; p.bound = d_bound; p.nodes = d_nodes; p.status = d_status;
+    p.M = M; p.K = K; p.want_max = want_max; p.max_nodes = max_nodes; p.eps_rel = eps_rel; p.eps_abs = eps_abs;
+    const size_t lds = sizeof(double) * kExWaves * kExStack * (size_t)(K + 3);
+    const long per_wg = kExWaves * kWave;
+    ScopedKernelTimer t(c, kernel_id);
+    hipLaunchKernelGGL(k_bern_extrema, dim3((unsigned)((M + per_wg - 1) / per_wg)), dim3(kExWaves * kWave), lds, c->stream, p);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
+// OBTG_ERR_UNSUPPORTED: not a shape of the fast-kernel list (the caller goes through obtg_temporal_sep's rows)
+int launch_temporal_sep_true_min(obtg_ctx* c, const double* dY, int B, double max_sep, double eps_rel, int max_nodes,
+                                 double* d_out, double* d_t, int* d_status)
+{
+    if (B <= 0 || c->n_pairs <= 0) return OBTG_OK;
+    const int nc = c->deg + 1;
+    if (!nc_in_sep(nc) || (c->dim != 2 && c->dim != 3)) return OBTG_ERR_UNSUPPORTED;
+    int rc = ensure_tables(c);
+    if (rc) return rc;
+    TsepExParams q{};
+    q.Y = dY; q.obs = c->d_obs.as<double>(); q.pairs = c->d_pairs.as<int2>(); q.W2 = c->d_w2.as<double>();
+    q.n_veh = c->n_veh; q.P = c->n_pairs;
+    q.sign = 1.0; q.offset = 0.0 - square_as_python(max_sep);
+    q.ex.val = d_out; q.ex.t = d_t; q.ex.status = d_status;
+    q.ex.M = (long)B * c->n_pairs; q.ex.K = 2 * c->deg + 1; q.ex.max_nodes = max_nodes; q.ex.eps_rel = eps_rel; q.ex.eps_abs = 0.0;
+    void (*kern)(const TsepExParams) = nullptr;
+#define OBTG_CASE(NC_, D_) if (nc == NC_ && c->dim == D_) kern = k_tsep_true_min<NC_, D_>;
+#define OBTG_CASE_D(NC_) OBTG_CASE(NC_, 2) OBTG_CASE(NC_, 3)
+    OBTG_NC_SEP(OBTG_CASE_D)
+#undef OBTG_CASE_D
+#undef OBTG_CASE
+    if (!kern) return OBTG_ERR_UNSUPPORTED;
+    const size_t lds = sizeof(double) * kExWaves * kExStack * (size_t)(q.ex.K + 3);
+    const long per_wg = kExWaves * kWave;
+    ScopedKernelTimer t(c, OBTG_K_TEMPORAL_SEP);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((q.ex.M + per_wg - 1) / per_wg)), dim3(kExWaves * kWave), lds, c->stream, q);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
+}  // namespace obtg

@@ -192,6 +192,7 @@ int binrow_offset(obtg_ctx* c, int n);  // ensures row C(n,.) is resident; retur
 int comm_gather_pair_minima(::obtg_comm* m, obtg_ctx* c, const double* dY, int B, double max_sep, double* d_min_all);
 int launch_temporal_sep(obtg_ctx* c, const double* dY, int B, double max_sep, int pair_begin,
                         int pair_count, bool min_only, double* d_out, int sel_k = 0, int* d_sel_idx = nullptr);
+int launch_temporal_sep_rows_r0_generic(obtg_ctx* c, const double* dY, int B, double max_sep, double* d_out);   // full rows at R = 0, any-degree kernel, c->R not read
 struct NsParams;
 // What launch_gjk_swarm may fold into its 3-D sweep launch (k_pair_sweep_3d): the row's temporal-separation block and,
 // when d_out_speed is set, its speed rows.  did_* report what the launch took over.
@@ -290,5 +291,14 @@ int launch_coll_check(obtg_ctx* c, const double* d_curves, int K, const int* d_p
 int launch_coll_check2poly(obtg_ctx* c, const double* d_curves, int K, const double* d_soa, const int* d_off, const int* d_pc,
                            const int* d_pp, int n_pairs, int max_iter, int md_cap, int max_nodes, double* d_stack, double* d_res,
                            int* d_info, int* d_queue, int max_poly_K, bool planar);      // planar: curves AND polygons
+
+// ---------------------------------------------------------------- launchers (extrema_kernels.hip): true Bernstein extrema
+bool bern_extrema_supported(int K);                    // 1 <= K <= 64: a row is a row of lanes
+int launch_bern_extrema(obtg_ctx* c, const double* d_c, long M, int K, int want_max, double eps_rel, double eps_abs,
+                        int max_nodes, double* d_val, double* d_t, double* d_bound, int* d_nodes, int* d_status,
+                        int kernel_id = OBTG_K_BERN);     // every output but d_val nullable
+// the fused form for the fast-kernel list's shapes; OBTG_ERR_UNSUPPORTED: go through obtg_temporal_sep's R = 0 rows
+int launch_temporal_sep_true_min(obtg_ctx* c, const double* dY, int B, double max_sep, double eps_rel, int max_nodes,
+                                 double* d_out, double* d_t, int* d_status);
 
 }  // namespace obtg

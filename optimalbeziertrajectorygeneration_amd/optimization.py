@@ -270,8 +270,11 @@ class BezOptimization(object):
         # 'active' (round 5; SURVEY.md 8(f) item 4 as worded: "only active / near-active constraint rows"): per pair its
         # `activeRows` SMALLEST elevated control points, in control-point order (1..4; obtg_temporal_sep_active) -- a fixed number of rows, so
         # SLSQP's constraint count is constant, but more than the single piecewise-smooth minimum that makes it stall.
-        if separationRows not in ('all', 'min', 'active'):
-            raise ValueError("separationRows must be 'all', 'min' or 'active', not {!r}".format(separationRows))
+        # 'true_min': per pair the true minimum over the trajectory's time of the squared separation minus maxSep^2
+        # (obtg_temporal_sep_true_min) -- the tight continuous-time value that the control points only bound from below
+        # and that DEG_ELEV exists to approach: P rows whatever DEG_ELEV is.
+        if separationRows not in ('all', 'min', 'active', 'true_min'):
+            raise ValueError("separationRows must be 'all', 'min', 'active' or 'true_min', not {!r}".format(separationRows))
         if separationRows == 'active' and not 1 <= int(activeRows) <= 4:
             raise ValueError("activeRows must be 1..4, not {!r}".format(activeRows))
         self.activeRows = int(activeRows)
@@ -344,6 +347,31 @@ class BezOptimization(object):
     def _active_k(self):
         """rows per pair of separationRows='active': never more than a pair has control points"""
         return min(self.activeRows, 2 * self.model['deg'] + int(DEG_ELEV) + 1)
+
+    # separationRows='true_min': the rows are differenced with h = FD_STEP (1.5e-8), so the search's own slack must sit far
+    # below h x the rows' slope: at the library's default eps_rel = 1e-9 a search path that differs between row 0 and row k
+    # would put up to 1e-9 s / 1.5e-8 = 0.07 s into a difference; at 1e-12 it is 7e-5 s, for two or three more bisection
+    # levels (the bracket closes as 4^-depth).  1e-12 s is still above the rounding of a degree-40 de Casteljau split.
+    TRUE_MIN_EPS_REL = 1e-12
+
+    def _true_min(self, ctx, Y):
+        """separationRows='true_min': [B][P] true per-pair minima; a search that ran out of budget raises (bezier._raise_md)"""
+        return self._true_min_checked(ctx, Y)['val']
+
+    def _true_min_checked(self, ctx, Y):
+        r = ctx.temporal_sep_true_min(Y, self.model['maxSep'], eps_rel=self.TRUE_MIN_EPS_REL)
+        bad = np.flatnonzero(r['status'].ravel() != _capi.MD_OK)
+        if bad.size:
+            bez._raise_md(int(r['status'].ravel()[bad[0]]), 'temporalSeparationConstraints(true_min)')
+        return r
+
+    def trueMinSeparation(self, x):
+        """(val[P], t_star[P]): per pair of vehicles / point obstacles, in the order of temporalSeparationConstraints, the true
+        minimum over the trajectory of the squared separation (normSquare's (d/2) factor kept) minus maxSep^2, and the
+        parameter in [0, 1] where it is reached (obtg_temporal_sep_true_min) -- whatever `separationRows` is."""
+        with_obs = self.pointObstacles is not None
+        r = self._true_min_checked(self._ctx(with_obs), self.reshapeVector(x)[None])
+        return r['val'][0], r['t_star'][0]
 
     def _timeopt(self):
         return self.model['minGoal'].lower() == 'timeopt'
@@ -430,6 +458,8 @@ class BezOptimization(object):
                 return self._ctx(with_obs).temporal_sep_min(y, self.model['maxSep'])[0]
             if self.separationRows == 'active':  # per pair its k smallest control points, selected on the device
                 return self._ctx(with_obs).temporal_sep_active(y, self.model['maxSep'], self._active_k())[0]
+            if self.separationRows == 'true_min':
+                return self._true_min(self._ctx(with_obs), y)[0]
             return self._ctx(with_obs).temporal_sep(y, self.model['maxSep'])[0]
         return wrapper
 
@@ -645,6 +675,8 @@ class BezOptimization(object):
                 F = self._ctx(with_obs).temporal_sep_min(Y, self.model['maxSep'])
             elif self.separationRows == 'active':
                 F = self._ctx(with_obs).temporal_sep_active(Y, self.model['maxSep'], self._active_k())
+            elif self.separationRows == 'true_min':
+                F = self._true_min(self._ctx(with_obs), Y)
             else:
                 F = self._ctx(with_obs).temporal_sep(Y, self.model['maxSep'])
         else:
@@ -671,8 +703,11 @@ class BezOptimization(object):
         separationRows 'min' / 'active' its rows are those of the control points the value kernels select at x."""
         _check_method(method)
         if method == 'exact':
+            if self.separationRows == 'true_min':
+                raise ValueError("temporalSeparationJacobian(method='exact') is not available with separationRows='true_min' "
+                                 "(the envelope derivative is not built): use method='fd'")
             return self._temporal_sep_jac_exact(x)
-        if not structured or self.separationRows == 'active':
+        if not structured or self.separationRows in ('active', 'true_min'):
             # 'active': the forward differences of the order statistics themselves -- what SciPy builds from n_x + 1 calls
             # of the closure -- from one batched call (k values per pair and row leave the device, not 2n+R+1)
             return self._jac(x, 'tsep')

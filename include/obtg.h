@@ -88,7 +88,9 @@ const char* obtg_strerror(int code);
  *      (OBTG_K_COUNT moved from 8 to 9).
  *      Later, still 7: new: the collision checks obtg_coll_check, obtg_coll_check2poly (timed under OBTG_K_MIN_DIST).
  *      Later, still 7: new: the true Bernstein extrema obtg_bern_extrema[_dev] (timed under OBTG_K_BERN) and
- *      obtg_temporal_sep_true_min[_dev] (timed under OBTG_K_TEMPORAL_SEP). */
+ *      obtg_temporal_sep_true_min[_dev] (timed under OBTG_K_TEMPORAL_SEP).
+ *      Later, still 7: new: obtg_ctx_set_fd_view_structured.  obtg_constraint_sweep_dev with dY = NULL inside a view now
+ *      takes the structured step where it applies: the same arrays with the same bits, so no meaning changed. */
 #define OBTG_ABI_VERSION 7
 int obtg_abi_version(void);
 
@@ -326,7 +328,15 @@ int obtg_pair_sweep_dev(obtg_ctx*, const double* dY, int B, double max_sep, doub
 /* EVERY constraint family of the batch in one call: obtg_pair_sweep_dev (temporal separation + gjkNew hull sweep) and
  * obtg_dynamics_dev (max/min speed + angular rate; d_out_ang may be NULL) of the same B rows -- what one evaluation of an
  * SLSQP step needs, as the library's best launch sequence for the shape (ONE launch for planar DEG_ELEV = 0 rows and 3-D
- * rows; two for planar DEG_ELEV > 0: the gjkNew sweep, and the separation rows with the speed / angular-rate groups).  Outputs are those of the two separate calls, bit for bit.  dY may be NULL inside an obtg_fd_view. */
+ * rows; two for planar DEG_ELEV > 0: the gjkNew sweep, and the separation rows with the speed / angular-rate groups).  Outputs are those of the two separate calls, bit for bit.  dY may be NULL inside an obtg_fd_view.
+ * Inside a view, with dY = NULL, B the view's B and d_out_ang given, the call says "these rows are x + h e_b": on planar
+ * DEG_ELEV = 0 shapes whose brute-force step is one launch and which the structured step covers (see
+ * obtg_constraint_sweep_fd_structured_dev) the ONE launch is that step (k_step_fd_structured; row-range views included,
+ * still timed as OBTG_K_PAIR_SWEEP) -- the same arrays, bit for bit, d_nsup / d_status written when given, without
+ * evaluating row 0's pairs and vehicles once per row.  Every other shape (3-D, DEG_ELEV > 0, deg + 1 = 21, de-duplication
+ * on, a materialised view, d_out_ang = NULL) and every call with a batch of the caller's (dY != NULL) runs the brute-force
+ * launches as before; OBTG_ERR_UNSUPPORTED is never returned for want of a structured kernel.
+ * obtg_ctx_set_fd_view_structured(ctx, 0) turns the routing off for a context. */
 int obtg_constraint_sweep_dev(obtg_ctx*, const double* dY, const double* d_tf, int B, double max_sep, double* d_out_sep,
                               double speed_bound, int speed_is_max, double max_rate, double* d_out_speed,
                               double* d_out_ang, int max_iter, int md_cap, int* d_flag, double* d_p1, double* d_p2,
@@ -381,7 +391,8 @@ int obtg_unpack_pair_blocks_dev(obtg_ctx*, const double* d_blocks, int B, int n_
  * deg + 1 in {11, 16}, rows of up to 158 KB (256 vehicles of degree 15 are 70 KB: two workgroups per CU):
  * OBTG_ERR_UNSUPPORTED otherwise -- the brute-force call gives the same numbers.  d_tf is read per row: the speed /
  * angular-rate rows of row 0 are copied only into rows whose tf equals tf[0] bit for bit, any other row is evaluated in full.  A different evaluation strategy from
- * "every row in full": bench.py reports it as variants.fd_structured, never as its headline value.  The call is a view
+ * "every row in full" with the same bits: obtg_constraint_sweep_dev inside a view routes to it where it applies, so bench.py's
+ * headline value is this launch and variants.fd_structured repeats it through this entry point.  The call is a view
  * of its own (begin .. end around its launch): with a view of the caller's open on the context it returns OBTG_ERR_ARG
  * instead of replacing and closing that view.
  * ..._rows_dev: the same for the row RANGE [row_begin, row_begin + B) of the batch (what obtg_fd_view_begin_rows views; d_tf and
@@ -404,6 +415,11 @@ int obtg_constraint_sweep_fd_structured_rows_dev(obtg_ctx*, const double* dY0, i
  * vehicle), runs gjkNew only for pairs with a changed hull and copies row 0's outputs for the
  * rest.  Results are identical to the brute-force sweep for any input. */
 int obtg_ctx_set_fd_dedup(obtg_ctx*, int on);
+/* Structured routing of obtg_constraint_sweep_dev inside a view (see there; on by default, and off by default for contexts
+ * created while the environment holds OBTG_FD_VIEW_STRUCTURED=0).  Off: the view's rows are evaluated in full, row by row,
+ * by the brute-force launch.  The outputs are the same bits either way: the switch is for A/B timing on one build and for
+ * tests that want the brute-force launch as the independent side.  obtg_pair_sweep_dev / obtg_dynamics_dev are not routed. */
+int obtg_ctx_set_fd_view_structured(obtg_ctx*, int on);
 /* Trip-count history of the planar sweep (on by default).  Each obtg_gjk_swarm[_dev] call keeps one
  * byte per (row, pair): the number of support scans gjkNew took.  The next call evaluates every
  * workgroup's pairs in descending order of that count, so that the lanes of a wavefront finish and

@@ -92,6 +92,7 @@ _SIGNATURES = {
     "obtg_ctx_set_polygons": (_i, [_vp, _vp, _i, _vp, _i]),
     "obtg_ctx_set_hull_pairs": (_i, [_vp, _vp, _vp, _i]),
     "obtg_ctx_set_fd_dedup": (_i, [_vp, _i]),
+    "obtg_ctx_set_fd_view_structured": (_i, [_vp, _i]),
     "obtg_ctx_set_gjk_history": (_i, [_vp, _i]),
     "obtg_pair_sweep_dev": (_i, [_vp, _vp, _i, _d, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "obtg_gjk_swarm_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -797,6 +798,11 @@ class Context(object):
 
     def set_fd_dedup(self, on):
         self._check(self._lib.obtg_ctx_set_fd_dedup(self._h, int(bool(on))), "obtg_ctx_set_fd_dedup")
+
+    def set_fd_view_structured(self, on):
+        """Structured routing of constraint_sweep_dev(None, ...) inside a view (on by default; OBTG_FD_VIEW_STRUCTURED=0 in
+        the environment makes new contexts start with it off).  Same bits either way."""
+        self._check(self._lib.obtg_ctx_set_fd_view_structured(self._h, int(bool(on))), "obtg_ctx_set_fd_view_structured")
 
     def set_gjk_history(self, on):
         self._check(self._lib.obtg_ctx_set_gjk_history(self._h, int(bool(on))), "obtg_ctx_set_gjk_history")

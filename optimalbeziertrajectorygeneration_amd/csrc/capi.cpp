@@ -234,7 +234,7 @@ const char* obtg_abi_symbols(void)
         "obtg_temporal_sep_fd\0obtg_temporal_sep_fd_dev\0obtg_one_vs_many_min\0obtg_one_vs_many_min_dev\0"
         "obtg_temporal_sep_dev\0obtg_temporal_sep_min_dev\0obtg_speed_dev\0obtg_ang_rate_dev\0obtg_dynamics_dev\0"
         "obtg_fd_batch_dev\0obtg_fd_view_begin\0obtg_fd_view_begin_rows\0obtg_fd_view_end\0obtg_fd_forms_on_the_fly\0obtg_pair_sweep_fd_dev\0obtg_dynamics_fd_dev\0obtg_gjk_pairs\0obtg_ctx_set_polygons\0obtg_ctx_set_hull_pairs\0"
-        "obtg_ctx_set_fd_dedup\0obtg_ctx_set_gjk_history\0obtg_pair_sweep_dev\0obtg_constraint_sweep_dev\0obtg_constraint_sweep_fd_structured_dev\0obtg_constraint_sweep_fd_structured_rows_dev\0obtg_gjk_swarm_dev\0obtg_gjk_swarm\0obtg_min_dist\0obtg_min_dist_robust\0obtg_min_dist2poly\0obtg_min_dist2poly_robust\0obtg_gjk_true_pairs\0obtg_coll_check\0obtg_coll_check2poly\0"
+        "obtg_ctx_set_fd_dedup\0obtg_ctx_set_fd_view_structured\0obtg_ctx_set_gjk_history\0obtg_pair_sweep_dev\0obtg_constraint_sweep_dev\0obtg_constraint_sweep_fd_structured_dev\0obtg_constraint_sweep_fd_structured_rows_dev\0obtg_gjk_swarm_dev\0obtg_gjk_swarm\0obtg_min_dist\0obtg_min_dist_robust\0obtg_min_dist2poly\0obtg_min_dist2poly_robust\0obtg_gjk_true_pairs\0obtg_coll_check\0obtg_coll_check2poly\0"
         "obtg_bern_extrema\0obtg_bern_extrema_dev\0obtg_temporal_sep_true_min\0obtg_temporal_sep_true_min_dev\0"
         "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_eval\0"
         "obtg_euclidean_obj\0obtg_accel_obj\0obtg_jerk_obj\0"
@@ -268,6 +268,8 @@ int obtg_ctx_create(obtg_ctx** out, int n_veh, int dim, int deg, int deg_elev, i
     c->stream = c->own_stream;
     // OBTG_ZERO_COPY=0 keeps every staging buffer in device memory (the path for large batches)
     { const char* e = getenv("OBTG_ZERO_COPY"); const bool zc = !(e && e[0] == '0'); c->ws_in.io = c->ws_in2.io = c->ws_out.io = zc; }
+    // OBTG_FD_VIEW_STRUCTURED=0: contexts start with the structured routing of a view's one-call sweep off (obtg_ctx_set_fd_view_structured)
+    { const char* e = getenv("OBTG_FD_VIEW_STRUCTURED"); c->fd_view_structured = !(e && e[0] == '0'); }
     int rc = OBTG_OK;
     c->h_pairs.resize((size_t)2 * c->n_pairs);
     {
@@ -1086,6 +1088,13 @@ int obtg_ctx_set_fd_dedup(obtg_ctx* c, int on)
     return OBTG_OK;
 }
 
+int obtg_ctx_set_fd_view_structured(obtg_ctx* c, int on)
+{
+    if (!check_ctx(c)) return OBTG_ERR_ARG;
+    c->fd_view_structured = on != 0;
+    return OBTG_OK;
+}
+
 int obtg_pair_sweep_dev(obtg_ctx* c, const double* dY, int B, double max_sep, double* d_out_sep, int max_iter,
                         int md_cap, int* d_flag, double* d_p1, double* d_p2, double* d_dist, int* d_nsup,
                         int* d_status)
@@ -1108,6 +1117,21 @@ int obtg_constraint_sweep_dev(obtg_ctx* c, const double* dY, const double* d_tf,
     if (!c->hull_pairs_set) return OBTG_ERR_ARG;
     if (d_out_ang && c->dim != 2) return OBTG_ERR_ARG;
     (void)hipSetDevice(c->device);
+    // The whole batch of an open view, every family wanted: its rows are row 0 with one control point of one vehicle
+    // advanced, and the structured step (k_step_fd_structured) fills the same arrays with the same bits without evaluating
+    // row 0's pairs and vehicles again for every row.  Decided before anything is launched: only shapes the structured
+    // kernel covers, and only where the brute-force form is itself ONE launch (DEG_ELEV > 0 keeps its two launches); any
+    // other shape takes the path below with no launch spent and the sweep's trip-count history untouched.
+    if (!dY && c->view.Y0 && B == c->view.B && B > 0 && !c->view.materialised && d_out_ang && c->fd_view_structured &&
+        constraint_sweep_is_one_launch(c, B) && step_fd_structured_supported(c)) {
+        SweepFold sp;
+        sp.d_tf = d_tf; sp.speed_bound = speed_bound; sp.speed_is_max = speed_is_max;
+        sp.d_out_speed = d_out_speed; sp.d_out_ang = d_out_ang; sp.max_rate = max_rate;
+        c->fd.Y0 = c->view.Y0; c->fd.h = c->view.h; c->fd.fixed = c->view.fixed; c->fd.row0 = c->view.row0;
+        const int rc = launch_step_fd_structured(c, B, max_sep, d_out_sep, max_iter, md_cap, d_flag, d_p1, d_p2, d_dist, d_nsup, d_status, &sp);
+        c->fd.Y0 = nullptr; c->fd.row0 = 0;
+        if (rc != OBTG_ERR_UNSUPPORTED) return rc;     // (the launcher answers that before it launches: the brute-force sweep below)
+    }
     return with_batch(c, dY, B, pair_sweep_can_fd(c) && dynamics_can_fd(c, true, d_out_ang != nullptr), [&](const double* src) {
         SweepFold sp;
         sp.d_tf = d_tf; sp.speed_bound = speed_bound; sp.speed_is_max = speed_is_max;

@@ -3811,14 +3811,43 @@ int launch_pair_sweep(obtg_ctx* c, const double* dY, int B, double max_sep, doub
     return OBTG_OK;
 }
 
-// obtg_constraint_sweep_fd_structured_dev: the whole step of an FD view as ONE launch that evaluates row 0 in full and,
-// per perturbed row, only what its vehicle touches (k_step_fd_structured).  OBTG_ERR_UNSUPPORTED for shapes outside the
-// one-launch planar sweep (the caller uses the brute-force sweep, whose results are the same).
-int launch_step_fd_structured(obtg_ctx* c, int B, double max_sep, double* d_out_sep, int max_iter, int md_cap, int* d_flag,
-                              double* d_p1, double* d_p2, double* d_dist, int* d_nsup, int* d_status, SweepFold* speed)
+// Is obtg_constraint_sweep_dev with all three row families ONE launch for this context and batch size -- launch_pair_sweep
+// with the speed / angular-rate groups as the grid's last workgroups, in its one-launch or its tiled form?  Mirrors
+// launch_pair_sweep's decisions and launches nothing (the tiled form's chunk tables are built, as its launch would).
+// DEG_ELEV > 0 is never one launch (gjkNew sweep + separation rows with the dynamics groups among them).
+bool constraint_sweep_is_one_launch(obtg_ctx* c, int B)
 {
-    if (B <= 0) return OBTG_OK;
-    if (!c->fd.Y0) return OBTG_ERR_ARG;
+    const int nc = c->deg + 1;
+    if (B <= 0 || !nc_in_dyn(nc)) return false;
+    if (!(c->dim == 2 && c->polys_planar && c->max_poly_K <= nc && c->n_hull_pairs > 0 && !c->fd_dedup && c->R == 0 &&
+          c->n_pairs > 0)) return false;
+    if (getenv("OBTG_FOLD_DYNAMICS") && getenv("OBTG_FOLD_DYNAMICS")[0] == '0') return false;
+    if (ensure_tables(c) != OBTG_OK || c->d_ang_w22n.p == nullptr) return false;
+    const int L4 = 4 * c->deg + 1, L = 2 * c->deg + 1;
+    const size_t lds_dyn = sizeof(double) * ((size_t)kWave * L4 + (size_t)(kWave / 2) * L);
+    size_t lds = sweep_shape(c, B, nc, kPairSweepWavesPerSimd, kPairSweepChunk).lds;
+    if (pair_sweep_tile_rows(c, nc, lds) > 0 && lds <= 48 * 1024)
+        return nc <= 11 && std::max(lds, lds_dyn) <= (size_t)160 * 1024 / kPairSweepWavesPerSimd - 1280;
+    if (c->n_obs != 0 || lds <= 48 * 1024) return false;
+    const int vpq = nc | 1;                // large rows: the tiled sweep
+    if (build_tiles(c, vpq) != OBTG_OK || !c->tile_ts_ok) return false;
+    const size_t ldst = planar_lds_bytes<2>(c->tile_max_objs, vpq, c->tile_max_pairs);
+    const int tpf = (L % 2 == 0) ? L + 1 : L;
+    if (ldst > 64 * 1024 || (size_t)4 * 8 * tpf * sizeof(double) > ldst - (size_t)16 * c->tile_max_objs * vpq) return false;
+    return std::max(ldst, lds_dyn) <= (size_t)160 * 1024 / 4 - 1280;
+}
+
+// Which shapes k_step_fd_structured covers, decided without launching anything: the launcher and the router of
+// obtg_constraint_sweep_dev (capi.cpp) share it, in the spirit of pair_sweep_is_one_launch.  OBTG_ERR_UNSUPPORTED: not this
+// shape (3-D, degree 20, obtg_ctx_set_ang_rate_order(2) with DEG_ELEV > 0, de-duplication on, rows beyond 158 KB of LDS).
+struct StructuredPlan {
+    void (*kern)(const StructuredParams) = nullptr;
+    size_t lds = 0;
+    int gjk_chunk_pairs = 80;
+    bool dyn_split = false;
+};
+static int step_fd_structured_plan(obtg_ctx* c, StructuredPlan& pl)
+{
     if (c->ang_exact && c->R > 0) return OBTG_ERR_UNSUPPORTED;   // (obtg_ctx_set_ang_rate_order(2): the double-double pass follows the brute-force launches)
     const int nc = c->deg + 1;
     void (*kern)(const StructuredParams) = nullptr;
@@ -3839,14 +3868,67 @@ int launch_step_fd_structured(obtg_ctx* c, int B, double max_sep, double* d_out_
         default: break;
     }
     const bool ok = kern && c->dim == 2 && c->polys_planar && c->max_poly_K <= nc && c->n_hull_pairs > 0 && !c->fd_dedup &&
-                    c->n_pairs > 0 && speed && speed->d_out_ang && speed->d_out_speed &&
-                    speed->d_tf && d_out_sep && c->n_veh + c->n_obs < 65535 && 2 * c->deg + c->R + 1 <= 512;      // (object ids as 16-bit halves of a word)
+                    c->n_pairs > 0 && c->n_veh + c->n_obs < 65535 && 2 * c->deg + c->R + 1 <= 512;      // (object ids as 16-bit halves of a word)
     if (!ok) return OBTG_ERR_UNSUPPORTED;
     int rc = ensure_tables(c);
     if (rc) return rc;
     if (c->d_ang_w22n.p == nullptr) return OBTG_ERR_UNSUPPORTED;
     if (elev && (c->ang_elevate_first || c->d_ang_T4.p == nullptr || c->d_ang_cv2.p == nullptr || c->d_Tf.p == nullptr))
         return OBTG_ERR_UNSUPPORTED;
+    const int n_obj = c->n_veh + c->n_poly, vpq = nc | 1, L = 2 * c->deg + 1, LR = L + c->R;
+    // G: chunks of ~80 hull pairs (one short gjkNew phase per workgroup)
+    pl.gjk_chunk_pairs = 16 * (size_t)n_obj * vpq > 40 * 1024 ? 64 : 80;       // (large rows: the chunk's results behind 70 KB of hulls stay under 80 KB)
+    if (const char* e = getenv("OBTG_STRUCT_GJK_CHUNK")) pl.gjk_chunk_pairs = std::max(16, atoi(e));
+    // (DEG_ELEV > 0: stream workgroups of 16 vehicles that collect their rows in LDS -- while that area fits beside the tables)
+    pl.dyn_split = elev && !(getenv("OBTG_STRUCT_DYN_SPLIT") && getenv("OBTG_STRUCT_DYN_SPLIT")[0] == '0') &&
+                   sizeof(double) * (dyn_elev_lds_doubles(c->deg, c->R) + dyn_elev_stage_doubles(c->deg, c->R)) <= 72 * (size_t)1024;
+    const int n_sobj = c->n_veh + c->n_obs;                  // what an S workgroup stages: vehicles and point obstacles
+    size_t lds_s = std::max((size_t)16 * n_sobj * vpq, sizeof(double) * kWave * L);      // (flat: the tile overlays the staged row)
+    size_t lds_d_elev = 0;
+    if (elev) {
+        // staged row + the group's coefficient image [64][PA] + one 16-row output tile of up to 128 columns
+        const int KS = (L + 3) / 4, PA = 4 * KS + 2;
+        lds_s = (size_t)16 * n_sobj * vpq + sizeof(double) * (kWave * PA + 16 * (size_t)std::min(LR, 128));
+        lds_d_elev = sizeof(double) * (dyn_elev_lds_doubles(c->deg, c->R) + (pl.dyn_split ? dyn_elev_stage_doubles(c->deg, c->R) : 0));
+    }
+    const size_t lds_g = (planar_lds_bytes<0>(n_obj, vpq, pl.gjk_chunk_pairs) + 15) / 16 * 16 + (size_t)pl.gjk_chunk_pairs * 68 + 16;
+    size_t lds_f = std::max(planar_lds_bytes<1>(n_obj, vpq, 256), (size_t)16 * (n_obj + c->n_obs) * vpq);      // (256: StructuredParams::fix_chunk)
+    if (elev) {                        // the fix-up rows' image [32][PA] and tile behind the staged objects
+        const int KS = (L + 3) / 4, PA = 4 * KS + 2;
+        lds_f = std::max(lds_f, (size_t)16 * (n_obj + c->n_obs) * vpq + sizeof(double) * (32 * PA + 16 * (size_t)std::min(LR, 128)));
+    }
+    const size_t lds_d = sizeof(double) * ((size_t)kWave * (4 * c->deg + 1) + (size_t)kWave * L);
+    const size_t lds = std::max(std::max(lds_s, lds_g), std::max(lds_f, elev ? lds_d_elev : lds_d));
+    if (lds > (elev ? 76 : 40) * (size_t)1024) {
+        const size_t with_static = lds + 1536;               // (the kernel's own __shared__ variables)
+        if (kern_mid && with_static <= 80 * (size_t)1024) kern = kern_mid;
+        else if (kern_big && with_static <= 158 * (size_t)1024) kern = kern_big;
+        else return OBTG_ERR_UNSUPPORTED;
+    }
+    pl.kern = kern; pl.lds = lds;
+    return OBTG_OK;
+}
+
+bool step_fd_structured_supported(obtg_ctx* c)
+{
+    StructuredPlan pl;
+    return step_fd_structured_plan(c, pl) == OBTG_OK;
+}
+
+// obtg_constraint_sweep_fd_structured_dev: the whole step of an FD view as ONE launch that evaluates row 0 in full and,
+// per perturbed row, only what its vehicle touches (k_step_fd_structured).  OBTG_ERR_UNSUPPORTED for shapes outside the
+// one-launch planar sweep (the caller uses the brute-force sweep, whose results are the same); nothing is launched then.
+int launch_step_fd_structured(obtg_ctx* c, int B, double max_sep, double* d_out_sep, int max_iter, int md_cap, int* d_flag,
+                              double* d_p1, double* d_p2, double* d_dist, int* d_nsup, int* d_status, SweepFold* speed)
+{
+    if (B <= 0) return OBTG_OK;
+    if (!c->fd.Y0) return OBTG_ERR_ARG;
+    if (!(speed && speed->d_out_ang && speed->d_out_speed && speed->d_tf && d_out_sep)) return OBTG_ERR_UNSUPPORTED;
+    StructuredPlan pl;
+    if (int rc = step_fd_structured_plan(c, pl)) return rc;
+    const int nc = c->deg + 1;
+    const bool elev = c->R > 0;
+    void (*kern)(const StructuredParams) = pl.kern;
     StructuredParams sp{};
     GjkSwarmParams& p = sp.g;
     p.Y = c->fd.Y0; p.fd = 1 + c->fd.row0; p.fd_fixed = c->fd.fixed; p.fd_h = c->fd.h;
@@ -3880,7 +3962,7 @@ int launch_step_fd_structured(obtg_ctx* c, int B, double max_sep, double* d_out_
         d.W2n = c->d_ang_w2n.as<double>(); d.W22n = c->d_ang_w22n.as<double>(); d.Wn = c->d_ang_wn.as<double>();
         d.fd = p.fd; d.fd_fixed = p.fd_fixed; d.fd_h = p.fd_h;
     }
-    const int n_obj = c->n_veh + c->n_poly, vpq = nc | 1, L = 2 * c->deg + 1, LR = L + c->R;
+    const int L = 2 * c->deg + 1, LR = L + c->R;
     // S: one workgroup per (64-pair group, row range); about two thousand workgroups of streams
     sp.n_sep_groups = (c->n_pairs + kWave - 1) / kWave;
     // (a large step -- C4: 58 GB of separation rows -- gets more, so that a stream stays near 4 MB)
@@ -3896,8 +3978,7 @@ int launch_step_fd_structured(obtg_ctx* c, int B, double max_sep, double* d_out_
     sp.sep_rows_per = (B + s_ranges - 1) / s_ranges;
     s_ranges = (B + sp.sep_rows_per - 1) / sp.sep_rows_per;
     // G: chunks of ~80 hull pairs (one short gjkNew phase per workgroup), row ranges for ~512 workgroups
-    sp.gjk_chunk_pairs = 16 * (size_t)n_obj * vpq > 40 * 1024 ? 64 : 80;       // (large rows: the chunk's results behind 70 KB of hulls stay under 80 KB)
-    if (const char* e = getenv("OBTG_STRUCT_GJK_CHUNK")) sp.gjk_chunk_pairs = std::max(16, atoi(e));
+    sp.gjk_chunk_pairs = pl.gjk_chunk_pairs;
     const int g_target = getenv("OBTG_STRUCT_GJK_WGS") ? std::max(1, atoi(getenv("OBTG_STRUCT_GJK_WGS")))
                                                        : (int)std::min(1024.0, std::max(192.0, 2.6 * B));
     sp.gjk_chunks = (c->n_hull_pairs + sp.gjk_chunk_pairs - 1) / sp.gjk_chunk_pairs;
@@ -3916,9 +3997,7 @@ int launch_step_fd_structured(obtg_ctx* c, int B, double max_sep, double* d_out_
     // group, and one workgroup per 8 rows that looks for rows with their own tf
     sp.dyn_groups_per_row = (c->n_veh + kWave - 1) / kWave;
     sp.dyn_rows_per = std::min(64, std::max((B + 255) / 256, std::min(4, B)));
-    // (DEG_ELEV > 0: stream workgroups of 16 vehicles that collect their rows in LDS -- while that area fits beside the tables)
-    sp.dyn_split = elev && !(getenv("OBTG_STRUCT_DYN_SPLIT") && getenv("OBTG_STRUCT_DYN_SPLIT")[0] == '0') &&
-                   sizeof(double) * (dyn_elev_lds_doubles(c->deg, c->R) + dyn_elev_stage_doubles(c->deg, c->R)) <= 72 * (size_t)1024;
+    sp.dyn_split = pl.dyn_split;      // (DEG_ELEV > 0: stream workgroups of 16 vehicles that collect their rows in LDS)
     if (sp.dyn_split) sp.dyn_rows_per = std::min(64, 4 * sp.dyn_rows_per);      // (16 vehicles per stream workgroup instead of 64: the same bytes)
     if (const char* e = getenv("OBTG_STRUCT_DYN_ROWS")) sp.dyn_rows_per = std::max(1, std::min(64, atoi(e)));
     sp.dyn_streams = (sp.dyn_split ? 4 : 1) * sp.dyn_groups_per_row * ((B + sp.dyn_rows_per - 1) / sp.dyn_rows_per);
@@ -3966,29 +4045,7 @@ int launch_step_fd_structured(obtg_ctx* c, int B, double max_sep, double* d_out_
         grid = (unsigned)groups * 16u;
     }
     p.dyn_first_block = 0;
-    const int n_sobj = c->n_veh + c->n_obs;                  // what an S workgroup stages: vehicles and point obstacles
-    size_t lds_s = std::max((size_t)16 * n_sobj * vpq, sizeof(double) * kWave * L);      // (flat: the tile overlays the staged row)
-    size_t lds_d_elev = 0;
-    if (elev) {
-        // staged row + the group's coefficient image [64][PA] + one 16-row output tile of up to 128 columns
-        const int KS = (L + 3) / 4, PA = 4 * KS + 2;
-        lds_s = (size_t)16 * n_sobj * vpq + sizeof(double) * (kWave * PA + 16 * (size_t)std::min(LR, 128));
-        lds_d_elev = sizeof(double) * (dyn_elev_lds_doubles(c->deg, c->R) + (sp.dyn_split ? dyn_elev_stage_doubles(c->deg, c->R) : 0));
-    }
-    const size_t lds_g = (planar_lds_bytes<0>(n_obj, vpq, sp.gjk_chunk_pairs) + 15) / 16 * 16 + (size_t)sp.gjk_chunk_pairs * 68 + 16;
-    size_t lds_f = std::max(planar_lds_bytes<1>(n_obj, vpq, sp.fix_chunk), (size_t)16 * (n_obj + c->n_obs) * vpq);
-    if (elev) {                        // the fix-up rows' image [32][PA] and tile behind the staged objects
-        const int KS = (L + 3) / 4, PA = 4 * KS + 2;
-        lds_f = std::max(lds_f, (size_t)16 * (n_obj + c->n_obs) * vpq + sizeof(double) * (32 * PA + 16 * (size_t)std::min(LR, 128)));
-    }
-    const size_t lds_d = sizeof(double) * ((size_t)kWave * (4 * c->deg + 1) + (size_t)kWave * L);
-    const size_t lds = std::max(std::max(lds_s, lds_g), std::max(lds_f, elev ? lds_d_elev : lds_d));
-    if (lds > (elev ? 76 : 40) * (size_t)1024) {
-        const size_t with_static = lds + 1536;               // (the kernel's own __shared__ variables)
-        if (kern_mid && with_static <= 80 * (size_t)1024) kern = kern_mid;
-        else if (kern_big && with_static <= 158 * (size_t)1024) kern = kern_big;
-        else return OBTG_ERR_UNSUPPORTED;
-    }
+    const size_t lds = pl.lds;
     if (lds > 48 * 1024)
         OBTG_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     TimelineDump tl(c, grid, p.timeline);

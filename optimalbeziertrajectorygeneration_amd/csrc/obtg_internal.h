@@ -115,6 +115,7 @@ struct obtg_ctx {
     int n_poly = 0, n_poly_pts = 0, max_poly_K = 0;
     bool polys_planar = true;   // every registered polygon vertex has z == 0
     bool fd_dedup = false;      // reuse row 0's GJK results for bit-identical hull pairs
+    bool fd_view_structured = true;   // obtg_ctx_set_fd_view_structured: the one-call sweep of a view takes the structured step where it applies
     obtg::DevBuf d_hp_a, d_hp_b;  // hull pair list
     obtg::DevBuf d_vp_off, d_vp_idx;   // per vehicle: the positions of the hull pairs that contain it (CSR; structured FD step)
     std::vector<int> h_hp_a, h_hp_b;   // host copy (tile-major chunking of large rows)
@@ -233,6 +234,8 @@ bool dynamics_fd_on_the_fly(const obtg_ctx* c, bool want_ang);
 int ang_rate_order_in_effect(obtg_ctx* c);
 bool bernstein_fd_on_the_fly(const obtg_ctx* c);      // the separate temporal-separation / speed kernels form a view's rows themselves
 bool pair_sweep_is_one_launch(const obtg_ctx* c);
+bool constraint_sweep_is_one_launch(obtg_ctx* c, int B);    // launch_pair_sweep with the dynamics groups folded in: one launch for B rows?
+bool step_fd_structured_supported(obtg_ctx* c);             // launch_step_fd_structured has a kernel for this context (given all outputs); launches nothing
 int launch_bern_elev(obtg_ctx* c, const double* d_in, int rows, int n, int R, double* d_out);
 int launch_bern_diff(obtg_ctx* c, const double* d_in, int rows, int n, double T, double* d_out);
 int launch_bern_split(obtg_ctx* c, const double* d_in, int rows, int n, double z, double* d_left, double* d_right);

@@ -223,6 +223,31 @@ def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+# -- arguments of the batched pair searches (Context.gjk_pairs .. coll_check2poly), as the C ABI takes them
+def _curves_arg(curves):
+    """curves[n_curves][3][K] -> (array, n_curves, K)"""
+    curves = _f64(curves)
+    n_curves, _, K = curves.shape
+    return curves, n_curves, K
+
+
+def _polys_arg(pts, off):
+    """-> (pts[n_pts][3], off[n_poly + 1])"""
+    return _f64(pts).reshape(-1, 3), _i32(off)
+
+
+def _pairs_arg(pair_a, pair_b):
+    """-> (pair_a, pair_b, n_pairs)"""
+    pa, pb = _i32(pair_a), _i32(pair_b)
+    return pa, pb, pa.shape[0]
+
+
+def _search_out(n, width, zeroed=False):
+    """Outputs of a curve search over n pairs: res[n][width] (res[n] for width 1), info[n][4], status[n]."""
+    shape = n if width == 1 else (n, width)
+    return np.zeros(shape) if zeroed else np.empty(shape), np.zeros((n, 4), np.int32), np.zeros(n, np.int32)
+
+
 def _prefer_torch_rccl():
     """One RCCL per process, as for the HIP runtime: PyTorch bundles a librccl.so; when it is there and the caller has not
     chosen a file, comm.cpp is told to open that one (OBTG_RCCL_LIB) so that obtg_comm_* and torch.distributed share it."""
@@ -756,10 +781,8 @@ class Context(object):
 
     # -- GJK
     def gjk_pairs(self, pts, off, pair_a, pair_b, max_iter=128, md_cap=4096, trace_cap=0):
-        pts = _f64(pts).reshape(-1, 3)
-        off = _i32(off)
-        pa, pb = _i32(pair_a), _i32(pair_b)
-        n = pa.shape[0]
+        pts, off = _polys_arg(pts, off)
+        pa, pb, n = _pairs_arg(pair_a, pair_b)
         flag = np.zeros(n, np.int32)
         nsup = np.zeros(n, np.int32)
         status = np.zeros(n, np.int32)
@@ -860,108 +883,59 @@ class Context(object):
             _vp(d_flag), _vp(d_p1), _vp(d_p2), _vp(d_dist), _vp(d_nsup) if d_nsup else None,
             _vp(d_status) if d_status else None), "obtg_constraint_sweep_fd_structured_rows_dev")
 
+    def _curve_search(self, name, curves, polys, pairs, params, width, zeroed=False, info_keys=("gjk_calls", "depth")):
+        """One of the six curve searches of the C ABI, which all take (curves, [polygons,] pair lists, the call's own scalars,
+        res, info, status).  polys: (pts, off) or None; pairs: (first, second); width: doubles of res per pair."""
+        curves, n_curves, K = _curves_arg(curves)
+        args = [self._h, _ptr(curves), n_curves, K]
+        if polys is not None:
+            pts, off = _polys_arg(*polys)
+            args += [_ptr(pts), pts.shape[0], _ptr(off), off.shape[0] - 1]
+        pa, pb, n = _pairs_arg(*pairs)
+        res, info, status = _search_out(n, width, zeroed)
+        self._check(getattr(self._lib, name)(*args, _ptr(pa), _ptr(pb), n, *params, _ptr(res), _ptr(info), _ptr(status)), name)
+        return {"res": res, "nodes": info[:, 0], info_keys[0]: info[:, 1], info_keys[1]: info[:, 2], "status": status}
+
     def min_dist(self, curves, pair_a, pair_b, eps=1e-9, max_iter=128, md_cap=4096, max_depth=64,
                  max_nodes=200000):
         """curves[n][3][K] (2-D curves: pass a zero z row)."""
-        curves = _f64(curves)
-        n_curves, _, K = curves.shape
-        pa, pb = _i32(pair_a), _i32(pair_b)
-        n = pa.shape[0]
-        res = np.empty((n, 3))
-        info = np.zeros((n, 4), np.int32)
-        status = np.zeros(n, np.int32)
-        self._check(self._lib.obtg_min_dist(self._h, _ptr(curves), n_curves, K, _ptr(pa), _ptr(pb), n, float(eps),
-                                            max_iter, md_cap, max_depth, max_nodes, _ptr(res), _ptr(info),
-                                            _ptr(status)), "obtg_min_dist")
-        return dict(res=res, nodes=info[:, 0], gjk_calls=info[:, 1], depth=info[:, 2], status=status)
+        return self._curve_search("obtg_min_dist", curves, None, (pair_a, pair_b),
+                                  (float(eps), max_iter, md_cap, max_depth, max_nodes), 3)
 
     def min_dist_robust(self, curves, pair_a, pair_b, eps=1e-9, max_nodes=200000):
         """Robust branch & bound (obtg_min_dist_robust): true minimum within relative eps when status == MD_OK."""
-        curves = _f64(curves)
-        n_curves, _, K = curves.shape
-        pa, pb = _i32(pair_a), _i32(pair_b)
-        n = pa.shape[0]
-        res = np.empty((n, 3))
-        info = np.zeros((n, 4), np.int32)
-        status = np.zeros(n, np.int32)
-        self._check(self._lib.obtg_min_dist_robust(self._h, _ptr(curves), n_curves, K, _ptr(pa), _ptr(pb), n, float(eps),
-                                                   int(max_nodes), _ptr(res), _ptr(info), _ptr(status)),
-                    "obtg_min_dist_robust")
-        return dict(res=res, nodes=info[:, 0], levels=info[:, 1], frontier=info[:, 2], status=status)
+        return self._curve_search("obtg_min_dist_robust", curves, None, (pair_a, pair_b), (float(eps), int(max_nodes)), 3,
+                                  info_keys=("levels", "frontier"))
 
     def min_dist2poly(self, curves, pts, off, pair_curve, pair_poly, eps=1e-6, max_iter=128, md_cap=4096,
                       max_depth=64, max_nodes=200000):
-        curves = _f64(curves)
-        n_curves, _, K = curves.shape
-        pts = _f64(pts).reshape(-1, 3)
-        off = _i32(off)
-        pc, pp = _i32(pair_curve), _i32(pair_poly)
-        n = pc.shape[0]
-        res = np.empty((n, 5))
-        info = np.zeros((n, 4), np.int32)
-        status = np.zeros(n, np.int32)
-        self._check(self._lib.obtg_min_dist2poly(self._h, _ptr(curves), n_curves, K, _ptr(pts), pts.shape[0],
-                                                 _ptr(off), off.shape[0] - 1, _ptr(pc), _ptr(pp), n, float(eps),
-                                                 max_iter, md_cap, max_depth, max_nodes, _ptr(res), _ptr(info),
-                                                 _ptr(status)), "obtg_min_dist2poly")
-        return dict(res=res, nodes=info[:, 0], gjk_calls=info[:, 1], depth=info[:, 2], status=status)
+        return self._curve_search("obtg_min_dist2poly", curves, (pts, off), (pair_curve, pair_poly),
+                                  (float(eps), max_iter, md_cap, max_depth, max_nodes), 5)
 
     def min_dist2poly_robust(self, curves, pts, off, pair_curve, pair_poly, eps=1e-9, max_nodes=200000):
         """Robust curve <-> polygon distance (obtg_min_dist2poly_robust): true minimum within relative eps when MD_OK."""
-        curves = _f64(curves)
-        n_curves, _, K = curves.shape
-        pts = _f64(pts).reshape(-1, 3)
-        off = _i32(off)
-        pc, pp = _i32(pair_curve), _i32(pair_poly)
-        n = pc.shape[0]
-        res = np.empty((n, 5))
-        info = np.zeros((n, 4), np.int32)
-        status = np.zeros(n, np.int32)
-        self._check(self._lib.obtg_min_dist2poly_robust(self._h, _ptr(curves), n_curves, K, _ptr(pts), pts.shape[0], _ptr(off),
-                                                        off.shape[0] - 1, _ptr(pc), _ptr(pp), n, float(eps), int(max_nodes),
-                                                        _ptr(res), _ptr(info), _ptr(status)), "obtg_min_dist2poly_robust")
-        return dict(res=res, nodes=info[:, 0], levels=info[:, 1], frontier=info[:, 2], status=status)
+        return self._curve_search("obtg_min_dist2poly_robust", curves, (pts, off), (pair_curve, pair_poly),
+                                  (float(eps), int(max_nodes)), 5, info_keys=("levels", "frontier"))
 
     def coll_check(self, curves, pair_a, pair_b, eps=1e-9, max_iter=128, md_cap=4096, max_nodes=200000):
         """_collCheckBez2Bez (bezier.py:1561-1614) on every pair (obtg_coll_check): res[n] is the reference's return value --
         1 (no collision), -1 (its cnt > 100), 0.0 or the smallest end-point distance met -- where status is MD_OK (0 beside any
         other status).  curves[n_curves][3][K], K <= 16."""
-        curves = _f64(curves)
-        n_curves, _, K = curves.shape
-        pa, pb = _i32(pair_a), _i32(pair_b)
-        n = pa.shape[0]
-        res = np.zeros(n)
-        info = np.zeros((n, 4), np.int32)
-        status = np.zeros(n, np.int32)
-        self._check(self._lib.obtg_coll_check(self._h, _ptr(curves), n_curves, K, _ptr(pa), _ptr(pb), n, float(eps), int(max_iter),
-                                              int(md_cap), int(max_nodes), _ptr(res), _ptr(info), _ptr(status)), "obtg_coll_check")
-        return dict(res=res, nodes=info[:, 0], gjk_calls=info[:, 1], depth=info[:, 2], status=status)
+        return self._curve_search("obtg_coll_check", curves, None, (pair_a, pair_b),
+                                  (float(eps), int(max_iter), int(md_cap), int(max_nodes)), 1, zeroed=True)
 
     def coll_check2poly(self, curves, pts, off, pair_curve, pair_poly, max_iter=128, md_cap=4096, max_nodes=200000):
         """_collCheckBez2Poly (bezier.py:1617-1651) on every (curve, polygon) pair (obtg_coll_check2poly): res[n] is 1 (no
         collision) or 0 where status is MD_OK.  Polygons as in min_dist2poly, at most 16 vertices each; K <= 16."""
-        curves = _f64(curves)
-        n_curves, _, K = curves.shape
-        pts = _f64(pts).reshape(-1, 3)
-        off = _i32(off)
-        pc, pp = _i32(pair_curve), _i32(pair_poly)
-        n = pc.shape[0]
-        res = np.zeros(n)
-        info = np.zeros((n, 4), np.int32)
-        status = np.zeros(n, np.int32)
-        self._check(self._lib.obtg_coll_check2poly(self._h, _ptr(curves), n_curves, K, _ptr(pts), pts.shape[0], _ptr(off),
-                                                   off.shape[0] - 1, _ptr(pc), _ptr(pp), n, int(max_iter), int(md_cap),
-                                                   int(max_nodes), _ptr(res), _ptr(info), _ptr(status)), "obtg_coll_check2poly")
-        return dict(res=res, nodes=info[:, 0], gjk_calls=info[:, 1], depth=info[:, 2], status=status)
+        return self._curve_search("obtg_coll_check2poly", curves, (pts, off), (pair_curve, pair_poly),
+                                  (int(max_iter), int(md_cap), int(max_nodes)), 1, zeroed=True)
 
     def gjk_true_pairs(self, pts, off, pair_a, pair_b, eps=1e-10, max_iter=64):
         """True hull distances (obtg_gjk_true_pairs; not gjkNew).  status 0: converged with the certificate
         dist - lower <= eps * dist; 1: iteration cap; 2: stalled at rounding level before the certificate closed -- dist is
         then still a distance between hull points and `lower` a proven lower bound: check `lower` (or status)."""
-        pts = _f64(pts).reshape(-1, 3)
-        off = _i32(off)
-        pa, pb = _i32(pair_a), _i32(pair_b)
-        n = pa.shape[0]
+        pts, off = _polys_arg(pts, off)
+        pa, pb, n = _pairs_arg(pair_a, pair_b)
         flag, iters, status = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
         p1, p2, dist, lower = np.empty((n, 3)), np.empty((n, 3)), np.empty(n), np.empty(n)
         self._check(self._lib.obtg_gjk_true_pairs(self._h, _ptr(pts), pts.shape[0], _ptr(off), off.shape[0] - 1, _ptr(pa), _ptr(pb),

@@ -1,6 +1,6 @@
 // C ABI of libobtg_hip.so (include/obtg.h): context, tables, host-buffer entry points.
-// Compiled with hipcc (host code + HIP runtime API); the kernels live in
-// bern_kernels.hip and gjk_kernels.hip.
+// Compiled with hipcc (host code + HIP runtime API); the kernels live in bern_kernels.hip, gjk_kernels.hip,
+// coll_kernels.hip, extrema_kernels.hip and jac_kernels.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -879,6 +879,128 @@ static int check_polys(const int* off, int n_poly, int n_pts)
     return OBTG_OK;
 }
 
+// ------------------------------------------------------------------ batched searches over a pair list
+// The one host path of obtg_gjk_pairs, obtg_gjk_true_pairs, obtg_min_dist[_robust], obtg_min_dist2poly[_robust] and
+// obtg_coll_check[2poly].  Every one of them is: its argument checks (check_polys, check_pairs), upload_operands, the
+// reservation of its outputs (reserve_search / reserve_gjk), its launcher, the download (download_search / download_gjk).
+// The workspace slots are obtg::WsSlot.  The next search entry point starts as a copy of obtg_min_dist_robust (curves
+// only) or obtg_min_dist2poly_robust (curves and polygons): nothing but checks, these helpers and a launcher.
+// What the entry points do NOT share, because a caller could tell the difference -- each keeps the answer it has given since
+// it was added:
+//  - the obtg_gjk_* and obtg_min_dist* calls reject null pair / result pointers whatever n_pairs is, the obtg_coll_check*
+//    calls only when n_pairs > 0;
+//  - obtg_coll_check* answer OBTG_ERR_UNSUPPORTED (more than 16 points) before an empty pair list answers OBTG_OK; in the
+//    others that answer is the launcher's, so an empty list is OBTG_OK whatever K is;
+//  - obtg_gjk_pairs (as obtg_ctx_set_polygons) counts z == -0.0 as planar; the curve searches ask for +0, because a -0
+//    would show in a returned closest point.
+extern "C++" {
+template <class T> static T* slot(obtg_ctx* c, WsSlot s) { return c->ws_misc[s].as<T>(); }
+
+static int check_pairs(const int* a, int na, const int* b, int nb, int n_pairs)
+{
+    for (int k = 0; k < n_pairs; ++k)
+        if (a[k] < 0 || a[k] >= na || b[k] < 0 || b[k] >= nb) return OBTG_ERR_ARG;
+    return OBTG_OK;
+}
+
+// every z of curves[n_curves][3][K] is +0 (2-D curves arrive padded with a zero z row, bezier.py:1294-1308): then the planar
+// gjkNew machine runs (the same bits)
+static bool curves_planar(const double* curves, int n_curves, int K)
+{
+    for (int i = 0; i < n_curves; ++i) {
+        const double* z = curves + ((size_t)i * 3 + 2) * K;
+        for (int j = 0; j < K; ++j) if (z[j] != 0.0 || std::signbit(z[j])) return false;
+    }
+    return true;
+}
+
+// every z of pts[n_pts][3] is zero; plus_zero_only: and none of them is -0
+static bool polys_planar(const double* pts, int n_pts, bool plus_zero_only)
+{
+    for (int k = 0; k < n_pts; ++k) {
+        const double z = pts[3 * (size_t)k + 2];
+        if (z != 0.0 || (plus_zero_only && std::signbit(z))) return false;
+    }
+    return true;
+}
+
+static int max_poly_size(const int* off, int n_poly)
+{
+    int max_K = 0;
+    for (int a = 0; a < n_poly; ++a) max_K = std::max(max_K, off[a + 1] - off[a]);
+    return max_K;
+}
+
+// the polygons of one call as the kernels read them; lives until the entry point returns (the uploads are asynchronous)
+struct PolySoa {
+    const int* off;
+    int n_poly, max_K;
+    std::vector<double> soa;
+    PolySoa(const double* pts, const int* off_, int n_poly_)
+        : off(off_), n_poly(n_poly_), max_K(max_poly_size(off_, n_poly_)), soa(to_soa(pts, off_, n_poly_)) {}
+};
+
+// curves (nullptr: none) -> ws_in; polygons (nullptr: none) -> ws_in2, or ws_in where there are no curves, and their
+// offsets -> WS_POLY_OFF; the pair lists -> WS_PAIR_A, WS_PAIR_B
+static int upload_operands(obtg_ctx* c, const double* curves, int n_curves, int K, const PolySoa* polys, const int* pair_a,
+                           const int* pair_b, int n_pairs)
+{
+    int rc;
+    if (curves && (rc = h2d(c, c->ws_in, curves, sizeof(double) * 3 * (size_t)K * n_curves))) return rc;
+    if (polys) {
+        if ((rc = h2d(c, curves ? c->ws_in2 : c->ws_in, polys->soa.data(), polys->soa.size() * sizeof(double)))) return rc;
+        if ((rc = h2d(c, c->ws_misc[WS_POLY_OFF], polys->off, sizeof(int) * (polys->n_poly + 1)))) return rc;
+    }
+    if ((rc = h2d(c, c->ws_misc[WS_PAIR_A], pair_a, sizeof(int) * n_pairs))) return rc;
+    return h2d(c, c->ws_misc[WS_PAIR_B], pair_b, sizeof(int) * n_pairs);
+}
+
+// device side of a curve search's outputs: its frame stacks, res[width][n_pairs] in ws_out, info[4 n_pairs]
+static int reserve_search(obtg_ctx* c, size_t stack_doubles, int width, int n_pairs)
+{
+    int rc = c->ws_misc[WS_STACK].reserve(sizeof(double) * stack_doubles);
+    if (rc) return rc;
+    if ((rc = c->ws_out.reserve(sizeof(double) * width * (size_t)n_pairs))) return rc;
+    return c->ws_misc[WS_INFO].reserve(sizeof(int) * 4 * (size_t)n_pairs);
+}
+
+// results of a curve search: info, then res (the copy that synchronises); info and status are optional
+static int download_search(obtg_ctx* c, int n_pairs, int width, double* res, int* info, int* status)
+{
+    std::vector<int> hinfo((size_t)4 * n_pairs);
+    int rc = d2h_copy(c, hinfo.data(), c->ws_misc[WS_INFO].p, sizeof(int) * 4 * n_pairs);
+    if (rc) return rc;
+    if ((rc = d2h(c, res, c->ws_out.p, sizeof(double) * width * n_pairs))) return rc;
+    if (info) std::memcpy(info, hinfo.data(), sizeof(int) * 4 * n_pairs);
+    if (status) for (int k = 0; k < n_pairs; ++k) status[k] = hinfo[4 * k + 3];
+    return OBTG_OK;
+}
+
+// device side of a GJK call's outputs (obtg_gjk_swarm's too): flag | aux (n_support or iters) | status in WS_INFO;
+// p1 | p2 | dist (| lower: `doubles` = 8) in ws_out
+struct GjkOut { int *flag, *aux, *status; double *p1, *p2, *dist; };
+static int reserve_gjk(obtg_ctx* c, size_t n, int doubles, GjkOut& o)
+{
+    int rc = c->ws_misc[WS_INFO].reserve(sizeof(int) * 3 * n);
+    if (rc) return rc;
+    if ((rc = c->ws_out.reserve(sizeof(double) * doubles * n))) return rc;
+    o.flag = slot<int>(c, WS_INFO); o.aux = o.flag + n; o.status = o.aux + n;
+    o.p1 = c->ws_out.as<double>(); o.p2 = o.p1 + 3 * n; o.dist = o.p2 + 3 * n;
+    return OBTG_OK;
+}
+
+// every output the GJK calls share but dist, which each copies last (the copy that synchronises); aux and status are optional
+static int download_gjk(obtg_ctx* c, const GjkOut& o, size_t n, int* flag, int* aux, int* status, double* p1, double* p2)
+{
+    int rc = d2h_copy(c, flag, o.flag, sizeof(int) * n);
+    if (rc) return rc;
+    if (aux && (rc = d2h_copy(c, aux, o.aux, sizeof(int) * n))) return rc;
+    if (status && (rc = d2h_copy(c, status, o.status, sizeof(int) * n))) return rc;
+    if ((rc = d2h_copy(c, p1, o.p1, sizeof(double) * 3 * n))) return rc;
+    return d2h_copy(c, p2, o.p2, sizeof(double) * 3 * n);
+}
+}  // extern "C++"
+
 int obtg_gjk_pairs(obtg_ctx* c, const double* pts, int n_pts, const int* poly_off, int n_poly,
                    const int* pair_a, const int* pair_b, int n_pairs, int max_iter, int md_cap, int* flag,
                    double* p1, double* p2, double* dist, short* support_trace, int trace_cap,
@@ -888,46 +1010,27 @@ int obtg_gjk_pairs(obtg_ctx* c, const double* pts, int n_pts, const int* poly_of
     if (n_pairs < 0 || max_iter < 1 || md_cap < 1 || trace_cap < 0) return OBTG_ERR_ARG;
     int rc = check_polys(poly_off, n_poly, n_pts);
     if (rc) return rc;
-    for (int k = 0; k < n_pairs; ++k)
-        if (pair_a[k] < 0 || pair_a[k] >= n_poly || pair_b[k] < 0 || pair_b[k] >= n_poly) return OBTG_ERR_ARG;
+    if ((rc = check_pairs(pair_a, n_poly, pair_b, n_poly, n_pairs))) return rc;
     if (n_pairs == 0) return OBTG_OK;
     (void)hipSetDevice(c->device);
-    auto soa = to_soa(pts, poly_off, n_poly);
-    DevBuf* m = c->ws_misc;
-    if ((rc = h2d(c, c->ws_in, soa.data(), soa.size() * sizeof(double)))) return rc;
-    if ((rc = h2d(c, m[0], poly_off, sizeof(int) * (n_poly + 1)))) return rc;
-    if ((rc = h2d(c, m[1], pair_a, sizeof(int) * n_pairs))) return rc;
-    if ((rc = h2d(c, m[2], pair_b, sizeof(int) * n_pairs))) return rc;
-    // outputs: flag | nsup | status (ints) ; p1 | p2 | dist (doubles) ; trace
-    if ((rc = m[3].reserve(sizeof(int) * 3 * (size_t)n_pairs))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * 7 * (size_t)n_pairs))) return rc;
+    const PolySoa polys(pts, poly_off, n_poly);
+    if ((rc = upload_operands(c, nullptr, 0, 0, &polys, pair_a, pair_b, n_pairs))) return rc;
+    GjkOut o;
+    if ((rc = reserve_gjk(c, n_pairs, 7, o))) return rc;
     short* d_trace = nullptr;
+    const size_t trace_bytes = sizeof(short) * 2 * (size_t)trace_cap * n_pairs;
     if (support_trace && trace_cap > 0) {
-        if ((rc = m[4].reserve(sizeof(short) * 2 * (size_t)trace_cap * n_pairs))) return rc;
-        d_trace = m[4].as<short>();
-        OBTG_HIP(c, hipMemsetAsync(d_trace, 0, sizeof(short) * 2 * (size_t)trace_cap * n_pairs, c->stream));
+        if ((rc = c->ws_misc[WS_TRACE].reserve(trace_bytes))) return rc;
+        d_trace = slot<short>(c, WS_TRACE);
+        OBTG_HIP(c, hipMemsetAsync(d_trace, 0, trace_bytes, c->stream));
     }
-    int* d_flag = m[3].as<int>();
-    int* d_nsup = d_flag + n_pairs;
-    int* d_status = d_nsup + n_pairs;
-    double* d_p1 = c->ws_out.as<double>();
-    double* d_p2 = d_p1 + 3 * (size_t)n_pairs;
-    double* d_dist = d_p2 + 3 * (size_t)n_pairs;
-    bool planar = true;
-    for (int k = 0; k < n_pts && planar; ++k) planar = pts[3 * (size_t)k + 2] == 0.0;
-    rc = launch_gjk_pairs(c, c->ws_in.as<double>(), m[0].as<int>(), m[1].as<int>(), m[2].as<int>(), n_pairs,
-                          max_iter, md_cap, d_flag, d_p1, d_p2, d_dist, d_trace, trace_cap, d_nsup, d_status,
-                          planar);
+    rc = launch_gjk_pairs(c, c->ws_in.as<double>(), slot<int>(c, WS_POLY_OFF), slot<int>(c, WS_PAIR_A), slot<int>(c, WS_PAIR_B),
+                          n_pairs, max_iter, md_cap, o.flag, o.p1, o.p2, o.dist, d_trace, trace_cap, o.aux, o.status,
+                          polys_planar(pts, n_pts, false));
     if (rc) return rc;
-    if ((rc = d2h_copy(c, flag, d_flag, sizeof(int) * n_pairs))) return rc;
-    if (n_support) if ((rc = d2h_copy(c, n_support, d_nsup, sizeof(int) * n_pairs))) return rc;
-    if (status) if ((rc = d2h_copy(c, status, d_status, sizeof(int) * n_pairs))) return rc;
-    if ((rc = d2h_copy(c, p1, d_p1, sizeof(double) * 3 * n_pairs))) return rc;
-    if ((rc = d2h_copy(c, p2, d_p2, sizeof(double) * 3 * n_pairs))) return rc;
-    if (d_trace)
-        OBTG_HIP(c, hipMemcpyAsync(support_trace, d_trace, sizeof(short) * 2 * (size_t)trace_cap * n_pairs,
-                                   hipMemcpyDeviceToHost, c->stream));
-    return d2h(c, dist, d_dist, sizeof(double) * n_pairs);
+    if ((rc = download_gjk(c, o, n_pairs, flag, n_support, status, p1, p2))) return rc;
+    if (d_trace) OBTG_HIP(c, hipMemcpyAsync(support_trace, d_trace, trace_bytes, hipMemcpyDeviceToHost, c->stream));
+    return d2h(c, dist, o.dist, sizeof(double) * n_pairs);
 }
 
 int obtg_gjk_true_pairs(obtg_ctx* c, const double* pts, int n_pts, const int* poly_off, int n_poly, const int* pair_a,
@@ -938,75 +1041,21 @@ int obtg_gjk_true_pairs(obtg_ctx* c, const double* pts, int n_pts, const int* po
     if (n_pairs < 0 || max_iter < 1 || !(eps > 0)) return OBTG_ERR_ARG;
     int rc = check_polys(poly_off, n_poly, n_pts);
     if (rc) return rc;
-    for (int k = 0; k < n_pairs; ++k)
-        if (pair_a[k] < 0 || pair_a[k] >= n_poly || pair_b[k] < 0 || pair_b[k] >= n_poly) return OBTG_ERR_ARG;
+    if ((rc = check_pairs(pair_a, n_poly, pair_b, n_poly, n_pairs))) return rc;
     if (n_pairs == 0) return OBTG_OK;
     (void)hipSetDevice(c->device);
-    auto soa = to_soa(pts, poly_off, n_poly);
-    DevBuf* m = c->ws_misc;
-    if ((rc = h2d(c, c->ws_in, soa.data(), soa.size() * sizeof(double)))) return rc;
-    if ((rc = h2d(c, m[0], poly_off, sizeof(int) * (n_poly + 1)))) return rc;
-    if ((rc = h2d(c, m[1], pair_a, sizeof(int) * n_pairs))) return rc;
-    if ((rc = h2d(c, m[2], pair_b, sizeof(int) * n_pairs))) return rc;
-    if ((rc = m[3].reserve(sizeof(int) * 3 * (size_t)n_pairs))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * 8 * (size_t)n_pairs))) return rc;
-    int* d_flag = m[3].as<int>();
-    int* d_iters = d_flag + n_pairs;
-    int* d_status = d_iters + n_pairs;
-    double* d_p1 = c->ws_out.as<double>();
-    double* d_p2 = d_p1 + 3 * (size_t)n_pairs;
-    double* d_dist = d_p2 + 3 * (size_t)n_pairs;
-    double* d_lower = d_dist + n_pairs;
-    rc = launch_gjk_true_pairs(c, c->ws_in.as<double>(), m[0].as<int>(), m[1].as<int>(), m[2].as<int>(), n_pairs, eps,
-                               max_iter, d_flag, d_p1, d_p2, d_dist, d_lower, d_iters, d_status);
+    const PolySoa polys(pts, poly_off, n_poly);
+    if ((rc = upload_operands(c, nullptr, 0, 0, &polys, pair_a, pair_b, n_pairs))) return rc;
+    GjkOut o;
+    if ((rc = reserve_gjk(c, n_pairs, 8, o))) return rc;
+    double* d_lower = o.dist + n_pairs;
+    rc = launch_gjk_true_pairs(c, c->ws_in.as<double>(), slot<int>(c, WS_POLY_OFF), slot<int>(c, WS_PAIR_A),
+                               slot<int>(c, WS_PAIR_B), n_pairs, eps, max_iter, o.flag, o.p1, o.p2, o.dist, d_lower, o.aux,
+                               o.status);
     if (rc) return rc;
-    if ((rc = d2h_copy(c, flag, d_flag, sizeof(int) * n_pairs))) return rc;
-    if (iters && (rc = d2h_copy(c, iters, d_iters, sizeof(int) * n_pairs))) return rc;
-    if (status && (rc = d2h_copy(c, status, d_status, sizeof(int) * n_pairs))) return rc;
-    if ((rc = d2h_copy(c, p1, d_p1, sizeof(double) * 3 * n_pairs))) return rc;
-    if ((rc = d2h_copy(c, p2, d_p2, sizeof(double) * 3 * n_pairs))) return rc;
+    if ((rc = download_gjk(c, o, n_pairs, flag, iters, status, p1, p2))) return rc;
     if (lower && (rc = d2h_copy(c, lower, d_lower, sizeof(double) * n_pairs))) return rc;
-    return d2h(c, dist, d_dist, sizeof(double) * n_pairs);
-}
-
-int obtg_min_dist2poly_robust(obtg_ctx* c, const double* curves, int n_curves, int K, const double* pts, int n_pts,
-                              const int* poly_off, int n_poly, const int* pair_curve, const int* pair_poly, int n_pairs,
-                              double eps, int max_nodes, double* res, int* info, int* status)
-{
-    if (!check_ctx(c) || !curves || !pts || !pair_curve || !pair_poly || !res || n_curves < 1 || n_pairs < 0)
-        return OBTG_ERR_ARG;
-    if (K < 2 || max_nodes < 1 || !(eps > 0)) return OBTG_ERR_ARG;
-    int rc = check_polys(poly_off, n_poly, n_pts);
-    if (rc) return rc;
-    for (int k = 0; k < n_pairs; ++k)
-        if (pair_curve[k] < 0 || pair_curve[k] >= n_curves || pair_poly[k] < 0 || pair_poly[k] >= n_poly)
-            return OBTG_ERR_ARG;
-    if (n_pairs == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
-    constexpr int kCap = 1024, kMaxLevel = 48;
-    DevBuf* m = c->ws_misc;
-    auto soa = to_soa(pts, poly_off, n_poly);
-    int max_K = 0;
-    for (int a = 0; a < n_poly; ++a) max_K = std::max(max_K, poly_off[a + 1] - poly_off[a]);
-    if ((rc = h2d(c, c->ws_in, curves, sizeof(double) * 3 * (size_t)K * n_curves))) return rc;
-    if ((rc = h2d(c, c->ws_in2, soa.data(), soa.size() * sizeof(double)))) return rc;
-    if ((rc = h2d(c, m[0], poly_off, sizeof(int) * (n_poly + 1)))) return rc;
-    if ((rc = h2d(c, m[1], pair_curve, sizeof(int) * n_pairs))) return rc;
-    if ((rc = h2d(c, m[2], pair_poly, sizeof(int) * n_pairs))) return rc;
-    if ((rc = m[5].reserve(sizeof(double) * 2 * kCap * 2 * (size_t)n_pairs))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * 5 * (size_t)n_pairs))) return rc;
-    if ((rc = m[3].reserve(sizeof(int) * 4 * (size_t)n_pairs))) return rc;
-    rc = launch_min_dist2poly_robust(c, c->ws_in.as<double>(), K, c->ws_in2.as<double>(), m[0].as<int>(), m[1].as<int>(),
-                                     m[2].as<int>(), n_pairs, eps, max_nodes, kMaxLevel, kCap, max_K, m[5].as<double>(),
-                                     c->ws_out.as<double>(), m[3].as<int>());
-    if (rc) return rc;
-    std::vector<int> hinfo((size_t)4 * n_pairs);
-    if ((rc = d2h_copy(c, hinfo.data(), m[3].p, sizeof(int) * 4 * n_pairs))) return rc;
-    rc = d2h(c, res, c->ws_out.p, sizeof(double) * 5 * n_pairs);
-    if (rc) return rc;
-    if (info) std::memcpy(info, hinfo.data(), sizeof(int) * 4 * n_pairs);
-    if (status) for (int k = 0; k < n_pairs; ++k) status[k] = hinfo[4 * k + 3];
-    return OBTG_OK;
+    return d2h(c, dist, o.dist, sizeof(double) * n_pairs);
 }
 
 int obtg_ctx_set_polygons(obtg_ctx* c, const double* pts, int n_pts, const int* poly_off, int n_poly)
@@ -1027,10 +1076,8 @@ int obtg_ctx_set_polygons(obtg_ctx* c, const double* pts, int n_pts, const int* 
     if ((rc = upload(c, c->d_poly_pts, soa.data(), soa.size() * sizeof(double)))) return rc;
     if ((rc = upload(c, c->d_poly_off, poly_off, sizeof(int) * (n_poly + 1)))) return rc;
     c->n_poly = n_poly; c->n_poly_pts = n_pts;
-    c->polys_planar = true;
-    for (int k = 0; k < n_pts && c->polys_planar; ++k) c->polys_planar = pts[3 * (size_t)k + 2] == 0.0;
-    c->max_poly_K = 0;
-    for (int a = 0; a < n_poly; ++a) c->max_poly_K = std::max(c->max_poly_K, poly_off[a + 1] - poly_off[a]);
+    c->polys_planar = polys_planar(pts, n_pts, false);
+    c->max_poly_K = max_poly_size(poly_off, n_poly);
     c->n_hull_pairs = 0;   // object ids may have changed meaning
     c->hull_pairs_set = false;
     c->tile_valid = false;
@@ -1205,52 +1252,30 @@ int obtg_gjk_swarm(obtg_ctx* c, const double* Y, int B, int max_iter, int md_cap
     const size_t n = (size_t)B * c->n_hull_pairs;
     if (n == 0) return OBTG_OK;
     (void)hipSetDevice(c->device);
-    DevBuf* m = c->ws_misc;
     int rc = h2d(c, c->ws_in, Y, sizeof(double) * ysize(c) * B);
     if (rc) return rc;
-    if ((rc = m[3].reserve(sizeof(int) * 3 * n))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * 7 * n))) return rc;
-    int* d_flag = m[3].as<int>();
-    int* d_nsup = d_flag + n;
-    int* d_status = d_nsup + n;
-    double* d_p1 = c->ws_out.as<double>();
-    double* d_p2 = d_p1 + 3 * n;
-    double* d_dist = d_p2 + 3 * n;
-    rc = launch_gjk_swarm(c, c->ws_in.as<double>(), B, max_iter, md_cap, d_flag, d_p1, d_p2, d_dist, d_nsup, d_status);
+    GjkOut o;
+    if ((rc = reserve_gjk(c, n, 7, o))) return rc;
+    rc = launch_gjk_swarm(c, c->ws_in.as<double>(), B, max_iter, md_cap, o.flag, o.p1, o.p2, o.dist, o.aux, o.status);
     if (rc) return rc;
-    if ((rc = d2h_copy(c, flag, d_flag, sizeof(int) * n))) return rc;
-    if (nsup) if ((rc = d2h_copy(c, nsup, d_nsup, sizeof(int) * n))) return rc;
-    if (status) if ((rc = d2h_copy(c, status, d_status, sizeof(int) * n))) return rc;
-    if ((rc = d2h_copy(c, p1, d_p1, sizeof(double) * 3 * n))) return rc;
-    if ((rc = d2h_copy(c, p2, d_p2, sizeof(double) * 3 * n))) return rc;
-    return d2h(c, dist, d_dist, sizeof(double) * n);
+    if ((rc = download_gjk(c, o, n, flag, nsup, status, p1, p2))) return rc;
+    return d2h(c, dist, o.dist, sizeof(double) * n);
 }
 
-// ------------------------------------------------------------------ minDist
+// ------------------------------------------------------------------ minDist, collCheck (the host path: "batched searches over a pair list" above)
 int obtg_min_dist(obtg_ctx* c, const double* curves, int n_curves, int K, const int* pair_a, const int* pair_b,
                   int n_pairs, double eps, int max_iter, int md_cap, int max_depth, int max_nodes, double* res,
                   int* info, int* status)
 {
     if (!check_ctx(c) || !curves || !pair_a || !pair_b || !res || n_curves < 1 || n_pairs < 0) return OBTG_ERR_ARG;
     if (K < 2 || max_iter < 1 || md_cap < 1 || max_depth < 1 || max_nodes < 1) return OBTG_ERR_ARG;
-    for (int k = 0; k < n_pairs; ++k)
-        if (pair_a[k] < 0 || pair_a[k] >= n_curves || pair_b[k] < 0 || pair_b[k] >= n_curves) return OBTG_ERR_ARG;
+    int rc = check_pairs(pair_a, n_curves, pair_b, n_curves, n_pairs);
+    if (rc) return rc;
     if (n_pairs == 0) return OBTG_OK;
     (void)hipSetDevice(c->device);
-    DevBuf* m = c->ws_misc;
-    int rc = h2d(c, c->ws_in, curves, sizeof(double) * 3 * (size_t)K * n_curves);
-    if (rc) return rc;
-    if ((rc = h2d(c, m[1], pair_a, sizeof(int) * n_pairs))) return rc;
-    if ((rc = h2d(c, m[2], pair_b, sizeof(int) * n_pairs))) return rc;
-    // 2-D curves arrive padded with a zero z row (bezier.py:1294-1308): then the planar gjkNew machine runs (the same bits)
-    bool planar = true;
-    for (int i = 0; i < n_curves && planar; ++i) {
-        const double* z = curves + ((size_t)i * 3 + 2) * K;
-        for (int j = 0; j < K; ++j) if (z[j] != 0.0 || std::signbit(z[j])) { planar = false; break; }      // (+0 only: a -0 would show in a returned closest point)
-    }
-    if ((rc = m[5].reserve(sizeof(double) * min_dist_stack_doubles(c, K, max_depth, n_pairs, planar)))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * 3 * (size_t)n_pairs))) return rc;
-    if ((rc = m[3].reserve(sizeof(int) * 4 * (size_t)n_pairs))) return rc;
+    if ((rc = upload_operands(c, curves, n_curves, K, nullptr, pair_a, pair_b, n_pairs))) return rc;
+    const bool planar = curves_planar(curves, n_curves, K);
+    if ((rc = reserve_search(c, min_dist_stack_doubles(c, K, max_depth, n_pairs, planar), 3, n_pairs))) return rc;
     // the order the worker waves take the pairs in: by the previous evaluation's node counts, longest search first, when
     // this very pair list was evaluated before (an SLSQP run evaluates one list over and over at nearby x); list order else
     unsigned long long sig = 1469598103934665603ull ^ (unsigned long long)n_pairs;
@@ -1260,61 +1285,49 @@ int obtg_min_dist(obtg_ctx* c, const double* curves, int n_curves, int K, const 
     }
     static const bool use_hist = !(getenv("OBTG_MD_HISTORY") && getenv("OBTG_MD_HISTORY")[0] == '0');
     std::vector<int> qbuf((size_t)n_pairs + 1, 0);           // [0] the queue counter, [1..] the order
-    int slot = -1;
+    int hist = -1;
     for (size_t h = 0; h < c->md_hist.size(); ++h)
-        if (c->md_hist[h].sig == sig && (int)c->md_hist[h].nodes.size() == n_pairs) slot = (int)h;
-    const bool have = use_hist && slot >= 0;
+        if (c->md_hist[h].sig == sig && (int)c->md_hist[h].nodes.size() == n_pairs) hist = (int)h;
+    const bool have = use_hist && hist >= 0;
     for (int k = 0; k < n_pairs; ++k) qbuf[1 + k] = k;
     if (have) {
-        const std::vector<int>& hn = c->md_hist[slot].nodes;
+        const std::vector<int>& hn = c->md_hist[hist].nodes;
         std::stable_sort(qbuf.begin() + 1, qbuf.end(), [&](int a, int b) { return hn[a] > hn[b]; });
     }
-    if ((rc = h2d(c, m[6], qbuf.data(), sizeof(int) * qbuf.size()))) return rc;
-    rc = launch_min_dist(c, c->ws_in.as<double>(), K, m[1].as<int>(), m[2].as<int>(), n_pairs, eps, max_iter,
-                         md_cap, max_depth, max_nodes, m[5].as<double>(), c->ws_out.as<double>(), m[3].as<int>(),
-                         have ? m[6].as<int>() + 1 : nullptr, m[6].as<int>(), planar);
+    if ((rc = h2d(c, c->ws_misc[WS_QUEUE], qbuf.data(), sizeof(int) * qbuf.size()))) return rc;
+    int* d_queue = slot<int>(c, WS_QUEUE);
+    rc = launch_min_dist(c, c->ws_in.as<double>(), K, slot<int>(c, WS_PAIR_A), slot<int>(c, WS_PAIR_B), n_pairs, eps, max_iter,
+                         md_cap, max_depth, max_nodes, slot<double>(c, WS_STACK), c->ws_out.as<double>(), slot<int>(c, WS_INFO),
+                         have ? d_queue + 1 : nullptr, d_queue, planar);
     if (rc) return rc;
-    std::vector<int> hinfo((size_t)4 * n_pairs);
-    if ((rc = d2h_copy(c, hinfo.data(), m[3].p, sizeof(int) * 4 * n_pairs))) return rc;
-    if (slot >= 0) c->md_hist.erase(c->md_hist.begin() + slot);
+    std::vector<int> own_info;                               // the history needs the node counts whether the caller asked for info or not
+    if (!info) { own_info.resize((size_t)4 * n_pairs); info = own_info.data(); }
+    if ((rc = download_search(c, n_pairs, 3, res, info, status))) return rc;
+    if (hist >= 0) c->md_hist.erase(c->md_hist.begin() + hist);
     if (c->md_hist.size() >= 4) c->md_hist.erase(c->md_hist.begin());
     c->md_hist.push_back({ sig, std::vector<int>((size_t)n_pairs) });
-    for (int k = 0; k < n_pairs; ++k) c->md_hist.back().nodes[k] = hinfo[4 * k];
-    rc = d2h(c, res, c->ws_out.p, sizeof(double) * 3 * n_pairs);
-    if (rc) return rc;
-    if (info) std::memcpy(info, hinfo.data(), sizeof(int) * 4 * n_pairs);
-    if (status) for (int k = 0; k < n_pairs; ++k) status[k] = hinfo[4 * k + 3];
+    for (int k = 0; k < n_pairs; ++k) c->md_hist.back().nodes[k] = info[4 * k];
     return OBTG_OK;
 }
+
+constexpr int kRobustCap = 1024, kRobustMaxLevel = 48;       // frontier capacity per pair and subdivision depth of the robust searches
 
 int obtg_min_dist_robust(obtg_ctx* c, const double* curves, int n_curves, int K, const int* pair_a, const int* pair_b,
                          int n_pairs, double eps, int max_nodes, double* res, int* info, int* status)
 {
     if (!check_ctx(c) || !curves || !pair_a || !pair_b || !res || n_curves < 1 || n_pairs < 0) return OBTG_ERR_ARG;
     if (K < 2 || max_nodes < 1 || !(eps > 0)) return OBTG_ERR_ARG;
-    for (int k = 0; k < n_pairs; ++k)
-        if (pair_a[k] < 0 || pair_a[k] >= n_curves || pair_b[k] < 0 || pair_b[k] >= n_curves) return OBTG_ERR_ARG;
+    int rc = check_pairs(pair_a, n_curves, pair_b, n_curves, n_pairs);
+    if (rc) return rc;
     if (n_pairs == 0) return OBTG_OK;
     (void)hipSetDevice(c->device);
-    constexpr int kCap = 1024, kMaxLevel = 48;
-    DevBuf* m = c->ws_misc;
-    int rc = h2d(c, c->ws_in, curves, sizeof(double) * 3 * (size_t)K * n_curves);
+    if ((rc = upload_operands(c, curves, n_curves, K, nullptr, pair_a, pair_b, n_pairs))) return rc;
+    if ((rc = reserve_search(c, (size_t)2 * kRobustCap * 3 * n_pairs, 3, n_pairs))) return rc;
+    rc = launch_min_dist_robust(c, c->ws_in.as<double>(), K, slot<int>(c, WS_PAIR_A), slot<int>(c, WS_PAIR_B), n_pairs, eps,
+                                max_nodes, kRobustMaxLevel, kRobustCap, slot<double>(c, WS_STACK), c->ws_out.as<double>(),
+                                slot<int>(c, WS_INFO));
     if (rc) return rc;
-    if ((rc = h2d(c, m[1], pair_a, sizeof(int) * n_pairs))) return rc;
-    if ((rc = h2d(c, m[2], pair_b, sizeof(int) * n_pairs))) return rc;
-    if ((rc = m[5].reserve(sizeof(double) * 2 * kCap * 3 * (size_t)n_pairs))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * 3 * (size_t)n_pairs))) return rc;
-    if ((rc = m[3].reserve(sizeof(int) * 4 * (size_t)n_pairs))) return rc;
-    rc = launch_min_dist_robust(c, c->ws_in.as<double>(), K, m[1].as<int>(), m[2].as<int>(), n_pairs, eps, max_nodes,
-                                kMaxLevel, kCap, m[5].as<double>(), c->ws_out.as<double>(), m[3].as<int>());
-    if (rc) return rc;
-    std::vector<int> hinfo((size_t)4 * n_pairs);
-    if ((rc = d2h_copy(c, hinfo.data(), m[3].p, sizeof(int) * 4 * n_pairs))) return rc;
-    rc = d2h(c, res, c->ws_out.p, sizeof(double) * 3 * n_pairs);
-    if (rc) return rc;
-    if (info) std::memcpy(info, hinfo.data(), sizeof(int) * 4 * n_pairs);
-    if (status) for (int k = 0; k < n_pairs; ++k) status[k] = hinfo[4 * k + 3];
-    return OBTG_OK;
+    return download_search(c, n_pairs, 3, res, info, status);
 }
 
 int obtg_min_dist2poly(obtg_ctx* c, const double* curves, int n_curves, int K, const double* pts, int n_pts,
@@ -1327,50 +1340,41 @@ int obtg_min_dist2poly(obtg_ctx* c, const double* curves, int n_curves, int K, c
     if (K < 2 || max_iter < 1 || md_cap < 1 || max_depth < 1 || max_nodes < 1) return OBTG_ERR_ARG;
     int rc = check_polys(poly_off, n_poly, n_pts);
     if (rc) return rc;
-    for (int k = 0; k < n_pairs; ++k)
-        if (pair_curve[k] < 0 || pair_curve[k] >= n_curves || pair_poly[k] < 0 || pair_poly[k] >= n_poly)
-            return OBTG_ERR_ARG;
+    if ((rc = check_pairs(pair_curve, n_curves, pair_poly, n_poly, n_pairs))) return rc;
     if (n_pairs == 0) return OBTG_OK;
     (void)hipSetDevice(c->device);
-    DevBuf* m = c->ws_misc;
-    auto soa = to_soa(pts, poly_off, n_poly);
-    int max_K = 0;
-    for (int a = 0; a < n_poly; ++a) max_K = std::max(max_K, poly_off[a + 1] - poly_off[a]);
-    if ((rc = h2d(c, c->ws_in, curves, sizeof(double) * 3 * (size_t)K * n_curves))) return rc;
-    if ((rc = h2d(c, c->ws_in2, soa.data(), soa.size() * sizeof(double)))) return rc;
-    if ((rc = h2d(c, m[0], poly_off, sizeof(int) * (n_poly + 1)))) return rc;
-    if ((rc = h2d(c, m[1], pair_curve, sizeof(int) * n_pairs))) return rc;
-    if ((rc = h2d(c, m[2], pair_poly, sizeof(int) * n_pairs))) return rc;
-    if ((rc = m[5].reserve(sizeof(double) * min_dist2poly_stack_doubles(K, max_depth) * n_pairs))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * 5 * (size_t)n_pairs))) return rc;
-    if ((rc = m[3].reserve(sizeof(int) * 4 * (size_t)n_pairs))) return rc;
-    bool planar = true;             // 2-D curves against polygons in the plane (bezier.py:1416-1430 pads both with z = 0)
-    for (int i = 0; i < n_curves && planar; ++i) {
-        const double* z = curves + ((size_t)i * 3 + 2) * K;
-        for (int j = 0; j < K; ++j) if (z[j] != 0.0 || std::signbit(z[j])) { planar = false; break; }      // (+0 only: a -0 would show in a returned closest point)
-    }
-    for (int i = 0; i < n_pts && planar; ++i) if (pts[3 * (size_t)i + 2] != 0.0 || std::signbit(pts[3 * (size_t)i + 2])) planar = false;
-    rc = launch_min_dist2poly(c, c->ws_in.as<double>(), K, c->ws_in2.as<double>(), m[0].as<int>(), m[1].as<int>(),
-                              m[2].as<int>(), n_pairs, eps, max_iter, md_cap, max_depth, max_nodes,
-                              m[5].as<double>(), c->ws_out.as<double>(), m[3].as<int>(), max_K, planar);
+    const PolySoa polys(pts, poly_off, n_poly);
+    if ((rc = upload_operands(c, curves, n_curves, K, &polys, pair_curve, pair_poly, n_pairs))) return rc;
+    // 2-D curves against polygons in the plane (bezier.py:1416-1430 pads both with z = 0)
+    const bool planar = curves_planar(curves, n_curves, K) && polys_planar(pts, n_pts, true);
+    if ((rc = reserve_search(c, min_dist2poly_stack_doubles(K, max_depth, n_pairs, polys.max_K, planar), 5, n_pairs))) return rc;
+    rc = launch_min_dist2poly(c, c->ws_in.as<double>(), K, c->ws_in2.as<double>(), slot<int>(c, WS_POLY_OFF), slot<int>(c, WS_PAIR_A),
+                              slot<int>(c, WS_PAIR_B), n_pairs, eps, max_iter, md_cap, max_depth, max_nodes,
+                              slot<double>(c, WS_STACK), c->ws_out.as<double>(), slot<int>(c, WS_INFO), polys.max_K, planar);
     if (rc) return rc;
-    std::vector<int> hinfo((size_t)4 * n_pairs);
-    if ((rc = d2h_copy(c, hinfo.data(), m[3].p, sizeof(int) * 4 * n_pairs))) return rc;
-    rc = d2h(c, res, c->ws_out.p, sizeof(double) * 5 * n_pairs);
-    if (rc) return rc;
-    if (info) std::memcpy(info, hinfo.data(), sizeof(int) * 4 * n_pairs);
-    if (status) for (int k = 0; k < n_pairs; ++k) status[k] = hinfo[4 * k + 3];
-    return OBTG_OK;
+    return download_search(c, n_pairs, 5, res, info, status);
 }
 
-// all-z-are-+0 test of curves[n_curves][3][K] (2-D curves arrive padded with a zero z row): then the planar gjkNew machine runs
-static bool curves_planar(const double* curves, int n_curves, int K)
+int obtg_min_dist2poly_robust(obtg_ctx* c, const double* curves, int n_curves, int K, const double* pts, int n_pts,
+                              const int* poly_off, int n_poly, const int* pair_curve, const int* pair_poly, int n_pairs,
+                              double eps, int max_nodes, double* res, int* info, int* status)
 {
-    for (int i = 0; i < n_curves; ++i) {
-        const double* z = curves + ((size_t)i * 3 + 2) * K;
-        for (int j = 0; j < K; ++j) if (z[j] != 0.0 || std::signbit(z[j])) return false;
-    }
-    return true;
+    if (!check_ctx(c) || !curves || !pts || !pair_curve || !pair_poly || !res || n_curves < 1 || n_pairs < 0)
+        return OBTG_ERR_ARG;
+    if (K < 2 || max_nodes < 1 || !(eps > 0)) return OBTG_ERR_ARG;
+    int rc = check_polys(poly_off, n_poly, n_pts);
+    if (rc) return rc;
+    if ((rc = check_pairs(pair_curve, n_curves, pair_poly, n_poly, n_pairs))) return rc;
+    if (n_pairs == 0) return OBTG_OK;
+    (void)hipSetDevice(c->device);
+    const PolySoa polys(pts, poly_off, n_poly);
+    if ((rc = upload_operands(c, curves, n_curves, K, &polys, pair_curve, pair_poly, n_pairs))) return rc;
+    if ((rc = reserve_search(c, (size_t)2 * kRobustCap * 2 * n_pairs, 5, n_pairs))) return rc;
+    rc = launch_min_dist2poly_robust(c, c->ws_in.as<double>(), K, c->ws_in2.as<double>(), slot<int>(c, WS_POLY_OFF),
+                                     slot<int>(c, WS_PAIR_A), slot<int>(c, WS_PAIR_B), n_pairs, eps, max_nodes, kRobustMaxLevel,
+                                     kRobustCap, polys.max_K, slot<double>(c, WS_STACK), c->ws_out.as<double>(), slot<int>(c, WS_INFO));
+    if (rc) return rc;
+    return download_search(c, n_pairs, 5, res, info, status);
 }
 
 int obtg_coll_check(obtg_ctx* c, const double* curves, int n_curves, int K, const int* pair_a, const int* pair_b,
@@ -1379,31 +1383,20 @@ int obtg_coll_check(obtg_ctx* c, const double* curves, int n_curves, int K, cons
     if (!check_ctx(c) || !curves || n_curves < 1 || n_pairs < 0) return OBTG_ERR_ARG;
     if (n_pairs > 0 && (!pair_a || !pair_b || !res)) return OBTG_ERR_ARG;
     if (K < 2 || max_iter < 1 || md_cap < 1 || max_nodes < 1) return OBTG_ERR_ARG;
-    for (int k = 0; k < n_pairs; ++k)
-        if (pair_a[k] < 0 || pair_a[k] >= n_curves || pair_b[k] < 0 || pair_b[k] >= n_curves) return OBTG_ERR_ARG;
+    int rc = check_pairs(pair_a, n_curves, pair_b, n_curves, n_pairs);
+    if (rc) return rc;
     if (!coll_check_supported(K, 0)) return OBTG_ERR_UNSUPPORTED;
     if (n_pairs == 0) return OBTG_OK;
     (void)hipSetDevice(c->device);
-    DevBuf* m = c->ws_misc;
-    int rc = h2d(c, c->ws_in, curves, sizeof(double) * 3 * (size_t)K * n_curves);
-    if (rc) return rc;
-    if ((rc = h2d(c, m[1], pair_a, sizeof(int) * n_pairs))) return rc;
-    if ((rc = h2d(c, m[2], pair_b, sizeof(int) * n_pairs))) return rc;
+    if ((rc = upload_operands(c, curves, n_curves, K, nullptr, pair_a, pair_b, n_pairs))) return rc;
     const bool planar = curves_planar(curves, n_curves, K);
-    if ((rc = m[5].reserve(sizeof(double) * coll_check_stack_doubles(c, K, n_pairs, false, planar)))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * (size_t)n_pairs))) return rc;
-    if ((rc = m[3].reserve(sizeof(int) * 4 * (size_t)n_pairs))) return rc;
-    if ((rc = m[6].reserve(sizeof(int)))) return rc;
-    rc = launch_coll_check(c, c->ws_in.as<double>(), K, m[1].as<int>(), m[2].as<int>(), n_pairs, eps, max_iter, md_cap,
-                           max_nodes, m[5].as<double>(), c->ws_out.as<double>(), m[3].as<int>(), m[6].as<int>(),
-                           planar);
+    if ((rc = reserve_search(c, coll_check_stack_doubles(c, K, n_pairs, false, planar), 1, n_pairs))) return rc;
+    if ((rc = c->ws_misc[WS_QUEUE].reserve(sizeof(int)))) return rc;
+    rc = launch_coll_check(c, c->ws_in.as<double>(), K, slot<int>(c, WS_PAIR_A), slot<int>(c, WS_PAIR_B), n_pairs, eps, max_iter,
+                           md_cap, max_nodes, slot<double>(c, WS_STACK), c->ws_out.as<double>(), slot<int>(c, WS_INFO),
+                           slot<int>(c, WS_QUEUE), planar);
     if (rc) return rc;
-    std::vector<int> hinfo((size_t)4 * n_pairs);
-    if ((rc = d2h_copy(c, hinfo.data(), m[3].p, sizeof(int) * 4 * n_pairs))) return rc;
-    if ((rc = d2h(c, res, c->ws_out.p, sizeof(double) * n_pairs))) return rc;
-    if (info) std::memcpy(info, hinfo.data(), sizeof(int) * 4 * n_pairs);
-    if (status) for (int k = 0; k < n_pairs; ++k) status[k] = hinfo[4 * k + 3];
-    return OBTG_OK;
+    return download_search(c, n_pairs, 1, res, info, status);
 }
 
 int obtg_coll_check2poly(obtg_ctx* c, const double* curves, int n_curves, int K, const double* pts, int n_pts,
@@ -1415,37 +1408,20 @@ int obtg_coll_check2poly(obtg_ctx* c, const double* curves, int n_curves, int K,
     if (K < 2 || max_iter < 1 || md_cap < 1 || max_nodes < 1) return OBTG_ERR_ARG;
     int rc = check_polys(poly_off, n_poly, n_pts);
     if (rc) return rc;
-    for (int k = 0; k < n_pairs; ++k)
-        if (pair_curve[k] < 0 || pair_curve[k] >= n_curves || pair_poly[k] < 0 || pair_poly[k] >= n_poly)
-            return OBTG_ERR_ARG;
-    int max_K = 0;
-    for (int a = 0; a < n_poly; ++a) max_K = std::max(max_K, poly_off[a + 1] - poly_off[a]);
-    if (!coll_check_supported(K, max_K)) return OBTG_ERR_UNSUPPORTED;
+    if ((rc = check_pairs(pair_curve, n_curves, pair_poly, n_poly, n_pairs))) return rc;
+    if (!coll_check_supported(K, max_poly_size(poly_off, n_poly))) return OBTG_ERR_UNSUPPORTED;
     if (n_pairs == 0) return OBTG_OK;
     (void)hipSetDevice(c->device);
-    DevBuf* m = c->ws_misc;
-    auto soa = to_soa(pts, poly_off, n_poly);
-    if ((rc = h2d(c, c->ws_in, curves, sizeof(double) * 3 * (size_t)K * n_curves))) return rc;
-    if ((rc = h2d(c, c->ws_in2, soa.data(), soa.size() * sizeof(double)))) return rc;
-    if ((rc = h2d(c, m[0], poly_off, sizeof(int) * (n_poly + 1)))) return rc;
-    if ((rc = h2d(c, m[1], pair_curve, sizeof(int) * n_pairs))) return rc;
-    if ((rc = h2d(c, m[2], pair_poly, sizeof(int) * n_pairs))) return rc;
-    bool planar = curves_planar(curves, n_curves, K);
-    for (int i = 0; i < n_pts && planar; ++i) if (pts[3 * (size_t)i + 2] != 0.0 || std::signbit(pts[3 * (size_t)i + 2])) planar = false;
-    if ((rc = m[5].reserve(sizeof(double) * coll_check_stack_doubles(c, K, n_pairs, true, planar)))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * (size_t)n_pairs))) return rc;
-    if ((rc = m[3].reserve(sizeof(int) * 4 * (size_t)n_pairs))) return rc;
-    if ((rc = m[6].reserve(sizeof(int)))) return rc;
-    rc = launch_coll_check2poly(c, c->ws_in.as<double>(), K, c->ws_in2.as<double>(), m[0].as<int>(), m[1].as<int>(),
-                                m[2].as<int>(), n_pairs, max_iter, md_cap, max_nodes, m[5].as<double>(),
-                                c->ws_out.as<double>(), m[3].as<int>(), m[6].as<int>(), max_K, planar);
+    const PolySoa polys(pts, poly_off, n_poly);
+    if ((rc = upload_operands(c, curves, n_curves, K, &polys, pair_curve, pair_poly, n_pairs))) return rc;
+    const bool planar = curves_planar(curves, n_curves, K) && polys_planar(pts, n_pts, true);
+    if ((rc = reserve_search(c, coll_check_stack_doubles(c, K, n_pairs, true, planar), 1, n_pairs))) return rc;
+    if ((rc = c->ws_misc[WS_QUEUE].reserve(sizeof(int)))) return rc;
+    rc = launch_coll_check2poly(c, c->ws_in.as<double>(), K, c->ws_in2.as<double>(), slot<int>(c, WS_POLY_OFF), slot<int>(c, WS_PAIR_A),
+                                slot<int>(c, WS_PAIR_B), n_pairs, max_iter, md_cap, max_nodes, slot<double>(c, WS_STACK),
+                                c->ws_out.as<double>(), slot<int>(c, WS_INFO), slot<int>(c, WS_QUEUE), polys.max_K, planar);
     if (rc) return rc;
-    std::vector<int> hinfo((size_t)4 * n_pairs);
-    if ((rc = d2h_copy(c, hinfo.data(), m[3].p, sizeof(int) * 4 * n_pairs))) return rc;
-    if ((rc = d2h(c, res, c->ws_out.p, sizeof(double) * n_pairs))) return rc;
-    if (info) std::memcpy(info, hinfo.data(), sizeof(int) * 4 * n_pairs);
-    if (status) for (int k = 0; k < n_pairs; ++k) status[k] = hinfo[4 * k + 3];
-    return OBTG_OK;
+    return download_search(c, n_pairs, 1, res, info, status);
 }
 
 // ------------------------------------------------------------------ true Bernstein extrema (extrema_kernels.hip)

@@ -4063,12 +4063,6 @@ int launch_step_fd_structured(obtg_ctx* c, int B, double max_sep, double* d_out_
     return tl.finish(hdr);
 }
 
-size_t min_dist2poly_stack_doubles(int K, int max_depth)      // per pair: the larger of the frame forms
-{
-    const int fr = 3 * K + G_NSCAL, bl = K <= kMdQuadMaxK ? md2_quad_frame(K) : 0;
-    return (size_t)max_depth * (fr > bl ? fr : bl);
-}
-
 // worker waves of the wave-per-pair searches: waves per SIMD x 4 SIMDs x CUs, never more than pairs (OBTG_MD_WAVES_PER_SIMD)
 int min_dist_workers(const obtg_ctx* c, int n_pairs, size_t lds_per_wave, int waves_per_simd)
 {
@@ -4536,6 +4530,54 @@ int launch_min_dist2poly_robust(obtg_ctx* c, const double* d_curves, int K, cons
     return OBTG_OK;
 }
 
+// The form obtg_min_dist2poly runs for one call, with its grid, LDS and the stride of a frame in a pair's stack: as md_launch, the
+// ONE place that decides, so that min_dist2poly_stack_doubles (the allocation) and launch_min_dist2poly (the launch) cannot disagree.
+// The switches are read per call (the tests flip them in-process): OBTG_MD_FORM=wave skips the quad form (the wave form where it
+// fits, else the one-lane form), OBTG_MD_FORM=lane runs the one-lane form whatever fits; OBTG_MD_PLANAR=0 keeps planar operands on
+// the 3-D machine.  Every form keeps a stack per pair, and `frame` is the larger of the frame forms whichever one runs: the
+// allocation depends on (K, max_depth, n_pairs) alone.
+enum Md2Form { MD2_QUAD_3D = 0, MD2_QUAD_PLANAR, MD2_WAVE, MD2_LANE };
+struct Md2Launch {
+    Md2Form form;
+    unsigned grid, block;
+    size_t lds;
+    int frame;                     // doubles per level of a pair's frame stack (Md2Params::quad_frame)
+};
+static Md2Launch md2_launch(int K, int max_depth, int n_pairs, int max_poly_K, bool planar)
+{
+    const size_t lds_w = sizeof(double) * ((size_t)6 * K + 8 * kMdMaxK + (size_t)max_depth * G_NSCAL);
+    const size_t lds_q = sizeof(double) * ((size_t)2 * md2_quad_blob(K) + 48 + 8 * kMdShRow + 64 +
+                                           (size_t)(max_depth < kMdScsLds ? max_depth : kMdScsLds) * G_NSCAL);
+    const char* env_form = getenv("OBTG_MD_FORM");
+    const bool want_wave = env_form && !strcmp(env_form, "wave"), want_lane = env_form && !strcmp(env_form, "lane");
+    const char* env_planar = getenv("OBTG_MD_PLANAR");
+    const bool no_planar = env_planar && env_planar[0] == '0';
+    const int fr = 3 * K + G_NSCAL, bl = K <= kMdQuadMaxK ? md2_quad_frame(K) : 0;
+    Md2Launch L;
+    L.frame = fr > bl ? fr : bl;
+    L.grid = (unsigned)n_pairs;            // the quad and wave forms: one workgroup per pair
+    L.block = kWave;
+    if (K <= kMdQuadMaxK && max_poly_K <= 16 && lds_q <= 48 * 1024 && !want_wave && !want_lane) {      // both children side by side
+        L.form = (planar && !no_planar) ? MD2_QUAD_PLANAR : MD2_QUAD_3D;
+        L.lds = lds_q;
+    } else if (lds_w <= 48 * 1024 && max_poly_K <= kMdMaxK && !want_lane) {                             // one pair per wavefront
+        L.form = MD2_WAVE;
+        L.lds = lds_w;
+    } else {                                                                                            // one lane per pair
+        L.form = MD2_LANE;
+        L.grid = (unsigned)((n_pairs + 63) / 64);
+        L.block = 64;
+        L.lds = 0;
+    }
+    return L;
+}
+
+// doubles of frame stack obtg_min_dist2poly has to provide: a stack per pair
+size_t min_dist2poly_stack_doubles(int K, int max_depth, int n_pairs, int max_poly_K, bool planar)
+{
+    return (size_t)max_depth * md2_launch(K, max_depth, n_pairs, max_poly_K, planar).frame * n_pairs;
+}
+
 int launch_min_dist2poly(obtg_ctx* c, const double* d_curves, int K, const double* d_soa,
                          const int* d_off, const int* d_pc, const int* d_pp, int n_pairs, double eps,
                          int max_iter, int md_cap, int max_depth, int max_nodes, double* d_stack,
@@ -4543,21 +4585,12 @@ int launch_min_dist2poly(obtg_ctx* c, const double* d_curves, int K, const doubl
 {
     if (n_pairs <= 0) return OBTG_OK;
     if (K < 2 || K > kMdMaxK || max_depth < 1) return OBTG_ERR_UNSUPPORTED;
+    const Md2Launch L = md2_launch(K, max_depth, n_pairs, max_poly_K, planar);
     Md2Params p{ d_curves, d_soa, d_off, d_pc, d_pp, n_pairs, K, max_iter, md_cap, max_depth, max_nodes, eps, cube_as_python(eps),
-                 d_stack, d_res, d_info, (int)(min_dist2poly_stack_doubles(K, max_depth) / (size_t)max_depth) };
+                 d_stack, d_res, d_info, L.frame };
     ScopedKernelTimer t(c, OBTG_K_MIN_DIST);
-    const size_t lds_w = sizeof(double) * ((size_t)6 * K + 8 * kMdMaxK + (size_t)max_depth * G_NSCAL);
-    const size_t lds_q = sizeof(double) * ((size_t)2 * md2_quad_blob(K) + 48 + 8 * kMdShRow + 64 +
-                                           (size_t)(max_depth < kMdScsLds ? max_depth : kMdScsLds) * G_NSCAL);
-    // (read per launch: the tests flip them) "wave": no quad form -- the wave form where it fits; "lane": the one-lane form.  Every
-    // form fits the stack obtg_min_dist2poly provides: min_dist2poly_stack_doubles per pair, the larger of the frame forms.
-    const char* env_form = getenv("OBTG_MD_FORM");
-    const bool want_wave = env_form && !strcmp(env_form, "wave"), want_lane = env_form && !strcmp(env_form, "lane");
-    const char* env_planar = getenv("OBTG_MD_PLANAR");                           // (A/B runs and tests; read per launch)
-    const bool no_planar = env_planar && env_planar[0] == '0';
-    if (K <= kMdQuadMaxK && max_poly_K <= 16 && lds_q <= 48 * 1024 && !want_wave && !want_lane) {
-        // both children side by side
-        const bool pl2 = planar && !no_planar;
+    if (L.form <= MD2_QUAD_PLANAR) {
+        const bool pl2 = L.form == MD2_QUAD_PLANAR;
         void (*kern)(const Md2Params) = pl2 ? k_min_dist2poly_quad<true, 0> : k_min_dist2poly_quad<false, 0>;
         switch (K) {        // the counts with a build of their own
 #define OBTG_CASE(NC_) case NC_: kern = pl2 ? k_min_dist2poly_quad<true, NC_> : k_min_dist2poly_quad<false, NC_>; break;
@@ -4565,12 +4598,11 @@ int launch_min_dist2poly(obtg_ctx* c, const double* d_curves, int K, const doubl
 #undef OBTG_CASE
             default: break;
         }
-        hipLaunchKernelGGL(kern, dim3((unsigned)n_pairs), dim3(kWave), lds_q, c->stream, p);
-    }
-    else if (lds_w <= 48 * 1024 && max_poly_K <= kMdMaxK && !want_lane)      // one pair per wavefront
-        hipLaunchKernelGGL(k_min_dist2poly_wave, dim3((unsigned)n_pairs), dim3(kWave), lds_w, c->stream, p);
+        hipLaunchKernelGGL(kern, dim3(L.grid), dim3(L.block), L.lds, c->stream, p);
+    } else if (L.form == MD2_WAVE)
+        hipLaunchKernelGGL(k_min_dist2poly_wave, dim3(L.grid), dim3(L.block), L.lds, c->stream, p);
     else
-        hipLaunchKernelGGL(k_min_dist2poly, dim3((n_pairs + 63) / 64), dim3(64), 0, c->stream, p);
+        hipLaunchKernelGGL(k_min_dist2poly, dim3(L.grid), dim3(L.block), 0, c->stream, p);
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;
 }

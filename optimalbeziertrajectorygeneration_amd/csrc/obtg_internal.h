@@ -66,6 +66,18 @@ struct KernelStat {
     long long launches = 0;
 };
 
+// obtg_ctx::ws_misc: what the batched pair searches of capi.cpp (obtg_gjk_pairs .. obtg_coll_check2poly) keep in each slot.  Other
+// entry points borrow slots as plain scratch between those calls; slot 7 belongs to none of the searches.
+enum WsSlot {
+    WS_POLY_OFF = 0,      // int[n_poly + 1]: polygon offsets
+    WS_PAIR_A = 1,        // int[n_pairs]: first operand of every pair
+    WS_PAIR_B = 2,        // int[n_pairs]: second operand
+    WS_INFO = 3,          // int[4 n_pairs]: counters and status of a curve search; flag | n_support or iters | status of a GJK call
+    WS_TRACE = 4,         // obtg_gjk_pairs: the support trace
+    WS_STACK = 5,         // frame stacks (the frontiers of the robust searches)
+    WS_QUEUE = 6,         // work-queue counter, and behind it obtg_min_dist's pair order
+};
+
 }  // namespace obtg
 
 struct obtg_ctx {
@@ -140,6 +152,7 @@ struct obtg_ctx {
     obtg::DevBuf ws_fd;                   // the view's batch, written only when some kernel needs it
 
     // scratch for host-buffer entry points
+    // (ws_misc: the batched pair searches name their slots, obtg::WsSlot above)
     obtg::DevBuf ws_in, ws_in2, ws_out, ws_misc[8];
     // obtg_min_dist: node counts of the previous evaluation of the SAME pair list (signature = count + hash of the lists):
     // the next evaluation hands its pairs to the worker waves in descending order of them (k_min_dist_wave)
@@ -282,7 +295,7 @@ int launch_min_dist2poly_robust(obtg_ctx* c, const double* d_curves, int K, cons
 double square_as_python(double x);
 double cube_as_python(double x);       // x**3 likewise (bezier.py:1468: eps**3)
 size_t min_dist_stack_doubles(const obtg_ctx* c, int K, int max_depth, int n_pairs, bool planar);   // whole launch, the form launch_min_dist runs
-size_t min_dist2poly_stack_doubles(int K, int max_depth);
+size_t min_dist2poly_stack_doubles(int K, int max_depth, int n_pairs, int max_poly_K, bool planar);   // whole launch, the form launch_min_dist2poly runs
 int min_dist_workers(const obtg_ctx* c, int n_pairs, size_t lds_per_wave, int waves_per_simd);   // worker waves of the queue forms
 
 // ---------------------------------------------------------------- launchers (coll_kernels.hip): _collCheckBez2Bez / _collCheckBez2Poly

@@ -228,6 +228,22 @@ int obtg_temporal_sep_fd_dev(obtg_ctx*, const double* dY0, int n_pert, const int
  * (obtg_fast_kernels(dim, deg) & 1), others OBTG_ERR_UNSUPPORTED. */
 int obtg_one_vs_many_min(obtg_ctx*, const double* one, int B, const double* many, int K, double max_sep, double* out /*[B][K]*/);
 int obtg_one_vs_many_min_dev(obtg_ctx*, const double* d_one, int B, const double* d_many, int K, double max_sep, double* d_out);
+/* The same for curves that live on DIFFERENT time spans: one_span[B][2], many_span[K][2] hold (t0, tf) per curve.  The
+ * reference's Bezier.sub does this through _temporalAlignment (bezier.py:347-374, 903-941 -> split 533-572 ->
+ * deCasteljauSplit 985-1027): both curves are cut down to the overlap [a, e] = [max t0, min tf] -- a curve that starts
+ * before a is split at (a - t0)/(tf - t0) and its right piece kept, then, if it ends after e, that piece is split at
+ * (e - a)/(tf - a) and its left piece kept; an end that already is the overlap's is not touched -- and the difference,
+ * normSquare, elev and minimum run on the pieces.  Pairs with a >= e (disjoint or touching spans: the reference returns
+ * None) get `no_overlap`.  A call whose spans are all equal takes no split and equals obtg_one_vs_many_min bit for bit.
+ * Degrees without a specialised kernel run a runtime-degree form up to 2 deg + DEG_ELEV + 1 <= 1024 (the any-degree
+ * separation kernel's limit); beyond, and for any span with t0 >= tf: OBTG_ERR_ARG.
+ * _dev: the curves and the output are device pointers; the spans stay HOST arrays (16 bytes per curve: they are checked
+ * without a round trip to the device; the call returns once they are copied, the kernel runs asynchronously on the
+ * context's stream). */
+int obtg_one_vs_many_min_spans(obtg_ctx*, const double* one, const double* one_span, int B, const double* many,
+                               const double* many_span, int K, double max_sep, double no_overlap, double* out /*[B][K]*/);
+int obtg_one_vs_many_min_spans_dev(obtg_ctx*, const double* d_one, const double* one_span, int B, const double* d_many,
+                                   const double* many_span, int K, double max_sep, double no_overlap, double* d_out);
 
 /* ---- same sweeps on DEVICE pointers, asynchronous on the context's stream ---------------
  * pair_begin/pair_count select a contiguous block of the lexicographic pair list (the
@@ -546,12 +562,17 @@ int obtg_temporal_sep_true_min_dev(obtg_ctx*, const double* dY, int B, double ma
  * obtg_bern_normsq: Bezier.normSquare() bezier.py:869-889   x[d][n+1]       -> out[2n+1]  ((d/2) quirk kept)
  * obtg_bern_split:  Bezier.split(tDiv)  bezier.py:533-572 -> deCasteljauSplit 985-1027   in[rows][n+1] ->
  *                   left[rows][n+1], right[rows][n+1] at z = (tDiv - t0)/(tf - t0); `right` is in the curve's own
- *                   orientation (the reference reverses deCasteljauSplit's second array, bezier.py:563) */
+ *                   orientation (the reference reverses deCasteljauSplit's second array, bezier.py:563)
+ * obtg_bern_restrict: one curve's share of _temporalAlignment  bezier.py:903-941   in[rows][n+1] on span[rows][2] = (t0, tf)
+ *                   -> out[rows][n+1] on target[rows][2] = (a, e): the right piece of a split at (a - t0)/(tf - t0) when
+ *                   t0 < a, then the left piece of a split at (e - a)/(tf - a) when e < tf (two curves aligned in ONE call
+ *                   instead of up to four obtg_bern_split calls).  OBTG_ERR_ARG unless t0 <= a < e <= tf in every row. */
 int obtg_bern_elev(obtg_ctx*, const double* in, int rows, int n, int R, double* out);
 int obtg_bern_diff(obtg_ctx*, const double* in, int rows, int n, double T, double* out);
 int obtg_bern_mul(obtg_ctx*, const double* a, const double* b, int rows, int m, int n, double* out);
 int obtg_bern_normsq(obtg_ctx*, const double* x, int d, int n, double* out);
 int obtg_bern_split(obtg_ctx*, const double* in, int rows, int n, double z, double* left, double* right);
+int obtg_bern_restrict(obtg_ctx*, const double* in, int rows, int n, const double* span, const double* target, double* out);
 /* Bezier.__call__ / Bezier.curve (bezier.py:184-199, 233-258) -> deCasteljauCurve (bezier.py:945-982): every row of
  * cpts[rows][n+1] at every tau[k]: out[rows][n_tau], T = (tau - t0) / (tf - t0), the de Casteljau triangle per sample. */
 int obtg_bern_eval(obtg_ctx*, const double* cpts, int rows, int n, const double* tau, int n_tau, double t0, double tf, double* out);

@@ -51,6 +51,8 @@ _SIGNATURES = {
                                                           _vp, _vp, _vp, _vp, _vp]),
     "obtg_one_vs_many_min": (_i, [_vp, _vp, _i, _vp, _i, _d, _vp]),
     "obtg_one_vs_many_min_dev": (_i, [_vp, _vp, _i, _vp, _i, _d, _vp]),
+    "obtg_one_vs_many_min_spans": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _d, _d, _vp]),
+    "obtg_one_vs_many_min_spans_dev": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _d, _d, _vp]),
     "obtg_sync": (_i, [_vp]),
     "obtg_len_temporal_sep": (_i, [_vp]),
     "obtg_len_speed": (_i, [_vp]),
@@ -114,6 +116,7 @@ _SIGNATURES = {
     "obtg_bern_mul": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "obtg_bern_normsq": (_i, [_vp, _vp, _i, _i, _vp]),
     "obtg_bern_split": (_i, [_vp, _vp, _i, _i, _d, _vp, _vp]),
+    "obtg_bern_restrict": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "obtg_bern_eval": (_i, [_vp, _vp, _i, _i, _vp, _i, _d, _d, _vp]),
     "obtg_euclidean_obj": (_i, [_vp, _vp, _i, _vp]),
     "obtg_accel_obj": (_i, [_vp, _vp, _vp, _i, _vp]),
@@ -739,6 +742,28 @@ class Context(object):
         self._check(self._lib.obtg_one_vs_many_min_dev(self._h, _vp(d_one), int(B), _vp(d_many), int(K), float(max_sep),
                                                        _vp(d_out)), "obtg_one_vs_many_min_dev")
 
+    def one_vs_many_min_spans(self, one, one_span, many, many_span, max_sep, no_overlap=np.inf):
+        """one_vs_many_min for curves on different time spans (include/obtg.h obtg_one_vs_many_min_spans; the reference's
+        Bezier.sub with _temporalAlignment, bezier.py:347-374, 903-941): one_span[B][2], many_span[K][2] = (t0, tf) per
+        curve; every pair is cut down to its overlap first.  -> out[B][K]; pairs whose spans do not overlap (the
+        reference's None, touching spans included) hold `no_overlap`."""
+        nc = self.deg + 1
+        one = np.ascontiguousarray(one, dtype=np.float64).reshape(-1, self.dim, nc)
+        many = np.ascontiguousarray(many, dtype=np.float64).reshape(-1, self.dim, nc)
+        B, K = one.shape[0], many.shape[0]
+        so, sm = _f64(one_span).reshape(B, 2), _f64(many_span).reshape(K, 2)
+        out = np.empty((B, K))
+        self._check(self._lib.obtg_one_vs_many_min_spans(self._h, _ptr(one), _ptr(so), B, _ptr(many), _ptr(sm), K, float(max_sep),
+                                                         float(no_overlap), _ptr(out)), "obtg_one_vs_many_min_spans")
+        return out
+
+    def one_vs_many_min_spans_dev(self, d_one, one_span, B, d_many, many_span, K, max_sep, d_out, no_overlap=np.inf):
+        """d_one, d_many, d_out: device pointers; one_span[B][2], many_span[K][2]: host arrays."""
+        so, sm = _f64(one_span).reshape(int(B), 2), _f64(many_span).reshape(int(K), 2)
+        self._check(self._lib.obtg_one_vs_many_min_spans_dev(self._h, _vp(d_one), _ptr(so), int(B), _vp(d_many), _ptr(sm), int(K),
+                                                             float(max_sep), float(no_overlap), _vp(d_out)),
+                    "obtg_one_vs_many_min_spans_dev")
+
     def set_second_speed_bound(self, bound, is_max, d_out2):
         """Both speed bounds from one dynamics pass (include/obtg.h obtg_ctx_set_second_speed_bound): while d_out2 (a
         device pointer, [B][N*(2n+R+1)]) is set, dynamics_dev / constraint_sweep_dev also write this bound's rows.
@@ -983,6 +1008,18 @@ class Context(object):
         self._check(self._lib.obtg_bern_split(self._h, _ptr(a), rows, nc - 1, float(z), _ptr(left), _ptr(right)),
                     "obtg_bern_split")
         return left, right
+
+    def bern_restrict(self, cpts, span, target):
+        """Every row of cpts, a curve on span[r] = (t0, tf), cut down to target[r] = (a, e) within it (one span / target for
+        all rows, or one per row) in the reference's _temporalAlignment order -> rows x (n+1) (obtg_bern_restrict)."""
+        a = np.atleast_2d(_f64(cpts))
+        rows, nc = a.shape
+        span = np.ascontiguousarray(np.broadcast_to(_f64(span).reshape(-1, 2), (rows, 2)))
+        target = np.ascontiguousarray(np.broadcast_to(_f64(target).reshape(-1, 2), (rows, 2)))
+        out = np.empty((rows, nc))
+        self._check(self._lib.obtg_bern_restrict(self._h, _ptr(a), rows, nc - 1, _ptr(span), _ptr(target), _ptr(out)),
+                    "obtg_bern_restrict")
+        return out
 
     def bern_eval(self, cpts, tau, t0, tf):
         """Every row of control points at every tau (obtg_bern_eval: de Casteljau per sample) -> rows x len(tau)."""

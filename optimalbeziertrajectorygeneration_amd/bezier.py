@@ -11,9 +11,11 @@ Differences from the reference, on purpose:
   * `minDist` / `minDist2Poly` work (at the reference's HEAD they raise because `gjkNew` is
     never imported, bezier.py:21-22) and report the reference's non-terminating inputs as
     exceptions instead of hanging;
-  * plotting (`plot`, matplotlib) and temporal alignment of curves with different [t0, tf] are outside the
-    accelerated path and are not provided; `curve` / `__call__` -- what the drivers' own
-    plotting code reads after a solve -- are (obtg_bern_eval);
+  * plotting (`plot`, matplotlib) is outside the accelerated path and is not provided; `curve` /
+    `__call__` -- what the drivers' own plotting code reads after a solve -- are (obtg_bern_eval);
+  * curves with different [t0, tf]: the reference's `add` / `sub` always align them (`_temporalAlignment`,
+    bezier.py:903-941); here that is `add(other, align=True)` / `sub(other, align=True)` (obtg_bern_restrict), and the
+    default -- so `+` and `-` -- still raises NotImplementedError on unequal spans;
   * `min` / `max` return the curve's true extremum within `tol` (obtg_bern_extrema: a certified subdivision search), not
     what the reference's recursion returns (bezier.py:631-667, 727-763).  That recursion splits a child at
     `minIdx / deg` taken as an absolute parameter, outside the child's span (bezier.py:659-661 with 560-561): on the
@@ -146,23 +148,33 @@ class Bezier(BezierParams):
     def copy(self):
         return Bezier(self.cpts, self.t0, self.tf)
 
-    # ---- arithmetic (bezier.py:318-374): equal time spans only
+    # ---- arithmetic (bezier.py:318-374).  Curves on different time spans: align=True cuts both down to the overlap first
+    # (the reference always does, `_temporalAlignment` below); the default, and with it `+` and `-`, still refuses them
     def _same_span(self, other):
         if not (self.t0 == other.t0 and self.tf == other.tf):
-            raise NotImplementedError('curves with different [t0, tf] need the reference\'s temporal '
-                                      'alignment (bezier.py:903-941), which is outside the accelerated path')
+            raise NotImplementedError('curves with different [t0, tf]: pass align=True to add / sub for the reference\'s '
+                                      'temporal alignment (bezier.py:903-941); the operators + and - take equal spans only')
 
-    def add(self, other):
-        self._same_span(other)
-        if self.t0 >= self.tf:
-            return None
-        return Bezier(self.cpts + other.cpts, t0=self.t0, tf=self.tf)
+    def _operands(self, other, align):
+        """(cpts, other's cpts, t0, tf) of the two curves on a common span, or None when there is none (t0 >= tf)."""
+        a, b = self, other
+        if align and not (self.t0 == other.t0 and self.tf == other.tf):
+            if max(self.t0, other.t0) >= min(self.tf, other.tf):          # the reference's `if t0 >= tf: return None`
+                return None
+            a, b = _temporalAlignment(self, other)
+        else:
+            self._same_span(other)
+            if self.t0 >= self.tf:
+                return None
+        return a.cpts, b.cpts, a.t0, a.tf
 
-    def sub(self, other):
-        self._same_span(other)
-        if self.t0 >= self.tf:
-            return None
-        return Bezier(self.cpts - other.cpts, t0=self.t0, tf=self.tf)
+    def add(self, other, align=False):
+        ops = self._operands(other, align)
+        return None if ops is None else Bezier(ops[0] + ops[1], t0=ops[2], tf=ops[3])
+
+    def sub(self, other, align=False):
+        ops = self._operands(other, align)
+        return None if ops is None else Bezier(ops[0] - ops[1], t0=ops[2], tf=ops[3])
 
     def mul(self, multiplicand):
         """Product of two curves (bezier.py:376-432), dimension by dimension."""
@@ -310,6 +322,23 @@ class Bezier(BezierParams):
         r = _ctx().coll_check2poly(self._padded()[None], poly, [0, poly.shape[0]], [0], [0], max_nodes=max_nodes)
         _raise_md(r['status'][0], 'collCheck2Poly')
         return int(r['res'][0])
+
+
+def _temporalAlignment(c1, c2):
+    """The reference's function of the same name (bezier.py:903-941): both curves cut down to the overlap
+    [max t0, min tf] of their spans -> (Bezier, Bezier) on that span.  One device call for the two curves
+    (obtg_bern_restrict: the reference's cut order -- what lies before the overlap is split off first, then what lies
+    after it; an end that already is the overlap's is left alone).  The spans must overlap (t0 < tf of the result): the
+    reference extrapolates there and its callers then return None, which `add` / `sub` here do without calling this."""
+    t0, tf = max(c1.t0, c2.t0), min(c1.tf, c2.tf)
+    if c1.dim != c2.dim or c1.deg != c2.deg:      # (one batched call: rows of equal length)
+        parts = [_ctx().bern_restrict(c.cpts, (c.t0, c.tf), (t0, tf)) for c in (c1, c2)]
+    else:
+        rows = np.concatenate([c1.cpts, c2.cpts])
+        spans = np.repeat([(c1.t0, c1.tf), (c2.t0, c2.tf)], c1.dim, axis=0)
+        out = _ctx().bern_restrict(rows, spans, (t0, tf))
+        parts = [out[:c1.dim], out[c1.dim:]]
+    return Bezier(parts[0], t0=t0, tf=tf), Bezier(parts[1], t0=t0, tf=tf)
 
 
 def _raise_md(status, what='minDist'):

@@ -172,21 +172,11 @@ struct OneManyParams {
     double sign, offset;
 };
 
+// the value of one item from its difference curve a = one_b - many_k: shared by k_one_vs_many and k_one_vs_many_spans
 template <int NC, int DIM>
-__global__ __launch_bounds__(256) void k_one_vs_many(const OneManyParams p)
+__device__ __forceinline__ double one_vs_many_value(const double (&a)[DIM][NC], const OneManyParams& p)
 {
-    using S = NsShape<NC, DIM>;
-    constexpr int L = S::L;
-    const long item = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (item >= (long)p.B * p.K) return;
-    const int b = (int)(item / p.K), k = (int)(item - (long)b * p.K);
-    const double* o = p.one + (size_t)b * DIM * NC;
-    const double* m = p.many + (size_t)k * DIM * NC;
-    double a[DIM][NC];
-#pragma unroll
-    for (int q = 0; q < DIM; ++q)
-#pragma unroll
-        for (int c = 0; c < NC; ++c) a[q][c] = o[q * NC + c] - m[q * NC + c];
+    constexpr int L = NsShape<NC, DIM>::L;
     double cf[L];
     normsq_coeffs<NC, DIM>(a, as_ctab(p.W2), cf);
     double mn;
@@ -204,7 +194,99 @@ __global__ __launch_bounds__(256) void k_one_vs_many(const OneManyParams p)
         mn = INFINITY;
         for (int kk = 0; kk < LR; ++kk) mn = fmin(mn, elev_at<L>(ch, Td + kk * L, p.offset));
     }
-    p.out[item] = mn;
+    return mn;
+}
+
+template <int NC, int DIM>
+__global__ __launch_bounds__(256) void k_one_vs_many(const OneManyParams p)
+{
+    const long item = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (item >= (long)p.B * p.K) return;
+    const int b = (int)(item / p.K), k = (int)(item - (long)b * p.K);
+    const double* o = p.one + (size_t)b * DIM * NC;
+    const double* m = p.many + (size_t)k * DIM * NC;
+    double a[DIM][NC];
+#pragma unroll
+    for (int q = 0; q < DIM; ++q)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) a[q][c] = o[q * NC + c] - m[q * NC + c];
+    p.out[item] = one_vs_many_value<NC, DIM>(a, p);
+}
+
+// =====================================================================================
+//  One-vs-many minima of curves on DIFFERENT time spans: the reference's Bezier.sub aligns first (bezier.py:347-374 ->
+//  _temporalAlignment 903-941 -> split 533-572 -> deCasteljauSplit 985-1027).  Both curves are cut down to the overlap
+//  [a, e] = [max t0, min tf] in the reference's order: a curve that starts before a is split at (a - t0)/(tf - t0) and its
+//  right piece kept; then, if it ends after e, that piece (now starting at a) is split at (e - a)/(tf - a) and its left
+//  piece kept.  A curve whose end already is the overlap's is not touched, so a call whose spans are all equal takes no
+//  split and is k_one_vs_many bit for bit.  a >= e (disjoint or touching spans: the reference's None) -> no_overlap.
+// =====================================================================================
+struct OneManySpanParams {
+    OneManyParams b;
+    const double* __restrict__ one_span;    // [B][2]  t0, tf
+    const double* __restrict__ many_span;   // [K][2]
+    double no_overlap;
+};
+
+// the cuts of one curve on [t0, tf] down to [a, e] (t0 <= a < e <= tf)
+struct SpanCut {
+    bool head, tail;          // split off what lies before a / after e
+    double zh, zt;
+    __device__ __forceinline__ SpanCut(double t0, double tf, double a, double e)
+    {
+        head = t0 < a;
+        zh = (a - t0) / (tf - t0);
+        if (head) t0 = a;
+        tail = tf > e;
+        zt = (e - t0) / (tf - t0);
+    }
+};
+
+// one coordinate row, in place in registers: every level is (1-z) p[i] + z p[i+1]
+template <int NC>
+__device__ __forceinline__ void restrict_row(double (&p)[NC], const SpanCut& s)
+{
+    if (s.head) {             // the right piece: level lev overwrites p[0 .. NC-lev), its last element stays behind
+        const double z = s.zh, w = 1.0 - z;
+#pragma unroll
+        for (int lev = 1; lev < NC; ++lev)
+#pragma unroll
+            for (int i = 0; i < NC - lev; ++i) p[i] = w * p[i] + z * p[i + 1];
+    }
+    if (s.tail) {             // the left piece: level lev overwrites p[lev .. NC), its first element stays behind
+        const double z = s.zt, w = 1.0 - z;
+#pragma unroll
+        for (int lev = 1; lev < NC; ++lev)
+#pragma unroll
+            for (int i = NC - 1; i >= lev; --i) p[i] = w * p[i - 1] + z * p[i];
+    }
+}
+
+template <int NC, int DIM>
+__global__ __launch_bounds__(256) void k_one_vs_many_spans(const OneManySpanParams p)
+{
+    const long item = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (item >= (long)p.b.B * p.b.K) return;
+    const int b = (int)(item / p.b.K), k = (int)(item - (long)b * p.b.K);
+    const double ot0 = p.one_span[2 * b], otf = p.one_span[2 * b + 1];
+    const double mt0 = p.many_span[2 * k], mtf = p.many_span[2 * k + 1];
+    const double a = ot0 > mt0 ? ot0 : mt0, e = otf < mtf ? otf : mtf;
+    if (a >= e) { p.b.out[item] = p.no_overlap; return; }
+    const SpanCut co(ot0, otf, a, e), cm(mt0, mtf, a, e);
+    const double* o = p.b.one + (size_t)b * DIM * NC;
+    const double* m = p.b.many + (size_t)k * DIM * NC;
+    double d[DIM][NC];
+#pragma unroll
+    for (int q = 0; q < DIM; ++q) {       // one dimension at a time: two rows live next to the difference
+        double x[NC], y[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) { x[c] = o[q * NC + c]; y[c] = m[q * NC + c]; }
+        restrict_row<NC>(x, co);
+        restrict_row<NC>(y, cm);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) d[q][c] = x[c] - y[c];
+    }
+    p.b.out[item] = one_vs_many_value<NC, DIM>(d, p.b);
 }
 
 // =====================================================================================
@@ -551,12 +633,44 @@ __device__ __forceinline__ double conv_at(const double* ah, int la, const double
     return s;
 }
 
+// ah = [dim][n+1] scaled operand C(n,j) a_j in LDS (complete), ch = [2n+1] scratch: the product, the elevation and the
+// output of one item (row `row` of the output) -- the second half of k_generic_normsq_elev, shared with the aligned form
+__device__ __forceinline__ void generic_normsq_elev_tail(const GenParams& p, const double* ah, double* ch, const size_t row, const int lane)
+{
+    const int n = p.n, nc = n + 1, L = 2 * n + 1, LR = L + p.R, dim = p.dim;
+    const double* b2n = p.bin + p.o_2n;
+    double mloc = INFINITY;
+    for (int k = lane; k < L; k += kWave) {
+        double s = 0.0;
+        for (int q = 0; q < dim; ++q) s += conv_at(ah + q * nc, nc, ah + q * nc, nc, k);
+        const double c = (0.5 * dim) * s / b2n[k];
+        if (p.R == 0) {
+            if (p.min_only) mloc = fmin(mloc, c);
+            else p.out[row * LR + k] = p.sign * c + p.offset;
+        } else ch[k] = c * b2n[k];
+    }
+    if (p.R > 0) {
+        __syncthreads();
+        const double* bR = p.bin + p.o_R;
+        const double* b2nR = p.bin + p.o_2nR;
+        for (int k = lane; k < LR; k += kWave) {
+            const double s = conv_at(ch, L, bR, p.R + 1, k) / b2nR[k];
+            if (p.min_only) mloc = fmin(mloc, s);
+            else p.out[row * LR + k] = p.sign * s + p.offset;
+        }
+    }
+    if (p.min_only) {
+        for (int o = 32; o > 0; o >>= 1) mloc = fmin(mloc, __shfl_down(mloc, o));
+        if (lane == 0) p.out[row] = p.sign * mloc + p.offset;
+    }
+}
+
 template <int MODE>
 __global__ __launch_bounds__(kWave) void k_generic_normsq_elev(const GenParams p)
 {
     extern __shared__ double lds[];
     const int lane = threadIdx.x;
-    const int n = p.n, nc = n + 1, L = 2 * n + 1, LR = L + p.R, dim = p.dim;
+    const int n = p.n, nc = n + 1, L = 2 * n + 1, dim = p.dim;
     const long gi = blockIdx.x;
     const int b = (int)(gi / p.item_count);
     const int item = p.item_begin + (int)(gi - (long)b * p.item_count);
@@ -564,7 +678,6 @@ __global__ __launch_bounds__(kWave) void k_generic_normsq_elev(const GenParams p
     double* ch = lds + dim * nc;    // [L]         C(2n,j) * c_j
     double* tm = ch + L;            // [dim][nc]   scratch (vehicle mode)
     const double* bn = p.bin + p.o_n;
-    const double* b2n = p.bin + p.o_2n;
     const double* Yrow = p.Y + (size_t)b * p.n_veh * dim * nc;
 
     if (MODE == 0) {
@@ -593,31 +706,74 @@ __global__ __launch_bounds__(kWave) void k_generic_normsq_elev(const GenParams p
         }
     }
     __syncthreads();
-    const size_t row = ((size_t)b * p.item_count + (size_t)(item - p.item_begin));
-    double mloc = INFINITY;
-    for (int k = lane; k < L; k += kWave) {
-        double s = 0.0;
-        for (int q = 0; q < dim; ++q) s += conv_at(ah + q * nc, nc, ah + q * nc, nc, k);
-        const double c = (0.5 * dim) * s / b2n[k];
-        if (p.R == 0) {
-            if (p.min_only) mloc = fmin(mloc, c);
-            else p.out[row * LR + k] = p.sign * c + p.offset;
-        } else ch[k] = c * b2n[k];
-    }
-    if (p.R > 0) {
+    generic_normsq_elev_tail(p, ah, ch, (size_t)b * p.item_count + (size_t)(item - p.item_begin), lane);
+}
+
+// ---- restriction of a row to a part of its span, any degree: one wave, the row in LDS (the cut order of SpanCut above)
+// de Casteljau at z of row[nc]; the kept piece (right: from the split point on, in the curve's own orientation; else
+// the piece before it) replaces row.  nxt, res: nc doubles of scratch each.  Level by level as k_bern_split.
+__device__ __forceinline__ void split_keep_lds(double* row, double* nxt, double* res, int nc, double z, bool right, int lane)
+{
+    const int n = nc - 1;
+    const double w = 1.0 - z;
+    double* cur = row;
+    for (int lev = 0; lev < n; ++lev) {
+        const int len = nc - lev;
+        if (lane == 0) res[right ? n - lev : lev] = cur[right ? len - 1 : 0];
+        for (int i = lane; i < len - 1; i += kWave) nxt[i] = w * cur[i] + z * cur[i + 1];
         __syncthreads();
-        const double* bR = p.bin + p.o_R;
-        const double* b2nR = p.bin + p.o_2nR;
-        for (int k = lane; k < LR; k += kWave) {
-            const double s = conv_at(ch, L, bR, p.R + 1, k) / b2nR[k];
-            if (p.min_only) mloc = fmin(mloc, s);
-            else p.out[row * LR + k] = p.sign * s + p.offset;
-        }
+        double* t = cur; cur = nxt; nxt = t;
     }
-    if (p.min_only) {
-        for (int o = 32; o > 0; o >>= 1) mloc = fmin(mloc, __shfl_down(mloc, o));
-        if (lane == 0) p.out[row] = p.sign * mloc + p.offset;
+    if (lane == 0) res[right ? 0 : n] = cur[0];
+    __syncthreads();
+    for (int i = lane; i < nc; i += kWave) row[i] = res[i];
+    __syncthreads();
+}
+
+__device__ __forceinline__ void restrict_row_lds(double* row, double* nxt, double* res, int nc, const SpanCut& s, int lane)
+{
+    if (s.head) split_keep_lds(row, nxt, res, nc, s.zh, true, lane);
+    if (s.tail) split_keep_lds(row, nxt, res, nc, s.zt, false, lane);
+}
+
+// k_one_vs_many_spans for the shapes without a specialised kernel: one wave per (candidate, other curve), the
+// restriction in LDS, then the any-degree separation arithmetic (generic_normsq_elev_tail, minimum kept)
+__global__ __launch_bounds__(kWave) void k_generic_one_vs_many_spans(const GenParams p, const double* __restrict__ one,
+                                                                     const double* __restrict__ many,
+                                                                     const double* __restrict__ one_span,
+                                                                     const double* __restrict__ many_span, int K, double no_overlap)
+{
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x;
+    const int nc = p.n + 1, L = 2 * p.n + 1, dim = p.dim;
+    const size_t item = blockIdx.x;
+    const int b = (int)(item / K), k = (int)(item - (size_t)b * K);
+    const double ot0 = one_span[2 * b], otf = one_span[2 * b + 1];
+    const double mt0 = many_span[2 * k], mtf = many_span[2 * k + 1];
+    const double a = ot0 > mt0 ? ot0 : mt0, e = otf < mtf ? otf : mtf;
+    if (a >= e) {                   // (the whole wave: the spans belong to the item)
+        if (lane == 0) p.out[item] = no_overlap;
+        return;
     }
+    const SpanCut co(ot0, otf, a, e), cm(mt0, mtf, a, e);
+    double* ah = lds;               // [dim][nc]
+    double* ch = ah + dim * nc;     // [L]
+    double* rm = ch + L;            // [nc] the other curve's row
+    double* nxt = rm + nc;          // [nc]
+    double* res = nxt + nc;         // [nc]
+    const double* bn = p.bin + p.o_n;
+    const double* o = one + (size_t)b * dim * nc;
+    const double* m = many + (size_t)k * dim * nc;
+    for (int q = 0; q < dim; ++q) {
+        double* ro = ah + q * nc;
+        for (int c = lane; c < nc; c += kWave) { ro[c] = o[q * nc + c]; rm[c] = m[q * nc + c]; }
+        __syncthreads();
+        restrict_row_lds(ro, nxt, res, nc, co, lane);
+        restrict_row_lds(rm, nxt, res, nc, cm, lane);
+        for (int c = lane; c < nc; c += kWave) ro[c] = (ro[c] - rm[c]) * bn[c];
+        __syncthreads();
+    }
+    generic_normsq_elev_tail(p, ah, ch, item, lane);
 }
 
 // Register-tiled convolution for the long products of the generic angular-rate kernel.
@@ -975,6 +1131,21 @@ __global__ __launch_bounds__(kWave) void k_bern_split(const BernParams p, double
         double* t = cur; cur = nxt; nxt = t;
     }
     if (lane == 0) { L[n] = cur[0]; Rt[0] = cur[0]; }
+}
+
+// _temporalAlignment's cuts of one curve (bezier.py:903-941), batched: row r of in[rows][nc] on span[r] = (t0, tf) is cut
+// down to target[r] = (a, e), t0 <= a < e <= tf, in the order of SpanCut; one wave per row, the row in LDS.
+__global__ __launch_bounds__(kWave) void k_bern_restrict(const double* __restrict__ in, const double* __restrict__ span,
+                                                         const double* __restrict__ target, double* __restrict__ out, int nc)
+{
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x, r = blockIdx.x;
+    double* row = lds;
+    for (int e = lane; e < nc; e += kWave) row[e] = in[(size_t)r * nc + e];
+    __syncthreads();
+    const SpanCut s(span[2 * r], span[2 * r + 1], target[2 * r], target[2 * r + 1]);
+    restrict_row_lds(row, lds + nc, lds + 2 * nc, nc, s, lane);
+    for (int e = lane; e < nc; e += kWave) out[(size_t)r * nc + e] = row[e];
 }
 
 // Bezier.__call__ / Bezier.curve (bezier.py:184-199, 233-258) -> deCasteljauCurve (bezier.py:945-982): every row of control
@@ -1497,6 +1668,48 @@ int launch_one_vs_many_min(obtg_ctx* c, const double* d_one, int B, const double
     return OBTG_OK;
 }
 
+// d_one_span[B][2], d_many_span[K][2]: (t0, tf) per curve, t0 < tf (checked by the caller)
+int launch_one_vs_many_min_spans(obtg_ctx* c, const double* d_one, const double* d_one_span, int B, const double* d_many,
+                                 const double* d_many_span, int K, double max_sep, double no_overlap, double* d_out)
+{
+    if (B <= 0 || K <= 0) return OBTG_OK;
+    int rc = ensure_tables(c);
+    if (rc) return rc;
+    const long items = (long)B * K;
+    const int nc = c->deg + 1;
+    void (*kern)(const OneManySpanParams) = nullptr;
+    if (fast_shape(c)) {
+#define OBTG_CASE(NC_, D_) if (nc == NC_ && c->dim == D_) kern = k_one_vs_many_spans<NC_, D_>;
+#define OBTG_CASE_D(NC_) OBTG_CASE(NC_, 2) OBTG_CASE(NC_, 3)
+        OBTG_NC_SEP(OBTG_CASE_D)
+#undef OBTG_CASE_D
+#undef OBTG_CASE
+    }
+    if (kern) {
+        OneManySpanParams p{};
+        p.b.one = d_one; p.b.many = d_many; p.b.W2 = c->d_w2.as<double>(); p.b.Td = c->d_Td.as<double>(); p.b.out = d_out;
+        p.b.B = B; p.b.K = K; p.b.R = c->R;
+        p.b.sign = 1.0; p.b.offset = 0.0 - square_as_python(max_sep);
+        p.one_span = d_one_span; p.many_span = d_many_span; p.no_overlap = no_overlap;
+        const int threads = items >= 16384 ? 256 : 64;        // (as launch_one_vs_many_min)
+        ScopedKernelTimer t(c, OBTG_K_TEMPORAL_SEP);
+        hipLaunchKernelGGL(kern, dim3((unsigned)((items + threads - 1) / threads)), dim3(threads), 0, c->stream, p);
+        OBTG_HIP(c, hipGetLastError());
+        return OBTG_OK;
+    }
+    // any degree: the limits of the any-degree separation kernel (launch_temporal_sep)
+    if (2 * c->deg + c->R + 1 > kMaxGenericLen || items > 0x7fffffffL) return OBTG_ERR_ARG;
+    GenParams g{};
+    if ((rc = gen_common(c, g))) return rc;
+    g.out = d_out; g.sign = 1.0; g.offset = 0.0 - square_as_python(max_sep); g.min_only = 1;
+    const size_t lds = sizeof(double) * ((size_t)c->dim * nc + 2 * c->deg + 1 + 3 * (size_t)nc);
+    ScopedKernelTimer t(c, OBTG_K_TEMPORAL_SEP);
+    hipLaunchKernelGGL(k_generic_one_vs_many_spans, dim3((unsigned)items), dim3(kWave), lds, c->stream, g, d_one, d_many,
+                       d_one_span, d_many_span, K, no_overlap);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
 template <int NC>
 static int launch_sep_dyn_elev_t(obtg_ctx* c, SepDynElevParams& sp, int B)
 {
@@ -1710,6 +1923,17 @@ int launch_bern_split(obtg_ctx* c, const double* d_in, int rows, int n, double z
     p.a = d_in; p.out = d_left; p.rows = rows; p.n = n; p.T = z;
     ScopedKernelTimer t(c, OBTG_K_BERN);
     hipLaunchKernelGGL(k_bern_split, dim3(rows), dim3(kWave), sizeof(double) * 2 * (n + 1), c->stream, p, d_right);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
+int launch_bern_restrict(obtg_ctx* c, const double* d_in, int rows, int n, const double* d_span, const double* d_target, double* d_out)
+{
+    if (rows <= 0) return OBTG_OK;
+    if (n < 0 || n + 1 > kMaxGenericLen) return OBTG_ERR_UNSUPPORTED;
+    ScopedKernelTimer t(c, OBTG_K_BERN);
+    hipLaunchKernelGGL(k_bern_restrict, dim3(rows), dim3(kWave), sizeof(double) * 3 * (n + 1), c->stream, d_in, d_span, d_target,
+                       d_out, n + 1);
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;
 }

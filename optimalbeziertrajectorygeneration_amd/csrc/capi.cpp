@@ -231,12 +231,12 @@ const char* obtg_abi_symbols(void)
         "obtg_len_temporal_sep\0obtg_len_speed\0obtg_len_ang_rate\0obtg_num_pairs\0"
         "obtg_temporal_sep\0obtg_speed\0obtg_ang_rate\0obtg_temporal_sep_min\0obtg_temporal_sep_min_range\0obtg_temporal_sep_active\0obtg_temporal_sep_active_dev\0obtg_temporal_sep_min_gather_dev\0obtg_temporal_sep_fd_min_rows_dev\0"
         "obtg_comm_unique_id\0obtg_comm_create\0obtg_comm_destroy\0obtg_comm_size\0obtg_comm_rank\0obtg_comm_last_error\0obtg_comm_all_gather_dev\0obtg_pair_block\0obtg_unpack_pair_blocks_dev\0"
-        "obtg_temporal_sep_fd\0obtg_temporal_sep_fd_dev\0obtg_one_vs_many_min\0obtg_one_vs_many_min_dev\0"
+        "obtg_temporal_sep_fd\0obtg_temporal_sep_fd_dev\0obtg_one_vs_many_min\0obtg_one_vs_many_min_dev\0obtg_one_vs_many_min_spans\0obtg_one_vs_many_min_spans_dev\0"
         "obtg_temporal_sep_dev\0obtg_temporal_sep_min_dev\0obtg_speed_dev\0obtg_ang_rate_dev\0obtg_dynamics_dev\0"
         "obtg_fd_batch_dev\0obtg_fd_view_begin\0obtg_fd_view_begin_rows\0obtg_fd_view_end\0obtg_fd_forms_on_the_fly\0obtg_pair_sweep_fd_dev\0obtg_dynamics_fd_dev\0obtg_gjk_pairs\0obtg_ctx_set_polygons\0obtg_ctx_set_hull_pairs\0"
         "obtg_ctx_set_fd_dedup\0obtg_ctx_set_fd_view_structured\0obtg_ctx_set_gjk_history\0obtg_pair_sweep_dev\0obtg_constraint_sweep_dev\0obtg_constraint_sweep_fd_structured_dev\0obtg_constraint_sweep_fd_structured_rows_dev\0obtg_gjk_swarm_dev\0obtg_gjk_swarm\0obtg_min_dist\0obtg_min_dist_robust\0obtg_min_dist2poly\0obtg_min_dist2poly_robust\0obtg_gjk_true_pairs\0obtg_coll_check\0obtg_coll_check2poly\0"
         "obtg_bern_extrema\0obtg_bern_extrema_dev\0obtg_temporal_sep_true_min\0obtg_temporal_sep_true_min_dev\0"
-        "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_eval\0"
+        "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_restrict\0obtg_bern_eval\0"
         "obtg_euclidean_obj\0obtg_accel_obj\0obtg_jerk_obj\0"
         "obtg_temporal_sep_jac\0obtg_temporal_sep_jac_dev\0obtg_speed_jac\0obtg_speed_jac_dev\0obtg_ang_rate_jac\0obtg_ang_rate_jac_dev\0obtg_euclidean_grad\0obtg_deriv_energy_grad\0"
         "obtg_set_profiling\0obtg_set_profile_period\0obtg_kernel_stats\0obtg_reset_kernel_stats\0obtg_kernel_name\0";
@@ -786,6 +786,55 @@ int obtg_one_vs_many_min(obtg_ctx* c, const double* one, int B, const double* ma
     if ((rc = h2d(c, c->ws_in2, many, curve * K))) return rc;
     if ((rc = c->ws_out.reserve(sizeof(double) * (size_t)B * K, true))) return rc;
     if ((rc = launch_one_vs_many_min(c, c->ws_in.as<double>(), B, c->ws_in2.as<double>(), K, max_sep, c->ws_out.as<double>()))) return rc;
+    return d2h(c, out, c->ws_out.p, sizeof(double) * (size_t)B * K);
+}
+
+// Bezier.sub on curves with different [t0, tf] (bezier.py:347-374 -> _temporalAlignment 903-941), then the same minimum
+static bool spans_ok(const double* s, int n)
+{
+    for (int i = 0; i < n; ++i) if (!(s[2 * i] < s[2 * i + 1])) return false;       // (NaN ends are refused too)
+    return true;
+}
+
+// the spans of both sides -> ws_misc[0], ws_misc[1]
+static int stage_spans(obtg_ctx* c, const double* one_span, int B, const double* many_span, int K)
+{
+    int rc = h2d(c, c->ws_misc[0], one_span, sizeof(double) * 2 * (size_t)B);
+    if (rc) return rc;
+    return h2d(c, c->ws_misc[1], many_span, sizeof(double) * 2 * (size_t)K);
+}
+
+int obtg_one_vs_many_min_spans_dev(obtg_ctx* c, const double* d_one, const double* one_span, int B, const double* d_many,
+                                   const double* many_span, int K, double max_sep, double no_overlap, double* d_out)
+{
+    if (!check_ctx(c) || B < 0 || K < 0) return OBTG_ERR_ARG;
+    if (B == 0 || K == 0) return OBTG_OK;
+    if (!d_one || !d_many || !d_out || !one_span || !many_span) return OBTG_ERR_ARG;
+    if (!spans_ok(one_span, B) || !spans_ok(many_span, K)) return OBTG_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    int rc = stage_spans(c, one_span, B, many_span, K);
+    if (rc) return rc;
+    OBTG_HIP(c, hipStreamSynchronize(c->stream));       // the caller's span arrays are free on return; the launch is asynchronous
+    return launch_one_vs_many_min_spans(c, d_one, c->ws_misc[0].as<double>(), B, d_many, c->ws_misc[1].as<double>(), K, max_sep,
+                                        no_overlap, d_out);
+}
+
+int obtg_one_vs_many_min_spans(obtg_ctx* c, const double* one, const double* one_span, int B, const double* many,
+                               const double* many_span, int K, double max_sep, double no_overlap, double* out)
+{
+    if (!check_ctx(c) || B < 0 || K < 0) return OBTG_ERR_ARG;
+    if (B == 0 || K == 0) return OBTG_OK;
+    if (!one || !many || !out || !one_span || !many_span) return OBTG_ERR_ARG;
+    if (!spans_ok(one_span, B) || !spans_ok(many_span, K)) return OBTG_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    const size_t curve = sizeof(double) * (size_t)c->dim * (c->deg + 1);
+    int rc = h2d(c, c->ws_in, one, curve * B, true);
+    if (rc) return rc;
+    if ((rc = h2d(c, c->ws_in2, many, curve * K))) return rc;
+    if ((rc = stage_spans(c, one_span, B, many_span, K))) return rc;
+    if ((rc = c->ws_out.reserve(sizeof(double) * (size_t)B * K, true))) return rc;
+    if ((rc = launch_one_vs_many_min_spans(c, c->ws_in.as<double>(), c->ws_misc[0].as<double>(), B, c->ws_in2.as<double>(),
+                                           c->ws_misc[1].as<double>(), K, max_sep, no_overlap, c->ws_out.as<double>()))) return rc;
     return d2h(c, out, c->ws_out.p, sizeof(double) * (size_t)B * K);
 }
 
@@ -1544,6 +1593,24 @@ int obtg_bern_split(obtg_ctx* c, const double* in, int rows, int n, double z, do
     if ((rc = launch_bern_split(c, c->ws_in.as<double>(), rows, n, z, dl, dl + len))) return rc;
     if ((rc = d2h_copy(c, left, dl, sizeof(double) * len))) return rc;
     return d2h(c, right, dl + len, sizeof(double) * len);
+}
+
+int obtg_bern_restrict(obtg_ctx* c, const double* in, int rows, int n, const double* span, const double* target, double* out)
+{
+    if (!check_ctx(c) || !in || !span || !target || !out || rows < 0 || n < 0) return OBTG_ERR_ARG;
+    for (int r = 0; r < rows; ++r)
+        if (!(span[2 * r] <= target[2 * r] && target[2 * r] < target[2 * r + 1] && target[2 * r + 1] <= span[2 * r + 1])) return OBTG_ERR_ARG;
+    if (rows == 0) return OBTG_OK;
+    (void)hipSetDevice(c->device);
+    const size_t len = (size_t)rows * (n + 1);
+    int rc = h2d(c, c->ws_in, in, sizeof(double) * len);
+    if (rc) return rc;
+    if ((rc = h2d(c, c->ws_misc[0], span, sizeof(double) * 2 * (size_t)rows))) return rc;
+    if ((rc = h2d(c, c->ws_misc[1], target, sizeof(double) * 2 * (size_t)rows))) return rc;
+    if ((rc = c->ws_out.reserve(sizeof(double) * len))) return rc;
+    if ((rc = launch_bern_restrict(c, c->ws_in.as<double>(), rows, n, c->ws_misc[0].as<double>(), c->ws_misc[1].as<double>(),
+                                   c->ws_out.as<double>()))) return rc;
+    return d2h(c, out, c->ws_out.p, sizeof(double) * len);
 }
 
 int obtg_bern_eval(obtg_ctx* c, const double* cpts, int rows, int n, const double* tau, int n_tau, double t0, double tf, double* out)

@@ -234,6 +234,9 @@ int launch_temporal_sep_fd(obtg_ctx* c, const double* dY0, int n_pert, const int
                            const double* d_pval, double max_sep, double* d_out, int min_only = 0, int fd_row0 = 0,
                            int fd_fixed = 0, double fd_h = 0.0);
 int launch_one_vs_many_min(obtg_ctx* c, const double* d_one, int B, const double* d_many, int K, double max_sep, double* d_out);
+int launch_one_vs_many_min_spans(obtg_ctx* c, const double* d_one, const double* d_one_span, int B, const double* d_many,
+                                 const double* d_many_span, int K, double max_sep, double no_overlap, double* d_out);
+int launch_bern_restrict(obtg_ctx* c, const double* d_in, int rows, int n, const double* d_span, const double* d_target, double* d_out);
 int launch_speed(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max,
                  double* d_out);
 int launch_ang_rate(obtg_ctx* c, const double* dY, const double* d_tf, int B, double max_rate,

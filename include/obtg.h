@@ -90,7 +90,9 @@ const char* obtg_strerror(int code);
  *      Later, still 7: new: the true Bernstein extrema obtg_bern_extrema[_dev] (timed under OBTG_K_BERN) and
  *      obtg_temporal_sep_true_min[_dev] (timed under OBTG_K_TEMPORAL_SEP).
  *      Later, still 7: new: obtg_ctx_set_fd_view_structured.  obtg_constraint_sweep_dev with dY = NULL inside a view now
- *      takes the structured step where it applies: the same arrays with the same bits, so no meaning changed. */
+ *      takes the structured step where it applies: the same arrays with the same bits, so no meaning changed.
+ *      Later, still 7: new: the envelope Jacobian of the true-minimum rows, obtg_temporal_sep_true_min_jac[_dev] (timed
+ *      under OBTG_K_TEMPORAL_SEP). */
 #define OBTG_ABI_VERSION 7
 int obtg_abi_version(void);
 
@@ -554,6 +556,32 @@ int obtg_temporal_sep_true_min(obtg_ctx*, const double* Y, int B, double max_sep
                                double* out /*[B][P]*/, double* t_star /*[B][P], nullable*/, int* status /*[B][P], nullable*/);
 int obtg_temporal_sep_true_min_dev(obtg_ctx*, const double* dY, int B, double max_sep, double eps_rel, int max_nodes,
                                    double* d_out, double* d_t_star, int* d_status);
+/* obtg_temporal_sep_true_min with its envelope (Danskin) Jacobian.  out, t_star, status are, bit for bit, those of
+ * obtg_temporal_sep_true_min with the same arguments: the search is the same.  jac[B][P][d][n+1] (d = dim, n = deg) is the
+ * partial derivative of the pair's polynomial p -- the one that call minimises, normSquare's (d/2) factor included -- taken
+ * AT THE RETURNED t_star with respect to the control points Y[a*d + c][i] of the pair's first object a:
+ *     jac[c][i] = d * B_i^n(t_star) * Delta_c(t_star),   Delta = v_a - v_b,
+ * which is sum_k B_k^2n(t_star) J_k over obtg_temporal_sep_jac's R = 0 blocks J_k.  The conventions are that entry point's:
+ * the second object's block is the exact negation and is not stored, a point obstacle has no variable, a pair of two
+ * obstacles is all zeros.  For g(Y) = min_t p(t; Y) this is dg/dY wherever the minimiser is unique (the envelope theorem);
+ * where two minimisers tie it is one element of the subdifferential.  t_star is the search's dyadic point with
+ * p(t_star) - min p <= tol, not a polished root of p': at a smooth interior minimum |t_star - t_min| is of the order
+ * sqrt(tol / p''), and the block differs from the one at t_min by that times the mixed second derivative of p.
+ * t_star = 0 or 1 leaves column 0 or n alone non-zero (the others are exact zeros).  A row with a non-finite coefficient gets a
+ * NaN block, like val (status OBTG_MD_OK).  With a status other than OBTG_MD_OK the block is still the derivative at the
+ * returned t_star.
+ * B_i^n(t_star) comes from the de Casteljau recurrence on the basis, Delta_c(t_star) from those weights in index order, every
+ * multiply-add an explicit fma (csrc/bern_device.h envelope_block): a block depends on the pair's control points and t_star
+ * alone -- not on B, the row's position, the entry point (host and _dev: same bits) or the kernel form.  Kernel form: shapes
+ * with a specialised kernel (obtg_fast_kernels & 1) form the blocks at the end of the search launch -- nothing but Y is read,
+ * one launch; other degrees up to 31 run the value path and then one launch that forms the blocks from Y and t_star (a context
+ * created while the environment holds OBTG_TRUE_MIN_JAC_FUSED=0 does so on every shape: same bits); beyond:
+ * OBTG_ERR_UNSUPPORTED.  t_star and status are nullable; _dev: dY may be NULL inside an obtg_fd_view. */
+int obtg_temporal_sep_true_min_jac(obtg_ctx*, const double* Y, int B, double max_sep, double eps_rel, int max_nodes,
+                                   double* out /*[B][P]*/, double* t_star /*[B][P], nullable*/, int* status /*[B][P], nullable*/,
+                                   double* jac /*[B][P][d][n+1]*/);
+int obtg_temporal_sep_true_min_jac_dev(obtg_ctx*, const double* dY, int B, double max_sep, double eps_rel, int max_nodes,
+                                       double* d_out, double* d_t_star, int* d_status, double* d_jac);
 
 /* ---- single-curve Bernstein algebra (the Bezier object's methods, batched over rows) ----
  * obtg_bern_elev:   Bezier.elev(R)      bezier.py:469-495   in[rows][n+1]   -> out[rows][n+R+1]

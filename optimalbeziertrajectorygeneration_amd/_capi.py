@@ -111,6 +111,8 @@ _SIGNATURES = {
     "obtg_bern_extrema_dev": (_i, [_vp, _vp, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "obtg_temporal_sep_true_min": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
     "obtg_temporal_sep_true_min_dev": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
+    "obtg_temporal_sep_true_min_jac": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp]),
+    "obtg_temporal_sep_true_min_jac_dev": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp]),
     "obtg_bern_elev": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "obtg_bern_diff": (_i, [_vp, _vp, _i, _i, _d, _vp]),
     "obtg_bern_mul": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
@@ -552,6 +554,26 @@ class Context(object):
         self._check(self._lib.obtg_temporal_sep_true_min_dev(self._h, _vp(dY), B, float(max_sep), float(eps_rel), int(max_nodes),
                                                              _vp(d_out), _vp(d_t_star), _vp(d_status)),
                     "obtg_temporal_sep_true_min_dev")
+
+    def temporal_sep_true_min_jac(self, Y, max_sep, eps_rel=1e-9, max_nodes=100000):
+        """temporal_sep_true_min with its envelope Jacobian (obtg_temporal_sep_true_min_jac): dict(val, t_star, status -- the
+        bits of temporal_sep_true_min --, jac[B][P][dim][deg+1]: d/d(control points of the pair's first object) of the pair's
+        polynomial at t_star; the second object's block is the negation, an obstacle has no variable)."""
+        Y, B = self._rows(Y)
+        out = pinned_empty((B, self.num_pairs))
+        t_star = np.empty((B, self.num_pairs))
+        status = np.zeros((B, self.num_pairs), np.int32)
+        jac = pinned_empty((B, self.num_pairs, self.dim, self.deg + 1))
+        self._check(self._lib.obtg_temporal_sep_true_min_jac(self._h, _ptr(Y), B, float(max_sep), float(eps_rel), int(max_nodes),
+                                                             _ptr(out), _ptr(t_star), _ptr(status), _ptr(jac)),
+                    "obtg_temporal_sep_true_min_jac")
+        return dict(val=out, t_star=t_star, status=status, jac=jac)
+
+    def temporal_sep_true_min_jac_dev(self, dY, B, max_sep, d_out, d_jac, d_t_star=None, d_status=None, eps_rel=1e-9,
+                                      max_nodes=100000):
+        self._check(self._lib.obtg_temporal_sep_true_min_jac_dev(self._h, _vp(dY), B, float(max_sep), float(eps_rel),
+                                                                 int(max_nodes), _vp(d_out), _vp(d_t_star), _vp(d_status),
+                                                                 _vp(d_jac)), "obtg_temporal_sep_true_min_jac_dev")
 
     def bern_extrema(self, c, want_max=False, eps_rel=1e-9, eps_abs=0.0, max_nodes=100000):
         """True minimum (want_max: maximum) over [0, 1] of every row of Bernstein coefficients c[M][K], K <= 64

@@ -205,6 +205,44 @@ __device__ __forceinline__ void normsq_coeffs(const double (&a)[DIM][NC], ctab_t
     }
 }
 
+// Envelope (Danskin) block of one pair at parameter t: the partial derivatives of p(t) = (DIM/2) |Delta(t)|^2,
+// Delta = v_a - v_b, with respect to the control points of a:  out[c][i] = DIM * B_i^n(t) * Delta_c(t), n = nc - 1
+// (obtg_temporal_sep_true_min_jac).  ya: a's [DIM][nc] control points; b's element (c, i) is yb[c * b_cs + i * b_is]
+// (a vehicle: nc, 1; a point obstacle: 1, 0).  The basis values come from the de Casteljau recurrence on the basis itself,
+// w_i <- (1 - t) w_i + t w_(i-1): products and sums of non-negative numbers, no cancellation (not from powers of t);
+// Delta_c(t) = sum_i w_i Delta_c,i in index order, Delta_c,i the rounded difference the value kernels form.
+// Contraction: none is left to the compiler.  Every multiply-add is written as fma(x, y, one product) and every other
+// product stands alone, so this function generates the same arithmetic under `fp contract(fast)` and `(off)`, for every
+// NCMAX >= nc and wherever it is inlined: the blocks of the fused and of the any-degree kernel are the same bits.
+// t = 0 / t = 1 leave exactly one non-zero column (0 / n); a NaN t gives a NaN block.
+template <int NCMAX, int DIM>
+__device__ __forceinline__ void envelope_block(const double* __restrict__ ya, const double* __restrict__ yb, int b_cs, int b_is,
+                                               int nc, double t, double* __restrict__ out)
+{
+    const double s = 1.0 - t;
+    double w[NCMAX];
+#pragma unroll
+    for (int i = 0; i < NCMAX; ++i) w[i] = i == 0 ? 1.0 : 0.0;
+#pragma unroll
+    for (int r = 1; r < NCMAX; ++r)
+        if (r < nc) {
+#pragma unroll
+            for (int i = r; i >= 1; --i) w[i] = __builtin_fma(t, w[i - 1], s * w[i]);
+            w[0] = s * w[0];
+        }
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+        double dl = 0.0;
+#pragma unroll
+        for (int i = 0; i < NCMAX; ++i)
+            if (i < nc) dl = __builtin_fma(w[i], ya[c * nc + i] - yb[c * b_cs + i * b_is], dl);
+        const double kd = (double)DIM * dl;
+#pragma unroll
+        for (int i = 0; i < NCMAX; ++i)
+            if (i < nc) out[c * nc + i] = kd * w[i];
+    }
+}
+
 // write a full [n_valid][LR] tile (pitch TP) as one contiguous run of n_valid*LR doubles
 template <int LR, int TP>
 __device__ __forceinline__ void flush_full(const double* __restrict__ tile, double* __restrict__ gout,

@@ -235,7 +235,7 @@ const char* obtg_abi_symbols(void)
         "obtg_temporal_sep_dev\0obtg_temporal_sep_min_dev\0obtg_speed_dev\0obtg_ang_rate_dev\0obtg_dynamics_dev\0"
         "obtg_fd_batch_dev\0obtg_fd_view_begin\0obtg_fd_view_begin_rows\0obtg_fd_view_end\0obtg_fd_forms_on_the_fly\0obtg_pair_sweep_fd_dev\0obtg_dynamics_fd_dev\0obtg_gjk_pairs\0obtg_ctx_set_polygons\0obtg_ctx_set_hull_pairs\0"
         "obtg_ctx_set_fd_dedup\0obtg_ctx_set_fd_view_structured\0obtg_ctx_set_gjk_history\0obtg_pair_sweep_dev\0obtg_constraint_sweep_dev\0obtg_constraint_sweep_fd_structured_dev\0obtg_constraint_sweep_fd_structured_rows_dev\0obtg_gjk_swarm_dev\0obtg_gjk_swarm\0obtg_min_dist\0obtg_min_dist_robust\0obtg_min_dist2poly\0obtg_min_dist2poly_robust\0obtg_gjk_true_pairs\0obtg_coll_check\0obtg_coll_check2poly\0"
-        "obtg_bern_extrema\0obtg_bern_extrema_dev\0obtg_temporal_sep_true_min\0obtg_temporal_sep_true_min_dev\0"
+        "obtg_bern_extrema\0obtg_bern_extrema_dev\0obtg_temporal_sep_true_min\0obtg_temporal_sep_true_min_dev\0obtg_temporal_sep_true_min_jac\0obtg_temporal_sep_true_min_jac_dev\0"
         "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_restrict\0obtg_bern_eval\0"
         "obtg_euclidean_obj\0obtg_accel_obj\0obtg_jerk_obj\0"
         "obtg_temporal_sep_jac\0obtg_temporal_sep_jac_dev\0obtg_speed_jac\0obtg_speed_jac_dev\0obtg_ang_rate_jac\0obtg_ang_rate_jac_dev\0obtg_euclidean_grad\0obtg_deriv_energy_grad\0"
@@ -270,6 +270,8 @@ int obtg_ctx_create(obtg_ctx** out, int n_veh, int dim, int deg, int deg_elev, i
     { const char* e = getenv("OBTG_ZERO_COPY"); const bool zc = !(e && e[0] == '0'); c->ws_in.io = c->ws_in2.io = c->ws_out.io = zc; }
     // OBTG_FD_VIEW_STRUCTURED=0: contexts start with the structured routing of a view's one-call sweep off (obtg_ctx_set_fd_view_structured)
     { const char* e = getenv("OBTG_FD_VIEW_STRUCTURED"); c->fd_view_structured = !(e && e[0] == '0'); }
+    // OBTG_TRUE_MIN_JAC_FUSED=0: obtg_temporal_sep_true_min_jac forms its blocks in a launch of their own on every shape
+    { const char* e = getenv("OBTG_TRUE_MIN_JAC_FUSED"); c->true_min_jac_fused = !(e && e[0] == '0'); }
     int rc = OBTG_OK;
     c->h_pairs.resize((size_t)2 * c->n_pairs);
     {
@@ -1552,6 +1554,54 @@ int obtg_temporal_sep_true_min(obtg_ctx* c, const double* Y, int B, double max_s
     if ((rc = true_min_launch(c, c->ws_in.as<double>(), B, max_sep, eps_rel, max_nodes, dv, dv + n, di.as<int>()))) return rc;
     if (t_star && (rc = d2h_copy(c, t_star, dv + n, sizeof(double) * n))) return rc;
     if (status && (rc = d2h_copy(c, status, di.p, sizeof(int) * n))) return rc;
+    return d2h(c, out, dv, sizeof(double) * n);
+}
+
+// values, t_star, status as true_min_launch gives them, and the envelope blocks: in the same launch where the shape has a
+// fused kernel, else (or with OBTG_TRUE_MIN_JAC_FUSED=0) from Y and t_star in a launch of their own
+static int true_min_jac_launch(obtg_ctx* c, const double* dY, int B, double max_sep, double eps_rel, int max_nodes, double* d_out,
+                               double* d_t, int* d_status, double* d_jac)
+{
+    if (c->deg + 1 > 32) return OBTG_ERR_UNSUPPORTED;
+    int rc = OBTG_ERR_UNSUPPORTED;
+    if (c->true_min_jac_fused) rc = launch_temporal_sep_true_min(c, dY, B, max_sep, eps_rel, max_nodes, d_out, d_t, d_status, d_jac);
+    if (rc != OBTG_ERR_UNSUPPORTED) return rc;
+    if (!d_t) {
+        DevBuf& wt = c->ws_misc[6];
+        if ((rc = wt.reserve(sizeof(double) * (size_t)B * c->n_pairs))) return rc;
+        d_t = wt.as<double>();
+    }
+    if ((rc = true_min_launch(c, dY, B, max_sep, eps_rel, max_nodes, d_out, d_t, d_status))) return rc;
+    return launch_temporal_sep_envelope(c, dY, B, d_t, d_jac);
+}
+
+int obtg_temporal_sep_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, double max_sep, double eps_rel, int max_nodes,
+                                       double* d_out, double* d_t_star, int* d_status, double* d_jac)
+{
+    if (!check_ctx(c) || !d_out || !d_jac || B < 0 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    return with_batch(c, dY, B, false, [&](const double* src) {
+        return true_min_jac_launch(c, src, B, max_sep, eps_rel, max_nodes, d_out, d_t_star, d_status, d_jac); });
+}
+
+int obtg_temporal_sep_true_min_jac(obtg_ctx* c, const double* Y, int B, double max_sep, double eps_rel, int max_nodes,
+                                   double* out, double* t_star, int* status, double* jac)
+{
+    if (!check_ctx(c) || !Y || !out || !jac || B < 0 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
+    if (B == 0 || c->n_pairs == 0) return OBTG_OK;
+    (void)hipSetDevice(c->device);
+    const size_t n = (size_t)B * c->n_pairs, nj = n * c->dim * (c->deg + 1);
+    int rc = h2d(c, c->ws_in, Y, sizeof(double) * ysize(c) * B, true);
+    if (rc) return rc;
+    if ((rc = c->ws_out.reserve(sizeof(double) * (2 * n + nj)))) return rc;
+    DevBuf& di = c->ws_misc[4];
+    if ((rc = di.reserve(sizeof(int) * n))) return rc;
+    double* dv = c->ws_out.as<double>();
+    if ((rc = true_min_jac_launch(c, c->ws_in.as<double>(), B, max_sep, eps_rel, max_nodes, dv, dv + n, di.as<int>(), dv + 2 * n)))
+        return rc;
+    if (t_star && (rc = d2h_copy(c, t_star, dv + n, sizeof(double) * n))) return rc;
+    if (status && (rc = d2h_copy(c, status, di.p, sizeof(int) * n))) return rc;
+    if ((rc = d2h_copy(c, jac, dv + 2 * n, sizeof(double) * nj))) return rc;
     return d2h(c, out, dv, sizeof(double) * n);
 }
 

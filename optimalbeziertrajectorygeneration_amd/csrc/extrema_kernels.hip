@@ -16,6 +16,12 @@
 // k, a de Casteljau level is one DPP move of the lane above's value and one average (md_device.h wave_next_lane), the left
 // piece is lane 0's value level by level, the right piece what each lane holds when it stops.  No per-lane coefficient
 // arrays in the search (K is a run-time count up to 64), the stack is kExStack x (K + 3) doubles per wave.
+//
+// Envelope Jacobian (obtg_temporal_sep_true_min_jac): the derivative of a pair's polynomial at the t_star the search
+// returned, bern_device.h envelope_block -- written with explicit fma, so it is the same arithmetic here (contraction
+// off) as anywhere else.  Fused form: k_tsep_true_min<NC, DIM, true> re-reads the pair's control points from Y after
+// the search (the differences are dead by then: no register is held across wave_search for it) and every lane writes
+// its own block.  Two-launch form: the value path, then k_tsep_envelope on Y and t_star, any degree up to 31.
 #include <algorithm>
 #include <cfloat>
 
@@ -209,11 +215,31 @@ struct TsepExParams {
     const int2* __restrict__ pairs;    // [P]
     const double* __restrict__ W2;
     ExParams ex;                       // outputs [B][P]; c unused
+    double* __restrict__ jac;          // [B][P][DIM][NC] (the envelope forms)
     int n_veh, P;
     double sign, offset;
 };
 
-template <int NC, int DIM>
+// One item's envelope block at t (a lane's own item): the a side of obtg_temporal_sep_jac's conventions -- b's block is
+// the negation, an obstacle has no variable, a pair of two obstacles is all zeros.
+template <int NCMAX, int DIM>
+__device__ __forceinline__ void tsep_envelope_item(const TsepExParams& q, long item, int nc, double t)
+{
+    const int b = (int)(item / q.P), pr = (int)(item - (long)b * q.P);
+    const int2 ij = q.pairs[pr];
+    double* o = q.jac + (size_t)item * (DIM * nc);
+    if (ij.x >= q.n_veh) {
+        for (int e = 0; e < DIM * nc; ++e) o[e] = 0.0;
+        return;
+    }
+    const double* Yrow = q.Y + (size_t)b * q.n_veh * (DIM * nc);
+    const double* ya = Yrow + (size_t)ij.x * (DIM * nc);
+    const bool veh = ij.y < q.n_veh;
+    const double* yb = veh ? Yrow + (size_t)ij.y * (DIM * nc) : q.obs + (size_t)(ij.y - q.n_veh) * DIM;
+    envelope_block<NCMAX, DIM>(ya, yb, veh ? nc : 1, veh ? 1 : 0, nc, t, o);
+}
+
+template <int NC, int DIM, bool JAC>
 __global__ __launch_bounds__(kExWaves * kWave) void k_tsep_true_min(const TsepExParams q)
 {
     using S = NsShape<NC, DIM>;
@@ -257,6 +283,17 @@ __global__ __launch_bounds__(kExWaves * kWave) void k_tsep_true_min(const TsepEx
         if (lane == src) mine = o;
     }
     if (valid) ex_store(p, item, mine, false);
+    if (JAC && valid) tsep_envelope_item<NC, DIM>(q, item, NC, mine.t);
+}
+
+// the blocks alone, from Y and the t_star of an earlier launch: one item per lane, nc <= kEnvMaxNC at run time
+constexpr int kEnvMaxNC = 32;
+constexpr int kEnvThreads = 128;
+template <int DIM>
+__global__ __launch_bounds__(kEnvThreads) void k_tsep_envelope(const TsepExParams q, const int nc)
+{
+    const long item = (long)blockIdx.x * kEnvThreads + threadIdx.x;
+    if (item < q.ex.M) tsep_envelope_item<kEnvMaxNC, DIM>(q, item, nc, q.ex.t[item]);
 }
 
 // =====================================================================================
@@ -281,8 +318,9 @@ int launch_bern_extrema(obtg_ctx* c, const double* d_c, long M, int K, int want_
 }
 
 // OBTG_ERR_UNSUPPORTED: not a shape of the fast-kernel list (the caller goes through obtg_temporal_sep's rows)
+// d_jac != nullptr: the fused envelope form (obtg_temporal_sep_true_min_jac), the same search and one launch
 int launch_temporal_sep_true_min(obtg_ctx* c, const double* dY, int B, double max_sep, double eps_rel, int max_nodes,
-                                 double* d_out, double* d_t, int* d_status)
+                                 double* d_out, double* d_t, int* d_status, double* d_jac)
 {
     if (B <= 0 || c->n_pairs <= 0) return OBTG_OK;
     const int nc = c->deg + 1;
@@ -291,12 +329,12 @@ int launch_temporal_sep_true_min(obtg_ctx* c, const double* dY, int B, double ma
     if (rc) return rc;
     TsepExParams q{};
     q.Y = dY; q.obs = c->d_obs.as<double>(); q.pairs = c->d_pairs.as<int2>(); q.W2 = c->d_w2.as<double>();
-    q.n_veh = c->n_veh; q.P = c->n_pairs;
+    q.n_veh = c->n_veh; q.P = c->n_pairs; q.jac = d_jac;
     q.sign = 1.0; q.offset = 0.0 - square_as_python(max_sep);
     q.ex.val = d_out; q.ex.t = d_t; q.ex.status = d_status;
     q.ex.M = (long)B * c->n_pairs; q.ex.K = 2 * c->deg + 1; q.ex.max_nodes = max_nodes; q.ex.eps_rel = eps_rel; q.ex.eps_abs = 0.0;
     void (*kern)(const TsepExParams) = nullptr;
-#define OBTG_CASE(NC_, D_) if (nc == NC_ && c->dim == D_) kern = k_tsep_true_min<NC_, D_>;
+#define OBTG_CASE(NC_, D_) if (nc == NC_ && c->dim == D_) kern = d_jac ? k_tsep_true_min<NC_, D_, true> : k_tsep_true_min<NC_, D_, false>;
 #define OBTG_CASE_D(NC_) OBTG_CASE(NC_, 2) OBTG_CASE(NC_, 3)
     OBTG_NC_SEP(OBTG_CASE_D)
 #undef OBTG_CASE_D
@@ -306,6 +344,23 @@ int launch_temporal_sep_true_min(obtg_ctx* c, const double* dY, int B, double ma
     const long per_wg = kExWaves * kWave;
     ScopedKernelTimer t(c, OBTG_K_TEMPORAL_SEP);
     hipLaunchKernelGGL(kern, dim3((unsigned)((q.ex.M + per_wg - 1) / per_wg)), dim3(kExWaves * kWave), lds, c->stream, q);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
+// the blocks of the two-launch form: d_t holds the t_star of the value path
+int launch_temporal_sep_envelope(obtg_ctx* c, const double* dY, int B, const double* d_t, double* d_jac)
+{
+    if (B <= 0 || c->n_pairs <= 0) return OBTG_OK;
+    const int nc = c->deg + 1;
+    if (nc > kEnvMaxNC) return OBTG_ERR_UNSUPPORTED;
+    TsepExParams q{};
+    q.Y = dY; q.obs = c->d_obs.as<double>(); q.pairs = c->d_pairs.as<int2>(); q.jac = d_jac;
+    q.n_veh = c->n_veh; q.P = c->n_pairs;
+    q.ex.t = const_cast<double*>(d_t); q.ex.M = (long)B * c->n_pairs;
+    void (*kern)(const TsepExParams, int) = c->dim == 1 ? k_tsep_envelope<1> : c->dim == 2 ? k_tsep_envelope<2> : k_tsep_envelope<3>;
+    ScopedKernelTimer t(c, OBTG_K_TEMPORAL_SEP);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((q.ex.M + kEnvThreads - 1) / kEnvThreads)), dim3(kEnvThreads), 0, c->stream, q, nc);
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;
 }

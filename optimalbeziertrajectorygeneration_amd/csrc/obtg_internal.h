@@ -127,6 +127,7 @@ struct obtg_ctx {
     int n_poly = 0, n_poly_pts = 0, max_poly_K = 0;
     bool polys_planar = true;   // every registered polygon vertex has z == 0
     bool fd_dedup = false;      // reuse row 0's GJK results for bit-identical hull pairs
+    bool true_min_jac_fused = true;   // OBTG_TRUE_MIN_JAC_FUSED=0: obtg_temporal_sep_true_min_jac takes the two-launch form on every shape
     bool fd_view_structured = true;   // obtg_ctx_set_fd_view_structured: the one-call sweep of a view takes the structured step where it applies
     obtg::DevBuf d_hp_a, d_hp_b;  // hull pair list
     obtg::DevBuf d_vp_off, d_vp_idx;   // per vehicle: the positions of the hull pairs that contain it (CSR; structured FD step)
@@ -318,6 +319,8 @@ int launch_bern_extrema(obtg_ctx* c, const double* d_c, long M, int K, int want_
                         int kernel_id = OBTG_K_BERN);     // every output but d_val nullable
 // the fused form for the fast-kernel list's shapes; OBTG_ERR_UNSUPPORTED: go through obtg_temporal_sep's R = 0 rows
 int launch_temporal_sep_true_min(obtg_ctx* c, const double* dY, int B, double max_sep, double eps_rel, int max_nodes,
-                                 double* d_out, double* d_t, int* d_status);
+                                 double* d_out, double* d_t, int* d_status, double* d_jac = nullptr);   // d_jac: with the envelope blocks
+// the envelope blocks [B][P][dim][deg+1] from Y and the t_star of a value launch: any degree up to 31 (else OBTG_ERR_UNSUPPORTED)
+int launch_temporal_sep_envelope(obtg_ctx* c, const double* dY, int B, const double* d_t, double* d_jac);
 
 }  // namespace obtg

@@ -700,12 +700,21 @@ class BezOptimization(object):
         speeds) and shapes outside the specialised kernels take the batch path.
 
         method='exact': the analytic Jacobian (obtg_temporal_sep_jac, one launch at x; `structured` is ignored).  With
-        separationRows 'min' / 'active' its rows are those of the control points the value kernels select at x."""
+        separationRows 'min' / 'active' its rows are those of the control points the value kernels select at x.
+
+        method='envelope' (separationRows='true_min' only): the envelope derivative of the true per-pair minima -- the
+        derivative of each pair's polynomial at the minimiser the search returns (obtg_temporal_sep_true_min_jac, one call
+        at x with TRUE_MIN_EPS_REL; DESIGN.md 4.14 says what it is where minimisers tie)."""
+        if method == 'envelope':
+            if self.separationRows != 'true_min':
+                raise ValueError("temporalSeparationJacobian(method='envelope') needs separationRows='true_min', not {!r}"
+                                 .format(self.separationRows))
+            return self._temporal_sep_jac_envelope(x)
         _check_method(method)
         if method == 'exact':
             if self.separationRows == 'true_min':
                 raise ValueError("temporalSeparationJacobian(method='exact') is not available with separationRows='true_min' "
-                                 "(the envelope derivative is not built): use method='fd'")
+                                 "(the envelope derivative is not built under that name): use method='envelope' or method='fd'")
             return self._temporal_sep_jac_exact(x)
         if not structured or self.separationRows in ('active', 'true_min'):
             # 'active': the forward differences of the order statistics themselves -- what SciPy builds from n_x + 1 calls
@@ -857,6 +866,24 @@ class BezOptimization(object):
             blk = blk[np.arange(P)[:, None], idx]
         pa, pb = np.triu_indices(n_obj, 1)
         return self._scatter_exact(blk, (pa, pb), (1.0, -1.0))
+
+    def _temporal_sep_jac_envelope(self, x):
+        x = np.asarray(x, dtype=float)
+        with_obs = self.pointObstacles is not None
+        ctx = self._ctx(with_obs)
+        n_obj = ctx.n_veh + ctx.n_obs
+        if n_obj < 2:
+            return np.zeros((0, x.size))
+        r = ctx.temporal_sep_true_min_jac(self.reshapeVectors(x[None]), self.model['maxSep'], eps_rel=self.TRUE_MIN_EPS_REL)
+        bad = np.flatnonzero(r['status'].ravel() != _capi.MD_OK)
+        if bad.size:
+            bez._raise_md(int(r['status'].ravel()[bad[0]]), 'temporalSeparationJacobian(envelope)')
+        pa, pb = np.triu_indices(n_obj, 1)
+        return self._scatter_exact(r['jac'][0][:, None], (pa, pb), (1.0, -1.0))      # blocks of one row each
+
+    def trueMinSeparationJacobian(self, x):
+        """temporalSeparationJacobian(x, method='envelope')"""
+        return self.temporalSeparationJacobian(x, method='envelope')
 
     def _jac_vehicle_exact(self, x, family):
         x = np.asarray(x, dtype=float)

@@ -1418,7 +1418,7 @@ int launch_temporal_sep(obtg_ctx* c, const double* dY, int B, double max_sep, in
         // any-degree shapes: whole rows into a workspace, then the selection as a launch of its own
         const int L = 2 * c->deg + c->R + 1;
         const long items = (long)B * pair_count;
-        DevBuf& ws = c->ws_misc[7];
+        DevBuf& ws = c->ws_misc[WS_L_ROWS];
         if ((rc = ws.reserve(sizeof(double) * (size_t)items * L))) return rc;
         if ((rc = launch_temporal_sep(c, dY, B, max_sep, pair_begin, pair_count, false, ws.as<double>(), 0, nullptr))) return rc;
         hipLaunchKernelGGL(k_select_smallest, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, c->stream,
@@ -1998,21 +1998,22 @@ int launch_deriv_energy_obj(obtg_ctx* c, const double* dY, const double* d_tf, d
     if (B <= 0) return OBTG_OK;
     if (order < 1 || order > 4) return OBTG_ERR_ARG;
     const int rows = B * c->n_veh * c->dim, nc = c->deg + 1;
-    int rc = c->ws_misc[3].reserve(sizeof(double) * (size_t)rows * nc);
-    if (rc) return rc;
-    if ((rc = c->ws_misc[6].reserve(sizeof(double) * (size_t)rows * nc))) return rc;
-    if ((rc = c->ws_misc[4].reserve(sizeof(double) * (size_t)B * c->n_veh * (2 * c->deg + c->R + 1)))) return rc;
+    DevBuf &diff_a = c->ws_misc[WS_L_DIFF_A], &diff_b = c->ws_misc[WS_L_DIFF_B], &speed = c->ws_misc[WS_L_SPEED];
+    int rc;
+    if ((rc = diff_a.reserve(sizeof(double) * (size_t)rows * nc))) return rc;
+    if ((rc = diff_b.reserve(sizeof(double) * (size_t)rows * nc))) return rc;
+    if ((rc = speed.reserve(sizeof(double) * (size_t)B * c->n_veh * (2 * c->deg + c->R + 1)))) return rc;
     // the reference passes ONE model['tf'] (optimization.py:294-308; tf differs per row only in time-optimal
     // problems, whose objective is x[-1]): tf0 is that value, d_tf[B] holds it B times (checked by the caller)
     const double* src = dY;
-    double* bufs[2] = { c->ws_misc[3].as<double>(), c->ws_misc[6].as<double>() };
+    double* bufs[2] = { diff_a.as<double>(), diff_b.as<double>() };
     for (int k = 0; k < order - 1; ++k) {
         if ((rc = launch_bern_diff(c, src, rows, c->deg, tf0, bufs[k & 1]))) return rc;
         src = bufs[k & 1];
     }
-    if ((rc = launch_speed(c, src, d_tf, B, 0.0, 0, c->ws_misc[4].as<double>()))) return rc;
+    if ((rc = launch_speed(c, src, d_tf, B, 0.0, 0, speed.as<double>()))) return rc;
     ScopedKernelTimer t(c, OBTG_K_BERN);
-    hipLaunchKernelGGL(k_rowsum, dim3(B), dim3(kWave), 0, c->stream, c->ws_misc[4].as<double>(), d_out,
+    hipLaunchKernelGGL(k_rowsum, dim3(B), dim3(kWave), 0, c->stream, speed.as<double>(), d_out,
                        c->n_veh * (2 * c->deg + c->R + 1));
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;

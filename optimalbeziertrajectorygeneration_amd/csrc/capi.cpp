@@ -713,6 +713,42 @@ static int d2h(obtg_ctx* c, void* dst, const void* src, size_t bytes)
 
 static size_t ysize(const obtg_ctx* c) { return (size_t)c->n_veh * c->dim * (c->deg + 1); }
 
+// ------------------------------------------------------------------ the Bernstein-family host entry points
+// The one host path of obtg_temporal_sep[_min[_range]|_active|_fd|_jac|_true_min[_jac]], obtg_one_vs_many_min[_spans],
+// obtg_speed[_jac], obtg_ang_rate[_jac], obtg_bern_*, the objectives and their gradients.  Every one of them is: its argument
+// checks, a HostCall, its operands by name (in), its outputs by name (out), its launcher (run), the download -- optional
+// outputs first (fetch, skipped for a null pointer), the mandatory one last (finish: the call's ONE synchronise).  The slots
+// of ws_misc are obtg::WsSlot, and so is the rule for who may hold which.  The next entry point of the family starts as a
+// copy of obtg_speed (one output) or obtg_temporal_sep_true_min (optional outputs).
+// What the entry points do NOT share, because a caller or a timing could tell -- each keeps the answer it has given since it
+// was added:
+//  - zero copy (mapped host memory; the one-row SLSQP callbacks): Y, tf and the result of obtg_temporal_sep[_min[_range]],
+//    obtg_speed, obtg_ang_rate and the objectives, Y of _active and _true_min[_jac], `one` and the result of
+//    obtg_one_vs_many_min[_spans]; NOT the outputs of _active / _true_min*, and nothing of the _jac / _grad calls, of
+//    obtg_temporal_sep_fd, obtg_bern_extrema or obtg_bern_*;
+//  - an empty call with null pointers is OBTG_OK in obtg_one_vs_many_min[_spans] (B or K == 0), obtg_temporal_sep_fd (no
+//    perturbations, or fewer than two objects) and obtg_bern_extrema (M == 0); every other call rejects a null mandatory
+//    pointer first, and a context without pairs answers OBTG_OK only after that;
+//  - obtg_bern_extrema requires status, obtg_temporal_sep_true_min[_jac] take it as optional;
+//  - obtg_bern_normsq has no empty case (d >= 1); obtg_bern_restrict looks at every span before rows == 0 answers OBTG_OK;
+//  - obtg_ang_rate answers dim != 2 after its pointer checks, obtg_ang_rate_jac before them;
+//  - the _dev twins of the _jac calls answer OBTG_OK for B == 0 before the pointer checks, the host calls after them.
+extern "C++" {
+template <class T> static T* slot(obtg_ctx* c, WsSlot s) { return c->ws_misc[s].as<T>(); }
+
+// One host-buffer call: remembers the first failure, after which every later step is skipped.  Counts are elements of T.
+struct HostCall {
+    obtg_ctx* c;
+    int rc = OBTG_OK;
+    explicit HostCall(obtg_ctx* c_) : c(c_) { (void)hipSetDevice(c->device); }
+    template <class T> const T* in(DevBuf& b, const T* src, size_t count, bool zero_copy = false) { if (!rc) rc = h2d(c, b, src, sizeof(T) * count, zero_copy); return b.as<T>(); }
+    template <class T> T* out(DevBuf& b, size_t count, bool zero_copy = false) { if (!rc) rc = b.reserve(sizeof(T) * count, zero_copy); return b.as<T>(); }
+    template <class Launch> void run(Launch launch) { if (!rc) rc = launch(); }
+    template <class T> void fetch(T* dst, const T* src, size_t count) { if (!rc && dst) rc = d2h_copy(c, dst, src, sizeof(T) * count); }     // optional output
+    template <class T> int finish(T* dst, const T* src, size_t count) { return rc ? rc : d2h(c, dst, src, sizeof(T) * count); }             // the ONE synchronise
+};
+}  // extern "C++"
+
 static int host_sep(obtg_ctx* c, const double* Y, int B, double max_sep, bool min_only, double* out,
                     int pair_begin = 0, int pair_count = -1)
 {
@@ -720,32 +756,26 @@ static int host_sep(obtg_ctx* c, const double* Y, int B, double max_sep, bool mi
     if (pair_count < 0) pair_count = c->n_pairs - pair_begin;
     if (pair_begin < 0 || pair_begin + pair_count > c->n_pairs) return OBTG_ERR_ARG;
     if (B == 0 || pair_count == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
-    const size_t per = min_only ? (size_t)pair_count : (size_t)pair_count * (2 * c->deg + c->R + 1);
-    int rc = h2d(c, c->ws_in, Y, sizeof(double) * ysize(c) * B, true);
-    if (rc) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * per * B, true))) return rc;
-    rc = launch_temporal_sep(c, c->ws_in.as<double>(), B, max_sep, pair_begin, pair_count, min_only,
-                             c->ws_out.as<double>());
-    if (rc) return rc;
-    return d2h(c, out, c->ws_out.p, sizeof(double) * per * B);
+    const size_t n = (min_only ? (size_t)pair_count : (size_t)pair_count * (2 * c->deg + c->R + 1)) * B;
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    double* d_out = h.out<double>(c->ws_out, n, true);
+    h.run([&] { return launch_temporal_sep(c, dY, B, max_sep, pair_begin, pair_count, min_only, d_out); });
+    return h.finish(out, d_out, n);
 }
 
 int obtg_temporal_sep_active(obtg_ctx* c, const double* Y, int B, double max_sep, int k, double* out_val, int* out_idx)
 {
     if (!check_ctx(c) || !Y || !out_val || B < 0 || k < 1 || k > 4 || k > 2 * c->deg + c->R + 1) return OBTG_ERR_ARG;
     if (B == 0 || c->n_pairs == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
     const size_t n = (size_t)c->n_pairs * k * B;
-    int rc = h2d(c, c->ws_in, Y, sizeof(double) * ysize(c) * B, true);
-    if (rc) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * n))) return rc;
-    DevBuf& di = c->ws_misc[4];
-    if ((rc = di.reserve(sizeof(int) * n))) return rc;
-    rc = launch_temporal_sep(c, c->ws_in.as<double>(), B, max_sep, 0, c->n_pairs, true, c->ws_out.as<double>(), k, di.as<int>());
-    if (rc) return rc;
-    if (out_idx && (rc = d2h_copy(c, out_idx, di.p, sizeof(int) * n))) return rc;
-    return d2h(c, out_val, c->ws_out.p, sizeof(double) * n);
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    double* d_val = h.out<double>(c->ws_out, n);
+    int* d_idx = h.out<int>(c->ws_misc[WS_STATUS], n);
+    h.run([&] { return launch_temporal_sep(c, dY, B, max_sep, 0, c->n_pairs, true, d_val, k, d_idx); });
+    h.fetch(out_idx, d_idx, n);
+    return h.finish(out_val, d_val, n);
 }
 
 int obtg_temporal_sep_min_range(obtg_ctx* c, const double* Y, int B, double max_sep, int pair_begin,
@@ -755,41 +785,8 @@ int obtg_temporal_sep_min_range(obtg_ctx* c, const double* Y, int B, double max_
     return host_sep(c, Y, B, max_sep, true, out, pair_begin, pair_count);
 }
 
-int obtg_temporal_sep(obtg_ctx* c, const double* Y, int B, double max_sep, double* out)
-{
-    return host_sep(c, Y, B, max_sep, false, out);
-}
-
-int obtg_temporal_sep_min(obtg_ctx* c, const double* Y, int B, double max_sep, double* out)
-{
-    return host_sep(c, Y, B, max_sep, true, out);
-}
-
-// Examples/SequentialSwarm.py:43-70: one curve against K others, per-pair minimum of the elevated control points
-int obtg_one_vs_many_min_dev(obtg_ctx* c, const double* d_one, int B, const double* d_many, int K, double max_sep, double* d_out)
-{
-    if (!check_ctx(c) || B < 0 || K < 0) return OBTG_ERR_ARG;
-    if (B == 0 || K == 0) return OBTG_OK;
-    if (!d_one || !d_many || !d_out) return OBTG_ERR_ARG;
-    (void)hipSetDevice(c->device);
-    return launch_one_vs_many_min(c, d_one, B, d_many, K, max_sep, d_out);
-}
-
-int obtg_one_vs_many_min(obtg_ctx* c, const double* one, int B, const double* many, int K, double max_sep, double* out)
-{
-    if (!check_ctx(c) || B < 0 || K < 0) return OBTG_ERR_ARG;
-    if (B == 0 || K == 0) return OBTG_OK;
-    if (!one || !many || !out) return OBTG_ERR_ARG;
-    (void)hipSetDevice(c->device);
-    const size_t curve = sizeof(double) * (size_t)c->dim * (c->deg + 1);
-    int rc = h2d(c, c->ws_in, one, curve * B, true);
-    if (rc) return rc;
-    // the planned trajectories grow by one curve per vehicle: the staging buffer grows with them, nothing else does
-    if ((rc = h2d(c, c->ws_in2, many, curve * K))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * (size_t)B * K, true))) return rc;
-    if ((rc = launch_one_vs_many_min(c, c->ws_in.as<double>(), B, c->ws_in2.as<double>(), K, max_sep, c->ws_out.as<double>()))) return rc;
-    return d2h(c, out, c->ws_out.p, sizeof(double) * (size_t)B * K);
-}
+int obtg_temporal_sep(obtg_ctx* c, const double* Y, int B, double max_sep, double* out) { return host_sep(c, Y, B, max_sep, false, out); }
+int obtg_temporal_sep_min(obtg_ctx* c, const double* Y, int B, double max_sep, double* out) { return host_sep(c, Y, B, max_sep, true, out); }
 
 // Bezier.sub on curves with different [t0, tf] (bezier.py:347-374 -> _temporalAlignment 903-941), then the same minimum
 static bool spans_ok(const double* s, int n)
@@ -798,82 +795,100 @@ static bool spans_ok(const double* s, int n)
     return true;
 }
 
-// the spans of both sides -> ws_misc[0], ws_misc[1]
-static int stage_spans(obtg_ctx* c, const double* one_span, int B, const double* many_span, int K)
+// A check shared by a host entry point and its _dev twin answers an OBTG_ERR_* code, OBTG_OK ("go on") or kNothingToDo: the
+// call is valid and empty, the entry point returns done(that) = OBTG_OK
+constexpr int kNothingToDo = 1;
+static int done(int chk) { return chk == kNothingToDo ? OBTG_OK : chk; }
+
+// Examples/SequentialSwarm.py:43-70: one curve against K others, per-pair minimum of the elevated control points
+static int one_vs_many_args(const obtg_ctx* c, const double* one, int B, const double* many, int K, const double* out,
+                            bool with_spans = false, const double* one_span = nullptr, const double* many_span = nullptr)
 {
-    int rc = h2d(c, c->ws_misc[0], one_span, sizeof(double) * 2 * (size_t)B);
-    if (rc) return rc;
-    return h2d(c, c->ws_misc[1], many_span, sizeof(double) * 2 * (size_t)K);
+    if (!check_ctx(c) || B < 0 || K < 0) return OBTG_ERR_ARG;
+    if (B == 0 || K == 0) return kNothingToDo;
+    if (!one || !many || !out) return OBTG_ERR_ARG;
+    if (with_spans && (!one_span || !many_span || !spans_ok(one_span, B) || !spans_ok(many_span, K))) return OBTG_ERR_ARG;
+    return OBTG_OK;
+}
+
+int obtg_one_vs_many_min_dev(obtg_ctx* c, const double* d_one, int B, const double* d_many, int K, double max_sep, double* d_out)
+{
+    if (int chk = one_vs_many_args(c, d_one, B, d_many, K, d_out)) return done(chk);
+    (void)hipSetDevice(c->device);
+    return launch_one_vs_many_min(c, d_one, B, d_many, K, max_sep, d_out);
+}
+
+int obtg_one_vs_many_min(obtg_ctx* c, const double* one, int B, const double* many, int K, double max_sep, double* out)
+{
+    if (int chk = one_vs_many_args(c, one, B, many, K, out)) return done(chk);
+    const size_t curve = (size_t)c->dim * (c->deg + 1), n = (size_t)B * K;
+    HostCall h(c);
+    const double* d_one = h.in(c->ws_in, one, curve * B, true);
+    // the planned trajectories grow by one curve per vehicle: the staging buffer grows with them, nothing else does
+    const double* d_many = h.in(c->ws_in2, many, curve * K);
+    double* d_out = h.out<double>(c->ws_out, n, true);
+    h.run([&] { return launch_one_vs_many_min(c, d_one, B, d_many, K, max_sep, d_out); });
+    return h.finish(out, d_out, n);
 }
 
 int obtg_one_vs_many_min_spans_dev(obtg_ctx* c, const double* d_one, const double* one_span, int B, const double* d_many,
                                    const double* many_span, int K, double max_sep, double no_overlap, double* d_out)
 {
-    if (!check_ctx(c) || B < 0 || K < 0) return OBTG_ERR_ARG;
-    if (B == 0 || K == 0) return OBTG_OK;
-    if (!d_one || !d_many || !d_out || !one_span || !many_span) return OBTG_ERR_ARG;
-    if (!spans_ok(one_span, B) || !spans_ok(many_span, K)) return OBTG_ERR_ARG;
-    (void)hipSetDevice(c->device);
-    int rc = stage_spans(c, one_span, B, many_span, K);
-    if (rc) return rc;
+    if (int chk = one_vs_many_args(c, d_one, B, d_many, K, d_out, true, one_span, many_span)) return done(chk);
+    HostCall h(c);
+    const double* d_one_span = h.in(c->ws_misc[WS_ARG_A], one_span, 2 * (size_t)B);
+    const double* d_many_span = h.in(c->ws_misc[WS_ARG_B], many_span, 2 * (size_t)K);
+    if (h.rc) return h.rc;
     OBTG_HIP(c, hipStreamSynchronize(c->stream));       // the caller's span arrays are free on return; the launch is asynchronous
-    return launch_one_vs_many_min_spans(c, d_one, c->ws_misc[0].as<double>(), B, d_many, c->ws_misc[1].as<double>(), K, max_sep,
-                                        no_overlap, d_out);
+    return launch_one_vs_many_min_spans(c, d_one, d_one_span, B, d_many, d_many_span, K, max_sep, no_overlap, d_out);
 }
 
 int obtg_one_vs_many_min_spans(obtg_ctx* c, const double* one, const double* one_span, int B, const double* many,
                                const double* many_span, int K, double max_sep, double no_overlap, double* out)
 {
-    if (!check_ctx(c) || B < 0 || K < 0) return OBTG_ERR_ARG;
-    if (B == 0 || K == 0) return OBTG_OK;
-    if (!one || !many || !out || !one_span || !many_span) return OBTG_ERR_ARG;
-    if (!spans_ok(one_span, B) || !spans_ok(many_span, K)) return OBTG_ERR_ARG;
-    (void)hipSetDevice(c->device);
-    const size_t curve = sizeof(double) * (size_t)c->dim * (c->deg + 1);
-    int rc = h2d(c, c->ws_in, one, curve * B, true);
-    if (rc) return rc;
-    if ((rc = h2d(c, c->ws_in2, many, curve * K))) return rc;
-    if ((rc = stage_spans(c, one_span, B, many_span, K))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * (size_t)B * K, true))) return rc;
-    if ((rc = launch_one_vs_many_min_spans(c, c->ws_in.as<double>(), c->ws_misc[0].as<double>(), B, c->ws_in2.as<double>(),
-                                           c->ws_misc[1].as<double>(), K, max_sep, no_overlap, c->ws_out.as<double>()))) return rc;
-    return d2h(c, out, c->ws_out.p, sizeof(double) * (size_t)B * K);
+    if (int chk = one_vs_many_args(c, one, B, many, K, out, true, one_span, many_span)) return done(chk);
+    const size_t curve = (size_t)c->dim * (c->deg + 1), n = (size_t)B * K;
+    HostCall h(c);
+    const double* d_one = h.in(c->ws_in, one, curve * B, true);
+    const double* d_many = h.in(c->ws_in2, many, curve * K);
+    const double* d_one_span = h.in(c->ws_misc[WS_ARG_A], one_span, 2 * (size_t)B);
+    const double* d_many_span = h.in(c->ws_misc[WS_ARG_B], many_span, 2 * (size_t)K);
+    double* d_out = h.out<double>(c->ws_out, n, true);
+    h.run([&] { return launch_one_vs_many_min_spans(c, d_one, d_one_span, B, d_many, d_many_span, K, max_sep, no_overlap, d_out); });
+    return h.finish(out, d_out, n);
 }
 
-static int check_perts(const obtg_ctx* c, int n_pert, const int* prow, const int* pcol)
+// host_arrays: the perturbation lists are host memory, so their entries can be checked too
+static int temporal_sep_fd_args(const obtg_ctx* c, const double* Y0, int n_pert, const int* pert_row, const int* pert_col,
+                                const double* pert_val, const double* out_blk, bool host_arrays)
 {
-    for (int t = 0; t < n_pert; ++t)
-        if (prow[t] < 0 || prow[t] >= c->n_veh * c->dim || pcol[t] < 0 || pcol[t] > c->deg) return OBTG_ERR_ARG;
+    if (!check_ctx(c) || n_pert < 0) return OBTG_ERR_ARG;
+    if (n_pert == 0 || c->n_obj < 2) return kNothingToDo;
+    if (!Y0 || !pert_row || !pert_col || !pert_val || !out_blk) return OBTG_ERR_ARG;
+    for (int t = 0; host_arrays && t < n_pert; ++t)
+        if (pert_row[t] < 0 || pert_row[t] >= c->n_veh * c->dim || pert_col[t] < 0 || pert_col[t] > c->deg) return OBTG_ERR_ARG;
     return OBTG_OK;
 }
 
 int obtg_temporal_sep_fd(obtg_ctx* c, const double* Y0, int n_pert, const int* pert_row, const int* pert_col,
                          const double* pert_val, double max_sep, double* out_blk)
 {
-    if (!check_ctx(c) || n_pert < 0) return OBTG_ERR_ARG;
-    if (n_pert == 0 || c->n_obj < 2) return OBTG_OK;
-    if (!Y0 || !pert_row || !pert_col || !pert_val || !out_blk) return OBTG_ERR_ARG;
-    if (int rc = check_perts(c, n_pert, pert_row, pert_col)) return rc;
-    (void)hipSetDevice(c->device);
-    const size_t per = (size_t)(c->n_obj - 1) * (2 * c->deg + c->R + 1);
-    int rc = h2d(c, c->ws_in, Y0, sizeof(double) * ysize(c));
-    if (rc) return rc;
-    if ((rc = h2d(c, c->ws_misc[0], pert_row, sizeof(int) * (size_t)n_pert))) return rc;
-    if ((rc = h2d(c, c->ws_misc[1], pert_col, sizeof(int) * (size_t)n_pert))) return rc;
-    if ((rc = h2d(c, c->ws_in2, pert_val, sizeof(double) * (size_t)n_pert))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * per * n_pert))) return rc;
-    rc = launch_temporal_sep_fd(c, c->ws_in.as<double>(), n_pert, c->ws_misc[0].as<int>(), c->ws_misc[1].as<int>(),
-                                c->ws_in2.as<double>(), max_sep, c->ws_out.as<double>());
-    if (rc) return rc;
-    return d2h(c, out_blk, c->ws_out.p, sizeof(double) * per * n_pert);
+    if (int chk = temporal_sep_fd_args(c, Y0, n_pert, pert_row, pert_col, pert_val, out_blk, true)) return done(chk);
+    const size_t n = (size_t)(c->n_obj - 1) * (2 * c->deg + c->R + 1) * n_pert;
+    HostCall h(c);
+    const double* dY0 = h.in(c->ws_in, Y0, ysize(c));
+    const int* d_row = h.in(c->ws_misc[WS_ARG_A], pert_row, (size_t)n_pert);
+    const int* d_col = h.in(c->ws_misc[WS_ARG_B], pert_col, (size_t)n_pert);
+    const double* d_val = h.in(c->ws_in2, pert_val, (size_t)n_pert);
+    double* d_out = h.out<double>(c->ws_out, n);
+    h.run([&] { return launch_temporal_sep_fd(c, dY0, n_pert, d_row, d_col, d_val, max_sep, d_out); });
+    return h.finish(out_blk, d_out, n);
 }
 
 int obtg_temporal_sep_fd_dev(obtg_ctx* c, const double* dY0, int n_pert, const int* d_pert_row,
                              const int* d_pert_col, const double* d_pert_val, double max_sep, double* d_out_blk)
 {
-    if (!check_ctx(c) || n_pert < 0) return OBTG_ERR_ARG;
-    if (n_pert == 0 || c->n_obj < 2) return OBTG_OK;
-    if (!dY0 || !d_pert_row || !d_pert_col || !d_pert_val || !d_out_blk) return OBTG_ERR_ARG;
+    if (int chk = temporal_sep_fd_args(c, dY0, n_pert, d_pert_row, d_pert_col, d_pert_val, d_out_blk, false)) return done(chk);
     (void)hipSetDevice(c->device);
     return launch_temporal_sep_fd(c, dY0, n_pert, d_pert_row, d_pert_col, d_pert_val, max_sep, d_out_blk);
 }
@@ -882,15 +897,13 @@ int obtg_speed(obtg_ctx* c, const double* Y, const double* tf, int B, double bou
 {
     if (!check_ctx(c) || !Y || !tf || !out || B < 0) return OBTG_ERR_ARG;
     if (B == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
-    const size_t per = (size_t)obtg_len_speed(c);
-    int rc = h2d(c, c->ws_in, Y, sizeof(double) * ysize(c) * B, true);
-    if (rc) return rc;
-    if ((rc = h2d(c, c->ws_in2, tf, sizeof(double) * B, true))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * per * B, true))) return rc;
-    rc = launch_speed(c, c->ws_in.as<double>(), c->ws_in2.as<double>(), B, bound, is_max, c->ws_out.as<double>());
-    if (rc) return rc;
-    return d2h(c, out, c->ws_out.p, sizeof(double) * per * B);
+    const size_t n = (size_t)obtg_len_speed(c) * B;
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    const double* d_tf = h.in(c->ws_in2, tf, (size_t)B, true);
+    double* d_out = h.out<double>(c->ws_out, n, true);
+    h.run([&] { return launch_speed(c, dY, d_tf, B, bound, is_max, d_out); });
+    return h.finish(out, d_out, n);
 }
 
 int obtg_ang_rate(obtg_ctx* c, const double* Y, const double* tf, int B, double max_rate, double* out)
@@ -898,15 +911,13 @@ int obtg_ang_rate(obtg_ctx* c, const double* Y, const double* tf, int B, double 
     if (!check_ctx(c) || !Y || !tf || !out || B < 0) return OBTG_ERR_ARG;
     if (c->dim != 2) return OBTG_ERR_ARG;
     if (B == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
-    const size_t per = (size_t)obtg_len_ang_rate(c);
-    int rc = h2d(c, c->ws_in, Y, sizeof(double) * ysize(c) * B, true);
-    if (rc) return rc;
-    if ((rc = h2d(c, c->ws_in2, tf, sizeof(double) * B, true))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * per * B, true))) return rc;
-    rc = launch_ang_rate(c, c->ws_in.as<double>(), c->ws_in2.as<double>(), B, max_rate, c->ws_out.as<double>());
-    if (rc) return rc;
-    return d2h(c, out, c->ws_out.p, sizeof(double) * per * B);
+    const size_t n = (size_t)obtg_len_ang_rate(c) * B;
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    const double* d_tf = h.in(c->ws_in2, tf, (size_t)B, true);
+    double* d_out = h.out<double>(c->ws_out, n, true);
+    h.run([&] { return launch_ang_rate(c, dY, d_tf, B, max_rate, d_out); });
+    return h.finish(out, d_out, n);
 }
 
 // ------------------------------------------------------------------ GJK
@@ -945,8 +956,6 @@ static int check_polys(const int* off, int n_poly, int n_pts)
 //  - obtg_gjk_pairs (as obtg_ctx_set_polygons) counts z == -0.0 as planar; the curve searches ask for +0, because a -0
 //    would show in a returned closest point.
 extern "C++" {
-template <class T> static T* slot(obtg_ctx* c, WsSlot s) { return c->ws_misc[s].as<T>(); }
-
 static int check_pairs(const int* a, int na, const int* b, int nb, int n_pairs)
 {
     for (int k = 0; k < n_pairs; ++k)
@@ -1476,12 +1485,19 @@ int obtg_coll_check2poly(obtg_ctx* c, const double* curves, int n_curves, int K,
 }
 
 // ------------------------------------------------------------------ true Bernstein extrema (extrema_kernels.hip)
-int obtg_bern_extrema_dev(obtg_ctx* c, const double* d_c, int M, int K, int want_max, double eps_rel, double eps_abs,
-                          int max_nodes, double* d_val, double* d_t_star, double* d_bound, int* d_nodes, int* d_status)
+static int bern_extrema_args(const obtg_ctx* c, const double* coef, int M, int K, double eps_rel, double eps_abs, int max_nodes,
+                             const double* val, bool need_status, const int* status)
 {
     if (!check_ctx(c) || M < 0 || !bern_extrema_supported(K) || max_nodes < 1) return OBTG_ERR_ARG;
     if (!(eps_rel >= 0.0) || !(eps_abs >= 0.0)) return OBTG_ERR_ARG;
-    if (M > 0 && (!d_c || !d_val)) return OBTG_ERR_ARG;
+    if (M > 0 && (!coef || !val || (need_status && !status))) return OBTG_ERR_ARG;
+    return OBTG_OK;
+}
+
+int obtg_bern_extrema_dev(obtg_ctx* c, const double* d_c, int M, int K, int want_max, double eps_rel, double eps_abs,
+                          int max_nodes, double* d_val, double* d_t_star, double* d_bound, int* d_nodes, int* d_status)
+{
+    if (int rc = bern_extrema_args(c, d_c, M, K, eps_rel, eps_abs, max_nodes, d_val, false, d_status)) return rc;
     (void)hipSetDevice(c->device);
     return launch_bern_extrema(c, d_c, M, K, want_max != 0, eps_rel, eps_abs, max_nodes, d_val, d_t_star, d_bound, d_nodes,
                                d_status);
@@ -1490,26 +1506,19 @@ int obtg_bern_extrema_dev(obtg_ctx* c, const double* d_c, int M, int K, int want
 int obtg_bern_extrema(obtg_ctx* c, const double* coef, int M, int K, int want_max, double eps_rel, double eps_abs,
                       int max_nodes, double* val, double* t_star, double* bound, int* nodes, int* status)
 {
-    if (!check_ctx(c) || M < 0 || !bern_extrema_supported(K) || max_nodes < 1) return OBTG_ERR_ARG;
-    if (!(eps_rel >= 0.0) || !(eps_abs >= 0.0)) return OBTG_ERR_ARG;
-    if (M > 0 && (!coef || !val || !status)) return OBTG_ERR_ARG;
+    if (int rc = bern_extrema_args(c, coef, M, K, eps_rel, eps_abs, max_nodes, val, true, status)) return rc;
     if (M == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
     const size_t m = (size_t)M;
-    int rc = h2d(c, c->ws_in, coef, sizeof(double) * m * K);
-    if (rc) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * 3 * m))) return rc;
-    DevBuf& di = c->ws_misc[3];
-    if ((rc = di.reserve(sizeof(int) * 2 * m))) return rc;
-    double* dv = c->ws_out.as<double>();
-    int* dn = di.as<int>();
-    if ((rc = launch_bern_extrema(c, c->ws_in.as<double>(), M, K, want_max != 0, eps_rel, eps_abs, max_nodes, dv, dv + m, dv + 2 * m,
-                                  dn, dn + m))) return rc;
-    if (t_star && (rc = d2h_copy(c, t_star, dv + m, sizeof(double) * m))) return rc;
-    if (bound && (rc = d2h_copy(c, bound, dv + 2 * m, sizeof(double) * m))) return rc;
-    if (nodes && (rc = d2h_copy(c, nodes, dn, sizeof(int) * m))) return rc;
-    if ((rc = d2h_copy(c, status, dn + m, sizeof(int) * m))) return rc;
-    return d2h(c, val, dv, sizeof(double) * m);
+    HostCall h(c);
+    const double* d_c = h.in(c->ws_in, coef, m * K);
+    double* dv = h.out<double>(c->ws_out, 3 * m);         // val | t_star | bound
+    int* dn = h.out<int>(c->ws_misc[WS_INFO], 2 * m);      // nodes | status
+    h.run([&] { return launch_bern_extrema(c, d_c, M, K, want_max != 0, eps_rel, eps_abs, max_nodes, dv, dv + m, dv + 2 * m, dn, dn + m); });
+    h.fetch(t_star, dv + m, m);
+    h.fetch(bound, dv + 2 * m, m);
+    h.fetch(nodes, dn, m);
+    h.fetch(status, dn + m, m);
+    return h.finish(val, dv, m);
 }
 
 // the fused kernel where the shape has one; else obtg_temporal_sep's rows at R = 0 into a workspace and obtg_bern_extrema on them
@@ -1521,7 +1530,7 @@ static int true_min_launch(obtg_ctx* c, const double* dY, int B, double max_sep,
     const int K = 2 * c->deg + 1;
     if (!bern_extrema_supported(K)) return OBTG_ERR_UNSUPPORTED;
     const long items = (long)B * c->n_pairs;
-    DevBuf& ws = c->ws_misc[7];
+    DevBuf& ws = c->ws_misc[WS_L_ROWS];
     if ((rc = ws.reserve(sizeof(double) * (size_t)items * K))) return rc;
     // DEG_ELEV does not enter: the any-degree kernel with R = 0 in its parameters, the context as it is
     if ((rc = launch_temporal_sep_rows_r0_generic(c, dY, B, max_sep, ws.as<double>()))) return rc;
@@ -1529,10 +1538,16 @@ static int true_min_launch(obtg_ctx* c, const double* dY, int B, double max_sep,
                                OBTG_K_TEMPORAL_SEP);
 }
 
+// what obtg_temporal_sep_true_min[_jac] and their _dev twins check alike (the host calls: Y too; the _jac calls: jac too)
+static bool true_min_args_ok(const obtg_ctx* c, const double* out, int B, int max_nodes, double eps_rel)
+{
+    return check_ctx(c) && out && B >= 0 && max_nodes >= 1 && eps_rel >= 0.0;
+}
+
 int obtg_temporal_sep_true_min_dev(obtg_ctx* c, const double* dY, int B, double max_sep, double eps_rel, int max_nodes,
                                    double* d_out, double* d_t_star, int* d_status)
 {
-    if (!check_ctx(c) || !d_out || B < 0 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
+    if (!true_min_args_ok(c, d_out, B, max_nodes, eps_rel)) return OBTG_ERR_ARG;
     (void)hipSetDevice(c->device);
     return with_batch(c, dY, B, false, [&](const double* src) {
         return true_min_launch(c, src, B, max_sep, eps_rel, max_nodes, d_out, d_t_star, d_status); });
@@ -1541,20 +1556,17 @@ int obtg_temporal_sep_true_min_dev(obtg_ctx* c, const double* dY, int B, double 
 int obtg_temporal_sep_true_min(obtg_ctx* c, const double* Y, int B, double max_sep, double eps_rel, int max_nodes,
                                double* out, double* t_star, int* status)
 {
-    if (!check_ctx(c) || !Y || !out || B < 0 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
+    if (!true_min_args_ok(c, out, B, max_nodes, eps_rel) || !Y) return OBTG_ERR_ARG;
     if (B == 0 || c->n_pairs == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
     const size_t n = (size_t)B * c->n_pairs;
-    int rc = h2d(c, c->ws_in, Y, sizeof(double) * ysize(c) * B, true);
-    if (rc) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * 2 * n))) return rc;
-    DevBuf& di = c->ws_misc[4];
-    if ((rc = di.reserve(sizeof(int) * n))) return rc;
-    double* dv = c->ws_out.as<double>();
-    if ((rc = true_min_launch(c, c->ws_in.as<double>(), B, max_sep, eps_rel, max_nodes, dv, dv + n, di.as<int>()))) return rc;
-    if (t_star && (rc = d2h_copy(c, t_star, dv + n, sizeof(double) * n))) return rc;
-    if (status && (rc = d2h_copy(c, status, di.p, sizeof(int) * n))) return rc;
-    return d2h(c, out, dv, sizeof(double) * n);
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    double* dv = h.out<double>(c->ws_out, 2 * n);           // val | t_star
+    int* ds = h.out<int>(c->ws_misc[WS_STATUS], n);
+    h.run([&] { return true_min_launch(c, dY, B, max_sep, eps_rel, max_nodes, dv, dv + n, ds); });
+    h.fetch(t_star, dv + n, n);
+    h.fetch(status, ds, n);
+    return h.finish(out, dv, n);
 }
 
 // values, t_star, status as true_min_launch gives them, and the envelope blocks: in the same launch where the shape has a
@@ -1567,7 +1579,7 @@ static int true_min_jac_launch(obtg_ctx* c, const double* dY, int B, double max_
     if (c->true_min_jac_fused) rc = launch_temporal_sep_true_min(c, dY, B, max_sep, eps_rel, max_nodes, d_out, d_t, d_status, d_jac);
     if (rc != OBTG_ERR_UNSUPPORTED) return rc;
     if (!d_t) {
-        DevBuf& wt = c->ws_misc[6];
+        DevBuf& wt = c->ws_misc[WS_L_TSTAR];
         if ((rc = wt.reserve(sizeof(double) * (size_t)B * c->n_pairs))) return rc;
         d_t = wt.as<double>();
     }
@@ -1578,7 +1590,7 @@ static int true_min_jac_launch(obtg_ctx* c, const double* dY, int B, double max_
 int obtg_temporal_sep_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, double max_sep, double eps_rel, int max_nodes,
                                        double* d_out, double* d_t_star, int* d_status, double* d_jac)
 {
-    if (!check_ctx(c) || !d_out || !d_jac || B < 0 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
+    if (!true_min_args_ok(c, d_out, B, max_nodes, eps_rel) || !d_jac) return OBTG_ERR_ARG;
     (void)hipSetDevice(c->device);
     return with_batch(c, dY, B, false, [&](const double* src) {
         return true_min_jac_launch(c, src, B, max_sep, eps_rel, max_nodes, d_out, d_t_star, d_status, d_jac); });
@@ -1587,22 +1599,18 @@ int obtg_temporal_sep_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, dou
 int obtg_temporal_sep_true_min_jac(obtg_ctx* c, const double* Y, int B, double max_sep, double eps_rel, int max_nodes,
                                    double* out, double* t_star, int* status, double* jac)
 {
-    if (!check_ctx(c) || !Y || !out || !jac || B < 0 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
+    if (!true_min_args_ok(c, out, B, max_nodes, eps_rel) || !Y || !jac) return OBTG_ERR_ARG;
     if (B == 0 || c->n_pairs == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
     const size_t n = (size_t)B * c->n_pairs, nj = n * c->dim * (c->deg + 1);
-    int rc = h2d(c, c->ws_in, Y, sizeof(double) * ysize(c) * B, true);
-    if (rc) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * (2 * n + nj)))) return rc;
-    DevBuf& di = c->ws_misc[4];
-    if ((rc = di.reserve(sizeof(int) * n))) return rc;
-    double* dv = c->ws_out.as<double>();
-    if ((rc = true_min_jac_launch(c, c->ws_in.as<double>(), B, max_sep, eps_rel, max_nodes, dv, dv + n, di.as<int>(), dv + 2 * n)))
-        return rc;
-    if (t_star && (rc = d2h_copy(c, t_star, dv + n, sizeof(double) * n))) return rc;
-    if (status && (rc = d2h_copy(c, status, di.p, sizeof(int) * n))) return rc;
-    if ((rc = d2h_copy(c, jac, dv + 2 * n, sizeof(double) * nj))) return rc;
-    return d2h(c, out, dv, sizeof(double) * n);
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    double* dv = h.out<double>(c->ws_out, 2 * n + nj);      // val | t_star | jac
+    int* ds = h.out<int>(c->ws_misc[WS_STATUS], n);
+    h.run([&] { return true_min_jac_launch(c, dY, B, max_sep, eps_rel, max_nodes, dv, dv + n, ds, dv + 2 * n); });
+    h.fetch(t_star, dv + n, n);
+    h.fetch(status, ds, n);
+    h.fetch(jac, dv + 2 * n, nj);
+    return h.finish(out, dv, n);
 }
 
 // ------------------------------------------------------------------ single-curve algebra
@@ -1610,39 +1618,37 @@ int obtg_bern_elev(obtg_ctx* c, const double* in, int rows, int n, int R, double
 {
     if (!check_ctx(c) || !in || !out || rows < 0 || n < 0 || R < 0) return OBTG_ERR_ARG;
     if (rows == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
-    int rc = h2d(c, c->ws_in, in, sizeof(double) * (size_t)rows * (n + 1));
-    if (rc) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * (size_t)rows * (n + R + 1)))) return rc;
-    if ((rc = launch_bern_elev(c, c->ws_in.as<double>(), rows, n, R, c->ws_out.as<double>()))) return rc;
-    return d2h(c, out, c->ws_out.p, sizeof(double) * (size_t)rows * (n + R + 1));
+    const size_t len = (size_t)rows * (n + R + 1);
+    HostCall h(c);
+    const double* d_in = h.in(c->ws_in, in, (size_t)rows * (n + 1));
+    double* d_out = h.out<double>(c->ws_out, len);
+    h.run([&] { return launch_bern_elev(c, d_in, rows, n, R, d_out); });
+    return h.finish(out, d_out, len);
 }
 
 int obtg_bern_diff(obtg_ctx* c, const double* in, int rows, int n, double T, double* out)
 {
     if (!check_ctx(c) || !in || !out || rows < 0 || n < 1) return OBTG_ERR_ARG;
     if (rows == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
-    int rc = h2d(c, c->ws_in, in, sizeof(double) * (size_t)rows * (n + 1));
-    if (rc) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * (size_t)rows * (n + 1)))) return rc;
-    if ((rc = launch_bern_diff(c, c->ws_in.as<double>(), rows, n, T, c->ws_out.as<double>()))) return rc;
-    return d2h(c, out, c->ws_out.p, sizeof(double) * (size_t)rows * (n + 1));
+    const size_t len = (size_t)rows * (n + 1);
+    HostCall h(c);
+    const double* d_in = h.in(c->ws_in, in, len);
+    double* d_out = h.out<double>(c->ws_out, len);
+    h.run([&] { return launch_bern_diff(c, d_in, rows, n, T, d_out); });
+    return h.finish(out, d_out, len);
 }
 
 int obtg_bern_split(obtg_ctx* c, const double* in, int rows, int n, double z, double* left, double* right)
 {
     if (!check_ctx(c) || !in || !left || !right || rows < 0 || n < 0) return OBTG_ERR_ARG;
     if (rows == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
     const size_t len = (size_t)rows * (n + 1);
-    int rc = h2d(c, c->ws_in, in, sizeof(double) * len);
-    if (rc) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * 2 * len))) return rc;
-    double* dl = c->ws_out.as<double>();
-    if ((rc = launch_bern_split(c, c->ws_in.as<double>(), rows, n, z, dl, dl + len))) return rc;
-    if ((rc = d2h_copy(c, left, dl, sizeof(double) * len))) return rc;
-    return d2h(c, right, dl + len, sizeof(double) * len);
+    HostCall h(c);
+    const double* d_in = h.in(c->ws_in, in, len);
+    double* dl = h.out<double>(c->ws_out, 2 * len);         // left | right
+    h.run([&] { return launch_bern_split(c, d_in, rows, n, z, dl, dl + len); });
+    h.fetch(left, dl, len);
+    return h.finish(right, dl + len, len);
 }
 
 int obtg_bern_restrict(obtg_ctx* c, const double* in, int rows, int n, const double* span, const double* target, double* out)
@@ -1651,55 +1657,51 @@ int obtg_bern_restrict(obtg_ctx* c, const double* in, int rows, int n, const dou
     for (int r = 0; r < rows; ++r)
         if (!(span[2 * r] <= target[2 * r] && target[2 * r] < target[2 * r + 1] && target[2 * r + 1] <= span[2 * r + 1])) return OBTG_ERR_ARG;
     if (rows == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
     const size_t len = (size_t)rows * (n + 1);
-    int rc = h2d(c, c->ws_in, in, sizeof(double) * len);
-    if (rc) return rc;
-    if ((rc = h2d(c, c->ws_misc[0], span, sizeof(double) * 2 * (size_t)rows))) return rc;
-    if ((rc = h2d(c, c->ws_misc[1], target, sizeof(double) * 2 * (size_t)rows))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * len))) return rc;
-    if ((rc = launch_bern_restrict(c, c->ws_in.as<double>(), rows, n, c->ws_misc[0].as<double>(), c->ws_misc[1].as<double>(),
-                                   c->ws_out.as<double>()))) return rc;
-    return d2h(c, out, c->ws_out.p, sizeof(double) * len);
+    HostCall h(c);
+    const double* d_in = h.in(c->ws_in, in, len);
+    const double* d_span = h.in(c->ws_misc[WS_ARG_A], span, 2 * (size_t)rows);
+    const double* d_target = h.in(c->ws_misc[WS_ARG_B], target, 2 * (size_t)rows);
+    double* d_out = h.out<double>(c->ws_out, len);
+    h.run([&] { return launch_bern_restrict(c, d_in, rows, n, d_span, d_target, d_out); });
+    return h.finish(out, d_out, len);
 }
 
 int obtg_bern_eval(obtg_ctx* c, const double* cpts, int rows, int n, const double* tau, int n_tau, double t0, double tf, double* out)
 {
     if (!check_ctx(c) || !cpts || !tau || !out || rows < 0 || n < 0 || n_tau < 0) return OBTG_ERR_ARG;
     if (rows == 0 || n_tau == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
-    int rc = h2d(c, c->ws_in, cpts, sizeof(double) * (size_t)rows * (n + 1));
-    if (rc) return rc;
-    if ((rc = h2d(c, c->ws_in2, tau, sizeof(double) * (size_t)n_tau))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * (size_t)rows * n_tau))) return rc;
-    if ((rc = launch_bern_eval(c, c->ws_in.as<double>(), rows, n, c->ws_in2.as<double>(), n_tau, t0, tf, c->ws_out.as<double>())))
-        return rc;
-    return d2h(c, out, c->ws_out.p, sizeof(double) * (size_t)rows * n_tau);
+    const size_t len = (size_t)rows * n_tau;
+    HostCall h(c);
+    const double* d_cpts = h.in(c->ws_in, cpts, (size_t)rows * (n + 1));
+    const double* d_tau = h.in(c->ws_in2, tau, (size_t)n_tau);
+    double* d_out = h.out<double>(c->ws_out, len);
+    h.run([&] { return launch_bern_eval(c, d_cpts, rows, n, d_tau, n_tau, t0, tf, d_out); });
+    return h.finish(out, d_out, len);
 }
 
 int obtg_bern_mul(obtg_ctx* c, const double* a, const double* b, int rows, int m, int n, double* out)
 {
     if (!check_ctx(c) || !a || !b || !out || rows < 0 || m < 0 || n < 0) return OBTG_ERR_ARG;
     if (rows == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
-    int rc = h2d(c, c->ws_in, a, sizeof(double) * (size_t)rows * (m + 1));
-    if (rc) return rc;
-    if ((rc = h2d(c, c->ws_in2, b, sizeof(double) * (size_t)rows * (n + 1)))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * (size_t)rows * (m + n + 1)))) return rc;
-    if ((rc = launch_bern_mul(c, c->ws_in.as<double>(), c->ws_in2.as<double>(), rows, m, n, c->ws_out.as<double>())))
-        return rc;
-    return d2h(c, out, c->ws_out.p, sizeof(double) * (size_t)rows * (m + n + 1));
+    const size_t len = (size_t)rows * (m + n + 1);
+    HostCall h(c);
+    const double* d_a = h.in(c->ws_in, a, (size_t)rows * (m + 1));
+    const double* d_b = h.in(c->ws_in2, b, (size_t)rows * (n + 1));
+    double* d_out = h.out<double>(c->ws_out, len);
+    h.run([&] { return launch_bern_mul(c, d_a, d_b, rows, m, n, d_out); });
+    return h.finish(out, d_out, len);
 }
 
 int obtg_bern_normsq(obtg_ctx* c, const double* x, int d, int n, double* out)
 {
     if (!check_ctx(c) || !x || !out || d < 1 || n < 0) return OBTG_ERR_ARG;
-    (void)hipSetDevice(c->device);
-    int rc = h2d(c, c->ws_in, x, sizeof(double) * (size_t)d * (n + 1));
-    if (rc) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * (size_t)(2 * n + 1)))) return rc;
-    if ((rc = launch_bern_normsq(c, c->ws_in.as<double>(), d, n, c->ws_out.as<double>()))) return rc;
-    return d2h(c, out, c->ws_out.p, sizeof(double) * (size_t)(2 * n + 1));
+    const size_t len = (size_t)(2 * n + 1);
+    HostCall h(c);
+    const double* d_x = h.in(c->ws_in, x, (size_t)d * (n + 1));
+    double* d_out = h.out<double>(c->ws_out, len);
+    h.run([&] { return launch_bern_normsq(c, d_x, d, n, d_out); });
+    return h.finish(out, d_out, len);
 }
 
 // ------------------------------------------------------------------ objectives
@@ -1707,12 +1709,11 @@ int obtg_euclidean_obj(obtg_ctx* c, const double* Y, int B, double* out)
 {
     if (!check_ctx(c) || !Y || !out || B < 0) return OBTG_ERR_ARG;
     if (B == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
-    int rc = h2d(c, c->ws_in, Y, sizeof(double) * ysize(c) * B, true);
-    if (rc) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * B, true))) return rc;
-    if ((rc = launch_euclidean_obj(c, c->ws_in.as<double>(), B, c->ws_out.as<double>()))) return rc;
-    return d2h(c, out, c->ws_out.p, sizeof(double) * B);
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    double* d_out = h.out<double>(c->ws_out, (size_t)B, true);
+    h.run([&] { return launch_euclidean_obj(c, dY, B, d_out); });
+    return h.finish(out, d_out, (size_t)B);
 }
 
 static int host_deriv_obj(obtg_ctx* c, const double* Y, const double* tf, int B, int order, double* out)
@@ -1721,25 +1722,16 @@ static int host_deriv_obj(obtg_ctx* c, const double* Y, const double* tf, int B,
     if (B == 0) return OBTG_OK;
     // one final time for the whole batch, as the reference's objectives have (optimization.py:294-308)
     for (int b = 1; b < B; ++b) if (!(tf[b] == tf[0])) return OBTG_ERR_ARG;
-    (void)hipSetDevice(c->device);
-    int rc = h2d(c, c->ws_in, Y, sizeof(double) * ysize(c) * B, true);
-    if (rc) return rc;
-    if ((rc = h2d(c, c->ws_in2, tf, sizeof(double) * B, true))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * B, true))) return rc;
-    if ((rc = launch_deriv_energy_obj(c, c->ws_in.as<double>(), c->ws_in2.as<double>(), tf[0], B, order, c->ws_out.as<double>())))
-        return rc;
-    return d2h(c, out, c->ws_out.p, sizeof(double) * B);
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    const double* d_tf = h.in(c->ws_in2, tf, (size_t)B, true);
+    double* d_out = h.out<double>(c->ws_out, (size_t)B, true);
+    h.run([&] { return launch_deriv_energy_obj(c, dY, d_tf, tf[0], B, order, d_out); });
+    return h.finish(out, d_out, (size_t)B);
 }
 
-int obtg_accel_obj(obtg_ctx* c, const double* Y, const double* tf, int B, double* out)
-{
-    return host_deriv_obj(c, Y, tf, B, 2, out);
-}
-
-int obtg_jerk_obj(obtg_ctx* c, const double* Y, const double* tf, int B, double* out)
-{
-    return host_deriv_obj(c, Y, tf, B, 3, out);
-}
+int obtg_accel_obj(obtg_ctx* c, const double* Y, const double* tf, int B, double* out) { return host_deriv_obj(c, Y, tf, B, 2, out); }
+int obtg_jerk_obj(obtg_ctx* c, const double* Y, const double* tf, int B, double* out) { return host_deriv_obj(c, Y, tf, B, 3, out); }
 
 // ------------------------------------------------------------------ exact derivatives (jac_kernels.hip)
 int obtg_temporal_sep_jac_dev(obtg_ctx* c, const double* dY, int B, double* d_out)
@@ -1755,13 +1747,12 @@ int obtg_temporal_sep_jac(obtg_ctx* c, const double* Y, int B, double* out)
 {
     if (!check_ctx(c) || !Y || !out || B < 0) return OBTG_ERR_ARG;
     if (B == 0 || c->n_pairs == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
-    const size_t per = (size_t)c->n_pairs * (2 * c->deg + c->R + 1) * c->dim * (c->deg + 1);
-    int rc = h2d(c, c->ws_in, Y, sizeof(double) * ysize(c) * B);
-    if (rc) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * per * B))) return rc;
-    if ((rc = launch_temporal_sep_jac(c, c->ws_in.as<double>(), B, c->ws_out.as<double>()))) return rc;
-    return d2h(c, out, c->ws_out.p, sizeof(double) * per * B);
+    const size_t n = (size_t)c->n_pairs * (2 * c->deg + c->R + 1) * c->dim * (c->deg + 1) * B;
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B);
+    double* d_out = h.out<double>(c->ws_out, n);
+    h.run([&] { return launch_temporal_sep_jac(c, dY, B, d_out); });
+    return h.finish(out, d_out, n);
 }
 
 int obtg_speed_jac_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, int is_max, double* d_out, double* d_out_tf)
@@ -1773,42 +1764,34 @@ int obtg_speed_jac_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B,
     return launch_speed_jac(c, dY, d_tf, B, is_max, d_out, d_out_tf);
 }
 
-// the per-vehicle families' host entry points: Y, tf in; [B][N][rows][d][n+1] and (nullable) [B][N][rows] out
-static int host_vehicle_jac(obtg_ctx* c, const double* Y, const double* tf, int B, int rows, double* out, double* out_tf,
-                            int (*launch)(obtg_ctx*, const double*, const double*, int, double*, double*, int), int arg)
+// the host entry points with a d/dtf output: Y, tf in; out[B][per] and (nullable) out_tf[B][per_tf] back.
+// launch(dY, d_tf, d_out, d_out_tf), d_out_tf null with out_tf
+extern "C++" {
+template <class Launch>
+static int host_jac_tf(obtg_ctx* c, const double* Y, const double* tf, int B, size_t per, size_t per_tf, double* out, double* out_tf,
+                       Launch launch)
 {
-    if (!check_ctx(c) || !Y || !tf || !out || B < 0) return OBTG_ERR_ARG;
+    if (!Y || !tf || !out || B < 0) return OBTG_ERR_ARG;
     if (B == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
-    const size_t per = (size_t)c->n_veh * rows * c->dim * (c->deg + 1), per_tf = (size_t)c->n_veh * rows;
-    int rc = h2d(c, c->ws_in, Y, sizeof(double) * ysize(c) * B);
-    if (rc) return rc;
-    if ((rc = h2d(c, c->ws_in2, tf, sizeof(double) * B))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * per * B))) return rc;
-    double* d_tfo = nullptr;
-    if (out_tf) {
-        if ((rc = c->ws_misc[5].reserve(sizeof(double) * per_tf * B))) return rc;
-        d_tfo = c->ws_misc[5].as<double>();
-    }
-    if ((rc = launch(c, c->ws_in.as<double>(), c->ws_in2.as<double>(), B, c->ws_out.as<double>(), d_tfo, arg))) return rc;
-    if (out_tf && (rc = d2h_copy(c, out_tf, d_tfo, sizeof(double) * per_tf * B))) return rc;
-    return d2h(c, out, c->ws_out.p, sizeof(double) * per * B);
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B);
+    const double* d_tf = h.in(c->ws_in2, tf, (size_t)B);
+    double* d_out = h.out<double>(c->ws_out, per * B);
+    double* d_out_tf = out_tf ? h.out<double>(c->ws_misc[WS_OUT_TF], per_tf * B) : nullptr;
+    h.run([&] { return launch(dY, d_tf, d_out, d_out_tf); });
+    h.fetch(out_tf, d_out_tf, per_tf * B);
+    return h.finish(out, d_out, per * B);
 }
+}  // extern "C++"
 
-static int speed_jac_launch(obtg_ctx* c, const double* dY, const double* d_tf, int B, double* d_out, double* d_out_tf, int is_max)
-{
-    return launch_speed_jac(c, dY, d_tf, B, is_max, d_out, d_out_tf);
-}
-
-static int ang_rate_jac_launch(obtg_ctx* c, const double* dY, const double* d_tf, int B, double* d_out, double* d_out_tf, int)
-{
-    return launch_ang_rate_jac(c, dY, d_tf, B, d_out, d_out_tf);
-}
-
+// the per-vehicle families: [B][N][rows][d][n+1] and [B][N][rows]
 int obtg_speed_jac(obtg_ctx* c, const double* Y, const double* tf, int B, int is_max, double* out, double* out_tf)
 {
     if (!check_ctx(c)) return OBTG_ERR_ARG;
-    return host_vehicle_jac(c, Y, tf, B, 2 * c->deg + c->R + 1, out, out_tf, speed_jac_launch, is_max);
+    const size_t per_tf = (size_t)c->n_veh * (2 * c->deg + c->R + 1);
+    return host_jac_tf(c, Y, tf, B, per_tf * c->dim * (c->deg + 1), per_tf, out, out_tf,
+                       [&](const double* dY, const double* d_tf, double* d_out, double* d_out_tf) {
+                           return launch_speed_jac(c, dY, d_tf, B, is_max, d_out, d_out_tf); });
 }
 
 int obtg_ang_rate_jac_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double* d_out, double* d_out_tf)
@@ -1823,39 +1806,29 @@ int obtg_ang_rate_jac_dev(obtg_ctx* c, const double* dY, const double* d_tf, int
 int obtg_ang_rate_jac(obtg_ctx* c, const double* Y, const double* tf, int B, double* out, double* out_tf)
 {
     if (!check_ctx(c) || c->dim != 2) return OBTG_ERR_ARG;
-    return host_vehicle_jac(c, Y, tf, B, 4 * (c->deg + c->R) + 1, out, out_tf, ang_rate_jac_launch, 0);
+    const size_t per_tf = (size_t)c->n_veh * (4 * (c->deg + c->R) + 1);
+    return host_jac_tf(c, Y, tf, B, per_tf * c->dim * (c->deg + 1), per_tf, out, out_tf,
+                       [&](const double* dY, const double* d_tf, double* d_out, double* d_out_tf) {
+                           return launch_ang_rate_jac(c, dY, d_tf, B, d_out, d_out_tf); });
 }
 
 int obtg_euclidean_grad(obtg_ctx* c, const double* Y, int B, double* out)
 {
     if (!check_ctx(c) || !Y || !out || B < 0) return OBTG_ERR_ARG;
     if (B == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
-    int rc = h2d(c, c->ws_in, Y, sizeof(double) * ysize(c) * B);
-    if (rc) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * ysize(c) * B))) return rc;
-    if ((rc = launch_euclidean_grad(c, c->ws_in.as<double>(), B, c->ws_out.as<double>()))) return rc;
-    return d2h(c, out, c->ws_out.p, sizeof(double) * ysize(c) * B);
+    const size_t n = ysize(c) * B;
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, n);
+    double* d_out = h.out<double>(c->ws_out, n);
+    h.run([&] { return launch_euclidean_grad(c, dY, B, d_out); });
+    return h.finish(out, d_out, n);
 }
 
 int obtg_deriv_energy_grad(obtg_ctx* c, const double* Y, const double* tf, int B, int order, double* out, double* out_tf)
 {
-    if (!check_ctx(c) || !Y || !tf || !out || B < 0 || order < 1 || order > 4) return OBTG_ERR_ARG;
-    if (B == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
-    int rc = h2d(c, c->ws_in, Y, sizeof(double) * ysize(c) * B);
-    if (rc) return rc;
-    if ((rc = h2d(c, c->ws_in2, tf, sizeof(double) * B))) return rc;
-    if ((rc = c->ws_out.reserve(sizeof(double) * ysize(c) * B))) return rc;
-    double* d_tfo = nullptr;
-    if (out_tf) {
-        if ((rc = c->ws_misc[5].reserve(sizeof(double) * B))) return rc;
-        d_tfo = c->ws_misc[5].as<double>();
-    }
-    if ((rc = launch_deriv_energy_grad(c, c->ws_in.as<double>(), c->ws_in2.as<double>(), B, order, c->ws_out.as<double>(), d_tfo)))
-        return rc;
-    if (out_tf && (rc = d2h_copy(c, out_tf, d_tfo, sizeof(double) * B))) return rc;
-    return d2h(c, out, c->ws_out.p, sizeof(double) * ysize(c) * B);
+    if (!check_ctx(c) || order < 1 || order > 4) return OBTG_ERR_ARG;
+    return host_jac_tf(c, Y, tf, B, ysize(c), 1, out, out_tf, [&](const double* dY, const double* d_tf, double* d_out, double* d_out_tf) {
+        return launch_deriv_energy_grad(c, dY, d_tf, B, order, d_out, d_out_tf); });
 }
 
 // ------------------------------------------------------------------ instrumentation

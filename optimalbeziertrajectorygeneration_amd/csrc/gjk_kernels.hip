@@ -3260,11 +3260,11 @@ struct TimelineDump {
         static const int at = getenv("OBTG_TIMELINE_AT") ? atoi(getenv("OBTG_TIMELINE_AT")) : 20;
         static int count = 0;
         if (!(path && path[0] && ++count == at)) return;
-        if ((rc = c->ws_misc[6].reserve((size_t)grid * 4 * sizeof(unsigned long long)))) return;
-        if (hipMemsetAsync(c->ws_misc[6].p, 0, (size_t)grid * 4 * sizeof(unsigned long long), c->stream) != hipSuccess) {
+        if ((rc = c->ws_misc[WS_L_TIMELINE].reserve((size_t)grid * 4 * sizeof(unsigned long long)))) return;
+        if (hipMemsetAsync(c->ws_misc[WS_L_TIMELINE].p, 0, (size_t)grid * 4 * sizeof(unsigned long long), c->stream) != hipSuccess) {
             rc = OBTG_ERR_DEVICE; return;
         }
-        dev = c->ws_misc[6].as<unsigned long long>();
+        dev = c->ws_misc[WS_L_TIMELINE].as<unsigned long long>();
         slot = dev;
     }
     int finish(const char* header)
@@ -3435,9 +3435,9 @@ int launch_gjk_swarm(obtg_ctx* c, const double* dY, int B, int max_iter, int md_
             if (c->fd_dedup && B > 1 && kf) {
                 // Finite-difference de-duplication: row 0 in full, its results broadcast to every
                 // row, then one workgroup per row re-evaluates the pairs whose hulls differ from row 0.
-                int rc = c->ws_misc[7].reserve((size_t)B * c->n_veh);
+                int rc = c->ws_misc[WS_L_CHANGED].reserve((size_t)B * c->n_veh);
                 if (rc) return rc;
-                unsigned char* chg = c->ws_misc[7].as<unsigned char>();
+                unsigned char* chg = c->ws_misc[WS_L_CHANGED].as<unsigned char>();
                 const int tot = B * c->n_veh;
                 hipLaunchKernelGGL(k_changed_objects, dim3((tot + 255) / 256), dim3(256), 0, c->stream, dY, B,
                                    c->n_veh, c->dim * (c->deg + 1), chg);

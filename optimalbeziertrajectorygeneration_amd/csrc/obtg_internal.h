@@ -66,16 +66,39 @@ struct KernelStat {
     long long launches = 0;
 };
 
-// obtg_ctx::ws_misc: what the batched pair searches of capi.cpp (obtg_gjk_pairs .. obtg_coll_check2poly) keep in each slot.  Other
-// entry points borrow slots as plain scratch between those calls; slot 7 belongs to none of the searches.
+// obtg_ctx::ws_misc: every slot by name.  The first name of an index is what the batched pair searches of capi.cpp
+// (obtg_gjk_pairs .. obtg_coll_check2poly) keep there; the names under it are the same buffer as the other calls use it.  A
+// host call leaves the device idle, so nothing lives from one entry point to the next: only uses inside ONE call can collide.
+// The rule the code relies on: an entry point holds (from its reservation to its last download) only names WITHOUT the L; a
+// launcher takes only WS_L_* names, and only those whose index none of its calling entry points holds across the call.
+// The chains that are two deep, by index:
+//   obtg_temporal_sep_true_min[_jac] holds 4 (WS_STATUS)
+//     -> true_min_jac_launch takes 6 (WS_L_TSTAR: only for a _dev caller that wants no t_star; the host call's is in ws_out)
+//     -> true_min_launch     takes 7 (WS_L_ROWS) across launch_temporal_sep_rows_r0_generic and launch_bern_extrema, which take none
+//   obtg_temporal_sep_active holds 4 (WS_STATUS) -> launch_temporal_sep takes 7 (WS_L_ROWS: the any-degree selection)
+//   host_deriv_obj           holds none -> launch_deriv_energy_obj takes 3, 6, 4 (launch_bern_diff and launch_speed take none)
+//   obtg_bern_extrema        holds 3 (WS_INFO) -> launch_bern_extrema takes none
+//   obtg_gjk_swarm           holds 3 (WS_INFO) -> launch_gjk_swarm takes 7 (WS_L_CHANGED) and, under OBTG_TIMELINE, 6
 enum WsSlot {
     WS_POLY_OFF = 0,      // int[n_poly + 1]: polygon offsets
+    WS_ARG_A = 0,         //   first small operand beside ws_in / ws_in2: one_span (obtg_one_vs_many_min_spans[_dev]), pert_row (obtg_temporal_sep_fd), span (obtg_bern_restrict)
     WS_PAIR_A = 1,        // int[n_pairs]: first operand of every pair
+    WS_ARG_B = 1,         //   second small operand: many_span, pert_col, target (the same three calls)
     WS_PAIR_B = 2,        // int[n_pairs]: second operand
-    WS_INFO = 3,          // int[4 n_pairs]: counters and status of a curve search; flag | n_support or iters | status of a GJK call
+    WS_INFO = 3,          // int[4 n_pairs]: counters and status of a curve search; flag | n_support or iters | status of a GJK call; nodes | status of obtg_bern_extrema
+    WS_L_DIFF_A = 3,      //   launch_deriv_energy_obj: derivative passes, even ones
     WS_TRACE = 4,         // obtg_gjk_pairs: the support trace
+    WS_STATUS = 4,        //   int per value: the row indices of obtg_temporal_sep_active, the status of obtg_temporal_sep_true_min[_jac]
+    WS_L_SPEED = 4,       //   launch_deriv_energy_obj: the speed-style rows before their sum
     WS_STACK = 5,         // frame stacks (the frontiers of the robust searches)
+    WS_OUT_TF = 5,        //   the d/dtf output of obtg_speed_jac, obtg_ang_rate_jac, obtg_deriv_energy_grad
     WS_QUEUE = 6,         // work-queue counter, and behind it obtg_min_dist's pair order
+    WS_L_DIFF_B = 6,      //   launch_deriv_energy_obj: derivative passes, odd ones
+    WS_L_TSTAR = 6,       //   true_min_jac_launch: t_star between the value launch and the envelope launch, when the caller wants none
+    WS_L_TIMELINE = 6,    //   TimelineDump (gjk_kernels.hip; the one-launch sweeps, which no holder of WS_QUEUE calls)
+    WS_L_ROWS = 7,        // whole separation rows under a reduction: launch_temporal_sep's any-degree selection, true_min_launch's R = 0 rows
+    WS_L_CHANGED = 7,     //   launch_gjk_swarm's de-duplicated sweep: which objects differ from row 0
+    WS_COUNT = 8,
 };
 
 }  // namespace obtg
@@ -153,8 +176,8 @@ struct obtg_ctx {
     obtg::DevBuf ws_fd;                   // the view's batch, written only when some kernel needs it
 
     // scratch for host-buffer entry points
-    // (ws_misc: the batched pair searches name their slots, obtg::WsSlot above)
-    obtg::DevBuf ws_in, ws_in2, ws_out, ws_misc[8];
+    // (ws_misc: every slot has a name and an owner rule, obtg::WsSlot above)
+    obtg::DevBuf ws_in, ws_in2, ws_out, ws_misc[obtg::WS_COUNT];
     // obtg_min_dist: node counts of the previous evaluation of the SAME pair list (signature = count + hash of the lists):
     // the next evaluation hands its pairs to the worker waves in descending order of them (k_min_dist_wave)
     // (up to four lists, least recently used dropped: a driver alternates the constraint's list with its Jacobian's longer one)

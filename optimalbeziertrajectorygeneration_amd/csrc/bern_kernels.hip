@@ -1602,8 +1602,9 @@ int ang_rate_order_in_effect(obtg_ctx* c)
 bool dynamics_fd_on_the_fly(const obtg_ctx* c, bool want_ang) { return dyn_fast(c) || (want_ang && dyn_fast_elev(c)); }
 bool bernstein_fd_on_the_fly(const obtg_ctx* c) { return fast_shape(c); }
 
-// the other speed bound's rows of the same pass (obtg_ctx_set_second_speed_bound)
-static void second_speed_rows(const obtg_ctx* c, AngParams& p)
+// the other speed bound's rows of the same pass (obtg_ctx_set_second_speed_bound); the sweeps that carry dynamics groups
+// (gjk_kernels.hip) fill theirs here too
+void second_speed_rows(const obtg_ctx* c, AngParams& p)
 {
     if (!c->speed2.d_out || !p.out_speed) return;
     const double b2 = square_as_python(c->speed2.bound);

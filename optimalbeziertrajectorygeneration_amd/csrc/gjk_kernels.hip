@@ -3132,6 +3132,19 @@ int launch_gjk_pairs(obtg_ctx* c, const double* d_soa, const int* d_off, const i
     return OBTG_OK;
 }
 
+// a workgroup's dynamic LDS when per_cu of them share a CU's 160 KB (1040 bytes of static LDS per workgroup, rounded up)
+static constexpr size_t lds_share(int per_cu) { return (size_t)160 * 1024 / per_cu - 1280; }
+constexpr size_t kLdsDefaultMax = 48 * 1024;      // what a launch may ask for without the attribute below
+constexpr size_t kLdsLaunchMax = 64 * 1024;       // ... and with it, for the sweeps
+
+// a launch that asks for more dynamic LDS than the default limit raises the kernel's own first
+template <class K>
+static hipError_t allow_lds(K kern, size_t lds)
+{
+    if (lds <= kLdsDefaultMax) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
 // Tile-major chunking of the hull pair list for rows that do not fit LDS (MODE 2 above).
 // Pairs are bucketed by (a / 8, b / 64); a chunk is one bucket (<= 512 pairs, <= 72 objects when the
 // list is the usual all-pairs sweep; arbitrary lists are handled by cutting buckets at kMaxPairs /
@@ -3143,7 +3156,7 @@ int launch_gjk_pairs(obtg_ctx* c, const double* d_soa, const int* d_off, const i
 static int tile_height(int nc)
 {
     const int vpq = nc | 1, occ = 4;
-    const size_t budget = (size_t)160 * 1024 / occ - 1280;          // 1040 bytes of static LDS per workgroup
+    const size_t budget = lds_share(occ);
     int ta = 8;
     while (ta < 32 && planar_lds_bytes<2>(ta + 1 + 64, vpq, (ta + 1) * 64) <= budget) ++ta;
     if (const char* e = getenv("OBTG_TILE_A")) ta = std::max(4, std::min(32, atoi(e)));     // (experiments)
@@ -3308,6 +3321,82 @@ static int sweep_refill_min()
     return v;
 }
 
+// OBTG_FOLD_DYNAMICS=0: the pair sweeps leave the speed / angular-rate groups to a launch of their own (read once per process)
+static bool fold_dynamics_enabled()
+{
+    static const bool on = !(getenv("OBTG_FOLD_DYNAMICS") && getenv("OBTG_FOLD_DYNAMICS")[0] == '0');
+    return on;
+}
+
+// ---- what every swarm sweep's parameter block starts from.  The grid's shape (chunk, wgs_per_row, passes, vp) is the caller's.
+static void fill_swarm_params(const obtg_ctx* c, GjkSwarmParams& p, const double* dY, int max_iter, int md_cap, int* d_flag,
+                              double* d_p1, double* d_p2, double* d_dist, int* d_nsup, int* d_status)
+{
+    p.Y = dY; p.poly = c->d_poly_pts.as<double>(); p.poly_off = c->d_poly_off.as<int>();
+    p.pa = c->d_hp_a.as<int>(); p.pb = c->d_hp_b.as<int>();
+    p.n_veh = c->n_veh; p.dim = c->dim; p.nc = c->deg + 1; p.n_poly = c->n_poly;
+    p.n_poly_pts = c->n_poly_pts; p.n_pairs = c->n_hull_pairs;
+    p.max_iter = max_iter; p.md_cap = md_cap;
+    p.refill_min = sweep_refill_min(); p.hist_shift = sweep_hist_shift();
+    p.flag = d_flag; p.p1 = d_p1; p.p2 = d_p2; p.dist = d_dist; p.nsup = d_nsup; p.status = d_status;
+    if (c->fd.Y0) { p.Y = c->fd.Y0; p.fd = 1 + c->fd.row0; p.fd_fixed = c->fd.fixed; p.fd_h = c->fd.h; }      // a view: rows formed while staging
+}
+
+// the tiled kernels' chunk tables (build_tiles) and the grid they give: one workgroup per chunk
+static void fill_tile_tables(const obtg_ctx* c, GjkSwarmParams& q)
+{
+    q.chunk_off = c->d_tile_chunk_off.as<int>(); q.order = c->d_tile_order.as<int>();
+    q.pslots = c->d_tile_pslots.as<unsigned>(); q.cobj_off = c->d_tile_cobj_off.as<int>();
+    q.cobjs = c->d_tile_cobjs.as<int>(); q.max_objs = c->tile_max_objs;
+    q.chunk = c->tile_max_pairs; q.wgs_per_row = c->tile_n_chunks;
+}
+
+// trip-count history: this sweep orders its pairs by the counts the previous one left behind (same batch shape: row by
+// row; otherwise every row follows the old row 0) and leaves its own in the other buffer, which becomes the current one.
+// With the history off nothing is reserved and nothing flips.
+static int fill_history(obtg_ctx* c, GjkSwarmParams& p, int B)
+{
+    const size_t np = (size_t)c->n_hull_pairs;
+    p.B = B;
+    p.len_in = (c->gjk_history && c->gjk_len_rows > 0) ? c->d_gjk_len[c->gjk_len_cur].as<unsigned char>() : nullptr;
+    p.len_in_stride = c->gjk_len_rows == B ? (int)np : 0;
+    p.len_out = nullptr;
+    if (!c->gjk_history) return OBTG_OK;
+    obtg::DevBuf& hist_out = c->d_gjk_len[c->gjk_len_cur ^ 1];
+    if (int rc = hist_out.reserve((size_t)B * np)) return rc;
+    p.len_out = hist_out.as<unsigned char>();
+    c->gjk_len_cur ^= 1;
+    c->gjk_len_rows = B;
+    return OBTG_OK;
+}
+
+// the row's temporal-separation block as the planar pair sweeps write it (GjkSwarmParams::ts), point obstacles included
+static void fill_sep_block(const obtg_ctx* c, GjkSwarmParams& p, double max_sep, double* d_out_sep)
+{
+    p.ts.pairs = c->d_pairs.as<int2>(); p.ts.W2 = c->d_w2.as<double>(); p.ts.out = d_out_sep;
+    p.ts.n_pairs = c->n_pairs; p.ts.sign = 1.0; p.ts.offset = 0.0 - square_as_python(max_sep);
+    if (c->n_obs > 0) {            // point obstacles (optimization.py:86-98): constant curves behind the hull objects, for the separation rows only
+        p.obs = c->d_obs.as<double>(); p.n_obs = c->n_obs;
+        p.ts.n_veh = c->n_veh; p.ts.obs_shift = c->n_poly;
+    }
+}
+
+// the speed / angular-rate groups a planar sweep's grid carries (GjkSwarmParams::dyn): launch_dynamics' fast-path rows of
+// the same B rows, from the sweep's Y or view
+static void fill_dynamics(const obtg_ctx* c, GjkSwarmParams& p, const SweepFold& f, int B)
+{
+    AngParams& d = p.dyn;
+    d.Y = p.Y; d.tf = f.d_tf; d.out = f.d_out_ang; d.out_speed = f.d_out_speed;
+    d.n_veh = c->n_veh; d.total = B * c->n_veh;
+    d.w2 = square_as_python(f.max_rate);
+    const double b2 = square_as_python(f.speed_bound);
+    d.sp_sign = f.speed_is_max ? -1.0 : 1.0; d.sp_offset = f.speed_is_max ? b2 : -b2;
+    second_speed_rows(c, d);
+    d.W2n = c->d_ang_w2n.as<double>(); d.W22n = c->d_ang_w22n.as<double>(); d.Wn = c->d_ang_wn.as<double>();
+    d.fd = p.fd; d.fd_fixed = p.fd_fixed; d.fd_h = p.fd_h;
+}
+static bool wants_dynamics(const SweepFold* f) { return f && f->d_out_ang && f->d_out_speed && f->d_tf; }
+
 struct SweepShape {
     int wgs = 1, passes = 1, chunk = 0, per_cu = 1;
     size_t lds = 0;
@@ -3321,8 +3410,8 @@ static SweepShape sweep_shape(const obtg_ctx* c, int B, int nc, int waves_per_si
     int per_cu = nc <= 11 ? waves_per_simd : 1;
     size_t budget = 0;
     for (; per_cu >= 1; --per_cu) {
-        budget = (size_t)160 * 1024 / per_cu - 1280;
-        if (per_cu == 1) budget = 64 * 1024;                       // one workgroup per CU: the launch limit
+        budget = lds_share(per_cu);
+        if (per_cu == 1) budget = kLdsLaunchMax;                   // one workgroup per CU: the launch limit
         if (fixed + 14 * 256 <= budget) break;
     }
     if (per_cu < 1) per_cu = 1;
@@ -3358,11 +3447,9 @@ int launch_gjk_swarm(obtg_ctx* c, const double* dY, int B, int max_iter, int md_
                      double* d_p1, double* d_p2, double* d_dist, int* d_nsup, int* d_status, SweepFold* fold)
 {
     if (B <= 0 || c->n_hull_pairs <= 0) return OBTG_OK;
+    if (c->fd.Y0 && c->fd_dedup) return kNeedBatch;      // the de-duplication mask compares rows in memory
     GjkSwarmParams p{};
-    p.Y = dY; p.poly = c->d_poly_pts.as<double>(); p.poly_off = c->d_poly_off.as<int>();
-    p.pa = c->d_hp_a.as<int>(); p.pb = c->d_hp_b.as<int>();
-    p.n_veh = c->n_veh; p.dim = c->dim; p.nc = c->deg + 1; p.n_poly = c->n_poly;
-    p.n_poly_pts = c->n_poly_pts; p.n_pairs = c->n_hull_pairs;
+    fill_swarm_params(c, p, dY, max_iter, md_cap, d_flag, d_p1, d_p2, d_dist, d_nsup, d_status);
     const int vlen = c->dim * (c->deg + 1);
     p.vp = (vlen % 2 == 0) ? vlen + 1 : vlen;
     // workgroups per row.  Lanes refill from their workgroup's chunk, so a chunk must hold several
@@ -3372,13 +3459,6 @@ int launch_gjk_swarm(obtg_ctx* c, const double* dY, int B, int max_iter, int md_
     const int wgs = std::max(1, (c->n_hull_pairs + kSweepChunk - 1) / kSweepChunk);     // the general kernels' chunking
     p.chunk = (c->n_hull_pairs + wgs - 1) / wgs;
     p.wgs_per_row = (c->n_hull_pairs + p.chunk - 1) / p.chunk;
-    p.max_iter = max_iter; p.md_cap = md_cap;
-    p.refill_min = sweep_refill_min(); p.hist_shift = sweep_hist_shift();
-    p.flag = d_flag; p.p1 = d_p1; p.p2 = d_p2; p.dist = d_dist; p.nsup = d_nsup; p.status = d_status;
-    if (c->fd.Y0) {
-        if (c->fd_dedup) return kNeedBatch;      // the de-duplication mask compares rows in memory
-        p.Y = c->fd.Y0; p.fd = 1 + c->fd.row0; p.fd_fixed = c->fd.fixed; p.fd_h = c->fd.h;
-    }
     size_t lds = sizeof(double) * ((size_t)c->n_veh * p.vp + 3 * (size_t)c->n_poly_pts);
     const bool planar = c->dim == 2 && c->polys_planar;
     if (planar && c->max_poly_K <= c->deg + 1 && c->deg + 1 <= 127) {
@@ -3397,29 +3477,17 @@ int launch_gjk_swarm(obtg_ctx* c, const double* dY, int B, int max_iter, int md_
             default: break;
         }
 #undef OBTG_GJK_CASE
-        constexpr size_t kTileAbove = 48 * 1024, kSweepMax = 64 * 1024;
-        if (kt && lds2 > kTileAbove) {
+        if (kt && lds2 > kLdsDefaultMax) {
             // large rows: tile-major chunks, each staging only the objects it touches
             int rc = build_tiles(c, vp2);
             if (rc == OBTG_OK) {
                 GjkSwarmParams q = p;
-                q.chunk_off = c->d_tile_chunk_off.as<int>(); q.order = c->d_tile_order.as<int>();
-                q.pslots = c->d_tile_pslots.as<unsigned>(); q.cobj_off = c->d_tile_cobj_off.as<int>();
-                q.cobjs = c->d_tile_cobjs.as<int>(); q.max_objs = c->tile_max_objs;
-                q.chunk = c->tile_max_pairs; q.wgs_per_row = c->tile_n_chunks; q.passes = 1;
+                fill_tile_tables(c, q);
+                q.passes = 1;
                 const size_t ldst = planar_lds_bytes<2>(q.max_objs, vp2, q.chunk);
-                if (ldst <= 64 * 1024) {
-                    const size_t npairs = (size_t)c->n_hull_pairs;
-                    obtg::DevBuf& hist_out = c->d_gjk_len[c->gjk_len_cur ^ 1];
-                    if (c->gjk_history) { if (int rc2 = hist_out.reserve((size_t)B * npairs)) return rc2; }
-                    q.B = B;
-                    q.len_in = (c->gjk_history && c->gjk_len_rows > 0) ? c->d_gjk_len[c->gjk_len_cur].as<unsigned char>() : nullptr;
-                    q.len_in_stride = c->gjk_len_rows == B ? (int)npairs : 0;
-                    q.len_out = c->gjk_history ? hist_out.as<unsigned char>() : nullptr;
-                    if (c->gjk_history) { c->gjk_len_cur ^= 1; c->gjk_len_rows = B; }
-                    if (ldst > 48 * 1024)
-                        OBTG_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kt),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldst));
+                if (ldst <= kLdsLaunchMax) {
+                    if (int rc2 = fill_history(c, q, B)) return rc2;
+                    OBTG_HIP(c, allow_lds(kt, ldst));
                     ScopedKernelTimer t(c, OBTG_K_GJK);
                     hipLaunchKernelGGL(kt, dim3((unsigned)((size_t)B * q.wgs_per_row)), dim3(256), ldst, c->stream, q);
                     OBTG_HIP(c, hipGetLastError());
@@ -3427,10 +3495,8 @@ int launch_gjk_swarm(obtg_ctx* c, const double* dY, int B, int max_iter, int md_
                 }
             } else if (rc != OBTG_ERR_UNSUPPORTED) return rc;
         }
-        if (kp && lds2 <= kSweepMax) {   // larger rows: the general kernel does better than 1-2 workgroups per CU
-            if (lds2 > 48 * 1024)
-                OBTG_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kp),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+        if (kp && lds2 <= kLdsLaunchMax) {   // larger rows: the general kernel does better than 1-2 workgroups per CU
+            OBTG_HIP(c, allow_lds(kp, lds2));
             ScopedKernelTimer t(c, OBTG_K_GJK);
             if (c->fd_dedup && B > 1 && kf) {
                 // Finite-difference de-duplication: row 0 in full, its results broadcast to every
@@ -3467,19 +3533,9 @@ int launch_gjk_swarm(obtg_ctx* c, const double* dY, int B, int max_iter, int md_
                 const size_t ldsf = planar_lds_bytes<1>(c->n_veh + c->n_poly, vp2, q.chunk);
                 hipLaunchKernelGGL(kf, dim3((unsigned)(B - 1)), dim3(256), ldsf, c->stream, q);
             } else {
-                // trip-count history: this sweep orders its pairs by the counts the previous one left
-                // behind (same batch shape: row by row; otherwise every row follows the old row 0)
-                const size_t np = (size_t)c->n_hull_pairs;
-                obtg::DevBuf& hist_out = c->d_gjk_len[c->gjk_len_cur ^ 1];
-                if (int rc = hist_out.reserve((size_t)B * np)) return rc;
-                p.B = B;
-                p.len_in = (c->gjk_history && c->gjk_len_rows > 0) ? c->d_gjk_len[c->gjk_len_cur].as<unsigned char>() : nullptr;
-                p.len_in_stride = c->gjk_len_rows == B ? (int)np : 0;
-                p.len_out = c->gjk_history ? hist_out.as<unsigned char>() : nullptr;
+                if (int rc = fill_history(c, p, B)) return rc;
                 const unsigned grid = (unsigned)(((size_t)B + 7) / 8 * 8 * p.wgs_per_row);
                 hipLaunchKernelGGL(kp, dim3(grid), dim3(OBTG_SWEEP_THREADS), lds2, c->stream, p);
-                c->gjk_len_cur ^= 1;
-                c->gjk_len_rows = B;
             }
             OBTG_HIP(c, hipGetLastError());
             return OBTG_OK;
@@ -3515,17 +3571,9 @@ int launch_gjk_swarm(obtg_ctx* c, const double* dY, int B, int max_iter, int md_
             p.wgs_per_row = (c->n_hull_pairs + p.chunk - 1) / p.chunk;
         }
         const size_t lds3 = sweep3d_lds_bytes(n_obj, nc, p.chunk);
-        if (k3 && lds3 <= 64 * 1024 && p.chunk <= 65535) {
-            if (lds3 > 48 * 1024)
-                OBTG_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k3),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
-            const size_t np = (size_t)c->n_hull_pairs;
-            obtg::DevBuf& hist_out = c->d_gjk_len[c->gjk_len_cur ^ 1];
-            if (int rc2 = hist_out.reserve((size_t)B * np)) return rc2;
-            p.B = B;
-            p.len_in = (c->gjk_history && c->gjk_len_rows > 0) ? c->d_gjk_len[c->gjk_len_cur].as<unsigned char>() : nullptr;
-            p.len_in_stride = c->gjk_len_rows == B ? (int)np : 0;
-            p.len_out = c->gjk_history ? hist_out.as<unsigned char>() : nullptr;
+        if (k3 && lds3 <= kLdsLaunchMax && p.chunk <= 65535) {
+            OBTG_HIP(c, allow_lds(k3, lds3));
+            if (int rc2 = fill_history(c, p, B)) return rc2;
             const unsigned grid = (unsigned)(((size_t)B + 7) / 8 * 8 * p.wgs_per_row);
             // one launch for the batch: fold the row's temporal-separation block (and speed rows) into the sweep
             bool folded = false;
@@ -3563,10 +3611,8 @@ int launch_gjk_swarm(obtg_ctx* c, const double* dY, int B, int max_iter, int md_
                     ns_bytes = std::max(ns_bytes, sizeof(double) * ((size_t)sp.stage_slots * vp3 + (size_t)4 * tr * tpf));
                 }
                 const size_t lds_a = (lds3 + 15) / 16 * 16;
-                if (kf3 && lds_a + ns_bytes <= 64 * 1024) {
-                    if (lds_a + ns_bytes > 48 * 1024)
-                        OBTG_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kf3),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_a + ns_bytes)));
+                if (kf3 && lds_a + ns_bytes <= kLdsLaunchMax) {
+                    OBTG_HIP(c, allow_lds(kf3, lds_a + ns_bytes));
                     ScopedKernelTimer t(c, OBTG_K_PAIR_SWEEP);
                     hipLaunchKernelGGL(kf3, dim3(grid), dim3(256), lds_a + ns_bytes, c->stream, p, ts, sp, (int)(lds_a / sizeof(double)));
                     folded = true;
@@ -3578,8 +3624,6 @@ int launch_gjk_swarm(obtg_ctx* c, const double* dY, int B, int max_iter, int md_
                 ScopedKernelTimer t(c, OBTG_K_GJK);
                 hipLaunchKernelGGL(k3, dim3(grid), dim3(256), lds3, c->stream, p);
             }
-            c->gjk_len_cur ^= 1;
-            c->gjk_len_rows = B;
             OBTG_HIP(c, hipGetLastError());
             return OBTG_OK;
         }
@@ -3588,18 +3632,13 @@ int launch_gjk_swarm(obtg_ctx* c, const double* dY, int B, int max_iter, int md_
     p.chunk = (c->n_hull_pairs + wgs - 1) / wgs;                  // (the fixed-count branches above may have reshaped the grid)
     p.wgs_per_row = (c->n_hull_pairs + p.chunk - 1) / p.chunk; p.passes = 1;
     auto kern = planar ? k_gjk_swarm<true> : k_gjk_swarm<false>;
-    if (lds > 48 * 1024)
-        OBTG_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    OBTG_HIP(c, allow_lds(kern, lds));
     ScopedKernelTimer t(c, OBTG_K_GJK);
     hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)B * p.wgs_per_row)), dim3(256), lds, c->stream, p);
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;
 }
 
-// The pair sweeps of a batch as one launch: the planar GJK sweep whose workgroups also write their
-// row's temporal-separation block (GjkSwarmParams::ts).  Shapes outside that kernel: two launches.
-// does obtg_pair_sweep_dev run as ONE launch for this context (large batch)?  Mirrors launch_pair_sweep's decision.
 // Rows per pass of the separation block's transposition tile (4 waves x rows x odd(2n+1) doubles), which borrows the LDS
 // behind the staged objects; small rows get a larger allocation so that 16 rows fit.  0: no room.
 static int pair_sweep_tile_rows(const obtg_ctx* c, int nc, size_t& lds)
@@ -3611,234 +3650,109 @@ static int pair_sweep_tile_rows(const obtg_ctx* c, int nc, size_t& lds)
     int tr = 64;                       // the largest multiple of 8 that fits
     while (tr >= 8 && objects + tile(tr) > lds) tr -= 8;
     // up to 32 rows per pass (two passes per 64-pair group) while the workgroup keeps its place in the CU's LDS
-    const size_t budget = (size_t)160 * 1024 / kPairSweepWavesPerSimd - 1280;
+    const size_t budget = lds_share(kPairSweepWavesPerSimd);
     for (int want = 32; want >= 8 && tr < want; want -= 8)
         if (objects + tile(want) <= budget) { lds = std::max(lds, objects + tile(want)); tr = want; break; }
     return tr >= 8 ? tr : 0;
 }
 
-bool pair_sweep_is_one_launch(const obtg_ctx* c)
+// The pair sweeps of a batch as one launch: the planar GJK sweep whose workgroups also write their row's
+// temporal-separation block (GjkSwarmParams::ts) and, as the grid's last workgroups, the batch's speed / angular-rate
+// groups (GjkSwarmParams::dyn).  Which form a context and a row count get is decided HERE and nowhere else:
+// launch_pair_sweep executes the plan, and the predicates capi.cpp routes by (pair_sweep_is_one_launch,
+// constraint_sweep_is_one_launch) are questions put to it.  A new form of the sweep adds its value to Form, its case to
+// pair_sweep_plan and its launch to launch_pair_sweep.
+// Where this differs from the three hand-written copies it replaces (no result changes):
+//   - History: every form takes the rule the tiled forms had (fill_history): the buffer is reserved and flipped only while
+//     the history is on, before the launch.  The other forms reserved and flipped always, after the launch; since
+//     obtg_ctx_set_gjk_history zeroes gjk_len_rows, a buffer written while the history was off was never read.  The history
+//     buffer is therefore no longer allocated while the history is off, and len_in_stride (unread beside a null len_in) may
+//     be 0 where it was n_pairs.
+//   - OBTG_FOLD_DYNAMICS is read once per process (fold_dynamics_enabled); the router used to read it on every call, the
+//     launcher once.
+//   - constraint_sweep_is_one_launch makes the context's tables (ensure_tables) before it looks at OBTG_FOLD_DYNAMICS, not after.
+//   - launch_gjk_swarm keeps its own routing: its de-duplicated branch chunks row 0 by its own rule (w0), and the general
+//     kernel reshapes chunk / wgs_per_row after the fixed-count branches.
+struct PairSweepPlan {
+    enum Form { kTwoLaunches, kOneLaunch, kTiled } form = kTwoLaunches;      // kTwoLaunches: launch_gjk_swarm (which folds what its 3-D sweep can) + the separation rows
+    void (*kern)(const GjkSwarmParams) = nullptr;      // k_pair_sweep<NC> or k_pair_sweep_tiled<NC>
+    SweepShape shape;                  // kOneLaunch: the grid (kTiled: the chunk tables give it)
+    size_t lds = 0;                    // dynamic LDS of the sweep's workgroups
+    int tile_rows = 0;                 // rows per pass of the separation block's transposition tile
+    bool fold_dyn = false;             // the speed / angular-rate groups join the grid
+    size_t lds_launch = 0;             // what the launch asks for: lds, or the larger of it and the dynamics groups'
+};
+// want_dyn: the caller wants speed AND angular-rate rows of the same batch (wants_dynamics).  may_build = false: decide the
+// one-launch planar form from the context as it is and touch nothing (tables, chunk tables): the tiled form is not looked at.
+static int pair_sweep_plan(obtg_ctx* c, int B, bool want_dyn, PairSweepPlan& pl, bool may_build = true)
 {
+    pl = PairSweepPlan{};
     const int nc = c->deg + 1;
-    if (!nc_in_dyn(nc)) return false;
-    if (!(c->dim == 2 && c->polys_planar && c->max_poly_K <= nc && c->n_hull_pairs > 0 && !c->fd_dedup && c->R == 0 &&
-          c->n_pairs > 0)) return false;
-    size_t lds = sweep_shape(c, 1 << 20, nc, kPairSweepWavesPerSimd, kPairSweepChunk).lds;
-    return pair_sweep_tile_rows(c, nc, lds) > 0 && lds <= 48 * 1024;
-}
-
-int launch_pair_sweep(obtg_ctx* c, const double* dY, int B, double max_sep, double* d_out_sep, int max_iter,
-                      int md_cap, int* d_flag, double* d_p1, double* d_p2, double* d_dist, int* d_nsup, int* d_status,
-                      SweepFold* speed)
-{
-    // with a virtual finite-difference batch (c->fd) only the one-launch kernel applies: it forms the rows while
-    // staging them; OBTG_ERR_UNSUPPORTED tells the caller to materialise the batch instead
-    if (B <= 0) return OBTG_OK;
-    const int nc = c->deg + 1;
-    void (*kern)(const GjkSwarmParams) = nullptr;
+    void (*k1)(const GjkSwarmParams) = nullptr;
+    void (*kt)(const GjkSwarmParams) = nullptr;
     switch (nc) {
-#define OBTG_CASE(NC_) case NC_: kern = k_pair_sweep<NC_>; break;
+#define OBTG_CASE(NC_) case NC_: k1 = k_pair_sweep<NC_>; break;
         OBTG_NC_DYN(OBTG_CASE)
 #undef OBTG_CASE
         default: break;
     }
-    bool fused = kern && c->dim == 2 && c->polys_planar && c->max_poly_K <= nc && c->n_hull_pairs > 0 &&
-                 !c->fd_dedup && c->R == 0 && c->n_pairs > 0;
-    GjkSwarmParams p{};
-    size_t lds = 0;
-    if (fused) {
-        int rc = ensure_tables(c);
-        if (rc) return rc;
-        p.Y = dY; p.poly = c->d_poly_pts.as<double>(); p.poly_off = c->d_poly_off.as<int>();
-        p.pa = c->d_hp_a.as<int>(); p.pb = c->d_hp_b.as<int>();
-        p.n_veh = c->n_veh; p.dim = c->dim; p.nc = nc; p.n_poly = c->n_poly;
-        p.n_poly_pts = c->n_poly_pts; p.n_pairs = c->n_hull_pairs;
-        const SweepShape shape = sweep_shape(c, B, nc, kPairSweepWavesPerSimd, kPairSweepChunk);
-        p.chunk = shape.chunk; p.wgs_per_row = shape.wgs; p.passes = shape.passes;
-        p.max_iter = max_iter; p.md_cap = md_cap;
-        p.refill_min = sweep_refill_min(); p.hist_shift = sweep_hist_shift();
-        p.flag = d_flag; p.p1 = d_p1; p.p2 = d_p2; p.dist = d_dist; p.nsup = d_nsup; p.status = d_status;
-        lds = shape.lds;
-        const int tr = pair_sweep_tile_rows(c, nc, lds);      // the transposition tile borrows the LDS behind the objects
-        fused = tr > 0 && lds <= 48 * 1024;
-        p.ts.pairs = c->d_pairs.as<int2>(); p.ts.W2 = c->d_w2.as<double>(); p.ts.out = d_out_sep;
-        p.ts.n_pairs = c->n_pairs; p.ts.sign = 1.0; p.ts.offset = 0.0 - square_as_python(max_sep);
-        p.ts_tile_rows = tr;
-        if (c->n_obs > 0) {            // point obstacles: constant curves behind the hull objects, for the separation rows only
-            p.obs = c->d_obs.as<double>(); p.n_obs = c->n_obs;
-            p.ts.n_veh = c->n_veh; p.ts.obs_shift = c->n_poly;
-        }
-        if (c->fd.Y0) { p.Y = c->fd.Y0; p.fd = 1 + c->fd.row0; p.fd_fixed = c->fd.fixed; p.fd_h = c->fd.h; }
-    }
-    if (!fused && kern && c->dim == 2 && c->polys_planar && c->max_poly_K <= nc && c->n_hull_pairs > 0 && !c->fd_dedup &&
-        c->R == 0 && c->n_obs == 0 && c->n_pairs > 0 && lds > 48 * 1024) {
-        // large rows: the tiled sweep, its chunks writing their tile's separation rows
-        void (*kt)(const GjkSwarmParams) = nullptr;
-        switch (nc) {
+    switch (nc) {                      // (a switch of its own: the kernels keep their order in the code object)
 #define OBTG_CASE(NC_) case NC_: kt = k_pair_sweep_tiled<NC_>; break;
-            OBTG_NC_DYN(OBTG_CASE)
+        OBTG_NC_DYN(OBTG_CASE)
 #undef OBTG_CASE
-            default: break;
-        }
-        const int vpq = nc | 1;
-        int rc = build_tiles(c, vpq);
-        if (rc != OBTG_OK && rc != OBTG_ERR_UNSUPPORTED) return rc;
-        if (rc == OBTG_OK && kt && c->tile_ts_ok) {
-            GjkSwarmParams q = p;
-            q.chunk_off = c->d_tile_chunk_off.as<int>(); q.order = c->d_tile_order.as<int>();
-            q.pslots = c->d_tile_pslots.as<unsigned>(); q.cobj_off = c->d_tile_cobj_off.as<int>();
-            q.cobjs = c->d_tile_cobjs.as<int>(); q.max_objs = c->tile_max_objs;
-            q.chunk_ij = c->d_tile_ij.as<int2>(); q.tile_a = c->tile_a;
-            q.chunk = c->tile_max_pairs; q.wgs_per_row = c->tile_n_chunks;
-            const size_t ldst = planar_lds_bytes<2>(q.max_objs, vpq, q.chunk);
-            const int L = 2 * c->deg + 1, tpf = (L % 2 == 0) ? L + 1 : L;
-            const size_t behind = ldst - (size_t)16 * q.max_objs * vpq;
-            int tr = 64;
-            while (tr >= 8 && (size_t)4 * tr * tpf * sizeof(double) > behind) tr -= 8;
-            if (tr >= 8 && ldst <= 64 * 1024) {
-                q.ts_tile_rows = tr;
-                const size_t npairs = (size_t)c->n_hull_pairs;
-                obtg::DevBuf& hist_out = c->d_gjk_len[c->gjk_len_cur ^ 1];
-                if (c->gjk_history) { if (int rc2 = hist_out.reserve((size_t)B * npairs)) return rc2; }
-                q.B = B;
-                q.len_in = (c->gjk_history && c->gjk_len_rows > 0) ? c->d_gjk_len[c->gjk_len_cur].as<unsigned char>() : nullptr;
-                q.len_in_stride = c->gjk_len_rows == B ? (int)npairs : 0;
-                q.len_out = c->gjk_history ? hist_out.as<unsigned char>() : nullptr;
-                if (c->gjk_history) { c->gjk_len_cur ^= 1; c->gjk_len_rows = B; }
-                unsigned grid_t = (unsigned)((size_t)B * q.wgs_per_row);
-                size_t lds_t = ldst;
-                static const bool fold_dyn_t = !(getenv("OBTG_FOLD_DYNAMICS") && getenv("OBTG_FOLD_DYNAMICS")[0] == '0');
-                if (fold_dyn_t && speed && speed->d_out_ang && speed->d_out_speed && speed->d_tf && c->d_ang_w22n.p != nullptr) {
-                    const int L4 = 4 * c->deg + 1;
-                    const size_t lds_dyn = sizeof(double) * ((size_t)kWave * L4 + (size_t)(kWave / 2) * L);
-                    if (std::max(ldst, lds_dyn) <= (size_t)160 * 1024 / 4 - 1280) {       // still four workgroups per CU
-                        AngParams& d = q.dyn;
-                        d.Y = q.Y; d.tf = speed->d_tf; d.out = speed->d_out_ang; d.out_speed = speed->d_out_speed;
-                        d.n_veh = c->n_veh; d.total = B * c->n_veh;
-                        d.w2 = square_as_python(speed->max_rate);
-                        const double b2 = square_as_python(speed->speed_bound);
-                        d.sp_sign = speed->speed_is_max ? -1.0 : 1.0; d.sp_offset = speed->speed_is_max ? b2 : -b2;
-                        if (c->speed2.d_out) {
-                            const double c2 = square_as_python(c->speed2.bound);
-                            d.out_speed2 = c->speed2.d_out;
-                            d.sp2_sign = c->speed2.is_max ? -1.0 : 1.0; d.sp2_offset = c->speed2.is_max ? c2 : -c2;
-                        }
-                        d.W2n = c->d_ang_w2n.as<double>(); d.W22n = c->d_ang_w22n.as<double>(); d.Wn = c->d_ang_wn.as<double>();
-                        d.fd = q.fd; d.fd_fixed = q.fd_fixed; d.fd_h = q.fd_h;
-                        q.dyn_first_block = (int)grid_t;
-                        grid_t += (unsigned)((d.total + kWave - 1) / kWave);
-                        lds_t = std::max(ldst, lds_dyn);
-                        speed->did_dynamics = true;
-                    }
-                }
-                if (lds_t > 48 * 1024)
-                    OBTG_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kt),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
-                ScopedKernelTimer tm(c, OBTG_K_PAIR_SWEEP, true);
-                launch_timed(tm, kt, dim3(grid_t), dim3(256), lds_t, c->stream, q);
-                OBTG_HIP(c, hipGetLastError());
-                return OBTG_OK;
-            }
-        }
+        default: break;
     }
-    if (!fused) {
-        // the 3-D sweep takes the separation block (and speed rows) into its launch where it can; otherwise two
-        // launches, each forming the virtual batch's rows itself or asking for the batch (kNeedBatch)
-        SweepFold f;
-        if (speed) f = *speed;
-        f.max_sep = max_sep; f.d_out_sep = d_out_sep; f.did_sep = f.did_speed = false;
-        int rc = launch_gjk_swarm(c, dY, B, max_iter, md_cap, d_flag, d_p1, d_p2, d_dist, d_nsup, d_status, &f);
+    if (!(k1 && c->dim == 2 && c->polys_planar && c->max_poly_K <= nc && c->n_hull_pairs > 0 && !c->fd_dedup && c->R == 0 &&
+          c->n_pairs > 0)) return OBTG_OK;
+    if (may_build) { if (int rc = ensure_tables(c)) return rc; }
+    const int vpq = nc | 1, L = 2 * c->deg + 1, L4 = 4 * c->deg + 1, tpf = (L % 2 == 0) ? L + 1 : L;
+    const bool dyn = want_dyn && fold_dynamics_enabled() && c->d_ang_w22n.p != nullptr;
+    const size_t lds_dyn = sizeof(double) * ((size_t)kWave * L4 + (size_t)(kWave / 2) * L);      // (26 KB at degree 10)
+    pl.shape = sweep_shape(c, B, nc, kPairSweepWavesPerSimd, kPairSweepChunk);
+    pl.lds = pl.shape.lds;
+    pl.tile_rows = pair_sweep_tile_rows(c, nc, pl.lds);      // the transposition tile borrows the LDS behind the objects
+    if (pl.tile_rows > 0 && pl.lds <= kLdsDefaultMax) {
+        pl.form = PairSweepPlan::kOneLaunch; pl.kern = k1;
+        // the speed / angular-rate groups of the batch as the grid's last workgroups (they fill the slots the sweep's tail
+        // leaves empty): when the caller wants them and their LDS fits the sweep's allocation class
+        pl.fold_dyn = dyn && nc <= 11 && std::max(pl.lds, lds_dyn) <= lds_share(kPairSweepWavesPerSimd);
+    } else {
+        // large rows: the tiled sweep, its chunks writing their tile's separation rows (point obstacles: not staged by it)
+        if (!may_build || c->n_obs != 0 || pl.lds <= kLdsDefaultMax) return OBTG_OK;
+        const int rc = build_tiles(c, vpq);
+        if (rc == OBTG_ERR_UNSUPPORTED || (rc == OBTG_OK && !c->tile_ts_ok)) return OBTG_OK;
         if (rc) return rc;
-        if (speed) speed->did_speed = f.did_speed;
-        if (f.did_sep) return OBTG_OK;
-        if (speed && c->R > 0) {       // DEG_ELEV > 0: the separation rows and the dynamics rows share a launch
-            rc = launch_sep_dynamics_elev(c, dY, B, max_sep, d_out_sep, *speed);
-            if (rc == OBTG_OK) { speed->did_dynamics = true; return OBTG_OK; }
-            if (rc != OBTG_ERR_UNSUPPORTED) return rc;
-        }
-        return launch_temporal_sep(c, dY, B, max_sep, 0, c->n_pairs, false, d_out_sep);
+        pl.lds = planar_lds_bytes<2>(c->tile_max_objs, vpq, c->tile_max_pairs);
+        const size_t behind = pl.lds - (size_t)16 * c->tile_max_objs * vpq;
+        pl.tile_rows = 64;
+        while (pl.tile_rows >= 8 && (size_t)4 * pl.tile_rows * tpf * sizeof(double) > behind) pl.tile_rows -= 8;
+        if (pl.tile_rows < 8 || pl.lds > kLdsLaunchMax) return OBTG_OK;
+        pl.form = PairSweepPlan::kTiled; pl.kern = kt;
+        pl.fold_dyn = dyn && std::max(pl.lds, lds_dyn) <= lds_share(4);      // still four workgroups per CU (k_pair_sweep_tiled's bound)
     }
-    const size_t np = (size_t)c->n_hull_pairs;
-    obtg::DevBuf& hist_out = c->d_gjk_len[c->gjk_len_cur ^ 1];
-    if (int rc = hist_out.reserve((size_t)B * np)) return rc;
-    p.B = B;
-    p.len_in = (c->gjk_history && c->gjk_len_rows > 0) ? c->d_gjk_len[c->gjk_len_cur].as<unsigned char>() : nullptr;
-    p.len_in_stride = c->gjk_len_rows == B ? (int)np : 0;
-    p.len_out = c->gjk_history ? hist_out.as<unsigned char>() : nullptr;
-    unsigned grid = (unsigned)(((size_t)B + 7) / 8 * 8 * p.wgs_per_row);
-    // the speed / angular-rate groups of the batch as the grid's last workgroups (they fill the slots the sweep's tail
-    // leaves empty): when the caller wants them and their 26 KB of LDS fit the sweep's allocation class
-    static const bool fold_dyn = !(getenv("OBTG_FOLD_DYNAMICS") && getenv("OBTG_FOLD_DYNAMICS")[0] == '0');
-    if (fold_dyn && speed && speed->d_out_ang && speed->d_out_speed && speed->d_tf && c->d_ang_w22n.p != nullptr) {
-        const int L4 = 4 * c->deg + 1, L2 = 2 * c->deg + 1;
-        const size_t lds_dyn = sizeof(double) * ((size_t)kWave * L4 + (size_t)(kWave / 2) * L2);
-        const size_t budget = (size_t)160 * 1024 / kPairSweepWavesPerSimd - 1280;
-        if (nc <= 11 && std::max(lds, lds_dyn) <= budget) {
-            AngParams& d = p.dyn;
-            d.Y = p.Y; d.tf = speed->d_tf; d.out = speed->d_out_ang; d.out_speed = speed->d_out_speed;
-            d.n_veh = c->n_veh; d.total = B * c->n_veh;
-            d.w2 = square_as_python(speed->max_rate);
-            const double b2 = square_as_python(speed->speed_bound);
-            d.sp_sign = speed->speed_is_max ? -1.0 : 1.0; d.sp_offset = speed->speed_is_max ? b2 : -b2;
-            if (c->speed2.d_out) {
-                const double c2 = square_as_python(c->speed2.bound);
-                d.out_speed2 = c->speed2.d_out;
-                d.sp2_sign = c->speed2.is_max ? -1.0 : 1.0; d.sp2_offset = c->speed2.is_max ? c2 : -c2;
-            }
-            d.W2n = c->d_ang_w2n.as<double>(); d.W22n = c->d_ang_w22n.as<double>(); d.Wn = c->d_ang_wn.as<double>();
-            d.fd = p.fd; d.fd_fixed = p.fd_fixed; d.fd_h = p.fd_h;
-            p.dyn_first_block = (int)grid;
-            grid += (unsigned)((d.total + kWave - 1) / kWave);
-            lds = std::max(lds, lds_dyn);
-            speed->did_dynamics = true;
-        }
-    }
-    TimelineDump tl(c, grid, p.timeline);
-    if (tl.rc) return tl.rc;
-    {
-        ScopedKernelTimer tm(c, OBTG_K_PAIR_SWEEP, true);
-        launch_timed(tm, kern, dim3(grid), dim3(OBTG_SWEEP_THREADS), lds, c->stream, p);
-    }
-    {
-        char hdr[256];
-        snprintf(hdr, sizeof hdr, "# grid %u sweep_blocks %d wgs_per_row %d passes %d chunk %d B %d", grid,
-                 p.dyn.out ? p.dyn_first_block : (int)grid, p.wgs_per_row, p.passes, p.chunk, B);
-        if (int rc = tl.finish(hdr)) return rc;
-    }
-    c->gjk_len_cur ^= 1;
-    c->gjk_len_rows = B;
-    OBTG_HIP(c, hipGetLastError());
+    pl.lds_launch = pl.fold_dyn ? std::max(pl.lds, lds_dyn) : pl.lds;
     return OBTG_OK;
 }
 
+// does obtg_pair_sweep_dev run as ONE launch that forms a view's rows itself for this context (large batch)?
+bool pair_sweep_is_one_launch(const obtg_ctx* c)
+{
+    PairSweepPlan pl;
+    return pair_sweep_plan(const_cast<obtg_ctx*>(c), 1 << 20, false, pl, false) == OBTG_OK && pl.form == PairSweepPlan::kOneLaunch;      // (may_build = false: nothing written)
+}
+
 // Is obtg_constraint_sweep_dev with all three row families ONE launch for this context and batch size -- launch_pair_sweep
-// with the speed / angular-rate groups as the grid's last workgroups, in its one-launch or its tiled form?  Mirrors
-// launch_pair_sweep's decisions and launches nothing (the tiled form's chunk tables are built, as its launch would).
+// with the speed / angular-rate groups as the grid's last workgroups, in its one-launch or its tiled form?  Launches nothing
+// (the tiled form's chunk tables are built, as its launch would).
 // DEG_ELEV > 0 is never one launch (gjkNew sweep + separation rows with the dynamics groups among them).
 bool constraint_sweep_is_one_launch(obtg_ctx* c, int B)
 {
-    const int nc = c->deg + 1;
-    if (B <= 0 || !nc_in_dyn(nc)) return false;
-    if (!(c->dim == 2 && c->polys_planar && c->max_poly_K <= nc && c->n_hull_pairs > 0 && !c->fd_dedup && c->R == 0 &&
-          c->n_pairs > 0)) return false;
-    if (getenv("OBTG_FOLD_DYNAMICS") && getenv("OBTG_FOLD_DYNAMICS")[0] == '0') return false;
-    if (ensure_tables(c) != OBTG_OK || c->d_ang_w22n.p == nullptr) return false;
-    const int L4 = 4 * c->deg + 1, L = 2 * c->deg + 1;
-    const size_t lds_dyn = sizeof(double) * ((size_t)kWave * L4 + (size_t)(kWave / 2) * L);
-    size_t lds = sweep_shape(c, B, nc, kPairSweepWavesPerSimd, kPairSweepChunk).lds;
-    if (pair_sweep_tile_rows(c, nc, lds) > 0 && lds <= 48 * 1024)
-        return nc <= 11 && std::max(lds, lds_dyn) <= (size_t)160 * 1024 / kPairSweepWavesPerSimd - 1280;
-    if (c->n_obs != 0 || lds <= 48 * 1024) return false;
-    const int vpq = nc | 1;                // large rows: the tiled sweep
-    if (build_tiles(c, vpq) != OBTG_OK || !c->tile_ts_ok) return false;
-    const size_t ldst = planar_lds_bytes<2>(c->tile_max_objs, vpq, c->tile_max_pairs);
-    const int tpf = (L % 2 == 0) ? L + 1 : L;
-    if (ldst > 64 * 1024 || (size_t)4 * 8 * tpf * sizeof(double) > ldst - (size_t)16 * c->tile_max_objs * vpq) return false;
-    return std::max(ldst, lds_dyn) <= (size_t)160 * 1024 / 4 - 1280;
+    PairSweepPlan pl;
+    return B > 0 && pair_sweep_plan(c, B, true, pl) == OBTG_OK && pl.form != PairSweepPlan::kTwoLaunches && pl.fold_dyn;
 }
 
 // Which shapes k_step_fd_structured covers, decided without launching anything: the launcher and the router of
-// obtg_constraint_sweep_dev (capi.cpp) share it, in the spirit of pair_sweep_is_one_launch.  OBTG_ERR_UNSUPPORTED: not this
+// obtg_constraint_sweep_dev (capi.cpp) share it, as they share pair_sweep_plan above.  OBTG_ERR_UNSUPPORTED: not this
 // shape (3-D, degree 20, obtg_ctx_set_ang_rate_order(2) with DEG_ELEV > 0, de-duplication on, rows beyond 158 KB of LDS).
 struct StructuredPlan {
     void (*kern)(const StructuredParams) = nullptr;
@@ -3915,6 +3829,73 @@ bool step_fd_structured_supported(obtg_ctx* c)
     return step_fd_structured_plan(c, pl) == OBTG_OK;
 }
 
+int launch_pair_sweep(obtg_ctx* c, const double* dY, int B, double max_sep, double* d_out_sep, int max_iter,
+                      int md_cap, int* d_flag, double* d_p1, double* d_p2, double* d_dist, int* d_nsup, int* d_status,
+                      SweepFold* speed)
+{
+    // with a virtual finite-difference batch (c->fd) only the one-launch kernels apply: they form the rows while
+    // staging them; kNeedBatch from the launchers below tells the caller to materialise the batch instead
+    if (B <= 0) return OBTG_OK;
+    PairSweepPlan pl;
+    if (int rc = pair_sweep_plan(c, B, wants_dynamics(speed), pl)) return rc;
+    if (pl.form == PairSweepPlan::kTwoLaunches) {
+        // the 3-D sweep takes the separation block (and speed rows) into its launch where it can; otherwise two
+        // launches, each forming the virtual batch's rows itself or asking for the batch (kNeedBatch)
+        SweepFold f;
+        if (speed) f = *speed;
+        f.max_sep = max_sep; f.d_out_sep = d_out_sep; f.did_sep = f.did_speed = false;
+        int rc = launch_gjk_swarm(c, dY, B, max_iter, md_cap, d_flag, d_p1, d_p2, d_dist, d_nsup, d_status, &f);
+        if (rc) return rc;
+        if (speed) speed->did_speed = f.did_speed;
+        if (f.did_sep) return OBTG_OK;
+        if (speed && c->R > 0) {       // DEG_ELEV > 0: the separation rows and the dynamics rows share a launch
+            rc = launch_sep_dynamics_elev(c, dY, B, max_sep, d_out_sep, *speed);
+            if (rc == OBTG_OK) { speed->did_dynamics = true; return OBTG_OK; }
+            if (rc != OBTG_ERR_UNSUPPORTED) return rc;
+        }
+        return launch_temporal_sep(c, dY, B, max_sep, 0, c->n_pairs, false, d_out_sep);
+    }
+    const bool tiled = pl.form == PairSweepPlan::kTiled;
+    GjkSwarmParams p{};
+    fill_swarm_params(c, p, dY, max_iter, md_cap, d_flag, d_p1, d_p2, d_dist, d_nsup, d_status);
+    p.chunk = pl.shape.chunk; p.wgs_per_row = pl.shape.wgs; p.passes = pl.shape.passes;
+    fill_sep_block(c, p, max_sep, d_out_sep);
+    p.ts_tile_rows = pl.tile_rows;
+    if (tiled) {
+        fill_tile_tables(c, p);
+        p.chunk_ij = c->d_tile_ij.as<int2>(); p.tile_a = c->tile_a;
+    }
+    if (int rc = fill_history(c, p, B)) return rc;
+    unsigned grid = tiled ? (unsigned)((size_t)B * p.wgs_per_row) : (unsigned)(((size_t)B + 7) / 8 * 8 * p.wgs_per_row);
+    if (pl.fold_dyn) {
+        fill_dynamics(c, p, *speed, B);
+        p.dyn_first_block = (int)grid;
+        grid += (unsigned)((p.dyn.total + kWave - 1) / kWave);
+        speed->did_dynamics = true;
+    }
+    OBTG_HIP(c, allow_lds(pl.kern, pl.lds_launch));
+    if (tiled) {
+        ScopedKernelTimer tm(c, OBTG_K_PAIR_SWEEP, true);
+        launch_timed(tm, pl.kern, dim3(grid), dim3(256), pl.lds_launch, c->stream, p);
+        OBTG_HIP(c, hipGetLastError());
+        return OBTG_OK;
+    }
+    TimelineDump tl(c, grid, p.timeline);
+    if (tl.rc) return tl.rc;
+    {
+        ScopedKernelTimer tm(c, OBTG_K_PAIR_SWEEP, true);
+        launch_timed(tm, pl.kern, dim3(grid), dim3(OBTG_SWEEP_THREADS), pl.lds_launch, c->stream, p);
+    }
+    {
+        char hdr[256];
+        snprintf(hdr, sizeof hdr, "# grid %u sweep_blocks %d wgs_per_row %d passes %d chunk %d B %d", grid,
+                 p.dyn.out ? p.dyn_first_block : (int)grid, p.wgs_per_row, p.passes, p.chunk, B);
+        if (int rc = tl.finish(hdr)) return rc;
+    }
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
 // obtg_constraint_sweep_fd_structured_dev: the whole step of an FD view as ONE launch that evaluates row 0 in full and,
 // per perturbed row, only what its vehicle touches (k_step_fd_structured).  OBTG_ERR_UNSUPPORTED for shapes outside the
 // one-launch planar sweep (the caller uses the brute-force sweep, whose results are the same); nothing is launched then.
@@ -3923,45 +3904,20 @@ int launch_step_fd_structured(obtg_ctx* c, int B, double max_sep, double* d_out_
 {
     if (B <= 0) return OBTG_OK;
     if (!c->fd.Y0) return OBTG_ERR_ARG;
-    if (!(speed && speed->d_out_ang && speed->d_out_speed && speed->d_tf && d_out_sep)) return OBTG_ERR_UNSUPPORTED;
+    if (!(wants_dynamics(speed) && d_out_sep)) return OBTG_ERR_UNSUPPORTED;
     StructuredPlan pl;
     if (int rc = step_fd_structured_plan(c, pl)) return rc;
-    const int nc = c->deg + 1;
     const bool elev = c->R > 0;
     void (*kern)(const StructuredParams) = pl.kern;
     StructuredParams sp{};
     GjkSwarmParams& p = sp.g;
-    p.Y = c->fd.Y0; p.fd = 1 + c->fd.row0; p.fd_fixed = c->fd.fixed; p.fd_h = c->fd.h;
-    p.poly = c->d_poly_pts.as<double>(); p.poly_off = c->d_poly_off.as<int>();
-    p.pa = c->d_hp_a.as<int>(); p.pb = c->d_hp_b.as<int>();
-    p.n_veh = c->n_veh; p.dim = c->dim; p.nc = nc; p.n_poly = c->n_poly;
-    p.n_poly_pts = c->n_poly_pts; p.n_pairs = c->n_hull_pairs;
-    p.max_iter = max_iter; p.md_cap = md_cap; p.refill_min = sweep_refill_min(); p.hist_shift = sweep_hist_shift();
-    p.flag = d_flag; p.p1 = d_p1; p.p2 = d_p2; p.dist = d_dist; p.nsup = d_nsup; p.status = d_status;
+    fill_swarm_params(c, p, nullptr, max_iter, md_cap, d_flag, d_p1, d_p2, d_dist, d_nsup, d_status);      // (the view's row: c->fd)
     p.B = B; p.chunk = 256; p.wgs_per_row = 1; p.passes = 1;
-    p.ts.pairs = c->d_pairs.as<int2>(); p.ts.W2 = c->d_w2.as<double>(); p.ts.out = d_out_sep;
-    p.ts.n_pairs = c->n_pairs; p.ts.sign = 1.0; p.ts.offset = 0.0 - square_as_python(max_sep);
+    fill_sep_block(c, p, max_sep, d_out_sep);
     p.ts.Td = c->d_Td.as<double>(); p.ts.Tf = c->d_Tf.as<double>(); p.ts.R = c->R;
-    if (c->n_obs > 0) {                // point obstacles (optimization.py:86-98): objects of the separation pair table only
-        p.obs = c->d_obs.as<double>(); p.n_obs = c->n_obs;
-        p.ts.n_veh = c->n_veh; p.ts.obs_shift = c->n_poly; p.ts.n_tobj = c->n_veh + c->n_obs;
-    }
+    if (c->n_obs > 0) p.ts.n_tobj = c->n_veh + c->n_obs;      // point obstacles: objects of the separation pair table only
     sp.cv4 = c->d_ang_T4.as<double>(); sp.cv2 = c->d_ang_cv2.as<double>(); sp.R = c->R;
-    {
-        AngParams& d = p.dyn;
-        d.Y = p.Y; d.tf = speed->d_tf; d.out = speed->d_out_ang; d.out_speed = speed->d_out_speed;
-        d.n_veh = c->n_veh; d.total = B * c->n_veh;
-        d.w2 = square_as_python(speed->max_rate);
-        const double b2 = square_as_python(speed->speed_bound);
-        d.sp_sign = speed->speed_is_max ? -1.0 : 1.0; d.sp_offset = speed->speed_is_max ? b2 : -b2;
-        if (c->speed2.d_out) {
-            const double c2 = square_as_python(c->speed2.bound);
-            d.out_speed2 = c->speed2.d_out;
-            d.sp2_sign = c->speed2.is_max ? -1.0 : 1.0; d.sp2_offset = c->speed2.is_max ? c2 : -c2;
-        }
-        d.W2n = c->d_ang_w2n.as<double>(); d.W22n = c->d_ang_w22n.as<double>(); d.Wn = c->d_ang_wn.as<double>();
-        d.fd = p.fd; d.fd_fixed = p.fd_fixed; d.fd_h = p.fd_h;
-    }
+    fill_dynamics(c, p, *speed, B);
     const int L = 2 * c->deg + 1, LR = L + c->R;
     // S: one workgroup per (64-pair group, row range); about two thousand workgroups of streams
     sp.n_sep_groups = (c->n_pairs + kWave - 1) / kWave;
@@ -4046,8 +4002,7 @@ int launch_step_fd_structured(obtg_ctx* c, int B, double max_sep, double* d_out_
     }
     p.dyn_first_block = 0;
     const size_t lds = pl.lds;
-    if (lds > 48 * 1024)
-        OBTG_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    OBTG_HIP(c, allow_lds(kern, lds));
     TimelineDump tl(c, grid, p.timeline);
     if (tl.rc) return tl.rc;
     {
@@ -4483,8 +4438,7 @@ int launch_min_dist_robust(obtg_ctx* c, const double* d_curves, int K, const int
     }
     // any-count form: a node's 3 K-row sub-curves per lane in LDS, past the default 48 KB from K = 32 (51 200 B)
     if (lds > 64 * 1024) return OBTG_ERR_UNSUPPORTED;
-    if (lds > 48 * 1024)
-        OBTG_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    OBTG_HIP(c, allow_lds(kern, lds));
     ScopedKernelTimer t(c, OBTG_K_MIN_DIST);
     hipLaunchKernelGGL(kern, dim3((unsigned)n_pairs), dim3(kWave), lds, c->stream, p);
     OBTG_HIP(c, hipGetLastError());
@@ -4522,8 +4476,7 @@ int launch_min_dist2poly_robust(obtg_ctx* c, const double* d_curves, int K, cons
             default: break;
         }
     }
-    if (lds > 48 * 1024)
-        OBTG_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    OBTG_HIP(c, allow_lds(kern, lds));
     ScopedKernelTimer t(c, OBTG_K_MIN_DIST);
     hipLaunchKernelGGL(kern, dim3((unsigned)n_pairs), dim3(kWave), lds, c->stream, p);
     OBTG_HIP(c, hipGetLastError());

@@ -270,11 +270,17 @@ int launch_sep_dynamics_elev(obtg_ctx* c, const double* dY, int B, double max_se
 int launch_dynamics(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max,
                     double max_rate, double* d_out_speed, double* d_out_ang);
 int launch_fd_batch(obtg_ctx* c, const double* dY0, int n_fixed_cols, double h, int B, double* dY, int row0 = 0);   // rows row0 .. row0 + B - 1 of the batch
+struct AngParams;
+void second_speed_rows(const obtg_ctx* c, AngParams& p);    // the second speed bound's output and offset of a dynamics pass, when one is set
 bool dynamics_fd_on_the_fly(const obtg_ctx* c, bool want_ang);
 int ang_rate_order_in_effect(obtg_ctx* c);
 bool bernstein_fd_on_the_fly(const obtg_ctx* c);      // the separate temporal-separation / speed kernels form a view's rows themselves
-bool pair_sweep_is_one_launch(const obtg_ctx* c);
-bool constraint_sweep_is_one_launch(obtg_ctx* c, int B);    // launch_pair_sweep with the dynamics groups folded in: one launch for B rows?
+// What the sweep launchers of gjk_kernels.hip will do, asked before anything is launched.  Each is a question put to the plan
+// its launcher executes (pair_sweep_plan for launch_pair_sweep, step_fd_structured_plan for launch_step_fd_structured): no
+// condition is written a second time here or in capi.cpp.
+bool pair_sweep_is_one_launch(const obtg_ctx* c);           // launch_pair_sweep of a large batch is the one-launch planar sweep (which forms a view's rows itself); touches nothing
+bool constraint_sweep_is_one_launch(obtg_ctx* c, int B);    // launch_pair_sweep of B rows, every dynamics output wanted, is ONE launch (one-launch planar or tiled, dynamics
+                                                            // groups folded in); may build what that launch needs (tables, the tiled form's chunk tables)
 bool step_fd_structured_supported(obtg_ctx* c);             // launch_step_fd_structured has a kernel for this context (given all outputs); launches nothing
 int launch_bern_elev(obtg_ctx* c, const double* d_in, int rows, int n, int R, double* d_out);
 int launch_bern_diff(obtg_ctx* c, const double* d_in, int rows, int n, double T, double* d_out);

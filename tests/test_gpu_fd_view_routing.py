@@ -306,6 +306,133 @@ def test_routed_c3_step_against_the_oracle_on_sampled_rows(capi, synth, oracle):
     c.close()
 
 
+# ---- which kernels every sweep entry point launches, per branch of the pair sweep's plan (gjk_kernels.hip pair_sweep_plan)
+# name: (N, d, n, R, M, point obstacles, option, row counts); the one polygon of seed 21 has 5 vertices: no more than n + 1
+ROUTING_CASES = {
+    "planar_16x5": (16, 2, 5, 0, 1, None, None, (1, 9)),                           # one-launch planar
+    "planar_16x5_point_obstacles": (16, 2, 5, 0, 1, [[20.0, 30.0], [55.5, 41.0]], None, (1, 9)),
+    "elevated_16x5": (16, 2, 5, 3, 1, None, None, (1, 9)),                         # DEG_ELEV > 0
+    "dedup_16x5": (16, 2, 5, 0, 1, None, "dedup", (1, 9)),
+    "history_off_16x5": (16, 2, 5, 0, 1, None, "history_off", (1, 9)),
+    "tiled_256x15": (256, 2, 15, 0, 0, None, None, (1,)),                          # rows beyond 48 KB: the tiled form
+    "tiled_partial_603x5": (603, 2, 5, 0, 1, None, "partial", (1, 9)),             # ... whose tiles cannot carry the separation rows
+    "tiled_duplicates_603x5": (603, 2, 5, 0, 1, None, "duplicates", (1, 9)),       # ... a tile cut into two chunks
+    "space3d_9x5": (9, 3, 5, 0, 1, None, None, (1, 9)),
+    "degree12_6": (6, 2, 12, 0, 1, None, None, (1, 9)),                            # no fixed-count kernel
+}
+ROUTING_OPS = ("gjk_swarm_batch", "pair_sweep_batch", "pair_sweep_view", "constraint_sweep_batch",
+               "constraint_sweep_view_structured_on", "constraint_sweep_view_structured_off")
+
+
+def routing_case(capi, synth, name):
+    """{"fly": fd_forms_on_the_fly(), "B<rows>": {operation: {kernel name: launches}}} of one ROUTING_CASES entry."""
+    import torch
+    N, d, n, R, M, pobs, option, row_counts = ROUTING_CASES[name]
+    c = Case(capi, synth, N, d, n, R, M, 1, B=max(row_counts), pobs=pobs, seed=21)
+    if option == "partial":          # (test_pair_sweep_one_launch_equals_separate_kernels' lists)
+        keep = np.random.default_rng(5).random(len(c.pa)) < 0.7
+        c.pa, c.pb = c.pa[keep], c.pb[keep]
+    if option == "duplicates":
+        c.pa, c.pb = np.concatenate([c.pa, c.pa[:4000]]), np.concatenate([c.pb, c.pb[:4000]])
+    if option in ("partial", "duplicates"):
+        c.ctx.set_hull_pairs(c.pa, c.pb)
+    if option == "dedup":
+        c.ctx.set_fd_dedup(True)
+    if option == "history_off":
+        c.ctx.set_gjk_history(False)
+    ctx, want_ang = c.ctx, d == 2
+
+    def launches(call):
+        ctx.reset_kernel_stats(); ctx.set_profiling(True)
+        call()
+        torch.cuda.synchronize()
+        ks = {k: v[1] for k, v in ctx.kernel_stats().items() if v[1]}
+        ctx.set_profiling(False)
+        return ks
+
+    def in_view(B, call):
+        ctx.fd_view_begin(c.d0.data_ptr(), c.fixed, c.h, B)
+        try:
+            return call()
+        finally:
+            ctx.fd_view_end()
+
+    out = {"fly": list(ctx.fd_forms_on_the_fly())}
+    for B in row_counts:
+        o = c.bufs(B, want_ang)
+        dY = c.materialised(B)
+        dtf = torch.from_numpy(tf_pattern("one_tf", B)).cuda()
+        gjk = (o["flag"].data_ptr(), o["p1"].data_ptr(), o["p2"].data_ptr(), o["dist"].data_ptr(), o["ns"].data_ptr(), o["st"].data_ptr(), 128, 500)
+        t = {}
+        t["gjk_swarm_batch"] = launches(lambda: ctx.gjk_swarm_dev(dY.data_ptr(), B, *gjk))
+        t["pair_sweep_batch"] = launches(lambda: ctx.pair_sweep_dev(dY.data_ptr(), B, 0.9, o["sep"].data_ptr(), *gjk))
+        t["pair_sweep_view"] = in_view(B, lambda: launches(lambda: ctx.pair_sweep_dev(None, B, 0.9, o["sep"].data_ptr(), *gjk)))
+        t["constraint_sweep_batch"] = c.sweep(dY.data_ptr(), dtf, B, o)
+        t["constraint_sweep_view_structured_on"] = c.in_view(dtf, B, o)
+        ctx.set_fd_view_structured(False)
+        t["constraint_sweep_view_structured_off"] = c.in_view(dtf, B, o)
+        ctx.set_fd_view_structured(True)
+        out["B%d" % B] = t
+        del o, dY
+    c.close()
+    return out
+
+
+# The answers of the library BEFORE the pair sweep's plan (commit ca17e6b: the three hand-written copies of the routing),
+# not of the tree under test.  NOT RECORDED: no GPU could be had when this was written, so the table is a reading of that
+# commit's source (launch_gjk_swarm, launch_pair_sweep, launch_dynamics, launch_sep_dynamics_elev, with_batch), the way
+# test_bernstein_host_return_codes' table was made; a launch counts once per ScopedKernelTimer.  Every case answers the same
+# for every row count it runs.
+_P, _G, _GT = {"pair_sweep": 1}, {"gjk": 1}, {"gjk": 1, "temporal_sep": 1}
+_GTA = {"gjk": 1, "temporal_sep": 1, "ang_rate": 1}
+
+
+def _ops(gjk, pair, pair_view, sweep, sweep_view):
+    return dict(zip(ROUTING_OPS, (gjk, pair, pair_view, sweep, sweep_view, sweep_view)))
+
+
+_ROUTING_BY_CASE = {
+    # one launch everywhere; the view's one-call sweep is the structured step or, switched off, the folded pair sweep
+    "planar_16x5": ([True, True], _ops(_G, _P, _P, _P, _P)),
+    "planar_16x5_point_obstacles": ([True, True], _ops(_G, _P, _P, _P, _P)),
+    "history_off_16x5": ([True, True], _ops(_G, _P, _P, _P, _P)),
+    # DEG_ELEV > 0: gjkNew sweep + separation rows; 120 pairs are two 64-pair groups, too few for k_sep_dynamics_elev, so
+    # the dynamics are k_dynamics_elev's launch
+    "elevated_16x5": ([False, True], _ops(_G, _GT, _GT, _GTA, _GTA)),
+    # de-duplication compares rows in memory: a view is materialised first
+    "dedup_16x5": ([False, True], _ops(_G, _GT, dict(_GT, fd_batch=1), _GTA, dict(_GTA, fd_batch=1))),
+    "tiled_256x15": ([False, True], _ops(_G, _P, _P, _P, _P)),
+    # the tiles cannot carry the separation rows: tiled gjkNew sweep + separation rows + dynamics
+    "tiled_partial_603x5": ([False, True], _ops(_G, _GT, _GT, _GTA, _GTA)),
+    "tiled_duplicates_603x5": ([False, True], _ops(_G, _GT, _GT, _GTA, _GTA)),
+    # 3-D: the sweep folds the separation rows; with a second speed bound set the two speed launches stay separate
+    "space3d_9x5": ([False, False], _ops(_G, _P, _P, {"pair_sweep": 1, "speed": 2}, {"pair_sweep": 1, "speed": 2})),
+    # any-degree kernels read their rows from memory
+    "degree12_6": ([False, False], _ops(_G, _GT, dict(_GT, fd_batch=1), {"gjk": 1, "temporal_sep": 1, "speed": 2, "ang_rate": 1},
+                                        {"gjk": 1, "temporal_sep": 1, "speed": 2, "ang_rate": 1, "fd_batch": 1})),
+}
+ROUTING_EXPECTED = {name: dict({"fly": fly}, **{"B%d" % B: ops for B in ROUTING_CASES[name][7]})
+                    for name, (fly, ops) in _ROUTING_BY_CASE.items()}
+
+
+@pytest.mark.gpu
+def test_sweep_routing_table(capi, synth):
+    """What must not move when the launch side of the sweeps is rearranged: per plan branch (one-launch planar, with point
+    obstacles, DEG_ELEV > 0, de-duplication, history off, tiled, tiled with a partial / a duplicated pair list, 3-D, a degree
+    without a fixed-count kernel) and row count, the launches per kernel name of obtg_gjk_swarm_dev, obtg_pair_sweep_dev (batch
+    and view) and obtg_constraint_sweep_dev (batch, view with the structured switch on and off), and obtg_fd_forms_on_the_fly."""
+    assert sorted(ROUTING_EXPECTED) == sorted(ROUTING_CASES)
+    for name in sorted(ROUTING_CASES):
+        got = routing_case(capi, synth, name)
+        want = ROUTING_EXPECTED[name]
+        assert sorted(got) == sorted(want), name
+        assert got["fly"] == want["fly"], (name, "fd_forms_on_the_fly", got["fly"], want["fly"])
+        for rows in (k for k in sorted(want) if k != "fly"):
+            assert sorted(got[rows]) == sorted(ROUTING_OPS)
+            for op in ROUTING_OPS:
+                assert got[rows][op] == want[rows][op], (name, rows, op, got[rows][op], want[rows][op])
+
+
 def test_header_export_list_and_binding_table_agree_on_the_switch():
     """obtg_ctx_set_fd_view_structured is declared in include/obtg.h, exported by the library, named by obtg_abi_symbols
     and bound in _capi.py with a wrapper on Context; a new symbol alone does not move the ABI revision.  No GPU needed."""

@@ -92,7 +92,8 @@ const char* obtg_strerror(int code);
  *      Later, still 7: new: obtg_ctx_set_fd_view_structured.  obtg_constraint_sweep_dev with dY = NULL inside a view now
  *      takes the structured step where it applies: the same arrays with the same bits, so no meaning changed.
  *      Later, still 7: new: the envelope Jacobian of the true-minimum rows, obtg_temporal_sep_true_min_jac[_dev] (timed
- *      under OBTG_K_TEMPORAL_SEP). */
+ *      under OBTG_K_TEMPORAL_SEP).
+ *      Later, still 7: new: obtg_min_dist_mixed, `_minDist` on curves of different degree (timed under OBTG_K_MIN_DIST). */
 #define OBTG_ABI_VERSION 7
 int obtg_abi_version(void);
 
@@ -487,6 +488,17 @@ int obtg_min_dist(obtg_ctx*, const double* curves, int n_curves, int K,
                   const int* pair_a, const int* pair_b, int n_pairs,
                   double eps, int max_iter, int md_cap, int max_depth, int max_nodes,
                   double* res, int* info, int* status);
+/* `_minDist` (bezier.py:1283-1408) on curves of DIFFERENT degree, as the reference takes them: poly1 / poly2 are each
+ * curve's own control points, t1 = p1idx[0] / c1.deg, t2 = p2idx[0] / c2.deg, and each curve is split by its own de
+ * Casteljau.  Curve i has K_i = curve_off[i + 1] - curve_off[i] control points (2 <= K_i <= 32; curve_off[0] = 0) and is
+ * stored as [3][K_i] row-major at cpts + 3 * curve_off[i]; 2-D curves carry a zero z row.  res, info and status as for
+ * obtg_min_dist.  OBTG_ERR_ARG: null pointers, offsets that do not ascend or any K_i < 2, pair indices out of range;
+ * OBTG_ERR_UNSUPPORTED: any K_i > 32 (or a max_depth above 760, whose frames no workgroup's LDS holds).  Where every K_i
+ * is equal the call is obtg_min_dist on the same arrays, bit for bit. */
+int obtg_min_dist_mixed(obtg_ctx*, const double* cpts, const int* curve_off, int n_curves,
+                        const int* pair_a, const int* pair_b, int n_pairs,
+                        double eps, int max_iter, int md_cap, int max_depth, int max_nodes,
+                        double* res, int* info, int* status);
 int obtg_min_dist2poly(obtg_ctx*, const double* curves, int n_curves, int K,
                        const double* pts, int n_pts, const int* poly_off, int n_poly,
                        const int* pair_curve, const int* pair_poly, int n_pairs,

@@ -101,6 +101,7 @@ _SIGNATURES = {
     "obtg_constraint_sweep_dev": (_i, [_vp, _vp, _vp, _i, _d, _vp, _d, _i, _d, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "obtg_gjk_swarm": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "obtg_min_dist": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _d, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "obtg_min_dist_mixed": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _d, _i, _i, _i, _i, _vp, _vp, _vp]),
     "obtg_min_dist_robust": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _d, _i, _vp, _vp, _vp]),
     "obtg_min_dist2poly": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _d, _i, _i, _i, _i, _vp, _vp, _vp]),
     "obtg_min_dist2poly_robust": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _d, _i, _vp, _vp, _vp]),
@@ -948,6 +949,20 @@ class Context(object):
         """curves[n][3][K] (2-D curves: pass a zero z row)."""
         return self._curve_search("obtg_min_dist", curves, None, (pair_a, pair_b),
                                   (float(eps), max_iter, md_cap, max_depth, max_nodes), 3)
+
+    def min_dist_mixed(self, curves, pair_a, pair_b, eps=1e-9, max_iter=128, md_cap=4096, max_depth=64,
+                       max_nodes=200000):
+        """`min_dist` on curves of different degree (obtg_min_dist_mixed): curves is a list of [3][K_i] arrays, 2 <= K_i <= 32
+        (2-D curves: pass a zero z row).  The same dict as min_dist."""
+        rows = [_f64(c).reshape(3, -1) for c in curves]
+        off = _i32(np.concatenate(([0], np.cumsum([r.shape[1] for r in rows]))))
+        cpts = _f64(np.concatenate([r.ravel() for r in rows]))
+        pa, pb, n = _pairs_arg(pair_a, pair_b)
+        res, info, status = _search_out(n, 3)
+        self._check(self._lib.obtg_min_dist_mixed(self._h, _ptr(cpts), _ptr(off), len(rows), _ptr(pa), _ptr(pb), n, float(eps),
+                                                  max_iter, md_cap, max_depth, max_nodes, _ptr(res), _ptr(info), _ptr(status)),
+                    "obtg_min_dist_mixed")
+        return {"res": res, "nodes": info[:, 0], "gjk_calls": info[:, 1], "depth": info[:, 2], "status": status}
 
     def min_dist_robust(self, curves, pair_a, pair_b, eps=1e-9, max_nodes=200000):
         """Robust branch & bound (obtg_min_dist_robust): true minimum within relative eps when status == MD_OK."""

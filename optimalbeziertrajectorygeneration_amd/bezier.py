@@ -20,7 +20,13 @@ Differences from the reference, on purpose:
     what the reference's recursion returns (bezier.py:631-667, 727-763).  That recursion splits a child at
     `minIdx / deg` taken as an absolute parameter, outside the child's span (bezier.py:659-661 with 560-561): on the
     reference's own example c6 = Bezier([(0,1,2,3,4,5), (5,0,2,5,7,5)]) `c6.min(dim=1)` returns 1.7744000000000004 where
-    the minimum is 2.2606668630782703, and `c6.max(dim=1)` ends in RecursionError (true maximum 5.699106677492463).
+    the minimum is 2.2606668630782703, and `c6.max(dim=1)` ends in RecursionError (true maximum 5.699106677492463);
+  * `minDist` on curves of different degree (obtg_min_dist_mixed) pads each 2-D curve to 3-D by its OWN length.  The
+    reference pads the second curve with `[0] * x1.size` (bezier.py:1302), the FIRST curve's length, so it raises on a
+    2-D second curve of another degree; 3-D pairs and a 2-D first curve against a 3-D second one are the reference's.
+    `minDist(robust=True)` and `collCheck(robust=True)` -- not the reference's algorithms: their answer is the true
+    distance of the curves -- elevate the lower curve to the other's degree (obtg_bern_elev: the same curve, the same
+    parameter) and run the equal-degree search; `collCheck` without `robust` still takes equal degrees only.
 """
 import numpy as np
 
@@ -232,21 +238,24 @@ class Bezier(BezierParams):
 
     def minDist(self, otherCurve, eps=1e-9, max_depth=128, max_nodes=4000000, robust=False):
         """(dist, t1, t2).  Default: the reference's `_minDist` step for step (bezier.py:1283-1408), including
-        its non-minimal answers.  robust=True: obtg_min_dist_robust, the true minimum within relative eps."""
+        its non-minimal answers; the curves may differ in degree (obtg_min_dist_mixed).  robust=True:
+        obtg_min_dist_robust, the true minimum within relative eps (on unequal degrees: the lower curve elevated)."""
         if self.dim < 2 or self.dim > 3 or otherCurve.dim < 2 or otherCurve.dim > 3:
             raise ValueError('Both curves must be either 2D or 3D, not {}D and {}D.'.format(self.dim, otherCurve.dim))
-        if self.deg != otherCurve.deg:
-            raise ValueError('minDist needs curves of equal degree here (got {} and {})'.format(self.deg, otherCurve.deg))
         if robust:
-            r = _ctx().min_dist_robust(np.stack([self._padded(), otherCurve._padded()]), [0], [1], eps=eps,
+            r = _ctx().min_dist_robust(elevated_stack([self._padded(), otherCurve._padded()]), [0], [1], eps=eps,
                                        max_nodes=max_nodes)
             if r['status'][0] != _capi.MD_OK:
                 raise RuntimeError('minDist(robust): search budget exhausted (curves coincide over a stretch?); '
                                    'best distance so far %g' % r['res'][0][0])
             a, t1, t2 = r['res'][0]
             return (float(a), float(t1), float(t2))
-        r = _ctx().min_dist(np.stack([self._padded(), otherCurve._padded()]), [0], [1], eps=eps,
-                            max_depth=max_depth, max_nodes=max_nodes)
+        if self.deg != otherCurve.deg:
+            r = _ctx().min_dist_mixed([self._padded(), otherCurve._padded()], [0], [1], eps=eps,
+                                      max_depth=max_depth, max_nodes=max_nodes)
+        else:
+            r = _ctx().min_dist(np.stack([self._padded(), otherCurve._padded()]), [0], [1], eps=eps,
+                                max_depth=max_depth, max_nodes=max_nodes)
         _raise_md(r['status'][0])
         a, t1, t2 = r['res'][0]
         return (float(a), float(t1), float(t2))
@@ -294,9 +303,10 @@ class Bezier(BezierParams):
         distance is above its own "the curves touch" tolerance, 1e-9 x the largest coordinate, else 0."""
         if self.dim < 2 or self.dim > 3 or otherCurve.dim < 2 or otherCurve.dim > 3:
             raise ValueError('Both curves must be either 2D or 3D, not {}D and {}D.'.format(self.dim, otherCurve.dim))
-        if self.deg != otherCurve.deg:
-            raise ValueError('collCheck needs curves of equal degree here (got {} and {})'.format(self.deg, otherCurve.deg))
-        curves = np.stack([self._padded(), otherCurve._padded()])
+        if self.deg != otherCurve.deg and not robust:
+            raise ValueError('collCheck takes curves of equal degree (got {} and {}); collCheck(robust=True) takes any two'
+                             .format(self.deg, otherCurve.deg))
+        curves = elevated_stack([self._padded(), otherCurve._padded()])
         if robust:
             r = _ctx().min_dist_robust(curves, [0], [1], eps=1e-9, max_nodes=max_nodes)
             if r['status'][0] != _capi.MD_OK:
@@ -322,6 +332,19 @@ class Bezier(BezierParams):
         r = _ctx().coll_check2poly(self._padded()[None], poly, [0, poly.shape[0]], [0], [0], max_nodes=max_nodes)
         _raise_md(r['status'][0], 'collCheck2Poly')
         return int(r['res'][0])
+
+
+def elevated_stack(curves):
+    """Padded curves [3][K_i] -> one array [n][3][max K_i]: the shorter ones degree-elevated to the longest (bezier.py:469-495
+    through obtg_bern_elev; a curve and its parameterisation do not change under elevation).  One device call per LENGTH
+    that occurs, all curves of that length as its rows.  Equal lengths: np.stack."""
+    K = max(c.shape[1] for c in curves)
+    out = np.empty((len(curves), 3, K))
+    for k in set(c.shape[1] for c in curves):
+        idx = [i for i, c in enumerate(curves) if c.shape[1] == k]
+        rows = np.concatenate([curves[i] for i in idx])
+        out[idx] = (rows if k == K else _ctx().bern_elev(rows, K - k)).reshape(len(idx), 3, K)
+    return out
 
 
 def _temporalAlignment(c1, c2):

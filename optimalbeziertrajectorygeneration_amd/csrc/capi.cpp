@@ -234,7 +234,7 @@ const char* obtg_abi_symbols(void)
         "obtg_temporal_sep_fd\0obtg_temporal_sep_fd_dev\0obtg_one_vs_many_min\0obtg_one_vs_many_min_dev\0obtg_one_vs_many_min_spans\0obtg_one_vs_many_min_spans_dev\0"
         "obtg_temporal_sep_dev\0obtg_temporal_sep_min_dev\0obtg_speed_dev\0obtg_ang_rate_dev\0obtg_dynamics_dev\0"
         "obtg_fd_batch_dev\0obtg_fd_view_begin\0obtg_fd_view_begin_rows\0obtg_fd_view_end\0obtg_fd_forms_on_the_fly\0obtg_pair_sweep_fd_dev\0obtg_dynamics_fd_dev\0obtg_gjk_pairs\0obtg_ctx_set_polygons\0obtg_ctx_set_hull_pairs\0"
-        "obtg_ctx_set_fd_dedup\0obtg_ctx_set_fd_view_structured\0obtg_ctx_set_gjk_history\0obtg_pair_sweep_dev\0obtg_constraint_sweep_dev\0obtg_constraint_sweep_fd_structured_dev\0obtg_constraint_sweep_fd_structured_rows_dev\0obtg_gjk_swarm_dev\0obtg_gjk_swarm\0obtg_min_dist\0obtg_min_dist_robust\0obtg_min_dist2poly\0obtg_min_dist2poly_robust\0obtg_gjk_true_pairs\0obtg_coll_check\0obtg_coll_check2poly\0"
+        "obtg_ctx_set_fd_dedup\0obtg_ctx_set_fd_view_structured\0obtg_ctx_set_gjk_history\0obtg_pair_sweep_dev\0obtg_constraint_sweep_dev\0obtg_constraint_sweep_fd_structured_dev\0obtg_constraint_sweep_fd_structured_rows_dev\0obtg_gjk_swarm_dev\0obtg_gjk_swarm\0obtg_min_dist\0obtg_min_dist_mixed\0obtg_min_dist_robust\0obtg_min_dist2poly\0obtg_min_dist2poly_robust\0obtg_gjk_true_pairs\0obtg_coll_check\0obtg_coll_check2poly\0"
         "obtg_bern_extrema\0obtg_bern_extrema_dev\0obtg_temporal_sep_true_min\0obtg_temporal_sep_true_min_dev\0obtg_temporal_sep_true_min_jac\0obtg_temporal_sep_true_min_jac_dev\0"
         "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_restrict\0obtg_bern_eval\0"
         "obtg_euclidean_obj\0obtg_accel_obj\0obtg_jerk_obj\0"
@@ -1322,6 +1322,55 @@ int obtg_gjk_swarm(obtg_ctx* c, const double* Y, int B, int max_iter, int md_cap
     return d2h(c, dist, o.dist, sizeof(double) * n);
 }
 
+// ------------------------------------------------------------------ the pair order of obtg_min_dist / obtg_min_dist_mixed
+// The order the worker waves take the pairs in: by the previous evaluation's node counts, longest search first, when this very
+// pair list was evaluated before (an SLSQP run evaluates one list over and over at nearby x); list order else.
+extern "C++" {
+struct MdOrder {
+    unsigned long long sig;        // of the pair lists (count + hash)
+    int hist;                      // its entry of c->md_hist, -1: none yet
+    bool have;                     // an order was uploaded behind the queue counter (WS_QUEUE)
+    std::vector<int> qbuf;         // [0] the queue counter, [1..] the order: the upload's source, which lives as long as this
+                                   // does -- in the entry point, until its synchronising download (the uploads are asynchronous)
+};
+
+static int md_order_upload(obtg_ctx* c, const int* pair_a, const int* pair_b, int n_pairs, MdOrder& o)
+{
+    o.sig = 1469598103934665603ull ^ (unsigned long long)n_pairs;
+    for (int k = 0; k < n_pairs; ++k) {
+        o.sig = (o.sig ^ (unsigned)pair_a[k]) * 1099511628211ull;
+        o.sig = (o.sig ^ (unsigned)pair_b[k]) * 1099511628211ull;
+    }
+    static const bool use_hist = !(getenv("OBTG_MD_HISTORY") && getenv("OBTG_MD_HISTORY")[0] == '0');
+    std::vector<int>& qbuf = o.qbuf;
+    qbuf.assign((size_t)n_pairs + 1, 0);
+    o.hist = -1;
+    for (size_t h = 0; h < c->md_hist.size(); ++h)
+        if (c->md_hist[h].sig == o.sig && (int)c->md_hist[h].nodes.size() == n_pairs) o.hist = (int)h;
+    o.have = use_hist && o.hist >= 0;
+    for (int k = 0; k < n_pairs; ++k) qbuf[1 + k] = k;
+    if (o.have) {
+        const std::vector<int>& hn = c->md_hist[o.hist].nodes;
+        std::stable_sort(qbuf.begin() + 1, qbuf.end(), [&](int a, int b) { return hn[a] > hn[b]; });
+    }
+    return h2d(c, c->ws_misc[WS_QUEUE], qbuf.data(), sizeof(int) * qbuf.size());
+}
+
+// download_search, then this evaluation's node counts become the list's history (most recent last, four lists kept)
+static int md_download_record(obtg_ctx* c, const MdOrder& o, int n_pairs, double* res, int* info, int* status)
+{
+    std::vector<int> own_info;                               // the history needs the node counts whether the caller asked for info or not
+    if (!info) { own_info.resize((size_t)4 * n_pairs); info = own_info.data(); }
+    const int rc = download_search(c, n_pairs, 3, res, info, status);
+    if (rc) return rc;
+    if (o.hist >= 0) c->md_hist.erase(c->md_hist.begin() + o.hist);
+    if (c->md_hist.size() >= 4) c->md_hist.erase(c->md_hist.begin());
+    c->md_hist.push_back({ o.sig, std::vector<int>((size_t)n_pairs) });
+    for (int k = 0; k < n_pairs; ++k) c->md_hist.back().nodes[k] = info[4 * k];
+    return OBTG_OK;
+}
+}
+
 // ------------------------------------------------------------------ minDist, collCheck (the host path: "batched searches over a pair list" above)
 int obtg_min_dist(obtg_ctx* c, const double* curves, int n_curves, int K, const int* pair_a, const int* pair_b,
                   int n_pairs, double eps, int max_iter, int md_cap, int max_depth, int max_nodes, double* res,
@@ -1336,38 +1385,61 @@ int obtg_min_dist(obtg_ctx* c, const double* curves, int n_curves, int K, const 
     if ((rc = upload_operands(c, curves, n_curves, K, nullptr, pair_a, pair_b, n_pairs))) return rc;
     const bool planar = curves_planar(curves, n_curves, K);
     if ((rc = reserve_search(c, min_dist_stack_doubles(c, K, max_depth, n_pairs, planar), 3, n_pairs))) return rc;
-    // the order the worker waves take the pairs in: by the previous evaluation's node counts, longest search first, when
-    // this very pair list was evaluated before (an SLSQP run evaluates one list over and over at nearby x); list order else
-    unsigned long long sig = 1469598103934665603ull ^ (unsigned long long)n_pairs;
-    for (int k = 0; k < n_pairs; ++k) {
-        sig = (sig ^ (unsigned)pair_a[k]) * 1099511628211ull;
-        sig = (sig ^ (unsigned)pair_b[k]) * 1099511628211ull;
-    }
-    static const bool use_hist = !(getenv("OBTG_MD_HISTORY") && getenv("OBTG_MD_HISTORY")[0] == '0');
-    std::vector<int> qbuf((size_t)n_pairs + 1, 0);           // [0] the queue counter, [1..] the order
-    int hist = -1;
-    for (size_t h = 0; h < c->md_hist.size(); ++h)
-        if (c->md_hist[h].sig == sig && (int)c->md_hist[h].nodes.size() == n_pairs) hist = (int)h;
-    const bool have = use_hist && hist >= 0;
-    for (int k = 0; k < n_pairs; ++k) qbuf[1 + k] = k;
-    if (have) {
-        const std::vector<int>& hn = c->md_hist[hist].nodes;
-        std::stable_sort(qbuf.begin() + 1, qbuf.end(), [&](int a, int b) { return hn[a] > hn[b]; });
-    }
-    if ((rc = h2d(c, c->ws_misc[WS_QUEUE], qbuf.data(), sizeof(int) * qbuf.size()))) return rc;
+    MdOrder ord;
+    if ((rc = md_order_upload(c, pair_a, pair_b, n_pairs, ord))) return rc;
     int* d_queue = slot<int>(c, WS_QUEUE);
     rc = launch_min_dist(c, c->ws_in.as<double>(), K, slot<int>(c, WS_PAIR_A), slot<int>(c, WS_PAIR_B), n_pairs, eps, max_iter,
                          md_cap, max_depth, max_nodes, slot<double>(c, WS_STACK), c->ws_out.as<double>(), slot<int>(c, WS_INFO),
-                         have ? d_queue + 1 : nullptr, d_queue, planar);
+                         ord.have ? d_queue + 1 : nullptr, d_queue, planar);
     if (rc) return rc;
-    std::vector<int> own_info;                               // the history needs the node counts whether the caller asked for info or not
-    if (!info) { own_info.resize((size_t)4 * n_pairs); info = own_info.data(); }
-    if ((rc = download_search(c, n_pairs, 3, res, info, status))) return rc;
-    if (hist >= 0) c->md_hist.erase(c->md_hist.begin() + hist);
-    if (c->md_hist.size() >= 4) c->md_hist.erase(c->md_hist.begin());
-    c->md_hist.push_back({ sig, std::vector<int>((size_t)n_pairs) });
-    for (int k = 0; k < n_pairs; ++k) c->md_hist.back().nodes[k] = info[4 * k];
-    return OBTG_OK;
+    return md_download_record(c, ord, n_pairs, res, info, status);
+}
+
+// _minDist on curves of different degree (bezier.py:1283-1408 takes any two): obtg_min_dist's host path with the curves as
+// offsets into one control-point array.  Every K_i equal: the call IS obtg_min_dist (that layout is its curves[n][3][K]).
+int obtg_min_dist_mixed(obtg_ctx* c, const double* cpts, const int* curve_off, int n_curves, const int* pair_a,
+                        const int* pair_b, int n_pairs, double eps, int max_iter, int md_cap, int max_depth, int max_nodes,
+                        double* res, int* info, int* status)
+{
+    if (!check_ctx(c) || !cpts || !curve_off || !pair_a || !pair_b || !res || n_curves < 1 || n_pairs < 0) return OBTG_ERR_ARG;
+    if (max_iter < 1 || md_cap < 1 || max_depth < 1 || max_nodes < 1 || curve_off[0] != 0) return OBTG_ERR_ARG;
+    bool equal = true, too_long = false;
+    for (int i = 0; i < n_curves; ++i) {
+        const int K = curve_off[i + 1] - curve_off[i];
+        if (K < 2) return OBTG_ERR_ARG;              // (a non-monotone offset list ends here too)
+        too_long |= K > kMdMaxCurveK;
+        equal &= K == curve_off[1];
+    }
+    if (too_long) return OBTG_ERR_UNSUPPORTED;
+    int rc = check_pairs(pair_a, n_curves, pair_b, n_curves, n_pairs);
+    if (rc) return rc;
+    if (equal)
+        return obtg_min_dist(c, cpts, n_curves, curve_off[1], pair_a, pair_b, n_pairs, eps, max_iter, md_cap, max_depth, max_nodes,
+                             res, info, status);
+    if (n_pairs == 0) return OBTG_OK;
+    (void)hipSetDevice(c->device);
+    const int n_pts = curve_off[n_curves];
+    int kt_max = 0;
+    for (int k = 0; k < n_pairs; ++k)
+        kt_max = std::max(kt_max, curve_off[pair_a[k] + 1] - curve_off[pair_a[k]] + curve_off[pair_b[k] + 1] - curve_off[pair_b[k]]);
+    // (the control points as ONE operand of 3 n_pts doubles: the kernel finds a curve by its offset)
+    if ((rc = upload_operands(c, cpts, 1, n_pts, nullptr, pair_a, pair_b, n_pairs))) return rc;
+    if ((rc = h2d(c, c->ws_misc[WS_CURVE_OFF], curve_off, sizeof(int) * (n_curves + 1)))) return rc;
+    bool planar = true;
+    for (int i = 0; i < n_curves && planar; ++i)
+        planar = curves_planar(cpts + 3 * (size_t)curve_off[i], 1, curve_off[i + 1] - curve_off[i]);
+    const size_t stack = min_dist_mixed_stack_doubles(c, kt_max, max_depth, n_pairs);
+    if (!stack) return OBTG_ERR_UNSUPPORTED;         // (max_depth frames of scalars that no workgroup's LDS holds)
+    if ((rc = reserve_search(c, stack, 3, n_pairs))) return rc;
+    MdOrder ord;
+    if ((rc = md_order_upload(c, pair_a, pair_b, n_pairs, ord))) return rc;
+    int* d_queue = slot<int>(c, WS_QUEUE);
+    rc = launch_min_dist_mixed(c, c->ws_in.as<double>(), slot<int>(c, WS_CURVE_OFF), kt_max, slot<int>(c, WS_PAIR_A),
+                               slot<int>(c, WS_PAIR_B), n_pairs, eps, max_iter, md_cap, max_depth, max_nodes,
+                               slot<double>(c, WS_STACK), c->ws_out.as<double>(), slot<int>(c, WS_INFO),
+                               ord.have ? d_queue + 1 : nullptr, d_queue, planar);
+    if (rc) return rc;
+    return md_download_record(c, ord, n_pairs, res, info, status);
 }
 
 constexpr int kRobustCap = 1024, kRobustMaxLevel = 48;       // frontier capacity per pair and subdivision depth of the robust searches

@@ -2050,6 +2050,190 @@ __global__ __launch_bounds__(64, OBTG_MD_MIN_WAVES) void k_min_dist_wave(const M
   }
 }
 
+// ---- _minDist on curves of DIFFERENT degree: k_min_dist_wave with a control-point count per curve --------------------
+// bezier.py:1283-1408 never asks that the two curves have one degree: poly1 / poly2 are each curve's own control points,
+// t1 = p1idx[0] / c1.deg and t2 = p2idx[0] / c2.deg, and each curve is split by its own de Casteljau.  Here a curve is
+// cpts + 3 * off[i], [3][K_i] with K_i = off[i + 1] - off[i], and a pair's node is c1[3 KA] c2[3 KB].  Everything of
+// k_min_dist_wave that was one K is now per curve: the two hulls of gjkNew (support_pts_wave already scans P1.K and P2.K
+// points in its two half-waves), the half-wave's hull_param_wave (its exact branch i / (K - 1), its weighted one W i / K),
+// the lane maps of the level-parallel split (rl = lane / K, il = lane - rl K: one pair of maps per curve) and the frame,
+// 3 (KA + KB) + F_NSCAL doubles.  The workers take pairs of different sizes from one queue, so a worker's LDS and its
+// frame stack are laid out for the call's largest KA + KB (kt_max: mdm_launch, the one place that sizes both); a pair's
+// own frames are packed at its own stride inside that.  The device functions are k_min_dist_wave's, in its order, so a
+// pair's result, node and gjkNew-call counts are those of the one-lane recursion with (KA, KB).
+// planar (every z of the call is +0): the hulls are declared without a z row (Poly::hasz = 0), which drops the z loads of
+// the support scans and of `point`; sdot then forms x dx + y dy + 0 dz from the literal 0 instead of the stored one: the
+// same operands, so the same bits.
+struct MdmParams {
+    const double* __restrict__ cpts;      // curve i: [3][K_i] at cpts + 3 * off[i]
+    const int* __restrict__ off;          // [n_curves + 1]
+    const int* __restrict__ pa;
+    const int* __restrict__ pb;
+    int n_pairs, kt_max, planar, max_iter, md_cap, max_depth, max_nodes;
+    double eps;
+    double* stack;                        // [workers][max_depth][3 * kt_max + F_NSCAL]
+    double* __restrict__ res;             // [n_pairs][3]
+    int* __restrict__ info;               // [n_pairs][4]
+    const int* __restrict__ order;        // the pairs in the order they are handed out (nullptr = list order)
+    int* queue;                           // the next slot of `order` (zeroed before the launch)
+};
+
+__global__ __launch_bounds__(64, OBTG_MD_MIN_WAVES) void k_min_dist_mixed(const MdmParams p)
+{
+    extern __shared__ double md_lds[];
+    const int lane = threadIdx.x, half = lane >> 5, li = lane & 31;
+    double* st = p.stack + (size_t)blockIdx.x * p.max_depth * (3 * p.kt_max + F_NSCAL);
+    double* sh_e = md_lds + 6 * p.kt_max;       // [2][kMdMaxK]; with sh_q also the scratch rows of a split
+    double* sh_q = sh_e + 2 * kMdMaxK;          // [2][kMdMaxK] (+ 2 more rows: 6 kMdMaxK doubles hold six scratch rows of any K)
+    double* scs = sh_q + 4 * kMdMaxK;           // [max_depth][F_NSCAL] frame scalars
+  for (;;) {
+    // (every lane issues the atomic and every lane stores the results: see the queue pull of k_min_dist_wave)
+    const int ticket = atomicAdd(p.queue, lane == 0 ? 1 : 0);
+    const int slot = __builtin_amdgcn_readfirstlane(ticket);
+    if (slot >= p.n_pairs) break;
+    const int k = p.order ? p.order[slot] : slot;
+    __syncthreads();                             // (one wave per workgroup: the previous pair's LDS reads are done)
+    const int ia = p.pa[k], ib = p.pb[k];
+    const int oa = p.off[ia], ob = p.off[ib];
+    const int KA = p.off[ia + 1] - oa, KB = p.off[ib + 1] - ob, KT = KA + KB, FR = 3 * KT + F_NSCAL;
+    const int rlA = lane / KA, ilA = lane - rlA * KA;     // (row, point) of the lane in curve 1's level-parallel split
+    const int rlB = lane / KB, ilB = lane - rlB * KB;     // ... and in curve 2's
+    const int Kh = half ? KB : KA;                        // the half-wave's curve in the parameter searches
+    double* cur = md_lds;                       // [3 KT] curves of the node being evaluated
+    double* nxt = cur + 3 * p.kt_max;           // [3 KT] curves of the child being built
+    const double* ca = p.cpts + (size_t)3 * oa;
+    const double* cb = p.cpts + (size_t)3 * ob;
+    for (int i = lane; i < 3 * KA; i += kWave) { const double a = ca[i]; st[i] = a; cur[i] = a; }
+    for (int i = lane; i < 3 * KB; i += kWave) { const double b = cb[i]; st[3 * KA + i] = b; cur[3 * KA + i] = b; }
+    if (lane == 0) {
+        scs[F_T1L] = 0; scs[F_T1H] = 1; scs[F_T2L] = 0; scs[F_T2H] = 1;
+        scs[F_ALPHA] = INFINITY; scs[F_STATE] = 0;
+    }
+    __syncthreads();
+    int depth = 0, cur_depth = 0;     // cur_depth: which frame's curves `cur` holds
+    int nodes = 0, calls = 0, dmax = 0, status = OBTG_MD_OK;
+    double r0 = INFINITY, r1 = -1, r2 = -1;
+    bool returning = false;
+    for (;;) {
+        double* f = st + (size_t)depth * FR;
+        double* sc = scs + depth * F_NSCAL;
+        int state = (int)sc[F_STATE];
+        if (!returning && state == 0) {
+            if (depth + 1 > 1000) { r0 = r1 = r2 = -1; returning = true; depth--; if (depth < 0) break; continue; }
+            if (nodes >= p.max_nodes) { status = OBTG_MD_NODE_CAP; break; }
+            nodes++;
+            if (depth + 1 > dmax) dmax = depth + 1;
+            Ctx<MemLds> g;
+            g.mem = MemLds{ cur };
+            g.P1 = Poly{ 0, KA, KA, p.planar ? 0 : 1 };
+            g.P2 = Poly{ 3 * KA, KB, KB, p.planar ? 0 : 1 };
+            g.trace = nullptr; g.trace_cap = 0; g.n_support = 0;
+            Result gr;
+            gjk::run<MemLds, false, true>(g, p.max_iter, p.md_cap, gr);
+            calls++;
+            if (gr.status == OBTG_ST_MD_CAP || gr.status == OBTG_ST_CYCLE) { status = OBTG_MD_GJK_CAP; break; }
+            double lb, t1, t2;
+            if (gr.flag > 0) {
+                lb = gr.dist;
+                const double tp = hull_param_wave(cur + half * 3 * KA, Kh, half ? gr.c2 : gr.c1, sh_e + half * kMdMaxK,
+                                                  sh_q + half * kMdMaxK, li);
+                t1 = __shfl(tp, 0); t2 = __shfl(tp, 32);
+            } else { t1 = 0.5; t2 = 0.5; lb = p.eps; }
+            // _upperbound (bezier.py:1499-1516): the four end-point pairs
+            const double* c1 = cur; const double* c2 = cur + 3 * KA;
+            double dd[4];
+            dd[0] = norm_seq(c1[0], c1[KA], c1[2 * KA], c2[0], c2[KB], c2[2 * KB]);
+            dd[1] = norm_seq(c1[0], c1[KA], c1[2 * KA], c2[KB - 1], c2[2 * KB - 1], c2[3 * KB - 1]);
+            dd[2] = norm_seq(c1[KA - 1], c1[2 * KA - 1], c1[3 * KA - 1], c2[0], c2[KB], c2[2 * KB]);
+            dd[3] = norm_seq(c1[KA - 1], c1[2 * KA - 1], c1[3 * KA - 1], c2[KB - 1], c2[2 * KB - 1], c2[3 * KB - 1]);
+            int am = 0;
+            for (int i = 1; i < 4; ++i) if (dd[i] < dd[am]) am = i;
+            for (int i = 0; i < 4; ++i) if (dd[i] != dd[i]) { am = i; break; }
+            const double ub = dd[am], t1loc = (am >> 1) ? 1.0 : 0.0, t2loc = (am & 1) ? 1.0 : 0.0;
+            double alpha = sc[F_ALPHA], nT1, nT2;
+            if (ub <= alpha) {
+                alpha = ub;
+                nT1 = (1 - t1loc) * sc[F_T1L] + t1loc * sc[F_T1H];
+                nT2 = (1 - t2loc) * sc[F_T2L] + t2loc * sc[F_T2H];
+            } else { nT1 = -1; nT2 = -1; }
+            if (lb >= alpha * (1 - p.eps)) {
+                r0 = alpha; r1 = nT1; r2 = nT2; returning = true; depth--;
+                if (depth < 0) break;
+                continue;
+            }
+            if (depth + 1 >= p.max_depth) { status = OBTG_MD_DEPTH_CAP; r0 = alpha; r1 = nT1; r2 = nT2; break; }
+            if (t1 != t1) t1 = 0;    // Bezier.split: NaN -> 0 (bezier.py:555-557)
+            if (t2 != t2) t2 = 0;
+            wave_sync();
+            if (lane == 0) {
+                sc[F_T1] = t1; sc[F_T2] = t2; sc[F_ALPHA] = alpha; sc[F_RT1] = nT1; sc[F_RT2] = nT2; sc[F_STATE] = 1;
+            }
+            wave_sync();
+            state = 1;
+        }
+        if (returning) {
+            if (r0 < sc[F_ALPHA]) {
+                wave_sync();
+                if (lane == 0) { sc[F_ALPHA] = r0; sc[F_RT1] = r1; sc[F_RT2] = r2; }
+                wave_sync();
+            }
+            returning = false;
+            state = (int)sc[F_STATE];
+        }
+        if (state >= 5) {
+            r0 = sc[F_ALPHA]; r1 = sc[F_RT1]; r2 = sc[F_RT2]; returning = true; depth--;
+            if (depth < 0) break;
+            continue;
+        }
+        // ---- descend into child state-1: (c3,c5) (c3,c6) (c4,c5) (c4,c6)
+        {
+            if (cur_depth != depth) {            // the walk came back up: fetch this frame's curves again
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // other lanes' stores of this frame have landed
+                for (int i = lane; i < 3 * KT; i += kWave) cur[i] = f[i];
+                cur_depth = depth;
+                wave_sync();
+            }
+            const int ch = state - 1, h1 = ch >> 1, h2 = ch & 1;
+            const double t1 = sc[F_T1], t2 = sc[F_T2];
+            double* nf = f + FR;
+            // each curve by its own count: level-parallel over its three rows where they fit a wavefront (3 K <= 64), else a
+            // lane per row -- lanes 0..2 curve 1, lanes 3..5 curve 2, side by side as in k_min_dist_wave.  The two curves write
+            // disjoint ranges of nxt and of the scratch (sh_e .. : 6 kMdMaxK doubles, idle here; curve 1 the first half, curve 2
+            // the second), so nothing orders them against each other.
+            const bool parA = 3 * KA <= kWave, parB = 3 * KB <= kWave;
+            if (parA) split_rows3_wave(cur, KA, t1, h1, nxt, rlA, ilA, sh_e);
+            if (parB) split_rows3_wave(cur + 3 * KA, KB, t2, h2, nxt + 3 * KA, rlB, ilB, sh_e + 3 * kMdMaxK);
+            if (lane < 6 && !(lane < 3 ? parA : parB)) {
+                const bool second = lane >= 3;
+                const int r = second ? lane - 3 : lane, Kr = second ? KB : KA, o = (second ? 3 * KA : 0) + r * Kr;
+                split_row_lds(cur + o, Kr, second ? t2 : t1, second ? h2 : h1, nxt + o, sh_e + (second ? 3 * kMdMaxK : 0) + r * Kr);
+            }
+            wave_sync();
+            for (int i = lane; i < 3 * KT; i += kWave) nf[i] = nxt[i];
+            const double t1len = sc[F_T1H] - sc[F_T1L], t2len = sc[F_T2H] - sc[F_T2L];
+            const double m1 = sc[F_T1L] + t1 * t1len, m2 = sc[F_T2L] + t2 * t2len;
+            const double a_in = sc[F_ALPHA];
+            const double n1l = h1 ? m1 : sc[F_T1L], n1h = h1 ? sc[F_T1H] : m1;
+            const double n2l = h2 ? m2 : sc[F_T2L], n2h = h2 ? sc[F_T2H] : m2;
+            wave_sync();
+            if (lane == 0) {
+                double* ns = sc + F_NSCAL;
+                ns[F_T1L] = n1l; ns[F_T1H] = n1h; ns[F_T2L] = n2l; ns[F_T2H] = n2h;
+                ns[F_ALPHA] = a_in; ns[F_STATE] = 0;
+                sc[F_STATE] = state + 1;
+            }
+            // the child is evaluated next: its curves become `cur`
+            double* tsw = cur; cur = nxt; nxt = tsw;
+            depth++;
+            cur_depth = depth;
+            wave_sync();
+        }
+    }
+    p.res[3 * k] = r0; p.res[3 * k + 1] = r1; p.res[3 * k + 2] = r2;
+    if (p.info) { p.info[4 * k] = nodes; p.info[4 * k + 1] = calls; p.info[4 * k + 2] = dmax; p.info[4 * k + 3] = status; }
+  }
+}
+
 // ---- _minDist, four children at a time (round 5) -------------------------------------------------------------------
 // bezier.py:1283-1408 calls itself on ALL four children of a node it does not cut off -- the cut (lb >= alpha (1 - eps)) is
 // taken inside the child, after the child's own gjkNew call and end-point distances -- so a child's gjkNew result, its split
@@ -4130,6 +4314,57 @@ int launch_min_dist(obtg_ctx* c, const double* d_curves, int K, const int* d_pa,
         hipLaunchKernelGGL(k_min_dist_wave, dim3(L.grid), dim3(L.block), L.lds, c->stream, p);
     else
         hipLaunchKernelGGL(k_min_dist, dim3(L.grid), dim3(L.block), 0, c->stream, p);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
+// The launch of obtg_min_dist_mixed for one call: its grid, LDS and frame stack.  As md_launch, the ONE place that decides, so
+// that min_dist_mixed_stack_doubles (the allocation) and launch_min_dist_mixed (the launch) cannot disagree.  kt_max: the largest
+// KA + KB among the call's pairs -- the workers take pairs of every size from one queue, so each is laid out for that one.
+// One form, k_min_dist_mixed (one pair per wavefront at a time).  Its LDS is 6 kt_max doubles of curves, 6 kMdMaxK of scratch and
+// max_depth frames of scalars: 13.1 KB at kt_max = 27 and max_depth 128, 14.8 KB at 64, so the worker count stays the register
+// bound's (OBTG_MD_MIN_WAVES per SIMD) up to a max_depth of about 200, then min_dist_workers thins them out; beyond 48 KB the
+// launch raises the kernel's limit (allow_lds), and a depth whose scalars pass kLdsLaunchMax (max_depth above 760) is refused.
+static_assert(kMdMaxK == kMdMaxCurveK, "the host checks obtg_min_dist_mixed's curve lengths against kMdMaxCurveK");
+struct MdmLaunch {
+    bool ok;
+    unsigned grid, block;
+    size_t lds;
+    size_t stack_doubles;          // the whole launch: a stack per worker wave, max_depth frames of 3 kt_max + F_NSCAL
+};
+static MdmLaunch mdm_launch(const obtg_ctx* c, int kt_max, int max_depth, int n_pairs)
+{
+    MdmLaunch L;
+    L.lds = sizeof(double) * ((size_t)6 * kt_max + 6 * kMdMaxK + (size_t)max_depth * F_NSCAL);
+    L.ok = kt_max >= 4 && kt_max <= 2 * kMdMaxK && max_depth >= 1 && L.lds <= kLdsLaunchMax;
+    L.grid = (unsigned)min_dist_workers(c, n_pairs, L.lds, OBTG_MD_MIN_WAVES);
+    L.block = kWave;
+    L.stack_doubles = (size_t)L.grid * max_depth * (3 * kt_max + F_NSCAL);
+    return L;
+}
+
+// doubles of frame stack obtg_min_dist_mixed has to provide (0: nothing to launch, or a shape launch_min_dist_mixed refuses)
+size_t min_dist_mixed_stack_doubles(const obtg_ctx* c, int kt_max, int max_depth, int n_pairs)
+{
+    if (n_pairs <= 0) return 0;
+    const MdmLaunch L = mdm_launch(c, kt_max, max_depth, n_pairs);
+    return L.ok ? L.stack_doubles : 0;
+}
+
+int launch_min_dist_mixed(obtg_ctx* c, const double* d_cpts, const int* d_off, int kt_max, const int* d_pa, const int* d_pb,
+                          int n_pairs, double eps, int max_iter, int md_cap, int max_depth, int max_nodes, double* d_stack,
+                          double* d_res, int* d_info, const int* d_order, int* d_queue, bool planar)
+{
+    if (n_pairs <= 0) return OBTG_OK;
+    const MdmLaunch L = mdm_launch(c, kt_max, max_depth, n_pairs);
+    if (!L.ok) return OBTG_ERR_UNSUPPORTED;
+    if (!d_queue) return OBTG_ERR_ARG;
+    MdmParams p{ d_cpts, d_off, d_pa, d_pb, n_pairs, kt_max, planar ? 1 : 0, max_iter, md_cap, max_depth, max_nodes, eps, d_stack,
+                 d_res, d_info, d_order, d_queue };
+    ScopedKernelTimer t(c, OBTG_K_MIN_DIST);
+    OBTG_HIP(c, hipMemsetAsync(d_queue, 0, sizeof(int), c->stream));
+    OBTG_HIP(c, allow_lds(k_min_dist_mixed, L.lds));
+    hipLaunchKernelGGL(k_min_dist_mixed, dim3(L.grid), dim3(L.block), L.lds, c->stream, p);
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;
 }

@@ -24,6 +24,7 @@ static inline bool nc_in_dyn(int nc)  { return false OBTG_NC_DYN(OBTG_NC_EQ_); }
 static inline bool nc_in_elev(int nc) { return false OBTG_NC_ELEV(OBTG_NC_EQ_); }
 
 constexpr int kWave = 64;
+constexpr int kMdMaxCurveK = 32;     // control points per curve of the branch & bound searches (gjk_kernels.hip: kMdMaxK), for the host's checks
 constexpr int kNeedBatch = 1077;      // internal launcher result: "this kernel needs the finite-difference batch in memory"
 constexpr int kMaxGenericLen = 1024;  // longest Bernstein coefficient vector of the generic kernels
 
@@ -81,6 +82,7 @@ struct KernelStat {
 //   obtg_gjk_swarm           holds 3 (WS_INFO) -> launch_gjk_swarm takes 7 (WS_L_CHANGED) and, under OBTG_TIMELINE, 6
 enum WsSlot {
     WS_POLY_OFF = 0,      // int[n_poly + 1]: polygon offsets
+    WS_CURVE_OFF = 0,     //   int[n_curves + 1]: control-point offsets of obtg_min_dist_mixed's curves
     WS_ARG_A = 0,         //   first small operand beside ws_in / ws_in2: one_span (obtg_one_vs_many_min_spans[_dev]), pert_row (obtg_temporal_sep_fd), span (obtg_bern_restrict)
     WS_PAIR_A = 1,        // int[n_pairs]: first operand of every pair
     WS_ARG_B = 1,         //   second small operand: many_span, pert_col, target (the same three calls)
@@ -311,6 +313,10 @@ int launch_min_dist(obtg_ctx* c, const double* d_curves, int K, const int* d_pa,
                     int n_pairs, double eps, int max_iter, int md_cap, int max_depth, int max_nodes,
                     double* d_stack, double* d_res, int* d_info, const int* d_order = nullptr, int* d_queue = nullptr,
                     bool planar = false);      // planar: every control point of every curve has z == 0 (the caller has looked)
+// curves of different degree: curve i is [3][K_i] at d_cpts + 3 * d_off[i]; kt_max: the largest KA + KB among the pairs
+int launch_min_dist_mixed(obtg_ctx* c, const double* d_cpts, const int* d_off, int kt_max, const int* d_pa, const int* d_pb,
+                          int n_pairs, double eps, int max_iter, int md_cap, int max_depth, int max_nodes, double* d_stack,
+                          double* d_res, int* d_info, const int* d_order, int* d_queue, bool planar);
 int launch_min_dist_robust(obtg_ctx* c, const double* d_curves, int K, const int* d_pa, const int* d_pb, int n_pairs,
                            double eps, int max_nodes, int max_level, int cap, double* d_frontier, double* d_res, int* d_info);
 int launch_min_dist2poly(obtg_ctx* c, const double* d_curves, int K, const double* d_soa,
@@ -328,6 +334,7 @@ int launch_min_dist2poly_robust(obtg_ctx* c, const double* d_curves, int K, cons
 double square_as_python(double x);
 double cube_as_python(double x);       // x**3 likewise (bezier.py:1468: eps**3)
 size_t min_dist_stack_doubles(const obtg_ctx* c, int K, int max_depth, int n_pairs, bool planar);   // whole launch, the form launch_min_dist runs
+size_t min_dist_mixed_stack_doubles(const obtg_ctx* c, int kt_max, int max_depth, int n_pairs);   // whole launch, as launch_min_dist_mixed lays it out
 size_t min_dist2poly_stack_doubles(int K, int max_depth, int n_pairs, int max_poly_K, bool planar);   // whole launch, the form launch_min_dist2poly runs
 int min_dist_workers(const obtg_ctx* c, int n_pairs, size_t lds_per_wave, int waves_per_simd);   // worker waves of the queue forms
 

@@ -175,34 +175,56 @@ def _raise_first_md(status):
         bez._raise_md(int(status[bad[0]]))
 
 
+def _min_dist_call(curves, pa, pb, robust):
+    """The `_minDist` sweep of the spatial-separation calls: curves is an array [n][3][K] (obtg_min_dist[_robust], as ever) or,
+    where degrees differ, a list of [3][K_i] arrays -- obtg_min_dist_mixed, or for robust=True the curves elevated to the
+    highest degree (bezier.elevated_stack) through obtg_min_dist_robust."""
+    ctx = _capi.scratch_context()
+    if robust:
+        stack = bez.elevated_stack(curves) if isinstance(curves, list) else curves
+        return ctx.min_dist_robust(stack, pa, pb, eps=1e-9, max_nodes=400000)
+    call = ctx.min_dist_mixed if isinstance(curves, list) else ctx.min_dist
+    return call(curves, pa, pb, eps=1e-9, max_depth=128, max_nodes=4000000)
+
+
 def _spatial_jac_plan(Y, numVeh, dim, obstacle_curves):
     """The curve and pair lists of ONE `obtg_min_dist` call that yields the 2-point Jacobian of
     spatialSeparationConstraints (optimization.py:109-133): the base evaluation's C(n, 2) pairs of the n = numVeh +
     obstacles curves of row 0 of Y, then, for every finite-difference row k + 1, the pairs that contain a vehicle whose
     control points differ from row 0's, with that vehicle's perturbed curve appended to the curve list.
-    Y: [n_x + 1][numVeh * dim][deg + 1]; obstacle_curves: padded [3][deg + 1] arrays.
+    Y: [n_x + 1][numVeh * dim][deg + 1]; obstacle_curves: padded [3][K_o] arrays, of any degree each.
     Returns (stack [n_curves][3][deg + 1], pa, pb, P, col, row, pos): entry e of the call's extra pairs is base pair
     row[e] re-evaluated for variable col[e] at position pos[e] of the pair list.  Pairs of a column come in base-pair
-    order, columns in order (array form of the loops it replaced: tests/test_host_logic.py holds it to them)."""
+    order, columns in order (array form of the loops it replaced: tests/test_host_logic.py holds it to them).
+    Where an obstacle's degree is not the vehicles', `stack` is the LIST of the same curves in the same order instead
+    (obtg_min_dist_mixed's operand); the pair lists do not depend on degrees."""
     nx = Y.shape[0] - 1
     K = Y.shape[2]
     n = numVeh + len(obstacle_curves)
     Yv = Y.reshape(nx + 1, numVeh, dim, K)
-    base = np.zeros((n, 3, K))
-    base[:numVeh, :dim, :] = Yv[0]
-    for o, c in enumerate(obstacle_curves):
-        base[numVeh + o] = c
     changed = np.any(Yv[1:] != Yv[0], axis=(2, 3))              # [n_x][numVeh]
     ck, cv = np.nonzero(changed)                                # (column, vehicle), columns ascending, vehicles ascending
     extra = np.zeros((ck.size, 3, K))
     extra[:, :dim, :] = Yv[ck + 1, cv]
+    if any(c.shape[1] != K for c in obstacle_curves):
+        base = np.zeros((numVeh, 3, K))
+        base[:, :dim, :] = Yv[0]
+        base = list(base) + list(obstacle_curves)
+        extra = list(extra)
+        join = lambda: base + extra
+    else:
+        base = np.zeros((n, 3, K))
+        base[:numVeh, :dim, :] = Yv[0]
+        for o, c in enumerate(obstacle_curves):
+            base[numVeh + o] = c
+        join = lambda: np.concatenate((base, extra))
     # The pair lists depend on WHICH vehicles every column moves, not on the values: an SLSQP run asks for the same pattern at
     # every iterate, so the lists of the last pattern are kept (round 6: building them was 16 of the provider's 35 ms at C5 size).
     memo = _spatial_jac_plan.memo
     pattern = (n, numVeh, changed.shape, changed.tobytes())
     if memo.get('pattern') == pattern:
         pa, pb, P, col, row, pos = memo['lists']
-        return np.concatenate((base, extra)), pa, pb, P, col, row, pos
+        return join(), pa, pb, P, col, row, pos
     pa0, pb0 = np.triu_indices(n, 1)                            # i < j, lexicographic: the reference's pair loop
     P = pa0.size
     new_id = np.full((nx, n), -1, dtype=np.int64)               # curve index of vehicle v's perturbed copy in column k
@@ -231,7 +253,7 @@ def _spatial_jac_plan(Y, numVeh, dim, obstacle_curves):
     pb = np.concatenate((pb0, np.where(nb >= 0, nb, ib))).astype(np.int32)
     pos = P + np.arange(col.size)
     memo['pattern'], memo['lists'] = pattern, (pa, pb, P, col, row, pos)
-    return np.concatenate((base, extra)), pa, pb, P, col, row, pos
+    return join(), pa, pb, P, col, row, pos
 
 
 _spatial_jac_plan.memo = {}
@@ -506,11 +528,13 @@ class BezOptimization(object):
         y = self.reshapeVector(x)
         curves = [bez.Bezier(y[i * dim:(i + 1) * dim, :]) for i in range(numVeh)] + list(self.shapeObstacles)
         n = len(curves)
-        stack = np.stack([c._padded() for c in curves])
+        stack = [c._padded() for c in curves]
+        if all(c.shape[1] == stack[0].shape[1] for c in stack):
+            stack = np.stack(stack)
         pa, pb = np.triu_indices(n, 1)                              # i < j, lexicographic: the reference's pair loop
+        r = _min_dist_call(stack, pa, pb, robust)
         if robust:
-            return _capi.scratch_context().min_dist_robust(stack, pa, pb, eps=1e-9, max_nodes=400000)['res'] - maxSep
-        r = _capi.scratch_context().min_dist(stack, pa, pb, eps=1e-9, max_depth=128, max_nodes=4000000)
+            return r['res'] - maxSep
         _raise_first_md(r['status'])
         return r['res'] - maxSep
 
@@ -523,13 +547,10 @@ class BezOptimization(object):
         Y = self.reshapeVectors(X)
         obstacles = list(self.shapeObstacles) if self.shapeObstacles is not None else []
         stack, pa, pb, P, t_col, t_row, t_pos = _spatial_jac_plan(Y, numVeh, dim, [c._padded() for c in obstacles])
-        if robust:
-            res = _capi.scratch_context().min_dist_robust(stack, pa, pb, eps=1e-9, max_nodes=400000)['res']
-        else:
-            r = _capi.scratch_context().min_dist(stack, pa, pb, eps=1e-9, max_depth=128, max_nodes=4000000)
-            if np.any(r['status'] != _capi.MD_OK):
-                return None
-            res = r['res']
+        r = _min_dist_call(stack, pa, pb, robust)
+        if not robust and np.any(r['status'] != _capi.MD_OK):
+            return None
+        res = r['res']
         F = np.repeat((res[:P] - maxSep)[None], X.shape[0], axis=0)          # [n_x + 1][P][3]
         F[t_col + 1, t_row] = res[t_pos] - maxSep
         return F
@@ -552,11 +573,9 @@ class BezOptimization(object):
         nx = X.shape[1]
         obstacles = list(self.shapeObstacles) if self.shapeObstacles is not None else []
         stack, pa, pb, P, t_col, t_row, t_pos = _spatial_jac_plan(Y, numVeh, dim, [c._padded() for c in obstacles])
-        if robust:
-            res = _capi.scratch_context().min_dist_robust(stack, pa, pb, eps=1e-9, max_nodes=400000)['res']
-        else:
-            r = _capi.scratch_context().min_dist(stack, pa, pb, eps=1e-9, max_depth=128, max_nodes=4000000)
-            res = r['res']
+        r = _min_dist_call(stack, pa, pb, robust)
+        res = r['res']
+        if not robust:
             if on_cap == 'nan':
                 res = np.where((r['status'] != 0)[:, None], np.nan, res)
             else:

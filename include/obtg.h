@@ -93,7 +93,9 @@ const char* obtg_strerror(int code);
  *      takes the structured step where it applies: the same arrays with the same bits, so no meaning changed.
  *      Later, still 7: new: the envelope Jacobian of the true-minimum rows, obtg_temporal_sep_true_min_jac[_dev] (timed
  *      under OBTG_K_TEMPORAL_SEP).
- *      Later, still 7: new: obtg_min_dist_mixed, `_minDist` on curves of different degree (timed under OBTG_K_MIN_DIST). */
+ *      Later, still 7: new: obtg_min_dist_mixed, `_minDist` on curves of different degree (timed under OBTG_K_MIN_DIST).
+ *      Later, still 7: new: the true speed rows obtg_speed_true_min[_dev] and their envelope Jacobian
+ *      obtg_speed_true_min_jac[_dev] (timed under OBTG_K_SPEED). */
 #define OBTG_ABI_VERSION 7
 int obtg_abi_version(void);
 
@@ -594,6 +596,42 @@ int obtg_temporal_sep_true_min_jac(obtg_ctx*, const double* Y, int B, double max
                                    double* jac /*[B][P][d][n+1]*/);
 int obtg_temporal_sep_true_min_jac_dev(obtg_ctx*, const double* dY, int B, double max_sep, double eps_rel, int max_nodes,
                                        double* d_out, double* d_t_star, int* d_status, double* d_jac);
+/* The tight continuous-time speed bound: for every row b and vehicle v the MINIMUM over t in [0, 1] of
+ *     q(t) = sign * (v.diff().normSquare())(t) + offset,   (sign, offset) = (-1, +bound^2) for is_max, (+1, -bound^2) otherwise
+ * (optimization.py:349-422 bounds q from below by its elevated control points): feasible iff >= 0 for either bound; for is_max
+ * it is bound^2 - max over t of (d/2)|dv/dt|^2.  normSquare's (d/2) factor and Python's bound**2 are kept.  DEG_ELEV does not
+ * enter and the context's R is not read.  The 2n+1 coefficients are the bits of obtg_speed's rows on a context with
+ * DEG_ELEV = 0 (diff with its trailing elev(1), the product, fma(sign, c, offset)), so out, t_star, status are the bits of
+ * obtg_bern_extrema(eps_abs = 0, want_max = 0) on those rows: out[B][N], t_star[B][N], status[B][N] as there.  An end
+ * coefficient that is the row's smallest is returned as is (t_star 0 or 1).  A row with a non-finite coefficient: val and
+ * t_star NaN, status OBTG_MD_OK.  tf <= 0 is the caller's business, as in obtg_speed.  Degrees with a specialised kernel
+ * (obtg_fast_kernels & 1) form the coefficients in registers, one launch; other degrees up to 31 go through a workspace of
+ * obtg_speed's R = 0 rows (two launches; the context's DEG_ELEV and tables are not touched); above 31: OBTG_ERR_UNSUPPORTED.
+ * t_star and status are nullable.  _dev: dY may be NULL inside an obtg_fd_view (the batch is then written once per view);
+ * d_tf is device memory, [B]. */
+int obtg_speed_true_min(obtg_ctx*, const double* Y, const double* tf /*[B]*/, int B, double bound, int is_max, double eps_rel,
+                        int max_nodes, double* out /*[B][N]*/, double* t_star /*[B][N], nullable*/, int* status /*[B][N], nullable*/);
+int obtg_speed_true_min_dev(obtg_ctx*, const double* dY, const double* d_tf, int B, double bound, int is_max, double eps_rel,
+                            int max_nodes, double* d_out, double* d_t_star, int* d_status);
+/* obtg_speed_true_min with its envelope (Danskin) Jacobian.  out, t_star, status are, bit for bit, those of
+ * obtg_speed_true_min with the same arguments.  With n = deg, d = dim, T = tf[b], w = B^(n-1)(t_star) and the velocity
+ * c'_c(t_star) = (n/T) sum_i w_i (P_c,i+1 - P_c,i) of vehicle v:
+ *     jac[B][N][d][n+1]:  jac[c][i] = sign * d * c'_c(t_star) * (n/T) * (w_(i-1) - w_i),   w_(-1) = w_n = 0
+ *     jac_tf[B][N] (nullable):  -2 (q(t_star) - offset) / T, q(t_star) - offset = sign (d/2) |c'(t_star)|^2 from the same w
+ * -- the partial derivatives of q AT THE RETURNED t_star with respect to the vehicle's own control points Y[v*d + c][i] and to
+ * tf at fixed control points; the derivative of min_t q wherever the minimiser is unique (obtg_temporal_sep_true_min_jac says
+ * what it is otherwise, and how close t_star is to the minimiser).  t_star = 0 leaves columns 0 and 1 as the only non-zero
+ * ones, t_star = 1 columns n-1 and n.  A row with a non-finite coefficient gets a NaN block and a NaN jac_tf (status
+ * OBTG_MD_OK); with another status the block is still the derivative at the returned t_star.  Every multiply-add is an explicit
+ * fma (csrc/bern_device.h speed_envelope_block): a block depends on the vehicle's control points, tf and t_star alone, not on
+ * the entry point (host and _dev: same bits) or the kernel form -- in the search launch where the shape has a specialised
+ * kernel, else (and on every shape in a context created under OBTG_TRUE_MIN_JAC_FUSED=0) the value path and one more launch
+ * from Y, tf and t_star.  Degrees above 31: OBTG_ERR_UNSUPPORTED.  _dev: dY may be NULL inside an obtg_fd_view. */
+int obtg_speed_true_min_jac(obtg_ctx*, const double* Y, const double* tf /*[B]*/, int B, double bound, int is_max, double eps_rel,
+                            int max_nodes, double* out /*[B][N]*/, double* t_star /*[B][N], nullable*/, int* status /*[B][N], nullable*/,
+                            double* jac /*[B][N][d][n+1]*/, double* jac_tf /*[B][N], nullable*/);
+int obtg_speed_true_min_jac_dev(obtg_ctx*, const double* dY, const double* d_tf, int B, double bound, int is_max, double eps_rel,
+                                int max_nodes, double* d_out, double* d_t_star, int* d_status, double* d_jac, double* d_jac_tf);
 
 /* ---- single-curve Bernstein algebra (the Bezier object's methods, batched over rows) ----
  * obtg_bern_elev:   Bezier.elev(R)      bezier.py:469-495   in[rows][n+1]   -> out[rows][n+R+1]

@@ -114,6 +114,10 @@ _SIGNATURES = {
     "obtg_temporal_sep_true_min_dev": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
     "obtg_temporal_sep_true_min_jac": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp]),
     "obtg_temporal_sep_true_min_jac_dev": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp]),
+    "obtg_speed_true_min": (_i, [_vp, _vp, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp]),
+    "obtg_speed_true_min_dev": (_i, [_vp, _vp, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp]),
+    "obtg_speed_true_min_jac": (_i, [_vp, _vp, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_speed_true_min_jac_dev": (_i, [_vp, _vp, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "obtg_bern_elev": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "obtg_bern_diff": (_i, [_vp, _vp, _i, _i, _d, _vp]),
     "obtg_bern_mul": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
@@ -635,6 +639,45 @@ class Context(object):
         self._check(self._lib.obtg_speed(self._h, _ptr(Y), _ptr(tf), B, float(bound), int(bool(is_max)), _ptr(out)),
                     "obtg_speed")
         return out
+
+    def speed_true_min(self, Y, tf, bound, is_max, eps_rel=1e-9, max_nodes=100000):
+        """Per vehicle the true minimum over t in [0, 1] of the speed row's polynomial sign (d/2)|v'|^2 + offset -- the polynomial
+        speed(Y, tf, bound, is_max) holds the control points of (obtg_speed_true_min; DEG_ELEV does not enter):
+        dict(val[B][N], t_star[B][N], status[B][N] as MD_*)."""
+        Y, B = self._rows(Y)
+        tf = self._tf(tf, B)
+        out = pinned_empty((B, self.n_veh))
+        t_star = np.empty((B, self.n_veh))
+        status = np.zeros((B, self.n_veh), np.int32)
+        self._check(self._lib.obtg_speed_true_min(self._h, _ptr(Y), _ptr(tf), B, float(bound), int(bool(is_max)), float(eps_rel),
+                                                  int(max_nodes), _ptr(out), _ptr(t_star), _ptr(status)), "obtg_speed_true_min")
+        return dict(val=out, t_star=t_star, status=status)
+
+    def speed_true_min_dev(self, dY, d_tf, B, bound, is_max, d_out, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
+        self._check(self._lib.obtg_speed_true_min_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(bound), int(bool(is_max)),
+                                                      float(eps_rel), int(max_nodes), _vp(d_out), _vp(d_t_star), _vp(d_status)),
+                    "obtg_speed_true_min_dev")
+
+    def speed_true_min_jac(self, Y, tf, bound, is_max, eps_rel=1e-9, max_nodes=100000):
+        """speed_true_min with its envelope Jacobian (obtg_speed_true_min_jac): dict(val, t_star, status -- the bits of
+        speed_true_min --, jac[B][N][dim][deg+1]: d/d(the vehicle's own control points) of its polynomial at t_star,
+        jac_tf[B][N]: d/dtf at fixed control points)."""
+        Y, B = self._rows(Y)
+        tf = self._tf(tf, B)
+        out = pinned_empty((B, self.n_veh))
+        t_star, jac_tf = np.empty((B, self.n_veh)), np.empty((B, self.n_veh))
+        status = np.zeros((B, self.n_veh), np.int32)
+        jac = pinned_empty((B, self.n_veh, self.dim, self.deg + 1))
+        self._check(self._lib.obtg_speed_true_min_jac(self._h, _ptr(Y), _ptr(tf), B, float(bound), int(bool(is_max)), float(eps_rel),
+                                                      int(max_nodes), _ptr(out), _ptr(t_star), _ptr(status), _ptr(jac), _ptr(jac_tf)),
+                    "obtg_speed_true_min_jac")
+        return dict(val=out, t_star=t_star, status=status, jac=jac, jac_tf=jac_tf)
+
+    def speed_true_min_jac_dev(self, dY, d_tf, B, bound, is_max, d_out, d_jac, d_jac_tf=None, d_t_star=None, d_status=None,
+                               eps_rel=1e-9, max_nodes=100000):
+        self._check(self._lib.obtg_speed_true_min_jac_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(bound), int(bool(is_max)),
+                                                          float(eps_rel), int(max_nodes), _vp(d_out), _vp(d_t_star), _vp(d_status),
+                                                          _vp(d_jac), _vp(d_jac_tf)), "obtg_speed_true_min_jac_dev")
 
     def ang_rate(self, Y, tf, max_rate):
         Y, B = self._rows(Y)

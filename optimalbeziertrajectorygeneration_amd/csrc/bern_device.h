@@ -243,6 +243,81 @@ __device__ __forceinline__ void envelope_block(const double* __restrict__ ya, co
     }
 }
 
+// The source curve of a speed row -- Bezier.diff(): (n/T)(P_(i+1) - P_i), then elev(1) back to degree n (bezier.py:497-519) --
+// in the arithmetic of k_normsq_elev's speed path, for the kernels that must reproduce obtg_speed's R = 0 rows bit for bit
+// (obtg_speed_true_min).  That path writes  t_c = p_c * (-val) + p_(c+1) * val  and  d_c = t_(c-1) * (c/n) + t_c * ((n-c)/n)
+// and leaves the contraction to the compiler, which fuses ONE product of each sum into an fma and rounds the other -- the
+// one with fewer uses, the first on a tie, decided sum by sum in index order, so which one depends on what the sums around
+// it share.  What that comes to, for every count of OBTG_NC_SEP and both dimensions (read off the kernel's instructions):
+//   t_c = fma(-val, p_c, val * p_(c+1))   for even c < n - 1,
+//   t_c = fma(val, p_(c+1), -(val * p_c))  for odd c and for c = n - 1          (val * p_k is one product, shared by t_(k-1), t_k)
+//   d_c = fma(c/n, t_(c-1), t_c * ((n-c)/n)),  but  fma((n-c)/n, t_c, t_(c-1) * (c/n))  at c = (n + 1) / 2, where that product
+//         is d_(c-1)'s as well.
+// Here every fma is explicit and every other product stands alone: the same bits under `fp contract(fast)` and `(off)`.
+// tests/test_gpu_speed_true_min.py holds the two kernels to each other, so a compiler that fuses the other way shows there.
+template <int NC>
+__device__ __forceinline__ void diff_elev1_speed_rows(const double (&p)[NC], double val, double (&d)[NC])
+{
+    constexpr int N = NC - 1;
+    double t[NC];
+#pragma unroll
+    for (int c = 0; c < N; ++c)
+        t[c] = ((c & 1) || c == N - 1) ? __builtin_fma(val, p[c + 1], -(val * p[c])) : __builtin_fma(-val, p[c], val * p[c + 1]);
+    d[0] = t[0];
+    d[N] = t[N - 1];
+#pragma unroll
+    for (int c = 1; c < N; ++c) {
+        const double r0 = (double)c / (double)N, r1 = (double)(N - c) / (double)N;
+        d[c] = (2 * c == N + 1) ? __builtin_fma(r1, t[c], t[c - 1] * r0) : __builtin_fma(r0, t[c - 1], t[c] * r1);
+    }
+}
+
+// Envelope block of one vehicle's speed row at parameter t: the partial derivatives of q(t) = sign (DIM/2) |c'(t)|^2 + offset,
+// c' = dc/dtime on a span of T, with respect to the vehicle's own control points and to T (obtg_speed_true_min_jac).
+// With n = nc - 1, w = B^(n-1)(t) and c'_c(t) = (n/T) sum_i w_i (P_c,i+1 - P_c,i):
+//     out[c][i] = sign DIM c'_c(t) (n/T) (w_(i-1) - w_i),  w_(-1) = w_n = 0;     returns dq/dT = -2 (q(t) - offset) / T,
+// q(t) - offset evaluated here from the same w.  y: the vehicle's [DIM][nc] control points.  Written as envelope_block is:
+// the basis from the de Casteljau recurrence on the basis, every multiply-add an explicit fma; contraction is switched off
+// inside the function, so the other products and the differences of the weights stay as written -- the same arithmetic
+// whatever the including unit's mode, for every NCMAX >= nc, wherever it is inlined.
+// t = 0 / t = 1 leave columns (0, 1) / (n - 1, n) as the only non-zero ones; a NaN t gives a NaN block and a NaN dq/dT.
+template <int NCMAX, int DIM>
+__device__ __forceinline__ double speed_envelope_block(const double* __restrict__ y, int nc, double T, double sign, double t,
+                                                       double* __restrict__ out)
+{
+    // (w_0 = s * w_0 is a bare product and w_0 - w_1 a difference of it: with contraction allowed the compiler fuses the two
+    // where it sees both -- the fused kernel, nc known -- and not behind the `r < n` selects of the any-degree one)
+#pragma clang fp contract(off)
+    const int n = nc - 1;
+    const double s = 1.0 - t;
+    double w[NCMAX];                       // w[0 .. n): B^(n-1)(t); w[n ..] stay zero
+#pragma unroll
+    for (int i = 0; i < NCMAX; ++i) w[i] = i == 0 ? 1.0 : 0.0;
+#pragma unroll
+    for (int r = 1; r < NCMAX - 1; ++r)
+        if (r < n) {
+#pragma unroll
+            for (int i = r; i >= 1; --i) w[i] = __builtin_fma(t, w[i - 1], s * w[i]);
+            w[0] = s * w[0];
+        }
+    const double nT = (double)n / T;
+    double ss = 0.0;
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+        double dl = 0.0;
+#pragma unroll
+        for (int i = 0; i < NCMAX - 1; ++i)
+            if (i < n) dl = __builtin_fma(w[i], y[c * nc + i + 1] - y[c * nc + i], dl);
+        const double v = nT * dl;
+        ss = c == 0 ? v * v : __builtin_fma(v, v, ss);
+        const double kd = (sign * (double)DIM) * (v * nT);
+#pragma unroll
+        for (int i = 0; i < NCMAX; ++i)
+            if (i < nc) out[c * nc + i] = kd * ((i == 0 ? 0.0 : w[i - 1]) - (i < n ? w[i] : 0.0));
+    }
+    return (-2.0 * ((sign * (0.5 * (double)DIM)) * ss)) / T;
+}
+
 // write a full [n_valid][LR] tile (pitch TP) as one contiguous run of n_valid*LR doubles
 template <int LR, int TP>
 __device__ __forceinline__ void flush_full(const double* __restrict__ tile, double* __restrict__ gout,

@@ -1500,6 +1500,26 @@ int launch_speed(obtg_ctx* c, const double* dY, const double* d_tf, int B, doubl
     return OBTG_OK;
 }
 
+// obtg_speed's rows AT R = 0 from the any-degree kernel, whatever the context's DEG_ELEV is (the route of
+// obtg_speed_true_min for degrees off the fast-kernel list): the launch a context with R = 0 makes, bit for bit; the
+// context is not touched
+int launch_speed_rows_r0_generic(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max, double* d_out)
+{
+    if (B <= 0) return OBTG_OK;
+    if (2 * c->deg + 1 > kMaxGenericLen) return OBTG_ERR_UNSUPPORTED;
+    GenParams g{};
+    int rc = gen_common(c, g, 0);
+    if (rc) return rc;
+    const double b2 = square_as_python(bound);
+    g.Y = dY; g.tf = d_tf; g.out = d_out; g.item_begin = 0; g.item_count = c->n_veh; g.B = B;
+    g.sign = is_max ? -1.0 : 1.0; g.offset = is_max ? b2 : -b2; g.min_only = 0;
+    const size_t lds = sizeof(double) * ((size_t)2 * c->dim * (c->deg + 1) + 2 * c->deg + 1);
+    ScopedKernelTimer t(c, OBTG_K_SPEED);
+    hipLaunchKernelGGL(k_generic_normsq_elev<1>, dim3((unsigned)((size_t)B * c->n_veh)), dim3(kWave), lds, c->stream, g);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
 template <int NC>
 static int launch_dyn_t(obtg_ctx* c, const AngParams& p, int kernel_id)
 {

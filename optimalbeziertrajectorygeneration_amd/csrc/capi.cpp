@@ -236,6 +236,7 @@ const char* obtg_abi_symbols(void)
         "obtg_fd_batch_dev\0obtg_fd_view_begin\0obtg_fd_view_begin_rows\0obtg_fd_view_end\0obtg_fd_forms_on_the_fly\0obtg_pair_sweep_fd_dev\0obtg_dynamics_fd_dev\0obtg_gjk_pairs\0obtg_ctx_set_polygons\0obtg_ctx_set_hull_pairs\0"
         "obtg_ctx_set_fd_dedup\0obtg_ctx_set_fd_view_structured\0obtg_ctx_set_gjk_history\0obtg_pair_sweep_dev\0obtg_constraint_sweep_dev\0obtg_constraint_sweep_fd_structured_dev\0obtg_constraint_sweep_fd_structured_rows_dev\0obtg_gjk_swarm_dev\0obtg_gjk_swarm\0obtg_min_dist\0obtg_min_dist_mixed\0obtg_min_dist_robust\0obtg_min_dist2poly\0obtg_min_dist2poly_robust\0obtg_gjk_true_pairs\0obtg_coll_check\0obtg_coll_check2poly\0"
         "obtg_bern_extrema\0obtg_bern_extrema_dev\0obtg_temporal_sep_true_min\0obtg_temporal_sep_true_min_dev\0obtg_temporal_sep_true_min_jac\0obtg_temporal_sep_true_min_jac_dev\0"
+        "obtg_speed_true_min\0obtg_speed_true_min_dev\0obtg_speed_true_min_jac\0obtg_speed_true_min_jac_dev\0"
         "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_restrict\0obtg_bern_eval\0"
         "obtg_euclidean_obj\0obtg_accel_obj\0obtg_jerk_obj\0"
         "obtg_temporal_sep_jac\0obtg_temporal_sep_jac_dev\0obtg_speed_jac\0obtg_speed_jac_dev\0obtg_ang_rate_jac\0obtg_ang_rate_jac_dev\0obtg_euclidean_grad\0obtg_deriv_energy_grad\0"
@@ -270,7 +271,7 @@ int obtg_ctx_create(obtg_ctx** out, int n_veh, int dim, int deg, int deg_elev, i
     { const char* e = getenv("OBTG_ZERO_COPY"); const bool zc = !(e && e[0] == '0'); c->ws_in.io = c->ws_in2.io = c->ws_out.io = zc; }
     // OBTG_FD_VIEW_STRUCTURED=0: contexts start with the structured routing of a view's one-call sweep off (obtg_ctx_set_fd_view_structured)
     { const char* e = getenv("OBTG_FD_VIEW_STRUCTURED"); c->fd_view_structured = !(e && e[0] == '0'); }
-    // OBTG_TRUE_MIN_JAC_FUSED=0: obtg_temporal_sep_true_min_jac forms its blocks in a launch of their own on every shape
+    // OBTG_TRUE_MIN_JAC_FUSED=0: obtg_temporal_sep_true_min_jac and obtg_speed_true_min_jac form their blocks in a launch of their own on every shape
     { const char* e = getenv("OBTG_TRUE_MIN_JAC_FUSED"); c->true_min_jac_fused = !(e && e[0] == '0'); }
     int rc = OBTG_OK;
     c->h_pairs.resize((size_t)2 * c->n_pairs);
@@ -715,7 +716,7 @@ static size_t ysize(const obtg_ctx* c) { return (size_t)c->n_veh * c->dim * (c->
 
 // ------------------------------------------------------------------ the Bernstein-family host entry points
 // The one host path of obtg_temporal_sep[_min[_range]|_active|_fd|_jac|_true_min[_jac]], obtg_one_vs_many_min[_spans],
-// obtg_speed[_jac], obtg_ang_rate[_jac], obtg_bern_*, the objectives and their gradients.  Every one of them is: its argument
+// obtg_speed[_jac|_true_min[_jac]], obtg_ang_rate[_jac], obtg_bern_*, the objectives and their gradients.  Every one of them is: its argument
 // checks, a HostCall, its operands by name (in), its outputs by name (out), its launcher (run), the download -- optional
 // outputs first (fetch, skipped for a null pointer), the mandatory one last (finish: the call's ONE synchronise).  The slots
 // of ws_misc are obtg::WsSlot, and so is the rule for who may hold which.  The next entry point of the family starts as a
@@ -723,13 +724,14 @@ static size_t ysize(const obtg_ctx* c) { return (size_t)c->n_veh * c->dim * (c->
 // What the entry points do NOT share, because a caller or a timing could tell -- each keeps the answer it has given since it
 // was added:
 //  - zero copy (mapped host memory; the one-row SLSQP callbacks): Y, tf and the result of obtg_temporal_sep[_min[_range]],
-//    obtg_speed, obtg_ang_rate and the objectives, Y of _active and _true_min[_jac], `one` and the result of
+//    obtg_speed, obtg_ang_rate and the objectives, Y of _active and _true_min[_jac], Y and tf of
+//    obtg_speed_true_min[_jac], `one` and the result of
 //    obtg_one_vs_many_min[_spans]; NOT the outputs of _active / _true_min*, and nothing of the _jac / _grad calls, of
 //    obtg_temporal_sep_fd, obtg_bern_extrema or obtg_bern_*;
 //  - an empty call with null pointers is OBTG_OK in obtg_one_vs_many_min[_spans] (B or K == 0), obtg_temporal_sep_fd (no
 //    perturbations, or fewer than two objects) and obtg_bern_extrema (M == 0); every other call rejects a null mandatory
 //    pointer first, and a context without pairs answers OBTG_OK only after that;
-//  - obtg_bern_extrema requires status, obtg_temporal_sep_true_min[_jac] take it as optional;
+//  - obtg_bern_extrema requires status, obtg_temporal_sep_true_min[_jac] and obtg_speed_true_min[_jac] take it as optional;
 //  - obtg_bern_normsq has no empty case (d >= 1); obtg_bern_restrict looks at every span before rows == 0 answers OBTG_OK;
 //  - obtg_ang_rate answers dim != 2 after its pointer checks, obtg_ang_rate_jac before them;
 //  - the _dev twins of the _jac calls answer OBTG_OK for B == 0 before the pointer checks, the host calls after them.
@@ -1682,6 +1684,109 @@ int obtg_temporal_sep_true_min_jac(obtg_ctx* c, const double* Y, int B, double m
     h.fetch(t_star, dv + n, n);
     h.fetch(status, ds, n);
     h.fetch(jac, dv + 2 * n, nj);
+    return h.finish(out, dv, n);
+}
+
+// ------------------------------------------------------------------ the true speed rows
+// the fused kernel where the shape has one; else obtg_speed's rows at R = 0 into a workspace and obtg_bern_extrema on them
+static int speed_true_min_launch(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max, double eps_rel,
+                                 int max_nodes, double* d_out, double* d_t, int* d_status)
+{
+    int rc = launch_speed_true_min(c, dY, d_tf, B, bound, is_max, eps_rel, max_nodes, d_out, d_t, d_status);
+    if (rc != OBTG_ERR_UNSUPPORTED) return rc;
+    const int K = 2 * c->deg + 1;
+    if (!bern_extrema_supported(K)) return OBTG_ERR_UNSUPPORTED;
+    const long items = (long)B * c->n_veh;
+    DevBuf& ws = c->ws_misc[WS_L_ROWS];
+    if ((rc = ws.reserve(sizeof(double) * (size_t)items * K))) return rc;
+    // DEG_ELEV does not enter: the any-degree kernel with R = 0 in its parameters, the context as it is
+    if ((rc = launch_speed_rows_r0_generic(c, dY, d_tf, B, bound, is_max, ws.as<double>()))) return rc;
+    return launch_bern_extrema(c, ws.as<double>(), items, K, 0, eps_rel, 0.0, max_nodes, d_out, d_t, nullptr, nullptr, d_status,
+                               OBTG_K_SPEED);
+}
+
+// what obtg_speed_true_min[_jac] and their _dev twins check alike (the host calls: Y too; the _jac calls: jac too)
+static int speed_true_min_args(const obtg_ctx* c, const double* tf, const double* out, int B, int max_nodes, double eps_rel)
+{
+    if (!check_ctx(c) || !tf || !out || B < 0 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
+    return c->deg > 31 ? OBTG_ERR_UNSUPPORTED : OBTG_OK;
+}
+
+int obtg_speed_true_min_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max, double eps_rel,
+                            int max_nodes, double* d_out, double* d_t_star, int* d_status)
+{
+    if (int rc = speed_true_min_args(c, d_tf, d_out, B, max_nodes, eps_rel)) return rc;
+    (void)hipSetDevice(c->device);
+    return with_batch(c, dY, B, false, [&](const double* src) {
+        return speed_true_min_launch(c, src, d_tf, B, bound, is_max != 0, eps_rel, max_nodes, d_out, d_t_star, d_status); });
+}
+
+int obtg_speed_true_min(obtg_ctx* c, const double* Y, const double* tf, int B, double bound, int is_max, double eps_rel,
+                        int max_nodes, double* out, double* t_star, int* status)
+{
+    if (int rc = speed_true_min_args(c, tf, out, B, max_nodes, eps_rel)) return rc;
+    if (!Y) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    const size_t n = (size_t)B * c->n_veh;
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    const double* d_tf = h.in(c->ws_in2, tf, (size_t)B, true);
+    double* dv = h.out<double>(c->ws_out, 2 * n);           // val | t_star
+    int* ds = h.out<int>(c->ws_misc[WS_STATUS], n);
+    h.run([&] { return speed_true_min_launch(c, dY, d_tf, B, bound, is_max != 0, eps_rel, max_nodes, dv, dv + n, ds); });
+    h.fetch(t_star, dv + n, n);
+    h.fetch(status, ds, n);
+    return h.finish(out, dv, n);
+}
+
+// values, t_star, status as speed_true_min_launch gives them, and the envelope blocks with their d/dtf: in the same launch
+// where the shape has a fused kernel, else (or with OBTG_TRUE_MIN_JAC_FUSED=0) from Y, tf and t_star in a launch of their own
+static int speed_true_min_jac_launch(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max,
+                                     double eps_rel, int max_nodes, double* d_out, double* d_t, int* d_status, double* d_jac,
+                                     double* d_jac_tf)
+{
+    int rc = OBTG_ERR_UNSUPPORTED;
+    if (c->true_min_jac_fused)
+        rc = launch_speed_true_min(c, dY, d_tf, B, bound, is_max, eps_rel, max_nodes, d_out, d_t, d_status, d_jac, d_jac_tf);
+    if (rc != OBTG_ERR_UNSUPPORTED) return rc;
+    if (!d_t) {
+        DevBuf& wt = c->ws_misc[WS_L_TSTAR];
+        if ((rc = wt.reserve(sizeof(double) * (size_t)B * c->n_veh))) return rc;
+        d_t = wt.as<double>();
+    }
+    if ((rc = speed_true_min_launch(c, dY, d_tf, B, bound, is_max, eps_rel, max_nodes, d_out, d_t, d_status))) return rc;
+    return launch_speed_envelope(c, dY, d_tf, B, is_max, d_t, d_jac, d_jac_tf);
+}
+
+int obtg_speed_true_min_jac_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max, double eps_rel,
+                                int max_nodes, double* d_out, double* d_t_star, int* d_status, double* d_jac, double* d_jac_tf)
+{
+    if (int rc = speed_true_min_args(c, d_tf, d_out, B, max_nodes, eps_rel)) return rc;
+    if (!d_jac) return OBTG_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    return with_batch(c, dY, B, false, [&](const double* src) {
+        return speed_true_min_jac_launch(c, src, d_tf, B, bound, is_max != 0, eps_rel, max_nodes, d_out, d_t_star, d_status, d_jac,
+                                         d_jac_tf); });
+}
+
+int obtg_speed_true_min_jac(obtg_ctx* c, const double* Y, const double* tf, int B, double bound, int is_max, double eps_rel,
+                            int max_nodes, double* out, double* t_star, int* status, double* jac, double* jac_tf)
+{
+    if (int rc = speed_true_min_args(c, tf, out, B, max_nodes, eps_rel)) return rc;
+    if (!Y || !jac) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    const size_t n = (size_t)B * c->n_veh, nj = n * c->dim * (c->deg + 1);
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    const double* d_tf = h.in(c->ws_in2, tf, (size_t)B, true);
+    double* dv = h.out<double>(c->ws_out, 3 * n + nj);      // val | t_star | jac_tf | jac
+    int* ds = h.out<int>(c->ws_misc[WS_STATUS], n);
+    h.run([&] { return speed_true_min_jac_launch(c, dY, d_tf, B, bound, is_max != 0, eps_rel, max_nodes, dv, dv + n, ds, dv + 3 * n,
+                                                 dv + 2 * n); });
+    h.fetch(t_star, dv + n, n);
+    h.fetch(status, ds, n);
+    h.fetch(jac_tf, dv + 2 * n, n);
+    h.fetch(jac, dv + 3 * n, nj);
     return h.finish(out, dv, n);
 }
 

@@ -22,6 +22,9 @@
 // off) as anywhere else.  Fused form: k_tsep_true_min<NC, DIM, true> re-reads the pair's control points from Y after
 // the search (the differences are dead by then: no register is held across wave_search for it) and every lane writes
 // its own block.  Two-launch form: the value path, then k_tsep_envelope on Y and t_star, any degree up to 31.
+//
+// True speed rows (obtg_speed_true_min[_jac]): the same search on a vehicle's own speed polynomial, k_speed_true_min, with
+// bern_device.h speed_envelope_block for the blocks and d/dtf; fused and two-launch forms as above (k_speed_envelope).
 #include <algorithm>
 #include <cfloat>
 
@@ -296,6 +299,86 @@ __global__ __launch_bounds__(kEnvThreads) void k_tsep_envelope(const TsepExParam
     if (item < q.ex.M) tsep_envelope_item<kEnvMaxNC, DIM>(q, item, nc, q.ex.t[item]);
 }
 
+// ---- the true speed rows: q(t) = sign (DIM/2) |c'(t)|^2 + offset of every (row, vehicle), the minimum over t of each
+// (obtg_speed_true_min[_jac]).  The coefficients are those of obtg_speed's rows at R = 0 -- diff_elev1_speed_rows per
+// coordinate (k_normsq_elev's speed path leaves the contraction of that step to the compiler: bern_device.h states what it
+// comes to, with explicit fma), normsq_coeffs, the output transform as one fma (sign is +-1: the product is exact, fused or
+// not) -- then the same first step and the same search as above.
+struct SpeedExParams {
+    const double* __restrict__ Y;      // [B][n_veh*DIM][NC]
+    const double* __restrict__ tf;     // [B]
+    const double* __restrict__ W2;
+    ExParams ex;                       // outputs [B][n_veh]; c unused
+    double* __restrict__ jac;          // [B][n_veh][DIM][NC] (the envelope forms)
+    double* __restrict__ jac_tf;       // [B][n_veh], nullable
+    int n_veh;
+    double sign, offset;
+};
+
+// One item's envelope block and d/dtf at t (a lane's own item)
+template <int NCMAX, int DIM>
+__device__ __forceinline__ void speed_envelope_item(const SpeedExParams& q, long item, int nc, double t)
+{
+    const int b = (int)(item / q.n_veh);
+    const double dtf = speed_envelope_block<NCMAX, DIM>(q.Y + (size_t)item * (DIM * nc), nc, q.tf[b], q.sign, t,
+                                                        q.jac + (size_t)item * (DIM * nc));
+    if (q.jac_tf) q.jac_tf[item] = dtf;
+}
+
+template <int NC, int DIM, bool JAC>
+__global__ __launch_bounds__(kExWaves * kWave) void k_speed_true_min(const SpeedExParams q)
+{
+    using S = NsShape<NC, DIM>;
+    constexpr int L = S::L;
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    double* stk = lds + (size_t)wave * kExStack * (L + 3);
+    const ExParams& p = q.ex;
+    const long item = ((long)blockIdx.x * kExWaves + wave) * kWave + lane;
+    const bool valid = item < p.M;
+    const long it = valid ? item : p.M - 1;
+    const int b = (int)(it / q.n_veh);
+    const double* v = q.Y + (size_t)it * S::VLEN;
+    const double val = (double)S::N / q.tf[b];           // Bezier.diff(): (n/T)(P_{i+1} - P_i), then elev(1)
+    double a[DIM][NC];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) {
+        double x[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) x[c] = v[d * NC + c];
+        diff_elev1_speed_rows<NC>(x, val, a[d]);
+    }
+    double cf[L];
+    normsq_coeffs<NC, DIM>(a, as_ctab(q.W2), cf);
+    ExScan sc;
+#pragma unroll
+    for (int k = 0; k < L; ++k) { cf[k] = fma(q.sign, cf[k], q.offset); sc.put(cf[k], k); }   // the R = 0 row's value
+    ExOut mine;
+    double tol;
+    const bool need = !ex_first(sc, p.eps_rel, p.eps_abs, mine, tol) && valid;
+    unsigned long long mask = __ballot(need);
+    while (mask) {
+        const int src = __ffsll((long long)mask) - 1;
+        mask &= mask - 1;
+        double bb = INFINITY;
+#pragma unroll
+        for (int k = 0; k < L; ++k) { const double c = ex_lane(cf[k], src); if (lane == k) bb = c; }
+        const ExOut o = wave_search(bb, L, ex_lane(tol, src), ex_lane(sc.c0, src), ex_lane(sc.cl, src), ex_lane(sc.m, src),
+                                    p.max_nodes, stk);
+        if (lane == src) mine = o;
+    }
+    if (valid) ex_store(p, item, mine, false);
+    if (JAC && valid) speed_envelope_item<NC, DIM>(q, item, NC, mine.t);
+}
+
+// the blocks alone, from Y, tf and the t_star of an earlier launch: one item per lane, nc <= kEnvMaxNC at run time
+template <int DIM>
+__global__ __launch_bounds__(kEnvThreads) void k_speed_envelope(const SpeedExParams q, const int nc)
+{
+    const long item = (long)blockIdx.x * kEnvThreads + threadIdx.x;
+    if (item < q.ex.M) speed_envelope_item<kEnvMaxNC, DIM>(q, item, nc, q.ex.t[item]);
+}
+
 // =====================================================================================
 //  launchers
 // =====================================================================================
@@ -360,6 +443,62 @@ int launch_temporal_sep_envelope(obtg_ctx* c, const double* dY, int B, const dou
     q.ex.t = const_cast<double*>(d_t); q.ex.M = (long)B * c->n_pairs;
     void (*kern)(const TsepExParams, int) = c->dim == 1 ? k_tsep_envelope<1> : c->dim == 2 ? k_tsep_envelope<2> : k_tsep_envelope<3>;
     ScopedKernelTimer t(c, OBTG_K_TEMPORAL_SEP);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((q.ex.M + kEnvThreads - 1) / kEnvThreads)), dim3(kEnvThreads), 0, c->stream, q, nc);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
+// the speed rows' sign and offset, as launch_speed sets them
+static void speed_transform(double bound, int is_max, double& sign, double& offset)
+{
+    const double b2 = square_as_python(bound);
+    sign = is_max ? -1.0 : 1.0;
+    offset = is_max ? b2 : -b2;
+}
+
+// OBTG_ERR_UNSUPPORTED: not a shape of the fast-kernel list (the caller goes through obtg_speed's R = 0 rows)
+// d_jac != nullptr: the fused envelope form (obtg_speed_true_min_jac), the same search and one launch; d_jac_tf nullable
+int launch_speed_true_min(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max, double eps_rel,
+                          int max_nodes, double* d_out, double* d_t, int* d_status, double* d_jac, double* d_jac_tf)
+{
+    if (B <= 0) return OBTG_OK;
+    const int nc = c->deg + 1;
+    if (!nc_in_sep(nc) || (c->dim != 2 && c->dim != 3)) return OBTG_ERR_UNSUPPORTED;
+    int rc = ensure_tables(c);
+    if (rc) return rc;
+    SpeedExParams q{};
+    q.Y = dY; q.tf = d_tf; q.W2 = c->d_w2.as<double>(); q.n_veh = c->n_veh; q.jac = d_jac; q.jac_tf = d_jac_tf;
+    speed_transform(bound, is_max, q.sign, q.offset);
+    q.ex.val = d_out; q.ex.t = d_t; q.ex.status = d_status;
+    q.ex.M = (long)B * c->n_veh; q.ex.K = 2 * c->deg + 1; q.ex.max_nodes = max_nodes; q.ex.eps_rel = eps_rel; q.ex.eps_abs = 0.0;
+    void (*kern)(const SpeedExParams) = nullptr;
+#define OBTG_CASE(NC_, D_) if (nc == NC_ && c->dim == D_) kern = d_jac ? k_speed_true_min<NC_, D_, true> : k_speed_true_min<NC_, D_, false>;
+#define OBTG_CASE_D(NC_) OBTG_CASE(NC_, 2) OBTG_CASE(NC_, 3)
+    OBTG_NC_SEP(OBTG_CASE_D)
+#undef OBTG_CASE_D
+#undef OBTG_CASE
+    if (!kern) return OBTG_ERR_UNSUPPORTED;
+    const size_t lds = sizeof(double) * kExWaves * kExStack * (size_t)(q.ex.K + 3);
+    const long per_wg = kExWaves * kWave;
+    ScopedKernelTimer t(c, OBTG_K_SPEED);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((q.ex.M + per_wg - 1) / per_wg)), dim3(kExWaves * kWave), lds, c->stream, q);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
+// the blocks of the two-launch form: d_t holds the t_star of the value path
+int launch_speed_envelope(obtg_ctx* c, const double* dY, const double* d_tf, int B, int is_max, const double* d_t, double* d_jac,
+                          double* d_jac_tf)
+{
+    if (B <= 0) return OBTG_OK;
+    const int nc = c->deg + 1;
+    if (nc > kEnvMaxNC) return OBTG_ERR_UNSUPPORTED;
+    SpeedExParams q{};
+    q.Y = dY; q.tf = d_tf; q.n_veh = c->n_veh; q.jac = d_jac; q.jac_tf = d_jac_tf;
+    q.sign = is_max ? -1.0 : 1.0;
+    q.ex.t = const_cast<double*>(d_t); q.ex.M = (long)B * c->n_veh;
+    void (*kern)(const SpeedExParams, int) = c->dim == 1 ? k_speed_envelope<1> : c->dim == 2 ? k_speed_envelope<2> : k_speed_envelope<3>;
+    ScopedKernelTimer t(c, OBTG_K_SPEED);
     hipLaunchKernelGGL(kern, dim3((unsigned)((q.ex.M + kEnvThreads - 1) / kEnvThreads)), dim3(kEnvThreads), 0, c->stream, q, nc);
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;

@@ -76,6 +76,8 @@ struct KernelStat {
 //   obtg_temporal_sep_true_min[_jac] holds 4 (WS_STATUS)
 //     -> true_min_jac_launch takes 6 (WS_L_TSTAR: only for a _dev caller that wants no t_star; the host call's is in ws_out)
 //     -> true_min_launch     takes 7 (WS_L_ROWS) across launch_temporal_sep_rows_r0_generic and launch_bern_extrema, which take none
+//   obtg_speed_true_min[_jac] holds 4 (WS_STATUS): the same chain through speed_true_min_jac_launch (6) and speed_true_min_launch (7:
+//     launch_speed_rows_r0_generic and launch_bern_extrema take none)
 //   obtg_temporal_sep_active holds 4 (WS_STATUS) -> launch_temporal_sep takes 7 (WS_L_ROWS: the any-degree selection)
 //   host_deriv_obj           holds none -> launch_deriv_energy_obj takes 3, 6, 4 (launch_bern_diff and launch_speed take none)
 //   obtg_bern_extrema        holds 3 (WS_INFO) -> launch_bern_extrema takes none
@@ -90,15 +92,15 @@ enum WsSlot {
     WS_INFO = 3,          // int[4 n_pairs]: counters and status of a curve search; flag | n_support or iters | status of a GJK call; nodes | status of obtg_bern_extrema
     WS_L_DIFF_A = 3,      //   launch_deriv_energy_obj: derivative passes, even ones
     WS_TRACE = 4,         // obtg_gjk_pairs: the support trace
-    WS_STATUS = 4,        //   int per value: the row indices of obtg_temporal_sep_active, the status of obtg_temporal_sep_true_min[_jac]
+    WS_STATUS = 4,        //   int per value: the row indices of obtg_temporal_sep_active, the status of obtg_temporal_sep_true_min[_jac] and obtg_speed_true_min[_jac]
     WS_L_SPEED = 4,       //   launch_deriv_energy_obj: the speed-style rows before their sum
     WS_STACK = 5,         // frame stacks (the frontiers of the robust searches)
     WS_OUT_TF = 5,        //   the d/dtf output of obtg_speed_jac, obtg_ang_rate_jac, obtg_deriv_energy_grad
     WS_QUEUE = 6,         // work-queue counter, and behind it obtg_min_dist's pair order
     WS_L_DIFF_B = 6,      //   launch_deriv_energy_obj: derivative passes, odd ones
-    WS_L_TSTAR = 6,       //   true_min_jac_launch: t_star between the value launch and the envelope launch, when the caller wants none
+    WS_L_TSTAR = 6,       //   true_min_jac_launch, speed_true_min_jac_launch: t_star between the value launch and the envelope launch, when the caller wants none
     WS_L_TIMELINE = 6,    //   TimelineDump (gjk_kernels.hip; the one-launch sweeps, which no holder of WS_QUEUE calls)
-    WS_L_ROWS = 7,        // whole separation rows under a reduction: launch_temporal_sep's any-degree selection, true_min_launch's R = 0 rows
+    WS_L_ROWS = 7,        // whole rows under a reduction: launch_temporal_sep's any-degree selection, true_min_launch's and speed_true_min_launch's R = 0 rows
     WS_L_CHANGED = 7,     //   launch_gjk_swarm's de-duplicated sweep: which objects differ from row 0
     WS_COUNT = 8,
 };
@@ -152,7 +154,7 @@ struct obtg_ctx {
     int n_poly = 0, n_poly_pts = 0, max_poly_K = 0;
     bool polys_planar = true;   // every registered polygon vertex has z == 0
     bool fd_dedup = false;      // reuse row 0's GJK results for bit-identical hull pairs
-    bool true_min_jac_fused = true;   // OBTG_TRUE_MIN_JAC_FUSED=0: obtg_temporal_sep_true_min_jac takes the two-launch form on every shape
+    bool true_min_jac_fused = true;   // OBTG_TRUE_MIN_JAC_FUSED=0: obtg_temporal_sep_true_min_jac and obtg_speed_true_min_jac take the two-launch form on every shape
     bool fd_view_structured = true;   // obtg_ctx_set_fd_view_structured: the one-call sweep of a view takes the structured step where it applies
     obtg::DevBuf d_hp_a, d_hp_b;  // hull pair list
     obtg::DevBuf d_vp_off, d_vp_idx;   // per vehicle: the positions of the hull pairs that contain it (CSR; structured FD step)
@@ -265,6 +267,7 @@ int launch_one_vs_many_min_spans(obtg_ctx* c, const double* d_one, const double*
 int launch_bern_restrict(obtg_ctx* c, const double* d_in, int rows, int n, const double* d_span, const double* d_target, double* d_out);
 int launch_speed(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max,
                  double* d_out);
+int launch_speed_rows_r0_generic(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max, double* d_out);   // rows at R = 0, any-degree kernel, c->R not read
 int launch_ang_rate(obtg_ctx* c, const double* dY, const double* d_tf, int B, double max_rate,
                     double* d_out);
 // DEG_ELEV > 0, planar: separation rows + speed / angular-rate rows in one launch; OBTG_ERR_UNSUPPORTED = not this shape
@@ -358,5 +361,12 @@ int launch_temporal_sep_true_min(obtg_ctx* c, const double* dY, int B, double ma
                                  double* d_out, double* d_t, int* d_status, double* d_jac = nullptr);   // d_jac: with the envelope blocks
 // the envelope blocks [B][P][dim][deg+1] from Y and the t_star of a value launch: any degree up to 31 (else OBTG_ERR_UNSUPPORTED)
 int launch_temporal_sep_envelope(obtg_ctx* c, const double* dY, int B, const double* d_t, double* d_jac);
+// the true speed rows (obtg_speed_true_min[_jac]), timed under OBTG_K_SPEED: the fused form for the fast-kernel list's shapes
+// (OBTG_ERR_UNSUPPORTED: go through obtg_speed's R = 0 rows); d_jac: with the envelope blocks, d_jac_tf (nullable) their d/dtf
+int launch_speed_true_min(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max, double eps_rel,
+                          int max_nodes, double* d_out, double* d_t, int* d_status, double* d_jac = nullptr, double* d_jac_tf = nullptr);
+// the envelope blocks [B][N][dim][deg+1] and d/dtf [B][N] from Y, tf and the t_star of a value launch: any degree up to 31
+int launch_speed_envelope(obtg_ctx* c, const double* dY, const double* d_tf, int B, int is_max, const double* d_t, double* d_jac,
+                          double* d_jac_tf);
 
 }  // namespace obtg

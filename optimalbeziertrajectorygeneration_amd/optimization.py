@@ -282,7 +282,8 @@ class BezOptimization(object):
                  separationRows='all',
                  angRateOrder='fast',
                  activeRows=2,
-                 fdBatching=True):
+                 fdBatching=True,
+                 speedRows='all'):
         """Beyond the reference's keywords: `device` (HIP ordinal; None: this process's, see _capi.default_device) and `separationRows` --
         'all': temporalSeparationConstraints returns every elevated control point of every pair, as the
         reference does (optimization.py:337); 'min': one row per pair, the smallest of them -- the
@@ -295,6 +296,12 @@ class BezOptimization(object):
         # 'true_min': per pair the true minimum over the trajectory's time of the squared separation minus maxSep^2
         # (obtg_temporal_sep_true_min) -- the tight continuous-time value that the control points only bound from below
         # and that DEG_ELEV exists to approach: P rows whatever DEG_ELEV is.
+        # speedRows 'true_min': per vehicle the true minimum over the trajectory's time of each speed row's polynomial
+        # (obtg_speed_true_min) -- N rows per bound whatever DEG_ELEV is, feasible iff >= 0 -- instead of its N (2n+R+1)
+        # elevated control points ('all', the reference's rows: optimization.py:349-422), which only bound it from below
+        if speedRows not in ('all', 'true_min'):
+            raise ValueError("speedRows must be 'all' or 'true_min', not {!r}".format(speedRows))
+        self.speedRows = speedRows
         if separationRows not in ('all', 'min', 'active', 'true_min'):
             raise ValueError("separationRows must be 'all', 'min', 'active' or 'true_min', not {!r}".format(separationRows))
         if separationRows == 'active' and not 1 <= int(activeRows) <= 4:
@@ -395,6 +402,32 @@ class BezOptimization(object):
         r = self._true_min_checked(self._ctx(with_obs), self.reshapeVector(x)[None])
         return r['val'][0], r['t_star'][0]
 
+    def _speed_true_min(self, ctx, Y, tf, family):
+        """speedRows='true_min': [B][N] true per-vehicle minima of the rows of `family` ('vmax' / 'vmin'); a search that ran
+        out of budget raises (bezier._raise_md)"""
+        is_max = family == 'vmax'
+        r = ctx.speed_true_min(Y, tf, self.model['maxSpeed' if is_max else 'minSpeed'], is_max, eps_rel=self.TRUE_MIN_EPS_REL)
+        self._raise_speed_md(r, ('maxSpeedConstraints' if is_max else 'minSpeedConstraints') + '(true_min)')
+        return r['val']
+
+    @staticmethod
+    def _raise_speed_md(r, what):
+        bad = np.flatnonzero(r['status'].ravel() != _capi.MD_OK)
+        if bad.size:
+            bez._raise_md(int(r['status'].ravel()[bad[0]]), what)
+
+    def trueSpeedRange(self, x):
+        """(min_val[N], t_min[N], max_val[N], t_max[N]): per vehicle the true extrema over the trajectory of (d/2)|dv/dt|^2
+        -- normSquare's factor kept: the scale of the speed rows, without their bound -- and the parameters in [0, 1] where
+        they are reached (obtg_speed_true_min with bound 0), whatever `speedRows` is."""
+        x = np.asarray(x, dtype=float)
+        ctx, Y, tf = self._ctx(False), self.reshapeVector(x)[None], self._tf_of(x)
+        lo = ctx.speed_true_min(Y, tf, 0.0, False, eps_rel=self.TRUE_MIN_EPS_REL)
+        hi = ctx.speed_true_min(Y, tf, 0.0, True, eps_rel=self.TRUE_MIN_EPS_REL)
+        for r in (lo, hi):
+            self._raise_speed_md(r, 'trueSpeedRange')
+        return lo['val'][0], lo['t_star'][0], -hi['val'][0], hi['t_star'][0]
+
     def _timeopt(self):
         return self.model['minGoal'].lower() == 'timeopt'
 
@@ -489,6 +522,8 @@ class BezOptimization(object):
     def minSpeedConstraints(self):
         def direct(x):
             y = self.reshapeVector(x)
+            if self.speedRows == 'true_min':
+                return self._speed_true_min(self._ctx(False), y, self._tf_of(x), 'vmin')[0]
             return self._ctx(False).speed(y, self._tf_of(x), self.model['minSpeed'], False)[0]
         return lambda x: self._serve('vmin', x, direct)
 
@@ -496,6 +531,8 @@ class BezOptimization(object):
     def maxSpeedConstraints(self):
         def direct(x):
             y = self.reshapeVector(x)
+            if self.speedRows == 'true_min':
+                return self._speed_true_min(self._ctx(False), y, self._tf_of(x), 'vmax')[0]
             return self._ctx(False).speed(y, self._tf_of(x), self.model['maxSpeed'], True)[0]
         return lambda x: self._serve('vmax', x, direct)
 
@@ -670,7 +707,7 @@ class BezOptimization(object):
         milliseconds); _serve asks for the key only when at most one variable moved."""
         if refresh or getattr(self, '_rv_cache', None) is None:
             self._rv_parts()
-        return (int(DEG_ELEV), self.separationRows, self.activeRows, self._rv_cache[0], self.model['maxSep'], self.model['maxSpeed'],
+        return (int(DEG_ELEV), self.separationRows, self.speedRows, self.activeRows, self._rv_cache[0], self.model['maxSep'], self.model['maxSpeed'],
                 self.model['minSpeed'], self.model['maxAngRate'], None if self._timeopt() else self.model['tf'],
                 None if self.pointObstacles is None else np.asarray(self.pointObstacles, dtype=float).tobytes(),
                 None if self.shapeObstacles is None else tuple(np.asarray(c.cpts, dtype=float).tobytes() for c in self.shapeObstacles))
@@ -701,7 +738,9 @@ class BezOptimization(object):
         else:
             tf = X[:, -1] if self._timeopt() else np.full(X.shape[0], self.model['tf'])
             c = self._ctx(False)
-            if family == 'vmax':
+            if family in ('vmax', 'vmin') and self.speedRows == 'true_min':
+                F = self._speed_true_min(c, Y, tf, family)
+            elif family == 'vmax':
                 F = c.speed(Y, tf, self.model['maxSpeed'], True)
             elif family == 'vmin':
                 F = c.speed(Y, tf, self.model['minSpeed'], False)
@@ -783,11 +822,26 @@ class BezOptimization(object):
         point of vehicle v only moves v's own rows.  structured=True evaluates, per variable, that one
         vehicle (a compact batch on a one-vehicle context: n_x vehicle evaluations instead of
         n_x N); entries equal the brute-force batch's bit for bit.  A trailing tf moves everything and
-        takes the batch path.  method='exact': the analytic blocks (obtg_speed_jac / obtg_ang_rate_jac, one launch at x)."""
+        takes the batch path.  method='exact': the analytic blocks (obtg_speed_jac / obtg_ang_rate_jac, one launch at x).
+
+        speedRows='true_min' (the speed families): method='envelope' is the envelope derivative of the true per-vehicle
+        minima -- each row's polynomial differentiated at the minimiser the search returns, with its d/dtf
+        (obtg_speed_true_min_jac, one call at x with TRUE_MIN_EPS_REL); method='fd' differences the search
+        itself (one batched call); method='exact' is not built for these rows."""
+        true_min = family in ('vmax', 'vmin') and self.speedRows == 'true_min'
+        if method == 'envelope' and family in ('vmax', 'vmin'):
+            if not true_min:
+                raise ValueError("{}SpeedJacobian(method='envelope') needs speedRows='true_min', not {!r}"
+                                 .format('max' if family == 'vmax' else 'min', self.speedRows))
+            return self._speed_jac_envelope(x, family)
         _check_method(method)
         if method == 'exact':
+            if true_min:
+                raise ValueError("{}SpeedJacobian(method='exact') is not available with speedRows='true_min' (the envelope "
+                                 "derivative is not built under that name): use method='envelope' or method='fd'"
+                                 .format('max' if family == 'vmax' else 'min'))
             return self._jac_vehicle_exact(x, family)
-        if not structured:
+        if not structured or true_min:
             return self._jac(x, family)
         x = np.asarray(x, dtype=float)
         X, dx = self._fd_rows(x)
@@ -899,6 +953,16 @@ class BezOptimization(object):
             bez._raise_md(int(r['status'].ravel()[bad[0]]), 'temporalSeparationJacobian(envelope)')
         pa, pb = np.triu_indices(n_obj, 1)
         return self._scatter_exact(r['jac'][0][:, None], (pa, pb), (1.0, -1.0))      # blocks of one row each
+
+    def _speed_jac_envelope(self, x, family):
+        x = np.asarray(x, dtype=float)
+        is_max = family == 'vmax'
+        r = self._ctx(False).speed_true_min_jac(self.reshapeVectors(x[None]), float(self._tf_of(x)),
+                                                self.model['maxSpeed' if is_max else 'minSpeed'], is_max,
+                                                eps_rel=self.TRUE_MIN_EPS_REL)
+        self._raise_speed_md(r, ('maxSpeedJacobian' if is_max else 'minSpeedJacobian') + '(envelope)')
+        N = self.model['numVeh']
+        return self._scatter_exact(r['jac'][0][:, None], (np.arange(N),), (1.0,), r['jac_tf'][0][:, None])   # blocks of one row each
 
     def trueMinSeparationJacobian(self, x):
         """temporalSeparationJacobian(x, method='envelope')"""

@@ -543,17 +543,25 @@ class Context(object):
                     "obtg_temporal_sep_active")
         return (out, idx) if with_index else out
 
+    def _true_min(self, name, items, Y, tf, lead, eps_rel, max_nodes, *blocks):
+        """The allocation, the call and the dict of the true-minimum host calls, `items` values per row:
+        obtg_<family>(Y[, tf], B, *lead, eps_rel, max_nodes, val, t_star, status[, jac[, jac_tf]]); blocks names the last two."""
+        Y, B = self._rows(Y)
+        ops = [Y] if tf is None else [Y, self._tf(tf, B)]
+        r = dict(val=pinned_empty((B, items)), t_star=np.empty((B, items)), status=np.zeros((B, items), np.int32))
+        if "jac" in blocks:
+            r["jac"] = pinned_empty((B, items, self.dim, self.deg + 1))
+        if "jac_tf" in blocks:
+            r["jac_tf"] = np.empty((B, items))
+        self._check(getattr(self._lib, name)(self._h, *[_ptr(a) for a in ops], B, *lead, float(eps_rel), int(max_nodes),
+                                             *[_ptr(a) for a in r.values()]), name)
+        return r
+
     def temporal_sep_true_min(self, Y, max_sep, eps_rel=1e-9, max_nodes=100000):
         """Per pair the true minimum over t in [0, 1] of the squared-separation polynomial minus max_sep^2
         (obtg_temporal_sep_true_min; DEG_ELEV does not enter): dict(val[B][P], t_star[B][P] -- where it is taken --,
         status[B][P] as MD_*).  val - (the search's lower bound) <= eps_rel x the pair's largest coefficient."""
-        Y, B = self._rows(Y)
-        out = pinned_empty((B, self.num_pairs))
-        t_star = np.empty((B, self.num_pairs))
-        status = np.zeros((B, self.num_pairs), np.int32)
-        self._check(self._lib.obtg_temporal_sep_true_min(self._h, _ptr(Y), B, float(max_sep), float(eps_rel), int(max_nodes),
-                                                         _ptr(out), _ptr(t_star), _ptr(status)), "obtg_temporal_sep_true_min")
-        return dict(val=out, t_star=t_star, status=status)
+        return self._true_min("obtg_temporal_sep_true_min", self.num_pairs, Y, None, (float(max_sep),), eps_rel, max_nodes)
 
     def temporal_sep_true_min_dev(self, dY, B, max_sep, d_out, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
         self._check(self._lib.obtg_temporal_sep_true_min_dev(self._h, _vp(dY), B, float(max_sep), float(eps_rel), int(max_nodes),
@@ -564,15 +572,7 @@ class Context(object):
         """temporal_sep_true_min with its envelope Jacobian (obtg_temporal_sep_true_min_jac): dict(val, t_star, status -- the
         bits of temporal_sep_true_min --, jac[B][P][dim][deg+1]: d/d(control points of the pair's first object) of the pair's
         polynomial at t_star; the second object's block is the negation, an obstacle has no variable)."""
-        Y, B = self._rows(Y)
-        out = pinned_empty((B, self.num_pairs))
-        t_star = np.empty((B, self.num_pairs))
-        status = np.zeros((B, self.num_pairs), np.int32)
-        jac = pinned_empty((B, self.num_pairs, self.dim, self.deg + 1))
-        self._check(self._lib.obtg_temporal_sep_true_min_jac(self._h, _ptr(Y), B, float(max_sep), float(eps_rel), int(max_nodes),
-                                                             _ptr(out), _ptr(t_star), _ptr(status), _ptr(jac)),
-                    "obtg_temporal_sep_true_min_jac")
-        return dict(val=out, t_star=t_star, status=status, jac=jac)
+        return self._true_min("obtg_temporal_sep_true_min_jac", self.num_pairs, Y, None, (float(max_sep),), eps_rel, max_nodes, "jac")
 
     def temporal_sep_true_min_jac_dev(self, dY, B, max_sep, d_out, d_jac, d_t_star=None, d_status=None, eps_rel=1e-9,
                                       max_nodes=100000):
@@ -644,14 +644,7 @@ class Context(object):
         """Per vehicle the true minimum over t in [0, 1] of the speed row's polynomial sign (d/2)|v'|^2 + offset -- the polynomial
         speed(Y, tf, bound, is_max) holds the control points of (obtg_speed_true_min; DEG_ELEV does not enter):
         dict(val[B][N], t_star[B][N], status[B][N] as MD_*)."""
-        Y, B = self._rows(Y)
-        tf = self._tf(tf, B)
-        out = pinned_empty((B, self.n_veh))
-        t_star = np.empty((B, self.n_veh))
-        status = np.zeros((B, self.n_veh), np.int32)
-        self._check(self._lib.obtg_speed_true_min(self._h, _ptr(Y), _ptr(tf), B, float(bound), int(bool(is_max)), float(eps_rel),
-                                                  int(max_nodes), _ptr(out), _ptr(t_star), _ptr(status)), "obtg_speed_true_min")
-        return dict(val=out, t_star=t_star, status=status)
+        return self._true_min("obtg_speed_true_min", self.n_veh, Y, tf, (float(bound), int(bool(is_max))), eps_rel, max_nodes)
 
     def speed_true_min_dev(self, dY, d_tf, B, bound, is_max, d_out, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
         self._check(self._lib.obtg_speed_true_min_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(bound), int(bool(is_max)),
@@ -662,16 +655,8 @@ class Context(object):
         """speed_true_min with its envelope Jacobian (obtg_speed_true_min_jac): dict(val, t_star, status -- the bits of
         speed_true_min --, jac[B][N][dim][deg+1]: d/d(the vehicle's own control points) of its polynomial at t_star,
         jac_tf[B][N]: d/dtf at fixed control points)."""
-        Y, B = self._rows(Y)
-        tf = self._tf(tf, B)
-        out = pinned_empty((B, self.n_veh))
-        t_star, jac_tf = np.empty((B, self.n_veh)), np.empty((B, self.n_veh))
-        status = np.zeros((B, self.n_veh), np.int32)
-        jac = pinned_empty((B, self.n_veh, self.dim, self.deg + 1))
-        self._check(self._lib.obtg_speed_true_min_jac(self._h, _ptr(Y), _ptr(tf), B, float(bound), int(bool(is_max)), float(eps_rel),
-                                                      int(max_nodes), _ptr(out), _ptr(t_star), _ptr(status), _ptr(jac), _ptr(jac_tf)),
-                    "obtg_speed_true_min_jac")
-        return dict(val=out, t_star=t_star, status=status, jac=jac, jac_tf=jac_tf)
+        return self._true_min("obtg_speed_true_min_jac", self.n_veh, Y, tf, (float(bound), int(bool(is_max))), eps_rel, max_nodes,
+                              "jac", "jac_tf")
 
     def speed_true_min_jac_dev(self, dY, d_tf, B, bound, is_max, d_out, d_jac, d_jac_tf=None, d_t_star=None, d_status=None,
                                eps_rel=1e-9, max_nodes=100000):

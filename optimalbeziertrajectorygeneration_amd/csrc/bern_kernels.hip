@@ -1394,6 +1394,25 @@ __global__ __launch_bounds__(256) void k_select_smallest(const double* __restric
     sm.store(out, idx, (size_t)it * k, k);
 }
 
+// MODE's rows (0: separation, 1: speed) from the any-degree kernel at elevation R, timed under the MODE's kernel id: the
+// tail of launch_temporal_sep / launch_speed with R = c->R, the R = 0 rows of the true-minimum families (rows_r0) with 0
+template <int MODE>
+static int launch_generic_rows(obtg_ctx* c, const double* dY, const double* d_tf, int B, int item_begin, int item_count, int R,
+                               double sign, double offset, bool min_only, double* d_out)
+{
+    GenParams g{};
+    int rc = gen_common(c, g, R);
+    if (rc) return rc;
+    if (2 * c->deg + R + 1 > kMaxGenericLen) return OBTG_ERR_UNSUPPORTED;
+    g.Y = dY; g.tf = d_tf; g.out = d_out; g.item_begin = item_begin; g.item_count = item_count; g.B = B;
+    g.sign = sign; g.offset = offset; g.min_only = min_only ? 1 : 0;
+    const size_t lds = sizeof(double) * ((size_t)2 * c->dim * (c->deg + 1) + 2 * c->deg + 1);
+    ScopedKernelTimer t(c, MODE ? OBTG_K_SPEED : OBTG_K_TEMPORAL_SEP);
+    hipLaunchKernelGGL(k_generic_normsq_elev<MODE>, dim3((unsigned)((size_t)B * item_count)), dim3(kWave), lds, c->stream, g);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
 int launch_temporal_sep(obtg_ctx* c, const double* dY, int B, double max_sep, int pair_begin,
                         int pair_count, bool min_only, double* d_out, int sel_k, int* d_sel_idx)
 {
@@ -1426,38 +1445,15 @@ int launch_temporal_sep(obtg_ctx* c, const double* dY, int B, double max_sep, in
         OBTG_HIP(c, hipGetLastError());
         return OBTG_OK;
     }
-    GenParams g{};
-    rc = gen_common(c, g);
-    if (rc) return rc;
-    if (2 * c->deg + c->R + 1 > kMaxGenericLen) return OBTG_ERR_UNSUPPORTED;
-    g.Y = dY; g.out = d_out; g.item_begin = pair_begin; g.item_count = pair_count; g.B = B;
-    g.sign = 1.0; g.offset = 0.0 - square_as_python(max_sep); g.min_only = min_only ? 1 : 0;
-    const int nc = c->deg + 1;
-    size_t lds = sizeof(double) * ((size_t)2 * c->dim * nc + 2 * c->deg + 1);
-    ScopedKernelTimer t(c, OBTG_K_TEMPORAL_SEP);
-    hipLaunchKernelGGL(k_generic_normsq_elev<0>, dim3((unsigned)((size_t)B * pair_count)), dim3(kWave), lds,
-                       c->stream, g);
-    OBTG_HIP(c, hipGetLastError());
-    return OBTG_OK;
+    return launch_generic_rows<0>(c, dY, nullptr, B, pair_begin, pair_count, c->R, 1.0, 0.0 - square_as_python(max_sep), min_only,
+                                  d_out);
 }
 
-// obtg_temporal_sep's rows AT R = 0 from the any-degree kernel, whatever the context's DEG_ELEV is (the route of
-// obtg_temporal_sep_true_min for degrees off the fast-kernel list): the launch a context with R = 0 makes, bit for bit; the
-// context is not touched
-int launch_temporal_sep_rows_r0_generic(obtg_ctx* c, const double* dY, int B, double max_sep, double* d_out)
+void speed_sign_offset(double bound, int is_max, double& sign, double& offset)
 {
-    if (B <= 0 || c->n_pairs <= 0) return OBTG_OK;
-    if (2 * c->deg + 1 > kMaxGenericLen) return OBTG_ERR_UNSUPPORTED;
-    GenParams g{};
-    int rc = gen_common(c, g, 0);
-    if (rc) return rc;
-    g.Y = dY; g.out = d_out; g.item_begin = 0; g.item_count = c->n_pairs; g.B = B;
-    g.sign = 1.0; g.offset = 0.0 - square_as_python(max_sep); g.min_only = 0;
-    const size_t lds = sizeof(double) * ((size_t)2 * c->dim * (c->deg + 1) + 2 * c->deg + 1);
-    ScopedKernelTimer t(c, OBTG_K_TEMPORAL_SEP);
-    hipLaunchKernelGGL(k_generic_normsq_elev<0>, dim3((unsigned)((size_t)B * c->n_pairs)), dim3(kWave), lds, c->stream, g);
-    OBTG_HIP(c, hipGetLastError());
-    return OBTG_OK;
+    const double b2 = square_as_python(bound);
+    sign = is_max ? -1.0 : 1.0;
+    offset = is_max ? b2 : -b2;
 }
 
 int launch_speed(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max,
@@ -1466,7 +1462,8 @@ int launch_speed(obtg_ctx* c, const double* dY, const double* d_tf, int B, doubl
     if (B <= 0) return OBTG_OK;
     int rc = ensure_tables(c);
     if (rc) return rc;
-    const double b2 = square_as_python(bound);
+    double sign, offset;
+    speed_sign_offset(bound, is_max, sign, offset);
     if (fast_shape(c)) {
         NsParams p{};
         p.Y = dY; p.obs = nullptr; p.tf = d_tf; p.pairs = nullptr;
@@ -1479,45 +1476,33 @@ int launch_speed(obtg_ctx* c, const double* dY, const double* d_tf, int B, doubl
         p.wgs_per_row = (c->n_veh + kWave - 1) / kWave;
         p.stage_slots = std::min(c->n_veh, kWave);
         p.stage_all = 0; p.tiling = 0; p.tiles = nullptr;
-        p.sign = is_max ? -1.0 : 1.0; p.offset = is_max ? b2 : -b2;
+        p.sign = sign; p.offset = offset;
         if (c->fd.Y0) { p.Y = c->fd.Y0; p.fd = 1 + c->fd.row0; p.fd_fixed = c->fd.fixed; p.fd_h = c->fd.h; }
         rc = dispatch_ns<1, false>(c, p, B, OBTG_K_SPEED);
         if (rc != OBTG_ERR_UNSUPPORTED) return rc;
     }
     if (c->fd.Y0) return kNeedBatch;
-    GenParams g{};
-    rc = gen_common(c, g);
-    if (rc) return rc;
-    if (2 * c->deg + c->R + 1 > kMaxGenericLen) return OBTG_ERR_UNSUPPORTED;
-    g.Y = dY; g.tf = d_tf; g.out = d_out; g.item_begin = 0; g.item_count = c->n_veh; g.B = B;
-    g.sign = is_max ? -1.0 : 1.0; g.offset = is_max ? b2 : -b2; g.min_only = 0;
-    const int nc = c->deg + 1;
-    size_t lds = sizeof(double) * ((size_t)2 * c->dim * nc + 2 * c->deg + 1);
-    ScopedKernelTimer t(c, OBTG_K_SPEED);
-    hipLaunchKernelGGL(k_generic_normsq_elev<1>, dim3((unsigned)((size_t)B * c->n_veh)), dim3(kWave), lds,
-                       c->stream, g);
-    OBTG_HIP(c, hipGetLastError());
-    return OBTG_OK;
+    return launch_generic_rows<1>(c, dY, d_tf, B, 0, c->n_veh, c->R, sign, offset, false, d_out);
 }
 
-// obtg_speed's rows AT R = 0 from the any-degree kernel, whatever the context's DEG_ELEV is (the route of
-// obtg_speed_true_min for degrees off the fast-kernel list): the launch a context with R = 0 makes, bit for bit; the
-// context is not touched
-int launch_speed_rows_r0_generic(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max, double* d_out)
+// the true-minimum row families' descriptors (obtg_internal.h RowFamily)
+template <int MODE>
+static int rows_r0(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out)
 {
-    if (B <= 0) return OBTG_OK;
-    if (2 * c->deg + 1 > kMaxGenericLen) return OBTG_ERR_UNSUPPORTED;
-    GenParams g{};
-    int rc = gen_common(c, g, 0);
-    if (rc) return rc;
-    const double b2 = square_as_python(bound);
-    g.Y = dY; g.tf = d_tf; g.out = d_out; g.item_begin = 0; g.item_count = c->n_veh; g.B = B;
-    g.sign = is_max ? -1.0 : 1.0; g.offset = is_max ? b2 : -b2; g.min_only = 0;
-    const size_t lds = sizeof(double) * ((size_t)2 * c->dim * (c->deg + 1) + 2 * c->deg + 1);
-    ScopedKernelTimer t(c, OBTG_K_SPEED);
-    hipLaunchKernelGGL(k_generic_normsq_elev<1>, dim3((unsigned)((size_t)B * c->n_veh)), dim3(kWave), lds, c->stream, g);
-    OBTG_HIP(c, hipGetLastError());
-    return OBTG_OK;
+    if (B <= 0 || f.items <= 0) return OBTG_OK;
+    return launch_generic_rows<MODE>(c, dY, f.d_tf, B, 0, f.items, 0, f.sign, f.offset, false, d_out);
+}
+
+RowFamily tsep_row_family(const obtg_ctx* c, double max_sep)
+{
+    return { ROWS_TSEP, c->n_pairs, OBTG_K_TEMPORAL_SEP, 1.0, 0.0 - square_as_python(max_sep), nullptr, rows_r0<0> };
+}
+
+RowFamily speed_row_family(const obtg_ctx* c, const double* d_tf, double bound, int is_max)
+{
+    RowFamily f{ ROWS_SPEED, c->n_veh, OBTG_K_SPEED, 0.0, 0.0, d_tf, rows_r0<1> };
+    speed_sign_offset(bound, is_max, f.sign, f.offset);
+    return f;
 }
 
 template <int NC>

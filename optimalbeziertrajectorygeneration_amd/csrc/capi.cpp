@@ -720,7 +720,8 @@ static size_t ysize(const obtg_ctx* c) { return (size_t)c->n_veh * c->dim * (c->
 // checks, a HostCall, its operands by name (in), its outputs by name (out), its launcher (run), the download -- optional
 // outputs first (fetch, skipped for a null pointer), the mandatory one last (finish: the call's ONE synchronise).  The slots
 // of ws_misc are obtg::WsSlot, and so is the rule for who may hold which.  The next entry point of the family starts as a
-// copy of obtg_speed (one output) or obtg_temporal_sep_true_min (optional outputs).
+// copy of obtg_speed (one output) or obtg_bern_extrema (optional outputs); the true-minimum row families have a path of
+// their own on top of this one (true_min_host, below).
 // What the entry points do NOT share, because a caller or a timing could tell -- each keeps the answer it has given since it
 // was added:
 //  - zero copy (mapped host memory; the one-row SLSQP callbacks): Y, tf and the result of obtg_temporal_sep[_min[_range]],
@@ -1595,21 +1596,78 @@ int obtg_bern_extrema(obtg_ctx* c, const double* coef, int M, int K, int want_ma
     return h.finish(val, dv, m);
 }
 
-// the fused kernel where the shape has one; else obtg_temporal_sep's rows at R = 0 into a workspace and obtg_bern_extrema on them
-static int true_min_launch(obtg_ctx* c, const double* dY, int B, double max_sep, double eps_rel, int max_nodes, double* d_out,
-                           double* d_t, int* d_status)
+// ------------------------------------------------------------------ the true-minimum row families
+// The one path of obtg_temporal_sep_true_min[_jac][_dev] and obtg_speed_true_min[_jac][_dev]: each entry point is its own
+// argument check and its family's descriptor (obtg_internal.h RowFamily); the launch chain (true_min_chain), the host body
+// (true_min_host) and the _dev body (true_min_dev) are shared.  The next family starts as a copy of the speed entry points.
+// What the entry points do NOT share -- each keeps the answer it has given since it was added:
+//  - check style: the separation calls check with a bool (true_min_args_ok), the speed calls with a code (speed_true_min_args);
+//  - deg > 31: the speed calls answer OBTG_ERR_UNSUPPORTED before the Y / jac check and before the empty batch;
+//    obtg_temporal_sep_true_min_jac answers it only from inside the chain (an empty batch or a context without pairs
+//    answers OBTG_OK first; its _dev twin has no such early answer); obtg_temporal_sep_true_min answers it from
+//    bern_extrema_supported(2 deg + 1), so only with items to evaluate;
+//  - the empty case: B == 0 || n_pairs == 0 for separation, B == 0 for speed, both after the pointer checks;
+//  - optional outputs: t_star, status, jac_tf; required: out, jac, tf;
+//  - launches per route, all timed under the family's kernel id: fused 1; blocks in a launch of their own on a listed
+//    degree (OBTG_TRUE_MIN_JAC_FUSED=0) 2; a degree off the list 2 for values, 3 with blocks.
+//
+// The chain: the fused kernel where the shape has one (with the blocks, d_jac set, only if true_min_jac_fused); else the
+// values -- the fused value kernel, or the family's rows at R = 0 into a workspace and obtg_bern_extrema on them -- and then
+// the blocks from Y and t_star in a launch of their own.
+static int true_min_chain(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double eps_rel, int max_nodes, double* d_out,
+                          double* d_t, int* d_status, double* d_jac, double* d_jac_tf)
 {
-    int rc = launch_temporal_sep_true_min(c, dY, B, max_sep, eps_rel, max_nodes, d_out, d_t, d_status);
+    if (d_jac && c->deg + 1 > 32) return OBTG_ERR_UNSUPPORTED;
+    int rc = OBTG_ERR_UNSUPPORTED;
+    if (!d_jac || c->true_min_jac_fused) rc = launch_true_min(c, f, dY, B, eps_rel, max_nodes, d_out, d_t, d_status, d_jac, d_jac_tf);
     if (rc != OBTG_ERR_UNSUPPORTED) return rc;
-    const int K = 2 * c->deg + 1;
-    if (!bern_extrema_supported(K)) return OBTG_ERR_UNSUPPORTED;
-    const long items = (long)B * c->n_pairs;
-    DevBuf& ws = c->ws_misc[WS_L_ROWS];
-    if ((rc = ws.reserve(sizeof(double) * (size_t)items * K))) return rc;
-    // DEG_ELEV does not enter: the any-degree kernel with R = 0 in its parameters, the context as it is
-    if ((rc = launch_temporal_sep_rows_r0_generic(c, dY, B, max_sep, ws.as<double>()))) return rc;
-    return launch_bern_extrema(c, ws.as<double>(), items, K, 0, eps_rel, 0.0, max_nodes, d_out, d_t, nullptr, nullptr, d_status,
-                               OBTG_K_TEMPORAL_SEP);
+    if (d_jac) {
+        if (!d_t) {
+            DevBuf& wt = c->ws_misc[WS_L_TSTAR];
+            if ((rc = wt.reserve(sizeof(double) * (size_t)B * f.items))) return rc;
+            d_t = wt.as<double>();
+        }
+        rc = launch_true_min(c, f, dY, B, eps_rel, max_nodes, d_out, d_t, d_status);
+    }
+    if (rc == OBTG_ERR_UNSUPPORTED) {
+        const int K = 2 * c->deg + 1;
+        if (!bern_extrema_supported(K)) return OBTG_ERR_UNSUPPORTED;
+        const long items = (long)B * f.items;
+        DevBuf& ws = c->ws_misc[WS_L_ROWS];
+        if ((rc = ws.reserve(sizeof(double) * (size_t)items * K))) return rc;
+        if ((rc = f.rows_r0(c, f, dY, B, ws.as<double>()))) return rc;
+        rc = launch_bern_extrema(c, ws.as<double>(), items, K, 0, eps_rel, 0.0, max_nodes, d_out, d_t, nullptr, nullptr, d_status,
+                                 f.kernel_id);
+    }
+    if (rc || !d_jac) return rc;
+    return launch_true_min_envelope(c, f, dY, B, d_t, d_jac, d_jac_tf);
+}
+
+// the host body: Y (and tf, where the family has one) up, val | t_star | jac_tf | jac in ws_out, status in WS_STATUS
+static int true_min_host(obtg_ctx* c, RowFamily f, const double* Y, const double* tf, int B, double eps_rel, int max_nodes,
+                         double* out, double* t_star, int* status, double* jac, double* jac_tf)
+{
+    const size_t n = (size_t)B * f.items, nj = jac ? n * c->dim * (c->deg + 1) : 0;
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    if (tf) f.d_tf = h.in(c->ws_in2, tf, (size_t)B, true);
+    double* dv = h.out<double>(c->ws_out, (jac ? 3 : 2) * n + nj);
+    int* ds = h.out<int>(c->ws_misc[WS_STATUS], n);
+    double* dj = jac ? dv + 3 * n : nullptr;
+    h.run([&] { return true_min_chain(c, f, dY, B, eps_rel, max_nodes, dv, dv + n, ds, dj, jac ? dv + 2 * n : nullptr); });
+    h.fetch(t_star, dv + n, n);
+    h.fetch(status, ds, n);
+    h.fetch(jac_tf, dv + 2 * n, n);
+    h.fetch(jac, dj, nj);
+    return h.finish(out, dv, n);
+}
+
+static int true_min_dev(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double eps_rel, int max_nodes, double* d_out,
+                        double* d_t_star, int* d_status, double* d_jac, double* d_jac_tf)
+{
+    (void)hipSetDevice(c->device);
+    return with_batch(c, dY, B, false, [&](const double* src) {
+        return true_min_chain(c, f, src, B, eps_rel, max_nodes, d_out, d_t_star, d_status, d_jac, d_jac_tf); });
 }
 
 // what obtg_temporal_sep_true_min[_jac] and their _dev twins check alike (the host calls: Y too; the _jac calls: jac too)
@@ -1622,9 +1680,7 @@ int obtg_temporal_sep_true_min_dev(obtg_ctx* c, const double* dY, int B, double 
                                    double* d_out, double* d_t_star, int* d_status)
 {
     if (!true_min_args_ok(c, d_out, B, max_nodes, eps_rel)) return OBTG_ERR_ARG;
-    (void)hipSetDevice(c->device);
-    return with_batch(c, dY, B, false, [&](const double* src) {
-        return true_min_launch(c, src, B, max_sep, eps_rel, max_nodes, d_out, d_t_star, d_status); });
+    return true_min_dev(c, tsep_row_family(c, max_sep), dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, nullptr, nullptr);
 }
 
 int obtg_temporal_sep_true_min(obtg_ctx* c, const double* Y, int B, double max_sep, double eps_rel, int max_nodes,
@@ -1632,42 +1688,14 @@ int obtg_temporal_sep_true_min(obtg_ctx* c, const double* Y, int B, double max_s
 {
     if (!true_min_args_ok(c, out, B, max_nodes, eps_rel) || !Y) return OBTG_ERR_ARG;
     if (B == 0 || c->n_pairs == 0) return OBTG_OK;
-    const size_t n = (size_t)B * c->n_pairs;
-    HostCall h(c);
-    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
-    double* dv = h.out<double>(c->ws_out, 2 * n);           // val | t_star
-    int* ds = h.out<int>(c->ws_misc[WS_STATUS], n);
-    h.run([&] { return true_min_launch(c, dY, B, max_sep, eps_rel, max_nodes, dv, dv + n, ds); });
-    h.fetch(t_star, dv + n, n);
-    h.fetch(status, ds, n);
-    return h.finish(out, dv, n);
-}
-
-// values, t_star, status as true_min_launch gives them, and the envelope blocks: in the same launch where the shape has a
-// fused kernel, else (or with OBTG_TRUE_MIN_JAC_FUSED=0) from Y and t_star in a launch of their own
-static int true_min_jac_launch(obtg_ctx* c, const double* dY, int B, double max_sep, double eps_rel, int max_nodes, double* d_out,
-                               double* d_t, int* d_status, double* d_jac)
-{
-    if (c->deg + 1 > 32) return OBTG_ERR_UNSUPPORTED;
-    int rc = OBTG_ERR_UNSUPPORTED;
-    if (c->true_min_jac_fused) rc = launch_temporal_sep_true_min(c, dY, B, max_sep, eps_rel, max_nodes, d_out, d_t, d_status, d_jac);
-    if (rc != OBTG_ERR_UNSUPPORTED) return rc;
-    if (!d_t) {
-        DevBuf& wt = c->ws_misc[WS_L_TSTAR];
-        if ((rc = wt.reserve(sizeof(double) * (size_t)B * c->n_pairs))) return rc;
-        d_t = wt.as<double>();
-    }
-    if ((rc = true_min_launch(c, dY, B, max_sep, eps_rel, max_nodes, d_out, d_t, d_status))) return rc;
-    return launch_temporal_sep_envelope(c, dY, B, d_t, d_jac);
+    return true_min_host(c, tsep_row_family(c, max_sep), Y, nullptr, B, eps_rel, max_nodes, out, t_star, status, nullptr, nullptr);
 }
 
 int obtg_temporal_sep_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, double max_sep, double eps_rel, int max_nodes,
                                        double* d_out, double* d_t_star, int* d_status, double* d_jac)
 {
     if (!true_min_args_ok(c, d_out, B, max_nodes, eps_rel) || !d_jac) return OBTG_ERR_ARG;
-    (void)hipSetDevice(c->device);
-    return with_batch(c, dY, B, false, [&](const double* src) {
-        return true_min_jac_launch(c, src, B, max_sep, eps_rel, max_nodes, d_out, d_t_star, d_status, d_jac); });
+    return true_min_dev(c, tsep_row_family(c, max_sep), dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, d_jac, nullptr);
 }
 
 int obtg_temporal_sep_true_min_jac(obtg_ctx* c, const double* Y, int B, double max_sep, double eps_rel, int max_nodes,
@@ -1675,34 +1703,7 @@ int obtg_temporal_sep_true_min_jac(obtg_ctx* c, const double* Y, int B, double m
 {
     if (!true_min_args_ok(c, out, B, max_nodes, eps_rel) || !Y || !jac) return OBTG_ERR_ARG;
     if (B == 0 || c->n_pairs == 0) return OBTG_OK;
-    const size_t n = (size_t)B * c->n_pairs, nj = n * c->dim * (c->deg + 1);
-    HostCall h(c);
-    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
-    double* dv = h.out<double>(c->ws_out, 2 * n + nj);      // val | t_star | jac
-    int* ds = h.out<int>(c->ws_misc[WS_STATUS], n);
-    h.run([&] { return true_min_jac_launch(c, dY, B, max_sep, eps_rel, max_nodes, dv, dv + n, ds, dv + 2 * n); });
-    h.fetch(t_star, dv + n, n);
-    h.fetch(status, ds, n);
-    h.fetch(jac, dv + 2 * n, nj);
-    return h.finish(out, dv, n);
-}
-
-// ------------------------------------------------------------------ the true speed rows
-// the fused kernel where the shape has one; else obtg_speed's rows at R = 0 into a workspace and obtg_bern_extrema on them
-static int speed_true_min_launch(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max, double eps_rel,
-                                 int max_nodes, double* d_out, double* d_t, int* d_status)
-{
-    int rc = launch_speed_true_min(c, dY, d_tf, B, bound, is_max, eps_rel, max_nodes, d_out, d_t, d_status);
-    if (rc != OBTG_ERR_UNSUPPORTED) return rc;
-    const int K = 2 * c->deg + 1;
-    if (!bern_extrema_supported(K)) return OBTG_ERR_UNSUPPORTED;
-    const long items = (long)B * c->n_veh;
-    DevBuf& ws = c->ws_misc[WS_L_ROWS];
-    if ((rc = ws.reserve(sizeof(double) * (size_t)items * K))) return rc;
-    // DEG_ELEV does not enter: the any-degree kernel with R = 0 in its parameters, the context as it is
-    if ((rc = launch_speed_rows_r0_generic(c, dY, d_tf, B, bound, is_max, ws.as<double>()))) return rc;
-    return launch_bern_extrema(c, ws.as<double>(), items, K, 0, eps_rel, 0.0, max_nodes, d_out, d_t, nullptr, nullptr, d_status,
-                               OBTG_K_SPEED);
+    return true_min_host(c, tsep_row_family(c, max_sep), Y, nullptr, B, eps_rel, max_nodes, out, t_star, status, jac, nullptr);
 }
 
 // what obtg_speed_true_min[_jac] and their _dev twins check alike (the host calls: Y too; the _jac calls: jac too)
@@ -1716,9 +1717,8 @@ int obtg_speed_true_min_dev(obtg_ctx* c, const double* dY, const double* d_tf, i
                             int max_nodes, double* d_out, double* d_t_star, int* d_status)
 {
     if (int rc = speed_true_min_args(c, d_tf, d_out, B, max_nodes, eps_rel)) return rc;
-    (void)hipSetDevice(c->device);
-    return with_batch(c, dY, B, false, [&](const double* src) {
-        return speed_true_min_launch(c, src, d_tf, B, bound, is_max != 0, eps_rel, max_nodes, d_out, d_t_star, d_status); });
+    return true_min_dev(c, speed_row_family(c, d_tf, bound, is_max), dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, nullptr,
+                        nullptr);
 }
 
 int obtg_speed_true_min(obtg_ctx* c, const double* Y, const double* tf, int B, double bound, int is_max, double eps_rel,
@@ -1727,35 +1727,8 @@ int obtg_speed_true_min(obtg_ctx* c, const double* Y, const double* tf, int B, d
     if (int rc = speed_true_min_args(c, tf, out, B, max_nodes, eps_rel)) return rc;
     if (!Y) return OBTG_ERR_ARG;
     if (B == 0) return OBTG_OK;
-    const size_t n = (size_t)B * c->n_veh;
-    HostCall h(c);
-    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
-    const double* d_tf = h.in(c->ws_in2, tf, (size_t)B, true);
-    double* dv = h.out<double>(c->ws_out, 2 * n);           // val | t_star
-    int* ds = h.out<int>(c->ws_misc[WS_STATUS], n);
-    h.run([&] { return speed_true_min_launch(c, dY, d_tf, B, bound, is_max != 0, eps_rel, max_nodes, dv, dv + n, ds); });
-    h.fetch(t_star, dv + n, n);
-    h.fetch(status, ds, n);
-    return h.finish(out, dv, n);
-}
-
-// values, t_star, status as speed_true_min_launch gives them, and the envelope blocks with their d/dtf: in the same launch
-// where the shape has a fused kernel, else (or with OBTG_TRUE_MIN_JAC_FUSED=0) from Y, tf and t_star in a launch of their own
-static int speed_true_min_jac_launch(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max,
-                                     double eps_rel, int max_nodes, double* d_out, double* d_t, int* d_status, double* d_jac,
-                                     double* d_jac_tf)
-{
-    int rc = OBTG_ERR_UNSUPPORTED;
-    if (c->true_min_jac_fused)
-        rc = launch_speed_true_min(c, dY, d_tf, B, bound, is_max, eps_rel, max_nodes, d_out, d_t, d_status, d_jac, d_jac_tf);
-    if (rc != OBTG_ERR_UNSUPPORTED) return rc;
-    if (!d_t) {
-        DevBuf& wt = c->ws_misc[WS_L_TSTAR];
-        if ((rc = wt.reserve(sizeof(double) * (size_t)B * c->n_veh))) return rc;
-        d_t = wt.as<double>();
-    }
-    if ((rc = speed_true_min_launch(c, dY, d_tf, B, bound, is_max, eps_rel, max_nodes, d_out, d_t, d_status))) return rc;
-    return launch_speed_envelope(c, dY, d_tf, B, is_max, d_t, d_jac, d_jac_tf);
+    return true_min_host(c, speed_row_family(c, nullptr, bound, is_max), Y, tf, B, eps_rel, max_nodes, out, t_star, status, nullptr,
+                         nullptr);
 }
 
 int obtg_speed_true_min_jac_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max, double eps_rel,
@@ -1763,10 +1736,8 @@ int obtg_speed_true_min_jac_dev(obtg_ctx* c, const double* dY, const double* d_t
 {
     if (int rc = speed_true_min_args(c, d_tf, d_out, B, max_nodes, eps_rel)) return rc;
     if (!d_jac) return OBTG_ERR_ARG;
-    (void)hipSetDevice(c->device);
-    return with_batch(c, dY, B, false, [&](const double* src) {
-        return speed_true_min_jac_launch(c, src, d_tf, B, bound, is_max != 0, eps_rel, max_nodes, d_out, d_t_star, d_status, d_jac,
-                                         d_jac_tf); });
+    return true_min_dev(c, speed_row_family(c, d_tf, bound, is_max), dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, d_jac,
+                        d_jac_tf);
 }
 
 int obtg_speed_true_min_jac(obtg_ctx* c, const double* Y, const double* tf, int B, double bound, int is_max, double eps_rel,
@@ -1775,19 +1746,8 @@ int obtg_speed_true_min_jac(obtg_ctx* c, const double* Y, const double* tf, int 
     if (int rc = speed_true_min_args(c, tf, out, B, max_nodes, eps_rel)) return rc;
     if (!Y || !jac) return OBTG_ERR_ARG;
     if (B == 0) return OBTG_OK;
-    const size_t n = (size_t)B * c->n_veh, nj = n * c->dim * (c->deg + 1);
-    HostCall h(c);
-    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
-    const double* d_tf = h.in(c->ws_in2, tf, (size_t)B, true);
-    double* dv = h.out<double>(c->ws_out, 3 * n + nj);      // val | t_star | jac_tf | jac
-    int* ds = h.out<int>(c->ws_misc[WS_STATUS], n);
-    h.run([&] { return speed_true_min_jac_launch(c, dY, d_tf, B, bound, is_max != 0, eps_rel, max_nodes, dv, dv + n, ds, dv + 3 * n,
-                                                 dv + 2 * n); });
-    h.fetch(t_star, dv + n, n);
-    h.fetch(status, ds, n);
-    h.fetch(jac_tf, dv + 2 * n, n);
-    h.fetch(jac, dv + 3 * n, nj);
-    return h.finish(out, dv, n);
+    return true_min_host(c, speed_row_family(c, nullptr, bound, is_max), Y, tf, B, eps_rel, max_nodes, out, t_star, status, jac,
+                         jac_tf);
 }
 
 // ------------------------------------------------------------------ single-curve algebra

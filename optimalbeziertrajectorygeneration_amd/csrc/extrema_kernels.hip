@@ -17,14 +17,14 @@
 // piece is lane 0's value level by level, the right piece what each lane holds when it stops.  No per-lane coefficient
 // arrays in the search (K is a run-time count up to 64), the stack is kExStack x (K + 3) doubles per wave.
 //
-// Envelope Jacobian (obtg_temporal_sep_true_min_jac): the derivative of a pair's polynomial at the t_star the search
-// returned, bern_device.h envelope_block -- written with explicit fma, so it is the same arithmetic here (contraction
-// off) as anywhere else.  Fused form: k_tsep_true_min<NC, DIM, true> re-reads the pair's control points from Y after
-// the search (the differences are dead by then: no register is held across wave_search for it) and every lane writes
-// its own block.  Two-launch form: the value path, then k_tsep_envelope on Y and t_star, any degree up to 31.
-//
-// True speed rows (obtg_speed_true_min[_jac]): the same search on a vehicle's own speed polynomial, k_speed_true_min, with
-// bern_device.h speed_envelope_block for the blocks and d/dtf; fused and two-launch forms as above (k_speed_envelope).
+// True-minimum row families (obtg_temporal_sep_true_min[_jac], obtg_speed_true_min[_jac]): the polynomial of a pair's
+// separation, of a vehicle's own speed, formed in the lane and searched as above -- one kernel body (true_min_body) over a
+// family struct (TsepRows, SpeedRows), under the kernel names k_tsep_true_min / k_speed_true_min.
+// Envelope Jacobian: the derivative of the item's polynomial at the t_star the search returned, bern_device.h
+// envelope_block / speed_envelope_block -- written with explicit fma, so it is the same arithmetic here (contraction off)
+// as anywhere else.  Fused form: the <NC, DIM, true> kernels re-read the item's control points from Y after the search (no
+// register is held across wave_search for it) and every lane writes its own block.  Two-launch form: the value path, then
+// k_tsep_envelope / k_speed_envelope on Y and t_star, any degree up to 31.
 #include <algorithm>
 #include <cfloat>
 
@@ -210,8 +210,14 @@ __global__ __launch_bounds__(kExWaves * kWave) void k_bern_extrema(const ExParam
     if (valid) ex_store(p, row, mine, neg);
 }
 
-// ---- fused: the separation polynomial of every (row, pair) formed in the lane (normsq_coeffs, the definition
-// obtg_temporal_sep's rows have at R = 0), then the same first step and the same search: the coefficients never reach memory
+// ---- the true-minimum row families: the polynomial of every item (a (row, pair), a (row, vehicle)) formed in the lane,
+// then the same first step and the same search: the coefficients never reach memory.  A family is a struct that names
+//   Params                  its parameter block (with ex, sign, offset: the outputs [M], the output transform of its rows),
+//   NC, L                   control points per curve, coefficients per item,
+//   coeffs(q, item, cf)     the item's coefficients BEFORE the output transform, as its rows have them at R = 0,
+//   envelope(q, item, nc, t) the item's envelope block(s) at t, nc <= NC control points at run time,
+// and two __global__ wrappers under names of their own (true_min_body, envelope_body; RowKernels finds them for the host).
+// The next family starts as a copy of SpeedRows.
 struct TsepExParams {
     const double* __restrict__ Y;      // [B][n_veh*DIM][NC]
     const double* __restrict__ obs;    // [n_obj - n_veh][DIM]
@@ -223,54 +229,106 @@ struct TsepExParams {
     double sign, offset;
 };
 
-// One item's envelope block at t (a lane's own item): the a side of obtg_temporal_sep_jac's conventions -- b's block is
-// the negation, an obstacle has no variable, a pair of two obstacles is all zeros.
-template <int NCMAX, int DIM>
-__device__ __forceinline__ void tsep_envelope_item(const TsepExParams& q, long item, int nc, double t)
-{
-    const int b = (int)(item / q.P), pr = (int)(item - (long)b * q.P);
-    const int2 ij = q.pairs[pr];
-    double* o = q.jac + (size_t)item * (DIM * nc);
-    if (ij.x >= q.n_veh) {
-        for (int e = 0; e < DIM * nc; ++e) o[e] = 0.0;
-        return;
+// obtg_temporal_sep's rows: normsq_coeffs of the pair's differences.  The envelope block is the a side of
+// obtg_temporal_sep_jac's conventions -- b's block is the negation, an obstacle has no variable, a pair of two obstacles is
+// all zeros; the fused form re-reads the pair's control points from Y (the differences are dead by then).
+template <int NC_, int DIM>
+struct TsepRows {
+    using Params = TsepExParams;
+    static constexpr int NC = NC_, L = 2 * NC_ - 1;
+    static __device__ __forceinline__ void coeffs(const Params& q, long item, double (&cf)[L])
+    {
+        const int b = (int)(item / q.P), pr = (int)(item - (long)b * q.P);
+        const int2 ij = q.pairs[pr];
+        const double* Yrow = q.Y + (size_t)b * q.n_veh * (DIM * NC);
+        double a[DIM][NC];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d)
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const double xi = ij.x < q.n_veh ? Yrow[(size_t)(ij.x * DIM + d) * NC + c] : q.obs[(ij.x - q.n_veh) * DIM + d];
+                const double xj = ij.y < q.n_veh ? Yrow[(size_t)(ij.y * DIM + d) * NC + c] : q.obs[(ij.y - q.n_veh) * DIM + d];
+                a[d][c] = xi - xj;
+            }
+        normsq_coeffs<NC, DIM>(a, as_ctab(q.W2), cf);
     }
-    const double* Yrow = q.Y + (size_t)b * q.n_veh * (DIM * nc);
-    const double* ya = Yrow + (size_t)ij.x * (DIM * nc);
-    const bool veh = ij.y < q.n_veh;
-    const double* yb = veh ? Yrow + (size_t)ij.y * (DIM * nc) : q.obs + (size_t)(ij.y - q.n_veh) * DIM;
-    envelope_block<NCMAX, DIM>(ya, yb, veh ? nc : 1, veh ? 1 : 0, nc, t, o);
-}
+    static __device__ __forceinline__ void envelope(const Params& q, long item, int nc, double t)
+    {
+        const int b = (int)(item / q.P), pr = (int)(item - (long)b * q.P);
+        const int2 ij = q.pairs[pr];
+        double* o = q.jac + (size_t)item * (DIM * nc);
+        if (ij.x >= q.n_veh) {
+            for (int e = 0; e < DIM * nc; ++e) o[e] = 0.0;
+            return;
+        }
+        const double* Yrow = q.Y + (size_t)b * q.n_veh * (DIM * nc);
+        const double* ya = Yrow + (size_t)ij.x * (DIM * nc);
+        const bool veh = ij.y < q.n_veh;
+        const double* yb = veh ? Yrow + (size_t)ij.y * (DIM * nc) : q.obs + (size_t)(ij.y - q.n_veh) * DIM;
+        envelope_block<NC, DIM>(ya, yb, veh ? nc : 1, veh ? 1 : 0, nc, t, o);
+    }
+};
 
-template <int NC, int DIM, bool JAC>
-__global__ __launch_bounds__(kExWaves * kWave) void k_tsep_true_min(const TsepExParams q)
+struct SpeedExParams {
+    const double* __restrict__ Y;      // [B][n_veh*DIM][NC]
+    const double* __restrict__ tf;     // [B]
+    const double* __restrict__ W2;
+    ExParams ex;                       // outputs [B][n_veh]; c unused
+    double* __restrict__ jac;          // [B][n_veh][DIM][NC] (the envelope forms)
+    double* __restrict__ jac_tf;       // [B][n_veh], nullable
+    int n_veh;
+    double sign, offset;
+};
+
+// obtg_speed's rows, q(t) = sign (DIM/2) |c'(t)|^2 + offset of a vehicle: diff_elev1_speed_rows per coordinate
+// (k_normsq_elev's speed path leaves the contraction of that step to the compiler: bern_device.h states what it comes to,
+// with explicit fma), then normsq_coeffs.  The envelope is the vehicle's block and its d/dtf.
+template <int NC_, int DIM>
+struct SpeedRows {
+    using Params = SpeedExParams;
+    static constexpr int NC = NC_, L = 2 * NC_ - 1;
+    static __device__ __forceinline__ void coeffs(const Params& q, long item, double (&cf)[L])
+    {
+        const int b = (int)(item / q.n_veh);
+        const double* v = q.Y + (size_t)item * (DIM * NC);
+        const double val = (double)(NC - 1) / q.tf[b];       // Bezier.diff(): (n/T)(P_{i+1} - P_i), then elev(1)
+        double a[DIM][NC];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) {
+            double x[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) x[c] = v[d * NC + c];
+            diff_elev1_speed_rows<NC>(x, val, a[d]);
+        }
+        normsq_coeffs<NC, DIM>(a, as_ctab(q.W2), cf);
+    }
+    static __device__ __forceinline__ void envelope(const Params& q, long item, int nc, double t)
+    {
+        const int b = (int)(item / q.n_veh);
+        const double dtf = speed_envelope_block<NC, DIM>(q.Y + (size_t)item * (DIM * nc), nc, q.tf[b], q.sign, t,
+                                                         q.jac + (size_t)item * (DIM * nc));
+        if (q.jac_tf) q.jac_tf[item] = dtf;
+    }
+};
+
+// The fused kernel of a family F: one item per lane -- its coefficients, the output transform as one fma (sign is +-1: the
+// product is exact, fused or not; this is the R = 0 row's value), the first step -- then the whole wave on each item that
+// needs the search, in lane order; JAC: every lane writes its own envelope block at the t_star it holds.
+template <class F, bool JAC>
+__device__ __forceinline__ void true_min_body(const typename F::Params& q)
 {
-    using S = NsShape<NC, DIM>;
-    constexpr int L = S::L;
+    constexpr int L = F::L;
     extern __shared__ double lds[];
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     double* stk = lds + (size_t)wave * kExStack * (L + 3);
     const ExParams& p = q.ex;
     const long item = ((long)blockIdx.x * kExWaves + wave) * kWave + lane;
     const bool valid = item < p.M;
-    const long it = valid ? item : p.M - 1;
-    const int b = (int)(it / q.P), pr = (int)(it - (long)b * q.P);
-    const int2 ij = q.pairs[pr];
-    const double* Yrow = q.Y + (size_t)b * q.n_veh * S::VLEN;
-    double a[DIM][NC];
-#pragma unroll
-    for (int d = 0; d < DIM; ++d)
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const double xi = ij.x < q.n_veh ? Yrow[(size_t)(ij.x * DIM + d) * NC + c] : q.obs[(ij.x - q.n_veh) * DIM + d];
-            const double xj = ij.y < q.n_veh ? Yrow[(size_t)(ij.y * DIM + d) * NC + c] : q.obs[(ij.y - q.n_veh) * DIM + d];
-            a[d][c] = xi - xj;
-        }
     double cf[L];
-    normsq_coeffs<NC, DIM>(a, as_ctab(q.W2), cf);
+    F::coeffs(q, valid ? item : p.M - 1, cf);
     ExScan sc;
 #pragma unroll
-    for (int k = 0; k < L; ++k) { cf[k] = fma(q.sign, cf[k], q.offset); sc.put(cf[k], k); }   // the R = 0 row's value (sign = 1)
+    for (int k = 0; k < L; ++k) { cf[k] = fma(q.sign, cf[k], q.offset); sc.put(cf[k], k); }
     ExOut mine;
     double tol;
     const bool need = !ex_first(sc, p.eps_rel, p.eps_abs, mine, tol) && valid;
@@ -286,98 +344,28 @@ __global__ __launch_bounds__(kExWaves * kWave) void k_tsep_true_min(const TsepEx
         if (lane == src) mine = o;
     }
     if (valid) ex_store(p, item, mine, false);
-    if (JAC && valid) tsep_envelope_item<NC, DIM>(q, item, NC, mine.t);
+    if (JAC && valid) F::envelope(q, item, F::NC, mine.t);
 }
 
-// the blocks alone, from Y and the t_star of an earlier launch: one item per lane, nc <= kEnvMaxNC at run time
+// The blocks alone, from the family's operands and the t_star of an earlier launch: one item per lane, nc <= kEnvMaxNC at
+// run time (F is the family at NC = kEnvMaxNC)
 constexpr int kEnvMaxNC = 32;
 constexpr int kEnvThreads = 128;
-template <int DIM>
-__global__ __launch_bounds__(kEnvThreads) void k_tsep_envelope(const TsepExParams q, const int nc)
+template <class F>
+__device__ __forceinline__ void envelope_body(const typename F::Params& q, const int nc)
 {
     const long item = (long)blockIdx.x * kEnvThreads + threadIdx.x;
-    if (item < q.ex.M) tsep_envelope_item<kEnvMaxNC, DIM>(q, item, nc, q.ex.t[item]);
-}
-
-// ---- the true speed rows: q(t) = sign (DIM/2) |c'(t)|^2 + offset of every (row, vehicle), the minimum over t of each
-// (obtg_speed_true_min[_jac]).  The coefficients are those of obtg_speed's rows at R = 0 -- diff_elev1_speed_rows per
-// coordinate (k_normsq_elev's speed path leaves the contraction of that step to the compiler: bern_device.h states what it
-// comes to, with explicit fma), normsq_coeffs, the output transform as one fma (sign is +-1: the product is exact, fused or
-// not) -- then the same first step and the same search as above.
-struct SpeedExParams {
-    const double* __restrict__ Y;      // [B][n_veh*DIM][NC]
-    const double* __restrict__ tf;     // [B]
-    const double* __restrict__ W2;
-    ExParams ex;                       // outputs [B][n_veh]; c unused
-    double* __restrict__ jac;          // [B][n_veh][DIM][NC] (the envelope forms)
-    double* __restrict__ jac_tf;       // [B][n_veh], nullable
-    int n_veh;
-    double sign, offset;
-};
-
-// One item's envelope block and d/dtf at t (a lane's own item)
-template <int NCMAX, int DIM>
-__device__ __forceinline__ void speed_envelope_item(const SpeedExParams& q, long item, int nc, double t)
-{
-    const int b = (int)(item / q.n_veh);
-    const double dtf = speed_envelope_block<NCMAX, DIM>(q.Y + (size_t)item * (DIM * nc), nc, q.tf[b], q.sign, t,
-                                                        q.jac + (size_t)item * (DIM * nc));
-    if (q.jac_tf) q.jac_tf[item] = dtf;
+    if (item < q.ex.M) F::envelope(q, item, nc, q.ex.t[item]);
 }
 
 template <int NC, int DIM, bool JAC>
-__global__ __launch_bounds__(kExWaves * kWave) void k_speed_true_min(const SpeedExParams q)
-{
-    using S = NsShape<NC, DIM>;
-    constexpr int L = S::L;
-    extern __shared__ double lds[];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    double* stk = lds + (size_t)wave * kExStack * (L + 3);
-    const ExParams& p = q.ex;
-    const long item = ((long)blockIdx.x * kExWaves + wave) * kWave + lane;
-    const bool valid = item < p.M;
-    const long it = valid ? item : p.M - 1;
-    const int b = (int)(it / q.n_veh);
-    const double* v = q.Y + (size_t)it * S::VLEN;
-    const double val = (double)S::N / q.tf[b];           // Bezier.diff(): (n/T)(P_{i+1} - P_i), then elev(1)
-    double a[DIM][NC];
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) {
-        double x[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) x[c] = v[d * NC + c];
-        diff_elev1_speed_rows<NC>(x, val, a[d]);
-    }
-    double cf[L];
-    normsq_coeffs<NC, DIM>(a, as_ctab(q.W2), cf);
-    ExScan sc;
-#pragma unroll
-    for (int k = 0; k < L; ++k) { cf[k] = fma(q.sign, cf[k], q.offset); sc.put(cf[k], k); }   // the R = 0 row's value
-    ExOut mine;
-    double tol;
-    const bool need = !ex_first(sc, p.eps_rel, p.eps_abs, mine, tol) && valid;
-    unsigned long long mask = __ballot(need);
-    while (mask) {
-        const int src = __ffsll((long long)mask) - 1;
-        mask &= mask - 1;
-        double bb = INFINITY;
-#pragma unroll
-        for (int k = 0; k < L; ++k) { const double c = ex_lane(cf[k], src); if (lane == k) bb = c; }
-        const ExOut o = wave_search(bb, L, ex_lane(tol, src), ex_lane(sc.c0, src), ex_lane(sc.cl, src), ex_lane(sc.m, src),
-                                    p.max_nodes, stk);
-        if (lane == src) mine = o;
-    }
-    if (valid) ex_store(p, item, mine, false);
-    if (JAC && valid) speed_envelope_item<NC, DIM>(q, item, NC, mine.t);
-}
-
-// the blocks alone, from Y, tf and the t_star of an earlier launch: one item per lane, nc <= kEnvMaxNC at run time
+__global__ __launch_bounds__(kExWaves * kWave) void k_tsep_true_min(const TsepExParams q) { true_min_body<TsepRows<NC, DIM>, JAC>(q); }
 template <int DIM>
-__global__ __launch_bounds__(kEnvThreads) void k_speed_envelope(const SpeedExParams q, const int nc)
-{
-    const long item = (long)blockIdx.x * kEnvThreads + threadIdx.x;
-    if (item < q.ex.M) speed_envelope_item<kEnvMaxNC, DIM>(q, item, nc, q.ex.t[item]);
-}
+__global__ __launch_bounds__(kEnvThreads) void k_tsep_envelope(const TsepExParams q, const int nc) { envelope_body<TsepRows<kEnvMaxNC, DIM>>(q, nc); }
+template <int NC, int DIM, bool JAC>
+__global__ __launch_bounds__(kExWaves * kWave) void k_speed_true_min(const SpeedExParams q) { true_min_body<SpeedRows<NC, DIM>, JAC>(q); }
+template <int DIM>
+__global__ __launch_bounds__(kEnvThreads) void k_speed_envelope(const SpeedExParams q, const int nc) { envelope_body<SpeedRows<kEnvMaxNC, DIM>>(q, nc); }
 
 // =====================================================================================
 //  launchers
@@ -400,108 +388,90 @@ int launch_bern_extrema(obtg_ctx* c, const double* d_c, long M, int K, int want_
     return OBTG_OK;
 }
 
-// OBTG_ERR_UNSUPPORTED: not a shape of the fast-kernel list (the caller goes through obtg_temporal_sep's rows)
-// d_jac != nullptr: the fused envelope form (obtg_temporal_sep_true_min_jac), the same search and one launch
-int launch_temporal_sep_true_min(obtg_ctx* c, const double* dY, int B, double max_sep, double eps_rel, int max_nodes,
-                                 double* d_out, double* d_t, int* d_status, double* d_jac)
+// The host side of a device family: its kernels by shape, and its parameter block from the context and the descriptor
+// (everything but ex and the outputs, which the launchers below set for every family alike)
+template <template <int, int> class Rows> struct RowKernels;
+template <> struct RowKernels<TsepRows> {
+    template <int NC, int DIM, bool JAC> static auto fused() { return k_tsep_true_min<NC, DIM, JAC>; }
+    template <int DIM> static auto envelope() { return k_tsep_envelope<DIM>; }
+    static TsepExParams params(const obtg_ctx* c, const RowFamily& f, const double* dY, double* d_jac, double*)
+    {
+        TsepExParams q{};
+        q.Y = dY; q.obs = c->d_obs.as<double>(); q.pairs = c->d_pairs.as<int2>(); q.W2 = c->d_w2.as<double>();
+        q.n_veh = c->n_veh; q.P = f.items; q.jac = d_jac; q.sign = f.sign; q.offset = f.offset;
+        return q;
+    }
+};
+template <> struct RowKernels<SpeedRows> {
+    template <int NC, int DIM, bool JAC> static auto fused() { return k_speed_true_min<NC, DIM, JAC>; }
+    template <int DIM> static auto envelope() { return k_speed_envelope<DIM>; }
+    static SpeedExParams params(const obtg_ctx* c, const RowFamily& f, const double* dY, double* d_jac, double* d_jac_tf)
+    {
+        SpeedExParams q{};
+        q.Y = dY; q.tf = f.d_tf; q.W2 = c->d_w2.as<double>(); q.n_veh = c->n_veh; q.jac = d_jac; q.jac_tf = d_jac_tf;
+        q.sign = f.sign; q.offset = f.offset;
+        return q;
+    }
+};
+
+template <template <int, int> class Rows>
+static int launch_fused(obtg_ctx* c, const RowFamily& f, const double* dY, const ExParams& ex, double* d_jac, double* d_jac_tf)
 {
-    if (B <= 0 || c->n_pairs <= 0) return OBTG_OK;
+    auto q = RowKernels<Rows>::params(c, f, dY, d_jac, d_jac_tf);
+    q.ex = ex;
     const int nc = c->deg + 1;
-    if (!nc_in_sep(nc) || (c->dim != 2 && c->dim != 3)) return OBTG_ERR_UNSUPPORTED;
-    int rc = ensure_tables(c);
-    if (rc) return rc;
-    TsepExParams q{};
-    q.Y = dY; q.obs = c->d_obs.as<double>(); q.pairs = c->d_pairs.as<int2>(); q.W2 = c->d_w2.as<double>();
-    q.n_veh = c->n_veh; q.P = c->n_pairs; q.jac = d_jac;
-    q.sign = 1.0; q.offset = 0.0 - square_as_python(max_sep);
-    q.ex.val = d_out; q.ex.t = d_t; q.ex.status = d_status;
-    q.ex.M = (long)B * c->n_pairs; q.ex.K = 2 * c->deg + 1; q.ex.max_nodes = max_nodes; q.ex.eps_rel = eps_rel; q.ex.eps_abs = 0.0;
-    void (*kern)(const TsepExParams) = nullptr;
-#define OBTG_CASE(NC_, D_) if (nc == NC_ && c->dim == D_) kern = d_jac ? k_tsep_true_min<NC_, D_, true> : k_tsep_true_min<NC_, D_, false>;
+    void (*kern)(const decltype(q)) = nullptr;
+#define OBTG_CASE(NC_, D_) \
+    if (nc == NC_ && c->dim == D_) kern = d_jac ? RowKernels<Rows>::template fused<NC_, D_, true>() : RowKernels<Rows>::template fused<NC_, D_, false>();
 #define OBTG_CASE_D(NC_) OBTG_CASE(NC_, 2) OBTG_CASE(NC_, 3)
     OBTG_NC_SEP(OBTG_CASE_D)
 #undef OBTG_CASE_D
 #undef OBTG_CASE
     if (!kern) return OBTG_ERR_UNSUPPORTED;
-    const size_t lds = sizeof(double) * kExWaves * kExStack * (size_t)(q.ex.K + 3);
+    const size_t lds = sizeof(double) * kExWaves * kExStack * (size_t)(ex.K + 3);
     const long per_wg = kExWaves * kWave;
-    ScopedKernelTimer t(c, OBTG_K_TEMPORAL_SEP);
-    hipLaunchKernelGGL(kern, dim3((unsigned)((q.ex.M + per_wg - 1) / per_wg)), dim3(kExWaves * kWave), lds, c->stream, q);
+    ScopedKernelTimer t(c, f.kernel_id);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((ex.M + per_wg - 1) / per_wg)), dim3(kExWaves * kWave), lds, c->stream, q);
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;
 }
 
-// the blocks of the two-launch form: d_t holds the t_star of the value path
-int launch_temporal_sep_envelope(obtg_ctx* c, const double* dY, int B, const double* d_t, double* d_jac)
+int launch_true_min(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double eps_rel, int max_nodes, double* d_out,
+                    double* d_t, int* d_status, double* d_jac, double* d_jac_tf)
 {
-    if (B <= 0 || c->n_pairs <= 0) return OBTG_OK;
-    const int nc = c->deg + 1;
-    if (nc > kEnvMaxNC) return OBTG_ERR_UNSUPPORTED;
-    TsepExParams q{};
-    q.Y = dY; q.obs = c->d_obs.as<double>(); q.pairs = c->d_pairs.as<int2>(); q.jac = d_jac;
-    q.n_veh = c->n_veh; q.P = c->n_pairs;
-    q.ex.t = const_cast<double*>(d_t); q.ex.M = (long)B * c->n_pairs;
-    void (*kern)(const TsepExParams, int) = c->dim == 1 ? k_tsep_envelope<1> : c->dim == 2 ? k_tsep_envelope<2> : k_tsep_envelope<3>;
-    ScopedKernelTimer t(c, OBTG_K_TEMPORAL_SEP);
-    hipLaunchKernelGGL(kern, dim3((unsigned)((q.ex.M + kEnvThreads - 1) / kEnvThreads)), dim3(kEnvThreads), 0, c->stream, q, nc);
-    OBTG_HIP(c, hipGetLastError());
-    return OBTG_OK;
-}
-
-// the speed rows' sign and offset, as launch_speed sets them
-static void speed_transform(double bound, int is_max, double& sign, double& offset)
-{
-    const double b2 = square_as_python(bound);
-    sign = is_max ? -1.0 : 1.0;
-    offset = is_max ? b2 : -b2;
-}
-
-// OBTG_ERR_UNSUPPORTED: not a shape of the fast-kernel list (the caller goes through obtg_speed's R = 0 rows)
-// d_jac != nullptr: the fused envelope form (obtg_speed_true_min_jac), the same search and one launch; d_jac_tf nullable
-int launch_speed_true_min(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max, double eps_rel,
-                          int max_nodes, double* d_out, double* d_t, int* d_status, double* d_jac, double* d_jac_tf)
-{
-    if (B <= 0) return OBTG_OK;
-    const int nc = c->deg + 1;
-    if (!nc_in_sep(nc) || (c->dim != 2 && c->dim != 3)) return OBTG_ERR_UNSUPPORTED;
+    if (B <= 0 || f.items <= 0) return OBTG_OK;
+    if (!nc_in_sep(c->deg + 1) || (c->dim != 2 && c->dim != 3)) return OBTG_ERR_UNSUPPORTED;
     int rc = ensure_tables(c);
     if (rc) return rc;
-    SpeedExParams q{};
-    q.Y = dY; q.tf = d_tf; q.W2 = c->d_w2.as<double>(); q.n_veh = c->n_veh; q.jac = d_jac; q.jac_tf = d_jac_tf;
-    speed_transform(bound, is_max, q.sign, q.offset);
-    q.ex.val = d_out; q.ex.t = d_t; q.ex.status = d_status;
-    q.ex.M = (long)B * c->n_veh; q.ex.K = 2 * c->deg + 1; q.ex.max_nodes = max_nodes; q.ex.eps_rel = eps_rel; q.ex.eps_abs = 0.0;
-    void (*kern)(const SpeedExParams) = nullptr;
-#define OBTG_CASE(NC_, D_) if (nc == NC_ && c->dim == D_) kern = d_jac ? k_speed_true_min<NC_, D_, true> : k_speed_true_min<NC_, D_, false>;
-#define OBTG_CASE_D(NC_) OBTG_CASE(NC_, 2) OBTG_CASE(NC_, 3)
-    OBTG_NC_SEP(OBTG_CASE_D)
-#undef OBTG_CASE_D
-#undef OBTG_CASE
-    if (!kern) return OBTG_ERR_UNSUPPORTED;
-    const size_t lds = sizeof(double) * kExWaves * kExStack * (size_t)(q.ex.K + 3);
-    const long per_wg = kExWaves * kWave;
-    ScopedKernelTimer t(c, OBTG_K_SPEED);
-    hipLaunchKernelGGL(kern, dim3((unsigned)((q.ex.M + per_wg - 1) / per_wg)), dim3(kExWaves * kWave), lds, c->stream, q);
+    ExParams ex{};
+    ex.val = d_out; ex.t = d_t; ex.status = d_status;
+    ex.M = (long)B * f.items; ex.K = 2 * c->deg + 1; ex.max_nodes = max_nodes; ex.eps_rel = eps_rel; ex.eps_abs = 0.0;
+    return f.kind == ROWS_SPEED ? launch_fused<SpeedRows>(c, f, dY, ex, d_jac, d_jac_tf)
+                                : launch_fused<TsepRows>(c, f, dY, ex, d_jac, d_jac_tf);
+}
+
+template <template <int, int> class Rows>
+static int launch_blocks(obtg_ctx* c, const RowFamily& f, const double* dY, const ExParams& ex, double* d_jac, double* d_jac_tf)
+{
+    auto q = RowKernels<Rows>::params(c, f, dY, d_jac, d_jac_tf);
+    q.ex = ex;
+    void (*kern)(const decltype(q), int) = c->dim == 1 ? RowKernels<Rows>::template envelope<1>()
+                                           : c->dim == 2 ? RowKernels<Rows>::template envelope<2>() : RowKernels<Rows>::template envelope<3>();
+    ScopedKernelTimer t(c, f.kernel_id);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((ex.M + kEnvThreads - 1) / kEnvThreads)), dim3(kEnvThreads), 0, c->stream, q, c->deg + 1);
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;
 }
 
-// the blocks of the two-launch form: d_t holds the t_star of the value path
-int launch_speed_envelope(obtg_ctx* c, const double* dY, const double* d_tf, int B, int is_max, const double* d_t, double* d_jac,
-                          double* d_jac_tf)
+int launch_true_min_envelope(obtg_ctx* c, const RowFamily& f, const double* dY, int B, const double* d_t, double* d_jac,
+                             double* d_jac_tf)
 {
-    if (B <= 0) return OBTG_OK;
-    const int nc = c->deg + 1;
-    if (nc > kEnvMaxNC) return OBTG_ERR_UNSUPPORTED;
-    SpeedExParams q{};
-    q.Y = dY; q.tf = d_tf; q.n_veh = c->n_veh; q.jac = d_jac; q.jac_tf = d_jac_tf;
-    q.sign = is_max ? -1.0 : 1.0;
-    q.ex.t = const_cast<double*>(d_t); q.ex.M = (long)B * c->n_veh;
-    void (*kern)(const SpeedExParams, int) = c->dim == 1 ? k_speed_envelope<1> : c->dim == 2 ? k_speed_envelope<2> : k_speed_envelope<3>;
-    ScopedKernelTimer t(c, OBTG_K_SPEED);
-    hipLaunchKernelGGL(kern, dim3((unsigned)((q.ex.M + kEnvThreads - 1) / kEnvThreads)), dim3(kEnvThreads), 0, c->stream, q, nc);
-    OBTG_HIP(c, hipGetLastError());
-    return OBTG_OK;
+    if (B <= 0 || f.items <= 0) return OBTG_OK;
+    if (c->deg + 1 > kEnvMaxNC) return OBTG_ERR_UNSUPPORTED;
+    ExParams ex{};
+    ex.t = const_cast<double*>(d_t); ex.M = (long)B * f.items;
+    return f.kind == ROWS_SPEED ? launch_blocks<SpeedRows>(c, f, dY, ex, d_jac, d_jac_tf)
+                                : launch_blocks<TsepRows>(c, f, dY, ex, d_jac, d_jac_tf);
 }
 
 }  // namespace obtg

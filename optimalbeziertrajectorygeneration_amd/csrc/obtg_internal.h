@@ -73,11 +73,10 @@ struct KernelStat {
 // The rule the code relies on: an entry point holds (from its reservation to its last download) only names WITHOUT the L; a
 // launcher takes only WS_L_* names, and only those whose index none of its calling entry points holds across the call.
 // The chains that are two deep, by index:
-//   obtg_temporal_sep_true_min[_jac] holds 4 (WS_STATUS)
-//     -> true_min_jac_launch takes 6 (WS_L_TSTAR: only for a _dev caller that wants no t_star; the host call's is in ws_out)
-//     -> true_min_launch     takes 7 (WS_L_ROWS) across launch_temporal_sep_rows_r0_generic and launch_bern_extrema, which take none
-//   obtg_speed_true_min[_jac] holds 4 (WS_STATUS): the same chain through speed_true_min_jac_launch (6) and speed_true_min_launch (7:
-//     launch_speed_rows_r0_generic and launch_bern_extrema take none)
+//   obtg_temporal_sep_true_min[_jac], obtg_speed_true_min[_jac] hold 4 (WS_STATUS: true_min_host)
+//     -> true_min_chain takes 6 (WS_L_TSTAR: only with blocks in a launch of their own for a _dev caller that wants no t_star;
+//        the host call's is in ws_out) and 7 (WS_L_ROWS: degrees off the fast-kernel list) across the family's R = 0 rows
+//        launcher, launch_bern_extrema and launch_true_min_envelope, which take none
 //   obtg_temporal_sep_active holds 4 (WS_STATUS) -> launch_temporal_sep takes 7 (WS_L_ROWS: the any-degree selection)
 //   host_deriv_obj           holds none -> launch_deriv_energy_obj takes 3, 6, 4 (launch_bern_diff and launch_speed take none)
 //   obtg_bern_extrema        holds 3 (WS_INFO) -> launch_bern_extrema takes none
@@ -92,15 +91,15 @@ enum WsSlot {
     WS_INFO = 3,          // int[4 n_pairs]: counters and status of a curve search; flag | n_support or iters | status of a GJK call; nodes | status of obtg_bern_extrema
     WS_L_DIFF_A = 3,      //   launch_deriv_energy_obj: derivative passes, even ones
     WS_TRACE = 4,         // obtg_gjk_pairs: the support trace
-    WS_STATUS = 4,        //   int per value: the row indices of obtg_temporal_sep_active, the status of obtg_temporal_sep_true_min[_jac] and obtg_speed_true_min[_jac]
+    WS_STATUS = 4,        //   int per value: the row indices of obtg_temporal_sep_active, the status of the true-minimum row families (true_min_host)
     WS_L_SPEED = 4,       //   launch_deriv_energy_obj: the speed-style rows before their sum
     WS_STACK = 5,         // frame stacks (the frontiers of the robust searches)
     WS_OUT_TF = 5,        //   the d/dtf output of obtg_speed_jac, obtg_ang_rate_jac, obtg_deriv_energy_grad
     WS_QUEUE = 6,         // work-queue counter, and behind it obtg_min_dist's pair order
     WS_L_DIFF_B = 6,      //   launch_deriv_energy_obj: derivative passes, odd ones
-    WS_L_TSTAR = 6,       //   true_min_jac_launch, speed_true_min_jac_launch: t_star between the value launch and the envelope launch, when the caller wants none
+    WS_L_TSTAR = 6,       //   true_min_chain: t_star between the value launches and the envelope launch, when the caller wants none
     WS_L_TIMELINE = 6,    //   TimelineDump (gjk_kernels.hip; the one-launch sweeps, which no holder of WS_QUEUE calls)
-    WS_L_ROWS = 7,        // whole rows under a reduction: launch_temporal_sep's any-degree selection, true_min_launch's and speed_true_min_launch's R = 0 rows
+    WS_L_ROWS = 7,        // whole rows under a reduction: launch_temporal_sep's any-degree selection, true_min_chain's R = 0 rows
     WS_L_CHANGED = 7,     //   launch_gjk_swarm's de-duplicated sweep: which objects differ from row 0
     WS_COUNT = 8,
 };
@@ -234,7 +233,6 @@ int binrow_offset(obtg_ctx* c, int n);  // ensures row C(n,.) is resident; retur
 int comm_gather_pair_minima(::obtg_comm* m, obtg_ctx* c, const double* dY, int B, double max_sep, double* d_min_all);
 int launch_temporal_sep(obtg_ctx* c, const double* dY, int B, double max_sep, int pair_begin,
                         int pair_count, bool min_only, double* d_out, int sel_k = 0, int* d_sel_idx = nullptr);
-int launch_temporal_sep_rows_r0_generic(obtg_ctx* c, const double* dY, int B, double max_sep, double* d_out);   // full rows at R = 0, any-degree kernel, c->R not read
 struct NsParams;
 // What launch_gjk_swarm may fold into its 3-D sweep launch (k_pair_sweep_3d): the row's temporal-separation block and,
 // when d_out_speed is set, its speed rows.  did_* report what the launch took over.
@@ -267,7 +265,7 @@ int launch_one_vs_many_min_spans(obtg_ctx* c, const double* d_one, const double*
 int launch_bern_restrict(obtg_ctx* c, const double* d_in, int rows, int n, const double* d_span, const double* d_target, double* d_out);
 int launch_speed(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max,
                  double* d_out);
-int launch_speed_rows_r0_generic(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max, double* d_out);   // rows at R = 0, any-degree kernel, c->R not read
+void speed_sign_offset(double bound, int is_max, double& sign, double& offset);    // the output transform of the speed rows
 int launch_ang_rate(obtg_ctx* c, const double* dY, const double* d_tf, int B, double max_rate,
                     double* d_out);
 // DEG_ELEV > 0, planar: separation rows + speed / angular-rate rows in one launch; OBTG_ERR_UNSUPPORTED = not this shape
@@ -356,17 +354,28 @@ bool bern_extrema_supported(int K);                    // 1 <= K <= 64: a row is
 int launch_bern_extrema(obtg_ctx* c, const double* d_c, long M, int K, int want_max, double eps_rel, double eps_abs,
                         int max_nodes, double* d_val, double* d_t, double* d_bound, int* d_nodes, int* d_status,
                         int kernel_id = OBTG_K_BERN);     // every output but d_val nullable
-// the fused form for the fast-kernel list's shapes; OBTG_ERR_UNSUPPORTED: go through obtg_temporal_sep's R = 0 rows
-int launch_temporal_sep_true_min(obtg_ctx* c, const double* dY, int B, double max_sep, double eps_rel, int max_nodes,
-                                 double* d_out, double* d_t, int* d_status, double* d_jac = nullptr);   // d_jac: with the envelope blocks
-// the envelope blocks [B][P][dim][deg+1] from Y and the t_star of a value launch: any degree up to 31 (else OBTG_ERR_UNSUPPORTED)
-int launch_temporal_sep_envelope(obtg_ctx* c, const double* dY, int B, const double* d_t, double* d_jac);
-// the true speed rows (obtg_speed_true_min[_jac]), timed under OBTG_K_SPEED: the fused form for the fast-kernel list's shapes
-// (OBTG_ERR_UNSUPPORTED: go through obtg_speed's R = 0 rows); d_jac: with the envelope blocks, d_jac_tf (nullable) their d/dtf
-int launch_speed_true_min(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max, double eps_rel,
-                          int max_nodes, double* d_out, double* d_t, int* d_status, double* d_jac = nullptr, double* d_jac_tf = nullptr);
-// the envelope blocks [B][N][dim][deg+1] and d/dtf [B][N] from Y, tf and the t_star of a value launch: any degree up to 31
-int launch_speed_envelope(obtg_ctx* c, const double* dY, const double* d_tf, int B, int is_max, const double* d_t, double* d_jac,
-                          double* d_jac_tf);
+// A true-minimum row family (obtg_temporal_sep_true_min[_jac], obtg_speed_true_min[_jac]) as the host path sees it: what one
+// call of the family contributes beyond the arguments every family has.  On the device the family is a struct of
+// extrema_kernels.hip (TsepRows, SpeedRows), found by `kind`.
+enum RowKind { ROWS_TSEP, ROWS_SPEED };
+struct RowFamily {
+    RowKind kind;
+    int items;                  // per batch row: n_pairs | n_veh
+    int kernel_id;              // every launch of the call is timed under it
+    double sign, offset;        // the output transform of its rows
+    const double* d_tf;         // [B], device; null where the rows have no time span
+    // its full rows at R = 0 from the any-degree kernel, [B][items][2 deg + 1], whatever the context's DEG_ELEV is: the launch
+    // a context with R = 0 makes, bit for bit; the context is not touched
+    int (*rows_r0)(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);
+};
+RowFamily tsep_row_family(const obtg_ctx* c, double max_sep);                                         // bern_kernels.hip
+RowFamily speed_row_family(const obtg_ctx* c, const double* d_tf, double bound, int is_max);
+// the fused form for the fast-kernel list's shapes, one launch; OBTG_ERR_UNSUPPORTED: go through the family's R = 0 rows.
+// d_jac: with the envelope blocks [B][items][dim][deg+1]; d_jac_tf (nullable, speed): their d/dtf [B][items]
+int launch_true_min(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double eps_rel, int max_nodes, double* d_out,
+                    double* d_t, int* d_status, double* d_jac = nullptr, double* d_jac_tf = nullptr);
+// the blocks alone from Y (tf) and the t_star of a value launch: any degree up to 31 (else OBTG_ERR_UNSUPPORTED)
+int launch_true_min_envelope(obtg_ctx* c, const RowFamily& f, const double* dY, int B, const double* d_t, double* d_jac,
+                             double* d_jac_tf);
 
 }  // namespace obtg

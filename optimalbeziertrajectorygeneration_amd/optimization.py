@@ -167,12 +167,14 @@ _MODEL_FIELDS = (
 )
 
 
-def _raise_first_md(status):
-    """The exception of the first pair, in list order, whose search did not end (bezier._raise_md): what the reference
-    would hit first in its pair loop (optimization.py:127-131)."""
-    bad = np.nonzero(np.asarray(status) != _capi.MD_OK)[0]
+def _md_checked(r, what='minDist'):
+    """r, the dict of a search call -- unless one of its searches did not end: then the exception of the first status, in list
+    order, that is not MD_OK (bezier._raise_md): what the reference would hit first in its pair loop (optimization.py:127-131)."""
+    status = np.asarray(r['status']).ravel()
+    bad = np.flatnonzero(status != _capi.MD_OK)
     if bad.size:
-        bez._raise_md(int(status[bad[0]]))
+        bez._raise_md(int(status[bad[0]]), what)
+    return r
 
 
 def _min_dist_call(curves, pa, pb, robust):
@@ -388,11 +390,8 @@ class BezOptimization(object):
         return self._true_min_checked(ctx, Y)['val']
 
     def _true_min_checked(self, ctx, Y):
-        r = ctx.temporal_sep_true_min(Y, self.model['maxSep'], eps_rel=self.TRUE_MIN_EPS_REL)
-        bad = np.flatnonzero(r['status'].ravel() != _capi.MD_OK)
-        if bad.size:
-            bez._raise_md(int(r['status'].ravel()[bad[0]]), 'temporalSeparationConstraints(true_min)')
-        return r
+        return _md_checked(ctx.temporal_sep_true_min(Y, self.model['maxSep'], eps_rel=self.TRUE_MIN_EPS_REL),
+                           'temporalSeparationConstraints(true_min)')
 
     def trueMinSeparation(self, x):
         """(val[P], t_star[P]): per pair of vehicles / point obstacles, in the order of temporalSeparationConstraints, the true
@@ -407,14 +406,7 @@ class BezOptimization(object):
         out of budget raises (bezier._raise_md)"""
         is_max = family == 'vmax'
         r = ctx.speed_true_min(Y, tf, self.model['maxSpeed' if is_max else 'minSpeed'], is_max, eps_rel=self.TRUE_MIN_EPS_REL)
-        self._raise_speed_md(r, ('maxSpeedConstraints' if is_max else 'minSpeedConstraints') + '(true_min)')
-        return r['val']
-
-    @staticmethod
-    def _raise_speed_md(r, what):
-        bad = np.flatnonzero(r['status'].ravel() != _capi.MD_OK)
-        if bad.size:
-            bez._raise_md(int(r['status'].ravel()[bad[0]]), what)
+        return _md_checked(r, ('maxSpeedConstraints' if is_max else 'minSpeedConstraints') + '(true_min)')['val']
 
     def trueSpeedRange(self, x):
         """(min_val[N], t_min[N], max_val[N], t_max[N]): per vehicle the true extrema over the trajectory of (d/2)|dv/dt|^2
@@ -425,7 +417,7 @@ class BezOptimization(object):
         lo = ctx.speed_true_min(Y, tf, 0.0, False, eps_rel=self.TRUE_MIN_EPS_REL)
         hi = ctx.speed_true_min(Y, tf, 0.0, True, eps_rel=self.TRUE_MIN_EPS_REL)
         for r in (lo, hi):
-            self._raise_speed_md(r, 'trueSpeedRange')
+            _md_checked(r, 'trueSpeedRange')
         return lo['val'][0], lo['t_star'][0], -hi['val'][0], hi['t_star'][0]
 
     def _timeopt(self):
@@ -572,7 +564,7 @@ class BezOptimization(object):
         r = _min_dist_call(stack, pa, pb, robust)
         if robust:
             return r['res'] - maxSep
-        _raise_first_md(r['status'])
+        _md_checked(r)
         return r['res'] - maxSep
 
     def _spatial_fd_values(self, x, robust):
@@ -616,7 +608,7 @@ class BezOptimization(object):
             if on_cap == 'nan':
                 res = np.where((r['status'] != 0)[:, None], np.nan, res)
             else:
-                _raise_first_md(r['status'])
+                _md_checked(r)
         F0 = res[:P] - maxSep
         if column is not None:           # the one column a driver hands to SLSQP: its (P, n_x) matrix alone (a third of the zeros to write)
             J1 = np.zeros((P, nx))
@@ -948,9 +940,7 @@ class BezOptimization(object):
         if n_obj < 2:
             return np.zeros((0, x.size))
         r = ctx.temporal_sep_true_min_jac(self.reshapeVectors(x[None]), self.model['maxSep'], eps_rel=self.TRUE_MIN_EPS_REL)
-        bad = np.flatnonzero(r['status'].ravel() != _capi.MD_OK)
-        if bad.size:
-            bez._raise_md(int(r['status'].ravel()[bad[0]]), 'temporalSeparationJacobian(envelope)')
+        _md_checked(r, 'temporalSeparationJacobian(envelope)')
         pa, pb = np.triu_indices(n_obj, 1)
         return self._scatter_exact(r['jac'][0][:, None], (pa, pb), (1.0, -1.0))      # blocks of one row each
 
@@ -960,7 +950,7 @@ class BezOptimization(object):
         r = self._ctx(False).speed_true_min_jac(self.reshapeVectors(x[None]), float(self._tf_of(x)),
                                                 self.model['maxSpeed' if is_max else 'minSpeed'], is_max,
                                                 eps_rel=self.TRUE_MIN_EPS_REL)
-        self._raise_speed_md(r, ('maxSpeedJacobian' if is_max else 'minSpeedJacobian') + '(envelope)')
+        _md_checked(r, ('maxSpeedJacobian' if is_max else 'minSpeedJacobian') + '(envelope)')
         N = self.model['numVeh']
         return self._scatter_exact(r['jac'][0][:, None], (np.arange(N),), (1.0,), r['jac_tf'][0][:, None])   # blocks of one row each
 

@@ -95,7 +95,9 @@ const char* obtg_strerror(int code);
  *      under OBTG_K_TEMPORAL_SEP).
  *      Later, still 7: new: obtg_min_dist_mixed, `_minDist` on curves of different degree (timed under OBTG_K_MIN_DIST).
  *      Later, still 7: new: the true speed rows obtg_speed_true_min[_dev] and their envelope Jacobian
- *      obtg_speed_true_min_jac[_dev] (timed under OBTG_K_SPEED). */
+ *      obtg_speed_true_min_jac[_dev] (timed under OBTG_K_SPEED).
+ *      Later, still 7: new: the true angular-rate rows obtg_ang_rate_true_min[_dev], their envelope Jacobian
+ *      obtg_ang_rate_true_min_jac[_dev] and the rows' polynomials obtg_ang_rate_poly[_dev] (timed under OBTG_K_ANG_RATE). */
 #define OBTG_ABI_VERSION 7
 int obtg_abi_version(void);
 
@@ -632,6 +634,47 @@ int obtg_speed_true_min_jac(obtg_ctx*, const double* Y, const double* tf /*[B]*/
                             double* jac /*[B][N][d][n+1]*/, double* jac_tf /*[B][N], nullable*/);
 int obtg_speed_true_min_jac_dev(obtg_ctx*, const double* dY, const double* d_tf, int B, double bound, int is_max, double eps_rel,
                                 int max_nodes, double* d_out, double* d_t_star, int* d_status, double* d_jac, double* d_jac_tf);
+/* The tight continuous-time angular-rate bound (dim 2).  With x' = x.diff(), x'' = x'.diff() (each the derivative followed by
+ * elev(1), degree n: optimization.py:543-574), den = x'^2 + y'^2 and num = y'' x' - x'' y' -- the weights and the numerator
+ * of _angularRate's rational curve, degree 2n -- |angular rate| <= max_rate for all t is, because den >= 0, the pair
+ *     p_+(t) = max_rate den(t) - num(t) >= 0  (side 0, left turns),     p_-(t) = max_rate den(t) + num(t) >= 0  (side 1, right turns).
+ * NOTE THE UNITS: these rows are max_rate * speed^2 -+ (turn rate * speed^2), NOT obtg_ang_rate's maxAngRate^2 - omega^2; a
+ * vehicle is feasible iff both are >= 0, 2 rows per vehicle whatever DEG_ELEV is (it does not enter; the context's R is not
+ * read).  They are meant for trajectories that do not stop: where the speed vanishes both polynomials vanish with it.
+ * obtg_ang_rate_poly: the Bernstein coefficients of both sides, out[B][N][2][2n+1],
+ *     p_k = fma(max_rate, den_k, -+num_k),  den_k / num_k the equal-degree products above (csrc/bern_device.h ang_row_coeff
+ *     states every operation; they are not the bits of obtg_ang_rate's intermediate products).
+ * obtg_ang_rate_true_min: out[B][N][2] = min over t in [0, 1] of p_+ / p_-, t_star and status as in obtg_speed_true_min; by
+ *     DEFINITION the bits of obtg_bern_extrema(eps_abs = 0, want_max = 0) on obtg_ang_rate_poly's rows.  A row with a
+ *     non-finite coefficient: val and t_star NaN, status OBTG_MD_OK.  A vehicle at rest: all coefficients zero, val +0.0.
+ * obtg_ang_rate_true_min_jac: the same out, t_star, status bit for bit, and the envelope (Danskin) block of every row at its
+ *     t_star.  With T = tf[b], w = B^(n-1)(t_star), u = B^(n-2)(t_star), entries out of range 0, sigma = +1 / -1 for side 0 / 1,
+ *         A_i = (n/T)(w_(i-1) - w_i),    C_i = (n(n-1)/T^2)(u_(i-2) - 2 u_(i-1) + u_i),
+ *         jac[B][N][2][2][n+1]:  jac[side][0][i] = 2 max_rate x' A_i - sigma (y'' A_i - y' C_i)
+ *                                jac[side][1][i] = 2 max_rate y' A_i - sigma (x' C_i - x'' A_i)
+ *         jac_tf[B][N][2] (nullable):  (-2 max_rate den + 3 sigma num) / T,
+ *     x', y', x'', y'', den, num at t_star from the same w and u (csrc/bern_device.h ang_envelope_block, every multiply-add an
+ *     explicit fma: host and _dev, fused and two-launch forms give the same bits).  t_star = 0 / 1 leave the first / last three
+ *     columns as the only non-zero ones.  A row with a non-finite coefficient gets a NaN block and a NaN jac_tf (status
+ *     OBTG_MD_OK); with another status the block is still the derivative at the returned t_star; a vehicle at rest has a zero
+ *     block.
+ * Checks as in obtg_speed_true_min[_jac] (t_star, status, jac_tf nullable; B == 0 is OBTG_OK); dim != 2: OBTG_ERR_ARG, as
+ * obtg_ang_rate; degrees above 31: OBTG_ERR_UNSUPPORTED.  Degrees 3, 5, 7, 8, 10, 15, 20 form the coefficients in registers, one
+ * launch (with the blocks too, unless the context was created under OBTG_TRUE_MIN_JAC_FUSED=0: then one more launch); other
+ * degrees from 1 to 31 go through a workspace of obtg_ang_rate_poly's rows (two launches, three with blocks).  Every launch
+ * is timed under OBTG_K_ANG_RATE.  tf <= 0 is the caller's business.  _dev: dY may be NULL inside an obtg_fd_view; d_tf is
+ * device memory, [B]. */
+int obtg_ang_rate_poly(obtg_ctx*, const double* Y, const double* tf /*[B]*/, int B, double max_rate, double* out /*[B][N][2][2n+1]*/);
+int obtg_ang_rate_poly_dev(obtg_ctx*, const double* dY, const double* d_tf, int B, double max_rate, double* d_out);
+int obtg_ang_rate_true_min(obtg_ctx*, const double* Y, const double* tf /*[B]*/, int B, double max_rate, double eps_rel, int max_nodes,
+                           double* out /*[B][N][2]*/, double* t_star /*[B][N][2], nullable*/, int* status /*[B][N][2], nullable*/);
+int obtg_ang_rate_true_min_dev(obtg_ctx*, const double* dY, const double* d_tf, int B, double max_rate, double eps_rel,
+                               int max_nodes, double* d_out, double* d_t_star, int* d_status);
+int obtg_ang_rate_true_min_jac(obtg_ctx*, const double* Y, const double* tf /*[B]*/, int B, double max_rate, double eps_rel,
+                               int max_nodes, double* out /*[B][N][2]*/, double* t_star /*nullable*/, int* status /*nullable*/,
+                               double* jac /*[B][N][2][2][n+1]*/, double* jac_tf /*[B][N][2], nullable*/);
+int obtg_ang_rate_true_min_jac_dev(obtg_ctx*, const double* dY, const double* d_tf, int B, double max_rate, double eps_rel,
+                                   int max_nodes, double* d_out, double* d_t_star, int* d_status, double* d_jac, double* d_jac_tf);
 
 /* ---- single-curve Bernstein algebra (the Bezier object's methods, batched over rows) ----
  * obtg_bern_elev:   Bezier.elev(R)      bezier.py:469-495   in[rows][n+1]   -> out[rows][n+R+1]

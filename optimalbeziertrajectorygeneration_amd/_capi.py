@@ -118,6 +118,12 @@ _SIGNATURES = {
     "obtg_speed_true_min_dev": (_i, [_vp, _vp, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp]),
     "obtg_speed_true_min_jac": (_i, [_vp, _vp, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "obtg_speed_true_min_jac_dev": (_i, [_vp, _vp, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_ang_rate_poly": (_i, [_vp, _vp, _vp, _i, _d, _vp]),
+    "obtg_ang_rate_poly_dev": (_i, [_vp, _vp, _vp, _i, _d, _vp]),
+    "obtg_ang_rate_true_min": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
+    "obtg_ang_rate_true_min_dev": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
+    "obtg_ang_rate_true_min_jac": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_ang_rate_true_min_jac_dev": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "obtg_bern_elev": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "obtg_bern_diff": (_i, [_vp, _vp, _i, _i, _d, _vp]),
     "obtg_bern_mul": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
@@ -544,15 +550,17 @@ class Context(object):
         return (out, idx) if with_index else out
 
     def _true_min(self, name, items, Y, tf, lead, eps_rel, max_nodes, *blocks):
-        """The allocation, the call and the dict of the true-minimum host calls, `items` values per row:
-        obtg_<family>(Y[, tf], B, *lead, eps_rel, max_nodes, val, t_star, status[, jac[, jac_tf]]); blocks names the last two."""
+        """The allocation, the call and the dict of the true-minimum host calls, `items` values per row (an int, or the
+        trailing shape of a row's values): obtg_<family>(Y[, tf], B, *lead, eps_rel, max_nodes, val, t_star, status[, jac[,
+        jac_tf]]); blocks names the last two."""
         Y, B = self._rows(Y)
         ops = [Y] if tf is None else [Y, self._tf(tf, B)]
-        r = dict(val=pinned_empty((B, items)), t_star=np.empty((B, items)), status=np.zeros((B, items), np.int32))
+        shape = (B,) + (tuple(items) if isinstance(items, tuple) else (items,))
+        r = dict(val=pinned_empty(shape), t_star=np.empty(shape), status=np.zeros(shape, np.int32))
         if "jac" in blocks:
-            r["jac"] = pinned_empty((B, items, self.dim, self.deg + 1))
+            r["jac"] = pinned_empty(shape + (self.dim, self.deg + 1))
         if "jac_tf" in blocks:
-            r["jac_tf"] = np.empty((B, items))
+            r["jac_tf"] = np.empty(shape)
         self._check(getattr(self._lib, name)(self._h, *[_ptr(a) for a in ops], B, *lead, float(eps_rel), int(max_nodes),
                                              *[_ptr(a) for a in r.values()]), name)
         return r
@@ -663,6 +671,44 @@ class Context(object):
         self._check(self._lib.obtg_speed_true_min_jac_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(bound), int(bool(is_max)),
                                                           float(eps_rel), int(max_nodes), _vp(d_out), _vp(d_t_star), _vp(d_status),
                                                           _vp(d_jac), _vp(d_jac_tf)), "obtg_speed_true_min_jac_dev")
+
+    def ang_rate_poly(self, Y, tf, max_rate):
+        """The true angular-rate rows' polynomials (obtg_ang_rate_poly; dim 2): [B][N][2][2 deg + 1] Bernstein coefficients of
+        p_+ = max_rate den - num (side 0) and p_- = max_rate den + num (side 1), den = x'^2 + y'^2, num = y'' x' - x'' y' --
+        in units of max_rate * speed^2, not ang_rate's maxAngRate^2 - omega^2."""
+        Y, B = self._rows(Y)
+        tf = self._tf(tf, B)
+        out = pinned_empty((B, self.n_veh, 2, 2 * self.deg + 1))
+        self._check(self._lib.obtg_ang_rate_poly(self._h, _ptr(Y), _ptr(tf), B, float(max_rate), _ptr(out)), "obtg_ang_rate_poly")
+        return out
+
+    def ang_rate_poly_dev(self, dY, d_tf, B, max_rate, d_out):
+        self._check(self._lib.obtg_ang_rate_poly_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(max_rate), _vp(d_out)),
+                    "obtg_ang_rate_poly_dev")
+
+    def ang_rate_true_min(self, Y, tf, max_rate, eps_rel=1e-9, max_nodes=100000):
+        """Per vehicle and side the true minimum over t in [0, 1] of ang_rate_poly's polynomial (obtg_ang_rate_true_min;
+        DEG_ELEV does not enter): dict(val[B][N][2], t_star[B][N][2], status[B][N][2] as MD_*); |angular rate| <= max_rate
+        on the whole trajectory iff both values of the vehicle are >= 0."""
+        return self._true_min("obtg_ang_rate_true_min", (self.n_veh, 2), Y, tf, (float(max_rate),), eps_rel, max_nodes)
+
+    def ang_rate_true_min_dev(self, dY, d_tf, B, max_rate, d_out, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
+        self._check(self._lib.obtg_ang_rate_true_min_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(max_rate), float(eps_rel),
+                                                         int(max_nodes), _vp(d_out), _vp(d_t_star), _vp(d_status)),
+                    "obtg_ang_rate_true_min_dev")
+
+    def ang_rate_true_min_jac(self, Y, tf, max_rate, eps_rel=1e-9, max_nodes=100000):
+        """ang_rate_true_min with its envelope Jacobian (obtg_ang_rate_true_min_jac): dict(val, t_star, status -- the bits of
+        ang_rate_true_min --, jac[B][N][2][2][deg+1]: d/d(the vehicle's own control points) of the side's polynomial at
+        t_star, jac_tf[B][N][2]: d/dtf at fixed control points)."""
+        return self._true_min("obtg_ang_rate_true_min_jac", (self.n_veh, 2), Y, tf, (float(max_rate),), eps_rel, max_nodes,
+                              "jac", "jac_tf")
+
+    def ang_rate_true_min_jac_dev(self, dY, d_tf, B, max_rate, d_out, d_jac, d_jac_tf=None, d_t_star=None, d_status=None,
+                                  eps_rel=1e-9, max_nodes=100000):
+        self._check(self._lib.obtg_ang_rate_true_min_jac_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(max_rate), float(eps_rel),
+                                                             int(max_nodes), _vp(d_out), _vp(d_t_star), _vp(d_status),
+                                                             _vp(d_jac), _vp(d_jac_tf)), "obtg_ang_rate_true_min_jac_dev")
 
     def ang_rate(self, Y, tf, max_rate):
         Y, B = self._rows(Y)

@@ -318,6 +318,103 @@ __device__ __forceinline__ double speed_envelope_block(const double* __restrict_
     return (-2.0 * ((sign * (0.5 * (double)DIM)) * ss)) / T;
 }
 
+// ---- The true angular-rate rows (obtg_ang_rate_poly, obtg_ang_rate_true_min[_jac]).  For a planar vehicle on a span T, with
+// x' = x.diff(), x'' = x'.diff() (each the derivative followed by elev(1): degree n) and the equal-degree product weights,
+//     den_k = sum_j w(k, j) (x'_j x'_(k-j) + y'_j y'_(k-j)),   num_k = sum_j w(k, j) (y''_j x'_(k-j) - x''_j y'_(k-j)),
+//     p_k   = fma(W, den_k, -+ num_k)            (sigma = +1: W den - num, left turns; sigma = -1: W den + num, right turns)
+// -- 2n + 1 coefficients per side, in units of W speed^2.  w(k, j) = C(n, j) C(n, k-j) / C(2n, k) is used in its separable
+// form: the operands come in as u_j = C(n, j) a_j and sk = 1 / C(2n, k) (capi.cpp ang_rows_table).  These two functions ARE
+// the definition of the rows: the fused kernels (register arrays, n and k known at compile time) and the any-degree rows
+// kernel (rows of LDS, n and k at run time) both call them, every multiply-add is an explicit fma, the sums run in index
+// order and contraction is switched off inside, so both give the same bits.  They do not reproduce dynamics2_group's.
+// diff_elev1_at: element c of Bezier.diff() of the n + 1 control points p, val = n / T (bezier.py:497-519).
+template <class A>
+__device__ __forceinline__ double diff_elev1_at(const A& p, const int c, const int n, const double val)
+{
+#pragma clang fp contract(off)
+    const double tl = c > 0 ? val * (p[c] - p[c - 1]) : 0.0;
+    const double tr = c < n ? val * (p[c + 1] - p[c]) : 0.0;
+    if (c == 0) return tr;
+    if (c == n) return tl;
+    return __builtin_fma((double)c / (double)n, tl, ((double)(n - c) / (double)n) * tr);
+}
+
+template <class A>
+__device__ __forceinline__ double ang_row_coeff(const A& ux, const A& uy, const A& uxx, const A& uyy, const int n, const int k,
+                                                const double sk, const double W, const double sigma)
+{
+#pragma clang fp contract(off)
+    const int jlo = k > n ? k - n : 0, jhi = k < n ? k : n;
+    double den = 0.0, num = 0.0;
+#pragma unroll
+    for (int j = jlo; j <= jhi; ++j) {
+        den = __builtin_fma(ux[j], ux[k - j], den);
+        den = __builtin_fma(uy[j], uy[k - j], den);
+        num = __builtin_fma(uyy[j], ux[k - j], num);
+        num = __builtin_fma(-uxx[j], uy[k - j], num);
+    }
+    const double den_k = sk * den, num_k = sk * num;
+    return __builtin_fma(W, den_k, -sigma * num_k);
+}
+
+// Envelope block of one side of one vehicle's angular-rate row at parameter t: the partial derivatives of
+// p_sigma(t) = W den(t) - sigma num(t) with respect to the vehicle's own control points and to T (obtg_ang_rate_true_min_jac).
+// With n = nc - 1, w = B^(n-1)(t), u = B^(n-2)(t), entries out of range 0:
+//     A_i = (n/T)(w_(i-1) - w_i),    C_i = (n(n-1)/T^2)(u_(i-2) - 2 u_(i-1) + u_i),
+//     out[0][i] = 2 W x' A_i - sigma (y'' A_i - y' C_i),    out[1][i] = 2 W y' A_i - sigma (x' C_i - x'' A_i),
+//     returns dp/dT = (-2 W den + 3 sigma num) / T,
+// x', y', x'', y'', den, num evaluated here from the same w and u.  y: the vehicle's [2][nc] control points.  Written as
+// speed_envelope_block is: u from the de Casteljau recurrence on the basis, w one more step of it; every multiply-add an
+// explicit fma, contraction off inside.  n = 1: u is empty, num = 0 and C = 0.  t = 0 / t = 1 leave the first / last three
+// columns as the only non-zero ones; a NaN t gives a NaN block (n >= 2) and a NaN dp/dT.
+template <int NCMAX>
+__device__ __forceinline__ double ang_envelope_block(const double* __restrict__ y, const int nc, const double T, const double W,
+                                                     const double sigma, const double t, double* __restrict__ out)
+{
+#pragma clang fp contract(off)
+    const int n = nc - 1;
+    const double s = 1.0 - t;
+    double u[NCMAX], w[NCMAX];             // u[0 .. n - 1): B^(n-2)(t); w[0 .. n): B^(n-1)(t); the rest stays zero
+#pragma unroll
+    for (int i = 0; i < NCMAX; ++i) u[i] = (i == 0 && n >= 2) ? 1.0 : 0.0;
+#pragma unroll
+    for (int r = 1; r < NCMAX - 2; ++r)
+        if (r < n - 1) {
+#pragma unroll
+            for (int i = r; i >= 1; --i) u[i] = __builtin_fma(t, u[i - 1], s * u[i]);
+            u[0] = s * u[0];
+        }
+#pragma unroll
+    for (int i = 0; i < NCMAX; ++i) w[i] = i == 0 ? s * u[0] : __builtin_fma(t, u[i - 1], s * u[i]);
+    if (n == 1) w[0] = 1.0;
+    const double nT = (double)n / T, nnT = nT * ((double)(n - 1) / T);
+    double d1[2], d2[2];                   // x', y' and x'', y'' at t
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        double a = 0.0, b = 0.0;
+#pragma unroll
+        for (int i = 0; i < NCMAX - 1; ++i)
+            if (i < n) a = __builtin_fma(w[i], y[c * nc + i + 1] - y[c * nc + i], a);
+#pragma unroll
+        for (int i = 0; i < NCMAX - 2; ++i)
+            if (i < n - 1) b = __builtin_fma(u[i], (y[c * nc + i + 2] - y[c * nc + i + 1]) - (y[c * nc + i + 1] - y[c * nc + i]), b);
+        d1[c] = nT * a;
+        d2[c] = nnT * b;
+    }
+    const double den = __builtin_fma(d1[1], d1[1], d1[0] * d1[0]);
+    const double num = __builtin_fma(d2[1], d1[0], -(d2[0] * d1[1]));
+    const double wx = (2.0 * W) * d1[0], wy = (2.0 * W) * d1[1];
+#pragma unroll
+    for (int i = 0; i < NCMAX; ++i)
+        if (i < nc) {
+            const double Ai = nT * ((i == 0 ? 0.0 : w[i - 1]) - w[i]);
+            const double Ci = nnT * (((i < 2 ? 0.0 : u[i - 2]) - (i == 0 ? 0.0 : u[i - 1])) - ((i == 0 ? 0.0 : u[i - 1]) - u[i]));
+            out[i] = __builtin_fma(wx, Ai, -sigma * __builtin_fma(d2[1], Ai, -(d1[1] * Ci)));
+            out[nc + i] = __builtin_fma(wy, Ai, -sigma * __builtin_fma(d1[0], Ci, -(d2[0] * Ai)));
+        }
+    return __builtin_fma(-2.0 * W, den, (3.0 * sigma) * num) / T;
+}
+
 // write a full [n_valid][LR] tile (pitch TP) as one contiguous run of n_valid*LR doubles
 template <int LR, int TP>
 __device__ __forceinline__ void flush_full(const double* __restrict__ tile, double* __restrict__ gout,

@@ -118,6 +118,15 @@ static std::vector<double> plain_product_weights(int n)
     return W;
 }
 
+// the true angular-rate rows' product weights in their separable form (bern_device.h ang_row_coeff): C(n, .), 1 / C(2n, .)
+static std::vector<double> ang_rows_table(int n)
+{
+    std::vector<double> W;
+    for (int j = 0; j <= n; ++j) W.push_back(binom(n, j));
+    for (int k = 0; k <= 2 * n; ++k) W.push_back(1.0 / binom(2 * n, k));
+    return W;
+}
+
 int ensure_tables(obtg_ctx* c)
 {
     if (c->tables_R == c->R) return OBTG_OK;
@@ -134,6 +143,10 @@ int ensure_tables(obtg_ctx* c)
             if ((rc = upload(c, c->d_ang_w2n, a.data(), a.size() * sizeof(double)))) return rc;
             if ((rc = upload(c, c->d_ang_w22n, b.data(), b.size() * sizeof(double)))) return rc;
             if ((rc = upload(c, c->d_ang_wn, w.data(), w.size() * sizeof(double)))) return rc;
+        }
+        if (c->dim == 2 && n >= 1 && n <= 31) {
+            auto t = ang_rows_table(n);
+            if ((rc = upload(c, c->d_ang_rows, t.data(), t.size() * sizeof(double)))) return rc;
         }
     }
     // the elevation tables belong to ONE R: a context that moves to R = 0 or beyond 512 must not keep the previous R's
@@ -237,6 +250,7 @@ const char* obtg_abi_symbols(void)
         "obtg_ctx_set_fd_dedup\0obtg_ctx_set_fd_view_structured\0obtg_ctx_set_gjk_history\0obtg_pair_sweep_dev\0obtg_constraint_sweep_dev\0obtg_constraint_sweep_fd_structured_dev\0obtg_constraint_sweep_fd_structured_rows_dev\0obtg_gjk_swarm_dev\0obtg_gjk_swarm\0obtg_min_dist\0obtg_min_dist_mixed\0obtg_min_dist_robust\0obtg_min_dist2poly\0obtg_min_dist2poly_robust\0obtg_gjk_true_pairs\0obtg_coll_check\0obtg_coll_check2poly\0"
         "obtg_bern_extrema\0obtg_bern_extrema_dev\0obtg_temporal_sep_true_min\0obtg_temporal_sep_true_min_dev\0obtg_temporal_sep_true_min_jac\0obtg_temporal_sep_true_min_jac_dev\0"
         "obtg_speed_true_min\0obtg_speed_true_min_dev\0obtg_speed_true_min_jac\0obtg_speed_true_min_jac_dev\0"
+        "obtg_ang_rate_poly\0obtg_ang_rate_poly_dev\0obtg_ang_rate_true_min\0obtg_ang_rate_true_min_dev\0obtg_ang_rate_true_min_jac\0obtg_ang_rate_true_min_jac_dev\0"
         "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_restrict\0obtg_bern_eval\0"
         "obtg_euclidean_obj\0obtg_accel_obj\0obtg_jerk_obj\0"
         "obtg_temporal_sep_jac\0obtg_temporal_sep_jac_dev\0obtg_speed_jac\0obtg_speed_jac_dev\0obtg_ang_rate_jac\0obtg_ang_rate_jac_dev\0obtg_euclidean_grad\0obtg_deriv_energy_grad\0"
@@ -271,7 +285,7 @@ int obtg_ctx_create(obtg_ctx** out, int n_veh, int dim, int deg, int deg_elev, i
     { const char* e = getenv("OBTG_ZERO_COPY"); const bool zc = !(e && e[0] == '0'); c->ws_in.io = c->ws_in2.io = c->ws_out.io = zc; }
     // OBTG_FD_VIEW_STRUCTURED=0: contexts start with the structured routing of a view's one-call sweep off (obtg_ctx_set_fd_view_structured)
     { const char* e = getenv("OBTG_FD_VIEW_STRUCTURED"); c->fd_view_structured = !(e && e[0] == '0'); }
-    // OBTG_TRUE_MIN_JAC_FUSED=0: obtg_temporal_sep_true_min_jac and obtg_speed_true_min_jac form their blocks in a launch of their own on every shape
+    // OBTG_TRUE_MIN_JAC_FUSED=0: obtg_temporal_sep_true_min_jac, obtg_speed_true_min_jac and obtg_ang_rate_true_min_jac form their blocks in a launch of their own on every shape
     { const char* e = getenv("OBTG_TRUE_MIN_JAC_FUSED"); c->true_min_jac_fused = !(e && e[0] == '0'); }
     int rc = OBTG_OK;
     c->h_pairs.resize((size_t)2 * c->n_pairs);
@@ -295,7 +309,7 @@ void obtg_ctx_destroy(obtg_ctx* c)
     (void)hipStreamSynchronize(c->stream);
     flush_pending_events(c);
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
-    DevBuf* bufs[] = { &c->d_pairs, &c->d_obs, &c->d_w2, &c->d_Tt, &c->d_Td, &c->d_Tf, &c->d_ang_dd, &c->d_ang_flags, &c->d_vp_off, &c->d_vp_idx, &c->d_ang_w2n, &c->d_ang_w22n, &c->d_ang_wn, &c->d_ang_T4, &c->d_ang_cv2, &c->d_jac,
+    DevBuf* bufs[] = { &c->d_pairs, &c->d_obs, &c->d_w2, &c->d_Tt, &c->d_Td, &c->d_Tf, &c->d_ang_dd, &c->d_ang_flags, &c->d_vp_off, &c->d_vp_idx, &c->d_ang_w2n, &c->d_ang_w22n, &c->d_ang_wn, &c->d_ang_rows, &c->d_ang_T4, &c->d_ang_cv2, &c->d_jac,
                        &c->d_binrows, &c->d_tiles, &c->d_poly_pts, &c->d_poly_off, &c->d_hp_a, &c->d_hp_b, &c->d_tile_chunk_off, &c->d_tile_order, &c->d_tile_pslots,
                        &c->d_tile_cobj_off, &c->d_tile_cobjs, &c->d_tile_ij, &c->ws_in,
                        &c->ws_in2, &c->ws_out, &c->ws_fd };
@@ -716,7 +730,7 @@ static size_t ysize(const obtg_ctx* c) { return (size_t)c->n_veh * c->dim * (c->
 
 // ------------------------------------------------------------------ the Bernstein-family host entry points
 // The one host path of obtg_temporal_sep[_min[_range]|_active|_fd|_jac|_true_min[_jac]], obtg_one_vs_many_min[_spans],
-// obtg_speed[_jac|_true_min[_jac]], obtg_ang_rate[_jac], obtg_bern_*, the objectives and their gradients.  Every one of them is: its argument
+// obtg_speed[_jac|_true_min[_jac]], obtg_ang_rate[_jac|_poly|_true_min[_jac]], obtg_bern_*, the objectives and their gradients.  Every one of them is: its argument
 // checks, a HostCall, its operands by name (in), its outputs by name (out), its launcher (run), the download -- optional
 // outputs first (fetch, skipped for a null pointer), the mandatory one last (finish: the call's ONE synchronise).  The slots
 // of ws_misc are obtg::WsSlot, and so is the rule for who may hold which.  The next entry point of the family starts as a
@@ -726,13 +740,14 @@ static size_t ysize(const obtg_ctx* c) { return (size_t)c->n_veh * c->dim * (c->
 // was added:
 //  - zero copy (mapped host memory; the one-row SLSQP callbacks): Y, tf and the result of obtg_temporal_sep[_min[_range]],
 //    obtg_speed, obtg_ang_rate and the objectives, Y of _active and _true_min[_jac], Y and tf of
-//    obtg_speed_true_min[_jac], `one` and the result of
+//    obtg_speed_true_min[_jac], obtg_ang_rate_true_min[_jac] and obtg_ang_rate_poly, `one` and the result of
 //    obtg_one_vs_many_min[_spans]; NOT the outputs of _active / _true_min*, and nothing of the _jac / _grad calls, of
 //    obtg_temporal_sep_fd, obtg_bern_extrema or obtg_bern_*;
 //  - an empty call with null pointers is OBTG_OK in obtg_one_vs_many_min[_spans] (B or K == 0), obtg_temporal_sep_fd (no
 //    perturbations, or fewer than two objects) and obtg_bern_extrema (M == 0); every other call rejects a null mandatory
 //    pointer first, and a context without pairs answers OBTG_OK only after that;
-//  - obtg_bern_extrema requires status, obtg_temporal_sep_true_min[_jac] and obtg_speed_true_min[_jac] take it as optional;
+//  - obtg_bern_extrema requires status, obtg_temporal_sep_true_min[_jac], obtg_speed_true_min[_jac] and
+//    obtg_ang_rate_true_min[_jac] take it as optional;
 //  - obtg_bern_normsq has no empty case (d >= 1); obtg_bern_restrict looks at every span before rows == 0 answers OBTG_OK;
 //  - obtg_ang_rate answers dim != 2 after its pointer checks, obtg_ang_rate_jac before them;
 //  - the _dev twins of the _jac calls answer OBTG_OK for B == 0 before the pointer checks, the host calls after them.
@@ -1597,9 +1612,11 @@ int obtg_bern_extrema(obtg_ctx* c, const double* coef, int M, int K, int want_ma
 }
 
 // ------------------------------------------------------------------ the true-minimum row families
-// The one path of obtg_temporal_sep_true_min[_jac][_dev] and obtg_speed_true_min[_jac][_dev]: each entry point is its own
-// argument check and its family's descriptor (obtg_internal.h RowFamily); the launch chain (true_min_chain), the host body
-// (true_min_host) and the _dev body (true_min_dev) are shared.  The next family starts as a copy of the speed entry points.
+// The one path of obtg_temporal_sep_true_min[_jac][_dev], obtg_speed_true_min[_jac][_dev] and
+// obtg_ang_rate_true_min[_jac][_dev]: each entry point is its own argument check and its family's descriptor
+// (obtg_internal.h RowFamily); the launch chain (true_min_chain), the host body (true_min_host) and the _dev body
+// (true_min_dev) are shared.  A further family starts as a copy of the speed entry points, as the angular-rate ones did
+// (they answer as the speed calls do, and dim != 2 with OBTG_ERR_ARG).
 // What the entry points do NOT share -- each keeps the answer it has given since it was added:
 //  - check style: the separation calls check with a bool (true_min_args_ok), the speed calls with a code (speed_true_min_args);
 //  - deg > 31: the speed calls answer OBTG_ERR_UNSUPPORTED before the Y / jac check and before the empty batch;
@@ -1748,6 +1765,69 @@ int obtg_speed_true_min_jac(obtg_ctx* c, const double* Y, const double* tf, int 
     if (B == 0) return OBTG_OK;
     return true_min_host(c, speed_row_family(c, nullptr, bound, is_max), Y, tf, B, eps_rel, max_nodes, out, t_star, status, jac,
                          jac_tf);
+}
+
+// what obtg_ang_rate_poly, obtg_ang_rate_true_min[_jac] and their _dev twins check alike: the speed calls' checks, and the
+// planar vehicle of obtg_ang_rate (the host calls: Y too; the _jac calls: jac too)
+static int ang_true_min_args(const obtg_ctx* c, const double* tf, const double* out, int B, int max_nodes, double eps_rel)
+{
+    if (!check_ctx(c) || c->dim != 2) return OBTG_ERR_ARG;
+    return speed_true_min_args(c, tf, out, B, max_nodes, eps_rel);
+}
+
+int obtg_ang_rate_poly_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double max_rate, double* d_out)
+{
+    if (int rc = ang_true_min_args(c, d_tf, d_out, B, 1, 0.0)) return rc;
+    (void)hipSetDevice(c->device);
+    const RowFamily f = ang_row_family(c, d_tf, max_rate);
+    return with_batch(c, dY, B, false, [&](const double* src) { return launch_ang_rows(c, f, src, B, d_out); });
+}
+
+int obtg_ang_rate_poly(obtg_ctx* c, const double* Y, const double* tf, int B, double max_rate, double* out)
+{
+    if (int rc = ang_true_min_args(c, tf, out, B, 1, 0.0)) return rc;
+    if (!Y) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    const size_t n = (size_t)B * c->n_veh * 2 * (2 * c->deg + 1);
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    const double* d_tf = h.in(c->ws_in2, tf, (size_t)B, true);
+    double* d_out = h.out<double>(c->ws_out, n);
+    h.run([&] { return launch_ang_rows(c, ang_row_family(c, d_tf, max_rate), dY, B, d_out); });
+    return h.finish(out, d_out, n);
+}
+
+int obtg_ang_rate_true_min_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double max_rate, double eps_rel,
+                               int max_nodes, double* d_out, double* d_t_star, int* d_status)
+{
+    if (int rc = ang_true_min_args(c, d_tf, d_out, B, max_nodes, eps_rel)) return rc;
+    return true_min_dev(c, ang_row_family(c, d_tf, max_rate), dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, nullptr, nullptr);
+}
+
+int obtg_ang_rate_true_min(obtg_ctx* c, const double* Y, const double* tf, int B, double max_rate, double eps_rel, int max_nodes,
+                           double* out, double* t_star, int* status)
+{
+    if (int rc = ang_true_min_args(c, tf, out, B, max_nodes, eps_rel)) return rc;
+    if (!Y) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    return true_min_host(c, ang_row_family(c, nullptr, max_rate), Y, tf, B, eps_rel, max_nodes, out, t_star, status, nullptr, nullptr);
+}
+
+int obtg_ang_rate_true_min_jac_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double max_rate, double eps_rel,
+                                   int max_nodes, double* d_out, double* d_t_star, int* d_status, double* d_jac, double* d_jac_tf)
+{
+    if (int rc = ang_true_min_args(c, d_tf, d_out, B, max_nodes, eps_rel)) return rc;
+    if (!d_jac) return OBTG_ERR_ARG;
+    return true_min_dev(c, ang_row_family(c, d_tf, max_rate), dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, d_jac, d_jac_tf);
+}
+
+int obtg_ang_rate_true_min_jac(obtg_ctx* c, const double* Y, const double* tf, int B, double max_rate, double eps_rel, int max_nodes,
+                               double* out, double* t_star, int* status, double* jac, double* jac_tf)
+{
+    if (int rc = ang_true_min_args(c, tf, out, B, max_nodes, eps_rel)) return rc;
+    if (!Y || !jac) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    return true_min_host(c, ang_row_family(c, nullptr, max_rate), Y, tf, B, eps_rel, max_nodes, out, t_star, status, jac, jac_tf);
 }
 
 // ------------------------------------------------------------------ single-curve algebra

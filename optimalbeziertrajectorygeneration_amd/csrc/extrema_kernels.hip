@@ -17,14 +17,15 @@
 // piece is lane 0's value level by level, the right piece what each lane holds when it stops.  No per-lane coefficient
 // arrays in the search (K is a run-time count up to 64), the stack is kExStack x (K + 3) doubles per wave.
 //
-// True-minimum row families (obtg_temporal_sep_true_min[_jac], obtg_speed_true_min[_jac]): the polynomial of a pair's
-// separation, of a vehicle's own speed, formed in the lane and searched as above -- one kernel body (true_min_body) over a
-// family struct (TsepRows, SpeedRows), under the kernel names k_tsep_true_min / k_speed_true_min.
+// True-minimum row families (obtg_temporal_sep_true_min[_jac], obtg_speed_true_min[_jac], obtg_ang_rate_true_min[_jac]): the
+// polynomial of a pair's separation, of a vehicle's own speed, of one side of its angular-rate bound, formed in the lane and
+// searched as above -- one kernel body (true_min_body) over a family struct (TsepRows, SpeedRows, AngRows), under the kernel
+// names k_tsep_true_min / k_speed_true_min / k_ang_true_min.
 // Envelope Jacobian: the derivative of the item's polynomial at the t_star the search returned, bern_device.h
-// envelope_block / speed_envelope_block -- written with explicit fma, so it is the same arithmetic here (contraction off)
-// as anywhere else.  Fused form: the <NC, DIM, true> kernels re-read the item's control points from Y after the search (no
+// envelope_block / speed_envelope_block / ang_envelope_block -- written with explicit fma, so it is the same arithmetic here
+// (contraction off) as anywhere else.  Fused form: the <NC, DIM, true> kernels re-read the item's control points from Y after the search (no
 // register is held across wave_search for it) and every lane writes its own block.  Two-launch form: the value path, then
-// k_tsep_envelope / k_speed_envelope on Y and t_star, any degree up to 31.
+// k_tsep_envelope / k_speed_envelope / k_ang_envelope on Y and t_star, any degree up to 31.
 #include <algorithm>
 #include <cfloat>
 
@@ -217,7 +218,7 @@ __global__ __launch_bounds__(kExWaves * kWave) void k_bern_extrema(const ExParam
 //   coeffs(q, item, cf)     the item's coefficients BEFORE the output transform, as its rows have them at R = 0,
 //   envelope(q, item, nc, t) the item's envelope block(s) at t, nc <= NC control points at run time,
 // and two __global__ wrappers under names of their own (true_min_body, envelope_body; RowKernels finds them for the host).
-// The next family starts as a copy of SpeedRows.
+// A further family starts as a copy of SpeedRows, as AngRows did.
 struct TsepExParams {
     const double* __restrict__ Y;      // [B][n_veh*DIM][NC]
     const double* __restrict__ obs;    // [n_obj - n_veh][DIM]
@@ -311,6 +312,60 @@ struct SpeedRows {
     }
 };
 
+struct AngExParams {
+    const double* __restrict__ Y;      // [B][n_veh*2][NC]
+    const double* __restrict__ tf;     // [B]
+    const double* __restrict__ tab;    // C(n, .)[n+1], then 1 / C(2n, .)[2n+1] (capi.cpp ang_rows_table)
+    ExParams ex;                       // outputs [B][n_veh][2]; c unused
+    double* __restrict__ jac;          // [B][n_veh][2][2][NC] (the envelope forms)
+    double* __restrict__ jac_tf;       // [B][n_veh][2], nullable
+    int n_veh;
+    double sign, offset;               // the identity (1, 0): W and the side enter in coeffs
+    double W;                          // the bound on |angular rate|
+};
+
+// The true angular-rate rows: item = (row, vehicle, side), side 0: p_+ = W den - num (sigma = +1), side 1: p_- = W den + num.
+// bern_device.h diff_elev1_at / ang_row_coeff define the coefficients (k_ang_rows below writes the same ones to memory);
+// the envelope is the side's block over the vehicle's control points and its d/dtf.  DIM is 2: the family has no other.
+template <int NC_, int DIM>
+struct AngRows {
+    using Params = AngExParams;
+    static constexpr int NC = NC_, L = 2 * NC_ - 1;
+    static __device__ __forceinline__ void coeffs(const Params& q, long item, double (&cf)[L])
+    {
+        constexpr int N = NC - 1;
+        const long veh = item >> 1;
+        const int b = (int)(veh / q.n_veh);
+        const double sigma = (item & 1) ? -1.0 : 1.0;
+        const double* v = q.Y + (size_t)veh * (2 * NC);
+        const double val = (double)N / q.tf[b];
+        const ctab_t Cn = as_ctab(q.tab), Sk = Cn + NC;
+        double u1[2][NC], u2[2][NC];           // C(n, j) x'_j, C(n, j) y'_j;  C(n, j) x''_j, C(n, j) y''_j
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+            double x[NC], x1[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) x[c] = v[d * NC + c];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) x1[c] = diff_elev1_at(x, c, N, val);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) u2[d][c] = Cn[c] * diff_elev1_at(x1, c, N, val);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) u1[d][c] = Cn[c] * x1[c];
+        }
+#pragma unroll
+        for (int k = 0; k < L; ++k) cf[k] = ang_row_coeff(u1[0], u1[1], u2[0], u2[1], N, k, Sk[k], q.W, sigma);
+    }
+    static __device__ __forceinline__ void envelope(const Params& q, long item, int nc, double t)
+    {
+        const long veh = item >> 1;
+        const int b = (int)(veh / q.n_veh);
+        const double dtf = ang_envelope_block<NC>(q.Y + (size_t)veh * (2 * nc), nc, q.tf[b], q.W, (item & 1) ? -1.0 : 1.0, t,
+                                                  q.jac + (size_t)item * (2 * nc));
+        if (q.jac_tf) q.jac_tf[item] = dtf;
+    }
+};
+
 // The fused kernel of a family F: one item per lane -- its coefficients, the output transform as one fma (sign is +-1: the
 // product is exact, fused or not; this is the R = 0 row's value), the first step -- then the whole wave on each item that
 // needs the search, in lane order; JAC: every lane writes its own envelope block at the t_star it holds.
@@ -366,6 +421,38 @@ template <int NC, int DIM, bool JAC>
 __global__ __launch_bounds__(kExWaves * kWave) void k_speed_true_min(const SpeedExParams q) { true_min_body<SpeedRows<NC, DIM>, JAC>(q); }
 template <int DIM>
 __global__ __launch_bounds__(kEnvThreads) void k_speed_envelope(const SpeedExParams q, const int nc) { envelope_body<SpeedRows<kEnvMaxNC, DIM>>(q, nc); }
+template <int NC, bool JAC>
+__global__ __launch_bounds__(kExWaves * kWave) void k_ang_true_min(const AngExParams q) { true_min_body<AngRows<NC, 2>, JAC>(q); }
+__global__ __launch_bounds__(kEnvThreads) void k_ang_envelope(const AngExParams q, const int nc) { envelope_body<AngRows<kEnvMaxNC, 2>>(q, nc); }
+
+// The angular-rate rows' polynomials to memory, any degree 1 .. 31: one wave per (row, vehicle), the derivative curves
+// through LDS, lane k forms coefficient k of both sides with the functions the fused kernels use -- out[B][n_veh][2][2n+1].
+// q.sign, q.offset: the fused body's output transform (the identity; fma(1, p, 0) takes a -0 to +0 there and so here).
+__global__ __launch_bounds__(kWave) void k_ang_rows(const AngExParams q, const int nc, double* __restrict__ out)
+{
+    __shared__ double sh[6][kEnvMaxNC];       // x, y -> u1x, u1y after the last read; x', y'; u2x, u2y
+    const long veh = blockIdx.x;
+    const int b = (int)(veh / q.n_veh), lane = threadIdx.x, n = nc - 1, L = 2 * n + 1;
+    const double val = (double)n / q.tf[b];
+    const double* v = q.Y + (size_t)veh * (2 * nc);
+    const double* Cn = q.tab;
+    const double* Sk = Cn + nc;
+    if (lane < nc) { sh[0][lane] = v[lane]; sh[1][lane] = v[nc + lane]; }
+    __syncthreads();
+    if (lane < nc)
+        for (int d = 0; d < 2; ++d) sh[2 + d][lane] = diff_elev1_at(sh[d], lane, n, val);
+    __syncthreads();
+    if (lane < nc)
+        for (int d = 0; d < 2; ++d) {
+            sh[4 + d][lane] = Cn[lane] * diff_elev1_at(sh[2 + d], lane, n, val);
+            sh[d][lane] = Cn[lane] * sh[2 + d][lane];
+        }
+    __syncthreads();
+    if (lane < L)
+        for (int side = 0; side < 2; ++side)
+            out[((size_t)veh * 2 + side) * L + lane] =
+                fma(q.sign, ang_row_coeff(sh[0], sh[1], sh[4], sh[5], n, lane, Sk[lane], q.W, side ? -1.0 : 1.0), q.offset);
+}
 
 // =====================================================================================
 //  launchers
@@ -414,6 +501,25 @@ template <> struct RowKernels<SpeedRows> {
     }
 };
 
+// the counts of OBTG_NC_SEP whose angular-rate kernels hold their operands in registers; the others
+// take the rows route
+static constexpr bool nc_in_ang(int nc) { return false OBTG_NC_ANG_LIST(OBTG_NC_EQ_); }
+template <> struct RowKernels<AngRows> {
+    template <int NC, int DIM, bool JAC> static auto fused() -> void (*)(const AngExParams)
+    {
+        if constexpr (DIM == 2 && nc_in_ang(NC)) return k_ang_true_min<NC, JAC>;
+        else return nullptr;
+    }
+    template <int DIM> static auto envelope() { return k_ang_envelope; }
+    static AngExParams params(const obtg_ctx* c, const RowFamily& f, const double* dY, double* d_jac, double* d_jac_tf)
+    {
+        AngExParams q{};
+        q.Y = dY; q.tf = f.d_tf; q.tab = c->d_ang_rows.as<double>(); q.n_veh = c->n_veh; q.jac = d_jac; q.jac_tf = d_jac_tf;
+        q.sign = f.sign; q.offset = f.offset; q.W = f.w;
+        return q;
+    }
+};
+
 template <template <int, int> class Rows>
 static int launch_fused(obtg_ctx* c, const RowFamily& f, const double* dY, const ExParams& ex, double* d_jac, double* d_jac_tf)
 {
@@ -446,8 +552,11 @@ int launch_true_min(obtg_ctx* c, const RowFamily& f, const double* dY, int B, do
     ExParams ex{};
     ex.val = d_out; ex.t = d_t; ex.status = d_status;
     ex.M = (long)B * f.items; ex.K = 2 * c->deg + 1; ex.max_nodes = max_nodes; ex.eps_rel = eps_rel; ex.eps_abs = 0.0;
-    return f.kind == ROWS_SPEED ? launch_fused<SpeedRows>(c, f, dY, ex, d_jac, d_jac_tf)
-                                : launch_fused<TsepRows>(c, f, dY, ex, d_jac, d_jac_tf);
+    switch (f.kind) {
+        case ROWS_ANG: return launch_fused<AngRows>(c, f, dY, ex, d_jac, d_jac_tf);
+        case ROWS_SPEED: return launch_fused<SpeedRows>(c, f, dY, ex, d_jac, d_jac_tf);
+        default: return launch_fused<TsepRows>(c, f, dY, ex, d_jac, d_jac_tf);
+    }
 }
 
 template <template <int, int> class Rows>
@@ -470,8 +579,32 @@ int launch_true_min_envelope(obtg_ctx* c, const RowFamily& f, const double* dY, 
     if (c->deg + 1 > kEnvMaxNC) return OBTG_ERR_UNSUPPORTED;
     ExParams ex{};
     ex.t = const_cast<double*>(d_t); ex.M = (long)B * f.items;
-    return f.kind == ROWS_SPEED ? launch_blocks<SpeedRows>(c, f, dY, ex, d_jac, d_jac_tf)
-                                : launch_blocks<TsepRows>(c, f, dY, ex, d_jac, d_jac_tf);
+    switch (f.kind) {
+        case ROWS_ANG: return launch_blocks<AngRows>(c, f, dY, ex, d_jac, d_jac_tf);
+        case ROWS_SPEED: return launch_blocks<SpeedRows>(c, f, dY, ex, d_jac, d_jac_tf);
+        default: return launch_blocks<TsepRows>(c, f, dY, ex, d_jac, d_jac_tf);
+    }
+}
+
+// obtg_ang_rate_poly's launch, and the family's rows_r0
+int launch_ang_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out)
+{
+    if (B <= 0 || f.items <= 0) return OBTG_OK;
+    if (c->dim != 2 || c->deg < 1 || c->deg + 1 > kEnvMaxNC) return OBTG_ERR_UNSUPPORTED;
+    int rc = ensure_tables(c);
+    if (rc) return rc;
+    const AngExParams q = RowKernels<AngRows>::params(c, f, dY, nullptr, nullptr);
+    ScopedKernelTimer t(c, f.kernel_id);
+    hipLaunchKernelGGL(k_ang_rows, dim3((unsigned)((size_t)B * c->n_veh)), dim3(kWave), 0, c->stream, q, c->deg + 1, d_out);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
+RowFamily ang_row_family(const obtg_ctx* c, const double* d_tf, double max_rate)
+{
+    RowFamily f{ ROWS_ANG, 2 * c->n_veh, OBTG_K_ANG_RATE, 1.0, 0.0, d_tf, launch_ang_rows };
+    f.w = max_rate;
+    return f;
 }
 
 }  // namespace obtg

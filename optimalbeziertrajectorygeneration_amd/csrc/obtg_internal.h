@@ -19,6 +19,9 @@ namespace obtg {
 #define OBTG_NC_DYN(X)  OBTG_NC_ELEV(X) X(16)
 #define OBTG_NC_SEP(X)  OBTG_NC_DYN(X) X(21)
 #define OBTG_NC_EQ_(N) || nc == N
+//   OBTG_NC_ANG_LIST : the true angular-rate rows' fused kernels (k_ang_true_min; 2-D), the counts of OBTG_NC_SEP that build
+//                      without scratch
+#define OBTG_NC_ANG_LIST(X) OBTG_NC_DYN(X) X(21)
 static inline bool nc_in_sep(int nc)  { return false OBTG_NC_SEP(OBTG_NC_EQ_); }
 static inline bool nc_in_dyn(int nc)  { return false OBTG_NC_DYN(OBTG_NC_EQ_); }
 static inline bool nc_in_elev(int nc) { return false OBTG_NC_ELEV(OBTG_NC_EQ_); }
@@ -73,7 +76,7 @@ struct KernelStat {
 // The rule the code relies on: an entry point holds (from its reservation to its last download) only names WITHOUT the L; a
 // launcher takes only WS_L_* names, and only those whose index none of its calling entry points holds across the call.
 // The chains that are two deep, by index:
-//   obtg_temporal_sep_true_min[_jac], obtg_speed_true_min[_jac] hold 4 (WS_STATUS: true_min_host)
+//   obtg_temporal_sep_true_min[_jac], obtg_speed_true_min[_jac], obtg_ang_rate_true_min[_jac] hold 4 (WS_STATUS: true_min_host)
 //     -> true_min_chain takes 6 (WS_L_TSTAR: only with blocks in a launch of their own for a _dev caller that wants no t_star;
 //        the host call's is in ws_out) and 7 (WS_L_ROWS: degrees off the fast-kernel list) across the family's R = 0 rows
 //        launcher, launch_bern_extrema and launch_true_min_envelope, which take none
@@ -123,6 +126,7 @@ struct obtg_ctx {
     obtg::DevBuf d_Td;        // the same elevation as a dense transposed matrix (elev_table_T_ld): rows for the lane-per-item chains
     obtg::DevBuf d_Tf;        // ... and as matrix-instruction B fragments (elev_table_frag): the batch kernels
     obtg::DevBuf d_ang_w2n, d_ang_w22n, d_ang_wn;  // angular-rate fast path weights
+    obtg::DevBuf d_ang_rows;  // the true angular-rate rows' separable product weights: C(n, .)[n+1], 1 / C(2n, .)[2n+1] (dim 2, n <= 31)
     obtg::DevBuf d_ang_T4;    // angular rate, R > 0: elevation 4*deg -> 4*(deg+R) as a scaled convolution (elev_conv_padded)
     obtg::DevBuf d_ang_cv2;   // the same for the speed rows, 2*deg -> 2*deg+R, with the 1/C(2n+R, k) row
     bool ang_elevate_first = false;   // true: the reference's order (elevate, then products at degree n+R; generic kernel)
@@ -153,7 +157,7 @@ struct obtg_ctx {
     int n_poly = 0, n_poly_pts = 0, max_poly_K = 0;
     bool polys_planar = true;   // every registered polygon vertex has z == 0
     bool fd_dedup = false;      // reuse row 0's GJK results for bit-identical hull pairs
-    bool true_min_jac_fused = true;   // OBTG_TRUE_MIN_JAC_FUSED=0: obtg_temporal_sep_true_min_jac and obtg_speed_true_min_jac take the two-launch form on every shape
+    bool true_min_jac_fused = true;   // OBTG_TRUE_MIN_JAC_FUSED=0: obtg_temporal_sep_true_min_jac, obtg_speed_true_min_jac and obtg_ang_rate_true_min_jac take the two-launch form on every shape
     bool fd_view_structured = true;   // obtg_ctx_set_fd_view_structured: the one-call sweep of a view takes the structured step where it applies
     obtg::DevBuf d_hp_a, d_hp_b;  // hull pair list
     obtg::DevBuf d_vp_off, d_vp_idx;   // per vehicle: the positions of the hull pairs that contain it (CSR; structured FD step)
@@ -354,22 +358,26 @@ bool bern_extrema_supported(int K);                    // 1 <= K <= 64: a row is
 int launch_bern_extrema(obtg_ctx* c, const double* d_c, long M, int K, int want_max, double eps_rel, double eps_abs,
                         int max_nodes, double* d_val, double* d_t, double* d_bound, int* d_nodes, int* d_status,
                         int kernel_id = OBTG_K_BERN);     // every output but d_val nullable
-// A true-minimum row family (obtg_temporal_sep_true_min[_jac], obtg_speed_true_min[_jac]) as the host path sees it: what one
+// A true-minimum row family (obtg_temporal_sep_true_min[_jac], obtg_speed_true_min[_jac], obtg_ang_rate_true_min[_jac]) as the host path sees it: what one
 // call of the family contributes beyond the arguments every family has.  On the device the family is a struct of
-// extrema_kernels.hip (TsepRows, SpeedRows), found by `kind`.
-enum RowKind { ROWS_TSEP, ROWS_SPEED };
+// extrema_kernels.hip (TsepRows, SpeedRows, AngRows), found by `kind`.
+enum RowKind { ROWS_TSEP, ROWS_SPEED, ROWS_ANG };
 struct RowFamily {
     RowKind kind;
-    int items;                  // per batch row: n_pairs | n_veh
+    int items;                  // per batch row: n_pairs | n_veh | 2 n_veh
     int kernel_id;              // every launch of the call is timed under it
     double sign, offset;        // the output transform of its rows
     const double* d_tf;         // [B], device; null where the rows have no time span
     // its full rows at R = 0 from the any-degree kernel, [B][items][2 deg + 1], whatever the context's DEG_ELEV is: the launch
     // a context with R = 0 makes, bit for bit; the context is not touched
     int (*rows_r0)(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);
+    double w = 0.0;             // ROWS_ANG: the bound on |angular rate| (it enters the coefficients, not the output transform)
 };
 RowFamily tsep_row_family(const obtg_ctx* c, double max_sep);                                         // bern_kernels.hip
 RowFamily speed_row_family(const obtg_ctx* c, const double* d_tf, double bound, int is_max);
+RowFamily ang_row_family(const obtg_ctx* c, const double* d_tf, double max_rate);                     // extrema_kernels.hip
+// the angular-rate family's polynomials [B][n_veh][2][2 deg + 1] (obtg_ang_rate_poly; its rows_r0): dim 2, degree 1 .. 31
+int launch_ang_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);
 // the fused form for the fast-kernel list's shapes, one launch; OBTG_ERR_UNSUPPORTED: go through the family's R = 0 rows.
 // d_jac: with the envelope blocks [B][items][dim][deg+1]; d_jac_tf (nullable, speed): their d/dtf [B][items]
 int launch_true_min(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double eps_rel, int max_nodes, double* d_out,

@@ -285,7 +285,8 @@ class BezOptimization(object):
                  angRateOrder='fast',
                  activeRows=2,
                  fdBatching=True,
-                 speedRows='all'):
+                 speedRows='all',
+                 angRateRows='all'):
         """Beyond the reference's keywords: `device` (HIP ordinal; None: this process's, see _capi.default_device) and `separationRows` --
         'all': temporalSeparationConstraints returns every elevated control point of every pair, as the
         reference does (optimization.py:337); 'min': one row per pair, the smallest of them -- the
@@ -301,6 +302,13 @@ class BezOptimization(object):
         # speedRows 'true_min': per vehicle the true minimum over the trajectory's time of each speed row's polynomial
         # (obtg_speed_true_min) -- N rows per bound whatever DEG_ELEV is, feasible iff >= 0 -- instead of its N (2n+R+1)
         # elevated control points ('all', the reference's rows: optimization.py:349-422), which only bound it from below
+        # angRateRows 'true_min': per vehicle the true minima over the trajectory's time of W den - num and W den + num
+        # (obtg_ang_rate_true_min; den = |v|^2, num = y'' x' - x'' y', W = maxAngRate): 2N rows whatever DEG_ELEV is, feasible
+        # iff >= 0, in units of W speed^2 -- NOT the scale of 'all', the reference's N (4(n+R)+1) quotients W^2 - num_k/den_k
+        # of control points (optimization.py:425-459), which bound omega^2 from one side only.  For trajectories that do not stop.
+        if angRateRows not in ('all', 'true_min'):
+            raise ValueError("angRateRows must be 'all' or 'true_min', not {!r}".format(angRateRows))
+        self.angRateRows = angRateRows
         if speedRows not in ('all', 'true_min'):
             raise ValueError("speedRows must be 'all' or 'true_min', not {!r}".format(speedRows))
         self.speedRows = speedRows
@@ -407,6 +415,26 @@ class BezOptimization(object):
         is_max = family == 'vmax'
         r = ctx.speed_true_min(Y, tf, self.model['maxSpeed' if is_max else 'minSpeed'], is_max, eps_rel=self.TRUE_MIN_EPS_REL)
         return _md_checked(r, ('maxSpeedConstraints' if is_max else 'minSpeedConstraints') + '(true_min)')['val']
+
+    def _ang_true_min(self, ctx, Y, tf):
+        """angRateRows='true_min': [B][2N] true minima of every vehicle's two angular-rate polynomials, row 2 v + side; a
+        search that ran out of budget raises (bezier._raise_md)"""
+        r = ctx.ang_rate_true_min(Y, tf, self.model['maxAngRate'], eps_rel=self.TRUE_MIN_EPS_REL)
+        v = _md_checked(r, 'maxAngularRateConstraints(true_min)')['val']
+        return v.reshape(v.shape[0], -1)
+
+    def trueAngularRateRows(self, x):
+        """(val[N][2], t_star[N][2]): per vehicle and side the true minimum over the trajectory of maxAngRate den - num (side 0)
+        and maxAngRate den + num (side 1), and the parameters in [0, 1] where they are reached (obtg_ang_rate_true_min),
+        whatever `angRateRows` is: |angular rate| <= maxAngRate on the whole trajectory iff both are >= 0."""
+        x = np.asarray(x, dtype=float)
+        if self.model['dim'] != 2:
+            raise ValueError('The input curve must be two dimensional,\n'
+                             'instead it is {} dimensional'.format(self.model['dim']))
+        r = self._ctx(False).ang_rate_true_min(self.reshapeVector(x)[None], self._tf_of(x), self.model['maxAngRate'],
+                                               eps_rel=self.TRUE_MIN_EPS_REL)
+        _md_checked(r, 'trueAngularRateRows')
+        return r['val'][0], r['t_star'][0]
 
     def trueSpeedRange(self, x):
         """(min_val[N], t_min[N], max_val[N], t_max[N]): per vehicle the true extrema over the trajectory of (d/2)|dv/dt|^2
@@ -542,6 +570,8 @@ class BezOptimization(object):
                 # arithmetic returns None for an empty span (bezier.py:340-343, 365-368) and optimization.py:603-604
                 # multiplies it -- the driver dies with this TypeError.  Same exception, same text, no device call.
                 raise TypeError("unsupported operand type(s) for *: 'NoneType' and 'NoneType'")
+            if self.angRateRows == 'true_min':
+                return self._serve('ang', x, lambda x_: self._ang_true_min(self._ctx(False), self.reshapeVector(x_)[None], self._tf_of(x_))[0])
             return self._serve('ang', x, lambda x_: self._ctx(False).ang_rate(self.reshapeVector(x_), self._tf_of(x_), self.model['maxAngRate'])[0])
         return wrapper
 
@@ -699,7 +729,7 @@ class BezOptimization(object):
         milliseconds); _serve asks for the key only when at most one variable moved."""
         if refresh or getattr(self, '_rv_cache', None) is None:
             self._rv_parts()
-        return (int(DEG_ELEV), self.separationRows, self.speedRows, self.activeRows, self._rv_cache[0], self.model['maxSep'], self.model['maxSpeed'],
+        return (int(DEG_ELEV), self.separationRows, self.speedRows, self.angRateRows, self.activeRows, self._rv_cache[0], self.model['maxSep'], self.model['maxSpeed'],
                 self.model['minSpeed'], self.model['maxAngRate'], None if self._timeopt() else self.model['tf'],
                 None if self.pointObstacles is None else np.asarray(self.pointObstacles, dtype=float).tobytes(),
                 None if self.shapeObstacles is None else tuple(np.asarray(c.cpts, dtype=float).tobytes() for c in self.shapeObstacles))
@@ -736,6 +766,8 @@ class BezOptimization(object):
                 F = c.speed(Y, tf, self.model['maxSpeed'], True)
             elif family == 'vmin':
                 F = c.speed(Y, tf, self.model['minSpeed'], False)
+            elif self.angRateRows == 'true_min':
+                F = self._ang_true_min(c, Y, tf)
             else:
                 F = c.ang_rate(Y, tf, self.model['maxAngRate'])
         return F, dx
@@ -819,8 +851,25 @@ class BezOptimization(object):
         speedRows='true_min' (the speed families): method='envelope' is the envelope derivative of the true per-vehicle
         minima -- each row's polynomial differentiated at the minimiser the search returns, with its d/dtf
         (obtg_speed_true_min_jac, one call at x with TRUE_MIN_EPS_REL); method='fd' differences the search
-        itself (one batched call); method='exact' is not built for these rows."""
-        true_min = family in ('vmax', 'vmin') and self.speedRows == 'true_min'
+        itself (one batched call); method='exact' is not built for these rows.
+
+        angRateRows='true_min' (the angular rate): the same three answers -- method='envelope' is dense [2N][n_x] from
+        obtg_ang_rate_true_min_jac, 'fd' differences the search, 'exact' raises."""
+        true_min = (family in ('vmax', 'vmin') and self.speedRows == 'true_min') or (family == 'ang' and self.angRateRows == 'true_min')
+        if family == 'ang' and (method == 'envelope' or true_min):
+            if self.model['dim'] != 2:
+                raise ValueError('The input curve must be two dimensional,\n'
+                                 'instead it is {} dimensional'.format(self.model['dim']))
+            if method == 'envelope':
+                if not true_min:
+                    raise ValueError("maxAngularRateJacobian(method='envelope') needs angRateRows='true_min', not {!r}"
+                                     .format(self.angRateRows))
+                return self._ang_jac_envelope(x)
+            _check_method(method)
+            if method == 'exact':
+                raise ValueError("maxAngularRateJacobian(method='exact') is not available with angRateRows='true_min' (the "
+                                 "envelope derivative is not built under that name): use method='envelope' or method='fd'")
+            return self._jac(x, family)
         if method == 'envelope' and family in ('vmax', 'vmin'):
             if not true_min:
                 raise ValueError("{}SpeedJacobian(method='envelope') needs speedRows='true_min', not {!r}"
@@ -953,6 +1002,14 @@ class BezOptimization(object):
         _md_checked(r, ('maxSpeedJacobian' if is_max else 'minSpeedJacobian') + '(envelope)')
         N = self.model['numVeh']
         return self._scatter_exact(r['jac'][0][:, None], (np.arange(N),), (1.0,), r['jac_tf'][0][:, None])   # blocks of one row each
+
+    def _ang_jac_envelope(self, x):
+        x = np.asarray(x, dtype=float)
+        r = self._ctx(False).ang_rate_true_min_jac(self.reshapeVectors(x[None]), float(self._tf_of(x)), self.model['maxAngRate'],
+                                                   eps_rel=self.TRUE_MIN_EPS_REL)
+        _md_checked(r, 'maxAngularRateJacobian(envelope)')
+        N = self.model['numVeh']
+        return self._scatter_exact(r['jac'][0], (np.arange(N),), (1.0,), r['jac_tf'][0])      # blocks of two rows each: the sides
 
     def trueMinSeparationJacobian(self, x):
         """temporalSeparationJacobian(x, method='envelope')"""

@@ -687,7 +687,13 @@ int obtg_ang_rate_true_min_jac_dev(obtg_ctx*, const double* dY, const double* d_
  * obtg_bern_restrict: one curve's share of _temporalAlignment  bezier.py:903-941   in[rows][n+1] on span[rows][2] = (t0, tf)
  *                   -> out[rows][n+1] on target[rows][2] = (a, e): the right piece of a split at (a - t0)/(tf - t0) when
  *                   t0 < a, then the left piece of a split at (e - a)/(tf - a) when e < tf (two curves aligned in ONE call
- *                   instead of up to four obtg_bern_split calls).  OBTG_ERR_ARG unless t0 <= a < e <= tf in every row. */
+ *                   instead of up to four obtg_bern_split calls).  OBTG_ERR_ARG unless t0 <= a < e <= tf in every row.
+ * Limits.  A row -- input or output -- holds at most 1024 coefficients (n + R + 1, m + n + 1, 2n + 1, n + 1 <= 1024), and
+ * obtg_bern_eval takes at most 125 control points (its per-lane working rows fill the 64 KB of LDS of one launch); beyond
+ * either the call answers OBTG_ERR_UNSUPPORTED and launches nothing.  Elevation and the products form the unnormalised sum
+ * sum_j a_j C(n,j) C(R,k-j) BEFORE dividing by C(n+R,k), so a result is finite only while max|a| C(n+R, (n+R)/2) stays
+ * below DBL_MAX (products: max|a| max|b| C(m+n, (m+n)/2)): magnitudes below about 50 at 1024 coefficients, below about
+ * 1e150 at 500. */
 int obtg_bern_elev(obtg_ctx*, const double* in, int rows, int n, int R, double* out);
 int obtg_bern_diff(obtg_ctx*, const double* in, int rows, int n, double T, double* out);
 int obtg_bern_mul(obtg_ctx*, const double* a, const double* b, int rows, int m, int n, double* out);

@@ -157,12 +157,16 @@ int obtg_ctx_set_deg_elev(obtg_ctx*, int deg_elev);
  * forms every product at degree n+R (a degree-4(n+R) square: 441 coefficients from degree-220 operands at R = 100).
  * Elevation commutes with diff/mul/add, so by default (elevate_first = 0) the library forms numerator and
  * denominator at degree 4n from the original control points and elevates both by 4R before the element-wise
- * quotient -- the same control points up to rounding (within the 1e-9 bar on every reference fixture), an order of
+ * quotient -- the same control points up to rounding (both orders pass the same exact-rational quotient test), an order of
  * magnitude less arithmetic.  elevate_first = 1 keeps the reference's order of operations (generic kernel).
  * 2 = "exact": the default order, then the rows of vehicles that nearly stop -- a control point of |v|^2 three orders
  * below the curve's largest, where every float64 evaluation of the quotient, the reference's included, loses up to
- * 1e-8 to cancellation -- once more in double-double arithmetic, rounded once: those rows are then within a few 1e-16
- * of the exact rational value.  One more (small) launch behind the dynamics launch; not in the structured step. */
+ * 1e-8 to cancellation -- once more in double-double arithmetic, rounded once.  The pass's tables carry 64 bits, so those
+ * rows are then within the row's condition number times 2^-64 of the exact rational value, 2^11 times closer than any
+ * float64 evaluation: element by element 2.3e-13 relative on the worst-conditioned fixture (tests/golden/nearstop.npz,
+ * where the float64 rows are 4e-10 off), 5.75e-15 of the vehicle's largest entry -- not "a few 1e-16", as this comment said
+ * until tests/test_gpu_constraint_rows.py measured it.  One more (small) launch behind the dynamics launch; not in the
+ * structured step. */
 int obtg_ctx_set_ang_rate_order(obtg_ctx*, int elevate_first);
 /* The order that is IN EFFECT for the context's present shape -- 0, 1 or 2 as above, negative = error.  A request holds
  * only where its kernels exist: DEG_ELEV = 0 has one order (0); without a products-then-elevation kernel for (deg, R) --
@@ -186,7 +190,24 @@ int obtg_num_pairs(const obtg_ctx*);        /* C(N+M,2)            */
  *   per vehicle diff() [derivative then elev(1), bezier.py:497-519], normSquare, elev(R);
  *   is_max ? bound^2 - cpts : cpts - bound^2.  tf[B]: final time of each row.
  * obtg_ang_rate: _maxAngularRateConstraints -> _angularRateSqr (optimization.py:425-459,
- *   578-611), dim must be 2: max_rate^2 - num.cpts/den.cpts element-wise (inf/nan kept). */
+ *   578-611), dim must be 2: max_rate^2 - num.cpts/den.cpts element-wise (inf/nan kept).
+ * Limits.  A separation or speed row holds at most 1024 coefficients (2n + R + 1 <= 1024; beyond: OBTG_ERR_UNSUPPORTED);
+ *   the angular rate stops at n + R = 250 outside the specialised counts.  Shapes on the any-degree kernels (dim 1,
+ *   n + 1 outside obtg_fast_kernels & 1, R > 512) form the unnormalised sum  sum_j C(2n,j) c_j C(R,k-j)  of the product's
+ *   coefficients c_j BEFORE dividing by C(2n+R,k), as obtg_bern_elev does, so their rows are finite only while
+ *       C(R, R/2) 4^n (d/2) max|D|^2  <  DBL_MAX,
+ *   D the control points of v_i - v_j (speed: of the derivative elevated by one).  At n = 2, R = 900 that allows |D| beyond
+ *   1e18; at 1024 coefficients (n = 2, R = 1019, d = 2) it is |D| < 9, where the reference's elevation matrix, built from
+ *   ratios, stays finite.  The specialised kernels (R <= 512) multiply by that matrix and have no such condition.
+ *   The any-degree angular rate (n + 1 outside obtg_fast_kernels & 2, or the position elevated first) likewise divides
+ *   C(4m,k) num_k by C(4m,k) den_k, m = n + R, both formed as plain sums: finite only while C(4m, 2m) times the largest
+ *   coefficient of (y''x' - x''y')^2 stays below DBL_MAX -- no limit in practice up to m = 200; at the kernel's last
+ *   m = 250, C(1000, 500) = 2.7e299 leaves 6e8 for that coefficient, which goes with tf^-6 (positions within +-10:
+ *   tf > 2).  k_dynamics_elev (R > 0 on the specialised counts) scales its binomial row and has no such condition.
+ * Accuracy.  Every element of these rows is within K 2^-53 M of its exact rational value, M the same formula on magnitudes
+ *   (the first difference v_i - v_j as |v_i - v_j|: a swarm far from the origin loses nothing) and K the count of rounded
+ *   operations: d T + 20 at R = 0 and d (n + 1) + Te + 28 at R > 0, T and Te the terms of the element's product and
+ *   elevation sums, the speed rows 14 more (tests/constraint_rows_ref.py; the angular rate: its quotient form). */
 int obtg_temporal_sep(obtg_ctx*, const double* Y, int B, double max_sep, double* out);
 int obtg_speed(obtg_ctx*, const double* Y, const double* tf, int B, double bound, int is_max, double* out);
 int obtg_ang_rate(obtg_ctx*, const double* Y, const double* tf, int B, double max_rate, double* out);

@@ -1455,13 +1455,18 @@ __device__ __forceinline__ void load_item_xy(const AngParams& p, int item, int b
     }
 }
 
+// Two equal control points have the derivative coefficient 0, exactly: the reference's unfused cpts.dot(diffMatrix) gives
+// -r + r with r = fl(val p).  The compiler fuses one product of the sum below, fma(-val, p_c, fl(val p_(c+1))), which for
+// equal points returns the rounding error of val p instead -- a vehicle at rest then had a velocity of 1e-16 |val p| and its
+// angular-rate row came out as max_rate^2 - 0 / tiny instead of the 0 / 0 = NaN of optimization.py:608
+// (tests/test_gpu_constraint_rows.py test_vehicle_at_rest).  Every other coefficient keeps its bits.
 template <int NC>
 __device__ __forceinline__ void diff_elev1(const double (&p)[NC], double val, double (&d)[NC])
 {
     constexpr int N = NC - 1;
     double t[NC];
 #pragma unroll
-    for (int c = 0; c < N; ++c) t[c] = p[c] * (-val) + p[c + 1] * val;
+    for (int c = 0; c < N; ++c) t[c] = p[c + 1] - p[c] == 0.0 ? 0.0 : p[c] * (-val) + p[c + 1] * val;   // (inf - inf is NaN: stays NaN)
     d[0] = t[0];
     d[N] = t[N - 1];
 #pragma unroll

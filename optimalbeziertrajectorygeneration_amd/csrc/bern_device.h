@@ -339,6 +339,68 @@ __device__ __forceinline__ double diff_elev1_at(const A& p, const int c, const i
     return __builtin_fma((double)c / (double)n, tl, ((double)(n - c) / (double)n) * tr);
 }
 
+// The source curve of an acceleration row (obtg_accel, obtg_accel_true_min[_jac]) -- Bezier.diff().diff(): the derivative and
+// elev(1), twice, each with val = n / T (optimization.py:503-519) -- as diff_elev1_at applied twice, the way x'' of the
+// angular-rate rows is formed.  Unlike the speed path's first derivative nothing here is left to the compiler: the
+// specialised rows kernel (normsq_elev_body, MODE 2), the fused true-minimum kernels (AccelRows) and, element by element
+// through LDS, the any-degree rows kernel all give the same bits.  n = 1: the second derivative is exactly zero.
+template <int NC>
+__device__ __forceinline__ void diff2_elev1_rows(const double (&p)[NC], const double val, double (&d)[NC])
+{
+    constexpr int N = NC - 1;
+    double x1[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) x1[c] = diff_elev1_at(p, c, N, val);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) d[c] = diff_elev1_at(x1, c, N, val);
+}
+
+// Envelope block of one vehicle's acceleration row at parameter t: the partial derivatives of
+// q(t) = sign (DIM/2) |c''(t)|^2 + offset, c'' = d^2 c / dtime^2 on a span of T, with respect to the vehicle's own control
+// points and to T (obtg_accel_true_min_jac).  With n = nc - 1, u = B^(n-2)(t), entries out of range 0, and
+// c''_c(t) = (n(n-1)/T^2) sum_i u_i (P_c,i+2 - 2 P_c,i+1 + P_c,i):
+//     C_i = (n(n-1)/T^2)(u_(i-2) - 2 u_(i-1) + u_i),    out[c][i] = sign DIM c''_c(t) C_i;    returns dq/dT = -4 (q(t) - offset) / T,
+// q(t) - offset evaluated here from the same u.  y: the vehicle's [DIM][nc] control points.  Written as speed_envelope_block
+// is: the basis from the de Casteljau recurrence on the basis, every multiply-add an explicit fma, contraction off inside
+// -- the same arithmetic whatever the including unit's mode, for every NCMAX >= nc, wherever it is inlined.
+// n = 1: u is empty, the block and dq/dT are zero.  t = 0 / t = 1 leave columns (0, 1, 2) / (n - 2, n - 1, n) as the only
+// non-zero ones; a NaN t gives a NaN block (n >= 2) and a NaN dq/dT.
+template <int NCMAX, int DIM>
+__device__ __forceinline__ double accel_envelope_block(const double* __restrict__ y, const int nc, const double T, const double sign,
+                                                       const double t, double* __restrict__ out)
+{
+#pragma clang fp contract(off)
+    const int n = nc - 1;
+    const double s = 1.0 - t;
+    double u[NCMAX];                       // u[0 .. n - 1): B^(n-2)(t); the rest stays zero
+#pragma unroll
+    for (int i = 0; i < NCMAX; ++i) u[i] = (i == 0 && n >= 2) ? 1.0 : 0.0;
+#pragma unroll
+    for (int r = 1; r < NCMAX - 2; ++r)
+        if (r < n - 1) {
+#pragma unroll
+            for (int i = r; i >= 1; --i) u[i] = __builtin_fma(t, u[i - 1], s * u[i]);
+            u[0] = s * u[0];
+        }
+    const double nnT = ((double)n / T) * ((double)(n - 1) / T);
+    double ss = 0.0;
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+        double b = 0.0;
+#pragma unroll
+        for (int i = 0; i < NCMAX - 2; ++i)
+            if (i < n - 1) b = __builtin_fma(u[i], (y[c * nc + i + 2] - y[c * nc + i + 1]) - (y[c * nc + i + 1] - y[c * nc + i]), b);
+        const double a = nnT * b;
+        ss = c == 0 ? a * a : __builtin_fma(a, a, ss);
+        const double kd = (sign * (double)DIM) * (a * nnT);
+#pragma unroll
+        for (int i = 0; i < NCMAX; ++i)
+            if (i < nc)
+                out[c * nc + i] = kd * (((i < 2 ? 0.0 : u[i - 2]) - (i == 0 ? 0.0 : u[i - 1])) - ((i == 0 ? 0.0 : u[i - 1]) - u[i]));
+    }
+    return (-4.0 * ((sign * (0.5 * (double)DIM)) * ss)) / T;
+}
+
 template <class A>
 __device__ __forceinline__ double ang_row_coeff(const A& ux, const A& uy, const A& uxx, const A& uyy, const int n, const int k,
                                                 const double sk, const double W, const double sigma)
@@ -1086,7 +1148,7 @@ __device__ __forceinline__ void tsep_tile_from_xy(const TsepXYParams& t, const d
 // (b, w) = evaluation row and workgroup index inside the row; lds = the workgroup's dynamic LDS.
 // A device function so that the pair sweep can run it next to the GJK workgroups in ONE launch
 // (gjk_kernels.hip k_pair_sweep); k_normsq_elev below is the stand-alone kernel.
-template <int NC, int DIM, int MODE /*0 = pairs, 1 = vehicles*/, bool MINONLY, bool ELEV>
+template <int NC, int DIM, int MODE /*0 = pairs, 1 = vehicles (speed), 2 = vehicles (acceleration)*/, bool MINONLY, bool ELEV>
 __device__ __forceinline__ void normsq_elev_body(const NsParams& p, const int b, const int w, double* lds)
 {
     using S = NsShape<NC, DIM>;
@@ -1182,7 +1244,7 @@ __device__ __forceinline__ void normsq_elev_body(const NsParams& p, const int b,
             for (int q = 0; q < DIM; ++q)
 #pragma unroll
                 for (int c = 0; c < NC; ++c) a[q][c] = vi[q * NC + c] - vj[q * NC + c];
-        } else {
+        } else if (MODE == 1) {
             // Bezier.diff(): (n/T)(P_{i+1}-P_i), then elev(1) back to degree n (bezier.py:497-519)
             const double* v = vl + si * S::VP;
             const double val = (double)N / p.tf[b];
@@ -1196,6 +1258,17 @@ __device__ __forceinline__ void normsq_elev_body(const NsParams& p, const int b,
 #pragma unroll
                 for (int c = 1; c < N; ++c)
                     a[q][c] = t[c - 1] * ((double)c / (double)N) + t[c] * ((double)(N - c) / (double)N);
+            }
+        } else {
+            // Bezier.diff().diff(): the acceleration rows' source curve (diff2_elev1_rows: nothing left to contraction)
+            const double* v = vl + si * S::VP;
+            const double val = (double)N / p.tf[b];
+#pragma unroll
+            for (int q = 0; q < DIM; ++q) {
+                double x[NC];
+#pragma unroll
+                for (int c = 0; c < NC; ++c) x[c] = v[q * NC + c];
+                diff2_elev1_rows<NC>(x, val, a[q]);
             }
         }
 

@@ -41,7 +41,7 @@ namespace obtg {
 
 // (the elevated full rows: B fragments, accumulators and A fragments of a group are ~210 registers, and LDS holds two
 // workgroups per CU anyway: two waves per SIMD)
-template <int NC, int DIM, int MODE /*0 = pairs, 1 = vehicles*/, bool MINONLY, bool ELEV>
+template <int NC, int DIM, int MODE /*0 = pairs, 1 = vehicles (speed), 2 = vehicles (acceleration)*/, bool MINONLY, bool ELEV>
 __global__ __launch_bounds__(256, (ELEV && !MINONLY) ? 2 : 1) void k_normsq_elev(const NsParams p)
 {
     extern __shared__ double lds[];
@@ -692,6 +692,19 @@ __global__ __launch_bounds__(kWave) void k_generic_normsq_elev(const GenParams p
             const double vi = ij.x < p.n_veh ? Yrow[(size_t)ij.x * dim * nc + e] : p.obs[(ij.x - p.n_veh) * dim + q];
             const double vj = ij.y < p.n_veh ? Yrow[(size_t)ij.y * dim * nc + e] : p.obs[(ij.y - p.n_veh) * dim + q];
             ah[e] = (vi - vj) * bn[c];
+        }
+    } else if (MODE == 2) {
+        // the acceleration rows' source curve, element by element: bern_device.h diff_elev1_at twice (diff2_elev1_rows)
+        const double val = (double)n / p.tf[b];
+        const double* v = Yrow + (size_t)item * dim * nc;
+        for (int e = lane; e < dim * nc; e += kWave) {
+            const int q = e / nc, c = e - q * nc;
+            tm[e] = diff_elev1_at(v + q * nc, c, n, val);
+        }
+        __syncthreads();
+        for (int e = lane; e < dim * nc; e += kWave) {
+            const int q = e / nc, c = e - q * nc;
+            ah[e] = diff_elev1_at(tm + q * nc, c, n, val) * bn[c];
         }
     } else {
         const double val = (double)n / p.tf[b];
@@ -1404,7 +1417,7 @@ __global__ __launch_bounds__(256) void k_select_smallest(const double* __restric
     sm.store(out, idx, (size_t)it * k, k);
 }
 
-// MODE's rows (0: separation, 1: speed) from the any-degree kernel at elevation R, timed under the MODE's kernel id: the
+// MODE's rows (0: separation, 1: speed, 2: acceleration) from the any-degree kernel at elevation R, timed under the MODE's kernel id: the
 // tail of launch_temporal_sep / launch_speed with R = c->R, the R = 0 rows of the true-minimum families (rows_r0) with 0
 template <int MODE>
 static int launch_generic_rows(obtg_ctx* c, const double* dY, const double* d_tf, int B, int item_begin, int item_count, int R,
@@ -1466,8 +1479,10 @@ void speed_sign_offset(double bound, int is_max, double& sign, double& offset)
     offset = is_max ? b2 : -b2;
 }
 
+// deriv: 1 = the speed rows, 2 = the acceleration rows (obtg_accel): the same staging, plan and dispatch, the source curve
+// one derivative further (MODE 2)
 int launch_speed(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max,
-                 double* d_out)
+                 double* d_out, int deriv)
 {
     if (B <= 0) return OBTG_OK;
     int rc = ensure_tables(c);
@@ -1488,11 +1503,12 @@ int launch_speed(obtg_ctx* c, const double* dY, const double* d_tf, int B, doubl
         p.stage_all = 0; p.tiling = 0; p.tiles = nullptr;
         p.sign = sign; p.offset = offset;
         if (c->fd.Y0) { p.Y = c->fd.Y0; p.fd = 1 + c->fd.row0; p.fd_fixed = c->fd.fixed; p.fd_h = c->fd.h; }
-        rc = dispatch_ns<1, false>(c, p, B, OBTG_K_SPEED);
+        rc = deriv == 2 ? dispatch_ns<2, false>(c, p, B, OBTG_K_SPEED) : dispatch_ns<1, false>(c, p, B, OBTG_K_SPEED);
         if (rc != OBTG_ERR_UNSUPPORTED) return rc;
     }
     if (c->fd.Y0) return kNeedBatch;
-    return launch_generic_rows<1>(c, dY, d_tf, B, 0, c->n_veh, c->R, sign, offset, false, d_out);
+    return deriv == 2 ? launch_generic_rows<2>(c, dY, d_tf, B, 0, c->n_veh, c->R, sign, offset, false, d_out)
+                      : launch_generic_rows<1>(c, dY, d_tf, B, 0, c->n_veh, c->R, sign, offset, false, d_out);
 }
 
 // the true-minimum row families' descriptors (obtg_internal.h RowFamily)
@@ -1512,6 +1528,13 @@ RowFamily speed_row_family(const obtg_ctx* c, const double* d_tf, double bound, 
 {
     RowFamily f{ ROWS_SPEED, c->n_veh, OBTG_K_SPEED, 0.0, 0.0, d_tf, rows_r0<1> };
     speed_sign_offset(bound, is_max, f.sign, f.offset);
+    return f;
+}
+
+RowFamily accel_row_family(const obtg_ctx* c, const double* d_tf, double bound)
+{
+    RowFamily f{ ROWS_ACCEL, c->n_veh, OBTG_K_SPEED, 0.0, 0.0, d_tf, rows_r0<2> };
+    speed_sign_offset(bound, 1, f.sign, f.offset);
     return f;
 }
 

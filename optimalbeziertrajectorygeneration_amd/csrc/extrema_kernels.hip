@@ -17,15 +17,17 @@
 // piece is lane 0's value level by level, the right piece what each lane holds when it stops.  No per-lane coefficient
 // arrays in the search (K is a run-time count up to 64), the stack is kExStack x (K + 3) doubles per wave.
 //
-// True-minimum row families (obtg_temporal_sep_true_min[_jac], obtg_speed_true_min[_jac], obtg_ang_rate_true_min[_jac]): the
-// polynomial of a pair's separation, of a vehicle's own speed, of one side of its angular-rate bound, formed in the lane and
-// searched as above -- one kernel body (true_min_body) over a family struct (TsepRows, SpeedRows, AngRows), under the kernel
-// names k_tsep_true_min / k_speed_true_min / k_ang_true_min.
+// True-minimum row families (obtg_temporal_sep_true_min[_jac], obtg_speed_true_min[_jac], obtg_ang_rate_true_min[_jac],
+// obtg_accel_true_min[_jac]): the polynomial of a pair's separation, of a vehicle's own speed, of one side of its angular-rate
+// bound, of its acceleration, formed in the lane and searched as above -- one kernel body (true_min_body) over a family struct
+// (TsepRows, SpeedRows, AngRows, AccelRows), under the kernel names k_tsep_true_min / k_speed_true_min / k_ang_true_min /
+// k_accel_true_min.  The acceleration family's fused value-and-blocks kernels are the counts of OBTG_NC_ACCEL_LIST
+// (obtg_internal.h): every count of OBTG_NC_SEP, in 2-D and 3-D.
 // Envelope Jacobian: the derivative of the item's polynomial at the t_star the search returned, bern_device.h
-// envelope_block / speed_envelope_block / ang_envelope_block -- written with explicit fma, so it is the same arithmetic here
+// envelope_block / speed_envelope_block / ang_envelope_block / accel_envelope_block -- written with explicit fma, so it is the same arithmetic here
 // (contraction off) as anywhere else.  Fused form: the <NC, DIM, true> kernels re-read the item's control points from Y after the search (no
 // register is held across wave_search for it) and every lane writes its own block.  Two-launch form: the value path, then
-// k_tsep_envelope / k_speed_envelope / k_ang_envelope on Y and t_star, any degree up to 31.
+// k_tsep_envelope / k_speed_envelope / k_ang_envelope / k_accel_envelope on Y and t_star, any degree up to 31.
 #include <algorithm>
 #include <cfloat>
 
@@ -218,7 +220,7 @@ __global__ __launch_bounds__(kExWaves * kWave) void k_bern_extrema(const ExParam
 //   coeffs(q, item, cf)     the item's coefficients BEFORE the output transform, as its rows have them at R = 0,
 //   envelope(q, item, nc, t) the item's envelope block(s) at t, nc <= NC control points at run time,
 // and two __global__ wrappers under names of their own (true_min_body, envelope_body; RowKernels finds them for the host).
-// A further family starts as a copy of SpeedRows, as AngRows did.
+// A further family starts as a copy of SpeedRows, as AngRows and AccelRows did.
 struct TsepExParams {
     const double* __restrict__ Y;      // [B][n_veh*DIM][NC]
     const double* __restrict__ obs;    // [n_obj - n_veh][DIM]
@@ -307,6 +309,37 @@ struct SpeedRows {
     {
         const int b = (int)(item / q.n_veh);
         const double dtf = speed_envelope_block<NC, DIM>(q.Y + (size_t)item * (DIM * nc), nc, q.tf[b], q.sign, t,
+                                                         q.jac + (size_t)item * (DIM * nc));
+        if (q.jac_tf) q.jac_tf[item] = dtf;
+    }
+};
+
+// obtg_accel's rows, q(t) = sign (DIM/2) |c''(t)|^2 + offset of a vehicle: SpeedRows with the source curve one derivative
+// further (bern_device.h diff2_elev1_rows, the rows kernels' own function: explicit fma throughout) and the block of the
+// second derivative.  The parameter block is the speed family's.
+template <int NC_, int DIM>
+struct AccelRows {
+    using Params = SpeedExParams;
+    static constexpr int NC = NC_, L = 2 * NC_ - 1;
+    static __device__ __forceinline__ void coeffs(const Params& q, long item, double (&cf)[L])
+    {
+        const int b = (int)(item / q.n_veh);
+        const double* v = q.Y + (size_t)item * (DIM * NC);
+        const double val = (double)(NC - 1) / q.tf[b];
+        double a[DIM][NC];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) {
+            double x[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) x[c] = v[d * NC + c];
+            diff2_elev1_rows<NC>(x, val, a[d]);
+        }
+        normsq_coeffs<NC, DIM>(a, as_ctab(q.W2), cf);
+    }
+    static __device__ __forceinline__ void envelope(const Params& q, long item, int nc, double t)
+    {
+        const int b = (int)(item / q.n_veh);
+        const double dtf = accel_envelope_block<NC, DIM>(q.Y + (size_t)item * (DIM * nc), nc, q.tf[b], q.sign, t,
                                                          q.jac + (size_t)item * (DIM * nc));
         if (q.jac_tf) q.jac_tf[item] = dtf;
     }
@@ -421,6 +454,10 @@ template <int NC, int DIM, bool JAC>
 __global__ __launch_bounds__(kExWaves * kWave) void k_speed_true_min(const SpeedExParams q) { true_min_body<SpeedRows<NC, DIM>, JAC>(q); }
 template <int DIM>
 __global__ __launch_bounds__(kEnvThreads) void k_speed_envelope(const SpeedExParams q, const int nc) { envelope_body<SpeedRows<kEnvMaxNC, DIM>>(q, nc); }
+template <int NC, int DIM, bool JAC>
+__global__ __launch_bounds__(kExWaves * kWave) void k_accel_true_min(const SpeedExParams q) { true_min_body<AccelRows<NC, DIM>, JAC>(q); }
+template <int DIM>
+__global__ __launch_bounds__(kEnvThreads) void k_accel_envelope(const SpeedExParams q, const int nc) { envelope_body<AccelRows<kEnvMaxNC, DIM>>(q, nc); }
 template <int NC, bool JAC>
 __global__ __launch_bounds__(kExWaves * kWave) void k_ang_true_min(const AngExParams q) { true_min_body<AngRows<NC, 2>, JAC>(q); }
 __global__ __launch_bounds__(kEnvThreads) void k_ang_envelope(const AngExParams q, const int nc) { envelope_body<AngRows<kEnvMaxNC, 2>>(q, nc); }
@@ -501,6 +538,22 @@ template <> struct RowKernels<SpeedRows> {
     }
 };
 
+// the counts whose fused value-and-blocks kernel builds without scratch; the others: value kernel, then
+// the blocks in a launch of their own
+static constexpr bool nc_in_accel(int nc) { return false OBTG_NC_ACCEL_LIST(OBTG_NC_EQ_); }
+template <> struct RowKernels<AccelRows> {
+    template <int NC, int DIM, bool JAC> static auto fused() -> void (*)(const SpeedExParams)
+    {
+        if constexpr (!JAC || nc_in_accel(NC)) return k_accel_true_min<NC, DIM, JAC>;
+        else return nullptr;
+    }
+    template <int DIM> static auto envelope() { return k_accel_envelope<DIM>; }
+    static SpeedExParams params(const obtg_ctx* c, const RowFamily& f, const double* dY, double* d_jac, double* d_jac_tf)
+    {
+        return RowKernels<SpeedRows>::params(c, f, dY, d_jac, d_jac_tf);
+    }
+};
+
 // the counts of OBTG_NC_SEP whose angular-rate kernels hold their operands in registers; the others
 // take the rows route
 static constexpr bool nc_in_ang(int nc) { return false OBTG_NC_ANG_LIST(OBTG_NC_EQ_); }
@@ -555,6 +608,7 @@ int launch_true_min(obtg_ctx* c, const RowFamily& f, const double* dY, int B, do
     switch (f.kind) {
         case ROWS_ANG: return launch_fused<AngRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_SPEED: return launch_fused<SpeedRows>(c, f, dY, ex, d_jac, d_jac_tf);
+        case ROWS_ACCEL: return launch_fused<AccelRows>(c, f, dY, ex, d_jac, d_jac_tf);
         default: return launch_fused<TsepRows>(c, f, dY, ex, d_jac, d_jac_tf);
     }
 }
@@ -582,6 +636,7 @@ int launch_true_min_envelope(obtg_ctx* c, const RowFamily& f, const double* dY, 
     switch (f.kind) {
         case ROWS_ANG: return launch_blocks<AngRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_SPEED: return launch_blocks<SpeedRows>(c, f, dY, ex, d_jac, d_jac_tf);
+        case ROWS_ACCEL: return launch_blocks<AccelRows>(c, f, dY, ex, d_jac, d_jac_tf);
         default: return launch_blocks<TsepRows>(c, f, dY, ex, d_jac, d_jac_tf);
     }
 }

@@ -107,6 +107,13 @@ def _maxSpeedConstraints(y, nVeh, dim, tf, maxSpeed):
     return _shape_ctx(nVeh, dim, y.shape[1] - 1, DEG_ELEV).speed(y, tf, maxSpeed, True)[0]
 
 
+def _maxAccelConstraints(y, nVeh, dim, tf, maxAccel):
+    """The acceleration-bound rows, maxAccel**2 - (pos.diff().diff().normSquare().elev(DEG_ELEV)) per vehicle (obtg_accel):
+    the curve of the reference's acceleration objective (optimization.py:503-519) as a constraint, any dimension."""
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    return _shape_ctx(nVeh, dim, y.shape[1] - 1, DEG_ELEV).accel(y, tf, maxAccel)[0]
+
+
 def _maxAngularRateConstraints(y, nVeh, dim, tf, maxAngRate):
     if dim != 2:
         raise ValueError('The input curve must be two dimensional,\n'
@@ -159,7 +166,7 @@ def _check_method(method):
 _MODEL_FIELDS = (
     ('numVeh', 'numVeh', None), ('dim', 'dimension', None), ('deg', 'degree', None), ('minGoal', 'minimizeGoal', None),
     ('maxSep', 'maxSep', None), ('minSpeed', 'minSpeed', None), ('maxSpeed', 'maxSpeed', None),
-    ('maxAngRate', 'maxAngRate', None),
+    ('maxAngRate', 'maxAngRate', None), ('maxAccel', 'maxAccel', None),
     ('initPoints', 'initPoints', np.atleast_2d), ('finalPoints', 'finalPoints', np.atleast_2d),
     ('initSpeeds', 'initSpeeds', np.atleast_1d), ('finalSpeeds', 'finalSpeeds', np.atleast_1d),
     ('initAngs', 'initAngs', np.atleast_1d), ('finalAngs', 'finalAngs', np.atleast_1d),
@@ -286,7 +293,9 @@ class BezOptimization(object):
                  activeRows=2,
                  fdBatching=True,
                  speedRows='all',
-                 angRateRows='all'):
+                 angRateRows='all',
+                 maxAccel=None,
+                 accelRows='all'):
         """Beyond the reference's keywords: `device` (HIP ordinal; None: this process's, see _capi.default_device) and `separationRows` --
         'all': temporalSeparationConstraints returns every elevated control point of every pair, as the
         reference does (optimization.py:337); 'min': one row per pair, the smallest of them -- the
@@ -306,6 +315,13 @@ class BezOptimization(object):
         # (obtg_ang_rate_true_min; den = |v|^2, num = y'' x' - x'' y', W = maxAngRate): 2N rows whatever DEG_ELEV is, feasible
         # iff >= 0, in units of W speed^2 -- NOT the scale of 'all', the reference's N (4(n+R)+1) quotients W^2 - num_k/den_k
         # of control points (optimization.py:425-459), which bound omega^2 from one side only.  For trajectories that do not stop.
+        # maxAccel (None: no bound): |acceleration| <= maxAccel per vehicle, in any dimension -- maxAccelConstraints.  accelRows
+        # 'all': the N (2n+R+1) elevated control points of maxAccel^2 - (d/2)|c''|^2 (the curve of the reference's acceleration
+        # objective, optimization.py:503-519, under a bound); 'true_min': per vehicle its true minimum over the trajectory's
+        # time (obtg_accel_true_min) -- N rows whatever DEG_ELEV is, feasible iff >= 0.
+        if accelRows not in ('all', 'true_min'):
+            raise ValueError("accelRows must be 'all' or 'true_min', not {!r}".format(accelRows))
+        self.accelRows = accelRows
         if angRateRows not in ('all', 'true_min'):
             raise ValueError("angRateRows must be 'all' or 'true_min', not {!r}".format(angRateRows))
         self.angRateRows = angRateRows
@@ -422,6 +438,27 @@ class BezOptimization(object):
         r = ctx.ang_rate_true_min(Y, tf, self.model['maxAngRate'], eps_rel=self.TRUE_MIN_EPS_REL)
         v = _md_checked(r, 'maxAngularRateConstraints(true_min)')['val']
         return v.reshape(v.shape[0], -1)
+
+    def _max_accel(self, what):
+        bound = self.model['maxAccel']
+        if bound is None:
+            raise ValueError("{} needs a bound: maxAccel is None".format(what))
+        return bound
+
+    def _accel_true_min(self, ctx, Y, tf):
+        """accelRows='true_min': [B][N] true per-vehicle minima of the acceleration rows; a search that ran out of budget
+        raises (bezier._raise_md)"""
+        r = ctx.accel_true_min(Y, tf, self._max_accel('maxAccelConstraints'), eps_rel=self.TRUE_MIN_EPS_REL)
+        return _md_checked(r, 'maxAccelConstraints(true_min)')['val']
+
+    def trueAccelMax(self, x):
+        """(max_val[N], t_max[N]): per vehicle the true maximum over the trajectory of (d/2)|acceleration|^2 -- normSquare's
+        factor kept: the scale of the acceleration rows, without their bound -- and the parameter in [0, 1] where it is
+        reached (obtg_accel_true_min with bound 0), whatever `accelRows` is."""
+        x = np.asarray(x, dtype=float)
+        r = self._ctx(False).accel_true_min(self.reshapeVector(x)[None], self._tf_of(x), 0.0, eps_rel=self.TRUE_MIN_EPS_REL)
+        _md_checked(r, 'trueAccelMax')
+        return -r['val'][0], r['t_star'][0]
 
     def trueAngularRateRows(self, x):
         """(val[N][2], t_star[N][2]): per vehicle and side the true minimum over the trajectory of maxAngRate den - num (side 0)
@@ -555,6 +592,17 @@ class BezOptimization(object):
                 return self._speed_true_min(self._ctx(False), y, self._tf_of(x), 'vmax')[0]
             return self._ctx(False).speed(y, self._tf_of(x), self.model['maxSpeed'], True)[0]
         return lambda x: self._serve('vmax', x, direct)
+
+    @property
+    def maxAccelConstraints(self):
+        """maxAccel^2 - (d/2)|acceleration|^2 >= 0: N (2n+R+1) control points (accelRows='all') or N true minima ('true_min')."""
+        def direct(x):
+            bound = self._max_accel('maxAccelConstraints')
+            y = self.reshapeVector(x)
+            if self.accelRows == 'true_min':
+                return self._accel_true_min(self._ctx(False), y, self._tf_of(x))[0]
+            return self._ctx(False).accel(y, self._tf_of(x), bound)[0]
+        return lambda x: self._serve('amax', x, direct)
 
     @property
     def maxAngularRateConstraints(self):
@@ -729,7 +777,7 @@ class BezOptimization(object):
         milliseconds); _serve asks for the key only when at most one variable moved."""
         if refresh or getattr(self, '_rv_cache', None) is None:
             self._rv_parts()
-        return (int(DEG_ELEV), self.separationRows, self.speedRows, self.angRateRows, self.activeRows, self._rv_cache[0], self.model['maxSep'], self.model['maxSpeed'],
+        return (int(DEG_ELEV), self.separationRows, self.speedRows, self.angRateRows, self.accelRows, self.model['maxAccel'], self.activeRows, self._rv_cache[0], self.model['maxSep'], self.model['maxSpeed'],
                 self.model['minSpeed'], self.model['maxAngRate'], None if self._timeopt() else self.model['tf'],
                 None if self.pointObstacles is None else np.asarray(self.pointObstacles, dtype=float).tobytes(),
                 None if self.shapeObstacles is None else tuple(np.asarray(c.cpts, dtype=float).tobytes() for c in self.shapeObstacles))
@@ -766,6 +814,9 @@ class BezOptimization(object):
                 F = c.speed(Y, tf, self.model['maxSpeed'], True)
             elif family == 'vmin':
                 F = c.speed(Y, tf, self.model['minSpeed'], False)
+            elif family == 'amax':
+                F = (self._accel_true_min(c, Y, tf) if self.accelRows == 'true_min'
+                     else c.accel(Y, tf, self._max_accel('maxAccelConstraints')))
             elif self.angRateRows == 'true_min':
                 F = self._ang_true_min(c, Y, tf)
             else:
@@ -854,8 +905,22 @@ class BezOptimization(object):
         itself (one batched call); method='exact' is not built for these rows.
 
         angRateRows='true_min' (the angular rate): the same three answers -- method='envelope' is dense [2N][n_x] from
-        obtg_ang_rate_true_min_jac, 'fd' differences the search, 'exact' raises."""
-        true_min = (family in ('vmax', 'vmin') and self.speedRows == 'true_min') or (family == 'ang' and self.angRateRows == 'true_min')
+        obtg_ang_rate_true_min_jac, 'fd' differences the search, 'exact' raises.
+
+        The acceleration rows ('amax'): 'fd' as above; method='envelope' needs accelRows='true_min' and is dense [N][n_x] from
+        obtg_accel_true_min_jac; method='exact' is not built for either form of the rows."""
+        true_min = ((family in ('vmax', 'vmin') and self.speedRows == 'true_min') or (family == 'ang' and self.angRateRows == 'true_min')
+                    or (family == 'amax' and self.accelRows == 'true_min'))
+        if family == 'amax':
+            if method == 'envelope':
+                if not true_min:
+                    raise ValueError("maxAccelJacobian(method='envelope') needs accelRows='true_min', not {!r}".format(self.accelRows))
+                return self._accel_jac_envelope(x)
+            _check_method(method)
+            if method == 'exact':
+                raise ValueError("maxAccelJacobian(method='exact') is not built for the acceleration rows: use method='fd'"
+                                 " or, with accelRows='true_min', method='envelope'")
+            self._max_accel('maxAccelJacobian')
         if family == 'ang' and (method == 'envelope' or true_min):
             if self.model['dim'] != 2:
                 raise ValueError('The input curve must be two dimensional,\n'
@@ -897,6 +962,8 @@ class BezOptimization(object):
                 return ctx.speed(Y, tf, self.model['maxSpeed'], True)
             if family == 'vmin':
                 return ctx.speed(Y, tf, self.model['minSpeed'], False)
+            if family == 'amax':
+                return ctx.accel(Y, tf, self.model['maxAccel'])
             return ctx.ang_rate(Y, tf, self.model['maxAngRate'])
 
         F0 = evaluate(self._ctx(False), Y0[None], np.array([tf0]))[0]
@@ -924,6 +991,9 @@ class BezOptimization(object):
 
     def maxAngularRateJacobian(self, x, structured=True, method='fd'):
         return self._jac_vehicle(x, 'ang', structured, method)
+
+    def maxAccelJacobian(self, x, structured=True, method='fd'):
+        return self._jac_vehicle(x, 'amax', structured, method)
 
     # ------------------------------------------------------------------ exact Jacobians (method='exact')
     # The device returns d rows / d Y per pair or vehicle ([..][rows][dim][deg+1] blocks, include/obtg.h obtg_*_jac); the chain
@@ -1000,6 +1070,14 @@ class BezOptimization(object):
                                                 self.model['maxSpeed' if is_max else 'minSpeed'], is_max,
                                                 eps_rel=self.TRUE_MIN_EPS_REL)
         _md_checked(r, ('maxSpeedJacobian' if is_max else 'minSpeedJacobian') + '(envelope)')
+        N = self.model['numVeh']
+        return self._scatter_exact(r['jac'][0][:, None], (np.arange(N),), (1.0,), r['jac_tf'][0][:, None])   # blocks of one row each
+
+    def _accel_jac_envelope(self, x):
+        x = np.asarray(x, dtype=float)
+        r = self._ctx(False).accel_true_min_jac(self.reshapeVectors(x[None]), float(self._tf_of(x)),
+                                                self._max_accel('maxAccelJacobian'), eps_rel=self.TRUE_MIN_EPS_REL)
+        _md_checked(r, 'maxAccelJacobian(envelope)')
         N = self.model['numVeh']
         return self._scatter_exact(r['jac'][0][:, None], (np.arange(N),), (1.0,), r['jac_tf'][0][:, None])   # blocks of one row each
 

@@ -99,7 +99,9 @@ const char* obtg_strerror(int code);
  *      Later, still 7: new: the true angular-rate rows obtg_ang_rate_true_min[_dev], their envelope Jacobian
  *      obtg_ang_rate_true_min_jac[_dev] and the rows' polynomials obtg_ang_rate_poly[_dev] (timed under OBTG_K_ANG_RATE).
  *      Later, still 7: new: the acceleration-bound rows obtg_accel[_dev], their true minima obtg_accel_true_min[_dev] and the
- *      envelope Jacobian obtg_accel_true_min_jac[_dev] (timed under OBTG_K_SPEED). */
+ *      envelope Jacobian obtg_accel_true_min_jac[_dev] (timed under OBTG_K_SPEED).
+ *      Later, still 7: new: the jerk-bound rows obtg_jerk[_dev], their true minima obtg_jerk_true_min[_dev] and the envelope
+ *      Jacobian obtg_jerk_true_min_jac[_dev] (timed under OBTG_K_SPEED). */
 #define OBTG_ABI_VERSION 7
 int obtg_abi_version(void);
 
@@ -742,6 +744,55 @@ int obtg_accel_true_min_jac(obtg_ctx*, const double* Y, const double* tf /*[B]*/
                             double* jac /*[B][N][d][n+1]*/, double* jac_tf /*[B][N], nullable*/);
 int obtg_accel_true_min_jac_dev(obtg_ctx*, const double* dY, const double* d_tf, int B, double bound, double eps_rel, int max_nodes,
                                 double* d_out, double* d_t_star, int* d_status, double* d_jac, double* d_jac_tf);
+
+/* ---- the jerk bound: |d^3 c / dtime^3| <= bound for every vehicle, in 2-D, 3-D and any other dimension ----
+ * For vehicle v with control points P[c][i] (c < d, i <= n) on a span T = tf[b]:
+ *     q(t) = bound**2 - (d/2) |c'''(t)|^2,
+ *     c'''_c(t) = (n(n-1)(n-2)/T^3) sum_{i<=n-3} B_i^(n-3)(t) (P[c][i+3] - 3 P[c][i+2] + 3 P[c][i+1] - P[c][i]).
+ * normSquare's (d/2) factor and Python's bound**2 are kept, as for the speed and acceleration rows.
+ * obtg_jerk: the 2n+R+1 Bernstein coefficients of q, out[B][N][2n+R+1], in the reference's sequence for the jerk
+ *     (optimization.py:522-539): diff() (the derivative, then elev(1)) three times, normSquare(), elev(R), then
+ *     fma(-1, c, bound**2).  The third derivative's control points are formed by csrc/bern_device.h diff_elev1_at applied
+ *     three times (diff3_elev1_rows), every multiply-add an explicit fma: every kernel form gives the same source curve.
+ *     Degree 1: the second pass is exactly zero, every row equals bound**2 bit for bit.  Degree 2: the third derivative is
+ *     zero, but three rounded passes need not cancel: the rows equal bound**2 up to that residue (the reference's own chain
+ *     leaves one too).  Degree 3: the jerk is constant, the row constant in t up to rounding.  Argument checks, the specialised
+ *     shapes and the any-degree route are obtg_speed's; _dev: dY may be NULL inside an obtg_fd_view.
+ * obtg_jerk_true_min: out[B][N] = min over t in [0, 1] of q: feasible iff >= 0, bound**2 - max over t of (d/2)|c'''|^2.
+ *     DEG_ELEV does not enter and the context's R is not read.  The 2n+1 coefficients are the bits of obtg_jerk's rows on a
+ *     context with DEG_ELEV = 0, so out, t_star, status are the bits of obtg_bern_extrema(eps_abs = 0, want_max = 0) on those
+ *     rows.  An end coefficient that is the row's smallest is returned as is (t_star 0 or 1).  Degree 3: t_star is anywhere in
+ *     [0, 1]; degree 4: c''' is linear, the row concave, every minimum at an end.  A row with a non-finite coefficient: val
+ *     and t_star NaN, status OBTG_MD_OK.  tf <= 0 is the caller's business.  Degrees with a specialised kernel
+ *     (obtg_fast_kernels & 1) form the coefficients in registers, one launch; other degrees up to 31 go through a workspace
+ *     of obtg_jerk's R = 0 rows (two launches); above 31: OBTG_ERR_UNSUPPORTED.  t_star and status are nullable.
+ * obtg_jerk_true_min_jac: out, t_star, status are, bit for bit, those of obtg_jerk_true_min with the same arguments, and the
+ *     envelope (Danskin) block of every row at its t_star.  With u = B^(n-3)(t_star), entries out of range 0:
+ *         C_i = (n(n-1)(n-2)/T^3)(u_(i-3) - 3 u_(i-2) + 3 u_(i-1) - u_i)
+ *         jac[B][N][d][n+1]:  jac[c][i] = -d * c'''_c(t_star) * C_i
+ *         jac_tf[B][N] (nullable):  -6 (q(t_star) - bound**2) / T, q(t_star) - bound**2 = -(d/2)|c'''(t_star)|^2 from the same u
+ *     -- the partial derivatives of q AT THE RETURNED t_star with respect to the vehicle's own control points and to tf at fixed
+ *     control points.  t_star = 0 leaves columns 0 .. 3 as the only non-zero ones, t_star = 1 columns n-3 .. n; degrees 1 and
+ *     2: a zero block; degree 3: the same block at every t.  A row with a non-finite coefficient gets a NaN block and a NaN
+ *     jac_tf (status OBTG_MD_OK); with another status the block is still the derivative at the returned t_star.  Every
+ *     multiply-add is an explicit fma (csrc/bern_device.h jerk_envelope_block): a block depends on the vehicle's control
+ *     points, tf and t_star alone, not on the entry point (host and _dev: same bits) or the kernel form.  Fused
+ *     value-and-blocks kernels (one launch): degrees 3, 5, 7, 8, 10, 15, 20 in 2-D and 3-D, every specialised count -- all
+ *     build without scratch; a context created under OBTG_TRUE_MIN_JAC_FUSED=0 forms the blocks in one more launch from Y, tf
+ *     and t_star on every shape, as other degrees up to 31 do after their value path (three launches).  Degrees above 31:
+ *     OBTG_ERR_UNSUPPORTED.
+ * Every launch is timed under OBTG_K_SPEED.  _dev: dY may be NULL inside an obtg_fd_view; d_tf is device memory, [B]. */
+int obtg_jerk(obtg_ctx*, const double* Y, const double* tf /*[B]*/, int B, double bound, double* out /*[B][N][2n+R+1]*/);
+int obtg_jerk_dev(obtg_ctx*, const double* dY, const double* d_tf, int B, double bound, double* d_out);
+int obtg_jerk_true_min(obtg_ctx*, const double* Y, const double* tf /*[B]*/, int B, double bound, double eps_rel, int max_nodes,
+                       double* out /*[B][N]*/, double* t_star /*[B][N], nullable*/, int* status /*[B][N], nullable*/);
+int obtg_jerk_true_min_dev(obtg_ctx*, const double* dY, const double* d_tf, int B, double bound, double eps_rel, int max_nodes,
+                           double* d_out, double* d_t_star, int* d_status);
+int obtg_jerk_true_min_jac(obtg_ctx*, const double* Y, const double* tf /*[B]*/, int B, double bound, double eps_rel, int max_nodes,
+                           double* out /*[B][N]*/, double* t_star /*[B][N], nullable*/, int* status /*[B][N], nullable*/,
+                           double* jac /*[B][N][d][n+1]*/, double* jac_tf /*[B][N], nullable*/);
+int obtg_jerk_true_min_jac_dev(obtg_ctx*, const double* dY, const double* d_tf, int B, double bound, double eps_rel, int max_nodes,
+                               double* d_out, double* d_t_star, int* d_status, double* d_jac, double* d_jac_tf);
 
 /* ---- single-curve Bernstein algebra (the Bezier object's methods, batched over rows) ----
  * obtg_bern_elev:   Bezier.elev(R)      bezier.py:469-495   in[rows][n+1]   -> out[rows][n+R+1]

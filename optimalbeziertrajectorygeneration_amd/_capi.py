@@ -142,6 +142,12 @@ _SIGNATURES = {
     "obtg_accel_true_min_dev": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
     "obtg_accel_true_min_jac": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "obtg_accel_true_min_jac_dev": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_jerk": (_i, [_vp, _vp, _vp, _i, _d, _vp]),
+    "obtg_jerk_dev": (_i, [_vp, _vp, _vp, _i, _d, _vp]),
+    "obtg_jerk_true_min": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
+    "obtg_jerk_true_min_dev": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
+    "obtg_jerk_true_min_jac": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_jerk_true_min_jac_dev": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "obtg_speed_jac": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "obtg_speed_jac_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "obtg_ang_rate_jac": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
@@ -711,6 +717,40 @@ class Context(object):
         self._check(self._lib.obtg_accel_true_min_jac_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(bound), float(eps_rel),
                                                           int(max_nodes), _vp(d_out), _vp(d_t_star), _vp(d_status), _vp(d_jac),
                                                           _vp(d_jac_tf)), "obtg_accel_true_min_jac_dev")
+
+    def jerk(self, Y, tf, bound):
+        """The jerk-bound rows (obtg_jerk): [B][N * (2 deg + DEG_ELEV + 1)] control points of
+        bound**2 - (d/2)|c'''|^2, c''' = diff().diff().diff() of the vehicle's curve on a span of tf."""
+        Y, B = self._rows(Y)
+        tf = self._tf(tf, B)
+        out = pinned_empty((B, self.len_speed))
+        self._check(self._lib.obtg_jerk(self._h, _ptr(Y), _ptr(tf), B, float(bound), _ptr(out)), "obtg_jerk")
+        return out
+
+    def jerk_dev(self, dY, d_tf, B, bound, d_out):
+        self._check(self._lib.obtg_jerk_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(bound), _vp(d_out)), "obtg_jerk_dev")
+
+    def jerk_true_min(self, Y, tf, bound, eps_rel=1e-9, max_nodes=100000):
+        """Per vehicle the true minimum over t in [0, 1] of bound**2 - (d/2)|c'''|^2 -- the polynomial jerk(Y, tf, bound) holds
+        the control points of (obtg_jerk_true_min; DEG_ELEV does not enter): dict(val[B][N], t_star[B][N], status[B][N])."""
+        return self._true_min("obtg_jerk_true_min", self.n_veh, Y, tf, (float(bound),), eps_rel, max_nodes)
+
+    def jerk_true_min_dev(self, dY, d_tf, B, bound, d_out, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
+        self._check(self._lib.obtg_jerk_true_min_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(bound), float(eps_rel),
+                                                      int(max_nodes), _vp(d_out), _vp(d_t_star), _vp(d_status)),
+                    "obtg_jerk_true_min_dev")
+
+    def jerk_true_min_jac(self, Y, tf, bound, eps_rel=1e-9, max_nodes=100000):
+        """jerk_true_min with its envelope Jacobian (obtg_jerk_true_min_jac): dict(val, t_star, status -- the bits of
+        jerk_true_min --, jac[B][N][dim][deg+1]: d/d(the vehicle's own control points) of its polynomial at t_star,
+        jac_tf[B][N]: d/dtf at fixed control points)."""
+        return self._true_min("obtg_jerk_true_min_jac", self.n_veh, Y, tf, (float(bound),), eps_rel, max_nodes, "jac", "jac_tf")
+
+    def jerk_true_min_jac_dev(self, dY, d_tf, B, bound, d_out, d_jac, d_jac_tf=None, d_t_star=None, d_status=None,
+                               eps_rel=1e-9, max_nodes=100000):
+        self._check(self._lib.obtg_jerk_true_min_jac_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(bound), float(eps_rel),
+                                                          int(max_nodes), _vp(d_out), _vp(d_t_star), _vp(d_status), _vp(d_jac),
+                                                          _vp(d_jac_tf)), "obtg_jerk_true_min_jac_dev")
 
     def ang_rate_poly(self, Y, tf, max_rate):
         """The true angular-rate rows' polynomials (obtg_ang_rate_poly; dim 2): [B][N][2][2 deg + 1] Bernstein coefficients of

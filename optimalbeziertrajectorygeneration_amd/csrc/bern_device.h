@@ -355,6 +355,21 @@ __device__ __forceinline__ void diff2_elev1_rows(const double (&p)[NC], const do
     for (int c = 0; c < NC; ++c) d[c] = diff_elev1_at(x1, c, N, val);
 }
 
+// The source curve of a jerk row (obtg_jerk, obtg_jerk_true_min[_jac]) -- Bezier.diff().diff().diff(), the curve of the
+// reference's jerk objective (optimization.py:522-539) -- as diff_elev1_at applied three times: diff2_elev1_rows and one more
+// pass, the same operations in the same order in the specialised rows kernel (normsq_elev_body, MODE 3), the fused
+// true-minimum kernels (JerkRows) and, element by element through LDS, the any-degree rows kernel.  n = 1: the second pass is
+// exactly zero, and so is the third; n = 2: zero up to the rounding of three passes.
+template <int NC>
+__device__ __forceinline__ void diff3_elev1_rows(const double (&p)[NC], const double val, double (&d)[NC])
+{
+    constexpr int N = NC - 1;
+    double x2[NC];
+    diff2_elev1_rows<NC>(p, val, x2);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) d[c] = diff_elev1_at(x2, c, N, val);
+}
+
 // Envelope block of one vehicle's acceleration row at parameter t: the partial derivatives of
 // q(t) = sign (DIM/2) |c''(t)|^2 + offset, c'' = d^2 c / dtime^2 on a span of T, with respect to the vehicle's own control
 // points and to T (obtg_accel_true_min_jac).  With n = nc - 1, u = B^(n-2)(t), entries out of range 0, and
@@ -399,6 +414,57 @@ __device__ __forceinline__ double accel_envelope_block(const double* __restrict_
                 out[c * nc + i] = kd * (((i < 2 ? 0.0 : u[i - 2]) - (i == 0 ? 0.0 : u[i - 1])) - ((i == 0 ? 0.0 : u[i - 1]) - u[i]));
     }
     return (-4.0 * ((sign * (0.5 * (double)DIM)) * ss)) / T;
+}
+
+// Envelope block of one vehicle's jerk row at parameter t (obtg_jerk_true_min_jac): accel_envelope_block one derivative further.
+// q(t) = sign (DIM/2) |c'''(t)|^2 + offset; with n = nc - 1, u = B^(n-3)(t), entries out of range 0, and
+// c'''_c(t) = (n(n-1)(n-2)/T^3) sum_i u_i (P_c,i+3 - 3 P_c,i+2 + 3 P_c,i+1 - P_c,i):
+//     C_i = (n(n-1)(n-2)/T^3)(u_(i-3) - 3 u_(i-2) + 3 u_(i-1) - u_i),    out[c][i] = sign DIM c'''_c(t) C_i;
+//     returns dq/dT = -6 (q(t) - offset) / T,
+// q(t) - offset evaluated here from the same u.  The third differences are differences of differences of differences, in
+// index order; the basis from the de Casteljau recurrence on the basis, every multiply-add an explicit fma, contraction off
+// inside.  n <= 2: u is empty, the block and dq/dT are zero.  t = 0 / t = 1 leave columns (0 .. 3) / (n - 3 .. n) as the only
+// non-zero ones; a NaN t gives a NaN block (n >= 3) and a NaN dq/dT.
+template <int NCMAX, int DIM>
+__device__ __forceinline__ double jerk_envelope_block(const double* __restrict__ y, const int nc, const double T, const double sign,
+                                                      const double t, double* __restrict__ out)
+{
+#pragma clang fp contract(off)
+    const int n = nc - 1;
+    const double s = 1.0 - t;
+    double u[NCMAX];                       // u[0 .. n - 2): B^(n-3)(t); the rest stays zero
+#pragma unroll
+    for (int i = 0; i < NCMAX; ++i) u[i] = (i == 0 && n >= 3) ? (t == t ? 1.0 : t) : 0.0;      // n = 3: B^0 = 1 carries a NaN t too
+#pragma unroll
+    for (int r = 1; r < NCMAX - 3; ++r)
+        if (r < n - 2) {
+#pragma unroll
+            for (int i = r; i >= 1; --i) u[i] = __builtin_fma(t, u[i - 1], s * u[i]);
+            u[0] = s * u[0];
+        }
+    const double nnT = (((double)n / T) * ((double)(n - 1) / T)) * ((double)(n - 2) / T);
+    double ss = 0.0;
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+        double b = 0.0;
+#pragma unroll
+        for (int i = 0; i < NCMAX - 3; ++i)
+            if (i < n - 2) {
+                const double d0 = y[c * nc + i + 1] - y[c * nc + i], d1 = y[c * nc + i + 2] - y[c * nc + i + 1],
+                             d2 = y[c * nc + i + 3] - y[c * nc + i + 2];
+                b = __builtin_fma(u[i], (d2 - d1) - (d1 - d0), b);
+            }
+        const double a = nnT * b;
+        ss = c == 0 ? a * a : __builtin_fma(a, a, ss);
+        const double kd = (sign * (double)DIM) * (a * nnT);
+#pragma unroll
+        for (int i = 0; i < NCMAX; ++i)
+            if (i < nc) {
+                const double u3 = i < 3 ? 0.0 : u[i - 3], u2 = i < 2 ? 0.0 : u[i - 2], u1 = i < 1 ? 0.0 : u[i - 1];
+                out[c * nc + i] = kd * (((u3 - u2) - (u2 - u1)) - ((u2 - u1) - (u1 - u[i])));
+            }
+    }
+    return (-6.0 * ((sign * (0.5 * (double)DIM)) * ss)) / T;
 }
 
 template <class A>
@@ -1148,7 +1214,7 @@ __device__ __forceinline__ void tsep_tile_from_xy(const TsepXYParams& t, const d
 // (b, w) = evaluation row and workgroup index inside the row; lds = the workgroup's dynamic LDS.
 // A device function so that the pair sweep can run it next to the GJK workgroups in ONE launch
 // (gjk_kernels.hip k_pair_sweep); k_normsq_elev below is the stand-alone kernel.
-template <int NC, int DIM, int MODE /*0 = pairs, 1 = vehicles (speed), 2 = vehicles (acceleration)*/, bool MINONLY, bool ELEV>
+template <int NC, int DIM, int MODE /*0 = pairs, 1 = vehicles (speed), 2 = vehicles (acceleration), 3 = vehicles (jerk)*/, bool MINONLY, bool ELEV>
 __device__ __forceinline__ void normsq_elev_body(const NsParams& p, const int b, const int w, double* lds)
 {
     using S = NsShape<NC, DIM>;
@@ -1259,7 +1325,7 @@ __device__ __forceinline__ void normsq_elev_body(const NsParams& p, const int b,
                 for (int c = 1; c < N; ++c)
                     a[q][c] = t[c - 1] * ((double)c / (double)N) + t[c] * ((double)(N - c) / (double)N);
             }
-        } else {
+        } else if (MODE == 2) {
             // Bezier.diff().diff(): the acceleration rows' source curve (diff2_elev1_rows: nothing left to contraction)
             const double* v = vl + si * S::VP;
             const double val = (double)N / p.tf[b];
@@ -1269,6 +1335,17 @@ __device__ __forceinline__ void normsq_elev_body(const NsParams& p, const int b,
 #pragma unroll
                 for (int c = 0; c < NC; ++c) x[c] = v[q * NC + c];
                 diff2_elev1_rows<NC>(x, val, a[q]);
+            }
+        } else {
+            // Bezier.diff().diff().diff(): the jerk rows' source curve (diff3_elev1_rows)
+            const double* v = vl + si * S::VP;
+            const double val = (double)N / p.tf[b];
+#pragma unroll
+            for (int q = 0; q < DIM; ++q) {
+                double x[NC];
+#pragma unroll
+                for (int c = 0; c < NC; ++c) x[c] = v[q * NC + c];
+                diff3_elev1_rows<NC>(x, val, a[q]);
             }
         }
 

@@ -41,7 +41,7 @@ namespace obtg {
 
 // (the elevated full rows: B fragments, accumulators and A fragments of a group are ~210 registers, and LDS holds two
 // workgroups per CU anyway: two waves per SIMD)
-template <int NC, int DIM, int MODE /*0 = pairs, 1 = vehicles (speed), 2 = vehicles (acceleration)*/, bool MINONLY, bool ELEV>
+template <int NC, int DIM, int MODE /*0 = pairs, 1 = vehicles (speed), 2 = vehicles (acceleration), 3 = vehicles (jerk)*/, bool MINONLY, bool ELEV>
 __global__ __launch_bounds__(256, (ELEV && !MINONLY) ? 2 : 1) void k_normsq_elev(const NsParams p)
 {
     extern __shared__ double lds[];
@@ -706,6 +706,27 @@ __global__ __launch_bounds__(kWave) void k_generic_normsq_elev(const GenParams p
             const int q = e / nc, c = e - q * nc;
             ah[e] = diff_elev1_at(tm + q * nc, c, n, val) * bn[c];
         }
+    } else if (MODE == 3) {
+        // the jerk rows' source curve, element by element: diff_elev1_at three times (diff3_elev1_rows), tm -> ah -> tm, then
+        // the scaled operand back into ah for the tail
+        const double val = (double)n / p.tf[b];
+        const double* v = Yrow + (size_t)item * dim * nc;
+        for (int e = lane; e < dim * nc; e += kWave) {
+            const int q = e / nc, c = e - q * nc;
+            tm[e] = diff_elev1_at(v + q * nc, c, n, val);
+        }
+        __syncthreads();
+        for (int e = lane; e < dim * nc; e += kWave) {
+            const int q = e / nc, c = e - q * nc;
+            ah[e] = diff_elev1_at(tm + q * nc, c, n, val);
+        }
+        __syncthreads();
+        for (int e = lane; e < dim * nc; e += kWave) {
+            const int q = e / nc, c = e - q * nc;
+            tm[e] = diff_elev1_at(ah + q * nc, c, n, val) * bn[c];
+        }
+        __syncthreads();
+        for (int e = lane; e < dim * nc; e += kWave) ah[e] = tm[e];
     } else {
         const double val = (double)n / p.tf[b];
         const double* v = Yrow + (size_t)item * dim * nc;
@@ -1417,7 +1438,7 @@ __global__ __launch_bounds__(256) void k_select_smallest(const double* __restric
     sm.store(out, idx, (size_t)it * k, k);
 }
 
-// MODE's rows (0: separation, 1: speed, 2: acceleration) from the any-degree kernel at elevation R, timed under the MODE's kernel id: the
+// MODE's rows (0: separation, 1: speed, 2: acceleration, 3: jerk) from the any-degree kernel at elevation R, timed under the MODE's kernel id: the
 // tail of launch_temporal_sep / launch_speed with R = c->R, the R = 0 rows of the true-minimum families (rows_r0) with 0
 template <int MODE>
 static int launch_generic_rows(obtg_ctx* c, const double* dY, const double* d_tf, int B, int item_begin, int item_count, int R,
@@ -1479,8 +1500,8 @@ void speed_sign_offset(double bound, int is_max, double& sign, double& offset)
     offset = is_max ? b2 : -b2;
 }
 
-// deriv: 1 = the speed rows, 2 = the acceleration rows (obtg_accel): the same staging, plan and dispatch, the source curve
-// one derivative further (MODE 2)
+// deriv: 1 = the speed rows, 2 = the acceleration rows (obtg_accel), 3 = the jerk rows (obtg_jerk): the same staging, plan and
+// dispatch, the source curve one and two derivatives further (MODE 2, MODE 3)
 int launch_speed(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max,
                  double* d_out, int deriv)
 {
@@ -1503,11 +1524,13 @@ int launch_speed(obtg_ctx* c, const double* dY, const double* d_tf, int B, doubl
         p.stage_all = 0; p.tiling = 0; p.tiles = nullptr;
         p.sign = sign; p.offset = offset;
         if (c->fd.Y0) { p.Y = c->fd.Y0; p.fd = 1 + c->fd.row0; p.fd_fixed = c->fd.fixed; p.fd_h = c->fd.h; }
-        rc = deriv == 2 ? dispatch_ns<2, false>(c, p, B, OBTG_K_SPEED) : dispatch_ns<1, false>(c, p, B, OBTG_K_SPEED);
+        rc = deriv == 3 ? dispatch_ns<3, false>(c, p, B, OBTG_K_SPEED)
+           : deriv == 2 ? dispatch_ns<2, false>(c, p, B, OBTG_K_SPEED) : dispatch_ns<1, false>(c, p, B, OBTG_K_SPEED);
         if (rc != OBTG_ERR_UNSUPPORTED) return rc;
     }
     if (c->fd.Y0) return kNeedBatch;
-    return deriv == 2 ? launch_generic_rows<2>(c, dY, d_tf, B, 0, c->n_veh, c->R, sign, offset, false, d_out)
+    return deriv == 3 ? launch_generic_rows<3>(c, dY, d_tf, B, 0, c->n_veh, c->R, sign, offset, false, d_out)
+         : deriv == 2 ? launch_generic_rows<2>(c, dY, d_tf, B, 0, c->n_veh, c->R, sign, offset, false, d_out)
                       : launch_generic_rows<1>(c, dY, d_tf, B, 0, c->n_veh, c->R, sign, offset, false, d_out);
 }
 
@@ -1534,6 +1557,13 @@ RowFamily speed_row_family(const obtg_ctx* c, const double* d_tf, double bound, 
 RowFamily accel_row_family(const obtg_ctx* c, const double* d_tf, double bound)
 {
     RowFamily f{ ROWS_ACCEL, c->n_veh, OBTG_K_SPEED, 0.0, 0.0, d_tf, rows_r0<2> };
+    speed_sign_offset(bound, 1, f.sign, f.offset);
+    return f;
+}
+
+RowFamily jerk_row_family(const obtg_ctx* c, const double* d_tf, double bound)
+{
+    RowFamily f{ ROWS_JERK, c->n_veh, OBTG_K_SPEED, 0.0, 0.0, d_tf, rows_r0<3> };
     speed_sign_offset(bound, 1, f.sign, f.offset);
     return f;
 }

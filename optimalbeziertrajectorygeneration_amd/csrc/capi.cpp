@@ -251,6 +251,7 @@ const char* obtg_abi_symbols(void)
         "obtg_bern_extrema\0obtg_bern_extrema_dev\0obtg_temporal_sep_true_min\0obtg_temporal_sep_true_min_dev\0obtg_temporal_sep_true_min_jac\0obtg_temporal_sep_true_min_jac_dev\0"
         "obtg_speed_true_min\0obtg_speed_true_min_dev\0obtg_speed_true_min_jac\0obtg_speed_true_min_jac_dev\0"
         "obtg_accel\0obtg_accel_dev\0obtg_accel_true_min\0obtg_accel_true_min_dev\0obtg_accel_true_min_jac\0obtg_accel_true_min_jac_dev\0"
+        "obtg_jerk\0obtg_jerk_dev\0obtg_jerk_true_min\0obtg_jerk_true_min_dev\0obtg_jerk_true_min_jac\0obtg_jerk_true_min_jac_dev\0"
         "obtg_ang_rate_poly\0obtg_ang_rate_poly_dev\0obtg_ang_rate_true_min\0obtg_ang_rate_true_min_dev\0obtg_ang_rate_true_min_jac\0obtg_ang_rate_true_min_jac_dev\0"
         "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_restrict\0obtg_bern_eval\0"
         "obtg_euclidean_obj\0obtg_accel_obj\0obtg_jerk_obj\0"
@@ -536,6 +537,13 @@ int obtg_accel_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, dou
     if (!check_ctx(c) || !d_tf || !d_out || B < 0) return OBTG_ERR_ARG;
     (void)hipSetDevice(c->device);
     return with_batch(c, dY, B, true, [&](const double* src) { return launch_speed(c, src, d_tf, B, bound, 1, d_out, 2); });
+}
+
+int obtg_jerk_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, double* d_out)
+{
+    if (!check_ctx(c) || !d_tf || !d_out || B < 0) return OBTG_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    return with_batch(c, dY, B, true, [&](const double* src) { return launch_speed(c, src, d_tf, B, bound, 1, d_out, 3); });
 }
 
 int obtg_ang_rate_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double max_rate, double* d_out)
@@ -943,6 +951,20 @@ int obtg_accel(obtg_ctx* c, const double* Y, const double* tf, int B, double bou
     const double* d_tf = h.in(c->ws_in2, tf, (size_t)B, true);
     double* d_out = h.out<double>(c->ws_out, n, true);
     h.run([&] { return launch_speed(c, dY, d_tf, B, bound, 1, d_out, 2); });
+    return h.finish(out, d_out, n);
+}
+
+// obtg_accel with the source curve one derivative further still
+int obtg_jerk(obtg_ctx* c, const double* Y, const double* tf, int B, double bound, double* out)
+{
+    if (!check_ctx(c) || !Y || !tf || !out || B < 0) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    const size_t n = (size_t)obtg_len_speed(c) * B;
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    const double* d_tf = h.in(c->ws_in2, tf, (size_t)B, true);
+    double* d_out = h.out<double>(c->ws_out, n, true);
+    h.run([&] { return launch_speed(c, dY, d_tf, B, bound, 1, d_out, 3); });
     return h.finish(out, d_out, n);
 }
 
@@ -1634,8 +1656,8 @@ int obtg_bern_extrema(obtg_ctx* c, const double* coef, int M, int K, int want_ma
 }
 
 // ------------------------------------------------------------------ the true-minimum row families
-// The one path of obtg_temporal_sep_true_min[_jac][_dev], obtg_speed_true_min[_jac][_dev], obtg_accel_true_min[_jac][_dev]
-// and obtg_ang_rate_true_min[_jac][_dev]: each entry point is its own argument check and its family's descriptor
+// The one path of obtg_temporal_sep_true_min[_jac][_dev], obtg_speed_true_min[_jac][_dev], obtg_accel_true_min[_jac][_dev],
+// obtg_jerk_true_min[_jac][_dev] and obtg_ang_rate_true_min[_jac][_dev]: each entry point is its own argument check and its family's descriptor
 // (obtg_internal.h RowFamily); the launch chain (true_min_chain), the host body (true_min_host) and the _dev body
 // (true_min_dev) are shared.  A further family starts as a copy of the speed entry points, as the angular-rate ones did
 // (they answer as the speed calls do, and dim != 2 with OBTG_ERR_ARG).
@@ -1821,6 +1843,40 @@ int obtg_accel_true_min_jac(obtg_ctx* c, const double* Y, const double* tf, int 
     if (!Y || !jac) return OBTG_ERR_ARG;
     if (B == 0) return OBTG_OK;
     return true_min_host(c, accel_row_family(c, nullptr, bound), Y, tf, B, eps_rel, max_nodes, out, t_star, status, jac, jac_tf);
+}
+
+// The jerk family: the speed entry points with jerk_row_family (checks: speed_true_min_args)
+int obtg_jerk_true_min_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, double eps_rel, int max_nodes,
+                            double* d_out, double* d_t_star, int* d_status)
+{
+    if (int rc = speed_true_min_args(c, d_tf, d_out, B, max_nodes, eps_rel)) return rc;
+    return true_min_dev(c, jerk_row_family(c, d_tf, bound), dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, nullptr, nullptr);
+}
+
+int obtg_jerk_true_min(obtg_ctx* c, const double* Y, const double* tf, int B, double bound, double eps_rel, int max_nodes,
+                        double* out, double* t_star, int* status)
+{
+    if (int rc = speed_true_min_args(c, tf, out, B, max_nodes, eps_rel)) return rc;
+    if (!Y) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    return true_min_host(c, jerk_row_family(c, nullptr, bound), Y, tf, B, eps_rel, max_nodes, out, t_star, status, nullptr, nullptr);
+}
+
+int obtg_jerk_true_min_jac_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, double eps_rel, int max_nodes,
+                                double* d_out, double* d_t_star, int* d_status, double* d_jac, double* d_jac_tf)
+{
+    if (int rc = speed_true_min_args(c, d_tf, d_out, B, max_nodes, eps_rel)) return rc;
+    if (!d_jac) return OBTG_ERR_ARG;
+    return true_min_dev(c, jerk_row_family(c, d_tf, bound), dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, d_jac, d_jac_tf);
+}
+
+int obtg_jerk_true_min_jac(obtg_ctx* c, const double* Y, const double* tf, int B, double bound, double eps_rel, int max_nodes,
+                            double* out, double* t_star, int* status, double* jac, double* jac_tf)
+{
+    if (int rc = speed_true_min_args(c, tf, out, B, max_nodes, eps_rel)) return rc;
+    if (!Y || !jac) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    return true_min_host(c, jerk_row_family(c, nullptr, bound), Y, tf, B, eps_rel, max_nodes, out, t_star, status, jac, jac_tf);
 }
 
 // what obtg_ang_rate_poly, obtg_ang_rate_true_min[_jac] and their _dev twins check alike: the speed calls' checks, and the

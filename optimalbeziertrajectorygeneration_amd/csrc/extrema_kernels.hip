@@ -18,16 +18,17 @@
 // arrays in the search (K is a run-time count up to 64), the stack is kExStack x (K + 3) doubles per wave.
 //
 // True-minimum row families (obtg_temporal_sep_true_min[_jac], obtg_speed_true_min[_jac], obtg_ang_rate_true_min[_jac],
-// obtg_accel_true_min[_jac]): the polynomial of a pair's separation, of a vehicle's own speed, of one side of its angular-rate
-// bound, of its acceleration, formed in the lane and searched as above -- one kernel body (true_min_body) over a family struct
-// (TsepRows, SpeedRows, AngRows, AccelRows), under the kernel names k_tsep_true_min / k_speed_true_min / k_ang_true_min /
-// k_accel_true_min.  The acceleration family's fused value-and-blocks kernels are the counts of OBTG_NC_ACCEL_LIST
-// (obtg_internal.h): every count of OBTG_NC_SEP, in 2-D and 3-D.
+// obtg_accel_true_min[_jac], obtg_jerk_true_min[_jac]): the polynomial of a pair's separation, of a vehicle's own speed, of one
+// side of its angular-rate bound, of its acceleration, of its jerk, formed in the lane and searched as above -- one kernel body
+// (true_min_body) over a family struct (TsepRows, SpeedRows, AngRows, AccelRows, JerkRows), under the kernel names
+// k_tsep_true_min / k_speed_true_min / k_ang_true_min / k_accel_true_min / k_jerk_true_min.  The acceleration and the jerk
+// families' fused value-and-blocks kernels are the counts of OBTG_NC_ACCEL_LIST / OBTG_NC_JERK_LIST (obtg_internal.h): every
+// count of OBTG_NC_SEP, in 2-D and 3-D.
 // Envelope Jacobian: the derivative of the item's polynomial at the t_star the search returned, bern_device.h
-// envelope_block / speed_envelope_block / ang_envelope_block / accel_envelope_block -- written with explicit fma, so it is the same arithmetic here
+// envelope_block / speed_envelope_block / ang_envelope_block / accel_envelope_block / jerk_envelope_block -- written with explicit fma, so it is the same arithmetic here
 // (contraction off) as anywhere else.  Fused form: the <NC, DIM, true> kernels re-read the item's control points from Y after the search (no
 // register is held across wave_search for it) and every lane writes its own block.  Two-launch form: the value path, then
-// k_tsep_envelope / k_speed_envelope / k_ang_envelope / k_accel_envelope on Y and t_star, any degree up to 31.
+// k_tsep_envelope / k_speed_envelope / k_ang_envelope / k_accel_envelope / k_jerk_envelope on Y and t_star, any degree up to 31.
 #include <algorithm>
 #include <cfloat>
 
@@ -220,7 +221,7 @@ __global__ __launch_bounds__(kExWaves * kWave) void k_bern_extrema(const ExParam
 //   coeffs(q, item, cf)     the item's coefficients BEFORE the output transform, as its rows have them at R = 0,
 //   envelope(q, item, nc, t) the item's envelope block(s) at t, nc <= NC control points at run time,
 // and two __global__ wrappers under names of their own (true_min_body, envelope_body; RowKernels finds them for the host).
-// A further family starts as a copy of SpeedRows, as AngRows and AccelRows did.
+// A further family starts as a copy of SpeedRows, as AngRows, AccelRows and JerkRows did.
 struct TsepExParams {
     const double* __restrict__ Y;      // [B][n_veh*DIM][NC]
     const double* __restrict__ obs;    // [n_obj - n_veh][DIM]
@@ -345,6 +346,37 @@ struct AccelRows {
     }
 };
 
+// obtg_jerk's rows, q(t) = sign (DIM/2) |c'''(t)|^2 + offset of a vehicle: AccelRows with the source curve one derivative
+// further still (bern_device.h diff3_elev1_rows) and the block of the third derivative -- a copy beside AccelRows, not an
+// order template over both: that form moved instructions in seven of the parent's k_accel_true_min kernels.
+template <int NC_, int DIM>
+struct JerkRows {
+    using Params = SpeedExParams;
+    static constexpr int NC = NC_, L = 2 * NC_ - 1;
+    static __device__ __forceinline__ void coeffs(const Params& q, long item, double (&cf)[L])
+    {
+        const int b = (int)(item / q.n_veh);
+        const double* v = q.Y + (size_t)item * (DIM * NC);
+        const double val = (double)(NC - 1) / q.tf[b];
+        double a[DIM][NC];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) {
+            double x[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) x[c] = v[d * NC + c];
+            diff3_elev1_rows<NC>(x, val, a[d]);
+        }
+        normsq_coeffs<NC, DIM>(a, as_ctab(q.W2), cf);
+    }
+    static __device__ __forceinline__ void envelope(const Params& q, long item, int nc, double t)
+    {
+        const int b = (int)(item / q.n_veh);
+        const double dtf = jerk_envelope_block<NC, DIM>(q.Y + (size_t)item * (DIM * nc), nc, q.tf[b], q.sign, t,
+                                                         q.jac + (size_t)item * (DIM * nc));
+        if (q.jac_tf) q.jac_tf[item] = dtf;
+    }
+};
+
 struct AngExParams {
     const double* __restrict__ Y;      // [B][n_veh*2][NC]
     const double* __restrict__ tf;     // [B]
@@ -458,6 +490,10 @@ template <int NC, int DIM, bool JAC>
 __global__ __launch_bounds__(kExWaves * kWave) void k_accel_true_min(const SpeedExParams q) { true_min_body<AccelRows<NC, DIM>, JAC>(q); }
 template <int DIM>
 __global__ __launch_bounds__(kEnvThreads) void k_accel_envelope(const SpeedExParams q, const int nc) { envelope_body<AccelRows<kEnvMaxNC, DIM>>(q, nc); }
+template <int NC, int DIM, bool JAC>
+__global__ __launch_bounds__(kExWaves * kWave) void k_jerk_true_min(const SpeedExParams q) { true_min_body<JerkRows<NC, DIM>, JAC>(q); }
+template <int DIM>
+__global__ __launch_bounds__(kEnvThreads) void k_jerk_envelope(const SpeedExParams q, const int nc) { envelope_body<JerkRows<kEnvMaxNC, DIM>>(q, nc); }
 template <int NC, bool JAC>
 __global__ __launch_bounds__(kExWaves * kWave) void k_ang_true_min(const AngExParams q) { true_min_body<AngRows<NC, 2>, JAC>(q); }
 __global__ __launch_bounds__(kEnvThreads) void k_ang_envelope(const AngExParams q, const int nc) { envelope_body<AngRows<kEnvMaxNC, 2>>(q, nc); }
@@ -554,6 +590,21 @@ template <> struct RowKernels<AccelRows> {
     }
 };
 
+// the jerk family: as the acceleration's, with a list of its own
+static constexpr bool nc_in_jerk(int nc) { return false OBTG_NC_JERK_LIST(OBTG_NC_EQ_); }
+template <> struct RowKernels<JerkRows> {
+    template <int NC, int DIM, bool JAC> static auto fused() -> void (*)(const SpeedExParams)
+    {
+        if constexpr (!JAC || nc_in_jerk(NC)) return k_jerk_true_min<NC, DIM, JAC>;
+        else return nullptr;
+    }
+    template <int DIM> static auto envelope() { return k_jerk_envelope<DIM>; }
+    static SpeedExParams params(const obtg_ctx* c, const RowFamily& f, const double* dY, double* d_jac, double* d_jac_tf)
+    {
+        return RowKernels<SpeedRows>::params(c, f, dY, d_jac, d_jac_tf);
+    }
+};
+
 // the counts of OBTG_NC_SEP whose angular-rate kernels hold their operands in registers; the others
 // take the rows route
 static constexpr bool nc_in_ang(int nc) { return false OBTG_NC_ANG_LIST(OBTG_NC_EQ_); }
@@ -609,6 +660,7 @@ int launch_true_min(obtg_ctx* c, const RowFamily& f, const double* dY, int B, do
         case ROWS_ANG: return launch_fused<AngRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_SPEED: return launch_fused<SpeedRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_ACCEL: return launch_fused<AccelRows>(c, f, dY, ex, d_jac, d_jac_tf);
+        case ROWS_JERK: return launch_fused<JerkRows>(c, f, dY, ex, d_jac, d_jac_tf);
         default: return launch_fused<TsepRows>(c, f, dY, ex, d_jac, d_jac_tf);
     }
 }
@@ -637,6 +689,7 @@ int launch_true_min_envelope(obtg_ctx* c, const RowFamily& f, const double* dY, 
         case ROWS_ANG: return launch_blocks<AngRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_SPEED: return launch_blocks<SpeedRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_ACCEL: return launch_blocks<AccelRows>(c, f, dY, ex, d_jac, d_jac_tf);
+        case ROWS_JERK: return launch_blocks<JerkRows>(c, f, dY, ex, d_jac, d_jac_tf);
         default: return launch_blocks<TsepRows>(c, f, dY, ex, d_jac, d_jac_tf);
     }
 }

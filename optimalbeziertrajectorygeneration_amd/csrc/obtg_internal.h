@@ -26,6 +26,10 @@ namespace obtg {
 //                      the counts of OBTG_NC_SEP that build without scratch; the others form their blocks
 //                      in a launch of their own
 #define OBTG_NC_ACCEL_LIST(X) OBTG_NC_DYN(X) X(21)
+//   OBTG_NC_JERK_LIST : the true jerk rows' fused value-and-blocks kernels (k_jerk_true_min<.., true>; 2-D and 3-D), the counts
+//                      of OBTG_NC_SEP that build without scratch; the others form their blocks in a launch
+//                      of their own
+#define OBTG_NC_JERK_LIST(X) OBTG_NC_DYN(X) X(21)
 static inline bool nc_in_sep(int nc)  { return false OBTG_NC_SEP(OBTG_NC_EQ_); }
 static inline bool nc_in_dyn(int nc)  { return false OBTG_NC_DYN(OBTG_NC_EQ_); }
 static inline bool nc_in_elev(int nc) { return false OBTG_NC_ELEV(OBTG_NC_EQ_); }
@@ -271,7 +275,7 @@ int launch_one_vs_many_min(obtg_ctx* c, const double* d_one, int B, const double
 int launch_one_vs_many_min_spans(obtg_ctx* c, const double* d_one, const double* d_one_span, int B, const double* d_many,
                                  const double* d_many_span, int K, double max_sep, double no_overlap, double* d_out);
 int launch_bern_restrict(obtg_ctx* c, const double* d_in, int rows, int n, const double* d_span, const double* d_target, double* d_out);
-int launch_speed(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max,      // deriv 2: the acceleration rows
+int launch_speed(obtg_ctx* c, const double* dY, const double* d_tf, int B, double bound, int is_max,      // deriv 2: the acceleration rows, 3: the jerk rows
                  double* d_out, int deriv = 1);
 void speed_sign_offset(double bound, int is_max, double& sign, double& offset);    // the output transform of the speed rows
 int launch_ang_rate(obtg_ctx* c, const double* dY, const double* d_tf, int B, double max_rate,
@@ -362,10 +366,10 @@ bool bern_extrema_supported(int K);                    // 1 <= K <= 64: a row is
 int launch_bern_extrema(obtg_ctx* c, const double* d_c, long M, int K, int want_max, double eps_rel, double eps_abs,
                         int max_nodes, double* d_val, double* d_t, double* d_bound, int* d_nodes, int* d_status,
                         int kernel_id = OBTG_K_BERN);     // every output but d_val nullable
-// A true-minimum row family (obtg_temporal_sep_true_min[_jac], obtg_speed_true_min[_jac], obtg_ang_rate_true_min[_jac], obtg_accel_true_min[_jac]) as the host path sees it: what one
+// A true-minimum row family (obtg_temporal_sep_true_min[_jac], obtg_speed_true_min[_jac], obtg_ang_rate_true_min[_jac], obtg_accel_true_min[_jac], obtg_jerk_true_min[_jac]) as the host path sees it: what one
 // call of the family contributes beyond the arguments every family has.  On the device the family is a struct of
-// extrema_kernels.hip (TsepRows, SpeedRows, AngRows, AccelRows), found by `kind`.
-enum RowKind { ROWS_TSEP, ROWS_SPEED, ROWS_ANG, ROWS_ACCEL };
+// extrema_kernels.hip (TsepRows, SpeedRows, AngRows, AccelRows, JerkRows), found by `kind`.
+enum RowKind { ROWS_TSEP, ROWS_SPEED, ROWS_ANG, ROWS_ACCEL, ROWS_JERK };
 struct RowFamily {
     RowKind kind;
     int items;                  // per batch row: n_pairs | n_veh | 2 n_veh
@@ -380,6 +384,7 @@ struct RowFamily {
 RowFamily tsep_row_family(const obtg_ctx* c, double max_sep);                                         // bern_kernels.hip
 RowFamily speed_row_family(const obtg_ctx* c, const double* d_tf, double bound, int is_max);
 RowFamily accel_row_family(const obtg_ctx* c, const double* d_tf, double bound);                      // q = bound^2 - (d/2)|c''|^2
+RowFamily jerk_row_family(const obtg_ctx* c, const double* d_tf, double bound);                       // q = bound^2 - (d/2)|c'''|^2
 RowFamily ang_row_family(const obtg_ctx* c, const double* d_tf, double max_rate);                     // extrema_kernels.hip
 // the angular-rate family's polynomials [B][n_veh][2][2 deg + 1] (obtg_ang_rate_poly; its rows_r0): dim 2, degree 1 .. 31
 int launch_ang_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);

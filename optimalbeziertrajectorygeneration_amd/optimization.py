@@ -114,6 +114,13 @@ def _maxAccelConstraints(y, nVeh, dim, tf, maxAccel):
     return _shape_ctx(nVeh, dim, y.shape[1] - 1, DEG_ELEV).accel(y, tf, maxAccel)[0]
 
 
+def _maxJerkConstraints(y, nVeh, dim, tf, maxJerk):
+    """The jerk-bound rows, maxJerk**2 - (pos.diff().diff().diff().normSquare().elev(DEG_ELEV)) per vehicle (obtg_jerk):
+    the curve of the reference's jerk objective (optimization.py:522-539) as a constraint, any dimension."""
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    return _shape_ctx(nVeh, dim, y.shape[1] - 1, DEG_ELEV).jerk(y, tf, maxJerk)[0]
+
+
 def _maxAngularRateConstraints(y, nVeh, dim, tf, maxAngRate):
     if dim != 2:
         raise ValueError('The input curve must be two dimensional,\n'
@@ -166,7 +173,7 @@ def _check_method(method):
 _MODEL_FIELDS = (
     ('numVeh', 'numVeh', None), ('dim', 'dimension', None), ('deg', 'degree', None), ('minGoal', 'minimizeGoal', None),
     ('maxSep', 'maxSep', None), ('minSpeed', 'minSpeed', None), ('maxSpeed', 'maxSpeed', None),
-    ('maxAngRate', 'maxAngRate', None), ('maxAccel', 'maxAccel', None),
+    ('maxAngRate', 'maxAngRate', None), ('maxAccel', 'maxAccel', None), ('maxJerk', 'maxJerk', None),
     ('initPoints', 'initPoints', np.atleast_2d), ('finalPoints', 'finalPoints', np.atleast_2d),
     ('initSpeeds', 'initSpeeds', np.atleast_1d), ('finalSpeeds', 'finalSpeeds', np.atleast_1d),
     ('initAngs', 'initAngs', np.atleast_1d), ('finalAngs', 'finalAngs', np.atleast_1d),
@@ -295,7 +302,9 @@ class BezOptimization(object):
                  speedRows='all',
                  angRateRows='all',
                  maxAccel=None,
-                 accelRows='all'):
+                 accelRows='all',
+                 maxJerk=None,
+                 jerkRows='all'):
         """Beyond the reference's keywords: `device` (HIP ordinal; None: this process's, see _capi.default_device) and `separationRows` --
         'all': temporalSeparationConstraints returns every elevated control point of every pair, as the
         reference does (optimization.py:337); 'min': one row per pair, the smallest of them -- the
@@ -319,6 +328,13 @@ class BezOptimization(object):
         # 'all': the N (2n+R+1) elevated control points of maxAccel^2 - (d/2)|c''|^2 (the curve of the reference's acceleration
         # objective, optimization.py:503-519, under a bound); 'true_min': per vehicle its true minimum over the trajectory's
         # time (obtg_accel_true_min) -- N rows whatever DEG_ELEV is, feasible iff >= 0.
+        # maxJerk (None: no bound): |jerk| <= maxJerk per vehicle, in any dimension -- maxJerkConstraints.  jerkRows 'all': the
+        # N (2n+R+1) elevated control points of maxJerk^2 - (d/2)|c'''|^2 (the curve of the reference's jerk objective,
+        # optimization.py:522-539, under a bound); 'true_min': per vehicle its true minimum over the trajectory's time
+        # (obtg_jerk_true_min) -- N rows whatever DEG_ELEV is, feasible iff >= 0.
+        if jerkRows not in ('all', 'true_min'):
+            raise ValueError("jerkRows must be 'all' or 'true_min', not {!r}".format(jerkRows))
+        self.jerkRows = jerkRows
         if accelRows not in ('all', 'true_min'):
             raise ValueError("accelRows must be 'all' or 'true_min', not {!r}".format(accelRows))
         self.accelRows = accelRows
@@ -458,6 +474,27 @@ class BezOptimization(object):
         x = np.asarray(x, dtype=float)
         r = self._ctx(False).accel_true_min(self.reshapeVector(x)[None], self._tf_of(x), 0.0, eps_rel=self.TRUE_MIN_EPS_REL)
         _md_checked(r, 'trueAccelMax')
+        return -r['val'][0], r['t_star'][0]
+
+    def _max_jerk(self, what):
+        bound = self.model['maxJerk']
+        if bound is None:
+            raise ValueError("{} needs a bound: maxJerk is None".format(what))
+        return bound
+
+    def _jerk_true_min(self, ctx, Y, tf):
+        """jerkRows='true_min': [B][N] true per-vehicle minima of the jerk rows; a search that ran out of budget
+        raises (bezier._raise_md)"""
+        r = ctx.jerk_true_min(Y, tf, self._max_jerk('maxJerkConstraints'), eps_rel=self.TRUE_MIN_EPS_REL)
+        return _md_checked(r, 'maxJerkConstraints(true_min)')['val']
+
+    def trueJerkMax(self, x):
+        """(max_val[N], t_max[N]): per vehicle the true maximum over the trajectory of (d/2)|jerk|^2 -- normSquare's
+        factor kept: the scale of the jerk rows, without their bound -- and the parameter in [0, 1] where it is
+        reached (obtg_jerk_true_min with bound 0), whatever `jerkRows` is."""
+        x = np.asarray(x, dtype=float)
+        r = self._ctx(False).jerk_true_min(self.reshapeVector(x)[None], self._tf_of(x), 0.0, eps_rel=self.TRUE_MIN_EPS_REL)
+        _md_checked(r, 'trueJerkMax')
         return -r['val'][0], r['t_star'][0]
 
     def trueAngularRateRows(self, x):
@@ -603,6 +640,17 @@ class BezOptimization(object):
                 return self._accel_true_min(self._ctx(False), y, self._tf_of(x))[0]
             return self._ctx(False).accel(y, self._tf_of(x), bound)[0]
         return lambda x: self._serve('amax', x, direct)
+
+    @property
+    def maxJerkConstraints(self):
+        """maxJerk^2 - (d/2)|jerk|^2 >= 0: N (2n+R+1) control points (jerkRows='all') or N true minima ('true_min')."""
+        def direct(x):
+            bound = self._max_jerk('maxJerkConstraints')
+            y = self.reshapeVector(x)
+            if self.jerkRows == 'true_min':
+                return self._jerk_true_min(self._ctx(False), y, self._tf_of(x))[0]
+            return self._ctx(False).jerk(y, self._tf_of(x), bound)[0]
+        return lambda x: self._serve('jmax', x, direct)
 
     @property
     def maxAngularRateConstraints(self):
@@ -777,7 +825,7 @@ class BezOptimization(object):
         milliseconds); _serve asks for the key only when at most one variable moved."""
         if refresh or getattr(self, '_rv_cache', None) is None:
             self._rv_parts()
-        return (int(DEG_ELEV), self.separationRows, self.speedRows, self.angRateRows, self.accelRows, self.model['maxAccel'], self.activeRows, self._rv_cache[0], self.model['maxSep'], self.model['maxSpeed'],
+        return (int(DEG_ELEV), self.separationRows, self.speedRows, self.angRateRows, self.accelRows, self.model['maxAccel'], self.jerkRows, self.model['maxJerk'], self.activeRows, self._rv_cache[0], self.model['maxSep'], self.model['maxSpeed'],
                 self.model['minSpeed'], self.model['maxAngRate'], None if self._timeopt() else self.model['tf'],
                 None if self.pointObstacles is None else np.asarray(self.pointObstacles, dtype=float).tobytes(),
                 None if self.shapeObstacles is None else tuple(np.asarray(c.cpts, dtype=float).tobytes() for c in self.shapeObstacles))
@@ -817,6 +865,9 @@ class BezOptimization(object):
             elif family == 'amax':
                 F = (self._accel_true_min(c, Y, tf) if self.accelRows == 'true_min'
                      else c.accel(Y, tf, self._max_accel('maxAccelConstraints')))
+            elif family == 'jmax':
+                F = (self._jerk_true_min(c, Y, tf) if self.jerkRows == 'true_min'
+                     else c.jerk(Y, tf, self._max_jerk('maxJerkConstraints')))
             elif self.angRateRows == 'true_min':
                 F = self._ang_true_min(c, Y, tf)
             else:
@@ -908,9 +959,20 @@ class BezOptimization(object):
         obtg_ang_rate_true_min_jac, 'fd' differences the search, 'exact' raises.
 
         The acceleration rows ('amax'): 'fd' as above; method='envelope' needs accelRows='true_min' and is dense [N][n_x] from
-        obtg_accel_true_min_jac; method='exact' is not built for either form of the rows."""
+        obtg_accel_true_min_jac; method='exact' is not built for either form of the rows.  The jerk rows
+        ('jmax', jerkRows, obtg_jerk_true_min_jac): the same."""
         true_min = ((family in ('vmax', 'vmin') and self.speedRows == 'true_min') or (family == 'ang' and self.angRateRows == 'true_min')
-                    or (family == 'amax' and self.accelRows == 'true_min'))
+                    or (family == 'amax' and self.accelRows == 'true_min') or (family == 'jmax' and self.jerkRows == 'true_min'))
+        if family == 'jmax':
+            if method == 'envelope':
+                if not true_min:
+                    raise ValueError("maxJerkJacobian(method='envelope') needs jerkRows='true_min', not {!r}".format(self.jerkRows))
+                return self._jerk_jac_envelope(x)
+            _check_method(method)
+            if method == 'exact':
+                raise ValueError("maxJerkJacobian(method='exact') is not built for the jerk rows: use method='fd'"
+                                 " or, with jerkRows='true_min', method='envelope'")
+            self._max_jerk('maxJerkJacobian')
         if family == 'amax':
             if method == 'envelope':
                 if not true_min:
@@ -964,6 +1026,8 @@ class BezOptimization(object):
                 return ctx.speed(Y, tf, self.model['minSpeed'], False)
             if family == 'amax':
                 return ctx.accel(Y, tf, self.model['maxAccel'])
+            if family == 'jmax':
+                return ctx.jerk(Y, tf, self.model['maxJerk'])
             return ctx.ang_rate(Y, tf, self.model['maxAngRate'])
 
         F0 = evaluate(self._ctx(False), Y0[None], np.array([tf0]))[0]
@@ -994,6 +1058,9 @@ class BezOptimization(object):
 
     def maxAccelJacobian(self, x, structured=True, method='fd'):
         return self._jac_vehicle(x, 'amax', structured, method)
+
+    def maxJerkJacobian(self, x, structured=True, method='fd'):
+        return self._jac_vehicle(x, 'jmax', structured, method)
 
     # ------------------------------------------------------------------ exact Jacobians (method='exact')
     # The device returns d rows / d Y per pair or vehicle ([..][rows][dim][deg+1] blocks, include/obtg.h obtg_*_jac); the chain
@@ -1078,6 +1145,14 @@ class BezOptimization(object):
         r = self._ctx(False).accel_true_min_jac(self.reshapeVectors(x[None]), float(self._tf_of(x)),
                                                 self._max_accel('maxAccelJacobian'), eps_rel=self.TRUE_MIN_EPS_REL)
         _md_checked(r, 'maxAccelJacobian(envelope)')
+        N = self.model['numVeh']
+        return self._scatter_exact(r['jac'][0][:, None], (np.arange(N),), (1.0,), r['jac_tf'][0][:, None])   # blocks of one row each
+
+    def _jerk_jac_envelope(self, x):
+        x = np.asarray(x, dtype=float)
+        r = self._ctx(False).jerk_true_min_jac(self.reshapeVectors(x[None]), float(self._tf_of(x)),
+                                                self._max_jerk('maxJerkJacobian'), eps_rel=self.TRUE_MIN_EPS_REL)
+        _md_checked(r, 'maxJerkJacobian(envelope)')
         N = self.model['numVeh']
         return self._scatter_exact(r['jac'][0][:, None], (np.arange(N),), (1.0,), r['jac_tf'][0][:, None])   # blocks of one row each
 

@@ -101,7 +101,10 @@ const char* obtg_strerror(int code);
  *      Later, still 7: new: the acceleration-bound rows obtg_accel[_dev], their true minima obtg_accel_true_min[_dev] and the
  *      envelope Jacobian obtg_accel_true_min_jac[_dev] (timed under OBTG_K_SPEED).
  *      Later, still 7: new: the jerk-bound rows obtg_jerk[_dev], their true minima obtg_jerk_true_min[_dev] and the envelope
- *      Jacobian obtg_jerk_true_min_jac[_dev] (timed under OBTG_K_SPEED). */
+ *      Jacobian obtg_jerk_true_min_jac[_dev] (timed under OBTG_K_SPEED).
+ *      Later, still 7: new: the true arc length obtg_bern_arc_length[_dev] and the objective obtg_arc_length_obj[_dev], timed
+ *      under a kernel-stats id of their own, OBTG_K_ARC_LENGTH = 9.  OBTG_K_COUNT stays 9, the ids of revision 7 as callers
+ *      have sized their arrays by it; OBTG_K_END = 10 is the end of the ids obtg_kernel_stats answers for. */
 #define OBTG_ABI_VERSION 7
 int obtg_abi_version(void);
 
@@ -830,6 +833,56 @@ int obtg_euclidean_obj(obtg_ctx*, const double* Y, int B, double* out /*[B]*/);
 int obtg_accel_obj(obtg_ctx*, const double* Y, const double* tf, int B, double* out /*[B]*/);
 int obtg_jerk_obj(obtg_ctx*, const double* Y, const double* tf, int B, double* out /*[B]*/);
 
+/* ---- true arc length (arclen_kernels.hip) ------------------------------------------------------
+ * The length of the curve itself, L = int_0^1 |c'(t)| dt, and its gradient -- NOT something the reference computes: its
+ * `minGoal='euclidean'` (optimization.py:462-489) sums the control polygon, an upper bound of L that shrinks under degree
+ * elevation and whose gradient is NaN where two neighbouring control points coincide.  This is the quantity that bound stands
+ * in for, with a stated contract like obtg_bern_extrema's.  L depends on neither tf nor the span: there is no tf argument.
+ * c[M][d][K]: M independent curves of K = n + 1 control points in d dimensions, 1 <= d <= 3 (else OBTG_ERR_ARG), degree
+ * 1 <= n <= 31 (K < 2: OBTG_ERR_ARG; K > 32: OBTG_ERR_UNSUPPORTED); independent of the context's shape.
+ * Rule: adaptive bisection with the 8-point Gauss-Legendre rule per panel.  A panel [a, a + w] has the estimate
+ * G = (w / 2) sum_k omega_k |c'(a + w (1 + x_k) / 2)|; with S = the length of the curve's control polygon (what
+ * obtg_euclidean_obj sums: a majorant of L known before the search) and tol = eps_rel * S it is accepted when
+ * |G - (G_left + G_right)| <= tol * w.  Depth first, left to right; a and w are dyadic and so exact.
+ *   len[M]      the sum of G_left + G_right over the accepted panels, in that order -- kept inside the bracket the length lies in,
+ *               chord <= L <= S (chord = |P_n - P_0|, both as rounded on the device): a sum that passes an end, which the
+ *               quadrature's error can do where the curve leaves no room (a straight line, a monotone curve in one dimension),
+ *               is returned as that end, which is nearer to L; so len never exceeds what obtg_euclidean_obj sums;
+ *   err[M]      the sum of |G - G_left - G_right| over them: with status OBTG_MD_OK err <= tol (the widths sum to 1), and the
+ *               true error of len is far below it (the accepted estimate is the finer one);
+ *   nodes[M]    panel estimates formed: 1 for [0, 1] and 2 per bisection (a straight line: 3 at any eps_rel);
+ *   status[M]   OBTG_MD_OK; OBTG_MD_DEPTH_CAP: a panel of width 2^-48 still failed the test and was accepted as it was (a cusp
+ *               off every dyadic point, under a tol near the floor); OBTG_MD_NODE_CAP: max_nodes estimates were used up and the
+ *               panels still waiting were accepted with the estimate they had (they add nothing to err).  Both: DEPTH_CAP.
+ *   grad[M][d][K]  nullable: the derivative of the returned len with respect to the control points, for the panel set the search
+ *               ended on: grad[c][i] = sum over the accepted nodes t_k with weight q_k of
+ *               q_k (c'_c(t_k) / |c'(t_k)|) n (B_(i-1)^(n-1)(t_k) - B_i^(n-1)(t_k)), B_(-1) = B_n = 0 -- what SLSQP needs: forward
+ *               differences of len at a step of 1.5e-8 divide tol by that step.  Where len is an end of the bracket, grad is
+ *               that end's gradient (S: the unit vectors of the two segments at a control point, none for a segment of length
+ *               0; chord: its unit vector at the two end points).  A node with |c'| = 0 adds nothing: a constant
+ *               curve has len 0 and an all-zero grad, not NaN.  Every entry is bounded by 2.  At a cusp the integrand of the
+ *               gradient jumps where that of the length has a kink: its error there is a larger multiple of eps_rel than len's.
+ * Floor of eps_rel: one estimate is 3 n + d + 9 rounded operations deep on a speed of up to n S, so below
+ * 2 n (3 n + d + 9) 2^-53 rounding alone can fail the test; a smaller eps_rel (0 included) is raised to that floor.
+ * A curve with a non-finite control point (or whose polygon overflows): len, err, grad NaN, nodes 0, status OBTG_MD_OK.
+ * A curve's results depend on its control points, eps_rel and max_nodes alone: not on M, the other curves, its position or
+ * the entry point; host and _dev give the same bits.  err, nodes, grad are nullable (and status in the _dev form); M == 0 is
+ * OBTG_OK; max_nodes < 1 or eps_rel < 0 (or NaN): OBTG_ERR_ARG.  Timed under OBTG_K_ARC_LENGTH.
+ *
+ * obtg_arc_length_obj: the objective on the context's shape, out[b] = sum_v len[b][v] in vehicle order on the device, with
+ * Y viewed as [B * N][d][n + 1]: the per-vehicle lengths and gradient blocks are the bits of obtg_bern_arc_length.
+ * status[B] (nullable): the worst status among the row's vehicles; grad[B][N*d][n+1] (nullable): obtg_euclidean_grad's layout.
+ * _dev: dY is a batch in device memory (not NULL: an obtg_fd_view does not serve these calls). */
+int obtg_bern_arc_length(obtg_ctx*, const double* c /*[M][d][K]*/, int M, int d, int K, double eps_rel, int max_nodes,
+                         double* len /*[M]*/, double* err /*[M], nullable*/, int* nodes /*[M], nullable*/,
+                         int* status /*[M]*/, double* grad /*[M][d][K], nullable*/);
+int obtg_bern_arc_length_dev(obtg_ctx*, const double* d_c, int M, int d, int K, double eps_rel, int max_nodes,
+                             double* d_len, double* d_err, int* d_nodes, int* d_status, double* d_grad);
+int obtg_arc_length_obj(obtg_ctx*, const double* Y, int B, double eps_rel, int max_nodes,
+                        double* out /*[B]*/, int* status /*[B], nullable*/, double* grad /*[B][N*d][n+1], nullable*/);
+int obtg_arc_length_obj_dev(obtg_ctx*, const double* dY, int B, double eps_rel, int max_nodes,
+                            double* d_out, int* d_status, double* d_grad);
+
 /* ---- exact derivatives (the `jac` SLSQP takes; no finite differences) ----------------------
  * With n = deg, d = dim, R = deg_elev, L = 2n+R+1, La = 4(n+R)+1, P = C(N+M, 2); every block is batched over the B rows
  * of Y like the value entry points, and the entries of a block are the partial derivatives with respect to the control
@@ -863,7 +916,9 @@ int obtg_deriv_energy_grad(obtg_ctx*, const double* Y, const double* tf, int B, 
  * obtg_kernel_stats returns the accumulated device time and launch count per kernel id. */
 enum {
     OBTG_K_TEMPORAL_SEP = 0, OBTG_K_SPEED = 1, OBTG_K_ANG_RATE = 2, OBTG_K_GJK = 3,
-    OBTG_K_MIN_DIST = 4, OBTG_K_FD_BATCH = 5, OBTG_K_BERN = 6, OBTG_K_PAIR_SWEEP = 7, OBTG_K_JAC = 8, OBTG_K_COUNT = 9
+    OBTG_K_MIN_DIST = 4, OBTG_K_FD_BATCH = 5, OBTG_K_BERN = 6, OBTG_K_PAIR_SWEEP = 7, OBTG_K_JAC = 8, OBTG_K_COUNT = 9,
+    /* ids added after revision 7 was cut (OBTG_K_COUNT is what that revision's callers size their arrays by, and stays) */
+    OBTG_K_ARC_LENGTH = 9, OBTG_K_END = 10
 };
 /* on: 0 = off, 1 = every kernel, OBTG_PROFILE_ONLY(id) = only launches of that kernel id (two
  * events per launch drain the queue between kernels: 15 % of a 0.25 ms step when all three

@@ -18,6 +18,7 @@ OK = 0
 ST_OK, ST_MD_CAP, ST_MAXITER, ST_CYCLE = 0, 1, 2, 3
 MD_OK, MD_NODE_CAP, MD_DEPTH_CAP, MD_GJK_CAP = 0, 1, 2, 3
 K_TEMPORAL_SEP, K_SPEED, K_ANG_RATE, K_GJK, K_MIN_DIST, K_FD_BATCH, K_BERN, K_PAIR_SWEEP, K_JAC, K_COUNT = range(10)
+K_ARC_LENGTH, K_END = 9, 10      # ids added after ABI revision 7 was cut: OBTG_K_COUNT stays what that revision's callers sized arrays by
 
 _lib = None
 
@@ -134,6 +135,10 @@ _SIGNATURES = {
     "obtg_euclidean_obj": (_i, [_vp, _vp, _i, _vp]),
     "obtg_accel_obj": (_i, [_vp, _vp, _vp, _i, _vp]),
     "obtg_jerk_obj": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "obtg_bern_arc_length": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_bern_arc_length_dev": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_arc_length_obj": (_i, [_vp, _vp, _i, _d, _i, _vp, _vp, _vp]),
+    "obtg_arc_length_obj_dev": (_i, [_vp, _vp, _i, _d, _i, _vp, _vp, _vp]),
     "obtg_temporal_sep_jac": (_i, [_vp, _vp, _i, _vp]),
     "obtg_temporal_sep_jac_dev": (_i, [_vp, _vp, _i, _vp]),
     "obtg_accel": (_i, [_vp, _vp, _vp, _i, _d, _vp]),
@@ -816,6 +821,45 @@ class Context(object):
     def accel_obj(self, Y, tf):
         return self.deriv_energy_obj(Y, tf, 2)
 
+    # -- true arc length (include/obtg.h obtg_bern_arc_length / obtg_arc_length_obj)
+    def bern_arc_length(self, c, eps_rel=1e-12, max_nodes=100000, grad=False):
+        """The length of every curve of c[M][d][K] (one curve: [d][K]; degree 1 .. 31, d <= 3), by adaptive 8-point Gauss-Legendre
+        bisection (obtg_bern_arc_length): dict(len[M], err[M], nodes[M], status[M] as MD_*) and, with grad, grad[M][d][K], the
+        derivative of len with respect to the control points.  Where status is MD_OK err <= eps_rel x the length of the
+        control polygon; an eps_rel below the kernel's floor (include/obtg.h) is raised to it."""
+        c = _f64(c)
+        if c.ndim == 2:
+            c = c[None]
+        M, d, K = c.shape
+        r = dict(len=np.empty(M), err=np.empty(M), nodes=np.zeros(M, np.int32), status=np.zeros(M, np.int32))
+        if grad:
+            r["grad"] = np.empty((M, d, K))
+        self._check(self._lib.obtg_bern_arc_length(self._h, _ptr(c), M, d, K, float(eps_rel), int(max_nodes), _ptr(r["len"]),
+                                                   _ptr(r["err"]), _ptr(r["nodes"]), _ptr(r["status"]), _ptr(r.get("grad"))),
+                    "obtg_bern_arc_length")
+        return r
+
+    def bern_arc_length_dev(self, d_c, M, d, K, d_len, d_err=None, d_nodes=None, d_status=None, d_grad=None, eps_rel=1e-12,
+                            max_nodes=100000):
+        self._check(self._lib.obtg_bern_arc_length_dev(self._h, _vp(d_c), int(M), int(d), int(K), float(eps_rel), int(max_nodes),
+                                                       _vp(d_len), _vp(d_err), _vp(d_nodes), _vp(d_status), _vp(d_grad)),
+                    "obtg_bern_arc_length_dev")
+
+    def arc_length_obj(self, Y, eps_rel=1e-12, max_nodes=100000, grad=False):
+        """Per row of Y the summed true lengths of its vehicles' curves (obtg_arc_length_obj): dict(val[B], status[B]: the worst
+        MD_* among the row's vehicles) and, with grad, grad[B][N d][n+1] in euclidean_grad's layout."""
+        Y, B = self._rows(Y)
+        r = dict(val=np.empty(B), status=np.zeros(B, np.int32))
+        if grad:
+            r["grad"] = np.empty((B, self.n_veh * self.dim, self.deg + 1))
+        self._check(self._lib.obtg_arc_length_obj(self._h, _ptr(Y), B, float(eps_rel), int(max_nodes), _ptr(r["val"]),
+                                                  _ptr(r["status"]), _ptr(r.get("grad"))), "obtg_arc_length_obj")
+        return r
+
+    def arc_length_obj_dev(self, dY, B, d_out, d_status=None, d_grad=None, eps_rel=1e-12, max_nodes=100000):
+        self._check(self._lib.obtg_arc_length_obj_dev(self._h, _vp(dY), int(B), float(eps_rel), int(max_nodes), _vp(d_out),
+                                                      _vp(d_status), _vp(d_grad)), "obtg_arc_length_obj_dev")
+
     # -- exact derivatives (include/obtg.h obtg_*_jac / *_grad): blocks per pair / vehicle, [..][d][deg + 1] per vehicle
     def temporal_sep_jac(self, Y):
         """d(temporal_sep rows)/d(first object's control points): [B][P][2n+R+1][d][n+1] (the second object's: the negation)."""
@@ -1244,7 +1288,7 @@ class Context(object):
         """on: events around every kernel launch; only='gjk' (a kernel name): around that kernel alone."""
         mode = int(bool(on))
         if on and only is not None:
-            names = [self._lib.obtg_kernel_name(k).decode() for k in range(K_COUNT)]
+            names = [self._lib.obtg_kernel_name(k).decode() for k in range(K_END)]
             mode = 0x100 | names.index(only)
         self._check(self._lib.obtg_set_profiling(self._h, mode), "obtg_set_profiling")
 
@@ -1256,7 +1300,7 @@ class Context(object):
 
     def kernel_stats(self):
         out = {}
-        for k in range(K_COUNT):
+        for k in range(K_END):
             ms = _d(0)
             n = C.c_longlong(0)
             self._check(self._lib.obtg_kernel_stats(self._h, k, C.byref(ms), C.byref(n)), "obtg_kernel_stats")

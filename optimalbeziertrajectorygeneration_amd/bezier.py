@@ -26,7 +26,10 @@ Differences from the reference, on purpose:
     2-D second curve of another degree; 3-D pairs and a 2-D first curve against a 3-D second one are the reference's.
     `minDist(robust=True)` and `collCheck(robust=True)` -- not the reference's algorithms: their answer is the true
     distance of the curves -- elevate the lower curve to the other's degree (obtg_bern_elev: the same curve, the same
-    parameter) and run the equal-degree search; `collCheck` without `robust` still takes equal degrees only.
+    parameter) and run the equal-degree search; `collCheck` without `robust` still takes equal degrees only;
+  * `arcLength` is not in the reference: the true length of the curve (obtg_bern_arc_length), the quantity the reference's
+    control-polygon sum (optimization.py:462-489) bounds from above.  `integrate` is the reference's (bezier.py:521-531),
+    on the host: a sum of deg + 1 numbers.
 """
 import numpy as np
 
@@ -214,6 +217,21 @@ class Bezier(BezierParams):
         new = self.copy()
         new.cpts = _ctx().bern_diff(self.cpts, self.tf - self.t0)
         return new
+
+    def integrate(self):
+        """The integral of every coordinate over the curve's span, one float per dimension (bezier.py:521-531):
+        tf * sum(cpts[d]) / (deg + 1), the control points summed left to right as Python's `sum` does, on the host.  The
+        reference scales by `tf` and not by `tf - t0` -- the integral over a span that starts at 0; that is kept."""
+        return np.array([self.tf * sum(list(row)) / (self.deg + 1) for row in self.cpts])
+
+    def arcLength(self, eps=1e-12, max_nodes=100000):
+        """The length of the curve in space, int |dc/dtau| dtau over [0, 1] (it depends on neither t0 nor tf), within eps x
+        (the length of the control polygon) by adaptive Gauss-Legendre bisection on the device (obtg_bern_arc_length); a
+        search that does not end within max_nodes panel estimates, or that meets a cusp it cannot resolve at eps, raises as
+        minDist does.  Not in the reference."""
+        r = _ctx().bern_arc_length(self.cpts, eps_rel=float(eps), max_nodes=int(max_nodes))
+        _raise_md(r['status'][0], 'arcLength')
+        return float(r['len'][0])
 
     def split(self, tDiv):
         """Two curves, before and after tDiv (bezier.py:533-572): de Casteljau at (tDiv - t0)/(tf - t0); the

@@ -255,6 +255,7 @@ const char* obtg_abi_symbols(void)
         "obtg_ang_rate_poly\0obtg_ang_rate_poly_dev\0obtg_ang_rate_true_min\0obtg_ang_rate_true_min_dev\0obtg_ang_rate_true_min_jac\0obtg_ang_rate_true_min_jac_dev\0"
         "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_restrict\0obtg_bern_eval\0"
         "obtg_euclidean_obj\0obtg_accel_obj\0obtg_jerk_obj\0"
+        "obtg_bern_arc_length\0obtg_bern_arc_length_dev\0obtg_arc_length_obj\0obtg_arc_length_obj_dev\0"
         "obtg_temporal_sep_jac\0obtg_temporal_sep_jac_dev\0obtg_speed_jac\0obtg_speed_jac_dev\0obtg_ang_rate_jac\0obtg_ang_rate_jac_dev\0obtg_euclidean_grad\0obtg_deriv_energy_grad\0"
         "obtg_set_profiling\0obtg_set_profile_period\0obtg_kernel_stats\0obtg_reset_kernel_stats\0obtg_kernel_name\0";
     return syms;
@@ -2062,6 +2063,76 @@ static int host_deriv_obj(obtg_ctx* c, const double* Y, const double* tf, int B,
 int obtg_accel_obj(obtg_ctx* c, const double* Y, const double* tf, int B, double* out) { return host_deriv_obj(c, Y, tf, B, 2, out); }
 int obtg_jerk_obj(obtg_ctx* c, const double* Y, const double* tf, int B, double* out) { return host_deriv_obj(c, Y, tf, B, 3, out); }
 
+// ------------------------------------------------------------------ true arc length (arclen_kernels.hip)
+// obtg_bern_arc_length starts as a copy of obtg_bern_extrema (optional outputs, status required in the host form, M == 0 is
+// OBTG_OK with null pointers, nothing zero copy); obtg_arc_length_obj as a copy of obtg_euclidean_obj (Y and out zero copy)
+// with the optional status and gradient of the _jac calls (not zero copy).
+static int arc_length_args(const obtg_ctx* c, const double* coef, int M, int d, int K, double eps_rel, int max_nodes,
+                           const double* len, bool need_status, const int* status)
+{
+    if (!check_ctx(c) || M < 0 || d < 1 || d > 3 || K < 2 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
+    if (!arc_length_supported(d, K)) return OBTG_ERR_UNSUPPORTED;
+    if (M > 0 && (!coef || !len || (need_status && !status))) return OBTG_ERR_ARG;
+    return OBTG_OK;
+}
+
+int obtg_bern_arc_length_dev(obtg_ctx* c, const double* d_c, int M, int d, int K, double eps_rel, int max_nodes, double* d_len,
+                             double* d_err, int* d_nodes, int* d_status, double* d_grad)
+{
+    if (int rc = arc_length_args(c, d_c, M, d, K, eps_rel, max_nodes, d_len, false, d_status)) return rc;
+    (void)hipSetDevice(c->device);
+    return launch_arc_length(c, d_c, M, d, K, eps_rel, max_nodes, d_len, d_err, d_nodes, d_status, d_grad);
+}
+
+int obtg_bern_arc_length(obtg_ctx* c, const double* coef, int M, int d, int K, double eps_rel, int max_nodes, double* len,
+                         double* err, int* nodes, int* status, double* grad)
+{
+    if (int rc = arc_length_args(c, coef, M, d, K, eps_rel, max_nodes, len, true, status)) return rc;
+    if (M == 0) return OBTG_OK;
+    const size_t m = (size_t)M, ng = grad ? m * d * K : 0;
+    HostCall h(c);
+    const double* d_c = h.in(c->ws_in, coef, m * d * K);
+    double* dv = h.out<double>(c->ws_out, 2 * m + ng);      // len | err | grad
+    int* dn = h.out<int>(c->ws_misc[WS_INFO], 2 * m);       // nodes | status
+    h.run([&] { return launch_arc_length(c, d_c, M, d, K, eps_rel, max_nodes, dv, dv + m, dn, dn + m, grad ? dv + 2 * m : nullptr); });
+    h.fetch(err, dv + m, m);
+    h.fetch(nodes, dn, m);
+    h.fetch(status, dn + m, m);
+    h.fetch(grad, dv + 2 * m, ng);
+    return h.finish(len, dv, m);
+}
+
+static int arc_length_obj_args(const obtg_ctx* c, const double* Y, int B, double eps_rel, int max_nodes, const double* out)
+{
+    if (!check_ctx(c) || !Y || !out || B < 0 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
+    if (!arc_length_supported(c->dim, c->deg + 1)) return OBTG_ERR_UNSUPPORTED;
+    return OBTG_OK;
+}
+
+int obtg_arc_length_obj_dev(obtg_ctx* c, const double* dY, int B, double eps_rel, int max_nodes, double* d_out, int* d_status,
+                            double* d_grad)
+{
+    if (int rc = arc_length_obj_args(c, dY, B, eps_rel, max_nodes, d_out)) return rc;
+    (void)hipSetDevice(c->device);
+    return launch_arc_length_obj(c, dY, B, eps_rel, max_nodes, d_out, d_status, d_grad);
+}
+
+int obtg_arc_length_obj(obtg_ctx* c, const double* Y, int B, double eps_rel, int max_nodes, double* out, int* status, double* grad)
+{
+    if (int rc = arc_length_obj_args(c, Y, B, eps_rel, max_nodes, out)) return rc;
+    if (B == 0) return OBTG_OK;
+    const size_t ng = grad ? ysize(c) * B : 0;
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    double* d_out = h.out<double>(c->ws_out, (size_t)B + ng, !grad);      // out | grad
+    double* d_grad = grad ? d_out + B : nullptr;
+    int* d_st = h.out<int>(c->ws_misc[WS_STATUS], (size_t)B);
+    h.run([&] { return launch_arc_length_obj(c, dY, B, eps_rel, max_nodes, d_out, d_st, d_grad); });
+    h.fetch(status, d_st, (size_t)B);
+    h.fetch(grad, d_grad, ng);
+    return h.finish(out, d_out, (size_t)B);
+}
+
 // ------------------------------------------------------------------ exact derivatives (jac_kernels.hip)
 int obtg_temporal_sep_jac_dev(obtg_ctx* c, const double* dY, int B, double* d_out)
 {
@@ -2164,7 +2235,7 @@ int obtg_deriv_energy_grad(obtg_ctx* c, const double* Y, const double* tf, int B
 int obtg_set_profiling(obtg_ctx* c, int on)
 {
     if (!check_ctx(c)) return OBTG_ERR_ARG;
-    if ((on & OBTG_PROFILE_ONLY_FLAG) && (on & 0xff) >= OBTG_K_COUNT) return OBTG_ERR_ARG;
+    if ((on & OBTG_PROFILE_ONLY_FLAG) && (on & 0xff) >= OBTG_K_END) return OBTG_ERR_ARG;
     OBTG_HIP(c, hipStreamSynchronize(c->stream));
     flush_pending_events(c);
     c->profiling = on != 0;
@@ -2182,7 +2253,7 @@ int obtg_set_profile_period(obtg_ctx* c, int every)
 
 int obtg_kernel_stats(obtg_ctx* c, int kernel_id, double* total_ms, long long* launches)
 {
-    if (!check_ctx(c) || kernel_id < 0 || kernel_id >= OBTG_K_COUNT) return OBTG_ERR_ARG;
+    if (!check_ctx(c) || kernel_id < 0 || kernel_id >= OBTG_K_END) return OBTG_ERR_ARG;
     flush_pending_events(c);
     if (total_ms) *total_ms = c->stats[kernel_id].ms;
     if (launches) *launches = c->stats[kernel_id].launches;
@@ -2209,6 +2280,7 @@ const char* obtg_kernel_name(int id)
         case OBTG_K_BERN: return "bern";
         case OBTG_K_PAIR_SWEEP: return "pair_sweep";
         case OBTG_K_JAC: return "jac";
+        case OBTG_K_ARC_LENGTH: return "arc_length";
         default: return "?";
     }
 }

@@ -92,6 +92,8 @@ struct KernelStat {
 //   host_deriv_obj           holds none -> launch_deriv_energy_obj takes 3, 6, 4 (launch_bern_diff and launch_speed take none)
 //   obtg_bern_extrema        holds 3 (WS_INFO) -> launch_bern_extrema takes none
 //   obtg_gjk_swarm           holds 3 (WS_INFO) -> launch_gjk_swarm takes 7 (WS_L_CHANGED) and, under OBTG_TIMELINE, 6
+//   obtg_bern_arc_length     holds 3 (WS_INFO) -> launch_arc_length takes none
+//   obtg_arc_length_obj      holds 4 (WS_STATUS) -> launch_arc_length_obj takes 7 (WS_L_ROWS: the vehicles' lengths and status)
 enum WsSlot {
     WS_POLY_OFF = 0,      // int[n_poly + 1]: polygon offsets
     WS_CURVE_OFF = 0,     //   int[n_curves + 1]: control-point offsets of obtg_min_dist_mixed's curves
@@ -110,7 +112,8 @@ enum WsSlot {
     WS_L_DIFF_B = 6,      //   launch_deriv_energy_obj: derivative passes, odd ones
     WS_L_TSTAR = 6,       //   true_min_chain: t_star between the value launches and the envelope launch, when the caller wants none
     WS_L_TIMELINE = 6,    //   TimelineDump (gjk_kernels.hip; the one-launch sweeps, which no holder of WS_QUEUE calls)
-    WS_L_ROWS = 7,        // whole rows under a reduction: launch_temporal_sep's any-degree selection, true_min_chain's R = 0 rows
+    WS_L_ROWS = 7,        // whole rows under a reduction: launch_temporal_sep's any-degree selection, true_min_chain's R = 0 rows,
+                          //   launch_arc_length_obj's per-vehicle lengths and status
     WS_L_CHANGED = 7,     //   launch_gjk_swarm's de-duplicated sweep: which objects differ from row 0
     WS_COUNT = 8,
 };
@@ -206,10 +209,10 @@ struct obtg_ctx {
     // instrumentation
     bool profiling = false;
     int profile_period = 1;               // events on every n-th eligible launch of a kernel id
-    long long profile_seen[OBTG_K_COUNT] = {};
+    long long profile_seen[OBTG_K_END] = {};
     unsigned profile_mask = ~0u;          // kernel ids that get events while profiling
     std::vector<hipEvent_t> event_pool;   // recycled events
-    obtg::KernelStat stats[OBTG_K_COUNT];
+    obtg::KernelStat stats[OBTG_K_END];
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending_events;
 };
@@ -395,5 +398,15 @@ int launch_true_min(obtg_ctx* c, const RowFamily& f, const double* dY, int B, do
 // the blocks alone from Y (tf) and the t_star of a value launch: any degree up to 31 (else OBTG_ERR_UNSUPPORTED)
 int launch_true_min_envelope(obtg_ctx* c, const RowFamily& f, const double* dY, int B, const double* d_t, double* d_jac,
                              double* d_jac_tf);
+
+// ---------------------------------------------------------------- launchers (arclen_kernels.hip): true arc length
+bool arc_length_supported(int dim, int K);             // 1 <= dim <= 3, 2 <= K <= 32
+// M curves c[M][dim][K]; an eps_rel below the floor is raised to it; every output but d_len nullable, d_grad [M][dim][K]
+int launch_arc_length(obtg_ctx* c, const double* d_c, long M, int dim, int K, double eps_rel, int max_nodes, double* d_len,
+                      double* d_err, int* d_nodes, int* d_status, double* d_grad);
+// the objective: the curves of dY[B] as the context shapes them, their lengths summed per row in vehicle order (takes
+// WS_L_ROWS); d_status[B] and d_grad[B][n_veh * dim][deg + 1] nullable
+int launch_arc_length_obj(obtg_ctx* c, const double* dY, int B, double eps_rel, int max_nodes, double* d_out, int* d_status,
+                          double* d_grad);
 
 }  // namespace obtg

@@ -522,6 +522,20 @@ class BezOptimization(object):
             _md_checked(r, 'trueSpeedRange')
         return lo['val'][0], lo['t_star'][0], -hi['val'][0], hi['t_star'][0]
 
+    ARC_LENGTH_EPS_REL = 1e-12
+
+    def _arc_length(self, ctx, Y, grad=False, what='arcLengthObjective'):
+        """arc_length_obj of the rows Y at ARC_LENGTH_EPS_REL, every row's search ended (else _md_checked's exception)."""
+        return _md_checked(ctx.arc_length_obj(Y, eps_rel=self.ARC_LENGTH_EPS_REL, grad=grad), what)
+
+    def trueArcLengths(self, x):
+        """len[N]: per vehicle the true length of its trajectory in space (obtg_bern_arc_length at ARC_LENGTH_EPS_REL),
+        whatever the goal is; with minGoal='arcLength' they sum to the objective."""
+        x = np.asarray(x, dtype=float)
+        Y = self.reshapeVector(x).reshape(self.model['numVeh'], self.model['dim'], self.model['deg'] + 1)
+        r = self._ctx(False).bern_arc_length(Y, eps_rel=self.ARC_LENGTH_EPS_REL)
+        return _md_checked(r, 'trueArcLengths')['len']
+
     def _timeopt(self):
         return self.model['minGoal'].lower() == 'timeopt'
 
@@ -536,6 +550,7 @@ class BezOptimization(object):
                           'timeopt': lambda x: x[-1],
                           'accel': self.accelObjective,
                           'jerk': self.jerkObjective,
+                          'arclength': self.arcLengthObjective,
                           }
         try:
             return objectivesDict[minGoal]
@@ -554,12 +569,19 @@ class BezOptimization(object):
     def jerkObjective(self, x):
         return float(self._serve('obj_jerk', x, lambda x_: self._ctx(False).deriv_energy_obj(self.reshapeVector(x_), self.model['tf'], 3)[:1])[0])
 
+    def arcLengthObjective(self, x):
+        """minGoal='arcLength' (not in the reference): the summed TRUE lengths of the vehicles' curves (obtg_arc_length_obj at
+        ARC_LENGTH_EPS_REL) -- what 'euclidean', the control polygon's length, bounds from above.  Forward differences of an
+        adaptive value at SciPy's step divide the rule's tolerance by 1.5e-8: pass objectiveGradient(method='exact') as jac."""
+        return float(self._serve('obj_arclength', x, lambda x_: self._arc_length(self._ctx(False), self.reshapeVector(x_)[None])['val'][:1])[0])
+
     def objectiveGradient(self, x, method='fd'):
         """Gradient of `objectiveFunction` the way SciPy would difference it (2-point, abs_step = sqrt(eps)), but from ONE
         batched evaluation of the n_x + 1 rows instead of n_x + 1 callbacks: pass it as `jac=` to `minimize`.  (With
         the constraint Jacobians supplied, the objective's finite differences are what is left of the per-iteration
         callback count: 17 983 of them in examples/example2_swarm_3d.py with 8 vehicles.)
-        method='exact': the analytic gradient from the device (obtg_euclidean_grad / obtg_deriv_energy_grad) instead."""
+        method='exact': the analytic gradient from the device (obtg_euclidean_grad / obtg_deriv_energy_grad /
+        obtg_arc_length_obj's grad) instead."""
         _check_method(method)
         x = np.asarray(x, dtype=float)
         goal = self.model['minGoal'].lower()
@@ -574,6 +596,8 @@ class BezOptimization(object):
                 G = c.euclidean_grad(Y0)[0]
             elif goal in ('accel', 'jerk'):
                 G = c.deriv_energy_grad(Y0, self.model['tf'], 2 if goal == 'accel' else 3)[0][0]
+            elif goal == 'arclength':
+                G = self._arc_length(c, Y0, grad=True, what='objectiveGradient')['grad'][0]
             else:
                 self.objectiveFunction          # raises the reference's ValueError for an unknown goal
             first = self._rv_parts()[1]
@@ -585,6 +609,8 @@ class BezOptimization(object):
             F = c.euclidean_obj(Y)
         elif goal in ('accel', 'jerk'):
             F = c.deriv_energy_obj(Y, self.model['tf'], 2 if goal == 'accel' else 3)
+        elif goal == 'arclength':
+            F = self._arc_length(c, Y, what='objectiveGradient')['val']
         else:
             self.objectiveFunction          # raises the reference's ValueError for an unknown goal
         return (F[1:] - F[0]) / dx
@@ -841,7 +867,10 @@ class BezOptimization(object):
         Y = self.reshapeVectors(X)
         if family.startswith('obj_'):      # the objectives (one value per row; a column here)
             c = self._ctx(False)
-            F = c.euclidean_obj(Y) if family == 'obj_euclidean' else c.deriv_energy_obj(Y, self.model['tf'], 2 if family == 'obj_accel' else 3)
+            if family == 'obj_arclength':
+                F = self._arc_length(c, Y)['val']
+            else:
+                F = c.euclidean_obj(Y) if family == 'obj_euclidean' else c.deriv_energy_obj(Y, self.model['tf'], 2 if family == 'obj_accel' else 3)
             return np.asarray(F, dtype=float).reshape(-1, 1), dx
         if family == 'tsep':
             with_obs = self.pointObstacles is not None

@@ -588,10 +588,22 @@ class Context(object):
         status[B][P] as MD_*).  val - (the search's lower bound) <= eps_rel x the pair's largest coefficient."""
         return self._true_min("obtg_temporal_sep_true_min", self.num_pairs, Y, None, (float(max_sep),), eps_rel, max_nodes)
 
+    def _true_min_dev(self, name, ops, B, lead, eps_rel, max_nodes, d_out, d_t_star, d_status, *d_blocks):
+        """The device-pointer form of the same calls: obtg_<family>_dev(*ops, B, *lead, eps_rel, max_nodes, d_out, d_t_star,
+        d_status[, d_jac[, d_jac_tf]]) -- ops: dY[, d_tf]; d_blocks: the last two, in the ABI's order."""
+        self._check(getattr(self._lib, name)(self._h, *[_vp(p) for p in ops], int(B), *lead, float(eps_rel), int(max_nodes),
+                                             *[_vp(p) for p in (d_out, d_t_star, d_status) + d_blocks]), name)
+
+    def _vehicle_rows(self, name, Y, tf, lead, shape):
+        """The allocation and the call of the per-vehicle host row calls: obtg_<family>(Y, tf, B, *lead, out[B] + shape)."""
+        Y, B = self._rows(Y)
+        tf = self._tf(tf, B)
+        out = pinned_empty((B,) + shape)
+        self._check(getattr(self._lib, name)(self._h, _ptr(Y), _ptr(tf), B, *lead, _ptr(out)), name)
+        return out
+
     def temporal_sep_true_min_dev(self, dY, B, max_sep, d_out, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
-        self._check(self._lib.obtg_temporal_sep_true_min_dev(self._h, _vp(dY), B, float(max_sep), float(eps_rel), int(max_nodes),
-                                                             _vp(d_out), _vp(d_t_star), _vp(d_status)),
-                    "obtg_temporal_sep_true_min_dev")
+        self._true_min_dev("obtg_temporal_sep_true_min_dev", (dY,), B, (float(max_sep),), eps_rel, max_nodes, d_out, d_t_star, d_status)
 
     def temporal_sep_true_min_jac(self, Y, max_sep, eps_rel=1e-9, max_nodes=100000):
         """temporal_sep_true_min with its envelope Jacobian (obtg_temporal_sep_true_min_jac): dict(val, t_star, status -- the
@@ -601,9 +613,8 @@ class Context(object):
 
     def temporal_sep_true_min_jac_dev(self, dY, B, max_sep, d_out, d_jac, d_t_star=None, d_status=None, eps_rel=1e-9,
                                       max_nodes=100000):
-        self._check(self._lib.obtg_temporal_sep_true_min_jac_dev(self._h, _vp(dY), B, float(max_sep), float(eps_rel),
-                                                                 int(max_nodes), _vp(d_out), _vp(d_t_star), _vp(d_status),
-                                                                 _vp(d_jac)), "obtg_temporal_sep_true_min_jac_dev")
+        self._true_min_dev("obtg_temporal_sep_true_min_jac_dev", (dY,), B, (float(max_sep),), eps_rel, max_nodes, d_out, d_t_star,
+                           d_status, d_jac)
 
     def bern_extrema(self, c, want_max=False, eps_rel=1e-9, eps_abs=0.0, max_nodes=100000):
         """True minimum (want_max: maximum) over [0, 1] of every row of Bernstein coefficients c[M][K], K <= 64
@@ -658,12 +669,7 @@ class Context(object):
                             (self._lib.obtg_comm_last_error(comm._h) or self._lib.obtg_last_error(self._h) or b"").decode()), rc)
 
     def speed(self, Y, tf, bound, is_max):
-        Y, B = self._rows(Y)
-        tf = self._tf(tf, B)
-        out = pinned_empty((B, self.len_speed))
-        self._check(self._lib.obtg_speed(self._h, _ptr(Y), _ptr(tf), B, float(bound), int(bool(is_max)), _ptr(out)),
-                    "obtg_speed")
-        return out
+        return self._vehicle_rows("obtg_speed", Y, tf, (float(bound), int(bool(is_max))), (self.len_speed,))
 
     def speed_true_min(self, Y, tf, bound, is_max, eps_rel=1e-9, max_nodes=100000):
         """Per vehicle the true minimum over t in [0, 1] of the speed row's polynomial sign (d/2)|v'|^2 + offset -- the polynomial
@@ -672,9 +678,8 @@ class Context(object):
         return self._true_min("obtg_speed_true_min", self.n_veh, Y, tf, (float(bound), int(bool(is_max))), eps_rel, max_nodes)
 
     def speed_true_min_dev(self, dY, d_tf, B, bound, is_max, d_out, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
-        self._check(self._lib.obtg_speed_true_min_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(bound), int(bool(is_max)),
-                                                      float(eps_rel), int(max_nodes), _vp(d_out), _vp(d_t_star), _vp(d_status)),
-                    "obtg_speed_true_min_dev")
+        self._true_min_dev("obtg_speed_true_min_dev", (dY, d_tf), B, (float(bound), int(bool(is_max))), eps_rel, max_nodes, d_out,
+                           d_t_star, d_status)
 
     def speed_true_min_jac(self, Y, tf, bound, is_max, eps_rel=1e-9, max_nodes=100000):
         """speed_true_min with its envelope Jacobian (obtg_speed_true_min_jac): dict(val, t_star, status -- the bits of
@@ -685,18 +690,13 @@ class Context(object):
 
     def speed_true_min_jac_dev(self, dY, d_tf, B, bound, is_max, d_out, d_jac, d_jac_tf=None, d_t_star=None, d_status=None,
                                eps_rel=1e-9, max_nodes=100000):
-        self._check(self._lib.obtg_speed_true_min_jac_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(bound), int(bool(is_max)),
-                                                          float(eps_rel), int(max_nodes), _vp(d_out), _vp(d_t_star), _vp(d_status),
-                                                          _vp(d_jac), _vp(d_jac_tf)), "obtg_speed_true_min_jac_dev")
+        self._true_min_dev("obtg_speed_true_min_jac_dev", (dY, d_tf), B, (float(bound), int(bool(is_max))), eps_rel, max_nodes,
+                           d_out, d_t_star, d_status, d_jac, d_jac_tf)
 
     def accel(self, Y, tf, bound):
         """The acceleration-bound rows (obtg_accel): [B][N * (2 deg + DEG_ELEV + 1)] control points of
         bound**2 - (d/2)|c''|^2, c'' = diff().diff() of the vehicle's curve on a span of tf."""
-        Y, B = self._rows(Y)
-        tf = self._tf(tf, B)
-        out = pinned_empty((B, self.len_speed))
-        self._check(self._lib.obtg_accel(self._h, _ptr(Y), _ptr(tf), B, float(bound), _ptr(out)), "obtg_accel")
-        return out
+        return self._vehicle_rows("obtg_accel", Y, tf, (float(bound),), (self.len_speed,))
 
     def accel_dev(self, dY, d_tf, B, bound, d_out):
         self._check(self._lib.obtg_accel_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(bound), _vp(d_out)), "obtg_accel_dev")
@@ -707,9 +707,7 @@ class Context(object):
         return self._true_min("obtg_accel_true_min", self.n_veh, Y, tf, (float(bound),), eps_rel, max_nodes)
 
     def accel_true_min_dev(self, dY, d_tf, B, bound, d_out, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
-        self._check(self._lib.obtg_accel_true_min_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(bound), float(eps_rel),
-                                                      int(max_nodes), _vp(d_out), _vp(d_t_star), _vp(d_status)),
-                    "obtg_accel_true_min_dev")
+        self._true_min_dev("obtg_accel_true_min_dev", (dY, d_tf), B, (float(bound),), eps_rel, max_nodes, d_out, d_t_star, d_status)
 
     def accel_true_min_jac(self, Y, tf, bound, eps_rel=1e-9, max_nodes=100000):
         """accel_true_min with its envelope Jacobian (obtg_accel_true_min_jac): dict(val, t_star, status -- the bits of
@@ -719,18 +717,13 @@ class Context(object):
 
     def accel_true_min_jac_dev(self, dY, d_tf, B, bound, d_out, d_jac, d_jac_tf=None, d_t_star=None, d_status=None,
                                eps_rel=1e-9, max_nodes=100000):
-        self._check(self._lib.obtg_accel_true_min_jac_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(bound), float(eps_rel),
-                                                          int(max_nodes), _vp(d_out), _vp(d_t_star), _vp(d_status), _vp(d_jac),
-                                                          _vp(d_jac_tf)), "obtg_accel_true_min_jac_dev")
+        self._true_min_dev("obtg_accel_true_min_jac_dev", (dY, d_tf), B, (float(bound),), eps_rel, max_nodes, d_out, d_t_star,
+                           d_status, d_jac, d_jac_tf)
 
     def jerk(self, Y, tf, bound):
         """The jerk-bound rows (obtg_jerk): [B][N * (2 deg + DEG_ELEV + 1)] control points of
         bound**2 - (d/2)|c'''|^2, c''' = diff().diff().diff() of the vehicle's curve on a span of tf."""
-        Y, B = self._rows(Y)
-        tf = self._tf(tf, B)
-        out = pinned_empty((B, self.len_speed))
-        self._check(self._lib.obtg_jerk(self._h, _ptr(Y), _ptr(tf), B, float(bound), _ptr(out)), "obtg_jerk")
-        return out
+        return self._vehicle_rows("obtg_jerk", Y, tf, (float(bound),), (self.len_speed,))
 
     def jerk_dev(self, dY, d_tf, B, bound, d_out):
         self._check(self._lib.obtg_jerk_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(bound), _vp(d_out)), "obtg_jerk_dev")
@@ -741,9 +734,7 @@ class Context(object):
         return self._true_min("obtg_jerk_true_min", self.n_veh, Y, tf, (float(bound),), eps_rel, max_nodes)
 
     def jerk_true_min_dev(self, dY, d_tf, B, bound, d_out, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
-        self._check(self._lib.obtg_jerk_true_min_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(bound), float(eps_rel),
-                                                      int(max_nodes), _vp(d_out), _vp(d_t_star), _vp(d_status)),
-                    "obtg_jerk_true_min_dev")
+        self._true_min_dev("obtg_jerk_true_min_dev", (dY, d_tf), B, (float(bound),), eps_rel, max_nodes, d_out, d_t_star, d_status)
 
     def jerk_true_min_jac(self, Y, tf, bound, eps_rel=1e-9, max_nodes=100000):
         """jerk_true_min with its envelope Jacobian (obtg_jerk_true_min_jac): dict(val, t_star, status -- the bits of
@@ -753,19 +744,14 @@ class Context(object):
 
     def jerk_true_min_jac_dev(self, dY, d_tf, B, bound, d_out, d_jac, d_jac_tf=None, d_t_star=None, d_status=None,
                                eps_rel=1e-9, max_nodes=100000):
-        self._check(self._lib.obtg_jerk_true_min_jac_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(bound), float(eps_rel),
-                                                          int(max_nodes), _vp(d_out), _vp(d_t_star), _vp(d_status), _vp(d_jac),
-                                                          _vp(d_jac_tf)), "obtg_jerk_true_min_jac_dev")
+        self._true_min_dev("obtg_jerk_true_min_jac_dev", (dY, d_tf), B, (float(bound),), eps_rel, max_nodes, d_out, d_t_star,
+                           d_status, d_jac, d_jac_tf)
 
     def ang_rate_poly(self, Y, tf, max_rate):
         """The true angular-rate rows' polynomials (obtg_ang_rate_poly; dim 2): [B][N][2][2 deg + 1] Bernstein coefficients of
         p_+ = max_rate den - num (side 0) and p_- = max_rate den + num (side 1), den = x'^2 + y'^2, num = y'' x' - x'' y' --
         in units of max_rate * speed^2, not ang_rate's maxAngRate^2 - omega^2."""
-        Y, B = self._rows(Y)
-        tf = self._tf(tf, B)
-        out = pinned_empty((B, self.n_veh, 2, 2 * self.deg + 1))
-        self._check(self._lib.obtg_ang_rate_poly(self._h, _ptr(Y), _ptr(tf), B, float(max_rate), _ptr(out)), "obtg_ang_rate_poly")
-        return out
+        return self._vehicle_rows("obtg_ang_rate_poly", Y, tf, (float(max_rate),), (self.n_veh, 2, 2 * self.deg + 1))
 
     def ang_rate_poly_dev(self, dY, d_tf, B, max_rate, d_out):
         self._check(self._lib.obtg_ang_rate_poly_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(max_rate), _vp(d_out)),
@@ -778,9 +764,8 @@ class Context(object):
         return self._true_min("obtg_ang_rate_true_min", (self.n_veh, 2), Y, tf, (float(max_rate),), eps_rel, max_nodes)
 
     def ang_rate_true_min_dev(self, dY, d_tf, B, max_rate, d_out, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
-        self._check(self._lib.obtg_ang_rate_true_min_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(max_rate), float(eps_rel),
-                                                         int(max_nodes), _vp(d_out), _vp(d_t_star), _vp(d_status)),
-                    "obtg_ang_rate_true_min_dev")
+        self._true_min_dev("obtg_ang_rate_true_min_dev", (dY, d_tf), B, (float(max_rate),), eps_rel, max_nodes, d_out, d_t_star,
+                           d_status)
 
     def ang_rate_true_min_jac(self, Y, tf, max_rate, eps_rel=1e-9, max_nodes=100000):
         """ang_rate_true_min with its envelope Jacobian (obtg_ang_rate_true_min_jac): dict(val, t_star, status -- the bits of
@@ -791,17 +776,11 @@ class Context(object):
 
     def ang_rate_true_min_jac_dev(self, dY, d_tf, B, max_rate, d_out, d_jac, d_jac_tf=None, d_t_star=None, d_status=None,
                                   eps_rel=1e-9, max_nodes=100000):
-        self._check(self._lib.obtg_ang_rate_true_min_jac_dev(self._h, _vp(dY), _vp(d_tf), int(B), float(max_rate), float(eps_rel),
-                                                             int(max_nodes), _vp(d_out), _vp(d_t_star), _vp(d_status),
-                                                             _vp(d_jac), _vp(d_jac_tf)), "obtg_ang_rate_true_min_jac_dev")
+        self._true_min_dev("obtg_ang_rate_true_min_jac_dev", (dY, d_tf), B, (float(max_rate),), eps_rel, max_nodes, d_out, d_t_star,
+                           d_status, d_jac, d_jac_tf)
 
     def ang_rate(self, Y, tf, max_rate):
-        Y, B = self._rows(Y)
-        tf = self._tf(tf, B)
-        out = pinned_empty((B, self.len_ang_rate))
-        self._check(self._lib.obtg_ang_rate(self._h, _ptr(Y), _ptr(tf), B, float(max_rate), _ptr(out)),
-                    "obtg_ang_rate")
-        return out
+        return self._vehicle_rows("obtg_ang_rate", Y, tf, (float(max_rate),), (self.len_ang_rate,))
 
     def euclidean_obj(self, Y):
         Y, B = self._rows(Y)

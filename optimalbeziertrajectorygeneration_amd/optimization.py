@@ -181,6 +181,53 @@ _MODEL_FIELDS = (
 )
 
 
+# The per-vehicle constraint-row families, each described ONCE: the closures, _fd_values, the Jacobian
+# providers, the true* accessors, the constructor's checks and _serve_key all read this table.
+#   key: the family's name in _serve / _fd_values / _jac;  bound: its key in `model`, optional: None there means "no bound";
+#   rows_attr: the attribute with its rows option ('all' / 'true_min');  rows, true_min, envelope, exact: the _capi.Context
+#   methods of the control-point rows, the true minima, the true minima with their envelope blocks and the exact Jacobian
+#   (None: not built), every one called (Y, tf[, bound], *lead);  planar: dim == 2 only;  sides: true-minimum rows per
+#   vehicle ([B][N] values, or [B][N][2] flattened to row 2 v + side);  constraints, jacobian: the public names, as the
+#   messages spell them;  noun: the rows' name in a sentence.
+_RowFamily = collections.namedtuple('_RowFamily', 'key bound optional rows_attr rows true_min envelope exact lead planar sides '
+                                                  'constraints jacobian noun')
+_ROW_FAMILIES = (
+    _RowFamily('vmax', 'maxSpeed', False, 'speedRows', 'speed', 'speed_true_min', 'speed_true_min_jac', 'speed_jac', (True,),
+               False, 1, 'maxSpeedConstraints', 'maxSpeedJacobian', 'speed'),
+    _RowFamily('vmin', 'minSpeed', False, 'speedRows', 'speed', 'speed_true_min', 'speed_true_min_jac', 'speed_jac', (False,),
+               False, 1, 'minSpeedConstraints', 'minSpeedJacobian', 'speed'),
+    _RowFamily('ang', 'maxAngRate', False, 'angRateRows', 'ang_rate', 'ang_rate_true_min', 'ang_rate_true_min_jac', 'ang_rate_jac', (),
+               True, 2, 'maxAngularRateConstraints', 'maxAngularRateJacobian', 'angular-rate'),
+    _RowFamily('amax', 'maxAccel', True, 'accelRows', 'accel', 'accel_true_min', 'accel_true_min_jac', None, (),
+               False, 1, 'maxAccelConstraints', 'maxAccelJacobian', 'acceleration'),
+    _RowFamily('jmax', 'maxJerk', True, 'jerkRows', 'jerk', 'jerk_true_min', 'jerk_true_min_jac', None, (),
+               False, 1, 'maxJerkConstraints', 'maxJerkJacobian', 'jerk'),
+)
+_FAMILY = {fam.key: fam for fam in _ROW_FAMILIES}
+_ROWS_OPTIONS = tuple(dict.fromkeys(fam.rows_attr for fam in _ROW_FAMILIES))      # speedRows, angRateRows, accelRows, jerkRows
+# What a kept finite-difference batch depends on per family, in _serve_key's order: every rows option with, right behind it,
+# the bounds that may be None; the other bounds follow maxSep.  A family enters the key by being in the table.
+_KEY_ROWS = tuple((attr, tuple(fam.bound for fam in _ROW_FAMILIES if fam.optional and fam.rows_attr == attr)) for attr in _ROWS_OPTIONS)
+_KEY_BOUNDS = tuple(fam.bound for fam in _ROW_FAMILIES if not fam.optional)
+
+# The goals with a device call ('timeopt' is x[-1]).  goal, lower case: (key in _serve / _fd_values; values [B] of the rows Y;
+# gradient blocks [B][N d][n+1] of the rows Y), both called (bezopt, ctx, Y, what) -- `what` names the caller where a search
+# that does not end raises (the arc length alone).
+_Goal = collections.namedtuple('_Goal', 'key value grad')
+_GOALS = {
+    'euclidean': _Goal('obj_euclidean', lambda bo, c, Y, what: c.euclidean_obj(Y), lambda bo, c, Y, what: c.euclidean_grad(Y)),
+    'accel': _Goal('obj_accel', lambda bo, c, Y, what: c.deriv_energy_obj(Y, bo.model['tf'], 2),
+                   lambda bo, c, Y, what: c.deriv_energy_grad(Y, bo.model['tf'], 2)[0]),
+    'jerk': _Goal('obj_jerk', lambda bo, c, Y, what: c.deriv_energy_obj(Y, bo.model['tf'], 3),
+                  lambda bo, c, Y, what: c.deriv_energy_grad(Y, bo.model['tf'], 3)[0]),
+    'arclength': _Goal('obj_arclength', lambda bo, c, Y, what: bo._arc_length(c, Y, what=what)['val'],
+                       lambda bo, c, Y, what: bo._arc_length(c, Y, grad=True, what=what)['grad']),
+}
+_GOAL_OF_KEY = {goal.key: goal for goal in _GOALS.values()}
+
+_ANG_RATE_ORDER_CODE = {'fast': 0, 'elevate_first': 1, 'exact': 2}      # obtg_ctx_set_ang_rate_order
+
+
 def _md_checked(r, what='minDist'):
     """r, the dict of a search call -- unless one of its searches did not end: then the exception of the first status, in list
     order, that is not MD_OK (bezier._raise_md): what the reference would hit first in its pair loop (optimization.py:127-131)."""
@@ -332,18 +379,11 @@ class BezOptimization(object):
         # N (2n+R+1) elevated control points of maxJerk^2 - (d/2)|c'''|^2 (the curve of the reference's jerk objective,
         # optimization.py:522-539, under a bound); 'true_min': per vehicle its true minimum over the trajectory's time
         # (obtg_jerk_true_min) -- N rows whatever DEG_ELEV is, feasible iff >= 0.
-        if jerkRows not in ('all', 'true_min'):
-            raise ValueError("jerkRows must be 'all' or 'true_min', not {!r}".format(jerkRows))
-        self.jerkRows = jerkRows
-        if accelRows not in ('all', 'true_min'):
-            raise ValueError("accelRows must be 'all' or 'true_min', not {!r}".format(accelRows))
-        self.accelRows = accelRows
-        if angRateRows not in ('all', 'true_min'):
-            raise ValueError("angRateRows must be 'all' or 'true_min', not {!r}".format(angRateRows))
-        self.angRateRows = angRateRows
-        if speedRows not in ('all', 'true_min'):
-            raise ValueError("speedRows must be 'all' or 'true_min', not {!r}".format(speedRows))
-        self.speedRows = speedRows
+        given = locals()
+        for attr in reversed(_ROWS_OPTIONS):         # (the newest family's option is checked first, as it always was)
+            if given[attr] not in ('all', 'true_min'):
+                raise ValueError("{} must be 'all' or 'true_min', not {!r}".format(attr, given[attr]))
+            setattr(self, attr, given[attr])
         if separationRows not in ('all', 'min', 'active', 'true_min'):
             raise ValueError("separationRows must be 'all', 'min', 'active' or 'true_min', not {!r}".format(separationRows))
         if separationRows == 'active' and not 1 <= int(activeRows) <= 4:
@@ -371,7 +411,6 @@ class BezOptimization(object):
         self.fdBatchingStats = {'batches': 0, 'served': 0, 'direct': 0}
         self._fd_state = None
 
-        given = locals()
         # `model` keeps the reference's keys (drivers read and edit them, Examples/*.py); what each holds is decided by
         # _MODEL_FIELDS: scalars as given, per-vehicle data as arrays with a vehicle axis
         self.model = {key: (given[kw] if shape is None else shape(given[kw])) for key, kw, shape in _MODEL_FIELDS}
@@ -384,14 +423,9 @@ class BezOptimization(object):
     def _ctx(self, with_point_obs):
         """Context for the current DEG_ELEV (created on first use; the reference's counterpart
         is the lazily filled class-level matrix caches, bezier.py:48-52)."""
-        key = bool(with_point_obs)
-        c = self._ctxs.get(key)
+        c = self._ctxs.get(bool(with_point_obs))
         if c is None:
-            obs = self.pointObstacles if with_point_obs else None
-            c = _capi.Context(self.model['numVeh'], self.model['dim'], self.model['deg'], int(DEG_ELEV),
-                              point_obs=obs, device=self._device)
-            c.set_ang_rate_order({'fast': 0, 'elevate_first': 1, 'exact': 2}[self.angRateOrder])
-            self._ctxs[key] = c
+            c = self._new_ctx(bool(with_point_obs), self.model['numVeh'], self.pointObstacles if with_point_obs else None)
         if c.deg_elev != int(DEG_ELEV):
             c.set_deg_elev(int(DEG_ELEV))
         return c
@@ -399,13 +433,15 @@ class BezOptimization(object):
     def _ctx_one(self):
         """A one-vehicle context of the same degree: the per-vehicle families evaluated on a compact
         batch of single vehicles (structured Jacobians)."""
-        c = self._ctxs.get('one')
-        if c is None:
-            c = _capi.Context(1, self.model['dim'], self.model['deg'], int(DEG_ELEV), device=self._device)
-            c.set_ang_rate_order({'fast': 0, 'elevate_first': 1, 'exact': 2}[self.angRateOrder])
-            self._ctxs['one'] = c
+        c = self._ctxs.get('one') or self._new_ctx('one', 1, None)
         if c.deg_elev != int(DEG_ELEV):
             c.set_deg_elev(int(DEG_ELEV))
+        return c
+
+    def _new_ctx(self, key, n_veh, obs):
+        c = _capi.Context(n_veh, self.model['dim'], self.model['deg'], int(DEG_ELEV), point_obs=obs, device=self._device)
+        c.set_ang_rate_order(_ANG_RATE_ORDER_CODE[self.angRateOrder])
+        self._ctxs[key] = c
         return c
 
     @property
@@ -425,11 +461,8 @@ class BezOptimization(object):
     # levels (the bracket closes as 4^-depth).  1e-12 s is still above the rounding of a degree-40 de Casteljau split.
     TRUE_MIN_EPS_REL = 1e-12
 
-    def _true_min(self, ctx, Y):
-        """separationRows='true_min': [B][P] true per-pair minima; a search that ran out of budget raises (bezier._raise_md)"""
-        return self._true_min_checked(ctx, Y)['val']
-
     def _true_min_checked(self, ctx, Y):
+        """The true per-pair minima of the rows Y; a search that ran out of budget raises (bezier._raise_md)"""
         return _md_checked(ctx.temporal_sep_true_min(Y, self.model['maxSep'], eps_rel=self.TRUE_MIN_EPS_REL),
                            'temporalSeparationConstraints(true_min)')
 
@@ -441,60 +474,54 @@ class BezOptimization(object):
         r = self._true_min_checked(self._ctx(with_obs), self.reshapeVector(x)[None])
         return r['val'][0], r['t_star'][0]
 
-    def _speed_true_min(self, ctx, Y, tf, family):
-        """speedRows='true_min': [B][N] true per-vehicle minima of the rows of `family` ('vmax' / 'vmin'); a search that ran
-        out of budget raises (bezier._raise_md)"""
-        is_max = family == 'vmax'
-        r = ctx.speed_true_min(Y, tf, self.model['maxSpeed' if is_max else 'minSpeed'], is_max, eps_rel=self.TRUE_MIN_EPS_REL)
-        return _md_checked(r, ('maxSpeedConstraints' if is_max else 'minSpeedConstraints') + '(true_min)')['val']
-
-    def _ang_true_min(self, ctx, Y, tf):
-        """angRateRows='true_min': [B][2N] true minima of every vehicle's two angular-rate polynomials, row 2 v + side; a
-        search that ran out of budget raises (bezier._raise_md)"""
-        r = ctx.ang_rate_true_min(Y, tf, self.model['maxAngRate'], eps_rel=self.TRUE_MIN_EPS_REL)
-        v = _md_checked(r, 'maxAngularRateConstraints(true_min)')['val']
-        return v.reshape(v.shape[0], -1)
-
-    def _max_accel(self, what):
-        bound = self.model['maxAccel']
+    # ------------------------------------------------------------------ the per-vehicle row families (_ROW_FAMILIES)
+    def _bound(self, fam, what):
+        """The family's bound from `model`; `what` (a public name) cannot be answered without one."""
+        bound = self.model[fam.bound]
         if bound is None:
-            raise ValueError("{} needs a bound: maxAccel is None".format(what))
+            raise ValueError("{} needs a bound: {} is None".format(what, fam.bound))
         return bound
 
-    def _accel_true_min(self, ctx, Y, tf):
-        """accelRows='true_min': [B][N] true per-vehicle minima of the acceleration rows; a search that ran out of budget
-        raises (bezier._raise_md)"""
-        r = ctx.accel_true_min(Y, tf, self._max_accel('maxAccelConstraints'), eps_rel=self.TRUE_MIN_EPS_REL)
-        return _md_checked(r, 'maxAccelConstraints(true_min)')['val']
+    def _vehicle_true_min(self, fam, ctx, Y, tf, bound, what, envelope=False):
+        """The family's true-minimum call on the rows Y at TRUE_MIN_EPS_REL (envelope: with the envelope blocks): its dict;
+        a search that ran out of budget raises in the name of `what` (bezier._raise_md)"""
+        call = getattr(ctx, fam.envelope if envelope else fam.true_min)
+        return _md_checked(call(Y, tf, bound, *fam.lead, eps_rel=self.TRUE_MIN_EPS_REL), what)
+
+    def _vehicle_rows(self, fam, ctx, Y, tf):
+        """[B][rows]: the family's rows under its rows option -- 'all': the control points of every vehicle; 'true_min': the
+        true minima, [B][N * fam.sides] -- of the rows Y on the context ctx."""
+        bound = self.model[fam.bound]
+        if bound is None:
+            self._bound(fam, fam.constraints)        # raises
+        if getattr(self, fam.rows_attr) == 'true_min':
+            v = self._vehicle_true_min(fam, ctx, Y, tf, bound, fam.constraints + '(true_min)')['val']
+            return v.reshape(v.shape[0], -1)
+        return getattr(ctx, fam.rows)(Y, tf, bound, *fam.lead)
+
+    def _vehicle_closure(self, fam):
+        def direct(x):
+            self._bound(fam, fam.constraints)        # a missing bound answers before anything is computed
+            y = self.reshapeVector(x)
+            return self._vehicle_rows(fam, self._ctx(False), y, self._tf_of(x))[0]
+        return lambda x: self._serve(fam.key, x, direct)
+
+    def _true_rows_at(self, fam, x, bound, what):
+        """The true-minimum dict of the family at the one point x, under `bound` -- whatever the family's rows option is."""
+        return self._vehicle_true_min(fam, self._ctx(False), self.reshapeVector(x)[None], self._tf_of(x), bound, what)
 
     def trueAccelMax(self, x):
         """(max_val[N], t_max[N]): per vehicle the true maximum over the trajectory of (d/2)|acceleration|^2 -- normSquare's
         factor kept: the scale of the acceleration rows, without their bound -- and the parameter in [0, 1] where it is
         reached (obtg_accel_true_min with bound 0), whatever `accelRows` is."""
-        x = np.asarray(x, dtype=float)
-        r = self._ctx(False).accel_true_min(self.reshapeVector(x)[None], self._tf_of(x), 0.0, eps_rel=self.TRUE_MIN_EPS_REL)
-        _md_checked(r, 'trueAccelMax')
+        r = self._true_rows_at(_FAMILY['amax'], np.asarray(x, dtype=float), 0.0, 'trueAccelMax')
         return -r['val'][0], r['t_star'][0]
-
-    def _max_jerk(self, what):
-        bound = self.model['maxJerk']
-        if bound is None:
-            raise ValueError("{} needs a bound: maxJerk is None".format(what))
-        return bound
-
-    def _jerk_true_min(self, ctx, Y, tf):
-        """jerkRows='true_min': [B][N] true per-vehicle minima of the jerk rows; a search that ran out of budget
-        raises (bezier._raise_md)"""
-        r = ctx.jerk_true_min(Y, tf, self._max_jerk('maxJerkConstraints'), eps_rel=self.TRUE_MIN_EPS_REL)
-        return _md_checked(r, 'maxJerkConstraints(true_min)')['val']
 
     def trueJerkMax(self, x):
         """(max_val[N], t_max[N]): per vehicle the true maximum over the trajectory of (d/2)|jerk|^2 -- normSquare's
         factor kept: the scale of the jerk rows, without their bound -- and the parameter in [0, 1] where it is
         reached (obtg_jerk_true_min with bound 0), whatever `jerkRows` is."""
-        x = np.asarray(x, dtype=float)
-        r = self._ctx(False).jerk_true_min(self.reshapeVector(x)[None], self._tf_of(x), 0.0, eps_rel=self.TRUE_MIN_EPS_REL)
-        _md_checked(r, 'trueJerkMax')
+        r = self._true_rows_at(_FAMILY['jmax'], np.asarray(x, dtype=float), 0.0, 'trueJerkMax')
         return -r['val'][0], r['t_star'][0]
 
     def trueAngularRateRows(self, x):
@@ -502,12 +529,8 @@ class BezOptimization(object):
         and maxAngRate den + num (side 1), and the parameters in [0, 1] where they are reached (obtg_ang_rate_true_min),
         whatever `angRateRows` is: |angular rate| <= maxAngRate on the whole trajectory iff both are >= 0."""
         x = np.asarray(x, dtype=float)
-        if self.model['dim'] != 2:
-            raise ValueError('The input curve must be two dimensional,\n'
-                             'instead it is {} dimensional'.format(self.model['dim']))
-        r = self._ctx(False).ang_rate_true_min(self.reshapeVector(x)[None], self._tf_of(x), self.model['maxAngRate'],
-                                               eps_rel=self.TRUE_MIN_EPS_REL)
-        _md_checked(r, 'trueAngularRateRows')
+        self._check_planar()
+        r = self._true_rows_at(_FAMILY['ang'], x, self.model['maxAngRate'], 'trueAngularRateRows')
         return r['val'][0], r['t_star'][0]
 
     def trueSpeedRange(self, x):
@@ -515,12 +538,13 @@ class BezOptimization(object):
         -- normSquare's factor kept: the scale of the speed rows, without their bound -- and the parameters in [0, 1] where
         they are reached (obtg_speed_true_min with bound 0), whatever `speedRows` is."""
         x = np.asarray(x, dtype=float)
-        ctx, Y, tf = self._ctx(False), self.reshapeVector(x)[None], self._tf_of(x)
-        lo = ctx.speed_true_min(Y, tf, 0.0, False, eps_rel=self.TRUE_MIN_EPS_REL)
-        hi = ctx.speed_true_min(Y, tf, 0.0, True, eps_rel=self.TRUE_MIN_EPS_REL)
-        for r in (lo, hi):
-            _md_checked(r, 'trueSpeedRange')
+        lo, hi = (self._true_rows_at(_FAMILY[key], x, 0.0, 'trueSpeedRange') for key in ('vmin', 'vmax'))
         return lo['val'][0], lo['t_star'][0], -hi['val'][0], hi['t_star'][0]
+
+    def _check_planar(self):
+        if self.model['dim'] != 2:
+            raise ValueError('The input curve must be two dimensional,\n'
+                             'instead it is {} dimensional'.format(self.model['dim']))                # optimization.py:590-593
 
     ARC_LENGTH_EPS_REL = 1e-12
 
@@ -560,20 +584,25 @@ class BezOptimization(object):
                    ).format(minGoal, objectivesDict.keys())
             raise ValueError(err)
 
+    def _objective(self, goal, x):
+        """The value of the goal (a key of _GOALS) at x, served like a constraint closure's rows."""
+        g = _GOALS[goal]
+        return float(self._serve(g.key, x, lambda x_: g.value(self, self._ctx(False), self.reshapeVector(x_)[None], 'arcLengthObjective')[:1])[0])
+
     def euclideanObjective(self, x):
-        return float(self._serve('obj_euclidean', x, lambda x_: self._ctx(False).euclidean_obj(self.reshapeVector(x_))[:1])[0])
+        return self._objective('euclidean', x)
 
     def accelObjective(self, x):
-        return float(self._serve('obj_accel', x, lambda x_: self._ctx(False).deriv_energy_obj(self.reshapeVector(x_), self.model['tf'], 2)[:1])[0])
+        return self._objective('accel', x)
 
     def jerkObjective(self, x):
-        return float(self._serve('obj_jerk', x, lambda x_: self._ctx(False).deriv_energy_obj(self.reshapeVector(x_), self.model['tf'], 3)[:1])[0])
+        return self._objective('jerk', x)
 
     def arcLengthObjective(self, x):
         """minGoal='arcLength' (not in the reference): the summed TRUE lengths of the vehicles' curves (obtg_arc_length_obj at
         ARC_LENGTH_EPS_REL) -- what 'euclidean', the control polygon's length, bounds from above.  Forward differences of an
         adaptive value at SciPy's step divide the rule's tolerance by 1.5e-8: pass objectiveGradient(method='exact') as jac."""
-        return float(self._serve('obj_arclength', x, lambda x_: self._arc_length(self._ctx(False), self.reshapeVector(x_)[None])['val'][:1])[0])
+        return self._objective('arclength', x)
 
     def objectiveGradient(self, x, method='fd'):
         """Gradient of `objectiveFunction` the way SciPy would difference it (2-point, abs_step = sqrt(eps)), but from ONE
@@ -589,30 +618,16 @@ class BezOptimization(object):
             g = np.zeros(x.size)
             g[-1] = 1.0
             return g
-        if method == 'exact':
-            Y0 = self.reshapeVectors(x[None])
-            c = self._ctx(False)
-            if goal == 'euclidean':
-                G = c.euclidean_grad(Y0)[0]
-            elif goal in ('accel', 'jerk'):
-                G = c.deriv_energy_grad(Y0, self.model['tf'], 2 if goal == 'accel' else 3)[0][0]
-            elif goal == 'arclength':
-                G = self._arc_length(c, Y0, grad=True, what='objectiveGradient')['grad'][0]
-            else:
-                self.objectiveFunction          # raises the reference's ValueError for an unknown goal
-            first = self._rv_parts()[1]
-            return G[:, first:first + self._numCols].ravel()
-        X, dx = self._fd_rows(x)
+        X, dx = (x[None], None) if method == 'exact' else self._fd_rows(x)
         Y = self.reshapeVectors(X)
         c = self._ctx(False)
-        if goal == 'euclidean':
-            F = c.euclidean_obj(Y)
-        elif goal in ('accel', 'jerk'):
-            F = c.deriv_energy_obj(Y, self.model['tf'], 2 if goal == 'accel' else 3)
-        elif goal == 'arclength':
-            F = self._arc_length(c, Y, what='objectiveGradient')['val']
-        else:
+        if goal not in _GOALS:
             self.objectiveFunction          # raises the reference's ValueError for an unknown goal
+        if method == 'exact':
+            G = _GOALS[goal].grad(self, c, Y, 'objectiveGradient')[0]
+            first = self._rv_parts()[1]
+            return G[:, first:first + self._numCols].ravel()
+        F = _GOALS[goal].value(self, c, Y, 'objectiveGradient')
         return (F[1:] - F[0]) / dx
 
     # ------------------------------------------------------------------ constraints
@@ -629,62 +644,44 @@ class BezOptimization(object):
         def direct(x):
             with_obs = self.pointObstacles is not None
             y = self.reshapeVector(x)
-            if self.separationRows == 'min':     # per-pair minimum, reduced on the device (obtg_temporal_sep_min)
-                return self._ctx(with_obs).temporal_sep_min(y, self.model['maxSep'])[0]
-            if self.separationRows == 'active':  # per pair its k smallest control points, selected on the device
-                return self._ctx(with_obs).temporal_sep_active(y, self.model['maxSep'], self._active_k())[0]
-            if self.separationRows == 'true_min':
-                return self._true_min(self._ctx(with_obs), y)[0]
-            return self._ctx(with_obs).temporal_sep(y, self.model['maxSep'])[0]
+            return self._tsep_rows(self._ctx(with_obs), y)[0]
         return wrapper
+
+    def _tsep_rows(self, ctx, Y):
+        """[B][rows]: the separation rows of the rows Y under `separationRows`, on the context ctx."""
+        rows = self.separationRows
+        if rows == 'min':                   # per-pair minimum, reduced on the device (obtg_temporal_sep_min)
+            return ctx.temporal_sep_min(Y, self.model['maxSep'])
+        if rows == 'active':                 # per pair its k smallest control points, selected on the device
+            return ctx.temporal_sep_active(Y, self.model['maxSep'], self._active_k())
+        if rows == 'true_min':
+            return self._true_min_checked(ctx, Y)['val']
+        return ctx.temporal_sep(Y, self.model['maxSep'])
 
     @property
     def minSpeedConstraints(self):
-        def direct(x):
-            y = self.reshapeVector(x)
-            if self.speedRows == 'true_min':
-                return self._speed_true_min(self._ctx(False), y, self._tf_of(x), 'vmin')[0]
-            return self._ctx(False).speed(y, self._tf_of(x), self.model['minSpeed'], False)[0]
-        return lambda x: self._serve('vmin', x, direct)
+        return self._vehicle_closure(_FAMILY['vmin'])
 
     @property
     def maxSpeedConstraints(self):
-        def direct(x):
-            y = self.reshapeVector(x)
-            if self.speedRows == 'true_min':
-                return self._speed_true_min(self._ctx(False), y, self._tf_of(x), 'vmax')[0]
-            return self._ctx(False).speed(y, self._tf_of(x), self.model['maxSpeed'], True)[0]
-        return lambda x: self._serve('vmax', x, direct)
+        return self._vehicle_closure(_FAMILY['vmax'])
 
     @property
     def maxAccelConstraints(self):
         """maxAccel^2 - (d/2)|acceleration|^2 >= 0: N (2n+R+1) control points (accelRows='all') or N true minima ('true_min')."""
-        def direct(x):
-            bound = self._max_accel('maxAccelConstraints')
-            y = self.reshapeVector(x)
-            if self.accelRows == 'true_min':
-                return self._accel_true_min(self._ctx(False), y, self._tf_of(x))[0]
-            return self._ctx(False).accel(y, self._tf_of(x), bound)[0]
-        return lambda x: self._serve('amax', x, direct)
+        return self._vehicle_closure(_FAMILY['amax'])
 
     @property
     def maxJerkConstraints(self):
         """maxJerk^2 - (d/2)|jerk|^2 >= 0: N (2n+R+1) control points (jerkRows='all') or N true minima ('true_min')."""
-        def direct(x):
-            bound = self._max_jerk('maxJerkConstraints')
-            y = self.reshapeVector(x)
-            if self.jerkRows == 'true_min':
-                return self._jerk_true_min(self._ctx(False), y, self._tf_of(x))[0]
-            return self._ctx(False).jerk(y, self._tf_of(x), bound)[0]
-        return lambda x: self._serve('jmax', x, direct)
+        return self._vehicle_closure(_FAMILY['jmax'])
 
     @property
     def maxAngularRateConstraints(self):
+        closure = self._vehicle_closure(_FAMILY['ang'])
+
         def wrapper(x):
-            if self.model['dim'] != 2:
-                msg = ('The input curve must be two dimensional,\n'
-                       'instead it is {} dimensional'.format(self.model['dim']))
-                raise ValueError(msg)            # optimization.py:590-593
+            self._check_planar()
             y = self.reshapeVector(x)
             tf = self._tf_of(x)
             if tf <= 0:
@@ -692,9 +689,7 @@ class BezOptimization(object):
                 # arithmetic returns None for an empty span (bezier.py:340-343, 365-368) and optimization.py:603-604
                 # multiplies it -- the driver dies with this TypeError.  Same exception, same text, no device call.
                 raise TypeError("unsupported operand type(s) for *: 'NoneType' and 'NoneType'")
-            if self.angRateRows == 'true_min':
-                return self._serve('ang', x, lambda x_: self._ang_true_min(self._ctx(False), self.reshapeVector(x_)[None], self._tf_of(x_))[0])
-            return self._serve('ang', x, lambda x_: self._ctx(False).ang_rate(self.reshapeVector(x_), self._tf_of(x_), self.model['maxAngRate'])[0])
+            return closure(x)
         return wrapper
 
     def spatialSeparationConstraints(self, x, robust=False):
@@ -851,8 +846,11 @@ class BezOptimization(object):
         milliseconds); _serve asks for the key only when at most one variable moved."""
         if refresh or getattr(self, '_rv_cache', None) is None:
             self._rv_parts()
-        return (int(DEG_ELEV), self.separationRows, self.speedRows, self.angRateRows, self.accelRows, self.model['maxAccel'], self.jerkRows, self.model['maxJerk'], self.activeRows, self._rv_cache[0], self.model['maxSep'], self.model['maxSpeed'],
-                self.model['minSpeed'], self.model['maxAngRate'], None if self._timeopt() else self.model['tf'],
+        m = self.model
+        rows = [v for attr, optional in _KEY_ROWS for v in (getattr(self, attr), *[m[b] for b in optional])]
+        bounds = [m[b] for b in _KEY_BOUNDS]
+        return (int(DEG_ELEV), self.separationRows, *rows, self.activeRows, self._rv_cache[0], self.model['maxSep'], *bounds,
+                None if self._timeopt() else self.model['tf'],
                 None if self.pointObstacles is None else np.asarray(self.pointObstacles, dtype=float).tobytes(),
                 None if self.shapeObstacles is None else tuple(np.asarray(c.cpts, dtype=float).tobytes() for c in self.shapeObstacles))
 
@@ -865,43 +863,14 @@ class BezOptimization(object):
         batched device call."""
         X, dx = self._fd_rows(x)
         Y = self.reshapeVectors(X)
-        if family.startswith('obj_'):      # the objectives (one value per row; a column here)
-            c = self._ctx(False)
-            if family == 'obj_arclength':
-                F = self._arc_length(c, Y)['val']
-            else:
-                F = c.euclidean_obj(Y) if family == 'obj_euclidean' else c.deriv_energy_obj(Y, self.model['tf'], 2 if family == 'obj_accel' else 3)
-            return np.asarray(F, dtype=float).reshape(-1, 1), dx
-        if family == 'tsep':
-            with_obs = self.pointObstacles is not None
-            if self.separationRows == 'min':
-                F = self._ctx(with_obs).temporal_sep_min(Y, self.model['maxSep'])
-            elif self.separationRows == 'active':
-                F = self._ctx(with_obs).temporal_sep_active(Y, self.model['maxSep'], self._active_k())
-            elif self.separationRows == 'true_min':
-                F = self._true_min(self._ctx(with_obs), Y)
-            else:
-                F = self._ctx(with_obs).temporal_sep(Y, self.model['maxSep'])
-        else:
+        fam = _FAMILY.get(family)
+        if fam is not None:
             tf = X[:, -1] if self._timeopt() else np.full(X.shape[0], self.model['tf'])
-            c = self._ctx(False)
-            if family in ('vmax', 'vmin') and self.speedRows == 'true_min':
-                F = self._speed_true_min(c, Y, tf, family)
-            elif family == 'vmax':
-                F = c.speed(Y, tf, self.model['maxSpeed'], True)
-            elif family == 'vmin':
-                F = c.speed(Y, tf, self.model['minSpeed'], False)
-            elif family == 'amax':
-                F = (self._accel_true_min(c, Y, tf) if self.accelRows == 'true_min'
-                     else c.accel(Y, tf, self._max_accel('maxAccelConstraints')))
-            elif family == 'jmax':
-                F = (self._jerk_true_min(c, Y, tf) if self.jerkRows == 'true_min'
-                     else c.jerk(Y, tf, self._max_jerk('maxJerkConstraints')))
-            elif self.angRateRows == 'true_min':
-                F = self._ang_true_min(c, Y, tf)
-            else:
-                F = c.ang_rate(Y, tf, self.model['maxAngRate'])
-        return F, dx
+            return self._vehicle_rows(fam, self._ctx(False), Y, tf), dx
+        if family == 'tsep':
+            return self._tsep_rows(self._ctx(self.pointObstacles is not None), Y), dx
+        F = _GOAL_OF_KEY[family].value(self, self._ctx(False), Y, 'arcLengthObjective')      # (one value per row; a column here)
+        return np.asarray(F, dtype=float).reshape(-1, 1), dx
 
     def temporalSeparationJacobian(self, x, structured=True, method='fd'):
         """d(temporalSeparationConstraints)/dx by SciPy-style forward differences.
@@ -968,7 +937,7 @@ class BezOptimization(object):
         J[rows.reshape(n_pts, -1), k[:, None]] = (blk - F0[rows]).reshape(n_pts, -1) / dx[:n_pts, None]
         if x.size > n_pts:      # tf: moves columns 1 / -2 of every vehicle when speeds are prescribed
             Yt = self.reshapeVectors(X[n_pts + 1:])
-            Ft = ctx.temporal_sep_min(Yt, self.model['maxSep']) if reduced else ctx.temporal_sep(Yt, self.model['maxSep'])
+            Ft = self._tsep_rows(ctx, Yt)                   # ('all' or 'min' here)
             J[:, n_pts:] = ((Ft - F0[None]) / dx[n_pts:, None]).T
         return J
 
@@ -977,67 +946,19 @@ class BezOptimization(object):
         point of vehicle v only moves v's own rows.  structured=True evaluates, per variable, that one
         vehicle (a compact batch on a one-vehicle context: n_x vehicle evaluations instead of
         n_x N); entries equal the brute-force batch's bit for bit.  A trailing tf moves everything and
-        takes the batch path.  method='exact': the analytic blocks (obtg_speed_jac / obtg_ang_rate_jac, one launch at x).
+        takes the batch path.  method='exact': the analytic blocks (obtg_speed_jac / obtg_ang_rate_jac, one launch at x; not
+        built for the acceleration and jerk rows).
 
-        speedRows='true_min' (the speed families): method='envelope' is the envelope derivative of the true per-vehicle
-        minima -- each row's polynomial differentiated at the minimiser the search returns, with its d/dtf
-        (obtg_speed_true_min_jac, one call at x with TRUE_MIN_EPS_REL); method='fd' differences the search
-        itself (one batched call); method='exact' is not built for these rows.
-
-        angRateRows='true_min' (the angular rate): the same three answers -- method='envelope' is dense [2N][n_x] from
-        obtg_ang_rate_true_min_jac, 'fd' differences the search, 'exact' raises.
-
-        The acceleration rows ('amax'): 'fd' as above; method='envelope' needs accelRows='true_min' and is dense [N][n_x] from
-        obtg_accel_true_min_jac; method='exact' is not built for either form of the rows.  The jerk rows
-        ('jmax', jerkRows, obtg_jerk_true_min_jac): the same."""
-        true_min = ((family in ('vmax', 'vmin') and self.speedRows == 'true_min') or (family == 'ang' and self.angRateRows == 'true_min')
-                    or (family == 'amax' and self.accelRows == 'true_min') or (family == 'jmax' and self.jerkRows == 'true_min'))
-        if family == 'jmax':
-            if method == 'envelope':
-                if not true_min:
-                    raise ValueError("maxJerkJacobian(method='envelope') needs jerkRows='true_min', not {!r}".format(self.jerkRows))
-                return self._jerk_jac_envelope(x)
-            _check_method(method)
-            if method == 'exact':
-                raise ValueError("maxJerkJacobian(method='exact') is not built for the jerk rows: use method='fd'"
-                                 " or, with jerkRows='true_min', method='envelope'")
-            self._max_jerk('maxJerkJacobian')
-        if family == 'amax':
-            if method == 'envelope':
-                if not true_min:
-                    raise ValueError("maxAccelJacobian(method='envelope') needs accelRows='true_min', not {!r}".format(self.accelRows))
-                return self._accel_jac_envelope(x)
-            _check_method(method)
-            if method == 'exact':
-                raise ValueError("maxAccelJacobian(method='exact') is not built for the acceleration rows: use method='fd'"
-                                 " or, with accelRows='true_min', method='envelope'")
-            self._max_accel('maxAccelJacobian')
-        if family == 'ang' and (method == 'envelope' or true_min):
-            if self.model['dim'] != 2:
-                raise ValueError('The input curve must be two dimensional,\n'
-                                 'instead it is {} dimensional'.format(self.model['dim']))
-            if method == 'envelope':
-                if not true_min:
-                    raise ValueError("maxAngularRateJacobian(method='envelope') needs angRateRows='true_min', not {!r}"
-                                     .format(self.angRateRows))
-                return self._ang_jac_envelope(x)
-            _check_method(method)
-            if method == 'exact':
-                raise ValueError("maxAngularRateJacobian(method='exact') is not available with angRateRows='true_min' (the "
-                                 "envelope derivative is not built under that name): use method='envelope' or method='fd'")
-            return self._jac(x, family)
-        if method == 'envelope' and family in ('vmax', 'vmin'):
-            if not true_min:
-                raise ValueError("{}SpeedJacobian(method='envelope') needs speedRows='true_min', not {!r}"
-                                 .format('max' if family == 'vmax' else 'min', self.speedRows))
-            return self._speed_jac_envelope(x, family)
-        _check_method(method)
+        With the family's rows option 'true_min': method='envelope' is the envelope derivative of the true per-vehicle minima
+        -- each row's polynomial differentiated at the minimiser the search returns, with its d/dtf (obtg_<family>_true_min_jac,
+        one call at x with TRUE_MIN_EPS_REL; dense [N * sides][n_x]); method='fd' differences the search
+        itself (one batched call); method='exact' is not built for these rows.  _check_jac_method says which of them raise."""
+        fam = _FAMILY[family]
+        true_min = self._check_jac_method(fam, method)
+        if method == 'envelope':
+            return self._jac_vehicle_envelope(x, fam)
         if method == 'exact':
-            if true_min:
-                raise ValueError("{}SpeedJacobian(method='exact') is not available with speedRows='true_min' (the envelope "
-                                 "derivative is not built under that name): use method='envelope' or method='fd'"
-                                 .format('max' if family == 'vmax' else 'min'))
-            return self._jac_vehicle_exact(x, family)
+            return self._jac_vehicle_exact(x, fam)
         if not structured or true_min:
             return self._jac(x, family)
         x = np.asarray(x, dtype=float)
@@ -1048,16 +969,8 @@ class BezOptimization(object):
         Y0 = self.reshapeVectors(x[None])[0]
         tf0 = float(self._tf_of(x))
 
-        def evaluate(ctx, Y, tf):
-            if family == 'vmax':
-                return ctx.speed(Y, tf, self.model['maxSpeed'], True)
-            if family == 'vmin':
-                return ctx.speed(Y, tf, self.model['minSpeed'], False)
-            if family == 'amax':
-                return ctx.accel(Y, tf, self.model['maxAccel'])
-            if family == 'jmax':
-                return ctx.jerk(Y, tf, self.model['maxJerk'])
-            return ctx.ang_rate(Y, tf, self.model['maxAngRate'])
+        def evaluate(ctx, Y, tf):                                 # (the control-point rows here)
+            return self._vehicle_rows(fam, ctx, Y, tf)
 
         F0 = evaluate(self._ctx(False), Y0[None], np.array([tf0]))[0]
         per = F0.size // numVeh
@@ -1159,56 +1072,50 @@ class BezOptimization(object):
         pa, pb = np.triu_indices(n_obj, 1)
         return self._scatter_exact(r['jac'][0][:, None], (pa, pb), (1.0, -1.0))      # blocks of one row each
 
-    def _speed_jac_envelope(self, x, family):
-        x = np.asarray(x, dtype=float)
-        is_max = family == 'vmax'
-        r = self._ctx(False).speed_true_min_jac(self.reshapeVectors(x[None]), float(self._tf_of(x)),
-                                                self.model['maxSpeed' if is_max else 'minSpeed'], is_max,
-                                                eps_rel=self.TRUE_MIN_EPS_REL)
-        _md_checked(r, ('maxSpeedJacobian' if is_max else 'minSpeedJacobian') + '(envelope)')
-        N = self.model['numVeh']
-        return self._scatter_exact(r['jac'][0][:, None], (np.arange(N),), (1.0,), r['jac_tf'][0][:, None])   # blocks of one row each
+    def _check_jac_method(self, fam, method):
+        """Whether the family's Jacobian provider can answer `method` under the family's rows option -- the same order of
+        checks for every family; what cannot be answered raises.  Returns whether the rows are the true minima."""
+        rows = getattr(self, fam.rows_attr)
+        true_min = rows == 'true_min'
+        if fam.planar and (method == 'envelope' or true_min):      # (control-point rows of another dimension: the device call answers)
+            self._check_planar()
+        if method == 'envelope':
+            if not true_min:
+                raise ValueError("{}(method='envelope') needs {}='true_min', not {!r}".format(fam.jacobian, fam.rows_attr, rows))
+            return true_min
+        _check_method(method)
+        if method == 'exact':
+            if fam.exact is None:
+                raise ValueError("{}(method='exact') is not built for the {} rows: use method='fd' or, with {}='true_min', "
+                                 "method='envelope'".format(fam.jacobian, fam.noun, fam.rows_attr))
+            if true_min:
+                raise ValueError("{}(method='exact') is not available with {}='true_min' (the envelope derivative is not built "
+                                 "under that name): use method='envelope' or method='fd'".format(fam.jacobian, fam.rows_attr))
+        elif fam.optional:
+            self._bound(fam, fam.jacobian)
+        return true_min
 
-    def _accel_jac_envelope(self, x):
+    def _jac_vehicle_envelope(self, x, fam):
         x = np.asarray(x, dtype=float)
-        r = self._ctx(False).accel_true_min_jac(self.reshapeVectors(x[None]), float(self._tf_of(x)),
-                                                self._max_accel('maxAccelJacobian'), eps_rel=self.TRUE_MIN_EPS_REL)
-        _md_checked(r, 'maxAccelJacobian(envelope)')
+        ctx = self._ctx(False)
+        Y0, tf = self.reshapeVectors(x[None]), float(self._tf_of(x))
+        r = self._vehicle_true_min(fam, ctx, Y0, tf, self._bound(fam, fam.jacobian), fam.jacobian + '(envelope)', envelope=True)
         N = self.model['numVeh']
-        return self._scatter_exact(r['jac'][0][:, None], (np.arange(N),), (1.0,), r['jac_tf'][0][:, None])   # blocks of one row each
-
-    def _jerk_jac_envelope(self, x):
-        x = np.asarray(x, dtype=float)
-        r = self._ctx(False).jerk_true_min_jac(self.reshapeVectors(x[None]), float(self._tf_of(x)),
-                                                self._max_jerk('maxJerkJacobian'), eps_rel=self.TRUE_MIN_EPS_REL)
-        _md_checked(r, 'maxJerkJacobian(envelope)')
-        N = self.model['numVeh']
-        return self._scatter_exact(r['jac'][0][:, None], (np.arange(N),), (1.0,), r['jac_tf'][0][:, None])   # blocks of one row each
-
-    def _ang_jac_envelope(self, x):
-        x = np.asarray(x, dtype=float)
-        r = self._ctx(False).ang_rate_true_min_jac(self.reshapeVectors(x[None]), float(self._tf_of(x)), self.model['maxAngRate'],
-                                                   eps_rel=self.TRUE_MIN_EPS_REL)
-        _md_checked(r, 'maxAngularRateJacobian(envelope)')
-        N = self.model['numVeh']
-        return self._scatter_exact(r['jac'][0], (np.arange(N),), (1.0,), r['jac_tf'][0])      # blocks of two rows each: the sides
+        blk = r['jac'][0].reshape((N, fam.sides) + r['jac'].shape[-2:])            # blocks of fam.sides rows each
+        return self._scatter_exact(blk, (np.arange(N),), (1.0,), r['jac_tf'][0].reshape(N, fam.sides))
 
     def trueMinSeparationJacobian(self, x):
         """temporalSeparationJacobian(x, method='envelope')"""
         return self.temporalSeparationJacobian(x, method='envelope')
 
-    def _jac_vehicle_exact(self, x, family):
+    def _jac_vehicle_exact(self, x, fam):
         x = np.asarray(x, dtype=float)
         Y0 = self.reshapeVectors(x[None])
         tf = float(self._tf_of(x))
         c = self._ctx(False)
-        if family == 'ang':
-            if self.model['dim'] != 2:
-                raise ValueError('The input curve must be two dimensional,\n'
-                                 'instead it is {} dimensional'.format(self.model['dim']))
-            blk, dtf = c.ang_rate_jac(Y0, tf)
-        else:
-            blk, dtf = c.speed_jac(Y0, tf, family == 'vmax')
+        if fam.planar:
+            self._check_planar()
+        blk, dtf = getattr(c, fam.exact)(Y0, tf, *fam.lead)
         N = self.model['numVeh']
         return self._scatter_exact(blk[0], (np.arange(N),), (1.0,), dtf[0])
 

@@ -104,7 +104,10 @@ const char* obtg_strerror(int code);
  *      Jacobian obtg_jerk_true_min_jac[_dev] (timed under OBTG_K_SPEED).
  *      Later, still 7: new: the true arc length obtg_bern_arc_length[_dev] and the objective obtg_arc_length_obj[_dev], timed
  *      under a kernel-stats id of their own, OBTG_K_ARC_LENGTH = 9.  OBTG_K_COUNT stays 9, the ids of revision 7 as callers
- *      have sized their arrays by it; OBTG_K_END = 10 is the end of the ids obtg_kernel_stats answers for. */
+ *      have sized their arrays by it; OBTG_K_END = 10 is the end of the ids obtg_kernel_stats answers for.
+ *      Later, still 7: new: the curvature-bound rows obtg_curvature_true_min[_dev], their envelope Jacobian
+ *      obtg_curvature_true_min_jac[_dev], their polynomials obtg_curvature_poly[_dev] and the curvature range of free curves
+ *      obtg_bern_curvature[_dev] (timed under OBTG_K_ANG_RATE; no kernel id added). */
 #define OBTG_ABI_VERSION 7
 int obtg_abi_version(void);
 
@@ -703,6 +706,78 @@ int obtg_ang_rate_true_min_jac(obtg_ctx*, const double* Y, const double* tf /*[B
                                double* jac /*[B][N][2][2][n+1]*/, double* jac_tf /*[B][N][2], nullable*/);
 int obtg_ang_rate_true_min_jac_dev(obtg_ctx*, const double* dY, const double* d_tf, int B, double max_rate, double eps_rel,
                                    int max_nodes, double* d_out, double* d_t_star, int* d_status, double* d_jac, double* d_jac_tf);
+/* The curvature bound (dim 2): |kappa| <= max_curv on the whole path, a minimum turning radius of 1 / max_curv.  With x', x''
+ * (each the derivative followed by elev(1), degree n) formed on T = 1 -- curvature does not depend on the time span, so no
+ * entry point takes tf -- den = x'^2 + y'^2 and num = y'' x' - x'' y' are the 2n+1 Bernstein coefficients den_k, num_k that
+ * obtg_ang_rate_poly's rows are made of at tf = 1 (csrc/bern_device.h curvature_row_coeff: ang_row_coeff's fma sequence and
+ * weights), and signed curvature is kappa(t) = num(t) / (den(t) sqrt(den(t))), left turns positive.  Two rows per vehicle,
+ * sigma = +1 (side 0, left turns) and sigma = -1 (side 1, right turns):
+ *     m_sigma = max over t in [0, 1] of max(0, sigma kappa(t)),      row_sigma = max_curv - m_sigma,
+ * a vehicle respects the bound iff both rows are >= 0.  The clamp at 0 is deliberate: a vehicle that never turns right has
+ * side 1 equal to max_curv exactly.  The family is meant for trajectories that do not stop.
+ * obtg_curvature_poly: out[B][N][2][2n+1], num_k then den_k.
+ * obtg_curvature_true_min: out[B][N][2] = row_sigma, t_star[B][N][2], status[B][N][2].  kappa is not a polynomial, so the search
+ *     is not obtg_bern_extrema's: a depth-first bisection at 1/2 over num and den at once (each de Casteljau level the same
+ *     pair of averages 0.5 a + 0.5 b on both), one wave per row.
+ *     Evaluation at a point: with num and den the end coefficients of a sub-curve, sigma kappa = (sigma num) / (den sqrt(den)) in
+ *     binary64; a point with den <= 0, or whose quotient is not finite, offers no value.
+ *     Incumbent U: starts at max(0, sigma kappa(0), sigma kappa(1)); every bisection midpoint updates it.
+ *     Upper bound of a sub-curve with coefficients (sigma num_k, den_k): d0 = 0.5 (min den_k + max den_k),
+ *     g_k = fma(1.5 sqrt(d0), den_k, -0.5 (d0 sqrt(d0))) -- the tangent of the convex den^(3/2) at d0, so
+ *     den(t)^(3/2) >= sum g_k B_k(t) --; lambda g_k - num_k >= 0 for EVERY k gives sigma kappa <= lambda, and a coefficient
+ *     with num_k <= 0 meets it for every lambda >= 0 only if its g_k >= 0.  So: 0 if no num_k > 0; else +inf if min den_k <= 0
+ *     or g at min den_k is <= 0 (that is max den_k >= 5 min den_k: the speed varies too much across the sub-curve for this
+ *     tangent, and it is split further); else the largest num_k / g_k over num_k > 0.  Its excess over the sub-curve's true
+ *     maximum falls with the square of the width.
+ *     A sub-curve is closed when bound - U <= tol, tol = eps_rel * max(max_curv, U) with U the incumbent at the time of the
+ *     test; of two open halves the one with the larger bound is followed, the other waits.
+ *     With OBTG_MD_OK: m_sigma is sigma kappa(t_star) as evaluated above, t_star a bisection point in [0, 1] (0 when the value
+ *     is the clamp's 0), and nothing on [0, 1] exceeds m_sigma + tol up to the rounding of the bound.  OBTG_MD_NODE_CAP:
+ *     max_nodes sub-curves examined; OBTG_MD_DEPTH_CAP: more than 32 sub-curves waiting; m_sigma is then still a value met
+ *     (or the clamp's 0).  Where den vanishes with num != 0 (a stop, a cusp) the bound stays infinite and the search ends
+ *     on a cap, never in a spin.  num == 0 identically (degree 1, a straight path, a vehicle at rest with every coefficient
+ *     zero): m_sigma = 0, t_star = 0, OBTG_MD_OK.  A row with a non-finite coefficient: out and t_star NaN, OBTG_MD_OK.
+ *     A row's result depends on its control points, max_curv, eps_rel and max_nodes alone: not on B, its position, the
+ *     launch form, or host versus _dev.
+ * obtg_curvature_true_min_jac: the same out, t_star, status bit for bit, and jac[B][N][2][2][n+1], the derivative of row_sigma
+ *     with respect to the vehicle's own control points at t_star.  With w = B^(n-1)(t_star), u = B^(n-2)(t_star),
+ *     A_i = n (w_(i-1) - w_i), C_i = n (n-1) (u_(i-2) - 2 u_(i-1) + u_i)  (obtg_ang_rate_true_min_jac's on T = 1):
+ *         jac[side][0][i] = -sigma [ (y'' A_i - y' C_i) / den^(3/2) - 3 num x' A_i / den^(5/2) ]
+ *         jac[side][1][i] = -sigma [ (x' C_i - x'' A_i) / den^(3/2) - 3 num y' A_i / den^(5/2) ]
+ *     x', y', x'', y'', den, num at t_star from the same w and u (csrc/bern_device.h curvature_envelope_block states every
+ *     operation; every multiply-add an explicit fma: host and _dev, fused and two-launch forms give the same bits).  The block
+ *     is zero where the returned row IS max_curv (m_sigma = 0: the clamp, num == 0), NaN for a NaN row; with a cap status it
+ *     is still the derivative at the returned t_star.  There is no jac_tf: it is identically 0.
+ * Checks: dim != 2: OBTG_ERR_ARG; degrees above 31: OBTG_ERR_UNSUPPORTED; t_star and status nullable; B == 0 is OBTG_OK.
+ * Degrees 3, 5, 7, 8, 10, 15, 20 form the coefficients in registers, one launch (with the blocks too, unless the context was
+ * created under OBTG_TRUE_MIN_JAC_FUSED=0: then one more launch); other degrees from 1 to 31 go through a workspace of
+ * obtg_curvature_poly's rows (two launches, three with blocks).  Every launch is timed under OBTG_K_ANG_RATE.  _dev: dY may be
+ * NULL inside an obtg_fd_view. */
+int obtg_curvature_poly(obtg_ctx*, const double* Y, int B, double* out /*[B][N][2][2n+1]*/);
+int obtg_curvature_poly_dev(obtg_ctx*, const double* dY, int B, double* d_out);
+int obtg_curvature_true_min(obtg_ctx*, const double* Y, int B, double max_curv, double eps_rel, int max_nodes,
+                            double* out /*[B][N][2]*/, double* t_star /*[B][N][2], nullable*/, int* status /*[B][N][2], nullable*/);
+int obtg_curvature_true_min_dev(obtg_ctx*, const double* dY, int B, double max_curv, double eps_rel, int max_nodes, double* d_out,
+                                double* d_t_star, int* d_status);
+int obtg_curvature_true_min_jac(obtg_ctx*, const double* Y, int B, double max_curv, double eps_rel, int max_nodes,
+                                double* out /*[B][N][2]*/, double* t_star /*nullable*/, int* status /*nullable*/,
+                                double* jac /*[B][N][2][2][n+1]*/);
+int obtg_curvature_true_min_jac_dev(obtg_ctx*, const double* dY, int B, double max_curv, double eps_rel, int max_nodes,
+                                    double* d_out, double* d_t_star, int* d_status, double* d_jac);
+/* The curvature range of M free planar curves c[M][2][K] (x row, y row; 2 <= K <= 32 control points, whatever the context's
+ * shape is; K > 32: OBTG_ERR_UNSUPPORTED): the search above with max_curv = 0 (tol = eps_rel |U|) and no clamp on the sign
+ * of what is reported -- the incumbent starts from the end values alone, and a sub-curve with no num_k > 0 is bounded by the
+ * chord of den^(3/2) over [min den_k, max den_k] (the largest num_k / h_k; 0 if min den_k <= 0):
+ *     k_max[M] = max kappa at t_max[M],    k_min[M] = -max(-kappa) at t_min[M],    status[M][2] (side 0: k_max, side 1: k_min).
+ * num == 0 identically: 0 at t = 0.  A curve with a non-finite coefficient: NaN, OBTG_MD_OK.  Ends with den <= 0 (a curve that
+ * starts or stops at rest) offer no value: the search goes on to interior points with tol = 0 until one does, and where none
+ * ever does it ends on a cap with NaN.
+ * status is nullable.  M == 0 is OBTG_OK.  Two launches, timed under OBTG_K_ANG_RATE. */
+int obtg_bern_curvature(obtg_ctx*, const double* c /*[M][2][K]*/, int M, int K, double eps_rel, int max_nodes,
+                        double* k_min /*[M]*/, double* t_min /*[M]*/, double* k_max /*[M]*/, double* t_max /*[M]*/,
+                        int* status /*[M][2], nullable*/);
+int obtg_bern_curvature_dev(obtg_ctx*, const double* d_c, int M, int K, double eps_rel, int max_nodes, double* d_k_min,
+                            double* d_t_min, double* d_k_max, double* d_t_max, int* d_status);
 
 /* ---- the acceleration bound: |d^2 c / dtime^2| <= bound for every vehicle, in 2-D, 3-D and any other dimension ----
  * For vehicle v with control points P[c][i] (c < d, i <= n) on a span T = tf[b]:

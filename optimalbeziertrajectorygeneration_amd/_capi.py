@@ -125,6 +125,14 @@ _SIGNATURES = {
     "obtg_ang_rate_true_min_dev": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
     "obtg_ang_rate_true_min_jac": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "obtg_ang_rate_true_min_jac_dev": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_curvature_poly": (_i, [_vp, _vp, _i, _vp]),
+    "obtg_curvature_poly_dev": (_i, [_vp, _vp, _i, _vp]),
+    "obtg_curvature_true_min": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
+    "obtg_curvature_true_min_dev": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
+    "obtg_curvature_true_min_jac": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp]),
+    "obtg_curvature_true_min_jac_dev": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp]),
+    "obtg_bern_curvature": (_i, [_vp, _vp, _i, _i, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_bern_curvature_dev": (_i, [_vp, _vp, _i, _i, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "obtg_bern_elev": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "obtg_bern_diff": (_i, [_vp, _vp, _i, _i, _d, _vp]),
     "obtg_bern_mul": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
@@ -778,6 +786,55 @@ class Context(object):
                                   eps_rel=1e-9, max_nodes=100000):
         self._true_min_dev("obtg_ang_rate_true_min_jac_dev", (dY, d_tf), B, (float(max_rate),), eps_rel, max_nodes, d_out, d_t_star,
                            d_status, d_jac, d_jac_tf)
+
+    def curvature_poly(self, Y):
+        """The curvature rows' polynomials (obtg_curvature_poly; dim 2): [B][N][2][2 deg + 1], the Bernstein coefficients of
+        num = y'' x' - x'' y' and then of den = x'^2 + y'^2 on a span of 1; kappa = num / den^(3/2)."""
+        Y, B = self._rows(Y)
+        out = pinned_empty((B, self.n_veh, 2, 2 * self.deg + 1))
+        self._check(self._lib.obtg_curvature_poly(self._h, _ptr(Y), B, _ptr(out)), "obtg_curvature_poly")
+        return out
+
+    def curvature_poly_dev(self, dY, B, d_out):
+        self._check(self._lib.obtg_curvature_poly_dev(self._h, _vp(dY), int(B), _vp(d_out)), "obtg_curvature_poly_dev")
+
+    def curvature_true_min(self, Y, max_curv, eps_rel=1e-9, max_nodes=100000):
+        """Per vehicle and side max_curv - max over t in [0, 1] of max(0, +-kappa) (obtg_curvature_true_min; no time span
+        enters): dict(val[B][N][2], t_star[B][N][2], status[B][N][2] as MD_*); |kappa| <= max_curv on the whole path iff both
+        values of the vehicle are >= 0."""
+        return self._true_min("obtg_curvature_true_min", (self.n_veh, 2), Y, None, (float(max_curv),), eps_rel, max_nodes)
+
+    def curvature_true_min_dev(self, dY, B, max_curv, d_out, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
+        self._true_min_dev("obtg_curvature_true_min_dev", (dY,), B, (float(max_curv),), eps_rel, max_nodes, d_out, d_t_star, d_status)
+
+    def curvature_true_min_jac(self, Y, max_curv, eps_rel=1e-9, max_nodes=100000):
+        """curvature_true_min with its envelope Jacobian (obtg_curvature_true_min_jac): dict(val, t_star, status -- the bits of
+        curvature_true_min --, jac[B][N][2][2][deg+1]: d/d(the vehicle's own control points) of the row at t_star; zero where
+        the row is max_curv itself).  The rows do not depend on tf."""
+        return self._true_min("obtg_curvature_true_min_jac", (self.n_veh, 2), Y, None, (float(max_curv),), eps_rel, max_nodes, "jac")
+
+    def curvature_true_min_jac_dev(self, dY, B, max_curv, d_out, d_jac, d_t_star=None, d_status=None, eps_rel=1e-9,
+                                   max_nodes=100000):
+        self._true_min_dev("obtg_curvature_true_min_jac_dev", (dY,), B, (float(max_curv),), eps_rel, max_nodes, d_out, d_t_star,
+                           d_status, d_jac)
+
+    def bern_curvature(self, c, eps_rel=1e-9, max_nodes=100000):
+        """The curvature range of free planar curves c[M][2][K], 2 <= K <= 32 control points (obtg_bern_curvature):
+        dict(k_min[M], t_min[M], k_max[M], t_max[M], status[M][2] -- side 0: k_max, side 1: k_min)."""
+        c = _f64(c)
+        if c.ndim == 2:
+            c = c[None]
+        M, two, K = c.shape
+        if two != 2:
+            raise ValueError("bern_curvature needs planar curves [M][2][K], got shape %r" % (c.shape,))
+        r = dict(k_min=np.empty(M), t_min=np.empty(M), k_max=np.empty(M), t_max=np.empty(M), status=np.zeros((M, 2), np.int32))
+        self._check(self._lib.obtg_bern_curvature(self._h, _ptr(c), M, K, float(eps_rel), int(max_nodes),
+                                                  *[_ptr(a) for a in r.values()]), "obtg_bern_curvature")
+        return r
+
+    def bern_curvature_dev(self, d_c, M, K, d_k_min, d_t_min, d_k_max, d_t_max, d_status=None, eps_rel=1e-9, max_nodes=100000):
+        self._check(self._lib.obtg_bern_curvature_dev(self._h, _vp(d_c), int(M), int(K), float(eps_rel), int(max_nodes), _vp(d_k_min),
+                                                      _vp(d_t_min), _vp(d_k_max), _vp(d_t_max), _vp(d_status)), "obtg_bern_curvature_dev")
 
     def ang_rate(self, Y, tf, max_rate):
         return self._vehicle_rows("obtg_ang_rate", Y, tf, (float(max_rate),), (self.len_ang_rate,))

@@ -233,6 +233,19 @@ class Bezier(BezierParams):
         _raise_md(r['status'][0], 'arcLength')
         return float(r['len'][0])
 
+    def curvatureRange(self, eps=1e-9, max_nodes=100000):
+        """(k_min, t_min, k_max, t_max): the extrema over the curve of the signed curvature of a planar curve (left turns
+        positive) and the parameters in [0, 1] where they are reached, each within eps x |its value| of the true extremum
+        (obtg_bern_curvature: a certified bisection on the device); a search that does not end within max_nodes sub-curves --
+        a cusp, a stop -- raises as minDist does.  Curvature does not depend on t0 or tf.  Not in the reference."""
+        if self.dim != 2:
+            raise ValueError('The input curve must be two dimensional,\n'
+                             'instead it is {} dimensional'.format(self.dim))
+        r = _ctx().bern_curvature(self.cpts, eps_rel=float(eps), max_nodes=int(max_nodes))
+        for side in (1, 0):
+            _raise_md(r['status'][0][side], 'curvatureRange')
+        return float(r['k_min'][0]), float(r['t_min'][0]), float(r['k_max'][0]), float(r['t_max'][0])
+
     def split(self, tDiv):
         """Two curves, before and after tDiv (bezier.py:533-572): de Casteljau at (tDiv - t0)/(tf - t0); the
         pieces keep the original span's ends, [t0, tDiv] and [tDiv, tf]."""

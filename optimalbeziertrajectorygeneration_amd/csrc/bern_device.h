@@ -543,6 +543,90 @@ __device__ __forceinline__ double ang_envelope_block(const double* __restrict__ 
     return __builtin_fma(-2.0 * W, den, (3.0 * sigma) * num) / T;
 }
 
+// ---- The curvature rows (obtg_curvature_poly, obtg_curvature_true_min[_jac], obtg_bern_curvature).  Signed curvature of a
+// planar curve is kappa(t) = num(t) / den(t)^(3/2) with the angular-rate rows' num and den formed on T = 1 (curvature does
+// not depend on the span): coefficient k of both, the fma sequence and the weights of ang_row_coeff above -- so a caller
+// that hands in the same u_j gets ang_row_coeff's den_k and num_k bit for bit.  This function IS the definition of the
+// curvature rows' coefficients: the in-register search kernels and the any-degree rows kernel both call it.
+struct NumDen { double num, den; };
+template <class A>
+__device__ __forceinline__ NumDen curvature_row_coeff(const A& ux, const A& uy, const A& uxx, const A& uyy, const int n, const int k,
+                                                      const double sk)
+{
+#pragma clang fp contract(off)
+    const int jlo = k > n ? k - n : 0, jhi = k < n ? k : n;
+    double den = 0.0, num = 0.0;
+#pragma unroll
+    for (int j = jlo; j <= jhi; ++j) {
+        den = __builtin_fma(ux[j], ux[k - j], den);
+        den = __builtin_fma(uy[j], uy[k - j], den);
+        num = __builtin_fma(uyy[j], ux[k - j], num);
+        num = __builtin_fma(-uxx[j], uy[k - j], num);
+    }
+    NumDen r;
+    r.num = sk * num; r.den = sk * den;
+    return r;
+}
+
+// Envelope block of one side of one vehicle's curvature row at parameter t: the partial derivatives of
+// row_sigma = max_curv - sigma kappa(t) with respect to the vehicle's own control points (obtg_curvature_true_min_jac).  With
+// n = nc - 1, w = B^(n-1)(t), u = B^(n-2)(t), entries out of range 0, A_i and C_i ang_envelope_block's on T = 1:
+//     A_i = n (w_(i-1) - w_i),    C_i = n (n - 1) (u_(i-2) - 2 u_(i-1) + u_i),
+//     r = 1 / (den sqrt(den)),    q = (3 num) / (den (den sqrt(den))),
+//     out[0][i] = -sigma fma(fma(y'', A_i, -(y' C_i)), r, -((q x') A_i)),
+//     out[1][i] = -sigma fma(fma(x', C_i, -(x'' A_i)), r, -((q y') A_i)),
+// x', y', x'', y'', den, num evaluated here from the same w and u exactly as ang_envelope_block evaluates them; contraction
+// off inside.  There is no d/dT: curvature does not depend on the span.  den = 0 at t (a stop) gives a non-finite block; the
+// callers do not come here for a clamped row or a NaN t (CurvRows::envelope).
+template <int NCMAX>
+__device__ __forceinline__ void curvature_envelope_block(const double* __restrict__ y, const int nc, const double sigma, const double t,
+                                                         double* __restrict__ out)
+{
+#pragma clang fp contract(off)
+    const int n = nc - 1;
+    const double s = 1.0 - t;
+    double u[NCMAX], w[NCMAX];             // u[0 .. n - 1): B^(n-2)(t); w[0 .. n): B^(n-1)(t); the rest stays zero
+#pragma unroll
+    for (int i = 0; i < NCMAX; ++i) u[i] = (i == 0 && n >= 2) ? 1.0 : 0.0;
+#pragma unroll
+    for (int r = 1; r < NCMAX - 2; ++r)
+        if (r < n - 1) {
+#pragma unroll
+            for (int i = r; i >= 1; --i) u[i] = __builtin_fma(t, u[i - 1], s * u[i]);
+            u[0] = s * u[0];
+        }
+#pragma unroll
+    for (int i = 0; i < NCMAX; ++i) w[i] = i == 0 ? s * u[0] : __builtin_fma(t, u[i - 1], s * u[i]);
+    if (n == 1) w[0] = 1.0;
+    const double nT = (double)n, nnT = nT * (double)(n - 1);
+    double d1[2], d2[2];                   // x', y' and x'', y'' at t
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        double a = 0.0, b = 0.0;
+#pragma unroll
+        for (int i = 0; i < NCMAX - 1; ++i)
+            if (i < n) a = __builtin_fma(w[i], y[c * nc + i + 1] - y[c * nc + i], a);
+#pragma unroll
+        for (int i = 0; i < NCMAX - 2; ++i)
+            if (i < n - 1) b = __builtin_fma(u[i], (y[c * nc + i + 2] - y[c * nc + i + 1]) - (y[c * nc + i + 1] - y[c * nc + i]), b);
+        d1[c] = nT * a;
+        d2[c] = nnT * b;
+    }
+    const double den = __builtin_fma(d1[1], d1[1], d1[0] * d1[0]);
+    const double num = __builtin_fma(d2[1], d1[0], -(d2[0] * d1[1]));
+    const double d32 = den * __builtin_sqrt(den);
+    const double r = 1.0 / d32, q = (3.0 * num) / (den * d32);
+    const double qx = q * d1[0], qy = q * d1[1];
+#pragma unroll
+    for (int i = 0; i < NCMAX; ++i)
+        if (i < nc) {
+            const double Ai = nT * ((i == 0 ? 0.0 : w[i - 1]) - w[i]);
+            const double Ci = nnT * (((i < 2 ? 0.0 : u[i - 2]) - (i == 0 ? 0.0 : u[i - 1])) - ((i == 0 ? 0.0 : u[i - 1]) - u[i]));
+            out[i] = -sigma * __builtin_fma(__builtin_fma(d2[1], Ai, -(d1[1] * Ci)), r, -(qx * Ai));
+            out[nc + i] = -sigma * __builtin_fma(__builtin_fma(d1[0], Ci, -(d2[0] * Ai)), r, -(qy * Ai));
+        }
+}
+
 // write a full [n_valid][LR] tile (pitch TP) as one contiguous run of n_valid*LR doubles
 template <int LR, int TP>
 __device__ __forceinline__ void flush_full(const double* __restrict__ tile, double* __restrict__ gout,

@@ -253,6 +253,7 @@ const char* obtg_abi_symbols(void)
         "obtg_accel\0obtg_accel_dev\0obtg_accel_true_min\0obtg_accel_true_min_dev\0obtg_accel_true_min_jac\0obtg_accel_true_min_jac_dev\0"
         "obtg_jerk\0obtg_jerk_dev\0obtg_jerk_true_min\0obtg_jerk_true_min_dev\0obtg_jerk_true_min_jac\0obtg_jerk_true_min_jac_dev\0"
         "obtg_ang_rate_poly\0obtg_ang_rate_poly_dev\0obtg_ang_rate_true_min\0obtg_ang_rate_true_min_dev\0obtg_ang_rate_true_min_jac\0obtg_ang_rate_true_min_jac_dev\0"
+        "obtg_curvature_poly\0obtg_curvature_poly_dev\0obtg_curvature_true_min\0obtg_curvature_true_min_dev\0obtg_curvature_true_min_jac\0obtg_curvature_true_min_jac_dev\0obtg_bern_curvature\0obtg_bern_curvature_dev\0"
         "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_restrict\0obtg_bern_eval\0"
         "obtg_euclidean_obj\0obtg_accel_obj\0obtg_jerk_obj\0"
         "obtg_bern_arc_length\0obtg_bern_arc_length_dev\0obtg_arc_length_obj\0obtg_arc_length_obj_dev\0"
@@ -312,7 +313,7 @@ void obtg_ctx_destroy(obtg_ctx* c)
     (void)hipStreamSynchronize(c->stream);
     flush_pending_events(c);
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
-    DevBuf* bufs[] = { &c->d_pairs, &c->d_obs, &c->d_w2, &c->d_Tt, &c->d_Td, &c->d_Tf, &c->d_ang_dd, &c->d_ang_flags, &c->d_vp_off, &c->d_vp_idx, &c->d_ang_w2n, &c->d_ang_w22n, &c->d_ang_wn, &c->d_ang_rows, &c->d_ang_T4, &c->d_ang_cv2, &c->d_jac,
+    DevBuf* bufs[] = { &c->d_pairs, &c->d_obs, &c->d_w2, &c->d_Tt, &c->d_Td, &c->d_Tf, &c->d_ang_dd, &c->d_ang_flags, &c->d_vp_off, &c->d_vp_idx, &c->d_ang_w2n, &c->d_ang_w22n, &c->d_ang_wn, &c->d_ang_rows, &c->d_curv_tab, &c->d_ang_T4, &c->d_ang_cv2, &c->d_jac,
                        &c->d_binrows, &c->d_tiles, &c->d_poly_pts, &c->d_poly_off, &c->d_hp_a, &c->d_hp_b, &c->d_tile_chunk_off, &c->d_tile_order, &c->d_tile_pslots,
                        &c->d_tile_cobj_off, &c->d_tile_cobjs, &c->d_tile_ij, &c->ws_in,
                        &c->ws_in2, &c->ws_out, &c->ws_fd };
@@ -1674,8 +1675,9 @@ int obtg_bern_extrema(obtg_ctx* c, const double* coef, int M, int K, int want_ma
 //    degree (OBTG_TRUE_MIN_JAC_FUSED=0) 2; a degree off the list 2 for values, 3 with blocks.
 //
 // The chain: the fused kernel where the shape has one (with the blocks, d_jac set, only if true_min_jac_fused); else the
-// values -- the fused value kernel, or the family's rows at R = 0 into a workspace and obtg_bern_extrema on them -- and then
-// the blocks from Y and t_star in a launch of their own.
+// values -- the fused value kernel, or the family's rows at R = 0 into a workspace and obtg_bern_extrema on them (the family's
+// own search where it names one: the curvature rows' two polynomials) -- and then the blocks from Y and t_star (and the rows'
+// values) in a launch of their own.
 static int true_min_chain(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double eps_rel, int max_nodes, double* d_out,
                           double* d_t, int* d_status, double* d_jac, double* d_jac_tf)
 {
@@ -1698,11 +1700,12 @@ static int true_min_chain(obtg_ctx* c, const RowFamily& f, const double* dY, int
         DevBuf& ws = c->ws_misc[WS_L_ROWS];
         if ((rc = ws.reserve(sizeof(double) * (size_t)items * K))) return rc;
         if ((rc = f.rows_r0(c, f, dY, B, ws.as<double>()))) return rc;
-        rc = launch_bern_extrema(c, ws.as<double>(), items, K, 0, eps_rel, 0.0, max_nodes, d_out, d_t, nullptr, nullptr, d_status,
-                                 f.kernel_id);
+        rc = f.search ? f.search(c, f, ws.as<double>(), items, eps_rel, max_nodes, d_out, d_t, d_status)
+                      : launch_bern_extrema(c, ws.as<double>(), items, K, 0, eps_rel, 0.0, max_nodes, d_out, d_t, nullptr, nullptr, d_status,
+                                            f.kernel_id);
     }
     if (rc || !d_jac) return rc;
-    return launch_true_min_envelope(c, f, dY, B, d_t, d_jac, d_jac_tf);
+    return launch_true_min_envelope(c, f, dY, B, d_t, d_jac, d_jac_tf, d_out);
 }
 
 // the host body: Y (and tf, where the family has one) up, val | t_star | jac_tf | jac in ws_out, status in WS_STATUS
@@ -1941,6 +1944,133 @@ int obtg_ang_rate_true_min_jac(obtg_ctx* c, const double* Y, const double* tf, i
     if (!Y || !jac) return OBTG_ERR_ARG;
     if (B == 0) return OBTG_OK;
     return true_min_host(c, ang_row_family(c, nullptr, max_rate), Y, tf, B, eps_rel, max_nodes, out, t_star, status, jac, jac_tf);
+}
+
+// The curvature family: the angular-rate entry points without a time span (nothing takes tf), with curvature_row_family.
+// jac_tf does not exist: the rows do not depend on the span.
+static int curvature_args(const obtg_ctx* c, const double* out, int B, int max_nodes, double eps_rel)
+{
+    if (!check_ctx(c) || c->dim != 2 || !out || B < 0 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
+    return c->deg > 31 ? OBTG_ERR_UNSUPPORTED : OBTG_OK;
+}
+
+int obtg_curvature_poly_dev(obtg_ctx* c, const double* dY, int B, double* d_out)
+{
+    if (int rc = curvature_args(c, d_out, B, 1, 0.0)) return rc;
+    (void)hipSetDevice(c->device);
+    const RowFamily f = curvature_row_family(c, 0.0);
+    return with_batch(c, dY, B, false, [&](const double* src) { return launch_curvature_rows(c, f, src, B, d_out); });
+}
+
+int obtg_curvature_poly(obtg_ctx* c, const double* Y, int B, double* out)
+{
+    if (int rc = curvature_args(c, out, B, 1, 0.0)) return rc;
+    if (!Y) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    const size_t n = (size_t)B * c->n_veh * 2 * (2 * c->deg + 1);
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    double* d_out = h.out<double>(c->ws_out, n);
+    h.run([&] { return launch_curvature_rows(c, curvature_row_family(c, 0.0), dY, B, d_out); });
+    return h.finish(out, d_out, n);
+}
+
+int obtg_curvature_true_min_dev(obtg_ctx* c, const double* dY, int B, double max_curv, double eps_rel, int max_nodes, double* d_out,
+                                double* d_t_star, int* d_status)
+{
+    if (int rc = curvature_args(c, d_out, B, max_nodes, eps_rel)) return rc;
+    return true_min_dev(c, curvature_row_family(c, max_curv), dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, nullptr, nullptr);
+}
+
+int obtg_curvature_true_min(obtg_ctx* c, const double* Y, int B, double max_curv, double eps_rel, int max_nodes, double* out,
+                            double* t_star, int* status)
+{
+    if (int rc = curvature_args(c, out, B, max_nodes, eps_rel)) return rc;
+    if (!Y) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    return true_min_host(c, curvature_row_family(c, max_curv), Y, nullptr, B, eps_rel, max_nodes, out, t_star, status, nullptr, nullptr);
+}
+
+int obtg_curvature_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, double max_curv, double eps_rel, int max_nodes,
+                                    double* d_out, double* d_t_star, int* d_status, double* d_jac)
+{
+    if (int rc = curvature_args(c, d_out, B, max_nodes, eps_rel)) return rc;
+    if (!d_jac) return OBTG_ERR_ARG;
+    return true_min_dev(c, curvature_row_family(c, max_curv), dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, d_jac, nullptr);
+}
+
+int obtg_curvature_true_min_jac(obtg_ctx* c, const double* Y, int B, double max_curv, double eps_rel, int max_nodes, double* out,
+                                double* t_star, int* status, double* jac)
+{
+    if (int rc = curvature_args(c, out, B, max_nodes, eps_rel)) return rc;
+    if (!Y || !jac) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    return true_min_host(c, curvature_row_family(c, max_curv), Y, nullptr, B, eps_rel, max_nodes, out, t_star, status, jac, nullptr);
+}
+
+// Free planar curves c[M][2][K], any K from 2 to 32 whatever the context's shape is: the family's rows kernel and workspace
+// search on them (max_curv = 0, no clamp).  The context's shape does not enter, so this is not a RowFamily (which describes
+// rows of the context's vehicles); the launchers are the family's.  The product table of degree K - 1 is kept from call to call.
+static int curvature_table(obtg_ctx* c, int n, const double** d_tab)
+{
+    if (c->curv_tab_n != n) {
+        c->curv_tab_n = -1;
+        auto t = ang_rows_table(n);
+        if (int rc = upload(c, c->d_curv_tab, t.data(), t.size() * sizeof(double))) return rc;
+        c->curv_tab_n = n;
+    }
+    *d_tab = c->d_curv_tab.as<double>();
+    return OBTG_OK;
+}
+
+static int bern_curvature_args(const obtg_ctx* c, int M, int K, double eps_rel, int max_nodes, const double* coef, const double* k_min,
+                               const double* t_min, const double* k_max, const double* t_max)
+{
+    if (!check_ctx(c) || M < 0 || K < 2 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
+    if (!curvature_supported(K)) return OBTG_ERR_UNSUPPORTED;
+    if (M > 0 && (!coef || !k_min || !t_min || !k_max || !t_max)) return OBTG_ERR_ARG;
+    return OBTG_OK;
+}
+
+// rows into WS_L_ROWS, then the search: both launches timed under OBTG_K_ANG_RATE
+static int bern_curvature_chain(obtg_ctx* c, const double* d_c, int M, int K, double eps_rel, int max_nodes, double* d_k_min,
+                                double* d_t_min, double* d_k_max, double* d_t_max, int* d_status)
+{
+    const double* d_tab = nullptr;
+    int rc = curvature_table(c, K - 1, &d_tab);
+    if (rc) return rc;
+    DevBuf& ws = c->ws_misc[WS_L_ROWS];
+    if ((rc = ws.reserve(sizeof(double) * (size_t)M * 2 * (2 * K - 1)))) return rc;
+    if ((rc = launch_curv_rows(c, d_c, d_tab, M, K, ws.as<double>(), OBTG_K_ANG_RATE))) return rc;
+    return launch_curv_search(c, ws.as<double>(), 2L * M, K, 0.0, eps_rel, max_nodes, d_k_max, d_t_max, d_k_min, d_t_min, nullptr,
+                              d_status, OBTG_K_ANG_RATE);
+}
+
+int obtg_bern_curvature_dev(obtg_ctx* c, const double* d_c, int M, int K, double eps_rel, int max_nodes, double* d_k_min,
+                            double* d_t_min, double* d_k_max, double* d_t_max, int* d_status)
+{
+    if (int rc = bern_curvature_args(c, M, K, eps_rel, max_nodes, d_c, d_k_min, d_t_min, d_k_max, d_t_max)) return rc;
+    if (M == 0) return OBTG_OK;
+    (void)hipSetDevice(c->device);
+    return bern_curvature_chain(c, d_c, M, K, eps_rel, max_nodes, d_k_min, d_t_min, d_k_max, d_t_max, d_status);
+}
+
+int obtg_bern_curvature(obtg_ctx* c, const double* coef, int M, int K, double eps_rel, int max_nodes, double* k_min, double* t_min,
+                        double* k_max, double* t_max, int* status)
+{
+    if (int rc = bern_curvature_args(c, M, K, eps_rel, max_nodes, coef, k_min, t_min, k_max, t_max)) return rc;
+    if (M == 0) return OBTG_OK;
+    const size_t m = (size_t)M;
+    HostCall h(c);
+    const double* d_c = h.in(c->ws_in, coef, m * 2 * K);
+    double* dv = h.out<double>(c->ws_out, 4 * m);          // k_min | t_min | k_max | t_max
+    int* ds = h.out<int>(c->ws_misc[WS_STATUS], 2 * m);
+    h.run([&] { return bern_curvature_chain(c, d_c, M, K, eps_rel, max_nodes, dv, dv + m, dv + 2 * m, dv + 3 * m, ds); });
+    h.fetch(t_min, dv + m, m);
+    h.fetch(k_max, dv + 2 * m, m);
+    h.fetch(t_max, dv + 3 * m, m);
+    h.fetch(status, ds, 2 * m);
+    return h.finish(k_min, dv, m);
 }
 
 // ------------------------------------------------------------------ single-curve algebra

@@ -528,6 +528,358 @@ __global__ __launch_bounds__(kWave) void k_ang_rows(const AngExParams q, const i
 }
 
 // =====================================================================================
+//  the curvature rows: kappa = num / den^(3/2) is not a polynomial, and its polynomial form has 6n + 1 coefficients -- more
+//  than a row of lanes from degree 11 on -- so the family has a search of its own over the two polynomials at once
+//  (include/obtg.h obtg_curvature_true_min states the contract; DESIGN.md 4.21 the reasoning).
+//
+//  An item is (row, vehicle, side); sigma = +1 / -1 for side 0 / 1 multiplies num once, when the coefficients are formed, and
+//  the search MAXIMISES sigma kappa.  The shape is wave_search's: the first step one lane per item, an item that needs the
+//  search gets the wave, lane k holds (sigma num_k, den_k), a de Casteljau level is the same pair of averages on both, the
+//  pieces are taken as wave_search takes them, waiting sub-curves are frames of 2K + 3 doubles (num | den | bound, t0, width)
+//  in LDS.  Incumbent U: the largest sigma kappa met at an end of [0, 1] or at a bisection midpoint (cv_kappa), from 0 when
+//  the row clamps.  Upper bound of a node (cv_node_bound): the tangent of the convex den^(3/2) at the node's mid-range.
+//  A node with bound - U <= eps_rel max(max_curv, |U|) is closed; of two open children the one with the larger bound is followed.
+// =====================================================================================
+constexpr int kCvWaves = 1;           // waves per workgroup: K = 63 is 33 KB of frames per wave, and the in-register first
+                                      // step wants the whole register file of a SIMD lane (launch bound 64: 512 VGPRs)
+constexpr int kCvMaxNC = 32;
+
+struct CvOut {
+    double val, t;                     // the incumbent and where it was met
+    int nodes, status;
+};
+
+struct CurvParams {
+    const double* __restrict__ Y;      // [items / 2][2][nc]: the vehicles (curves) in item order
+    const double* __restrict__ tab;    // C(n, .)[n+1], then 1 / C(2n, .)[2n+1] (capi.cpp ang_rows_table)
+    const double* __restrict__ rows;   // [items / 2][2][2n+1], num then den (k_curv_rows): the workspace form's operand
+    double* __restrict__ val;          // [items]: max_curv - m_sigma;  free curves: k_max[items / 2]
+    double* __restrict__ t;            // [items] nullable;             free curves: t_max[items / 2]
+    double* __restrict__ val1;         // free curves: k_min[items / 2], t_min[items / 2]; null otherwise
+    double* __restrict__ t1;
+    int* __restrict__ nodes;           // [items] nullable
+    int* __restrict__ status;          // [items] nullable
+    double* __restrict__ jac;          // [items][2][nc] (the envelope forms)
+    long M;                            // items
+    int nc, max_nodes;
+    double W, eps_rel;                 // W = max_curv; free curves: 0, and the incumbent does not start from 0
+};
+
+// sigma kappa at a point, NaN where the point offers no incumbent: den <= 0, or a quotient that is not finite
+__device__ __forceinline__ double cv_kappa(double num, double den)
+{
+    if (!(den > 0.0)) return __builtin_nan("");
+    const double k = num / (den * __builtin_sqrt(den));
+    return fabs(k) <= DBL_MAX ? k : __builtin_nan("");
+}
+// (a free curve's incumbent is -inf until a point offers a value: it does not enter the tolerance, and the search goes on)
+__device__ __forceinline__ double cv_tol(double W, double eps_rel, double U) { return eps_rel * fmax(W, U > -INFINITY ? fabs(U) : 0.0); }
+
+// The bound of a node from what its coefficients reduce to.  One coefficient's share, given the node's dmin and dmax:
+// d0 = 0.5 (dmin + dmax), g_k = fma(1.5 sqrt(d0), den_k, -0.5 (d0 sqrt(d0))) is the tangent of den^(3/2) at d0 -- below the
+// convex function, so sum g_k B_k(t) <= den(t)^(3/2) -- and lambda g_k - num_k >= 0 for EVERY k gives sigma kappa <= lambda.
+// A coefficient with num_k <= 0 meets that for every lambda >= 0 only if its g_k >= 0, so the rule needs g > 0 at dmin (g is
+// increasing in den: that is every g_k > 0; it fails once dmax >= 5 dmin, where the tangent at the mid-range is below 0 at
+// dmin).  Then the bound is the largest num_k / g_k over num_k > 0, which is > 0.  +inf where g at dmin is <= 0 or dmin <= 0;
+// -inf stands for "no num_k > 0" (the clamp or cv_chord_ratio answers that case).  max is exact, so the order of the reduction does not enter.
+__device__ __forceinline__ double cv_ratio(double num, double den, double dmin, double dmax)
+{
+    if (!(num > 0.0)) return -INFINITY;
+    if (!(dmin > 0.0)) return INFINITY;
+    const double d0 = 0.5 * (dmin + dmax), s0 = __builtin_sqrt(d0);
+    const double a = 1.5 * s0, c = -0.5 * (d0 * s0);
+    return fma(a, dmin, c) > 0.0 ? num / fma(a, den, c) : INFINITY;
+}
+// No num_k > 0 on the node.  A clamped row: sigma kappa <= 0 there, the bound is 0.  A free curve needs a bound below 0 that
+// converges as fast: the chord of den^(3/2) over [dmin, dmax] lies above it, h_k = fma(slope, den_k - dmin, dmin sqrt(dmin)),
+// slope = (dmax + sqrt(dmax dmin) + dmin) / (sqrt(dmax) + sqrt(dmin)), and num / den^(3/2) <= num / h for num <= 0: the
+// bound is the largest num_k / h_k (dmin <= 0: 0).
+__device__ __forceinline__ double cv_chord_ratio(double num, double den, double dmin, double dmax)
+{
+    if (!(dmin > 0.0)) return 0.0;
+    const double a = __builtin_sqrt(dmax), b = __builtin_sqrt(dmin);
+    const double slope = ((dmax + a * b) + dmin) / (a + b);
+    return num / fma(slope, den - dmin, dmin * b);
+}
+
+__device__ __forceinline__ double cv_wave_max(double v)
+{
+#pragma unroll
+    for (int o = 32; o; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+// the whole wave on one node: lane k < K holds (num_k, den_k); the same value in every lane
+__device__ __forceinline__ double cv_node_bound(double num, double den, bool act, bool clamp)
+{
+    const double dmin = ex_wave_min(act ? den : INFINITY), dmax = cv_wave_max(act ? den : -INFINITY);
+    double ub = cv_wave_max(act ? cv_ratio(num, den, dmin, dmax) : -INFINITY);
+    if (ub == -INFINITY) ub = clamp ? 0.0 : cv_wave_max(act ? cv_chord_ratio(num, den, dmin, dmax) : -INFINITY);
+    return ub;
+}
+
+// The first step of an item (node 1), one lane: get(k) is its (sigma num_k, den_k).  true: `o` is the item's answer;
+// false: the search has to run from (o.val, o.t) as the incumbent.
+template <int KC, class Get>
+__device__ __forceinline__ bool cv_first(const Get& get, int K, double W, double eps_rel, bool clamp, CvOut& o)
+{
+    if (KC > 0) K = KC;
+    bool bad = false, any = false;
+    double dmin = INFINITY, dmax = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < (KC > 0 ? KC : K); ++k) {
+        const NumDen c = get(k);
+        bad = bad || !(fabs(c.num) <= DBL_MAX) || !(fabs(c.den) <= DBL_MAX);
+        any = any || c.num != 0.0;
+        dmin = fmin(dmin, c.den); dmax = fmax(dmax, c.den);
+    }
+    o.status = OBTG_MD_OK;
+    if (bad) { o.val = o.t = __builtin_nan(""); o.nodes = 0; return true; }
+    o.nodes = 1;
+    o.val = 0.0; o.t = 0.0;
+    if (!any) return true;                  // num == 0 identically: a straight path, degree 1, a vehicle at rest
+    if (!clamp) o.val = -INFINITY;
+    const NumDen c0 = get(0), c1 = get(K - 1);
+    const double k0 = cv_kappa(c0.num, c0.den), k1 = cv_kappa(c1.num, c1.den);
+    if (k0 > o.val) { o.val = k0; o.t = 0.0; }
+    if (k1 > o.val) { o.val = k1; o.t = 1.0; }
+    double ub = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < (KC > 0 ? KC : K); ++k) { const NumDen c = get(k); ub = fmax(ub, cv_ratio(c.num, c.den, dmin, dmax)); }
+    if (ub == -INFINITY) {
+        ub = 0.0;
+        if (!clamp) {
+            ub = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < (KC > 0 ? KC : K); ++k) { const NumDen c = get(k); ub = fmax(ub, cv_chord_ratio(c.num, c.den, dmin, dmax)); }
+        }
+    }
+    return !(ub - o.val > cv_tol(W, eps_rel, o.val));
+}
+
+// The whole wave on ONE item (every lane must be here).  Lane k < K holds (bn, bd) = (sigma num_k, den_k); (U, tU): the first
+// step's incumbent.  stk: this wave's kExStack x (2K + 3) doubles.  Every scalar below is the same in all lanes.
+__device__ __forceinline__ CvOut cv_wave_search(double bn, double bd, const int K, const double W, const double eps_rel,
+                                                const bool clamp, double U, double tU, const int max_nodes, double* stk)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const bool act = lane < K;
+    const int pitch = 2 * K + 3;
+    double t0 = 0.0, w = 1.0;
+    int nodes = 1, sp = 0, status = OBTG_MD_OK;
+    for (;;) {
+        if (nodes + 2 > max_nodes) { status = OBTG_MD_NODE_CAP; break; }
+        // deCasteljau at 1/2 of both polynomials, both pieces: left[r] is lane 0's value after level r, right[i] lane i's
+        double ln = bn, ld = bd, mn = ex_lane0(bn), md = ex_lane0(bd);
+        for (int r = 1; r < K; ++r) {
+            const double upn = wave_next_lane(bn), upd = wave_next_lane(bd);
+            if (lane <= K - 1 - r) { bn = 0.5 * bn + 0.5 * upn; bd = 0.5 * bd + 0.5 * upd; }
+            mn = ex_lane0(bn); md = ex_lane0(bd);
+            if (lane == r) { ln = mn; ld = md; }
+        }
+        const double hw = 0.5 * w, tm = t0 + hw;
+        nodes += 2;
+        const double km = cv_kappa(mn, md);
+        if (km > U) { U = km; tU = tm; }
+        const double tol = cv_tol(W, eps_rel, U);
+        const double ubL = cv_node_bound(ln, ld, act, clamp), ubR = cv_node_bound(bn, bd, act, clamp);
+        const bool aliveL = ubL - U > tol, aliveR = ubR - U > tol;
+        if (aliveL && aliveR) {
+            if (sp == kExStack) { status = OBTG_MD_DEPTH_CAP; break; }
+            const bool go_left = ubL >= ubR;
+            double* f = stk + sp * pitch;
+            if (act) { f[lane] = go_left ? bn : ln; f[K + lane] = go_left ? bd : ld; }
+            if (lane == 0) { f[2 * K] = go_left ? ubR : ubL; f[2 * K + 1] = go_left ? tm : t0; f[2 * K + 2] = hw; }
+            ++sp;
+            if (go_left) { bn = ln; bd = ld; } else t0 = tm;
+            w = hw;
+        } else if (aliveL) { bn = ln; bd = ld; w = hw; }
+        else if (aliveR) { t0 = tm; w = hw; }
+        else {
+            bool found = false;
+            wave_sync();
+            while (sp > 0) {
+                --sp;
+                const double* f = stk + sp * pitch;
+                if (f[2 * K] - U > tol) {
+                    bn = act ? f[lane] : 0.0; bd = act ? f[K + lane] : 0.0;
+                    t0 = f[2 * K + 1]; w = f[2 * K + 2];
+                    found = true;
+                    break;
+                }
+            }
+            wave_sync();
+            if (!found) break;
+        }
+    }
+    CvOut o;
+    o.val = U; o.t = tU; o.nodes = nodes; o.status = status;
+    return o;
+}
+
+// An item's answer to memory: row = max_curv - m_sigma; a free curve's sides are k_max = m_+ and k_min = -m_-.  A free
+// curve on which no point offered an incumbent (den <= 0 at every point met) has no curvature to report: NaN.
+__device__ __forceinline__ double cv_store(const CurvParams& q, long item, CvOut o)
+{
+    double v;
+    if (q.val1) {
+        if (o.val == -INFINITY) o.val = o.t = __builtin_nan("");
+        const long m = item >> 1;
+        v = (item & 1) ? -o.val : o.val;
+        ((item & 1) ? q.val1 : q.val)[m] = v;
+        ((item & 1) ? q.t1 : q.t)[m] = o.t;
+    } else {
+        v = q.W - o.val;
+        q.val[item] = v;
+        if (q.t) q.t[item] = o.t;
+    }
+    if (q.nodes) q.nodes[item] = o.nodes;
+    if (q.status) q.status[item] = o.status;
+    return v;
+}
+
+// The item's block from Y at the t_star and the row value an earlier step left: zero where the row IS max_curv (m_sigma = 0:
+// the clamp, a straight path, a vehicle at rest), NaN for a NaN t_star, bern_device.h curvature_envelope_block otherwise.
+template <int NCMAX>
+__device__ __forceinline__ void cv_envelope(const CurvParams& q, long item, int nc, double row, double t)
+{
+    double* o = q.jac + (size_t)item * (2 * nc);
+    if (row == q.W || !(t == t)) {
+        const double fill = t == t ? 0.0 : t;
+        for (int e = 0; e < 2 * nc; ++e) o[e] = fill;
+        return;
+    }
+    curvature_envelope_block<NCMAX>(q.Y + (size_t)(item >> 1) * (2 * nc), nc, (item & 1) ? -1.0 : 1.0, t, o);
+}
+
+// What both kernel forms do once an item's first step is known: the wave on every item that needs it, in lane order; `load`
+// puts item src's coefficients into the lanes.
+template <class Load>
+__device__ __forceinline__ void cv_search_items(const CurvParams& q, const Load& load, int K, bool need, CvOut& mine, double* stk)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const bool clamp = q.val1 == nullptr;
+    unsigned long long mask = __ballot(need);
+    while (mask) {
+        const int src = __ffsll((long long)mask) - 1;
+        mask &= mask - 1;
+        double bn = 0.0, bd = 0.0;
+        load(src, bn, bd);
+        const CvOut o = cv_wave_search(bn, bd, K, q.W, q.eps_rel, clamp, ex_lane(mine.val, src), ex_lane(mine.t, src), q.max_nodes, stk);
+        if (lane == src) mine = o;
+    }
+}
+
+// Coefficients in registers, one launch (the counts of OBTG_NC_CURV_LIST): AngRows::coeffs on T = 1 with
+// curvature_row_coeff, then the steps above; JAC: every lane writes its own block.
+template <int NC, bool JAC>
+__global__ __launch_bounds__(kCvWaves * kWave) void k_curv_true_min(const CurvParams q)
+{
+    constexpr int N = NC - 1, L = 2 * NC - 1;
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    double* stk = lds + (size_t)wave * kExStack * (2 * L + 3);
+    const long item = ((long)blockIdx.x * kCvWaves + wave) * kWave + lane;
+    const bool valid = item < q.M;
+    const long it = valid ? item : q.M - 1;
+    const double sigma = (it & 1) ? -1.0 : 1.0;
+    const double* v = q.Y + (size_t)(it >> 1) * (2 * NC);
+    const ctab_t Cn = as_ctab(q.tab), Sk = Cn + NC;
+    double num[L], den[L];
+    {
+        double u1[2][NC], u2[2][NC];           // C(n, j) x'_j, C(n, j) y'_j;  C(n, j) x''_j, C(n, j) y''_j
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+            double x[NC], x1[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) x[c] = v[d * NC + c];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) x1[c] = diff_elev1_at(x, c, N, (double)N);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) u2[d][c] = Cn[c] * diff_elev1_at(x1, c, N, (double)N);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) u1[d][c] = Cn[c] * x1[c];
+        }
+#pragma unroll
+        for (int k = 0; k < L; ++k) {
+            const NumDen c = curvature_row_coeff(u1[0], u1[1], u2[0], u2[1], N, k, Sk[k]);
+            num[k] = sigma * c.num; den[k] = c.den;
+        }
+    }
+    CvOut mine;
+    const bool need = !cv_first<L>([&](int k) { NumDen c; c.num = num[k]; c.den = den[k]; return c; }, L, q.W, q.eps_rel,
+                                   q.val1 == nullptr, mine) && valid;
+    cv_search_items(q, [&](int src, double& bn, double& bd) {
+#pragma unroll
+        for (int k = 0; k < L; ++k) {
+            const double a = ex_lane(num[k], src), b = ex_lane(den[k], src);
+            if (lane == k) { bn = a; bd = b; }
+        }
+    }, L, need, mine, stk);
+    if (valid) {
+        const double row = cv_store(q, item, mine);
+        if (JAC) cv_envelope<NC>(q, item, NC, row, mine.t);
+    }
+}
+
+// The workspace form, any degree 1 .. 31: the coefficients are k_curv_rows' rows in memory, K = 2 nc - 1 at run time
+__global__ __launch_bounds__(kCvWaves * kWave) void k_curv_search(const CurvParams q)
+{
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6, K = 2 * q.nc - 1;
+    double* stk = lds + (size_t)wave * kExStack * (2 * K + 3);
+    const long item0 = ((long)blockIdx.x * kCvWaves + wave) * kWave, item = item0 + lane;
+    const bool valid = item < q.M;
+    const long it = valid ? item : q.M - 1;
+    const double sigma = (it & 1) ? -1.0 : 1.0;
+    const double* r = q.rows + (size_t)(it >> 1) * (2 * K);
+    CvOut mine;
+    const bool need = !cv_first<0>([&](int k) { NumDen c; c.num = sigma * r[k]; c.den = r[K + k]; return c; }, K, q.W, q.eps_rel,
+                                   q.val1 == nullptr, mine) && valid;
+    cv_search_items(q, [&](int src, double& bn, double& bd) {
+        const long is = item0 + src;
+        const double* rs = q.rows + (size_t)(is >> 1) * (2 * K);
+        if (lane < K) { bn = ((is & 1) ? -1.0 : 1.0) * rs[lane]; bd = rs[K + lane]; }
+    }, K, need, mine, stk);
+    if (valid) cv_store(q, item, mine);
+}
+
+// The blocks alone, from Y, the rows' values and their t_star: one item per lane, nc <= kCvMaxNC at run time
+__global__ __launch_bounds__(kEnvThreads) void k_curv_envelope(const CurvParams q)
+{
+    const long item = (long)blockIdx.x * kEnvThreads + threadIdx.x;
+    if (item < q.M) cv_envelope<kCvMaxNC>(q, item, q.nc, q.val[item], q.t[item]);
+}
+
+// The curvature rows' polynomials to memory, any degree 1 .. 31: k_ang_rows on T = 1 without a side -- one wave per vehicle
+// (curve), lane k forms coefficient k of num and of den with the function the in-register kernels use: out[.][2][2n+1].
+__global__ __launch_bounds__(kWave) void k_curv_rows(const CurvParams q, double* __restrict__ out)
+{
+    __shared__ double sh[6][kCvMaxNC];       // x, y -> u1x, u1y after the last read; x', y'; u2x, u2y
+    const long veh = blockIdx.x;
+    const int lane = threadIdx.x, nc = q.nc, n = nc - 1, L = 2 * n + 1;
+    const double val = (double)n;
+    const double* v = q.Y + (size_t)veh * (2 * nc);
+    const double* Cn = q.tab;
+    const double* Sk = Cn + nc;
+    if (lane < nc) { sh[0][lane] = v[lane]; sh[1][lane] = v[nc + lane]; }
+    __syncthreads();
+    if (lane < nc)
+        for (int d = 0; d < 2; ++d) sh[2 + d][lane] = diff_elev1_at(sh[d], lane, n, val);
+    __syncthreads();
+    if (lane < nc)
+        for (int d = 0; d < 2; ++d) {
+            sh[4 + d][lane] = Cn[lane] * diff_elev1_at(sh[2 + d], lane, n, val);
+            sh[d][lane] = Cn[lane] * sh[2 + d][lane];
+        }
+    __syncthreads();
+    if (lane < L) {
+        const NumDen c = curvature_row_coeff(sh[0], sh[1], sh[4], sh[5], n, lane, Sk[lane]);
+        out[(size_t)veh * 2 * L + lane] = c.num;
+        out[((size_t)veh * 2 + 1) * L + lane] = c.den;
+    }
+}
+
+// =====================================================================================
 //  launchers
 // =====================================================================================
 bool bern_extrema_supported(int K) { return K >= 1 && K <= kExMaxK; }
@@ -646,6 +998,60 @@ static int launch_fused(obtg_ctx* c, const RowFamily& f, const double* dY, const
     return OBTG_OK;
 }
 
+// ---- the curvature family's launches.  Frames: kExStack x (2K + 3) doubles per wave, 33 KB at K = 63.
+static CurvParams curv_params(const double* d_curves, const double* d_tab, int nc, long items, double W, double eps_rel, int max_nodes)
+{
+    CurvParams q{};
+    q.Y = d_curves; q.tab = d_tab; q.nc = nc; q.M = items; q.W = W; q.eps_rel = eps_rel; q.max_nodes = max_nodes;
+    return q;
+}
+static size_t curv_lds_bytes(int K) { return sizeof(double) * kCvWaves * kExStack * (size_t)(2 * K + 3); }
+static unsigned curv_grid(long items) { const long per_wg = kCvWaves * kWave; return (unsigned)((items + per_wg - 1) / per_wg); }
+
+bool curvature_supported(int nc) { return nc >= 2 && nc <= kCvMaxNC; }
+
+int launch_curv_rows(obtg_ctx* c, const double* d_curves, const double* d_tab, long n_curves, int nc, double* d_out, int kernel_id)
+{
+    if (n_curves <= 0) return OBTG_OK;
+    if (!curvature_supported(nc)) return OBTG_ERR_UNSUPPORTED;
+    const CurvParams q = curv_params(d_curves, d_tab, nc, 2 * n_curves, 0.0, 0.0, 1);
+    ScopedKernelTimer t(c, kernel_id);
+    hipLaunchKernelGGL(k_curv_rows, dim3((unsigned)n_curves), dim3(kWave), 0, c->stream, q, d_out);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
+int launch_curv_search(obtg_ctx* c, const double* d_rows, long items, int nc, double max_curv, double eps_rel, int max_nodes,
+                       double* d_val, double* d_t, double* d_val1, double* d_t1, int* d_nodes, int* d_status, int kernel_id)
+{
+    if (items <= 0) return OBTG_OK;
+    if (!curvature_supported(nc)) return OBTG_ERR_UNSUPPORTED;
+    CurvParams q = curv_params(nullptr, nullptr, nc, items, max_curv, eps_rel, max_nodes);
+    q.rows = d_rows; q.val = d_val; q.t = d_t; q.val1 = d_val1; q.t1 = d_t1; q.nodes = d_nodes; q.status = d_status;
+    ScopedKernelTimer t(c, kernel_id);
+    hipLaunchKernelGGL(k_curv_search, dim3(curv_grid(items)), dim3(kCvWaves * kWave), curv_lds_bytes(2 * nc - 1), c->stream, q);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
+// the counts of OBTG_NC_CURV_LIST: coefficients in registers, one launch (with the blocks when d_jac is set)
+static int launch_curv_fused(obtg_ctx* c, const RowFamily& f, const double* dY, const ExParams& ex, double* d_jac)
+{
+    if (c->dim != 2) return OBTG_ERR_UNSUPPORTED;
+    const int nc = c->deg + 1;
+    void (*kern)(const CurvParams) = nullptr;
+#define OBTG_CASE(NC_) if (nc == NC_) kern = d_jac ? k_curv_true_min<NC_, true> : k_curv_true_min<NC_, false>;
+    OBTG_NC_CURV_LIST(OBTG_CASE)
+#undef OBTG_CASE
+    if (!kern) return OBTG_ERR_UNSUPPORTED;
+    CurvParams q = curv_params(dY, c->d_ang_rows.as<double>(), nc, ex.M, f.w, ex.eps_rel, ex.max_nodes);
+    q.val = ex.val; q.t = ex.t; q.status = ex.status; q.jac = d_jac;
+    ScopedKernelTimer t(c, f.kernel_id);
+    hipLaunchKernelGGL(kern, dim3(curv_grid(ex.M)), dim3(kCvWaves * kWave), curv_lds_bytes(ex.K), c->stream, q);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
 int launch_true_min(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double eps_rel, int max_nodes, double* d_out,
                     double* d_t, int* d_status, double* d_jac, double* d_jac_tf)
 {
@@ -661,6 +1067,7 @@ int launch_true_min(obtg_ctx* c, const RowFamily& f, const double* dY, int B, do
         case ROWS_SPEED: return launch_fused<SpeedRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_ACCEL: return launch_fused<AccelRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_JERK: return launch_fused<JerkRows>(c, f, dY, ex, d_jac, d_jac_tf);
+        case ROWS_CURV: return launch_curv_fused(c, f, dY, ex, d_jac);
         default: return launch_fused<TsepRows>(c, f, dY, ex, d_jac, d_jac_tf);
     }
 }
@@ -679,13 +1086,21 @@ static int launch_blocks(obtg_ctx* c, const RowFamily& f, const double* dY, cons
 }
 
 int launch_true_min_envelope(obtg_ctx* c, const RowFamily& f, const double* dY, int B, const double* d_t, double* d_jac,
-                             double* d_jac_tf)
+                             double* d_jac_tf, const double* d_val)
 {
     if (B <= 0 || f.items <= 0) return OBTG_OK;
     if (c->deg + 1 > kEnvMaxNC) return OBTG_ERR_UNSUPPORTED;
     ExParams ex{};
     ex.t = const_cast<double*>(d_t); ex.M = (long)B * f.items;
     switch (f.kind) {
+        case ROWS_CURV: {
+            CurvParams q = curv_params(dY, c->d_ang_rows.as<double>(), c->deg + 1, ex.M, f.w, 0.0, 1);
+            q.val = const_cast<double*>(d_val); q.t = ex.t; q.jac = d_jac;
+            ScopedKernelTimer t(c, f.kernel_id);
+            hipLaunchKernelGGL(k_curv_envelope, dim3((unsigned)((ex.M + kEnvThreads - 1) / kEnvThreads)), dim3(kEnvThreads), 0, c->stream, q);
+            OBTG_HIP(c, hipGetLastError());
+            return OBTG_OK;
+        }
         case ROWS_ANG: return launch_blocks<AngRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_SPEED: return launch_blocks<SpeedRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_ACCEL: return launch_blocks<AccelRows>(c, f, dY, ex, d_jac, d_jac_tf);
@@ -712,6 +1127,32 @@ RowFamily ang_row_family(const obtg_ctx* c, const double* d_tf, double max_rate)
 {
     RowFamily f{ ROWS_ANG, 2 * c->n_veh, OBTG_K_ANG_RATE, 1.0, 0.0, d_tf, launch_ang_rows };
     f.w = max_rate;
+    return f;
+}
+
+// obtg_curvature_poly's launch, and the family's rows_r0: [B][n_veh][2][2 deg + 1], num then den
+int launch_curvature_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out)
+{
+    if (B <= 0 || f.items <= 0) return OBTG_OK;
+    if (c->dim != 2 || !curvature_supported(c->deg + 1)) return OBTG_ERR_UNSUPPORTED;
+    int rc = ensure_tables(c);
+    if (rc) return rc;
+    return launch_curv_rows(c, dY, c->d_ang_rows.as<double>(), (long)B * c->n_veh, c->deg + 1, d_out, f.kernel_id);
+}
+
+// the family's search of its workspace rows: two items (sides) per pair of rows
+static int curvature_rows_search(obtg_ctx* c, const RowFamily& f, const double* d_rows, long items, double eps_rel, int max_nodes,
+                                 double* d_out, double* d_t, int* d_status)
+{
+    return launch_curv_search(c, d_rows, items, c->deg + 1, f.w, eps_rel, max_nodes, d_out, d_t, nullptr, nullptr, nullptr, d_status,
+                              f.kernel_id);
+}
+
+RowFamily curvature_row_family(const obtg_ctx* c, double max_curv)
+{
+    RowFamily f{ ROWS_CURV, 2 * c->n_veh, OBTG_K_ANG_RATE, 1.0, 0.0, nullptr, launch_curvature_rows };
+    f.w = max_curv;
+    f.search = curvature_rows_search;
     return f;
 }
 

@@ -30,6 +30,9 @@ namespace obtg {
 //                      of OBTG_NC_SEP that build without scratch; the others form their blocks in a launch
 //                      of their own
 #define OBTG_NC_JERK_LIST(X) OBTG_NC_DYN(X) X(21)
+//   OBTG_NC_CURV_LIST : the curvature rows' in-register kernels (k_curv_true_min; 2-D), the counts of OBTG_NC_ANG_LIST that
+//                      build without scratch; the others take the workspace route
+#define OBTG_NC_CURV_LIST(X) OBTG_NC_DYN(X) X(21)
 static inline bool nc_in_sep(int nc)  { return false OBTG_NC_SEP(OBTG_NC_EQ_); }
 static inline bool nc_in_dyn(int nc)  { return false OBTG_NC_DYN(OBTG_NC_EQ_); }
 static inline bool nc_in_elev(int nc) { return false OBTG_NC_ELEV(OBTG_NC_EQ_); }
@@ -94,6 +97,8 @@ struct KernelStat {
 //   obtg_gjk_swarm           holds 3 (WS_INFO) -> launch_gjk_swarm takes 7 (WS_L_CHANGED) and, under OBTG_TIMELINE, 6
 //   obtg_bern_arc_length     holds 3 (WS_INFO) -> launch_arc_length takes none
 //   obtg_arc_length_obj      holds 4 (WS_STATUS) -> launch_arc_length_obj takes 7 (WS_L_ROWS: the vehicles' lengths and status)
+//   obtg_curvature_true_min[_jac] are true_min_host / true_min_chain calls like the first line's (the workspace rows are num and den)
+//   obtg_bern_curvature      holds 4 (WS_STATUS) -> bern_curvature_chain takes 7 (WS_L_ROWS: the curves' num and den rows)
 enum WsSlot {
     WS_POLY_OFF = 0,      // int[n_poly + 1]: polygon offsets
     WS_CURVE_OFF = 0,     //   int[n_curves + 1]: control-point offsets of obtg_min_dist_mixed's curves
@@ -138,6 +143,8 @@ struct obtg_ctx {
     obtg::DevBuf d_Tf;        // ... and as matrix-instruction B fragments (elev_table_frag): the batch kernels
     obtg::DevBuf d_ang_w2n, d_ang_w22n, d_ang_wn;  // angular-rate fast path weights
     obtg::DevBuf d_ang_rows;  // the true angular-rate rows' separable product weights: C(n, .)[n+1], 1 / C(2n, .)[2n+1] (dim 2, n <= 31)
+    obtg::DevBuf d_curv_tab;  // obtg_bern_curvature: the same table for the degree of the last call's curves (curv_tab_n)
+    int curv_tab_n = -1;
     obtg::DevBuf d_ang_T4;    // angular rate, R > 0: elevation 4*deg -> 4*(deg+R) as a scaled convolution (elev_conv_padded)
     obtg::DevBuf d_ang_cv2;   // the same for the speed rows, 2*deg -> 2*deg+R, with the 1/C(2n+R, k) row
     bool ang_elevate_first = false;   // true: the reference's order (elevate, then products at degree n+R; generic kernel)
@@ -372,7 +379,7 @@ int launch_bern_extrema(obtg_ctx* c, const double* d_c, long M, int K, int want_
 // A true-minimum row family (obtg_temporal_sep_true_min[_jac], obtg_speed_true_min[_jac], obtg_ang_rate_true_min[_jac], obtg_accel_true_min[_jac], obtg_jerk_true_min[_jac]) as the host path sees it: what one
 // call of the family contributes beyond the arguments every family has.  On the device the family is a struct of
 // extrema_kernels.hip (TsepRows, SpeedRows, AngRows, AccelRows, JerkRows), found by `kind`.
-enum RowKind { ROWS_TSEP, ROWS_SPEED, ROWS_ANG, ROWS_ACCEL, ROWS_JERK };
+enum RowKind { ROWS_TSEP, ROWS_SPEED, ROWS_ANG, ROWS_ACCEL, ROWS_JERK, ROWS_CURV };
 struct RowFamily {
     RowKind kind;
     int items;                  // per batch row: n_pairs | n_veh | 2 n_veh
@@ -382,7 +389,12 @@ struct RowFamily {
     // its full rows at R = 0 from the any-degree kernel, [B][items][2 deg + 1], whatever the context's DEG_ELEV is: the launch
     // a context with R = 0 makes, bit for bit; the context is not touched
     int (*rows_r0)(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);
-    double w = 0.0;             // ROWS_ANG: the bound on |angular rate| (it enters the coefficients, not the output transform)
+    double w = 0.0;             // ROWS_ANG: the bound on |angular rate| (it enters the coefficients, not the output transform);
+                                // ROWS_CURV: max_curv
+    // the search of the workspace rows rows_r0 wrote; null: launch_bern_extrema, one row per item.  ROWS_CURV: a vehicle's two
+    // rows are num and den and serve both of its items, so the workspace has as many rows as the batch has items
+    int (*search)(obtg_ctx* c, const RowFamily& f, const double* d_rows, long items, double eps_rel, int max_nodes, double* d_out,
+                  double* d_t, int* d_status) = nullptr;
 };
 RowFamily tsep_row_family(const obtg_ctx* c, double max_sep);                                         // bern_kernels.hip
 RowFamily speed_row_family(const obtg_ctx* c, const double* d_tf, double bound, int is_max);
@@ -391,13 +403,23 @@ RowFamily jerk_row_family(const obtg_ctx* c, const double* d_tf, double bound); 
 RowFamily ang_row_family(const obtg_ctx* c, const double* d_tf, double max_rate);                     // extrema_kernels.hip
 // the angular-rate family's polynomials [B][n_veh][2][2 deg + 1] (obtg_ang_rate_poly; its rows_r0): dim 2, degree 1 .. 31
 int launch_ang_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);
+// The curvature family (dim 2, degree 1 .. 31; no time span).  Its search is its own (extrema_kernels.hip cv_wave_search).
+RowFamily curvature_row_family(const obtg_ctx* c, double max_curv);
+int launch_curvature_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);      // obtg_curvature_poly; its rows_r0
+// free curves (obtg_bern_curvature): d_curves[n][2][nc], d_tab = C(nc-1, .)[nc] | 1 / C(2 nc - 2, .)[2 nc - 1]; rows out[n][2][2 nc - 1];
+// the search of 2 n items with max_curv = 0; d_val1 / d_t1 set: the free-curve outputs k_max, t_max | k_min, t_min [n] each
+bool curvature_supported(int nc);                       // 2 <= nc <= 32
+int launch_curv_rows(obtg_ctx* c, const double* d_curves, const double* d_tab, long n_curves, int nc, double* d_out, int kernel_id);
+int launch_curv_search(obtg_ctx* c, const double* d_rows, long items, int nc, double max_curv, double eps_rel, int max_nodes,
+                       double* d_val, double* d_t, double* d_val1, double* d_t1, int* d_nodes, int* d_status, int kernel_id);
 // the fused form for the fast-kernel list's shapes, one launch; OBTG_ERR_UNSUPPORTED: go through the family's R = 0 rows.
 // d_jac: with the envelope blocks [B][items][dim][deg+1]; d_jac_tf (nullable, speed): their d/dtf [B][items]
 int launch_true_min(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double eps_rel, int max_nodes, double* d_out,
                     double* d_t, int* d_status, double* d_jac = nullptr, double* d_jac_tf = nullptr);
 // the blocks alone from Y (tf) and the t_star of a value launch: any degree up to 31 (else OBTG_ERR_UNSUPPORTED)
+// d_val: the rows' values of the value launch (ROWS_CURV reads them: a row that is its bound has a zero block)
 int launch_true_min_envelope(obtg_ctx* c, const RowFamily& f, const double* dY, int B, const double* d_t, double* d_jac,
-                             double* d_jac_tf);
+                             double* d_jac_tf, const double* d_val = nullptr);
 
 // ---------------------------------------------------------------- launchers (arclen_kernels.hip): true arc length
 bool arc_length_supported(int dim, int K);             // 1 <= dim <= 3, 2 <= K <= 32

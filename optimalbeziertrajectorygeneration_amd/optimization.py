@@ -174,6 +174,7 @@ _MODEL_FIELDS = (
     ('numVeh', 'numVeh', None), ('dim', 'dimension', None), ('deg', 'degree', None), ('minGoal', 'minimizeGoal', None),
     ('maxSep', 'maxSep', None), ('minSpeed', 'minSpeed', None), ('maxSpeed', 'maxSpeed', None),
     ('maxAngRate', 'maxAngRate', None), ('maxAccel', 'maxAccel', None), ('maxJerk', 'maxJerk', None),
+    ('maxCurvature', 'maxCurvature', None),
     ('initPoints', 'initPoints', np.atleast_2d), ('finalPoints', 'finalPoints', np.atleast_2d),
     ('initSpeeds', 'initSpeeds', np.atleast_1d), ('finalSpeeds', 'finalSpeeds', np.atleast_1d),
     ('initAngs', 'initAngs', np.atleast_1d), ('finalAngs', 'finalAngs', np.atleast_1d),
@@ -188,9 +189,12 @@ _MODEL_FIELDS = (
 #   methods of the control-point rows, the true minima, the true minima with their envelope blocks and the exact Jacobian
 #   (None: not built), every one called (Y, tf[, bound], *lead);  planar: dim == 2 only;  sides: true-minimum rows per
 #   vehicle ([B][N] values, or [B][N][2] flattened to row 2 v + side);  constraints, jacobian: the public names, as the
-#   messages spell them;  noun: the rows' name in a sentence.
+#   messages spell them;  noun: the rows' name in a sentence;  span: the device calls take tf (False: the rows do not depend
+#   on the time span -- they are called (Y, bound, *lead), have no d/dtf, and their explicit tf column is an exact 0).
+#   A family without a `rows` method (rows_attr and rows None) has true rows only: it has no rows option, its rows are always
+#   the true ones, and it enters _serve_key behind the obstacles, only while its bound is set.
 _RowFamily = collections.namedtuple('_RowFamily', 'key bound optional rows_attr rows true_min envelope exact lead planar sides '
-                                                  'constraints jacobian noun')
+                                                  'constraints jacobian noun span', defaults=(True,))
 _ROW_FAMILIES = (
     _RowFamily('vmax', 'maxSpeed', False, 'speedRows', 'speed', 'speed_true_min', 'speed_true_min_jac', 'speed_jac', (True,),
                False, 1, 'maxSpeedConstraints', 'maxSpeedJacobian', 'speed'),
@@ -202,13 +206,16 @@ _ROW_FAMILIES = (
                False, 1, 'maxAccelConstraints', 'maxAccelJacobian', 'acceleration'),
     _RowFamily('jmax', 'maxJerk', True, 'jerkRows', 'jerk', 'jerk_true_min', 'jerk_true_min_jac', None, (),
                False, 1, 'maxJerkConstraints', 'maxJerkJacobian', 'jerk'),
+    _RowFamily('curv', 'maxCurvature', True, None, None, 'curvature_true_min', 'curvature_true_min_jac', None, (),
+               True, 2, 'maxCurvatureConstraints', 'maxCurvatureJacobian', 'curvature', False),
 )
 _FAMILY = {fam.key: fam for fam in _ROW_FAMILIES}
-_ROWS_OPTIONS = tuple(dict.fromkeys(fam.rows_attr for fam in _ROW_FAMILIES))      # speedRows, angRateRows, accelRows, jerkRows
+_ROWS_OPTIONS = tuple(dict.fromkeys(fam.rows_attr for fam in _ROW_FAMILIES if fam.rows is not None))      # speedRows, angRateRows, accelRows, jerkRows
 # What a kept finite-difference batch depends on per family, in _serve_key's order: every rows option with, right behind it,
 # the bounds that may be None; the other bounds follow maxSep.  A family enters the key by being in the table.
 _KEY_ROWS = tuple((attr, tuple(fam.bound for fam in _ROW_FAMILIES if fam.optional and fam.rows_attr == attr)) for attr in _ROWS_OPTIONS)
 _KEY_BOUNDS = tuple(fam.bound for fam in _ROW_FAMILIES if not fam.optional)
+_KEY_TAIL = tuple(fam.bound for fam in _ROW_FAMILIES if fam.rows is None)            # (name, value) behind the obstacles, while set
 
 # The goals with a device call ('timeopt' is x[-1]).  goal, lower case: (key in _serve / _fd_values; values [B] of the rows Y;
 # gradient blocks [B][N d][n+1] of the rows Y), both called (bezopt, ctx, Y, what) -- `what` names the caller where a search
@@ -351,7 +358,8 @@ class BezOptimization(object):
                  maxAccel=None,
                  accelRows='all',
                  maxJerk=None,
-                 jerkRows='all'):
+                 jerkRows='all',
+                 maxCurvature=None):
         """Beyond the reference's keywords: `device` (HIP ordinal; None: this process's, see _capi.default_device) and `separationRows` --
         'all': temporalSeparationConstraints returns every elevated control point of every pair, as the
         reference does (optimization.py:337); 'min': one row per pair, the smallest of them -- the
@@ -379,6 +387,9 @@ class BezOptimization(object):
         # N (2n+R+1) elevated control points of maxJerk^2 - (d/2)|c'''|^2 (the curve of the reference's jerk objective,
         # optimization.py:522-539, under a bound); 'true_min': per vehicle its true minimum over the trajectory's time
         # (obtg_jerk_true_min) -- N rows whatever DEG_ELEV is, feasible iff >= 0.
+        # maxCurvature (None: no bound; dim 2): |curvature| <= maxCurvature per vehicle, a turning radius of 1 / maxCurvature
+        # that does not move with tf -- maxCurvatureConstraints: 2N true rows, maxCurvature - max over the path of max(0, +-kappa)
+        # (obtg_curvature_true_min).  Curvature is not a polynomial: there is no control-point form and no rows option.
         given = locals()
         for attr in reversed(_ROWS_OPTIONS):         # (the newest family's option is checked first, as it always was)
             if given[attr] not in ('all', 'true_min'):
@@ -486,7 +497,12 @@ class BezOptimization(object):
         """The family's true-minimum call on the rows Y at TRUE_MIN_EPS_REL (envelope: with the envelope blocks): its dict;
         a search that ran out of budget raises in the name of `what` (bezier._raise_md)"""
         call = getattr(ctx, fam.envelope if envelope else fam.true_min)
-        return _md_checked(call(Y, tf, bound, *fam.lead, eps_rel=self.TRUE_MIN_EPS_REL), what)
+        operands = (Y, tf, bound) if fam.span else (Y, bound)
+        return _md_checked(call(*operands, *fam.lead, eps_rel=self.TRUE_MIN_EPS_REL), what)
+
+    def _rows_option(self, fam):
+        """'all' / 'true_min': the family's rows option; a family without a `rows` method has true rows only"""
+        return 'true_min' if fam.rows is None else getattr(self, fam.rows_attr)
 
     def _vehicle_rows(self, fam, ctx, Y, tf):
         """[B][rows]: the family's rows under its rows option -- 'all': the control points of every vehicle; 'true_min': the
@@ -494,7 +510,7 @@ class BezOptimization(object):
         bound = self.model[fam.bound]
         if bound is None:
             self._bound(fam, fam.constraints)        # raises
-        if getattr(self, fam.rows_attr) == 'true_min':
+        if self._rows_option(fam) == 'true_min':
             v = self._vehicle_true_min(fam, ctx, Y, tf, bound, fam.constraints + '(true_min)')['val']
             return v.reshape(v.shape[0], -1)
         return getattr(ctx, fam.rows)(Y, tf, bound, *fam.lead)
@@ -532,6 +548,16 @@ class BezOptimization(object):
         self._check_planar()
         r = self._true_rows_at(_FAMILY['ang'], x, self.model['maxAngRate'], 'trueAngularRateRows')
         return r['val'][0], r['t_star'][0]
+
+    def trueCurvatureRange(self, x):
+        """(k_min[N], t_min[N], k_max[N], t_max[N]): per vehicle the true extrema over the path of its signed curvature (left
+        turns positive) and the parameters in [0, 1] where they are reached (obtg_bern_curvature at TRUE_MIN_EPS_REL),
+        whatever maxCurvature is."""
+        x = np.asarray(x, dtype=float)
+        self._check_planar()
+        Y = self.reshapeVector(x).reshape(self.model['numVeh'], 2, self.model['deg'] + 1)
+        r = _md_checked(self._ctx(False).bern_curvature(Y, eps_rel=self.TRUE_MIN_EPS_REL), 'trueCurvatureRange')
+        return r['k_min'], r['t_min'], r['k_max'], r['t_max']
 
     def trueSpeedRange(self, x):
         """(min_val[N], t_min[N], max_val[N], t_max[N]): per vehicle the true extrema over the trajectory of (d/2)|dv/dt|^2
@@ -692,6 +718,18 @@ class BezOptimization(object):
             return closure(x)
         return wrapper
 
+    @property
+    def maxCurvatureConstraints(self):
+        """maxCurvature -+ curvature >= 0 on the whole path: float64[2N], row 2 v + side -- side 0: maxCurvature - max(0, max
+        kappa) (left turns), side 1: maxCurvature - max(0, max -kappa) (right turns); true rows (obtg_curvature_true_min), the
+        same whatever tf is."""
+        closure = self._vehicle_closure(_FAMILY['curv'])
+
+        def wrapper(x):
+            self._check_planar()
+            return closure(x)
+        return wrapper
+
     def spatialSeparationConstraints(self, x, robust=False):
         """All-pairs minDist over vehicles AND shape obstacles (optimization.py:109-133);
         returns shape (P, 3): (dist, t1, t2) - maxSep, as the reference does.
@@ -849,10 +887,12 @@ class BezOptimization(object):
         m = self.model
         rows = [v for attr, optional in _KEY_ROWS for v in (getattr(self, attr), *[m[b] for b in optional])]
         bounds = [m[b] for b in _KEY_BOUNDS]
+        tail = [(b, m[b]) for b in _KEY_TAIL if m[b] is not None]
         return (int(DEG_ELEV), self.separationRows, *rows, self.activeRows, self._rv_cache[0], self.model['maxSep'], *bounds,
                 None if self._timeopt() else self.model['tf'],
                 None if self.pointObstacles is None else np.asarray(self.pointObstacles, dtype=float).tobytes(),
-                None if self.shapeObstacles is None else tuple(np.asarray(c.cpts, dtype=float).tobytes() for c in self.shapeObstacles))
+                None if self.shapeObstacles is None else tuple(np.asarray(c.cpts, dtype=float).tobytes() for c in self.shapeObstacles),
+                *tail)
 
     def _jac(self, x, family):
         F, dx = self._fd_values(x, family)
@@ -1004,6 +1044,13 @@ class BezOptimization(object):
     def maxJerkJacobian(self, x, structured=True, method='fd'):
         return self._jac_vehicle(x, 'jmax', structured, method)
 
+    def maxCurvatureJacobian(self, x, structured=True, method='fd'):
+        """d(maxCurvatureConstraints)/dx, dense [2N][n_x]: method='fd' differences the search (one batched call),
+        method='envelope' is the derivative of each row at the parameter its search returns (obtg_curvature_true_min_jac; zero
+        for a row that is maxCurvature itself).  The rows have no explicit dependence on tf: that part of a time-optimal
+        problem's tf column is an exact 0 (with prescribed speeds the column still carries dY/dtf)."""
+        return self._jac_vehicle(x, 'curv', structured, method)
+
     # ------------------------------------------------------------------ exact Jacobians (method='exact')
     # The device returns d rows / d Y per pair or vehicle ([..][rows][dim][deg+1] blocks, include/obtg.h obtg_*_jac); the chain
     # rule to x keeps the free columns, and for a time-optimal problem adds the tf column: the explicit d/dtf of the speed and
@@ -1075,7 +1122,7 @@ class BezOptimization(object):
     def _check_jac_method(self, fam, method):
         """Whether the family's Jacobian provider can answer `method` under the family's rows option -- the same order of
         checks for every family; what cannot be answered raises.  Returns whether the rows are the true minima."""
-        rows = getattr(self, fam.rows_attr)
+        rows = self._rows_option(fam)
         true_min = rows == 'true_min'
         if fam.planar and (method == 'envelope' or true_min):      # (control-point rows of another dimension: the device call answers)
             self._check_planar()
@@ -1085,6 +1132,9 @@ class BezOptimization(object):
             return true_min
         _check_method(method)
         if method == 'exact':
+            if fam.exact is None and fam.rows is None:
+                raise ValueError("{}(method='exact') is not built for the {} rows: use method='fd' or method='envelope'"
+                                 .format(fam.jacobian, fam.noun))
             if fam.exact is None:
                 raise ValueError("{}(method='exact') is not built for the {} rows: use method='fd' or, with {}='true_min', "
                                  "method='envelope'".format(fam.jacobian, fam.noun, fam.rows_attr))
@@ -1102,7 +1152,8 @@ class BezOptimization(object):
         r = self._vehicle_true_min(fam, ctx, Y0, tf, self._bound(fam, fam.jacobian), fam.jacobian + '(envelope)', envelope=True)
         N = self.model['numVeh']
         blk = r['jac'][0].reshape((N, fam.sides) + r['jac'].shape[-2:])            # blocks of fam.sides rows each
-        return self._scatter_exact(blk, (np.arange(N),), (1.0,), r['jac_tf'][0].reshape(N, fam.sides))
+        dtf = r['jac_tf'][0].reshape(N, fam.sides) if fam.span else np.zeros((N, fam.sides))
+        return self._scatter_exact(blk, (np.arange(N),), (1.0,), dtf)
 
     def trueMinSeparationJacobian(self, x):
         """temporalSeparationJacobian(x, method='envelope')"""

@@ -301,6 +301,13 @@ int obtg_ctx_create(obtg_ctx** out, int n_veh, int dim, int deg, int deg_elev, i
     rc = upload(c, c->d_pairs, c->h_pairs.data(), c->h_pairs.size() * sizeof(int));
     if (!rc) rc = upload(c, c->d_obs, point_obs, sizeof(double) * (size_t)n_point_obs * dim);
     if (!rc) rc = ensure_tables(c);
+    if (!rc) {
+        // the structured FD step's ticket counters (obtg_ctx::d_struct_tickets): both banks zero
+        c->struct_ticket_stride = std::max(256, (c->n_pairs + 63) / 64 + 64);
+        const size_t bytes = sizeof(int) * 2 * (size_t)c->struct_ticket_stride;
+        rc = c->d_struct_tickets.reserve(bytes);
+        if (!rc && hipMemset(c->d_struct_tickets.p, 0, bytes) != hipSuccess) { (void)hipGetLastError(); rc = OBTG_ERR_DEVICE; }
+    }
     if (rc) { obtg_ctx_destroy(c); return rc; }
     *out = c;
     return OBTG_OK;
@@ -315,7 +322,7 @@ void obtg_ctx_destroy(obtg_ctx* c)
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
     DevBuf* bufs[] = { &c->d_pairs, &c->d_obs, &c->d_w2, &c->d_Tt, &c->d_Td, &c->d_Tf, &c->d_ang_dd, &c->d_ang_flags, &c->d_vp_off, &c->d_vp_idx, &c->d_ang_w2n, &c->d_ang_w22n, &c->d_ang_wn, &c->d_ang_rows, &c->d_curv_tab, &c->d_ang_T4, &c->d_ang_cv2, &c->d_jac,
                        &c->d_binrows, &c->d_tiles, &c->d_poly_pts, &c->d_poly_off, &c->d_hp_a, &c->d_hp_b, &c->d_tile_chunk_off, &c->d_tile_order, &c->d_tile_pslots,
-                       &c->d_tile_cobj_off, &c->d_tile_cobjs, &c->d_tile_ij, &c->ws_in,
+                       &c->d_tile_cobj_off, &c->d_tile_cobjs, &c->d_tile_ij, &c->d_struct_tickets, &c->ws_in,
                        &c->ws_in2, &c->ws_out, &c->ws_fd };
     for (DevBuf* b : bufs) b->release();
     for (auto& b : c->ws_misc) b.release();

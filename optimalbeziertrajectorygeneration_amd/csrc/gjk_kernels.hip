@@ -993,6 +993,65 @@ struct StructuredParams {
     int dyn_groups_per_row, dyn_rows_per, dyn_streams, dyn_fix_groups;   // D: see the kernel
     int dyn_split;                     // D, DEG_ELEV > 0: stream workgroups of 16 vehicles (DynEmit::sub) instead of 64
     int first_pert;                    // the view's first perturbed local row: 1 (the view starts at the batch's row 0) or 0 (a later row range)
+    // Rows handed out at run time (flat S and G kinds; nullptr: fixed ranges only).  The first sep_static_ranges /
+    // gjk_static_ranges workgroups of a group own fixed ranges of rows [0, sep_static_rows) / [0, gjk_static_rows), as ever.
+    // The workgroups behind them are the group's SWEEPERS: they draw tickets of sep_ticket_rows / gjk_ticket_rows of the
+    // remaining rows from the group's counter (one per separation group, then one per hull-pair chunk), lowest rows first,
+    // until it passes the last row: whenever a sweeper was dispatched, all sweepers of a group end within one ticket of
+    // each other, and one that comes late leaves at once.  Nobody waits for anybody.  `tickets` is zero when the launch
+    // starts; its first workgroup zeroes `tickets_idle`, the bank of the context's NEXT launch (obtg_ctx::struct_ticket_bank).
+    int* tickets;
+    int* tickets_idle;
+    int sep_ticket_rows, gjk_ticket_rows;
+    int sep_static_ranges, sep_static_rows, gjk_static_ranges, gjk_static_rows;
+};
+
+// One ticket for the calling wave: the counter's value before `rows` were added to it (StructuredParams::tickets).  Every
+// lane issues the atomic, lane 0 with the increment and the others with 0 (see the queue pull of k_min_dist_wave).
+__device__ __forceinline__ int draw_rows(int* counter, int rows)
+{
+    const int t = atomicAdd(counter, (threadIdx.x & (kWave - 1)) == 0 ? rows : 0);
+    return __builtin_amdgcn_readfirstlane(t);
+}
+
+// The S kind's output run -- the [64][L] tile of a separation group -- in the registers of a workgroup's first NT threads,
+// as 16-byte pieces (256: every thread streams; fewer: a sweeper, whose last wave draws the tickets instead)
+template <int NC, int NT>
+struct SepRun {
+    static constexpr int L = 2 * NC - 1;
+    static constexpr int kSlots = (kWave * L / 2 + NT - 1) / NT;      // 16-byte pieces per thread
+    double v0[kSlots], v1[kSlots];
+    int pr0[kSlots], pr1[kSlots];                                // (i | j << 16) of the pair each element belongs to, -1: none
+    __device__ __forceinline__ void load(const double* tile, const unsigned* gpair, int n_el)
+    {
+#pragma unroll
+        for (int s = 0; s < kSlots; ++s) {
+            const int m = (int)threadIdx.x + NT * s, e0 = 2 * m, e1 = e0 + 1;
+            v0[s] = v1[s] = 0.0; pr0[s] = pr1[s] = -1;
+            if (NT < 256 && (int)threadIdx.x >= NT) continue;
+            if (e0 < n_el) { pr0[s] = (int)gpair[e0 / L]; v0[s] = tile[e0]; }
+            if (e1 < n_el) { pr1[s] = (int)gpair[e1 / L]; v1[s] = tile[e1]; }
+        }
+    }
+    // row b of the view: every element but those of pairs that hold the row's own vehicle (its F workgroup writes them)
+    __device__ __forceinline__ void write_row(const GjkSwarmParams& p, int g, int b) const
+    {
+        const int fd_e = fd_element(p.fd, p.fd_fixed, NC, b);
+        const int vb = fd_e >= 0 ? fd_e / (2 * NC) : -1;
+        const size_t ob = ((size_t)b * p.ts.n_pairs + (size_t)g * kWave) * L;
+        double* o = p.ts.out + ob;
+        const bool aligned = (ob & 1) == 0;                     // rows of an odd length start on odd elements
+#pragma unroll
+        for (int s = 0; s < kSlots; ++s) {
+            const int m = (int)threadIdx.x + NT * s;
+            const bool w0 = pr0[s] >= 0 && (pr0[s] & 0xffff) != vb && (pr0[s] >> 16) != vb;
+            const bool w1 = pr1[s] >= 0 && (pr1[s] & 0xffff) != vb && (pr1[s] >> 16) != vb;
+            if (w0 && w1 && aligned) store_nt2(o + 2 * m, v0[s], v1[s]);
+            else if (w0 && w1) { store_nt(o + 2 * m, v0[s]); store_nt(o + 2 * m + 1, v1[s]); }
+            else if (w0) store_nt(o + 2 * m, v0[s]);
+            else if (w1) store_nt(o + 2 * m + 1, v1[s]);
+        }
+    }
 };
 
 // ELEV: DEG_ELEV > 0 -- the separation groups are elevated (tsep_elev_group_stream), the fix-up rows too, and the
@@ -1017,7 +1076,19 @@ __global__ __launch_bounds__(256, WPC) void k_step_fd_structured(const Structure
     const int grp = (int)blockIdx.x >> 4, slot = ((int)blockIdx.x + grp) & 15;
     const int kind = sp.pat[slot];
     const int id = grp * sp.per16[kind] + sp.rank[slot];
+    // (the first workgroup, whatever its kind, zeroes the ticket counters of the context's next launch: a launch may have
+    // sweepers of one kind only, or none for a batch of a few rows, and still owes the next one a zero bank)
+    if (!ELEV && sp.tickets_idle != nullptr && blockIdx.x == 0)
+        for (int i = threadIdx.x; i < sp.n_sep_groups + sp.gjk_chunks; i += blockDim.x)
+            __hip_atomic_store(sp.tickets_idle + i, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (id >= sp.n_kind[kind]) return;
+    const bool dyn_rows = !ELEV && sp.tickets != nullptr;      // S and G: sweepers behind the fixed ranges (StructuredParams::tickets)
+    __shared__ int s_ticket[2];                                 // the current ticket's first row and the next one's, alternately
+    // A sweeper's last wave is its DISPATCHER: it draws the tickets and stores no rows, the other three stream.  A wave that
+    // waits for an atomic's result waits for every store it issued before it (one in-order counter): drawn by a streaming
+    // wave, each ticket drained that wave's stores and held the others at the barrier.
+    constexpr int kStreamThreads = 256 - kWave;
+    const bool last_wave = threadIdx.x >= kStreamThreads;
     if (kind == 3) {
         // ---- D: row 0's vehicle groups streamed into row ranges | the advanced vehicles, 64 rows to a group | rows whose
         //      tf is not tf[0] (a finite-difference row of tf itself), eight rows to a workgroup, in full
@@ -1096,6 +1167,19 @@ __global__ __launch_bounds__(256, WPC) void k_step_fd_structured(const Structure
         const int t = id, c = t % sp.gjk_chunks, r = t / sp.gjk_chunks;
         const int cp = sp.gjk_chunk_pairs;
         const int k0 = c * cp, n_valid = max(0, min(cp, p.n_pairs - k0));
+        // ranges [0, gjk_static_ranges) own rows of [0, gjk_static_rows); the workgroups behind them are the chunk's sweepers
+        const bool sweeper = dyn_rows && r >= sp.gjk_static_ranges;
+        const bool dispatcher = sweeper && last_wave;
+        const int n_stream = sweeper ? kStreamThreads : 256;
+        const int n_swept = p.B - sp.gjk_static_rows;                // rows the chunk's counter hands out
+        int* const counter = sweeper ? sp.tickets + sp.n_sep_groups + c : nullptr;
+        if (sweeper) {
+            // a sweeper that finds its chunk's rows gone leaves before it evaluates anything (one look for the whole
+            // workgroup: its waves must agree)
+            if (dispatcher) s_ticket[0] = __hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __syncthreads();
+            if (s_ticket[0] >= n_swept) return;
+        }
         // results in LDS behind the body's own arrays
         char* base = reinterpret_cast<char*>(xy_dyn) + ((planar_lds_bytes<0>(n_obj, VPQ, cp) + 15) / 16) * 16;
         double* r_p1 = reinterpret_cast<double*>(base);
@@ -1111,35 +1195,66 @@ __global__ __launch_bounds__(256, WPC) void k_step_fd_structured(const Structure
         q.status = r_stat - k0; q.nsup = r_nsup - k0;
         gjk_planar_body<NC, 0, false>(q, xy_dyn, 0, c);
         __syncthreads();
-        const int b0 = r * sp.gjk_rows_per, b1 = min(p.B, b0 + sp.gjk_rows_per);
-        // every thread streams one pair into every n_sub-th row of the range
-        const int n_sub = max(1, (int)blockDim.x / max(n_valid, 1));
-        for (int t = (int)threadIdx.x; t < n_valid * n_sub; t += (int)blockDim.x) {
-            const int l = t % n_valid, sub = t / n_valid;
-            const int kq = k0 + l;
-            const int a = p.pa[kq], bb = p.pb[kq];
-            const int fl = r_flag[l], st = r_stat[l], ns = r_nsup[l];
-            const double di = r_dist[l];
-            const double p1x = r_p1[3 * l], p1y = r_p1[3 * l + 1], p1z = r_p1[3 * l + 2];
-            const double p2x = r_p2[3 * l], p2y = r_p2[3 * l + 1], p2z = r_p2[3 * l + 2];
-            for (int b = b0 + sub; b < b1; b += n_sub) {
-                const int fd_e = fd_element(p.fd, p.fd_fixed, NC, b);
-                const int vb = fd_e >= 0 ? fd_e / (2 * NC) : -1;
-                if (a == vb || bb == vb) continue;                   // row b's own workgroup evaluates this pair
-                const size_t o = (size_t)b * p.n_pairs + kq;
-                p.flag[o] = fl;
-                p.p1[3 * o] = p1x; p.p1[3 * o + 1] = p1y; p.p1[3 * o + 2] = p1z;
-                p.p2[3 * o] = p2x; p.p2[3 * o + 1] = p2y; p.p2[3 * o + 2] = p2z;
-                p.dist[o] = di;
-                if (p.nsup) p.nsup[o] = ns;
-                if (p.status) p.status[o] = st;
+        // every streaming thread streams one pair into every n_sub-th row of rows [bs, be)
+        const int n_sub = max(1, n_stream / max(n_valid, 1));
+        auto stream_rows = [&](int bs, int be) {
+            for (int t = (int)threadIdx.x; t < n_valid * n_sub; t += n_stream) {
+                const int l = t % n_valid, sub = t / n_valid;
+                const int kq = k0 + l;
+                const int a = p.pa[kq], bb = p.pb[kq];
+                const int fl = r_flag[l], st = r_stat[l], ns = r_nsup[l];
+                const double di = r_dist[l];
+                const double p1x = r_p1[3 * l], p1y = r_p1[3 * l + 1], p1z = r_p1[3 * l + 2];
+                const double p2x = r_p2[3 * l], p2y = r_p2[3 * l + 1], p2z = r_p2[3 * l + 2];
+                for (int b = bs + sub; b < be; b += n_sub) {
+                    const int fd_e = fd_element(p.fd, p.fd_fixed, NC, b);
+                    const int vb = fd_e >= 0 ? fd_e / (2 * NC) : -1;
+                    if (a == vb || bb == vb) continue;                   // row b's own workgroup evaluates this pair
+                    const size_t o = (size_t)b * p.n_pairs + kq;
+                    p.flag[o] = fl;
+                    p.p1[3 * o] = p1x; p.p1[3 * o + 1] = p1y; p.p1[3 * o + 2] = p1z;
+                    p.p2[3 * o] = p2x; p.p2[3 * o + 1] = p2y; p.p2[3 * o + 2] = p2z;
+                    p.dist[o] = di;
+                    if (p.nsup) p.nsup[o] = ns;
+                    if (p.status) p.status[o] = st;
+                }
             }
+        };
+        if (!sweeper) {
+            const int b0 = r * sp.gjk_rows_per;
+            stream_rows(b0, min(sp.gjk_static_rows, b0 + sp.gjk_rows_per));
+            return;
+        }
+        // tickets: the dispatcher wave draws, the workgroup reads the row from LDS behind a barrier.  The next ticket is
+        // drawn while the current one is written, so that the counter's round trip runs under the stores.
+        const int tr = sp.gjk_ticket_rows;
+        int par = 1;
+        if (dispatcher) {
+            s_ticket[1] = draw_rows(counter, tr);
+        }
+        __syncthreads();
+        for (int cur = s_ticket[1]; cur < n_swept; cur = s_ticket[par]) {
+            par ^= 1;
+            if (dispatcher) s_ticket[par] = draw_rows(counter, tr);
+            else stream_rows(sp.gjk_static_rows + cur, sp.gjk_static_rows + min(n_swept, cur + tr));
+            __syncthreads();
         }
         return;
     }
     // ---- S: group g of row 0's separation block, streamed into the rows of range r
     {
         const int g = id % sp.n_sep_groups, r = id / sp.n_sep_groups;
+        // ranges [0, sep_static_ranges) own rows of [0, sep_static_rows); the workgroups behind them are the group's sweepers
+        const bool sweeper = dyn_rows && r >= sp.sep_static_ranges;
+        const bool dispatcher = sweeper && last_wave;
+        const int n_swept = p.B - sp.sep_static_rows;                // rows the group's counter hands out
+        int* const counter = sweeper ? sp.tickets + g : nullptr;
+        if (sweeper) {
+            // the sweeper's first ticket, before it stages anything: one that finds its group's rows gone leaves here
+            if (dispatcher) s_ticket[0] = draw_rows(counter, sp.sep_ticket_rows);
+            __syncthreads();
+            if (s_ticket[0] >= n_swept) return;
+        }
         for (int e = threadIdx.x; e < p.n_veh * 2 * NC; e += blockDim.x) {
             const int v = e / (2 * NC), rr = e - v * (2 * NC), qd = rr / NC, k = rr - qd * NC;
             lds[2 * (v * VPQ + k) + qd] = p.Y[e];
@@ -1169,33 +1284,26 @@ __global__ __launch_bounds__(256, WPC) void k_step_fd_structured(const Structure
         }
         __syncthreads();
         const int n_el = s_nv * L;                                   // doubles in the run
-        constexpr int kSlots = (kWave * L / 2 + 255) / 256;          // 16-byte pieces per thread
-        double v0[kSlots], v1[kSlots];
-        int pr0[kSlots], pr1[kSlots];                                // (i | j << 16) of the pair each element belongs to, -1: none
-#pragma unroll
-        for (int s = 0; s < kSlots; ++s) {
-            const int m = (int)threadIdx.x + 256 * s, e0 = 2 * m, e1 = e0 + 1;
-            v0[s] = v1[s] = 0.0; pr0[s] = pr1[s] = -1;
-            if (e0 < n_el) { pr0[s] = (int)s_gpair[e0 / L]; v0[s] = tile[e0]; }
-            if (e1 < n_el) { pr1[s] = (int)s_gpair[e1 / L]; v1[s] = tile[e1]; }
+        if (!sweeper) {
+            SepRun<NC, 256> run;
+            run.load(tile, s_gpair, n_el);
+            const int b0 = r * sp.sep_rows_per, b1 = min(sp.sep_static_rows, b0 + sp.sep_rows_per);
+            for (int b = b0; b < b1; ++b) run.write_row(p, g, b);
+            return;
         }
-        const int b0 = r * sp.sep_rows_per, b1 = min(p.B, b0 + sp.sep_rows_per);
-        for (int b = b0; b < b1; ++b) {
-            const int fd_e = fd_element(p.fd, p.fd_fixed, NC, b);
-            const int vb = fd_e >= 0 ? fd_e / (2 * NC) : -1;
-            const size_t ob = ((size_t)b * p.ts.n_pairs + (size_t)g * kWave) * L;
-            double* o = p.ts.out + ob;
-            const bool aligned = (ob & 1) == 0;                     // rows of an odd length start on odd elements
-#pragma unroll
-            for (int s = 0; s < kSlots; ++s) {
-                const int m = (int)threadIdx.x + 256 * s;
-                const bool w0 = pr0[s] >= 0 && (pr0[s] & 0xffff) != vb && (pr0[s] >> 16) != vb;
-                const bool w1 = pr1[s] >= 0 && (pr1[s] & 0xffff) != vb && (pr1[s] >> 16) != vb;
-                if (w0 && w1 && aligned) store_nt2(o + 2 * m, v0[s], v1[s]);
-                else if (w0 && w1) { store_nt(o + 2 * m, v0[s]); store_nt(o + 2 * m + 1, v1[s]); }
-                else if (w0) store_nt(o + 2 * m, v0[s]);
-                else if (w1) store_nt(o + 2 * m + 1, v1[s]);
+        // tickets, as in the G kind: the next one is drawn while the current one is written
+        SepRun<NC, kStreamThreads> run;
+        run.load(tile, s_gpair, n_el);
+        const int tr = sp.sep_ticket_rows;
+        int par = 0;
+        for (int cur = s_ticket[0]; cur < n_swept; cur = s_ticket[par]) {
+            par ^= 1;
+            if (dispatcher) s_ticket[par] = draw_rows(counter, tr);
+            else {
+                const int be = sp.sep_static_rows + min(n_swept, cur + tr);
+                for (int b = sp.sep_static_rows + cur; b < be; ++b) run.write_row(p, g, b);
             }
+            __syncthreads();
         }
     }
 }
@@ -3938,11 +4046,17 @@ bool constraint_sweep_is_one_launch(obtg_ctx* c, int B)
 // Which shapes k_step_fd_structured covers, decided without launching anything: the launcher and the router of
 // obtg_constraint_sweep_dev (capi.cpp) share it, as they share pair_sweep_plan above.  OBTG_ERR_UNSUPPORTED: not this
 // shape (3-D, degree 20, obtg_ctx_set_ang_rate_order(2) with DEG_ELEV > 0, de-duplication on, rows beyond 158 KB of LDS).
+// rows at run time: the default share of a group's rows, in per cent, that its sweepers write (launch_step_fd_structured).
+// C3, short runs on one box, parent 0.1009 ms: S 10 / 20 / 30 / 40 / 50 / 60 / 70 % swept 0.0988 / 0.1030 / 0.1041 / 0.1077 /
+// 0.1105 / 0.1149 / 0.1259 ms -- a chip full of sweepers alone stores at 5.7 TB/s, under the 6.3 of the mixed launch, so they
+// get what fills the tail and no more; G sweepers on top cost more (20,20: 0.1144; 30,30: 0.1161 against 0.1041)
+constexpr int kStructSweptShareSep = 10, kStructSweptShareGjk = 0;
 struct StructuredPlan {
     void (*kern)(const StructuredParams) = nullptr;
     size_t lds = 0;
     int gjk_chunk_pairs = 80;
     bool dyn_split = false;
+    int wpc = 4;                       // workgroups per CU of `kern` (its WPC)
 };
 static int step_fd_structured_plan(obtg_ctx* c, StructuredPlan& pl)
 {
@@ -3999,10 +4113,10 @@ static int step_fd_structured_plan(obtg_ctx* c, StructuredPlan& pl)
     const size_t lds = std::max(std::max(lds_s, lds_g), std::max(lds_f, elev ? lds_d_elev : lds_d));
     if (lds > (elev ? 76 : 40) * (size_t)1024) {
         const size_t with_static = lds + 1536;               // (the kernel's own __shared__ variables)
-        if (kern_mid && with_static <= 80 * (size_t)1024) kern = kern_mid;
-        else if (kern_big && with_static <= 158 * (size_t)1024) kern = kern_big;
+        if (kern_mid && with_static <= 80 * (size_t)1024) { kern = kern_mid; pl.wpc = 2; }
+        else if (kern_big && with_static <= 158 * (size_t)1024) { kern = kern_big; pl.wpc = 1; }
         else return OBTG_ERR_UNSUPPORTED;
-    }
+    } else pl.wpc = elev ? 2 : 4;
     pl.kern = kern; pl.lds = lds;
     return OBTG_OK;
 }
@@ -4113,25 +4227,73 @@ int launch_step_fd_structured(obtg_ctx* c, int B, double max_sep, double* d_out_
     // workgroups, B = 289 0.055 -> 0.040 with 1024 / 512; from B = 577 on the old numbers are the best)
     const double s_floor = std::min(2048.0, std::max(256.0, 3.5 * B));
     int s_target = (int)std::min(32768.0, std::max(s_floor, sep_stream_bytes / (4 << 20)));
-    if (const char* e = getenv("OBTG_STRUCT_SEP_WGS")) s_target = std::max(1, atoi(e));      // (experiments)
+    // G: chunks of ~80 hull pairs (one short gjkNew phase per workgroup), row ranges for ~512 workgroups
+    sp.gjk_chunk_pairs = pl.gjk_chunk_pairs;
+    sp.gjk_chunks = (c->n_hull_pairs + sp.gjk_chunk_pairs - 1) / sp.gjk_chunk_pairs;
+    // (rows at run time, below: with the sweepers on, the two worker-count knobs count sweepers, not fixed ranges)
+    const int slots = (c->n_cus > 0 ? c->n_cus : 256) * pl.wpc;
+    const char* e_dyn = getenv("OBTG_STRUCT_DYNAMIC_ROWS");
+    const bool dyn_rows = !elev && (e_dyn && e_dyn[0] ? e_dyn[0] != '0' : 2 * (sp.n_sep_groups + sp.gjk_chunks) <= slots);
+    const char* e_sep_wgs = getenv("OBTG_STRUCT_SEP_WGS");      // (experiments)
+    const char* e_gjk_wgs = getenv("OBTG_STRUCT_GJK_WGS");
+    if (e_sep_wgs && !dyn_rows) s_target = std::max(1, atoi(e_sep_wgs));
+    const int g_target = e_gjk_wgs && !dyn_rows ? std::max(1, atoi(e_gjk_wgs)) : (int)std::min(1024.0, std::max(192.0, 2.6 * B));
+    int g_target_b = (int)std::min(32768.0, std::max((double)g_target, 68.0 * c->n_hull_pairs * (double)B / (4 << 20)));
     int s_ranges = std::max(1, std::min(B, s_target / std::max(1, sp.n_sep_groups)));
     sp.sep_rows_per = (B + s_ranges - 1) / s_ranges;
     s_ranges = (B + sp.sep_rows_per - 1) / sp.sep_rows_per;
-    // G: chunks of ~80 hull pairs (one short gjkNew phase per workgroup), row ranges for ~512 workgroups
-    sp.gjk_chunk_pairs = pl.gjk_chunk_pairs;
-    const int g_target = getenv("OBTG_STRUCT_GJK_WGS") ? std::max(1, atoi(getenv("OBTG_STRUCT_GJK_WGS")))
-                                                       : (int)std::min(1024.0, std::max(192.0, 2.6 * B));
-    sp.gjk_chunks = (c->n_hull_pairs + sp.gjk_chunk_pairs - 1) / sp.gjk_chunk_pairs;
-    const int g_target_b = (int)std::min(32768.0, std::max((double)g_target, 68.0 * c->n_hull_pairs * (double)B / (4 << 20)));
     int g_ranges = std::max(1, std::min(B, g_target_b / std::max(1, sp.gjk_chunks)));
     sp.gjk_rows_per = (B + g_ranges - 1) / g_ranges;
     g_ranges = (B + sp.gjk_rows_per - 1) / sp.gjk_rows_per;
+    sp.sep_static_ranges = s_ranges; sp.gjk_static_ranges = g_ranges;
+    sp.sep_static_rows = sp.gjk_static_rows = B;
+    // Rows at run time (flat steps).  With fixed ranges alone the launch has a tail: whichever workgroup is dispatched last
+    // still has its whole range to write, and for the last tenth of the span most slots are empty
+    // (profiles/struct_dynamic_rows/timeline_parent_c3.txt).  So only the first rows of every group go to fixed ranges, of the
+    // usual length; the rest are handed out by ticket (StructuredParams::tickets) to SWEEPERS, whose block ids come behind
+    // every other id of the grid: they start in the slots the draining launch leaves empty, share what is left down to a
+    // ticket and end together.  A sweeper stays until its group's rows are gone, which is why they are not mixed in
+    // earlier: S and G workers that draw ALL rows by ticket crowd the F and D workgroups out of the slots.
+    // With more groups than half the slots (C4: 510 groups on 256 or 512 slots) the fixed ranges stay alone.
+    // OBTG_STRUCT_DYNAMIC_ROWS=0 / 1: fixed ranges alone / sweepers whatever the shape (read per call: A/B runs and tests).
+    int s_sweep = 0, g_sweep = 0;                          // sweepers per group / per chunk
+    if (dyn_rows) {
+        // a ticket of 40 - 48 KB (C3: 4 rows of a separation group, 9 of a chunk): about 3 us of a sweeper's stores
+        sp.sep_ticket_rows = std::max(2, (48 << 10) / (8 * kWave * L));
+        sp.gjk_ticket_rows = std::max(2, (48 << 10) / (68 * sp.gjk_chunk_pairs));
+        if (const char* e = getenv("OBTG_STRUCT_TICKET_ROWS")) {      // S rows per ticket; G tickets are twice as many rows (half as wide)
+            sp.sep_ticket_rows = std::max(1, atoi(e));
+            sp.gjk_ticket_rows = 2 * sp.sep_ticket_rows;
+        }
+        // the share of a group's rows that is swept, in per cent ("S,G"; 100: no fixed ranges at all)
+        int share[2] = { kStructSweptShareSep, kStructSweptShareGjk };
+        if (const char* e = getenv("OBTG_STRUCT_DYNAMIC_SHARE")) {
+            if (sscanf(e, "%d,%d", &share[0], &share[1]) < 2) share[1] = share[0];
+            for (int& v : share) v = std::max(0, std::min(100, v));
+        }
+        // (whole ranges: a fixed range is as long as without sweepers)
+        sp.sep_static_rows = B - (int)((long long)B * share[0] / 100);
+        sp.sep_static_rows -= sp.sep_static_rows % sp.sep_rows_per;
+        sp.gjk_static_rows = B - (int)((long long)B * share[1] / 100);
+        sp.gjk_static_rows -= sp.gjk_static_rows % sp.gjk_rows_per;
+        sp.sep_static_ranges = sp.sep_static_rows / sp.sep_rows_per;
+        sp.gjk_static_ranges = sp.gjk_static_rows / sp.gjk_rows_per;
+        // sweepers: a chip's worth of S, half of one of G; no more than tickets, unless the count was asked for (with the
+        // tickets on, OBTG_STRUCT_SEP_WGS / OBTG_STRUCT_GJK_WGS count the sweepers of all groups together)
+        const int s_swept = B - sp.sep_static_rows, g_swept = B - sp.gjk_static_rows;
+        if (s_swept > 0)
+            s_sweep = e_sep_wgs ? std::max(1, atoi(e_sep_wgs) / std::max(1, sp.n_sep_groups))
+                                : std::max(1, std::min(slots / std::max(1, sp.n_sep_groups), (s_swept + sp.sep_ticket_rows - 1) / sp.sep_ticket_rows));
+        if (g_swept > 0)
+            g_sweep = e_gjk_wgs ? std::max(1, atoi(e_gjk_wgs) / std::max(1, sp.gjk_chunks))
+                                : std::max(1, std::min(slots / 2 / std::max(1, sp.gjk_chunks), (g_swept + sp.gjk_ticket_rows - 1) / sp.gjk_ticket_rows));
+    }
     sp.fix_chunk = 256;
     p.vp_off = c->d_vp_off.as<int>(); p.vp_idx = c->d_vp_idx.as<int>();
-    sp.n_kind[0] = sp.n_sep_groups * s_ranges;
+    sp.n_kind[0] = sp.n_sep_groups * (sp.sep_static_ranges + s_sweep);
     sp.first_pert = c->fd.row0 > 0 ? 0 : 1;            // (a range that starts later: its local row 0 is a perturbed row too)
     sp.n_kind[1] = B - sp.first_pert;
-    sp.n_kind[2] = sp.gjk_chunks * g_ranges;
+    sp.n_kind[2] = sp.gjk_chunks * (sp.gjk_static_ranges + g_sweep);
     // D: ~256 streams of row 0's groups (at most 64 rows each, at least 4 when there are that many: at C5 a stream of 19
     // rows keeps its workgroup for 430 us of a 650 us launch, one of 5 rows for 190), the advanced vehicles 64 to a
     // group, and one workgroup per 8 rows that looks for rows with their own tf
@@ -4152,7 +4314,10 @@ int launch_step_fd_structured(obtg_ctx* c, int B, double max_sep, double* d_out_
         const double cost_flat[4] = { 12.5, 15.2, 20.2, 16.0 }, cost_elev[4] = { 40.0, 36.0, 38.0, 40.0 };
         const double* cost = elev ? cost_elev : cost_flat;     // (DEG_ELEV > 0: the streams are 2n+R+1 columns wide, the dynamics groups k_dynamics_elev's)
         double w[4], tot = 0.0;
-        for (int k = 0; k < 4; ++k) { w[k] = sp.n_kind[k] * cost[k]; tot += w[k]; }
+        // (the sweepers are left out: the shares make the fixed ranges, F, G and D run out of ids together, and the sweepers'
+        // ids follow)
+        const int n_fixed[4] = { sp.n_sep_groups * sp.sep_static_ranges, sp.n_kind[1], sp.gjk_chunks * sp.gjk_static_ranges, sp.n_kind[3] };
+        for (int k = 0; k < 4; ++k) { w[k] = n_fixed[k] * cost[k]; tot += w[k]; }
         tot -= w[3];
         w[3] = (sp.dyn_streams + sp.dyn_fix_groups) * cost[3];      // (the workgroups that look for rows with their own tf come last and cost nothing)
         tot += w[3];
@@ -4187,6 +4352,24 @@ int launch_step_fd_structured(obtg_ctx* c, int B, double max_sep, double* d_out_
     p.dyn_first_block = 0;
     const size_t lds = pl.lds;
     OBTG_HIP(c, allow_lds(kern, lds));
+    if (dyn_rows) {
+        // this launch's bank of ticket counters (obtg_ctx::d_struct_tickets).  Nothing is queued for it on the step's path:
+        // the previous launch left it zero.  Only a layout the banks have not seen (another pair list, more groups than
+        // the banks hold) zeroes them here.
+        const int n_counters = sp.n_sep_groups + sp.gjk_chunks;
+        const bool grow = n_counters > c->struct_ticket_stride;
+        if (grow || sp.n_sep_groups != c->struct_ticket_layout[0] || sp.gjk_chunks != c->struct_ticket_layout[1]) {
+            if (grow) {
+                if (int rc = c->d_struct_tickets.reserve(sizeof(int) * 2 * (size_t)(n_counters + 64))) return rc;
+                c->struct_ticket_stride = n_counters + 64;
+            }
+            OBTG_HIP(c, hipMemsetAsync(c->d_struct_tickets.p, 0, sizeof(int) * 2 * (size_t)c->struct_ticket_stride, c->stream));
+            c->struct_ticket_bank = 0;
+            c->struct_ticket_layout[0] = sp.n_sep_groups; c->struct_ticket_layout[1] = sp.gjk_chunks;
+        }
+        sp.tickets = c->d_struct_tickets.as<int>() + (size_t)c->struct_ticket_bank * c->struct_ticket_stride;
+        sp.tickets_idle = c->d_struct_tickets.as<int>() + (size_t)(c->struct_ticket_bank ^ 1) * c->struct_ticket_stride;
+    }
     TimelineDump tl(c, grid, p.timeline);
     if (tl.rc) return tl.rc;
     {
@@ -4194,11 +4377,12 @@ int launch_step_fd_structured(obtg_ctx* c, int B, double max_sep, double* d_out_
         launch_timed(tm, kern, dim3(grid), dim3(256), lds, c->stream, sp);
     }
     OBTG_HIP(c, hipGetLastError());
+    if (dyn_rows) c->struct_ticket_bank ^= 1;      // (the launch is on the stream: it leaves the other bank zero)
     char hdr[256];
-    snprintf(hdr, sizeof hdr, "# grid %u structured n_S %d n_F %d n_G %d n_D %d per16 %d %d %d %d pat %d%d%d%d%d%d%d%d%d%d%d%d%d%d%d%d B %d",
+    snprintf(hdr, sizeof hdr, "# grid %u structured n_S %d n_F %d n_G %d n_D %d per16 %d %d %d %d pat %d%d%d%d%d%d%d%d%d%d%d%d%d%d%d%d B %d ticket_rows %d %d",
              grid, sp.n_kind[0], sp.n_kind[1], sp.n_kind[2], sp.n_kind[3], sp.per16[0], sp.per16[1], sp.per16[2], sp.per16[3],
              sp.pat[0], sp.pat[1], sp.pat[2], sp.pat[3], sp.pat[4], sp.pat[5], sp.pat[6], sp.pat[7], sp.pat[8], sp.pat[9], sp.pat[10],
-             sp.pat[11], sp.pat[12], sp.pat[13], sp.pat[14], sp.pat[15], B);
+             sp.pat[11], sp.pat[12], sp.pat[13], sp.pat[14], sp.pat[15], B, dyn_rows ? sp.sep_ticket_rows : 0, dyn_rows ? sp.gjk_ticket_rows : 0);
     return tl.finish(hdr);
 }
 

@@ -179,6 +179,13 @@ struct obtg_ctx {
     bool fd_view_structured = true;   // obtg_ctx_set_fd_view_structured: the one-call sweep of a view takes the structured step where it applies
     obtg::DevBuf d_hp_a, d_hp_b;  // hull pair list
     obtg::DevBuf d_vp_off, d_vp_idx;   // per vehicle: the positions of the hull pairs that contain it (CSR; structured FD step)
+    // Structured FD step, rows handed out at run time (gjk_kernels.hip StructuredParams::tickets): two banks of
+    // struct_ticket_stride counters, one per separation group and then one per hull-pair chunk.  Both are zero at creation;
+    // a launch draws from bank struct_ticket_bank and zeroes the other, which the next launch draws from -- the bank
+    // changes only once a launch is on the stream, so a call that failed before that leaves the next one a zero bank.
+    // struct_ticket_layout: (groups, chunks) of the last launch; another layout zeroes both banks first.
+    obtg::DevBuf d_struct_tickets;
+    int struct_ticket_bank = 0, struct_ticket_stride = 0, struct_ticket_layout[2] = { 0, 0 };
     std::vector<int> h_hp_a, h_hp_b;   // host copy (tile-major chunking of large rows)
     obtg::DevBuf d_tile_chunk_off, d_tile_order, d_tile_pslots, d_tile_cobj_off, d_tile_cobjs, d_tile_ij;
     bool tile_ts_ok = false;  // every chunk's tile origin is recorded and the hull pair list holds every vehicle pair: the tiled

@@ -107,7 +107,10 @@ const char* obtg_strerror(int code);
  *      have sized their arrays by it; OBTG_K_END = 10 is the end of the ids obtg_kernel_stats answers for.
  *      Later, still 7: new: the curvature-bound rows obtg_curvature_true_min[_dev], their envelope Jacobian
  *      obtg_curvature_true_min_jac[_dev], their polynomials obtg_curvature_poly[_dev] and the curvature range of free curves
- *      obtg_bern_curvature[_dev] (timed under OBTG_K_ANG_RATE; no kernel id added). */
+ *      obtg_bern_curvature[_dev] (timed under OBTG_K_ANG_RATE; no kernel id added).
+ *      Later, still 7: new: the space-curvature rows of 3-D vehicles obtg_space_curvature_true_min[_dev], their envelope Jacobian
+ *      obtg_space_curvature_true_min_jac[_dev], their polynomials obtg_space_curvature_poly[_dev] and the largest curvature of
+ *      free space curves obtg_bern_space_curvature[_dev] (timed under OBTG_K_ANG_RATE; no kernel id added). */
 #define OBTG_ABI_VERSION 7
 int obtg_abi_version(void);
 
@@ -778,6 +781,72 @@ int obtg_bern_curvature(obtg_ctx*, const double* c /*[M][2][K]*/, int M, int K, 
                         int* status /*[M][2], nullable*/);
 int obtg_bern_curvature_dev(obtg_ctx*, const double* d_c, int M, int K, double eps_rel, int max_nodes, double* d_k_min,
                             double* d_t_min, double* d_k_max, double* d_t_max, int* d_status);
+/* The space-curvature bound (dim 3): kappa <= max_curv on the whole path of a vehicle in space, a minimum turning radius of
+ * 1 / max_curv.  With c' and c'' (each the derivative followed by elev(1), degree n) formed on T = 1 -- no entry point takes
+ * tf --, w = c' x c'' and den = |c'|^2 are four polynomials of 2n+1 Bernstein coefficients: the components of w are
+ * obtg_curvature_poly's num on the coordinate pairs (y, z), (z, x), (x, y) (csrc/bern_device.h curvature_row_coeff), den_k is
+ * the sum over j in index order of fma(x'_j, x'_(k-j), .), fma(y'_j, y'_(k-j), .), fma(z'_j, z'_(k-j), .) with the same
+ * weights (space_curvature_row_coeff).  kappa(t) = |w(t)| / (den(t) sqrt(den(t))) >= 0: the norm of a vector of polynomials,
+ * not a polynomial and without a sign.  One row per vehicle, no sides, no clamp:
+ *     m = max over t in [0, 1] of kappa(t),      row = max_curv - m,
+ * a vehicle respects the bound iff its row is >= 0.  The family is meant for trajectories that do not stop.
+ * obtg_space_curvature_poly: out[B][N][4][2n+1]: wx_k, wy_k, wz_k, den_k.
+ * obtg_space_curvature_true_min: out[B][N] = row, t_star[B][N], status[B][N].  A depth-first bisection at 1/2 over the four
+ *     polynomials at once (each de Casteljau level the same average 0.5 a + 0.5 b on all four), one wave per row.
+ *     Evaluation at a point: with (wx, wy, wz, den) the end coefficients of a sub-curve,
+ *         nu = sqrt(fma(wz, wz, fma(wy, wy, wx wx))),    kappa = nu / (den sqrt(den))
+ *     in binary64, in this order; a point with den <= 0, or whose value is not finite, offers no value.
+ *     Incumbent U: starts at 0 (at t = 0); kappa(0), kappa(1) and every bisection midpoint update it.
+ *     Upper bound of a sub-curve: nu_k from (wx_k, wy_k, wz_k) as above, one per coefficient -- the norm is convex, so
+ *     |w(t)| <= sum nu_k B_k(t) --; d0 = 0.5 (min den_k + max den_k), g_k = fma(1.5 sqrt(d0), den_k, -0.5 (d0 sqrt(d0))), the
+ *     tangent of the convex den^(3/2) at d0, so den(t)^(3/2) >= sum g_k B_k(t); lambda g_k - nu_k >= 0 for EVERY k gives
+ *     kappa <= lambda.  So: 0 if every nu_k == 0; else +inf if min den_k <= 0 or g at min den_k is <= 0 (the speed varies too
+ *     much across the sub-curve for this tangent, and it is split further); else the largest nu_k / g_k.  Its excess over
+ *     the sub-curve's true maximum falls with the square of the width.
+ *     A sub-curve is closed when bound - U <= tol, tol = eps_rel * max(max_curv, U) with U the incumbent at the time of the
+ *     test; of two open halves the one with the larger bound is followed, the other waits.
+ *     With OBTG_MD_OK: m is kappa(t_star) as evaluated above, t_star a bisection point in [0, 1], and nothing on [0, 1]
+ *     exceeds m + tol up to the rounding of the bound.  OBTG_MD_NODE_CAP: max_nodes sub-curves examined; OBTG_MD_DEPTH_CAP:
+ *     more than 32 sub-curves waiting; m is then still a value met (or 0).  Where den vanishes with w != 0 (a stop, a
+ *     cusp) the bound stays infinite and the search ends on a cap, never in a spin.  w == 0 identically (degree 1, a
+ *     straight path, a vehicle at rest): row = max_curv exactly, t_star = 0, OBTG_MD_OK from the first step.  A row with a
+ *     non-finite coefficient: out and t_star NaN, OBTG_MD_OK.
+ *     A row's result depends on its control points, max_curv, eps_rel and max_nodes alone: not on B, its position, the
+ *     launch form, or host versus _dev.
+ * obtg_space_curvature_true_min_jac: the same out, t_star, status bit for bit, and jac[B][N][3][n+1], the derivative of the row
+ *     with respect to the vehicle's own control points at t_star.  With A_i, C_i obtg_curvature_true_min_jac's, v = c'(t_star),
+ *     a = c''(t_star), w = v x a, wh = w / |w|, den = |v|^2:
+ *         jac[d][i] = -[ (A_i (a x wh)_d + C_i (wh x v)_d) / den^(3/2) - 3 |w| v_d A_i / den^(5/2) ]
+ *     (csrc/bern_device.h space_curvature_envelope_block states every operation; every multiply-add an explicit fma: host and
+ *     _dev, fused and two-launch forms give the same bits).  With wh = e_z this is obtg_curvature_true_min_jac's block.  The
+ *     block is zero where the returned row IS max_curv, NaN for a NaN row; with a cap status it is still the derivative at
+ *     the returned t_star.  There is no jac_tf: it is identically 0.
+ * Checks: a context whose dim is not 3, degrees above 31: OBTG_ERR_UNSUPPORTED; t_star and status nullable; B == 0 is OBTG_OK.
+ * Control-point counts 4, 6, 8, 9, 11, 16 form the coefficients in registers, one launch (with the blocks too, unless the
+ * context was created under OBTG_TRUE_MIN_JAC_FUSED=0: then one more launch); other degrees from 1 to 31 go through a
+ * workspace of obtg_space_curvature_poly's rows (two launches, three with blocks).  Every launch is timed under
+ * OBTG_K_ANG_RATE.  _dev: dY may be NULL inside an obtg_fd_view. */
+int obtg_space_curvature_poly(obtg_ctx*, const double* Y, int B, double* out /*[B][N][4][2n+1]*/);
+int obtg_space_curvature_poly_dev(obtg_ctx*, const double* dY, int B, double* d_out);
+int obtg_space_curvature_true_min(obtg_ctx*, const double* Y, int B, double max_curv, double eps_rel, int max_nodes,
+                                  double* out /*[B][N]*/, double* t_star /*[B][N], nullable*/, int* status /*[B][N], nullable*/);
+int obtg_space_curvature_true_min_dev(obtg_ctx*, const double* dY, int B, double max_curv, double eps_rel, int max_nodes,
+                                      double* d_out, double* d_t_star, int* d_status);
+int obtg_space_curvature_true_min_jac(obtg_ctx*, const double* Y, int B, double max_curv, double eps_rel, int max_nodes,
+                                      double* out /*[B][N]*/, double* t_star /*nullable*/, int* status /*nullable*/,
+                                      double* jac /*[B][N][3][n+1]*/);
+int obtg_space_curvature_true_min_jac_dev(obtg_ctx*, const double* dY, int B, double max_curv, double eps_rel, int max_nodes,
+                                          double* d_out, double* d_t_star, int* d_status, double* d_jac);
+/* The largest curvature of M free space curves c[M][3][K] (x, y, z rows; 2 <= K <= 32 control points, whatever the context's
+ * shape and dimension are; K > 32: OBTG_ERR_UNSUPPORTED): the search above with max_curv = 0 (tol = eps_rel U):
+ *     k_max[M] = max kappa at t_max[M],    status[M].
+ * w == 0 identically: 0 at t = 0.  A curve with a non-finite coefficient: NaN, OBTG_MD_OK.  Points with den <= 0 offer no
+ * value; a curve on which none does ends on a cap with k_max = 0.
+ * status is nullable.  M == 0 is OBTG_OK.  Two launches, timed under OBTG_K_ANG_RATE. */
+int obtg_bern_space_curvature(obtg_ctx*, const double* c /*[M][3][K]*/, int M, int K, double eps_rel, int max_nodes,
+                              double* k_max /*[M]*/, double* t_max /*[M]*/, int* status /*[M], nullable*/);
+int obtg_bern_space_curvature_dev(obtg_ctx*, const double* d_c, int M, int K, double eps_rel, int max_nodes, double* d_k_max,
+                                  double* d_t_max, int* d_status);
 
 /* ---- the acceleration bound: |d^2 c / dtime^2| <= bound for every vehicle, in 2-D, 3-D and any other dimension ----
  * For vehicle v with control points P[c][i] (c < d, i <= n) on a span T = tf[b]:

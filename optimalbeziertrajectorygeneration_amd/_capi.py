@@ -133,6 +133,14 @@ _SIGNATURES = {
     "obtg_curvature_true_min_jac_dev": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp]),
     "obtg_bern_curvature": (_i, [_vp, _vp, _i, _i, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "obtg_bern_curvature_dev": (_i, [_vp, _vp, _i, _i, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_space_curvature_poly": (_i, [_vp, _vp, _i, _vp]),
+    "obtg_space_curvature_poly_dev": (_i, [_vp, _vp, _i, _vp]),
+    "obtg_space_curvature_true_min": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
+    "obtg_space_curvature_true_min_dev": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
+    "obtg_space_curvature_true_min_jac": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp]),
+    "obtg_space_curvature_true_min_jac_dev": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp]),
+    "obtg_bern_space_curvature": (_i, [_vp, _vp, _i, _i, _d, _i, _vp, _vp, _vp]),
+    "obtg_bern_space_curvature_dev": (_i, [_vp, _vp, _i, _i, _d, _i, _vp, _vp, _vp]),
     "obtg_bern_elev": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "obtg_bern_diff": (_i, [_vp, _vp, _i, _i, _d, _vp]),
     "obtg_bern_mul": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
@@ -835,6 +843,56 @@ class Context(object):
     def bern_curvature_dev(self, d_c, M, K, d_k_min, d_t_min, d_k_max, d_t_max, d_status=None, eps_rel=1e-9, max_nodes=100000):
         self._check(self._lib.obtg_bern_curvature_dev(self._h, _vp(d_c), int(M), int(K), float(eps_rel), int(max_nodes), _vp(d_k_min),
                                                       _vp(d_t_min), _vp(d_k_max), _vp(d_t_max), _vp(d_status)), "obtg_bern_curvature_dev")
+
+    def space_curvature_poly(self, Y):
+        """The space-curvature rows' polynomials (obtg_space_curvature_poly; dim 3): [B][N][4][2 deg + 1], the Bernstein
+        coefficients of the three components of w = c' x c'' and then of den = |c'|^2 on a span of 1;
+        kappa = |w| / den^(3/2)."""
+        Y, B = self._rows(Y)
+        out = pinned_empty((B, self.n_veh, 4, 2 * self.deg + 1))
+        self._check(self._lib.obtg_space_curvature_poly(self._h, _ptr(Y), B, _ptr(out)), "obtg_space_curvature_poly")
+        return out
+
+    def space_curvature_poly_dev(self, dY, B, d_out):
+        self._check(self._lib.obtg_space_curvature_poly_dev(self._h, _vp(dY), int(B), _vp(d_out)), "obtg_space_curvature_poly_dev")
+
+    def space_curvature_true_min(self, Y, max_curv, eps_rel=1e-9, max_nodes=100000):
+        """Per vehicle max_curv - max over t in [0, 1] of kappa (obtg_space_curvature_true_min; dim 3; no time span enters):
+        dict(val[B][N], t_star[B][N], status[B][N] as MD_*); kappa <= max_curv on the whole path iff the value is >= 0."""
+        return self._true_min("obtg_space_curvature_true_min", self.n_veh, Y, None, (float(max_curv),), eps_rel, max_nodes)
+
+    def space_curvature_true_min_dev(self, dY, B, max_curv, d_out, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
+        self._true_min_dev("obtg_space_curvature_true_min_dev", (dY,), B, (float(max_curv),), eps_rel, max_nodes, d_out, d_t_star,
+                           d_status)
+
+    def space_curvature_true_min_jac(self, Y, max_curv, eps_rel=1e-9, max_nodes=100000):
+        """space_curvature_true_min with its envelope Jacobian (obtg_space_curvature_true_min_jac): dict(val, t_star, status --
+        the bits of space_curvature_true_min --, jac[B][N][3][deg+1]: d/d(the vehicle's own control points) of the row at
+        t_star; zero where the row is max_curv itself).  The rows do not depend on tf."""
+        return self._true_min("obtg_space_curvature_true_min_jac", self.n_veh, Y, None, (float(max_curv),), eps_rel, max_nodes, "jac")
+
+    def space_curvature_true_min_jac_dev(self, dY, B, max_curv, d_out, d_jac, d_t_star=None, d_status=None, eps_rel=1e-9,
+                                         max_nodes=100000):
+        self._true_min_dev("obtg_space_curvature_true_min_jac_dev", (dY,), B, (float(max_curv),), eps_rel, max_nodes, d_out,
+                           d_t_star, d_status, d_jac)
+
+    def bern_space_curvature(self, c, eps_rel=1e-9, max_nodes=100000):
+        """The largest curvature of free space curves c[M][3][K], 2 <= K <= 32 control points (obtg_bern_space_curvature):
+        dict(k_max[M], t_max[M], status[M])."""
+        c = _f64(c)
+        if c.ndim == 2:
+            c = c[None]
+        M, three, K = c.shape
+        if three != 3:
+            raise ValueError("bern_space_curvature needs space curves [M][3][K], got shape %r" % (c.shape,))
+        r = dict(k_max=np.empty(M), t_max=np.empty(M), status=np.zeros(M, np.int32))
+        self._check(self._lib.obtg_bern_space_curvature(self._h, _ptr(c), M, K, float(eps_rel), int(max_nodes),
+                                                        *[_ptr(a) for a in r.values()]), "obtg_bern_space_curvature")
+        return r
+
+    def bern_space_curvature_dev(self, d_c, M, K, d_k_max, d_t_max, d_status=None, eps_rel=1e-9, max_nodes=100000):
+        self._check(self._lib.obtg_bern_space_curvature_dev(self._h, _vp(d_c), int(M), int(K), float(eps_rel), int(max_nodes),
+                                                            _vp(d_k_max), _vp(d_t_max), _vp(d_status)), "obtg_bern_space_curvature_dev")
 
     def ang_rate(self, Y, tf, max_rate):
         return self._vehicle_rows("obtg_ang_rate", Y, tf, (float(max_rate),), (self.len_ang_rate,))

@@ -246,6 +246,18 @@ class Bezier(BezierParams):
             _raise_md(r['status'][0][side], 'curvatureRange')
         return float(r['k_min'][0]), float(r['t_min'][0]), float(r['k_max'][0]), float(r['t_max'][0])
 
+    def spaceCurvatureMax(self, eps=1e-9, max_nodes=100000):
+        """(k_max, t_max): the largest curvature |c' x c''| / |c'|^3 of a curve in space and the parameter in [0, 1] where it
+        is reached, within eps x k_max of the true maximum (obtg_bern_space_curvature: a certified bisection on the device); a
+        search that does not end within max_nodes sub-curves -- a cusp, a stop -- raises as minDist does.  Curvature does
+        not depend on t0 or tf.  Not in the reference."""
+        if self.dim != 3:
+            raise ValueError('The input curve must be three dimensional,\n'
+                             'instead it is {} dimensional'.format(self.dim))
+        r = _ctx().bern_space_curvature(self.cpts, eps_rel=float(eps), max_nodes=int(max_nodes))
+        _raise_md(r['status'][0], 'spaceCurvatureMax')
+        return float(r['k_max'][0]), float(r['t_max'][0])
+
     def split(self, tDiv):
         """Two curves, before and after tDiv (bezier.py:533-572): de Casteljau at (tDiv - t0)/(tf - t0); the
         pieces keep the original span's ends, [t0, tDiv] and [tDiv, tf]."""

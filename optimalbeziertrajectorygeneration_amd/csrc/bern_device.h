@@ -627,6 +627,113 @@ __device__ __forceinline__ void curvature_envelope_block(const double* __restric
         }
 }
 
+// ---- The space-curvature rows (obtg_space_curvature_poly, obtg_space_curvature_true_min[_jac], obtg_bern_space_curvature;
+// dim 3).  kappa(t) = |w(t)| / den(t)^(3/2) with w = c' x c'' and den = |c'|^2 formed on T = 1.  Coefficient k of the three
+// components of w is curvature_row_coeff's num on the coordinate pairs (y, z), (z, x), (x, y) -- its fma sequence and
+// weights --; coefficient k of den is the sum in index order of fma(x'_j, x'_(k-j), .), fma(y'_j, y'_(k-j), .),
+// fma(z'_j, z'_(k-j), .) times sk.  This function IS the definition of the space-curvature rows' coefficients: the
+// in-register search kernels and the any-degree rows kernel both call it.
+struct SpaceCurv { double wx, wy, wz, den; };
+template <class A>
+__device__ __forceinline__ SpaceCurv space_curvature_row_coeff(const A& ux, const A& uy, const A& uz, const A& uxx, const A& uyy,
+                                                               const A& uzz, const int n, const int k, const double sk)
+{
+#pragma clang fp contract(off)
+    const int jlo = k > n ? k - n : 0, jhi = k < n ? k : n;
+    double den = 0.0;
+#pragma unroll
+    for (int j = jlo; j <= jhi; ++j) {
+        den = __builtin_fma(ux[j], ux[k - j], den);
+        den = __builtin_fma(uy[j], uy[k - j], den);
+        den = __builtin_fma(uz[j], uz[k - j], den);
+    }
+    SpaceCurv r;
+    r.wx = curvature_row_coeff(uy, uz, uyy, uzz, n, k, sk).num;
+    r.wy = curvature_row_coeff(uz, ux, uzz, uxx, n, k, sk).num;
+    r.wz = curvature_row_coeff(ux, uy, uxx, uyy, n, k, sk).num;
+    r.den = sk * den;
+    return r;
+}
+
+// |w| from its components, the one sequence every evaluation and every node bound uses
+__device__ __forceinline__ double space_curvature_norm(const double wx, const double wy, const double wz)
+{
+#pragma clang fp contract(off)
+    return __builtin_sqrt(__builtin_fma(wz, wz, __builtin_fma(wy, wy, wx * wx)));
+}
+
+// Envelope block of one vehicle's space-curvature row at parameter t: the partial derivatives of row = max_curv - kappa(t)
+// with respect to the vehicle's own control points (obtg_space_curvature_true_min_jac).  With n = nc - 1, w = B^(n-1)(t),
+// u = B^(n-2)(t), A_i and C_i curvature_envelope_block's, v = c'(t), a = c''(t) evaluated as there (three coordinates):
+//     wx = fma(v_y, a_z, -(v_z a_y)),  wy = fma(v_z, a_x, -(v_x a_z)),  wz = fma(v_x, a_y, -(v_y a_x)),
+//     den = fma(v_z, v_z, fma(v_y, v_y, v_x v_x)),    nw = space_curvature_norm(wx, wy, wz),    wh = w / nw,
+//     r = 1 / (den sqrt(den)),    q = (3 nw) / (den (den sqrt(den))),
+//     P = a x wh: P_x = fma(a_y, wh_z, -(a_z wh_y)), ...;    Q = wh x v: Q_x = fma(wh_y, v_z, -(wh_z v_y)), ...,
+//     out[d][i] = -fma(fma(P_d, A_i, Q_d C_i), r, -((q v_d) A_i)).
+// Contraction off inside.  den = 0 or w = 0 at t gives a non-finite block; the callers do not come here for a row that is
+// its bound or for a NaN t (sc_envelope).
+template <int NCMAX>
+__device__ __forceinline__ void space_curvature_envelope_block(const double* __restrict__ y, const int nc, const double t,
+                                                               double* __restrict__ out)
+{
+#pragma clang fp contract(off)
+    const int n = nc - 1;
+    const double s = 1.0 - t;
+    double u[NCMAX], w[NCMAX];             // u[0 .. n - 1): B^(n-2)(t); w[0 .. n): B^(n-1)(t); the rest stays zero
+#pragma unroll
+    for (int i = 0; i < NCMAX; ++i) u[i] = (i == 0 && n >= 2) ? 1.0 : 0.0;
+#pragma unroll
+    for (int r = 1; r < NCMAX - 2; ++r)
+        if (r < n - 1) {
+#pragma unroll
+            for (int i = r; i >= 1; --i) u[i] = __builtin_fma(t, u[i - 1], s * u[i]);
+            u[0] = s * u[0];
+        }
+#pragma unroll
+    for (int i = 0; i < NCMAX; ++i) w[i] = i == 0 ? s * u[0] : __builtin_fma(t, u[i - 1], s * u[i]);
+    if (n == 1) w[0] = 1.0;
+    const double nT = (double)n, nnT = nT * (double)(n - 1);
+    double d1[3], d2[3];                   // c' and c'' at t
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        double a = 0.0, b = 0.0;
+#pragma unroll
+        for (int i = 0; i < NCMAX - 1; ++i)
+            if (i < n) a = __builtin_fma(w[i], y[c * nc + i + 1] - y[c * nc + i], a);
+#pragma unroll
+        for (int i = 0; i < NCMAX - 2; ++i)
+            if (i < n - 1) b = __builtin_fma(u[i], (y[c * nc + i + 2] - y[c * nc + i + 1]) - (y[c * nc + i + 1] - y[c * nc + i]), b);
+        d1[c] = nT * a;
+        d2[c] = nnT * b;
+    }
+    const double wx = __builtin_fma(d1[1], d2[2], -(d1[2] * d2[1]));
+    const double wy = __builtin_fma(d1[2], d2[0], -(d1[0] * d2[2]));
+    const double wz = __builtin_fma(d1[0], d2[1], -(d1[1] * d2[0]));
+    const double den = __builtin_fma(d1[2], d1[2], __builtin_fma(d1[1], d1[1], d1[0] * d1[0]));
+    const double nw = space_curvature_norm(wx, wy, wz);
+    const double hx = wx / nw, hy = wy / nw, hz = wz / nw;
+    const double d32 = den * __builtin_sqrt(den);
+    const double r = 1.0 / d32, q = (3.0 * nw) / (den * d32);
+    double P[3], Q[3], qv[3];
+    P[0] = __builtin_fma(d2[1], hz, -(d2[2] * hy));
+    P[1] = __builtin_fma(d2[2], hx, -(d2[0] * hz));
+    P[2] = __builtin_fma(d2[0], hy, -(d2[1] * hx));
+    Q[0] = __builtin_fma(hy, d1[2], -(hz * d1[1]));
+    Q[1] = __builtin_fma(hz, d1[0], -(hx * d1[2]));
+    Q[2] = __builtin_fma(hx, d1[1], -(hy * d1[0]));
+#pragma unroll
+    for (int c = 0; c < 3; ++c) qv[c] = q * d1[c];
+#pragma unroll
+    for (int i = 0; i < NCMAX; ++i)
+        if (i < nc) {
+            const double Ai = nT * ((i == 0 ? 0.0 : w[i - 1]) - w[i]);
+            const double Ci = nnT * (((i < 2 ? 0.0 : u[i - 2]) - (i == 0 ? 0.0 : u[i - 1])) - ((i == 0 ? 0.0 : u[i - 1]) - u[i]));
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                out[c * nc + i] = -__builtin_fma(__builtin_fma(P[c], Ai, Q[c] * Ci), r, -(qv[c] * Ai));
+        }
+}
+
 // write a full [n_valid][LR] tile (pitch TP) as one contiguous run of n_valid*LR doubles
 template <int LR, int TP>
 __device__ __forceinline__ void flush_full(const double* __restrict__ tile, double* __restrict__ gout,

@@ -144,7 +144,7 @@ int ensure_tables(obtg_ctx* c)
             if ((rc = upload(c, c->d_ang_w22n, b.data(), b.size() * sizeof(double)))) return rc;
             if ((rc = upload(c, c->d_ang_wn, w.data(), w.size() * sizeof(double)))) return rc;
         }
-        if (c->dim == 2 && n >= 1 && n <= 31) {
+        if ((c->dim == 2 || c->dim == 3) && n >= 1 && n <= 31) {       // (dim 3: the space-curvature rows)
             auto t = ang_rows_table(n);
             if ((rc = upload(c, c->d_ang_rows, t.data(), t.size() * sizeof(double)))) return rc;
         }
@@ -254,6 +254,7 @@ const char* obtg_abi_symbols(void)
         "obtg_jerk\0obtg_jerk_dev\0obtg_jerk_true_min\0obtg_jerk_true_min_dev\0obtg_jerk_true_min_jac\0obtg_jerk_true_min_jac_dev\0"
         "obtg_ang_rate_poly\0obtg_ang_rate_poly_dev\0obtg_ang_rate_true_min\0obtg_ang_rate_true_min_dev\0obtg_ang_rate_true_min_jac\0obtg_ang_rate_true_min_jac_dev\0"
         "obtg_curvature_poly\0obtg_curvature_poly_dev\0obtg_curvature_true_min\0obtg_curvature_true_min_dev\0obtg_curvature_true_min_jac\0obtg_curvature_true_min_jac_dev\0obtg_bern_curvature\0obtg_bern_curvature_dev\0"
+        "obtg_space_curvature_poly\0obtg_space_curvature_poly_dev\0obtg_space_curvature_true_min\0obtg_space_curvature_true_min_dev\0obtg_space_curvature_true_min_jac\0obtg_space_curvature_true_min_jac_dev\0obtg_bern_space_curvature\0obtg_bern_space_curvature_dev\0"
         "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_restrict\0obtg_bern_eval\0"
         "obtg_euclidean_obj\0obtg_accel_obj\0obtg_jerk_obj\0"
         "obtg_bern_arc_length\0obtg_bern_arc_length_dev\0obtg_arc_length_obj\0obtg_arc_length_obj_dev\0"
@@ -1705,7 +1706,7 @@ static int true_min_chain(obtg_ctx* c, const RowFamily& f, const double* dY, int
         if (!bern_extrema_supported(K)) return OBTG_ERR_UNSUPPORTED;
         const long items = (long)B * f.items;
         DevBuf& ws = c->ws_misc[WS_L_ROWS];
-        if ((rc = ws.reserve(sizeof(double) * (size_t)items * K))) return rc;
+        if ((rc = ws.reserve(sizeof(double) * (size_t)items * K * f.ws_rows))) return rc;
         if ((rc = f.rows_r0(c, f, dY, B, ws.as<double>()))) return rc;
         rc = f.search ? f.search(c, f, ws.as<double>(), items, eps_rel, max_nodes, d_out, d_t, d_status)
                       : launch_bern_extrema(c, ws.as<double>(), items, K, 0, eps_rel, 0.0, max_nodes, d_out, d_t, nullptr, nullptr, d_status,
@@ -2078,6 +2079,117 @@ int obtg_bern_curvature(obtg_ctx* c, const double* coef, int M, int K, double ep
     h.fetch(t_max, dv + 3 * m, m);
     h.fetch(status, ds, 2 * m);
     return h.finish(k_min, dv, m);
+}
+
+// The space-curvature family (dim 3): the curvature entry points above with space_curvature_row_family -- one row per
+// vehicle, four polynomials per row in the workspace.  A context of another dimension: OBTG_ERR_UNSUPPORTED.
+static int space_curvature_args(const obtg_ctx* c, const double* out, int B, int max_nodes, double eps_rel)
+{
+    if (!check_ctx(c) || !out || B < 0 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
+    return c->dim != 3 || c->deg > 31 ? OBTG_ERR_UNSUPPORTED : OBTG_OK;
+}
+
+int obtg_space_curvature_poly_dev(obtg_ctx* c, const double* dY, int B, double* d_out)
+{
+    if (int rc = space_curvature_args(c, d_out, B, 1, 0.0)) return rc;
+    (void)hipSetDevice(c->device);
+    const RowFamily f = space_curvature_row_family(c, 0.0);
+    return with_batch(c, dY, B, false, [&](const double* src) { return launch_space_curvature_rows(c, f, src, B, d_out); });
+}
+
+int obtg_space_curvature_poly(obtg_ctx* c, const double* Y, int B, double* out)
+{
+    if (int rc = space_curvature_args(c, out, B, 1, 0.0)) return rc;
+    if (!Y) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    const size_t n = (size_t)B * c->n_veh * 4 * (2 * c->deg + 1);
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    double* d_out = h.out<double>(c->ws_out, n);
+    h.run([&] { return launch_space_curvature_rows(c, space_curvature_row_family(c, 0.0), dY, B, d_out); });
+    return h.finish(out, d_out, n);
+}
+
+int obtg_space_curvature_true_min_dev(obtg_ctx* c, const double* dY, int B, double max_curv, double eps_rel, int max_nodes,
+                                      double* d_out, double* d_t_star, int* d_status)
+{
+    if (int rc = space_curvature_args(c, d_out, B, max_nodes, eps_rel)) return rc;
+    return true_min_dev(c, space_curvature_row_family(c, max_curv), dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, nullptr, nullptr);
+}
+
+int obtg_space_curvature_true_min(obtg_ctx* c, const double* Y, int B, double max_curv, double eps_rel, int max_nodes, double* out,
+                                  double* t_star, int* status)
+{
+    if (int rc = space_curvature_args(c, out, B, max_nodes, eps_rel)) return rc;
+    if (!Y) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    return true_min_host(c, space_curvature_row_family(c, max_curv), Y, nullptr, B, eps_rel, max_nodes, out, t_star, status, nullptr, nullptr);
+}
+
+int obtg_space_curvature_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, double max_curv, double eps_rel, int max_nodes,
+                                          double* d_out, double* d_t_star, int* d_status, double* d_jac)
+{
+    if (int rc = space_curvature_args(c, d_out, B, max_nodes, eps_rel)) return rc;
+    if (!d_jac) return OBTG_ERR_ARG;
+    return true_min_dev(c, space_curvature_row_family(c, max_curv), dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, d_jac, nullptr);
+}
+
+int obtg_space_curvature_true_min_jac(obtg_ctx* c, const double* Y, int B, double max_curv, double eps_rel, int max_nodes, double* out,
+                                      double* t_star, int* status, double* jac)
+{
+    if (int rc = space_curvature_args(c, out, B, max_nodes, eps_rel)) return rc;
+    if (!Y || !jac) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    return true_min_host(c, space_curvature_row_family(c, max_curv), Y, nullptr, B, eps_rel, max_nodes, out, t_star, status, jac, nullptr);
+}
+
+// Free space curves c[M][3][K], any K from 2 to 32 whatever the context's shape is: the family's rows kernel and workspace
+// search on them (max_curv = 0; the maximum itself is returned).  obtg_bern_curvature's product table serves.
+static int bern_space_curvature_args(const obtg_ctx* c, int M, int K, double eps_rel, int max_nodes, const double* coef,
+                                     const double* k_max, const double* t_max)
+{
+    if (!check_ctx(c) || M < 0 || K < 2 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
+    if (!curvature_supported(K)) return OBTG_ERR_UNSUPPORTED;
+    if (M > 0 && (!coef || !k_max || !t_max)) return OBTG_ERR_ARG;
+    return OBTG_OK;
+}
+
+// rows into WS_L_ROWS, then the search: both launches timed under OBTG_K_ANG_RATE
+static int bern_space_curvature_chain(obtg_ctx* c, const double* d_c, int M, int K, double eps_rel, int max_nodes, double* d_k_max,
+                                      double* d_t_max, int* d_status)
+{
+    const double* d_tab = nullptr;
+    int rc = curvature_table(c, K - 1, &d_tab);
+    if (rc) return rc;
+    DevBuf& ws = c->ws_misc[WS_L_ROWS];
+    if ((rc = ws.reserve(sizeof(double) * (size_t)M * 4 * (2 * K - 1)))) return rc;
+    if ((rc = launch_scurv_rows(c, d_c, d_tab, M, K, ws.as<double>(), OBTG_K_ANG_RATE))) return rc;
+    return launch_scurv_search(c, ws.as<double>(), M, K, 0.0, 1, eps_rel, max_nodes, d_k_max, d_t_max, d_status, OBTG_K_ANG_RATE);
+}
+
+int obtg_bern_space_curvature_dev(obtg_ctx* c, const double* d_c, int M, int K, double eps_rel, int max_nodes, double* d_k_max,
+                                  double* d_t_max, int* d_status)
+{
+    if (int rc = bern_space_curvature_args(c, M, K, eps_rel, max_nodes, d_c, d_k_max, d_t_max)) return rc;
+    if (M == 0) return OBTG_OK;
+    (void)hipSetDevice(c->device);
+    return bern_space_curvature_chain(c, d_c, M, K, eps_rel, max_nodes, d_k_max, d_t_max, d_status);
+}
+
+int obtg_bern_space_curvature(obtg_ctx* c, const double* coef, int M, int K, double eps_rel, int max_nodes, double* k_max,
+                              double* t_max, int* status)
+{
+    if (int rc = bern_space_curvature_args(c, M, K, eps_rel, max_nodes, coef, k_max, t_max)) return rc;
+    if (M == 0) return OBTG_OK;
+    const size_t m = (size_t)M;
+    HostCall h(c);
+    const double* d_c = h.in(c->ws_in, coef, m * 3 * K);
+    double* dv = h.out<double>(c->ws_out, 2 * m);          // k_max | t_max
+    int* ds = h.out<int>(c->ws_misc[WS_STATUS], m);
+    h.run([&] { return bern_space_curvature_chain(c, d_c, M, K, eps_rel, max_nodes, dv, dv + m, ds); });
+    h.fetch(t_max, dv + m, m);
+    h.fetch(status, ds, m);
+    return h.finish(k_max, dv, m);
 }
 
 // ------------------------------------------------------------------ single-curve algebra

@@ -880,6 +880,307 @@ __global__ __launch_bounds__(kWave) void k_curv_rows(const CurvParams q, double*
 }
 
 // =====================================================================================
+//  the space-curvature rows (dim 3): kappa = |w| / den^(3/2), w = c' x c'' three polynomials, den = |c'|^2.  |w| is the norm
+//  of a vector of polynomials: not a polynomial, without a sign -- one row per vehicle, no sides, no clamp logic, the
+//  incumbent starts at 0 (include/obtg.h obtg_space_curvature_true_min states the contract; DESIGN.md 4.22 the reasoning).
+//
+//  The shape is the curvature rows' above: the first step one lane per item, an item that needs the search gets the wave,
+//  lane k holds (wx_k, wy_k, wz_k, den_k), a de Casteljau level is the same average on all four, waiting sub-curves are
+//  frames of 4K + 3 doubles (wx | wy | wz | den | bound, t0, width) in LDS.  Upper bound of a node (sc_node_bound): with
+//  nu_k = |(wx_k, wy_k, wz_k)| the norm's convexity gives |w(t)| <= sum nu_k B_k(t), and the tangent of den^(3/2) at the
+//  node's mid-range bounds the denominator from below as cv_ratio's does.
+// =====================================================================================
+struct SpaceCurvParams {
+    const double* __restrict__ Y;      // [items][3][nc]: the vehicles (curves) in item order
+    const double* __restrict__ tab;    // C(n, .)[n+1], then 1 / C(2n, .)[2n+1] (capi.cpp ang_rows_table)
+    const double* __restrict__ rows;   // [items][4][2n+1], wx, wy, wz, den (k_scurv_rows): the workspace form's operand
+    double* __restrict__ val;          // [items]: max_curv - max kappa;  free curves: max kappa
+    double* __restrict__ t;            // [items] nullable
+    int* __restrict__ status;          // [items] nullable
+    double* __restrict__ jac;          // [items][3][nc] (the envelope forms)
+    long M;                            // items
+    int nc, max_nodes, free_curve;     // free_curve: the value written is the maximum itself (obtg_bern_space_curvature, W = 0)
+    double W, eps_rel;                 // W = max_curv
+};
+
+// kappa at a point, NaN where the point offers no incumbent: den <= 0, or a value that is not finite
+__device__ __forceinline__ double sc_kappa(const SpaceCurv& c)
+{
+    if (!(c.den > 0.0)) return __builtin_nan("");
+    const double k = space_curvature_norm(c.wx, c.wy, c.wz) / (c.den * __builtin_sqrt(c.den));
+    return k <= DBL_MAX ? k : __builtin_nan("");
+}
+__device__ __forceinline__ double sc_tol(double W, double eps_rel, double U) { return eps_rel * fmax(W, U); }
+
+// One coefficient's share of a node's bound, nu = |(wx_k, wy_k, wz_k)| >= 0: 0 where nu is 0 (the coefficient meets
+// lambda g_k - nu_k >= 0 for every lambda >= 0 wherever the rule holds, and a node of such coefficients alone has w == 0);
+// else +inf if dmin <= 0 or the tangent at the mid-range is <= 0 at dmin -- a g_k <= 0 beside a positive nu_k breaks the
+// inequality --; else nu / g_k with cv_ratio's g_k.
+__device__ __forceinline__ double sc_ratio(double nu, double den, double dmin, double dmax)
+{
+    if (nu == 0.0) return 0.0;
+    if (!(dmin > 0.0)) return INFINITY;
+    const double d0 = 0.5 * (dmin + dmax), s0 = __builtin_sqrt(d0);
+    const double a = 1.5 * s0, c = -0.5 * (d0 * s0);
+    return fma(a, dmin, c) > 0.0 ? nu / fma(a, den, c) : INFINITY;
+}
+// the whole wave on one node: lane k < K holds coefficient k; the same value in every lane
+__device__ __forceinline__ double sc_node_bound(const SpaceCurv& b, bool act)
+{
+    const double dmin = ex_wave_min(act ? b.den : INFINITY), dmax = cv_wave_max(act ? b.den : -INFINITY);
+    return cv_wave_max(act ? sc_ratio(space_curvature_norm(b.wx, b.wy, b.wz), b.den, dmin, dmax) : 0.0);
+}
+
+// The first step of an item (node 1), one lane: get(k) is its coefficient k.  true: `o` is the item's answer; false: the
+// search has to run from (o.val, o.t) as the incumbent.
+template <int KC, class Get>
+__device__ __forceinline__ bool sc_first(const Get& get, int K, double W, double eps_rel, CvOut& o)
+{
+    if (KC > 0) K = KC;
+    bool bad = false, any = false;
+    double dmin = INFINITY, dmax = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < (KC > 0 ? KC : K); ++k) {
+        const SpaceCurv c = get(k);
+        bad = bad || !(fabs(c.wx) <= DBL_MAX) || !(fabs(c.wy) <= DBL_MAX) || !(fabs(c.wz) <= DBL_MAX) || !(fabs(c.den) <= DBL_MAX);
+        any = any || c.wx != 0.0 || c.wy != 0.0 || c.wz != 0.0;
+        dmin = fmin(dmin, c.den); dmax = fmax(dmax, c.den);
+    }
+    o.status = OBTG_MD_OK;
+    if (bad) { o.val = o.t = __builtin_nan(""); o.nodes = 0; return true; }
+    o.nodes = 1;
+    o.val = 0.0; o.t = 0.0;
+    if (!any) return true;                  // w == 0 identically: a straight path, degree 1, a vehicle at rest
+    const double k0 = sc_kappa(get(0)), k1 = sc_kappa(get(K - 1));
+    if (k0 > o.val) { o.val = k0; o.t = 0.0; }
+    if (k1 > o.val) { o.val = k1; o.t = 1.0; }
+    double ub = 0.0;
+#pragma unroll
+    for (int k = 0; k < (KC > 0 ? KC : K); ++k) {
+        const SpaceCurv c = get(k);
+        ub = fmax(ub, sc_ratio(space_curvature_norm(c.wx, c.wy, c.wz), c.den, dmin, dmax));
+    }
+    return !(ub - o.val > sc_tol(W, eps_rel, o.val));
+}
+
+// The whole wave on ONE item (every lane must be here).  Lane k < K holds coefficient k in b; (U, tU): the first step's
+// incumbent.  stk: this wave's kExStack x (4K + 3) doubles.  Every scalar below is the same in all lanes.
+__device__ __forceinline__ CvOut sc_wave_search(SpaceCurv b, const int K, const double W, const double eps_rel, double U, double tU,
+                                                const int max_nodes, double* stk)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const bool act = lane < K;
+    const int pitch = 4 * K + 3;
+    double t0 = 0.0, w = 1.0;
+    int nodes = 1, sp = 0, status = OBTG_MD_OK;
+    for (;;) {
+        if (nodes + 2 > max_nodes) { status = OBTG_MD_NODE_CAP; break; }
+        // deCasteljau at 1/2 of the four polynomials, both pieces: l is lane 0's value after level r in lane r, b lane i's
+        SpaceCurv l = b, m;
+        m.wx = ex_lane0(b.wx); m.wy = ex_lane0(b.wy); m.wz = ex_lane0(b.wz); m.den = ex_lane0(b.den);
+        for (int r = 1; r < K; ++r) {
+            const double ux = wave_next_lane(b.wx), uy = wave_next_lane(b.wy), uz = wave_next_lane(b.wz), ud = wave_next_lane(b.den);
+            if (lane <= K - 1 - r) {
+                b.wx = 0.5 * b.wx + 0.5 * ux; b.wy = 0.5 * b.wy + 0.5 * uy; b.wz = 0.5 * b.wz + 0.5 * uz; b.den = 0.5 * b.den + 0.5 * ud;
+            }
+            m.wx = ex_lane0(b.wx); m.wy = ex_lane0(b.wy); m.wz = ex_lane0(b.wz); m.den = ex_lane0(b.den);
+            if (lane == r) l = m;
+        }
+        const double hw = 0.5 * w, tm = t0 + hw;
+        nodes += 2;
+        const double km = sc_kappa(m);
+        if (km > U) { U = km; tU = tm; }
+        const double tol = sc_tol(W, eps_rel, U);
+        const double ubL = sc_node_bound(l, act), ubR = sc_node_bound(b, act);
+        const bool aliveL = ubL - U > tol, aliveR = ubR - U > tol;
+        if (aliveL && aliveR) {
+            if (sp == kExStack) { status = OBTG_MD_DEPTH_CAP; break; }
+            const bool go_left = ubL >= ubR;
+            double* f = stk + sp * pitch;
+            if (act) {
+                f[lane] = go_left ? b.wx : l.wx; f[K + lane] = go_left ? b.wy : l.wy;
+                f[2 * K + lane] = go_left ? b.wz : l.wz; f[3 * K + lane] = go_left ? b.den : l.den;
+            }
+            if (lane == 0) { f[4 * K] = go_left ? ubR : ubL; f[4 * K + 1] = go_left ? tm : t0; f[4 * K + 2] = hw; }
+            ++sp;
+            if (go_left) b = l; else t0 = tm;
+            w = hw;
+        } else if (aliveL) { b = l; w = hw; }
+        else if (aliveR) { t0 = tm; w = hw; }
+        else {
+            bool found = false;
+            wave_sync();
+            while (sp > 0) {
+                --sp;
+                const double* f = stk + sp * pitch;
+                if (f[4 * K] - U > tol) {
+                    b.wx = act ? f[lane] : 0.0; b.wy = act ? f[K + lane] : 0.0;
+                    b.wz = act ? f[2 * K + lane] : 0.0; b.den = act ? f[3 * K + lane] : 0.0;
+                    t0 = f[4 * K + 1]; w = f[4 * K + 2];
+                    found = true;
+                    break;
+                }
+            }
+            wave_sync();
+            if (!found) break;
+        }
+    }
+    CvOut o;
+    o.val = U; o.t = tU; o.nodes = nodes; o.status = status;
+    return o;
+}
+
+// An item's answer to memory: row = max_curv - max kappa (a free curve: max kappa itself)
+__device__ __forceinline__ double sc_store(const SpaceCurvParams& q, long item, const CvOut& o)
+{
+    const double v = q.free_curve ? o.val : q.W - o.val;
+    q.val[item] = v;
+    if (q.t) q.t[item] = o.t;
+    if (q.status) q.status[item] = o.status;
+    return v;
+}
+
+// The item's block from Y at the t_star and the row value an earlier step left: zero where the row IS max_curv (a straight
+// path, degree 1, a vehicle at rest), NaN for a NaN t_star, bern_device.h space_curvature_envelope_block otherwise.
+template <int NCMAX>
+__device__ __forceinline__ void sc_envelope(const SpaceCurvParams& q, long item, int nc, double row, double t)
+{
+    double* o = q.jac + (size_t)item * (3 * nc);
+    if (row == q.W || !(t == t)) {
+        const double fill = t == t ? 0.0 : t;
+        for (int e = 0; e < 3 * nc; ++e) o[e] = fill;
+        return;
+    }
+    space_curvature_envelope_block<NCMAX>(q.Y + (size_t)item * (3 * nc), nc, t, o);
+}
+
+// What both kernel forms do once an item's first step is known: the wave on every item that needs it, in lane order; `load`
+// puts item src's coefficients into the lanes.
+template <class Load>
+__device__ __forceinline__ void sc_search_items(const SpaceCurvParams& q, const Load& load, int K, bool need, CvOut& mine, double* stk)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    unsigned long long mask = __ballot(need);
+    while (mask) {
+        const int src = __ffsll((long long)mask) - 1;
+        mask &= mask - 1;
+        SpaceCurv b;
+        b.wx = b.wy = b.wz = b.den = 0.0;
+        load(src, b);
+        const CvOut o = sc_wave_search(b, K, q.W, q.eps_rel, ex_lane(mine.val, src), ex_lane(mine.t, src), q.max_nodes, stk);
+        if (lane == src) mine = o;
+    }
+}
+
+// Coefficients in registers, one launch (the counts of OBTG_NC_SCURV_LIST): one lane forms an item's 4 (2n + 1)
+// coefficients with space_curvature_row_coeff, then the steps above; JAC: every lane writes its own block.
+template <int NC, bool JAC>
+__global__ __launch_bounds__(kCvWaves * kWave) void k_scurv_true_min(const SpaceCurvParams q)
+{
+    constexpr int N = NC - 1, L = 2 * NC - 1;
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    double* stk = lds + (size_t)wave * kExStack * (4 * L + 3);
+    const long item = ((long)blockIdx.x * kCvWaves + wave) * kWave + lane;
+    const bool valid = item < q.M;
+    const long it = valid ? item : q.M - 1;
+    const double* v = q.Y + (size_t)it * (3 * NC);
+    const ctab_t Cn = as_ctab(q.tab), Sk = Cn + NC;
+    double cw[3][L], den[L];
+    {
+        double u1[3][NC], u2[3][NC];           // C(n, j) c'_j;  C(n, j) c''_j
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            double x[NC], x1[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) x[c] = v[d * NC + c];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) x1[c] = diff_elev1_at(x, c, N, (double)N);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) u2[d][c] = Cn[c] * diff_elev1_at(x1, c, N, (double)N);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) u1[d][c] = Cn[c] * x1[c];
+        }
+#pragma unroll
+        for (int k = 0; k < L; ++k) {
+            const SpaceCurv c = space_curvature_row_coeff(u1[0], u1[1], u1[2], u2[0], u2[1], u2[2], N, k, Sk[k]);
+            cw[0][k] = c.wx; cw[1][k] = c.wy; cw[2][k] = c.wz; den[k] = c.den;
+        }
+    }
+    CvOut mine;
+    const bool need = !sc_first<L>([&](int k) { SpaceCurv c; c.wx = cw[0][k]; c.wy = cw[1][k]; c.wz = cw[2][k]; c.den = den[k]; return c; },
+                                   L, q.W, q.eps_rel, mine) && valid;
+    sc_search_items(q, [&](int src, SpaceCurv& b) {
+#pragma unroll
+        for (int k = 0; k < L; ++k) {
+            const double a0 = ex_lane(cw[0][k], src), a1 = ex_lane(cw[1][k], src), a2 = ex_lane(cw[2][k], src), a3 = ex_lane(den[k], src);
+            if (lane == k) { b.wx = a0; b.wy = a1; b.wz = a2; b.den = a3; }
+        }
+    }, L, need, mine, stk);
+    if (valid) {
+        const double row = sc_store(q, item, mine);
+        if (JAC) sc_envelope<NC>(q, item, NC, row, mine.t);
+    }
+}
+
+// The workspace form, any degree 1 .. 31: the coefficients are k_scurv_rows' rows in memory, K = 2 nc - 1 at run time
+__global__ __launch_bounds__(kCvWaves * kWave) void k_scurv_search(const SpaceCurvParams q)
+{
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6, K = 2 * q.nc - 1;
+    double* stk = lds + (size_t)wave * kExStack * (4 * K + 3);
+    const long item0 = ((long)blockIdx.x * kCvWaves + wave) * kWave, item = item0 + lane;
+    const bool valid = item < q.M;
+    const long it = valid ? item : q.M - 1;
+    const double* r = q.rows + (size_t)it * (4 * K);
+    CvOut mine;
+    const bool need = !sc_first<0>([&](int k) { SpaceCurv c; c.wx = r[k]; c.wy = r[K + k]; c.wz = r[2 * K + k]; c.den = r[3 * K + k]; return c; },
+                                   K, q.W, q.eps_rel, mine) && valid;
+    sc_search_items(q, [&](int src, SpaceCurv& b) {
+        const double* rs = q.rows + (size_t)(item0 + src) * (4 * K);
+        if (lane < K) { b.wx = rs[lane]; b.wy = rs[K + lane]; b.wz = rs[2 * K + lane]; b.den = rs[3 * K + lane]; }
+    }, K, need, mine, stk);
+    if (valid) sc_store(q, item, mine);
+}
+
+// The blocks alone, from Y, the rows' values and their t_star: one item per lane, nc <= kCvMaxNC at run time
+__global__ __launch_bounds__(kEnvThreads) void k_scurv_envelope(const SpaceCurvParams q)
+{
+    const long item = (long)blockIdx.x * kEnvThreads + threadIdx.x;
+    if (item < q.M) sc_envelope<kCvMaxNC>(q, item, q.nc, q.val[item], q.t[item]);
+}
+
+// The space-curvature rows' polynomials to memory, any degree 1 .. 31: one wave per vehicle (curve), lane k forms
+// coefficient k of wx, wy, wz and den with the function the in-register kernels use: out[.][4][2n+1].
+__global__ __launch_bounds__(kWave) void k_scurv_rows(const SpaceCurvParams q, double* __restrict__ out)
+{
+    __shared__ double sh[9][kCvMaxNC];       // c -> u1 after the last read; c'; u2
+    const long veh = blockIdx.x;
+    const int lane = threadIdx.x, nc = q.nc, n = nc - 1, L = 2 * n + 1;
+    const double val = (double)n;
+    const double* v = q.Y + (size_t)veh * (3 * nc);
+    const double* Cn = q.tab;
+    const double* Sk = Cn + nc;
+    if (lane < nc)
+        for (int d = 0; d < 3; ++d) sh[d][lane] = v[d * nc + lane];
+    __syncthreads();
+    if (lane < nc)
+        for (int d = 0; d < 3; ++d) sh[3 + d][lane] = diff_elev1_at(sh[d], lane, n, val);
+    __syncthreads();
+    if (lane < nc)
+        for (int d = 0; d < 3; ++d) {
+            sh[6 + d][lane] = Cn[lane] * diff_elev1_at(sh[3 + d], lane, n, val);
+            sh[d][lane] = Cn[lane] * sh[3 + d][lane];
+        }
+    __syncthreads();
+    if (lane < L) {
+        const SpaceCurv c = space_curvature_row_coeff(sh[0], sh[1], sh[2], sh[6], sh[7], sh[8], n, lane, Sk[lane]);
+        double* o = out + (size_t)veh * 4 * L + lane;
+        o[0] = c.wx; o[L] = c.wy; o[2 * L] = c.wz; o[3 * L] = c.den;
+    }
+}
+
+// =====================================================================================
 //  launchers
 // =====================================================================================
 bool bern_extrema_supported(int K) { return K >= 1 && K <= kExMaxK; }
@@ -1052,6 +1353,60 @@ static int launch_curv_fused(obtg_ctx* c, const RowFamily& f, const double* dY, 
     return OBTG_OK;
 }
 
+// ---- the space-curvature family's launches.  Frames: kExStack x (4K + 3) doubles per wave, 65 280 bytes at K = 63: under the
+// 64 KB a workgroup's dynamic LDS may be without raising a limit, one wave per workgroup.
+static SpaceCurvParams scurv_params(const double* d_curves, const double* d_tab, int nc, long items, double W, double eps_rel,
+                                    int max_nodes)
+{
+    SpaceCurvParams q{};
+    q.Y = d_curves; q.tab = d_tab; q.nc = nc; q.M = items; q.W = W; q.eps_rel = eps_rel; q.max_nodes = max_nodes;
+    return q;
+}
+static size_t scurv_lds_bytes(int K) { return sizeof(double) * kCvWaves * kExStack * (size_t)(4 * K + 3); }
+static_assert(sizeof(double) * kCvWaves * kExStack * (4 * (2 * kCvMaxNC - 1) + 3) <= 65536, "space-curvature frames: lower the frame count");
+
+int launch_scurv_rows(obtg_ctx* c, const double* d_curves, const double* d_tab, long n_curves, int nc, double* d_out, int kernel_id)
+{
+    if (n_curves <= 0) return OBTG_OK;
+    if (!curvature_supported(nc)) return OBTG_ERR_UNSUPPORTED;
+    const SpaceCurvParams q = scurv_params(d_curves, d_tab, nc, n_curves, 0.0, 0.0, 1);
+    ScopedKernelTimer t(c, kernel_id);
+    hipLaunchKernelGGL(k_scurv_rows, dim3((unsigned)n_curves), dim3(kWave), 0, c->stream, q, d_out);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
+int launch_scurv_search(obtg_ctx* c, const double* d_rows, long items, int nc, double max_curv, int free_curve, double eps_rel,
+                        int max_nodes, double* d_val, double* d_t, int* d_status, int kernel_id)
+{
+    if (items <= 0) return OBTG_OK;
+    if (!curvature_supported(nc)) return OBTG_ERR_UNSUPPORTED;
+    SpaceCurvParams q = scurv_params(nullptr, nullptr, nc, items, max_curv, eps_rel, max_nodes);
+    q.rows = d_rows; q.val = d_val; q.t = d_t; q.status = d_status; q.free_curve = free_curve;
+    ScopedKernelTimer t(c, kernel_id);
+    hipLaunchKernelGGL(k_scurv_search, dim3(curv_grid(items)), dim3(kCvWaves * kWave), scurv_lds_bytes(2 * nc - 1), c->stream, q);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
+// the counts of OBTG_NC_SCURV_LIST: coefficients in registers, one launch (with the blocks when d_jac is set)
+static int launch_scurv_fused(obtg_ctx* c, const RowFamily& f, const double* dY, const ExParams& ex, double* d_jac)
+{
+    if (c->dim != 3) return OBTG_ERR_UNSUPPORTED;
+    const int nc = c->deg + 1;
+    void (*kern)(const SpaceCurvParams) = nullptr;
+#define OBTG_CASE(NC_) if (nc == NC_) kern = d_jac ? k_scurv_true_min<NC_, true> : k_scurv_true_min<NC_, false>;
+    OBTG_NC_SCURV_LIST(OBTG_CASE)
+#undef OBTG_CASE
+    if (!kern) return OBTG_ERR_UNSUPPORTED;
+    SpaceCurvParams q = scurv_params(dY, c->d_ang_rows.as<double>(), nc, ex.M, f.w, ex.eps_rel, ex.max_nodes);
+    q.val = ex.val; q.t = ex.t; q.status = ex.status; q.jac = d_jac;
+    ScopedKernelTimer t(c, f.kernel_id);
+    hipLaunchKernelGGL(kern, dim3(curv_grid(ex.M)), dim3(kCvWaves * kWave), scurv_lds_bytes(ex.K), c->stream, q);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
 int launch_true_min(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double eps_rel, int max_nodes, double* d_out,
                     double* d_t, int* d_status, double* d_jac, double* d_jac_tf)
 {
@@ -1068,6 +1423,7 @@ int launch_true_min(obtg_ctx* c, const RowFamily& f, const double* dY, int B, do
         case ROWS_ACCEL: return launch_fused<AccelRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_JERK: return launch_fused<JerkRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_CURV: return launch_curv_fused(c, f, dY, ex, d_jac);
+        case ROWS_SCURV: return launch_scurv_fused(c, f, dY, ex, d_jac);
         default: return launch_fused<TsepRows>(c, f, dY, ex, d_jac, d_jac_tf);
     }
 }
@@ -1098,6 +1454,14 @@ int launch_true_min_envelope(obtg_ctx* c, const RowFamily& f, const double* dY, 
             q.val = const_cast<double*>(d_val); q.t = ex.t; q.jac = d_jac;
             ScopedKernelTimer t(c, f.kernel_id);
             hipLaunchKernelGGL(k_curv_envelope, dim3((unsigned)((ex.M + kEnvThreads - 1) / kEnvThreads)), dim3(kEnvThreads), 0, c->stream, q);
+            OBTG_HIP(c, hipGetLastError());
+            return OBTG_OK;
+        }
+        case ROWS_SCURV: {
+            SpaceCurvParams q = scurv_params(dY, c->d_ang_rows.as<double>(), c->deg + 1, ex.M, f.w, 0.0, 1);
+            q.val = const_cast<double*>(d_val); q.t = ex.t; q.jac = d_jac;
+            ScopedKernelTimer t(c, f.kernel_id);
+            hipLaunchKernelGGL(k_scurv_envelope, dim3((unsigned)((ex.M + kEnvThreads - 1) / kEnvThreads)), dim3(kEnvThreads), 0, c->stream, q);
             OBTG_HIP(c, hipGetLastError());
             return OBTG_OK;
         }
@@ -1153,6 +1517,32 @@ RowFamily curvature_row_family(const obtg_ctx* c, double max_curv)
     RowFamily f{ ROWS_CURV, 2 * c->n_veh, OBTG_K_ANG_RATE, 1.0, 0.0, nullptr, launch_curvature_rows };
     f.w = max_curv;
     f.search = curvature_rows_search;
+    return f;
+}
+
+// obtg_space_curvature_poly's launch, and the family's rows_r0: [B][n_veh][4][2 deg + 1], wx, wy, wz, den
+int launch_space_curvature_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out)
+{
+    if (B <= 0 || f.items <= 0) return OBTG_OK;
+    if (c->dim != 3 || !curvature_supported(c->deg + 1)) return OBTG_ERR_UNSUPPORTED;
+    int rc = ensure_tables(c);
+    if (rc) return rc;
+    return launch_scurv_rows(c, dY, c->d_ang_rows.as<double>(), (long)B * c->n_veh, c->deg + 1, d_out, f.kernel_id);
+}
+
+// the family's search of its workspace rows: one item per four rows
+static int space_curvature_rows_search(obtg_ctx* c, const RowFamily& f, const double* d_rows, long items, double eps_rel, int max_nodes,
+                                       double* d_out, double* d_t, int* d_status)
+{
+    return launch_scurv_search(c, d_rows, items, c->deg + 1, f.w, 0, eps_rel, max_nodes, d_out, d_t, d_status, f.kernel_id);
+}
+
+RowFamily space_curvature_row_family(const obtg_ctx* c, double max_curv)
+{
+    RowFamily f{ ROWS_SCURV, c->n_veh, OBTG_K_ANG_RATE, 1.0, 0.0, nullptr, launch_space_curvature_rows };
+    f.w = max_curv;
+    f.search = space_curvature_rows_search;
+    f.ws_rows = 4;
     return f;
 }
 

@@ -33,6 +33,9 @@ namespace obtg {
 //   OBTG_NC_CURV_LIST : the curvature rows' in-register kernels (k_curv_true_min; 2-D), the counts of OBTG_NC_ANG_LIST that
 //                      build without scratch; the others take the workspace route
 #define OBTG_NC_CURV_LIST(X) OBTG_NC_DYN(X) X(21)
+//   OBTG_NC_SCURV_LIST: the space-curvature rows' in-register kernels (k_scurv_true_min; 3-D), the counts that build without
+//                      scratch with four registers per coefficient (21 does not); the others take the workspace route
+#define OBTG_NC_SCURV_LIST(X) OBTG_NC_DYN(X)
 static inline bool nc_in_sep(int nc)  { return false OBTG_NC_SEP(OBTG_NC_EQ_); }
 static inline bool nc_in_dyn(int nc)  { return false OBTG_NC_DYN(OBTG_NC_EQ_); }
 static inline bool nc_in_elev(int nc) { return false OBTG_NC_ELEV(OBTG_NC_EQ_); }
@@ -142,7 +145,7 @@ struct obtg_ctx {
     obtg::DevBuf d_Td;        // the same elevation as a dense transposed matrix (elev_table_T_ld): rows for the lane-per-item chains
     obtg::DevBuf d_Tf;        // ... and as matrix-instruction B fragments (elev_table_frag): the batch kernels
     obtg::DevBuf d_ang_w2n, d_ang_w22n, d_ang_wn;  // angular-rate fast path weights
-    obtg::DevBuf d_ang_rows;  // the true angular-rate rows' separable product weights: C(n, .)[n+1], 1 / C(2n, .)[2n+1] (dim 2, n <= 31)
+    obtg::DevBuf d_ang_rows;  // the true angular-rate rows' separable product weights: C(n, .)[n+1], 1 / C(2n, .)[2n+1] (dim 2 and 3, n <= 31)
     obtg::DevBuf d_curv_tab;  // obtg_bern_curvature: the same table for the degree of the last call's curves (curv_tab_n)
     int curv_tab_n = -1;
     obtg::DevBuf d_ang_T4;    // angular rate, R > 0: elevation 4*deg -> 4*(deg+R) as a scaled convolution (elev_conv_padded)
@@ -386,7 +389,7 @@ int launch_bern_extrema(obtg_ctx* c, const double* d_c, long M, int K, int want_
 // A true-minimum row family (obtg_temporal_sep_true_min[_jac], obtg_speed_true_min[_jac], obtg_ang_rate_true_min[_jac], obtg_accel_true_min[_jac], obtg_jerk_true_min[_jac]) as the host path sees it: what one
 // call of the family contributes beyond the arguments every family has.  On the device the family is a struct of
 // extrema_kernels.hip (TsepRows, SpeedRows, AngRows, AccelRows, JerkRows), found by `kind`.
-enum RowKind { ROWS_TSEP, ROWS_SPEED, ROWS_ANG, ROWS_ACCEL, ROWS_JERK, ROWS_CURV };
+enum RowKind { ROWS_TSEP, ROWS_SPEED, ROWS_ANG, ROWS_ACCEL, ROWS_JERK, ROWS_CURV, ROWS_SCURV };
 struct RowFamily {
     RowKind kind;
     int items;                  // per batch row: n_pairs | n_veh | 2 n_veh
@@ -402,6 +405,7 @@ struct RowFamily {
     // rows are num and den and serve both of its items, so the workspace has as many rows as the batch has items
     int (*search)(obtg_ctx* c, const RowFamily& f, const double* d_rows, long items, double eps_rel, int max_nodes, double* d_out,
                   double* d_t, int* d_status) = nullptr;
+    int ws_rows = 1;            // workspace rows of 2 deg + 1 per item (ROWS_SCURV: 4 -- wx, wy, wz, den)
 };
 RowFamily tsep_row_family(const obtg_ctx* c, double max_sep);                                         // bern_kernels.hip
 RowFamily speed_row_family(const obtg_ctx* c, const double* d_tf, double bound, int is_max);
@@ -415,6 +419,15 @@ RowFamily curvature_row_family(const obtg_ctx* c, double max_curv);
 int launch_curvature_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);      // obtg_curvature_poly; its rows_r0
 // free curves (obtg_bern_curvature): d_curves[n][2][nc], d_tab = C(nc-1, .)[nc] | 1 / C(2 nc - 2, .)[2 nc - 1]; rows out[n][2][2 nc - 1];
 // the search of 2 n items with max_curv = 0; d_val1 / d_t1 set: the free-curve outputs k_max, t_max | k_min, t_min [n] each
+// The space-curvature family (dim 3, degree 1 .. 31; no time span; one row per vehicle).  Its search is its own
+// (extrema_kernels.hip sc_wave_search); its workspace holds four rows per item.
+RowFamily space_curvature_row_family(const obtg_ctx* c, double max_curv);
+int launch_space_curvature_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);   // obtg_space_curvature_poly; its rows_r0
+// free curves (obtg_bern_space_curvature): d_curves[n][3][nc], d_tab as launch_curv_rows'; rows out[n][4][2 nc - 1]; the
+// search of n items -- free_curve: max_curv = 0 and d_val receives the maximum itself
+int launch_scurv_rows(obtg_ctx* c, const double* d_curves, const double* d_tab, long n_curves, int nc, double* d_out, int kernel_id);
+int launch_scurv_search(obtg_ctx* c, const double* d_rows, long items, int nc, double max_curv, int free_curve, double eps_rel,
+                        int max_nodes, double* d_val, double* d_t, int* d_status, int kernel_id);
 bool curvature_supported(int nc);                       // 2 <= nc <= 32
 int launch_curv_rows(obtg_ctx* c, const double* d_curves, const double* d_tab, long n_curves, int nc, double* d_out, int kernel_id);
 int launch_curv_search(obtg_ctx* c, const double* d_rows, long items, int nc, double max_curv, double eps_rel, int max_nodes,

@@ -174,7 +174,7 @@ _MODEL_FIELDS = (
     ('numVeh', 'numVeh', None), ('dim', 'dimension', None), ('deg', 'degree', None), ('minGoal', 'minimizeGoal', None),
     ('maxSep', 'maxSep', None), ('minSpeed', 'minSpeed', None), ('maxSpeed', 'maxSpeed', None),
     ('maxAngRate', 'maxAngRate', None), ('maxAccel', 'maxAccel', None), ('maxJerk', 'maxJerk', None),
-    ('maxCurvature', 'maxCurvature', None),
+    ('maxCurvature', 'maxCurvature', None), ('maxSpaceCurvature', 'maxSpaceCurvature', None),
     ('initPoints', 'initPoints', np.atleast_2d), ('finalPoints', 'finalPoints', np.atleast_2d),
     ('initSpeeds', 'initSpeeds', np.atleast_1d), ('finalSpeeds', 'finalSpeeds', np.atleast_1d),
     ('initAngs', 'initAngs', np.atleast_1d), ('finalAngs', 'finalAngs', np.atleast_1d),
@@ -193,8 +193,10 @@ _MODEL_FIELDS = (
 #   on the time span -- they are called (Y, bound, *lead), have no d/dtf, and their explicit tf column is an exact 0).
 #   A family without a `rows` method (rows_attr and rows None) has true rows only: it has no rows option, its rows are always
 #   the true ones, and it enters _serve_key behind the obstacles, only while its bound is set.
+#   only_dim: the one dimension the family is built for (None: `planar` says it all) -- every public entry of the family
+#   raises in any other dimension before a device call.
 _RowFamily = collections.namedtuple('_RowFamily', 'key bound optional rows_attr rows true_min envelope exact lead planar sides '
-                                                  'constraints jacobian noun span', defaults=(True,))
+                                                  'constraints jacobian noun span only_dim', defaults=(True, None))
 _ROW_FAMILIES = (
     _RowFamily('vmax', 'maxSpeed', False, 'speedRows', 'speed', 'speed_true_min', 'speed_true_min_jac', 'speed_jac', (True,),
                False, 1, 'maxSpeedConstraints', 'maxSpeedJacobian', 'speed'),
@@ -208,6 +210,8 @@ _ROW_FAMILIES = (
                False, 1, 'maxJerkConstraints', 'maxJerkJacobian', 'jerk'),
     _RowFamily('curv', 'maxCurvature', True, None, None, 'curvature_true_min', 'curvature_true_min_jac', None, (),
                True, 2, 'maxCurvatureConstraints', 'maxCurvatureJacobian', 'curvature', False),
+    _RowFamily('scurv', 'maxSpaceCurvature', True, None, None, 'space_curvature_true_min', 'space_curvature_true_min_jac', None, (),
+               False, 1, 'maxSpaceCurvatureConstraints', 'maxSpaceCurvatureJacobian', 'space curvature', False, 3),
 )
 _FAMILY = {fam.key: fam for fam in _ROW_FAMILIES}
 _ROWS_OPTIONS = tuple(dict.fromkeys(fam.rows_attr for fam in _ROW_FAMILIES if fam.rows is not None))      # speedRows, angRateRows, accelRows, jerkRows
@@ -359,7 +363,8 @@ class BezOptimization(object):
                  accelRows='all',
                  maxJerk=None,
                  jerkRows='all',
-                 maxCurvature=None):
+                 maxCurvature=None,
+                 maxSpaceCurvature=None):
         """Beyond the reference's keywords: `device` (HIP ordinal; None: this process's, see _capi.default_device) and `separationRows` --
         'all': temporalSeparationConstraints returns every elevated control point of every pair, as the
         reference does (optimization.py:337); 'min': one row per pair, the smallest of them -- the
@@ -390,6 +395,9 @@ class BezOptimization(object):
         # maxCurvature (None: no bound; dim 2): |curvature| <= maxCurvature per vehicle, a turning radius of 1 / maxCurvature
         # that does not move with tf -- maxCurvatureConstraints: 2N true rows, maxCurvature - max over the path of max(0, +-kappa)
         # (obtg_curvature_true_min).  Curvature is not a polynomial: there is no control-point form and no rows option.
+        # maxSpaceCurvature (None: no bound; dim 3): curvature <= maxSpaceCurvature per vehicle in space, |c' x c''| / |c'|^3
+        # -- maxSpaceCurvatureConstraints: N true rows, maxSpaceCurvature - max over the path of kappa
+        # (obtg_space_curvature_true_min).  The norm of a cross product has no sign: one row per vehicle.
         given = locals()
         for attr in reversed(_ROWS_OPTIONS):         # (the newest family's option is checked first, as it always was)
             if given[attr] not in ('all', 'true_min'):
@@ -559,6 +567,16 @@ class BezOptimization(object):
         r = _md_checked(self._ctx(False).bern_curvature(Y, eps_rel=self.TRUE_MIN_EPS_REL), 'trueCurvatureRange')
         return r['k_min'], r['t_min'], r['k_max'], r['t_max']
 
+    def trueSpaceCurvatureMax(self, x):
+        """(k_max[N], t_max[N]): per vehicle of a 3-D problem the true maximum over the path of its curvature
+        |c' x c''| / |c'|^3 and the parameter in [0, 1] where it is reached (obtg_bern_space_curvature at TRUE_MIN_EPS_REL),
+        whatever maxSpaceCurvature is."""
+        x = np.asarray(x, dtype=float)
+        self._check_dimension(3)
+        Y = self.reshapeVector(x).reshape(self.model['numVeh'], 3, self.model['deg'] + 1)
+        r = _md_checked(self._ctx(False).bern_space_curvature(Y, eps_rel=self.TRUE_MIN_EPS_REL), 'trueSpaceCurvatureMax')
+        return r['k_max'], r['t_max']
+
     def trueSpeedRange(self, x):
         """(min_val[N], t_min[N], max_val[N], t_max[N]): per vehicle the true extrema over the trajectory of (d/2)|dv/dt|^2
         -- normSquare's factor kept: the scale of the speed rows, without their bound -- and the parameters in [0, 1] where
@@ -571,6 +589,13 @@ class BezOptimization(object):
         if self.model['dim'] != 2:
             raise ValueError('The input curve must be two dimensional,\n'
                              'instead it is {} dimensional'.format(self.model['dim']))                # optimization.py:590-593
+
+    _DIMENSION_WORDS = {3: 'three'}
+
+    def _check_dimension(self, dim):
+        if self.model['dim'] != dim:
+            raise ValueError('The input curve must be {} dimensional,\n'
+                             'instead it is {} dimensional'.format(self._DIMENSION_WORDS[dim], self.model['dim']))
 
     ARC_LENGTH_EPS_REL = 1e-12
 
@@ -727,6 +752,17 @@ class BezOptimization(object):
 
         def wrapper(x):
             self._check_planar()
+            return closure(x)
+        return wrapper
+
+    @property
+    def maxSpaceCurvatureConstraints(self):
+        """maxSpaceCurvature - curvature >= 0 on the whole path of a vehicle in space: float64[N], one true row per vehicle
+        (obtg_space_curvature_true_min), the same whatever tf is."""
+        closure = self._vehicle_closure(_FAMILY['scurv'])
+
+        def wrapper(x):
+            self._check_dimension(3)
             return closure(x)
         return wrapper
 
@@ -1051,6 +1087,14 @@ class BezOptimization(object):
         problem's tf column is an exact 0 (with prescribed speeds the column still carries dY/dtf)."""
         return self._jac_vehicle(x, 'curv', structured, method)
 
+    def maxSpaceCurvatureJacobian(self, x, structured=True, method='fd'):
+        """d(maxSpaceCurvatureConstraints)/dx, dense [N][n_x]: method='fd' differences the search (one batched call),
+        method='envelope' is the derivative of each row at the parameter its search returns
+        (obtg_space_curvature_true_min_jac; zero for a row that is maxSpaceCurvature itself).  The rows have no explicit
+        dependence on tf: that part of a time-optimal problem's tf column is an exact 0 (with prescribed speeds the column
+        still carries dY/dtf)."""
+        return self._jac_vehicle(x, 'scurv', structured, method)
+
     # ------------------------------------------------------------------ exact Jacobians (method='exact')
     # The device returns d rows / d Y per pair or vehicle ([..][rows][dim][deg+1] blocks, include/obtg.h obtg_*_jac); the chain
     # rule to x keeps the free columns, and for a time-optimal problem adds the tf column: the explicit d/dtf of the speed and
@@ -1124,6 +1168,8 @@ class BezOptimization(object):
         checks for every family; what cannot be answered raises.  Returns whether the rows are the true minima."""
         rows = self._rows_option(fam)
         true_min = rows == 'true_min'
+        if fam.only_dim is not None:
+            self._check_dimension(fam.only_dim)
         if fam.planar and (method == 'envelope' or true_min):      # (control-point rows of another dimension: the device call answers)
             self._check_planar()
         if method == 'envelope':

@@ -224,9 +224,31 @@ int obtg_num_pairs(const obtg_ctx*);        /* C(N+M,2)            */
 int obtg_temporal_sep(obtg_ctx*, const double* Y, int B, double max_sep, double* out);
 int obtg_speed(obtg_ctx*, const double* Y, const double* tf, int B, double bound, int is_max, double* out);
 int obtg_ang_rate(obtg_ctx*, const double* Y, const double* tf, int B, double max_rate, double* out);
+/* ---- Non-finite control points in the REDUCED separation forms -----------------------------------------------------
+ * obtg_temporal_sep keeps inf / nan element by element.  Every form that reduces a pair's row -- obtg_temporal_sep_min
+ * [_range][_dev], obtg_temporal_sep_active[_dev], obtg_temporal_sep_min_gather_dev, obtg_temporal_sep_fd_min_rows_dev,
+ * obtg_temporal_sep_min_dev inside a view, obtg_one_vs_many_min[_spans][_dev], on the specialised and on the any-degree
+ * kernels, in every launch form -- answers by the pair's FULL ROW: the 2n+R+1 values obtg_temporal_sep returns for that
+ * pair on the same context (the same DEG_ELEV).
+ *   1. A CLEAN row -- every element finite -- reduces to the bits of the minimum over those elements (the active form: to
+ *      the elements themselves), as it always did.
+ *   2. A DIRTY row -- any element NaN or +-inf, which includes finite control points whose products overflow -- reduces to
+ *      NaN.  obtg_temporal_sep_active: all k values NaN and out_idx = 0 .. k-1 (in range; -1 is never written); k = 1
+ *      still is obtg_temporal_sep_min, NaN for NaN.  This is what the reference's reduced form returns
+ *      (Examples/SequentialSwarm.py:65, `dv.normSquare().elev(10).cpts.min()`: elev is a dense np.dot with the elevation
+ *      matrix, bezier.py:469-495, so one non-finite coefficient makes the whole elevated row NaN, and ndarray.min() keeps
+ *      it) and what the true-minimum families below state.  The values are inequality rows of SLSQP, whose iterates do
+ *      become non-finite: a finite or +inf ("feasible") answer to such an iterate hides it.
+ *   3. obtg_one_vs_many_min_spans: a pair whose spans do not overlap returns `no_overlap` whatever its control points hold
+ *      (the reference returns None before it looks at them); a pair that overlaps follows 1 and 2 on the CUT curves.
+ * Every reduction has one definition, RowMin (csrc/bern_device.h): the minimum, and whether any value was not finite.
+ * Not covered: the full rows themselves.  Their element-wise pattern may be NARROWER than the reference's all-NaN row --
+ * band-limited elevation sums skip the 0 * nan terms of np.dot -- which rule 2 does not depend on: one non-finite element
+ * makes the row dirty.  The searches with data-dependent loops (gjk*, min_dist*, coll_check*, the robust forms) promise
+ * nothing on non-finite input. */
 /* fused per-pair minimum of the elevated separation control points minus max_sep^2
  * (the `dv.normSquare().min()` variant commented at optimization.py:338 and used by
- * Examples/SequentialSwarm.py:65): out[B][C(N+M,2)]. */
+ * Examples/SequentialSwarm.py:65): out[B][C(N+M,2)].  A pair with a non-finite element in its full row: NaN (rules 1, 2 above). */
 int obtg_temporal_sep_min(obtg_ctx*, const double* Y, int B, double max_sep, double* out);
 /* SURVEY.md 8(f) item 4 as the survey words it -- "feed SLSQP only active / near-active constraint rows": per pair the k
  * SMALLEST of its 2n+R+1 elevated separation control points (minus max_sep^2) -- among equal values the lower
@@ -237,11 +259,13 @@ int obtg_temporal_sep_min(obtg_ctx*, const double* Y, int B, double max_sep, dou
  * value order they would kink at every crossing inside the set as well).  k = 1 is obtg_temporal_sep_min.  The specialised kernels select in the epilogue of their reduced form (one lane holds a pair's
  * control points: a branch-free insertion into four registers per value); other degrees write the rows to a workspace and
  * select in a second launch.  Same values as the corresponding entries of obtg_temporal_sep, bit for bit.
+ * A pair with a non-finite element in its full row (rule 2 above): out_val NaN in all k places, out_idx 0 .. k-1 -- no
+ * control point is "the smallest" of such a row, and an index is always one that can be gathered with.
  * optimization.py:337-338 is where the reference builds the full rows / leaves the minimum commented out. */
 int obtg_temporal_sep_active(obtg_ctx*, const double* Y, int B, double max_sep, int k, double* out_val, int* out_idx);
 /* the same restricted to pairs [pair_begin, pair_begin+pair_count) of the lexicographic list:
  * out[B][pair_count].  With pair_begin = 0, pair_count = N-1 this is the one-vs-many constraint
- * of Examples/SequentialSwarm.py:43-70 (vehicle 0 against every other one). */
+ * of Examples/SequentialSwarm.py:43-70 (vehicle 0 against every other one).  Non-finite rows: NaN (rules 1, 2 above). */
 int obtg_temporal_sep_min_range(obtg_ctx*, const double* Y, int B, double max_sep,
                                 int pair_begin, int pair_count, double* out);
 
@@ -266,7 +290,9 @@ int obtg_temporal_sep_fd_dev(obtg_ctx*, const double* dY0, int n_pert, const int
  * callback, n_x + 1 for a finite-difference batch of the vehicle being planned), many[K][dim][deg+1] the curves it is
  * checked against.  No pair table: the context fixes (dim, deg, DEG_ELEV) only -- its vehicle count is not used -- and K
  * may differ from call to call (the planner's K grows by one per vehicle).  Degrees with a specialised kernel
- * (obtg_fast_kernels(dim, deg) & 1), others OBTG_ERR_UNSUPPORTED. */
+ * (obtg_fast_kernels(dim, deg) & 1), others OBTG_ERR_UNSUPPORTED.  A pair whose elevated control points are not all finite
+ * (a NaN or +-inf control point in either curve, products that overflow): NaN, as the reference's `.min()` (rules 1, 2 above;
+ * the full row of a pair is obtg_temporal_sep's for the two curves as vehicles of one context). */
 int obtg_one_vs_many_min(obtg_ctx*, const double* one, int B, const double* many, int K, double max_sep, double* out /*[B][K]*/);
 int obtg_one_vs_many_min_dev(obtg_ctx*, const double* d_one, int B, const double* d_many, int K, double max_sep, double* d_out);
 /* The same for curves that live on DIFFERENT time spans: one_span[B][2], many_span[K][2] hold (t0, tf) per curve.  The
@@ -275,7 +301,9 @@ int obtg_one_vs_many_min_dev(obtg_ctx*, const double* d_one, int B, const double
  * before a is split at (a - t0)/(tf - t0) and its right piece kept, then, if it ends after e, that piece is split at
  * (e - a)/(tf - a) and its left piece kept; an end that already is the overlap's is not touched -- and the difference,
  * normSquare, elev and minimum run on the pieces.  Pairs with a >= e (disjoint or touching spans: the reference returns
- * None) get `no_overlap`.  A call whose spans are all equal takes no split and equals obtg_one_vs_many_min bit for bit.
+ * None) get `no_overlap`, whatever their control points hold (rule 3 above); a pair that overlaps and whose CUT curves give
+ * a non-finite elevated control point gets NaN.  A call whose spans are all equal takes no split and equals
+ * obtg_one_vs_many_min bit for bit.
  * Degrees without a specialised kernel run a runtime-degree form up to 2 deg + DEG_ELEV + 1 <= 1024 (the any-degree
  * separation kernel's limit); beyond, and for any span with t0 >= tf: OBTG_ERR_ARG.
  * _dev: the curves and the output are device pointers; the spans stay HOST arrays (16 bytes per curve: they are checked
@@ -289,7 +317,9 @@ int obtg_one_vs_many_min_spans_dev(obtg_ctx*, const double* d_one, const double*
 /* ---- same sweeps on DEVICE pointers, asynchronous on the context's stream ---------------
  * pair_begin/pair_count select a contiguous block of the lexicographic pair list (the
  * pair-partitioned multi-GPU mode); out rows then hold only that block:
- * out[B][pair_count*(2n+R+1)].  Pass 0, obtg_num_pairs() for everything. */
+ * out[B][pair_count*(2n+R+1)].  Pass 0, obtg_num_pairs() for everything.  obtg_temporal_sep_min_dev and
+ * obtg_temporal_sep_active_dev follow the non-finite rules of their host forms (NaN for a dirty row, indices 0 .. k-1),
+ * with dY and inside a view alike. */
 int obtg_temporal_sep_dev(obtg_ctx*, const double* dY, int B, double max_sep,
                           int pair_begin, int pair_count, double* d_out);
 int obtg_temporal_sep_min_dev(obtg_ctx*, const double* dY, int B, double max_sep,
@@ -411,7 +441,8 @@ int obtg_constraint_sweep_dev(obtg_ctx*, const double* dY, const double* d_tf, i
  * balanced blocks of the lexicographic list, the first P mod G ranks one pair more), each rank evaluating the per-pair
  * separation minima of ITS block for the B rows (every rank holds all control points: dY, or an open view with dY = NULL),
  * ONE all-gather of 8 B P bytes in all, and d_min_all[B][P] complete on every rank.  The reference loops over every pair
- * in one process (optimization.py:311-346); the minimum per pair is its commented form at optimization.py:338. */
+ * in one process (optimization.py:311-346); the minimum per pair is its commented form at optimization.py:338.  Every
+ * rank's block is obtg_temporal_sep_min_dev's: NaN for a pair with a non-finite element in its full row. */
 typedef struct obtg_comm obtg_comm;
 int obtg_comm_unique_id(unsigned char* id /*[128]*/);
 int obtg_comm_create(obtg_comm** out, int n_ranks, int rank, const unsigned char* id /*[128]*/, int device);
@@ -429,7 +460,8 @@ int obtg_temporal_sep_min_gather_dev(obtg_ctx*, obtg_comm*, const double* dY, in
  * it advances, so for the rows [row_begin, row_begin + n_rows) of the batch over dY0 (obtg_fd_view_begin's rows, row_begin >= 1)
  * d_out[n_rows][n_obj - 1] holds, per row, the minima of exactly those pairs, partners ascending -- evaluated from dY0
  * directly (n_rows (n_obj - 1) pair evaluations; no [B][P] block is formed), the same bits as the corresponding entries of
- * obtg_temporal_sep_min_dev inside the view.  Row 0's P minima are obtg_temporal_sep_min_dev(dY0, 1, ...). */
+ * obtg_temporal_sep_min_dev inside the view -- NaN for NaN: a pair with a non-finite element in its full row is NaN in both
+ * (rules 1, 2 of the reduced forms).  Row 0's P minima are obtg_temporal_sep_min_dev(dY0, 1, ...). */
 int obtg_temporal_sep_fd_min_rows_dev(obtg_ctx*, const double* dY0, int n_fixed_cols, double h, int row_begin, int n_rows,
                                       double max_sep, double* d_out);
 int obtg_pair_block(const obtg_ctx*, int n_ranks, int rank, int* begin, int* count);
@@ -597,7 +629,7 @@ int obtg_bern_extrema_dev(obtg_ctx*, const double* d_c, int M, int K, int want_m
  * DEG_ELEV does not enter -- elevation does not change the polynomial -- so the context's R is not read.  The 2n+1
  * coefficients are formed by the device definition of obtg_temporal_sep's rows at R = 0, so out equals
  * obtg_bern_extrema(eps_abs = 0) of those rows bit for bit, and a pair whose smallest coefficient is an end coefficient
- * gives the bits of obtg_temporal_sep_min at R = 0.  out[B][P], t_star[B][P] (where the minimum is taken), status[B][P]
+ * gives the bits of obtg_temporal_sep_min at R = 0 (a row with a non-finite coefficient: NaN in both).  out[B][P], t_star[B][P] (where the minimum is taken), status[B][P]
  * as above.  Degrees with a specialised kernel (obtg_fast_kernels & 1) form the coefficients in registers: nothing but Y
  * is read and 8 to 20 bytes per pair are written; other degrees up to 31 go through a workspace of obtg_temporal_sep's
  * R = 0 rows (two launches; the context's DEG_ELEV and tables are not touched); beyond: OBTG_ERR_UNSUPPORTED.

@@ -564,6 +564,9 @@ class Context(object):
         return out
 
     def temporal_sep_min(self, Y, max_sep, pair_begin=0, pair_count=None):
+        """Per pair the smallest of its elevated separation control points minus max_sep^2 (obtg_temporal_sep_min_range):
+        [B][pair_count].  A pair whose full row (temporal_sep) has a NaN or +-inf element is NaN, not the minimum of the
+        finite rest (include/obtg.h, "Non-finite control points in the REDUCED separation forms")."""
         Y, B = self._rows(Y)
         if pair_count is None:
             pair_count = self.num_pairs - pair_begin
@@ -574,7 +577,8 @@ class Context(object):
 
     def temporal_sep_active(self, Y, max_sep, k, with_index=False):
         """Per pair its k smallest elevated separation control points, in control-point order (obtg_temporal_sep_active): [B][P * k]
-        (and, with_index, the int32 control-point indices of the same shape)."""
+        (and, with_index, the int32 control-point indices of the same shape).  A pair whose full row has a NaN or +-inf
+        element: k NaNs with the indices 0 .. k-1 (always indices one can gather with; k = 1 is temporal_sep_min, NaN for NaN)."""
         Y, B = self._rows(Y)
         out = pinned_empty((B, self.num_pairs * int(k)))
         idx = np.empty((B, self.num_pairs * int(k)), np.int32) if with_index else None
@@ -661,7 +665,7 @@ class Context(object):
 
     def temporal_sep_fd_min_rows_dev(self, dY0, n_fixed_cols, h, row_begin, n_rows, max_sep, d_out):
         """Per finite-difference row only the minima of the pairs its vehicle touches: d_out[n_rows][n_obj - 1]
-        (obtg_temporal_sep_fd_min_rows_dev)."""
+        (obtg_temporal_sep_fd_min_rows_dev).  NaN for a pair with a non-finite element, as temporal_sep_min_dev inside the view."""
         self._check(self._lib.obtg_temporal_sep_fd_min_rows_dev(self._h, _vp(dY0), int(n_fixed_cols), float(h), int(row_begin),
                                                                 int(n_rows), float(max_sep), _vp(d_out)),
                     "obtg_temporal_sep_fd_min_rows_dev")
@@ -1043,7 +1047,8 @@ class Context(object):
     def one_vs_many_min(self, one, many, max_sep):
         """Examples/SequentialSwarm.py:43-70: one[B][dim][deg+1] (or [dim][deg+1]) against many[K][dim][deg+1] ->
         out[B][K], the per-pair minimum of the elevated squared-distance control points minus max_sep^2
-        (include/obtg.h obtg_one_vs_many_min)."""
+        (include/obtg.h obtg_one_vs_many_min).  NaN for a pair whose elevated control points are not all finite -- what the
+        reference's `.cpts.min()` returns."""
         nc = self.deg + 1
         one = np.ascontiguousarray(one, dtype=np.float64).reshape(-1, self.dim, nc)
         many = np.ascontiguousarray(many, dtype=np.float64).reshape(-1, self.dim, nc)
@@ -1061,7 +1066,8 @@ class Context(object):
         """one_vs_many_min for curves on different time spans (include/obtg.h obtg_one_vs_many_min_spans; the reference's
         Bezier.sub with _temporalAlignment, bezier.py:347-374, 903-941): one_span[B][2], many_span[K][2] = (t0, tf) per
         curve; every pair is cut down to its overlap first.  -> out[B][K]; pairs whose spans do not overlap (the
-        reference's None, touching spans included) hold `no_overlap`."""
+        reference's None, touching spans included) hold `no_overlap`, whatever their control points hold; an overlapping pair
+        whose cut curves give a non-finite control point holds NaN."""
         nc = self.deg + 1
         one = np.ascontiguousarray(one, dtype=np.float64).reshape(-1, self.dim, nc)
         many = np.ascontiguousarray(many, dtype=np.float64).reshape(-1, self.dim, nc)

@@ -65,18 +65,37 @@ struct NsParams {
     int* __restrict__ sel_idx;        //   (obtg_temporal_sep_active): out[item][sel_k], sel_idx[item][sel_k] = their columns (nullable)
 };
 
+// The reduced row forms on non-finite input (include/obtg.h, "Non-finite control points"): a row with ANY element that is
+// NaN or +-inf reduces to NaN, as ndarray.min() of the reference's elevated row does; a row of finite elements keeps the bits
+// of fmin over them.  fmin alone drops a NaN operand and `<` never lets one in, so every reduction of a row -- the minimum
+// chains, Smallest4, the lanes of a wave -- sees its values through this one definition: a lane collects the minimum and
+// whether any value was not finite (one compare per value), and value() folds the two.
+struct RowMin {
+    double m;
+    bool dirty;
+    __device__ __forceinline__ RowMin() : m(INFINITY), dirty(false) {}
+    static __device__ __forceinline__ bool not_finite(double x) { return !(fabs(x) < INFINITY); }
+    __device__ __forceinline__ void put(double x) { dirty |= not_finite(x); m = fmin(m, x); }
+    __device__ __forceinline__ double value() const { return dirty ? (double)NAN : m; }
+    // two value()s of parts of one row (lanes of a wave): NaN if either part was dirty; a part without elements is +inf
+    static __device__ __forceinline__ double merge(double a, double b) { return (a != a || b != b) ? (double)NAN : fmin(a, b); }
+};
+
 // The four smallest of a stream of values with their positions, ascending in value while they are collected; ties keep
 // the earlier position first (the order numpy's stable argsort gives).  Branch-free insertion: v[] is sorted, so x < v[j] implies x < v[j + 1].
+// A stream with a non-finite value (RowMin::not_finite) stores NaN in all n places with the positions 0 .. n-1.
 struct Smallest4 {
     double v[4];
     int i[4];
-    __device__ __forceinline__ Smallest4()
+    bool dirty;
+    __device__ __forceinline__ Smallest4() : dirty(false)
     {
 #pragma unroll
         for (int j = 0; j < 4; ++j) { v[j] = INFINITY; i[j] = -1; }
     }
     __device__ __forceinline__ void put(double x, int k)
     {
+        dirty |= RowMin::not_finite(x);
         const bool l0 = x < v[0], l1 = x < v[1], l2 = x < v[2], l3 = x < v[3];
         v[3] = l2 ? v[2] : (l3 ? x : v[3]); i[3] = l2 ? i[2] : (l3 ? k : i[3]);
         v[2] = l1 ? v[1] : (l2 ? x : v[2]); i[2] = l1 ? i[1] : (l2 ? k : i[2]);
@@ -101,7 +120,7 @@ struct Smallest4 {
         cswap(0, 1); cswap(2, 3); cswap(0, 2); cswap(1, 3); cswap(1, 2);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            if (j < n) { out[base + j] = w[j]; if (idx) idx[base + j] = q[j]; }
+            if (j < n) { out[base + j] = dirty ? (double)NAN : w[j]; if (idx) idx[base + j] = dirty ? j : q[j]; }
     }
 };
 
@@ -1552,10 +1571,10 @@ __device__ __forceinline__ void normsq_elev_body(const NsParams& p, const int b,
                     for (int k = 0; k < L; ++k) sm.put(p.sign * cf[k] + p.offset, k);
                     if (mine) sm.store(p.out, p.sel_idx, (row + r) * p.sel_k, p.sel_k);
                 } else {
-                    double m = cf[0];
+                    RowMin m;
 #pragma unroll
-                    for (int k = 1; k < L; ++k) m = fmin(m, cf[k]);
-                    if (mine) p.out[row + r] = p.sign * m + p.offset;
+                    for (int k = 0; k < L; ++k) m.put(cf[k]);
+                    if (mine) p.out[row + r] = p.sign * m.value() + p.offset;
                 }
             } else {
                 // transpose TR rows at a time through the wave's tile
@@ -1584,9 +1603,9 @@ __device__ __forceinline__ void normsq_elev_body(const NsParams& p, const int b,
                     for (int k = 0; k < LR; ++k) sm.put(elev_at<L>(ch, Td + k * L, p.offset), k);
                     if (mine) sm.store(p.out, p.sel_idx, (row + r) * p.sel_k, p.sel_k);
                 } else {
-                    double m = INFINITY;
-                    for (int k = 0; k < LR; ++k) m = fmin(m, elev_at<L>(ch, Td + k * L, p.offset));
-                    if (mine) p.out[row + r] = m;
+                    RowMin m;
+                    for (int k = 0; k < LR; ++k) m.put(elev_at<L>(ch, Td + k * L, p.offset));
+                    if (mine) p.out[row + r] = m.value();
                 }
             } else {
                 // (history at C5, R = 100, 2.26 GB per launch: lane = output column with LDS broadcasts 0.65 ms; lane = item with

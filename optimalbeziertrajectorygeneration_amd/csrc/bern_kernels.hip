@@ -132,18 +132,18 @@ __global__ __launch_bounds__(kWave) void k_tsep_fd(const TsepFdParams p)
     normsq_coeffs<NC, DIM>(a, as_ctab(p.W2), cf);
     const int LR = L + p.R;
     if (p.min_only) {
-        double m = INFINITY;
+        RowMin m;
         if (p.R == 0) {
 #pragma unroll
-            for (int k = 0; k < L; ++k) m = fmin(m, p.sign * cf[k] + p.offset);
+            for (int k = 0; k < L; ++k) m.put(p.sign * cf[k] + p.offset);
         } else {
             const ctab_t Td = as_ctab(p.Td);
             double ch[L];
 #pragma unroll
             for (int j = 0; j < L; ++j) ch[j] = p.sign * cf[j];
-            for (int k = 0; k < LR; ++k) m = fmin(m, elev_at<L>(ch, Td + k * L, p.offset));
+            for (int k = 0; k < LR; ++k) m.put(elev_at<L>(ch, Td + k * L, p.offset));
         }
-        p.out[item] = m;
+        p.out[item] = m.value();
         return;
     }
     double* o = p.out + (size_t)item * LR;
@@ -184,22 +184,19 @@ __device__ __forceinline__ double one_vs_many_value(const double (&a)[DIM][NC], 
     constexpr int L = NsShape<NC, DIM>::L;
     double cf[L];
     normsq_coeffs<NC, DIM>(a, as_ctab(p.W2), cf);
-    double mn;
+    RowMin mn;
     if (p.R == 0) {
-        mn = cf[0];
 #pragma unroll
-        for (int j = 1; j < L; ++j) mn = fmin(mn, cf[j]);
-        mn = p.sign * mn + p.offset;
-    } else {
-        const int LR = L + p.R;
-        const ctab_t Td = as_ctab(p.Td);
-        double ch[L];
-#pragma unroll
-        for (int j = 0; j < L; ++j) ch[j] = p.sign * cf[j];
-        mn = INFINITY;
-        for (int kk = 0; kk < LR; ++kk) mn = fmin(mn, elev_at<L>(ch, Td + kk * L, p.offset));
+        for (int j = 0; j < L; ++j) mn.put(cf[j]);
+        return p.sign * mn.value() + p.offset;
     }
-    return mn;
+    const int LR = L + p.R;
+    const ctab_t Td = as_ctab(p.Td);
+    double ch[L];
+#pragma unroll
+    for (int j = 0; j < L; ++j) ch[j] = p.sign * cf[j];
+    for (int kk = 0; kk < LR; ++kk) mn.put(elev_at<L>(ch, Td + kk * L, p.offset));
+    return mn.value();
 }
 
 template <int NC, int DIM>
@@ -644,13 +641,13 @@ __device__ __forceinline__ void generic_normsq_elev_tail(const GenParams& p, con
 {
     const int n = p.n, nc = n + 1, L = 2 * n + 1, LR = L + p.R, dim = p.dim;
     const double* b2n = p.bin + p.o_2n;
-    double mloc = INFINITY;
+    RowMin mloc;
     for (int k = lane; k < L; k += kWave) {
         double s = 0.0;
         for (int q = 0; q < dim; ++q) s += conv_at(ah + q * nc, nc, ah + q * nc, nc, k);
         const double c = (0.5 * dim) * s / b2n[k];
         if (p.R == 0) {
-            if (p.min_only) mloc = fmin(mloc, c);
+            if (p.min_only) mloc.put(c);
             else p.out[row * LR + k] = p.sign * c + p.offset;
         } else ch[k] = c * b2n[k];
     }
@@ -660,13 +657,14 @@ __device__ __forceinline__ void generic_normsq_elev_tail(const GenParams& p, con
         const double* b2nR = p.bin + p.o_2nR;
         for (int k = lane; k < LR; k += kWave) {
             const double s = conv_at(ch, L, bR, p.R + 1, k) / b2nR[k];
-            if (p.min_only) mloc = fmin(mloc, s);
+            if (p.min_only) mloc.put(s);
             else p.out[row * LR + k] = p.sign * s + p.offset;
         }
     }
     if (p.min_only) {
-        for (int o = 32; o > 0; o >>= 1) mloc = fmin(mloc, __shfl_down(mloc, o));
-        if (lane == 0) p.out[row] = p.sign * mloc + p.offset;
+        double m = mloc.value();            // (a lane without a column: +inf)
+        for (int o = 32; o > 0; o >>= 1) m = RowMin::merge(m, __shfl_down(m, o));
+        if (lane == 0) p.out[row] = p.sign * m + p.offset;
     }
 }
 

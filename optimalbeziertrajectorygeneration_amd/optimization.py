@@ -1146,8 +1146,11 @@ class BezOptimization(object):
         P = blk.shape[0]
         if self.separationRows in ('min', 'active'):
             k = 1 if self.separationRows == 'min' else self._active_k()
-            idx = ctx.temporal_sep_active(Y0, self.model['maxSep'], k, with_index=True)[1][0].reshape(P, k)
-            blk = blk[np.arange(P)[:, None], idx]
+            val, idx = ctx.temporal_sep_active(Y0, self.model['maxSep'], k, with_index=True)
+            blk = blk[np.arange(P)[:, None], idx[0].reshape(P, k)]
+            # a pair with a non-finite element has NaN rows (include/obtg.h, "Non-finite control points") and no control point
+            # that they follow: its derivative is NaN in the columns of its own vehicles, not the one of control points 0 .. k-1
+            blk[np.isnan(val[0].reshape(P, k))] = np.nan
         pa, pb = np.triu_indices(n_obj, 1)
         return self._scatter_exact(blk, (pa, pb), (1.0, -1.0))
 

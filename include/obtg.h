@@ -244,8 +244,8 @@ int obtg_ang_rate(obtg_ctx*, const double* Y, const double* tf, int B, double ma
  * Every reduction has one definition, RowMin (csrc/bern_device.h): the minimum, and whether any value was not finite.
  * Not covered: the full rows themselves.  Their element-wise pattern may be NARROWER than the reference's all-NaN row --
  * band-limited elevation sums skip the 0 * nan terms of np.dot -- which rule 2 does not depend on: one non-finite element
- * makes the row dirty.  The searches with data-dependent loops (gjk*, min_dist*, coll_check*, the robust forms) promise
- * nothing on non-finite input. */
+ * makes the row dirty.  The searches with data-dependent loops (gjk*, min_dist*, the robust forms) promise nothing on
+ * non-finite input; obtg_coll_check and obtg_coll_check2poly return the reference's value for it (see there). */
 /* fused per-pair minimum of the elevated separation control points minus max_sep^2
  * (the `dv.normSquare().min()` variant commented at optimization.py:338 and used by
  * Examples/SequentialSwarm.py:65): out[B][C(N+M,2)].  A pair with a non-finite element in its full row: NaN (rules 1, 2 above). */
@@ -584,7 +584,14 @@ int obtg_min_dist2poly(obtg_ctx*, const double* curves, int n_curves, int K,
  * not a status: there is no max_depth.  info[n_pairs][4] (nullable) = nodes visited (every one makes one gjkNew
  * call), gjkNew calls, max depth (the reference's cnt, at most 100), status; status[n_pairs]: OBTG_MD_OK,
  * OBTG_MD_NODE_CAP (max_nodes visited: the reference does not return in reasonable time) or OBTG_MD_GJK_CAP (an
- * inner gjkNew that never returns: a proven cycle or md_cap rounds).  res is 0 beside a status other than OBTG_MD_OK. */
+ * inner gjkNew that never returns: a proven cycle or md_cap rounds).  res is 0 beside a status other than OBTG_MD_OK.
+ * max_iter, md_cap or max_nodes below 1: OBTG_ERR_ARG (a search of max_nodes = 1 visits the root and, unless it ends
+ * there, stops with OBTG_MD_NODE_CAP).
+ * Non-finite input (NaN, +inf or -inf in a control point or a vertex) is not an error: both calls return what the
+ * reference returns for it, whatever that is, with OBTG_MD_OK -- its comparisons with NaN are all false, so a curve
+ * with a NaN control point can come back as 1, "no collision"; others walk to cnt = 100 and return -1 (curve form) or 0
+ * (polygon form).  A call that holds a non-finite coordinate runs the 3-D gjkNew machine even when every z is +0: the
+ * reference's 0 * inf and 0 * nan are NaN, terms the planar machine does not form. */
 int obtg_coll_check(obtg_ctx*, const double* curves, int n_curves, int K,
                     const int* pair_a, const int* pair_b, int n_pairs,
                     double eps, int max_iter, int md_cap, int max_nodes,

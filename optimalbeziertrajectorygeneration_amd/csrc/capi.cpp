@@ -1056,6 +1056,15 @@ static bool polys_planar(const double* pts, int n_pts, bool plus_zero_only)
     return true;
 }
 
+// every one of a[n] is finite.  The planar gjkNew machine (gjk_device.h) keeps the terms of the reference's 3-D arithmetic that
+// survive z == 0: those it drops are +-0 for finite x and y only (0 * inf and 0 * nan are NaN in the reference's cross and dot
+// products).  The collision checks return the reference's value on non-finite input, so they send it to the 3-D machine.
+static bool all_finite(const double* a, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) if (!std::isfinite(a[i])) return false;
+    return true;
+}
+
 static int max_poly_size(const int* off, int n_poly)
 {
     int max_K = 0;
@@ -1593,7 +1602,7 @@ int obtg_coll_check(obtg_ctx* c, const double* curves, int n_curves, int K, cons
     if (n_pairs == 0) return OBTG_OK;
     (void)hipSetDevice(c->device);
     if ((rc = upload_operands(c, curves, n_curves, K, nullptr, pair_a, pair_b, n_pairs))) return rc;
-    const bool planar = curves_planar(curves, n_curves, K);
+    const bool planar = curves_planar(curves, n_curves, K) && all_finite(curves, (size_t)3 * K * n_curves);
     if ((rc = reserve_search(c, coll_check_stack_doubles(c, K, n_pairs, false, planar), 1, n_pairs))) return rc;
     if ((rc = c->ws_misc[WS_QUEUE].reserve(sizeof(int)))) return rc;
     rc = launch_coll_check(c, c->ws_in.as<double>(), K, slot<int>(c, WS_PAIR_A), slot<int>(c, WS_PAIR_B), n_pairs, eps, max_iter,
@@ -1618,7 +1627,8 @@ int obtg_coll_check2poly(obtg_ctx* c, const double* curves, int n_curves, int K,
     (void)hipSetDevice(c->device);
     const PolySoa polys(pts, poly_off, n_poly);
     if ((rc = upload_operands(c, curves, n_curves, K, &polys, pair_curve, pair_poly, n_pairs))) return rc;
-    const bool planar = curves_planar(curves, n_curves, K) && polys_planar(pts, n_pts, true);
+    const bool planar = curves_planar(curves, n_curves, K) && polys_planar(pts, n_pts, true) &&
+                        all_finite(curves, (size_t)3 * K * n_curves) && all_finite(pts, (size_t)3 * n_pts);
     if ((rc = reserve_search(c, coll_check_stack_doubles(c, K, n_pairs, true, planar), 1, n_pairs))) return rc;
     if ((rc = c->ws_misc[WS_QUEUE].reserve(sizeof(int)))) return rc;
     rc = launch_coll_check2poly(c, c->ws_in.as<double>(), K, c->ws_in2.as<double>(), slot<int>(c, WS_POLY_OFF), slot<int>(c, WS_PAIR_A),

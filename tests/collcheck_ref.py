@@ -6,7 +6,8 @@ budget and a status.  A search stops with MD_GJK_CAP at the first gjkNew call th
 ST_MD_CAP / ST_CYCLE: the reference loops forever there; ST_MAXITER is a return, flag -1, as in the reference) and with
 MD_NODE_CAP when `max_nodes` nodes have been visited.  A node is a call that passes the reference's `cnt > 100` test;
 every node makes exactly one gjkNew call.  tests/test_collcheck_ref.py holds this file to the reference's recorded
-values and call counts; tests/test_gpu_collcheck.py holds the device to this file.
+values and call counts (tests/test_collcheck_cases_ref.py: on non-finite input, 13 control points and deep 3-D walks too);
+tests/test_gpu_collcheck.py and tests/test_gpu_collcheck_forms.py hold the device to this file.
 
 -> dict(res, nodes, gjk_calls, depth, status); res is 0.0 beside a status other than MD_OK.
 """
@@ -69,8 +70,9 @@ def upperbound(c1, c2):
     """_upperbound (bezier.py:1499-1541): the smallest of the four end-point distances, `norm` summed left to right."""
     def norm(a, b):
         s = 0.0
-        for v in a - b:
-            s += v * v
+        with np.errstate(invalid="ignore"):          # inf - inf of a non-finite control point: NaN, as in the reference
+            for v in a - b:
+                s += v * v
         return math.sqrt(s)
     d = np.array([norm(c1[:, 0], c2[:, 0]), norm(c1[:, 0], c2[:, -1]), norm(c1[:, -1], c2[:, 0]), norm(c1[:, -1], c2[:, -1])])
     return float(d[int(np.argmin(d))])

@@ -1,6 +1,13 @@
 """The collision checks on the MI355X (obtg_coll_check, obtg_coll_check2poly, Bezier.collCheck / collCheck2Poly) held to the
 reference's recorded values (tests/golden/collcheck.npz) and to tests/collcheck_ref.py, the restatement of both
-recursions over the CPU oracle: value, node count, gjkNew-call count, depth and status."""
+recursions over the CPU oracle: value, node count, gjkNew-call count, depth and status.
+
+What this file runs: the builds of 4, 6, 8, 9, 11 and 16 control points and the any-count build at 5 (2 in the fixture), with the
+default eps, max_iter and md_cap; the planar kernels to depth 100 and the `-1` return; the 3-D machine on random 3-D walks,
+which are rarely close (the restatement's deepest node there is 5); polygons of 3 .. 16 vertices; config 5's pair list.
+tests/test_gpu_collcheck_forms.py holds the forms left over: the any-count build's other counts and its two-pass split
+(12 .. 15), the 3-D machine walked deep, polygons of 1 and 2 vertices, the parameters off their defaults, the node budget's
+edge, non-finite input, and one context through changing calls."""
 import os
 import sys
 
@@ -9,6 +16,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import collcheck_ref as R  # noqa: E402
+from collcheck_cases import walks as _walks  # noqa: E402
 from util import assert_identical  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -35,12 +43,6 @@ def _same(got, ref, what):
         bad = np.flatnonzero(got[k] != ref[k])
         assert bad.size == 0, "%s: %s differs on %d pairs, first %d: %d vs %d" % (what, k, bad.size, bad[0], got[k][bad[0]], ref[k][bad[0]])
     assert_identical(got["res"], ref["res"], what)
-
-
-def _walks(rng, n, K, dim, spread):
-    c = np.zeros((n, 3, K))
-    c[:, :dim] = rng.uniform(0.0, spread, size=(n, dim, 1)) + np.cumsum(rng.normal(0.0, 4.0 / np.sqrt(K), size=(n, dim, K)), axis=2)
-    return c
 
 
 @pytest.mark.gpu

@@ -690,7 +690,7 @@ __device__ __forceinline__ double space_curvature_norm(const double wx, const do
 //     P = a x wh: P_x = fma(a_y, wh_z, -(a_z wh_y)), ...;    Q = wh x v: Q_x = fma(wh_y, v_z, -(wh_z v_y)), ...,
 //     out[d][i] = -fma(fma(P_d, A_i, Q_d C_i), r, -((q v_d) A_i)).
 // Contraction off inside.  den = 0 or w = 0 at t gives a non-finite block; the callers do not come here for a row that is
-// its bound or for a NaN t (sc_envelope).
+// its bound or for a NaN t (extrema_kernels.hip curv_envelope).
 template <int NCMAX>
 __device__ __forceinline__ void space_curvature_envelope_block(const double* __restrict__ y, const int nc, const double t,
                                                                double* __restrict__ out)

@@ -1964,71 +1964,59 @@ int obtg_ang_rate_true_min_jac(obtg_ctx* c, const double* Y, const double* tf, i
     return true_min_host(c, ang_row_family(c, nullptr, max_rate), Y, tf, B, eps_rel, max_nodes, out, t_star, status, jac, jac_tf);
 }
 
-// The curvature family: the angular-rate entry points without a time span (nothing takes tf), with curvature_row_family.
-// jac_tf does not exist: the rows do not depend on the span.
-static int curvature_args(const obtg_ctx* c, const double* out, int B, int max_nodes, double eps_rel)
+// The two curvature families, ROWS_CURV (dim 2) and ROWS_SCURV (dim 3): the angular-rate entry points without a time span
+// (nothing takes tf), with curvature_row_family(kind).  jac_tf does not exist: the rows do not depend on the span.  One host
+// path for both; `kind` picks the family.  The one difference in refusals: a planar call on a context that is not planar is
+// OBTG_ERR_ARG, a space call on a context that is not in space OBTG_ERR_UNSUPPORTED.
+static int curvature_args(const obtg_ctx* c, RowKind kind, const double* out, int B, int max_nodes, double eps_rel)
 {
-    if (!check_ctx(c) || c->dim != 2 || !out || B < 0 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
-    return c->deg > 31 ? OBTG_ERR_UNSUPPORTED : OBTG_OK;
+    if (!check_ctx(c) || (kind == ROWS_CURV && c->dim != 2) || !out || B < 0 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
+    return (kind == ROWS_SCURV && c->dim != 3) || c->deg > 31 ? OBTG_ERR_UNSUPPORTED : OBTG_OK;
 }
 
-int obtg_curvature_poly_dev(obtg_ctx* c, const double* dY, int B, double* d_out)
+static int curvature_poly_dev(obtg_ctx* c, RowKind kind, const double* dY, int B, double* d_out)
 {
-    if (int rc = curvature_args(c, d_out, B, 1, 0.0)) return rc;
+    if (int rc = curvature_args(c, kind, d_out, B, 1, 0.0)) return rc;
     (void)hipSetDevice(c->device);
-    const RowFamily f = curvature_row_family(c, 0.0);
+    const RowFamily f = curvature_row_family(c, kind, 0.0);
     return with_batch(c, dY, B, false, [&](const double* src) { return launch_curvature_rows(c, f, src, B, d_out); });
 }
 
-int obtg_curvature_poly(obtg_ctx* c, const double* Y, int B, double* out)
+static int curvature_poly(obtg_ctx* c, RowKind kind, const double* Y, int B, double* out)
 {
-    if (int rc = curvature_args(c, out, B, 1, 0.0)) return rc;
+    if (int rc = curvature_args(c, kind, out, B, 1, 0.0)) return rc;
     if (!Y) return OBTG_ERR_ARG;
     if (B == 0) return OBTG_OK;
-    const size_t n = (size_t)B * c->n_veh * 2 * (2 * c->deg + 1);
+    const size_t n = (size_t)B * c->n_veh * curvature_shape(kind).np * (2 * c->deg + 1);
     HostCall h(c);
     const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
     double* d_out = h.out<double>(c->ws_out, n);
-    h.run([&] { return launch_curvature_rows(c, curvature_row_family(c, 0.0), dY, B, d_out); });
+    h.run([&] { return launch_curvature_rows(c, curvature_row_family(c, kind, 0.0), dY, B, d_out); });
     return h.finish(out, d_out, n);
 }
 
-int obtg_curvature_true_min_dev(obtg_ctx* c, const double* dY, int B, double max_curv, double eps_rel, int max_nodes, double* d_out,
-                                double* d_t_star, int* d_status)
+// want_jac: the _jac entry points, where the blocks are not optional
+static int curvature_true_min_dev(obtg_ctx* c, RowKind kind, const double* dY, int B, double max_curv, double eps_rel, int max_nodes,
+                                  double* d_out, double* d_t_star, int* d_status, bool want_jac, double* d_jac)
 {
-    if (int rc = curvature_args(c, d_out, B, max_nodes, eps_rel)) return rc;
-    return true_min_dev(c, curvature_row_family(c, max_curv), dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, nullptr, nullptr);
+    if (int rc = curvature_args(c, kind, d_out, B, max_nodes, eps_rel)) return rc;
+    if (want_jac && !d_jac) return OBTG_ERR_ARG;
+    return true_min_dev(c, curvature_row_family(c, kind, max_curv), dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, d_jac, nullptr);
 }
 
-int obtg_curvature_true_min(obtg_ctx* c, const double* Y, int B, double max_curv, double eps_rel, int max_nodes, double* out,
-                            double* t_star, int* status)
+static int curvature_true_min(obtg_ctx* c, RowKind kind, const double* Y, int B, double max_curv, double eps_rel, int max_nodes,
+                              double* out, double* t_star, int* status, bool want_jac, double* jac)
 {
-    if (int rc = curvature_args(c, out, B, max_nodes, eps_rel)) return rc;
-    if (!Y) return OBTG_ERR_ARG;
+    if (int rc = curvature_args(c, kind, out, B, max_nodes, eps_rel)) return rc;
+    if (!Y || (want_jac && !jac)) return OBTG_ERR_ARG;
     if (B == 0) return OBTG_OK;
-    return true_min_host(c, curvature_row_family(c, max_curv), Y, nullptr, B, eps_rel, max_nodes, out, t_star, status, nullptr, nullptr);
+    return true_min_host(c, curvature_row_family(c, kind, max_curv), Y, nullptr, B, eps_rel, max_nodes, out, t_star, status, jac, nullptr);
 }
 
-int obtg_curvature_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, double max_curv, double eps_rel, int max_nodes,
-                                    double* d_out, double* d_t_star, int* d_status, double* d_jac)
-{
-    if (int rc = curvature_args(c, d_out, B, max_nodes, eps_rel)) return rc;
-    if (!d_jac) return OBTG_ERR_ARG;
-    return true_min_dev(c, curvature_row_family(c, max_curv), dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, d_jac, nullptr);
-}
-
-int obtg_curvature_true_min_jac(obtg_ctx* c, const double* Y, int B, double max_curv, double eps_rel, int max_nodes, double* out,
-                                double* t_star, int* status, double* jac)
-{
-    if (int rc = curvature_args(c, out, B, max_nodes, eps_rel)) return rc;
-    if (!Y || !jac) return OBTG_ERR_ARG;
-    if (B == 0) return OBTG_OK;
-    return true_min_host(c, curvature_row_family(c, max_curv), Y, nullptr, B, eps_rel, max_nodes, out, t_star, status, jac, nullptr);
-}
-
-// Free planar curves c[M][2][K], any K from 2 to 32 whatever the context's shape is: the family's rows kernel and workspace
-// search on them (max_curv = 0, no clamp).  The context's shape does not enter, so this is not a RowFamily (which describes
-// rows of the context's vehicles); the launchers are the family's.  The product table of degree K - 1 is kept from call to call.
+// Free curves c[M][dim][K], any K from 2 to 32 whatever the context's shape is: the family's rows kernel and workspace search
+// on them (max_curv = 0; planar: no clamp, both extrema; space: the maximum itself).  The context's shape does not enter, so
+// this is not a RowFamily (which describes rows of the context's vehicles); the launchers are the family's.  The product table
+// of degree K - 1 is kept from call to call and serves both families.
 static int curvature_table(obtg_ctx* c, int n, const double** d_tab)
 {
     if (c->curv_tab_n != n) {
@@ -2041,165 +2029,128 @@ static int curvature_table(obtg_ctx* c, int n, const double** d_tab)
     return OBTG_OK;
 }
 
-static int bern_curvature_args(const obtg_ctx* c, int M, int K, double eps_rel, int max_nodes, const double* coef, const double* k_min,
-                               const double* t_min, const double* k_max, const double* t_max)
+// k_min and t_min: the planar family's second side; null in space
+static int bern_curvature_args(const obtg_ctx* c, RowKind kind, int M, int K, double eps_rel, int max_nodes, const double* coef,
+                               const double* k_max, const double* t_max, const double* k_min, const double* t_min)
 {
     if (!check_ctx(c) || M < 0 || K < 2 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
     if (!curvature_supported(K)) return OBTG_ERR_UNSUPPORTED;
-    if (M > 0 && (!coef || !k_min || !t_min || !k_max || !t_max)) return OBTG_ERR_ARG;
+    if (M > 0 && (!coef || !k_max || !t_max || (kind == ROWS_CURV && (!k_min || !t_min)))) return OBTG_ERR_ARG;
     return OBTG_OK;
 }
 
 // rows into WS_L_ROWS, then the search: both launches timed under OBTG_K_ANG_RATE
-static int bern_curvature_chain(obtg_ctx* c, const double* d_c, int M, int K, double eps_rel, int max_nodes, double* d_k_min,
-                                double* d_t_min, double* d_k_max, double* d_t_max, int* d_status)
+static int bern_curvature_chain(obtg_ctx* c, RowKind kind, const double* d_c, int M, int K, double eps_rel, int max_nodes,
+                                double* d_k_max, double* d_t_max, double* d_k_min, double* d_t_min, int* d_status)
 {
+    const CurvShape s = curvature_shape(kind);
     const double* d_tab = nullptr;
     int rc = curvature_table(c, K - 1, &d_tab);
     if (rc) return rc;
     DevBuf& ws = c->ws_misc[WS_L_ROWS];
-    if ((rc = ws.reserve(sizeof(double) * (size_t)M * 2 * (2 * K - 1)))) return rc;
-    if ((rc = launch_curv_rows(c, d_c, d_tab, M, K, ws.as<double>(), OBTG_K_ANG_RATE))) return rc;
-    return launch_curv_search(c, ws.as<double>(), 2L * M, K, 0.0, eps_rel, max_nodes, d_k_max, d_t_max, d_k_min, d_t_min, nullptr,
+    if ((rc = ws.reserve(sizeof(double) * (size_t)M * s.np * (2 * K - 1)))) return rc;
+    if ((rc = launch_curv_rows(c, kind, d_c, d_tab, M, K, ws.as<double>(), OBTG_K_ANG_RATE))) return rc;
+    return launch_curv_search(c, kind, ws.as<double>(), (long)s.sides * M, K, 0.0, 1, eps_rel, max_nodes, d_k_max, d_t_max, d_k_min, d_t_min,
                               d_status, OBTG_K_ANG_RATE);
 }
 
+static int bern_curvature_dev(obtg_ctx* c, RowKind kind, const double* d_c, int M, int K, double eps_rel, int max_nodes,
+                              double* d_k_max, double* d_t_max, double* d_k_min, double* d_t_min, int* d_status)
+{
+    if (int rc = bern_curvature_args(c, kind, M, K, eps_rel, max_nodes, d_c, d_k_max, d_t_max, d_k_min, d_t_min)) return rc;
+    if (M == 0) return OBTG_OK;
+    (void)hipSetDevice(c->device);
+    return bern_curvature_chain(c, kind, d_c, M, K, eps_rel, max_nodes, d_k_max, d_t_max, d_k_min, d_t_min, d_status);
+}
+
+static int bern_curvature(obtg_ctx* c, RowKind kind, const double* coef, int M, int K, double eps_rel, int max_nodes, double* k_max,
+                          double* t_max, double* k_min, double* t_min, int* status)
+{
+    if (int rc = bern_curvature_args(c, kind, M, K, eps_rel, max_nodes, coef, k_max, t_max, k_min, t_min)) return rc;
+    if (M == 0) return OBTG_OK;
+    const CurvShape s = curvature_shape(kind);
+    const size_t m = (size_t)M;
+    const bool sides = s.sides == 2;
+    HostCall h(c);
+    const double* d_c = h.in(c->ws_in, coef, m * s.dim * K);
+    double* dv = h.out<double>(c->ws_out, 2 * s.sides * m);          // k_max | t_max [| k_min | t_min]
+    int* ds = h.out<int>(c->ws_misc[WS_STATUS], s.sides * m);
+    h.run([&] {
+        return bern_curvature_chain(c, kind, d_c, M, K, eps_rel, max_nodes, dv, dv + m, sides ? dv + 2 * m : nullptr, sides ? dv + 3 * m : nullptr, ds);
+    });
+    h.fetch(t_max, dv + m, m);
+    if (sides) {
+        h.fetch(k_min, dv + 2 * m, m);
+        h.fetch(t_min, dv + 3 * m, m);
+    }
+    h.fetch(status, ds, s.sides * m);
+    return h.finish(k_max, dv, m);
+}
+
+int obtg_curvature_poly_dev(obtg_ctx* c, const double* dY, int B, double* d_out) { return curvature_poly_dev(c, ROWS_CURV, dY, B, d_out); }
+int obtg_curvature_poly(obtg_ctx* c, const double* Y, int B, double* out) { return curvature_poly(c, ROWS_CURV, Y, B, out); }
+int obtg_curvature_true_min_dev(obtg_ctx* c, const double* dY, int B, double max_curv, double eps_rel, int max_nodes, double* d_out,
+                                double* d_t_star, int* d_status)
+{
+    return curvature_true_min_dev(c, ROWS_CURV, dY, B, max_curv, eps_rel, max_nodes, d_out, d_t_star, d_status, false, nullptr);
+}
+int obtg_curvature_true_min(obtg_ctx* c, const double* Y, int B, double max_curv, double eps_rel, int max_nodes, double* out,
+                            double* t_star, int* status)
+{
+    return curvature_true_min(c, ROWS_CURV, Y, B, max_curv, eps_rel, max_nodes, out, t_star, status, false, nullptr);
+}
+int obtg_curvature_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, double max_curv, double eps_rel, int max_nodes,
+                                    double* d_out, double* d_t_star, int* d_status, double* d_jac)
+{
+    return curvature_true_min_dev(c, ROWS_CURV, dY, B, max_curv, eps_rel, max_nodes, d_out, d_t_star, d_status, true, d_jac);
+}
+int obtg_curvature_true_min_jac(obtg_ctx* c, const double* Y, int B, double max_curv, double eps_rel, int max_nodes, double* out,
+                                double* t_star, int* status, double* jac)
+{
+    return curvature_true_min(c, ROWS_CURV, Y, B, max_curv, eps_rel, max_nodes, out, t_star, status, true, jac);
+}
 int obtg_bern_curvature_dev(obtg_ctx* c, const double* d_c, int M, int K, double eps_rel, int max_nodes, double* d_k_min,
                             double* d_t_min, double* d_k_max, double* d_t_max, int* d_status)
 {
-    if (int rc = bern_curvature_args(c, M, K, eps_rel, max_nodes, d_c, d_k_min, d_t_min, d_k_max, d_t_max)) return rc;
-    if (M == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
-    return bern_curvature_chain(c, d_c, M, K, eps_rel, max_nodes, d_k_min, d_t_min, d_k_max, d_t_max, d_status);
+    return bern_curvature_dev(c, ROWS_CURV, d_c, M, K, eps_rel, max_nodes, d_k_max, d_t_max, d_k_min, d_t_min, d_status);
 }
-
 int obtg_bern_curvature(obtg_ctx* c, const double* coef, int M, int K, double eps_rel, int max_nodes, double* k_min, double* t_min,
                         double* k_max, double* t_max, int* status)
 {
-    if (int rc = bern_curvature_args(c, M, K, eps_rel, max_nodes, coef, k_min, t_min, k_max, t_max)) return rc;
-    if (M == 0) return OBTG_OK;
-    const size_t m = (size_t)M;
-    HostCall h(c);
-    const double* d_c = h.in(c->ws_in, coef, m * 2 * K);
-    double* dv = h.out<double>(c->ws_out, 4 * m);          // k_min | t_min | k_max | t_max
-    int* ds = h.out<int>(c->ws_misc[WS_STATUS], 2 * m);
-    h.run([&] { return bern_curvature_chain(c, d_c, M, K, eps_rel, max_nodes, dv, dv + m, dv + 2 * m, dv + 3 * m, ds); });
-    h.fetch(t_min, dv + m, m);
-    h.fetch(k_max, dv + 2 * m, m);
-    h.fetch(t_max, dv + 3 * m, m);
-    h.fetch(status, ds, 2 * m);
-    return h.finish(k_min, dv, m);
+    return bern_curvature(c, ROWS_CURV, coef, M, K, eps_rel, max_nodes, k_max, t_max, k_min, t_min, status);
 }
 
-// The space-curvature family (dim 3): the curvature entry points above with space_curvature_row_family -- one row per
-// vehicle, four polynomials per row in the workspace.  A context of another dimension: OBTG_ERR_UNSUPPORTED.
-static int space_curvature_args(const obtg_ctx* c, const double* out, int B, int max_nodes, double eps_rel)
-{
-    if (!check_ctx(c) || !out || B < 0 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
-    return c->dim != 3 || c->deg > 31 ? OBTG_ERR_UNSUPPORTED : OBTG_OK;
-}
-
-int obtg_space_curvature_poly_dev(obtg_ctx* c, const double* dY, int B, double* d_out)
-{
-    if (int rc = space_curvature_args(c, d_out, B, 1, 0.0)) return rc;
-    (void)hipSetDevice(c->device);
-    const RowFamily f = space_curvature_row_family(c, 0.0);
-    return with_batch(c, dY, B, false, [&](const double* src) { return launch_space_curvature_rows(c, f, src, B, d_out); });
-}
-
-int obtg_space_curvature_poly(obtg_ctx* c, const double* Y, int B, double* out)
-{
-    if (int rc = space_curvature_args(c, out, B, 1, 0.0)) return rc;
-    if (!Y) return OBTG_ERR_ARG;
-    if (B == 0) return OBTG_OK;
-    const size_t n = (size_t)B * c->n_veh * 4 * (2 * c->deg + 1);
-    HostCall h(c);
-    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
-    double* d_out = h.out<double>(c->ws_out, n);
-    h.run([&] { return launch_space_curvature_rows(c, space_curvature_row_family(c, 0.0), dY, B, d_out); });
-    return h.finish(out, d_out, n);
-}
-
+int obtg_space_curvature_poly_dev(obtg_ctx* c, const double* dY, int B, double* d_out) { return curvature_poly_dev(c, ROWS_SCURV, dY, B, d_out); }
+int obtg_space_curvature_poly(obtg_ctx* c, const double* Y, int B, double* out) { return curvature_poly(c, ROWS_SCURV, Y, B, out); }
 int obtg_space_curvature_true_min_dev(obtg_ctx* c, const double* dY, int B, double max_curv, double eps_rel, int max_nodes,
                                       double* d_out, double* d_t_star, int* d_status)
 {
-    if (int rc = space_curvature_args(c, d_out, B, max_nodes, eps_rel)) return rc;
-    return true_min_dev(c, space_curvature_row_family(c, max_curv), dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, nullptr, nullptr);
+    return curvature_true_min_dev(c, ROWS_SCURV, dY, B, max_curv, eps_rel, max_nodes, d_out, d_t_star, d_status, false, nullptr);
 }
-
 int obtg_space_curvature_true_min(obtg_ctx* c, const double* Y, int B, double max_curv, double eps_rel, int max_nodes, double* out,
                                   double* t_star, int* status)
 {
-    if (int rc = space_curvature_args(c, out, B, max_nodes, eps_rel)) return rc;
-    if (!Y) return OBTG_ERR_ARG;
-    if (B == 0) return OBTG_OK;
-    return true_min_host(c, space_curvature_row_family(c, max_curv), Y, nullptr, B, eps_rel, max_nodes, out, t_star, status, nullptr, nullptr);
+    return curvature_true_min(c, ROWS_SCURV, Y, B, max_curv, eps_rel, max_nodes, out, t_star, status, false, nullptr);
 }
-
 int obtg_space_curvature_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, double max_curv, double eps_rel, int max_nodes,
                                           double* d_out, double* d_t_star, int* d_status, double* d_jac)
 {
-    if (int rc = space_curvature_args(c, d_out, B, max_nodes, eps_rel)) return rc;
-    if (!d_jac) return OBTG_ERR_ARG;
-    return true_min_dev(c, space_curvature_row_family(c, max_curv), dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, d_jac, nullptr);
+    return curvature_true_min_dev(c, ROWS_SCURV, dY, B, max_curv, eps_rel, max_nodes, d_out, d_t_star, d_status, true, d_jac);
 }
-
 int obtg_space_curvature_true_min_jac(obtg_ctx* c, const double* Y, int B, double max_curv, double eps_rel, int max_nodes, double* out,
                                       double* t_star, int* status, double* jac)
 {
-    if (int rc = space_curvature_args(c, out, B, max_nodes, eps_rel)) return rc;
-    if (!Y || !jac) return OBTG_ERR_ARG;
-    if (B == 0) return OBTG_OK;
-    return true_min_host(c, space_curvature_row_family(c, max_curv), Y, nullptr, B, eps_rel, max_nodes, out, t_star, status, jac, nullptr);
+    return curvature_true_min(c, ROWS_SCURV, Y, B, max_curv, eps_rel, max_nodes, out, t_star, status, true, jac);
 }
-
-// Free space curves c[M][3][K], any K from 2 to 32 whatever the context's shape is: the family's rows kernel and workspace
-// search on them (max_curv = 0; the maximum itself is returned).  obtg_bern_curvature's product table serves.
-static int bern_space_curvature_args(const obtg_ctx* c, int M, int K, double eps_rel, int max_nodes, const double* coef,
-                                     const double* k_max, const double* t_max)
-{
-    if (!check_ctx(c) || M < 0 || K < 2 || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
-    if (!curvature_supported(K)) return OBTG_ERR_UNSUPPORTED;
-    if (M > 0 && (!coef || !k_max || !t_max)) return OBTG_ERR_ARG;
-    return OBTG_OK;
-}
-
-// rows into WS_L_ROWS, then the search: both launches timed under OBTG_K_ANG_RATE
-static int bern_space_curvature_chain(obtg_ctx* c, const double* d_c, int M, int K, double eps_rel, int max_nodes, double* d_k_max,
-                                      double* d_t_max, int* d_status)
-{
-    const double* d_tab = nullptr;
-    int rc = curvature_table(c, K - 1, &d_tab);
-    if (rc) return rc;
-    DevBuf& ws = c->ws_misc[WS_L_ROWS];
-    if ((rc = ws.reserve(sizeof(double) * (size_t)M * 4 * (2 * K - 1)))) return rc;
-    if ((rc = launch_scurv_rows(c, d_c, d_tab, M, K, ws.as<double>(), OBTG_K_ANG_RATE))) return rc;
-    return launch_scurv_search(c, ws.as<double>(), M, K, 0.0, 1, eps_rel, max_nodes, d_k_max, d_t_max, d_status, OBTG_K_ANG_RATE);
-}
-
 int obtg_bern_space_curvature_dev(obtg_ctx* c, const double* d_c, int M, int K, double eps_rel, int max_nodes, double* d_k_max,
                                   double* d_t_max, int* d_status)
 {
-    if (int rc = bern_space_curvature_args(c, M, K, eps_rel, max_nodes, d_c, d_k_max, d_t_max)) return rc;
-    if (M == 0) return OBTG_OK;
-    (void)hipSetDevice(c->device);
-    return bern_space_curvature_chain(c, d_c, M, K, eps_rel, max_nodes, d_k_max, d_t_max, d_status);
+    return bern_curvature_dev(c, ROWS_SCURV, d_c, M, K, eps_rel, max_nodes, d_k_max, d_t_max, nullptr, nullptr, d_status);
 }
-
 int obtg_bern_space_curvature(obtg_ctx* c, const double* coef, int M, int K, double eps_rel, int max_nodes, double* k_max,
                               double* t_max, int* status)
 {
-    if (int rc = bern_space_curvature_args(c, M, K, eps_rel, max_nodes, coef, k_max, t_max)) return rc;
-    if (M == 0) return OBTG_OK;
-    const size_t m = (size_t)M;
-    HostCall h(c);
-    const double* d_c = h.in(c->ws_in, coef, m * 3 * K);
-    double* dv = h.out<double>(c->ws_out, 2 * m);          // k_max | t_max
-    int* ds = h.out<int>(c->ws_misc[WS_STATUS], m);
-    h.run([&] { return bern_space_curvature_chain(c, d_c, M, K, eps_rel, max_nodes, dv, dv + m, ds); });
-    h.fetch(t_max, dv + m, m);
-    h.fetch(status, ds, m);
-    return h.finish(k_max, dv, m);
+    return bern_curvature(c, ROWS_SCURV, coef, M, K, eps_rel, max_nodes, k_max, t_max, nullptr, nullptr, status);
 }
 
 // ------------------------------------------------------------------ single-curve algebra

@@ -31,6 +31,7 @@
 // k_tsep_envelope / k_speed_envelope / k_ang_envelope / k_accel_envelope / k_jerk_envelope on Y and t_star, any degree up to 31.
 #include <algorithm>
 #include <cfloat>
+#include <utility>
 
 #include "obtg_internal.h"
 #include "md_device.h"
@@ -528,79 +529,48 @@ __global__ __launch_bounds__(kWave) void k_ang_rows(const AngExParams q, const i
 }
 
 // =====================================================================================
-//  the curvature rows: kappa = num / den^(3/2) is not a polynomial, and its polynomial form has 6n + 1 coefficients -- more
-//  than a row of lanes from degree 11 on -- so the family has a search of its own over the two polynomials at once
-//  (include/obtg.h obtg_curvature_true_min states the contract; DESIGN.md 4.21 the reasoning).
+//  the curvature rows, planar (dim 2) and in space (dim 3): kappa = mag / den^(3/2) is not a polynomial -- the planar one's
+//  polynomial form has 6n + 1 coefficients, more than a row of lanes from degree 11 on; the norm of the space one's numerator
+//  has none -- so the two families have a search of their own over an item's NP polynomials at once, den last
+//  (include/obtg.h obtg_curvature_true_min and obtg_space_curvature_true_min state the contracts; DESIGN.md 4.21, 4.22 the
+//  reasoning).  One body, written over a policy that says what a family's own is (PlanarCurv, SpaceCurv3 below):
 //
-//  An item is (row, vehicle, side); sigma = +1 / -1 for side 0 / 1 multiplies num once, when the coefficients are formed, and
-//  the search MAXIMISES sigma kappa.  The shape is wave_search's: the first step one lane per item, an item that needs the
-//  search gets the wave, lane k holds (sigma num_k, den_k), a de Casteljau level is the same pair of averages on both, the
-//  pieces are taken as wave_search takes them, waiting sub-curves are frames of 2K + 3 doubles (num | den | bound, t0, width)
-//  in LDS.  Incumbent U: the largest sigma kappa met at an end of [0, 1] or at a bisection midpoint (cv_kappa), from 0 when
-//  the row clamps.  Upper bound of a node (cv_node_bound): the tangent of the convex den^(3/2) at the node's mid-range.
-//  A node with bound - U <= eps_rel max(max_curv, |U|) is closed; of two open children the one with the larger bound is followed.
+//    planar   NP = 2: (sigma num, den), num = x' y'' - y' x''.  An item is (row, vehicle, side); sigma = +1 / -1 for side 0 / 1
+//             multiplies num once, when the coefficients are formed, and the search MAXIMISES sigma kappa.  mag = sigma num.
+//    space    NP = 4: (wx, wy, wz, den), w = c' x c''.  An item is (row, vehicle); mag = |(wx, wy, wz)|, the norm of a vector
+//             of polynomials: without a sign, so no sides and no clamp logic, and the incumbent starts at 0.
+//
+//  The shape is wave_search's: the first step one lane per item, an item that needs the search gets the wave, lane k holds
+//  coefficient k of the NP polynomials, a de Casteljau level is the same pair of averages on each of them, the pieces are taken
+//  as wave_search takes them, waiting sub-curves are frames of NP K + 3 doubles (the polynomials | bound, t0, width) in LDS.
+//  Incumbent U: the largest value met at an end of [0, 1] or at a bisection midpoint (curv_kappa).  Upper bound of a node
+//  (curv_node_bound): the tangent of the convex den^(3/2) at the node's mid-range under every coefficient's mag, which for the
+//  space family bounds |w(t)| by the norm's convexity, |w(t)| <= sum |w_k| B_k(t).  A node with bound - U <= the family's
+//  tolerance is closed; of two open children the one with the larger bound is followed.
 // =====================================================================================
-constexpr int kCvWaves = 1;           // waves per workgroup: K = 63 is 33 KB of frames per wave, and the in-register first
-                                      // step wants the whole register file of a SIMD lane (launch bound 64: 512 VGPRs)
+constexpr int kCvWaves = 1;           // waves per workgroup: K = 63 is 33 KB (planar) or 64 KB (space) of frames per wave, and the
+                                      // in-register first step wants the whole register file of a SIMD lane (launch bound 64: 512 VGPRs)
 constexpr int kCvMaxNC = 32;
 
 struct CvOut {
     double val, t;                     // the incumbent and where it was met
-    int nodes, status;
+    int status;
 };
 
 struct CurvParams {
-    const double* __restrict__ Y;      // [items / 2][2][nc]: the vehicles (curves) in item order
+    const double* __restrict__ Y;      // [curves][DIM][nc]: the vehicles (curves) in item order, SIDES items per curve
     const double* __restrict__ tab;    // C(n, .)[n+1], then 1 / C(2n, .)[2n+1] (capi.cpp ang_rows_table)
-    const double* __restrict__ rows;   // [items / 2][2][2n+1], num then den (k_curv_rows): the workspace form's operand
-    double* __restrict__ val;          // [items]: max_curv - m_sigma;  free curves: k_max[items / 2]
-    double* __restrict__ t;            // [items] nullable;             free curves: t_max[items / 2]
-    double* __restrict__ val1;         // free curves: k_min[items / 2], t_min[items / 2]; null otherwise
+    const double* __restrict__ rows;   // [curves][NP][2n+1], den last (k_curv_rows, k_scurv_rows): the workspace form's operand
+    double* __restrict__ val;          // [items]: max_curv - the maximum;  free curves: k_max[curves]
+    double* __restrict__ t;            // [items] nullable;                 free curves: t_max[curves]
+    double* __restrict__ val1;         // free planar curves: k_min[curves], t_min[curves]; null otherwise
     double* __restrict__ t1;
-    int* __restrict__ nodes;           // [items] nullable
     int* __restrict__ status;          // [items] nullable
-    double* __restrict__ jac;          // [items][2][nc] (the envelope forms)
+    double* __restrict__ jac;          // [items][DIM][nc] (the envelope forms)
     long M;                            // items
-    int nc, max_nodes;
-    double W, eps_rel;                 // W = max_curv; free curves: 0, and the incumbent does not start from 0
+    int nc, max_nodes, free_curve;     // free_curve: the extrema themselves are written (obtg_bern_[space_]curvature, W = 0), no clamp
+    double W, eps_rel;                 // W = max_curv
 };
-
-// sigma kappa at a point, NaN where the point offers no incumbent: den <= 0, or a quotient that is not finite
-__device__ __forceinline__ double cv_kappa(double num, double den)
-{
-    if (!(den > 0.0)) return __builtin_nan("");
-    const double k = num / (den * __builtin_sqrt(den));
-    return fabs(k) <= DBL_MAX ? k : __builtin_nan("");
-}
-// (a free curve's incumbent is -inf until a point offers a value: it does not enter the tolerance, and the search goes on)
-__device__ __forceinline__ double cv_tol(double W, double eps_rel, double U) { return eps_rel * fmax(W, U > -INFINITY ? fabs(U) : 0.0); }
-
-// The bound of a node from what its coefficients reduce to.  One coefficient's share, given the node's dmin and dmax:
-// d0 = 0.5 (dmin + dmax), g_k = fma(1.5 sqrt(d0), den_k, -0.5 (d0 sqrt(d0))) is the tangent of den^(3/2) at d0 -- below the
-// convex function, so sum g_k B_k(t) <= den(t)^(3/2) -- and lambda g_k - num_k >= 0 for EVERY k gives sigma kappa <= lambda.
-// A coefficient with num_k <= 0 meets that for every lambda >= 0 only if its g_k >= 0, so the rule needs g > 0 at dmin (g is
-// increasing in den: that is every g_k > 0; it fails once dmax >= 5 dmin, where the tangent at the mid-range is below 0 at
-// dmin).  Then the bound is the largest num_k / g_k over num_k > 0, which is > 0.  +inf where g at dmin is <= 0 or dmin <= 0;
-// -inf stands for "no num_k > 0" (the clamp or cv_chord_ratio answers that case).  max is exact, so the order of the reduction does not enter.
-__device__ __forceinline__ double cv_ratio(double num, double den, double dmin, double dmax)
-{
-    if (!(num > 0.0)) return -INFINITY;
-    if (!(dmin > 0.0)) return INFINITY;
-    const double d0 = 0.5 * (dmin + dmax), s0 = __builtin_sqrt(d0);
-    const double a = 1.5 * s0, c = -0.5 * (d0 * s0);
-    return fma(a, dmin, c) > 0.0 ? num / fma(a, den, c) : INFINITY;
-}
-// No num_k > 0 on the node.  A clamped row: sigma kappa <= 0 there, the bound is 0.  A free curve needs a bound below 0 that
-// converges as fast: the chord of den^(3/2) over [dmin, dmax] lies above it, h_k = fma(slope, den_k - dmin, dmin sqrt(dmin)),
-// slope = (dmax + sqrt(dmax dmin) + dmin) / (sqrt(dmax) + sqrt(dmin)), and num / den^(3/2) <= num / h for num <= 0: the
-// bound is the largest num_k / h_k (dmin <= 0: 0).
-__device__ __forceinline__ double cv_chord_ratio(double num, double den, double dmin, double dmax)
-{
-    if (!(dmin > 0.0)) return 0.0;
-    const double a = __builtin_sqrt(dmax), b = __builtin_sqrt(dmin);
-    const double slope = ((dmax + a * b) + dmin) / (a + b);
-    return num / fma(slope, den - dmin, dmin * b);
-}
 
 __device__ __forceinline__ double cv_wave_max(double v)
 {
@@ -608,415 +578,264 @@ __device__ __forceinline__ double cv_wave_max(double v)
     for (int o = 32; o; o >>= 1) v = fmax(v, __shfl_xor(v, o));
     return v;
 }
-// the whole wave on one node: lane k < K holds (num_k, den_k); the same value in every lane
-__device__ __forceinline__ double cv_node_bound(double num, double den, bool act, bool clamp)
+
+// mag / den^(3/2) at a point, NaN where the point offers no incumbent: den <= 0, or a quotient that is not finite
+__device__ __forceinline__ double curv_kappa(double mag, double den)
 {
-    const double dmin = ex_wave_min(act ? den : INFINITY), dmax = cv_wave_max(act ? den : -INFINITY);
-    double ub = cv_wave_max(act ? cv_ratio(num, den, dmin, dmax) : -INFINITY);
-    if (ub == -INFINITY) ub = clamp ? 0.0 : cv_wave_max(act ? cv_chord_ratio(num, den, dmin, dmax) : -INFINITY);
-    return ub;
+    if (!(den > 0.0)) return __builtin_nan("");
+    const double k = mag / (den * __builtin_sqrt(den));
+    return fabs(k) <= DBL_MAX ? k : __builtin_nan("");
 }
 
-// The first step of an item (node 1), one lane: get(k) is its (sigma num_k, den_k).  true: `o` is the item's answer;
-// false: the search has to run from (o.val, o.t) as the incumbent.
-template <int KC, class Get>
-__device__ __forceinline__ bool cv_first(const Get& get, int K, double W, double eps_rel, bool clamp, CvOut& o)
+// One coefficient's share of a node's bound, given the node's dmin and dmax: d0 = 0.5 (dmin + dmax),
+// g_k = fma(1.5 sqrt(d0), den_k, -0.5 (d0 sqrt(d0))) is the tangent of den^(3/2) at d0 -- below the convex function, so
+// sum g_k B_k(t) <= den(t)^(3/2) -- and lambda g_k - mag_k >= 0 for EVERY k gives kappa <= lambda.  A coefficient with
+// mag_k <= 0 meets that for every lambda >= 0 only if its g_k >= 0, and a g_k <= 0 beside a positive mag_k breaks it, so the
+// rule needs g > 0 at dmin (g is increasing in den: that is every g_k > 0; it fails once dmax >= 5 dmin, where the tangent at
+// the mid-range is below 0 at dmin).  Then the bound is the largest mag_k / g_k over mag_k > 0.  +inf where g at dmin is <= 0 or
+// dmin <= 0.  What a coefficient with mag_k <= 0 contributes is the family's (ratio).  max is exact, so the order of the
+// reduction does not enter.
+__device__ __forceinline__ double curv_tangent_ratio(double mag, double den, double dmin, double dmax)
 {
-    if (KC > 0) K = KC;
-    bool bad = false, any = false;
-    double dmin = INFINITY, dmax = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < (KC > 0 ? KC : K); ++k) {
-        const NumDen c = get(k);
-        bad = bad || !(fabs(c.num) <= DBL_MAX) || !(fabs(c.den) <= DBL_MAX);
-        any = any || c.num != 0.0;
-        dmin = fmin(dmin, c.den); dmax = fmax(dmax, c.den);
-    }
-    o.status = OBTG_MD_OK;
-    if (bad) { o.val = o.t = __builtin_nan(""); o.nodes = 0; return true; }
-    o.nodes = 1;
-    o.val = 0.0; o.t = 0.0;
-    if (!any) return true;                  // num == 0 identically: a straight path, degree 1, a vehicle at rest
-    if (!clamp) o.val = -INFINITY;
-    const NumDen c0 = get(0), c1 = get(K - 1);
-    const double k0 = cv_kappa(c0.num, c0.den), k1 = cv_kappa(c1.num, c1.den);
-    if (k0 > o.val) { o.val = k0; o.t = 0.0; }
-    if (k1 > o.val) { o.val = k1; o.t = 1.0; }
-    double ub = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < (KC > 0 ? KC : K); ++k) { const NumDen c = get(k); ub = fmax(ub, cv_ratio(c.num, c.den, dmin, dmax)); }
-    if (ub == -INFINITY) {
-        ub = 0.0;
-        if (!clamp) {
-            ub = -INFINITY;
-#pragma unroll
-            for (int k = 0; k < (KC > 0 ? KC : K); ++k) { const NumDen c = get(k); ub = fmax(ub, cv_chord_ratio(c.num, c.den, dmin, dmax)); }
-        }
-    }
-    return !(ub - o.val > cv_tol(W, eps_rel, o.val));
-}
-
-// The whole wave on ONE item (every lane must be here).  Lane k < K holds (bn, bd) = (sigma num_k, den_k); (U, tU): the first
-// step's incumbent.  stk: this wave's kExStack x (2K + 3) doubles.  Every scalar below is the same in all lanes.
-__device__ __forceinline__ CvOut cv_wave_search(double bn, double bd, const int K, const double W, const double eps_rel,
-                                                const bool clamp, double U, double tU, const int max_nodes, double* stk)
-{
-    const int lane = threadIdx.x & (kWave - 1);
-    const bool act = lane < K;
-    const int pitch = 2 * K + 3;
-    double t0 = 0.0, w = 1.0;
-    int nodes = 1, sp = 0, status = OBTG_MD_OK;
-    for (;;) {
-        if (nodes + 2 > max_nodes) { status = OBTG_MD_NODE_CAP; break; }
-        // deCasteljau at 1/2 of both polynomials, both pieces: left[r] is lane 0's value after level r, right[i] lane i's
-        double ln = bn, ld = bd, mn = ex_lane0(bn), md = ex_lane0(bd);
-        for (int r = 1; r < K; ++r) {
-            const double upn = wave_next_lane(bn), upd = wave_next_lane(bd);
-            if (lane <= K - 1 - r) { bn = 0.5 * bn + 0.5 * upn; bd = 0.5 * bd + 0.5 * upd; }
-            mn = ex_lane0(bn); md = ex_lane0(bd);
-            if (lane == r) { ln = mn; ld = md; }
-        }
-        const double hw = 0.5 * w, tm = t0 + hw;
-        nodes += 2;
-        const double km = cv_kappa(mn, md);
-        if (km > U) { U = km; tU = tm; }
-        const double tol = cv_tol(W, eps_rel, U);
-        const double ubL = cv_node_bound(ln, ld, act, clamp), ubR = cv_node_bound(bn, bd, act, clamp);
-        const bool aliveL = ubL - U > tol, aliveR = ubR - U > tol;
-        if (aliveL && aliveR) {
-            if (sp == kExStack) { status = OBTG_MD_DEPTH_CAP; break; }
-            const bool go_left = ubL >= ubR;
-            double* f = stk + sp * pitch;
-            if (act) { f[lane] = go_left ? bn : ln; f[K + lane] = go_left ? bd : ld; }
-            if (lane == 0) { f[2 * K] = go_left ? ubR : ubL; f[2 * K + 1] = go_left ? tm : t0; f[2 * K + 2] = hw; }
-            ++sp;
-            if (go_left) { bn = ln; bd = ld; } else t0 = tm;
-            w = hw;
-        } else if (aliveL) { bn = ln; bd = ld; w = hw; }
-        else if (aliveR) { t0 = tm; w = hw; }
-        else {
-            bool found = false;
-            wave_sync();
-            while (sp > 0) {
-                --sp;
-                const double* f = stk + sp * pitch;
-                if (f[2 * K] - U > tol) {
-                    bn = act ? f[lane] : 0.0; bd = act ? f[K + lane] : 0.0;
-                    t0 = f[2 * K + 1]; w = f[2 * K + 2];
-                    found = true;
-                    break;
-                }
-            }
-            wave_sync();
-            if (!found) break;
-        }
-    }
-    CvOut o;
-    o.val = U; o.t = tU; o.nodes = nodes; o.status = status;
-    return o;
-}
-
-// An item's answer to memory: row = max_curv - m_sigma; a free curve's sides are k_max = m_+ and k_min = -m_-.  A free
-// curve on which no point offered an incumbent (den <= 0 at every point met) has no curvature to report: NaN.
-__device__ __forceinline__ double cv_store(const CurvParams& q, long item, CvOut o)
-{
-    double v;
-    if (q.val1) {
-        if (o.val == -INFINITY) o.val = o.t = __builtin_nan("");
-        const long m = item >> 1;
-        v = (item & 1) ? -o.val : o.val;
-        ((item & 1) ? q.val1 : q.val)[m] = v;
-        ((item & 1) ? q.t1 : q.t)[m] = o.t;
-    } else {
-        v = q.W - o.val;
-        q.val[item] = v;
-        if (q.t) q.t[item] = o.t;
-    }
-    if (q.nodes) q.nodes[item] = o.nodes;
-    if (q.status) q.status[item] = o.status;
-    return v;
-}
-
-// The item's block from Y at the t_star and the row value an earlier step left: zero where the row IS max_curv (m_sigma = 0:
-// the clamp, a straight path, a vehicle at rest), NaN for a NaN t_star, bern_device.h curvature_envelope_block otherwise.
-template <int NCMAX>
-__device__ __forceinline__ void cv_envelope(const CurvParams& q, long item, int nc, double row, double t)
-{
-    double* o = q.jac + (size_t)item * (2 * nc);
-    if (row == q.W || !(t == t)) {
-        const double fill = t == t ? 0.0 : t;
-        for (int e = 0; e < 2 * nc; ++e) o[e] = fill;
-        return;
-    }
-    curvature_envelope_block<NCMAX>(q.Y + (size_t)(item >> 1) * (2 * nc), nc, (item & 1) ? -1.0 : 1.0, t, o);
-}
-
-// What both kernel forms do once an item's first step is known: the wave on every item that needs it, in lane order; `load`
-// puts item src's coefficients into the lanes.
-template <class Load>
-__device__ __forceinline__ void cv_search_items(const CurvParams& q, const Load& load, int K, bool need, CvOut& mine, double* stk)
-{
-    const int lane = threadIdx.x & (kWave - 1);
-    const bool clamp = q.val1 == nullptr;
-    unsigned long long mask = __ballot(need);
-    while (mask) {
-        const int src = __ffsll((long long)mask) - 1;
-        mask &= mask - 1;
-        double bn = 0.0, bd = 0.0;
-        load(src, bn, bd);
-        const CvOut o = cv_wave_search(bn, bd, K, q.W, q.eps_rel, clamp, ex_lane(mine.val, src), ex_lane(mine.t, src), q.max_nodes, stk);
-        if (lane == src) mine = o;
-    }
-}
-
-// Coefficients in registers, one launch (the counts of OBTG_NC_CURV_LIST): AngRows::coeffs on T = 1 with
-// curvature_row_coeff, then the steps above; JAC: every lane writes its own block.
-template <int NC, bool JAC>
-__global__ __launch_bounds__(kCvWaves * kWave) void k_curv_true_min(const CurvParams q)
-{
-    constexpr int N = NC - 1, L = 2 * NC - 1;
-    extern __shared__ double lds[];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    double* stk = lds + (size_t)wave * kExStack * (2 * L + 3);
-    const long item = ((long)blockIdx.x * kCvWaves + wave) * kWave + lane;
-    const bool valid = item < q.M;
-    const long it = valid ? item : q.M - 1;
-    const double sigma = (it & 1) ? -1.0 : 1.0;
-    const double* v = q.Y + (size_t)(it >> 1) * (2 * NC);
-    const ctab_t Cn = as_ctab(q.tab), Sk = Cn + NC;
-    double num[L], den[L];
-    {
-        double u1[2][NC], u2[2][NC];           // C(n, j) x'_j, C(n, j) y'_j;  C(n, j) x''_j, C(n, j) y''_j
-#pragma unroll
-        for (int d = 0; d < 2; ++d) {
-            double x[NC], x1[NC];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) x[c] = v[d * NC + c];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) x1[c] = diff_elev1_at(x, c, N, (double)N);
-#pragma unroll
-            for (int c = 0; c < NC; ++c) u2[d][c] = Cn[c] * diff_elev1_at(x1, c, N, (double)N);
-#pragma unroll
-            for (int c = 0; c < NC; ++c) u1[d][c] = Cn[c] * x1[c];
-        }
-#pragma unroll
-        for (int k = 0; k < L; ++k) {
-            const NumDen c = curvature_row_coeff(u1[0], u1[1], u2[0], u2[1], N, k, Sk[k]);
-            num[k] = sigma * c.num; den[k] = c.den;
-        }
-    }
-    CvOut mine;
-    const bool need = !cv_first<L>([&](int k) { NumDen c; c.num = num[k]; c.den = den[k]; return c; }, L, q.W, q.eps_rel,
-                                   q.val1 == nullptr, mine) && valid;
-    cv_search_items(q, [&](int src, double& bn, double& bd) {
-#pragma unroll
-        for (int k = 0; k < L; ++k) {
-            const double a = ex_lane(num[k], src), b = ex_lane(den[k], src);
-            if (lane == k) { bn = a; bd = b; }
-        }
-    }, L, need, mine, stk);
-    if (valid) {
-        const double row = cv_store(q, item, mine);
-        if (JAC) cv_envelope<NC>(q, item, NC, row, mine.t);
-    }
-}
-
-// The workspace form, any degree 1 .. 31: the coefficients are k_curv_rows' rows in memory, K = 2 nc - 1 at run time
-__global__ __launch_bounds__(kCvWaves * kWave) void k_curv_search(const CurvParams q)
-{
-    extern __shared__ double lds[];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6, K = 2 * q.nc - 1;
-    double* stk = lds + (size_t)wave * kExStack * (2 * K + 3);
-    const long item0 = ((long)blockIdx.x * kCvWaves + wave) * kWave, item = item0 + lane;
-    const bool valid = item < q.M;
-    const long it = valid ? item : q.M - 1;
-    const double sigma = (it & 1) ? -1.0 : 1.0;
-    const double* r = q.rows + (size_t)(it >> 1) * (2 * K);
-    CvOut mine;
-    const bool need = !cv_first<0>([&](int k) { NumDen c; c.num = sigma * r[k]; c.den = r[K + k]; return c; }, K, q.W, q.eps_rel,
-                                   q.val1 == nullptr, mine) && valid;
-    cv_search_items(q, [&](int src, double& bn, double& bd) {
-        const long is = item0 + src;
-        const double* rs = q.rows + (size_t)(is >> 1) * (2 * K);
-        if (lane < K) { bn = ((is & 1) ? -1.0 : 1.0) * rs[lane]; bd = rs[K + lane]; }
-    }, K, need, mine, stk);
-    if (valid) cv_store(q, item, mine);
-}
-
-// The blocks alone, from Y, the rows' values and their t_star: one item per lane, nc <= kCvMaxNC at run time
-__global__ __launch_bounds__(kEnvThreads) void k_curv_envelope(const CurvParams q)
-{
-    const long item = (long)blockIdx.x * kEnvThreads + threadIdx.x;
-    if (item < q.M) cv_envelope<kCvMaxNC>(q, item, q.nc, q.val[item], q.t[item]);
-}
-
-// The curvature rows' polynomials to memory, any degree 1 .. 31: k_ang_rows on T = 1 without a side -- one wave per vehicle
-// (curve), lane k forms coefficient k of num and of den with the function the in-register kernels use: out[.][2][2n+1].
-__global__ __launch_bounds__(kWave) void k_curv_rows(const CurvParams q, double* __restrict__ out)
-{
-    __shared__ double sh[6][kCvMaxNC];       // x, y -> u1x, u1y after the last read; x', y'; u2x, u2y
-    const long veh = blockIdx.x;
-    const int lane = threadIdx.x, nc = q.nc, n = nc - 1, L = 2 * n + 1;
-    const double val = (double)n;
-    const double* v = q.Y + (size_t)veh * (2 * nc);
-    const double* Cn = q.tab;
-    const double* Sk = Cn + nc;
-    if (lane < nc) { sh[0][lane] = v[lane]; sh[1][lane] = v[nc + lane]; }
-    __syncthreads();
-    if (lane < nc)
-        for (int d = 0; d < 2; ++d) sh[2 + d][lane] = diff_elev1_at(sh[d], lane, n, val);
-    __syncthreads();
-    if (lane < nc)
-        for (int d = 0; d < 2; ++d) {
-            sh[4 + d][lane] = Cn[lane] * diff_elev1_at(sh[2 + d], lane, n, val);
-            sh[d][lane] = Cn[lane] * sh[2 + d][lane];
-        }
-    __syncthreads();
-    if (lane < L) {
-        const NumDen c = curvature_row_coeff(sh[0], sh[1], sh[4], sh[5], n, lane, Sk[lane]);
-        out[(size_t)veh * 2 * L + lane] = c.num;
-        out[((size_t)veh * 2 + 1) * L + lane] = c.den;
-    }
-}
-
-// =====================================================================================
-//  the space-curvature rows (dim 3): kappa = |w| / den^(3/2), w = c' x c'' three polynomials, den = |c'|^2.  |w| is the norm
-//  of a vector of polynomials: not a polynomial, without a sign -- one row per vehicle, no sides, no clamp logic, the
-//  incumbent starts at 0 (include/obtg.h obtg_space_curvature_true_min states the contract; DESIGN.md 4.22 the reasoning).
-//
-//  The shape is the curvature rows' above: the first step one lane per item, an item that needs the search gets the wave,
-//  lane k holds (wx_k, wy_k, wz_k, den_k), a de Casteljau level is the same average on all four, waiting sub-curves are
-//  frames of 4K + 3 doubles (wx | wy | wz | den | bound, t0, width) in LDS.  Upper bound of a node (sc_node_bound): with
-//  nu_k = |(wx_k, wy_k, wz_k)| the norm's convexity gives |w(t)| <= sum nu_k B_k(t), and the tangent of den^(3/2) at the
-//  node's mid-range bounds the denominator from below as cv_ratio's does.
-// =====================================================================================
-struct SpaceCurvParams {
-    const double* __restrict__ Y;      // [items][3][nc]: the vehicles (curves) in item order
-    const double* __restrict__ tab;    // C(n, .)[n+1], then 1 / C(2n, .)[2n+1] (capi.cpp ang_rows_table)
-    const double* __restrict__ rows;   // [items][4][2n+1], wx, wy, wz, den (k_scurv_rows): the workspace form's operand
-    double* __restrict__ val;          // [items]: max_curv - max kappa;  free curves: max kappa
-    double* __restrict__ t;            // [items] nullable
-    int* __restrict__ status;          // [items] nullable
-    double* __restrict__ jac;          // [items][3][nc] (the envelope forms)
-    long M;                            // items
-    int nc, max_nodes, free_curve;     // free_curve: the value written is the maximum itself (obtg_bern_space_curvature, W = 0)
-    double W, eps_rel;                 // W = max_curv
-};
-
-// kappa at a point, NaN where the point offers no incumbent: den <= 0, or a value that is not finite
-__device__ __forceinline__ double sc_kappa(const SpaceCurv& c)
-{
-    if (!(c.den > 0.0)) return __builtin_nan("");
-    const double k = space_curvature_norm(c.wx, c.wy, c.wz) / (c.den * __builtin_sqrt(c.den));
-    return k <= DBL_MAX ? k : __builtin_nan("");
-}
-__device__ __forceinline__ double sc_tol(double W, double eps_rel, double U) { return eps_rel * fmax(W, U); }
-
-// One coefficient's share of a node's bound, nu = |(wx_k, wy_k, wz_k)| >= 0: 0 where nu is 0 (the coefficient meets
-// lambda g_k - nu_k >= 0 for every lambda >= 0 wherever the rule holds, and a node of such coefficients alone has w == 0);
-// else +inf if dmin <= 0 or the tangent at the mid-range is <= 0 at dmin -- a g_k <= 0 beside a positive nu_k breaks the
-// inequality --; else nu / g_k with cv_ratio's g_k.
-__device__ __forceinline__ double sc_ratio(double nu, double den, double dmin, double dmax)
-{
-    if (nu == 0.0) return 0.0;
     if (!(dmin > 0.0)) return INFINITY;
     const double d0 = 0.5 * (dmin + dmax), s0 = __builtin_sqrt(d0);
     const double a = 1.5 * s0, c = -0.5 * (d0 * s0);
-    return fma(a, dmin, c) > 0.0 ? nu / fma(a, den, c) : INFINITY;
-}
-// the whole wave on one node: lane k < K holds coefficient k; the same value in every lane
-__device__ __forceinline__ double sc_node_bound(const SpaceCurv& b, bool act)
-{
-    const double dmin = ex_wave_min(act ? b.den : INFINITY), dmax = cv_wave_max(act ? b.den : -INFINITY);
-    return cv_wave_max(act ? sc_ratio(space_curvature_norm(b.wx, b.wy, b.wz), b.den, dmin, dmax) : 0.0);
+    return fma(a, dmin, c) > 0.0 ? mag / fma(a, den, c) : INFINITY;
 }
 
-// The first step of an item (node 1), one lane: get(k) is its coefficient k.  true: `o` is the item's answer; false: the
-// search has to run from (o.val, o.t) as the incumbent.
-template <int KC, class Get>
-__device__ __forceinline__ bool sc_first(const Get& get, int K, double W, double eps_rel, CvOut& o)
+// A family's policy.  NP polynomials per item, den last; DIM coordinates; SIDES items per curve (2: polynomial 0 is signed).
+//   curve, sigma     the item's curve and sign
+//   coeff            coefficient k of the curve's polynomials, unsigned, from u1 = C(n, .) c', u2 = C(n, .) c'': THE definition
+//                    of the rows (bern_device.h), for the in-register kernel and the rows kernel alike
+//   mag              a coefficient's or a point's numerator
+//   start, tol       the incumbent before any point is met; when bound - U closes a node
+//   bound            a node's bound from max_over(share, idle): the largest share(mag_k, den_k) over its coefficients, idle
+//                    where there is none (a lane past K)
+//   store            the item's answer to memory; returns the row's value
+//   block            the item's envelope block (bern_device.h)
+struct PlanarCurv {
+    static constexpr int NP = 2, DIM = 2, SIDES = 2;
+    static __device__ __forceinline__ long curve(long item) { return item >> 1; }
+    static __device__ __forceinline__ double sigma(long item) { return (item & 1) ? -1.0 : 1.0; }
+    template <int R>
+    static __device__ __forceinline__ void coeff(const double (*u1)[R], const double (*u2)[R], int n, int k, double sk, double (&c)[NP])
+    {
+        const NumDen r = curvature_row_coeff(u1[0], u1[1], u2[0], u2[1], n, k, sk);
+        c[0] = r.num; c[1] = r.den;
+    }
+    static __device__ __forceinline__ double mag(const double (&c)[NP]) { return c[0]; }
+    // a free curve's incumbent is -inf until a point offers a value: it does not enter the tolerance, and the search goes on
+    static __device__ __forceinline__ double start(bool clamp) { return clamp ? 0.0 : -INFINITY; }
+    static __device__ __forceinline__ double tol(double W, double eps_rel, double U) { return eps_rel * fmax(W, U > -INFINITY ? fabs(U) : 0.0); }
+    // -inf stands for "no num_k > 0": the clamp or the chord answers that case
+    static __device__ __forceinline__ double ratio(double num, double den, double dmin, double dmax)
+    {
+        return num > 0.0 ? curv_tangent_ratio(num, den, dmin, dmax) : -INFINITY;
+    }
+    // No num_k > 0 on the node.  A clamped row: sigma kappa <= 0 there, the bound is 0.  A free curve needs a bound below 0 that
+    // converges as fast: the chord of den^(3/2) over [dmin, dmax] lies above it, h_k = fma(slope, den_k - dmin, dmin sqrt(dmin)),
+    // slope = (dmax + sqrt(dmax dmin) + dmin) / (sqrt(dmax) + sqrt(dmin)), and num / den^(3/2) <= num / h for num <= 0: the
+    // bound is the largest num_k / h_k (dmin <= 0: 0).
+    static __device__ __forceinline__ double chord_ratio(double num, double den, double dmin, double dmax)
+    {
+        if (!(dmin > 0.0)) return 0.0;
+        const double a = __builtin_sqrt(dmax), b = __builtin_sqrt(dmin);
+        const double slope = ((dmax + a * b) + dmin) / (a + b);
+        return num / fma(slope, den - dmin, dmin * b);
+    }
+    template <class MaxOver>
+    static __device__ __forceinline__ double bound(const MaxOver& max_over, double dmin, double dmax, bool clamp)
+    {
+        double ub = max_over([&](double num, double den) { return ratio(num, den, dmin, dmax); }, -INFINITY);
+        if (ub == -INFINITY)
+            ub = clamp ? 0.0 : max_over([&](double num, double den) { return chord_ratio(num, den, dmin, dmax); }, -INFINITY);
+        return ub;
+    }
+    // row = max_curv - m_sigma; a free curve's sides are k_max = m_+ and k_min = -m_-.  A free curve on which no point offered
+    // an incumbent (den <= 0 at every point met) has no curvature to report: NaN.
+    static __device__ __forceinline__ double store(const CurvParams& q, long item, CvOut o)
+    {
+        double v;
+        if (q.free_curve) {
+            if (o.val == -INFINITY) o.val = o.t = __builtin_nan("");
+            const long m = item >> 1;
+            v = (item & 1) ? -o.val : o.val;
+            ((item & 1) ? q.val1 : q.val)[m] = v;
+            ((item & 1) ? q.t1 : q.t)[m] = o.t;
+        } else {
+            v = q.W - o.val;
+            q.val[item] = v;
+            if (q.t) q.t[item] = o.t;
+        }
+        if (q.status) q.status[item] = o.status;
+        return v;
+    }
+    template <int NCMAX>
+    static __device__ __forceinline__ void block(const double* y, int nc, double sigma, double t, double* o)
+    {
+        curvature_envelope_block<NCMAX>(y, nc, sigma, t, o);
+    }
+};
+
+struct SpaceCurv3 {
+    static constexpr int NP = 4, DIM = 3, SIDES = 1;
+    static __device__ __forceinline__ long curve(long item) { return item; }
+    static __device__ __forceinline__ double sigma(long) { return 1.0; }
+    template <int R>
+    static __device__ __forceinline__ void coeff(const double (*u1)[R], const double (*u2)[R], int n, int k, double sk, double (&c)[NP])
+    {
+        const SpaceCurv r = space_curvature_row_coeff(u1[0], u1[1], u1[2], u2[0], u2[1], u2[2], n, k, sk);
+        c[0] = r.wx; c[1] = r.wy; c[2] = r.wz; c[3] = r.den;
+    }
+    static __device__ __forceinline__ double mag(const double (&c)[NP]) { return space_curvature_norm(c[0], c[1], c[2]); }
+    static __device__ __forceinline__ double start(bool) { return 0.0; }
+    static __device__ __forceinline__ double tol(double W, double eps_rel, double U) { return eps_rel * fmax(W, U); }
+    // 0 where nu is 0: the coefficient meets lambda g_k - nu_k >= 0 for every lambda >= 0 wherever the rule holds, and a node of
+    // such coefficients alone has w == 0
+    static __device__ __forceinline__ double ratio(double nu, double den, double dmin, double dmax)
+    {
+        return nu == 0.0 ? 0.0 : curv_tangent_ratio(nu, den, dmin, dmax);
+    }
+    template <class MaxOver>
+    static __device__ __forceinline__ double bound(const MaxOver& max_over, double dmin, double dmax, bool)
+    {
+        return max_over([&](double nu, double den) { return ratio(nu, den, dmin, dmax); }, 0.0);
+    }
+    // row = max_curv - max kappa (a free curve: max kappa itself)
+    static __device__ __forceinline__ double store(const CurvParams& q, long item, const CvOut& o)
+    {
+        const double v = q.free_curve ? o.val : q.W - o.val;
+        q.val[item] = v;
+        if (q.t) q.t[item] = o.t;
+        if (q.status) q.status[item] = o.status;
+        return v;
+    }
+    template <int NCMAX>
+    static __device__ __forceinline__ void block(const double* y, int nc, double, double t, double* o)
+    {
+        space_curvature_envelope_block<NCMAX>(y, nc, t, o);
+    }
+};
+
+// f(p) for p = 0 .. NP - 1 with p a constant of the language: no loop is left for the optimiser to unroll
+template <class F, int... P>
+__device__ __forceinline__ void curv_each_(const F& f, std::integer_sequence<int, P...>) { (f(std::integral_constant<int, P>()), ...); }
+template <int NP, class F>
+__device__ __forceinline__ void curv_each(const F& f) { curv_each_(f, std::make_integer_sequence<int, NP>()); }
+
+// the whole wave on one node: lane k < K holds coefficient k; the same value in every lane
+template <class Fam>
+__device__ __forceinline__ double curv_node_bound(const double (&b)[Fam::NP], bool act, bool clamp)
 {
+    const double den = b[Fam::NP - 1];
+    const double dmin = ex_wave_min(act ? den : INFINITY), dmax = cv_wave_max(act ? den : -INFINITY);
+    return Fam::bound([&](auto share, double idle) { return cv_wave_max(act ? share(Fam::mag(b), den) : idle); }, dmin, dmax, clamp);
+}
+
+// The first step of an item (node 1), one lane: get(k, c) puts its coefficient k into c (signed).  true: `o` is the item's
+// answer; false: the search has to run from (o.val, o.t) as the incumbent.
+template <class Fam, int KC, class Get>
+__device__ __forceinline__ bool curv_first(const Get& get, int K, double W, double eps_rel, bool clamp, CvOut& o)
+{
+    constexpr int NP = Fam::NP;
     if (KC > 0) K = KC;
     bool bad = false, any = false;
     double dmin = INFINITY, dmax = -INFINITY;
 #pragma unroll
     for (int k = 0; k < (KC > 0 ? KC : K); ++k) {
-        const SpaceCurv c = get(k);
-        bad = bad || !(fabs(c.wx) <= DBL_MAX) || !(fabs(c.wy) <= DBL_MAX) || !(fabs(c.wz) <= DBL_MAX) || !(fabs(c.den) <= DBL_MAX);
-        any = any || c.wx != 0.0 || c.wy != 0.0 || c.wz != 0.0;
-        dmin = fmin(dmin, c.den); dmax = fmax(dmax, c.den);
+        double c[NP];
+        get(k, c);
+#pragma unroll
+        for (int p = 0; p < NP; ++p) bad = bad || !(fabs(c[p]) <= DBL_MAX);
+#pragma unroll
+        for (int p = 0; p < NP - 1; ++p) any = any || c[p] != 0.0;
+        dmin = fmin(dmin, c[NP - 1]); dmax = fmax(dmax, c[NP - 1]);
     }
     o.status = OBTG_MD_OK;
-    if (bad) { o.val = o.t = __builtin_nan(""); o.nodes = 0; return true; }
-    o.nodes = 1;
+    if (bad) { o.val = o.t = __builtin_nan(""); return true; }
     o.val = 0.0; o.t = 0.0;
-    if (!any) return true;                  // w == 0 identically: a straight path, degree 1, a vehicle at rest
-    const double k0 = sc_kappa(get(0)), k1 = sc_kappa(get(K - 1));
+    if (!any) return true;                  // the numerator == 0 identically: a straight path, degree 1, a vehicle at rest
+    o.val = Fam::start(clamp);
+    double c0[NP], c1[NP];
+    get(0, c0); get(K - 1, c1);
+    const double k0 = curv_kappa(Fam::mag(c0), c0[NP - 1]), k1 = curv_kappa(Fam::mag(c1), c1[NP - 1]);
     if (k0 > o.val) { o.val = k0; o.t = 0.0; }
     if (k1 > o.val) { o.val = k1; o.t = 1.0; }
-    double ub = 0.0;
+    const double ub = Fam::bound([&](auto share, double idle) {
+        double m = idle;
 #pragma unroll
-    for (int k = 0; k < (KC > 0 ? KC : K); ++k) {
-        const SpaceCurv c = get(k);
-        ub = fmax(ub, sc_ratio(space_curvature_norm(c.wx, c.wy, c.wz), c.den, dmin, dmax));
-    }
-    return !(ub - o.val > sc_tol(W, eps_rel, o.val));
+        for (int k = 0; k < (KC > 0 ? KC : K); ++k) { double c[NP]; get(k, c); m = fmax(m, share(Fam::mag(c), c[NP - 1])); }
+        return m;
+    }, dmin, dmax, clamp);
+    return !(ub - o.val > Fam::tol(W, eps_rel, o.val));
 }
 
-// The whole wave on ONE item (every lane must be here).  Lane k < K holds coefficient k in b; (U, tU): the first step's
-// incumbent.  stk: this wave's kExStack x (4K + 3) doubles.  Every scalar below is the same in all lanes.
-__device__ __forceinline__ CvOut sc_wave_search(SpaceCurv b, const int K, const double W, const double eps_rel, double U, double tU,
-                                                const int max_nodes, double* stk)
+// The whole wave on ONE item (every lane must be here).  Lane k < K holds coefficient k in b0; (U, tU): the first step's
+// incumbent.  stk: this wave's kExStack x (NP K + 3) doubles.  Every scalar below is the same in all lanes.
+template <class Fam>
+__device__ __forceinline__ CvOut curv_wave_search(const double (&b0)[Fam::NP], const int K, const double W, const double eps_rel,
+                                                  const bool clamp, double U, double tU, const int max_nodes, double* stk)
 {
+    constexpr int NP = Fam::NP;
     const int lane = threadIdx.x & (kWave - 1);
     const bool act = lane < K;
-    const int pitch = 4 * K + 3;
+    const int pitch = NP * K + 3;
+    double b[NP];                      // the search's own copy: written through the caller's array it costs registers
+#pragma unroll
+    for (int p = 0; p < NP; ++p) b[p] = b0[p];
     double t0 = 0.0, w = 1.0;
     int nodes = 1, sp = 0, status = OBTG_MD_OK;
     for (;;) {
         if (nodes + 2 > max_nodes) { status = OBTG_MD_NODE_CAP; break; }
-        // deCasteljau at 1/2 of the four polynomials, both pieces: l is lane 0's value after level r in lane r, b lane i's
-        SpaceCurv l = b, m;
-        m.wx = ex_lane0(b.wx); m.wy = ex_lane0(b.wy); m.wz = ex_lane0(b.wz); m.den = ex_lane0(b.den);
+        // deCasteljau at 1/2 of the NP polynomials, both pieces: l is lane 0's value after level r in lane r, b lane i's
+        double l[NP], m[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) { l[p] = b[p]; m[p] = ex_lane0(b[p]); }
         for (int r = 1; r < K; ++r) {
-            const double ux = wave_next_lane(b.wx), uy = wave_next_lane(b.wy), uz = wave_next_lane(b.wz), ud = wave_next_lane(b.den);
-            if (lane <= K - 1 - r) {
-                b.wx = 0.5 * b.wx + 0.5 * ux; b.wy = 0.5 * b.wy + 0.5 * uy; b.wz = 0.5 * b.wz + 0.5 * uz; b.den = 0.5 * b.den + 0.5 * ud;
-            }
-            m.wx = ex_lane0(b.wx); m.wy = ex_lane0(b.wy); m.wz = ex_lane0(b.wz); m.den = ex_lane0(b.den);
-            if (lane == r) l = m;
+            double up[NP];
+            curv_each<NP>([&](auto p) { up[p] = wave_next_lane(b[p]); });
+            const bool below = lane <= K - 1 - r;
+            curv_each<NP>([&](auto p) { b[p] = below ? 0.5 * b[p] + 0.5 * up[p] : b[p]; });
+            curv_each<NP>([&](auto p) { m[p] = ex_lane0(b[p]); });
+            if (lane == r) curv_each<NP>([&](auto p) { l[p] = m[p]; });
         }
         const double hw = 0.5 * w, tm = t0 + hw;
         nodes += 2;
-        const double km = sc_kappa(m);
+        const double km = curv_kappa(Fam::mag(m), m[NP - 1]);
         if (km > U) { U = km; tU = tm; }
-        const double tol = sc_tol(W, eps_rel, U);
-        const double ubL = sc_node_bound(l, act), ubR = sc_node_bound(b, act);
+        const double tol = Fam::tol(W, eps_rel, U);
+        const double ubL = curv_node_bound<Fam>(l, act, clamp), ubR = curv_node_bound<Fam>(b, act, clamp);
         const bool aliveL = ubL - U > tol, aliveR = ubR - U > tol;
         if (aliveL && aliveR) {
             if (sp == kExStack) { status = OBTG_MD_DEPTH_CAP; break; }
             const bool go_left = ubL >= ubR;
             double* f = stk + sp * pitch;
             if (act) {
-                f[lane] = go_left ? b.wx : l.wx; f[K + lane] = go_left ? b.wy : l.wy;
-                f[2 * K + lane] = go_left ? b.wz : l.wz; f[3 * K + lane] = go_left ? b.den : l.den;
+#pragma unroll
+                for (int p = 0; p < NP; ++p) f[p * K + lane] = go_left ? b[p] : l[p];
             }
-            if (lane == 0) { f[4 * K] = go_left ? ubR : ubL; f[4 * K + 1] = go_left ? tm : t0; f[4 * K + 2] = hw; }
+            if (lane == 0) { f[NP * K] = go_left ? ubR : ubL; f[NP * K + 1] = go_left ? tm : t0; f[NP * K + 2] = hw; }
             ++sp;
-            if (go_left) b = l; else t0 = tm;
+            if (go_left) {
+#pragma unroll
+                for (int p = 0; p < NP; ++p) b[p] = l[p];
+            } else t0 = tm;
             w = hw;
-        } else if (aliveL) { b = l; w = hw; }
-        else if (aliveR) { t0 = tm; w = hw; }
+        } else if (aliveL) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) b[p] = l[p];
+            w = hw;
+        } else if (aliveR) { t0 = tm; w = hw; }
         else {
             bool found = false;
             wave_sync();
             while (sp > 0) {
                 --sp;
                 const double* f = stk + sp * pitch;
-                if (f[4 * K] - U > tol) {
-                    b.wx = act ? f[lane] : 0.0; b.wy = act ? f[K + lane] : 0.0;
-                    b.wz = act ? f[2 * K + lane] : 0.0; b.den = act ? f[3 * K + lane] : 0.0;
-                    t0 = f[4 * K + 1]; w = f[4 * K + 2];
+                if (f[NP * K] - U > tol) {
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) b[p] = act ? f[p * K + lane] : 0.0;
+                    t0 = f[NP * K + 1]; w = f[NP * K + 2];
                     found = true;
                     break;
                 }
@@ -1026,71 +845,64 @@ __device__ __forceinline__ CvOut sc_wave_search(SpaceCurv b, const int K, const 
         }
     }
     CvOut o;
-    o.val = U; o.t = tU; o.nodes = nodes; o.status = status;
+    o.val = U; o.t = tU; o.status = status;
     return o;
 }
 
-// An item's answer to memory: row = max_curv - max kappa (a free curve: max kappa itself)
-__device__ __forceinline__ double sc_store(const SpaceCurvParams& q, long item, const CvOut& o)
+// The item's block from Y at the t_star and the row value an earlier step left: zero where the row IS max_curv (the maximum
+// is 0: the clamp, a straight path, degree 1, a vehicle at rest), NaN for a NaN t_star, the family's block otherwise.
+template <class Fam, int NCMAX>
+__device__ __forceinline__ void curv_envelope(const CurvParams& q, long item, int nc, double row, double t)
 {
-    const double v = q.free_curve ? o.val : q.W - o.val;
-    q.val[item] = v;
-    if (q.t) q.t[item] = o.t;
-    if (q.status) q.status[item] = o.status;
-    return v;
-}
-
-// The item's block from Y at the t_star and the row value an earlier step left: zero where the row IS max_curv (a straight
-// path, degree 1, a vehicle at rest), NaN for a NaN t_star, bern_device.h space_curvature_envelope_block otherwise.
-template <int NCMAX>
-__device__ __forceinline__ void sc_envelope(const SpaceCurvParams& q, long item, int nc, double row, double t)
-{
-    double* o = q.jac + (size_t)item * (3 * nc);
+    double* o = q.jac + (size_t)item * (Fam::DIM * nc);
     if (row == q.W || !(t == t)) {
         const double fill = t == t ? 0.0 : t;
-        for (int e = 0; e < 3 * nc; ++e) o[e] = fill;
+        for (int e = 0; e < Fam::DIM * nc; ++e) o[e] = fill;
         return;
     }
-    space_curvature_envelope_block<NCMAX>(q.Y + (size_t)item * (3 * nc), nc, t, o);
+    Fam::template block<NCMAX>(q.Y + (size_t)Fam::curve(item) * (Fam::DIM * nc), nc, Fam::sigma(item), t, o);
 }
 
 // What both kernel forms do once an item's first step is known: the wave on every item that needs it, in lane order; `load`
 // puts item src's coefficients into the lanes.
-template <class Load>
-__device__ __forceinline__ void sc_search_items(const SpaceCurvParams& q, const Load& load, int K, bool need, CvOut& mine, double* stk)
+template <class Fam, class Load>
+__device__ __forceinline__ void curv_search_items(const CurvParams& q, const Load& load, int K, bool need, CvOut& mine, double* stk)
 {
     const int lane = threadIdx.x & (kWave - 1);
     unsigned long long mask = __ballot(need);
     while (mask) {
         const int src = __ffsll((long long)mask) - 1;
         mask &= mask - 1;
-        SpaceCurv b;
-        b.wx = b.wy = b.wz = b.den = 0.0;
+        double b[Fam::NP];
+#pragma unroll
+        for (int p = 0; p < Fam::NP; ++p) b[p] = 0.0;
         load(src, b);
-        const CvOut o = sc_wave_search(b, K, q.W, q.eps_rel, ex_lane(mine.val, src), ex_lane(mine.t, src), q.max_nodes, stk);
+        const CvOut o = curv_wave_search<Fam>(b, K, q.W, q.eps_rel, !q.free_curve, ex_lane(mine.val, src), ex_lane(mine.t, src), q.max_nodes, stk);
         if (lane == src) mine = o;
     }
 }
 
-// Coefficients in registers, one launch (the counts of OBTG_NC_SCURV_LIST): one lane forms an item's 4 (2n + 1)
-// coefficients with space_curvature_row_coeff, then the steps above; JAC: every lane writes its own block.
-template <int NC, bool JAC>
-__global__ __launch_bounds__(kCvWaves * kWave) void k_scurv_true_min(const SpaceCurvParams q)
+// Coefficients in registers, one launch (the counts of OBTG_NC_CURV_LIST / OBTG_NC_SCURV_LIST): one lane forms its item's
+// NP (2n + 1) coefficients -- AngRows::coeffs on T = 1 with the family's coeff --, then the steps above; JAC: every lane writes
+// its own block.
+template <class Fam, int NC, bool JAC>
+__device__ __forceinline__ void curv_true_min_body(const CurvParams& q)
 {
-    constexpr int N = NC - 1, L = 2 * NC - 1;
+    constexpr int N = NC - 1, L = 2 * NC - 1, NP = Fam::NP, DIM = Fam::DIM;
     extern __shared__ double lds[];
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    double* stk = lds + (size_t)wave * kExStack * (4 * L + 3);
+    double* stk = lds + (size_t)wave * kExStack * (NP * L + 3);
     const long item = ((long)blockIdx.x * kCvWaves + wave) * kWave + lane;
     const bool valid = item < q.M;
     const long it = valid ? item : q.M - 1;
-    const double* v = q.Y + (size_t)it * (3 * NC);
+    const double sigma = Fam::sigma(it);
+    const double* v = q.Y + (size_t)Fam::curve(it) * (DIM * NC);
     const ctab_t Cn = as_ctab(q.tab), Sk = Cn + NC;
-    double cw[3][L], den[L];
+    double co[NP][L];
     {
-        double u1[3][NC], u2[3][NC];           // C(n, j) c'_j;  C(n, j) c''_j
+        double u1[DIM][NC], u2[DIM][NC];       // C(n, j) c'_j;  C(n, j) c''_j
 #pragma unroll
-        for (int d = 0; d < 3; ++d) {
+        for (int d = 0; d < DIM; ++d) {
             double x[NC], x1[NC];
 #pragma unroll
             for (int c = 0; c < NC; ++c) x[c] = v[d * NC + c];
@@ -1103,82 +915,113 @@ __global__ __launch_bounds__(kCvWaves * kWave) void k_scurv_true_min(const Space
         }
 #pragma unroll
         for (int k = 0; k < L; ++k) {
-            const SpaceCurv c = space_curvature_row_coeff(u1[0], u1[1], u1[2], u2[0], u2[1], u2[2], N, k, Sk[k]);
-            cw[0][k] = c.wx; cw[1][k] = c.wy; cw[2][k] = c.wz; den[k] = c.den;
+            double c[NP];
+            Fam::coeff(u1, u2, N, k, Sk[k], c);
+            if constexpr (Fam::SIDES == 2) c[0] = sigma * c[0];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) co[p][k] = c[p];
         }
     }
     CvOut mine;
-    const bool need = !sc_first<L>([&](int k) { SpaceCurv c; c.wx = cw[0][k]; c.wy = cw[1][k]; c.wz = cw[2][k]; c.den = den[k]; return c; },
-                                   L, q.W, q.eps_rel, mine) && valid;
-    sc_search_items(q, [&](int src, SpaceCurv& b) {
+    const bool need = !curv_first<Fam, L>([&](int k, double (&c)[NP]) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) c[p] = co[p][k];
+    }, L, q.W, q.eps_rel, !q.free_curve, mine) && valid;
+    curv_search_items<Fam>(q, [&](int src, double (&b)[NP]) {
 #pragma unroll
         for (int k = 0; k < L; ++k) {
-            const double a0 = ex_lane(cw[0][k], src), a1 = ex_lane(cw[1][k], src), a2 = ex_lane(cw[2][k], src), a3 = ex_lane(den[k], src);
-            if (lane == k) { b.wx = a0; b.wy = a1; b.wz = a2; b.den = a3; }
+            double a[NP];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) a[p] = ex_lane(co[p][k], src);
+            if (lane == k) {
+#pragma unroll
+                for (int p = 0; p < NP; ++p) b[p] = a[p];
+            }
         }
     }, L, need, mine, stk);
     if (valid) {
-        const double row = sc_store(q, item, mine);
-        if (JAC) sc_envelope<NC>(q, item, NC, row, mine.t);
+        const double row = Fam::store(q, item, mine);
+        if (JAC) curv_envelope<Fam, NC>(q, item, NC, row, mine.t);
     }
 }
 
-// The workspace form, any degree 1 .. 31: the coefficients are k_scurv_rows' rows in memory, K = 2 nc - 1 at run time
-__global__ __launch_bounds__(kCvWaves * kWave) void k_scurv_search(const SpaceCurvParams q)
+// The workspace form, any degree 1 .. 31: the coefficients are the rows kernel's rows in memory, K = 2 nc - 1 at run time
+template <class Fam>
+__device__ __forceinline__ void curv_search_body(const CurvParams& q)
 {
+    constexpr int NP = Fam::NP;
     extern __shared__ double lds[];
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6, K = 2 * q.nc - 1;
-    double* stk = lds + (size_t)wave * kExStack * (4 * K + 3);
+    double* stk = lds + (size_t)wave * kExStack * (NP * K + 3);
     const long item0 = ((long)blockIdx.x * kCvWaves + wave) * kWave, item = item0 + lane;
     const bool valid = item < q.M;
     const long it = valid ? item : q.M - 1;
-    const double* r = q.rows + (size_t)it * (4 * K);
+    // coefficient k of item i, signed
+    const auto coef = [&](long i, int k, double (&c)[NP]) {
+        const double* r = q.rows + (size_t)Fam::curve(i) * (NP * K);
+#pragma unroll
+        for (int p = 0; p < NP; ++p) c[p] = r[p * K + k];
+        if constexpr (Fam::SIDES == 2) c[0] = Fam::sigma(i) * c[0];
+    };
     CvOut mine;
-    const bool need = !sc_first<0>([&](int k) { SpaceCurv c; c.wx = r[k]; c.wy = r[K + k]; c.wz = r[2 * K + k]; c.den = r[3 * K + k]; return c; },
-                                   K, q.W, q.eps_rel, mine) && valid;
-    sc_search_items(q, [&](int src, SpaceCurv& b) {
-        const double* rs = q.rows + (size_t)(item0 + src) * (4 * K);
-        if (lane < K) { b.wx = rs[lane]; b.wy = rs[K + lane]; b.wz = rs[2 * K + lane]; b.den = rs[3 * K + lane]; }
-    }, K, need, mine, stk);
-    if (valid) sc_store(q, item, mine);
+    const bool need = !curv_first<Fam, 0>([&](int k, double (&c)[NP]) { coef(it, k, c); }, K, q.W, q.eps_rel, !q.free_curve, mine) && valid;
+    curv_search_items<Fam>(q, [&](int src, double (&b)[NP]) { if (lane < K) coef(item0 + src, lane, b); }, K, need, mine, stk);
+    if (valid) Fam::store(q, item, mine);
 }
 
-// The blocks alone, from Y, the rows' values and their t_star: one item per lane, nc <= kCvMaxNC at run time
-__global__ __launch_bounds__(kEnvThreads) void k_scurv_envelope(const SpaceCurvParams q)
+// The rows' polynomials to memory, any degree 1 .. 31: k_ang_rows on T = 1 without a side -- one wave per vehicle (curve),
+// lane k forms coefficient k of the NP polynomials with the function the in-register kernels use: out[.][NP][2n+1].
+template <class Fam>
+__device__ __forceinline__ void curv_rows_body(const CurvParams& q, double* __restrict__ out)
 {
-    const long item = (long)blockIdx.x * kEnvThreads + threadIdx.x;
-    if (item < q.M) sc_envelope<kCvMaxNC>(q, item, q.nc, q.val[item], q.t[item]);
-}
-
-// The space-curvature rows' polynomials to memory, any degree 1 .. 31: one wave per vehicle (curve), lane k forms
-// coefficient k of wx, wy, wz and den with the function the in-register kernels use: out[.][4][2n+1].
-__global__ __launch_bounds__(kWave) void k_scurv_rows(const SpaceCurvParams q, double* __restrict__ out)
-{
-    __shared__ double sh[9][kCvMaxNC];       // c -> u1 after the last read; c'; u2
+    constexpr int NP = Fam::NP, DIM = Fam::DIM;
+    __shared__ double sh[3 * DIM][kCvMaxNC];     // c -> u1 after the last read; c'; u2
     const long veh = blockIdx.x;
     const int lane = threadIdx.x, nc = q.nc, n = nc - 1, L = 2 * n + 1;
     const double val = (double)n;
-    const double* v = q.Y + (size_t)veh * (3 * nc);
+    const double* v = q.Y + (size_t)veh * (DIM * nc);
     const double* Cn = q.tab;
     const double* Sk = Cn + nc;
     if (lane < nc)
-        for (int d = 0; d < 3; ++d) sh[d][lane] = v[d * nc + lane];
+        for (int d = 0; d < DIM; ++d) sh[d][lane] = v[d * nc + lane];
     __syncthreads();
     if (lane < nc)
-        for (int d = 0; d < 3; ++d) sh[3 + d][lane] = diff_elev1_at(sh[d], lane, n, val);
+        for (int d = 0; d < DIM; ++d) sh[DIM + d][lane] = diff_elev1_at(sh[d], lane, n, val);
     __syncthreads();
     if (lane < nc)
-        for (int d = 0; d < 3; ++d) {
-            sh[6 + d][lane] = Cn[lane] * diff_elev1_at(sh[3 + d], lane, n, val);
-            sh[d][lane] = Cn[lane] * sh[3 + d][lane];
+        for (int d = 0; d < DIM; ++d) {
+            sh[2 * DIM + d][lane] = Cn[lane] * diff_elev1_at(sh[DIM + d], lane, n, val);
+            sh[d][lane] = Cn[lane] * sh[DIM + d][lane];
         }
     __syncthreads();
     if (lane < L) {
-        const SpaceCurv c = space_curvature_row_coeff(sh[0], sh[1], sh[2], sh[6], sh[7], sh[8], n, lane, Sk[lane]);
-        double* o = out + (size_t)veh * 4 * L + lane;
-        o[0] = c.wx; o[L] = c.wy; o[2 * L] = c.wz; o[3 * L] = c.den;
+        double c[NP];
+        Fam::coeff(sh, sh + 2 * DIM, n, lane, Sk[lane], c);
+        double* o = out + (size_t)veh * NP * L + lane;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) o[p * L] = c[p];
     }
 }
+
+// the kernels: the bodies above under the names the host (and a profile) knows them by
+template <int NC, bool JAC>
+__global__ __launch_bounds__(kCvWaves * kWave) void k_curv_true_min(const CurvParams q) { curv_true_min_body<PlanarCurv, NC, JAC>(q); }
+__global__ __launch_bounds__(kCvWaves * kWave) void k_curv_search(const CurvParams q) { curv_search_body<PlanarCurv>(q); }
+__global__ __launch_bounds__(kWave) void k_curv_rows(const CurvParams q, double* __restrict__ out) { curv_rows_body<PlanarCurv>(q, out); }
+template <int NC, bool JAC>
+__global__ __launch_bounds__(kCvWaves * kWave) void k_scurv_true_min(const CurvParams q) { curv_true_min_body<SpaceCurv3, NC, JAC>(q); }
+__global__ __launch_bounds__(kCvWaves * kWave) void k_scurv_search(const CurvParams q) { curv_search_body<SpaceCurv3>(q); }
+__global__ __launch_bounds__(kWave) void k_scurv_rows(const CurvParams q, double* __restrict__ out) { curv_rows_body<SpaceCurv3>(q, out); }
+
+// The blocks alone, from Y, the rows' values and their t_star: one item per lane, nc <= kCvMaxNC at run time
+template <class Fam>
+__device__ __forceinline__ void curv_envelope_body(const CurvParams& q)
+{
+    const long item = (long)blockIdx.x * kEnvThreads + threadIdx.x;
+    if (item < q.M) curv_envelope<Fam, kCvMaxNC>(q, item, q.nc, q.val[item], q.t[item]);
+}
+__global__ __launch_bounds__(kEnvThreads) void k_curv_envelope(const CurvParams q) { curv_envelope_body<PlanarCurv>(q); }
+__global__ __launch_bounds__(kEnvThreads) void k_scurv_envelope(const CurvParams q) { curv_envelope_body<SpaceCurv3>(q); }
 
 // =====================================================================================
 //  launchers
@@ -1299,110 +1142,103 @@ static int launch_fused(obtg_ctx* c, const RowFamily& f, const double* dY, const
     return OBTG_OK;
 }
 
-// ---- the curvature family's launches.  Frames: kExStack x (2K + 3) doubles per wave, 33 KB at K = 63.
+// ---- the two curvature families' launches.  Frames: kExStack x (NP K + 3) doubles per wave; at K = 63 that is 33 KB for the
+// planar family and 65 280 bytes for the space family: under the 64 KB a workgroup's dynamic LDS may be without raising a
+// limit, one wave per workgroup.
+static_assert(sizeof(double) * kCvWaves * kExStack * (SpaceCurv3::NP * (2 * kCvMaxNC - 1) + 3) <= 65536, "space-curvature frames: lower the frame count");
+
+// The host side of a curvature family, found by `kind`: the policy's shape and the kernels by name
+typedef void (*CurvKernel)(const CurvParams);
+struct CurvHost {
+    int np, sides, dim;                            // the policy's NP, SIDES, DIM
+    void (*rows)(const CurvParams, double*);
+    CurvKernel search, envelope;
+    CurvKernel (*fused)(int nc, bool jac);         // the in-register kernel of a count of the family's list, else null
+};
+static CurvKernel curv_fused(int nc, bool jac)
+{
+#define OBTG_CASE(NC_) if (nc == NC_) return jac ? k_curv_true_min<NC_, true> : k_curv_true_min<NC_, false>;
+    OBTG_NC_CURV_LIST(OBTG_CASE)
+#undef OBTG_CASE
+    return nullptr;
+}
+static CurvKernel scurv_fused(int nc, bool jac)
+{
+#define OBTG_CASE(NC_) if (nc == NC_) return jac ? k_scurv_true_min<NC_, true> : k_scurv_true_min<NC_, false>;
+    OBTG_NC_SCURV_LIST(OBTG_CASE)
+#undef OBTG_CASE
+    return nullptr;
+}
+static const CurvHost& curv_host(RowKind kind)
+{
+    static const CurvHost planar{ PlanarCurv::NP, PlanarCurv::SIDES, PlanarCurv::DIM, k_curv_rows, k_curv_search, k_curv_envelope, curv_fused };
+    static const CurvHost space{ SpaceCurv3::NP, SpaceCurv3::SIDES, SpaceCurv3::DIM, k_scurv_rows, k_scurv_search, k_scurv_envelope, scurv_fused };
+    return kind == ROWS_SCURV ? space : planar;
+}
+
 static CurvParams curv_params(const double* d_curves, const double* d_tab, int nc, long items, double W, double eps_rel, int max_nodes)
 {
     CurvParams q{};
     q.Y = d_curves; q.tab = d_tab; q.nc = nc; q.M = items; q.W = W; q.eps_rel = eps_rel; q.max_nodes = max_nodes;
     return q;
 }
-static size_t curv_lds_bytes(int K) { return sizeof(double) * kCvWaves * kExStack * (size_t)(2 * K + 3); }
+static size_t curv_lds_bytes(const CurvHost& h, int K) { return sizeof(double) * kCvWaves * kExStack * (size_t)(h.np * K + 3); }
 static unsigned curv_grid(long items) { const long per_wg = kCvWaves * kWave; return (unsigned)((items + per_wg - 1) / per_wg); }
 
 bool curvature_supported(int nc) { return nc >= 2 && nc <= kCvMaxNC; }
+CurvShape curvature_shape(RowKind kind) { const CurvHost& h = curv_host(kind); return CurvShape{ h.np, h.sides, h.dim }; }
 
-int launch_curv_rows(obtg_ctx* c, const double* d_curves, const double* d_tab, long n_curves, int nc, double* d_out, int kernel_id)
+int launch_curv_rows(obtg_ctx* c, RowKind kind, const double* d_curves, const double* d_tab, long n_curves, int nc, double* d_out,
+                     int kernel_id)
 {
     if (n_curves <= 0) return OBTG_OK;
     if (!curvature_supported(nc)) return OBTG_ERR_UNSUPPORTED;
-    const CurvParams q = curv_params(d_curves, d_tab, nc, 2 * n_curves, 0.0, 0.0, 1);
+    const CurvHost& h = curv_host(kind);
+    const CurvParams q = curv_params(d_curves, d_tab, nc, h.sides * n_curves, 0.0, 0.0, 1);
     ScopedKernelTimer t(c, kernel_id);
-    hipLaunchKernelGGL(k_curv_rows, dim3((unsigned)n_curves), dim3(kWave), 0, c->stream, q, d_out);
+    hipLaunchKernelGGL(h.rows, dim3((unsigned)n_curves), dim3(kWave), 0, c->stream, q, d_out);
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;
 }
 
-int launch_curv_search(obtg_ctx* c, const double* d_rows, long items, int nc, double max_curv, double eps_rel, int max_nodes,
-                       double* d_val, double* d_t, double* d_val1, double* d_t1, int* d_nodes, int* d_status, int kernel_id)
+int launch_curv_search(obtg_ctx* c, RowKind kind, const double* d_rows, long items, int nc, double max_curv, int free_curve,
+                       double eps_rel, int max_nodes, double* d_val, double* d_t, double* d_val1, double* d_t1, int* d_status,
+                       int kernel_id)
 {
     if (items <= 0) return OBTG_OK;
     if (!curvature_supported(nc)) return OBTG_ERR_UNSUPPORTED;
+    const CurvHost& h = curv_host(kind);
     CurvParams q = curv_params(nullptr, nullptr, nc, items, max_curv, eps_rel, max_nodes);
-    q.rows = d_rows; q.val = d_val; q.t = d_t; q.val1 = d_val1; q.t1 = d_t1; q.nodes = d_nodes; q.status = d_status;
+    q.rows = d_rows; q.val = d_val; q.t = d_t; q.val1 = d_val1; q.t1 = d_t1; q.status = d_status; q.free_curve = free_curve;
     ScopedKernelTimer t(c, kernel_id);
-    hipLaunchKernelGGL(k_curv_search, dim3(curv_grid(items)), dim3(kCvWaves * kWave), curv_lds_bytes(2 * nc - 1), c->stream, q);
+    hipLaunchKernelGGL(h.search, dim3(curv_grid(items)), dim3(kCvWaves * kWave), curv_lds_bytes(h, 2 * nc - 1), c->stream, q);
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;
 }
 
-// the counts of OBTG_NC_CURV_LIST: coefficients in registers, one launch (with the blocks when d_jac is set)
+// the counts of the family's list: coefficients in registers, one launch (with the blocks when d_jac is set)
 static int launch_curv_fused(obtg_ctx* c, const RowFamily& f, const double* dY, const ExParams& ex, double* d_jac)
 {
-    if (c->dim != 2) return OBTG_ERR_UNSUPPORTED;
+    const CurvHost& h = curv_host(f.kind);
+    if (c->dim != h.dim) return OBTG_ERR_UNSUPPORTED;
     const int nc = c->deg + 1;
-    void (*kern)(const CurvParams) = nullptr;
-#define OBTG_CASE(NC_) if (nc == NC_) kern = d_jac ? k_curv_true_min<NC_, true> : k_curv_true_min<NC_, false>;
-    OBTG_NC_CURV_LIST(OBTG_CASE)
-#undef OBTG_CASE
+    const CurvKernel kern = h.fused(nc, d_jac != nullptr);
     if (!kern) return OBTG_ERR_UNSUPPORTED;
     CurvParams q = curv_params(dY, c->d_ang_rows.as<double>(), nc, ex.M, f.w, ex.eps_rel, ex.max_nodes);
     q.val = ex.val; q.t = ex.t; q.status = ex.status; q.jac = d_jac;
     ScopedKernelTimer t(c, f.kernel_id);
-    hipLaunchKernelGGL(kern, dim3(curv_grid(ex.M)), dim3(kCvWaves * kWave), curv_lds_bytes(ex.K), c->stream, q);
+    hipLaunchKernelGGL(kern, dim3(curv_grid(ex.M)), dim3(kCvWaves * kWave), curv_lds_bytes(h, ex.K), c->stream, q);
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;
 }
 
-// ---- the space-curvature family's launches.  Frames: kExStack x (4K + 3) doubles per wave, 65 280 bytes at K = 63: under the
-// 64 KB a workgroup's dynamic LDS may be without raising a limit, one wave per workgroup.
-static SpaceCurvParams scurv_params(const double* d_curves, const double* d_tab, int nc, long items, double W, double eps_rel,
-                                    int max_nodes)
+// the blocks alone, from Y, the rows' values and their t_star
+static int launch_curv_blocks(obtg_ctx* c, const RowFamily& f, const double* dY, const ExParams& ex, const double* d_val, double* d_jac)
 {
-    SpaceCurvParams q{};
-    q.Y = d_curves; q.tab = d_tab; q.nc = nc; q.M = items; q.W = W; q.eps_rel = eps_rel; q.max_nodes = max_nodes;
-    return q;
-}
-static size_t scurv_lds_bytes(int K) { return sizeof(double) * kCvWaves * kExStack * (size_t)(4 * K + 3); }
-static_assert(sizeof(double) * kCvWaves * kExStack * (4 * (2 * kCvMaxNC - 1) + 3) <= 65536, "space-curvature frames: lower the frame count");
-
-int launch_scurv_rows(obtg_ctx* c, const double* d_curves, const double* d_tab, long n_curves, int nc, double* d_out, int kernel_id)
-{
-    if (n_curves <= 0) return OBTG_OK;
-    if (!curvature_supported(nc)) return OBTG_ERR_UNSUPPORTED;
-    const SpaceCurvParams q = scurv_params(d_curves, d_tab, nc, n_curves, 0.0, 0.0, 1);
-    ScopedKernelTimer t(c, kernel_id);
-    hipLaunchKernelGGL(k_scurv_rows, dim3((unsigned)n_curves), dim3(kWave), 0, c->stream, q, d_out);
-    OBTG_HIP(c, hipGetLastError());
-    return OBTG_OK;
-}
-
-int launch_scurv_search(obtg_ctx* c, const double* d_rows, long items, int nc, double max_curv, int free_curve, double eps_rel,
-                        int max_nodes, double* d_val, double* d_t, int* d_status, int kernel_id)
-{
-    if (items <= 0) return OBTG_OK;
-    if (!curvature_supported(nc)) return OBTG_ERR_UNSUPPORTED;
-    SpaceCurvParams q = scurv_params(nullptr, nullptr, nc, items, max_curv, eps_rel, max_nodes);
-    q.rows = d_rows; q.val = d_val; q.t = d_t; q.status = d_status; q.free_curve = free_curve;
-    ScopedKernelTimer t(c, kernel_id);
-    hipLaunchKernelGGL(k_scurv_search, dim3(curv_grid(items)), dim3(kCvWaves * kWave), scurv_lds_bytes(2 * nc - 1), c->stream, q);
-    OBTG_HIP(c, hipGetLastError());
-    return OBTG_OK;
-}
-
-// the counts of OBTG_NC_SCURV_LIST: coefficients in registers, one launch (with the blocks when d_jac is set)
-static int launch_scurv_fused(obtg_ctx* c, const RowFamily& f, const double* dY, const ExParams& ex, double* d_jac)
-{
-    if (c->dim != 3) return OBTG_ERR_UNSUPPORTED;
-    const int nc = c->deg + 1;
-    void (*kern)(const SpaceCurvParams) = nullptr;
-#define OBTG_CASE(NC_) if (nc == NC_) kern = d_jac ? k_scurv_true_min<NC_, true> : k_scurv_true_min<NC_, false>;
-    OBTG_NC_SCURV_LIST(OBTG_CASE)
-#undef OBTG_CASE
-    if (!kern) return OBTG_ERR_UNSUPPORTED;
-    SpaceCurvParams q = scurv_params(dY, c->d_ang_rows.as<double>(), nc, ex.M, f.w, ex.eps_rel, ex.max_nodes);
-    q.val = ex.val; q.t = ex.t; q.status = ex.status; q.jac = d_jac;
+    CurvParams q = curv_params(dY, c->d_ang_rows.as<double>(), c->deg + 1, ex.M, f.w, 0.0, 1);
+    q.val = const_cast<double*>(d_val); q.t = ex.t; q.jac = d_jac;
     ScopedKernelTimer t(c, f.kernel_id);
-    hipLaunchKernelGGL(kern, dim3(curv_grid(ex.M)), dim3(kCvWaves * kWave), scurv_lds_bytes(ex.K), c->stream, q);
+    hipLaunchKernelGGL(curv_host(f.kind).envelope, dim3((unsigned)((ex.M + kEnvThreads - 1) / kEnvThreads)), dim3(kEnvThreads), 0, c->stream, q);
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;
 }
@@ -1422,8 +1258,7 @@ int launch_true_min(obtg_ctx* c, const RowFamily& f, const double* dY, int B, do
         case ROWS_SPEED: return launch_fused<SpeedRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_ACCEL: return launch_fused<AccelRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_JERK: return launch_fused<JerkRows>(c, f, dY, ex, d_jac, d_jac_tf);
-        case ROWS_CURV: return launch_curv_fused(c, f, dY, ex, d_jac);
-        case ROWS_SCURV: return launch_scurv_fused(c, f, dY, ex, d_jac);
+        case ROWS_CURV: case ROWS_SCURV: return launch_curv_fused(c, f, dY, ex, d_jac);
         default: return launch_fused<TsepRows>(c, f, dY, ex, d_jac, d_jac_tf);
     }
 }
@@ -1449,22 +1284,7 @@ int launch_true_min_envelope(obtg_ctx* c, const RowFamily& f, const double* dY, 
     ExParams ex{};
     ex.t = const_cast<double*>(d_t); ex.M = (long)B * f.items;
     switch (f.kind) {
-        case ROWS_CURV: {
-            CurvParams q = curv_params(dY, c->d_ang_rows.as<double>(), c->deg + 1, ex.M, f.w, 0.0, 1);
-            q.val = const_cast<double*>(d_val); q.t = ex.t; q.jac = d_jac;
-            ScopedKernelTimer t(c, f.kernel_id);
-            hipLaunchKernelGGL(k_curv_envelope, dim3((unsigned)((ex.M + kEnvThreads - 1) / kEnvThreads)), dim3(kEnvThreads), 0, c->stream, q);
-            OBTG_HIP(c, hipGetLastError());
-            return OBTG_OK;
-        }
-        case ROWS_SCURV: {
-            SpaceCurvParams q = scurv_params(dY, c->d_ang_rows.as<double>(), c->deg + 1, ex.M, f.w, 0.0, 1);
-            q.val = const_cast<double*>(d_val); q.t = ex.t; q.jac = d_jac;
-            ScopedKernelTimer t(c, f.kernel_id);
-            hipLaunchKernelGGL(k_scurv_envelope, dim3((unsigned)((ex.M + kEnvThreads - 1) / kEnvThreads)), dim3(kEnvThreads), 0, c->stream, q);
-            OBTG_HIP(c, hipGetLastError());
-            return OBTG_OK;
-        }
+        case ROWS_CURV: case ROWS_SCURV: return launch_curv_blocks(c, f, dY, ex, d_val, d_jac);
         case ROWS_ANG: return launch_blocks<AngRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_SPEED: return launch_blocks<SpeedRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_ACCEL: return launch_blocks<AccelRows>(c, f, dY, ex, d_jac, d_jac_tf);
@@ -1494,55 +1314,31 @@ RowFamily ang_row_family(const obtg_ctx* c, const double* d_tf, double max_rate)
     return f;
 }
 
-// obtg_curvature_poly's launch, and the family's rows_r0: [B][n_veh][2][2 deg + 1], num then den
+// obtg_[space_]curvature_poly's launch, and the families' rows_r0: [B][n_veh][NP][2 deg + 1] -- num then den; wx, wy, wz, den
 int launch_curvature_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out)
 {
     if (B <= 0 || f.items <= 0) return OBTG_OK;
-    if (c->dim != 2 || !curvature_supported(c->deg + 1)) return OBTG_ERR_UNSUPPORTED;
+    if (c->dim != curv_host(f.kind).dim || !curvature_supported(c->deg + 1)) return OBTG_ERR_UNSUPPORTED;
     int rc = ensure_tables(c);
     if (rc) return rc;
-    return launch_curv_rows(c, dY, c->d_ang_rows.as<double>(), (long)B * c->n_veh, c->deg + 1, d_out, f.kernel_id);
+    return launch_curv_rows(c, f.kind, dY, c->d_ang_rows.as<double>(), (long)B * c->n_veh, c->deg + 1, d_out, f.kernel_id);
 }
 
-// the family's search of its workspace rows: two items (sides) per pair of rows
+// a family's search of its workspace rows: a curve's NP rows serve its SIDES items
 static int curvature_rows_search(obtg_ctx* c, const RowFamily& f, const double* d_rows, long items, double eps_rel, int max_nodes,
                                  double* d_out, double* d_t, int* d_status)
 {
-    return launch_curv_search(c, d_rows, items, c->deg + 1, f.w, eps_rel, max_nodes, d_out, d_t, nullptr, nullptr, nullptr, d_status,
+    return launch_curv_search(c, f.kind, d_rows, items, c->deg + 1, f.w, 0, eps_rel, max_nodes, d_out, d_t, nullptr, nullptr, d_status,
                               f.kernel_id);
 }
 
-RowFamily curvature_row_family(const obtg_ctx* c, double max_curv)
+RowFamily curvature_row_family(const obtg_ctx* c, RowKind kind, double max_curv)
 {
-    RowFamily f{ ROWS_CURV, 2 * c->n_veh, OBTG_K_ANG_RATE, 1.0, 0.0, nullptr, launch_curvature_rows };
+    const CurvHost& h = curv_host(kind);
+    RowFamily f{ kind, h.sides * c->n_veh, OBTG_K_ANG_RATE, 1.0, 0.0, nullptr, launch_curvature_rows };
     f.w = max_curv;
     f.search = curvature_rows_search;
-    return f;
-}
-
-// obtg_space_curvature_poly's launch, and the family's rows_r0: [B][n_veh][4][2 deg + 1], wx, wy, wz, den
-int launch_space_curvature_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out)
-{
-    if (B <= 0 || f.items <= 0) return OBTG_OK;
-    if (c->dim != 3 || !curvature_supported(c->deg + 1)) return OBTG_ERR_UNSUPPORTED;
-    int rc = ensure_tables(c);
-    if (rc) return rc;
-    return launch_scurv_rows(c, dY, c->d_ang_rows.as<double>(), (long)B * c->n_veh, c->deg + 1, d_out, f.kernel_id);
-}
-
-// the family's search of its workspace rows: one item per four rows
-static int space_curvature_rows_search(obtg_ctx* c, const RowFamily& f, const double* d_rows, long items, double eps_rel, int max_nodes,
-                                       double* d_out, double* d_t, int* d_status)
-{
-    return launch_scurv_search(c, d_rows, items, c->deg + 1, f.w, 0, eps_rel, max_nodes, d_out, d_t, d_status, f.kernel_id);
-}
-
-RowFamily space_curvature_row_family(const obtg_ctx* c, double max_curv)
-{
-    RowFamily f{ ROWS_SCURV, c->n_veh, OBTG_K_ANG_RATE, 1.0, 0.0, nullptr, launch_space_curvature_rows };
-    f.w = max_curv;
-    f.search = space_curvature_rows_search;
-    f.ws_rows = 4;
+    f.ws_rows = h.np / h.sides;
     return f;
 }
 

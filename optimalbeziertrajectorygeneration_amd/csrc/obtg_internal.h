@@ -414,24 +414,22 @@ RowFamily jerk_row_family(const obtg_ctx* c, const double* d_tf, double bound); 
 RowFamily ang_row_family(const obtg_ctx* c, const double* d_tf, double max_rate);                     // extrema_kernels.hip
 // the angular-rate family's polynomials [B][n_veh][2][2 deg + 1] (obtg_ang_rate_poly; its rows_r0): dim 2, degree 1 .. 31
 int launch_ang_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);
-// The curvature family (dim 2, degree 1 .. 31; no time span).  Its search is its own (extrema_kernels.hip cv_wave_search).
-RowFamily curvature_row_family(const obtg_ctx* c, double max_curv);
-int launch_curvature_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);      // obtg_curvature_poly; its rows_r0
-// free curves (obtg_bern_curvature): d_curves[n][2][nc], d_tab = C(nc-1, .)[nc] | 1 / C(2 nc - 2, .)[2 nc - 1]; rows out[n][2][2 nc - 1];
-// the search of 2 n items with max_curv = 0; d_val1 / d_t1 set: the free-curve outputs k_max, t_max | k_min, t_min [n] each
-// The space-curvature family (dim 3, degree 1 .. 31; no time span; one row per vehicle).  Its search is its own
-// (extrema_kernels.hip sc_wave_search); its workspace holds four rows per item.
-RowFamily space_curvature_row_family(const obtg_ctx* c, double max_curv);
-int launch_space_curvature_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);   // obtg_space_curvature_poly; its rows_r0
-// free curves (obtg_bern_space_curvature): d_curves[n][3][nc], d_tab as launch_curv_rows'; rows out[n][4][2 nc - 1]; the
-// search of n items -- free_curve: max_curv = 0 and d_val receives the maximum itself
-int launch_scurv_rows(obtg_ctx* c, const double* d_curves, const double* d_tab, long n_curves, int nc, double* d_out, int kernel_id);
-int launch_scurv_search(obtg_ctx* c, const double* d_rows, long items, int nc, double max_curv, int free_curve, double eps_rel,
-                        int max_nodes, double* d_val, double* d_t, int* d_status, int kernel_id);
+// The two curvature families, kind = ROWS_CURV (dim 2; two items, the sides, per vehicle; workspace rows num, den) or ROWS_SCURV
+// (dim 3; one item per vehicle; workspace rows wx, wy, wz, den): degree 1 .. 31, no time span.  Their search is their own
+// (extrema_kernels.hip curv_wave_search over the policies PlanarCurv and SpaceCurv3).
+RowFamily curvature_row_family(const obtg_ctx* c, RowKind kind, double max_curv);
+int launch_curvature_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);      // obtg_[space_]curvature_poly; their rows_r0
+// free curves (obtg_bern_[space_]curvature): d_curves[n][dim][nc], d_tab = C(nc-1, .)[nc] | 1 / C(2 nc - 2, .)[2 nc - 1]; rows
+// out[n][2 or 4][2 nc - 1]; the search of 2 n or n items -- free_curve: max_curv = 0 and the extrema themselves are written,
+// planar k_max, t_max to d_val, d_t and k_min, t_min to d_val1, d_t1 ([n] each), space the maximum to d_val, d_t (d_val1, d_t1 null)
 bool curvature_supported(int nc);                       // 2 <= nc <= 32
-int launch_curv_rows(obtg_ctx* c, const double* d_curves, const double* d_tab, long n_curves, int nc, double* d_out, int kernel_id);
-int launch_curv_search(obtg_ctx* c, const double* d_rows, long items, int nc, double max_curv, double eps_rel, int max_nodes,
-                       double* d_val, double* d_t, double* d_val1, double* d_t1, int* d_nodes, int* d_status, int kernel_id);
+struct CurvShape { int np, sides, dim; };               // of a kind: polynomials per curve (den last), items per curve, coordinates
+CurvShape curvature_shape(RowKind kind);
+int launch_curv_rows(obtg_ctx* c, RowKind kind, const double* d_curves, const double* d_tab, long n_curves, int nc, double* d_out,
+                     int kernel_id);
+int launch_curv_search(obtg_ctx* c, RowKind kind, const double* d_rows, long items, int nc, double max_curv, int free_curve,
+                       double eps_rel, int max_nodes, double* d_val, double* d_t, double* d_val1, double* d_t1, int* d_status,
+                       int kernel_id);
 // the fused form for the fast-kernel list's shapes, one launch; OBTG_ERR_UNSUPPORTED: go through the family's R = 0 rows.
 // d_jac: with the envelope blocks [B][items][dim][deg+1]; d_jac_tf (nullable, speed): their d/dtf [B][items]
 int launch_true_min(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double eps_rel, int max_nodes, double* d_out,

@@ -50,7 +50,7 @@ def _kappa(n, d):
 
 
 def _bound(num, den):
-    """extrema_kernels.hip cv_ratio / cv_node_bound for a clamped row, in float64 (g's fma is a product and a sum here)"""
+    """extrema_kernels.hip PlanarCurv::ratio / curv_node_bound for a clamped row, in float64 (g's fma is a product and a sum here)"""
     pos = num > 0.0
     if not pos.any():
         return 0.0
@@ -75,7 +75,7 @@ def _halves(c):
 
 
 def rule_nodes(num, den, W, eps, max_nodes=100000):
-    """Sub-curves the device's rule examines on one clamped item (cv_first, cv_wave_search: the same incumbent, bound, closing
+    """Sub-curves the device's rule examines on one clamped item (curv_first, curv_wave_search under PlanarCurv: the same incumbent, bound, closing
     test and order of descent), restated in float64 on the device's own coefficients: a count, not the device's counter."""
     if not num.any():
         return 1

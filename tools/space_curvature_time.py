@@ -37,7 +37,7 @@ def _kappa(c):
 
 
 def _bound(co):
-    """extrema_kernels.hip sc_ratio / sc_node_bound in float64 (g's fma is a product and a sum here)"""
+    """extrema_kernels.hip SpaceCurv3::ratio / curv_node_bound in float64 (g's fma is a product and a sum here)"""
     nu = np.sqrt(co[0] ** 2 + co[1] ** 2 + co[2] ** 2)
     if not nu.any():
         return 0.0
@@ -53,7 +53,7 @@ def _bound(co):
 
 
 def rule_nodes(co, W, eps, max_nodes=100000):
-    """Sub-curves the device's rule examines on one item (sc_first, sc_wave_search: the same incumbent, bound, closing test and
+    """Sub-curves the device's rule examines on one item (curv_first, curv_wave_search under SpaceCurv3: the same incumbent, bound, closing test and
     order of descent), restated in float64 on the device's own coefficients co[4][K]: a count, not the device's counter."""
     if not co[:3].any():
         return 1

@@ -110,7 +110,10 @@ const char* obtg_strerror(int code);
  *      obtg_bern_curvature[_dev] (timed under OBTG_K_ANG_RATE; no kernel id added).
  *      Later, still 7: new: the space-curvature rows of 3-D vehicles obtg_space_curvature_true_min[_dev], their envelope Jacobian
  *      obtg_space_curvature_true_min_jac[_dev], their polynomials obtg_space_curvature_poly[_dev] and the largest curvature of
- *      free space curves obtg_bern_space_curvature[_dev] (timed under OBTG_K_ANG_RATE; no kernel id added). */
+ *      free space curves obtg_bern_space_curvature[_dev] (timed under OBTG_K_ANG_RATE; no kernel id added).
+ *      Later, still 7: new: the keep-in region obtg_ctx_set_keep_in, its rows obtg_keep_in[_dev] (obtg_len_keep_in), their true
+ *      margins obtg_keep_in_true_min[_dev] and the envelope Jacobian obtg_keep_in_true_min_jac[_dev] (timed under OBTG_K_SPEED;
+ *      no kernel id added). */
 #define OBTG_ABI_VERSION 7
 int obtg_abi_version(void);
 
@@ -886,6 +889,50 @@ int obtg_bern_space_curvature(obtg_ctx*, const double* c /*[M][3][K]*/, int M, i
                               double* k_max /*[M]*/, double* t_max /*[M]*/, int* status /*[M], nullable*/);
 int obtg_bern_space_curvature_dev(obtg_ctx*, const double* d_c, int M, int K, double eps_rel, int max_nodes, double* d_k_max,
                                   double* d_t_max, int* d_status);
+
+/* ---- keep-in regions: every listed vehicle stays inside its half-spaces, in 2-D and 3-D ----
+ * A region is F half-spaces a_f . p <= b_f, H[F][d+1] = (a_f[0 .. d-1], b_f); a is not normalised (with |a| = 1 a row is a
+ * distance).  An item is a (vehicle, face) pair of the list VF[P][2]; vehicles may have different faces, or none.  For vehicle v
+ * with control points P[c][i] (c < d, i <= n):
+ *     g(t) = b_f - a_f . c_v(t),    Bernstein coefficient i:  g_i = b_f - sum_c a_f[c] P[c][i]     (degree n; feasible iff g >= 0)
+ * formed as fma(-a[0], P[0][i], b), then fma(-a[c], P[c][i], .) for c = 1 .. d-1 (csrc/bern_device.h keep_in_coeff) in every
+ * kernel form.  Neither tf nor a time span enters: nothing here takes tf and there is no jac_tf.
+ * obtg_ctx_set_keep_in: copies H and VF to the context (P = 0 clears the region).  OBTG_ERR_ARG for a vehicle index outside
+ *     0 .. N-1, a face index outside 0 .. F-1, a context whose d is not 2 or 3, F < 1 or a null table with P > 0.
+ * obtg_len_keep_in: P (n+R+1).
+ * obtg_keep_in: out[B][P][n+R+1], the R = 0 coefficients elevated by the context's DEG_ELEV -- formed first, then elevated once
+ *     per row: the bits of obtg_bern_elev(R) applied to the R = 0 row (R = 0: the coefficients themselves; a -0 is written +0).
+ *     Any degree up to 31, above that OBTG_ERR_UNSUPPORTED.  These are exact linear constraints on the control points.
+ * obtg_keep_in_true_min: out[B][P] = min over t in [0, 1] of g, the true margin.  DEG_ELEV does not enter.  out, t_star and
+ *     status are the bits of obtg_bern_extrema(eps_abs = 0, want_max = 0) on obtg_keep_in's rows of a DEG_ELEV = 0 context.  An
+ *     end coefficient that is the row's smallest is returned as is (t_star 0 or 1).  A row with a non-finite coefficient: val
+ *     and t_star NaN, status OBTG_MD_OK.  Degrees with a specialised kernel (obtg_fast_kernels & 1) form the coefficients in
+ *     registers, one launch; other degrees up to 31 go through a workspace of the R = 0 rows (two launches); above 31:
+ *     OBTG_ERR_UNSUPPORTED.  t_star and status are nullable.
+ * obtg_keep_in_true_min_jac: out, t_star, status are the bits of the value call with the same arguments, plus the envelope
+ *     block of every row at its t_star with respect to the control points of the item's own vehicle:
+ *         jac[B][P][d][n+1]:  jac[c][i] = -a_f[c] B_i^n(t_star)
+ *     (csrc/bern_device.h keep_in_envelope_block; g is linear in the control points, so the block does not read them).  An end
+ *     minimiser (t_star 0 or 1) leaves column 0 or n as the only non-zero one; a row with a non-finite coefficient gets a NaN
+ *     block (status OBTG_MD_OK).  Every specialised count has a fused value-and-blocks kernel (one launch; all build without
+ *     scratch); a context created under OBTG_TRUE_MIN_JAC_FUSED=0 forms the blocks in one more launch, as other degrees up to 31
+ *     do after their value path (three launches).
+ * Host and _dev calls give the same bits.  No region set, or a context whose d is not 2 or 3: OBTG_ERR_ARG before any launch.
+ * Every launch is timed under OBTG_K_SPEED.  _dev: dY is device memory [B][N d][n+1]; dY = NULL inside an obtg_fd_view is not
+ * built for this family and answers OBTG_ERR_ARG.  Not part of obtg_constraint_sweep_dev or of the structured step. */
+int obtg_ctx_set_keep_in(obtg_ctx*, const double* H /*[F][d+1]*/, int F, const int* VF /*[P][2]*/, int P);
+int obtg_len_keep_in(const obtg_ctx*);      /* P * (n+R+1)         */
+int obtg_keep_in(obtg_ctx*, const double* Y, int B, double* out /*[B][P][n+R+1]*/);
+int obtg_keep_in_dev(obtg_ctx*, const double* dY, int B, double* d_out);
+int obtg_keep_in_true_min(obtg_ctx*, const double* Y, int B, double eps_rel, int max_nodes,
+                          double* out /*[B][P]*/, double* t_star /*[B][P], nullable*/, int* status /*[B][P], nullable*/);
+int obtg_keep_in_true_min_dev(obtg_ctx*, const double* dY, int B, double eps_rel, int max_nodes, double* d_out, double* d_t_star,
+                              int* d_status);
+int obtg_keep_in_true_min_jac(obtg_ctx*, const double* Y, int B, double eps_rel, int max_nodes,
+                              double* out /*[B][P]*/, double* t_star /*[B][P], nullable*/, int* status /*[B][P], nullable*/,
+                              double* jac /*[B][P][d][n+1]*/);
+int obtg_keep_in_true_min_jac_dev(obtg_ctx*, const double* dY, int B, double eps_rel, int max_nodes, double* d_out, double* d_t_star,
+                                  int* d_status, double* d_jac);
 
 /* ---- the acceleration bound: |d^2 c / dtime^2| <= bound for every vehicle, in 2-D, 3-D and any other dimension ----
  * For vehicle v with control points P[c][i] (c < d, i <= n) on a span T = tf[b]:

@@ -163,6 +163,14 @@ _SIGNATURES = {
     "obtg_accel_true_min_dev": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
     "obtg_accel_true_min_jac": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "obtg_accel_true_min_jac_dev": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_ctx_set_keep_in": (_i, [_vp, _vp, _i, _vp, _i]),
+    "obtg_len_keep_in": (_i, [_vp]),
+    "obtg_keep_in": (_i, [_vp, _vp, _i, _vp]),
+    "obtg_keep_in_dev": (_i, [_vp, _vp, _i, _vp]),
+    "obtg_keep_in_true_min": (_i, [_vp, _vp, _i, _d, _i, _vp, _vp, _vp]),
+    "obtg_keep_in_true_min_dev": (_i, [_vp, _vp, _i, _d, _i, _vp, _vp, _vp]),
+    "obtg_keep_in_true_min_jac": (_i, [_vp, _vp, _i, _d, _i, _vp, _vp, _vp, _vp]),
+    "obtg_keep_in_true_min_jac_dev": (_i, [_vp, _vp, _i, _d, _i, _vp, _vp, _vp, _vp]),
     "obtg_jerk": (_i, [_vp, _vp, _vp, _i, _d, _vp]),
     "obtg_jerk_dev": (_i, [_vp, _vp, _vp, _i, _d, _vp]),
     "obtg_jerk_true_min": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
@@ -475,6 +483,8 @@ class Context(object):
         self.device = device
         self.n_poly = 0
         self.n_hull_pairs = None      # no hull pair list registered yet
+        self.keep_in_items = 0        # (vehicle, face) items of the keep-in region; 0: none set
+        self._keep_in_key = None      # the bytes of the tables set_keep_in last sent
 
     # -- plumbing
     def close(self):
@@ -739,6 +749,57 @@ class Context(object):
                                eps_rel=1e-9, max_nodes=100000):
         self._true_min_dev("obtg_accel_true_min_jac_dev", (dY, d_tf), B, (float(bound),), eps_rel, max_nodes, d_out, d_t_star,
                            d_status, d_jac, d_jac_tf)
+
+    # -- keep-in regions (include/obtg.h "keep-in regions"): region = (H[F][dim+1], VF[P][2]); every call below takes it as its
+    # optional `region` operand -- sent to the context only when its bytes differ from what the context holds -- or, with None,
+    # works on the region set_keep_in left there
+    def set_keep_in(self, H, VF):
+        """obtg_ctx_set_keep_in: F half-spaces a . p <= b as rows (a, b) of H and the (vehicle, face) items VF; an empty VF
+        clears the region."""
+        VF = _i32(VF).reshape(-1, 2)
+        H = _f64(H).reshape(-1, self.dim + 1)
+        self._check(self._lib.obtg_ctx_set_keep_in(self._h, _ptr(H), H.shape[0], _ptr(VF), VF.shape[0]), "obtg_ctx_set_keep_in")
+        self.keep_in_items = VF.shape[0]
+        self._keep_in_key = (H.tobytes(), VF.tobytes())
+
+    def _keep_in(self, region):
+        if region is not None:
+            H, VF = _f64(region[0]), _i32(region[1])
+            if self._keep_in_key != (H.tobytes(), VF.tobytes()):
+                self.set_keep_in(H, VF)
+        return self.keep_in_items          # (0: no region -- the library's call answers OBTG_ERR_ARG)
+
+    @property
+    def len_keep_in(self):
+        return self._lib.obtg_len_keep_in(self._h)
+
+    def keep_in(self, Y, region=None):
+        """The keep-in rows (obtg_keep_in): [B][P * (deg + DEG_ELEV + 1)] control points of b_f - a_f . c_v per (vehicle,
+        face) item -- exact linear constraints on the control points."""
+        self._keep_in(region)
+        Y, B = self._rows(Y)
+        out = pinned_empty((B, self.len_keep_in))
+        self._check(self._lib.obtg_keep_in(self._h, _ptr(Y), B, _ptr(out)), "obtg_keep_in")
+        return out
+
+    def keep_in_dev(self, dY, B, d_out):
+        self._check(self._lib.obtg_keep_in_dev(self._h, _vp(dY), int(B), _vp(d_out)), "obtg_keep_in_dev")
+
+    def keep_in_true_min(self, Y, region=None, eps_rel=1e-9, max_nodes=100000):
+        """Per item the true margin, the minimum over t in [0, 1] of b_f - a_f . c_v(t) (obtg_keep_in_true_min; DEG_ELEV does
+        not enter): dict(val[B][P], t_star[B][P], status[B][P])."""
+        return self._true_min("obtg_keep_in_true_min", self._keep_in(region), Y, None, (), eps_rel, max_nodes)
+
+    def keep_in_true_min_dev(self, dY, B, d_out, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
+        self._true_min_dev("obtg_keep_in_true_min_dev", (dY,), B, (), eps_rel, max_nodes, d_out, d_t_star, d_status)
+
+    def keep_in_true_min_jac(self, Y, region=None, eps_rel=1e-9, max_nodes=100000):
+        """keep_in_true_min with its envelope Jacobian (obtg_keep_in_true_min_jac): dict(val, t_star, status -- the bits of
+        keep_in_true_min --, jac[B][P][dim][deg+1] = -a_f[c] B_i(t_star): d/d(the item's own vehicle's control points))."""
+        return self._true_min("obtg_keep_in_true_min_jac", self._keep_in(region), Y, None, (), eps_rel, max_nodes, "jac")
+
+    def keep_in_true_min_jac_dev(self, dY, B, d_out, d_jac, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
+        self._true_min_dev("obtg_keep_in_true_min_jac_dev", (dY,), B, (), eps_rel, max_nodes, d_out, d_t_star, d_status, d_jac)
 
     def jerk(self, Y, tf, bound):
         """The jerk-bound rows (obtg_jerk): [B][N * (2 deg + DEG_ELEV + 1)] control points of

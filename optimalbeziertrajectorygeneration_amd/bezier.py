@@ -258,6 +258,28 @@ class Bezier(BezierParams):
         _raise_md(r['status'][0], 'spaceCurvatureMax')
         return float(r['k_max'][0]), float(r['t_max'][0])
 
+    def keepInMargins(self, A, b, eps=1e-12, max_nodes=100000):
+        """(margins[F], t[F]): per half-space a_f . p <= b_f of the region A p <= b (A[F][dim], b[F], dim 2 or 3) the true
+        minimum over the curve of b_f - a_f . c(t) and the parameter in [0, 1] where it is reached (obtg_keep_in_true_min, the
+        call behind BezOptimization.keepInConstraints): the curve stays inside iff every margin is >= 0; with |a_f| = 1 a
+        margin is a distance.  It depends on neither t0 nor tf.  Not in the reference."""
+        if self.dim not in (2, 3):
+            raise ValueError('The input curve must be two or three dimensional,\n'
+                             'instead it is {} dimensional'.format(self.dim))
+        A, b = np.asarray(A, dtype=np.float64), np.asarray(b, dtype=np.float64)
+        if A.ndim != 2 or A.shape[0] < 1 or A.shape[1] != self.dim or b.shape != (A.shape[0],):
+            raise ValueError('keepInMargins needs A[F][{}] and b[F], F >= 1, not shapes {} and {}'.format(self.dim, A.shape, b.shape))
+        F = A.shape[0]
+        ctx = _capi.Context(1, self.dim, self.deg, 0, device=_capi.default_device())
+        try:
+            region = (np.hstack((A, b[:, None])), np.stack((np.zeros(F, np.int32), np.arange(F, dtype=np.int32)), axis=1))
+            r = ctx.keep_in_true_min(self.cpts, region, eps_rel=float(eps), max_nodes=int(max_nodes))
+        finally:
+            ctx.close()
+        for st in r['status'][0]:
+            _raise_md(st, 'keepInMargins')
+        return r['val'][0].copy(), r['t_star'][0].copy()
+
     def split(self, tDiv):
         """Two curves, before and after tDiv (bezier.py:533-572): de Casteljau at (tDiv - t0)/(tf - t0); the
         pieces keep the original span's ends, [t0, tDiv] and [tDiv, tf]."""

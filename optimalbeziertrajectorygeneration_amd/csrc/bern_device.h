@@ -262,6 +262,48 @@ __device__ __forceinline__ void envelope_block(const double* __restrict__ ya, co
     }
 }
 
+// ---- The keep-in rows (obtg_keep_in, obtg_keep_in_true_min[_jac]): a vehicle against one half-space a . p <= b of its region.
+// h = (a[0 .. DIM-1], b), one row of the region's table; y: the vehicle's [DIM][nc] control points.
+//     g(t) = b - a . c(t),  Bernstein coefficient i:  g_i = b - sum_c a[c] P[c][i]   (degree n: no product of curves, no span)
+// keep_in_coeff IS the definition of the rows: the fused kernels, the blocks kernel's operands and the rows kernel all call
+// it, the sum runs in coordinate order and every step is an explicit fma, so every form gives the same bits.
+template <int DIM>
+__device__ __forceinline__ double keep_in_coeff(const double* __restrict__ h, const double* __restrict__ y, const int nc, const int i)
+{
+    double g = __builtin_fma(-h[0], y[i], h[DIM]);
+#pragma unroll
+    for (int c = 1; c < DIM; ++c) g = __builtin_fma(-h[c], y[c * nc + i], g);
+    return g;
+}
+
+// Envelope block of one keep-in row at parameter t (obtg_keep_in_true_min_jac): g is linear in the control points, so the
+// block does not read them:  out[c][i] = -a[c] B_i^n(t), n = nc - 1.  The basis as envelope_block forms its own -- the de
+// Casteljau recurrence on the basis, every multiply-add an explicit fma, every other product alone: the same arithmetic under
+// `fp contract(fast)` and `(off)`, for every NCMAX >= nc.  t = 0 / t = 1 leave exactly one non-zero column (0 / n); a NaN t
+// gives a NaN block (0 x NaN is NaN: a face with a[c] == 0 too).
+template <int NCMAX, int DIM>
+__device__ __forceinline__ void keep_in_envelope_block(const double* __restrict__ h, const int nc, const double t, double* __restrict__ out)
+{
+    const double s = 1.0 - t;
+    double w[NCMAX];
+#pragma unroll
+    for (int i = 0; i < NCMAX; ++i) w[i] = i == 0 ? 1.0 : 0.0;
+#pragma unroll
+    for (int r = 1; r < NCMAX; ++r)
+        if (r < nc) {
+#pragma unroll
+            for (int i = r; i >= 1; --i) w[i] = __builtin_fma(t, w[i - 1], s * w[i]);
+            w[0] = s * w[0];
+        }
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+        const double na = -h[c];
+#pragma unroll
+        for (int i = 0; i < NCMAX; ++i)
+            if (i < nc) out[c * nc + i] = na * w[i];
+    }
+}
+
 // The source curve of a speed row -- Bezier.diff(): (n/T)(P_(i+1) - P_i), then elev(1) back to degree n (bezier.py:497-519) --
 // in the arithmetic of k_normsq_elev's speed path, for the kernels that must reproduce obtg_speed's R = 0 rows bit for bit
 // (obtg_speed_true_min).  That path writes  t_c = p_c * (-val) + p_(c+1) * val  and  d_c = t_(c-1) * (c/n) + t_c * ((n-c)/n)

@@ -1566,6 +1566,78 @@ RowFamily jerk_row_family(const obtg_ctx* c, const double* d_tf, double bound)
     return f;
 }
 
+// The keep-in rows to memory (obtg_keep_in; the family's rows_r0 with R = 0), any degree 1 .. 31: one wave per (row, item),
+// lane i forms coefficient i (bern_device.h keep_in_coeff, then the fused body's output transform: fma(1, g, 0) takes a -0 to
+// +0 there and so here); R > 0: the row is then elevated ONCE, in k_bern_elev's arithmetic -- C(n, .) g in LDS, conv_at with
+// C(R, .), the quotient by C(n + R, .) -- so the result is the bits of obtg_bern_elev on the R = 0 row.
+struct KeepInRowsParams {
+    const double* __restrict__ Y;      // [B][n_veh*DIM][nc]
+    const double* __restrict__ H;      // [F][DIM + 1]
+    const int2* __restrict__ VF;       // [P]
+    const double* __restrict__ bin;    // concatenated binomial rows
+    double* __restrict__ out;          // [B][P][nc + R]
+    int n_veh, P, nc, R;
+    int o_n, o_R, o_nR;                // offsets of rows C(n, .), C(R, .), C(n + R, .)
+    double sign, offset;
+};
+
+template <int DIM>
+__global__ __launch_bounds__(kWave) void k_keep_in_rows(const KeepInRowsParams p)
+{
+    __shared__ double sh[kMdMaxCurveK];
+    const long item = blockIdx.x;
+    const int lane = threadIdx.x, nc = p.nc, LR = nc + p.R;
+    const int b = (int)(item / p.P), it = (int)(item - (long)b * p.P);
+    const int2 vf = p.VF[it];
+    const double* v = p.Y + ((size_t)b * p.n_veh + vf.x) * (DIM * nc);
+    const double* h = p.H + (size_t)vf.y * (DIM + 1);
+    double g = 0.0;
+    if (lane < nc) g = fma(p.sign, keep_in_coeff<DIM>(h, v, nc, lane), p.offset);
+    double* o = p.out + (size_t)item * LR;
+    if (p.R == 0) {
+        if (lane < nc) o[lane] = g;
+        return;
+    }
+    const double* bn = p.bin + p.o_n;
+    const double* bR = p.bin + p.o_R;
+    const double* bo = p.bin + p.o_nR;
+    if (lane < nc) sh[lane] = g * bn[lane];
+    __syncthreads();
+    for (int k = lane; k < LR; k += kWave) o[k] = conv_at(sh, nc, bR, p.R + 1, k) / bo[k];
+}
+
+int launch_keep_in_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, int R, double* d_out)
+{
+    if (B <= 0 || f.items <= 0) return OBTG_OK;
+    const int n = c->deg;
+    if ((c->dim != 2 && c->dim != 3) || n + 1 > kMdMaxCurveK || R < 0 || n + R + 1 > kMaxGenericLen) return OBTG_ERR_UNSUPPORTED;
+    KeepInRowsParams p{};
+    p.Y = dY; p.H = c->d_keep_H.as<double>(); p.VF = c->d_keep_VF.as<int2>(); p.out = d_out;
+    p.n_veh = c->n_veh; p.P = f.items; p.nc = n + 1; p.R = R; p.sign = f.sign; p.offset = f.offset;
+    if (R > 0) {
+        for (int v : { n, R, n + R }) { const int o = binrow_offset(c, v); if (o < 0) return o; }
+        p.o_n = binrow_offset(c, n); p.o_R = binrow_offset(c, R); p.o_nR = binrow_offset(c, n + R);
+    }
+    p.bin = c->d_binrows.as<double>();
+    ScopedKernelTimer t(c, f.kernel_id);
+    hipLaunchKernelGGL(c->dim == 2 ? k_keep_in_rows<2> : k_keep_in_rows<3>, dim3((unsigned)((size_t)B * f.items)), dim3(kWave), 0,
+                       c->stream, p);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
+static int keep_in_rows_r0(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out)
+{
+    return launch_keep_in_rows(c, f, dY, B, 0, d_out);
+}
+
+RowFamily keep_in_row_family(const obtg_ctx* c)
+{
+    RowFamily f{ ROWS_KEEP_IN, c->keep_P, OBTG_K_SPEED, 1.0, 0.0, nullptr, keep_in_rows_r0 };
+    f.row_len = c->deg + 1;
+    return f;
+}
+
 template <int NC>
 static int launch_dyn_t(obtg_ctx* c, const AngParams& p, int kernel_id)
 {

@@ -255,6 +255,7 @@ const char* obtg_abi_symbols(void)
         "obtg_ang_rate_poly\0obtg_ang_rate_poly_dev\0obtg_ang_rate_true_min\0obtg_ang_rate_true_min_dev\0obtg_ang_rate_true_min_jac\0obtg_ang_rate_true_min_jac_dev\0"
         "obtg_curvature_poly\0obtg_curvature_poly_dev\0obtg_curvature_true_min\0obtg_curvature_true_min_dev\0obtg_curvature_true_min_jac\0obtg_curvature_true_min_jac_dev\0obtg_bern_curvature\0obtg_bern_curvature_dev\0"
         "obtg_space_curvature_poly\0obtg_space_curvature_poly_dev\0obtg_space_curvature_true_min\0obtg_space_curvature_true_min_dev\0obtg_space_curvature_true_min_jac\0obtg_space_curvature_true_min_jac_dev\0obtg_bern_space_curvature\0obtg_bern_space_curvature_dev\0"
+        "obtg_ctx_set_keep_in\0obtg_len_keep_in\0obtg_keep_in\0obtg_keep_in_dev\0obtg_keep_in_true_min\0obtg_keep_in_true_min_dev\0obtg_keep_in_true_min_jac\0obtg_keep_in_true_min_jac_dev\0"
         "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_restrict\0obtg_bern_eval\0"
         "obtg_euclidean_obj\0obtg_accel_obj\0obtg_jerk_obj\0"
         "obtg_bern_arc_length\0obtg_bern_arc_length_dev\0obtg_arc_length_obj\0obtg_arc_length_obj_dev\0"
@@ -323,7 +324,7 @@ void obtg_ctx_destroy(obtg_ctx* c)
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
     DevBuf* bufs[] = { &c->d_pairs, &c->d_obs, &c->d_w2, &c->d_Tt, &c->d_Td, &c->d_Tf, &c->d_ang_dd, &c->d_ang_flags, &c->d_vp_off, &c->d_vp_idx, &c->d_ang_w2n, &c->d_ang_w22n, &c->d_ang_wn, &c->d_ang_rows, &c->d_curv_tab, &c->d_ang_T4, &c->d_ang_cv2, &c->d_jac,
                        &c->d_binrows, &c->d_tiles, &c->d_poly_pts, &c->d_poly_off, &c->d_hp_a, &c->d_hp_b, &c->d_tile_chunk_off, &c->d_tile_order, &c->d_tile_pslots,
-                       &c->d_tile_cobj_off, &c->d_tile_cobjs, &c->d_tile_ij, &c->d_struct_tickets, &c->ws_in,
+                       &c->d_tile_cobj_off, &c->d_tile_cobjs, &c->d_tile_ij, &c->d_struct_tickets, &c->d_keep_H, &c->d_keep_VF, &c->ws_in,
                        &c->ws_in2, &c->ws_out, &c->ws_fd };
     for (DevBuf* b : bufs) b->release();
     for (auto& b : c->ws_misc) b.release();
@@ -1712,7 +1713,7 @@ static int true_min_chain(obtg_ctx* c, const RowFamily& f, const double* dY, int
         rc = launch_true_min(c, f, dY, B, eps_rel, max_nodes, d_out, d_t, d_status);
     }
     if (rc == OBTG_ERR_UNSUPPORTED) {
-        const int K = 2 * c->deg + 1;
+        const int K = row_len(f, c->deg);
         if (!bern_extrema_supported(K)) return OBTG_ERR_UNSUPPORTED;
         const long items = (long)B * f.items;
         DevBuf& ws = c->ws_misc[WS_L_ROWS];
@@ -2011,6 +2012,100 @@ static int curvature_true_min(obtg_ctx* c, RowKind kind, const double* Y, int B,
     if (!Y || (want_jac && !jac)) return OBTG_ERR_ARG;
     if (B == 0) return OBTG_OK;
     return true_min_host(c, curvature_row_family(c, kind, max_curv), Y, nullptr, B, eps_rel, max_nodes, out, t_star, status, jac, nullptr);
+}
+
+// The keep-in family (ROWS_KEEP_IN): the curvature entry points' shape -- no time span, nothing takes tf, no jac_tf -- with
+// keep_in_row_family, whose operand is the region obtg_ctx_set_keep_in left on the context.  Refusals, all before any launch:
+// no region set or a context that is neither planar nor in space is OBTG_ERR_ARG; a degree above 31 OBTG_ERR_UNSUPPORTED.  The
+// _dev calls take dY itself: the batch of an open obtg_fd_view (dY == NULL) is not built for this family, OBTG_ERR_ARG.
+int obtg_ctx_set_keep_in(obtg_ctx* c, const double* H, int F, const int* VF, int P)
+{
+    if (!check_ctx(c) || F < 0 || P < 0) return OBTG_ERR_ARG;
+    if (P > 0) {
+        if ((c->dim != 2 && c->dim != 3) || F < 1 || !H || !VF) return OBTG_ERR_ARG;
+        for (int k = 0; k < P; ++k)
+            if (VF[2 * k] < 0 || VF[2 * k] >= c->n_veh || VF[2 * k + 1] < 0 || VF[2 * k + 1] >= F) return OBTG_ERR_ARG;
+    }
+    (void)hipSetDevice(c->device);
+    OBTG_HIP(c, hipStreamSynchronize(c->stream));
+    c->keep_F = c->keep_P = 0;             // (set again once both tables are on the device)
+    if (P == 0) return OBTG_OK;
+    int rc = upload(c, c->d_keep_H, H, sizeof(double) * (size_t)F * (c->dim + 1));
+    if (!rc) rc = upload(c, c->d_keep_VF, VF, sizeof(int) * 2 * (size_t)P);
+    if (rc) return rc;
+    c->keep_F = F; c->keep_P = P;
+    return OBTG_OK;
+}
+
+int obtg_len_keep_in(const obtg_ctx* c) { return c ? c->keep_P * (c->deg + c->R + 1) : 0; }
+
+static int keep_in_args(const obtg_ctx* c, const double* out, int B, int max_nodes, double eps_rel)
+{
+    if (!check_ctx(c) || c->keep_P <= 0 || (c->dim != 2 && c->dim != 3) || !out || B < 0 || max_nodes < 1 || !(eps_rel >= 0.0))
+        return OBTG_ERR_ARG;
+    return c->deg > 31 ? OBTG_ERR_UNSUPPORTED : OBTG_OK;
+}
+
+int obtg_keep_in_dev(obtg_ctx* c, const double* dY, int B, double* d_out)
+{
+    if (int rc = keep_in_args(c, d_out, B, 1, 0.0)) return rc;
+    if (!dY) return OBTG_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    return launch_keep_in_rows(c, keep_in_row_family(c), dY, B, c->R, d_out);
+}
+
+int obtg_keep_in(obtg_ctx* c, const double* Y, int B, double* out)
+{
+    if (int rc = keep_in_args(c, out, B, 1, 0.0)) return rc;
+    if (!Y) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    const size_t n = (size_t)obtg_len_keep_in(c) * B;
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    double* d_out = h.out<double>(c->ws_out, n, true);
+    h.run([&] { return launch_keep_in_rows(c, keep_in_row_family(c), dY, B, c->R, d_out); });
+    return h.finish(out, d_out, n);
+}
+
+// want_jac: the _jac entry points, where the blocks are not optional
+static int keep_in_true_min_dev(obtg_ctx* c, const double* dY, int B, double eps_rel, int max_nodes, double* d_out, double* d_t_star,
+                                int* d_status, bool want_jac, double* d_jac)
+{
+    if (int rc = keep_in_args(c, d_out, B, max_nodes, eps_rel)) return rc;
+    if (!dY || (want_jac && !d_jac)) return OBTG_ERR_ARG;
+    return true_min_dev(c, keep_in_row_family(c), dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, d_jac, nullptr);
+}
+
+static int keep_in_true_min(obtg_ctx* c, const double* Y, int B, double eps_rel, int max_nodes, double* out, double* t_star,
+                            int* status, bool want_jac, double* jac)
+{
+    if (int rc = keep_in_args(c, out, B, max_nodes, eps_rel)) return rc;
+    if (!Y || (want_jac && !jac)) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    return true_min_host(c, keep_in_row_family(c), Y, nullptr, B, eps_rel, max_nodes, out, t_star, status, jac, nullptr);
+}
+
+int obtg_keep_in_true_min_dev(obtg_ctx* c, const double* dY, int B, double eps_rel, int max_nodes, double* d_out, double* d_t_star,
+                              int* d_status)
+{
+    return keep_in_true_min_dev(c, dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, false, nullptr);
+}
+
+int obtg_keep_in_true_min(obtg_ctx* c, const double* Y, int B, double eps_rel, int max_nodes, double* out, double* t_star, int* status)
+{
+    return keep_in_true_min(c, Y, B, eps_rel, max_nodes, out, t_star, status, false, nullptr);
+}
+
+int obtg_keep_in_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, double eps_rel, int max_nodes, double* d_out, double* d_t_star,
+                                  int* d_status, double* d_jac)
+{
+    return keep_in_true_min_dev(c, dY, B, eps_rel, max_nodes, d_out, d_t_star, d_status, true, d_jac);
+}
+
+int obtg_keep_in_true_min_jac(obtg_ctx* c, const double* Y, int B, double eps_rel, int max_nodes, double* out, double* t_star,
+                              int* status, double* jac)
+{
+    return keep_in_true_min(c, Y, B, eps_rel, max_nodes, out, t_star, status, true, jac);
 }
 
 // Free curves c[M][dim][K], any K from 2 to 32 whatever the context's shape is: the family's rows kernel and workspace search

@@ -23,7 +23,9 @@
 // (true_min_body) over a family struct (TsepRows, SpeedRows, AngRows, AccelRows, JerkRows), under the kernel names
 // k_tsep_true_min / k_speed_true_min / k_ang_true_min / k_accel_true_min / k_jerk_true_min.  The acceleration and the jerk
 // families' fused value-and-blocks kernels are the counts of OBTG_NC_ACCEL_LIST / OBTG_NC_JERK_LIST (obtg_internal.h): every
-// count of OBTG_NC_SEP, in 2-D and 3-D.
+// count of OBTG_NC_SEP, in 2-D and 3-D.  The keep-in family (obtg_keep_in_true_min[_jac]: KeepInRows, k_keep_in_true_min,
+// k_keep_in_envelope, bern_device.h keep_in_coeff / keep_in_envelope_block) is the one whose polynomial is linear in the curve:
+// L = NC coefficients per item, not 2 NC - 1 -- the row length is the family's (obtg_internal.h RowFamily::row_len).
 // Envelope Jacobian: the derivative of the item's polynomial at the t_star the search returned, bern_device.h
 // envelope_block / speed_envelope_block / ang_envelope_block / accel_envelope_block / jerk_envelope_block -- written with explicit fma, so it is the same arithmetic here
 // (contraction off) as anywhere else.  Fused form: the <NC, DIM, true> kernels re-read the item's control points from Y after the search (no
@@ -378,6 +380,38 @@ struct JerkRows {
     }
 };
 
+struct KeepInExParams {
+    const double* __restrict__ Y;      // [B][n_veh*DIM][NC]
+    const double* __restrict__ H;      // [F][DIM + 1]: (a, b) of every half-space a . p <= b
+    const int2* __restrict__ VF;       // [P]: (vehicle, face)
+    ExParams ex;                       // outputs [B][P]; c unused
+    double* __restrict__ jac;          // [B][P][DIM][NC] (the envelope forms)
+    int n_veh, P;
+    double sign, offset;               // the identity (1, 0)
+};
+
+// obtg_keep_in's rows at R = 0, g(t) = b_f - a_f . c_v(t) of a (vehicle, face) item: a polynomial of the curve's own degree, so
+// L = NC (bern_device.h keep_in_coeff).  No span.  The envelope block does not read Y: g is linear in the control points.
+template <int NC_, int DIM>
+struct KeepInRows {
+    using Params = KeepInExParams;
+    static constexpr int NC = NC_, L = NC_;
+    static __device__ __forceinline__ void coeffs(const Params& q, long item, double (&cf)[L])
+    {
+        const int b = (int)(item / q.P), it = (int)(item - (long)b * q.P);
+        const int2 vf = q.VF[it];
+        const double* v = q.Y + ((size_t)b * q.n_veh + vf.x) * (DIM * NC);
+        const double* h = q.H + (size_t)vf.y * (DIM + 1);
+#pragma unroll
+        for (int i = 0; i < NC; ++i) cf[i] = keep_in_coeff<DIM>(h, v, NC, i);
+    }
+    static __device__ __forceinline__ void envelope(const Params& q, long item, int nc, double t)
+    {
+        const int it = (int)(item % q.P);
+        keep_in_envelope_block<NC, DIM>(q.H + (size_t)q.VF[it].y * (DIM + 1), nc, t, q.jac + (size_t)item * (DIM * nc));
+    }
+};
+
 struct AngExParams {
     const double* __restrict__ Y;      // [B][n_veh*2][NC]
     const double* __restrict__ tf;     // [B]
@@ -495,6 +529,10 @@ template <int NC, int DIM, bool JAC>
 __global__ __launch_bounds__(kExWaves * kWave) void k_jerk_true_min(const SpeedExParams q) { true_min_body<JerkRows<NC, DIM>, JAC>(q); }
 template <int DIM>
 __global__ __launch_bounds__(kEnvThreads) void k_jerk_envelope(const SpeedExParams q, const int nc) { envelope_body<JerkRows<kEnvMaxNC, DIM>>(q, nc); }
+template <int NC, int DIM, bool JAC>
+__global__ __launch_bounds__(kExWaves * kWave) void k_keep_in_true_min(const KeepInExParams q) { true_min_body<KeepInRows<NC, DIM>, JAC>(q); }
+template <int DIM>
+__global__ __launch_bounds__(kEnvThreads) void k_keep_in_envelope(const KeepInExParams q, const int nc) { envelope_body<KeepInRows<kEnvMaxNC, DIM>>(q, nc); }
 template <int NC, bool JAC>
 __global__ __launch_bounds__(kExWaves * kWave) void k_ang_true_min(const AngExParams q) { true_min_body<AngRows<NC, 2>, JAC>(q); }
 __global__ __launch_bounds__(kEnvThreads) void k_ang_envelope(const AngExParams q, const int nc) { envelope_body<AngRows<kEnvMaxNC, 2>>(q, nc); }
@@ -1101,6 +1139,19 @@ template <> struct RowKernels<JerkRows> {
     }
 };
 
+// the keep-in family: every count of OBTG_NC_SEP, values and blocks, builds without scratch: no list
+template <> struct RowKernels<KeepInRows> {
+    template <int NC, int DIM, bool JAC> static auto fused() { return k_keep_in_true_min<NC, DIM, JAC>; }
+    template <int DIM> static auto envelope() { return k_keep_in_envelope<DIM>; }
+    static KeepInExParams params(const obtg_ctx* c, const RowFamily& f, const double* dY, double* d_jac, double*)
+    {
+        KeepInExParams q{};
+        q.Y = dY; q.H = c->d_keep_H.as<double>(); q.VF = c->d_keep_VF.as<int2>(); q.n_veh = c->n_veh; q.P = f.items; q.jac = d_jac;
+        q.sign = f.sign; q.offset = f.offset;
+        return q;
+    }
+};
+
 // the counts of OBTG_NC_SEP whose angular-rate kernels hold their operands in registers; the others
 // take the rows route
 static constexpr bool nc_in_ang(int nc) { return false OBTG_NC_ANG_LIST(OBTG_NC_EQ_); }
@@ -1252,12 +1303,13 @@ int launch_true_min(obtg_ctx* c, const RowFamily& f, const double* dY, int B, do
     if (rc) return rc;
     ExParams ex{};
     ex.val = d_out; ex.t = d_t; ex.status = d_status;
-    ex.M = (long)B * f.items; ex.K = 2 * c->deg + 1; ex.max_nodes = max_nodes; ex.eps_rel = eps_rel; ex.eps_abs = 0.0;
+    ex.M = (long)B * f.items; ex.K = row_len(f, c->deg); ex.max_nodes = max_nodes; ex.eps_rel = eps_rel; ex.eps_abs = 0.0;
     switch (f.kind) {
         case ROWS_ANG: return launch_fused<AngRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_SPEED: return launch_fused<SpeedRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_ACCEL: return launch_fused<AccelRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_JERK: return launch_fused<JerkRows>(c, f, dY, ex, d_jac, d_jac_tf);
+        case ROWS_KEEP_IN: return launch_fused<KeepInRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_CURV: case ROWS_SCURV: return launch_curv_fused(c, f, dY, ex, d_jac);
         default: return launch_fused<TsepRows>(c, f, dY, ex, d_jac, d_jac_tf);
     }
@@ -1289,6 +1341,7 @@ int launch_true_min_envelope(obtg_ctx* c, const RowFamily& f, const double* dY, 
         case ROWS_SPEED: return launch_blocks<SpeedRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_ACCEL: return launch_blocks<AccelRows>(c, f, dY, ex, d_jac, d_jac_tf);
         case ROWS_JERK: return launch_blocks<JerkRows>(c, f, dY, ex, d_jac, d_jac_tf);
+        case ROWS_KEEP_IN: return launch_blocks<KeepInRows>(c, f, dY, ex, d_jac, d_jac_tf);
         default: return launch_blocks<TsepRows>(c, f, dY, ex, d_jac, d_jac_tf);
     }
 }

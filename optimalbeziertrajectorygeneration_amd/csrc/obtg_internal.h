@@ -163,6 +163,10 @@ struct obtg_ctx {
     int ang_dd_R = -1;
     // obtg_ctx_set_second_speed_bound: every dynamics pass that writes speed rows also writes the other bound's rows
     struct { double bound = 0.0; int is_max = 0; double* d_out = nullptr; } speed2;
+    // obtg_ctx_set_keep_in: the region's half-spaces and the (vehicle, face) items of the keep-in rows; keep_P == 0: none set
+    obtg::DevBuf d_keep_H;    // double[keep_F][dim + 1]: (a, b) of a . p <= b
+    obtg::DevBuf d_keep_VF;   // int2[keep_P]
+    int keep_F = 0, keep_P = 0;
     std::vector<int> h_pairs; // host copy of the pair table (2 ints per pair)
     std::vector<int> h_tiles; // row-window tiles of the current (pair_begin, pair_count)
     obtg::DevBuf d_tiles;
@@ -389,14 +393,14 @@ int launch_bern_extrema(obtg_ctx* c, const double* d_c, long M, int K, int want_
 // A true-minimum row family (obtg_temporal_sep_true_min[_jac], obtg_speed_true_min[_jac], obtg_ang_rate_true_min[_jac], obtg_accel_true_min[_jac], obtg_jerk_true_min[_jac]) as the host path sees it: what one
 // call of the family contributes beyond the arguments every family has.  On the device the family is a struct of
 // extrema_kernels.hip (TsepRows, SpeedRows, AngRows, AccelRows, JerkRows), found by `kind`.
-enum RowKind { ROWS_TSEP, ROWS_SPEED, ROWS_ANG, ROWS_ACCEL, ROWS_JERK, ROWS_CURV, ROWS_SCURV };
+enum RowKind { ROWS_TSEP, ROWS_SPEED, ROWS_ANG, ROWS_ACCEL, ROWS_JERK, ROWS_CURV, ROWS_SCURV, ROWS_KEEP_IN };
 struct RowFamily {
     RowKind kind;
     int items;                  // per batch row: n_pairs | n_veh | 2 n_veh
     int kernel_id;              // every launch of the call is timed under it
     double sign, offset;        // the output transform of its rows
     const double* d_tf;         // [B], device; null where the rows have no time span
-    // its full rows at R = 0 from the any-degree kernel, [B][items][2 deg + 1], whatever the context's DEG_ELEV is: the launch
+    // its full rows at R = 0 from the any-degree kernel, [B][items][row_len], whatever the context's DEG_ELEV is: the launch
     // a context with R = 0 makes, bit for bit; the context is not touched
     int (*rows_r0)(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);
     double w = 0.0;             // ROWS_ANG: the bound on |angular rate| (it enters the coefficients, not the output transform);
@@ -405,13 +409,21 @@ struct RowFamily {
     // rows are num and den and serve both of its items, so the workspace has as many rows as the batch has items
     int (*search)(obtg_ctx* c, const RowFamily& f, const double* d_rows, long items, double eps_rel, int max_nodes, double* d_out,
                   double* d_t, int* d_status) = nullptr;
-    int ws_rows = 1;            // workspace rows of 2 deg + 1 per item (ROWS_SCURV: 4 -- wx, wy, wz, den)
+    int ws_rows = 1;            // workspace rows per item (ROWS_SCURV: 4 -- wx, wy, wz, den)
+    int row_len = 0;            // coefficients of a row at R = 0 -- what a workspace row holds and what the search sees; 0: 2 deg + 1
+                                // (ROWS_KEEP_IN: deg + 1, the polynomial is linear in the curve)
 };
+static inline int row_len(const RowFamily& f, int deg) { return f.row_len ? f.row_len : 2 * deg + 1; }
 RowFamily tsep_row_family(const obtg_ctx* c, double max_sep);                                         // bern_kernels.hip
 RowFamily speed_row_family(const obtg_ctx* c, const double* d_tf, double bound, int is_max);
 RowFamily accel_row_family(const obtg_ctx* c, const double* d_tf, double bound);                      // q = bound^2 - (d/2)|c''|^2
 RowFamily jerk_row_family(const obtg_ctx* c, const double* d_tf, double bound);                       // q = bound^2 - (d/2)|c'''|^2
 RowFamily ang_row_family(const obtg_ctx* c, const double* d_tf, double max_rate);                     // extrema_kernels.hip
+// The keep-in family (ROWS_KEEP_IN): the context's region (obtg_ctx_set_keep_in), one item per listed (vehicle, face), rows of
+// deg + 1 coefficients, no time span; dim 2 or 3.  launch_keep_in_rows: obtg_keep_in's rows out[B][P][deg + R + 1], the R = 0
+// coefficients elevated once per row (R = 0: the family's rows_r0), degree up to 31
+RowFamily keep_in_row_family(const obtg_ctx* c);                                                      // bern_kernels.hip
+int launch_keep_in_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, int R, double* d_out);
 // the angular-rate family's polynomials [B][n_veh][2][2 deg + 1] (obtg_ang_rate_poly; its rows_r0): dim 2, degree 1 .. 31
 int launch_ang_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);
 // The two curvature families, kind = ROWS_CURV (dim 2; two items, the sides, per vehicle; workspace rows num, den) or ROWS_SCURV

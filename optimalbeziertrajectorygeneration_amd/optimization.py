@@ -221,6 +221,49 @@ _KEY_ROWS = tuple((attr, tuple(fam.bound for fam in _ROW_FAMILIES if fam.optiona
 _KEY_BOUNDS = tuple(fam.bound for fam in _ROW_FAMILIES if not fam.optional)
 _KEY_TAIL = tuple(fam.bound for fam in _ROW_FAMILIES if fam.rows is None)            # (name, value) behind the obstacles, while set
 
+# The keep-in family, BESIDE the table: its operand is an array kept on the object (`keepIn`, like
+# `pointObstacles`), not a scalar bound of `model`, so it is in none of the tuples derived above -- the constructor checks its
+# rows option after the table's and _serve_key appends its own entry while a region is set.  It is found by key like the
+# others; its `bound` names the attribute, and what the device calls take in the bound's place is the pair of tables
+# _keep_in_tables makes of it (BezOptimization._operand).
+_KEEP_IN = _RowFamily('keepin', 'keepIn', True, 'keepInRows', 'keep_in', 'keep_in_true_min', 'keep_in_true_min_jac', None, (),
+                      False, 1, 'keepInConstraints', 'keepInJacobian', 'keep-in', False)
+_FAMILY[_KEEP_IN.key] = _KEEP_IN
+
+
+def _keep_in_tables(keepIn, numVeh, dim):
+    """(H[F][dim+1], VF[P][2]) of a `keepIn` argument, checked: a pair (A[F][dim], b[F]) -- the region A p <= b for every
+    vehicle, items vehicle-major with the faces in order -- or a LIST of numVeh such pairs or Nones (a vehicle of its own
+    region, or of none).  H holds the rows (a_f, b_f), VF the (vehicle, face) items (obtg_ctx_set_keep_in)."""
+    if dim not in (2, 3):
+        raise ValueError("keepIn needs dimension 2 or 3, not {}".format(dim))
+
+    def faces(pair, who):
+        try:
+            A, b = pair
+            A, b = np.asarray(A, dtype=float), np.asarray(b, dtype=float)
+        except (TypeError, ValueError):
+            raise ValueError("keepIn{} must be a pair (A[F][{}], b[F])".format(who, dim))
+        if A.ndim != 2 or A.shape[0] < 1 or A.shape[1] != dim or b.shape != (A.shape[0],):
+            raise ValueError("keepIn{} must be a pair (A[F][{}], b[F]) with F >= 1, not shapes {} and {}"
+                             .format(who, dim, A.shape, b.shape))
+        return np.hstack((A, b[:, None]))
+
+    if isinstance(keepIn, list):
+        if len(keepIn) != numVeh:
+            raise ValueError("a keepIn list must have numVeh = {} entries (pairs or None), not {}".format(numVeh, len(keepIn)))
+        tables = [(v, faces(pair, '[{}]'.format(v))) for v, pair in enumerate(keepIn) if pair is not None]
+        if not tables:
+            raise ValueError("a keepIn list needs a region for at least one vehicle")
+        first = np.cumsum([0] + [Hv.shape[0] for _, Hv in tables])
+        VF = np.concatenate([np.stack((np.full(Hv.shape[0], v), o + np.arange(Hv.shape[0])), axis=1)
+                             for (v, Hv), o in zip(tables, first)])
+        return np.ascontiguousarray(np.vstack([Hv for _, Hv in tables])), np.ascontiguousarray(VF, dtype=np.int32)
+    H = faces(keepIn, '')
+    F = H.shape[0]
+    VF = np.stack((np.repeat(np.arange(numVeh), F), np.tile(np.arange(F), numVeh)), axis=1)
+    return np.ascontiguousarray(H), np.ascontiguousarray(VF, dtype=np.int32)
+
 # The goals with a device call ('timeopt' is x[-1]).  goal, lower case: (key in _serve / _fd_values; values [B] of the rows Y;
 # gradient blocks [B][N d][n+1] of the rows Y), both called (bezopt, ctx, Y, what) -- `what` names the caller where a search
 # that does not end raises (the arc length alone).
@@ -364,7 +407,9 @@ class BezOptimization(object):
                  maxJerk=None,
                  jerkRows='all',
                  maxCurvature=None,
-                 maxSpaceCurvature=None):
+                 maxSpaceCurvature=None,
+                 keepIn=None,
+                 keepInRows='all'):
         """Beyond the reference's keywords: `device` (HIP ordinal; None: this process's, see _capi.default_device) and `separationRows` --
         'all': temporalSeparationConstraints returns every elevated control point of every pair, as the
         reference does (optimization.py:337); 'min': one row per pair, the smallest of them -- the
@@ -398,11 +443,22 @@ class BezOptimization(object):
         # maxSpaceCurvature (None: no bound; dim 3): curvature <= maxSpaceCurvature per vehicle in space, |c' x c''| / |c'|^3
         # -- maxSpaceCurvatureConstraints: N true rows, maxSpaceCurvature - max over the path of kappa
         # (obtg_space_curvature_true_min).  The norm of a cross product has no sign: one row per vehicle.
+        # keepIn (None: no region; dim 2 or 3): stay inside -- a pair (A[F][d], b[F]), the region A p <= b for every vehicle, or
+        # a LIST of numVeh such pairs or Nones (a tuple is one pair, a list is per vehicle) -- keepInConstraints: one row
+        # b_f - a_f . c_v per (vehicle, face), vehicle-major, faces in order.  keepInRows 'all': its n+R+1 control points, exact
+        # linear constraints (obtg_keep_in); 'true_min': its true margin over the trajectory (obtg_keep_in_true_min), P rows
+        # whatever DEG_ELEV is.  Kept as `self.keepIn`, like pointObstacles: a driver may edit the arrays in place between solves.
         given = locals()
         for attr in reversed(_ROWS_OPTIONS):         # (the newest family's option is checked first, as it always was)
             if given[attr] not in ('all', 'true_min'):
                 raise ValueError("{} must be 'all' or 'true_min', not {!r}".format(attr, given[attr]))
             setattr(self, attr, given[attr])
+        if keepInRows not in ('all', 'true_min'):    # (the keep-in family is beside the table: after the table's options)
+            raise ValueError("keepInRows must be 'all' or 'true_min', not {!r}".format(keepInRows))
+        self.keepInRows = keepInRows
+        if keepIn is not None:
+            _keep_in_tables(keepIn, numVeh, dimension)      # raises for a region the device calls could not take
+        self.keepIn = keepIn
         if separationRows not in ('all', 'min', 'active', 'true_min'):
             raise ValueError("separationRows must be 'all', 'min', 'active' or 'true_min', not {!r}".format(separationRows))
         if separationRows == 'active' and not 1 <= int(activeRows) <= 4:
@@ -496,10 +552,17 @@ class BezOptimization(object):
     # ------------------------------------------------------------------ the per-vehicle row families (_ROW_FAMILIES)
     def _bound(self, fam, what):
         """The family's bound from `model`; `what` (a public name) cannot be answered without one."""
-        bound = self.model[fam.bound]
+        bound = self._operand(fam)
         if bound is None:
             raise ValueError("{} needs a bound: {} is None".format(what, fam.bound))
         return bound
+
+    def _operand(self, fam):
+        """What the family's device calls take as their bound: the value in `model` -- for the keep-in family the region's
+        tables (H, VF) of `keepIn` as it is NOW (drivers edit it in place); None: not set."""
+        if fam is not _KEEP_IN:
+            return self.model[fam.bound]
+        return None if self.keepIn is None else _keep_in_tables(self.keepIn, self.model['numVeh'], self.model['dim'])
 
     def _vehicle_true_min(self, fam, ctx, Y, tf, bound, what, envelope=False):
         """The family's true-minimum call on the rows Y at TRUE_MIN_EPS_REL (envelope: with the envelope blocks): its dict;
@@ -515,13 +578,12 @@ class BezOptimization(object):
     def _vehicle_rows(self, fam, ctx, Y, tf):
         """[B][rows]: the family's rows under its rows option -- 'all': the control points of every vehicle; 'true_min': the
         true minima, [B][N * fam.sides] -- of the rows Y on the context ctx."""
-        bound = self.model[fam.bound]
-        if bound is None:
-            self._bound(fam, fam.constraints)        # raises
+        bound = self._bound(fam, fam.constraints)
         if self._rows_option(fam) == 'true_min':
             v = self._vehicle_true_min(fam, ctx, Y, tf, bound, fam.constraints + '(true_min)')['val']
             return v.reshape(v.shape[0], -1)
-        return getattr(ctx, fam.rows)(Y, tf, bound, *fam.lead)
+        operands = (Y, tf, bound) if fam.span else (Y, bound)
+        return getattr(ctx, fam.rows)(*operands, *fam.lead)
 
     def _vehicle_closure(self, fam):
         def direct(x):
@@ -766,6 +828,14 @@ class BezOptimization(object):
             return closure(x)
         return wrapper
 
+    @property
+    def keepInConstraints(self):
+        """b_f - a_f . c_v >= 0 for every (vehicle, face) of `keepIn`, vehicle-major: P (n+R+1) control points, exact linear
+        constraints (keepInRows='all'; obtg_keep_in), or P true margins over the trajectory ('true_min'; obtg_keep_in_true_min)
+        -- the same whatever tf is.  Not part of the one-launch structured step, of the constraint sweep, of distributed.py or
+        of sequential.py."""
+        return self._vehicle_closure(_KEEP_IN)
+
     def spatialSeparationConstraints(self, x, robust=False):
         """All-pairs minDist over vehicles AND shape obstacles (optimization.py:109-133);
         returns shape (P, 3): (dist, t1, t2) - maxSep, as the reference does.
@@ -924,6 +994,9 @@ class BezOptimization(object):
         rows = [v for attr, optional in _KEY_ROWS for v in (getattr(self, attr), *[m[b] for b in optional])]
         bounds = [m[b] for b in _KEY_BOUNDS]
         tail = [(b, m[b]) for b in _KEY_TAIL if m[b] is not None]
+        if self.keepIn is not None:          # the region by its tables' BYTES, as the obstacles: drivers edit it in place
+            H, VF = self._operand(_KEEP_IN)
+            tail.append(('keepIn', self.keepInRows, H.tobytes() + VF.tobytes()))
         return (int(DEG_ELEV), self.separationRows, *rows, self.activeRows, self._rv_cache[0], self.model['maxSep'], *bounds,
                 None if self._timeopt() else self.model['tf'],
                 None if self.pointObstacles is None else np.asarray(self.pointObstacles, dtype=float).tobytes(),
@@ -1094,6 +1167,31 @@ class BezOptimization(object):
         dependence on tf: that part of a time-optimal problem's tf column is an exact 0 (with prescribed speeds the column
         still carries dY/dtf)."""
         return self._jac_vehicle(x, 'scurv', structured, method)
+
+    def keepInJacobian(self, x, structured=True, method='fd'):
+        """d(keepInConstraints)/dx, dense [rows][n_x]: method='fd' differences the closure's rows (one batched call; the rows
+        are linear in x, `structured` changes nothing); method='envelope' (keepInRows='true_min') is the derivative of each true
+        margin at the parameter its search returns (obtg_keep_in_true_min_jac, one call at x), scattered to the columns of the
+        item's own vehicle; method='exact' is not built.  The rows have no explicit dependence on tf: that part of a
+        time-optimal problem's tf column is an exact 0 (with prescribed speeds the column still carries dY/dtf)."""
+        fam = _KEEP_IN
+        region = self._bound(fam, fam.jacobian)          # a missing region answers before anything is computed
+        self._check_jac_method(fam, method)
+        if method != 'envelope':
+            return self._jac(x, fam.key)
+        x = np.asarray(x, dtype=float)
+        r = self._vehicle_true_min(fam, self._ctx(False), self.reshapeVectors(x[None]), None, region, fam.jacobian + '(envelope)',
+                                   envelope=True)
+        owner = region[1][:, 0].astype(np.int64)
+        return self._scatter_exact(r['jac'][0][:, None], (owner,), (1.0,), np.zeros((owner.size, 1)))      # blocks of one row each
+
+    def trueKeepInMargins(self, x):
+        """(val[P], t_star[P]): per (vehicle, face) of `keepIn`, in the order of keepInConstraints, the true minimum over the
+        trajectory of b_f - a_f . c_v and the parameter in [0, 1] where it is reached (obtg_keep_in_true_min), whatever
+        `keepInRows` is: the vehicle stays inside iff every one is >= 0."""
+        region = self._bound(_KEEP_IN, 'trueKeepInMargins')
+        r = self._true_rows_at(_KEEP_IN, np.asarray(x, dtype=float), region, 'trueKeepInMargins')
+        return r['val'][0], r['t_star'][0]
 
     # ------------------------------------------------------------------ exact Jacobians (method='exact')
     # The device returns d rows / d Y per pair or vehicle ([..][rows][dim][deg+1] blocks, include/obtg.h obtg_*_jac); the chain

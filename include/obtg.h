@@ -113,7 +113,10 @@ const char* obtg_strerror(int code);
  *      free space curves obtg_bern_space_curvature[_dev] (timed under OBTG_K_ANG_RATE; no kernel id added).
  *      Later, still 7: new: the keep-in region obtg_ctx_set_keep_in, its rows obtg_keep_in[_dev] (obtg_len_keep_in), their true
  *      margins obtg_keep_in_true_min[_dev] and the envelope Jacobian obtg_keep_in_true_min_jac[_dev] (timed under OBTG_K_SPEED;
- *      no kernel id added). */
+ *      no kernel id added).
+ *      Later, still 7: new: the keep-out obstacles obtg_ctx_set_keep_out (obtg_len_keep_out), their true clearances
+ *      obtg_keep_out_true_min[_dev], the envelope Jacobian obtg_keep_out_true_min_jac[_dev] and the clearance of free curves
+ *      obtg_bern_keep_out[_dev] (timed under OBTG_K_SPEED; no kernel id added). */
 #define OBTG_ABI_VERSION 7
 int obtg_abi_version(void);
 
@@ -933,6 +936,69 @@ int obtg_keep_in_true_min_jac(obtg_ctx*, const double* Y, int B, double eps_rel,
                               double* jac /*[B][P][d][n+1]*/);
 int obtg_keep_in_true_min_jac_dev(obtg_ctx*, const double* dY, int B, double eps_rel, int max_nodes, double* d_out, double* d_t_star,
                                   int* d_status, double* d_jac);
+
+/* ---- keep-out obstacles: every listed vehicle stays outside convex obstacles, in 2-D and 3-D ----
+ * An obstacle is a convex set {p : a_f . p <= b_f, f = 1 .. F_o}: a run of rows (a_f[0 .. d-1], b_f) of H[F][d+1], obstacle o
+ * owning rows obs_off[o] .. obs_off[o+1]-1.  a is not normalised (with |a| = 1 the rows are distances).  An item is a (vehicle,
+ * obstacle) pair of the list VO[P][2].  For vehicle v with control points P[c][i] (c < d, i <= n) and obstacle o:
+ *     g_f(t) = a_f . c_v(t) - b_f      Bernstein coefficient i:  a_f . P_i - b_f, formed as fma(a[0], P[0][i], -b), then
+ *                                      fma(a[c], P[c][i], .): the exact negation of obtg_keep_in's coefficient
+ *     G(t)   = max over the obstacle's faces of g_f(t)      (> 0 outside; inside: minus the penetration depth)
+ *     row    = min over t in [0, 1] of G(t)  -  margin      (feasible iff >= 0)
+ * G(t) <= dist(c(t), obstacle) outside -- equal where the nearest feature is a face, smaller near a corner -- so row >= 0
+ * implies a true clearance >= margin: the row is CONSERVATIVE near corners.  G is negative inside, so a start that penetrates
+ * still has a gradient that pushes out.  Neither tf nor a time span enters.
+ * Search (csrc/keepout_kernels.hip), the conventions of obtg_bern_extrema: bisection at 1/2 by de Casteljau on the coordinate
+ * rows; a sub-curve's bound is max_f min_i of its face coefficients, exact values of G at its ends and its mid point;
+ * s = max |g_f,i| of the root, tol = eps_rel s; the incumbent is replaced on strict decrease only, a child is dropped when
+ * incumbent - bound <= tol; depth-first, the smaller bound first; nodes counts sub-curves, the root being 1; OBTG_MD_NODE_CAP
+ * when the next split would pass max_nodes, OBTG_MD_DEPTH_CAP at 32 waiting frames, both with a valid bracket [bound, out].  A
+ * non-finite control point or face: NaN outputs (face -1, nodes 0), status OBTG_MD_OK.  A root that closes: out is an end
+ * value, t_star 0 or 1, nodes 1.
+ * Envelope block.  t* the minimiser, f1 = argmax_f g_f(t*) (the first of equals), values and slopes taken at c(t*), c'(t*):
+ *   an end minimiser (t* 0 or 1) or a smooth interior minimum: one face, jac[c][i] = a_f1[c] B_i^n(t*);
+ *   a kink: a second face f2 is CO-ACTIVE iff  g_f2'(t*) and g_f1'(t*) have opposite signs  and
+ *           g_f1(t*) - g_f2(t*) <= 2 tol (1 + |g_f2'| / |g_f1'|);
+ *       among several the one with the largest g_f(t*); g_f1'(t*) == 0 is a smooth minimum.  (The search's dyadic t* may sit
+ *       tol / |slope| from the kink where the two faces cross; the rule is what G(t*) - min G <= tol leaves.)  Then
+ *           lam1 = g_f2' / (g_f2' - g_f1'), lam2 = 1 - lam1 (both in [0, 1]),
+ *           jac[c][i] = (lam1 a_f1[c] + lam2 a_f2[c]) B_i^n(t*).
+ *   The block is linear in the control points of the item's own vehicle only; the basis comes from the recurrence of the other
+ *   envelope blocks, every multiply-add an explicit fma.  An end minimiser leaves one non-zero column; a NaN row a NaN block.
+ * obtg_ctx_set_keep_out: copies H, obs_off and VO to the context (P = 0 clears the tables).  OBTG_ERR_ARG for a vehicle index
+ *     outside 0 .. N-1, an obstacle index outside 0 .. O-1, a context whose d is not 2 or 3, obs_off[0] != 0, offsets that do not
+ *     ascend (an empty obstacle) or a null table with P > 0; OBTG_ERR_UNSUPPORTED for an obstacle of more than 16 faces.
+ * obtg_len_keep_out: P.
+ * obtg_keep_out_true_min: out[B][P] the rows; nullable: t_star[B][P]; face[B][P][2], indices into H of f1 and f2 (-1: no second
+ *     face); lam[B][P] = lam1 (1 without a second face); bound[B][P], the certified lower bound (the smallest bound dropped)
+ *     minus margin, bound <= true row <= out and out - bound <= tol when status is OBTG_MD_OK; nodes[B][P]; status[B][P].
+ *     Degrees 1 .. 31 (above: OBTG_ERR_UNSUPPORTED), one kernel, one launch.
+ * obtg_keep_out_true_min_jac: the same outputs, bit for bit (the same kernel; the blocks are one more output), plus
+ *     jac[B][P][d][n+1].
+ * obtg_bern_keep_out: the same search on M free curves c[M][dim][K] (dim 2 or 3, 2 <= K <= 32, whatever the context's shape
+ *     is) against ONE obstacle, the F <= 16 faces of H (a host array in the _dev form too), margin 0: val[M], nullable
+ *     t_star[M], status[M].
+ * An item's outputs depend on its control points, its faces, margin, eps_rel and max_nodes alone.  Host and _dev calls give the
+ * same bits.  No tables set, or a context whose d is not 2 or 3: OBTG_ERR_ARG before any launch.  Every launch is timed under
+ * OBTG_K_SPEED.  _dev: dY is device memory [B][N d][n+1]; dY = NULL inside an obtg_fd_view is not built for this family and
+ * answers OBTG_ERR_ARG.  Not part of obtg_constraint_sweep_dev or of the structured step. */
+int obtg_ctx_set_keep_out(obtg_ctx*, const double* H /*[F][d+1]*/, const int* obs_off /*[O+1]*/, int O, const int* VO /*[P][2]*/, int P);
+int obtg_len_keep_out(const obtg_ctx*);     /* P                   */
+int obtg_keep_out_true_min(obtg_ctx*, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out /*[B][P]*/,
+                           double* t_star /*[B][P], nullable*/, int* face /*[B][P][2], nullable*/, double* lam /*[B][P], nullable*/,
+                           double* bound /*[B][P], nullable*/, int* nodes /*[B][P], nullable*/, int* status /*[B][P], nullable*/);
+int obtg_keep_out_true_min_dev(obtg_ctx*, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
+                               double* d_t_star, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status);
+int obtg_keep_out_true_min_jac(obtg_ctx*, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
+                               double* t_star, int* face, double* lam, double* bound, int* nodes, int* status,
+                               double* jac /*[B][P][d][n+1]*/);
+int obtg_keep_out_true_min_jac_dev(obtg_ctx*, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
+                                   double* d_t_star, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status,
+                                   double* d_jac);
+int obtg_bern_keep_out(obtg_ctx*, const double* c /*[M][dim][K]*/, int M, int dim, int K, const double* H /*[F][dim+1]*/, int F,
+                       double eps_rel, int max_nodes, double* val /*[M]*/, double* t_star /*[M], nullable*/, int* status /*[M], nullable*/);
+int obtg_bern_keep_out_dev(obtg_ctx*, const double* d_c, int M, int dim, int K, const double* H, int F, double eps_rel, int max_nodes,
+                           double* d_val, double* d_t_star, int* d_status);
 
 /* ---- the acceleration bound: |d^2 c / dtime^2| <= bound for every vehicle, in 2-D, 3-D and any other dimension ----
  * For vehicle v with control points P[c][i] (c < d, i <= n) on a span T = tf[b]:

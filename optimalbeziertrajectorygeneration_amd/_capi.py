@@ -171,6 +171,14 @@ _SIGNATURES = {
     "obtg_keep_in_true_min_dev": (_i, [_vp, _vp, _i, _d, _i, _vp, _vp, _vp]),
     "obtg_keep_in_true_min_jac": (_i, [_vp, _vp, _i, _d, _i, _vp, _vp, _vp, _vp]),
     "obtg_keep_in_true_min_jac_dev": (_i, [_vp, _vp, _i, _d, _i, _vp, _vp, _vp, _vp]),
+    "obtg_ctx_set_keep_out": (_i, [_vp, _vp, _vp, _i, _vp, _i]),
+    "obtg_len_keep_out": (_i, [_vp]),
+    "obtg_keep_out_true_min": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_keep_out_true_min_dev": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_keep_out_true_min_jac": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_keep_out_true_min_jac_dev": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_bern_keep_out": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _d, _i, _vp, _vp, _vp]),
+    "obtg_bern_keep_out_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _d, _i, _vp, _vp, _vp]),
     "obtg_jerk": (_i, [_vp, _vp, _vp, _i, _d, _vp]),
     "obtg_jerk_dev": (_i, [_vp, _vp, _vp, _i, _d, _vp]),
     "obtg_jerk_true_min": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
@@ -485,6 +493,8 @@ class Context(object):
         self.n_hull_pairs = None      # no hull pair list registered yet
         self.keep_in_items = 0        # (vehicle, face) items of the keep-in region; 0: none set
         self._keep_in_key = None      # the bytes of the tables set_keep_in last sent
+        self.keep_out_items = 0       # (vehicle, obstacle) items of the keep-out tables; 0: none set
+        self._keep_out_key = None     # the bytes of the tables set_keep_out last sent
 
     # -- plumbing
     def close(self):
@@ -800,6 +810,84 @@ class Context(object):
 
     def keep_in_true_min_jac_dev(self, dY, B, d_out, d_jac, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
         self._true_min_dev("obtg_keep_in_true_min_jac_dev", (dY,), B, (), eps_rel, max_nodes, d_out, d_t_star, d_status, d_jac)
+
+    # -- keep-out obstacles (include/obtg.h "keep-out obstacles"): obstacles = (H[F][dim+1], obs_off[O+1], VO[P][2]); every call
+    # below takes them as its optional `obstacles` operand -- sent to the context only when their bytes differ from what the
+    # context holds -- or, with None, works on the tables set_keep_out left there
+    def set_keep_out(self, H, obs_off, VO):
+        """obtg_ctx_set_keep_out: the faces a . p <= b of every obstacle as rows (a, b) of H, obstacle o owning rows
+        obs_off[o] .. obs_off[o+1]-1, and the (vehicle, obstacle) items VO; an empty VO clears the tables."""
+        VO = _i32(VO).reshape(-1, 2)
+        H = _f64(H).reshape(-1, self.dim + 1)
+        obs_off = _i32(obs_off).reshape(-1)
+        self._check(self._lib.obtg_ctx_set_keep_out(self._h, _ptr(H), _ptr(obs_off), max(obs_off.shape[0] - 1, 0), _ptr(VO),
+                                                    VO.shape[0]), "obtg_ctx_set_keep_out")
+        self.keep_out_items = VO.shape[0]
+        self._keep_out_key = (H.tobytes(), obs_off.tobytes(), VO.tobytes())
+
+    def _keep_out(self, obstacles):
+        if obstacles is not None:
+            H, off, VO = _f64(obstacles[0]), _i32(obstacles[1]), _i32(obstacles[2])
+            if self._keep_out_key != (H.tobytes(), off.tobytes(), VO.tobytes()):
+                self.set_keep_out(H, off, VO)
+        return self.keep_out_items         # (0: no tables -- the library's call answers OBTG_ERR_ARG)
+
+    @property
+    def len_keep_out(self):
+        return self._lib.obtg_len_keep_out(self._h)
+
+    def _keep_out_call(self, name, Y, obstacles, margin, eps_rel, max_nodes, jac):
+        P = self._keep_out(obstacles)
+        Y, B = self._rows(Y)
+        r = dict(val=pinned_empty((B, P)), t_star=np.empty((B, P)), face=np.zeros((B, P, 2), np.int32), lam=np.empty((B, P)),
+                 bound=np.empty((B, P)), nodes=np.zeros((B, P), np.int32), status=np.zeros((B, P), np.int32))
+        if jac:
+            r["jac"] = pinned_empty((B, P, self.dim, self.deg + 1))
+        self._check(getattr(self._lib, name)(self._h, _ptr(Y), B, float(margin), float(eps_rel), int(max_nodes),
+                                             *[_ptr(a) for a in r.values()]), name)
+        return r
+
+    def keep_out_true_min(self, Y, obstacles=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
+        """Per (vehicle, obstacle) item the clearance row: the minimum over t in [0, 1] of the largest a_f . c_v(t) - b_f over
+        the obstacle's faces, minus margin (obtg_keep_out_true_min): dict(val[B][P], t_star[B][P], face[B][P][2] -- the
+        active faces as indices into H, the second -1 without one --, lam[B][P] -- the first face's weight --, bound[B][P] --
+        the certified lower bound --, nodes[B][P], status[B][P])."""
+        return self._keep_out_call("obtg_keep_out_true_min", Y, obstacles, margin, eps_rel, max_nodes, False)
+
+    def keep_out_true_min_jac(self, Y, obstacles=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
+        """keep_out_true_min with its envelope Jacobian (obtg_keep_out_true_min_jac): the same dict, bit for bit, and
+        jac[B][P][dim][deg+1] = (lam a_f1[c] + (1 - lam) a_f2[c]) B_i(t_star): d/d(the item's own vehicle's control points)."""
+        return self._keep_out_call("obtg_keep_out_true_min_jac", Y, obstacles, margin, eps_rel, max_nodes, True)
+
+    def keep_out_true_min_dev(self, dY, B, d_out, d_t_star=None, d_face=None, d_lam=None, d_bound=None, d_nodes=None, d_status=None,
+                              margin=0.0, eps_rel=1e-9, max_nodes=100000):
+        self._check(self._lib.obtg_keep_out_true_min_dev(self._h, _vp(dY), int(B), float(margin), float(eps_rel), int(max_nodes),
+                                                         *[_vp(q) for q in (d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status)]),
+                    "obtg_keep_out_true_min_dev")
+
+    def keep_out_true_min_jac_dev(self, dY, B, d_out, d_jac, d_t_star=None, d_face=None, d_lam=None, d_bound=None, d_nodes=None,
+                                  d_status=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
+        self._check(self._lib.obtg_keep_out_true_min_jac_dev(self._h, _vp(dY), int(B), float(margin), float(eps_rel), int(max_nodes),
+                                                             *[_vp(q) for q in (d_out, d_t_star, d_face, d_lam, d_bound, d_nodes,
+                                                                                d_status, d_jac)]), "obtg_keep_out_true_min_jac_dev")
+
+    def bern_keep_out(self, c, H, eps_rel=1e-9, max_nodes=100000):
+        """The clearance of free curves c[M][dim][K] (dim 2 or 3, 2 <= K <= 32, whatever the context's shape is) from ONE
+        convex obstacle, the faces H[F][dim+1] (obtg_bern_keep_out): dict(val[M], t_star[M], status[M])."""
+        c = _f64(c)
+        if c.ndim == 2:
+            c = c[None]
+        M, dim, K = c.shape
+        H = _f64(H).reshape(-1, dim + 1)
+        r = dict(val=np.empty(M), t_star=np.empty(M), status=np.zeros(M, np.int32))
+        self._check(self._lib.obtg_bern_keep_out(self._h, _ptr(c), M, dim, K, _ptr(H), H.shape[0], float(eps_rel), int(max_nodes),
+                                                 *[_ptr(a) for a in r.values()]), "obtg_bern_keep_out")
+        return r
+
+    def bern_keep_out_dev(self, d_c, M, dim, K, H, d_val, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
+        H = _f64(H).reshape(-1, int(dim) + 1)
+        self._check(self._lib.obtg_bern_keep_out_dev(self._h, _vp(d_c), int(M), int(dim), int(K), _ptr(H), H.shape[0], float(eps_rel),
+                                                     int(max_nodes), _vp(d_val), _vp(d_t_star), _vp(d_status)), "obtg_bern_keep_out_dev")
 
     def jerk(self, Y, tf, bound):
         """The jerk-bound rows (obtg_jerk): [B][N * (2 deg + DEG_ELEV + 1)] control points of

@@ -280,6 +280,22 @@ class Bezier(BezierParams):
             _raise_md(st, 'keepInMargins')
         return r['val'][0].copy(), r['t_star'][0].copy()
 
+    def keepOutClearance(self, A, b, eps=1e-12, max_nodes=100000):
+        """(clearance, t): the minimum over the curve of G(t) = max_f (a_f . c(t) - b_f) for the convex obstacle A p <= b
+        (A[F][dim], b[F], dim 2 or 3, F <= 16) and the parameter in [0, 1] where it is reached (obtg_bern_keep_out, the search
+        behind BezOptimization.keepOutConstraints).  Positive: the curve stays outside, and with |a_f| = 1 its true distance to
+        the obstacle is at least the clearance (equal where the nearest feature is a face, larger near a corner); negative:
+        minus the deepest penetration.  It depends on neither t0 nor tf.  Not in the reference."""
+        if self.dim not in (2, 3):
+            raise ValueError('The input curve must be two or three dimensional,\n'
+                             'instead it is {} dimensional'.format(self.dim))
+        A, b = np.asarray(A, dtype=np.float64), np.asarray(b, dtype=np.float64)
+        if A.ndim != 2 or A.shape[0] < 1 or A.shape[1] != self.dim or b.shape != (A.shape[0],):
+            raise ValueError('keepOutClearance needs A[F][{}] and b[F], F >= 1, not shapes {} and {}'.format(self.dim, A.shape, b.shape))
+        r = _ctx().bern_keep_out(self.cpts, np.hstack((A, b[:, None])), eps_rel=float(eps), max_nodes=int(max_nodes))
+        _raise_md(r['status'][0], 'keepOutClearance')
+        return float(r['val'][0]), float(r['t_star'][0])
+
     def split(self, tDiv):
         """Two curves, before and after tDiv (bezier.py:533-572): de Casteljau at (tDiv - t0)/(tf - t0); the
         pieces keep the original span's ends, [t0, tDiv] and [tDiv, tf]."""
@@ -397,6 +413,32 @@ class Bezier(BezierParams):
         r = _ctx().coll_check2poly(self._padded()[None], poly, [0, poly.shape[0]], [0], [0], max_nodes=max_nodes)
         _raise_md(r['status'][0], 'collCheck2Poly')
         return int(r['res'][0])
+
+
+def halfspacesOfPolygon(vertices):
+    """(A[F][2], b[F]) with unit outward normals: the convex polygon with the given vertices, in order, in either orientation,
+    as the half-planes a_f . p <= b_f -- face f through vertices f and f + 1 -- that BezOptimization(keepOut=...),
+    Bezier.keepOutClearance and keepIn take.  ValueError for fewer than 3 vertices, a repeated vertex or an order that is not
+    convex (collinear neighbours included).  Host arithmetic only: no device is touched."""
+    V = np.asarray(vertices, dtype=np.float64)
+    if V.ndim != 2 or V.shape[1] != 2 or V.shape[0] < 3:
+        raise ValueError('halfspacesOfPolygon needs at least 3 vertices [n][2], not shape {}'.format(V.shape))
+    n = V.shape[0]
+    for i in range(n):
+        for j in range(i + 1, n):
+            if np.array_equal(V[i], V[j]):
+                raise ValueError('halfspacesOfPolygon: vertices {} and {} are the same point'.format(i, j))
+    E = np.roll(V, -1, axis=0) - V                      # edge f: vertex f -> vertex f + 1
+    E2 = np.roll(E, -1, axis=0)
+    turn = E[:, 0] * E2[:, 1] - E[:, 1] * E2[:, 0]
+    if not (np.all(turn > 0.0) or np.all(turn < 0.0)):
+        raise ValueError('halfspacesOfPolygon: the vertices are not in a convex order')
+    if abs(np.sum(np.arctan2(turn, np.sum(E * E2, axis=1)))) > 2.0 * np.pi + 1e-6:
+        raise ValueError('halfspacesOfPolygon: the vertices are not in a convex order')      # (winds more than once)
+    sgn = 1.0 if turn[0] > 0.0 else -1.0                # counter-clockwise: the outward normal is the edge turned by -90 degrees
+    A = sgn * np.stack((E[:, 1], -E[:, 0]), axis=1)
+    A /= np.hypot(A[:, 0], A[:, 1])[:, None]
+    return A, np.sum(A * V, axis=1)
 
 
 def elevated_stack(curves):

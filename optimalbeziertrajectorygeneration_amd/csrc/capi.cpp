@@ -256,6 +256,7 @@ const char* obtg_abi_symbols(void)
         "obtg_curvature_poly\0obtg_curvature_poly_dev\0obtg_curvature_true_min\0obtg_curvature_true_min_dev\0obtg_curvature_true_min_jac\0obtg_curvature_true_min_jac_dev\0obtg_bern_curvature\0obtg_bern_curvature_dev\0"
         "obtg_space_curvature_poly\0obtg_space_curvature_poly_dev\0obtg_space_curvature_true_min\0obtg_space_curvature_true_min_dev\0obtg_space_curvature_true_min_jac\0obtg_space_curvature_true_min_jac_dev\0obtg_bern_space_curvature\0obtg_bern_space_curvature_dev\0"
         "obtg_ctx_set_keep_in\0obtg_len_keep_in\0obtg_keep_in\0obtg_keep_in_dev\0obtg_keep_in_true_min\0obtg_keep_in_true_min_dev\0obtg_keep_in_true_min_jac\0obtg_keep_in_true_min_jac_dev\0"
+        "obtg_ctx_set_keep_out\0obtg_len_keep_out\0obtg_keep_out_true_min\0obtg_keep_out_true_min_dev\0obtg_keep_out_true_min_jac\0obtg_keep_out_true_min_jac_dev\0obtg_bern_keep_out\0obtg_bern_keep_out_dev\0"
         "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_restrict\0obtg_bern_eval\0"
         "obtg_euclidean_obj\0obtg_accel_obj\0obtg_jerk_obj\0"
         "obtg_bern_arc_length\0obtg_bern_arc_length_dev\0obtg_arc_length_obj\0obtg_arc_length_obj_dev\0"
@@ -324,7 +325,7 @@ void obtg_ctx_destroy(obtg_ctx* c)
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
     DevBuf* bufs[] = { &c->d_pairs, &c->d_obs, &c->d_w2, &c->d_Tt, &c->d_Td, &c->d_Tf, &c->d_ang_dd, &c->d_ang_flags, &c->d_vp_off, &c->d_vp_idx, &c->d_ang_w2n, &c->d_ang_w22n, &c->d_ang_wn, &c->d_ang_rows, &c->d_curv_tab, &c->d_ang_T4, &c->d_ang_cv2, &c->d_jac,
                        &c->d_binrows, &c->d_tiles, &c->d_poly_pts, &c->d_poly_off, &c->d_hp_a, &c->d_hp_b, &c->d_tile_chunk_off, &c->d_tile_order, &c->d_tile_pslots,
-                       &c->d_tile_cobj_off, &c->d_tile_cobjs, &c->d_tile_ij, &c->d_struct_tickets, &c->d_keep_H, &c->d_keep_VF, &c->ws_in,
+                       &c->d_tile_cobj_off, &c->d_tile_cobjs, &c->d_tile_ij, &c->d_struct_tickets, &c->d_keep_H, &c->d_keep_VF, &c->d_ko_H, &c->d_ko_off, &c->d_ko_VO, &c->ws_in,
                        &c->ws_in2, &c->ws_out, &c->ws_fd };
     for (DevBuf* b : bufs) b->release();
     for (auto& b : c->ws_misc) b.release();
@@ -2106,6 +2107,159 @@ int obtg_keep_in_true_min_jac(obtg_ctx* c, const double* Y, int B, double eps_re
                               int* status, double* jac)
 {
     return keep_in_true_min(c, Y, B, eps_rel, max_nodes, out, t_star, status, true, jac);
+}
+
+// The keep-out rows (keepout_kernels.hip): items are (vehicle, obstacle) pairs of the tables obtg_ctx_set_keep_out left on the
+// context; an obstacle is a run of faces of H.  The search is a kernel of its own (a minimum over t of a maximum over faces),
+// not a RowFamily: there is no polynomial row to write.  Refusals as keep-in's, all before any launch; more than 16 faces in an
+// obstacle or a degree above 31 is OBTG_ERR_UNSUPPORTED.  The _dev calls take dY itself (dY == NULL: OBTG_ERR_ARG).
+constexpr int kKeepOutMaxFaces = 16;
+
+int obtg_ctx_set_keep_out(obtg_ctx* c, const double* H, const int* obs_off, int O, const int* VO, int P)
+{
+    if (!check_ctx(c) || O < 0 || P < 0) return OBTG_ERR_ARG;
+    int F = 0;
+    if (P > 0) {
+        if ((c->dim != 2 && c->dim != 3) || O < 1 || !H || !obs_off || !VO || obs_off[0] != 0) return OBTG_ERR_ARG;
+        for (int o = 0; o < O; ++o)
+            if (obs_off[o + 1] <= obs_off[o]) return OBTG_ERR_ARG;           // (an empty obstacle, offsets that do not ascend)
+        for (int k = 0; k < P; ++k)
+            if (VO[2 * k] < 0 || VO[2 * k] >= c->n_veh || VO[2 * k + 1] < 0 || VO[2 * k + 1] >= O) return OBTG_ERR_ARG;
+        for (int o = 0; o < O; ++o)
+            if (obs_off[o + 1] - obs_off[o] > kKeepOutMaxFaces) return OBTG_ERR_UNSUPPORTED;
+        F = obs_off[O];
+    }
+    (void)hipSetDevice(c->device);
+    OBTG_HIP(c, hipStreamSynchronize(c->stream));
+    c->ko_F = c->ko_O = c->ko_P = 0;       // (set again once the tables are on the device)
+    if (P == 0) return OBTG_OK;
+    int rc = upload(c, c->d_ko_H, H, sizeof(double) * (size_t)F * (c->dim + 1));
+    if (!rc) rc = upload(c, c->d_ko_off, obs_off, sizeof(int) * ((size_t)O + 1));
+    if (!rc) rc = upload(c, c->d_ko_VO, VO, sizeof(int) * 2 * (size_t)P);
+    if (rc) return rc;
+    c->ko_F = F; c->ko_O = O; c->ko_P = P;
+    return OBTG_OK;
+}
+
+int obtg_len_keep_out(const obtg_ctx* c) { return c ? c->ko_P : 0; }
+
+static int keep_out_args(const obtg_ctx* c, const double* out, int B, int max_nodes, double eps_rel, double margin)
+{
+    if (!check_ctx(c) || c->ko_P <= 0 || (c->dim != 2 && c->dim != 3) || !out || B < 0 || max_nodes < 1 || !(eps_rel >= 0.0) ||
+        margin != margin)
+        return OBTG_ERR_ARG;
+    return c->deg > 31 ? OBTG_ERR_UNSUPPORTED : OBTG_OK;
+}
+
+static int keep_out_launch(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
+                           double* d_t, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status, double* d_jac)
+{
+    return launch_keep_out(c, c->dim, c->deg + 1, dY, (long)B * c->ko_P, c->n_veh, c->ko_P, c->d_ko_H.as<double>(),
+                           c->d_ko_off.as<int>(), c->d_ko_VO.as<int>(), 0, margin, eps_rel, max_nodes, d_out, d_t, d_face, d_lam,
+                           d_bound, d_nodes, d_status, d_jac, OBTG_K_SPEED);
+}
+
+// want_jac: the _jac entry points, where the blocks are not optional
+static int keep_out_true_min_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
+                                 double* d_t, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status, bool want_jac,
+                                 double* d_jac)
+{
+    if (int rc = keep_out_args(c, d_out, B, max_nodes, eps_rel, margin)) return rc;
+    if (!dY || (want_jac && !d_jac)) return OBTG_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    return keep_out_launch(c, dY, B, margin, eps_rel, max_nodes, d_out, d_t, d_face, d_lam, d_bound, d_nodes, d_status, d_jac);
+}
+
+// the host body: Y up; val | t_star | lam | bound | jac in ws_out, face | nodes | status in WS_STATUS
+static int keep_out_true_min(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
+                             double* t_star, int* face, double* lam, double* bound, int* nodes, int* status, bool want_jac, double* jac)
+{
+    if (int rc = keep_out_args(c, out, B, max_nodes, eps_rel, margin)) return rc;
+    if (!Y || (want_jac && !jac)) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    const size_t n = (size_t)B * c->ko_P, nj = jac ? n * c->dim * (c->deg + 1) : 0;
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    double* dv = h.out<double>(c->ws_out, 4 * n + nj);
+    int* di = h.out<int>(c->ws_misc[WS_STATUS], 4 * n);
+    double* dj = jac ? dv + 4 * n : nullptr;
+    h.run([&] { return keep_out_launch(c, dY, B, margin, eps_rel, max_nodes, dv, dv + n, di, dv + 2 * n, dv + 3 * n, di + 2 * n,
+                                       di + 3 * n, dj); });
+    h.fetch(t_star, dv + n, n);
+    h.fetch(lam, dv + 2 * n, n);
+    h.fetch(bound, dv + 3 * n, n);
+    h.fetch(face, di, 2 * n);
+    h.fetch(nodes, di + 2 * n, n);
+    h.fetch(status, di + 3 * n, n);
+    h.fetch(jac, dj, nj);
+    return h.finish(out, dv, n);
+}
+
+int obtg_keep_out_true_min_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
+                               double* d_t_star, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status)
+{
+    return keep_out_true_min_dev(c, dY, B, margin, eps_rel, max_nodes, d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, false,
+                                 nullptr);
+}
+
+int obtg_keep_out_true_min(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out, double* t_star,
+                           int* face, double* lam, double* bound, int* nodes, int* status)
+{
+    return keep_out_true_min(c, Y, B, margin, eps_rel, max_nodes, out, t_star, face, lam, bound, nodes, status, false, nullptr);
+}
+
+int obtg_keep_out_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
+                                   double* d_t_star, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status,
+                                   double* d_jac)
+{
+    return keep_out_true_min_dev(c, dY, B, margin, eps_rel, max_nodes, d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, true,
+                                 d_jac);
+}
+
+int obtg_keep_out_true_min_jac(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
+                               double* t_star, int* face, double* lam, double* bound, int* nodes, int* status, double* jac)
+{
+    return keep_out_true_min(c, Y, B, margin, eps_rel, max_nodes, out, t_star, face, lam, bound, nodes, status, true, jac);
+}
+
+// Free curves cv[M][dim][K] against ONE face table H[F][dim+1] (a host array in both forms), whatever the context's shape is:
+// the same kernel, one obstacle of all F faces, margin 0.  The context's own keep-out tables are not touched.
+static int bern_keep_out_args(const obtg_ctx* c, const double* cv, int M, int dim, int K, const double* H, int F, double eps_rel,
+                              int max_nodes, const double* val)
+{
+    if (!check_ctx(c) || M < 0 || (dim != 2 && dim != 3) || K < 2 || F < 1 || !H || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
+    if (K > kMdMaxCurveK || F > kKeepOutMaxFaces) return OBTG_ERR_UNSUPPORTED;
+    if (M == 0) return kNothingToDo;
+    return cv && val ? OBTG_OK : OBTG_ERR_ARG;
+}
+
+int obtg_bern_keep_out_dev(obtg_ctx* c, const double* d_c, int M, int dim, int K, const double* H, int F, double eps_rel, int max_nodes,
+                           double* d_val, double* d_t_star, int* d_status)
+{
+    if (int chk = bern_keep_out_args(c, d_c, M, dim, K, H, F, eps_rel, max_nodes, d_val)) return done(chk);
+    (void)hipSetDevice(c->device);
+    DevBuf& dH = c->ws_misc[WS_ARG_A];
+    if (int rc = upload(c, dH, H, sizeof(double) * (size_t)F * (dim + 1))) return rc;
+    return launch_keep_out(c, dim, K, d_c, M, 1, 1, dH.as<double>(), nullptr, nullptr, F, 0.0, eps_rel, max_nodes, d_val, d_t_star,
+                           nullptr, nullptr, nullptr, nullptr, d_status, nullptr, OBTG_K_SPEED);
+}
+
+int obtg_bern_keep_out(obtg_ctx* c, const double* cv, int M, int dim, int K, const double* H, int F, double eps_rel, int max_nodes,
+                       double* val, double* t_star, int* status)
+{
+    if (int chk = bern_keep_out_args(c, cv, M, dim, K, H, F, eps_rel, max_nodes, val)) return done(chk);
+    const size_t n = (size_t)M;
+    HostCall h(c);
+    DevBuf& dH = c->ws_misc[WS_ARG_A];
+    if (int rc = upload(c, dH, H, sizeof(double) * (size_t)F * (dim + 1))) return rc;
+    const double* d_c = h.in(c->ws_in, cv, n * dim * K);
+    double* dv = h.out<double>(c->ws_out, 2 * n);
+    int* ds = h.out<int>(c->ws_misc[WS_STATUS], n);
+    h.run([&] { return launch_keep_out(c, dim, K, d_c, M, 1, 1, dH.as<double>(), nullptr, nullptr, F, 0.0, eps_rel, max_nodes, dv, dv + n,
+                                       nullptr, nullptr, nullptr, nullptr, ds, nullptr, OBTG_K_SPEED); });
+    h.fetch(t_star, dv + n, n);
+    h.fetch(status, ds, n);
+    return h.finish(val, dv, n);
 }
 
 // Free curves c[M][dim][K], any K from 2 to 32 whatever the context's shape is: the family's rows kernel and workspace search

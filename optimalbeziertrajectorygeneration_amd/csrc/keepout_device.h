@@ -1,0 +1,112 @@
+// Device functions of the keep-out rows (keepout_kernels.hip; include/obtg.h "keep-out obstacles"): a curve against a convex
+// obstacle {p : a_f . p <= b_f}.  Per face f the polynomial g_f(t) = a_f . c(t) - b_f has the curve's own degree; the row is
+//     min over t in [0, 1] of G(t),  G(t) = max over the obstacle's faces of g_f(t)      (> 0 outside, minus the depth inside).
+// Every multiply-add below is an explicit fma and every other product stands alone: the same bits whatever contraction the
+// including unit is compiled under.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <cmath>
+
+namespace obtg {
+
+constexpr int kKoMaxFaces = 16;      // faces per obstacle (above: OBTG_ERR_UNSUPPORTED)
+constexpr int kKoMaxK = 32;          // control points per curve: a child of a split is half a wavefront
+constexpr int kKoStack = 32;         // sub-curves waiting per item; one more: OBTG_MD_DEPTH_CAP
+constexpr int kKoWaves = 2;          // waves (items) per workgroup
+
+__device__ __forceinline__ void ko_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ double ko_lane(double v, int src)      // src wave-uniform
+{
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src), hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
+    return __hiloint2double(hi, lo);
+}
+// Smallest value of each 32-lane half, in every lane of the half.  (A DPP form -- quad_perm, row_half_mirror, row_mirror,
+// row_bcast15 -- was measured 12 % SLOWER on C3's batch: the kernel is bound by issue, not by this chain's latency, and the
+// register moves cost more issue slots than the five cross-lane reads.  DESIGN.md 4.24.)
+__device__ __forceinline__ double ko_half_min(double v)
+{
+#pragma unroll
+    for (int o = 16; o; o >>= 1) v = fmin(v, __shfl_xor(v, o));
+    return v;
+}
+constexpr int kKoLowLast = 0, kKoHighLast = 32;       // a lane of either half to read its minimum from
+__device__ __forceinline__ double ko_wave_max(double v)
+{
+#pragma unroll
+    for (int o = 32; o; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+
+// Coefficient of g_f at the control point p: a . p - b for the face h = (a[0 .. DIM-1], b), summed in coordinate order --
+// fma(a[0], p[0], -b), then fma(a[c], p[c], .): operand for operand the negation of keep_in_coeff (bern_device.h), so the
+// bits are its bits with the sign flipped.
+template <int DIM>
+__device__ __forceinline__ double keep_out_coeff(const double* __restrict__ h, const double (&p)[DIM])
+{
+    double g = __builtin_fma(h[0], p[0], -h[DIM]);
+#pragma unroll
+    for (int c = 1; c < DIM; ++c) g = __builtin_fma(h[c], p[c], g);
+    return g;
+}
+
+// Slope of g_f along the direction d (the curve's derivative): a . d, in coordinate order.
+template <int DIM>
+__device__ __forceinline__ double keep_out_slope(const double* __restrict__ h, const double (&d)[DIM])
+{
+    double s = h[0] * d[0];
+#pragma unroll
+    for (int c = 1; c < DIM; ++c) s = __builtin_fma(h[c], d[c], s);
+    return s;
+}
+
+// Which faces carry the envelope block at the minimiser t* (0 < t* < 1), from every face's value g[f] and slope dg[f] there
+// (pt = c(t*), dir = c'(t*)).  f1 = argmax g (the first of equals).  The co-activity rule: a face f != f1 is co-active iff
+//     dg[f] and dg[f1] have opposite signs   and   g[f1] - g[f] <= 2 tol (1 + |dg[f]| / |dg[f1]|);
+// among several the one with the largest g[f] (the first of equals) is f2.  dg[f1] == 0: a smooth minimum, no f2.  The bound
+// is what G(t*) - min G <= tol leaves: the dyadic t* may sit tol / |slope| from the kink where the two faces cross.
+//     lam1 = dg[f2] / (dg[f2] - dg[f1]),  lam2 = 1 - lam1          (both in [0, 1]; lam1 = 1 and f2 = -1 without a second face)
+struct KoActive {
+    int f1, f2;
+    double lam1;
+};
+template <int DIM>
+__device__ __forceinline__ KoActive keep_out_active(const double* __restrict__ hf, const int F, const double (&pt)[DIM],
+                                                    const double (&dir)[DIM], const double tol, const bool interior)
+{
+    KoActive a;
+    a.f1 = 0; a.f2 = -1; a.lam1 = 1.0;
+    double g1 = keep_out_coeff<DIM>(hf, pt);
+    for (int f = 1; f < F; ++f) {
+        const double g = keep_out_coeff<DIM>(hf + f * (DIM + 1), pt);
+        if (g > g1) { g1 = g; a.f1 = f; }
+    }
+    const double s1 = keep_out_slope<DIM>(hf + a.f1 * (DIM + 1), dir);
+    if (!interior || s1 == 0.0) return a;
+    double g2 = -INFINITY, s2 = 0.0;
+    for (int f = 0; f < F; ++f) {
+        if (f == a.f1) continue;
+        const double* h = hf + f * (DIM + 1);
+        const double g = keep_out_coeff<DIM>(h, pt), s = keep_out_slope<DIM>(h, dir);
+        const bool opposite = (s > 0.0 && s1 < 0.0) || (s < 0.0 && s1 > 0.0);
+        if (opposite && g1 - g <= 2.0 * tol * (1.0 + fabs(s) / fabs(s1)) && g > g2) { g2 = g; s2 = s; a.f2 = f; }
+    }
+    if (a.f2 >= 0) a.lam1 = s2 / (s2 - s1);
+    return a;
+}
+
+// One level of the de Casteljau recurrence on the Bernstein basis held a lane per index (lane i: B_i), the arithmetic of
+// envelope_block / keep_in_envelope_block (bern_device.h):  w[i] = fma(t, w[i-1], s w[i]) for i >= 1,  w[0] = s w[0].
+// prev: lane i - 1's value (anything in lane 0).
+__device__ __forceinline__ double keep_out_basis_level(const int lane, const double w, const double prev, const double t, const double s)
+{
+    return lane == 0 ? s * w : __builtin_fma(t, prev, s * w);
+}
+
+}  // namespace obtg

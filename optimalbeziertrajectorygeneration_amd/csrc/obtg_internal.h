@@ -167,6 +167,12 @@ struct obtg_ctx {
     obtg::DevBuf d_keep_H;    // double[keep_F][dim + 1]: (a, b) of a . p <= b
     obtg::DevBuf d_keep_VF;   // int2[keep_P]
     int keep_F = 0, keep_P = 0;
+    // obtg_ctx_set_keep_out: the obstacles' faces, the face ranges of the obstacles and the (vehicle, obstacle) items of the
+    // keep-out rows; ko_P == 0: none set
+    obtg::DevBuf d_ko_H;      // double[ko_F][dim + 1]: (a, b) of a . p <= b
+    obtg::DevBuf d_ko_off;    // int[ko_O + 1]
+    obtg::DevBuf d_ko_VO;     // int2[ko_P]
+    int ko_F = 0, ko_O = 0, ko_P = 0;
     std::vector<int> h_pairs; // host copy of the pair table (2 ints per pair)
     std::vector<int> h_tiles; // row-window tiles of the current (pair_begin, pair_count)
     obtg::DevBuf d_tiles;
@@ -424,6 +430,13 @@ RowFamily ang_row_family(const obtg_ctx* c, const double* d_tf, double max_rate)
 // coefficients elevated once per row (R = 0: the family's rows_r0), degree up to 31
 RowFamily keep_in_row_family(const obtg_ctx* c);                                                      // bern_kernels.hip
 int launch_keep_in_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, int R, double* d_out);
+// The keep-out rows (keepout_kernels.hip): min over t of the max over an obstacle's faces of a_f . c(t) - b_f, per item -- a
+// (batch row, vehicle, obstacle) of the tables d_VO / d_off, or (d_VO null) free curve m of dY[M][dim][K] against faces
+// 0 .. F_all - 1 of d_H.  dim 2 or 3, 2 <= K <= 32, at most 16 faces per obstacle (the callers check the faces).  Every output
+// but d_val is nullable; d_jac null: no blocks -- the other outputs are the same bits either way.
+int launch_keep_out(obtg_ctx* c, int dim, int K, const double* dY, long M, int n_veh, int P, const double* d_H, const int* d_off,
+                    const int* d_VO, int F_all, double margin, double eps_rel, int max_nodes, double* d_val, double* d_t, int* d_face,
+                    double* d_lam, double* d_bound, int* d_nodes, int* d_status, double* d_jac, int kernel_id);
 // the angular-rate family's polynomials [B][n_veh][2][2 deg + 1] (obtg_ang_rate_poly; its rows_r0): dim 2, degree 1 .. 31
 int launch_ang_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);
 // The two curvature families, kind = ROWS_CURV (dim 2; two items, the sides, per vehicle; workspace rows num, den) or ROWS_SCURV

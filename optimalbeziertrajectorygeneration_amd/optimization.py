@@ -264,6 +264,43 @@ def _keep_in_tables(keepIn, numVeh, dim):
     VF = np.stack((np.repeat(np.arange(numVeh), F), np.tile(np.arange(F), numVeh)), axis=1)
     return np.ascontiguousarray(H), np.ascontiguousarray(VF, dtype=np.int32)
 
+# The keep-out family, beside the table as _KEEP_IN is and for the same reason: its operand is the list
+# `keepOut` kept on the object.  True rows only, like curvature (no rows option, no `rows` method): one row per (vehicle,
+# obstacle), the least of max_f (a_f . c_v - b_f) over the trajectory minus `keepOutMargin`.  What the device calls take in the
+# bound's place is the triple of tables _keep_out_tables makes of it; the margin goes beside it (_vehicle_true_min).
+_KEEP_OUT = _RowFamily('keepout', 'keepOut', True, None, None, 'keep_out_true_min', 'keep_out_true_min_jac', None, (),
+                       False, 1, 'keepOutConstraints', 'keepOutJacobian', 'keep-out', False)
+_FAMILY[_KEEP_OUT.key] = _KEEP_OUT
+_KEEP_OUT_MAX_FACES = 16
+
+
+def _keep_out_tables(keepOut, numVeh, dim):
+    """(H[F][dim+1], obs_off[O+1], VO[P][2]) of a `keepOut` argument, checked: a LIST of pairs (A[F_o][dim], b[F_o]), the convex
+    obstacles A p <= b, every vehicle against every obstacle -- items vehicle-major with the obstacles in order, N * O rows
+    (obtg_ctx_set_keep_out)."""
+    if dim not in (2, 3):
+        raise ValueError("keepOut needs dimension 2 or 3, not {}".format(dim))
+    if not isinstance(keepOut, (list, tuple)) or len(keepOut) < 1:
+        raise ValueError("keepOut must be a list of pairs (A[F][{}], b[F]), one per obstacle".format(dim))
+    tables = []
+    for o, pair in enumerate(keepOut):
+        try:
+            A, b = pair
+            A, b = np.asarray(A, dtype=float), np.asarray(b, dtype=float)
+        except (TypeError, ValueError):
+            raise ValueError("keepOut[{}] must be a pair (A[F][{}], b[F])".format(o, dim))
+        if A.ndim != 2 or A.shape[0] < 1 or A.shape[1] != dim or b.shape != (A.shape[0],):
+            raise ValueError("keepOut[{}] must be a pair (A[F][{}], b[F]) with F >= 1, not shapes {} and {}"
+                             .format(o, dim, A.shape, b.shape))
+        if A.shape[0] > _KEEP_OUT_MAX_FACES:
+            raise ValueError("keepOut[{}] has {} faces: an obstacle may have at most {}".format(o, A.shape[0], _KEEP_OUT_MAX_FACES))
+        tables.append(np.hstack((A, b[:, None])))
+    O = len(tables)
+    off = np.cumsum([0] + [Ho.shape[0] for Ho in tables])
+    VO = np.stack((np.repeat(np.arange(numVeh), O), np.tile(np.arange(O), numVeh)), axis=1)
+    return (np.ascontiguousarray(np.vstack(tables)), np.ascontiguousarray(off, dtype=np.int32),
+            np.ascontiguousarray(VO, dtype=np.int32))
+
 # The goals with a device call ('timeopt' is x[-1]).  goal, lower case: (key in _serve / _fd_values; values [B] of the rows Y;
 # gradient blocks [B][N d][n+1] of the rows Y), both called (bezopt, ctx, Y, what) -- `what` names the caller where a search
 # that does not end raises (the arc length alone).
@@ -409,7 +446,9 @@ class BezOptimization(object):
                  maxCurvature=None,
                  maxSpaceCurvature=None,
                  keepIn=None,
-                 keepInRows='all'):
+                 keepInRows='all',
+                 keepOut=None,
+                 keepOutMargin=0.0):
         """Beyond the reference's keywords: `device` (HIP ordinal; None: this process's, see _capi.default_device) and `separationRows` --
         'all': temporalSeparationConstraints returns every elevated control point of every pair, as the
         reference does (optimization.py:337); 'min': one row per pair, the smallest of them -- the
@@ -459,6 +498,17 @@ class BezOptimization(object):
         if keepIn is not None:
             _keep_in_tables(keepIn, numVeh, dimension)      # raises for a region the device calls could not take
         self.keepIn = keepIn
+        # keepOut (None: no obstacles; dim 2 or 3): stay outside -- a list of pairs (A[F][d], b[F]), the convex obstacles
+        # A p <= b (bezier.halfspacesOfPolygon makes one of a polygon's vertices), every vehicle against every obstacle --
+        # keepOutConstraints: N * O true rows, vehicle-major, min over the trajectory of max_f (a_f . c_v - b_f) minus
+        # keepOutMargin (obtg_keep_out_true_min).  With unit normals a row >= 0 implies a true clearance >= keepOutMargin; the
+        # row is conservative near corners and negative (minus the depth) inside.  Kept as `self.keepOut`, like keepIn.
+        if keepOut is not None:
+            _keep_out_tables(keepOut, numVeh, dimension)     # raises for obstacles the device calls could not take
+            if not np.isfinite(float(keepOutMargin)):
+                raise ValueError("keepOutMargin must be finite, not {!r}".format(keepOutMargin))
+        self.keepOut = keepOut
+        self.keepOutMargin = float(keepOutMargin)
         if separationRows not in ('all', 'min', 'active', 'true_min'):
             raise ValueError("separationRows must be 'all', 'min', 'active' or 'true_min', not {!r}".format(separationRows))
         if separationRows == 'active' and not 1 <= int(activeRows) <= 4:
@@ -560,6 +610,8 @@ class BezOptimization(object):
     def _operand(self, fam):
         """What the family's device calls take as their bound: the value in `model` -- for the keep-in family the region's
         tables (H, VF) of `keepIn` as it is NOW (drivers edit it in place); None: not set."""
+        if fam is _KEEP_OUT:
+            return None if self.keepOut is None else _keep_out_tables(self.keepOut, self.model['numVeh'], self.model['dim'])
         if fam is not _KEEP_IN:
             return self.model[fam.bound]
         return None if self.keepIn is None else _keep_in_tables(self.keepIn, self.model['numVeh'], self.model['dim'])
@@ -569,7 +621,8 @@ class BezOptimization(object):
         a search that ran out of budget raises in the name of `what` (bezier._raise_md)"""
         call = getattr(ctx, fam.envelope if envelope else fam.true_min)
         operands = (Y, tf, bound) if fam.span else (Y, bound)
-        return _md_checked(call(*operands, *fam.lead, eps_rel=self.TRUE_MIN_EPS_REL), what)
+        beside = {'margin': self.keepOutMargin} if fam is _KEEP_OUT else {}
+        return _md_checked(call(*operands, *fam.lead, eps_rel=self.TRUE_MIN_EPS_REL, **beside), what)
 
     def _rows_option(self, fam):
         """'all' / 'true_min': the family's rows option; a family without a `rows` method has true rows only"""
@@ -836,6 +889,14 @@ class BezOptimization(object):
         of sequential.py."""
         return self._vehicle_closure(_KEEP_IN)
 
+    @property
+    def keepOutConstraints(self):
+        """min over the trajectory of max_f (a_f . c_v - b_f) - keepOutMargin >= 0 for every (vehicle, obstacle) of `keepOut`,
+        vehicle-major: N * O true rows (obtg_keep_out_true_min) -- the same whatever tf is.  Conservative near corners (the row
+        is at most the true distance minus the margin, with unit normals); negative, minus the depth, inside.  Not part of the
+        one-launch structured step, of the constraint sweep, of distributed.py or of sequential.py."""
+        return self._vehicle_closure(_KEEP_OUT)
+
     def spatialSeparationConstraints(self, x, robust=False):
         """All-pairs minDist over vehicles AND shape obstacles (optimization.py:109-133);
         returns shape (P, 3): (dist, t1, t2) - maxSep, as the reference does.
@@ -997,6 +1058,8 @@ class BezOptimization(object):
         if self.keepIn is not None:          # the region by its tables' BYTES, as the obstacles: drivers edit it in place
             H, VF = self._operand(_KEEP_IN)
             tail.append(('keepIn', self.keepInRows, H.tobytes() + VF.tobytes()))
+        if self.keepOut is not None:         # after keep-in's, likewise by the tables' bytes
+            tail.append(('keepOut', self.keepOutMargin, b''.join(t.tobytes() for t in self._operand(_KEEP_OUT))))
         return (int(DEG_ELEV), self.separationRows, *rows, self.activeRows, self._rv_cache[0], self.model['maxSep'], *bounds,
                 None if self._timeopt() else self.model['tf'],
                 None if self.pointObstacles is None else np.asarray(self.pointObstacles, dtype=float).tobytes(),
@@ -1192,6 +1255,33 @@ class BezOptimization(object):
         region = self._bound(_KEEP_IN, 'trueKeepInMargins')
         r = self._true_rows_at(_KEEP_IN, np.asarray(x, dtype=float), region, 'trueKeepInMargins')
         return r['val'][0], r['t_star'][0]
+
+    def keepOutJacobian(self, x, structured=True, method='fd'):
+        """d(keepOutConstraints)/dx, dense [N * O][n_x]: method='fd' differences the closure's rows (one batched call;
+        `structured` changes nothing); method='envelope' is the derivative of each row at the parameter and the active faces its
+        search returns -- one face at an end or a smooth minimum, the weighted pair at a kink (obtg_keep_out_true_min_jac, one
+        call at x) -- scattered to the columns of the item's own vehicle; method='exact' is not built.  The rows have no explicit
+        dependence on tf: that part of a time-optimal problem's tf column is an exact 0 (with prescribed speeds the column still
+        carries dY/dtf)."""
+        fam = _KEEP_OUT
+        tables = self._bound(fam, fam.jacobian)          # missing obstacles answer before anything is computed
+        self._check_jac_method(fam, method)
+        if method != 'envelope':
+            return self._jac(x, fam.key)
+        x = np.asarray(x, dtype=float)
+        r = self._vehicle_true_min(fam, self._ctx(False), self.reshapeVectors(x[None]), None, tables, fam.jacobian + '(envelope)',
+                                   envelope=True)
+        owner = tables[2][:, 0].astype(np.int64)
+        return self._scatter_exact(r['jac'][0][:, None], (owner,), (1.0,), np.zeros((owner.size, 1)))      # blocks of one row each
+
+    def trueKeepOutClearances(self, x):
+        """dict(val[P], t_star[P], face[P][2], lam[P], status[P]): per (vehicle, obstacle) of `keepOut`, in the order of
+        keepOutConstraints, the row (clearance minus keepOutMargin), the parameter in [0, 1] where it is reached, the active
+        faces as indices into the stacked face table (the second -1 without one), the first face's weight and the search's
+        status (obtg_keep_out_true_min): the vehicles stay clear iff every val is >= 0."""
+        tables = self._bound(_KEEP_OUT, 'trueKeepOutClearances')
+        r = self._true_rows_at(_KEEP_OUT, np.asarray(x, dtype=float), tables, 'trueKeepOutClearances')
+        return {k: r[k][0] for k in ('val', 't_star', 'face', 'lam', 'status')}
 
     # ------------------------------------------------------------------ exact Jacobians (method='exact')
     # The device returns d rows / d Y per pair or vehicle ([..][rows][dim][deg+1] blocks, include/obtg.h obtg_*_jac); the chain

@@ -1244,13 +1244,12 @@ __device__ __forceinline__ void tsep_elev_group_stream(const TsepXYParams& t, co
     __syncthreads();
     const int n_tiles = (n_valid + 15) >> 4;
     constexpr int kSlots = 4;                                          // 16 x 128 doubles = 1024 pieces over 256 threads
-#ifndef OBTG_STRUCT_S_TILE_MAJOR
     if (NT <= 8) {
         // Rows of up to 128 columns (one column group): all four tiles of the group wait in registers and the stream goes batch
         // row by batch row -- the workgroup writes its 64 pairs' rows (up to 62 KB, contiguous) of batch row b, while the
         // workgroups of the neighbouring groups write theirs: together one dense run per batch row, which is what the memory
         // system rewards (tools/store_pattern_probe2.hip: a dense advancing write front).  Tile after tile across the batch
-        // rows, as below (and with -DOBTG_STRUCT_S_TILE_MAJOR, the A/B build), every workgroup leaves a quarter of each row for later:
+        // rows, as below (the form of rows wider than 128 columns), every workgroup leaves a quarter of each row for later:
         // C5 0.545 against 0.528 ms over four interleaved pairs of runs on one box.
         double bfr[2][E::KS];
         coop_load_bfrag<L>(t.Tf, NT, 0, wave, lane, bfr);
@@ -1306,7 +1305,6 @@ __device__ __forceinline__ void tsep_elev_group_stream(const TsepXYParams& t, co
         }
         return;
     }
-#endif
     for (int cg = 0; 8 * cg < NT; ++cg) {
         const int c0 = 128 * cg, cw = min(LR - c0, 128);
         double bfr[2][E::KS];

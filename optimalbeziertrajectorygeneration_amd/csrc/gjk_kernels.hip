@@ -25,6 +25,7 @@
 #include "gjk_true.h"
 #include "obtg_internal.h"
 #include "md_device.h"
+#include "struct_layout.h"
 // the Bernstein sweep body that k_pair_sweep runs beside the GJK workgroups: same contraction
 // setting as in bern_kernels.hip, so that both units produce the same arithmetic
 #pragma clang fp contract(fast)
@@ -1070,7 +1071,9 @@ __global__ __launch_bounds__(256, WPC) void k_step_fd_structured(const Structure
     TimelineScope tl(p.timeline);
     const int n_obj = p.n_veh + p.n_poly;
     double* lds = reinterpret_cast<double*>(xy_dyn);
-    // kind (0 S, 1 F, 2 G, 3 D) and index inside the kind from the block id
+    // The decode of the block id below has a host mirror in struct_layout.h, piece by piece (named at each piece), which
+    // tests/test_struct_layout.py walks for every block id of a layout: a change here is a change there.
+    // kind (0 S, 1 F, 2 G, 3 D) and index inside the kind from the block id (mirror: struct_block)
     // (block id mod 8 is the XCD: the pattern is rotated by one slot per group of 16, or every XCD would see one or two
     // kinds only and the XCD with the dearest kind would finish last)
     const int grp = (int)blockIdx.x >> 4, slot = ((int)blockIdx.x + grp) & 15;
@@ -1092,6 +1095,7 @@ __global__ __launch_bounds__(256, WPC) void k_step_fd_structured(const Structure
     if (kind == 3) {
         // ---- D: row 0's vehicle groups streamed into row ranges | the advanced vehicles, 64 rows to a group | rows whose
         //      tf is not tf[0] (a finite-difference row of tf itself), eight rows to a workgroup, in full
+        //      (mirror: struct_dyn_worker)
         __shared__ int s_dmap[kWave];
         const int gd = sp.dyn_groups_per_row;
         DynEmit em{ 0, 0, 0, 0, 0, s_dmap };
@@ -1139,7 +1143,7 @@ __global__ __launch_bounds__(256, WPC) void k_step_fd_structured(const Structure
         return;
     }
     if (kind == 1) {
-        // ---- F: row b's own pairs
+        // ---- F: row b's own pairs (mirror: struct_fix_row)
         const int b = id + sp.first_pert;
         GjkSwarmParams q = p;
         q.chunk = sp.fix_chunk; q.chg_from_fd = 1; q.passes = 1; q.len_in = nullptr; q.len_out = nullptr;
@@ -1163,7 +1167,8 @@ __global__ __launch_bounds__(256, WPC) void k_step_fd_structured(const Structure
         return;
     }
     if (kind == 2) {
-        // ---- G: chunk c of row 0's hull pairs, streamed into the rows of range r
+        // ---- G: chunk c of row 0's hull pairs, streamed into the rows of range r (mirrors: struct_worker and struct_chunk_pairs;
+        //      struct_range_rows and struct_ticket_rows for the rows, all on struct_gjk_kind)
         const int t = id, c = t % sp.gjk_chunks, r = t / sp.gjk_chunks;
         const int cp = sp.gjk_chunk_pairs;
         const int k0 = c * cp, n_valid = max(0, min(cp, p.n_pairs - k0));
@@ -1241,7 +1246,8 @@ __global__ __launch_bounds__(256, WPC) void k_step_fd_structured(const Structure
         }
         return;
     }
-    // ---- S: group g of row 0's separation block, streamed into the rows of range r
+    // ---- S: group g of row 0's separation block, streamed into the rows of range r (mirrors: struct_worker, struct_range_rows
+    //      and struct_ticket_rows on struct_sep_kind; ELEV bounds its ranges by B, which sep_static_rows is with the tickets off)
     {
         const int g = id % sp.n_sep_groups, r = id / sp.n_sep_groups;
         // ranges [0, sep_static_ranges) own rows of [0, sep_static_rows); the workgroups behind them are the group's sweepers
@@ -4046,11 +4052,7 @@ bool constraint_sweep_is_one_launch(obtg_ctx* c, int B)
 // Which shapes k_step_fd_structured covers, decided without launching anything: the launcher and the router of
 // obtg_constraint_sweep_dev (capi.cpp) share it, as they share pair_sweep_plan above.  OBTG_ERR_UNSUPPORTED: not this
 // shape (3-D, degree 20, obtg_ctx_set_ang_rate_order(2) with DEG_ELEV > 0, de-duplication on, rows beyond 158 KB of LDS).
-// rows at run time: the default share of a group's rows, in per cent, that its sweepers write (launch_step_fd_structured).
-// C3, short runs on one box, parent 0.1009 ms: S 10 / 20 / 30 / 40 / 50 / 60 / 70 % swept 0.0988 / 0.1030 / 0.1041 / 0.1077 /
-// 0.1105 / 0.1149 / 0.1259 ms -- a chip full of sweepers alone stores at 5.7 TB/s, under the 6.3 of the mixed launch, so they
-// get what fills the tail and no more; G sweepers on top cost more (20,20: 0.1144; 30,30: 0.1161 against 0.1041)
-constexpr int kStructSweptShareSep = 10, kStructSweptShareGjk = 0;
+// The plan chooses the kernel form and its LDS; how the work is split over the grid is struct_layout.h's.
 struct StructuredPlan {
     void (*kern)(const StructuredParams) = nullptr;
     size_t lds = 0;
@@ -4090,9 +4092,8 @@ static int step_fd_structured_plan(obtg_ctx* c, StructuredPlan& pl)
     const int n_obj = c->n_veh + c->n_poly, vpq = nc | 1, L = 2 * c->deg + 1, LR = L + c->R;
     // G: chunks of ~80 hull pairs (one short gjkNew phase per workgroup)
     pl.gjk_chunk_pairs = 16 * (size_t)n_obj * vpq > 40 * 1024 ? 64 : 80;       // (large rows: the chunk's results behind 70 KB of hulls stay under 80 KB)
-    if (const char* e = getenv("OBTG_STRUCT_GJK_CHUNK")) pl.gjk_chunk_pairs = std::max(16, atoi(e));
     // (DEG_ELEV > 0: stream workgroups of 16 vehicles that collect their rows in LDS -- while that area fits beside the tables)
-    pl.dyn_split = elev && !(getenv("OBTG_STRUCT_DYN_SPLIT") && getenv("OBTG_STRUCT_DYN_SPLIT")[0] == '0') &&
+    pl.dyn_split = elev &&
                    sizeof(double) * (dyn_elev_lds_doubles(c->deg, c->R) + dyn_elev_stage_doubles(c->deg, c->R)) <= 72 * (size_t)1024;
     const int n_sobj = c->n_veh + c->n_obs;                  // what an S workgroup stages: vehicles and point obstacles
     size_t lds_s = std::max((size_t)16 * n_sobj * vpq, sizeof(double) * kWave * L);      // (flat: the tile overlays the staged row)
@@ -4205,8 +4206,6 @@ int launch_step_fd_structured(obtg_ctx* c, int B, double max_sep, double* d_out_
     if (!(wants_dynamics(speed) && d_out_sep)) return OBTG_ERR_UNSUPPORTED;
     StructuredPlan pl;
     if (int rc = step_fd_structured_plan(c, pl)) return rc;
-    const bool elev = c->R > 0;
-    void (*kern)(const StructuredParams) = pl.kern;
     StructuredParams sp{};
     GjkSwarmParams& p = sp.g;
     fill_swarm_params(c, p, nullptr, max_iter, md_cap, d_flag, d_p1, d_p2, d_dist, d_nsup, d_status);      // (the view's row: c->fd)
@@ -4216,143 +4215,26 @@ int launch_step_fd_structured(obtg_ctx* c, int B, double max_sep, double* d_out_
     if (c->n_obs > 0) p.ts.n_tobj = c->n_veh + c->n_obs;      // point obstacles: objects of the separation pair table only
     sp.cv4 = c->d_ang_T4.as<double>(); sp.cv2 = c->d_ang_cv2.as<double>(); sp.R = c->R;
     fill_dynamics(c, p, *speed, B);
-    const int L = 2 * c->deg + 1, LR = L + c->R;
-    // S: one workgroup per (64-pair group, row range); about two thousand workgroups of streams
-    sp.n_sep_groups = (c->n_pairs + kWave - 1) / kWave;
-    // (a large step -- C4: 58 GB of separation rows -- gets more, so that a stream stays near 4 MB)
-    const double sep_stream_bytes = 8.0 * kWave * LR * (double)B * sp.n_sep_groups;
-    // (small batches -- a rank's share of a row-sharded iteration -- get fewer, longer streams: every S workgroup repeats row
-    // 0's products for its group and every G workgroup its gjkNew chunk, and 2048 + 1024 of them are three rounds of resident
-    // workgroups for a few rows each.  C3, tools/r04_struct_small_batch_scan.sh: B = 145 0.044 -> 0.027 ms with 512 / 384
-    // workgroups, B = 289 0.055 -> 0.040 with 1024 / 512; from B = 577 on the old numbers are the best)
-    const double s_floor = std::min(2048.0, std::max(256.0, 3.5 * B));
-    int s_target = (int)std::min(32768.0, std::max(s_floor, sep_stream_bytes / (4 << 20)));
-    // G: chunks of ~80 hull pairs (one short gjkNew phase per workgroup), row ranges for ~512 workgroups
-    sp.gjk_chunk_pairs = pl.gjk_chunk_pairs;
-    sp.gjk_chunks = (c->n_hull_pairs + sp.gjk_chunk_pairs - 1) / sp.gjk_chunk_pairs;
-    // (rows at run time, below: with the sweepers on, the two worker-count knobs count sweepers, not fixed ranges)
-    const int slots = (c->n_cus > 0 ? c->n_cus : 256) * pl.wpc;
-    const char* e_dyn = getenv("OBTG_STRUCT_DYNAMIC_ROWS");
-    const bool dyn_rows = !elev && (e_dyn && e_dyn[0] ? e_dyn[0] != '0' : 2 * (sp.n_sep_groups + sp.gjk_chunks) <= slots);
-    const char* e_sep_wgs = getenv("OBTG_STRUCT_SEP_WGS");      // (experiments)
-    const char* e_gjk_wgs = getenv("OBTG_STRUCT_GJK_WGS");
-    if (e_sep_wgs && !dyn_rows) s_target = std::max(1, atoi(e_sep_wgs));
-    const int g_target = e_gjk_wgs && !dyn_rows ? std::max(1, atoi(e_gjk_wgs)) : (int)std::min(1024.0, std::max(192.0, 2.6 * B));
-    int g_target_b = (int)std::min(32768.0, std::max((double)g_target, 68.0 * c->n_hull_pairs * (double)B / (4 << 20)));
-    int s_ranges = std::max(1, std::min(B, s_target / std::max(1, sp.n_sep_groups)));
-    sp.sep_rows_per = (B + s_ranges - 1) / s_ranges;
-    s_ranges = (B + sp.sep_rows_per - 1) / sp.sep_rows_per;
-    int g_ranges = std::max(1, std::min(B, g_target_b / std::max(1, sp.gjk_chunks)));
-    sp.gjk_rows_per = (B + g_ranges - 1) / g_ranges;
-    g_ranges = (B + sp.gjk_rows_per - 1) / sp.gjk_rows_per;
-    sp.sep_static_ranges = s_ranges; sp.gjk_static_ranges = g_ranges;
-    sp.sep_static_rows = sp.gjk_static_rows = B;
-    // Rows at run time (flat steps).  With fixed ranges alone the launch has a tail: whichever workgroup is dispatched last
-    // still has its whole range to write, and for the last tenth of the span most slots are empty
-    // (profiles/struct_dynamic_rows/timeline_parent_c3.txt).  So only the first rows of every group go to fixed ranges, of the
-    // usual length; the rest are handed out by ticket (StructuredParams::tickets) to SWEEPERS, whose block ids come behind
-    // every other id of the grid: they start in the slots the draining launch leaves empty, share what is left down to a
-    // ticket and end together.  A sweeper stays until its group's rows are gone, which is why they are not mixed in
-    // earlier: S and G workers that draw ALL rows by ticket crowd the F and D workgroups out of the slots.
-    // With more groups than half the slots (C4: 510 groups on 256 or 512 slots) the fixed ranges stay alone.
-    // OBTG_STRUCT_DYNAMIC_ROWS=0 / 1: fixed ranges alone / sweepers whatever the shape (read per call: A/B runs and tests).
-    int s_sweep = 0, g_sweep = 0;                          // sweepers per group / per chunk
-    if (dyn_rows) {
-        // a ticket of 40 - 48 KB (C3: 4 rows of a separation group, 9 of a chunk): about 3 us of a sweeper's stores
-        sp.sep_ticket_rows = std::max(2, (48 << 10) / (8 * kWave * L));
-        sp.gjk_ticket_rows = std::max(2, (48 << 10) / (68 * sp.gjk_chunk_pairs));
-        if (const char* e = getenv("OBTG_STRUCT_TICKET_ROWS")) {      // S rows per ticket; G tickets are twice as many rows (half as wide)
-            sp.sep_ticket_rows = std::max(1, atoi(e));
-            sp.gjk_ticket_rows = 2 * sp.sep_ticket_rows;
-        }
-        // the share of a group's rows that is swept, in per cent ("S,G"; 100: no fixed ranges at all)
-        int share[2] = { kStructSweptShareSep, kStructSweptShareGjk };
-        if (const char* e = getenv("OBTG_STRUCT_DYNAMIC_SHARE")) {
-            if (sscanf(e, "%d,%d", &share[0], &share[1]) < 2) share[1] = share[0];
-            for (int& v : share) v = std::max(0, std::min(100, v));
-        }
-        // (whole ranges: a fixed range is as long as without sweepers)
-        sp.sep_static_rows = B - (int)((long long)B * share[0] / 100);
-        sp.sep_static_rows -= sp.sep_static_rows % sp.sep_rows_per;
-        sp.gjk_static_rows = B - (int)((long long)B * share[1] / 100);
-        sp.gjk_static_rows -= sp.gjk_static_rows % sp.gjk_rows_per;
-        sp.sep_static_ranges = sp.sep_static_rows / sp.sep_rows_per;
-        sp.gjk_static_ranges = sp.gjk_static_rows / sp.gjk_rows_per;
-        // sweepers: a chip's worth of S, half of one of G; no more than tickets, unless the count was asked for (with the
-        // tickets on, OBTG_STRUCT_SEP_WGS / OBTG_STRUCT_GJK_WGS count the sweepers of all groups together)
-        const int s_swept = B - sp.sep_static_rows, g_swept = B - sp.gjk_static_rows;
-        if (s_swept > 0)
-            s_sweep = e_sep_wgs ? std::max(1, atoi(e_sep_wgs) / std::max(1, sp.n_sep_groups))
-                                : std::max(1, std::min(slots / std::max(1, sp.n_sep_groups), (s_swept + sp.sep_ticket_rows - 1) / sp.sep_ticket_rows));
-        if (g_swept > 0)
-            g_sweep = e_gjk_wgs ? std::max(1, atoi(e_gjk_wgs) / std::max(1, sp.gjk_chunks))
-                                : std::max(1, std::min(slots / 2 / std::max(1, sp.gjk_chunks), (g_swept + sp.gjk_ticket_rows - 1) / sp.gjk_ticket_rows));
-    }
-    sp.fix_chunk = 256;
     p.vp_off = c->d_vp_off.as<int>(); p.vp_idx = c->d_vp_idx.as<int>();
-    sp.n_kind[0] = sp.n_sep_groups * (sp.sep_static_ranges + s_sweep);
-    sp.first_pert = c->fd.row0 > 0 ? 0 : 1;            // (a range that starts later: its local row 0 is a perturbed row too)
-    sp.n_kind[1] = B - sp.first_pert;
-    sp.n_kind[2] = sp.gjk_chunks * (sp.gjk_static_ranges + g_sweep);
-    // D: ~256 streams of row 0's groups (at most 64 rows each, at least 4 when there are that many: at C5 a stream of 19
-    // rows keeps its workgroup for 430 us of a 650 us launch, one of 5 rows for 190), the advanced vehicles 64 to a
-    // group, and one workgroup per 8 rows that looks for rows with their own tf
-    sp.dyn_groups_per_row = (c->n_veh + kWave - 1) / kWave;
-    sp.dyn_rows_per = std::min(64, std::max((B + 255) / 256, std::min(4, B)));
-    sp.dyn_split = pl.dyn_split;      // (DEG_ELEV > 0: stream workgroups of 16 vehicles that collect their rows in LDS)
-    if (sp.dyn_split) sp.dyn_rows_per = std::min(64, 4 * sp.dyn_rows_per);      // (16 vehicles per stream workgroup instead of 64: the same bytes)
-    if (const char* e = getenv("OBTG_STRUCT_DYN_ROWS")) sp.dyn_rows_per = std::max(1, std::min(64, atoi(e)));
-    sp.dyn_streams = (sp.dyn_split ? 4 : 1) * sp.dyn_groups_per_row * ((B + sp.dyn_rows_per - 1) / sp.dyn_rows_per);
-    sp.dyn_fix_groups = (B - sp.first_pert + kWave - 1) / kWave;
-    const int dyn_x = sp.dyn_groups_per_row * ((B - 1 + 7) / 8);
-    sp.n_kind[3] = sp.dyn_streams + sp.dyn_fix_groups + dyn_x;
-    unsigned grid = 0;
-    {
-        // shares of every 16 block ids by expected work (workgroups x duration on the C3 timeline: S 12.5, F 15.2, G 20.2, D 10.7 us)
-        // (what decides is where each kind's ids run out: the kinds should end at about the same block id, so the D
-        // weights are those of its neighbours, not its 190 us streams: 7:3:3:3 instead of 7:4:4:1 costs C5 10 %)
-        const double cost_flat[4] = { 12.5, 15.2, 20.2, 16.0 }, cost_elev[4] = { 40.0, 36.0, 38.0, 40.0 };
-        const double* cost = elev ? cost_elev : cost_flat;     // (DEG_ELEV > 0: the streams are 2n+R+1 columns wide, the dynamics groups k_dynamics_elev's)
-        double w[4], tot = 0.0;
-        // (the sweepers are left out: the shares make the fixed ranges, F, G and D run out of ids together, and the sweepers'
-        // ids follow)
-        const int n_fixed[4] = { sp.n_sep_groups * sp.sep_static_ranges, sp.n_kind[1], sp.gjk_chunks * sp.gjk_static_ranges, sp.n_kind[3] };
-        for (int k = 0; k < 4; ++k) { w[k] = n_fixed[k] * cost[k]; tot += w[k]; }
-        tot -= w[3];
-        w[3] = (sp.dyn_streams + sp.dyn_fix_groups) * cost[3];      // (the workgroups that look for rows with their own tf come last and cost nothing)
-        tot += w[3];
-        int sum = 0;
-        for (int k = 0; k < 4; ++k) { sp.per16[k] = sp.n_kind[k] > 0 ? std::max(1, (int)(16.0 * w[k] / tot + 0.5)) : 0; sum += sp.per16[k]; }
-        if (const char* e = getenv("OBTG_STRUCT_PER16")) {      // (experiments: "S,F,G,D" summing to 16)
-            int v[4] = { 0, 0, 0, 0 };
-            if (sscanf(e, "%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3]) == 4 && v[0] + v[1] + v[2] + v[3] == 16) {
-                for (int k = 0; k < 4; ++k) sp.per16[k] = v[k];
-                sum = 16;
-            }
-        }
-        while (sum != 16) {             // give to / take from the kind with the largest share
-            int kmax = 0;
-            for (int k = 1; k < 4; ++k) if (sp.per16[k] > sp.per16[kmax]) kmax = k;
-            sp.per16[kmax] += sum < 16 ? 1 : -1;
-            sum += sum < 16 ? 1 : -1;
-        }
-        // spread each kind's slots evenly over the 16
-        struct Slot { double pos; int kind; };
-        std::vector<Slot> slots;
-        for (int k = 0; k < 4; ++k)
-            for (int j = 0; j < sp.per16[k]; ++j) slots.push_back({ (j + 0.5) / sp.per16[k] + 1e-3 * k, k });
-        std::sort(slots.begin(), slots.end(), [](const Slot& a, const Slot& b) { return a.pos < b.pos; });
-        int seen[4] = { 0, 0, 0, 0 };
-        int groups = 0;
-        for (int i = 0; i < 16; ++i) { sp.pat[i] = (unsigned char)slots[i].kind; sp.rank[i] = (unsigned char)seen[slots[i].kind]++; }
-        for (int k = 0; k < 4; ++k)
-            if (sp.per16[k] > 0) groups = std::max(groups, (sp.n_kind[k] + sp.per16[k] - 1) / sp.per16[k]);
-        grid = (unsigned)groups * 16u;
-    }
     p.dyn_first_block = 0;
-    const size_t lds = pl.lds;
-    OBTG_HIP(c, allow_lds(kern, lds));
-    if (dyn_rows) {
+    // the split of the work over the grid: struct_layout.h (the switches are read per call: A/B runs and tests)
+    StructShape shape{};
+    shape.deg = c->deg; shape.R = c->R; shape.n_veh = c->n_veh; shape.n_pairs = c->n_pairs; shape.n_hull_pairs = c->n_hull_pairs;
+    shape.n_cus = c->n_cus; shape.row0 = c->fd.row0;
+    shape.wpc = pl.wpc; shape.gjk_chunk_pairs = pl.gjk_chunk_pairs; shape.dyn_split = pl.dyn_split;
+    const StructLayout l = struct_layout(shape, B, struct_knobs_from_env());
+    sp.n_sep_groups = l.n_sep_groups; sp.sep_rows_per = l.sep_rows_per;
+    sp.gjk_chunks = l.gjk_chunks; sp.gjk_chunk_pairs = l.gjk_chunk_pairs; sp.gjk_rows_per = l.gjk_rows_per;
+    sp.fix_chunk = l.fix_chunk;
+    for (int k = 0; k < 4; ++k) { sp.n_kind[k] = l.n_kind[k]; sp.per16[k] = l.per16[k]; }
+    for (int i = 0; i < 16; ++i) { sp.pat[i] = l.pat[i]; sp.rank[i] = l.rank[i]; }
+    sp.dyn_groups_per_row = l.dyn_groups_per_row; sp.dyn_rows_per = l.dyn_rows_per; sp.dyn_streams = l.dyn_streams;
+    sp.dyn_fix_groups = l.dyn_fix_groups; sp.dyn_split = l.dyn_split; sp.first_pert = l.first_pert;
+    sp.sep_ticket_rows = l.sep_ticket_rows; sp.gjk_ticket_rows = l.gjk_ticket_rows;
+    sp.sep_static_ranges = l.sep_static_ranges; sp.sep_static_rows = l.sep_static_rows;
+    sp.gjk_static_ranges = l.gjk_static_ranges; sp.gjk_static_rows = l.gjk_static_rows;
+    OBTG_HIP(c, allow_lds(pl.kern, pl.lds));
+    if (l.tickets) {
         // this launch's bank of ticket counters (obtg_ctx::d_struct_tickets).  Nothing is queued for it on the step's path:
         // the previous launch left it zero.  Only a layout the banks have not seen (another pair list, more groups than
         // the banks hold) zeroes them here.
@@ -4370,19 +4252,16 @@ int launch_step_fd_structured(obtg_ctx* c, int B, double max_sep, double* d_out_
         sp.tickets = c->d_struct_tickets.as<int>() + (size_t)c->struct_ticket_bank * c->struct_ticket_stride;
         sp.tickets_idle = c->d_struct_tickets.as<int>() + (size_t)(c->struct_ticket_bank ^ 1) * c->struct_ticket_stride;
     }
-    TimelineDump tl(c, grid, p.timeline);
+    TimelineDump tl(c, (unsigned)l.grid, p.timeline);
     if (tl.rc) return tl.rc;
     {
         ScopedKernelTimer tm(c, OBTG_K_PAIR_SWEEP, true);
-        launch_timed(tm, kern, dim3(grid), dim3(256), lds, c->stream, sp);
+        launch_timed(tm, pl.kern, dim3((unsigned)l.grid), dim3(256), pl.lds, c->stream, sp);
     }
     OBTG_HIP(c, hipGetLastError());
-    if (dyn_rows) c->struct_ticket_bank ^= 1;      // (the launch is on the stream: it leaves the other bank zero)
+    if (l.tickets) c->struct_ticket_bank ^= 1;      // (the launch is on the stream: it leaves the other bank zero)
     char hdr[256];
-    snprintf(hdr, sizeof hdr, "# grid %u structured n_S %d n_F %d n_G %d n_D %d per16 %d %d %d %d pat %d%d%d%d%d%d%d%d%d%d%d%d%d%d%d%d B %d ticket_rows %d %d",
-             grid, sp.n_kind[0], sp.n_kind[1], sp.n_kind[2], sp.n_kind[3], sp.per16[0], sp.per16[1], sp.per16[2], sp.per16[3],
-             sp.pat[0], sp.pat[1], sp.pat[2], sp.pat[3], sp.pat[4], sp.pat[5], sp.pat[6], sp.pat[7], sp.pat[8], sp.pat[9], sp.pat[10],
-             sp.pat[11], sp.pat[12], sp.pat[13], sp.pat[14], sp.pat[15], B, dyn_rows ? sp.sep_ticket_rows : 0, dyn_rows ? sp.gjk_ticket_rows : 0);
+    struct_layout_header(l, hdr, sizeof hdr);
     return tl.finish(hdr);
 }
 

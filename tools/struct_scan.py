@@ -1,5 +1,5 @@
 """Interleaved scan of the structured step's launch parameters in ONE process (the launch reads OBTG_STRUCT_* per call):
-    python tools/struct_scan.py C5 "OBTG_STRUCT_PER16=7,4,4,1" "OBTG_STRUCT_PER16=8,3,3,2;OBTG_STRUCT_SEP_WGS=4096" ...
+    python tools/struct_scan.py C3 "" "OBTG_STRUCT_DYNAMIC_SHARE=20" "OBTG_STRUCT_DYNAMIC_ROWS=0;OBTG_STRUCT_SEP_WGS=4096" ...
 every configuration ROUNDS times in turn, N launches each; prints median / min ms per launch.  "" = the defaults."""
 import os
 import sys
@@ -10,7 +10,7 @@ sys.argv, ARGS = sys.argv[:2], sys.argv[2:]
 exec(open("tools/timeline_structured_run.py").read().split("import time")[0])     # the workload's context and buffers (WL = argv[1])
 import numpy as np
 
-KEYS = ("OBTG_STRUCT_PER16", "OBTG_STRUCT_SEP_WGS", "OBTG_STRUCT_GJK_WGS", "OBTG_STRUCT_GJK_CHUNK", "OBTG_STRUCT_DYN_ROWS", "OBTG_STRUCT_DYN_SPLIT")
+KEYS = ("OBTG_STRUCT_DYNAMIC_ROWS", "OBTG_STRUCT_DYNAMIC_SHARE", "OBTG_STRUCT_TICKET_ROWS", "OBTG_STRUCT_SEP_WGS", "OBTG_STRUCT_GJK_WGS")
 ROUNDS, N = int(os.environ.get("SCAN_ROUNDS", "5")), int(os.environ.get("SCAN_N", "60"))
 
 

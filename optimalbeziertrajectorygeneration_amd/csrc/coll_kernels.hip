@@ -88,29 +88,8 @@ __device__ __forceinline__ void cc_eval_row(const double* lds, int o1, int K, in
     const bool cap = gr.status == OBTG_ST_MD_CAP || gr.status == OBTG_ST_CYCLE;
     double ub = 0.0;
     if constexpr (CURVES) {
-        const double* c1 = lds + o1; const double* c2 = lds + o2;
-        double dd[4];
-        if constexpr (PLANAR) {          // (norm_seq with dz = 0: s + 0 * 0 = s)
-            auto n2 = [](double ax, double ay, double bx, double by) {
-                const double dx = ax - bx, dy = ay - by;
-                double s = 0.0;
-                s += dx * dx; s += dy * dy;
-                return __builtin_sqrt(s);
-            };
-            dd[0] = n2(c1[0], c1[K], c2[0], c2[K]);
-            dd[1] = n2(c1[0], c1[K], c2[K - 1], c2[2 * K - 1]);
-            dd[2] = n2(c1[K - 1], c1[2 * K - 1], c2[0], c2[K]);
-            dd[3] = n2(c1[K - 1], c1[2 * K - 1], c2[K - 1], c2[2 * K - 1]);
-        } else {
-            dd[0] = norm_seq(c1[0], c1[K], c1[2 * K], c2[0], c2[K], c2[2 * K]);
-            dd[1] = norm_seq(c1[0], c1[K], c1[2 * K], c2[K - 1], c2[2 * K - 1], c2[3 * K - 1]);
-            dd[2] = norm_seq(c1[K - 1], c1[2 * K - 1], c1[3 * K - 1], c2[0], c2[K], c2[2 * K]);
-            dd[3] = norm_seq(c1[K - 1], c1[2 * K - 1], c1[3 * K - 1], c2[K - 1], c2[2 * K - 1], c2[3 * K - 1]);
-        }
-        int am = 0;
-        for (int i = 1; i < 4; ++i) if (dd[i] < dd[am]) am = i;
-        for (int i = 0; i < 4; ++i) if (dd[i] != dd[i]) { am = i; break; }
-        ub = dd[am];
+        int am;
+        ub = md_upper_bound<PLANAR>(lds + o1, K, lds + o2, K, am);
     }
     rec[C_CAP] = cap ? 1.0 : 0.0; rec[C_POS] = (gr.flag > 0 && !cap) ? 1.0 : 0.0; rec[C_UB] = ub;
 }

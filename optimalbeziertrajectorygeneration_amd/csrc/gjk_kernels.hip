@@ -1671,7 +1671,11 @@ __global__ void k_bcast_row0(T* __restrict__ a, size_t row_len, int B)
 }
 
 // -------------------------------------------------------------------------------------
-//  _minDist / _minDist2Poly: depth-first branch & bound with an explicit per-lane stack
+//  _minDist / _minDist2Poly: depth-first branch & bound with an explicit stack of frames.
+//  First the pieces of a node (split parameter, de Casteljau split), serial and wave-parallel; then the walk,
+//  once per family (md_walk, md2_walk), and the kernels that stage a pair and call it: one lane per pair
+//  (k_min_dist, k_min_dist2poly), one wavefront per pair (k_min_dist_wave, k_min_dist_mixed,
+//  k_min_dist2poly_wave).  The quad and robust forms further down have walks of their own.
 // -------------------------------------------------------------------------------------
 constexpr int kMdMaxK = 32;   // control points per curve supported by the branch & bound kernels
 
@@ -1732,7 +1736,7 @@ __device__ void split_row(const double* src, int K, double t, int half, double* 
     if (half == 0) dst[K - 1] = tmp[0]; else dst[0] = tmp[0];
 }
 
-// frame layout (doubles): c1[3K] c2[3K] then scalars
+// frame layout (doubles): c1[3 KA] c2[3 KB] then scalars
 enum { F_T1 = 0, F_T2, F_T1L, F_T1H, F_T2L, F_T2H, F_ALPHA, F_RT1, F_RT2, F_STATE, F_NSCAL };
 
 struct MdParams {
@@ -1748,121 +1752,12 @@ struct MdParams {
     int* queue;                           // wave form: the next slot of `order` (zeroed before the launch)
 };
 
-__global__ __launch_bounds__(64) void k_min_dist(const MdParams p)
-{
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= p.n_pairs) return;
-    const int K = p.K, FR = 6 * K + F_NSCAL;
-    double* st = p.stack + (size_t)k * p.max_depth * FR;
-    const double* ca = p.curves + (size_t)p.pa[k] * 3 * K;
-    const double* cb = p.curves + (size_t)p.pb[k] * 3 * K;
-    for (int i = 0; i < 3 * K; ++i) { st[i] = ca[i]; st[3 * K + i] = cb[i]; }
-    {
-        double* sc = st + 6 * K;
-        sc[F_T1L] = 0; sc[F_T1H] = 1; sc[F_T2L] = 0; sc[F_T2H] = 1;
-        sc[F_ALPHA] = INFINITY; sc[F_STATE] = 0;
-    }
-    int depth = 0;           // index of the current frame; cnt = depth + 1
-    int nodes = 0, calls = 0, dmax = 0, status = OBTG_MD_OK;
-    double r0 = INFINITY, r1 = -1, r2 = -1;   // value returned by the frame that just finished
-    bool returning = false;
-    for (;;) {
-        double* f = st + (size_t)depth * FR;
-        double* sc = f + 6 * K;
-        int state = (int)sc[F_STATE];
-        if (!returning && state == 0) {
-            // ---- evaluate this node (bezier.py:1310-1374)
-            if (depth + 1 > 1000) { r0 = r1 = r2 = -1; returning = true; depth--; if (depth < 0) break; continue; }
-            if (nodes >= p.max_nodes) { status = OBTG_MD_NODE_CAP; break; }
-            nodes++;
-            if (depth + 1 > dmax) dmax = depth + 1;
-            Ctx<MemGlobal> g;
-            g.mem = MemGlobal{ f };
-            g.P1 = Poly{ 0, K, K, 1 };
-            g.P2 = Poly{ 3 * K, K, K, 1 };
-            g.trace = nullptr; g.trace_cap = 0; g.n_support = 0;
-            Result gr;
-            gjk::run(g, p.max_iter, p.md_cap, gr);
-            calls++;
-            if (gr.status == OBTG_ST_MD_CAP || gr.status == OBTG_ST_CYCLE) { status = OBTG_MD_GJK_CAP; break; }
-            double lb, t1, t2;
-            if (gr.flag > 0) {
-                lb = gr.dist;
-                t1 = hull_param(f, K, gr.c1);
-                t2 = hull_param(f + 3 * K, K, gr.c2);
-            } else { t1 = 0.5; t2 = 0.5; lb = p.eps; }
-            // _upperbound (bezier.py:1499-1516)
-            const double* c1 = f; const double* c2 = f + 3 * K;
-            double dd[4];
-            dd[0] = norm_seq(c1[0], c1[K], c1[2 * K], c2[0], c2[K], c2[2 * K]);
-            dd[1] = norm_seq(c1[0], c1[K], c1[2 * K], c2[K - 1], c2[2 * K - 1], c2[3 * K - 1]);
-            dd[2] = norm_seq(c1[K - 1], c1[2 * K - 1], c1[3 * K - 1], c2[0], c2[K], c2[2 * K]);
-            dd[3] = norm_seq(c1[K - 1], c1[2 * K - 1], c1[3 * K - 1], c2[K - 1], c2[2 * K - 1], c2[3 * K - 1]);
-            int am = 0;
-            for (int i = 1; i < 4; ++i) if (dd[i] < dd[am]) am = i;
-            for (int i = 0; i < 4; ++i) if (dd[i] != dd[i]) { am = i; break; }
-            const double ub = dd[am], t1loc = (am >> 1) ? 1.0 : 0.0, t2loc = (am & 1) ? 1.0 : 0.0;
-            double alpha = sc[F_ALPHA], nT1, nT2;
-            if (ub <= alpha) {
-                alpha = ub;
-                nT1 = (1 - t1loc) * sc[F_T1L] + t1loc * sc[F_T1H];
-                nT2 = (1 - t2loc) * sc[F_T2L] + t2loc * sc[F_T2H];
-            } else { nT1 = -1; nT2 = -1; }
-            if (lb >= alpha * (1 - p.eps)) {
-                r0 = alpha; r1 = nT1; r2 = nT2; returning = true; depth--;
-                if (depth < 0) break;
-                continue;
-            }
-            if (depth + 1 >= p.max_depth) { status = OBTG_MD_DEPTH_CAP; r0 = alpha; r1 = nT1; r2 = nT2; break; }
-            if (t1 != t1) t1 = 0;    // Bezier.split: NaN -> 0 (bezier.py:555-557)
-            if (t2 != t2) t2 = 0;
-            sc[F_T1] = t1; sc[F_T2] = t2; sc[F_ALPHA] = alpha; sc[F_RT1] = nT1; sc[F_RT2] = nT2;
-            state = 1; sc[F_STATE] = 1;
-        }
-        if (returning) {
-            // a child of this frame finished: keep the better answer (bezier.py:1384-1406)
-            if (r0 < sc[F_ALPHA]) { sc[F_ALPHA] = r0; sc[F_RT1] = r1; sc[F_RT2] = r2; }
-            returning = false;
-            state = (int)sc[F_STATE];
-        }
-        if (state >= 5) {
-            r0 = sc[F_ALPHA]; r1 = sc[F_RT1]; r2 = sc[F_RT2]; returning = true; depth--;
-            if (depth < 0) break;
-            continue;
-        }
-        // ---- descend into child state-1: (c3,c5) (c3,c6) (c4,c5) (c4,c6)
-        {
-            const int ch = state - 1, h1 = ch >> 1, h2 = ch & 1;
-            const double t1 = sc[F_T1], t2 = sc[F_T2];
-            double* nf = f + FR;
-            for (int c = 0; c < 3; ++c) {
-                split_row(f + c * K, K, t1, h1, nf + c * K);
-                split_row(f + 3 * K + c * K, K, t2, h2, nf + 3 * K + c * K);
-            }
-            double* ns = nf + 6 * K;
-            const double t1len = sc[F_T1H] - sc[F_T1L], t2len = sc[F_T2H] - sc[F_T2L];
-            const double m1 = sc[F_T1L] + t1 * t1len, m2 = sc[F_T2L] + t2 * t2len;
-            ns[F_T1L] = h1 ? m1 : sc[F_T1L]; ns[F_T1H] = h1 ? sc[F_T1H] : m1;
-            ns[F_T2L] = h2 ? m2 : sc[F_T2L]; ns[F_T2H] = h2 ? sc[F_T2H] : m2;
-            ns[F_ALPHA] = sc[F_ALPHA]; ns[F_STATE] = 0;
-            sc[F_STATE] = state + 1;
-            depth++;
-        }
-    }
-    p.res[3 * k] = r0; p.res[3 * k + 1] = r1; p.res[3 * k + 2] = r2;
-    if (p.info) { p.info[4 * k] = nodes; p.info[4 * k + 1] = calls; p.info[4 * k + 2] = dmax; p.info[4 * k + 3] = status; }
-}
-
 // -------------------------------------------------------------------------------------
-//  _minDist with one pair per WAVEFRONT.  The recursion of bezier.py:1283-1408 is sequential per pair
-//  (every child is pruned against the alpha its elder siblings returned), so the parallelism inside a
-//  pair is inside a node: the support scans of gjkNew (support_pts_wave), the two closest-point
+//  The pieces of a node with one pair per WAVEFRONT.  The recursion of bezier.py:1283-1408 is sequential
+//  per pair (every child is pruned against the alpha its elder siblings returned), so the parallelism
+//  inside a pair is inside a node: the support scans of gjkNew (support_pts_wave), the two closest-point
 //  parameters (one curve per half-wave, one hull point per lane) and the six de Casteljau rows of a
-//  child.  Everything else runs redundantly in all lanes with wave-uniform control flow, on the same
-//  device functions as k_min_dist, so results, node and GJK-call counts are those of the one-lane form.
-//  LDS per pair: current node's curves, the next child's curves, the scalar part of every stack frame;
-//  the curve part of the frames stays in the global stack (written once per child, re-read when the
-//  walk comes back to a node to split its next child).
+//  child.  They form the same values, operation for operation, as hull_param and split_row above.
 // -------------------------------------------------------------------------------------
 // np_sum over q(0..n-1) without materialising the vector (same association as np_sum above)
 template <class F>
@@ -1972,6 +1867,270 @@ __device__ __forceinline__ double hull_param_wave(const double* c, int K, const 
     return np_sum(sh_q, K);
 }
 
+// -------------------------------------------------------------------------------------
+//  The depth-first walk of _minDist (bezier.py:1283-1408) and of _minDist2Poly (bezier.py:1411-1496), once each
+//  (md_walk, md2_walk), for the two ways a walk is EXECUTED:
+//   one lane per pair (WAVE = false): a frame of the pair's global stack holds the node's curves and, behind them, its
+//     scalars; hull_param and split_row are the serial ones, a child is split straight into the next frame, and every
+//     store to a frame is a plain store.
+//   one wavefront per pair (WAVE = true): the node being evaluated (`cur`), the child being built (`nxt`) and the scalars
+//     of every frame (`scs`) are in LDS; the curve part of the frames stays in the global stack (written once per child,
+//     fetched again when the walk comes back to a node to split its next child).  Control flow is wave-uniform and every
+//     lane computes the scalars redundantly; what goes to a frame's scalars is lane 0's store between two wave_sync()s
+//     (md_publish).  Same device functions in the same order as the one-lane form: results, node and gjkNew-call counts
+//     are its.
+// -------------------------------------------------------------------------------------
+// the wave form's LDS regions (the one-lane form passes an empty one: it touches none of them)
+struct MdWave {
+    double* cur;                          // curves of the node being evaluated (where the LDS array starts)
+    double* nxt;                          // curves of the child being built
+    double* sh_e;                         // hull_param_wave's distances, a row per half-wave; with sh_q also a split's scratch
+    double* sh_q;
+    double* scs;                          // [max_depth][scalars of a frame]
+};
+
+// info[] of a pair: nodes, gjkNew calls, deepest level, status
+struct MdCounts {
+    int nodes = 0, calls = 0, dmax = 0, status = OBTG_MD_OK;
+};
+
+// node entry: false when the node budget is spent
+__device__ __forceinline__ bool md_enter_node(MdCounts& n, int depth, int max_nodes)
+{
+    if (n.nodes >= max_nodes) { n.status = OBTG_MD_NODE_CAP; return false; }
+    n.nodes++;
+    if (depth + 1 > n.dmax) n.dmax = depth + 1;
+    return true;
+}
+
+// gjkNew on the node's two point sets; false: it ran into a cap of its own
+template <int WAVE, class Mem>
+__device__ __forceinline__ bool md_gjk(const Mem& mem, const Poly& P1, const Poly& P2, int max_iter, int md_cap, MdCounts& n, Result& gr)
+{
+    Ctx<Mem> g;
+    g.mem = mem; g.P1 = P1; g.P2 = P2;
+    g.trace = nullptr; g.trace_cap = 0; g.n_support = 0;
+    gjk::run<Mem, false, WAVE>(g, max_iter, md_cap, gr);
+    n.calls++;
+    if (gr.status == OBTG_ST_MD_CAP || gr.status == OBTG_ST_CYCLE) { n.status = OBTG_MD_GJK_CAP; return false; }
+    return true;
+}
+
+// the parameter interval of piece h (0: left, 1: right) of a curve on [lo, hi] split at t
+__device__ __forceinline__ void md_child_interval(double lo, double hi, double t, int h, double& nlo, double& nhi)
+{
+    const double len = hi - lo, m = lo + t * len;
+    nlo = h ? m : lo; nhi = h ? hi : m;
+}
+
+// a store to a frame's scalars
+template <bool WAVE, class F>
+__device__ __forceinline__ void md_publish(F store)
+{
+    if constexpr (WAVE) {
+        wave_sync();
+        if (threadIdx.x == 0) store();
+        wave_sync();
+    } else store();
+}
+
+// wave form, the walk came back up to a frame: fetch its n doubles of curves into `cur` again
+__device__ __forceinline__ void md_refetch(double* cur, const double* f, int n)
+{
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // other lanes' stores of this frame have landed
+    for (int i = threadIdx.x; i < n; i += kWave) cur[i] = f[i];
+    wave_sync();
+}
+
+#ifdef OBTG_MD_TIMING      // (variant builds: where a node's clocks go -- info[] of k_min_dist_wave, the walk called with CLOCKS,
+                           //  then carries phase totals in units of 1024 clocks; the other kernels keep their counts)
+#define OBTG_TM_START() tm_t = __builtin_readcyclecounter()
+#define OBTG_TM(acc) acc += __builtin_readcyclecounter() - tm_t
+#else
+#define OBTG_TM_START()
+#define OBTG_TM(acc)
+#endif
+
+struct MdOut {
+    double r0 = INFINITY, r1 = -1, r2 = -1;      // (distance, t1, t2)
+    MdCounts n;
+};
+
+__device__ __forceinline__ void md_root_scalars(double* sc)
+{
+    sc[F_T1L] = 0; sc[F_T1H] = 1; sc[F_T2L] = 0; sc[F_T2H] = 1;
+    sc[F_ALPHA] = INFINITY; sc[F_STATE] = 0;
+}
+
+template <class P>
+__device__ __forceinline__ void md_store(const P& p, int k, const MdOut& o)
+{
+    p.res[3 * k] = o.r0; p.res[3 * k + 1] = o.r1; p.res[3 * k + 2] = o.r2;
+    if (p.info) { p.info[4 * k] = o.n.nodes; p.info[4 * k + 1] = o.n.calls; p.info[4 * k + 2] = o.n.dmax; p.info[4 * k + 3] = o.n.status; }
+}
+
+// The walk of one pair of curves c1[3][KA], c2[3][KB] whose frame 0 the kernel has staged: st, the pair's frames in the
+// global stack, 3 (KA + KB) + F_NSCAL doubles each (and, wave form, w.cur and w.scs).  P: MdParams or MdmParams, for the budgets.
+// HASZ: what the hulls of gjkNew are declared with (0: no z row, every z of the call being +0) -- a compile-time value: as a
+// run-time one it cost k_min_dist_mixed 1 % (profiles/mindist_one_walk.json).  (rlA, ilA), (rlB, ilB): wave form, (row, point)
+// = (lane / K, lane % K) of the lane in a level-parallel split of curve 1 / of curve 2.
+// bezier.py never asks that the two curves have one degree: poly1 / poly2 are each curve's own control points, t1 = p1idx[0]
+// / c1.deg and t2 = p2idx[0] / c2.deg, and each curve is split by its own de Casteljau.
+template <bool WAVE, int HASZ, bool CLOCKS = false, class P>
+__device__ __forceinline__ MdOut md_walk(const P& p, int KA, int KB, double* st, const MdWave& w, int rlA, int ilA, int rlB, int ilB)
+{
+    const int lane = threadIdx.x, half = lane >> 5, li = lane & 31;
+    const int KT = KA + KB, FR = 3 * KT + F_NSCAL;
+    double* cur = w.cur;
+    double* nxt = w.nxt;
+    int depth = 0;           // index of the current frame; cnt = depth + 1
+    int cur_depth = 0;       // wave form: which frame's curves `cur` holds
+    MdOut o;                 // r0, r1, r2: the value returned by the frame that just finished
+    bool returning = false;
+#ifdef OBTG_MD_TIMING
+    unsigned long long tm_gjk = 0, tm_eval = 0, tm_desc = 0, tm_fetch = 0, tm_t;
+#endif
+    for (;;) {
+        double* f = st + (size_t)depth * FR;
+        double* sc = WAVE ? w.scs + depth * F_NSCAL : f + 3 * KT;
+        int state = (int)sc[F_STATE];
+        if (!returning && state == 0) {
+            // ---- evaluate this node (bezier.py:1310-1374)
+            if (depth + 1 > 1000) { o.r0 = o.r1 = o.r2 = -1; returning = true; depth--; if (depth < 0) break; continue; }
+            if (!md_enter_node(o.n, depth, p.max_nodes)) break;
+            // wave form: `cur` holds this frame, frame 0 from the kernel, every other one from the descend step
+            const double* c1 = WAVE ? cur : f;
+            const double* c2 = c1 + 3 * KA;
+            const Poly P1{ 0, KA, KA, HASZ }, P2{ 3 * KA, KB, KB, HASZ };
+            Result gr;
+            OBTG_TM_START();
+            bool ok;
+            if constexpr (WAVE) ok = md_gjk<1>(MemLds{ c1 }, P1, P2, p.max_iter, p.md_cap, o.n, gr);
+            else ok = md_gjk<0>(MemGlobal{ c1 }, P1, P2, p.max_iter, p.md_cap, o.n, gr);
+            OBTG_TM(tm_gjk);
+            OBTG_TM_START();
+            if (!ok) break;
+            double lb, t1, t2;
+            if (gr.flag > 0) {
+                lb = gr.dist;
+                if constexpr (WAVE) {            // one curve per half-wave
+                    const double tp = hull_param_wave(c1 + half * 3 * KA, half ? KB : KA, half ? gr.c2 : gr.c1,
+                                                      w.sh_e + half * kMdMaxK, w.sh_q + half * kMdMaxK, li);
+                    t1 = __shfl(tp, 0); t2 = __shfl(tp, 32);
+                } else {
+                    t1 = hull_param(c1, KA, gr.c1);
+                    t2 = hull_param(c2, KB, gr.c2);
+                }
+            } else { t1 = 0.5; t2 = 0.5; lb = p.eps; }
+            int am;
+            const double ub = md_upper_bound<false>(c1, KA, c2, KB, am);
+            const double t1loc = (am >> 1) ? 1.0 : 0.0, t2loc = (am & 1) ? 1.0 : 0.0;
+            double alpha = sc[F_ALPHA], nT1, nT2;
+            if (ub <= alpha) {
+                alpha = ub;
+                nT1 = (1 - t1loc) * sc[F_T1L] + t1loc * sc[F_T1H];
+                nT2 = (1 - t2loc) * sc[F_T2L] + t2loc * sc[F_T2H];
+            } else { nT1 = -1; nT2 = -1; }
+            if (lb >= alpha * (1 - p.eps)) {
+                o.r0 = alpha; o.r1 = nT1; o.r2 = nT2; returning = true; depth--;
+                if (depth < 0) break;
+                continue;
+            }
+            if (depth + 1 >= p.max_depth) { o.n.status = OBTG_MD_DEPTH_CAP; o.r0 = alpha; o.r1 = nT1; o.r2 = nT2; break; }
+            if (t1 != t1) t1 = 0;    // Bezier.split: NaN -> 0 (bezier.py:555-557)
+            if (t2 != t2) t2 = 0;
+            md_publish<WAVE>([&] {
+                sc[F_T1] = t1; sc[F_T2] = t2; sc[F_ALPHA] = alpha; sc[F_RT1] = nT1; sc[F_RT2] = nT2; sc[F_STATE] = 1;
+            });
+            state = 1;
+            OBTG_TM(tm_eval);
+        }
+        if (returning) {
+            // a child of this frame finished: keep the better answer (bezier.py:1384-1406)
+            if (o.r0 < sc[F_ALPHA]) md_publish<WAVE>([&] { sc[F_ALPHA] = o.r0; sc[F_RT1] = o.r1; sc[F_RT2] = o.r2; });
+            returning = false;
+            state = (int)sc[F_STATE];
+        }
+        if (state >= 5) {
+            o.r0 = sc[F_ALPHA]; o.r1 = sc[F_RT1]; o.r2 = sc[F_RT2]; returning = true; depth--;
+            if (depth < 0) break;
+            continue;
+        }
+        // ---- descend into child state-1: (c3,c5) (c3,c6) (c4,c5) (c4,c6)
+        {
+            OBTG_TM_START();
+            if constexpr (WAVE) {
+                if (cur_depth != depth) {
+                    md_refetch(cur, f, 3 * KT);
+                    cur_depth = depth;
+#ifdef OBTG_MD_TIMING
+                    if (cur[0] != cur[0]) tm_fetch += 1;      // (keeps the loads ahead of the stamp)
+                    OBTG_TM(tm_fetch);
+#endif
+                }
+            }
+            const int ch = state - 1, h1 = ch >> 1, h2 = ch & 1;
+            const double t1 = sc[F_T1], t2 = sc[F_T2];
+            double* nf = f + FR;
+            if constexpr (WAVE) {
+                // each curve by its own count: level-parallel over its three rows where they fit a wavefront (3 K <= 64), else a
+                // lane per row -- lanes 0..2 curve 1, lanes 3..5 curve 2.  The two curves write disjoint ranges of nxt and of the
+                // scratch (sh_e .. : 6 kMdMaxK doubles, idle here; curve 1 the first half, curve 2 the second), so nothing orders
+                // them against each other.
+                const bool parA = 3 * KA <= kWave, parB = 3 * KB <= kWave;
+                if (parA) split_rows3_wave(cur, KA, t1, h1, nxt, rlA, ilA, w.sh_e);
+                if (parB) split_rows3_wave(cur + 3 * KA, KB, t2, h2, nxt + 3 * KA, rlB, ilB, w.sh_e + 3 * kMdMaxK);
+                if (lane < 6 && !(lane < 3 ? parA : parB)) {
+                    const bool second = lane >= 3;
+                    const int r = second ? lane - 3 : lane, Kr = second ? KB : KA, c = (second ? 3 * KA : 0) + r * Kr;
+                    split_row_lds(cur + c, Kr, second ? t2 : t1, second ? h2 : h1, nxt + c, w.sh_e + (second ? 3 * kMdMaxK : 0) + r * Kr);
+                }
+                wave_sync();
+                for (int i = lane; i < 3 * KT; i += kWave) nf[i] = nxt[i];
+            } else {
+                for (int c = 0; c < 3; ++c) {
+                    split_row(f + c * KA, KA, t1, h1, nf + c * KA);
+                    split_row(f + 3 * KA + c * KB, KB, t2, h2, nf + 3 * KA + c * KB);
+                }
+            }
+            double n1l, n1h, n2l, n2h;
+            md_child_interval(sc[F_T1L], sc[F_T1H], t1, h1, n1l, n1h);
+            md_child_interval(sc[F_T2L], sc[F_T2H], t2, h2, n2l, n2h);
+            const double a_in = sc[F_ALPHA];
+            double* ns = WAVE ? sc + F_NSCAL : nf + 3 * KT;
+            md_publish<WAVE>([&] {
+                ns[F_T1L] = n1l; ns[F_T1H] = n1h; ns[F_T2L] = n2l; ns[F_T2H] = n2h;
+                ns[F_ALPHA] = a_in; ns[F_STATE] = 0;
+                sc[F_STATE] = state + 1;
+            });
+            // wave form: the child is evaluated next, its curves become `cur`
+            double* tsw = cur; cur = nxt; nxt = tsw;
+            depth++;
+            cur_depth = depth;
+            OBTG_TM(tm_desc);
+        }
+    }
+#ifdef OBTG_MD_TIMING
+    if constexpr (CLOCKS) {
+        o.n.calls = (int)(tm_gjk >> 10); o.n.dmax = (int)(tm_eval >> 10); o.n.status = (int)(tm_desc >> 10) | ((int)(tm_fetch >> 10) << 16);
+    }
+#endif
+    return o;
+}
+
+__global__ __launch_bounds__(64) void k_min_dist(const MdParams p)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= p.n_pairs) return;
+    const int K = p.K;
+    double* st = p.stack + (size_t)k * p.max_depth * (6 * K + F_NSCAL);
+    const double* ca = p.curves + (size_t)p.pa[k] * 3 * K;
+    const double* cb = p.curves + (size_t)p.pb[k] * 3 * K;
+    for (int i = 0; i < 3 * K; ++i) { st[i] = ca[i]; st[3 * K + i] = cb[i]; }
+    md_root_scalars(st + 6 * K);
+    md_store(p, k, md_walk<false, 1>(p, K, K, st, MdWave{}, 0, 0, 0, 0));
+}
+
 // Round 5: the waves are WORKERS.  A pair's search costs anything from one gjkNew call to max_nodes nodes of four, and a
 // launch of one single-wave workgroup per pair, all resident at once, lasts as long as the SIMD that happened to receive the
 // most long pairs (C5-sized sweep, PMC: VALU 23 % busy over the launch, profiles/r05_mindist_pmc_before.txt).  Now a fixed
@@ -1982,13 +2141,20 @@ __device__ __forceinline__ double hull_param_wave(const double* c, int K, const 
 #ifndef OBTG_MD_MIN_WAVES
 #define OBTG_MD_MIN_WAVES 2     // worker waves per SIMD the register allocation is held to (launch bound's second argument)
 #endif
+// Equal degree: every curve of the call has K control points, and the hulls keep their z row (hasz = 1) for planar input too.
 __global__ __launch_bounds__(64, OBTG_MD_MIN_WAVES) void k_min_dist_wave(const MdParams p)
 {
     extern __shared__ double md_lds[];
-    const int lane = threadIdx.x, half = lane >> 5, li = lane & 31;
-    const int K = p.K, FR = 6 * K + F_NSCAL;
-    const int rl = lane / K, il = lane - rl * K;          // (row, point) of the lane in the level-parallel splits
-    double* st = p.stack + (size_t)blockIdx.x * p.max_depth * FR;
+    const int lane = threadIdx.x;
+    const int K = p.K;
+    const int rl = lane / K, il = lane - rl * K;          // (row, point) of the lane in the level-parallel splits, once per launch
+    double* st = p.stack + (size_t)blockIdx.x * p.max_depth * (6 * K + F_NSCAL);
+    MdWave w;
+    w.cur = md_lds;                             // [6K]
+    w.nxt = w.cur + 6 * K;                      // [6K]
+    w.sh_e = w.nxt + 6 * K;                     // [2][kMdMaxK]; with sh_q also the six scratch rows of a split
+    w.sh_q = w.sh_e + 2 * kMdMaxK;              // [2][kMdMaxK] (+ 2 more rows so that 6 K doubles fit)
+    w.scs = w.sh_q + 4 * kMdMaxK;               // [max_depth][F_NSCAL]
   for (;;) {
     // The pull must not hang on a lane-dependent branch.  The first form -- `if (lane == 0) slot = atomicAdd(queue, 1);
     // slot = __shfl(slot, 0);`, with `if (lane == 0) { write the results }` as the loop's last statement -- was compiled
@@ -2003,178 +2169,23 @@ __global__ __launch_bounds__(64, OBTG_MD_MIN_WAVES) void k_min_dist_wave(const M
     if (slot >= p.n_pairs) break;                // every worker ends here: the queue only grows
     const int k = p.order ? p.order[slot] : slot;
     __syncthreads();                             // (one wave per workgroup: the previous pair's LDS reads are done)
-    double* cur = md_lds;                       // [6K] curves of the node being evaluated
-    double* nxt = cur + 6 * K;                  // [6K] curves of the child being built
-    double* sh_e = nxt + 6 * K;                 // [2][kMdMaxK]; with sh_q also the six scratch rows of a split
-    double* sh_q = sh_e + 2 * kMdMaxK;          // [2][kMdMaxK] (+ 2 more rows so that 6 K doubles fit)
-    double* scs = sh_q + 4 * kMdMaxK;           // [max_depth][F_NSCAL] frame scalars
     const double* ca = p.curves + (size_t)p.pa[k] * 3 * K;
     const double* cb = p.curves + (size_t)p.pb[k] * 3 * K;
     for (int i = lane; i < 3 * K; i += kWave) {
         const double a = ca[i], bq = cb[i];
-        st[i] = a; st[3 * K + i] = bq; cur[i] = a; cur[3 * K + i] = bq;
+        st[i] = a; st[3 * K + i] = bq; w.cur[i] = a; w.cur[3 * K + i] = bq;
     }
-    if (lane == 0) {
-        scs[F_T1L] = 0; scs[F_T1H] = 1; scs[F_T2L] = 0; scs[F_T2H] = 1;
-        scs[F_ALPHA] = INFINITY; scs[F_STATE] = 0;
-    }
+    if (lane == 0) md_root_scalars(w.scs);
     __syncthreads();
-    int depth = 0, cur_depth = 0;     // cur_depth: which frame's curves `cur` holds
-    int nodes = 0, calls = 0, dmax = 0, status = OBTG_MD_OK;
-    double r0 = INFINITY, r1 = -1, r2 = -1;
-    bool returning = false;
-#ifdef OBTG_MD_TIMING      // (variant builds: where a node's clocks go -- info[] then carries phase totals in units of 1024 clocks)
-    unsigned long long tm_gjk = 0, tm_eval = 0, tm_desc = 0, tm_fetch = 0, tm_t;
-#define OBTG_TM(acc, t0) acc += __builtin_readcyclecounter() - (t0)
-#else
-#define OBTG_TM(acc, t0)
-#endif
-    for (;;) {
-        double* f = st + (size_t)depth * FR;
-        double* sc = scs + depth * F_NSCAL;
-        int state = (int)sc[F_STATE];
-        if (!returning && state == 0) {
-            if (depth + 1 > 1000) { r0 = r1 = r2 = -1; returning = true; depth--; if (depth < 0) break; continue; }
-            if (nodes >= p.max_nodes) { status = OBTG_MD_NODE_CAP; break; }
-            nodes++;
-            if (depth + 1 > dmax) dmax = depth + 1;
-            // `cur` holds this frame: frame 0 from the prologue, every other one from the descend step
-            Ctx<MemLds> g;
-            g.mem = MemLds{ cur };
-            g.P1 = Poly{ 0, K, K, 1 };
-            g.P2 = Poly{ 3 * K, K, K, 1 };
-            g.trace = nullptr; g.trace_cap = 0; g.n_support = 0;
-            Result gr;
-#ifdef OBTG_MD_TIMING
-            tm_t = __builtin_readcyclecounter();
-#endif
-            gjk::run<MemLds, false, true>(g, p.max_iter, p.md_cap, gr);
-            OBTG_TM(tm_gjk, tm_t);
-#ifdef OBTG_MD_TIMING
-            tm_t = __builtin_readcyclecounter();
-#endif
-            calls++;
-            if (gr.status == OBTG_ST_MD_CAP || gr.status == OBTG_ST_CYCLE) { status = OBTG_MD_GJK_CAP; break; }
-            double lb, t1, t2;
-            if (gr.flag > 0) {
-                lb = gr.dist;
-                const double tp = hull_param_wave(cur + half * 3 * K, K, half ? gr.c2 : gr.c1, sh_e + half * kMdMaxK,
-                                                  sh_q + half * kMdMaxK, li);
-                t1 = __shfl(tp, 0); t2 = __shfl(tp, 32);
-            } else { t1 = 0.5; t2 = 0.5; lb = p.eps; }
-            const double* c1 = cur; const double* c2 = cur + 3 * K;
-            double dd[4];
-            dd[0] = norm_seq(c1[0], c1[K], c1[2 * K], c2[0], c2[K], c2[2 * K]);
-            dd[1] = norm_seq(c1[0], c1[K], c1[2 * K], c2[K - 1], c2[2 * K - 1], c2[3 * K - 1]);
-            dd[2] = norm_seq(c1[K - 1], c1[2 * K - 1], c1[3 * K - 1], c2[0], c2[K], c2[2 * K]);
-            dd[3] = norm_seq(c1[K - 1], c1[2 * K - 1], c1[3 * K - 1], c2[K - 1], c2[2 * K - 1], c2[3 * K - 1]);
-            int am = 0;
-            for (int i = 1; i < 4; ++i) if (dd[i] < dd[am]) am = i;
-            for (int i = 0; i < 4; ++i) if (dd[i] != dd[i]) { am = i; break; }
-            const double ub = dd[am], t1loc = (am >> 1) ? 1.0 : 0.0, t2loc = (am & 1) ? 1.0 : 0.0;
-            double alpha = sc[F_ALPHA], nT1, nT2;
-            if (ub <= alpha) {
-                alpha = ub;
-                nT1 = (1 - t1loc) * sc[F_T1L] + t1loc * sc[F_T1H];
-                nT2 = (1 - t2loc) * sc[F_T2L] + t2loc * sc[F_T2H];
-            } else { nT1 = -1; nT2 = -1; }
-            if (lb >= alpha * (1 - p.eps)) {
-                r0 = alpha; r1 = nT1; r2 = nT2; returning = true; depth--;
-                if (depth < 0) break;
-                continue;
-            }
-            if (depth + 1 >= p.max_depth) { status = OBTG_MD_DEPTH_CAP; r0 = alpha; r1 = nT1; r2 = nT2; break; }
-            if (t1 != t1) t1 = 0;
-            if (t2 != t2) t2 = 0;
-            wave_sync();
-            if (lane == 0) {
-                sc[F_T1] = t1; sc[F_T2] = t2; sc[F_ALPHA] = alpha; sc[F_RT1] = nT1; sc[F_RT2] = nT2; sc[F_STATE] = 1;
-            }
-            wave_sync();
-            state = 1;
-            OBTG_TM(tm_eval, tm_t);
-        }
-        if (returning) {
-            if (r0 < sc[F_ALPHA]) {
-                wave_sync();
-                if (lane == 0) { sc[F_ALPHA] = r0; sc[F_RT1] = r1; sc[F_RT2] = r2; }
-                wave_sync();
-            }
-            returning = false;
-            state = (int)sc[F_STATE];
-        }
-        if (state >= 5) {
-            r0 = sc[F_ALPHA]; r1 = sc[F_RT1]; r2 = sc[F_RT2]; returning = true; depth--;
-            if (depth < 0) break;
-            continue;
-        }
-        // ---- descend into child state-1: (c3,c5) (c3,c6) (c4,c5) (c4,c6)
-        {
-#ifdef OBTG_MD_TIMING
-            tm_t = __builtin_readcyclecounter();
-#endif
-            if (cur_depth != depth) {            // the walk came back up: fetch this frame's curves again
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // other lanes' stores of this frame have landed
-                for (int i = lane; i < 6 * K; i += kWave) cur[i] = f[i];
-                cur_depth = depth;
-                wave_sync();
-#ifdef OBTG_MD_TIMING
-                if (cur[0] != cur[0]) tm_fetch += 1;      // (keeps the loads ahead of the stamp)
-                OBTG_TM(tm_fetch, tm_t);
-#endif
-            }
-            const int ch = state - 1, h1 = ch >> 1, h2 = ch & 1;
-            const double t1 = sc[F_T1], t2 = sc[F_T2];
-            double* nf = f + FR;
-            if (3 * K <= kWave) {                 // rows 0..2: curve 1 (x, y, z), rows 3..5: curve 2; level-parallel
-                split_rows3_wave(cur, K, t1, h1, nxt, rl, il, sh_e);                 // (sh_e: 64 doubles, idle here)
-                split_rows3_wave(cur + 3 * K, K, t2, h2, nxt + 3 * K, rl, il, sh_e);
-            } else if (lane < 6) {
-                const bool second = lane >= 3;
-                split_row_lds(cur + lane * K, K, second ? t2 : t1, second ? h2 : h1, nxt + lane * K, sh_e + lane * K);
-            }
-            wave_sync();
-            for (int i = lane; i < 6 * K; i += kWave) nf[i] = nxt[i];
-            const double t1len = sc[F_T1H] - sc[F_T1L], t2len = sc[F_T2H] - sc[F_T2L];
-            const double m1 = sc[F_T1L] + t1 * t1len, m2 = sc[F_T2L] + t2 * t2len;
-            const double a_in = sc[F_ALPHA];
-            const double n1l = h1 ? m1 : sc[F_T1L], n1h = h1 ? sc[F_T1H] : m1;
-            const double n2l = h2 ? m2 : sc[F_T2L], n2h = h2 ? sc[F_T2H] : m2;
-            wave_sync();
-            if (lane == 0) {
-                double* ns = sc + F_NSCAL;
-                ns[F_T1L] = n1l; ns[F_T1H] = n1h; ns[F_T2L] = n2l; ns[F_T2H] = n2h;
-                ns[F_ALPHA] = a_in; ns[F_STATE] = 0;
-                sc[F_STATE] = state + 1;
-            }
-            // the child is evaluated next: its curves become `cur`
-            double* tsw = cur; cur = nxt; nxt = tsw;
-            depth++;
-            cur_depth = depth;
-            wave_sync();
-            OBTG_TM(tm_desc, tm_t);
-        }
-    }
-#ifdef OBTG_MD_TIMING
-    calls = (int)(tm_gjk >> 10); dmax = (int)(tm_eval >> 10); status = (int)(tm_desc >> 10) | ((int)(tm_fetch >> 10) << 16);
-#endif
     // (every lane, the same values to the same addresses: see the pull above)
-    p.res[3 * k] = r0; p.res[3 * k + 1] = r1; p.res[3 * k + 2] = r2;
-    if (p.info) { p.info[4 * k] = nodes; p.info[4 * k + 1] = calls; p.info[4 * k + 2] = dmax; p.info[4 * k + 3] = status; }
+    md_store(p, k, md_walk<true, 1, true>(p, K, K, st, w, rl, il, rl, il));
   }
 }
 
-// ---- _minDist on curves of DIFFERENT degree: k_min_dist_wave with a control-point count per curve --------------------
-// bezier.py:1283-1408 never asks that the two curves have one degree: poly1 / poly2 are each curve's own control points,
-// t1 = p1idx[0] / c1.deg and t2 = p2idx[0] / c2.deg, and each curve is split by its own de Casteljau.  Here a curve is
-// cpts + 3 * off[i], [3][K_i] with K_i = off[i + 1] - off[i], and a pair's node is c1[3 KA] c2[3 KB].  Everything of
-// k_min_dist_wave that was one K is now per curve: the two hulls of gjkNew (support_pts_wave already scans P1.K and P2.K
-// points in its two half-waves), the half-wave's hull_param_wave (its exact branch i / (K - 1), its weighted one W i / K),
-// the lane maps of the level-parallel split (rl = lane / K, il = lane - rl K: one pair of maps per curve) and the frame,
-// 3 (KA + KB) + F_NSCAL doubles.  The workers take pairs of different sizes from one queue, so a worker's LDS and its
-// frame stack are laid out for the call's largest KA + KB (kt_max: mdm_launch, the one place that sizes both); a pair's
-// own frames are packed at its own stride inside that.  The device functions are k_min_dist_wave's, in its order, so a
-// pair's result, node and gjkNew-call counts are those of the one-lane recursion with (KA, KB).
+// Curves of DIFFERENT degree: curve i is cpts + 3 * off[i], [3][K_i] with K_i = off[i + 1] - off[i], and a pair's node is
+// c1[3 KA] c2[3 KB].  The workers take pairs of different sizes from one queue, so a worker's LDS and its frame stack are
+// laid out for the call's largest KA + KB (kt_max: mdm_launch, the one place that sizes both); a pair's own frames are
+// packed at its own stride inside that.
 // planar (every z of the call is +0): the hulls are declared without a z row (Poly::hasz = 0), which drops the z loads of
 // the support scans and of `point`; sdot then forms x dx + y dy + 0 dz from the literal 0 instead of the stored one: the
 // same operands, so the same bits.
@@ -2195,13 +2206,16 @@ struct MdmParams {
 __global__ __launch_bounds__(64, OBTG_MD_MIN_WAVES) void k_min_dist_mixed(const MdmParams p)
 {
     extern __shared__ double md_lds[];
-    const int lane = threadIdx.x, half = lane >> 5, li = lane & 31;
+    const int lane = threadIdx.x;
     double* st = p.stack + (size_t)blockIdx.x * p.max_depth * (3 * p.kt_max + F_NSCAL);
-    double* sh_e = md_lds + 6 * p.kt_max;       // [2][kMdMaxK]; with sh_q also the scratch rows of a split
-    double* sh_q = sh_e + 2 * kMdMaxK;          // [2][kMdMaxK] (+ 2 more rows: 6 kMdMaxK doubles hold six scratch rows of any K)
-    double* scs = sh_q + 4 * kMdMaxK;           // [max_depth][F_NSCAL] frame scalars
+    MdWave w;
+    w.cur = md_lds;                             // [3 KT]
+    w.nxt = w.cur + 3 * p.kt_max;               // [3 KT]
+    w.sh_e = md_lds + 6 * p.kt_max;             // [2][kMdMaxK]; with sh_q also the scratch rows of a split
+    w.sh_q = w.sh_e + 2 * kMdMaxK;              // [2][kMdMaxK] (+ 2 more rows: 6 kMdMaxK doubles hold six scratch rows of any K)
+    w.scs = w.sh_q + 4 * kMdMaxK;               // [max_depth][F_NSCAL]
   for (;;) {
-    // (every lane issues the atomic and every lane stores the results: see the queue pull of k_min_dist_wave)
+    // (the pull and the stores of k_min_dist_wave, for its reason)
     const int ticket = atomicAdd(p.queue, lane == 0 ? 1 : 0);
     const int slot = __builtin_amdgcn_readfirstlane(ticket);
     if (slot >= p.n_pairs) break;
@@ -2209,142 +2223,16 @@ __global__ __launch_bounds__(64, OBTG_MD_MIN_WAVES) void k_min_dist_mixed(const 
     __syncthreads();                             // (one wave per workgroup: the previous pair's LDS reads are done)
     const int ia = p.pa[k], ib = p.pb[k];
     const int oa = p.off[ia], ob = p.off[ib];
-    const int KA = p.off[ia + 1] - oa, KB = p.off[ib + 1] - ob, KT = KA + KB, FR = 3 * KT + F_NSCAL;
-    const int rlA = lane / KA, ilA = lane - rlA * KA;     // (row, point) of the lane in curve 1's level-parallel split
-    const int rlB = lane / KB, ilB = lane - rlB * KB;     // ... and in curve 2's
-    const int Kh = half ? KB : KA;                        // the half-wave's curve in the parameter searches
-    double* cur = md_lds;                       // [3 KT] curves of the node being evaluated
-    double* nxt = cur + 3 * p.kt_max;           // [3 KT] curves of the child being built
+    const int KA = p.off[ia + 1] - oa, KB = p.off[ib + 1] - ob;
+    const int rlA = lane / KA, ilA = lane - rlA * KA;
+    const int rlB = lane / KB, ilB = lane - rlB * KB;
     const double* ca = p.cpts + (size_t)3 * oa;
     const double* cb = p.cpts + (size_t)3 * ob;
-    for (int i = lane; i < 3 * KA; i += kWave) { const double a = ca[i]; st[i] = a; cur[i] = a; }
-    for (int i = lane; i < 3 * KB; i += kWave) { const double b = cb[i]; st[3 * KA + i] = b; cur[3 * KA + i] = b; }
-    if (lane == 0) {
-        scs[F_T1L] = 0; scs[F_T1H] = 1; scs[F_T2L] = 0; scs[F_T2H] = 1;
-        scs[F_ALPHA] = INFINITY; scs[F_STATE] = 0;
-    }
+    for (int i = lane; i < 3 * KA; i += kWave) { const double a = ca[i]; st[i] = a; w.cur[i] = a; }
+    for (int i = lane; i < 3 * KB; i += kWave) { const double b = cb[i]; st[3 * KA + i] = b; w.cur[3 * KA + i] = b; }
+    if (lane == 0) md_root_scalars(w.scs);
     __syncthreads();
-    int depth = 0, cur_depth = 0;     // cur_depth: which frame's curves `cur` holds
-    int nodes = 0, calls = 0, dmax = 0, status = OBTG_MD_OK;
-    double r0 = INFINITY, r1 = -1, r2 = -1;
-    bool returning = false;
-    for (;;) {
-        double* f = st + (size_t)depth * FR;
-        double* sc = scs + depth * F_NSCAL;
-        int state = (int)sc[F_STATE];
-        if (!returning && state == 0) {
-            if (depth + 1 > 1000) { r0 = r1 = r2 = -1; returning = true; depth--; if (depth < 0) break; continue; }
-            if (nodes >= p.max_nodes) { status = OBTG_MD_NODE_CAP; break; }
-            nodes++;
-            if (depth + 1 > dmax) dmax = depth + 1;
-            Ctx<MemLds> g;
-            g.mem = MemLds{ cur };
-            g.P1 = Poly{ 0, KA, KA, p.planar ? 0 : 1 };
-            g.P2 = Poly{ 3 * KA, KB, KB, p.planar ? 0 : 1 };
-            g.trace = nullptr; g.trace_cap = 0; g.n_support = 0;
-            Result gr;
-            gjk::run<MemLds, false, true>(g, p.max_iter, p.md_cap, gr);
-            calls++;
-            if (gr.status == OBTG_ST_MD_CAP || gr.status == OBTG_ST_CYCLE) { status = OBTG_MD_GJK_CAP; break; }
-            double lb, t1, t2;
-            if (gr.flag > 0) {
-                lb = gr.dist;
-                const double tp = hull_param_wave(cur + half * 3 * KA, Kh, half ? gr.c2 : gr.c1, sh_e + half * kMdMaxK,
-                                                  sh_q + half * kMdMaxK, li);
-                t1 = __shfl(tp, 0); t2 = __shfl(tp, 32);
-            } else { t1 = 0.5; t2 = 0.5; lb = p.eps; }
-            // _upperbound (bezier.py:1499-1516): the four end-point pairs
-            const double* c1 = cur; const double* c2 = cur + 3 * KA;
-            double dd[4];
-            dd[0] = norm_seq(c1[0], c1[KA], c1[2 * KA], c2[0], c2[KB], c2[2 * KB]);
-            dd[1] = norm_seq(c1[0], c1[KA], c1[2 * KA], c2[KB - 1], c2[2 * KB - 1], c2[3 * KB - 1]);
-            dd[2] = norm_seq(c1[KA - 1], c1[2 * KA - 1], c1[3 * KA - 1], c2[0], c2[KB], c2[2 * KB]);
-            dd[3] = norm_seq(c1[KA - 1], c1[2 * KA - 1], c1[3 * KA - 1], c2[KB - 1], c2[2 * KB - 1], c2[3 * KB - 1]);
-            int am = 0;
-            for (int i = 1; i < 4; ++i) if (dd[i] < dd[am]) am = i;
-            for (int i = 0; i < 4; ++i) if (dd[i] != dd[i]) { am = i; break; }
-            const double ub = dd[am], t1loc = (am >> 1) ? 1.0 : 0.0, t2loc = (am & 1) ? 1.0 : 0.0;
-            double alpha = sc[F_ALPHA], nT1, nT2;
-            if (ub <= alpha) {
-                alpha = ub;
-                nT1 = (1 - t1loc) * sc[F_T1L] + t1loc * sc[F_T1H];
-                nT2 = (1 - t2loc) * sc[F_T2L] + t2loc * sc[F_T2H];
-            } else { nT1 = -1; nT2 = -1; }
-            if (lb >= alpha * (1 - p.eps)) {
-                r0 = alpha; r1 = nT1; r2 = nT2; returning = true; depth--;
-                if (depth < 0) break;
-                continue;
-            }
-            if (depth + 1 >= p.max_depth) { status = OBTG_MD_DEPTH_CAP; r0 = alpha; r1 = nT1; r2 = nT2; break; }
-            if (t1 != t1) t1 = 0;    // Bezier.split: NaN -> 0 (bezier.py:555-557)
-            if (t2 != t2) t2 = 0;
-            wave_sync();
-            if (lane == 0) {
-                sc[F_T1] = t1; sc[F_T2] = t2; sc[F_ALPHA] = alpha; sc[F_RT1] = nT1; sc[F_RT2] = nT2; sc[F_STATE] = 1;
-            }
-            wave_sync();
-            state = 1;
-        }
-        if (returning) {
-            if (r0 < sc[F_ALPHA]) {
-                wave_sync();
-                if (lane == 0) { sc[F_ALPHA] = r0; sc[F_RT1] = r1; sc[F_RT2] = r2; }
-                wave_sync();
-            }
-            returning = false;
-            state = (int)sc[F_STATE];
-        }
-        if (state >= 5) {
-            r0 = sc[F_ALPHA]; r1 = sc[F_RT1]; r2 = sc[F_RT2]; returning = true; depth--;
-            if (depth < 0) break;
-            continue;
-        }
-        // ---- descend into child state-1: (c3,c5) (c3,c6) (c4,c5) (c4,c6)
-        {
-            if (cur_depth != depth) {            // the walk came back up: fetch this frame's curves again
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // other lanes' stores of this frame have landed
-                for (int i = lane; i < 3 * KT; i += kWave) cur[i] = f[i];
-                cur_depth = depth;
-                wave_sync();
-            }
-            const int ch = state - 1, h1 = ch >> 1, h2 = ch & 1;
-            const double t1 = sc[F_T1], t2 = sc[F_T2];
-            double* nf = f + FR;
-            // each curve by its own count: level-parallel over its three rows where they fit a wavefront (3 K <= 64), else a
-            // lane per row -- lanes 0..2 curve 1, lanes 3..5 curve 2, side by side as in k_min_dist_wave.  The two curves write
-            // disjoint ranges of nxt and of the scratch (sh_e .. : 6 kMdMaxK doubles, idle here; curve 1 the first half, curve 2
-            // the second), so nothing orders them against each other.
-            const bool parA = 3 * KA <= kWave, parB = 3 * KB <= kWave;
-            if (parA) split_rows3_wave(cur, KA, t1, h1, nxt, rlA, ilA, sh_e);
-            if (parB) split_rows3_wave(cur + 3 * KA, KB, t2, h2, nxt + 3 * KA, rlB, ilB, sh_e + 3 * kMdMaxK);
-            if (lane < 6 && !(lane < 3 ? parA : parB)) {
-                const bool second = lane >= 3;
-                const int r = second ? lane - 3 : lane, Kr = second ? KB : KA, o = (second ? 3 * KA : 0) + r * Kr;
-                split_row_lds(cur + o, Kr, second ? t2 : t1, second ? h2 : h1, nxt + o, sh_e + (second ? 3 * kMdMaxK : 0) + r * Kr);
-            }
-            wave_sync();
-            for (int i = lane; i < 3 * KT; i += kWave) nf[i] = nxt[i];
-            const double t1len = sc[F_T1H] - sc[F_T1L], t2len = sc[F_T2H] - sc[F_T2L];
-            const double m1 = sc[F_T1L] + t1 * t1len, m2 = sc[F_T2L] + t2 * t2len;
-            const double a_in = sc[F_ALPHA];
-            const double n1l = h1 ? m1 : sc[F_T1L], n1h = h1 ? sc[F_T1H] : m1;
-            const double n2l = h2 ? m2 : sc[F_T2L], n2h = h2 ? sc[F_T2H] : m2;
-            wave_sync();
-            if (lane == 0) {
-                double* ns = sc + F_NSCAL;
-                ns[F_T1L] = n1l; ns[F_T1H] = n1h; ns[F_T2L] = n2l; ns[F_T2H] = n2h;
-                ns[F_ALPHA] = a_in; ns[F_STATE] = 0;
-                sc[F_STATE] = state + 1;
-            }
-            // the child is evaluated next: its curves become `cur`
-            double* tsw = cur; cur = nxt; nxt = tsw;
-            depth++;
-            cur_depth = depth;
-            wave_sync();
-        }
-    }
-    p.res[3 * k] = r0; p.res[3 * k + 1] = r1; p.res[3 * k + 2] = r2;
-    if (p.info) { p.info[4 * k] = nodes; p.info[4 * k + 1] = calls; p.info[4 * k + 2] = dmax; p.info[4 * k + 3] = status; }
+    md_store(p, k, p.planar ? md_walk<true, 0>(p, KA, KB, st, w, rlA, ilA, rlB, ilB) : md_walk<true, 1>(p, KA, KB, st, w, rlA, ilA, rlB, ilB));
   }
 }
 
@@ -2660,28 +2548,9 @@ __device__ __forceinline__ void md_eval_rows(const double* lds, int o1, int o2, 
     tm[1] += __builtin_readcyclecounter() - tq1;
     const unsigned long long tq2 = __builtin_readcyclecounter();
 #endif
-    double dd[4];
-    if constexpr (PLANAR) {          // (norm_seq with dz = 0: s + 0 * 0 = s)
-        auto n2 = [](double ax, double ay, double bx, double by) {
-            const double dx = ax - bx, dy = ay - by;
-            double s = 0.0;
-            s += dx * dx; s += dy * dy;
-            return __builtin_sqrt(s);
-        };
-        dd[0] = n2(c1[0], c1[K], c2[0], c2[K]);
-        dd[1] = n2(c1[0], c1[K], c2[K - 1], c2[2 * K - 1]);
-        dd[2] = n2(c1[K - 1], c1[2 * K - 1], c2[0], c2[K]);
-        dd[3] = n2(c1[K - 1], c1[2 * K - 1], c2[K - 1], c2[2 * K - 1]);
-    } else {
-        dd[0] = norm_seq(c1[0], c1[K], c1[2 * K], c2[0], c2[K], c2[2 * K]);
-        dd[1] = norm_seq(c1[0], c1[K], c1[2 * K], c2[K - 1], c2[2 * K - 1], c2[3 * K - 1]);
-        dd[2] = norm_seq(c1[K - 1], c1[2 * K - 1], c1[3 * K - 1], c2[0], c2[K], c2[2 * K]);
-        dd[3] = norm_seq(c1[K - 1], c1[2 * K - 1], c1[3 * K - 1], c2[K - 1], c2[2 * K - 1], c2[3 * K - 1]);
-    }
-    int am = 0;
-    for (int i = 1; i < 4; ++i) if (dd[i] < dd[am]) am = i;
-    for (int i = 0; i < 4; ++i) if (dd[i] != dd[i]) { am = i; break; }
-    rec[R_CAP] = cap ? 1.0 : 0.0; rec[R_LB] = lb; rec[R_T1] = t1; rec[R_T2] = t2; rec[R_UB] = dd[am]; rec[R_AM] = (double)am;
+    int am;
+    const double ub = md_upper_bound<PLANAR>(c1, K, c2, K, am);
+    rec[R_CAP] = cap ? 1.0 : 0.0; rec[R_LB] = lb; rec[R_T1] = t1; rec[R_T2] = t2; rec[R_UB] = ub; rec[R_AM] = (double)am;
 #ifdef OBTG_MD_TIMING
     wave_sync();
     if (rec[R_UB] == -1.0) rec[R_CAP] = 0.0;
@@ -3319,12 +3188,125 @@ struct MemTwo {   // indices below kPolyBias address the stack frame, the rest t
     }
 };
 
+struct Md2Out {
+    double r0 = INFINITY, r1 = -1, rx = -1, ry = -1, rz = -1;      // (distance, t, the polygon's closest point)
+    MdCounts n;
+};
+
+__device__ __forceinline__ void md2_store(const Md2Params& p, int k, const Md2Out& o)
+{
+    p.res[5 * k] = o.r0; p.res[5 * k + 1] = o.r1; p.res[5 * k + 2] = o.rx; p.res[5 * k + 3] = o.ry; p.res[5 * k + 4] = o.rz;
+    if (p.info) { p.info[4 * k] = o.n.nodes; p.info[4 * k + 1] = o.n.calls; p.info[4 * k + 2] = o.n.dmax; p.info[4 * k + 3] = o.n.status; }
+}
+
+// The walk of one (curve, polygon) pair (bezier.py:1411-1496) whose frame 0 the kernel has staged, in the two executions of
+// md_walk: a node is the curve alone, c1[3][K], with two children; the polygon (PK vertices from vertex po of the table) never
+// changes.  One lane per pair: gjkNew reads it from the table (MemTwo).  One wavefront per pair: the kernel has copied it to
+// LDS once (pol: [3][kMdMaxK]), and w.sh_e .. is 4 kMdMaxK doubles, one half-wave's hull_param_wave rows or a split's scratch.
+template <bool WAVE>
+__device__ __forceinline__ Md2Out md2_walk(const Md2Params& p, int K, int po, int PK, double* st, const MdWave& w, const double* pol,
+                                               int rl, int il)
+{
+    const int lane = threadIdx.x, li = lane & 31;
+    const int FR = 3 * K + G_NSCAL;
+    const double* lds = w.cur;
+    double* cur = w.cur;
+    double* nxt = w.nxt;
+    int depth = 0, cur_depth = 0;
+    Md2Out o;
+    bool returning = false;
+    for (;;) {
+        double* f = st + (size_t)depth * FR;
+        double* sc = WAVE ? w.scs + depth * G_NSCAL : f + 3 * K;
+        int state = (int)sc[G_STATE];
+        if (!returning && state == 0) {
+            if (depth + 1 > 1000) { o.r0 = o.r1 = o.rx = -1; o.ry = o.rz = -1; returning = true; depth--; if (depth < 0) break; continue; }
+            if (!md_enter_node(o.n, depth, p.max_nodes)) break;
+            const double* c1 = WAVE ? cur : f;
+            Result gr;
+            bool ok;
+            if constexpr (WAVE)
+                ok = md_gjk<1>(MemLds{ lds }, Poly{ (int)(cur - lds), K, K, 1 }, Poly{ (int)(pol - lds), kMdMaxK, PK, 1 }, p.max_iter,
+                               p.md_cap, o.n, gr);
+            else
+                ok = md_gjk<0>(MemTwo{ f, p.soa }, Poly{ 0, K, K, 1 }, Poly{ kPolyBias + 3 * po, PK, PK, 1 }, p.max_iter, p.md_cap, o.n, gr);
+            if (!ok) break;
+            double lb, t1, nT1, alpha = sc[G_ALPHA];
+            double cx, cy, cz;
+            if (gr.flag > 0) {
+                lb = gr.dist;
+                if constexpr (WAVE) t1 = __shfl(hull_param_wave(c1, K, gr.c1, w.sh_e, w.sh_q, lane < 32 ? li : kMdMaxK), 0);
+                else t1 = hull_param(c1, K, gr.c1);
+                cx = gr.c2.x; cy = gr.c2.y; cz = gr.c2.z;
+                int am;
+                const double ub = md_upper_bound_poly(c1, K, cx, cy, cz, am), t1loc = am ? 1.0 : 0.0;
+                if (ub <= alpha) { alpha = ub; nT1 = (1 - t1loc) * sc[G_T1L] + t1loc * sc[G_T1H]; }
+                else nT1 = -1;
+            } else {
+                t1 = 0.5; nT1 = -1; cx = cy = cz = -1; lb = p.eps3;
+            }
+            if (lb >= alpha * (1 - p.eps)) {
+                o.r0 = alpha; o.r1 = nT1; o.rx = cx; o.ry = cy; o.rz = cz; returning = true; depth--;
+                if (depth < 0) break;
+                continue;
+            }
+            if (depth + 1 >= p.max_depth) { o.n.status = OBTG_MD_DEPTH_CAP; o.r0 = alpha; o.r1 = nT1; o.rx = cx; o.ry = cy; o.rz = cz; break; }
+            if (t1 != t1) t1 = 0;
+            md_publish<WAVE>([&] {
+                sc[G_T1] = t1; sc[G_ALPHA] = alpha; sc[G_RT1] = nT1; sc[G_PX] = cx; sc[G_PY] = cy; sc[G_PZ] = cz; sc[G_STATE] = 1;
+            });
+            state = 1;
+        }
+        if (returning) {
+            if (o.r0 < sc[G_ALPHA])
+                md_publish<WAVE>([&] { sc[G_ALPHA] = o.r0; sc[G_RT1] = o.r1; sc[G_PX] = o.rx; sc[G_PY] = o.ry; sc[G_PZ] = o.rz; });
+            returning = false;
+            state = (int)sc[G_STATE];
+        }
+        if (state >= 3) {
+            o.r0 = sc[G_ALPHA]; o.r1 = sc[G_RT1]; o.rx = sc[G_PX]; o.ry = sc[G_PY]; o.rz = sc[G_PZ];
+            returning = true; depth--;
+            if (depth < 0) break;
+            continue;
+        }
+        // ---- descend into child state-1: the left piece, then the right one
+        {
+            if constexpr (WAVE) {
+                if (cur_depth != depth) { md_refetch(cur, f, 3 * K); cur_depth = depth; }
+            }
+            const int h1 = state - 1;
+            const double t1 = sc[G_T1];
+            double* nf = f + FR;
+            if constexpr (WAVE) {
+                if (3 * K <= kWave) split_rows3_wave(cur, K, t1, h1, nxt, rl, il, w.sh_e);      // (sh_e + sh_q: 64 idle doubles)
+                else if (lane < 3) split_row_lds(cur + lane * K, K, t1, h1, nxt + lane * K, w.sh_e + lane * kMdMaxK);
+                wave_sync();
+                for (int i = lane; i < 3 * K; i += kWave) nf[i] = nxt[i];
+            } else {
+                for (int c = 0; c < 3; ++c) split_row(f + c * K, K, t1, h1, nf + c * K);
+            }
+            double n1l, n1h;
+            md_child_interval(sc[G_T1L], sc[G_T1H], t1, h1, n1l, n1h);
+            const double a_in = sc[G_ALPHA];
+            double* ns = WAVE ? sc + G_NSCAL : nf + 3 * K;
+            md_publish<WAVE>([&] {
+                ns[G_T1L] = n1l; ns[G_T1H] = n1h; ns[G_ALPHA] = a_in; ns[G_STATE] = 0;
+                sc[G_STATE] = state + 1;
+            });
+            double* tsw = cur; cur = nxt; nxt = tsw;
+            depth++;
+            cur_depth = depth;
+        }
+    }
+    return o;
+}
+
 __global__ __launch_bounds__(64) void k_min_dist2poly(const Md2Params p)
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= p.n_pairs) return;
-    const int K = p.K, FR = 3 * K + G_NSCAL;
-    double* st = p.stack + (size_t)k * p.max_depth * FR;
+    const int K = p.K;
+    double* st = p.stack + (size_t)k * p.max_depth * (3 * K + G_NSCAL);
     const double* ca = p.curves + (size_t)p.pc[k] * 3 * K;
     const int po = p.off[p.pp[k]], PK = p.off[p.pp[k] + 1] - po;
     for (int i = 0; i < 3 * K; ++i) st[i] = ca[i];
@@ -3332,81 +3314,32 @@ __global__ __launch_bounds__(64) void k_min_dist2poly(const Md2Params p)
         double* sc = st + 3 * K;
         sc[G_T1L] = 0; sc[G_T1H] = 1; sc[G_ALPHA] = INFINITY; sc[G_STATE] = 0;
     }
-    int depth = 0, nodes = 0, calls = 0, dmax = 0, status = OBTG_MD_OK;
-    double r0 = INFINITY, r1 = -1, rx = -1, ry = -1, rz = -1;
-    bool returning = false;
-    for (;;) {
-        double* f = st + (size_t)depth * FR;
-        double* sc = f + 3 * K;
-        int state = (int)sc[G_STATE];
-        if (!returning && state == 0) {
-            if (depth + 1 > 1000) { r0 = r1 = rx = -1; ry = rz = -1; returning = true; depth--; if (depth < 0) break; continue; }
-            if (nodes >= p.max_nodes) { status = OBTG_MD_NODE_CAP; break; }
-            nodes++;
-            if (depth + 1 > dmax) dmax = depth + 1;
-            Ctx<MemTwo> g;
-            g.mem = MemTwo{ f, p.soa };
-            g.P1 = Poly{ 0, K, K, 1 };
-            g.P2 = Poly{ kPolyBias + 3 * po, PK, PK, 1 };
-            g.trace = nullptr; g.trace_cap = 0; g.n_support = 0;
-            Result gr;
-            gjk::run(g, p.max_iter, p.md_cap, gr);
-            calls++;
-            if (gr.status == OBTG_ST_MD_CAP || gr.status == OBTG_ST_CYCLE) { status = OBTG_MD_GJK_CAP; break; }
-            double lb, t1, nT1, alpha = sc[G_ALPHA];
-            double cx, cy, cz;
-            if (gr.flag > 0) {
-                lb = gr.dist;
-                t1 = hull_param(f, K, gr.c1);
-                cx = gr.c2.x; cy = gr.c2.y; cz = gr.c2.z;
-                // _upperboundPoly (bezier.py:1535-1547)
-                const double d0 = norm_seq(f[0], f[K], f[2 * K], cx, cy, cz);
-                const double d1 = norm_seq(f[K - 1], f[2 * K - 1], f[3 * K - 1], cx, cy, cz);
-                int am = (d1 < d0) ? 1 : 0;
-                if (d0 != d0) am = 0; else if (d1 != d1) am = 1;
-                const double ub = am ? d1 : d0, t1loc = am ? 1.0 : 0.0;
-                if (ub <= alpha) { alpha = ub; nT1 = (1 - t1loc) * sc[G_T1L] + t1loc * sc[G_T1H]; }
-                else nT1 = -1;
-            } else {
-                t1 = 0.5; nT1 = -1; cx = cy = cz = -1; lb = p.eps3;
-            }
-            if (lb >= alpha * (1 - p.eps)) {
-                r0 = alpha; r1 = nT1; rx = cx; ry = cy; rz = cz; returning = true; depth--;
-                if (depth < 0) break;
-                continue;
-            }
-            if (depth + 1 >= p.max_depth) { status = OBTG_MD_DEPTH_CAP; r0 = alpha; r1 = nT1; rx = cx; ry = cy; rz = cz; break; }
-            if (t1 != t1) t1 = 0;
-            sc[G_T1] = t1; sc[G_ALPHA] = alpha; sc[G_RT1] = nT1; sc[G_PX] = cx; sc[G_PY] = cy; sc[G_PZ] = cz;
-            state = 1; sc[G_STATE] = 1;
-        }
-        if (returning) {
-            if (r0 < sc[G_ALPHA]) { sc[G_ALPHA] = r0; sc[G_RT1] = r1; sc[G_PX] = rx; sc[G_PY] = ry; sc[G_PZ] = rz; }
-            returning = false;
-            state = (int)sc[G_STATE];
-        }
-        if (state >= 3) {
-            r0 = sc[G_ALPHA]; r1 = sc[G_RT1]; rx = sc[G_PX]; ry = sc[G_PY]; rz = sc[G_PZ];
-            returning = true; depth--;
-            if (depth < 0) break;
-            continue;
-        }
-        {
-            const int h1 = state - 1;
-            const double t1 = sc[G_T1];
-            double* nf = f + FR;
-            for (int c = 0; c < 3; ++c) split_row(f + c * K, K, t1, h1, nf + c * K);
-            double* ns = nf + 3 * K;
-            const double t1len = sc[G_T1H] - sc[G_T1L];
-            const double m1 = sc[G_T1L] + t1 * t1len;
-            ns[G_T1L] = h1 ? m1 : sc[G_T1L]; ns[G_T1H] = h1 ? sc[G_T1H] : m1;
-            ns[G_ALPHA] = sc[G_ALPHA]; ns[G_STATE] = 0;
-            sc[G_STATE] = state + 1;
-            depth++;
-        }
-    }
-    p.res[5 * k] = r0; p.res[5 * k + 1] = r1; p.res[5 * k + 2] = rx; p.res[5 * k + 3] = ry; p.res[5 * k + 4] = rz;
-    if (p.info) { p.info[4 * k] = nodes; p.info[4 * k + 1] = calls; p.info[4 * k + 2] = dmax; p.info[4 * k + 3] = status; }
+    md2_store(p, k, md2_walk<false>(p, K, po, PK, st, MdWave{}, nullptr, 0, 0));
+}
+
+// One (curve, polygon) pair per wavefront, a workgroup per pair: the polygon (<= 32 vertices) goes to LDS once.
+__global__ __launch_bounds__(64) void k_min_dist2poly_wave(const Md2Params p)
+{
+    extern __shared__ double m2_lds[];
+    const int k = blockIdx.x, lane = threadIdx.x;
+    const int K = p.K;
+    const int po = p.off[p.pp[k]], PK = p.off[p.pp[k] + 1] - po;
+    MdWave w;
+    w.cur = m2_lds;                             // [3K]
+    w.nxt = w.cur + 3 * K;                      // [3K]
+    double* pol = w.nxt + 3 * K;                // [3][32] polygon, SoA
+    w.sh_e = pol + 3 * kMdMaxK;                 // [kMdMaxK] (+ the three scratch rows of a split, with sh_q)
+    w.sh_q = w.sh_e + kMdMaxK;                  // [kMdMaxK] + 2 rows
+    w.scs = w.sh_q + 3 * kMdMaxK;               // [max_depth][G_NSCAL]
+    const int rl = lane / K, il = lane - rl * K;          // (row, point) of the lane in the level-parallel splits
+    double* st = p.stack + (size_t)k * p.max_depth * (3 * K + G_NSCAL);
+    const double* ca = p.curves + (size_t)p.pc[k] * 3 * K;
+    for (int i = lane; i < 3 * K; i += kWave) { const double a = ca[i]; st[i] = a; w.cur[i] = a; }
+    for (int i = lane; i < 3 * PK; i += kWave) pol[(i / PK) * kMdMaxK + (i % PK)] = p.soa[3 * po + i];
+    if (lane == 0) { w.scs[G_T1L] = 0; w.scs[G_T1H] = 1; w.scs[G_ALPHA] = INFINITY; w.scs[G_STATE] = 0; }
+    __syncthreads();
+    const Md2Out o = md2_walk<true>(p, K, po, PK, st, w, pol, rl, il);
+    if (lane == 0) md2_store(p, k, o);
 }
 
 // =====================================================================================
@@ -4430,130 +4363,6 @@ int launch_min_dist_mixed(obtg_ctx* c, const double* d_cpts, const int* d_off, i
     hipLaunchKernelGGL(k_min_dist_mixed, dim3(L.grid), dim3(L.block), L.lds, c->stream, p);
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;
-}
-
-// _minDist2Poly with one (curve, polygon) pair per wavefront: as k_min_dist_wave, with the polygon (<= 32
-// vertices) copied to LDS once and only the curve in the frames.
-__global__ __launch_bounds__(64) void k_min_dist2poly_wave(const Md2Params p)
-{
-    extern __shared__ double m2_lds[];
-    const int k = blockIdx.x, lane = threadIdx.x, li = lane & 31;
-    const int K = p.K, FR = 3 * K + G_NSCAL;
-    const int rl = lane / K, il = lane - rl * K;          // (row, point) of the lane in the level-parallel splits
-    const int po = p.off[p.pp[k]], PK = p.off[p.pp[k] + 1] - po;
-    double* cur = m2_lds;                       // [3K] curve of the node being evaluated
-    double* nxt = cur + 3 * K;                  // [3K] the child being built
-    double* pol = nxt + 3 * K;                  // [3][32] polygon, SoA
-    double* sh_e = pol + 3 * kMdMaxK;           // [kMdMaxK] (+ the three scratch rows of a split, with sh_q)
-    double* sh_q = sh_e + kMdMaxK;              // [kMdMaxK] + 2 rows
-    double* scs = sh_q + 3 * kMdMaxK;           // [max_depth][G_NSCAL]
-    double* st = p.stack + (size_t)k * p.max_depth * FR;
-    const double* ca = p.curves + (size_t)p.pc[k] * 3 * K;
-    for (int i = lane; i < 3 * K; i += kWave) { const double a = ca[i]; st[i] = a; cur[i] = a; }
-    for (int i = lane; i < 3 * PK; i += kWave) pol[(i / PK) * kMdMaxK + (i % PK)] = p.soa[3 * po + i];
-    if (lane == 0) { scs[G_T1L] = 0; scs[G_T1H] = 1; scs[G_ALPHA] = INFINITY; scs[G_STATE] = 0; }
-    __syncthreads();
-    int depth = 0, cur_depth = 0, nodes = 0, calls = 0, dmax = 0, status = OBTG_MD_OK;
-    double r0 = INFINITY, r1 = -1, rx = -1, ry = -1, rz = -1;
-    bool returning = false;
-    for (;;) {
-        double* f = st + (size_t)depth * FR;
-        double* sc = scs + depth * G_NSCAL;
-        int state = (int)sc[G_STATE];
-        if (!returning && state == 0) {
-            if (depth + 1 > 1000) { r0 = r1 = rx = -1; ry = rz = -1; returning = true; depth--; if (depth < 0) break; continue; }
-            if (nodes >= p.max_nodes) { status = OBTG_MD_NODE_CAP; break; }
-            nodes++;
-            if (depth + 1 > dmax) dmax = depth + 1;
-            Ctx<MemLds> g;
-            g.mem = MemLds{ m2_lds };
-            g.P1 = Poly{ (int)(cur - m2_lds), K, K, 1 };
-            g.P2 = Poly{ (int)(pol - m2_lds), kMdMaxK, PK, 1 };
-            g.trace = nullptr; g.trace_cap = 0; g.n_support = 0;
-            Result gr;
-            gjk::run<MemLds, false, true>(g, p.max_iter, p.md_cap, gr);
-            calls++;
-            if (gr.status == OBTG_ST_MD_CAP || gr.status == OBTG_ST_CYCLE) { status = OBTG_MD_GJK_CAP; break; }
-            double lb, t1, nT1, alpha = sc[G_ALPHA];
-            double cx, cy, cz;
-            if (gr.flag > 0) {
-                lb = gr.dist;
-                const double tp = hull_param_wave(cur, K, gr.c1, sh_e, sh_q, lane < 32 ? li : kMdMaxK);
-                t1 = __shfl(tp, 0);
-                cx = gr.c2.x; cy = gr.c2.y; cz = gr.c2.z;
-                const double d0 = norm_seq(cur[0], cur[K], cur[2 * K], cx, cy, cz);
-                const double d1 = norm_seq(cur[K - 1], cur[2 * K - 1], cur[3 * K - 1], cx, cy, cz);
-                int am = (d1 < d0) ? 1 : 0;
-                if (d0 != d0) am = 0; else if (d1 != d1) am = 1;
-                const double ub = am ? d1 : d0, t1loc = am ? 1.0 : 0.0;
-                if (ub <= alpha) { alpha = ub; nT1 = (1 - t1loc) * sc[G_T1L] + t1loc * sc[G_T1H]; }
-                else nT1 = -1;
-            } else {
-                t1 = 0.5; nT1 = -1; cx = cy = cz = -1; lb = p.eps3;
-            }
-            if (lb >= alpha * (1 - p.eps)) {
-                r0 = alpha; r1 = nT1; rx = cx; ry = cy; rz = cz; returning = true; depth--;
-                if (depth < 0) break;
-                continue;
-            }
-            if (depth + 1 >= p.max_depth) { status = OBTG_MD_DEPTH_CAP; r0 = alpha; r1 = nT1; rx = cx; ry = cy; rz = cz; break; }
-            if (t1 != t1) t1 = 0;
-            wave_sync();
-            if (lane == 0) {
-                sc[G_T1] = t1; sc[G_ALPHA] = alpha; sc[G_RT1] = nT1; sc[G_PX] = cx; sc[G_PY] = cy; sc[G_PZ] = cz; sc[G_STATE] = 1;
-            }
-            wave_sync();
-            state = 1;
-        }
-        if (returning) {
-            if (r0 < sc[G_ALPHA]) {
-                wave_sync();
-                if (lane == 0) { sc[G_ALPHA] = r0; sc[G_RT1] = r1; sc[G_PX] = rx; sc[G_PY] = ry; sc[G_PZ] = rz; }
-                wave_sync();
-            }
-            returning = false;
-            state = (int)sc[G_STATE];
-        }
-        if (state >= 3) {
-            r0 = sc[G_ALPHA]; r1 = sc[G_RT1]; rx = sc[G_PX]; ry = sc[G_PY]; rz = sc[G_PZ];
-            returning = true; depth--;
-            if (depth < 0) break;
-            continue;
-        }
-        {
-            if (cur_depth != depth) {
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-                for (int i = lane; i < 3 * K; i += kWave) cur[i] = f[i];
-                cur_depth = depth;
-                wave_sync();
-            }
-            const int h1 = state - 1;
-            const double t1 = sc[G_T1];
-            double* nf = f + FR;
-            if (3 * K <= kWave) split_rows3_wave(cur, K, t1, h1, nxt, rl, il, sh_e);  // level-parallel (see k_min_dist_wave); sh_e + sh_q: 64 idle doubles
-            else if (lane < 3) split_row_lds(cur + lane * K, K, t1, h1, nxt + lane * K, sh_e + lane * kMdMaxK);
-            wave_sync();
-            for (int i = lane; i < 3 * K; i += kWave) nf[i] = nxt[i];
-            const double t1len = sc[G_T1H] - sc[G_T1L];
-            const double m1 = sc[G_T1L] + t1 * t1len;
-            const double a_in = sc[G_ALPHA];
-            const double n1l = h1 ? m1 : sc[G_T1L], n1h = h1 ? sc[G_T1H] : m1;
-            wave_sync();
-            if (lane == 0) {
-                double* ns = sc + G_NSCAL;
-                ns[G_T1L] = n1l; ns[G_T1H] = n1h; ns[G_ALPHA] = a_in; ns[G_STATE] = 0;
-                sc[G_STATE] = state + 1;
-            }
-            double* tsw = cur; cur = nxt; nxt = tsw;
-            depth++;
-            cur_depth = depth;
-            wave_sync();
-        }
-    }
-    if (lane == 0) {
-        p.res[5 * k] = r0; p.res[5 * k + 1] = r1; p.res[5 * k + 2] = rx; p.res[5 * k + 3] = ry; p.res[5 * k + 4] = rz;
-        if (p.info) { p.info[4 * k] = nodes; p.info[4 * k + 1] = calls; p.info[4 * k + 2] = dmax; p.info[4 * k + 3] = status; }
-    }
 }
 
 // ---- _minDist2Poly, both children at a time (round 5): k_min_dist_quad's arrangement for bezier.py:1411-1496, whose nodes have TWO

@@ -18,6 +18,51 @@ __device__ __forceinline__ double norm_seq(double ax, double ay, double az, doub
     return __builtin_sqrt(s);
 }
 
+// numpy's argmin over n distances: the smallest, the first of equals -- and the first NaN wins
+template <int N>
+__device__ __forceinline__ int np_argmin(const double (&dd)[N])
+{
+    int am = 0;
+    for (int i = 1; i < N; ++i) if (dd[i] < dd[am]) am = i;
+    for (int i = 0; i < N; ++i) if (dd[i] != dd[i]) { am = i; break; }
+    return am;
+}
+
+// _upperbound (bezier.py:1499-1516): the smallest of the four end-point distances of c1[3][KA] and c2[3][KB]; am: which one
+// (bit 1: curve 1's last point, bit 0: curve 2's).  PLANAR: every z is +0, and norm_seq with dz = 0 is s + 0 * 0 = s.
+template <bool PLANAR>
+__device__ __forceinline__ double md_upper_bound(const double* c1, int KA, const double* c2, int KB, int& am)
+{
+    double dd[4];
+    if constexpr (PLANAR) {
+        auto n2 = [](double ax, double ay, double bx, double by) {
+            const double dx = ax - bx, dy = ay - by;
+            double s = 0.0;
+            s += dx * dx; s += dy * dy;
+            return __builtin_sqrt(s);
+        };
+        dd[0] = n2(c1[0], c1[KA], c2[0], c2[KB]);
+        dd[1] = n2(c1[0], c1[KA], c2[KB - 1], c2[2 * KB - 1]);
+        dd[2] = n2(c1[KA - 1], c1[2 * KA - 1], c2[0], c2[KB]);
+        dd[3] = n2(c1[KA - 1], c1[2 * KA - 1], c2[KB - 1], c2[2 * KB - 1]);
+    } else {
+        dd[0] = norm_seq(c1[0], c1[KA], c1[2 * KA], c2[0], c2[KB], c2[2 * KB]);
+        dd[1] = norm_seq(c1[0], c1[KA], c1[2 * KA], c2[KB - 1], c2[2 * KB - 1], c2[3 * KB - 1]);
+        dd[2] = norm_seq(c1[KA - 1], c1[2 * KA - 1], c1[3 * KA - 1], c2[0], c2[KB], c2[2 * KB]);
+        dd[3] = norm_seq(c1[KA - 1], c1[2 * KA - 1], c1[3 * KA - 1], c2[KB - 1], c2[2 * KB - 1], c2[3 * KB - 1]);
+    }
+    am = np_argmin(dd);
+    return dd[am];
+}
+
+// _upperboundPoly (bezier.py:1535-1547): the nearer end point of c[3][K] to the polygon's closest point; am: 1 = the last point
+__device__ __forceinline__ double md_upper_bound_poly(const double* c, int K, double cx, double cy, double cz, int& am)
+{
+    const double dd[2] = { norm_seq(c[0], c[K], c[2 * K], cx, cy, cz), norm_seq(c[K - 1], c[2 * K - 1], c[3 * K - 1], cx, cy, cz) };
+    am = np_argmin(dd);
+    return dd[am];
+}
+
 // The lane above's value (lane 63: zero): one DPP move per half of the double, no LDS round trip.
 __device__ __forceinline__ double wave_next_lane(double v)
 {

@@ -94,6 +94,29 @@ def test_equal_degrees_forward_to_min_dist(capi):
             assert np.array_equal(a[key], b[key], equal_nan=(key == "res")), (K, key)
 
 
+@pytest.mark.parametrize("dim,K", [(2, 6), (3, 20), (3, 22)])
+def test_equal_degree_pairs_on_the_mixed_kernel(capi, monkeypatch, dim, K):
+    """A call of equal-degree curves is forwarded to obtg_min_dist (above), so k_min_dist_mixed never sees KA == KB through it.
+    Here one curve of another length (K = 3) that no pair names keeps the call on k_min_dist_mixed: all 28 pairs of 8 curves
+    give what obtg_min_dist gives on the same curves in its one-wavefront and its one-lane form -- res (NaN equal to NaN),
+    node and gjkNew-call counts, depth and status, no pair left out -- when the searches end, under a depth cap, and under a
+    one-node budget.  K = 6 planar (hulls without a z row in the mixed kernel, with one in the others), K = 20 in 3-D (3 K <= 64:
+    the level-parallel split), K = 22 in 3-D (3 K > 64: a lane per row)."""
+    ctx = capi.scratch_context()
+    rng = np.random.default_rng(600 + K)
+    curves = R.walk(rng, 8, K, dim, 0.0)
+    spare = R.walk(rng, 1, 3, dim, 0.0)[0]
+    pa, pb = np.triu_indices(8, 1)
+    for kw in (dict(max_depth=32, max_nodes=300), dict(max_depth=5, max_nodes=300), dict(max_depth=32, max_nodes=1)):
+        mixed = ctx.min_dist_mixed(list(curves) + [spare], pa, pb, **kw)
+        for form in ("wave", "lane"):
+            monkeypatch.setenv("OBTG_MD_FORM", form)
+            same = ctx.min_dist(curves, pa, pb, **kw)
+            monkeypatch.delenv("OBTG_MD_FORM")
+            for key in ("res", "nodes", "gjk_calls", "depth", "status"):
+                assert np.array_equal(mixed[key], same[key], equal_nan=(key == "res")), (K, kw, form, key)
+
+
 def test_mixed_degree_reference_fixture(capi, oracle, golden_dir):
     """The reference's own `_minDist` on curves of different degree (tests/golden/mixed_degree.npz: 3-D against 3-D and a 2-D
     first curve against a 3-D second one, degrees from {2, 4, 5, 10, 15}): the same triple, bit for bit, and the same number of

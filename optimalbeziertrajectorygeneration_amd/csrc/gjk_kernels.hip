@@ -2825,11 +2825,25 @@ __global__ __launch_bounds__(64) void k_min_dist_robust(const MdrParams p)
     const double* ca = p.curves + (size_t)p.pa[k] * 3 * K;
     const double* cb = p.curves + (size_t)p.pb[k] * 3 * K;
     double scale = 0.0;
+    bool dirty = false;                            // a NaN (which fmax drops) or an inf (which makes abs_tol inf) in the pair
+    bool bent1 = false, bent2 = false;             // a control point that is not the curve's first one
     for (int i = lane; i < 3 * K; i += kWave) {
         const double a = ca[i], bq = cb[i];
         orig[i] = a; orig[3 * K + i] = bq;
         scale = fmax(scale, fmax(__builtin_fabs(a), __builtin_fabs(bq)));
+        dirty = dirty || !(__builtin_fabs(a) < INFINITY) || !(__builtin_fabs(bq) < INFINITY);
+        bent1 = bent1 || a != ca[(i / K) * K]; bent2 = bent2 || bq != cb[(i / K) * K];
     }
+    if (__ballot(dirty)) {                         // non-finite input: NaN for NaN, no search (include/obtg.h)
+        if (lane == 0) {
+            p.res[3 * k] = NAN; p.res[3 * k + 1] = -1; p.res[3 * k + 2] = -1;
+            if (p.info) { p.info[4 * k] = 0; p.info[4 * k + 1] = 0; p.info[4 * k + 2] = 0; p.info[4 * k + 3] = OBTG_MD_OK; }
+        }
+        return;
+    }
+    // a point-curve (every control point the same) is that point at every parameter: its side of a node is not cut, or the
+    // line of equal minimisers along its parameter would fill the frontier.  Every other pair: four children, as before.
+    const int cut1 = __ballot(bent1) ? 2 : 1, cut2 = __ballot(bent2) ? 2 : 1;
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) scale = fmax(scale, __shfl_xor(scale, m));
     const double abs_tol = p.eps * scale;          // "the curves touch": a relative criterion cannot close on distance 0
@@ -2921,14 +2935,17 @@ __global__ __launch_bounds__(64) void k_min_dist_robust(const MdrParams p)
             if (keep) {
                 if (lev + 1 > p.max_level) status = OBTG_MD_DEPTH_CAP;
                 else {
-                    const int pos = atomicAdd(&s_count, 4);
-                    if (pos + 4 <= p.cap) {
+                    const int kids = cut1 * cut2;
+                    const int pos = atomicAdd(&s_count, kids);
+                    if (pos + kids <= p.cap) {
                         const double h = 0.5 * w;
-                        for (int c4 = 0; c4 < 4; ++c4) {
-                            fb[3 * (pos + c4)] = t1 + (c4 >> 1) * h;
-                            fb[3 * (pos + c4) + 1] = t2 + (c4 & 1) * h;
-                            fb[3 * (pos + c4) + 2] = (double)(lev + 1);
-                        }
+                        int at = pos;
+                        for (int c1 = 0; c1 < cut1; ++c1)
+                            for (int c2 = 0; c2 < cut2; ++c2, ++at) {
+                                fb[3 * at] = t1 + c1 * h;
+                                fb[3 * at + 1] = t2 + c2 * h;
+                                fb[3 * at + 2] = (double)(lev + 1);
+                            }
                     } else status = OBTG_MD_NODE_CAP;
                 }
             }
@@ -3063,8 +3080,21 @@ __global__ __launch_bounds__(64) void k_min_dist2poly_robust(const Md2rParams p)
     double* work = poly + 3 * Kp + lane * pitch;   // per lane: the node's sub-curve [3][K]
     const double* cc = p.curves + (size_t)p.pc[k] * 3 * K;
     double scale = 0.0;
-    for (int i = lane; i < 3 * K; i += kWave) { const double a = cc[i]; orig[i] = a; scale = fmax(scale, __builtin_fabs(a)); }
-    for (int i = lane; i < 3 * Kp; i += kWave) { const double a = p.soa[3 * po + i]; poly[i] = a; scale = fmax(scale, __builtin_fabs(a)); }
+    bool dirty = false;                            // as in k_min_dist_robust: a NaN or an inf in the curve or the polygon
+    for (int i = lane; i < 3 * K; i += kWave) {
+        const double a = cc[i]; orig[i] = a; scale = fmax(scale, __builtin_fabs(a)); dirty = dirty || !(__builtin_fabs(a) < INFINITY);
+    }
+    for (int i = lane; i < 3 * Kp; i += kWave) {
+        const double a = p.soa[3 * po + i]; poly[i] = a; scale = fmax(scale, __builtin_fabs(a)); dirty = dirty || !(__builtin_fabs(a) < INFINITY);
+    }
+    if (__ballot(dirty)) {                         // non-finite input: NaN for NaN, no search (include/obtg.h)
+        if (lane == 0) {
+            double* o = p.res + 5 * (size_t)k;
+            o[0] = NAN; o[1] = -1; o[2] = NAN; o[3] = NAN; o[4] = NAN;
+            if (p.info) { p.info[4 * k] = 0; p.info[4 * k + 1] = 0; p.info[4 * k + 2] = 0; p.info[4 * k + 3] = OBTG_MD_OK; }
+        }
+        return;
+    }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) scale = fmax(scale, __shfl_xor(scale, m));
     const double abs_tol = p.eps * scale;
@@ -3107,7 +3137,9 @@ __global__ __launch_bounds__(64) void k_min_dist2poly_robust(const Md2rParams p)
                 const int ie = e ? K - 1 : 0;
                 const OnePoint one{ tgjk::P3{ work[ie], work[K + ie], work[2 * K + ie] } };
                 const SupportScan<OnePoint, LdsRows> sup{ one, pset, 1, Kp };
-                const tgjk::Result r = tgjk::true_distance(sup, one, pset, 1e-13, abs_tol, 64);
+                // (no "touching" tolerance here: dist stays the distance between the curve's point and a point of the hull, an
+                //  upper bound of the minimum also where it is below abs_tol)
+                const tgjk::Result r = tgjk::true_distance(sup, one, pset, 1e-13, 0.0, 64);
                 if (r.dist < best) { best = r.dist; bt_l = t + e * w; bc = r.c2; }
             }
             if (!valid) best = INFINITY;

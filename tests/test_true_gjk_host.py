@@ -77,3 +77,18 @@ def test_true_gjk_known_cases(host_gjk):
     p1 = np.array([(4, 11, 0), (4, 5, 0), (9, 9, 0)], float)
     p2 = np.array([(8, 6, 0), (10, 2, 0), (13, 1, 0), (15, 6, 0)], float)
     assert abs(host_gjk(p1, p2)["dist"] - qp_distance(p1, p2)) < 1e-9
+
+
+@pytest.mark.parametrize("eps", [1e-6, 1e-9])
+def test_true_gjk_host_against_exact_hull_distances(host_gjk, eps):
+    """The host build against robust_distance_ref.hull_dist_sq (exact rationals) on the point sets and with the assertions
+    of tests/test_gpu_robust_distance.py::test_gjk_true_pairs_against_exact_hull_distances (test_robust_distance_ref.check_gjk):
+    flag, lower^2 <= exact <= dist^2, the certificate, |c1 - c2| = dist, c1 / c2 in their hulls."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import test_robust_distance_ref as T
+    ms = []
+    for case in T.shared("gjk"):
+        r = host_gjk(case["P"], case["Q"], eps=eps, abs_tol=eps * float(case["scale"]))
+        ms.append(T.check_gjk(case, r, eps, T.ALLOW["gjk"]))
+    print("host gjk_true.h, eps %g, multiples of 2^-53 scale: %s" % (eps, T.worst(ms)))

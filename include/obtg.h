@@ -116,7 +116,10 @@ const char* obtg_strerror(int code);
  *      no kernel id added).
  *      Later, still 7: new: the keep-out obstacles obtg_ctx_set_keep_out (obtg_len_keep_out), their true clearances
  *      obtg_keep_out_true_min[_dev], the envelope Jacobian obtg_keep_out_true_min_jac[_dev] and the clearance of free curves
- *      obtg_bern_keep_out[_dev] (timed under OBTG_K_SPEED; no kernel id added). */
+ *      obtg_bern_keep_out[_dev] (timed under OBTG_K_SPEED; no kernel id added).
+ *      Later, still 7: new: keep-out obstacles that move along a known path: obtg_ctx_set_keep_out_motion, the clearances
+ *      obtg_keep_out_moving_true_min[_dev], the envelope Jacobian with its tf column obtg_keep_out_moving_true_min_jac[_dev] and
+ *      free curves against one moving obstacle obtg_bern_keep_out_moving[_dev] (timed under OBTG_K_SPEED; no kernel id added). */
 #define OBTG_ABI_VERSION 7
 int obtg_abi_version(void);
 
@@ -978,7 +981,8 @@ int obtg_keep_in_true_min_jac_dev(obtg_ctx*, const double* dY, int B, double eps
  *           jac[c][i] = (lam1 a_f1[c] + lam2 a_f2[c]) B_i^n(t*).
  *   The block is linear in the control points of the item's own vehicle only; the basis comes from the recurrence of the other
  *   envelope blocks, every multiply-add an explicit fma.  An end minimiser leaves one non-zero column; a NaN row a NaN block.
- * obtg_ctx_set_keep_out: copies H, obs_off and VO to the context (P = 0 clears the tables).  OBTG_ERR_ARG for a vehicle index
+ * obtg_ctx_set_keep_out: copies H, obs_off and VO to the context (P = 0 clears the tables) and CLEARS any motion that
+ *     obtg_ctx_set_keep_out_motion left: new tables stand still.  OBTG_ERR_ARG for a vehicle index
  *     outside 0 .. N-1, an obstacle index outside 0 .. O-1, a context whose d is not 2 or 3, obs_off[0] != 0, offsets that do not
  *     ascend (an empty obstacle) or a null table with P > 0; OBTG_ERR_UNSUPPORTED for an obstacle of more than 16 faces.
  * obtg_len_keep_out: P.
@@ -1012,6 +1016,60 @@ int obtg_bern_keep_out(obtg_ctx*, const double* c /*[M][dim][K]*/, int M, int di
                        double eps_rel, int max_nodes, double* val /*[M]*/, double* t_star /*[M], nullable*/, int* status /*[M], nullable*/);
 int obtg_bern_keep_out_dev(obtg_ctx*, const double* d_c, int M, int dim, int K, const double* H, int F, double eps_rel, int max_nodes,
                            double* d_val, double* d_t_star, int* d_status);
+
+/* ---- moving keep-out obstacles: a convex obstacle that translates along a known path ----
+ * Obstacle o of the keep-out tables keeps its faces and may carry a motion: a Bezier offset q_o(time) with control points
+ * Q_o[d][m_o+1] on the ABSOLUTE span [0, T_o].  Its body at `time` is {p : a_f . (p - q_o(time)) <= b_f}: translation only.
+ * Vehicles live on [0, tf], tf per batch row.  With s in [0, 1] and r = tf / T_o:
+ *     E(s)   = q_o(s tf)        the motion restricted to [0, r] of its own parameter, raised to the vehicle's degree n
+ *     D_i    = P_i - E_i        the relative control points, i <= n
+ *     g_f(s) = a_f . D(s) - b_f,  G = max_f g_f,  row = min_s G(s) - margin:   the static row of the curve D.
+ * An obstacle without a motion is the static obstacle: D = P bit for bit, tf does not enter, d row / d tf is an exact 0.
+ * The arithmetic of D (csrc/keepout_device.h keep_out_motion_points), every multiply-add an explicit fma; it needs m_o <= n:
+ *     ratio        r = tf / T_o, one division;
+ *     restriction  de Casteljau at r, each level b = fma(r, up, (1 - r) * b) with 1 - r rounded once; point j of the left piece
+ *                  is the first value after level j.  At r == 1 this is the identity, bit for bit (a zero may change sign);
+ *     elevation    n - m_o single-degree steps, degree k -> k + 1: E_i = fma(w, E_(i-1), (1 - w) * E_i) with
+ *                  w = (double)i / (k + 1); the ends (w = 0 and w = 1) are exact; at m_o == n there are zero steps;
+ *     difference   D = P - E, one subtraction.
+ * r > 1 (tf beyond the motion's span; a time-optimal solve may overshoot) is answered by the polynomial's continuation, the
+ * same instructions: NO rounding bound is claimed there (de Casteljau outside [0, 1] is not a convex combination).
+ * Non-finite input follows the static convention: a non-finite Q, T_o or tf, tf <= 0, or a ratio that is not finite and
+ * positive: NaN outputs (rel and jac_tf too; face -1, nodes 0), status OBTG_MD_OK -- for the items of a moving obstacle.
+ * Envelope Jacobian.  a^ = lam1 a_f1 + lam2 a_f2, faces and lam by the static rule on D(s*), D'(s*).  The block with respect to
+ * the vehicle's control points is the static one, jac[c][i] = a^[c] B_i(s*).  New is the explicit
+ *     d row / d tf = -(a^ . E'(s*)) s* / tf          (dE/d tf = s q_o'(s tf) = s E'(s) / tf),
+ * E'(s*) = n (E1 - E0) of de Casteljau on E at s*, the dot product summed in coordinate order, then * s*, then / tf: jac_tf[B][P].
+ * obtg_ctx_set_keep_out_motion: Q the obstacles' [d][m_o+1] blocks one after the other, q_off[O+1] in control points (an empty
+ *     run: that obstacle stands still), T[O] (read for moving obstacles only).  O = 0 clears the motion.  OBTG_ERR_ARG: no
+ *     keep-out tables set, an O other than the tables', offsets that do not start at 0 or descend, a T_o that is not finite and
+ *     positive, a null table; OBTG_ERR_UNSUPPORTED: m_o > n.
+ * obtg_keep_out_moving_true_min: the outputs and conventions of obtg_keep_out_true_min, tf[B] the rows' spans; rel (nullable)
+ *     returns the relative control points D[B][P][d][n+1] the search ran on.  OBTG_ERR_ARG without a motion on the context.
+ * obtg_keep_out_moving_true_min_jac: the same outputs, bit for bit, plus jac[B][P][d][n+1] and jac_tf[B][P].
+ * obtg_bern_keep_out_moving: M free curves c[M][dim][K] against ONE obstacle H[F][dim+1] moving by Q[dim][Km], 1 <= Km <= K
+ *     (above: OBTG_ERR_UNSUPPORTED); r[M] the ratio per curve (null: 1 for all) -- H and Q host arrays in both forms, r device
+ *     memory in the _dev form.  margin 0: val[M], nullable t_star[M], status[M].
+ * One kernel, one launch: the static search's body, whose root is read from D (csrc/keepout_kernels.hip).  Host and _dev calls
+ * give the same bits; dY = NULL inside an obtg_fd_view answers OBTG_ERR_ARG; every launch is timed under OBTG_K_SPEED. */
+int obtg_ctx_set_keep_out_motion(obtg_ctx*, const double* Q, const int* q_off /*[O+1]*/, const double* T /*[O]*/, int O);
+int obtg_keep_out_moving_true_min(obtg_ctx*, const double* Y, const double* tf /*[B]*/, int B, double margin, double eps_rel,
+                                  int max_nodes, double* out /*[B][P]*/, double* t_star, int* face, double* lam, double* bound,
+                                  int* nodes, int* status, double* rel /*[B][P][d][n+1], nullable*/);
+int obtg_keep_out_moving_true_min_dev(obtg_ctx*, const double* dY, const double* d_tf, int B, double margin, double eps_rel,
+                                      int max_nodes, double* d_out, double* d_t_star, int* d_face, double* d_lam, double* d_bound,
+                                      int* d_nodes, int* d_status, double* d_rel);
+int obtg_keep_out_moving_true_min_jac(obtg_ctx*, const double* Y, const double* tf, int B, double margin, double eps_rel, int max_nodes,
+                                      double* out, double* t_star, int* face, double* lam, double* bound, int* nodes, int* status,
+                                      double* rel, double* jac /*[B][P][d][n+1]*/, double* jac_tf /*[B][P]*/);
+int obtg_keep_out_moving_true_min_jac_dev(obtg_ctx*, const double* dY, const double* d_tf, int B, double margin, double eps_rel,
+                                          int max_nodes, double* d_out, double* d_t_star, int* d_face, double* d_lam, double* d_bound,
+                                          int* d_nodes, int* d_status, double* d_rel, double* d_jac, double* d_jac_tf);
+int obtg_bern_keep_out_moving(obtg_ctx*, const double* c /*[M][dim][K]*/, int M, int dim, int K, const double* H /*[F][dim+1]*/, int F,
+                              const double* Q /*[dim][Km]*/, int Km, const double* r /*[M], nullable: 1*/, double eps_rel, int max_nodes,
+                              double* val /*[M]*/, double* t_star /*[M], nullable*/, int* status /*[M], nullable*/);
+int obtg_bern_keep_out_moving_dev(obtg_ctx*, const double* d_c, int M, int dim, int K, const double* H, int F, const double* Q, int Km,
+                                  const double* d_r, double eps_rel, int max_nodes, double* d_val, double* d_t_star, int* d_status);
 
 /* ---- the acceleration bound: |d^2 c / dtime^2| <= bound for every vehicle, in 2-D, 3-D and any other dimension ----
  * For vehicle v with control points P[c][i] (c < d, i <= n) on a span T = tf[b]:

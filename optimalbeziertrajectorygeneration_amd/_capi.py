@@ -179,6 +179,13 @@ _SIGNATURES = {
     "obtg_keep_out_true_min_jac_dev": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "obtg_bern_keep_out": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _d, _i, _vp, _vp, _vp]),
     "obtg_bern_keep_out_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _d, _i, _vp, _vp, _vp]),
+    "obtg_ctx_set_keep_out_motion": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "obtg_keep_out_moving_true_min": (_i, [_vp, _vp, _vp, _i, _d, _d, _i] + [_vp] * 8),
+    "obtg_keep_out_moving_true_min_dev": (_i, [_vp, _vp, _vp, _i, _d, _d, _i] + [_vp] * 8),
+    "obtg_keep_out_moving_true_min_jac": (_i, [_vp, _vp, _vp, _i, _d, _d, _i] + [_vp] * 10),
+    "obtg_keep_out_moving_true_min_jac_dev": (_i, [_vp, _vp, _vp, _i, _d, _d, _i] + [_vp] * 10),
+    "obtg_bern_keep_out_moving": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _d, _i, _vp, _vp, _vp]),
+    "obtg_bern_keep_out_moving_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _d, _i, _vp, _vp, _vp]),
     "obtg_jerk": (_i, [_vp, _vp, _vp, _i, _d, _vp]),
     "obtg_jerk_dev": (_i, [_vp, _vp, _vp, _i, _d, _vp]),
     "obtg_jerk_true_min": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
@@ -495,6 +502,7 @@ class Context(object):
         self._keep_in_key = None      # the bytes of the tables set_keep_in last sent
         self.keep_out_items = 0       # (vehicle, obstacle) items of the keep-out tables; 0: none set
         self._keep_out_key = None     # the bytes of the tables set_keep_out last sent
+        self._keep_out_motion_key = None     # the bytes of the motion set_keep_out_motion last sent; None: none set
 
     # -- plumbing
     def close(self):
@@ -824,6 +832,7 @@ class Context(object):
                                                     VO.shape[0]), "obtg_ctx_set_keep_out")
         self.keep_out_items = VO.shape[0]
         self._keep_out_key = (H.tobytes(), obs_off.tobytes(), VO.tobytes())
+        self._keep_out_motion_key = None       # (the library clears the motion with the tables)
 
     def _keep_out(self, obstacles):
         if obstacles is not None:
@@ -888,6 +897,87 @@ class Context(object):
         H = _f64(H).reshape(-1, int(dim) + 1)
         self._check(self._lib.obtg_bern_keep_out_dev(self._h, _vp(d_c), int(M), int(dim), int(K), _ptr(H), H.shape[0], float(eps_rel),
                                                      int(max_nodes), _vp(d_val), _vp(d_t_star), _vp(d_status)), "obtg_bern_keep_out_dev")
+
+    # -- moving keep-out obstacles (include/obtg.h "moving keep-out obstacles"): motion = (Q, q_off[O+1], T[O]) -- Q the
+    # obstacles' [dim][m_o+1] control-point blocks one after the other, flat; q_off in control points, an empty run for an
+    # obstacle that stands still -- sent like `obstacles`, only when its bytes differ from what the context holds
+    def set_keep_out_motion(self, Q, q_off, T):
+        """obtg_ctx_set_keep_out_motion: the offset curves of the keep-out tables' obstacles; an empty q_off clears them."""
+        Q, q_off, T = _f64(Q).reshape(-1), _i32(q_off).reshape(-1), _f64(T).reshape(-1)
+        self._check(self._lib.obtg_ctx_set_keep_out_motion(self._h, _ptr(Q), _ptr(q_off), _ptr(T), max(q_off.shape[0] - 1, 0)),
+                    "obtg_ctx_set_keep_out_motion")
+        self._keep_out_motion_key = (Q.tobytes(), q_off.tobytes(), T.tobytes()) if q_off.shape[0] > 1 else None
+
+    def _keep_out_motion(self, obstacles, motion):
+        P = self._keep_out(obstacles)
+        if motion is not None:
+            Q, q_off, T = _f64(motion[0]).reshape(-1), _i32(motion[1]).reshape(-1), _f64(motion[2]).reshape(-1)
+            if self._keep_out_motion_key != (Q.tobytes(), q_off.tobytes(), T.tobytes()):
+                self.set_keep_out_motion(Q, q_off, T)
+        return P
+
+    def _keep_out_moving_call(self, name, Y, tf, obstacles, motion, margin, eps_rel, max_nodes, jac):
+        P = self._keep_out_motion(obstacles, motion)
+        Y, B = self._rows(Y)
+        tf = np.ascontiguousarray(np.broadcast_to(_f64(tf).reshape(-1), (B,)))
+        r = dict(val=pinned_empty((B, P)), t_star=np.empty((B, P)), face=np.zeros((B, P, 2), np.int32), lam=np.empty((B, P)),
+                 bound=np.empty((B, P)), nodes=np.zeros((B, P), np.int32), status=np.zeros((B, P), np.int32),
+                 rel=np.empty((B, P, self.dim, self.deg + 1)))
+        if jac:
+            r["jac"] = pinned_empty((B, P, self.dim, self.deg + 1))
+            r["jac_tf"] = np.empty((B, P))
+        self._check(getattr(self._lib, name)(self._h, _ptr(Y), _ptr(tf), B, float(margin), float(eps_rel), int(max_nodes),
+                                             *[_ptr(a) for a in r.values()]), name)
+        return r
+
+    def keep_out_moving_true_min(self, Y, tf, obstacles=None, motion=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
+        """keep_out_true_min against obstacles that translate along Bezier offsets (obtg_keep_out_moving_true_min): per
+        (vehicle, obstacle) item the static row of the relative curve c_v(s) - q_o(s tf), tf[B] the rows' spans.  The dict of
+        keep_out_true_min and rel[B][P][dim][deg+1], the relative control points the search ran on."""
+        return self._keep_out_moving_call("obtg_keep_out_moving_true_min", Y, tf, obstacles, motion, margin, eps_rel, max_nodes, False)
+
+    def keep_out_moving_true_min_jac(self, Y, tf, obstacles=None, motion=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
+        """keep_out_moving_true_min with its envelope Jacobian (obtg_keep_out_moving_true_min_jac): the same dict, bit for bit,
+        jac[B][P][dim][deg+1] (d/d the item's own vehicle's control points) and jac_tf[B][P], the explicit d/dtf."""
+        return self._keep_out_moving_call("obtg_keep_out_moving_true_min_jac", Y, tf, obstacles, motion, margin, eps_rel, max_nodes, True)
+
+    def keep_out_moving_true_min_dev(self, dY, d_tf, B, d_out, d_t_star=None, d_face=None, d_lam=None, d_bound=None, d_nodes=None,
+                                     d_status=None, d_rel=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
+        self._check(self._lib.obtg_keep_out_moving_true_min_dev(
+            self._h, _vp(dY), _vp(d_tf), int(B), float(margin), float(eps_rel), int(max_nodes),
+            *[_vp(q) for q in (d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel)]), "obtg_keep_out_moving_true_min_dev")
+
+    def keep_out_moving_true_min_jac_dev(self, dY, d_tf, B, d_out, d_jac, d_jac_tf, d_t_star=None, d_face=None, d_lam=None, d_bound=None,
+                                         d_nodes=None, d_status=None, d_rel=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
+        self._check(self._lib.obtg_keep_out_moving_true_min_jac_dev(
+            self._h, _vp(dY), _vp(d_tf), int(B), float(margin), float(eps_rel), int(max_nodes),
+            *[_vp(q) for q in (d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel, d_jac, d_jac_tf)]),
+            "obtg_keep_out_moving_true_min_jac_dev")
+
+    def bern_keep_out_moving(self, c, H, Q, r=None, eps_rel=1e-9, max_nodes=100000):
+        """The clearance of free curves c[M][dim][K] from ONE convex obstacle H[F][dim+1] that moves by the offset curve
+        Q[dim][Km], Km <= K; r[M]: the part [0, r] of the motion's parameter each curve spans (None: 1)
+        (obtg_bern_keep_out_moving): dict(val[M], t_star[M], status[M])."""
+        c = _f64(c)
+        if c.ndim == 2:
+            c = c[None]
+        M, dim, K = c.shape
+        H = _f64(H).reshape(-1, dim + 1)
+        Q = _f64(Q).reshape(dim, -1)
+        if r is not None:
+            r = np.ascontiguousarray(np.broadcast_to(_f64(r).reshape(-1), (M,)))
+        out = dict(val=np.empty(M), t_star=np.empty(M), status=np.zeros(M, np.int32))
+        self._check(self._lib.obtg_bern_keep_out_moving(self._h, _ptr(c), M, dim, K, _ptr(H), H.shape[0], _ptr(Q), Q.shape[1],
+                                                        None if r is None else _ptr(r), float(eps_rel), int(max_nodes),
+                                                        *[_ptr(a) for a in out.values()]), "obtg_bern_keep_out_moving")
+        return out
+
+    def bern_keep_out_moving_dev(self, d_c, M, dim, K, H, Q, d_val, d_r=None, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
+        H = _f64(H).reshape(-1, int(dim) + 1)
+        Q = _f64(Q).reshape(int(dim), -1)
+        self._check(self._lib.obtg_bern_keep_out_moving_dev(self._h, _vp(d_c), int(M), int(dim), int(K), _ptr(H), H.shape[0], _ptr(Q),
+                                                            Q.shape[1], _vp(d_r), float(eps_rel), int(max_nodes), _vp(d_val),
+                                                            _vp(d_t_star), _vp(d_status)), "obtg_bern_keep_out_moving_dev")
 
     def jerk(self, Y, tf, bound):
         """The jerk-bound rows (obtg_jerk): [B][N * (2 deg + DEG_ELEV + 1)] control points of

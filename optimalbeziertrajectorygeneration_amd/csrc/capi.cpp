@@ -257,6 +257,7 @@ const char* obtg_abi_symbols(void)
         "obtg_space_curvature_poly\0obtg_space_curvature_poly_dev\0obtg_space_curvature_true_min\0obtg_space_curvature_true_min_dev\0obtg_space_curvature_true_min_jac\0obtg_space_curvature_true_min_jac_dev\0obtg_bern_space_curvature\0obtg_bern_space_curvature_dev\0"
         "obtg_ctx_set_keep_in\0obtg_len_keep_in\0obtg_keep_in\0obtg_keep_in_dev\0obtg_keep_in_true_min\0obtg_keep_in_true_min_dev\0obtg_keep_in_true_min_jac\0obtg_keep_in_true_min_jac_dev\0"
         "obtg_ctx_set_keep_out\0obtg_len_keep_out\0obtg_keep_out_true_min\0obtg_keep_out_true_min_dev\0obtg_keep_out_true_min_jac\0obtg_keep_out_true_min_jac_dev\0obtg_bern_keep_out\0obtg_bern_keep_out_dev\0"
+        "obtg_ctx_set_keep_out_motion\0obtg_keep_out_moving_true_min\0obtg_keep_out_moving_true_min_dev\0obtg_keep_out_moving_true_min_jac\0obtg_keep_out_moving_true_min_jac_dev\0obtg_bern_keep_out_moving\0obtg_bern_keep_out_moving_dev\0"
         "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_restrict\0obtg_bern_eval\0"
         "obtg_euclidean_obj\0obtg_accel_obj\0obtg_jerk_obj\0"
         "obtg_bern_arc_length\0obtg_bern_arc_length_dev\0obtg_arc_length_obj\0obtg_arc_length_obj_dev\0"
@@ -325,7 +326,7 @@ void obtg_ctx_destroy(obtg_ctx* c)
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
     DevBuf* bufs[] = { &c->d_pairs, &c->d_obs, &c->d_w2, &c->d_Tt, &c->d_Td, &c->d_Tf, &c->d_ang_dd, &c->d_ang_flags, &c->d_vp_off, &c->d_vp_idx, &c->d_ang_w2n, &c->d_ang_w22n, &c->d_ang_wn, &c->d_ang_rows, &c->d_curv_tab, &c->d_ang_T4, &c->d_ang_cv2, &c->d_jac,
                        &c->d_binrows, &c->d_tiles, &c->d_poly_pts, &c->d_poly_off, &c->d_hp_a, &c->d_hp_b, &c->d_tile_chunk_off, &c->d_tile_order, &c->d_tile_pslots,
-                       &c->d_tile_cobj_off, &c->d_tile_cobjs, &c->d_tile_ij, &c->d_struct_tickets, &c->d_keep_H, &c->d_keep_VF, &c->d_ko_H, &c->d_ko_off, &c->d_ko_VO, &c->ws_in,
+                       &c->d_tile_cobj_off, &c->d_tile_cobjs, &c->d_tile_ij, &c->d_struct_tickets, &c->d_keep_H, &c->d_keep_VF, &c->d_ko_H, &c->d_ko_off, &c->d_ko_VO, &c->d_ko_Q, &c->d_ko_qoff, &c->d_ko_T, &c->ws_in,
                        &c->ws_in2, &c->ws_out, &c->ws_fd };
     for (DevBuf* b : bufs) b->release();
     for (auto& b : c->ws_misc) b.release();
@@ -2132,6 +2133,7 @@ int obtg_ctx_set_keep_out(obtg_ctx* c, const double* H, const int* obs_off, int 
     (void)hipSetDevice(c->device);
     OBTG_HIP(c, hipStreamSynchronize(c->stream));
     c->ko_F = c->ko_O = c->ko_P = 0;       // (set again once the tables are on the device)
+    c->ko_motion = false;                  // new tables: every obstacle stands still until obtg_ctx_set_keep_out_motion says otherwise
     if (P == 0) return OBTG_OK;
     int rc = upload(c, c->d_ko_H, H, sizeof(double) * (size_t)F * (c->dim + 1));
     if (!rc) rc = upload(c, c->d_ko_off, obs_off, sizeof(int) * ((size_t)O + 1));
@@ -2257,6 +2259,175 @@ int obtg_bern_keep_out(obtg_ctx* c, const double* cv, int M, int dim, int K, con
     int* ds = h.out<int>(c->ws_misc[WS_STATUS], n);
     h.run([&] { return launch_keep_out(c, dim, K, d_c, M, 1, 1, dH.as<double>(), nullptr, nullptr, F, 0.0, eps_rel, max_nodes, dv, dv + n,
                                        nullptr, nullptr, nullptr, nullptr, ds, nullptr, OBTG_K_SPEED); });
+    h.fetch(t_star, dv + n, n);
+    h.fetch(status, ds, n);
+    return h.finish(val, dv, n);
+}
+
+// Moving keep-out obstacles (include/obtg.h "moving keep-out obstacles"): obstacle o's faces are translated by a Bezier offset
+// on [0, T_o]; the search runs on the relative curve, formed per item in the kernel's prologue (tf differs per batch row).
+// The motion lives beside the keep-out tables and goes when they are set again.
+int obtg_ctx_set_keep_out_motion(obtg_ctx* c, const double* Q, const int* q_off, const double* T, int O)
+{
+    if (!check_ctx(c) || O < 0) return OBTG_ERR_ARG;
+    if (O > 0) {
+        if (c->ko_P <= 0 || O != c->ko_O || !q_off || !T || q_off[0] != 0) return OBTG_ERR_ARG;
+        for (int o = 0; o < O; ++o) {
+            if (q_off[o + 1] < q_off[o]) return OBTG_ERR_ARG;
+            if (q_off[o + 1] > q_off[o] && !(T[o] > 0.0 && std::isfinite(T[o]))) return OBTG_ERR_ARG;
+        }
+        if (q_off[O] > 0 && !Q) return OBTG_ERR_ARG;
+        for (int o = 0; o < O; ++o)
+            if (q_off[o + 1] - q_off[o] > c->deg + 1) return OBTG_ERR_UNSUPPORTED;
+    }
+    (void)hipSetDevice(c->device);
+    OBTG_HIP(c, hipStreamSynchronize(c->stream));
+    c->ko_motion = false;
+    if (O == 0) return OBTG_OK;
+    const size_t nq = (size_t)q_off[O] * c->dim;
+    const double none = 0.0;
+    int rc = upload(c, c->d_ko_Q, nq ? Q : &none, sizeof(double) * (nq ? nq : 1));
+    if (!rc) rc = upload(c, c->d_ko_qoff, q_off, sizeof(int) * ((size_t)O + 1));
+    if (!rc) rc = upload(c, c->d_ko_T, T, sizeof(double) * (size_t)O);
+    if (rc) return rc;
+    c->ko_motion = true;
+    return OBTG_OK;
+}
+
+// (the entry points below refuse a context without a motion, OBTG_ERR_ARG: that is a caller who forgot to set one, not a
+// request for the static rows)
+static int keep_out_moving_launch(obtg_ctx* c, const double* dY, const double* d_tf, int B, double margin, double eps_rel, int max_nodes,
+                                  double* d_out, double* d_t, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status,
+                                  double* d_rel, double* d_jac, double* d_jac_tf)
+{
+    KeepOutMotionArgs mo{};
+    mo.d_Q = c->d_ko_Q.as<double>(); mo.d_q_off = c->d_ko_qoff.as<int>(); mo.d_T = c->d_ko_T.as<double>(); mo.d_tf = d_tf;
+    mo.d_rel = d_rel; mo.d_jac_tf = d_jac_tf;
+    return launch_keep_out_moving(c, c->dim, c->deg + 1, dY, (long)B * c->ko_P, c->n_veh, c->ko_P, c->d_ko_H.as<double>(),
+                                  c->d_ko_off.as<int>(), c->d_ko_VO.as<int>(), 0, &mo, margin, eps_rel, max_nodes, d_out, d_t, d_face,
+                                  d_lam, d_bound, d_nodes, d_status, d_jac, OBTG_K_SPEED);
+}
+
+static int keep_out_moving_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double margin, double eps_rel, int max_nodes,
+                               double* d_out, double* d_t, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status,
+                               double* d_rel, bool want_jac, double* d_jac, double* d_jac_tf)
+{
+    if (int rc = keep_out_args(c, d_out, B, max_nodes, eps_rel, margin)) return rc;
+    if (!c->ko_motion || !dY || !d_tf || (want_jac && (!d_jac || !d_jac_tf))) return OBTG_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    return keep_out_moving_launch(c, dY, d_tf, B, margin, eps_rel, max_nodes, d_out, d_t, d_face, d_lam, d_bound, d_nodes, d_status,
+                                  d_rel, d_jac, d_jac_tf);
+}
+
+// the host body: Y and tf up; val | t_star | lam | bound | jac_tf | rel | jac in ws_out, face | nodes | status in WS_STATUS
+static int keep_out_moving(obtg_ctx* c, const double* Y, const double* tf, int B, double margin, double eps_rel, int max_nodes,
+                           double* out, double* t_star, int* face, double* lam, double* bound, int* nodes, int* status, double* rel,
+                           bool want_jac, double* jac, double* jac_tf)
+{
+    if (int rc = keep_out_args(c, out, B, max_nodes, eps_rel, margin)) return rc;
+    if (!c->ko_motion || !Y || !tf || (want_jac && (!jac || !jac_tf))) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    const size_t n = (size_t)B * c->ko_P, nb = n * c->dim * (c->deg + 1), nr = rel ? nb : 0, nj = want_jac ? nb : 0;
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    const double* d_tf = h.in(c->ws_in2, tf, (size_t)B, true);
+    double* dv = h.out<double>(c->ws_out, 5 * n + nr + nj);
+    int* di = h.out<int>(c->ws_misc[WS_STATUS], 4 * n);
+    double* dr = rel ? dv + 5 * n : nullptr;
+    double* dj = want_jac ? dv + 5 * n + nr : nullptr;
+    h.run([&] { return keep_out_moving_launch(c, dY, d_tf, B, margin, eps_rel, max_nodes, dv, dv + n, di, dv + 2 * n, dv + 3 * n, di + 2 * n,
+                                              di + 3 * n, dr, dj, want_jac ? dv + 4 * n : nullptr); });
+    h.fetch(t_star, dv + n, n);
+    h.fetch(lam, dv + 2 * n, n);
+    h.fetch(bound, dv + 3 * n, n);
+    if (want_jac) h.fetch(jac_tf, dv + 4 * n, n);
+    h.fetch(face, di, 2 * n);
+    h.fetch(nodes, di + 2 * n, n);
+    h.fetch(status, di + 3 * n, n);
+    h.fetch(rel, dr, nr);
+    if (want_jac) h.fetch(jac, dj, nj);
+    return h.finish(out, dv, n);
+}
+
+int obtg_keep_out_moving_true_min_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double margin, double eps_rel, int max_nodes,
+                                      double* d_out, double* d_t_star, int* d_face, double* d_lam, double* d_bound, int* d_nodes,
+                                      int* d_status, double* d_rel)
+{
+    return keep_out_moving_dev(c, dY, d_tf, B, margin, eps_rel, max_nodes, d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel,
+                               false, nullptr, nullptr);
+}
+
+int obtg_keep_out_moving_true_min(obtg_ctx* c, const double* Y, const double* tf, int B, double margin, double eps_rel, int max_nodes,
+                                  double* out, double* t_star, int* face, double* lam, double* bound, int* nodes, int* status, double* rel)
+{
+    return keep_out_moving(c, Y, tf, B, margin, eps_rel, max_nodes, out, t_star, face, lam, bound, nodes, status, rel, false, nullptr,
+                           nullptr);
+}
+
+int obtg_keep_out_moving_true_min_jac_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double margin, double eps_rel,
+                                          int max_nodes, double* d_out, double* d_t_star, int* d_face, double* d_lam, double* d_bound,
+                                          int* d_nodes, int* d_status, double* d_rel, double* d_jac, double* d_jac_tf)
+{
+    return keep_out_moving_dev(c, dY, d_tf, B, margin, eps_rel, max_nodes, d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel,
+                               true, d_jac, d_jac_tf);
+}
+
+int obtg_keep_out_moving_true_min_jac(obtg_ctx* c, const double* Y, const double* tf, int B, double margin, double eps_rel, int max_nodes,
+                                      double* out, double* t_star, int* face, double* lam, double* bound, int* nodes, int* status,
+                                      double* rel, double* jac, double* jac_tf)
+{
+    return keep_out_moving(c, Y, tf, B, margin, eps_rel, max_nodes, out, t_star, face, lam, bound, nodes, status, rel, true, jac, jac_tf);
+}
+
+// Free curves cv[M][dim][K] against ONE obstacle H[F][dim+1] that moves by Q[dim][Km] (H and Q host arrays in both forms); r[M]:
+// per curve the part [0, r] of the motion's parameter that the curve spans (null: 1); a host array, device memory in the _dev form.
+static int bern_keep_out_moving_args(const obtg_ctx* c, const double* cv, int M, int dim, int K, const double* H, int F, const double* Q,
+                                     int Km, double eps_rel, int max_nodes, const double* val)
+{
+    if (int chk = bern_keep_out_args(c, cv, M, dim, K, H, F, eps_rel, max_nodes, val)) {
+        if (chk != kNothingToDo) return chk;
+        return (Km < 1 || !Q) ? OBTG_ERR_ARG : Km > K ? OBTG_ERR_UNSUPPORTED : kNothingToDo;
+    }
+    if (Km < 1 || !Q) return OBTG_ERR_ARG;
+    return Km > K ? OBTG_ERR_UNSUPPORTED : OBTG_OK;
+}
+
+static int bern_keep_out_moving_launch(obtg_ctx* c, const double* d_c, int M, int dim, int K, const double* dH, int F, const double* dQ,
+                                       int Km, const double* d_r, double eps_rel, int max_nodes, double* d_val, double* d_t, int* d_status)
+{
+    KeepOutMotionArgs mo{};
+    mo.d_Q = dQ; mo.Km = Km; mo.d_r = d_r;
+    return launch_keep_out_moving(c, dim, K, d_c, M, 1, 1, dH, nullptr, nullptr, F, &mo, 0.0, eps_rel, max_nodes, d_val, d_t, nullptr,
+                                  nullptr, nullptr, nullptr, d_status, nullptr, OBTG_K_SPEED);
+}
+
+int obtg_bern_keep_out_moving_dev(obtg_ctx* c, const double* d_c, int M, int dim, int K, const double* H, int F, const double* Q, int Km,
+                                  const double* d_r, double eps_rel, int max_nodes, double* d_val, double* d_t_star, int* d_status)
+{
+    if (int chk = bern_keep_out_moving_args(c, d_c, M, dim, K, H, F, Q, Km, eps_rel, max_nodes, d_val)) return done(chk);
+    (void)hipSetDevice(c->device);
+    DevBuf &dH = c->ws_misc[WS_ARG_A], &dQ = c->ws_misc[WS_ARG_B];
+    if (int rc = upload(c, dH, H, sizeof(double) * (size_t)F * (dim + 1))) return rc;
+    if (int rc = upload(c, dQ, Q, sizeof(double) * (size_t)Km * dim)) return rc;
+    return bern_keep_out_moving_launch(c, d_c, M, dim, K, dH.as<double>(), F, dQ.as<double>(), Km, d_r, eps_rel, max_nodes, d_val, d_t_star,
+                                       d_status);
+}
+
+int obtg_bern_keep_out_moving(obtg_ctx* c, const double* cv, int M, int dim, int K, const double* H, int F, const double* Q, int Km,
+                              const double* r, double eps_rel, int max_nodes, double* val, double* t_star, int* status)
+{
+    if (int chk = bern_keep_out_moving_args(c, cv, M, dim, K, H, F, Q, Km, eps_rel, max_nodes, val)) return done(chk);
+    const size_t n = (size_t)M;
+    HostCall h(c);
+    DevBuf &dH = c->ws_misc[WS_ARG_A], &dQ = c->ws_misc[WS_ARG_B];
+    if (int rc = upload(c, dH, H, sizeof(double) * (size_t)F * (dim + 1))) return rc;
+    if (int rc = upload(c, dQ, Q, sizeof(double) * (size_t)Km * dim)) return rc;
+    const double* d_c = h.in(c->ws_in, cv, n * dim * K);
+    const double* d_r = r ? h.in(c->ws_in2, r, n) : nullptr;
+    double* dv = h.out<double>(c->ws_out, 2 * n);
+    int* ds = h.out<int>(c->ws_misc[WS_STATUS], n);
+    h.run([&] { return bern_keep_out_moving_launch(c, d_c, M, dim, K, dH.as<double>(), F, dQ.as<double>(), Km, d_r, eps_rel, max_nodes, dv,
+                                                   dv + n, ds); });
     h.fetch(t_star, dv + n, n);
     h.fetch(status, ds, n);
     return h.finish(val, dv, n);

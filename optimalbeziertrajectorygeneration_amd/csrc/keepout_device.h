@@ -9,6 +9,8 @@
 #include <cfloat>
 #include <cmath>
 
+#include "md_device.h"
+
 namespace obtg {
 
 constexpr int kKoMaxFaces = 16;      // faces per obstacle (above: OBTG_ERR_UNSUPPORTED)
@@ -99,6 +101,33 @@ __device__ __forceinline__ KoActive keep_out_active(const double* __restrict__ h
     }
     if (a.f2 >= 0) a.lam1 = s2 / (s2 - s1);
     return a;
+}
+
+// A moving obstacle's offset on the vehicle's parameter, E(s) = q(s r) with r = tf / T_o, at the vehicle's degree: lane i
+// returns E_i for i < K and 0 above (include/obtg.h "moving keep-out obstacles" fixes this arithmetic).  q: the Km = m + 1
+// control points of one coordinate of the motion, 1 <= Km <= K; every argument but `lane` is wave-uniform.
+//   restriction to [0, r]: de Casteljau at r, each level b = fma(r, up, (1 - r) b) with 1 - r rounded once; point j of the
+//       left piece is lane 0's value after level j.  r == 1: fma(1, up, 0 b) = up, the identity.  r > 1: the polynomial's
+//       continuation, the same instructions;
+//   elevation: K - Km single-degree steps, degree k -> k + 1: E_i = fma(w, E_(i-1), (1 - w) E_i), w = (double)i / (k + 1);
+//       w = 0 at i = 0 and w = 1 at i = k + 1 (lane k + 1 holds 0 before the step), so the ends are exact.
+__device__ __forceinline__ double keep_out_motion_points(const double* __restrict__ q, const int Km, const int K, const double r,
+                                                         const int lane)
+{
+    double b = lane < Km ? q[lane] : 0.0, l = b;
+    const double omr = 1.0 - r;
+    for (int lv = 1; lv < Km; ++lv) {
+        const double up = wave_next_lane(b);
+        if (lane <= Km - 1 - lv) b = __builtin_fma(r, up, omr * b);
+        const double first = ko_lane(b, 0);
+        if (lane == lv) l = first;
+    }
+    for (int k = Km - 1; k < K - 1; ++k) {
+        const double prev = __shfl_up(l, 1);
+        const double w = (double)lane / (double)(k + 1);
+        if (lane <= k + 1) l = __builtin_fma(w, prev, (1.0 - w) * l);
+    }
+    return l;
 }
 
 // One level of the de Casteljau recurrence on the Bernstein basis held a lane per index (lane i: B_i), the arithmetic of

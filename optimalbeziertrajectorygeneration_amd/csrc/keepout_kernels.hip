@@ -21,6 +21,13 @@
 // kernel: the value call and the _jac call run the same instructions up to there, so they agree bit for bit; an item's
 // outputs depend on its control points, its faces, margin, eps_rel and max_nodes alone.
 // No finishing step (a monotone root of g_f1 - g_f2) is built: convergence at a kink is linear.
+//
+// Moving obstacles (obtg_keep_out_moving_*; KeepOutMovingParams): the same body on the RELATIVE curve
+// D = P - E, E the obstacle's offset q(s tf) at the vehicle's degree (keep_out_motion_points).  A prologue forms E and D a lane
+// per control point and leaves them in LDS beside the faces (2 DIM K doubles per wave); the root reads D from its registers and
+// the evaluation at t_star reads it from LDS where the static form reads the item's control points -- everything between is
+// the code above, the same instructions.  One more nullable output, jac_tf = -(a^ . E'(t_star)) t_star / tf.  The static
+// instantiation has no prologue, no extra LDS and no extra argument.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -49,37 +56,83 @@ struct KeepOutParams {
     long M;
     int n_veh, P, K, F_all, max_nodes;
     double margin, eps_rel;
+    static constexpr bool kMoving = false;
 };
 
-template <int DIM>
-__global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const KeepOutParams p)
+struct KeepOutMovingParams : KeepOutParams {
+    const double* __restrict__ Q;        // the obstacles' [DIM][m_o + 1] blocks, one after the other; free curves: [DIM][Km]
+    const int* __restrict__ q_off;       // [O + 1], in control points; an empty run: the obstacle stands still
+    const double* __restrict__ T;        // [O]: the motions' spans
+    const double* __restrict__ tf;       // [B]: the vehicles' spans
+    const double* __restrict__ r;        // free curves: [M] the ratios, null: 1
+    double* __restrict__ rel;            // [M][DIM][K] nullable: the relative control points
+    double* __restrict__ jac_tf;         // [M] nullable
+    int Km;                              // free curves: the motion's control points
+    static constexpr bool kMoving = true;
+};
+
+template <int DIM, class PRM>
+__global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const PRM p)
 {
+    constexpr bool MV = PRM::kMoving;
     extern __shared__ double lds[];
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     const int K = p.K, pitch = DIM * K + 3;
-    double* stk = lds + (size_t)wave * (kKoStack * pitch + kKoMaxFaces * (DIM + 1));
+    double* stk = lds + (size_t)wave * (kKoStack * pitch + kKoMaxFaces * (DIM + 1) + (MV ? 2 * DIM * K : 0));
     double* hf = stk + kKoStack * pitch;
+    double* ed = hf + kKoMaxFaces * (DIM + 1);     // MV: E[DIM][K] | D[DIM][K]
     const long item = (long)blockIdx.x * kKoWaves + wave;
     if (item >= p.M) return;                       // (wave-uniform; the kernel has no workgroup barrier)
 
     int f0 = 0, F = p.F_all;
     const double* y;
+    const double* q = nullptr;                     // MV: the obstacle's motion, Km control points per coordinate (0: none)
+    int Km = 0;
+    double tf_b = 1.0, ratio = 1.0;
     if (p.VO) {
         const long b = item / p.P;
         const int2 vo = p.VO[(int)(item - b * p.P)];
         f0 = p.obs_off[vo.y];
         F = p.obs_off[vo.y + 1] - f0;
         y = p.Y + ((size_t)b * p.n_veh + vo.x) * (DIM * K);
+        if constexpr (MV) {
+            const int q0 = p.q_off[vo.y];
+            Km = p.q_off[vo.y + 1] - q0;
+            q = p.Q + (size_t)DIM * q0;
+            if (Km > 0) { tf_b = p.tf[b]; ratio = tf_b / p.T[vo.y]; }
+        }
     } else {
         y = p.Y + (size_t)item * (DIM * K);
+        if constexpr (MV) {
+            Km = p.Km; q = p.Q;
+            if (p.r) ratio = p.r[item];
+            tf_b = ratio;
+        }
     }
     for (int k = lane; k < F * (DIM + 1); k += kWave) hf[k] = p.H[(size_t)f0 * (DIM + 1) + k];
-    ko_wave_sync();
 
     // ---- the root (node 1)
     double x[DIM];
+    bool bad_m = false;
+    if constexpr (MV) {
+        // the relative curve: E from the motion, D = P - E, both kept for the evaluations at t_star
+        bad_m = Km > 0 && !(tf_b > 0.0 && tf_b <= DBL_MAX && ratio > 0.0 && ratio <= DBL_MAX);
 #pragma unroll
-    for (int c = 0; c < DIM; ++c) x[c] = lane < K ? y[c * K + lane] : 0.0;
+        for (int c = 0; c < DIM; ++c) {
+            const double e = Km > 0 ? keep_out_motion_points(q + c * Km, Km, K, ratio, lane) : 0.0;
+            const double d = (lane < K ? y[c * K + lane] : 0.0) - e;
+            if (lane < K) {
+                ed[c * K + lane] = e;
+                ed[(DIM + c) * K + lane] = d;
+            }
+            x[c] = d;
+        }
+    }
+    ko_wave_sync();
+    if constexpr (!MV) {
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) x[c] = lane < K ? y[c * K + lane] : 0.0;
+    }
     double gm = -INFINITY, lb = -INFINITY, s = 0.0;
     bool bad = false;
     for (int f = 0; f < F; ++f) {
@@ -90,6 +143,13 @@ __global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const KeepOutPara
         lb = fmax(lb, ko_lane(m, kKoLowLast));
     }
     bad = __any(bad) != 0;
+    if constexpr (MV) {
+        bad = bad || bad_m;
+        if (p.rel && lane < K) {                   // (x is still the root: D itself)
+#pragma unroll
+            for (int c = 0; c < DIM; ++c) p.rel[(size_t)item * (DIM * K) + c * K + lane] = bad ? __builtin_nan("") : x[c];
+        }
+    }
     s = ko_wave_max(s);
     const double tol = p.eps_rel * s;
     const double G0 = ko_lane(gm, 0), G1 = ko_lane(gm, K - 1);
@@ -189,7 +249,7 @@ __global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const KeepOutPara
         bound = lb;
     }
 
-    // ---- the active faces at t_star: c(t_star) and c'(t_star) from the item's own control points
+    // ---- the active faces at t_star: c(t_star) and c'(t_star) from the item's own control points (MV: the relative ones)
     const double nan = __builtin_nan("");
     KoActive a;
     a.f1 = -1; a.f2 = -1; a.lam1 = nan;
@@ -199,7 +259,9 @@ __global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const KeepOutPara
         double pt[DIM], dir[DIM];
 #pragma unroll
         for (int c = 0; c < DIM; ++c) {
-            double b = lane < K ? y[c * K + lane] : 0.0;
+            double b;
+            if constexpr (MV) b = lane < K ? ed[(DIM + c) * K + lane] : 0.0;
+            else b = lane < K ? y[c * K + lane] : 0.0;
             for (int r = 1; r < K - 1; ++r) {
                 const double up = wave_next_lane(b);
                 b = __builtin_fma(ts, up, sc * b);
@@ -219,6 +281,29 @@ __global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const KeepOutPara
         if (p.bound) p.bound[item] = bound - p.margin;
         if (p.nodes) p.nodes[item] = nodes;
         if (p.status) p.status[item] = status;
+    }
+    if constexpr (MV) {
+        // ---- d row / d tf = -(a^ . E'(t_star)) t_star / tf, E' by de Casteljau on E; an obstacle that stands still: an exact 0
+        if (p.jac_tf) {
+            double jt = bad ? nan : 0.0;
+            if (!bad && Km > 0) {
+                const double ts = tU, sc = 1.0 - ts;
+                double dE[DIM], ah[DIM];
+#pragma unroll
+                for (int c = 0; c < DIM; ++c) {
+                    double b = lane < K ? ed[c * K + lane] : 0.0;
+                    for (int r = 1; r < K - 1; ++r) {
+                        const double up = wave_next_lane(b);
+                        b = __builtin_fma(ts, up, sc * b);
+                    }
+                    dE[c] = (double)(K - 1) * (ko_lane(b, 1) - ko_lane(b, 0));
+                    ah[c] = hf[a.f1 * (DIM + 1) + c];
+                    if (a.f2 >= 0) ah[c] = __builtin_fma(a.lam1, ah[c], (1.0 - a.lam1) * hf[a.f2 * (DIM + 1) + c]);
+                }
+                jt = -(keep_out_slope<DIM>(ah, dE) * ts / tf_b);
+            }
+            if (lane == 0) p.jac_tf[item] = jt;
+        }
     }
     if (!p.jac) return;
     // ---- the envelope block: the basis a lane per index
@@ -247,16 +332,35 @@ int launch_keep_out(obtg_ctx* c, int dim, int K, const double* dY, long M, int n
                     const int* d_VO, int F_all, double margin, double eps_rel, int max_nodes, double* d_val, double* d_t, int* d_face,
                     double* d_lam, double* d_bound, int* d_nodes, int* d_status, double* d_jac, int kernel_id)
 {
+    return launch_keep_out_moving(c, dim, K, dY, M, n_veh, P, d_H, d_off, d_VO, F_all, nullptr, margin, eps_rel, max_nodes, d_val, d_t,
+                                  d_face, d_lam, d_bound, d_nodes, d_status, d_jac, kernel_id);
+}
+
+// mo null: the static form.  mo->Q | q_off | T | tf | r: device tables; mo->rel, mo->jac_tf: nullable outputs
+int launch_keep_out_moving(obtg_ctx* c, int dim, int K, const double* dY, long M, int n_veh, int P, const double* d_H, const int* d_off,
+                           const int* d_VO, int F_all, const KeepOutMotionArgs* mo, double margin, double eps_rel, int max_nodes,
+                           double* d_val, double* d_t, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status,
+                           double* d_jac, int kernel_id)
+{
     if (M <= 0) return OBTG_OK;
     if ((dim != 2 && dim != 3) || K < 2 || K > kKoMaxK) return OBTG_ERR_UNSUPPORTED;
-    KeepOutParams p{};
+    KeepOutMovingParams p{};
     p.Y = dY; p.H = d_H; p.obs_off = d_off; p.VO = (const int2*)d_VO;
     p.val = d_val; p.t = d_t; p.face = d_face; p.lam = d_lam; p.bound = d_bound; p.nodes = d_nodes; p.status = d_status; p.jac = d_jac;
     p.M = M; p.n_veh = n_veh; p.P = P; p.K = K; p.F_all = F_all; p.max_nodes = max_nodes; p.margin = margin; p.eps_rel = eps_rel;
-    const size_t lds = sizeof(double) * kKoWaves * ((size_t)kKoStack * (dim * K + 3) + kKoMaxFaces * (dim + 1));
+    const size_t lds = sizeof(double) * kKoWaves * ((size_t)kKoStack * (dim * K + 3) + kKoMaxFaces * (dim + 1) + (mo ? 2 * dim * K : 0));
+    const dim3 grid((unsigned)((M + kKoWaves - 1) / kKoWaves)), block(kKoWaves * kWave);
     ScopedKernelTimer t(c, kernel_id);
-    hipLaunchKernelGGL(dim == 2 ? k_keep_out<2> : k_keep_out<3>, dim3((unsigned)((M + kKoWaves - 1) / kKoWaves)), dim3(kKoWaves * kWave),
-                       lds, c->stream, p);
+    if (mo) {
+        p.Q = mo->d_Q; p.q_off = mo->d_q_off; p.T = mo->d_T; p.tf = mo->d_tf; p.r = mo->d_r; p.rel = mo->d_rel; p.jac_tf = mo->d_jac_tf;
+        p.Km = mo->Km;
+        void (*const kernel)(KeepOutMovingParams) = dim == 2 ? k_keep_out<2, KeepOutMovingParams> : k_keep_out<3, KeepOutMovingParams>;
+        hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, p);
+    } else {
+        void (*const kernel)(KeepOutParams) = dim == 2 ? k_keep_out<2, KeepOutParams> : k_keep_out<3, KeepOutParams>;
+        const KeepOutParams& ps = p;
+        hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, ps);
+    }
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;
 }

@@ -173,6 +173,11 @@ struct obtg_ctx {
     obtg::DevBuf d_ko_off;    // int[ko_O + 1]
     obtg::DevBuf d_ko_VO;     // int2[ko_P]
     int ko_F = 0, ko_O = 0, ko_P = 0;
+    // obtg_ctx_set_keep_out_motion: the obstacles' offset curves; ko_motion false: none set (every obstacle stands still)
+    obtg::DevBuf d_ko_Q;      // double: the [dim][m_o + 1] blocks, one after the other
+    obtg::DevBuf d_ko_qoff;   // int[ko_O + 1], in control points
+    obtg::DevBuf d_ko_T;      // double[ko_O]
+    bool ko_motion = false;
     std::vector<int> h_pairs; // host copy of the pair table (2 ints per pair)
     std::vector<int> h_tiles; // row-window tiles of the current (pair_begin, pair_count)
     obtg::DevBuf d_tiles;
@@ -437,6 +442,24 @@ int launch_keep_in_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B
 int launch_keep_out(obtg_ctx* c, int dim, int K, const double* dY, long M, int n_veh, int P, const double* d_H, const int* d_off,
                     const int* d_VO, int F_all, double margin, double eps_rel, int max_nodes, double* d_val, double* d_t, int* d_face,
                     double* d_lam, double* d_bound, int* d_nodes, int* d_status, double* d_jac, int kernel_id);
+// The same search against obstacles that move (obtg_keep_out_moving_*): mo null is launch_keep_out.  With tables (d_VO): d_Q the
+// obstacles' [dim][m_o + 1] blocks one after the other, d_q_off[O + 1] in control points (an empty run: the obstacle stands
+// still), d_T[O], d_tf[B]; free curves (d_VO null): d_Q[dim][Km], d_r[M] or null (1).  Km <= K is the callers' check.
+// d_rel[M][dim][K] and d_jac_tf[M] are nullable outputs.
+struct KeepOutMotionArgs {
+    const double* d_Q;
+    const int* d_q_off;
+    const double* d_T;
+    const double* d_tf;
+    const double* d_r;
+    int Km;
+    double* d_rel;
+    double* d_jac_tf;
+};
+int launch_keep_out_moving(obtg_ctx* c, int dim, int K, const double* dY, long M, int n_veh, int P, const double* d_H, const int* d_off,
+                           const int* d_VO, int F_all, const KeepOutMotionArgs* mo, double margin, double eps_rel, int max_nodes,
+                           double* d_val, double* d_t, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status,
+                           double* d_jac, int kernel_id);
 // the angular-rate family's polynomials [B][n_veh][2][2 deg + 1] (obtg_ang_rate_poly; its rows_r0): dim 2, degree 1 .. 31
 int launch_ang_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);
 // The two curvature families, kind = ROWS_CURV (dim 2; two items, the sides, per vehicle; workspace rows num, den) or ROWS_SCURV

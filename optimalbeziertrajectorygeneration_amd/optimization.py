@@ -301,6 +301,50 @@ def _keep_out_tables(keepOut, numVeh, dim):
     return (np.ascontiguousarray(np.vstack(tables)), np.ascontiguousarray(off, dtype=np.int32),
             np.ascontiguousarray(VO, dtype=np.int32))
 
+
+def _keep_out_motion_tables(keepOutMotion, keepOut, dim, deg, tf=None):
+    """(Q, q_off[O+1], T[O]) of a `keepOutMotion` argument, checked: a LIST with one entry per obstacle of `keepOut` -- None (the
+    obstacle stands still), a bezier.Bezier of the problem's dimension with t0 == 0 (the obstacle's offset on [0, tf]), or a pair
+    (cpts[dim][m+1], T).  Q holds the [dim][m+1] blocks one after the other, q_off counts control points, an empty run for None
+    (obtg_ctx_set_keep_out_motion).  tf: the span of a fixed-tf problem, which no motion may end before."""
+    if keepOut is None:
+        raise ValueError("keepOutMotion needs keepOut: there are no obstacles to move")
+    if not isinstance(keepOutMotion, (list, tuple)) or len(keepOutMotion) != len(keepOut):
+        raise ValueError("keepOutMotion must be a list with one entry per obstacle of keepOut ({}): None, a Bezier or a pair "
+                         "(cpts[{}][m+1], T)".format(len(keepOut), dim))
+    blocks, counts, spans = [], [], []
+    for o, entry in enumerate(keepOutMotion):
+        if entry is None:
+            counts.append(0)
+            spans.append(1.0)
+            continue
+        if isinstance(entry, bez.Bezier):
+            if entry.t0 != 0:
+                raise ValueError("keepOutMotion[{}] must start at t0 = 0, not {!r}".format(o, entry.t0))
+            cpts, T = np.asarray(entry.cpts, dtype=float), float(entry.tf)
+        else:
+            try:
+                cpts, T = entry
+                cpts, T = np.asarray(cpts, dtype=float), float(T)
+            except (TypeError, ValueError):
+                raise ValueError("keepOutMotion[{}] must be None, a Bezier or a pair (cpts[{}][m+1], T)".format(o, dim))
+        if cpts.ndim != 2 or cpts.shape[0] != dim or cpts.shape[1] < 1:
+            raise ValueError("keepOutMotion[{}] must have dimension {} (control points [{}][m+1]), not shape {}"
+                             .format(o, dim, dim, cpts.shape))
+        if cpts.shape[1] - 1 > deg:
+            raise ValueError("keepOutMotion[{}] has degree {}: a motion's degree may not be above the problem's, {}"
+                             .format(o, cpts.shape[1] - 1, deg))
+        if not (np.isfinite(T) and T > 0):
+            raise ValueError("keepOutMotion[{}] needs a finite span T > 0, not {!r}".format(o, T))
+        if tf is not None and T < tf:
+            raise ValueError("keepOutMotion[{}] ends at T = {!r}, before the problem's tf = {!r}".format(o, T, tf))
+        blocks.append(np.ascontiguousarray(cpts).reshape(-1))
+        counts.append(cpts.shape[1])
+        spans.append(T)
+    Q = np.concatenate(blocks) if blocks else np.zeros(0)
+    return (np.ascontiguousarray(Q), np.ascontiguousarray(np.cumsum([0] + counts), dtype=np.int32),
+            np.ascontiguousarray(spans, dtype=float))
+
 # The goals with a device call ('timeopt' is x[-1]).  goal, lower case: (key in _serve / _fd_values; values [B] of the rows Y;
 # gradient blocks [B][N d][n+1] of the rows Y), both called (bezopt, ctx, Y, what) -- `what` names the caller where a search
 # that does not end raises (the arc length alone).
@@ -448,7 +492,8 @@ class BezOptimization(object):
                  keepIn=None,
                  keepInRows='all',
                  keepOut=None,
-                 keepOutMargin=0.0):
+                 keepOutMargin=0.0,
+                 keepOutMotion=None):
         """Beyond the reference's keywords: `device` (HIP ordinal; None: this process's, see _capi.default_device) and `separationRows` --
         'all': temporalSeparationConstraints returns every elevated control point of every pair, as the
         reference does (optimization.py:337); 'min': one row per pair, the smallest of them -- the
@@ -509,6 +554,14 @@ class BezOptimization(object):
                 raise ValueError("keepOutMargin must be finite, not {!r}".format(keepOutMargin))
         self.keepOut = keepOut
         self.keepOutMargin = float(keepOutMargin)
+        # keepOutMotion (None: every obstacle stands still): one entry per obstacle of keepOut -- None, a bezier.Bezier with
+        # t0 == 0 or a pair (cpts[d][m+1], T): the obstacle's OFFSET as a function of absolute time on [0, T], translation only,
+        # of a degree no higher than the problem's.  The rows become those of the relative curve c_v(s) - q_o(s tf)
+        # (obtg_keep_out_moving_true_min) and, in a time-optimal problem, depend on tf.  Kept as `self.keepOutMotion`.
+        if keepOutMotion is not None:
+            _keep_out_motion_tables(keepOutMotion, keepOut, dimension, degree,
+                                    None if str(minimizeGoal).lower() == 'timeopt' else float(tf))
+        self.keepOutMotion = keepOutMotion
         if separationRows not in ('all', 'min', 'active', 'true_min'):
             raise ValueError("separationRows must be 'all', 'min', 'active' or 'true_min', not {!r}".format(separationRows))
         if separationRows == 'active' and not 1 <= int(activeRows) <= 4:
@@ -619,10 +672,19 @@ class BezOptimization(object):
     def _vehicle_true_min(self, fam, ctx, Y, tf, bound, what, envelope=False):
         """The family's true-minimum call on the rows Y at TRUE_MIN_EPS_REL (envelope: with the envelope blocks): its dict;
         a search that ran out of budget raises in the name of `what` (bezier._raise_md)"""
+        if fam is _KEEP_OUT and self.keepOutMotion is not None:       # moving obstacles: the rows of the relative curves, with tf
+            call = ctx.keep_out_moving_true_min_jac if envelope else ctx.keep_out_moving_true_min
+            return _md_checked(call(Y, tf, bound, self._keep_out_motion(), margin=self.keepOutMargin, eps_rel=self.TRUE_MIN_EPS_REL),
+                               what)
         call = getattr(ctx, fam.envelope if envelope else fam.true_min)
         operands = (Y, tf, bound) if fam.span else (Y, bound)
         beside = {'margin': self.keepOutMargin} if fam is _KEEP_OUT else {}
         return _md_checked(call(*operands, *fam.lead, eps_rel=self.TRUE_MIN_EPS_REL, **beside), what)
+
+    def _keep_out_motion(self):
+        """The motion's tables (Q, q_off, T) of `keepOutMotion` as it is NOW, checked against the problem as the constructor does"""
+        m = self.model
+        return _keep_out_motion_tables(self.keepOutMotion, self.keepOut, m['dim'], m['deg'], None if self._timeopt() else m['tf'])
 
     def _rows_option(self, fam):
         """'all' / 'true_min': the family's rows option; a family without a `rows` method has true rows only"""
@@ -892,7 +954,9 @@ class BezOptimization(object):
     @property
     def keepOutConstraints(self):
         """min over the trajectory of max_f (a_f . c_v - b_f) - keepOutMargin >= 0 for every (vehicle, obstacle) of `keepOut`,
-        vehicle-major: N * O true rows (obtg_keep_out_true_min) -- the same whatever tf is.  Conservative near corners (the row
+        vehicle-major: N * O true rows (obtg_keep_out_true_min) -- the same whatever tf is, unless `keepOutMotion` moves an
+        obstacle: then c_v is the curve relative to the obstacle's offset at the same moment, c_v(s) - q_o(s tf)
+        (obtg_keep_out_moving_true_min).  Conservative near corners (the row
         is at most the true distance minus the margin, with unit normals); negative, minus the depth, inside.  Not part of the
         one-launch structured step, of the constraint sweep, of distributed.py or of sequential.py."""
         return self._vehicle_closure(_KEEP_OUT)
@@ -1060,6 +1124,8 @@ class BezOptimization(object):
             tail.append(('keepIn', self.keepInRows, H.tobytes() + VF.tobytes()))
         if self.keepOut is not None:         # after keep-in's, likewise by the tables' bytes
             tail.append(('keepOut', self.keepOutMargin, b''.join(t.tobytes() for t in self._operand(_KEEP_OUT))))
+            if self.keepOutMotion is not None:      # one more entry, only while a motion is set: its control points and spans
+                tail.append(('keepOutMotion', b''.join(t.tobytes() for t in self._keep_out_motion())))
         return (int(DEG_ELEV), self.separationRows, *rows, self.activeRows, self._rv_cache[0], self.model['maxSep'], *bounds,
                 None if self._timeopt() else self.model['tf'],
                 None if self.pointObstacles is None else np.asarray(self.pointObstacles, dtype=float).tobytes(),
@@ -1262,17 +1328,21 @@ class BezOptimization(object):
         search returns -- one face at an end or a smooth minimum, the weighted pair at a kink (obtg_keep_out_true_min_jac, one
         call at x) -- scattered to the columns of the item's own vehicle; method='exact' is not built.  The rows have no explicit
         dependence on tf: that part of a time-optimal problem's tf column is an exact 0 (with prescribed speeds the column still
-        carries dY/dtf)."""
+        carries dY/dtf).  With `keepOutMotion` the rows are those of the relative curves (obtg_keep_out_moving_true_min[_jac])
+        and DO depend on tf: the envelope's tf column then carries the kernel's jac_tf = -(a^ . E'(t*)) t* / tf as well."""
         fam = _KEEP_OUT
         tables = self._bound(fam, fam.jacobian)          # missing obstacles answer before anything is computed
         self._check_jac_method(fam, method)
         if method != 'envelope':
             return self._jac(x, fam.key)
         x = np.asarray(x, dtype=float)
-        r = self._vehicle_true_min(fam, self._ctx(False), self.reshapeVectors(x[None]), None, tables, fam.jacobian + '(envelope)',
-                                   envelope=True)
+        moving = self.keepOutMotion is not None
+        r = self._vehicle_true_min(fam, self._ctx(False), self.reshapeVectors(x[None]), np.atleast_1d(self._tf_of(x)) if moving else None,
+                                   tables, fam.jacobian + '(envelope)', envelope=True)
         owner = tables[2][:, 0].astype(np.int64)
-        return self._scatter_exact(r['jac'][0][:, None], (owner,), (1.0,), np.zeros((owner.size, 1)))      # blocks of one row each
+        # (blocks of one row each; against moving obstacles the rows have an explicit d/dtf, the kernel's jac_tf)
+        dtf = r['jac_tf'][0][:, None] if moving else np.zeros((owner.size, 1))
+        return self._scatter_exact(r['jac'][0][:, None], (owner,), (1.0,), dtf)
 
     def trueKeepOutClearances(self, x):
         """dict(val[P], t_star[P], face[P][2], lam[P], status[P]): per (vehicle, obstacle) of `keepOut`, in the order of

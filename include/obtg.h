@@ -119,7 +119,8 @@ const char* obtg_strerror(int code);
  *      obtg_bern_keep_out[_dev] (timed under OBTG_K_SPEED; no kernel id added).
  *      Later, still 7: new: keep-out obstacles that move along a known path: obtg_ctx_set_keep_out_motion, the clearances
  *      obtg_keep_out_moving_true_min[_dev], the envelope Jacobian with its tf column obtg_keep_out_moving_true_min_jac[_dev] and
- *      free curves against one moving obstacle obtg_bern_keep_out_moving[_dev] (timed under OBTG_K_SPEED; no kernel id added). */
+ *      free curves against one moving obstacle obtg_bern_keep_out_moving[_dev] (timed under OBTG_K_SPEED; no kernel id added).
+ *      Later, still 7: new: the read-only query obtg_sweep_shape (which form and grid the hull-pair sweeps take). */
 #define OBTG_ABI_VERSION 7
 int obtg_abi_version(void);
 
@@ -525,6 +526,22 @@ int obtg_ctx_set_fd_view_structured(obtg_ctx*, int on);
  * refill together (SLSQP's consecutive calls see nearly the same geometry).  Scheduling only:
  * every pair is evaluated in full and the outputs do not depend on the order.  Off = list order. */
 int obtg_ctx_set_gjk_history(obtg_ctx*, int on);
+/* Which form and grid the hull-pair sweep of B rows takes on this context, as the launchers would decide it now (the
+ * environment's OBTG_SWEEP_WGS / OBTG_SWEEP_PASSES / OBTG_TILE_A included): a read-only question for tests and A/B runs that
+ * force a shape and want to know that it is in effect.  Launches nothing; may build what the launch would (the context's
+ * tables, the tiled forms' chunk tables).
+ *   which = 0: the plain gjkNew sweep, obtg_gjk_swarm[_dev];  which = 1: obtg_pair_sweep_dev, and with want_dyn != 0
+ *   obtg_constraint_sweep_dev with every family wanted (brute-force launches; the structured step of a view is not asked).
+ *   out[0] form: 1 = one launch of the planar sweep (rows that fit LDS), 2 = the tiled sweep (large rows), 3 = the general
+ *          kernel (3-D, polygons with more points than a hull, ...; out[1 .. 4] are 0), 4 = the finite-difference
+ *          de-duplicated sequence (which = 0 with obtg_ctx_set_fd_dedup on), 0 = two launches (which = 1 only: the plain
+ *          sweep, which out[1 .. 4] then describe, and the separation rows)
+ *   out[1] workgroups per row, out[2] passes of a workgroup over one staging, out[3] hull pairs per pass (tiled: chunks per
+ *          row, 1, the longest chunk), out[4] tile height (tiled forms, else 0),
+ *   out[5] lanes that must be idle before a batch of them refills (OBTG_REFILL_MIN, read once per process),
+ *   out[6] shift of the trip-count bins of the history order (OBTG_HIST_SHIFT, once per process),
+ *   out[7] 1: the speed / angular-rate groups ride in the sweep's grid (which = 1, want_dyn). */
+int obtg_sweep_shape(obtg_ctx*, int B, int which, int want_dyn, int* out /*[8]*/);
 /* host-buffer form of the same sweep (B rows of Y in, arrays out) */
 int obtg_gjk_swarm(obtg_ctx*, const double* Y, int B, int max_iter, int md_cap,
                    int* flag, double* p1, double* p2, double* dist, int* nsup, int* status);

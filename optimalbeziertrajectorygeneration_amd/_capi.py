@@ -97,6 +97,7 @@ _SIGNATURES = {
     "obtg_ctx_set_fd_dedup": (_i, [_vp, _i]),
     "obtg_ctx_set_fd_view_structured": (_i, [_vp, _i]),
     "obtg_ctx_set_gjk_history": (_i, [_vp, _i]),
+    "obtg_sweep_shape": (_i, [_vp, _i, _i, _i, _vp]),
     "obtg_pair_sweep_dev": (_i, [_vp, _vp, _i, _d, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "obtg_gjk_swarm_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "obtg_constraint_sweep_dev": (_i, [_vp, _vp, _vp, _i, _d, _vp, _d, _i, _d, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -1414,6 +1415,17 @@ class Context(object):
 
     def set_gjk_history(self, on):
         self._check(self._lib.obtg_ctx_set_gjk_history(self._h, int(bool(on))), "obtg_ctx_set_gjk_history")
+
+    SWEEP_FORMS = ("two_launches", "one_launch", "tiled", "general", "dedup")
+
+    def sweep_shape(self, B, which=1, want_dyn=False):
+        """Which form and grid the hull-pair sweep of B rows takes now (obtg_sweep_shape; launches nothing).  which = 0:
+        gjk_swarm[_dev]; which = 1: pair_sweep_dev, with want_dyn constraint_sweep_dev with every family wanted."""
+        self._need_hull_pairs("sweep_shape")
+        out = (C.c_int * 8)()
+        self._check(self._lib.obtg_sweep_shape(self._h, int(B), int(which), int(bool(want_dyn)), C.cast(out, _vp)), "obtg_sweep_shape")
+        return dict(form=self.SWEEP_FORMS[out[0]], wgs=out[1], passes=out[2], chunk=out[3], tile_height=out[4],
+                    refill_min=out[5], hist_shift=out[6], fold_dyn=bool(out[7]))
 
     def gjk_swarm(self, Y, max_iter=128, md_cap=4096):
         self._need_hull_pairs("gjk_swarm")

@@ -247,7 +247,7 @@ const char* obtg_abi_symbols(void)
         "obtg_temporal_sep_fd\0obtg_temporal_sep_fd_dev\0obtg_one_vs_many_min\0obtg_one_vs_many_min_dev\0obtg_one_vs_many_min_spans\0obtg_one_vs_many_min_spans_dev\0"
         "obtg_temporal_sep_dev\0obtg_temporal_sep_min_dev\0obtg_speed_dev\0obtg_ang_rate_dev\0obtg_dynamics_dev\0"
         "obtg_fd_batch_dev\0obtg_fd_view_begin\0obtg_fd_view_begin_rows\0obtg_fd_view_end\0obtg_fd_forms_on_the_fly\0obtg_pair_sweep_fd_dev\0obtg_dynamics_fd_dev\0obtg_gjk_pairs\0obtg_ctx_set_polygons\0obtg_ctx_set_hull_pairs\0"
-        "obtg_ctx_set_fd_dedup\0obtg_ctx_set_fd_view_structured\0obtg_ctx_set_gjk_history\0obtg_pair_sweep_dev\0obtg_constraint_sweep_dev\0obtg_constraint_sweep_fd_structured_dev\0obtg_constraint_sweep_fd_structured_rows_dev\0obtg_gjk_swarm_dev\0obtg_gjk_swarm\0obtg_min_dist\0obtg_min_dist_mixed\0obtg_min_dist_robust\0obtg_min_dist2poly\0obtg_min_dist2poly_robust\0obtg_gjk_true_pairs\0obtg_coll_check\0obtg_coll_check2poly\0"
+        "obtg_ctx_set_fd_dedup\0obtg_ctx_set_fd_view_structured\0obtg_ctx_set_gjk_history\0obtg_sweep_shape\0obtg_pair_sweep_dev\0obtg_constraint_sweep_dev\0obtg_constraint_sweep_fd_structured_dev\0obtg_constraint_sweep_fd_structured_rows_dev\0obtg_gjk_swarm_dev\0obtg_gjk_swarm\0obtg_min_dist\0obtg_min_dist_mixed\0obtg_min_dist_robust\0obtg_min_dist2poly\0obtg_min_dist2poly_robust\0obtg_gjk_true_pairs\0obtg_coll_check\0obtg_coll_check2poly\0"
         "obtg_bern_extrema\0obtg_bern_extrema_dev\0obtg_temporal_sep_true_min\0obtg_temporal_sep_true_min_dev\0obtg_temporal_sep_true_min_jac\0obtg_temporal_sep_true_min_jac_dev\0"
         "obtg_speed_true_min\0obtg_speed_true_min_dev\0obtg_speed_true_min_jac\0obtg_speed_true_min_jac_dev\0"
         "obtg_accel\0obtg_accel_dev\0obtg_accel_true_min\0obtg_accel_true_min_dev\0obtg_accel_true_min_jac\0obtg_accel_true_min_jac_dev\0"
@@ -1284,6 +1284,14 @@ int obtg_ctx_set_fd_view_structured(obtg_ctx* c, int on)
     if (!check_ctx(c)) return OBTG_ERR_ARG;
     c->fd_view_structured = on != 0;
     return OBTG_OK;
+}
+
+int obtg_sweep_shape(obtg_ctx* c, int B, int which, int want_dyn, int* out)
+{
+    if (!check_ctx(c) || !out || B < 1 || (which != 0 && which != 1)) return OBTG_ERR_ARG;
+    if (!c->hull_pairs_set || c->n_hull_pairs <= 0) return OBTG_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    return sweep_shape_query(c, B, which, want_dyn != 0, out);
 }
 
 int obtg_pair_sweep_dev(obtg_ctx* c, const double* dY, int B, double max_sep, double* d_out_sep, int max_iter,

@@ -26,6 +26,7 @@
 #include "obtg_internal.h"
 #include "md_device.h"
 #include "struct_layout.h"
+#include "sweep_shape.h"
 // the Bernstein sweep body that k_pair_sweep runs beside the GJK workgroups: same contraction
 // setting as in bern_kernels.hip, so that both units produce the same arithmetic
 #pragma clang fp contract(fast)
@@ -407,13 +408,7 @@ __device__ __forceinline__ void support_fixed(const double2* __restrict__ o1, co
 //         pair matrix) and cut it into chunks that touch at most p.max_objs objects; a workgroup
 //         stages only its chunk's objects (p.cobjs) and the pairs carry LDS slots (p.pslots);
 //         results go to the pairs' original positions (p.order).
-template <int MODE>
-__host__ __device__ constexpr size_t planar_lds_bytes(int cap_obj, int vpq, int chunk)
-{
-    // objects | rec int2[chunk], plist u32[chunk] | ext int[2 cap_obj] | MODE 1: list int[chunk]; MODE 0, 2: ord u16[chunk]
-    // (14 bytes per pair for the sweeps: five workgroups of 1264 pairs and 72 objects per CU)
-    return 16 * (size_t)cap_obj * vpq + 12 * (size_t)chunk + 8 * (size_t)cap_obj + (MODE == 1 ? 4 : 2) * (size_t)chunk;
-}
+// (the dynamic LDS of each mode: planar_lds_bytes<MODE>, sweep_shape.h)
 
 #define OBTG_SWEEP_THREADS 256      // 512-thread workgroups (half as many stagings per row) measured no faster
 // Occupancy: the sweep is sensitive to waves per SIMD (C3: 2 / 3 / 4 / 5 waves = 0.58 / 0.17 / 0.153 /
@@ -3395,11 +3390,7 @@ int launch_gjk_pairs(obtg_ctx* c, const double* d_soa, const int* d_off, const i
     return OBTG_OK;
 }
 
-// a workgroup's dynamic LDS when per_cu of them share a CU's 160 KB (1040 bytes of static LDS per workgroup, rounded up)
-static constexpr size_t lds_share(int per_cu) { return (size_t)160 * 1024 / per_cu - 1280; }
-constexpr size_t kLdsDefaultMax = 48 * 1024;      // what a launch may ask for without the attribute below
-constexpr size_t kLdsLaunchMax = 64 * 1024;       // ... and with it, for the sweeps
-
+// (lds_share, kLdsDefaultMax, kLdsLaunchMax: sweep_shape.h)
 // a launch that asks for more dynamic LDS than the default limit raises the kernel's own first
 template <class K>
 static hipError_t allow_lds(K kern, size_t lds)
@@ -3412,24 +3403,11 @@ static hipError_t allow_lds(K kern, size_t lds)
 // Pairs are bucketed by (a / 8, b / 64); a chunk is one bucket (<= 512 pairs, <= 72 objects when the
 // list is the usual all-pairs sweep; arbitrary lists are handled by cutting buckets at kMaxPairs /
 // kMaxObjs).  Cached in the context until the pair list or the polygons change.
-// Tiles are TA x 64 blocks of the pair matrix.  A workgroup's lanes refill from its tile only, so the taller the tile
-// the fewer lanes idle at its end -- as long as the four workgroups a CU can hold (register bound of the tiled
-// kernels) still fit its 160 KB of LDS.  C4 (16 points): TA = 8 / 12 / 13 / 14 -> 17.96 / 14.25 / 13.80 /
-// 16.11 ms per sweep (14 costs a workgroup per CU).
-static int tile_height(int nc)
-{
-    const int vpq = nc | 1, occ = 4;
-    const size_t budget = lds_share(occ);
-    int ta = 8;
-    while (ta < 32 && planar_lds_bytes<2>(ta + 1 + 64, vpq, (ta + 1) * 64) <= budget) ++ta;
-    if (const char* e = getenv("OBTG_TILE_A")) ta = std::max(4, std::min(32, atoi(e)));     // (experiments)
-    return ta;
-}
-
+// Tiles are TA x 64 blocks of the pair matrix (TA: tile_height, sweep_shape.h).
 static int build_tiles(obtg_ctx* c, int /*vp*/)
 {
     if (c->tile_valid) return OBTG_OK;
-    const int TA = tile_height(c->deg + 1), TB = 64, kMaxPairs = TA * TB, kMaxObjs = TA + TB;
+    const int TA = tile_height(c->deg + 1, sweep_knobs_from_env()), TB = 64, kMaxPairs = TA * TB, kMaxObjs = TA + TB;
     const int np = c->n_hull_pairs, nobj = c->n_veh + c->n_poly;
     if (nobj > 65535) return OBTG_ERR_UNSUPPORTED;
     const std::vector<int>& pa = c->h_hp_a;
@@ -3660,50 +3638,44 @@ static void fill_dynamics(const obtg_ctx* c, GjkSwarmParams& p, const SweepFold&
 }
 static bool wants_dynamics(const SweepFold* f) { return f && f->d_out_ang && f->d_out_speed && f->d_tf; }
 
-struct SweepShape {
-    int wgs = 1, passes = 1, chunk = 0, per_cu = 1;
-    size_t lds = 0;
-};
+// the grid of a MODE 0 sweep for this context (sweep_shape.h; OBTG_SWEEP_WGS / OBTG_SWEEP_PASSES are read per launch)
 static SweepShape sweep_shape(const obtg_ctx* c, int B, int nc, int waves_per_simd, int chunk_target)
 {
-    const int np = c->n_hull_pairs, n_obj = c->n_veh + c->n_poly + c->n_obs, vpq = nc | 1;   // (point obstacles: staged by the pair sweep)
-    const size_t fixed = planar_lds_bytes<0>(n_obj, vpq, 0);
-    SweepShape sh;
-    // workgroups per CU: what the kernel's registers allow, fewer while the row's objects leave no room for 256 pairs
-    int per_cu = nc <= 11 ? waves_per_simd : 1;
-    size_t budget = 0;
-    for (; per_cu >= 1; --per_cu) {
-        budget = lds_share(per_cu);
-        if (per_cu == 1) budget = kLdsLaunchMax;                   // one workgroup per CU: the launch limit
-        if (fixed + 14 * 256 <= budget) break;
+    const int n_obj = c->n_veh + c->n_poly + c->n_obs;      // (point obstacles: staged by the pair sweep)
+    return sweep_shape(c->n_hull_pairs, n_obj, nc, c->n_cus, B, waves_per_simd, chunk_target, sweep_knobs_from_env(false));
+}
+
+// Which form obtg_gjk_swarm[_dev] takes for this context and row count, decided HERE for the launcher and for
+// obtg_sweep_shape: the planar sweep of rows that fit LDS (kSweep: the grid is `shape`), its finite-difference
+// de-duplicated sequence (kDedup), the tiled sweep of large rows (kTiled: the chunk tables, built here, give the grid) or
+// the general kernel (kGeneral: 3-D, polygons with more points than a hull, counts without an instance, rows beyond LDS).
+struct SwarmPlan {
+    enum Form { kGeneral, kSweep, kDedup, kTiled } form = kGeneral;
+    bool planar = false;               // the planar branch was looked at (`shape` is set)
+    SweepShape shape;
+    size_t lds = 0;
+};
+static int gjk_swarm_plan(obtg_ctx* c, int B, SwarmPlan& pl)
+{
+    pl = SwarmPlan{};
+    const int nc = c->deg + 1, vp2 = nc | 1;
+    if (!(c->dim == 2 && c->polys_planar && c->max_poly_K <= nc && nc <= 127)) return OBTG_OK;
+    pl.planar = true;
+    pl.shape = sweep_shape(c, B, nc, kSweepWavesPerSimd, kSweepChunk);
+    const bool instantiated = false OBTG_NC_SEP(OBTG_NC_EQ_);      // k_gjk_swarm_planar<NC, 0 / 1 / 2>
+    if (!instantiated) return OBTG_OK;
+    if (pl.shape.lds > kLdsDefaultMax) {
+        const int rc = build_tiles(c, vp2);
+        if (rc == OBTG_OK) {
+            const size_t ldst = planar_lds_bytes<2>(c->tile_max_objs, vp2, c->tile_max_pairs);
+            if (ldst <= kLdsLaunchMax) { pl.form = SwarmPlan::kTiled; pl.lds = ldst; return OBTG_OK; }
+        } else if (rc != OBTG_ERR_UNSUPPORTED) return rc;
     }
-    if (per_cu < 1) per_cu = 1;
-    const int chunk_max = fixed + 14 * 256 <= budget ? (int)std::min<size_t>((budget - fixed) / 14, 65535) : 256;
-    int W = std::max(1, (np + chunk_target - 1) / chunk_target);
-    // Small batches (a rank's share of a row-sharded iteration, bench.py --mode rows): as many workgroups per row as ONE
-    // round of resident workgroups has room for beside the row's dynamics group -- a second round costs a whole
-    // workgroup's latency again (B = 145 at C3: 6 per row 0.040 ms, 8 per row 0.052, the old rule's 16 per row 0.068;
-    // B = 289: 3 per row 0.061, 8 per row 0.080) -- and three per row while the launch is two or three rounds
-    // (B = 577: 0.104 against 0.109 / 0.116 for 4 / 2); tools/r04_small_batch_scan.sh, profiles/r04_experiments/.
-    {
-        const long slots = (long)per_cu * std::max(1, c->n_cus);
-        if ((long)B * (W + 1) < slots) {
-            const int fill = (int)((slots - B + B / 2) / std::max(1, B));         // round((slots - B) / B)
-            W = std::max(W, std::min(fill, std::max(1, np / 128)));
-        } else if ((long)B * (W + 1) < 3 * slots) W = std::max(W, std::min(3, std::max(1, np / 128)));
+    if (pl.shape.lds <= kLdsLaunchMax) {
+        pl.form = c->fd_dedup && B > 1 ? SwarmPlan::kDedup : SwarmPlan::kSweep;
+        pl.lds = pl.shape.lds;
     }
-    while ((np + W - 1) / W > chunk_max && (np + W - 1) / W > 256) ++W;           // the row's objects leave less LDS
-    int Q = 1;
-    if (const char* e = getenv("OBTG_SWEEP_WGS")) W = std::max(1, atoi(e));
-    if (const char* e = getenv("OBTG_SWEEP_PASSES")) Q = std::max(1, atoi(e));
-    const int per_wg = (np + W - 1) / W;
-    while ((per_wg + Q - 1) / Q > chunk_max && (per_wg + Q - 1) / Q > 64) ++Q;   // (a forced shape may need passes to fit)
-    sh.passes = Q;
-    sh.chunk = (per_wg + Q - 1) / Q;
-    sh.wgs = (np + sh.passes * sh.chunk - 1) / (sh.passes * sh.chunk);
-    sh.per_cu = per_cu;
-    sh.lds = planar_lds_bytes<0>(n_obj, vpq, sh.chunk);
-    return sh;
+    return OBTG_OK;
 }
 
 int launch_gjk_swarm(obtg_ctx* c, const double* dY, int B, int max_iter, int md_cap, int* d_flag,
@@ -3724,12 +3696,13 @@ int launch_gjk_swarm(obtg_ctx* c, const double* dY, int B, int max_iter, int md_
     p.wgs_per_row = (c->n_hull_pairs + p.chunk - 1) / p.chunk;
     size_t lds = sizeof(double) * ((size_t)c->n_veh * p.vp + 3 * (size_t)c->n_poly_pts);
     const bool planar = c->dim == 2 && c->polys_planar;
-    if (planar && c->max_poly_K <= c->deg + 1 && c->deg + 1 <= 127) {
+    SwarmPlan pl;
+    if (int rc = gjk_swarm_plan(c, B, pl)) return rc;
+    if (pl.planar) {
         const int nc = c->deg + 1;
         const int vp2 = nc | 1;                    // object pitch in 16-byte points (PlanarShape<NC>::VPQ)
-        const SweepShape shape = sweep_shape(c, B, nc, kSweepWavesPerSimd, kSweepChunk);
-        p.chunk = shape.chunk; p.wgs_per_row = shape.wgs; p.passes = shape.passes;
-        const size_t lds2 = shape.lds;
+        p.chunk = pl.shape.chunk; p.wgs_per_row = pl.shape.wgs; p.passes = pl.shape.passes;
+        const size_t lds2 = pl.shape.lds;
         void (*kp)(const GjkSwarmParams) = nullptr;
         void (*kf)(const GjkSwarmParams) = nullptr;
         void (*kt)(const GjkSwarmParams) = nullptr;
@@ -3740,28 +3713,23 @@ int launch_gjk_swarm(obtg_ctx* c, const double* dY, int B, int max_iter, int md_
             default: break;
         }
 #undef OBTG_GJK_CASE
-        if (kt && lds2 > kLdsDefaultMax) {
+        if (kt && pl.form == SwarmPlan::kTiled) {
             // large rows: tile-major chunks, each staging only the objects it touches
-            int rc = build_tiles(c, vp2);
-            if (rc == OBTG_OK) {
-                GjkSwarmParams q = p;
-                fill_tile_tables(c, q);
-                q.passes = 1;
-                const size_t ldst = planar_lds_bytes<2>(q.max_objs, vp2, q.chunk);
-                if (ldst <= kLdsLaunchMax) {
-                    if (int rc2 = fill_history(c, q, B)) return rc2;
-                    OBTG_HIP(c, allow_lds(kt, ldst));
-                    ScopedKernelTimer t(c, OBTG_K_GJK);
-                    hipLaunchKernelGGL(kt, dim3((unsigned)((size_t)B * q.wgs_per_row)), dim3(256), ldst, c->stream, q);
-                    OBTG_HIP(c, hipGetLastError());
-                    return OBTG_OK;
-                }
-            } else if (rc != OBTG_ERR_UNSUPPORTED) return rc;
+            GjkSwarmParams q = p;
+            fill_tile_tables(c, q);
+            q.passes = 1;
+            const size_t ldst = pl.lds;
+            if (int rc2 = fill_history(c, q, B)) return rc2;
+            OBTG_HIP(c, allow_lds(kt, ldst));
+            ScopedKernelTimer t(c, OBTG_K_GJK);
+            hipLaunchKernelGGL(kt, dim3((unsigned)((size_t)B * q.wgs_per_row)), dim3(256), ldst, c->stream, q);
+            OBTG_HIP(c, hipGetLastError());
+            return OBTG_OK;
         }
-        if (kp && lds2 <= kLdsLaunchMax) {   // larger rows: the general kernel does better than 1-2 workgroups per CU
+        if (kp && (pl.form == SwarmPlan::kSweep || pl.form == SwarmPlan::kDedup)) {   // larger rows: the general kernel does better than 1-2 workgroups per CU
             OBTG_HIP(c, allow_lds(kp, lds2));
             ScopedKernelTimer t(c, OBTG_K_GJK);
-            if (c->fd_dedup && B > 1 && kf) {
+            if (kf && pl.form == SwarmPlan::kDedup) {
                 // Finite-difference de-duplication: row 0 in full, its results broadcast to every
                 // row, then one workgroup per row re-evaluates the pairs whose hulls differ from row 0.
                 int rc = c->ws_misc[WS_L_CHANGED].reserve((size_t)B * c->n_veh);
@@ -4012,6 +3980,39 @@ bool constraint_sweep_is_one_launch(obtg_ctx* c, int B)
 {
     PairSweepPlan pl;
     return B > 0 && pair_sweep_plan(c, B, true, pl) == OBTG_OK && pl.form != PairSweepPlan::kTwoLaunches && pl.fold_dyn;
+}
+
+// obtg_sweep_shape: the form and grid the next sweep of B rows would take, read off the plans above.  Launches nothing (the
+// tables and the tiled forms' chunk tables are built, as the launch would).
+int sweep_shape_query(obtg_ctx* c, int B, int which, bool want_dyn, int out[8])
+{
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    out[5] = sweep_refill_min(); out[6] = sweep_hist_shift();
+    if (which == 1) {
+        PairSweepPlan pl;
+        if (int rc = pair_sweep_plan(c, B, want_dyn, pl)) return rc;
+        if (pl.form != PairSweepPlan::kTwoLaunches) {
+            const bool tiled = pl.form == PairSweepPlan::kTiled;
+            out[0] = tiled ? 2 : 1;
+            out[1] = tiled ? c->tile_n_chunks : pl.shape.wgs;
+            out[2] = tiled ? 1 : pl.shape.passes;
+            out[3] = tiled ? c->tile_max_pairs : pl.shape.chunk;
+            out[4] = tiled ? c->tile_a : 0;
+            out[7] = pl.fold_dyn;
+            return OBTG_OK;
+        }
+    }
+    SwarmPlan sp;                      // the plain sweep; which = 1: the first of the two launches
+    if (int rc = gjk_swarm_plan(c, B, sp)) return rc;
+    const bool tiled = sp.form == SwarmPlan::kTiled;
+    out[0] = which == 1 ? 0 : (sp.form == SwarmPlan::kSweep ? 1 : tiled ? 2 : sp.form == SwarmPlan::kDedup ? 4 : 3);
+    if (sp.form != SwarmPlan::kGeneral) {
+        out[1] = tiled ? c->tile_n_chunks : sp.shape.wgs;
+        out[2] = tiled ? 1 : sp.shape.passes;
+        out[3] = tiled ? c->tile_max_pairs : sp.shape.chunk;
+        out[4] = tiled ? c->tile_a : 0;
+    }
+    return OBTG_OK;
 }
 
 // Which shapes k_step_fd_structured covers, decided without launching anything: the launcher and the router of

@@ -331,6 +331,7 @@ bool bernstein_fd_on_the_fly(const obtg_ctx* c);      // the separate temporal-s
 bool pair_sweep_is_one_launch(const obtg_ctx* c);           // launch_pair_sweep of a large batch is the one-launch planar sweep (which forms a view's rows itself); touches nothing
 bool constraint_sweep_is_one_launch(obtg_ctx* c, int B);    // launch_pair_sweep of B rows, every dynamics output wanted, is ONE launch (one-launch planar or tiled, dynamics
                                                             // groups folded in); may build what that launch needs (tables, the tiled form's chunk tables)
+int sweep_shape_query(obtg_ctx* c, int B, int which, bool want_dyn, int out[8]);      // obtg_sweep_shape: the plans' form and grid; launches nothing
 bool step_fd_structured_supported(obtg_ctx* c);             // launch_step_fd_structured has a kernel for this context (given all outputs); launches nothing
 int launch_bern_elev(obtg_ctx* c, const double* d_in, int rows, int n, int R, double* d_out);
 int launch_bern_diff(obtg_ctx* c, const double* d_in, int rows, int n, double T, double* d_out);

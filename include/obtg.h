@@ -120,7 +120,10 @@ const char* obtg_strerror(int code);
  *      Later, still 7: new: keep-out obstacles that move along a known path: obtg_ctx_set_keep_out_motion, the clearances
  *      obtg_keep_out_moving_true_min[_dev], the envelope Jacobian with its tf column obtg_keep_out_moving_true_min_jac[_dev] and
  *      free curves against one moving obstacle obtg_bern_keep_out_moving[_dev] (timed under OBTG_K_SPEED; no kernel id added).
- *      Later, still 7: new: the read-only query obtg_sweep_shape (which form and grid the hull-pair sweeps take). */
+ *      Later, still 7: new: the read-only query obtg_sweep_shape (which form and grid the hull-pair sweeps take).
+ *      Later, still 7: new: the Euclidean keep-out clearance: the host geometry obtg_keep_out_features, the rows
+ *      obtg_keep_out_euclid_true_min[_dev], the envelope Jacobian obtg_keep_out_euclid_true_min_jac[_dev] and free curves
+ *      obtg_bern_keep_out_euclid[_dev] (timed under OBTG_K_SPEED; no kernel id added). */
 #define OBTG_ABI_VERSION 7
 int obtg_abi_version(void);
 
@@ -1033,6 +1036,91 @@ int obtg_bern_keep_out(obtg_ctx*, const double* c /*[M][dim][K]*/, int M, int di
                        double eps_rel, int max_nodes, double* val /*[M]*/, double* t_star /*[M], nullable*/, int* status /*[M], nullable*/);
 int obtg_bern_keep_out_dev(obtg_ctx*, const double* d_c, int M, int dim, int K, const double* H, int F, double eps_rel, int max_nodes,
                            double* d_val, double* d_t_star, int* d_status);
+
+/* ---- Euclidean keep-out clearance: the signed Euclidean distance in place of the largest face value ----
+ * The rows above measure an obstacle by G = max_f g_f, which is the distance only where the nearest feature is a face; beside
+ * a corner it is smaller, so a margin keeps a round vehicle out of the obstacle inflated with SHARP corners.  These calls use
+ * the signed Euclidean distance D (rounded corners).  They read the tables of obtg_ctx_set_keep_out; obstacles that stand still
+ * only (a motion on the context: OBTG_ERR_UNSUPPORTED).  The faces-metric calls above are untouched and keep reading the raw H.
+ * Host geometry (csrc/keepout_features.h; obtg_keep_out_features), once per table, on the first Euclidean call after
+ * obtg_ctx_set_keep_out, plain double arithmetic in this order:
+ *     normalisation  s = a[0] a[0], then s = fma(a[c], a[c], s); n = sqrt(s); a^[c] = a[c] / n, b^ = b / n.  A face with
+ *                    |a| = 1 is left bit for bit; |a| = 0 or a non-finite entry gives a NaN normal.
+ *     Gram entries   G_kl = a^_k . a^_l in coordinate order, the first product alone, then fma; the diagonal likewise.
+ *     features       d = 2: a pair (i < j) with det = G_ii G_jj - G_ij G_ij > 1e-12 whose point admits every other face;
+ *                    d = 3, edges: such a pair whose common line, clipped by every other face, is not empty (a single point
+ *                    counts); d = 3, vertices: a triple (i < j < k) with det Gram > 1e-12 whose point admits every other face.
+ *                    The point is A^T (Gram^-1 b^); face m admits p iff a^_m . p - b^_m <= 1e-9 (1 + |b^_m|): tolerant, so a
+ *                    feature is included rather than left out.  The line's direction is a^_i x a^_j; with s = a^_m . v and
+ *                    r = 1e-9 (1 + |b^_m|) - (a^_m . p - b^_m): |s| <= 1e-12 empties the line iff r < 0, s > 0 gives t <= r / s,
+ *                    s < 0 gives t >= r / s.
+ *     Gram^-1        pair: (G_jj / det, -G_ij / det, G_ii / det) = entries (00, 01, 11); triple: the symmetric cofactors over
+ *                    det = fma(G_ik, C_02, fma(G_ij, C_01, G_ii C_00)), entries (00, 01, 02, 11, 12, 22).
+ *     table order    every pair in lexicographic order, then every triple in lexicographic order.
+ * More than 128 features on one obstacle: OBTG_ERR_UNSUPPORTED from the Euclidean calls (never from obtg_ctx_set_keep_out).
+ * The quantity.  With g_f(p) = a^_f . p - b^_f (the coefficient arithmetic of the rows above, on the normalised faces):
+ *     D(p) = max_f g_f(p)                                   when that is <= 0     (inside: minus the depth)
+ *     D(p) = max over the candidates of their value         otherwise,
+ * the candidates being the faces (value g_f, lambda = e_f) and the features S whose multipliers mu = Gram_S^-1 g_S are all >= 0
+ * (value sqrt(g_S . mu), lambda = mu / value).  Every candidate is dual feasible (lambda >= 0, |A^T lambda| = 1), so every
+ * candidate is a lower bound of the distance and the largest is the distance; no primal test is made.  A feature left out of
+ * the table can only make a row smaller (conservative); a set that is no feature changes nothing.
+ *     row = min over t in [0, 1] of D(c(t))  -  margin.
+ * Device arithmetic at a point (csrc/keepout_device.h), every multiply-add an explicit fma:
+ *     pair     mu0 = fma(i01, g1, i00 g0), mu1 = fma(i11, g1, i01 g0); q = fma(g1, mu1, g0 mu0)
+ *     triple   mu0 = fma(i02, g2, fma(i01, g1, i00 g0)), mu1 = fma(i12, g2, fma(i11, g1, i01 g0)),
+ *              mu2 = fma(i22, g2, fma(i12, g1, i02 g0)); q = fma(g2, mu2, fma(g1, mu1, g0 mu0))
+ *     a feature counts iff every mu >= 0 and q > 0; its value is sqrt(q).
+ *     Evaluation order and ties: the candidates are taken in the order faces 0 .. F-1, then features in table order; lane l of
+ *     the item's wavefront looks at face l and features l and l + 64, the wavefront's largest value wins, the FIRST of equals
+ *     in that order.  The winner's dual pair: a face's (u, beta) = (a^_f, b^_f); a feature's lambda_k = mu_k / value,
+ *     u[c] = lambda_0 a^_0[c], then fma(lambda_k, a^_k[c], .) for k = 1, 2, and beta the same on b^.
+ * Search: the rows' above, word for word -- s = max |g_f,i| of the root, tol = eps_rel s, strict-decrease incumbent,
+ * depth-first with the smaller bound first, 32 waiting frames, nodes, both caps with a valid bracket, the NaN rule (a face with
+ * |a| = 0 or a non-finite entry: NaN items, status OBTG_MD_OK) -- with two changes.  The exact values at the root's ends and at
+ * every split point are D there (the feature evaluation runs only where max_f g_f > 0).  And a sub-curve's bound is
+ *     max( max_f min_i g_f,i ,  min_i (u . P_i - beta) ),
+ * (u, beta) the winner's dual pair at the split point both children share, formed as fma(u[0], P[0][i], -beta), then
+ * fma(u[c], P[c][i], .); the root takes the pairs of both ends.  It holds because D(p) >= u . p - beta for every p and every
+ * dual-feasible pair (inside too: lambda . g <= (sum lambda) max g <= max g, as sum lambda >= |A^T lambda| = 1 and max g <= 0).
+ * Near the minimiser u is perpendicular to c', so the gap closes quadratically in the width; the face bound alone never closes
+ * at a corner minimum.
+ * A root that closes reports bound = min(its bound, out): a dual bound and the value it meets are rounded apart, and
+ * bound <= out holds in every case.
+ * Envelope block at t*: jac[c][i] = dir[c] B_i^n(t*).  c(t*) and c'(t*) come from the item's own control points as for the rows
+ * above.  max_f g_f(c(t*)) > 0: dir = u of the winner there and faces = its set -- no co-activity rule, D is C^1 outside.
+ * Otherwise dir = lam1 a^_f1 + lam2 a^_f2 and faces = (f1, f2, -1) by the co-activity rule above on the normalised faces.
+ * obtg_keep_out_features: Hn[F][d+1] the normalised faces; idx[128][3] the features' faces ascending, -1 padded; ginv[128][6] a
+ *     pair's (00, 01, 11, 0, 0, 0), a triple's six; *n the count.  Needs no context and no device.  OBTG_ERR_ARG: a null pointer,
+ *     F < 1, d not 2 or 3; OBTG_ERR_UNSUPPORTED: F > 16, or more than 128 features (*n is the count found, the first 128 stored).
+ * obtg_keep_out_euclid_true_min: the outputs and conventions of obtg_keep_out_true_min with faces[B][P][3] (the active set,
+ *     indices into H, -1 padded) and dir[B][P][d] in place of face and lam; both nullable.  bound <= true row <= out and
+ *     out - bound <= tol when status is OBTG_MD_OK.
+ * obtg_keep_out_euclid_true_min_jac: the same outputs, bit for bit (the same kernel; the blocks are one more output), plus
+ *     jac[B][P][d][n+1].
+ * obtg_bern_keep_out_euclid: M free curves against ONE obstacle H[F][dim+1] (raw faces, a host array in both forms), margin 0.
+ * One kernel body with the rows above (csrc/keepout_kernels.hip), one launch; host and _dev calls give the same bits; an obstacle
+ * of one face with |a| = 1 gives the bits of obtg_keep_out_true_min in every output the two share.  Refusals, timing and the
+ * obtg_fd_view rule are those of the rows above. */
+int obtg_keep_out_features(const double* H /*[F][d+1]*/, int F, int d, double* Hn /*[F][d+1]*/, int* idx /*[128][3]*/,
+                           double* ginv /*[128][6]*/, int* n);
+int obtg_keep_out_euclid_true_min(obtg_ctx*, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out /*[B][P]*/,
+                                  double* t_star /*[B][P], nullable*/, int* faces /*[B][P][3], nullable*/,
+                                  double* dir /*[B][P][d], nullable*/, double* bound /*[B][P], nullable*/, int* nodes /*[B][P], nullable*/,
+                                  int* status /*[B][P], nullable*/);
+int obtg_keep_out_euclid_true_min_dev(obtg_ctx*, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
+                                      double* d_t_star, int* d_faces, double* d_dir, double* d_bound, int* d_nodes, int* d_status);
+int obtg_keep_out_euclid_true_min_jac(obtg_ctx*, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
+                                      double* t_star, int* faces, double* dir, double* bound, int* nodes, int* status,
+                                      double* jac /*[B][P][d][n+1]*/);
+int obtg_keep_out_euclid_true_min_jac_dev(obtg_ctx*, const double* dY, int B, double margin, double eps_rel, int max_nodes,
+                                          double* d_out, double* d_t_star, int* d_faces, double* d_dir, double* d_bound, int* d_nodes,
+                                          int* d_status, double* d_jac);
+int obtg_bern_keep_out_euclid(obtg_ctx*, const double* c /*[M][dim][K]*/, int M, int dim, int K, const double* H /*[F][dim+1]*/, int F,
+                              double eps_rel, int max_nodes, double* val /*[M]*/, double* t_star /*[M], nullable*/,
+                              int* status /*[M], nullable*/);
+int obtg_bern_keep_out_euclid_dev(obtg_ctx*, const double* d_c, int M, int dim, int K, const double* H, int F, double eps_rel,
+                                  int max_nodes, double* d_val, double* d_t_star, int* d_status);
 
 /* ---- moving keep-out obstacles: a convex obstacle that translates along a known path ----
  * Obstacle o of the keep-out tables keeps its faces and may carry a motion: a Bezier offset q_o(time) with control points

@@ -187,6 +187,13 @@ _SIGNATURES = {
     "obtg_keep_out_moving_true_min_jac_dev": (_i, [_vp, _vp, _vp, _i, _d, _d, _i] + [_vp] * 10),
     "obtg_bern_keep_out_moving": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _d, _i, _vp, _vp, _vp]),
     "obtg_bern_keep_out_moving_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _d, _i, _vp, _vp, _vp]),
+    "obtg_keep_out_features": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "obtg_keep_out_euclid_true_min": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_keep_out_euclid_true_min_dev": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_keep_out_euclid_true_min_jac": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_keep_out_euclid_true_min_jac_dev": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_bern_keep_out_euclid": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _d, _i, _vp, _vp, _vp]),
+    "obtg_bern_keep_out_euclid_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _d, _i, _vp, _vp, _vp]),
     "obtg_jerk": (_i, [_vp, _vp, _vp, _i, _d, _vp]),
     "obtg_jerk_dev": (_i, [_vp, _vp, _vp, _i, _d, _vp]),
     "obtg_jerk_true_min": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
@@ -286,6 +293,20 @@ def fast_kernels(dim, deg):
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(_vp)
+
+
+def keep_out_features(H, d=None):
+    """obtg_keep_out_features: the host geometry of the Euclidean keep-out rows for ONE obstacle, the faces H[F][d+1].  Needs no
+    device.  dict(Hn[F][d+1] -- the normalised faces --, idx[n][3] -- the features' faces, -1 padded --, ginv[n][6] -- their
+    inverse Gram matrices --, n, rc): rc is OBTG_ERR_UNSUPPORTED with more than 128 features (n the count found, 128 stored)."""
+    H = np.ascontiguousarray(H, np.float64)
+    if d is None:
+        d = H.shape[-1] - 1
+    H = H.reshape(-1, d + 1)
+    Hn, idx, ginv, n = np.empty_like(H), np.full((128, 3), -1, np.int32), np.zeros((128, 6)), C.c_int(0)
+    rc = load().obtg_keep_out_features(_ptr(H), H.shape[0], int(d), _ptr(Hn), _ptr(idx), _ptr(ginv), C.byref(n))
+    k = min(max(n.value, 0), 128)
+    return dict(Hn=Hn, idx=idx[:k], ginv=ginv[:k], n=n.value, rc=rc)
 
 
 def _f64(a):
@@ -898,6 +919,61 @@ class Context(object):
         H = _f64(H).reshape(-1, int(dim) + 1)
         self._check(self._lib.obtg_bern_keep_out_dev(self._h, _vp(d_c), int(M), int(dim), int(K), _ptr(H), H.shape[0], float(eps_rel),
                                                      int(max_nodes), _vp(d_val), _vp(d_t_star), _vp(d_status)), "obtg_bern_keep_out_dev")
+
+    # -- the Euclidean metric (include/obtg.h "Euclidean keep-out clearance"): the same tables, the signed Euclidean distance
+    def _keep_out_euclid_call(self, name, Y, obstacles, margin, eps_rel, max_nodes, jac):
+        P = self._keep_out(obstacles)
+        Y, B = self._rows(Y)
+        r = dict(val=pinned_empty((B, P)), t_star=np.empty((B, P)), faces=np.zeros((B, P, 3), np.int32), dir=np.empty((B, P, self.dim)),
+                 bound=np.empty((B, P)), nodes=np.zeros((B, P), np.int32), status=np.zeros((B, P), np.int32))
+        if jac:
+            r["jac"] = pinned_empty((B, P, self.dim, self.deg + 1))
+        self._check(getattr(self._lib, name)(self._h, _ptr(Y), B, float(margin), float(eps_rel), int(max_nodes),
+                                             *[_ptr(a) for a in r.values()]), name)
+        return r
+
+    def keep_out_euclid_true_min(self, Y, obstacles=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
+        """Per (vehicle, obstacle) item the Euclidean clearance row: the minimum over t in [0, 1] of the signed Euclidean
+        distance from c_v(t) to the obstacle, minus margin (obtg_keep_out_euclid_true_min): dict(val[B][P], t_star[B][P],
+        faces[B][P][3] -- the active set as indices into H, -1 padded --, dir[B][P][dim] -- the unit direction at t_star --,
+        bound[B][P], nodes[B][P], status[B][P])."""
+        return self._keep_out_euclid_call("obtg_keep_out_euclid_true_min", Y, obstacles, margin, eps_rel, max_nodes, False)
+
+    def keep_out_euclid_true_min_jac(self, Y, obstacles=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
+        """keep_out_euclid_true_min with its envelope Jacobian (obtg_keep_out_euclid_true_min_jac): the same dict, bit for bit,
+        and jac[B][P][dim][deg+1] = dir[c] B_i(t_star): d/d(the item's own vehicle's control points)."""
+        return self._keep_out_euclid_call("obtg_keep_out_euclid_true_min_jac", Y, obstacles, margin, eps_rel, max_nodes, True)
+
+    def keep_out_euclid_true_min_dev(self, dY, B, d_out, d_t_star=None, d_faces=None, d_dir=None, d_bound=None, d_nodes=None,
+                                     d_status=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
+        self._check(self._lib.obtg_keep_out_euclid_true_min_dev(
+            self._h, _vp(dY), int(B), float(margin), float(eps_rel), int(max_nodes),
+            *[_vp(q) for q in (d_out, d_t_star, d_faces, d_dir, d_bound, d_nodes, d_status)]), "obtg_keep_out_euclid_true_min_dev")
+
+    def keep_out_euclid_true_min_jac_dev(self, dY, B, d_out, d_jac, d_t_star=None, d_faces=None, d_dir=None, d_bound=None, d_nodes=None,
+                                         d_status=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
+        self._check(self._lib.obtg_keep_out_euclid_true_min_jac_dev(
+            self._h, _vp(dY), int(B), float(margin), float(eps_rel), int(max_nodes),
+            *[_vp(q) for q in (d_out, d_t_star, d_faces, d_dir, d_bound, d_nodes, d_status, d_jac)]), "obtg_keep_out_euclid_true_min_jac_dev")
+
+    def bern_keep_out_euclid(self, c, H, eps_rel=1e-9, max_nodes=100000):
+        """The Euclidean clearance of free curves c[M][dim][K] from ONE convex obstacle, the raw faces H[F][dim+1]
+        (obtg_bern_keep_out_euclid): dict(val[M], t_star[M], status[M])."""
+        c = _f64(c)
+        if c.ndim == 2:
+            c = c[None]
+        M, dim, K = c.shape
+        H = _f64(H).reshape(-1, dim + 1)
+        r = dict(val=np.empty(M), t_star=np.empty(M), status=np.zeros(M, np.int32))
+        self._check(self._lib.obtg_bern_keep_out_euclid(self._h, _ptr(c), M, dim, K, _ptr(H), H.shape[0], float(eps_rel), int(max_nodes),
+                                                        *[_ptr(a) for a in r.values()]), "obtg_bern_keep_out_euclid")
+        return r
+
+    def bern_keep_out_euclid_dev(self, d_c, M, dim, K, H, d_val, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
+        H = _f64(H).reshape(-1, int(dim) + 1)
+        self._check(self._lib.obtg_bern_keep_out_euclid_dev(self._h, _vp(d_c), int(M), int(dim), int(K), _ptr(H), H.shape[0],
+                                                            float(eps_rel), int(max_nodes), _vp(d_val), _vp(d_t_star), _vp(d_status)),
+                    "obtg_bern_keep_out_euclid_dev")
 
     # -- moving keep-out obstacles (include/obtg.h "moving keep-out obstacles"): motion = (Q, q_off[O+1], T[O]) -- Q the
     # obstacles' [dim][m_o+1] control-point blocks one after the other, flat; q_off in control points, an empty run for an

@@ -280,16 +280,23 @@ class Bezier(BezierParams):
             _raise_md(st, 'keepInMargins')
         return r['val'][0].copy(), r['t_star'][0].copy()
 
-    def keepOutClearance(self, A, b, eps=1e-12, max_nodes=100000, motion=None):
+    def keepOutClearance(self, A, b, eps=1e-12, max_nodes=100000, motion=None, metric='faces'):
         """(clearance, t): the minimum over the curve of G(t) = max_f (a_f . c(t) - b_f) for the convex obstacle A p <= b
         (A[F][dim], b[F], dim 2 or 3, F <= 16) and the parameter in [0, 1] where it is reached (obtg_bern_keep_out, the search
         behind BezOptimization.keepOutConstraints).  Positive: the curve stays outside, and with |a_f| = 1 its true distance to
-        the obstacle is at least the clearance (equal where the nearest feature is a face, larger near a corner); negative:
+        the obstacle is at least the clearance (equal where the nearest feature is a face, larger near a corner: conservative
+        near corners unless metric='euclidean'); negative:
         minus the deepest penetration.  It depends on neither t0 nor tf.  Not in the reference.
         motion (a Bezier of this curve's dimension, of a degree no higher than this curve's, whose span contains this curve's):
         the obstacle's offset as a function of time, translation only -- the clearance is then that of the relative curve
         c(t) - motion(t) over this curve's span (obtg_bern_keep_out_moving; the motion is cut down to the span on the host by
-        obtg_bern_restrict, so the device call gets r = 1)."""
+        obtg_bern_restrict, so the device call gets r = 1).
+        metric='euclidean': the signed Euclidean distance to the obstacle in G's place (obtg_bern_keep_out_euclid) -- the true
+        clearance near a corner too, whatever |a_f| is; not built together with a motion."""
+        if metric not in ('faces', 'euclidean'):
+            raise ValueError("metric must be 'faces' or 'euclidean', not {!r}".format(metric))
+        if metric == 'euclidean' and motion is not None:
+            raise ValueError("metric='euclidean' together with a motion is not built")
         if self.dim not in (2, 3):
             raise ValueError('The input curve must be two or three dimensional,\n'
                              'instead it is {} dimensional'.format(self.dim))
@@ -297,7 +304,9 @@ class Bezier(BezierParams):
         if A.ndim != 2 or A.shape[0] < 1 or A.shape[1] != self.dim or b.shape != (A.shape[0],):
             raise ValueError('keepOutClearance needs A[F][{}] and b[F], F >= 1, not shapes {} and {}'.format(self.dim, A.shape, b.shape))
         H = np.hstack((A, b[:, None]))
-        if motion is None:
+        if metric == 'euclidean':
+            r = _ctx().bern_keep_out_euclid(self.cpts, H, eps_rel=float(eps), max_nodes=int(max_nodes))
+        elif motion is None:
             r = _ctx().bern_keep_out(self.cpts, H, eps_rel=float(eps), max_nodes=int(max_nodes))
         else:
             if not isinstance(motion, Bezier) or motion.dim != self.dim:

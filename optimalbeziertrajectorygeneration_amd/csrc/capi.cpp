@@ -8,6 +8,7 @@
 #include <new>
 
 #include "obtg_internal.h"
+#include "keepout_features.h"
 
 namespace obtg {
 
@@ -258,6 +259,7 @@ const char* obtg_abi_symbols(void)
         "obtg_ctx_set_keep_in\0obtg_len_keep_in\0obtg_keep_in\0obtg_keep_in_dev\0obtg_keep_in_true_min\0obtg_keep_in_true_min_dev\0obtg_keep_in_true_min_jac\0obtg_keep_in_true_min_jac_dev\0"
         "obtg_ctx_set_keep_out\0obtg_len_keep_out\0obtg_keep_out_true_min\0obtg_keep_out_true_min_dev\0obtg_keep_out_true_min_jac\0obtg_keep_out_true_min_jac_dev\0obtg_bern_keep_out\0obtg_bern_keep_out_dev\0"
         "obtg_ctx_set_keep_out_motion\0obtg_keep_out_moving_true_min\0obtg_keep_out_moving_true_min_dev\0obtg_keep_out_moving_true_min_jac\0obtg_keep_out_moving_true_min_jac_dev\0obtg_bern_keep_out_moving\0obtg_bern_keep_out_moving_dev\0"
+        "obtg_keep_out_features\0obtg_keep_out_euclid_true_min\0obtg_keep_out_euclid_true_min_dev\0obtg_keep_out_euclid_true_min_jac\0obtg_keep_out_euclid_true_min_jac_dev\0obtg_bern_keep_out_euclid\0obtg_bern_keep_out_euclid_dev\0"
         "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_restrict\0obtg_bern_eval\0"
         "obtg_euclidean_obj\0obtg_accel_obj\0obtg_jerk_obj\0"
         "obtg_bern_arc_length\0obtg_bern_arc_length_dev\0obtg_arc_length_obj\0obtg_arc_length_obj_dev\0"
@@ -2142,12 +2144,15 @@ int obtg_ctx_set_keep_out(obtg_ctx* c, const double* H, const int* obs_off, int 
     OBTG_HIP(c, hipStreamSynchronize(c->stream));
     c->ko_F = c->ko_O = c->ko_P = 0;       // (set again once the tables are on the device)
     c->ko_motion = false;                  // new tables: every obstacle stands still until obtg_ctx_set_keep_out_motion says otherwise
+    c->ko_eu_state = 0;
     if (P == 0) return OBTG_OK;
     int rc = upload(c, c->d_ko_H, H, sizeof(double) * (size_t)F * (c->dim + 1));
     if (!rc) rc = upload(c, c->d_ko_off, obs_off, sizeof(int) * ((size_t)O + 1));
     if (!rc) rc = upload(c, c->d_ko_VO, VO, sizeof(int) * 2 * (size_t)P);
     if (rc) return rc;
     c->ko_F = F; c->ko_O = O; c->ko_P = P;
+    c->h_ko_H.assign(H, H + (size_t)F * (c->dim + 1));       // (for the Euclidean calls' tables, made on their first use)
+    c->h_ko_off.assign(obs_off, obs_off + O + 1);
     return OBTG_OK;
 }
 
@@ -2267,6 +2272,175 @@ int obtg_bern_keep_out(obtg_ctx* c, const double* cv, int M, int dim, int K, con
     int* ds = h.out<int>(c->ws_misc[WS_STATUS], n);
     h.run([&] { return launch_keep_out(c, dim, K, d_c, M, 1, 1, dH.as<double>(), nullptr, nullptr, F, 0.0, eps_rel, max_nodes, dv, dv + n,
                                        nullptr, nullptr, nullptr, nullptr, ds, nullptr, OBTG_K_SPEED); });
+    h.fetch(t_star, dv + n, n);
+    h.fetch(status, ds, n);
+    return h.finish(val, dv, n);
+}
+
+// The Euclidean metric (include/obtg.h "Euclidean keep-out clearance"; csrc/keepout_features.h): the signed Euclidean distance in
+// place of the largest face value.  The normalised faces and the feature records are host work, done once per table.
+int obtg_keep_out_features(const double* H, int F, int d, double* Hn, int* idx, double* ginv, int* n)
+{
+    if (!H || !Hn || !idx || !ginv || !n || F < 1 || (d != 2 && d != 3)) return OBTG_ERR_ARG;
+    if (F > kKoFeatMaxFaces) return OBTG_ERR_UNSUPPORTED;
+    keep_out_normalise(H, F, d, Hn);
+    *n = keep_out_enumerate(Hn, F, d, kKoMaxFeatures, idx, ginv);
+    return *n > kKoMaxFeatures ? OBTG_ERR_UNSUPPORTED : OBTG_OK;
+}
+
+// the device records of one obstacle behind `rec`: Gram^-1 (6) | the faces a byte each, 0xff for none
+static void keep_out_pack_features(const int* idx, const double* ginv, int n, std::vector<double>& rec)
+{
+    for (int k = 0; k < n; ++k) {
+        for (int e = 0; e < 6; ++e) rec.push_back(ginv[6 * k + e]);
+        const long long pk = (long long)(idx[3 * k] & 0xff) | ((long long)(idx[3 * k + 1] & 0xff) << 8) | ((long long)(idx[3 * k + 2] & 0xff) << 16);
+        double slot;
+        std::memcpy(&slot, &pk, sizeof slot);
+        rec.push_back(slot);
+    }
+}
+
+// the context's tables, on the first Euclidean call after obtg_ctx_set_keep_out
+static int keep_out_euclid_tables(obtg_ctx* c)
+{
+    if (c->ko_eu_state) return c->ko_eu_state == 1 ? OBTG_OK : c->ko_eu_state;
+    const int d = c->dim, O = c->ko_O;
+    std::vector<double> Hn(c->h_ko_H.size()), rec, ginv(6 * (size_t)kKoMaxFeatures);
+    std::vector<int> foff(O + 1, 0), idx(3 * (size_t)kKoMaxFeatures);
+    for (int o = 0; o < O; ++o) {
+        const int f0 = c->h_ko_off[o], F = c->h_ko_off[o + 1] - f0;
+        keep_out_normalise(c->h_ko_H.data() + (size_t)f0 * (d + 1), F, d, Hn.data() + (size_t)f0 * (d + 1));
+        const int n = keep_out_enumerate(Hn.data() + (size_t)f0 * (d + 1), F, d, kKoMaxFeatures, idx.data(), ginv.data());
+        if (n > kKoMaxFeatures) return c->ko_eu_state = OBTG_ERR_UNSUPPORTED;
+        keep_out_pack_features(idx.data(), ginv.data(), n, rec);
+        foff[o + 1] = foff[o] + n;
+    }
+    if (rec.empty()) rec.push_back(0.0);           // (no obstacle has a feature: the buffer is never read)
+    (void)hipSetDevice(c->device);
+    int rc = upload(c, c->d_ko_Hn, Hn.data(), sizeof(double) * Hn.size());
+    if (!rc) rc = upload(c, c->d_ko_feat, rec.data(), sizeof(double) * rec.size());
+    if (!rc) rc = upload(c, c->d_ko_foff, foff.data(), sizeof(int) * foff.size());
+    if (rc) return rc;
+    c->ko_eu_state = 1;
+    return OBTG_OK;
+}
+
+static int keep_out_euclid_launch(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
+                                  double* d_t, int* d_faces, double* d_dir, double* d_bound, int* d_nodes, int* d_status, double* d_jac)
+{
+    return launch_keep_out_euclid(c, c->dim, c->deg + 1, dY, (long)B * c->ko_P, c->n_veh, c->ko_P, c->d_ko_Hn.as<double>(),
+                                  c->d_ko_off.as<int>(), c->d_ko_VO.as<int>(), 0, c->d_ko_feat.as<double>(), c->d_ko_foff.as<int>(), 0,
+                                  margin, eps_rel, max_nodes, d_out, d_t, d_faces, d_dir, d_bound, d_nodes, d_status, d_jac, OBTG_K_SPEED);
+}
+
+static int keep_out_euclid_args(obtg_ctx* c, const double* out, int B, int max_nodes, double eps_rel, double margin)
+{
+    if (int rc = keep_out_args(c, out, B, max_nodes, eps_rel, margin)) return rc;
+    if (c->ko_motion) return OBTG_ERR_UNSUPPORTED;           // moving obstacles under this metric are not built
+    return keep_out_euclid_tables(c);
+}
+
+static int keep_out_euclid_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
+                               double* d_t, int* d_faces, double* d_dir, double* d_bound, int* d_nodes, int* d_status, bool want_jac,
+                               double* d_jac)
+{
+    if (int rc = keep_out_euclid_args(c, d_out, B, max_nodes, eps_rel, margin)) return rc;
+    if (!dY || (want_jac && !d_jac)) return OBTG_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    return keep_out_euclid_launch(c, dY, B, margin, eps_rel, max_nodes, d_out, d_t, d_faces, d_dir, d_bound, d_nodes, d_status, d_jac);
+}
+
+// the host body: Y up; val | t_star | bound | dir | jac in ws_out, faces | nodes | status in WS_STATUS
+static int keep_out_euclid_host(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
+                                double* t_star, int* faces, double* dir, double* bound, int* nodes, int* status, bool want_jac, double* jac)
+{
+    if (int rc = keep_out_euclid_args(c, out, B, max_nodes, eps_rel, margin)) return rc;
+    if (!Y || (want_jac && !jac)) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    const size_t n = (size_t)B * c->ko_P, nd = n * c->dim, nj = jac ? n * c->dim * (c->deg + 1) : 0;
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    double* dv = h.out<double>(c->ws_out, 3 * n + nd + nj);
+    int* di = h.out<int>(c->ws_misc[WS_STATUS], 5 * n);
+    double* dj = jac ? dv + 3 * n + nd : nullptr;
+    h.run([&] { return keep_out_euclid_launch(c, dY, B, margin, eps_rel, max_nodes, dv, dv + n, di, dv + 3 * n, dv + 2 * n, di + 3 * n,
+                                              di + 4 * n, dj); });
+    h.fetch(t_star, dv + n, n);
+    h.fetch(bound, dv + 2 * n, n);
+    h.fetch(dir, dv + 3 * n, nd);
+    h.fetch(faces, di, 3 * n);
+    h.fetch(nodes, di + 3 * n, n);
+    h.fetch(status, di + 4 * n, n);
+    h.fetch(jac, dj, nj);
+    return h.finish(out, dv, n);
+}
+
+int obtg_keep_out_euclid_true_min_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
+                                      double* d_t_star, int* d_faces, double* d_dir, double* d_bound, int* d_nodes, int* d_status)
+{
+    return keep_out_euclid_dev(c, dY, B, margin, eps_rel, max_nodes, d_out, d_t_star, d_faces, d_dir, d_bound, d_nodes, d_status, false,
+                               nullptr);
+}
+
+int obtg_keep_out_euclid_true_min(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
+                                  double* t_star, int* faces, double* dir, double* bound, int* nodes, int* status)
+{
+    return keep_out_euclid_host(c, Y, B, margin, eps_rel, max_nodes, out, t_star, faces, dir, bound, nodes, status, false, nullptr);
+}
+
+int obtg_keep_out_euclid_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes,
+                                          double* d_out, double* d_t_star, int* d_faces, double* d_dir, double* d_bound, int* d_nodes,
+                                          int* d_status, double* d_jac)
+{
+    return keep_out_euclid_dev(c, dY, B, margin, eps_rel, max_nodes, d_out, d_t_star, d_faces, d_dir, d_bound, d_nodes, d_status, true,
+                               d_jac);
+}
+
+int obtg_keep_out_euclid_true_min_jac(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
+                                      double* t_star, int* faces, double* dir, double* bound, int* nodes, int* status, double* jac)
+{
+    return keep_out_euclid_host(c, Y, B, margin, eps_rel, max_nodes, out, t_star, faces, dir, bound, nodes, status, true, jac);
+}
+
+// Free curves against ONE obstacle under the Euclidean metric: Hn | the records in one buffer (WS_ARG_A); *nf the records
+static int bern_keep_out_euclid_tables(obtg_ctx* c, const double* H, int F, int dim, int* nf)
+{
+    std::vector<double> buf((size_t)F * (dim + 1)), ginv(6 * (size_t)kKoMaxFeatures);
+    std::vector<int> idx(3 * (size_t)kKoMaxFeatures);
+    keep_out_normalise(H, F, dim, buf.data());
+    *nf = keep_out_enumerate(buf.data(), F, dim, kKoMaxFeatures, idx.data(), ginv.data());
+    if (*nf > kKoMaxFeatures) return OBTG_ERR_UNSUPPORTED;
+    keep_out_pack_features(idx.data(), ginv.data(), *nf, buf);
+    return upload(c, c->ws_misc[WS_ARG_A], buf.data(), sizeof(double) * buf.size());
+}
+
+int obtg_bern_keep_out_euclid_dev(obtg_ctx* c, const double* d_c, int M, int dim, int K, const double* H, int F, double eps_rel,
+                                  int max_nodes, double* d_val, double* d_t_star, int* d_status)
+{
+    if (int chk = bern_keep_out_args(c, d_c, M, dim, K, H, F, eps_rel, max_nodes, d_val)) return done(chk);
+    (void)hipSetDevice(c->device);
+    int nf = 0;
+    if (int rc = bern_keep_out_euclid_tables(c, H, F, dim, &nf)) return rc;
+    const double* dH = c->ws_misc[WS_ARG_A].as<double>();
+    return launch_keep_out_euclid(c, dim, K, d_c, M, 1, 1, dH, nullptr, nullptr, F, dH + (size_t)F * (dim + 1), nullptr, nf, 0.0, eps_rel,
+                                  max_nodes, d_val, d_t_star, nullptr, nullptr, nullptr, nullptr, d_status, nullptr, OBTG_K_SPEED);
+}
+
+int obtg_bern_keep_out_euclid(obtg_ctx* c, const double* cv, int M, int dim, int K, const double* H, int F, double eps_rel, int max_nodes,
+                              double* val, double* t_star, int* status)
+{
+    if (int chk = bern_keep_out_args(c, cv, M, dim, K, H, F, eps_rel, max_nodes, val)) return done(chk);
+    const size_t n = (size_t)M;
+    HostCall h(c);
+    int nf = 0;
+    if (int rc = bern_keep_out_euclid_tables(c, H, F, dim, &nf)) return rc;
+    const double* dH = c->ws_misc[WS_ARG_A].as<double>();
+    const double* d_c = h.in(c->ws_in, cv, n * dim * K);
+    double* dv = h.out<double>(c->ws_out, 2 * n);
+    int* ds = h.out<int>(c->ws_misc[WS_STATUS], n);
+    h.run([&] { return launch_keep_out_euclid(c, dim, K, d_c, M, 1, 1, dH, nullptr, nullptr, F, dH + (size_t)F * (dim + 1), nullptr, nf, 0.0,
+                                              eps_rel, max_nodes, dv, dv + n, nullptr, nullptr, nullptr, nullptr, ds, nullptr,
+                                              OBTG_K_SPEED); });
     h.fetch(t_star, dv + n, n);
     h.fetch(status, ds, n);
     return h.finish(val, dv, n);

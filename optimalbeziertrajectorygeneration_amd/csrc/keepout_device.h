@@ -10,6 +10,7 @@
 #include <cmath>
 
 #include "md_device.h"
+#include "keepout_features.h"
 
 namespace obtg {
 
@@ -101,6 +102,105 @@ __device__ __forceinline__ KoActive keep_out_active(const double* __restrict__ h
     }
     if (a.f2 >= 0) a.lam1 = s2 / (s2 - s1);
     return a;
+}
+
+// ---- the Euclidean metric (obtg_keep_out_euclid_*; include/obtg.h "Euclidean keep-out clearance")
+// The faces are the NORMALISED ones (csrc/keepout_features.h), and the obstacle's features come with them: per feature a record
+// of kKoFeatRec doubles, Gram^-1 (a pair's 00, 01, 11, 0, 0, 0; a triple's 00, 01, 02, 11, 12, 22) and the feature's faces packed
+// a byte each into the low bytes of the seventh slot (0xff: no third face).  The signed distance at a point p with
+// g_f = a^_f . p - b^_f (keep_out_coeff):
+//     max_f g_f <= 0:  D = max_f g_f                                   (inside: minus the depth; the callers never come here)
+//     otherwise        D = the largest candidate: a face's g_f, or a feature's sqrt(g_S . mu) with mu = Gram_S^-1 g_S all >= 0.
+// Every candidate (S, lambda = mu / value) is dual feasible, so every candidate is a lower bound of the distance and the largest
+// is the distance; with u = sum lambda_k a^_k and beta = sum lambda_k b^_k, D(q) >= u . q - beta for EVERY q.
+// (kKoMaxFeatures, features per obstacle: keepout_features.h; the host refuses more)
+constexpr int kKoFeatRec = 7;        // doubles per feature record
+
+// The value of feature `rec` at p, or -INFINITY when a multiplier is negative (or the quadratic form is not positive); mu out.
+//   pair:    mu0 = fma(i01, g1, i00 g0), mu1 = fma(i11, g1, i01 g0);  q = fma(g1, mu1, g0 mu0)
+//   triple:  mu0 = fma(i02, g2, fma(i01, g1, i00 g0)), mu1 = fma(i12, g2, fma(i11, g1, i01 g0)), mu2 = fma(i22, g2, fma(i12, g1, i02 g0));
+//            q = fma(g2, mu2, fma(g1, mu1, g0 mu0))
+//   value = sqrt(q)
+template <int DIM>
+__device__ __forceinline__ double ko_feature_value(const double* __restrict__ hf, const double* __restrict__ rec, const double (&p)[DIM],
+                                                   double (&mu)[3], int (&fc)[3])
+{
+    const long long pk = __double_as_longlong(rec[6]);
+    fc[0] = (int)(pk & (kKoMaxFaces - 1)); fc[1] = (int)((pk >> 8) & (kKoMaxFaces - 1)); fc[2] = (int)((pk >> 16) & 0xff);
+    if (fc[2] != 0xff) fc[2] &= kKoMaxFaces - 1;        // (a face index stays inside the wave's face area whatever the record holds)
+    const double g0 = keep_out_coeff<DIM>(hf + fc[0] * (DIM + 1), p), g1 = keep_out_coeff<DIM>(hf + fc[1] * (DIM + 1), p);
+    double q;
+    if (fc[2] == 0xff) {
+        fc[2] = -1;
+        mu[0] = __builtin_fma(rec[1], g1, rec[0] * g0);
+        mu[1] = __builtin_fma(rec[2], g1, rec[1] * g0);
+        mu[2] = 0.0;
+        q = __builtin_fma(g1, mu[1], g0 * mu[0]);
+    } else {
+        const double g2 = keep_out_coeff<DIM>(hf + fc[2] * (DIM + 1), p);
+        mu[0] = __builtin_fma(rec[2], g2, __builtin_fma(rec[1], g1, rec[0] * g0));
+        mu[1] = __builtin_fma(rec[4], g2, __builtin_fma(rec[3], g1, rec[1] * g0));
+        mu[2] = __builtin_fma(rec[5], g2, __builtin_fma(rec[4], g1, rec[2] * g0));
+        q = __builtin_fma(g2, mu[2], __builtin_fma(g1, mu[1], g0 * mu[0]));
+    }
+    if (!(mu[0] >= 0.0 && mu[1] >= 0.0 && mu[2] >= 0.0 && q > 0.0)) return -INFINITY;
+    return sqrt(q);
+}
+
+// The maximiser at p (every argument but `lane` wave-uniform; call only where max_f g_f(p) > 0).  Candidates in this order:
+// the faces 0 .. F - 1, then the features 0 .. nf - 1 in table order; lane l looks at face l and at features l and l + 64, and
+// the wave's largest wins, the FIRST of equals in that order.  Every lane then forms the winner's dual pair again from LDS (the
+// same instructions in every lane, so the same bits):
+//     a face:     ub = (a^_f, b^_f), v = g_f
+//     a feature:  lambda_k = mu_k / v;  ub[c] = lambda_0 a^_0[c], then fma(lambda_k, a^_k[c], .), c = DIM the same on b^.
+// fc: the winner's faces (-1 padded), obstacle-local.
+template <int DIM>
+struct KoDual {
+    double v;
+    double ub[DIM + 1];
+    int fc[3];
+};
+template <int DIM>
+__device__ __forceinline__ KoDual<DIM> keep_out_euclid_point(const double* __restrict__ hf, const int F, const double* __restrict__ ft,
+                                                             const int nf, const double (&p)[DIM], const int lane)
+{
+    double mu[3];
+    int fc[3];
+    double bv = -INFINITY;
+    int bc = 0x7fffffff;
+    if (lane < F) { bv = keep_out_coeff<DIM>(hf + lane * (DIM + 1), p); bc = lane; }
+    for (int j = lane; j < nf; j += kWave) {
+        const double v = ko_feature_value<DIM>(hf, ft + j * kKoFeatRec, p, mu, fc);
+        if (v > bv) { bv = v; bc = F + j; }
+    }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+        const double ov = __shfl_xor(bv, o);
+        const int oc = __shfl_xor(bc, o);
+        if (ov > bv || (ov == bv && oc < bc)) { bv = ov; bc = oc; }
+    }
+    bc = __builtin_amdgcn_readfirstlane(bc);
+    if (bc >= F + nf) bc = 0;                  // (never with finite input: lane 0 always holds face 0 or better)
+    KoDual<DIM> r;
+    if (bc < F) {
+        const double* h = hf + bc * (DIM + 1);
+#pragma unroll
+        for (int c = 0; c <= DIM; ++c) r.ub[c] = h[c];
+        r.v = keep_out_coeff<DIM>(h, p);
+        r.fc[0] = bc; r.fc[1] = -1; r.fc[2] = -1;
+    } else {
+        r.v = ko_feature_value<DIM>(hf, ft + (bc - F) * kKoFeatRec, p, mu, r.fc);
+        const double l0 = mu[0] / r.v, l1 = mu[1] / r.v, l2 = mu[2] / r.v;
+        const double *h0 = hf + r.fc[0] * (DIM + 1), *h1 = hf + r.fc[1] * (DIM + 1);
+#pragma unroll
+        for (int c = 0; c <= DIM; ++c) r.ub[c] = __builtin_fma(l1, h1[c], l0 * h0[c]);
+        if (r.fc[2] >= 0) {
+            const double* h2 = hf + r.fc[2] * (DIM + 1);
+#pragma unroll
+            for (int c = 0; c <= DIM; ++c) r.ub[c] = __builtin_fma(l2, h2[c], r.ub[c]);
+        }
+    }
+    return r;
 }
 
 // A moving obstacle's offset on the vehicle's parameter, E(s) = q(s r) with r = tf / T_o, at the vehicle's degree: lane i

@@ -28,6 +28,15 @@
 // the evaluation at t_star reads it from LDS where the static form reads the item's control points -- everything between is
 // the code above, the same instructions.  One more nullable output, jac_tf = -(a^ . E'(t_star)) t_star / tf.  The static
 // instantiation has no prologue, no extra LDS and no extra argument.
+//
+// The Euclidean metric (obtg_keep_out_euclid_*; KeepOutEuclidParams): the same body on the NORMALISED faces with
+// the signed Euclidean distance D in G's place.  The obstacle's feature records (keepout_features.h) are staged in LDS beside the
+// faces; where the search takes an exact value -- the root's ends, each split point, c(t_star) -- and max_f g_f > 0 there, the
+// wave evaluates the features of that point in parallel (keep_out_euclid_point) and the winner's dual pair (u, beta) adds
+// min_i (u . P_i - beta) to the bound of both children (of the root: both ends' pairs).  What it changes is folded into the
+// per-lane accumulators (gm, gmx, lbh, lb) AHEAD of the statements that read them out, and dir and the active set leave through
+// keep_out_euclid_outputs, so the other instantiations keep every statement and their instruction streams.  A root that closes:
+// bound = min(lb, val), since a dual bound and the value it meets are rounded apart.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -57,6 +66,17 @@ struct KeepOutParams {
     int n_veh, P, K, F_all, max_nodes;
     double margin, eps_rel;
     static constexpr bool kMoving = false;
+    static constexpr bool kEuclid = false;
+};
+
+// The Euclidean metric: H holds the NORMALISED faces; the static form only
+struct KeepOutEuclidParams : KeepOutParams {
+    const double* __restrict__ feat;     // [NF][kKoFeatRec]: the obstacles' feature records, one obstacle after the other
+    const int* __restrict__ feat_off;    // [O + 1]: obstacle o owns records feat_off[o] .. feat_off[o + 1] - 1; free curves: null
+    double* __restrict__ dir;            // [M][DIM] nullable: the unit direction the block carries
+    int* __restrict__ faces3;            // [M][3] nullable: the active set, -1 padded
+    int NF_all;                          // free curves: the records of the one obstacle
+    static constexpr bool kEuclid = true;
 };
 
 struct KeepOutMovingParams : KeepOutParams {
@@ -71,16 +91,39 @@ struct KeepOutMovingParams : KeepOutParams {
     static constexpr bool kMoving = true;
 };
 
+// The Euclidean outputs of one item: dir[DIM] and the active set (obstacle-local faces fc, -1 padded; f0 the obstacle's first
+// face) -- ud null: a NaN item.  dir is left in the wave's first frame slots too, for the envelope block.
+template <int DIM>
+__device__ __forceinline__ void keep_out_euclid_outputs(const KeepOutEuclidParams& p, const long item, const int lane, double* stk,
+                                                        const double* ud, const int* fc, const int f0)
+{
+    ko_wave_sync();
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) {
+            const double v = ud ? ud[c] : __builtin_nan("");
+            stk[c] = v;
+            if (p.dir) p.dir[DIM * item + c] = v;
+        }
+        if (p.faces3) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) p.faces3[3 * item + k] = (!fc || fc[k] < 0) ? -1 : f0 + fc[k];
+        }
+    }
+    ko_wave_sync();
+}
+
 template <int DIM, class PRM>
 __global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const PRM p)
 {
-    constexpr bool MV = PRM::kMoving;
+    constexpr bool MV = PRM::kMoving, EU = PRM::kEuclid;
+    static_assert(!(MV && EU), "the Euclidean metric is built for obstacles that stand still");
     extern __shared__ double lds[];
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     const int K = p.K, pitch = DIM * K + 3;
-    double* stk = lds + (size_t)wave * (kKoStack * pitch + kKoMaxFaces * (DIM + 1) + (MV ? 2 * DIM * K : 0));
+    double* stk = lds + (size_t)wave * (kKoStack * pitch + kKoMaxFaces * (DIM + 1) + (MV ? 2 * DIM * K : 0) + (EU ? kKoMaxFeatures * kKoFeatRec : 0));
     double* hf = stk + kKoStack * pitch;
-    double* ed = hf + kKoMaxFaces * (DIM + 1);     // MV: E[DIM][K] | D[DIM][K]
+    double* ed = hf + kKoMaxFaces * (DIM + 1);     // MV: E[DIM][K] | D[DIM][K];  EU: the obstacle's feature records
     const long item = (long)blockIdx.x * kKoWaves + wave;
     if (item >= p.M) return;                       // (wave-uniform; the kernel has no workgroup barrier)
 
@@ -89,6 +132,7 @@ __global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const PRM p)
     const double* q = nullptr;                     // MV: the obstacle's motion, Km control points per coordinate (0: none)
     int Km = 0;
     double tf_b = 1.0, ratio = 1.0;
+    int nf = 0;                                    // EU: the obstacle's features
     if (p.VO) {
         const long b = item / p.P;
         const int2 vo = p.VO[(int)(item - b * p.P)];
@@ -101,12 +145,21 @@ __global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const PRM p)
             q = p.Q + (size_t)DIM * q0;
             if (Km > 0) { tf_b = p.tf[b]; ratio = tf_b / p.T[vo.y]; }
         }
+        if constexpr (EU) {
+            const int r0 = p.feat_off[vo.y];
+            nf = min(p.feat_off[vo.y + 1] - r0, kKoMaxFeatures);
+            for (int k = lane; k < nf * kKoFeatRec; k += kWave) ed[k] = p.feat[(size_t)r0 * kKoFeatRec + k];
+        }
     } else {
         y = p.Y + (size_t)item * (DIM * K);
         if constexpr (MV) {
             Km = p.Km; q = p.Q;
             if (p.r) ratio = p.r[item];
             tf_b = ratio;
+        }
+        if constexpr (EU) {
+            nf = min(p.NF_all, kKoMaxFeatures);
+            for (int k = lane; k < nf * kKoFeatRec; k += kWave) ed[k] = p.feat[k];
         }
     }
     for (int k = lane; k < F * (DIM + 1); k += kWave) hf[k] = p.H[(size_t)f0 * (DIM + 1) + k];
@@ -152,6 +205,23 @@ __global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const PRM p)
     }
     s = ko_wave_max(s);
     const double tol = p.eps_rel * s;
+    if constexpr (EU) {
+        // the ends' exact distances and the root's dual bounds: the maximisers at both ends
+        if (!bad) {
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int le = e ? K - 1 : 0;
+                if (!(ko_lane(gm, le) > 0.0)) continue;
+                double pe[DIM];
+#pragma unroll
+                for (int c = 0; c < DIM; ++c) pe[c] = ko_lane(x[c], le);
+                const KoDual<DIM> du = keep_out_euclid_point<DIM>(hf, F, ed, nf, pe, lane);
+                const double m = ko_half_min(lane < K ? keep_out_coeff<DIM>(du.ub, x) : INFINITY);
+                lb = fmax(lb, ko_lane(m, kKoLowLast));
+                if (lane == le) gm = du.v;
+            }
+        }
+    }
     const double G0 = ko_lane(gm, 0), G1 = ko_lane(gm, K - 1);
     double U, tU;
     if (G0 <= G1) { U = G0; tU = 0.0; } else { U = G1; tU = 1.0; }
@@ -190,6 +260,17 @@ __global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const PRM p)
                 const double g = keep_out_coeff<DIM>(hf + f * (DIM + 1), q);
                 gmx = fmax(gmx, g);
                 lbh = fmax(lbh, ko_half_min(act ? g : INFINITY));
+            }
+            if constexpr (EU) {
+                // outside at the split point: its exact distance, and the maximiser there bounds both children
+                if (ko_lane(gmx, K - 1) > 0.0) {
+                    double pm[DIM];
+#pragma unroll
+                    for (int c = 0; c < DIM; ++c) pm[c] = ko_lane(q[c], K - 1);
+                    const KoDual<DIM> du = keep_out_euclid_point<DIM>(hf, F, ed, nf, pm, lane);
+                    lbh = fmax(lbh, ko_half_min(act ? keep_out_coeff<DIM>(du.ub, q) : INFINITY));
+                    gmx = du.v;
+                }
             }
             const double lbL = ko_lane(lbh, kKoLowLast), lbR = ko_lane(lbh, kKoHighLast), mid = ko_lane(gmx, K - 1);
             const double hw = 0.5 * w, tm = t0 + hw;
@@ -247,13 +328,17 @@ __global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const PRM p)
         bound = fmin(bound, U);
     } else {
         bound = lb;
+        if constexpr (EU) bound = fmin(lb, U);     // (a dual bound and the value it meets are rounded apart: keep bound <= val)
     }
 
     // ---- the active faces at t_star: c(t_star) and c'(t_star) from the item's own control points (MV: the relative ones)
     const double nan = __builtin_nan("");
     KoActive a;
     a.f1 = -1; a.f2 = -1; a.lam1 = nan;
-    if (bad) { U = tU = bound = nan; nodes = 0; }
+    if (bad) {
+        U = tU = bound = nan; nodes = 0;
+        if constexpr (EU) keep_out_euclid_outputs<DIM>(p, item, lane, stk, nullptr, nullptr, 0);
+    }
     else {
         const double ts = tU, sc = 1.0 - ts;
         double pt[DIM], dir[DIM];
@@ -271,6 +356,27 @@ __global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const PRM p)
             pt[c] = __builtin_fma(ts, d1, sc * d0);
         }
         a = keep_out_active<DIM>(hf, F, pt, dir, tol, ts > 0.0 && ts < 1.0);
+        if constexpr (EU) {
+            // outside at c(t_star): the maximiser's unit direction, no co-activity rule (D is C^1 there); otherwise the rule's
+            // faces, which are the normalised ones here.  dir goes through LDS (the frames are free now) to the block below
+            double gp = -INFINITY;
+            for (int f = 0; f < F; ++f) gp = fmax(gp, keep_out_coeff<DIM>(hf + f * (DIM + 1), pt));
+            double ud[DIM];
+            int fc[3] = {a.f1, a.f2, -1};
+            if (gp > 0.0) {
+                const KoDual<DIM> du = keep_out_euclid_point<DIM>(hf, F, ed, nf, pt, lane);
+#pragma unroll
+                for (int c = 0; c < DIM; ++c) ud[c] = du.ub[c];
+                fc[0] = du.fc[0]; fc[1] = du.fc[1]; fc[2] = du.fc[2];
+            } else {
+#pragma unroll
+                for (int c = 0; c < DIM; ++c) {
+                    ud[c] = hf[a.f1 * (DIM + 1) + c];
+                    if (a.f2 >= 0) ud[c] = __builtin_fma(a.lam1, ud[c], (1.0 - a.lam1) * hf[a.f2 * (DIM + 1) + c]);
+                }
+            }
+            keep_out_euclid_outputs<DIM>(p, item, lane, stk, ud, fc, f0);
+        }
     }
 
     if (lane == 0) {
@@ -322,6 +428,7 @@ __global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const PRM p)
                 ac = hf[a.f1 * (DIM + 1) + c];
                 if (a.f2 >= 0) ac = __builtin_fma(a.lam1, ac, (1.0 - a.lam1) * hf[a.f2 * (DIM + 1) + c]);
             }
+            if constexpr (EU) ac = stk[c];               // (keep_out_euclid_outputs left dir there, NaN for a NaN item)
             o[c * K + lane] = ac * wv;
         }
     }
@@ -361,6 +468,30 @@ int launch_keep_out_moving(obtg_ctx* c, int dim, int K, const double* dY, long M
         const KeepOutParams& ps = p;
         hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, ps);
     }
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
+// The Euclidean metric: d_Hn the normalised faces, d_feat | d_feat_off the feature records (d_feat_off null with d_VO null: free
+// curves, records 0 .. NF_all - 1); d_dir[M][dim] and d_faces3[M][3] in place of face and lam
+int launch_keep_out_euclid(obtg_ctx* c, int dim, int K, const double* dY, long M, int n_veh, int P, const double* d_Hn, const int* d_off,
+                           const int* d_VO, int F_all, const double* d_feat, const int* d_feat_off, int NF_all, double margin,
+                           double eps_rel, int max_nodes, double* d_val, double* d_t, int* d_faces3, double* d_dir, double* d_bound,
+                           int* d_nodes, int* d_status, double* d_jac, int kernel_id)
+{
+    if (M <= 0) return OBTG_OK;
+    if ((dim != 2 && dim != 3) || K < 2 || K > kKoMaxK || NF_all > kKoMaxFeatures) return OBTG_ERR_UNSUPPORTED;
+    KeepOutEuclidParams p{};
+    p.Y = dY; p.H = d_Hn; p.obs_off = d_off; p.VO = (const int2*)d_VO;
+    p.val = d_val; p.t = d_t; p.bound = d_bound; p.nodes = d_nodes; p.status = d_status; p.jac = d_jac;
+    p.M = M; p.n_veh = n_veh; p.P = P; p.K = K; p.F_all = F_all; p.max_nodes = max_nodes; p.margin = margin; p.eps_rel = eps_rel;
+    p.feat = d_feat; p.feat_off = d_feat_off; p.dir = d_dir; p.faces3 = d_faces3; p.NF_all = NF_all;
+    const size_t lds = sizeof(double) * kKoWaves * ((size_t)kKoStack * (dim * K + 3) + kKoMaxFaces * (dim + 1) + kKoMaxFeatures * kKoFeatRec);
+    const dim3 grid((unsigned)((M + kKoWaves - 1) / kKoWaves)), block(kKoWaves * kWave);
+    void (*const kernel)(KeepOutEuclidParams) = dim == 2 ? k_keep_out<2, KeepOutEuclidParams> : k_keep_out<3, KeepOutEuclidParams>;
+    if (lds > 64 * 1024) OBTG_HIP(c, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ScopedKernelTimer t(c, kernel_id);
+    hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, p);
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;
 }

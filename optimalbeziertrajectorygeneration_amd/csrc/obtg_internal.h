@@ -173,6 +173,15 @@ struct obtg_ctx {
     obtg::DevBuf d_ko_off;    // int[ko_O + 1]
     obtg::DevBuf d_ko_VO;     // int2[ko_P]
     int ko_F = 0, ko_O = 0, ko_P = 0;
+    // the Euclidean metric (obtg_keep_out_euclid_*): host copies of H and obs_off, kept by obtg_ctx_set_keep_out, and what the
+    // first Euclidean call after it makes of them (csrc/keepout_features.h): the normalised faces and the feature records
+    // beside H on the device.  ko_eu_state 0: not made yet; 1: made; any other value: the code every Euclidean call answers
+    std::vector<double> h_ko_H;
+    std::vector<int> h_ko_off;
+    obtg::DevBuf d_ko_Hn;     // double[ko_F][dim + 1]
+    obtg::DevBuf d_ko_feat;   // double[features][7]: Gram^-1 (6) | the faces, a byte each
+    obtg::DevBuf d_ko_foff;   // int[ko_O + 1]
+    int ko_eu_state = 0;
     // obtg_ctx_set_keep_out_motion: the obstacles' offset curves; ko_motion false: none set (every obstacle stands still)
     obtg::DevBuf d_ko_Q;      // double: the [dim][m_o + 1] blocks, one after the other
     obtg::DevBuf d_ko_qoff;   // int[ko_O + 1], in control points
@@ -461,6 +470,13 @@ int launch_keep_out_moving(obtg_ctx* c, int dim, int K, const double* dY, long M
                            const int* d_VO, int F_all, const KeepOutMotionArgs* mo, double margin, double eps_rel, int max_nodes,
                            double* d_val, double* d_t, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status,
                            double* d_jac, int kernel_id);
+// The Euclidean metric of the static form (obtg_keep_out_euclid_*): the same kernel body over d_Hn, the NORMALISED faces, with
+// the obstacles' feature records d_feat[.][7] and their ranges d_feat_off[O + 1] (free curves, d_VO null: d_feat_off null and
+// records 0 .. NF_all - 1; at most 128 records per obstacle).  d_faces3[M][3] and d_dir[M][dim] are nullable outputs.
+int launch_keep_out_euclid(obtg_ctx* c, int dim, int K, const double* dY, long M, int n_veh, int P, const double* d_Hn, const int* d_off,
+                           const int* d_VO, int F_all, const double* d_feat, const int* d_feat_off, int NF_all, double margin,
+                           double eps_rel, int max_nodes, double* d_val, double* d_t, int* d_faces3, double* d_dir, double* d_bound,
+                           int* d_nodes, int* d_status, double* d_jac, int kernel_id);
 // the angular-rate family's polynomials [B][n_veh][2][2 deg + 1] (obtg_ang_rate_poly; its rows_r0): dim 2, degree 1 .. 31
 int launch_ang_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);
 // The two curvature families, kind = ROWS_CURV (dim 2; two items, the sides, per vehicle; workspace rows num, den) or ROWS_SCURV

@@ -493,7 +493,8 @@ class BezOptimization(object):
                  keepInRows='all',
                  keepOut=None,
                  keepOutMargin=0.0,
-                 keepOutMotion=None):
+                 keepOutMotion=None,
+                 keepOutMetric='faces'):
         """Beyond the reference's keywords: `device` (HIP ordinal; None: this process's, see _capi.default_device) and `separationRows` --
         'all': temporalSeparationConstraints returns every elevated control point of every pair, as the
         reference does (optimization.py:337); 'min': one row per pair, the smallest of them -- the
@@ -547,7 +548,8 @@ class BezOptimization(object):
         # A p <= b (bezier.halfspacesOfPolygon makes one of a polygon's vertices), every vehicle against every obstacle --
         # keepOutConstraints: N * O true rows, vehicle-major, min over the trajectory of max_f (a_f . c_v - b_f) minus
         # keepOutMargin (obtg_keep_out_true_min).  With unit normals a row >= 0 implies a true clearance >= keepOutMargin; the
-        # row is conservative near corners and negative (minus the depth) inside.  Kept as `self.keepOut`, like keepIn.
+        # row is conservative near corners (unless keepOutMetric='euclidean') and negative (minus the depth) inside.  Kept as
+        # `self.keepOut`, like keepIn.
         if keepOut is not None:
             _keep_out_tables(keepOut, numVeh, dimension)     # raises for obstacles the device calls could not take
             if not np.isfinite(float(keepOutMargin)):
@@ -562,6 +564,11 @@ class BezOptimization(object):
             _keep_out_motion_tables(keepOutMotion, keepOut, dimension, degree,
                                     None if str(minimizeGoal).lower() == 'timeopt' else float(tf))
         self.keepOutMotion = keepOutMotion
+        # keepOutMetric ('faces': the rows above; 'euclidean': the signed Euclidean distance in their place -- rounded corners,
+        # obtg_keep_out_euclid_true_min): with unit normals both agree where the nearest feature is a face; the Euclidean rows
+        # are not conservative near corners and C^1 outside.  Kept as `self.keepOutMetric`.
+        self._check_keep_out_metric(keepOutMetric, keepOutMotion)
+        self.keepOutMetric = keepOutMetric
         if separationRows not in ('all', 'min', 'active', 'true_min'):
             raise ValueError("separationRows must be 'all', 'min', 'active' or 'true_min', not {!r}".format(separationRows))
         if separationRows == 'active' and not 1 <= int(activeRows) <= 4:
@@ -669,9 +676,21 @@ class BezOptimization(object):
             return self.model[fam.bound]
         return None if self.keepIn is None else _keep_in_tables(self.keepIn, self.model['numVeh'], self.model['dim'])
 
+    @staticmethod
+    def _check_keep_out_metric(metric, motion):
+        if metric not in ('faces', 'euclidean'):
+            raise ValueError("keepOutMetric must be 'faces' or 'euclidean', not {!r}".format(metric))
+        if metric == 'euclidean' and motion is not None:
+            raise ValueError("keepOutMetric='euclidean' together with keepOutMotion is not built: moving obstacles take the "
+                             "'faces' metric")
+
     def _vehicle_true_min(self, fam, ctx, Y, tf, bound, what, envelope=False):
         """The family's true-minimum call on the rows Y at TRUE_MIN_EPS_REL (envelope: with the envelope blocks): its dict;
         a search that ran out of budget raises in the name of `what` (bezier._raise_md)"""
+        if fam is _KEEP_OUT and self.keepOutMetric != 'faces':        # the Euclidean metric: the same tables, another quantity
+            self._check_keep_out_metric(self.keepOutMetric, self.keepOutMotion)
+            call = ctx.keep_out_euclid_true_min_jac if envelope else ctx.keep_out_euclid_true_min
+            return _md_checked(call(Y, bound, margin=self.keepOutMargin, eps_rel=self.TRUE_MIN_EPS_REL), what)
         if fam is _KEEP_OUT and self.keepOutMotion is not None:       # moving obstacles: the rows of the relative curves, with tf
             call = ctx.keep_out_moving_true_min_jac if envelope else ctx.keep_out_moving_true_min
             return _md_checked(call(Y, tf, bound, self._keep_out_motion(), margin=self.keepOutMargin, eps_rel=self.TRUE_MIN_EPS_REL),
@@ -956,8 +975,10 @@ class BezOptimization(object):
         """min over the trajectory of max_f (a_f . c_v - b_f) - keepOutMargin >= 0 for every (vehicle, obstacle) of `keepOut`,
         vehicle-major: N * O true rows (obtg_keep_out_true_min) -- the same whatever tf is, unless `keepOutMotion` moves an
         obstacle: then c_v is the curve relative to the obstacle's offset at the same moment, c_v(s) - q_o(s tf)
-        (obtg_keep_out_moving_true_min).  Conservative near corners (the row
-        is at most the true distance minus the margin, with unit normals); negative, minus the depth, inside.  Not part of the
+        (obtg_keep_out_moving_true_min).  Conservative near corners unless `keepOutMetric='euclidean'` (the row
+        is at most the true distance minus the margin, with unit normals); negative, minus the depth, inside.  With
+        `keepOutMetric='euclidean'` the rows are the signed Euclidean distance minus the margin (obtg_keep_out_euclid_true_min):
+        the obstacle inflated with ROUNDED corners.  Not part of the
         one-launch structured step, of the constraint sweep, of distributed.py or of sequential.py."""
         return self._vehicle_closure(_KEEP_OUT)
 
@@ -1126,6 +1147,8 @@ class BezOptimization(object):
             tail.append(('keepOut', self.keepOutMargin, b''.join(t.tobytes() for t in self._operand(_KEEP_OUT))))
             if self.keepOutMotion is not None:      # one more entry, only while a motion is set: its control points and spans
                 tail.append(('keepOutMotion', b''.join(t.tobytes() for t in self._keep_out_motion())))
+            if self.keepOutMetric != 'faces':       # one more entry, only while the metric is not the default
+                tail.append(('keepOutMetric', self.keepOutMetric))
         return (int(DEG_ELEV), self.separationRows, *rows, self.activeRows, self._rv_cache[0], self.model['maxSep'], *bounds,
                 None if self._timeopt() else self.model['tf'],
                 None if self.pointObstacles is None else np.asarray(self.pointObstacles, dtype=float).tobytes(),
@@ -1348,9 +1371,14 @@ class BezOptimization(object):
         """dict(val[P], t_star[P], face[P][2], lam[P], status[P]): per (vehicle, obstacle) of `keepOut`, in the order of
         keepOutConstraints, the row (clearance minus keepOutMargin), the parameter in [0, 1] where it is reached, the active
         faces as indices into the stacked face table (the second -1 without one), the first face's weight and the search's
-        status (obtg_keep_out_true_min): the vehicles stay clear iff every val is >= 0."""
+        status (obtg_keep_out_true_min): the vehicles stay clear iff every val is >= 0.  With keepOutMetric='euclidean':
+        dict(val[P], t_star[P], faces[P][3], dir[P][dim], status[P]) -- the Euclidean clearance minus keepOutMargin, the active
+        set (-1 padded) and the unit direction from the obstacle's nearest point to the trajectory there
+        (obtg_keep_out_euclid_true_min)."""
         tables = self._bound(_KEEP_OUT, 'trueKeepOutClearances')
         r = self._true_rows_at(_KEEP_OUT, np.asarray(x, dtype=float), tables, 'trueKeepOutClearances')
+        if self.keepOutMetric != 'faces':
+            return {k: r[k][0] for k in ('val', 't_star', 'faces', 'dir', 'status')}
         return {k: r[k][0] for k in ('val', 't_star', 'face', 'lam', 'status')}
 
     # ------------------------------------------------------------------ exact Jacobians (method='exact')

@@ -123,7 +123,11 @@ const char* obtg_strerror(int code);
  *      Later, still 7: new: the read-only query obtg_sweep_shape (which form and grid the hull-pair sweeps take).
  *      Later, still 7: new: the Euclidean keep-out clearance: the host geometry obtg_keep_out_features, the rows
  *      obtg_keep_out_euclid_true_min[_dev], the envelope Jacobian obtg_keep_out_euclid_true_min_jac[_dev] and free curves
- *      obtg_bern_keep_out_euclid[_dev] (timed under OBTG_K_SPEED; no kernel id added). */
+ *      obtg_bern_keep_out_euclid[_dev] (timed under OBTG_K_SPEED; no kernel id added).
+ *      Later, still 7: new: polytopic vehicle-to-vehicle separation: the region obtg_ctx_set_pair_keep_out
+ *      (obtg_len_pair_keep_out), the rows obtg_pair_keep_out_true_min[_dev] and obtg_pair_keep_out_euclid_true_min[_dev] and
+ *      their envelope Jacobians obtg_pair_keep_out_true_min_jac[_dev], obtg_pair_keep_out_euclid_true_min_jac[_dev] (timed
+ *      under OBTG_K_SPEED; no kernel id added). */
 #define OBTG_ABI_VERSION 7
 int obtg_abi_version(void);
 
@@ -1175,6 +1179,62 @@ int obtg_bern_keep_out_moving(obtg_ctx*, const double* c /*[M][dim][K]*/, int M,
                               double* val /*[M]*/, double* t_star /*[M], nullable*/, int* status /*[M], nullable*/);
 int obtg_bern_keep_out_moving_dev(obtg_ctx*, const double* d_c, int M, int dim, int K, const double* H, int F, const double* Q, int Km,
                                   const double* d_r, double eps_rel, int max_nodes, double* d_val, double* d_t_star, int* d_status);
+
+/* ---- polytopic vehicle-to-vehicle separation: a pair's relative curve stays outside ONE convex region around the origin ----
+ * The context holds one separation region R = {d : a_f . d <= b_f}, F faces (1 <= F <= 16), every b_f > 0: the origin is
+ * strictly inside, so vehicles at the same place violate the row.  For batch row B the items are the pairs i < j of the N
+ * vehicles in lexicographic order (np.triu_indices(N, 1); the order of obtg_temporal_sep_true_min), P = N (N - 1) / 2:
+ *     D[c][k]  = Y[i*d + c][k] - Y[j*d + c][k]          one subtraction per control point: the relative curve c_i - c_j
+ *     row(i,j) = min over t in [0, 1] of G(D(t)) - margin,
+ * G = max_f (a_f . p - b_f) for the faces calls (the keep-out rows above) and the signed Euclidean distance on the normalised
+ * faces for the _euclid calls ("Euclidean keep-out clearance" above): negative inside, as for obstacles.  The region does not
+ * move in the pair's frame, so a row IS the static keep-out row of a vehicle whose control points are D against the region as
+ * its one obstacle -- the same kernel body (csrc/keepout_kernels.hip), whose root reads D where the static form reads Y; every
+ * output equals that static call's, bit for bit.  A region with R != -R makes a row depend on which vehicle of the pair comes
+ * first (i, the one with the smaller index); ordered pairs are not built.  Vehicles only: point and curve obstacles do not enter.
+ * Envelope block at the returned t_star, jac[B][P][d][n+1]: the block of the pair's FIRST vehicle, what the static calls give for
+ * the curve D (faces: (lam1 a_f1 + lam2 a_f2)[c] B_k(t_star); Euclidean: dir[c] B_k(t_star)).  The second vehicle's block is
+ * its exact negation and is not stored.  There is no explicit tf column: tf enters through dY/dtf alone.
+ * obtg_ctx_set_pair_keep_out: H[F][d+1] = (a_f, b_f), copied; F = 0 clears.  Independent of obtg_ctx_set_keep_out and of a motion
+ *     set on it.  OBTG_ERR_ARG: a context whose d is not 2 or 3, a null H, F < 0, a b_f that is not > 0 (a NaN b_f passes and gives
+ *     NaN rows, as a NaN face does everywhere); OBTG_ERR_UNSUPPORTED: F > 16.
+ * obtg_len_pair_keep_out: P while a region is set, else 0.
+ * obtg_pair_keep_out_true_min: the outputs and conventions of obtg_keep_out_true_min (face indexes the region's faces), plus rel
+ *     (nullable): the D[B][P][d][n+1] the search ran on, NaN for an item that is not finite.  A non-finite control point: NaN
+ *     outputs for exactly the pairs that contain its vehicle (face -1, nodes 0), status OBTG_MD_OK.
+ * obtg_pair_keep_out_true_min_jac: the same bits, plus jac.
+ * obtg_pair_keep_out_euclid_true_min[_jac]: the outputs of obtg_keep_out_euclid_true_min[_jac] (faces[B][P][3], dir[B][P][d]),
+ *     plus rel.  The normalised faces and the feature records are made on the first Euclidean call after the region is set; more
+ *     than 128 features: OBTG_ERR_UNSUPPORTED, from these calls only.
+ * Refusals, all before any launch: no region, d not 2 or 3, or an argument obtg_keep_out_true_min refuses: OBTG_ERR_ARG; degree
+ * above 31: OBTG_ERR_UNSUPPORTED.  N = 1: P = 0, OBTG_OK, nothing written.  One launch, timed under OBTG_K_SPEED; host and _dev
+ * calls give the same bits; _dev takes device pointers, and dY = NULL inside an obtg_fd_view answers OBTG_ERR_ARG. */
+int obtg_ctx_set_pair_keep_out(obtg_ctx*, const double* H /*[F][d+1]*/, int F);
+int obtg_len_pair_keep_out(const obtg_ctx*);
+int obtg_pair_keep_out_true_min(obtg_ctx*, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out /*[B][P]*/,
+                                double* t_star, int* face /*[B][P][2]*/, double* lam, double* bound, int* nodes, int* status,
+                                double* rel /*[B][P][d][n+1], nullable*/);
+int obtg_pair_keep_out_true_min_dev(obtg_ctx*, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
+                                    double* d_t_star, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status,
+                                    double* d_rel);
+int obtg_pair_keep_out_true_min_jac(obtg_ctx*, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
+                                    double* t_star, int* face, double* lam, double* bound, int* nodes, int* status, double* rel,
+                                    double* jac /*[B][P][d][n+1]*/);
+int obtg_pair_keep_out_true_min_jac_dev(obtg_ctx*, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
+                                        double* d_t_star, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status,
+                                        double* d_rel, double* d_jac);
+int obtg_pair_keep_out_euclid_true_min(obtg_ctx*, const double* Y, int B, double margin, double eps_rel, int max_nodes,
+                                       double* out /*[B][P]*/, double* t_star, int* faces /*[B][P][3]*/, double* dir /*[B][P][d]*/,
+                                       double* bound, int* nodes, int* status, double* rel /*[B][P][d][n+1], nullable*/);
+int obtg_pair_keep_out_euclid_true_min_dev(obtg_ctx*, const double* dY, int B, double margin, double eps_rel, int max_nodes,
+                                           double* d_out, double* d_t_star, int* d_faces, double* d_dir, double* d_bound, int* d_nodes,
+                                           int* d_status, double* d_rel);
+int obtg_pair_keep_out_euclid_true_min_jac(obtg_ctx*, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
+                                           double* t_star, int* faces, double* dir, double* bound, int* nodes, int* status, double* rel,
+                                           double* jac /*[B][P][d][n+1]*/);
+int obtg_pair_keep_out_euclid_true_min_jac_dev(obtg_ctx*, const double* dY, int B, double margin, double eps_rel, int max_nodes,
+                                               double* d_out, double* d_t_star, int* d_faces, double* d_dir, double* d_bound,
+                                               int* d_nodes, int* d_status, double* d_rel, double* d_jac);
 
 /* ---- the acceleration bound: |d^2 c / dtime^2| <= bound for every vehicle, in 2-D, 3-D and any other dimension ----
  * For vehicle v with control points P[c][i] (c < d, i <= n) on a span T = tf[b]:

@@ -194,6 +194,16 @@ _SIGNATURES = {
     "obtg_keep_out_euclid_true_min_jac_dev": (_i, [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "obtg_bern_keep_out_euclid": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _d, _i, _vp, _vp, _vp]),
     "obtg_bern_keep_out_euclid_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _d, _i, _vp, _vp, _vp]),
+    "obtg_ctx_set_pair_keep_out": (_i, [_vp, _vp, _i]),
+    "obtg_len_pair_keep_out": (_i, [_vp]),
+    "obtg_pair_keep_out_true_min": (_i, [_vp, _vp, _i, _d, _d, _i] + [_vp] * 8),
+    "obtg_pair_keep_out_true_min_dev": (_i, [_vp, _vp, _i, _d, _d, _i] + [_vp] * 8),
+    "obtg_pair_keep_out_true_min_jac": (_i, [_vp, _vp, _i, _d, _d, _i] + [_vp] * 9),
+    "obtg_pair_keep_out_true_min_jac_dev": (_i, [_vp, _vp, _i, _d, _d, _i] + [_vp] * 9),
+    "obtg_pair_keep_out_euclid_true_min": (_i, [_vp, _vp, _i, _d, _d, _i] + [_vp] * 8),
+    "obtg_pair_keep_out_euclid_true_min_dev": (_i, [_vp, _vp, _i, _d, _d, _i] + [_vp] * 8),
+    "obtg_pair_keep_out_euclid_true_min_jac": (_i, [_vp, _vp, _i, _d, _d, _i] + [_vp] * 9),
+    "obtg_pair_keep_out_euclid_true_min_jac_dev": (_i, [_vp, _vp, _i, _d, _d, _i] + [_vp] * 9),
     "obtg_jerk": (_i, [_vp, _vp, _vp, _i, _d, _vp]),
     "obtg_jerk_dev": (_i, [_vp, _vp, _vp, _i, _d, _vp]),
     "obtg_jerk_true_min": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
@@ -525,6 +535,7 @@ class Context(object):
         self.keep_out_items = 0       # (vehicle, obstacle) items of the keep-out tables; 0: none set
         self._keep_out_key = None     # the bytes of the tables set_keep_out last sent
         self._keep_out_motion_key = None     # the bytes of the motion set_keep_out_motion last sent; None: none set
+        self._pair_keep_out_key = None       # the bytes of the separation region set_pair_keep_out last sent; None: none set
 
     # -- plumbing
     def close(self):
@@ -1055,6 +1066,72 @@ class Context(object):
         self._check(self._lib.obtg_bern_keep_out_moving_dev(self._h, _vp(d_c), int(M), int(dim), int(K), _ptr(H), H.shape[0], _ptr(Q),
                                                             Q.shape[1], _vp(d_r), float(eps_rel), int(max_nodes), _vp(d_val),
                                                             _vp(d_t_star), _vp(d_status)), "obtg_bern_keep_out_moving_dev")
+
+    # -- polytopic vehicle-to-vehicle separation (include/obtg.h): ONE region H[F][dim+1] around the origin, the pairs i < j in
+    # the order of np.triu_indices(N, 1); `region` as `obstacles` above: sent only when its bytes differ, None: what is set
+    def set_pair_keep_out(self, H):
+        """obtg_ctx_set_pair_keep_out: the separation region's faces a . d <= b (every b > 0) as rows (a, b); an empty H clears."""
+        H = _f64(H).reshape(-1, self.dim + 1)
+        self._pair_keep_out_key = None
+        self._check(self._lib.obtg_ctx_set_pair_keep_out(self._h, _ptr(H), H.shape[0]), "obtg_ctx_set_pair_keep_out")
+        self._pair_keep_out_key = H.tobytes() if H.shape[0] else None
+
+    def _pair_keep_out(self, region):
+        if region is not None:
+            H = _f64(region)
+            if self._pair_keep_out_key != H.tobytes():
+                self.set_pair_keep_out(H)
+        return self.len_pair_keep_out
+
+    @property
+    def len_pair_keep_out(self):
+        return self._lib.obtg_len_pair_keep_out(self._h)
+
+    def _pair_keep_out_call(self, name, euclid, Y, region, margin, eps_rel, max_nodes, jac):
+        self._pair_keep_out(region)
+        P = self.n_veh * (self.n_veh - 1) // 2       # (no region: the library's call answers OBTG_ERR_ARG)
+        Y, B = self._rows(Y)
+        r = dict(val=pinned_empty((B, P)), t_star=np.empty((B, P)))
+        if euclid:
+            r.update(faces=np.zeros((B, P, 3), np.int32), dir=np.empty((B, P, self.dim)))
+        else:
+            r.update(face=np.zeros((B, P, 2), np.int32), lam=np.empty((B, P)))
+        r.update(bound=np.empty((B, P)), nodes=np.zeros((B, P), np.int32), status=np.zeros((B, P), np.int32),
+                 rel=np.empty((B, P, self.dim, self.deg + 1)))
+        if jac:
+            r["jac"] = pinned_empty((B, P, self.dim, self.deg + 1))
+        self._check(getattr(self._lib, name)(self._h, _ptr(Y), B, float(margin), float(eps_rel), int(max_nodes),
+                                             *[_ptr(a) for a in r.values()]), name)
+        return r
+
+    def pair_keep_out_true_min(self, Y, region=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
+        """Per vehicle pair i < j the separation row: the minimum over t in [0, 1] of the largest a_f . (c_i - c_j)(t) - b_f over
+        the region's faces, minus margin (obtg_pair_keep_out_true_min): the dict of keep_out_true_min over the P = N (N - 1) / 2
+        pairs and rel[B][P][dim][deg+1], the relative control points the search ran on."""
+        return self._pair_keep_out_call("obtg_pair_keep_out_true_min", False, Y, region, margin, eps_rel, max_nodes, False)
+
+    def pair_keep_out_true_min_jac(self, Y, region=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
+        """pair_keep_out_true_min with its envelope Jacobian (obtg_pair_keep_out_true_min_jac): the same dict, bit for bit, and
+        jac[B][P][dim][deg+1], the block of the pair's FIRST vehicle; the second vehicle's is its exact negation."""
+        return self._pair_keep_out_call("obtg_pair_keep_out_true_min_jac", False, Y, region, margin, eps_rel, max_nodes, True)
+
+    def pair_keep_out_euclid_true_min(self, Y, region=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
+        """pair_keep_out_true_min under the Euclidean metric (obtg_pair_keep_out_euclid_true_min): the dict of
+        keep_out_euclid_true_min (faces[B][P][3], dir[B][P][dim]) and rel."""
+        return self._pair_keep_out_call("obtg_pair_keep_out_euclid_true_min", True, Y, region, margin, eps_rel, max_nodes, False)
+
+    def pair_keep_out_euclid_true_min_jac(self, Y, region=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
+        """pair_keep_out_euclid_true_min with jac[B][P][dim][deg+1] = dir[c] B_i(t_star), the first vehicle's block."""
+        return self._pair_keep_out_call("obtg_pair_keep_out_euclid_true_min_jac", True, Y, region, margin, eps_rel, max_nodes, True)
+
+    def pair_keep_out_true_min_dev(self, dY, B, d_out, d_t_star=None, d_face=None, d_lam=None, d_bound=None, d_nodes=None, d_status=None,
+                                   d_rel=None, d_jac=None, euclid=False, margin=0.0, eps_rel=1e-9, max_nodes=100000):
+        """The four _dev calls in one: euclid picks the metric (d_face, d_lam are then faces[.][3], dir[.][dim]), d_jac the _jac
+        form."""
+        name = "obtg_pair_keep_out_%strue_min%s_dev" % ("euclid_" if euclid else "", "" if d_jac is None else "_jac")
+        ptrs = [d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel] + ([] if d_jac is None else [d_jac])
+        self._check(getattr(self._lib, name)(self._h, _vp(dY), int(B), float(margin), float(eps_rel), int(max_nodes),
+                                             *[_vp(q) for q in ptrs]), name)
 
     def jerk(self, Y, tf, bound):
         """The jerk-bound rows (obtg_jerk): [B][N * (2 deg + DEG_ELEV + 1)] control points of

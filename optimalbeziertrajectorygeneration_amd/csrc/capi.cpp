@@ -260,6 +260,8 @@ const char* obtg_abi_symbols(void)
         "obtg_ctx_set_keep_out\0obtg_len_keep_out\0obtg_keep_out_true_min\0obtg_keep_out_true_min_dev\0obtg_keep_out_true_min_jac\0obtg_keep_out_true_min_jac_dev\0obtg_bern_keep_out\0obtg_bern_keep_out_dev\0"
         "obtg_ctx_set_keep_out_motion\0obtg_keep_out_moving_true_min\0obtg_keep_out_moving_true_min_dev\0obtg_keep_out_moving_true_min_jac\0obtg_keep_out_moving_true_min_jac_dev\0obtg_bern_keep_out_moving\0obtg_bern_keep_out_moving_dev\0"
         "obtg_keep_out_features\0obtg_keep_out_euclid_true_min\0obtg_keep_out_euclid_true_min_dev\0obtg_keep_out_euclid_true_min_jac\0obtg_keep_out_euclid_true_min_jac_dev\0obtg_bern_keep_out_euclid\0obtg_bern_keep_out_euclid_dev\0"
+        "obtg_ctx_set_pair_keep_out\0obtg_len_pair_keep_out\0obtg_pair_keep_out_true_min\0obtg_pair_keep_out_true_min_dev\0obtg_pair_keep_out_true_min_jac\0obtg_pair_keep_out_true_min_jac_dev\0"
+        "obtg_pair_keep_out_euclid_true_min\0obtg_pair_keep_out_euclid_true_min_dev\0obtg_pair_keep_out_euclid_true_min_jac\0obtg_pair_keep_out_euclid_true_min_jac_dev\0"
         "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_restrict\0obtg_bern_eval\0"
         "obtg_euclidean_obj\0obtg_accel_obj\0obtg_jerk_obj\0"
         "obtg_bern_arc_length\0obtg_bern_arc_length_dev\0obtg_arc_length_obj\0obtg_arc_length_obj_dev\0"
@@ -328,7 +330,7 @@ void obtg_ctx_destroy(obtg_ctx* c)
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
     DevBuf* bufs[] = { &c->d_pairs, &c->d_obs, &c->d_w2, &c->d_Tt, &c->d_Td, &c->d_Tf, &c->d_ang_dd, &c->d_ang_flags, &c->d_vp_off, &c->d_vp_idx, &c->d_ang_w2n, &c->d_ang_w22n, &c->d_ang_wn, &c->d_ang_rows, &c->d_curv_tab, &c->d_ang_T4, &c->d_ang_cv2, &c->d_jac,
                        &c->d_binrows, &c->d_tiles, &c->d_poly_pts, &c->d_poly_off, &c->d_hp_a, &c->d_hp_b, &c->d_tile_chunk_off, &c->d_tile_order, &c->d_tile_pslots,
-                       &c->d_tile_cobj_off, &c->d_tile_cobjs, &c->d_tile_ij, &c->d_struct_tickets, &c->d_keep_H, &c->d_keep_VF, &c->d_ko_H, &c->d_ko_off, &c->d_ko_VO, &c->d_ko_Q, &c->d_ko_qoff, &c->d_ko_T, &c->ws_in,
+                       &c->d_tile_cobj_off, &c->d_tile_cobjs, &c->d_tile_ij, &c->d_struct_tickets, &c->d_keep_H, &c->d_keep_VF, &c->d_ko_H, &c->d_ko_off, &c->d_ko_VO, &c->d_ko_Q, &c->d_ko_qoff, &c->d_ko_T, &c->d_pk_H, &c->d_pk_IJ, &c->d_pk_Hn, &c->d_pk_feat, &c->ws_in,
                        &c->ws_in2, &c->ws_out, &c->ws_fd };
     for (DevBuf* b : bufs) b->release();
     for (auto& b : c->ws_misc) b.release();
@@ -2158,10 +2160,11 @@ int obtg_ctx_set_keep_out(obtg_ctx* c, const double* H, const int* obs_off, int 
 
 int obtg_len_keep_out(const obtg_ctx* c) { return c ? c->ko_P : 0; }
 
-static int keep_out_args(const obtg_ctx* c, const double* out, int B, int max_nodes, double eps_rel, double margin)
+// pair: the rows of the vehicle pairs (obtg_pair_keep_out_*), which need the separation region in place of the obstacle tables
+static int keep_out_args(const obtg_ctx* c, const double* out, int B, int max_nodes, double eps_rel, double margin, bool pair = false)
 {
-    if (!check_ctx(c) || c->ko_P <= 0 || (c->dim != 2 && c->dim != 3) || !out || B < 0 || max_nodes < 1 || !(eps_rel >= 0.0) ||
-        margin != margin)
+    if (!check_ctx(c) || (pair ? c->pk_F : c->ko_P) <= 0 || (c->dim != 2 && c->dim != 3) || !out || B < 0 || max_nodes < 1 ||
+        !(eps_rel >= 0.0) || margin != margin)
         return OBTG_ERR_ARG;
     return c->deg > 31 ? OBTG_ERR_UNSUPPORTED : OBTG_OK;
 }
@@ -2613,6 +2616,176 @@ int obtg_bern_keep_out_moving(obtg_ctx* c, const double* cv, int M, int dim, int
     h.fetch(t_star, dv + n, n);
     h.fetch(status, ds, n);
     return h.finish(val, dv, n);
+}
+
+// Vehicle pairs against ONE separation region (include/obtg.h "polytopic vehicle-to-vehicle separation"): the keep-out kernel on
+// D = Y_i - Y_j, the pairs i < j in lexicographic order from a table made here.  The region is a state of its own: the obstacle
+// tables and their motion neither read nor write it.
+int obtg_ctx_set_pair_keep_out(obtg_ctx* c, const double* H, int F)
+{
+    if (!check_ctx(c) || F < 0) return OBTG_ERR_ARG;
+    if (F > 0) {
+        if ((c->dim != 2 && c->dim != 3) || !H) return OBTG_ERR_ARG;
+        if (F > kKeepOutMaxFaces) return OBTG_ERR_UNSUPPORTED;
+        for (int f = 0; f < F; ++f)
+            if (H[(size_t)f * (c->dim + 1) + c->dim] <= 0.0) return OBTG_ERR_ARG;        // (the origin is strictly inside; a NaN passes)
+    }
+    (void)hipSetDevice(c->device);
+    OBTG_HIP(c, hipStreamSynchronize(c->stream));
+    c->pk_F = c->pk_NF = c->pk_eu_state = 0;
+    if (F == 0) return OBTG_OK;
+    const int N = c->n_veh;
+    std::vector<int> ij;
+    for (int i = 0; i < N; ++i)
+        for (int j = i + 1; j < N; ++j) { ij.push_back(i); ij.push_back(j); }
+    if (ij.empty()) ij.assign(2, 0);               // (one vehicle: no pair, the table is never read)
+    int rc = upload(c, c->d_pk_H, H, sizeof(double) * (size_t)F * (c->dim + 1));
+    if (!rc) rc = upload(c, c->d_pk_IJ, ij.data(), sizeof(int) * ij.size());
+    if (rc) return rc;
+    c->h_pk_H.assign(H, H + (size_t)F * (c->dim + 1));
+    c->pk_F = F;
+    return OBTG_OK;
+}
+
+int obtg_len_pair_keep_out(const obtg_ctx* c) { return c && c->pk_F > 0 ? c->n_veh * (c->n_veh - 1) / 2 : 0; }
+
+// the region's normalised faces and feature records, on the first Euclidean pair call after obtg_ctx_set_pair_keep_out
+static int pair_keep_out_euclid_tables(obtg_ctx* c)
+{
+    if (c->pk_eu_state) return c->pk_eu_state == 1 ? OBTG_OK : c->pk_eu_state;
+    const int d = c->dim, F = c->pk_F;
+    std::vector<double> Hn(c->h_pk_H.size()), rec, ginv(6 * (size_t)kKoMaxFeatures);
+    std::vector<int> idx(3 * (size_t)kKoMaxFeatures);
+    keep_out_normalise(c->h_pk_H.data(), F, d, Hn.data());
+    const int n = keep_out_enumerate(Hn.data(), F, d, kKoMaxFeatures, idx.data(), ginv.data());
+    if (n > kKoMaxFeatures) return c->pk_eu_state = OBTG_ERR_UNSUPPORTED;
+    keep_out_pack_features(idx.data(), ginv.data(), n, rec);
+    if (rec.empty()) rec.push_back(0.0);           // (a region without a feature: the buffer is never read)
+    (void)hipSetDevice(c->device);
+    int rc = upload(c, c->d_pk_Hn, Hn.data(), sizeof(double) * Hn.size());
+    if (!rc) rc = upload(c, c->d_pk_feat, rec.data(), sizeof(double) * rec.size());
+    if (rc) return rc;
+    c->pk_NF = n;
+    c->pk_eu_state = 1;
+    return OBTG_OK;
+}
+
+static int pair_keep_out_args(obtg_ctx* c, const double* out, int B, int max_nodes, double eps_rel, double margin, bool euclid)
+{
+    if (int rc = keep_out_args(c, out, B, max_nodes, eps_rel, margin, true)) return rc;
+    return euclid ? pair_keep_out_euclid_tables(c) : OBTG_OK;
+}
+
+// d_fi | d_ld: face[.][2] | lam, under the Euclidean metric faces[.][3] | dir[.][d]
+static int pair_keep_out_launch(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, bool euclid,
+                                double* d_out, double* d_t, int* d_fi, double* d_ld, double* d_bound, int* d_nodes, int* d_status,
+                                double* d_rel, double* d_jac)
+{
+    const int P = obtg_len_pair_keep_out(c);
+    KeepOutPairEuclidArgs eu{c->d_pk_feat.as<double>(), c->pk_NF, d_fi, d_ld};
+    return launch_keep_out_pair(c, c->dim, c->deg + 1, dY, (long)B * P, c->n_veh, P, (euclid ? c->d_pk_Hn : c->d_pk_H).as<double>(),
+                                c->d_pk_IJ.as<int>(), c->pk_F, euclid ? &eu : nullptr, margin, eps_rel, max_nodes, d_out, d_t,
+                                euclid ? nullptr : d_fi, euclid ? nullptr : d_ld, d_bound, d_nodes, d_status, d_rel, d_jac, OBTG_K_SPEED);
+}
+
+// want_jac: the _jac entry points, where the blocks are not optional
+static int pair_keep_out_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, bool euclid, double* d_out,
+                             double* d_t, int* d_fi, double* d_ld, double* d_bound, int* d_nodes, int* d_status, double* d_rel,
+                             bool want_jac, double* d_jac)
+{
+    if (int rc = pair_keep_out_args(c, d_out, B, max_nodes, eps_rel, margin, euclid)) return rc;
+    if (!dY || (want_jac && !d_jac)) return OBTG_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    return pair_keep_out_launch(c, dY, B, margin, eps_rel, max_nodes, euclid, d_out, d_t, d_fi, d_ld, d_bound, d_nodes, d_status, d_rel,
+                                d_jac);
+}
+
+// the host body: Y up; val | t_star | bound | lam or dir | rel | jac in ws_out, face(s) | nodes | status in WS_STATUS
+static int pair_keep_out_host(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, bool euclid, double* out,
+                              double* t_star, int* fi, double* ld, double* bound, int* nodes, int* status, double* rel, bool want_jac,
+                              double* jac)
+{
+    if (int rc = pair_keep_out_args(c, out, B, max_nodes, eps_rel, margin, euclid)) return rc;
+    if (!Y || (want_jac && !jac)) return OBTG_ERR_ARG;
+    const size_t n = (size_t)B * obtg_len_pair_keep_out(c);
+    if (n == 0) return OBTG_OK;
+    const size_t nb = n * c->dim * (c->deg + 1), nl = euclid ? n * c->dim : n, nf = euclid ? 3 : 2, nr = rel ? nb : 0,
+                 nj = want_jac ? nb : 0;
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    double* dv = h.out<double>(c->ws_out, 3 * n + nl + nr + nj);
+    int* di = h.out<int>(c->ws_misc[WS_STATUS], (nf + 2) * n);
+    double* dr = rel ? dv + 3 * n + nl : nullptr;
+    double* dj = want_jac ? dv + 3 * n + nl + nr : nullptr;
+    h.run([&] { return pair_keep_out_launch(c, dY, B, margin, eps_rel, max_nodes, euclid, dv, dv + n, di, dv + 3 * n, dv + 2 * n,
+                                            di + nf * n, di + (nf + 1) * n, dr, dj); });
+    h.fetch(t_star, dv + n, n);
+    h.fetch(bound, dv + 2 * n, n);
+    h.fetch(ld, dv + 3 * n, nl);
+    h.fetch(fi, di, nf * n);
+    h.fetch(nodes, di + nf * n, n);
+    h.fetch(status, di + (nf + 1) * n, n);
+    h.fetch(rel, dr, nr);
+    h.fetch(jac, dj, nj);
+    return h.finish(out, dv, n);
+}
+
+int obtg_pair_keep_out_true_min_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
+                                    double* d_t_star, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status,
+                                    double* d_rel)
+{
+    return pair_keep_out_dev(c, dY, B, margin, eps_rel, max_nodes, false, d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel,
+                             false, nullptr);
+}
+
+int obtg_pair_keep_out_true_min(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
+                                double* t_star, int* face, double* lam, double* bound, int* nodes, int* status, double* rel)
+{
+    return pair_keep_out_host(c, Y, B, margin, eps_rel, max_nodes, false, out, t_star, face, lam, bound, nodes, status, rel, false, nullptr);
+}
+
+int obtg_pair_keep_out_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
+                                        double* d_t_star, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status,
+                                        double* d_rel, double* d_jac)
+{
+    return pair_keep_out_dev(c, dY, B, margin, eps_rel, max_nodes, false, d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel,
+                             true, d_jac);
+}
+
+int obtg_pair_keep_out_true_min_jac(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
+                                    double* t_star, int* face, double* lam, double* bound, int* nodes, int* status, double* rel,
+                                    double* jac)
+{
+    return pair_keep_out_host(c, Y, B, margin, eps_rel, max_nodes, false, out, t_star, face, lam, bound, nodes, status, rel, true, jac);
+}
+
+int obtg_pair_keep_out_euclid_true_min_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes,
+                                           double* d_out, double* d_t_star, int* d_faces, double* d_dir, double* d_bound, int* d_nodes,
+                                           int* d_status, double* d_rel)
+{
+    return pair_keep_out_dev(c, dY, B, margin, eps_rel, max_nodes, true, d_out, d_t_star, d_faces, d_dir, d_bound, d_nodes, d_status, d_rel,
+                             false, nullptr);
+}
+
+int obtg_pair_keep_out_euclid_true_min(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
+                                       double* t_star, int* faces, double* dir, double* bound, int* nodes, int* status, double* rel)
+{
+    return pair_keep_out_host(c, Y, B, margin, eps_rel, max_nodes, true, out, t_star, faces, dir, bound, nodes, status, rel, false, nullptr);
+}
+
+int obtg_pair_keep_out_euclid_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes,
+                                               double* d_out, double* d_t_star, int* d_faces, double* d_dir, double* d_bound,
+                                               int* d_nodes, int* d_status, double* d_rel, double* d_jac)
+{
+    return pair_keep_out_dev(c, dY, B, margin, eps_rel, max_nodes, true, d_out, d_t_star, d_faces, d_dir, d_bound, d_nodes, d_status, d_rel,
+                             true, d_jac);
+}
+
+int obtg_pair_keep_out_euclid_true_min_jac(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
+                                           double* t_star, int* faces, double* dir, double* bound, int* nodes, int* status, double* rel,
+                                           double* jac)
+{
+    return pair_keep_out_host(c, Y, B, margin, eps_rel, max_nodes, true, out, t_star, faces, dir, bound, nodes, status, rel, true, jac);
 }
 
 // Free curves c[M][dim][K], any K from 2 to 32 whatever the context's shape is: the family's rows kernel and workspace search

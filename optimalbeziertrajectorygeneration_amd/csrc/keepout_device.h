@@ -40,6 +40,22 @@ __device__ __forceinline__ double ko_half_min(double v)
     return v;
 }
 constexpr int kKoLowLast = 0, kKoHighLast = 32;       // a lane of either half to read its minimum from
+constexpr int kKoFeatRec = 7;        // doubles per feature record
+
+// One wave's LDS, in doubles -- the ONE statement of the layout, for the kernel and for every launch's dynamic size:
+//     kKoStack frames of (dim K + 3) | kKoMaxFaces faces of (dim + 1) | ed
+//     ed: moving E[dim][K] | D[dim][K];  Euclidean: kKoMaxFeatures records;  pair: D[dim][K], behind the records where both
+constexpr int ko_lds_pair_d(bool euclid) { return euclid ? kKoMaxFeatures * kKoFeatRec : 0; }      // D's offset in ed (pair forms)
+// A macro and not a function, `pitch` (= dim K + 3) the kernel's own variable: token for token the expression the kernel had before
+// the pair forms.  As an inlined constexpr function the same sum changed the scalar address arithmetic, and with it the instruction
+// streams, of the six forms built before (tried twice).
+#define OBTG_KO_LDS_WAVE_DOUBLES(DIM, K, pitch, MV, EU, PR)                                                                          \
+    (kKoStack * pitch + kKoMaxFaces * (DIM + 1) + (MV ? 2 * DIM * K : 0) + (EU ? kKoMaxFeatures * kKoFeatRec : 0) + (PR ? DIM * K : 0))
+inline size_t ko_lds_bytes(int dim, int K, bool moving, bool euclid, bool pair)       // a launch's dynamic LDS
+{
+    const int pitch = dim * K + 3;
+    return sizeof(double) * kKoWaves * (size_t)OBTG_KO_LDS_WAVE_DOUBLES(dim, K, pitch, moving, euclid, pair);
+}
 __device__ __forceinline__ double ko_wave_max(double v)
 {
 #pragma unroll
@@ -113,8 +129,7 @@ __device__ __forceinline__ KoActive keep_out_active(const double* __restrict__ h
 //     otherwise        D = the largest candidate: a face's g_f, or a feature's sqrt(g_S . mu) with mu = Gram_S^-1 g_S all >= 0.
 // Every candidate (S, lambda = mu / value) is dual feasible, so every candidate is a lower bound of the distance and the largest
 // is the distance; with u = sum lambda_k a^_k and beta = sum lambda_k b^_k, D(q) >= u . q - beta for EVERY q.
-// (kKoMaxFeatures, features per obstacle: keepout_features.h; the host refuses more)
-constexpr int kKoFeatRec = 7;        // doubles per feature record
+// (kKoMaxFeatures, features per obstacle: keepout_features.h; the host refuses more.  kKoFeatRec: above, with the LDS layout)
 
 // The value of feature `rec` at p, or -INFINITY when a multiplier is negative (or the quadratic form is not positive); mu out.
 //   pair:    mu0 = fma(i01, g1, i00 g0), mu1 = fma(i11, g1, i01 g0);  q = fma(g1, mu1, g0 mu0)

@@ -37,6 +37,11 @@
 // per-lane accumulators (gm, gmx, lbh, lb) AHEAD of the statements that read them out, and dir and the active set leave through
 // keep_out_euclid_outputs, so the other instantiations keep every statement and their instruction streams.  A root that closes:
 // bound = min(lb, val), since a dual bound and the value it meets are rounded apart.
+//
+// Vehicle pairs (obtg_pair_keep_out_*; KeepOutPairParams, KeepOutEuclidPairParams): the same body on D = Y_i - Y_j
+// against ONE region around the origin, under either metric.  The prologue is one subtraction per control point; D stays in LDS
+// behind the faces (behind the records under the Euclidean metric: OBTG_KO_LDS_WAVE_DOUBLES), the root reads it from its registers and the
+// evaluation at t_star from LDS -- what the moving form does with its D.  No E, no restriction, no jac_tf.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -67,6 +72,7 @@ struct KeepOutParams {
     double margin, eps_rel;
     static constexpr bool kMoving = false;
     static constexpr bool kEuclid = false;
+    static constexpr bool kPair = false;
 };
 
 // The Euclidean metric: H holds the NORMALISED faces; the static form only
@@ -89,6 +95,19 @@ struct KeepOutMovingParams : KeepOutParams {
     double* __restrict__ jac_tf;         // [M] nullable
     int Km;                              // free curves: the motion's control points
     static constexpr bool kMoving = true;
+};
+
+// Vehicle pairs (obtg_pair_keep_out_*): VO holds the pair's (i, j), i < j, read from the table as the static form
+// reads its (vehicle, obstacle) -- no integer square root per item, and the order is the host's, whatever it is; the ONE region
+// is faces 0 .. F_all - 1 (and records 0 .. NF_all - 1).  The search runs on D = Y_i - Y_j; obs_off and feat_off are not read.
+struct KeepOutPairParams : KeepOutParams {
+    double* __restrict__ rel;            // [M][DIM][K] nullable: the relative control points
+    static constexpr bool kPair = true;
+};
+
+struct KeepOutEuclidPairParams : KeepOutEuclidParams {
+    double* __restrict__ rel;            // [M][DIM][K] nullable
+    static constexpr bool kPair = true;
 };
 
 // The Euclidean outputs of one item: dir[DIM] and the active set (obstacle-local faces fc, -1 padded; f0 the obstacle's first
@@ -116,14 +135,15 @@ __device__ __forceinline__ void keep_out_euclid_outputs(const KeepOutEuclidParam
 template <int DIM, class PRM>
 __global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const PRM p)
 {
-    constexpr bool MV = PRM::kMoving, EU = PRM::kEuclid;
+    constexpr bool MV = PRM::kMoving, EU = PRM::kEuclid, PR = PRM::kPair;
     static_assert(!(MV && EU), "the Euclidean metric is built for obstacles that stand still");
+    static_assert(!(MV && PR), "a pair's region does not move in the pair's own frame");
     extern __shared__ double lds[];
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     const int K = p.K, pitch = DIM * K + 3;
-    double* stk = lds + (size_t)wave * (kKoStack * pitch + kKoMaxFaces * (DIM + 1) + (MV ? 2 * DIM * K : 0) + (EU ? kKoMaxFeatures * kKoFeatRec : 0));
+    double* stk = lds + (size_t)wave * OBTG_KO_LDS_WAVE_DOUBLES(DIM, K, pitch, MV, EU, PR);
     double* hf = stk + kKoStack * pitch;
-    double* ed = hf + kKoMaxFaces * (DIM + 1);     // MV: E[DIM][K] | D[DIM][K];  EU: the obstacle's feature records
+    double* ed = hf + kKoMaxFaces * (DIM + 1);     // MV: E[DIM][K] | D[DIM][K];  EU: the feature records;  PR: D[DIM][K] behind them
     const long item = (long)blockIdx.x * kKoWaves + wave;
     if (item >= p.M) return;                       // (wave-uniform; the kernel has no workgroup barrier)
 
@@ -133,7 +153,13 @@ __global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const PRM p)
     int Km = 0;
     double tf_b = 1.0, ratio = 1.0;
     int nf = 0;                                    // EU: the obstacle's features
-    if (p.VO) {
+    if constexpr (PR) {
+        y = nullptr;                               // (the prologue below reads both vehicles; nothing after it reads y)
+        if constexpr (EU) {
+            nf = min(p.NF_all, kKoMaxFeatures);
+            for (int k = lane; k < nf * kKoFeatRec; k += kWave) ed[k] = p.feat[k];
+        }
+    } else if (p.VO) {
         const long b = item / p.P;
         const int2 vo = p.VO[(int)(item - b * p.P)];
         f0 = p.obs_off[vo.y];
@@ -181,8 +207,21 @@ __global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const PRM p)
             x[c] = d;
         }
     }
+    if constexpr (PR) {
+        // the relative curve D = Y_i - Y_j, one subtraction per control point, kept for the evaluation at t_star
+        const long b = item / p.P;
+        const int2 ij = p.VO[(int)(item - b * p.P)];
+        const double* yi = p.Y + ((size_t)b * p.n_veh + ij.x) * (DIM * K);
+        const double* yj = p.Y + ((size_t)b * p.n_veh + ij.y) * (DIM * K);
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) {
+            const double d = lane < K ? yi[c * K + lane] - yj[c * K + lane] : 0.0;
+            if (lane < K) ed[ko_lds_pair_d(EU) + c * K + lane] = d;
+            x[c] = d;
+        }
+    }
     ko_wave_sync();
-    if constexpr (!MV) {
+    if constexpr (!MV && !PR) {
 #pragma unroll
         for (int c = 0; c < DIM; ++c) x[c] = lane < K ? y[c * K + lane] : 0.0;
     }
@@ -198,6 +237,12 @@ __global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const PRM p)
     bad = __any(bad) != 0;
     if constexpr (MV) {
         bad = bad || bad_m;
+        if (p.rel && lane < K) {                   // (x is still the root: D itself)
+#pragma unroll
+            for (int c = 0; c < DIM; ++c) p.rel[(size_t)item * (DIM * K) + c * K + lane] = bad ? __builtin_nan("") : x[c];
+        }
+    }
+    if constexpr (PR) {
         if (p.rel && lane < K) {                   // (x is still the root: D itself)
 #pragma unroll
             for (int c = 0; c < DIM; ++c) p.rel[(size_t)item * (DIM * K) + c * K + lane] = bad ? __builtin_nan("") : x[c];
@@ -346,6 +391,7 @@ __global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const PRM p)
         for (int c = 0; c < DIM; ++c) {
             double b;
             if constexpr (MV) b = lane < K ? ed[(DIM + c) * K + lane] : 0.0;
+            else if constexpr (PR) b = lane < K ? ed[ko_lds_pair_d(EU) + c * K + lane] : 0.0;
             else b = lane < K ? y[c * K + lane] : 0.0;
             for (int r = 1; r < K - 1; ++r) {
                 const double up = wave_next_lane(b);
@@ -455,7 +501,7 @@ int launch_keep_out_moving(obtg_ctx* c, int dim, int K, const double* dY, long M
     p.Y = dY; p.H = d_H; p.obs_off = d_off; p.VO = (const int2*)d_VO;
     p.val = d_val; p.t = d_t; p.face = d_face; p.lam = d_lam; p.bound = d_bound; p.nodes = d_nodes; p.status = d_status; p.jac = d_jac;
     p.M = M; p.n_veh = n_veh; p.P = P; p.K = K; p.F_all = F_all; p.max_nodes = max_nodes; p.margin = margin; p.eps_rel = eps_rel;
-    const size_t lds = sizeof(double) * kKoWaves * ((size_t)kKoStack * (dim * K + 3) + kKoMaxFaces * (dim + 1) + (mo ? 2 * dim * K : 0));
+    const size_t lds = ko_lds_bytes(dim, K, mo != nullptr, false, false);
     const dim3 grid((unsigned)((M + kKoWaves - 1) / kKoWaves)), block(kKoWaves * kWave);
     ScopedKernelTimer t(c, kernel_id);
     if (mo) {
@@ -486,12 +532,48 @@ int launch_keep_out_euclid(obtg_ctx* c, int dim, int K, const double* dY, long M
     p.val = d_val; p.t = d_t; p.bound = d_bound; p.nodes = d_nodes; p.status = d_status; p.jac = d_jac;
     p.M = M; p.n_veh = n_veh; p.P = P; p.K = K; p.F_all = F_all; p.max_nodes = max_nodes; p.margin = margin; p.eps_rel = eps_rel;
     p.feat = d_feat; p.feat_off = d_feat_off; p.dir = d_dir; p.faces3 = d_faces3; p.NF_all = NF_all;
-    const size_t lds = sizeof(double) * kKoWaves * ((size_t)kKoStack * (dim * K + 3) + kKoMaxFaces * (dim + 1) + kKoMaxFeatures * kKoFeatRec);
+    const size_t lds = ko_lds_bytes(dim, K, false, true, false);
     const dim3 grid((unsigned)((M + kKoWaves - 1) / kKoWaves)), block(kKoWaves * kWave);
     void (*const kernel)(KeepOutEuclidParams) = dim == 2 ? k_keep_out<2, KeepOutEuclidParams> : k_keep_out<3, KeepOutEuclidParams>;
     if (lds > 64 * 1024) OBTG_HIP(c, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     ScopedKernelTimer t(c, kernel_id);
     hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, p);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
+// Vehicle pairs against the ONE region d_H[F_all][dim + 1] (eu: the NORMALISED faces, with eu->d_feat[eu->NF] records): d_IJ[P]
+// the pairs' (i, j).  faces metric: d_face[M][2], d_lam[M];  Euclidean: eu->d_faces3[M][3], eu->d_dir[M][dim].  d_rel nullable.
+int launch_keep_out_pair(obtg_ctx* c, int dim, int K, const double* dY, long M, int n_veh, int P, const double* d_H, const int* d_IJ,
+                         int F_all, const KeepOutPairEuclidArgs* eu, double margin, double eps_rel, int max_nodes, double* d_val,
+                         double* d_t, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status, double* d_rel,
+                         double* d_jac, int kernel_id)
+{
+    if (M <= 0) return OBTG_OK;
+    if ((dim != 2 && dim != 3) || K < 2 || K > kKoMaxK || F_all < 1 || F_all > kKoMaxFaces || (eu && eu->NF > kKoMaxFeatures))
+        return OBTG_ERR_UNSUPPORTED;
+    KeepOutEuclidPairParams p{};
+    p.Y = dY; p.H = d_H; p.VO = (const int2*)d_IJ;
+    p.val = d_val; p.t = d_t; p.face = d_face; p.lam = d_lam; p.bound = d_bound; p.nodes = d_nodes; p.status = d_status; p.jac = d_jac;
+    p.M = M; p.n_veh = n_veh; p.P = P; p.K = K; p.F_all = F_all; p.max_nodes = max_nodes; p.margin = margin; p.eps_rel = eps_rel;
+    p.rel = d_rel;
+    const size_t lds = ko_lds_bytes(dim, K, false, eu != nullptr, true);
+    const dim3 grid((unsigned)((M + kKoWaves - 1) / kKoWaves)), block(kKoWaves * kWave);
+    if (eu) {
+        p.face = nullptr; p.lam = nullptr;
+        p.feat = eu->d_feat; p.NF_all = eu->NF; p.dir = eu->d_dir; p.faces3 = eu->d_faces3;
+        void (*const kernel)(KeepOutEuclidPairParams) = dim == 2 ? k_keep_out<2, KeepOutEuclidPairParams> : k_keep_out<3, KeepOutEuclidPairParams>;
+        if (lds > 64 * 1024) OBTG_HIP(c, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ScopedKernelTimer t(c, kernel_id);
+        hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, p);
+    } else {
+        KeepOutPairParams pf{};
+        static_cast<KeepOutParams&>(pf) = p;
+        pf.rel = d_rel;
+        void (*const kernel)(KeepOutPairParams) = dim == 2 ? k_keep_out<2, KeepOutPairParams> : k_keep_out<3, KeepOutPairParams>;
+        ScopedKernelTimer t(c, kernel_id);
+        hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, pf);
+    }
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;
 }

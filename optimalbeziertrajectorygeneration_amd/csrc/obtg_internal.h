@@ -187,6 +187,14 @@ struct obtg_ctx {
     obtg::DevBuf d_ko_qoff;   // int[ko_O + 1], in control points
     obtg::DevBuf d_ko_T;      // double[ko_O]
     bool ko_motion = false;
+    // obtg_ctx_set_pair_keep_out: the ONE separation region of the vehicle pairs and the pairs' (i, j) in lexicographic order;
+    // pk_F == 0: none set.  The Euclidean tables as above: h_pk_H the host copy, pk_eu_state 0 / 1 / the code; pk_NF the records
+    obtg::DevBuf d_pk_H;      // double[pk_F][dim + 1]
+    obtg::DevBuf d_pk_IJ;     // int2[n_veh (n_veh - 1) / 2]
+    obtg::DevBuf d_pk_Hn;     // double[pk_F][dim + 1]
+    obtg::DevBuf d_pk_feat;   // double[pk_NF][7]
+    std::vector<double> h_pk_H;
+    int pk_F = 0, pk_NF = 0, pk_eu_state = 0;
     std::vector<int> h_pairs; // host copy of the pair table (2 ints per pair)
     std::vector<int> h_tiles; // row-window tiles of the current (pair_begin, pair_count)
     obtg::DevBuf d_tiles;
@@ -477,6 +485,20 @@ int launch_keep_out_euclid(obtg_ctx* c, int dim, int K, const double* dY, long M
                            const int* d_VO, int F_all, const double* d_feat, const int* d_feat_off, int NF_all, double margin,
                            double eps_rel, int max_nodes, double* d_val, double* d_t, int* d_faces3, double* d_dir, double* d_bound,
                            int* d_nodes, int* d_status, double* d_jac, int kernel_id);
+// Vehicle pairs against ONE region around the origin (obtg_pair_keep_out_*): the same kernel body on D = Y_i - Y_j, d_IJ[P] the
+// pairs' (i, j), d_H[F_all][dim + 1] the region (1 <= F_all <= 16).  eu null: the faces metric (d_face[M][2], d_lam[M]); eu set:
+// d_H holds the NORMALISED faces, eu->d_feat[eu->NF][7] the region's records (at most 128), and eu->d_faces3[M][3], eu->d_dir[M][dim]
+// stand in for d_face and d_lam, which are not written.  d_rel[M][dim][K] is a nullable output.
+struct KeepOutPairEuclidArgs {
+    const double* d_feat;
+    int NF;
+    int* d_faces3;
+    double* d_dir;
+};
+int launch_keep_out_pair(obtg_ctx* c, int dim, int K, const double* dY, long M, int n_veh, int P, const double* d_H, const int* d_IJ,
+                         int F_all, const KeepOutPairEuclidArgs* eu, double margin, double eps_rel, int max_nodes, double* d_val,
+                         double* d_t, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status, double* d_rel,
+                         double* d_jac, int kernel_id);
 // the angular-rate family's polynomials [B][n_veh][2][2 deg + 1] (obtg_ang_rate_poly; its rows_r0): dim 2, degree 1 .. 31
 int launch_ang_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);
 // The two curvature families, kind = ROWS_CURV (dim 2; two items, the sides, per vehicle; workspace rows num, den) or ROWS_SCURV

@@ -302,6 +302,37 @@ def _keep_out_tables(keepOut, numVeh, dim):
             np.ascontiguousarray(VO, dtype=np.int32))
 
 
+# The separation-region family, beside the table like _KEEP_OUT: its operand is the pair `separationRegion` kept
+# on the object, ONE convex region around the origin that the relative curve c_i - c_j of every vehicle pair i < j must stay out
+# of.  True rows only: one row per pair in the order of np.triu_indices(N, 1), the least of max_f (a_f . (c_i - c_j) - b_f) over
+# the trajectory minus `separationRegionMargin` -- or, with separationRegionMetric='euclidean', of the signed Euclidean distance.
+# What the device calls take in the bound's place is the table _separation_region_table makes of it.  Its rows belong to PAIRS:
+# the envelope provider scatters each block to both vehicles (separationRegionJacobian), not to one owner.
+_SEP_REGION = _RowFamily('sepregion', 'separationRegion', True, None, None, 'pair_keep_out_true_min', 'pair_keep_out_true_min_jac',
+                         None, (), False, 1, 'separationRegionConstraints', 'separationRegionJacobian', 'separation-region', False)
+_FAMILY[_SEP_REGION.key] = _SEP_REGION
+
+
+def _separation_region_table(region, dim):
+    """H[F][dim+1] of a `separationRegion` argument, checked like a `keepOut` entry: a pair (A[F][dim], b[F]), the region
+    A d <= b around the origin -- every b_f finite and > 0 (obtg_ctx_set_pair_keep_out)."""
+    if dim not in (2, 3):
+        raise ValueError("separationRegion needs dimension 2 or 3, not {}".format(dim))
+    try:
+        A, b = region
+        A, b = np.asarray(A, dtype=float), np.asarray(b, dtype=float)
+    except (TypeError, ValueError):
+        raise ValueError("separationRegion must be a pair (A[F][{}], b[F])".format(dim))
+    if A.ndim != 2 or A.shape[0] < 1 or A.shape[1] != dim or b.shape != (A.shape[0],):
+        raise ValueError("separationRegion must be a pair (A[F][{}], b[F]) with F >= 1, not shapes {} and {}"
+                         .format(dim, A.shape, b.shape))
+    if A.shape[0] > _KEEP_OUT_MAX_FACES:
+        raise ValueError("separationRegion has {} faces: a region may have at most {}".format(A.shape[0], _KEEP_OUT_MAX_FACES))
+    if not (np.all(np.isfinite(b)) and np.all(b > 0.0)):
+        raise ValueError("separationRegion needs every b_f finite and > 0 (the origin strictly inside), not {!r}".format(b.tolist()))
+    return np.ascontiguousarray(np.hstack((A, b[:, None])))
+
+
 def _keep_out_motion_tables(keepOutMotion, keepOut, dim, deg, tf=None):
     """(Q, q_off[O+1], T[O]) of a `keepOutMotion` argument, checked: a LIST with one entry per obstacle of `keepOut` -- None (the
     obstacle stands still), a bezier.Bezier of the problem's dimension with t0 == 0 (the obstacle's offset on [0, tf]), or a pair
@@ -494,7 +525,10 @@ class BezOptimization(object):
                  keepOut=None,
                  keepOutMargin=0.0,
                  keepOutMotion=None,
-                 keepOutMetric='faces'):
+                 keepOutMetric='faces',
+                 separationRegion=None,
+                 separationRegionMargin=0.0,
+                 separationRegionMetric='faces'):
         """Beyond the reference's keywords: `device` (HIP ordinal; None: this process's, see _capi.default_device) and `separationRows` --
         'all': temporalSeparationConstraints returns every elevated control point of every pair, as the
         reference does (optimization.py:337); 'min': one row per pair, the smallest of them -- the
@@ -569,6 +603,20 @@ class BezOptimization(object):
         # are not conservative near corners and C^1 outside.  Kept as `self.keepOutMetric`.
         self._check_keep_out_metric(keepOutMetric, keepOutMotion)
         self.keepOutMetric = keepOutMetric
+        # separationRegion (None: none; dim 2 or 3): polytopic vehicle-to-vehicle separation -- a pair (A[F][d], b[F]), every
+        # b_f > 0: the relative curve c_i - c_j of every pair i < j stays outside {d : A d <= b}.  separationRegionConstraints:
+        # N (N - 1) / 2 true rows in the order of np.triu_indices(N, 1), min over the trajectory of max_f (a_f . (c_i - c_j) - b_f)
+        # minus separationRegionMargin (obtg_pair_keep_out_true_min), or with separationRegionMetric='euclidean' of the signed
+        # Euclidean distance (obtg_pair_keep_out_euclid_true_min).  Beside maxSep, not in its place; vehicles only.  A region
+        # with R != -R makes a row depend on which vehicle of the pair has the smaller index.  Kept as `self.separationRegion`.
+        if separationRegion is not None:
+            _separation_region_table(separationRegion, dimension)
+            if not np.isfinite(float(separationRegionMargin)):
+                raise ValueError("separationRegionMargin must be finite, not {!r}".format(separationRegionMargin))
+        self._check_separation_region_metric(separationRegionMetric)
+        self.separationRegion = separationRegion
+        self.separationRegionMargin = float(separationRegionMargin)
+        self.separationRegionMetric = separationRegionMetric
         if separationRows not in ('all', 'min', 'active', 'true_min'):
             raise ValueError("separationRows must be 'all', 'min', 'active' or 'true_min', not {!r}".format(separationRows))
         if separationRows == 'active' and not 1 <= int(activeRows) <= 4:
@@ -672,6 +720,8 @@ class BezOptimization(object):
         tables (H, VF) of `keepIn` as it is NOW (drivers edit it in place); None: not set."""
         if fam is _KEEP_OUT:
             return None if self.keepOut is None else _keep_out_tables(self.keepOut, self.model['numVeh'], self.model['dim'])
+        if fam is _SEP_REGION:
+            return None if self.separationRegion is None else _separation_region_table(self.separationRegion, self.model['dim'])
         if fam is not _KEEP_IN:
             return self.model[fam.bound]
         return None if self.keepIn is None else _keep_in_tables(self.keepIn, self.model['numVeh'], self.model['dim'])
@@ -684,9 +734,19 @@ class BezOptimization(object):
             raise ValueError("keepOutMetric='euclidean' together with keepOutMotion is not built: moving obstacles take the "
                              "'faces' metric")
 
+    @staticmethod
+    def _check_separation_region_metric(metric):
+        if metric not in ('faces', 'euclidean'):
+            raise ValueError("separationRegionMetric must be 'faces' or 'euclidean', not {!r}".format(metric))
+
     def _vehicle_true_min(self, fam, ctx, Y, tf, bound, what, envelope=False):
         """The family's true-minimum call on the rows Y at TRUE_MIN_EPS_REL (envelope: with the envelope blocks): its dict;
         a search that ran out of budget raises in the name of `what` (bezier._raise_md)"""
+        if fam is _SEP_REGION:                                        # the vehicle pairs: one region, either metric
+            self._check_separation_region_metric(self.separationRegionMetric)
+            name = 'pair_keep_out_euclid_true_min' if self.separationRegionMetric != 'faces' else fam.true_min
+            call = getattr(ctx, name + ('_jac' if envelope else ''))
+            return _md_checked(call(Y, bound, margin=self.separationRegionMargin, eps_rel=self.TRUE_MIN_EPS_REL), what)
         if fam is _KEEP_OUT and self.keepOutMetric != 'faces':        # the Euclidean metric: the same tables, another quantity
             self._check_keep_out_metric(self.keepOutMetric, self.keepOutMotion)
             call = ctx.keep_out_euclid_true_min_jac if envelope else ctx.keep_out_euclid_true_min
@@ -982,6 +1042,18 @@ class BezOptimization(object):
         one-launch structured step, of the constraint sweep, of distributed.py or of sequential.py."""
         return self._vehicle_closure(_KEEP_OUT)
 
+    @property
+    def separationRegionConstraints(self):
+        """min over the trajectory of max_f (a_f . (c_i - c_j) - b_f) - separationRegionMargin >= 0 for every vehicle pair i < j,
+        in the order of np.triu_indices(N, 1): N (N - 1) / 2 true rows (obtg_pair_keep_out_true_min) -- the relative curve stays
+        outside `separationRegion`; negative, minus the depth, inside (vehicles at the same place: max_f (-b_f) - margin).  With
+        `separationRegionMetric='euclidean'` the rows are the signed Euclidean distance to the region minus the margin
+        (obtg_pair_keep_out_euclid_true_min).  The same whatever tf is.  A region with R != -R (a triangle, a box off centre)
+        makes a row depend on which vehicle of the pair comes first -- the one with the smaller index; ordered pairs are not
+        built.  Vehicles only: point and curve obstacles do not enter.  Not part of the one-launch structured step, of the
+        constraint sweep, of distributed.py or of sequential.py."""
+        return self._vehicle_closure(_SEP_REGION)
+
     def spatialSeparationConstraints(self, x, robust=False):
         """All-pairs minDist over vehicles AND shape obstacles (optimization.py:109-133);
         returns shape (P, 3): (dist, t1, t2) - maxSep, as the reference does.
@@ -1149,6 +1221,9 @@ class BezOptimization(object):
                 tail.append(('keepOutMotion', b''.join(t.tobytes() for t in self._keep_out_motion())))
             if self.keepOutMetric != 'faces':       # one more entry, only while the metric is not the default
                 tail.append(('keepOutMetric', self.keepOutMetric))
+        if self.separationRegion is not None:       # one trailing entry, only while a region is set: its bytes, margin and metric
+            tail.append(('separationRegion', self._operand(_SEP_REGION).tobytes(), self.separationRegionMargin,
+                         self.separationRegionMetric))
         return (int(DEG_ELEV), self.separationRows, *rows, self.activeRows, self._rv_cache[0], self.model['maxSep'], *bounds,
                 None if self._timeopt() else self.model['tf'],
                 None if self.pointObstacles is None else np.asarray(self.pointObstacles, dtype=float).tobytes(),
@@ -1378,6 +1453,36 @@ class BezOptimization(object):
         tables = self._bound(_KEEP_OUT, 'trueKeepOutClearances')
         r = self._true_rows_at(_KEEP_OUT, np.asarray(x, dtype=float), tables, 'trueKeepOutClearances')
         if self.keepOutMetric != 'faces':
+            return {k: r[k][0] for k in ('val', 't_star', 'faces', 'dir', 'status')}
+        return {k: r[k][0] for k in ('val', 't_star', 'face', 'lam', 'status')}
+
+    def separationRegionJacobian(self, x, structured=True, method='fd'):
+        """d(separationRegionConstraints)/dx, dense [N (N - 1) / 2][n_x]: method='fd' differences the closure's rows (one batched
+        call; `structured` changes nothing); method='envelope' is the derivative of each row at the parameter and the active faces
+        (Euclidean metric: the direction) its search returns (obtg_pair_keep_out[_euclid]_true_min_jac, one call at x): the block
+        of the pair's first vehicle, scattered with +1 to its columns and with -1 to the second vehicle's; method='exact' is not
+        built.  The rows have no explicit dependence on tf: that part of a time-optimal problem's tf column is an exact 0 (with
+        prescribed speeds the column still carries dY/dtf)."""
+        fam = _SEP_REGION
+        region = self._bound(fam, fam.jacobian)          # a missing region answers before anything is computed
+        self._check_jac_method(fam, method)
+        if method != 'envelope':
+            return self._jac(x, fam.key)
+        x = np.asarray(x, dtype=float)
+        r = self._vehicle_true_min(fam, self._ctx(False), self.reshapeVectors(x[None]), None, region, fam.jacobian + '(envelope)',
+                                   envelope=True)
+        pa, pb = np.triu_indices(self.model['numVeh'], 1)
+        return self._scatter_exact(r['jac'][0][:, None], (pa, pb), (1.0, -1.0))      # blocks of one row each
+
+    def trueSeparationRegionClearances(self, x):
+        """dict(val[P], t_star[P], face[P][2], lam[P], status[P]): per vehicle pair, in the order of separationRegionConstraints,
+        the row (clearance of c_i - c_j from the region minus separationRegionMargin), the parameter in [0, 1] where it is
+        reached, the active faces of the region (the second -1 without one), the first face's weight and the search's status
+        (obtg_pair_keep_out_true_min).  With separationRegionMetric='euclidean': dict(val[P], t_star[P], faces[P][3], dir[P][dim],
+        status[P]) (obtg_pair_keep_out_euclid_true_min)."""
+        region = self._bound(_SEP_REGION, 'trueSeparationRegionClearances')
+        r = self._true_rows_at(_SEP_REGION, np.asarray(x, dtype=float), region, 'trueSeparationRegionClearances')
+        if self.separationRegionMetric != 'faces':
             return {k: r[k][0] for k in ('val', 't_star', 'faces', 'dir', 'status')}
         return {k: r[k][0] for k in ('val', 't_star', 'face', 'lam', 'status')}
 

@@ -127,7 +127,11 @@ const char* obtg_strerror(int code);
  *      Later, still 7: new: polytopic vehicle-to-vehicle separation: the region obtg_ctx_set_pair_keep_out
  *      (obtg_len_pair_keep_out), the rows obtg_pair_keep_out_true_min[_dev] and obtg_pair_keep_out_euclid_true_min[_dev] and
  *      their envelope Jacobians obtg_pair_keep_out_true_min_jac[_dev], obtg_pair_keep_out_euclid_true_min_jac[_dev] (timed
- *      under OBTG_K_SPEED; no kernel id added). */
+ *      under OBTG_K_SPEED; no kernel id added).
+ *      Later, still 7: new: the proximity rows ("come close", "stay close"): the items obtg_ctx_set_proximity
+ *      (obtg_len_proximity), their polynomials obtg_proximity_poly[_dev], the certified extrema obtg_proximity_true[_dev] and
+ *      the envelope Jacobian obtg_proximity_true_jac[_dev] (timed under OBTG_K_TEMPORAL_SEP; no kernel id added).  New symbols
+ *      alone do not move the number: no existing meaning changed. */
 #define OBTG_ABI_VERSION 7
 int obtg_abi_version(void);
 
@@ -976,6 +980,62 @@ int obtg_keep_in_true_min_jac(obtg_ctx*, const double* Y, int B, double eps_rel,
                               double* jac /*[B][P][d][n+1]*/);
 int obtg_keep_in_true_min_jac_dev(obtg_ctx*, const double* dY, int B, double eps_rel, int max_nodes, double* d_out, double* d_t_star,
                                   int* d_status, double* d_jac);
+
+/* ---- proximity rows: a vehicle comes within, or stays within, a Euclidean radius of a point or of another vehicle ----
+ * An item is (a, b, kind) of items[P][3] with (rho, tau0, tau1) of params[P][3]: a is a vehicle, b another vehicle (b < N) or
+ * point b - N of points[Q][d], a table the family owns (it is not the context's point obstacles); kind is OBTG_PROX_WITHIN (0)
+ * or OBTG_PROX_REACH (1); rho > 0 is a Euclidean radius; 0 <= tau0 < tau1 <= 1 is the window of the normalised parameter in
+ * which the extremum is taken (a window in tau does not depend on tf: nothing here takes tf and there is no jac_tf).
+ *     g(tau) = (d/2) (rho^2 - |c_a(tau) - c_b(tau)|^2),  tau in [tau0, tau1]       (degree 2n; >= 0 iff the distance is <= rho)
+ * -- normSquare's (d/2) factor, as the separation rows carry it, here on rho^2 as well.
+ *     OBTG_PROX_WITHIN: the row is the MINIMUM of g over the window: >= 0 iff the pair never leaves range;
+ *     OBTG_PROX_REACH:  the row is the MAXIMUM of g over the window: >= 0 iff it comes within rho at some time.
+ * Coefficients (csrc/bern_device.h proximity_coeffs): every coordinate row of a, and of b when b is a vehicle, is cut down to
+ * the window in the order of obtg_bern_restrict on the span (0, 1) -- the right piece of a split at tau0 when tau0 > 0, then the
+ * left piece of a split of THAT piece at (tau1 - tau0) / (1 - tau0) when tau1 < 1, every level (1 - z) p[i] + z p[i+1] in plain
+ * double arithmetic (two products, one sum); the full window takes no split -- then the rounded difference, the product of
+ * obtg_temporal_sep's R = 0 rows, and g_k = fma(-1, c_k, (0.5 d) (rho rho)).  A point is a constant curve and is not cut.  An item
+ * with the full window is therefore fma(-1, ., (0.5 d)(rho rho)) of obtg_temporal_sep's R = 0 row at max_sep = 0 for the same pair.
+ * obtg_ctx_set_proximity: copies the three tables to the context (P = 0 clears them).  OBTG_ERR_ARG for a outside 0 .. N-1, b
+ *     outside 0 .. N+Q-1, a == b, a kind that is neither, rho that is not finite and > 0, a window that is not
+ *     0 <= tau0 < tau1 <= 1 (NaN ends too), a context whose d is not 2 or 3, or a null table that is needed.
+ * obtg_len_proximity: P, the rows per batch row.
+ * obtg_proximity_poly: out[B][P][2n+1], g's coefficients, un-negated for both kinds.  Degrees with a specialised kernel
+ *     (obtg_fast_kernels & 1) form them as the fused kernels do; other degrees up to 31 in the any-degree separation arithmetic
+ *     of obtg_temporal_sep on those degrees; above 31: OBTG_ERR_UNSUPPORTED.  DEG_ELEV does not enter anywhere in the family.
+ * obtg_proximity_true: val, bound, nodes, status are the bits of obtg_bern_extrema(eps_abs = 0, want_max = kind) on
+ *     obtg_proximity_poly's rows -- val is the value ATTAINED at the returned parameter, bound closes the bracket on the other
+ *     side (within: bound <= min g <= val; reach: val <= max g <= bound) -- and t_star = fma(t_w, tau1 - tau0, tau0) is the
+ *     CURVE's parameter of that call's t, the window's parameter t_w.  A row with a non-finite coefficient: val, t_star and bound
+ *     NaN, nodes 0, status OBTG_MD_OK, no search.  Specialised degrees: one launch, the coefficients never reach memory; other
+ *     degrees up to 31: the rows into a workspace, then their search (two launches).  Every output but val is nullable.
+ * obtg_proximity_true_jac: the same outputs with the same bits, plus the envelope block of every row at its t_star with respect
+ *     to the control points of a, evaluated on the UNRESTRICTED control points:
+ *         jac[B][P][d][n+1]:  jac[c][i] = -d B_i^n(t_star) (c_a - c_b)_c(t_star)          (both kinds)
+ *     -- obtg_temporal_sep_true_min_jac's block with the sign turned, every element its exact negation (csrc/bern_device.h
+ *     envelope_block), and its conventions: when b is a vehicle its block is the exact negation and is not stored; a point has no
+ *     variable.  A NaN t_star gives a NaN block.  Every specialised count has a fused value-and-blocks kernel (one launch); a
+ *     context created under OBTG_TRUE_MIN_JAC_FUSED=0 forms the blocks in one more launch, as other degrees do after their values.
+ * Host and _dev calls give the same bits.  No items set, or a context whose d is not 2 or 3: OBTG_ERR_ARG before any launch.
+ * Every launch is timed under OBTG_K_TEMPORAL_SEP.  _dev: dY is device memory [B][N d][n+1]; dY = NULL inside an obtg_fd_view is
+ * not built for this family and answers OBTG_ERR_ARG.  Not part of obtg_constraint_sweep_dev or of the structured step. */
+#define OBTG_PROX_WITHIN 0
+#define OBTG_PROX_REACH 1
+int obtg_ctx_set_proximity(obtg_ctx*, const int* items /*[P][3]*/, const double* params /*[P][3]*/, const double* points /*[Q][d]*/,
+                           int P, int Q);
+int obtg_len_proximity(const obtg_ctx*);    /* P                   */
+int obtg_proximity_poly(obtg_ctx*, const double* Y, int B, double* out /*[B][P][2n+1]*/);
+int obtg_proximity_poly_dev(obtg_ctx*, const double* dY, int B, double* d_out);
+int obtg_proximity_true(obtg_ctx*, const double* Y, int B, double eps_rel, int max_nodes, double* val /*[B][P]*/,
+                        double* t_star /*[B][P], nullable*/, double* bound /*[B][P], nullable*/, int* nodes /*[B][P], nullable*/,
+                        int* status /*[B][P], nullable*/);
+int obtg_proximity_true_dev(obtg_ctx*, const double* dY, int B, double eps_rel, int max_nodes, double* d_val, double* d_t_star,
+                            double* d_bound, int* d_nodes, int* d_status);
+int obtg_proximity_true_jac(obtg_ctx*, const double* Y, int B, double eps_rel, int max_nodes, double* val /*[B][P]*/,
+                            double* t_star /*[B][P], nullable*/, double* bound /*[B][P], nullable*/, int* nodes /*[B][P], nullable*/,
+                            int* status /*[B][P], nullable*/, double* jac /*[B][P][d][n+1]*/);
+int obtg_proximity_true_jac_dev(obtg_ctx*, const double* dY, int B, double eps_rel, int max_nodes, double* d_val, double* d_t_star,
+                                double* d_bound, int* d_nodes, int* d_status, double* d_jac);
 
 /* ---- keep-out obstacles: every listed vehicle stays outside convex obstacles, in 2-D and 3-D ----
  * An obstacle is a convex set {p : a_f . p <= b_f, f = 1 .. F_o}: a run of rows (a_f[0 .. d-1], b_f) of H[F][d+1], obstacle o

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("OBTG_LIB") or os.path.join(HERE, "libobtg_hip.so")   
 OK = 0
 ST_OK, ST_MD_CAP, ST_MAXITER, ST_CYCLE = 0, 1, 2, 3
 MD_OK, MD_NODE_CAP, MD_DEPTH_CAP, MD_GJK_CAP = 0, 1, 2, 3
+PROX_WITHIN, PROX_REACH = 0, 1     # the kinds of a proximity item (obtg_ctx_set_proximity): the minimum / the maximum of g
 K_TEMPORAL_SEP, K_SPEED, K_ANG_RATE, K_GJK, K_MIN_DIST, K_FD_BATCH, K_BERN, K_PAIR_SWEEP, K_JAC, K_COUNT = range(10)
 K_ARC_LENGTH, K_END = 9, 10      # ids added after ABI revision 7 was cut: OBTG_K_COUNT stays what that revision's callers sized arrays by
 
@@ -164,6 +165,14 @@ _SIGNATURES = {
     "obtg_accel_true_min_dev": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp]),
     "obtg_accel_true_min_jac": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "obtg_accel_true_min_jac_dev": (_i, [_vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_ctx_set_proximity": (_i, [_vp, _vp, _vp, _vp, _i, _i]),
+    "obtg_len_proximity": (_i, [_vp]),
+    "obtg_proximity_poly": (_i, [_vp, _vp, _i, _vp]),
+    "obtg_proximity_poly_dev": (_i, [_vp, _vp, _i, _vp]),
+    "obtg_proximity_true": (_i, [_vp, _vp, _i, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_proximity_true_dev": (_i, [_vp, _vp, _i, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_proximity_true_jac": (_i, [_vp, _vp, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "obtg_proximity_true_jac_dev": (_i, [_vp, _vp, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "obtg_ctx_set_keep_in": (_i, [_vp, _vp, _i, _vp, _i]),
     "obtg_len_keep_in": (_i, [_vp]),
     "obtg_keep_in": (_i, [_vp, _vp, _i, _vp]),
@@ -536,6 +545,8 @@ class Context(object):
         self._keep_out_key = None     # the bytes of the tables set_keep_out last sent
         self._keep_out_motion_key = None     # the bytes of the motion set_keep_out_motion last sent; None: none set
         self._pair_keep_out_key = None       # the bytes of the separation region set_pair_keep_out last sent; None: none set
+        self.proximity_items = 0      # items of the proximity rows; 0: none set
+        self._proximity_key = None    # the bytes of the tables set_proximity last sent
 
     # -- plumbing
     def close(self):
@@ -855,6 +866,80 @@ class Context(object):
     # -- keep-out obstacles (include/obtg.h "keep-out obstacles"): obstacles = (H[F][dim+1], obs_off[O+1], VO[P][2]); every call
     # below takes them as its optional `obstacles` operand -- sent to the context only when their bytes differ from what the
     # context holds -- or, with None, works on the tables set_keep_out left there
+    # -- proximity rows ("come close", "stay close": DESIGN.md 4.28).  The same shape as keep-in's: `tables` is (items[P][3],
+    # params[P][3], points[Q][dim]) to set first when it differs from what the context holds, or None: the call works on the
+    # tables set_proximity left there
+    def set_proximity(self, items, params, points=None):
+        """obtg_ctx_set_proximity: items (a, b, kind) -- vehicle a against vehicle b < n_veh or point b - n_veh of `points`, kind
+        PROX_WITHIN (the minimum of g over the window) or PROX_REACH (the maximum) -- and params (rho, tau0, tau1), the Euclidean
+        radius and the window of the normalised parameter; an empty list clears the tables."""
+        items = np.ascontiguousarray(np.asarray(items, dtype=np.int32).reshape(-1, 3))
+        params = _f64(np.asarray(params, dtype=np.float64).reshape(-1, 3))
+        points = _f64(np.zeros((0, self.dim)) if points is None else np.asarray(points, dtype=np.float64).reshape(-1, self.dim))
+        if items.shape[0] != params.shape[0]:
+            raise ValueError("proximity items and params must have one row per item, got %d and %d" % (items.shape[0], params.shape[0]))
+        self._check(self._lib.obtg_ctx_set_proximity(self._h, _ptr(items), _ptr(params), _ptr(points) if points.size else None,
+                                                     items.shape[0], points.shape[0]), "obtg_ctx_set_proximity")
+        self.proximity_items = items.shape[0]
+        self._proximity_key = (items.tobytes(), params.tobytes(), points.tobytes())
+
+    def _proximity(self, tables):
+        if tables is not None:
+            items, params, points = tables
+            items = np.ascontiguousarray(np.asarray(items, dtype=np.int32).reshape(-1, 3))
+            params = _f64(np.asarray(params, dtype=np.float64).reshape(-1, 3))
+            points = _f64(np.asarray(points, dtype=np.float64).reshape(-1, self.dim))
+            if self._proximity_key != (items.tobytes(), params.tobytes(), points.tobytes()):
+                self.set_proximity(items, params, points)
+        return self.proximity_items        # (0: no items -- the library's call answers OBTG_ERR_ARG)
+
+    @property
+    def len_proximity(self):
+        return self._lib.obtg_len_proximity(self._h)
+
+    def proximity_poly(self, Y, tables=None):
+        """g's Bernstein coefficients per item (obtg_proximity_poly): [B][P][2 deg + 1], g = (dim/2)(rho^2 - |c_a - c_b|^2) on the
+        item's window, un-negated for both kinds."""
+        P = self._proximity(tables)
+        Y, B = self._rows(Y)
+        out = pinned_empty((B, P, 2 * self.deg + 1))
+        self._check(self._lib.obtg_proximity_poly(self._h, _ptr(Y), B, _ptr(out)), "obtg_proximity_poly")
+        return out
+
+    def proximity_poly_dev(self, dY, B, d_out):
+        self._check(self._lib.obtg_proximity_poly_dev(self._h, _vp(dY), int(B), _vp(d_out)), "obtg_proximity_poly_dev")
+
+    def _proximity_true(self, name, Y, tables, eps_rel, max_nodes, jac):
+        P = self._proximity(tables)
+        Y, B = self._rows(Y)
+        r = dict(val=pinned_empty((B, P)), t_star=np.empty((B, P)), bound=np.empty((B, P)), nodes=np.zeros((B, P), np.int32),
+                 status=np.zeros((B, P), np.int32))
+        if jac:
+            r["jac"] = pinned_empty((B, P, self.dim, self.deg + 1))
+        self._check(getattr(self._lib, name)(self._h, _ptr(Y), B, float(eps_rel), int(max_nodes), *[_ptr(a) for a in r.values()]), name)
+        return r
+
+    def proximity_true(self, Y, tables=None, eps_rel=1e-9, max_nodes=100000):
+        """Per item the certified extremum of g over its window (obtg_proximity_true): dict(val[B][P] -- the value attained at
+        t_star[B][P], the curve's parameter --, bound[B][P] closing the bracket on the other side, nodes[B][P], status[B][P] as
+        MD_*).  A `within` row is the minimum (>= 0: the pair never leaves range), a `reach` row the maximum (>= 0: it comes
+        within rho at some time)."""
+        return self._proximity_true("obtg_proximity_true", Y, tables, eps_rel, max_nodes, False)
+
+    def proximity_true_jac(self, Y, tables=None, eps_rel=1e-9, max_nodes=100000):
+        """proximity_true with its envelope Jacobian (obtg_proximity_true_jac): the same outputs with the same bits, and
+        jac[B][P][dim][deg+1] = -dim B_i(t_star) (c_a - c_b)(t_star): d/d(a's control points); a second vehicle's block is the
+        negation, a point has none."""
+        return self._proximity_true("obtg_proximity_true_jac", Y, tables, eps_rel, max_nodes, True)
+
+    def proximity_true_dev(self, dY, B, d_val, d_t_star=None, d_bound=None, d_nodes=None, d_status=None, d_jac=None, eps_rel=1e-9,
+                           max_nodes=100000):
+        """The device-pointer form (obtg_proximity_true_dev; with d_jac: obtg_proximity_true_jac_dev)."""
+        name = "obtg_proximity_true_jac_dev" if d_jac is not None else "obtg_proximity_true_dev"
+        tail = (d_jac,) if d_jac is not None else ()
+        self._check(getattr(self._lib, name)(self._h, _vp(dY), int(B), float(eps_rel), int(max_nodes),
+                                             *[_vp(p) for p in (d_val, d_t_star, d_bound, d_nodes, d_status) + tail]), name)
+
     def set_keep_out(self, H, obs_off, VO):
         """obtg_ctx_set_keep_out: the faces a . p <= b of every obstacle as rows (a, b) of H, obstacle o owning rows
         obs_off[o] .. obs_off[o+1]-1, and the (vehicle, obstacle) items VO; an empty VO clears the tables."""

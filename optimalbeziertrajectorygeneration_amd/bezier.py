@@ -321,6 +321,38 @@ class Bezier(BezierParams):
         _raise_md(r['status'][0], 'keepOutClearance')
         return float(r['val'][0]), float(r['t_star'][0])
 
+    def proximityMargin(self, target, radius, kind='reach', window=(0.0, 1.0), eps=1e-12, max_nodes=100000):
+        """(margin, t): the certified extremum over the window (tau0, tau1) of the curve's normalised parameter of
+        g = (dim/2) (radius^2 - |c - target|^2) and the parameter in [0, 1] where it is attained (obtg_proximity_true, the
+        search behind BezOptimization.proximityConstraints).  kind='reach': the maximum -- >= 0 iff the curve comes within the
+        Euclidean `radius` of the target at some time of the window; kind='within': the minimum -- >= 0 iff it never leaves that
+        range.  target: a point of the curve's dimension, or a Bezier of the same dimension, degree and span (the distance is
+        then taken at equal times).  Dimension 2 or 3.  Not in the reference."""
+        if kind not in ('reach', 'within'):
+            raise ValueError("kind must be 'reach' or 'within', not {!r}".format(kind))
+        if self.dim not in (2, 3):
+            raise ValueError('The input curve must be two or three dimensional,\n'
+                             'instead it is {} dimensional'.format(self.dim))
+        code = _capi.PROX_REACH if kind == 'reach' else _capi.PROX_WITHIN
+        if isinstance(target, Bezier):
+            if target.dim != self.dim or target.deg != self.deg or (target.t0, target.tf) != (self.t0, self.tf):
+                raise ValueError('proximityMargin needs a target curve of the same dimension, degree and span')
+            Y, n_veh, b, pts = np.vstack((self.cpts, target.cpts)), 2, 1, None
+        else:
+            pts = np.asarray(target, dtype=np.float64).reshape(-1)
+            if pts.shape != (self.dim,):
+                raise ValueError('proximityMargin needs a target point of dimension {} or a Bezier'.format(self.dim))
+            Y, n_veh, b = self.cpts, 1, 1
+        ctx = _capi.Context(n_veh, self.dim, self.deg, 0, device=_capi.default_device())
+        try:
+            tables = (np.array([[0, b, code]], np.int32), np.array([[float(radius), float(window[0]), float(window[1])]]),
+                      np.zeros((0, self.dim)) if pts is None else pts[None])
+            r = ctx.proximity_true(Y, tables, eps_rel=float(eps), max_nodes=int(max_nodes))
+        finally:
+            ctx.close()
+        _raise_md(r['status'][0, 0], 'proximityMargin')
+        return float(r['val'][0, 0]), float(r['t_star'][0, 0])
+
     def split(self, tDiv):
         """Two curves, before and after tDiv (bezier.py:533-572): de Casteljau at (tDiv - t0)/(tf - t0); the
         pieces keep the original span's ends, [t0, tDiv] and [tDiv, tf]."""

@@ -234,7 +234,9 @@ __device__ __forceinline__ void normsq_coeffs(const double (&a)[DIM][NC], ctab_t
 // product stands alone, so this function generates the same arithmetic under `fp contract(fast)` and `(off)`, for every
 // NCMAX >= nc and wherever it is inlined: the blocks of the fused and of the any-degree kernel are the same bits.
 // t = 0 / t = 1 leave exactly one non-zero column (0 / n); a NaN t gives a NaN block.
-template <int NCMAX, int DIM>
+// NEG: the block of -p(t), every element the exact negation (the proximity rows, whose polynomial carries the distance with a
+// minus sign).
+template <int NCMAX, int DIM, bool NEG = false>
 __device__ __forceinline__ void envelope_block(const double* __restrict__ ya, const double* __restrict__ yb, int b_cs, int b_is,
                                                int nc, double t, double* __restrict__ out)
 {
@@ -255,7 +257,7 @@ __device__ __forceinline__ void envelope_block(const double* __restrict__ ya, co
 #pragma unroll
         for (int i = 0; i < NCMAX; ++i)
             if (i < nc) dl = __builtin_fma(w[i], ya[c * nc + i] - yb[c * b_cs + i * b_is], dl);
-        const double kd = (double)DIM * dl;
+        const double kd = NEG ? -((double)DIM * dl) : (double)DIM * dl;
 #pragma unroll
         for (int i = 0; i < NCMAX; ++i)
             if (i < nc) out[c * nc + i] = kd * w[i];
@@ -302,6 +304,89 @@ __device__ __forceinline__ void keep_in_envelope_block(const double* __restrict_
         for (int i = 0; i < NCMAX; ++i)
             if (i < nc) out[c * nc + i] = na * w[i];
     }
+}
+
+// The cuts of one curve on [t0, tf] down to [a, e] (t0 <= a < e <= tf), in the reference's order (bern_kernels.hip, the
+// one-vs-many minima of curves on different time spans): what lies before a first, then what lies after e of THAT piece.
+struct SpanCut {
+    bool head, tail;          // split off what lies before a / after e
+    double zh, zt;
+    __device__ __forceinline__ SpanCut(double t0, double tf, double a, double e)
+    {
+        head = t0 < a;
+        zh = (a - t0) / (tf - t0);
+        if (head) t0 = a;
+        tail = tf > e;
+        zt = (e - t0) / (tf - t0);
+    }
+};
+
+// out[k] (k < L_out, lanes strided) = (1/bo[k]) * sum_j ah[j] * bh[k-j],  ah: la entries, bh: lb entries
+__device__ __forceinline__ double conv_at(const double* ah, int la, const double* bh, int lb, int k)
+{
+    double s = 0.0;
+    const int j0 = max(0, k - (lb - 1)), j1 = min(la - 1, k);
+    for (int j = j0; j <= j1; ++j) s = fma(ah[j], bh[k - j], s);
+    return s;
+}
+
+// ---- The proximity rows (obtg_proximity_poly, obtg_proximity_true[_jac]): vehicle a against b -- another vehicle or a fixed
+// point -- within the Euclidean radius rho on the window [tau0, tau1] of the normalised parameter:
+//     g(tau) = (DIM/2) (rho^2 - |c_a(tau) - c_b(tau)|^2),  tau in [tau0, tau1]      (degree 2n; >= 0 iff the distance is <= rho)
+// proximity_coeffs IS the definition of the rows for the counts with a kernel of their own: every coordinate row of a, and of b
+// when b is a vehicle, cut down to the window under SpanCut(0, 1, tau0, tau1) by window_row -- bern_kernels.hip restrict_row's
+// levels with each product rounded alone: contraction is switched off inside, so the bits are those of (1 - z) p[i] + z p[i+1]
+// in plain double arithmetic whatever the including unit's mode; the full window takes no cut and leaves the row's bits --
+// then the difference, normsq_coeffs, and fma(-1, c_k, (DIM/2) rho^2) with the offset proximity_offset forms.  A point is a
+// constant curve and is not cut.  ya: a's [DIM][NC] control points; b's element (c, i) is yb[c * b_cs + i * b_is] (a vehicle:
+// NC, 1; a point: 1, 0).  The value kernels, the value-and-blocks kernels and the rows kernel all call this.
+template <int NC>
+__device__ __forceinline__ void window_row(double (&p)[NC], const SpanCut& s)
+{
+#pragma clang fp contract(off)
+    if (s.head) {             // the right piece: level lev overwrites p[0 .. NC-lev), its last element stays behind
+        const double z = s.zh, w = 1.0 - z;
+#pragma unroll
+        for (int lev = 1; lev < NC; ++lev)
+#pragma unroll
+            for (int i = 0; i < NC - lev; ++i) p[i] = w * p[i] + z * p[i + 1];
+    }
+    if (s.tail) {             // the left piece: level lev overwrites p[lev .. NC), its first element stays behind
+        const double z = s.zt, w = 1.0 - z;
+#pragma unroll
+        for (int lev = 1; lev < NC; ++lev)
+#pragma unroll
+            for (int i = NC - 1; i >= lev; --i) p[i] = w * p[i - 1] + z * p[i];
+    }
+}
+
+template <int DIM>
+__device__ __forceinline__ double proximity_offset(const double rho) { return (0.5 * (double)DIM) * (rho * rho); }
+
+template <int NC, int DIM>
+__device__ __forceinline__ void proximity_coeffs(const double* __restrict__ ya, const double* __restrict__ yb, const int b_cs,
+                                                 const int b_is, const double rho, const double tau0, const double tau1,
+                                                 const ctab_t W2, double (&cf)[2 * NC - 1])
+{
+    // (the last line is fma(-1, c_k, off) of the ROUNDED c_k = S_k s, the separation row's own coefficient: with contraction
+    // allowed here the compiler folds the product into it, fma(-S_k, s, off), one rounding fewer)
+#pragma clang fp contract(off)
+    const SpanCut cut(0.0, 1.0, tau0, tau1);
+    double a[DIM][NC];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) {       // one dimension at a time: two rows live next to the difference
+        double x[NC], y[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) { x[c] = ya[d * NC + c]; y[c] = yb[d * b_cs + c * b_is]; }
+        window_row<NC>(x, cut);
+        if (b_is) window_row<NC>(y, cut);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) a[d][c] = x[c] - y[c];
+    }
+    normsq_coeffs<NC, DIM>(a, W2, cf);
+    const double off = proximity_offset<DIM>(rho);
+#pragma unroll
+    for (int k = 0; k < 2 * NC - 1; ++k) cf[k] = __builtin_fma(-1.0, cf[k], off);
 }
 
 // The source curve of a speed row -- Bezier.diff(): (n/T)(P_(i+1) - P_i), then elev(1) back to degree n (bezier.py:497-519) --

@@ -230,20 +230,7 @@ struct OneManySpanParams {
     double no_overlap;
 };
 
-// the cuts of one curve on [t0, tf] down to [a, e] (t0 <= a < e <= tf)
-struct SpanCut {
-    bool head, tail;          // split off what lies before a / after e
-    double zh, zt;
-    __device__ __forceinline__ SpanCut(double t0, double tf, double a, double e)
-    {
-        head = t0 < a;
-        zh = (a - t0) / (tf - t0);
-        if (head) t0 = a;
-        tail = tf > e;
-        zt = (e - t0) / (tf - t0);
-    }
-};
-
+// (the cuts of one curve on [t0, tf] down to [a, e]: bern_device.h SpanCut)
 // one coordinate row, in place in registers: every level is (1-z) p[i] + z p[i+1]
 template <int NC>
 __device__ __forceinline__ void restrict_row(double (&p)[NC], const SpanCut& s)
@@ -626,14 +613,7 @@ struct GenParams {
     int min_only;
 };
 
-// out[k] (k < L_out, lanes strided) = (1/bo[k]) * sum_j ah[j] * bh[k-j],  ah: la entries, bh: lb entries
-__device__ __forceinline__ double conv_at(const double* ah, int la, const double* bh, int lb, int k)
-{
-    double s = 0.0;
-    const int j0 = max(0, k - (lb - 1)), j1 = min(la - 1, k);
-    for (int j = j0; j <= j1; ++j) s = fma(ah[j], bh[k - j], s);
-    return s;
-}
+// (conv_at, one output of such a convolution: bern_device.h)
 
 // ah = [dim][n+1] scaled operand C(n,j) a_j in LDS (complete), ch = [2n+1] scratch: the product, the elevation and the
 // output of one item (row `row` of the output) -- the second half of k_generic_normsq_elev, shared with the aligned form

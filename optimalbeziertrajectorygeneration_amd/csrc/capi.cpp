@@ -262,6 +262,7 @@ const char* obtg_abi_symbols(void)
         "obtg_keep_out_features\0obtg_keep_out_euclid_true_min\0obtg_keep_out_euclid_true_min_dev\0obtg_keep_out_euclid_true_min_jac\0obtg_keep_out_euclid_true_min_jac_dev\0obtg_bern_keep_out_euclid\0obtg_bern_keep_out_euclid_dev\0"
         "obtg_ctx_set_pair_keep_out\0obtg_len_pair_keep_out\0obtg_pair_keep_out_true_min\0obtg_pair_keep_out_true_min_dev\0obtg_pair_keep_out_true_min_jac\0obtg_pair_keep_out_true_min_jac_dev\0"
         "obtg_pair_keep_out_euclid_true_min\0obtg_pair_keep_out_euclid_true_min_dev\0obtg_pair_keep_out_euclid_true_min_jac\0obtg_pair_keep_out_euclid_true_min_jac_dev\0"
+        "obtg_ctx_set_proximity\0obtg_len_proximity\0obtg_proximity_poly\0obtg_proximity_poly_dev\0obtg_proximity_true\0obtg_proximity_true_dev\0obtg_proximity_true_jac\0obtg_proximity_true_jac_dev\0"
         "obtg_bern_elev\0obtg_bern_diff\0obtg_bern_mul\0obtg_bern_normsq\0obtg_bern_split\0obtg_bern_restrict\0obtg_bern_eval\0"
         "obtg_euclidean_obj\0obtg_accel_obj\0obtg_jerk_obj\0"
         "obtg_bern_arc_length\0obtg_bern_arc_length_dev\0obtg_arc_length_obj\0obtg_arc_length_obj_dev\0"
@@ -330,7 +331,7 @@ void obtg_ctx_destroy(obtg_ctx* c)
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
     DevBuf* bufs[] = { &c->d_pairs, &c->d_obs, &c->d_w2, &c->d_Tt, &c->d_Td, &c->d_Tf, &c->d_ang_dd, &c->d_ang_flags, &c->d_vp_off, &c->d_vp_idx, &c->d_ang_w2n, &c->d_ang_w22n, &c->d_ang_wn, &c->d_ang_rows, &c->d_curv_tab, &c->d_ang_T4, &c->d_ang_cv2, &c->d_jac,
                        &c->d_binrows, &c->d_tiles, &c->d_poly_pts, &c->d_poly_off, &c->d_hp_a, &c->d_hp_b, &c->d_tile_chunk_off, &c->d_tile_order, &c->d_tile_pslots,
-                       &c->d_tile_cobj_off, &c->d_tile_cobjs, &c->d_tile_ij, &c->d_struct_tickets, &c->d_keep_H, &c->d_keep_VF, &c->d_ko_H, &c->d_ko_off, &c->d_ko_VO, &c->d_ko_Q, &c->d_ko_qoff, &c->d_ko_T, &c->d_pk_H, &c->d_pk_IJ, &c->d_pk_Hn, &c->d_pk_feat, &c->ws_in,
+                       &c->d_tile_cobj_off, &c->d_tile_cobjs, &c->d_tile_ij, &c->d_struct_tickets, &c->d_keep_H, &c->d_keep_VF, &c->d_ko_H, &c->d_ko_off, &c->d_ko_VO, &c->d_ko_Q, &c->d_ko_qoff, &c->d_ko_T, &c->d_pk_H, &c->d_pk_IJ, &c->d_pk_Hn, &c->d_pk_feat, &c->d_prox_items, &c->d_prox_par, &c->d_prox_pts, &c->ws_in,
                        &c->ws_in2, &c->ws_out, &c->ws_fd };
     for (DevBuf* b : bufs) b->release();
     for (auto& b : c->ws_misc) b.release();
@@ -2120,6 +2121,150 @@ int obtg_keep_in_true_min_jac(obtg_ctx* c, const double* Y, int B, double eps_re
                               int* status, double* jac)
 {
     return keep_in_true_min(c, Y, B, eps_rel, max_nodes, out, t_star, status, true, jac);
+}
+
+// The proximity family (extrema_kernels.hip ProxRows): "come close" and "stay close" rows -- items (a, b, kind) with
+// (rho, tau0, tau1) of the tables obtg_ctx_set_proximity left on the context, b a vehicle or one of the family's own points.  The
+// keep-in entry points' shape -- no time span, nothing takes tf, no jac_tf -- with bound and nodes beside val, t_star and
+// status, so the family has a chain and a host body of its own on HostCall, laid out as true_min_chain and true_min_host are:
+// the fused kernel where the shape has one (with the blocks only if true_min_jac_fused); else the values -- the fused value
+// kernel, or the rows into WS_L_ROWS and their search -- and then the blocks from Y and t_star in a launch of their own.
+// Refusals, all before any launch: no items set or a context that is neither planar nor in space is OBTG_ERR_ARG; a degree above
+// 31 OBTG_ERR_UNSUPPORTED.  The _dev calls take dY itself (dY == NULL inside an obtg_fd_view: OBTG_ERR_ARG).
+int obtg_ctx_set_proximity(obtg_ctx* c, const int* items, const double* params, const double* points, int P, int Q)
+{
+    if (!check_ctx(c) || P < 0 || Q < 0) return OBTG_ERR_ARG;
+    if (P > 0) {
+        if ((c->dim != 2 && c->dim != 3) || !items || !params || (Q > 0 && !points)) return OBTG_ERR_ARG;
+        for (int k = 0; k < P; ++k) {
+            const int a = items[3 * k], b = items[3 * k + 1], kind = items[3 * k + 2];
+            const double rho = params[3 * k], tau0 = params[3 * k + 1], tau1 = params[3 * k + 2];
+            if (a < 0 || a >= c->n_veh || b < 0 || b >= c->n_veh + Q || a == b) return OBTG_ERR_ARG;
+            if (kind != OBTG_PROX_WITHIN && kind != OBTG_PROX_REACH) return OBTG_ERR_ARG;
+            if (!(rho > 0.0) || !std::isfinite(rho)) return OBTG_ERR_ARG;
+            if (!(0.0 <= tau0 && tau0 < tau1 && tau1 <= 1.0)) return OBTG_ERR_ARG;      // (a NaN end is refused too)
+        }
+    }
+    (void)hipSetDevice(c->device);
+    OBTG_HIP(c, hipStreamSynchronize(c->stream));
+    c->prox_P = c->prox_Q = 0;             // (set again once the tables are on the device)
+    if (P == 0) return OBTG_OK;
+    int rc = upload(c, c->d_prox_items, items, sizeof(int) * 3 * (size_t)P);
+    if (!rc) rc = upload(c, c->d_prox_par, params, sizeof(double) * 3 * (size_t)P);
+    if (!rc && Q > 0) rc = upload(c, c->d_prox_pts, points, sizeof(double) * (size_t)Q * c->dim);
+    if (rc) return rc;
+    c->prox_P = P; c->prox_Q = Q;
+    return OBTG_OK;
+}
+
+int obtg_len_proximity(const obtg_ctx* c) { return c ? c->prox_P : 0; }
+
+static int proximity_args(const obtg_ctx* c, const double* out, int B, int max_nodes, double eps_rel)
+{
+    if (!check_ctx(c) || c->prox_P <= 0 || (c->dim != 2 && c->dim != 3) || !out || B < 0 || max_nodes < 1 || !(eps_rel >= 0.0))
+        return OBTG_ERR_ARG;
+    return c->deg > 31 ? OBTG_ERR_UNSUPPORTED : OBTG_OK;
+}
+
+int obtg_proximity_poly_dev(obtg_ctx* c, const double* dY, int B, double* d_out)
+{
+    if (int rc = proximity_args(c, d_out, B, 1, 0.0)) return rc;
+    if (!dY) return OBTG_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    return launch_proximity_rows(c, dY, B, d_out);
+}
+
+int obtg_proximity_poly(obtg_ctx* c, const double* Y, int B, double* out)
+{
+    if (int rc = proximity_args(c, out, B, 1, 0.0)) return rc;
+    if (!Y) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    const size_t n = (size_t)B * c->prox_P * (2 * c->deg + 1);
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    double* d_out = h.out<double>(c->ws_out, n);
+    h.run([&] { return launch_proximity_rows(c, dY, B, d_out); });
+    return h.finish(out, d_out, n);
+}
+
+static int proximity_chain(obtg_ctx* c, const double* dY, int B, double eps_rel, int max_nodes, ProxOut o, double* d_jac)
+{
+    int rc = OBTG_ERR_UNSUPPORTED;
+    if (!d_jac || c->true_min_jac_fused) rc = launch_proximity_true(c, dY, B, eps_rel, max_nodes, o, d_jac);
+    if (rc != OBTG_ERR_UNSUPPORTED) return rc;
+    const size_t n = (size_t)B * c->prox_P;
+    if (d_jac) {
+        if (!o.t) {
+            DevBuf& wt = c->ws_misc[WS_L_TSTAR];
+            if ((rc = wt.reserve(sizeof(double) * n))) return rc;
+            o.t = wt.as<double>();
+        }
+        rc = launch_proximity_true(c, dY, B, eps_rel, max_nodes, o, nullptr);
+    }
+    if (rc == OBTG_ERR_UNSUPPORTED) {
+        DevBuf& ws = c->ws_misc[WS_L_ROWS];
+        if ((rc = ws.reserve(sizeof(double) * n * (2 * c->deg + 1)))) return rc;
+        if ((rc = launch_proximity_rows(c, dY, B, ws.as<double>()))) return rc;
+        rc = launch_proximity_search(c, ws.as<double>(), B, eps_rel, max_nodes, o);
+    }
+    if (rc || !d_jac) return rc;
+    return launch_proximity_envelope(c, dY, B, o.t, d_jac);
+}
+
+// want_jac: the _jac entry points, where the blocks are not optional
+static int proximity_true_dev(obtg_ctx* c, const double* dY, int B, double eps_rel, int max_nodes, const ProxOut& o, bool want_jac,
+                              double* d_jac)
+{
+    if (int rc = proximity_args(c, o.val, B, max_nodes, eps_rel)) return rc;
+    if (!dY || (want_jac && !d_jac)) return OBTG_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    return proximity_chain(c, dY, B, eps_rel, max_nodes, o, d_jac);
+}
+
+// the host body: Y up, val | t_star | bound | jac in ws_out, nodes | status in WS_STATUS
+static int proximity_true_host(obtg_ctx* c, const double* Y, int B, double eps_rel, int max_nodes, const ProxOut& o, bool want_jac,
+                               double* jac)
+{
+    if (int rc = proximity_args(c, o.val, B, max_nodes, eps_rel)) return rc;
+    if (!Y || (want_jac && !jac)) return OBTG_ERR_ARG;
+    if (B == 0) return OBTG_OK;
+    const size_t n = (size_t)B * c->prox_P, nj = jac ? n * c->dim * (c->deg + 1) : 0;
+    HostCall h(c);
+    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
+    double* dv = h.out<double>(c->ws_out, 3 * n + nj);
+    int* di = h.out<int>(c->ws_misc[WS_STATUS], 2 * n);
+    double* dj = jac ? dv + 3 * n : nullptr;
+    h.run([&] { return proximity_chain(c, dY, B, eps_rel, max_nodes, ProxOut{ dv, dv + n, dv + 2 * n, di, di + n }, dj); });
+    h.fetch(o.t, dv + n, n);
+    h.fetch(o.bound, dv + 2 * n, n);
+    h.fetch(o.nodes, di, n);
+    h.fetch(o.status, di + n, n);
+    h.fetch(jac, dj, nj);
+    return h.finish(o.val, dv, n);
+}
+
+int obtg_proximity_true_dev(obtg_ctx* c, const double* dY, int B, double eps_rel, int max_nodes, double* d_val, double* d_t_star,
+                            double* d_bound, int* d_nodes, int* d_status)
+{
+    return proximity_true_dev(c, dY, B, eps_rel, max_nodes, ProxOut{ d_val, d_t_star, d_bound, d_nodes, d_status }, false, nullptr);
+}
+
+int obtg_proximity_true(obtg_ctx* c, const double* Y, int B, double eps_rel, int max_nodes, double* val, double* t_star, double* bound,
+                        int* nodes, int* status)
+{
+    return proximity_true_host(c, Y, B, eps_rel, max_nodes, ProxOut{ val, t_star, bound, nodes, status }, false, nullptr);
+}
+
+int obtg_proximity_true_jac_dev(obtg_ctx* c, const double* dY, int B, double eps_rel, int max_nodes, double* d_val, double* d_t_star,
+                                double* d_bound, int* d_nodes, int* d_status, double* d_jac)
+{
+    return proximity_true_dev(c, dY, B, eps_rel, max_nodes, ProxOut{ d_val, d_t_star, d_bound, d_nodes, d_status }, true, d_jac);
+}
+
+int obtg_proximity_true_jac(obtg_ctx* c, const double* Y, int B, double eps_rel, int max_nodes, double* val, double* t_star,
+                            double* bound, int* nodes, int* status, double* jac)
+{
+    return proximity_true_host(c, Y, B, eps_rel, max_nodes, ProxOut{ val, t_star, bound, nodes, status }, true, jac);
 }
 
 // The keep-out rows (keepout_kernels.hip): items are (vehicle, obstacle) pairs of the tables obtg_ctx_set_keep_out left on the

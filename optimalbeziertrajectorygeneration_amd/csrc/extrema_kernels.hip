@@ -566,6 +566,206 @@ __global__ __launch_bounds__(kWave) void k_ang_rows(const AngExParams q, const i
                 fma(q.sign, ang_row_coeff(sh[0], sh[1], sh[4], sh[5], n, lane, Sk[lane], q.W, side ? -1.0 : 1.0), q.offset);
 }
 
+// ---- the proximity family (obtg_proximity_poly, obtg_proximity_true[_jac]; include/obtg.h states the contract, DESIGN.md 4.28
+// the reasoning): an item (a, b, kind, rho, tau0, tau1) of the context's table is vehicle a against vehicle b or point
+// b - n_veh of the family's own point table, g = (DIM/2)(rho^2 - |c_a - c_b|^2) on the window (bern_device.h proximity_coeffs).
+// kind OBTG_PROX_WITHIN takes the minimum of g, OBTG_PROX_REACH the maximum -- k_bern_extrema's want_max, per ITEM: the
+// coefficients are negated going in, val and bound coming out, and the search's parameter t_w becomes the curve's,
+// fma(t_w, tau1 - tau0, tau0).  That transform cannot ride on true_min_body's one (sign, offset) pair, so the family has a body
+// of its own over ex_first / wave_search / ex_store (prox_body), and true_min_body stays as it is.  The envelope kernel is
+// envelope_body's.
+struct ProxExParams {
+    const double* __restrict__ Y;      // [B][n_veh*DIM][NC]
+    const double* __restrict__ pts;    // [Q][DIM]
+    const int* __restrict__ items;     // [P][3]: a, b, kind
+    const double* __restrict__ par;    // [P][3]: rho, tau0, tau1
+    const double* __restrict__ W2;
+    ExParams ex;                       // outputs [B][P]; c: the workspace rows of k_prox_search
+    double* __restrict__ jac;          // [B][P][DIM][NC] (the envelope forms)
+    double* __restrict__ rows;         // [B][P][2 NC - 1] (the rows kernels)
+    int n_veh, P;
+};
+
+// the item's two curves as proximity_coeffs and envelope_block take them: b's element (c, i) is yb[c * b_cs + i * b_is]
+struct ProxPair {
+    const double* ya;
+    const double* yb;
+    int b_cs, b_is;
+};
+template <int DIM>
+__device__ __forceinline__ ProxPair prox_pair(const ProxExParams& q, const int b, const int it, const int nc)
+{
+    const int ia = q.items[3 * it], ib = q.items[3 * it + 1];
+    const double* Yrow = q.Y + (size_t)b * q.n_veh * (DIM * nc);
+    const bool veh = ib < q.n_veh;
+    return ProxPair{ Yrow + (size_t)ia * (DIM * nc), veh ? Yrow + (size_t)ib * (DIM * nc) : q.pts + (size_t)(ib - q.n_veh) * DIM,
+                     veh ? nc : 1, veh ? 1 : 0 };
+}
+
+template <int NC_, int DIM>
+struct ProxRows {
+    using Params = ProxExParams;
+    static constexpr int NC = NC_, L = 2 * NC_ - 1;
+    static __device__ __forceinline__ void coeffs(const Params& q, long item, double (&cf)[L])
+    {
+        const int b = (int)(item / q.P), it = (int)(item - (long)b * q.P);
+        const ProxPair pr = prox_pair<DIM>(q, b, it, NC);
+        const double* w = q.par + 3 * it;
+        proximity_coeffs<NC, DIM>(pr.ya, pr.yb, pr.b_cs, pr.b_is, w[0], w[1], w[2], as_ctab(q.W2), cf);
+    }
+    // the first object's block of g at the CURVE's parameter t, on the unrestricted control points: envelope_block negated (a
+    // second vehicle's block is the exact negation and is not stored; a point has no variable)
+    static __device__ __forceinline__ void envelope(const Params& q, long item, int nc, double t)
+    {
+        const int b = (int)(item / q.P), it = (int)(item - (long)b * q.P);
+        const ProxPair pr = prox_pair<DIM>(q, b, it, nc);
+        envelope_block<NC, DIM, true>(pr.ya, pr.yb, pr.b_cs, pr.b_is, nc, t, q.jac + (size_t)item * (DIM * nc));
+    }
+};
+
+// the item's answer to memory; returns t_star, the CURVE's parameter of the search's t_w
+__device__ __forceinline__ double prox_store(const ProxExParams& q, long item, ExOut o, bool neg)
+{
+    const double* w = q.par + 3 * (item % q.P);
+    o.t = fma(o.t, w[2] - w[1], w[1]);
+    ex_store(q.ex, item, o, neg);
+    return o.t;
+}
+
+// MODE 0: the values; 1: the values and the blocks; 2: the coefficients to memory, no search (obtg_proximity_poly)
+template <class F, int MODE>
+__device__ __forceinline__ void prox_body(const ProxExParams& q)
+{
+    constexpr int L = F::L;
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    double* stk = lds + (size_t)wave * kExStack * (L + 3);
+    const ExParams& p = q.ex;
+    const long item = ((long)blockIdx.x * kExWaves + wave) * kWave + lane;
+    const bool valid = item < p.M;
+    const long it = valid ? item : p.M - 1;
+    double cf[L];
+    F::coeffs(q, it, cf);
+    if (MODE == 2) {
+        if (valid) {
+#pragma unroll
+            for (int k = 0; k < L; ++k) q.rows[(size_t)item * L + k] = cf[k];
+        }
+        return;
+    }
+    const bool neg = q.items[3 * (it % q.P) + 2] != 0;
+    ExScan sc;
+#pragma unroll
+    for (int k = 0; k < L; ++k) { cf[k] = neg ? -cf[k] : cf[k]; sc.put(cf[k], k); }
+    ExOut mine;
+    double tol;
+    const bool need = !ex_first(sc, p.eps_rel, p.eps_abs, mine, tol) && valid;
+    unsigned long long mask = __ballot(need);
+    while (mask) {
+        const int src = __ffsll((long long)mask) - 1;
+        mask &= mask - 1;
+        double bb = INFINITY;
+#pragma unroll
+        for (int k = 0; k < L; ++k) { const double v = ex_lane(cf[k], src); if (lane == k) bb = v; }
+        const ExOut o = wave_search(bb, L, ex_lane(tol, src), ex_lane(sc.c0, src), ex_lane(sc.cl, src), ex_lane(sc.m, src),
+                                    p.max_nodes, stk);
+        if (lane == src) mine = o;
+    }
+    if (valid) {
+        const double t_star = prox_store(q, item, mine, neg);
+        if (MODE == 1) F::envelope(q, item, F::NC, t_star);
+    }
+}
+
+template <int NC, int DIM, int MODE>
+__global__ __launch_bounds__(kExWaves * kWave) void k_prox_true(const ProxExParams q) { prox_body<ProxRows<NC, DIM>, MODE>(q); }
+template <int DIM>
+__global__ __launch_bounds__(kEnvThreads) void k_prox_envelope(const ProxExParams q, const int nc) { envelope_body<ProxRows<kEnvMaxNC, DIM>>(q, nc); }
+
+// The family's rows for the counts without a kernel of their own, any degree 1 .. 31: one wave per item, lane i holds control
+// point i.  The window's cuts are window_row's levels lane-parallel (a level reads only values of the level before), then the
+// difference and the product in the any-degree separation kernel's arithmetic (bern_kernels.hip k_generic_normsq_elev, R = 0):
+// ah = (x - y) C(n, i), c_k = (DIM/2) sum_q conv_at(ah_q, ah_q, k) / C(2n, k) -- so a full-window item is fma(-1, ., off) of
+// obtg_temporal_sep's R = 0 row on those degrees too.  bn, b2n: the binomial rows C(n, .) and C(2n, .).
+__device__ __forceinline__ double prox_window_lane(double v, const SpanCut& s, const int nc, const int lane)
+{
+    if (s.head) {
+        const double z = s.zh, w = 1.0 - z;
+        for (int lev = 1; lev < nc; ++lev) {
+            const double up = __shfl_down(v, 1);
+            if (lane < nc - lev) v = w * v + z * up;
+        }
+    }
+    if (s.tail) {
+        const double z = s.zt, w = 1.0 - z;
+        for (int lev = 1; lev < nc; ++lev) {
+            const double dn = __shfl_up(v, 1);
+            if (lane >= lev && lane < nc) v = w * dn + z * v;
+        }
+    }
+    return v;
+}
+
+template <int DIM>
+__global__ __launch_bounds__(kWave) void k_prox_rows(const ProxExParams q, const int nc, const double* __restrict__ bn,
+                                                     const double* __restrict__ b2n)
+{
+    __shared__ double ah[DIM][kEnvMaxNC];
+    const long item = blockIdx.x;
+    const int lane = threadIdx.x, n = nc - 1, L = 2 * n + 1;
+    const int b = (int)(item / q.P), it = (int)(item - (long)b * q.P);
+    const ProxPair pr = prox_pair<DIM>(q, b, it, nc);
+    const double* w = q.par + 3 * it;
+    const SpanCut cut(0.0, 1.0, w[1], w[2]);            // (the whole wave: the window belongs to the item)
+    const int i = lane < nc ? lane : 0;
+    for (int d = 0; d < DIM; ++d) {
+        double x = pr.ya[d * nc + i], y = pr.yb[d * pr.b_cs + i * pr.b_is];
+        x = prox_window_lane(x, cut, nc, lane);
+        if (pr.b_is) y = prox_window_lane(y, cut, nc, lane);
+        if (lane < nc) ah[d][lane] = (x - y) * bn[lane];
+    }
+    __syncthreads();
+    if (lane < L) {
+        double s = 0.0;
+        for (int d = 0; d < DIM; ++d) s += conv_at(ah[d], nc, ah[d], nc, lane);
+        const double c = (0.5 * DIM) * s / b2n[lane];
+        q.rows[(size_t)item * L + lane] = fma(-1.0, c, proximity_offset<DIM>(w[0]));
+    }
+}
+
+// k_bern_extrema on the family's workspace rows q.ex.c[M][K], want_max and the window per item
+__global__ __launch_bounds__(kExWaves * kWave) void k_prox_search(const ProxExParams q)
+{
+    extern __shared__ double lds[];
+    const ExParams& p = q.ex;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    double* stk = lds + (size_t)wave * kExStack * (p.K + 3);
+    const long row0 = ((long)blockIdx.x * kExWaves + wave) * kWave;
+    const long row = row0 + lane;
+    const bool valid = row < p.M;
+    const long rr = valid ? row : p.M - 1;
+    const bool neg = q.items[3 * (rr % q.P) + 2] != 0;
+    const double* cr = p.c + rr * p.K;
+    ExScan sc;
+    for (int k = 0; k < p.K; ++k) { const double v = cr[k]; sc.put(neg ? -v : v, k); }
+    ExOut mine;
+    double tol;
+    const bool need = !ex_first(sc, p.eps_rel, p.eps_abs, mine, tol) && valid;
+    unsigned long long mask = __ballot(need);
+    while (mask) {
+        const int src = __ffsll((long long)mask) - 1;
+        mask &= mask - 1;
+        const double* cs = p.c + (row0 + src) * p.K;
+        const bool sneg = __shfl((int)neg, src) != 0;
+        double b = INFINITY;
+        if (lane < p.K) { const double v = cs[lane]; b = sneg ? -v : v; }
+        const ExOut o = wave_search(b, p.K, ex_lane(tol, src), ex_lane(sc.c0, src), ex_lane(sc.cl, src), ex_lane(sc.m, src),
+                                    p.max_nodes, stk);
+        if (lane == src) mine = o;
+    }
+    if (valid) prox_store(q, row, mine, neg);
+}
+
 // =====================================================================================
 //  the curvature rows, planar (dim 2) and in space (dim 3): kappa = mag / den^(3/2) is not a polynomial -- the planar one's
 //  polynomial form has 6n + 1 coefficients, more than a row of lanes from degree 11 on; the norm of the space one's numerator
@@ -1383,6 +1583,104 @@ static int curvature_rows_search(obtg_ctx* c, const RowFamily& f, const double* 
 {
     return launch_curv_search(c, f.kind, d_rows, items, c->deg + 1, f.w, 0, eps_rel, max_nodes, d_out, d_t, nullptr, nullptr, d_status,
                               f.kernel_id);
+}
+
+// ---- the proximity family's launches (the chain that puts them together: capi.cpp proximity_chain)
+static constexpr bool nc_in_prox(int nc) { return false OBTG_NC_PROX_LIST(OBTG_NC_EQ_); }
+bool proximity_fused(const obtg_ctx* c) { return (c->dim == 2 || c->dim == 3) && nc_in_prox(c->deg + 1); }
+
+static ProxExParams prox_params(const obtg_ctx* c, const double* dY, int B)
+{
+    ProxExParams q{};
+    q.Y = dY; q.pts = c->d_prox_pts.as<double>(); q.items = c->d_prox_items.as<int>(); q.par = c->d_prox_par.as<double>();
+    q.n_veh = c->n_veh; q.P = c->prox_P;             // (W2: the fused launches, once ensure_tables has made it)
+    q.ex.M = (long)B * c->prox_P; q.ex.K = 2 * c->deg + 1;
+    return q;
+}
+static void prox_outputs(ProxExParams& q, const ProxOut& o, double eps_rel, int max_nodes)
+{
+    q.ex.val = o.val; q.ex.t = o.t; q.ex.bound = o.bound; q.ex.nodes = o.nodes; q.ex.status = o.status;
+    q.ex.eps_rel = eps_rel; q.ex.eps_abs = 0.0; q.ex.max_nodes = max_nodes;
+}
+static unsigned prox_grid(long M) { const long per_wg = kExWaves * kWave; return (unsigned)((M + per_wg - 1) / per_wg); }
+static size_t prox_lds(int K) { return sizeof(double) * kExWaves * kExStack * (size_t)(K + 3); }
+
+// MODE as prox_body's; null: the count has no kernel of its own
+static void (*prox_kernel(const obtg_ctx* c, int mode))(const ProxExParams)
+{
+    const int nc = c->deg + 1;
+#define OBTG_CASE(NC_, D_) \
+    if (nc == NC_ && c->dim == D_) return mode == 2 ? k_prox_true<NC_, D_, 2> : mode == 1 ? k_prox_true<NC_, D_, 1> : k_prox_true<NC_, D_, 0>;
+#define OBTG_CASE_D(NC_) OBTG_CASE(NC_, 2) OBTG_CASE(NC_, 3)
+    OBTG_NC_PROX_LIST(OBTG_CASE_D)
+#undef OBTG_CASE_D
+#undef OBTG_CASE
+    return nullptr;
+}
+
+int launch_proximity_rows(obtg_ctx* c, const double* dY, int B, double* d_out)
+{
+    if (B <= 0 || c->prox_P <= 0) return OBTG_OK;
+    if ((c->dim != 2 && c->dim != 3) || c->deg + 1 > kEnvMaxNC) return OBTG_ERR_UNSUPPORTED;
+    ProxExParams q = prox_params(c, dY, B);
+    q.rows = d_out;
+    if (auto kern = prox_kernel(c, 2)) {
+        if (int rc = ensure_tables(c)) return rc;
+        q.W2 = c->d_w2.as<double>();
+        ScopedKernelTimer t(c, OBTG_K_TEMPORAL_SEP);
+        hipLaunchKernelGGL(kern, dim3(prox_grid(q.ex.M)), dim3(kExWaves * kWave), 0, c->stream, q);
+        OBTG_HIP(c, hipGetLastError());
+        return OBTG_OK;
+    }
+    for (int v : { c->deg, 2 * c->deg }) { const int o = binrow_offset(c, v); if (o < 0) return o; }
+    const double* bin = c->d_binrows.as<double>();
+    ScopedKernelTimer t(c, OBTG_K_TEMPORAL_SEP);
+    hipLaunchKernelGGL(c->dim == 2 ? k_prox_rows<2> : k_prox_rows<3>, dim3((unsigned)q.ex.M), dim3(kWave), 0, c->stream, q, c->deg + 1,
+                       bin + binrow_offset(c, c->deg), bin + binrow_offset(c, 2 * c->deg));
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
+int launch_proximity_true(obtg_ctx* c, const double* dY, int B, double eps_rel, int max_nodes, const ProxOut& o, double* d_jac)
+{
+    if (B <= 0 || c->prox_P <= 0) return OBTG_OK;
+    auto kern = proximity_fused(c) ? prox_kernel(c, d_jac ? 1 : 0) : nullptr;
+    if (!kern) return OBTG_ERR_UNSUPPORTED;
+    ProxExParams q = prox_params(c, dY, B);
+    prox_outputs(q, o, eps_rel, max_nodes);
+    q.jac = d_jac;
+    if (int rc = ensure_tables(c)) return rc;
+    q.W2 = c->d_w2.as<double>();
+    ScopedKernelTimer t(c, OBTG_K_TEMPORAL_SEP);
+    hipLaunchKernelGGL(kern, dim3(prox_grid(q.ex.M)), dim3(kExWaves * kWave), prox_lds(q.ex.K), c->stream, q);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
+int launch_proximity_search(obtg_ctx* c, const double* d_rows, int B, double eps_rel, int max_nodes, const ProxOut& o)
+{
+    if (B <= 0 || c->prox_P <= 0) return OBTG_OK;
+    if (!bern_extrema_supported(2 * c->deg + 1)) return OBTG_ERR_UNSUPPORTED;
+    ProxExParams q = prox_params(c, nullptr, B);
+    prox_outputs(q, o, eps_rel, max_nodes);
+    q.ex.c = d_rows;
+    ScopedKernelTimer t(c, OBTG_K_TEMPORAL_SEP);
+    hipLaunchKernelGGL(k_prox_search, dim3(prox_grid(q.ex.M)), dim3(kExWaves * kWave), prox_lds(q.ex.K), c->stream, q);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
+}
+
+int launch_proximity_envelope(obtg_ctx* c, const double* dY, int B, const double* d_t, double* d_jac)
+{
+    if (B <= 0 || c->prox_P <= 0) return OBTG_OK;
+    if ((c->dim != 2 && c->dim != 3) || c->deg + 1 > kEnvMaxNC) return OBTG_ERR_UNSUPPORTED;
+    ProxExParams q = prox_params(c, dY, B);
+    q.ex.t = const_cast<double*>(d_t); q.jac = d_jac;
+    ScopedKernelTimer t(c, OBTG_K_TEMPORAL_SEP);
+    hipLaunchKernelGGL(c->dim == 2 ? k_prox_envelope<2> : k_prox_envelope<3>, dim3((unsigned)((q.ex.M + kEnvThreads - 1) / kEnvThreads)),
+                       dim3(kEnvThreads), 0, c->stream, q, c->deg + 1);
+    OBTG_HIP(c, hipGetLastError());
+    return OBTG_OK;
 }
 
 RowFamily curvature_row_family(const obtg_ctx* c, RowKind kind, double max_curv)

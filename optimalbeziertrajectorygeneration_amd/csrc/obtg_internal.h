@@ -36,6 +36,9 @@ namespace obtg {
 //   OBTG_NC_SCURV_LIST: the space-curvature rows' in-register kernels (k_scurv_true_min; 3-D), the counts that build without
 //                      scratch with four registers per coefficient (21 does not); the others take the workspace route
 #define OBTG_NC_SCURV_LIST(X) OBTG_NC_DYN(X)
+//   OBTG_NC_PROX_LIST : the proximity rows' fused kernels (k_prox_true: values, values and blocks, the rows; 2-D and 3-D), the
+//                      counts of OBTG_NC_SEP that build without scratch; the others take the workspace route
+#define OBTG_NC_PROX_LIST(X) OBTG_NC_DYN(X) X(21)
 static inline bool nc_in_sep(int nc)  { return false OBTG_NC_SEP(OBTG_NC_EQ_); }
 static inline bool nc_in_dyn(int nc)  { return false OBTG_NC_DYN(OBTG_NC_EQ_); }
 static inline bool nc_in_elev(int nc) { return false OBTG_NC_ELEV(OBTG_NC_EQ_); }
@@ -101,6 +104,7 @@ struct KernelStat {
 //   obtg_bern_arc_length     holds 3 (WS_INFO) -> launch_arc_length takes none
 //   obtg_arc_length_obj      holds 4 (WS_STATUS) -> launch_arc_length_obj takes 7 (WS_L_ROWS: the vehicles' lengths and status)
 //   obtg_curvature_true_min[_jac] are true_min_host / true_min_chain calls like the first line's (the workspace rows are num and den)
+//   obtg_proximity_true[_jac] hold 4 (WS_STATUS: nodes | status, proximity_true_host) -> proximity_chain takes 6 and 7 as true_min_chain does
 //   obtg_bern_curvature      holds 4 (WS_STATUS) -> bern_curvature_chain takes 7 (WS_L_ROWS: the curves' num and den rows)
 enum WsSlot {
     WS_POLY_OFF = 0,      // int[n_poly + 1]: polygon offsets
@@ -195,6 +199,12 @@ struct obtg_ctx {
     obtg::DevBuf d_pk_feat;   // double[pk_NF][7]
     std::vector<double> h_pk_H;
     int pk_F = 0, pk_NF = 0, pk_eu_state = 0;
+    // obtg_ctx_set_proximity: the items (a, b, kind) and (rho, tau0, tau1) of the proximity rows and the family's own points;
+    // prox_P == 0: none set
+    obtg::DevBuf d_prox_items;   // int[prox_P][3]
+    obtg::DevBuf d_prox_par;     // double[prox_P][3]
+    obtg::DevBuf d_prox_pts;     // double[prox_Q][dim]
+    int prox_P = 0, prox_Q = 0;
     std::vector<int> h_pairs; // host copy of the pair table (2 ints per pair)
     std::vector<int> h_tiles; // row-window tiles of the current (pair_begin, pair_count)
     obtg::DevBuf d_tiles;
@@ -525,6 +535,19 @@ int launch_true_min(obtg_ctx* c, const RowFamily& f, const double* dY, int B, do
 // d_val: the rows' values of the value launch (ROWS_CURV reads them: a row that is its bound has a zero block)
 int launch_true_min_envelope(obtg_ctx* c, const RowFamily& f, const double* dY, int B, const double* d_t, double* d_jac,
                              double* d_jac_tf, const double* d_val = nullptr);
+
+// The proximity family (obtg_ctx_set_proximity's items; dim 2 or 3): its outputs [B][P], all but val nullable
+struct ProxOut { double* val; double* t; double* bound; int* nodes; int* status; };
+bool proximity_fused(const obtg_ctx* c);       // the shape has kernels that form the coefficients in registers (OBTG_NC_PROX_LIST)
+// obtg_proximity_poly: g's coefficients out[B][P][2 deg + 1], degree up to 31 -- the fused kernels' own on their counts, the
+// any-degree separation arithmetic on the others
+int launch_proximity_rows(obtg_ctx* c, const double* dY, int B, double* d_out);
+// one launch on the fused counts (d_jac: with the blocks [B][P][dim][deg+1]); OBTG_ERR_UNSUPPORTED: go through the rows
+int launch_proximity_true(obtg_ctx* c, const double* dY, int B, double eps_rel, int max_nodes, const ProxOut& o, double* d_jac);
+// the search of launch_proximity_rows' rows: obtg_bern_extrema with want_max and the window per item
+int launch_proximity_search(obtg_ctx* c, const double* d_rows, int B, double eps_rel, int max_nodes, const ProxOut& o);
+// the blocks alone from Y and the t_star of a value launch
+int launch_proximity_envelope(obtg_ctx* c, const double* dY, int B, const double* d_t, double* d_jac);
 
 // ---------------------------------------------------------------- launchers (arclen_kernels.hip): true arc length
 bool arc_length_supported(int dim, int K);             // 1 <= dim <= 3, 2 <= K <= 32

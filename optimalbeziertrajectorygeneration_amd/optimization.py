@@ -333,6 +333,71 @@ def _separation_region_table(region, dim):
     return np.ascontiguousarray(np.hstack((A, b[:, None])))
 
 
+# The proximity family, beside the table like _SEP_REGION: its operand is the pair of lists `waypoints` and
+# `stayWithin` kept on the object.  True rows only: one row per entry, the waypoints in list order (the MAXIMUM over the entry's
+# window of (d/2)(radius^2 - |c_v - target|^2): >= 0 iff the vehicle comes within the radius at some time of the window), then the
+# stayWithin entries (the MINIMUM: >= 0 iff it never leaves range).  What the device calls take in the bound's place is the
+# triple of tables _proximity_tables makes of the lists.  A row with a vehicle target belongs to both vehicles: the envelope
+# provider scatters its block with +1 and -1 (proximityJacobian).
+_PROXIMITY = _RowFamily('proximity', 'waypoints/stayWithin', True, None, None, 'proximity_true', 'proximity_true_jac', None, (),
+                        False, 1, 'proximityConstraints', 'proximityJacobian', 'proximity', False)
+_FAMILY[_PROXIMITY.key] = _PROXIMITY
+
+
+def _proximity_tables(waypoints, stayWithin, numVeh, dim):
+    """(items[P][3], params[P][3], points[Q][dim]) of the `waypoints` and `stayWithin` arguments, checked: each a list (or None)
+    of entries (vehicle, target, radius) or (vehicle, target, radius, (tau0, tau1)) -- target an int (another vehicle) or a point
+    of the problem's dimension, radius finite and > 0, 0 <= tau0 < tau1 <= 1 the window of the normalised parameter (default the
+    whole trajectory).  Rows: the waypoints in list order, then the stayWithin entries (obtg_ctx_set_proximity)."""
+    if dim not in (2, 3):
+        raise ValueError("waypoints and stayWithin need dimension 2 or 3, not {}".format(dim))
+    items, params, points = [], [], []
+    for name, entries, kind in (('waypoints', waypoints, _capi.PROX_REACH), ('stayWithin', stayWithin, _capi.PROX_WITHIN)):
+        if entries is None:
+            continue
+        if not isinstance(entries, (list, tuple)) or len(entries) < 1:
+            raise ValueError("{} must be a list of entries (vehicle, target, radius[, (tau0, tau1)])".format(name))
+        for e, entry in enumerate(entries):
+            who = "{}[{}]".format(name, e)
+            if not isinstance(entry, (list, tuple)) or len(entry) not in (3, 4):
+                raise ValueError("{} must be (vehicle, target, radius) or (vehicle, target, radius, (tau0, tau1))".format(who))
+            veh, target, radius = entry[:3]
+            if not isinstance(veh, (int, np.integer)) or not 0 <= veh < numVeh:
+                raise ValueError("{} needs a vehicle index in 0 .. {}, not {!r}".format(who, numVeh - 1, veh))
+            if isinstance(target, (int, np.integer)):
+                if not 0 <= target < numVeh or target == veh:
+                    raise ValueError("{} needs another vehicle's index in 0 .. {} as its target, not {!r}".format(who, numVeh - 1, target))
+                b = int(target)
+            else:
+                try:
+                    pt = np.asarray(target, dtype=float).reshape(-1)
+                except (TypeError, ValueError):
+                    pt = np.zeros(0)
+                if pt.shape != (dim,) or not np.all(np.isfinite(pt)):
+                    raise ValueError("{} needs a target that is a vehicle index or a finite point of dimension {}, not {!r}"
+                                     .format(who, dim, target))
+                b = numVeh + len(points)
+                points.append(pt)
+            try:
+                rho = float(radius)
+            except (TypeError, ValueError):
+                rho = float('nan')
+            if not (np.isfinite(rho) and rho > 0.0):
+                raise ValueError("{} needs a finite radius > 0, not {!r}".format(who, radius))
+            try:
+                tau0, tau1 = (float(v) for v in (entry[3] if len(entry) == 4 else (0.0, 1.0)))
+            except (TypeError, ValueError):
+                tau0 = tau1 = float('nan')
+            if not 0.0 <= tau0 < tau1 <= 1.0:
+                raise ValueError("{} needs a window (tau0, tau1) with 0 <= tau0 < tau1 <= 1, not {!r}".format(who, entry[3]))
+            items.append((int(veh), b, kind))
+            params.append((rho, tau0, tau1))
+    if not items:
+        raise ValueError("waypoints and stayWithin are both None: there are no proximity rows")
+    return (np.ascontiguousarray(items, dtype=np.int32).reshape(-1, 3), np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 3),
+            np.ascontiguousarray(points, dtype=np.float64).reshape(-1, dim))
+
+
 def _keep_out_motion_tables(keepOutMotion, keepOut, dim, deg, tf=None):
     """(Q, q_off[O+1], T[O]) of a `keepOutMotion` argument, checked: a LIST with one entry per obstacle of `keepOut` -- None (the
     obstacle stands still), a bezier.Bezier of the problem's dimension with t0 == 0 (the obstacle's offset on [0, tf]), or a pair
@@ -528,7 +593,9 @@ class BezOptimization(object):
                  keepOutMetric='faces',
                  separationRegion=None,
                  separationRegionMargin=0.0,
-                 separationRegionMetric='faces'):
+                 separationRegionMetric='faces',
+                 waypoints=None,
+                 stayWithin=None):
         """Beyond the reference's keywords: `device` (HIP ordinal; None: this process's, see _capi.default_device) and `separationRows` --
         'all': temporalSeparationConstraints returns every elevated control point of every pair, as the
         reference does (optimization.py:337); 'min': one row per pair, the smallest of them -- the
@@ -617,6 +684,15 @@ class BezOptimization(object):
         self.separationRegion = separationRegion
         self.separationRegionMargin = float(separationRegionMargin)
         self.separationRegionMetric = separationRegionMetric
+        # waypoints, stayWithin (None: none; dim 2 or 3): "come close" and "stay close" -- lists of (vehicle, target, radius) or
+        # (vehicle, target, radius, (tau0, tau1)), target another vehicle's index or a point, (tau0, tau1) the window of the
+        # normalised parameter in which the row is taken (ordered gates: (0, 0.5), then (0.5, 1)).  proximityConstraints: one
+        # true row per entry, the waypoints first (obtg_proximity_true).  A window in tau does not depend on tf.  Kept as
+        # `self.waypoints` and `self.stayWithin`, read when a closure is called, like keepOut.
+        if waypoints is not None or stayWithin is not None:
+            _proximity_tables(waypoints, stayWithin, numVeh, dimension)      # raises for entries the device calls could not take
+        self.waypoints = waypoints
+        self.stayWithin = stayWithin
         if separationRows not in ('all', 'min', 'active', 'true_min'):
             raise ValueError("separationRows must be 'all', 'min', 'active' or 'true_min', not {!r}".format(separationRows))
         if separationRows == 'active' and not 1 <= int(activeRows) <= 4:
@@ -722,6 +798,10 @@ class BezOptimization(object):
             return None if self.keepOut is None else _keep_out_tables(self.keepOut, self.model['numVeh'], self.model['dim'])
         if fam is _SEP_REGION:
             return None if self.separationRegion is None else _separation_region_table(self.separationRegion, self.model['dim'])
+        if fam is _PROXIMITY:
+            if self.waypoints is None and self.stayWithin is None:
+                return None
+            return _proximity_tables(self.waypoints, self.stayWithin, self.model['numVeh'], self.model['dim'])
         if fam is not _KEEP_IN:
             return self.model[fam.bound]
         return None if self.keepIn is None else _keep_in_tables(self.keepIn, self.model['numVeh'], self.model['dim'])
@@ -1054,6 +1134,14 @@ class BezOptimization(object):
         constraint sweep, of distributed.py or of sequential.py."""
         return self._vehicle_closure(_SEP_REGION)
 
+    @property
+    def proximityConstraints(self):
+        """One true row per entry of `waypoints` (list order), then of `stayWithin`: the maximum (waypoints) or the minimum
+        (stayWithin) over the entry's window of (d/2)(radius^2 - |c_v - target|^2), >= 0 iff the vehicle comes within the Euclidean
+        radius at some time of the window / never leaves it (obtg_proximity_true) -- the same whatever tf is.  Not part of the
+        one-launch structured step, of the constraint sweep, of distributed.py or of sequential.py."""
+        return self._vehicle_closure(_PROXIMITY)
+
     def spatialSeparationConstraints(self, x, robust=False):
         """All-pairs minDist over vehicles AND shape obstacles (optimization.py:109-133);
         returns shape (P, 3): (dist, t1, t2) - maxSep, as the reference does.
@@ -1224,6 +1312,8 @@ class BezOptimization(object):
         if self.separationRegion is not None:       # one trailing entry, only while a region is set: its bytes, margin and metric
             tail.append(('separationRegion', self._operand(_SEP_REGION).tobytes(), self.separationRegionMargin,
                          self.separationRegionMetric))
+        if self.waypoints is not None or self.stayWithin is not None:      # one trailing entry, only while a list is set
+            tail.append(('proximity', b''.join(t.tobytes() for t in self._operand(_PROXIMITY))))
         return (int(DEG_ELEV), self.separationRows, *rows, self.activeRows, self._rv_cache[0], self.model['maxSep'], *bounds,
                 None if self._timeopt() else self.model['tf'],
                 None if self.pointObstacles is None else np.asarray(self.pointObstacles, dtype=float).tobytes(),
@@ -1485,6 +1575,32 @@ class BezOptimization(object):
         if self.separationRegionMetric != 'faces':
             return {k: r[k][0] for k in ('val', 't_star', 'faces', 'dir', 'status')}
         return {k: r[k][0] for k in ('val', 't_star', 'face', 'lam', 'status')}
+
+    def proximityJacobian(self, x, structured=True, method='fd'):
+        """d(proximityConstraints)/dx, dense [P][n_x]: method='fd' differences the closure's rows (one batched call; `structured`
+        changes nothing); method='envelope' is the derivative of each row's polynomial at the parameter its search returns
+        (obtg_proximity_true_jac, one call at x): the block of the entry's vehicle, scattered with +1 to its columns and, when
+        the target is a vehicle, with -1 to that vehicle's (a point has no variable); method='exact' is not built.  The rows
+        have no explicit dependence on tf: that part of a time-optimal problem's tf column is an exact 0 (with prescribed speeds
+        the column still carries dY/dtf)."""
+        fam = _PROXIMITY
+        tables = self._bound(fam, fam.jacobian)          # missing lists answer before anything is computed
+        self._check_jac_method(fam, method)
+        if method != 'envelope':
+            return self._jac(x, fam.key)
+        x = np.asarray(x, dtype=float)
+        r = self._vehicle_true_min(fam, self._ctx(False), self.reshapeVectors(x[None]), None, tables, fam.jacobian + '(envelope)',
+                                   envelope=True)
+        items = tables[0].astype(np.int64)
+        return self._scatter_exact(r['jac'][0][:, None], (items[:, 0], items[:, 1]), (1.0, -1.0))      # blocks of one row each
+
+    def trueProximityMargins(self, x):
+        """(val[P], t_star[P]): per entry of `waypoints`, then of `stayWithin`, in the order of proximityConstraints, the row --
+        (d/2)(radius^2 - distance^2) at the closest approach (waypoints) or at the farthest point (stayWithin) of its window -- and
+        the parameter in [0, 1] where it is attained (obtg_proximity_true): every entry holds iff every val is >= 0."""
+        tables = self._bound(_PROXIMITY, 'trueProximityMargins')
+        r = self._true_rows_at(_PROXIMITY, np.asarray(x, dtype=float), tables, 'trueProximityMargins')
+        return r['val'][0], r['t_star'][0]
 
     # ------------------------------------------------------------------ exact Jacobians (method='exact')
     # The device returns d rows / d Y per pair or vehicle ([..][rows][dim][deg+1] blocks, include/obtg.h obtg_*_jac); the chain

@@ -963,113 +963,125 @@ class Context(object):
     def len_keep_out(self):
         return self._lib.obtg_len_keep_out(self._h)
 
-    def _keep_out_call(self, name, Y, obstacles, margin, eps_rel, max_nodes, jac):
-        P = self._keep_out(obstacles)
+    def _keep_out_call(self, name, P, Y, margin, eps_rel, max_nodes, jac, tf=None, euclid=False, rel=False):
+        """The one host caller of the keep-out family: P items per row; tf: the moving forms' spans (they return jac_tf beside
+        jac); euclid: faces[.][3] and dir[.][dim] in the place of face[.][2] and lam; rel: the forms that return the relative
+        control points.  The dict's order is the order of the library's arguments."""
         Y, B = self._rows(Y)
-        r = dict(val=pinned_empty((B, P)), t_star=np.empty((B, P)), face=np.zeros((B, P, 2), np.int32), lam=np.empty((B, P)),
-                 bound=np.empty((B, P)), nodes=np.zeros((B, P), np.int32), status=np.zeros((B, P), np.int32))
+        lead = (_ptr(Y),)
+        if tf is not None:
+            tf = np.ascontiguousarray(np.broadcast_to(_f64(tf).reshape(-1), (B,)))
+            lead += (_ptr(tf),)
+        block = (B, P, self.dim, self.deg + 1)
+        r = dict(val=pinned_empty((B, P)), t_star=np.empty((B, P)))
+        if euclid:
+            r.update(faces=np.zeros((B, P, 3), np.int32), dir=np.empty((B, P, self.dim)))
+        else:
+            r.update(face=np.zeros((B, P, 2), np.int32), lam=np.empty((B, P)))
+        r.update(bound=np.empty((B, P)), nodes=np.zeros((B, P), np.int32), status=np.zeros((B, P), np.int32))
+        if rel:
+            r["rel"] = np.empty(block)
         if jac:
-            r["jac"] = pinned_empty((B, P, self.dim, self.deg + 1))
-        self._check(getattr(self._lib, name)(self._h, _ptr(Y), B, float(margin), float(eps_rel), int(max_nodes),
+            r["jac"] = pinned_empty(block)
+            if tf is not None:
+                r["jac_tf"] = np.empty((B, P))
+        self._check(getattr(self._lib, name)(self._h, *lead, B, float(margin), float(eps_rel), int(max_nodes),
                                              *[_ptr(a) for a in r.values()]), name)
         return r
+
+    def _keep_out_call_dev(self, name, lead, B, margin, eps_rel, max_nodes, outs):
+        self._check(getattr(self._lib, name)(self._h, *[_vp(q) for q in lead], int(B), float(margin), float(eps_rel), int(max_nodes),
+                                             *[_vp(q) for q in outs]), name)
+
+    def _bern_keep_out(self, name, c, H, eps_rel, max_nodes, moving=False, Q=None, r=None):
+        """The one caller of the free-curve forms; moving: Q is the obstacle's offset curve, r[M] or None the curves' ratios."""
+        c = _f64(c)
+        if c.ndim == 2:
+            c = c[None]
+        M, dim, K = c.shape
+        H = _f64(H).reshape(-1, dim + 1)
+        motion = ()
+        if moving:
+            Q = _f64(Q).reshape(dim, -1)
+            if r is not None:
+                r = np.ascontiguousarray(np.broadcast_to(_f64(r).reshape(-1), (M,)))
+            motion = (_ptr(Q), Q.shape[1], None if r is None else _ptr(r))
+        out = dict(val=np.empty(M), t_star=np.empty(M), status=np.zeros(M, np.int32))
+        self._check(getattr(self._lib, name)(self._h, _ptr(c), M, dim, K, _ptr(H), H.shape[0], *motion, float(eps_rel), int(max_nodes),
+                                             *[_ptr(a) for a in out.values()]), name)
+        return out
+
+    def _bern_keep_out_dev(self, name, d_c, M, dim, K, H, eps_rel, max_nodes, d_val, d_t_star, d_status, moving=False, Q=None, d_r=None):
+        H = _f64(H).reshape(-1, int(dim) + 1)
+        motion = ()
+        if moving:
+            Q = _f64(Q).reshape(int(dim), -1)
+            motion = (_ptr(Q), Q.shape[1], _vp(d_r))
+        self._check(getattr(self._lib, name)(self._h, _vp(d_c), int(M), int(dim), int(K), _ptr(H), H.shape[0], *motion, float(eps_rel),
+                                             int(max_nodes), _vp(d_val), _vp(d_t_star), _vp(d_status)), name)
 
     def keep_out_true_min(self, Y, obstacles=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
         """Per (vehicle, obstacle) item the clearance row: the minimum over t in [0, 1] of the largest a_f . c_v(t) - b_f over
         the obstacle's faces, minus margin (obtg_keep_out_true_min): dict(val[B][P], t_star[B][P], face[B][P][2] -- the
         active faces as indices into H, the second -1 without one --, lam[B][P] -- the first face's weight --, bound[B][P] --
         the certified lower bound --, nodes[B][P], status[B][P])."""
-        return self._keep_out_call("obtg_keep_out_true_min", Y, obstacles, margin, eps_rel, max_nodes, False)
+        return self._keep_out_call("obtg_keep_out_true_min", self._keep_out(obstacles), Y, margin, eps_rel, max_nodes, False)
 
     def keep_out_true_min_jac(self, Y, obstacles=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
         """keep_out_true_min with its envelope Jacobian (obtg_keep_out_true_min_jac): the same dict, bit for bit, and
         jac[B][P][dim][deg+1] = (lam a_f1[c] + (1 - lam) a_f2[c]) B_i(t_star): d/d(the item's own vehicle's control points)."""
-        return self._keep_out_call("obtg_keep_out_true_min_jac", Y, obstacles, margin, eps_rel, max_nodes, True)
+        return self._keep_out_call("obtg_keep_out_true_min_jac", self._keep_out(obstacles), Y, margin, eps_rel, max_nodes, True)
 
     def keep_out_true_min_dev(self, dY, B, d_out, d_t_star=None, d_face=None, d_lam=None, d_bound=None, d_nodes=None, d_status=None,
                               margin=0.0, eps_rel=1e-9, max_nodes=100000):
-        self._check(self._lib.obtg_keep_out_true_min_dev(self._h, _vp(dY), int(B), float(margin), float(eps_rel), int(max_nodes),
-                                                         *[_vp(q) for q in (d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status)]),
-                    "obtg_keep_out_true_min_dev")
+        self._keep_out_call_dev("obtg_keep_out_true_min_dev", (dY,), B, margin, eps_rel, max_nodes,
+                                (d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status))
 
     def keep_out_true_min_jac_dev(self, dY, B, d_out, d_jac, d_t_star=None, d_face=None, d_lam=None, d_bound=None, d_nodes=None,
                                   d_status=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
-        self._check(self._lib.obtg_keep_out_true_min_jac_dev(self._h, _vp(dY), int(B), float(margin), float(eps_rel), int(max_nodes),
-                                                             *[_vp(q) for q in (d_out, d_t_star, d_face, d_lam, d_bound, d_nodes,
-                                                                                d_status, d_jac)]), "obtg_keep_out_true_min_jac_dev")
+        self._keep_out_call_dev("obtg_keep_out_true_min_jac_dev", (dY,), B, margin, eps_rel, max_nodes,
+                                (d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_jac))
 
     def bern_keep_out(self, c, H, eps_rel=1e-9, max_nodes=100000):
         """The clearance of free curves c[M][dim][K] (dim 2 or 3, 2 <= K <= 32, whatever the context's shape is) from ONE
         convex obstacle, the faces H[F][dim+1] (obtg_bern_keep_out): dict(val[M], t_star[M], status[M])."""
-        c = _f64(c)
-        if c.ndim == 2:
-            c = c[None]
-        M, dim, K = c.shape
-        H = _f64(H).reshape(-1, dim + 1)
-        r = dict(val=np.empty(M), t_star=np.empty(M), status=np.zeros(M, np.int32))
-        self._check(self._lib.obtg_bern_keep_out(self._h, _ptr(c), M, dim, K, _ptr(H), H.shape[0], float(eps_rel), int(max_nodes),
-                                                 *[_ptr(a) for a in r.values()]), "obtg_bern_keep_out")
-        return r
+        return self._bern_keep_out("obtg_bern_keep_out", c, H, eps_rel, max_nodes)
 
     def bern_keep_out_dev(self, d_c, M, dim, K, H, d_val, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
-        H = _f64(H).reshape(-1, int(dim) + 1)
-        self._check(self._lib.obtg_bern_keep_out_dev(self._h, _vp(d_c), int(M), int(dim), int(K), _ptr(H), H.shape[0], float(eps_rel),
-                                                     int(max_nodes), _vp(d_val), _vp(d_t_star), _vp(d_status)), "obtg_bern_keep_out_dev")
+        self._bern_keep_out_dev("obtg_bern_keep_out_dev", d_c, M, dim, K, H, eps_rel, max_nodes, d_val, d_t_star, d_status)
 
     # -- the Euclidean metric (include/obtg.h "Euclidean keep-out clearance"): the same tables, the signed Euclidean distance
-    def _keep_out_euclid_call(self, name, Y, obstacles, margin, eps_rel, max_nodes, jac):
-        P = self._keep_out(obstacles)
-        Y, B = self._rows(Y)
-        r = dict(val=pinned_empty((B, P)), t_star=np.empty((B, P)), faces=np.zeros((B, P, 3), np.int32), dir=np.empty((B, P, self.dim)),
-                 bound=np.empty((B, P)), nodes=np.zeros((B, P), np.int32), status=np.zeros((B, P), np.int32))
-        if jac:
-            r["jac"] = pinned_empty((B, P, self.dim, self.deg + 1))
-        self._check(getattr(self._lib, name)(self._h, _ptr(Y), B, float(margin), float(eps_rel), int(max_nodes),
-                                             *[_ptr(a) for a in r.values()]), name)
-        return r
-
     def keep_out_euclid_true_min(self, Y, obstacles=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
         """Per (vehicle, obstacle) item the Euclidean clearance row: the minimum over t in [0, 1] of the signed Euclidean
         distance from c_v(t) to the obstacle, minus margin (obtg_keep_out_euclid_true_min): dict(val[B][P], t_star[B][P],
         faces[B][P][3] -- the active set as indices into H, -1 padded --, dir[B][P][dim] -- the unit direction at t_star --,
         bound[B][P], nodes[B][P], status[B][P])."""
-        return self._keep_out_euclid_call("obtg_keep_out_euclid_true_min", Y, obstacles, margin, eps_rel, max_nodes, False)
+        return self._keep_out_call("obtg_keep_out_euclid_true_min", self._keep_out(obstacles),
+                                   Y, margin, eps_rel, max_nodes, False, euclid=True)
 
     def keep_out_euclid_true_min_jac(self, Y, obstacles=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
         """keep_out_euclid_true_min with its envelope Jacobian (obtg_keep_out_euclid_true_min_jac): the same dict, bit for bit,
         and jac[B][P][dim][deg+1] = dir[c] B_i(t_star): d/d(the item's own vehicle's control points)."""
-        return self._keep_out_euclid_call("obtg_keep_out_euclid_true_min_jac", Y, obstacles, margin, eps_rel, max_nodes, True)
+        return self._keep_out_call("obtg_keep_out_euclid_true_min_jac", self._keep_out(obstacles),
+                                   Y, margin, eps_rel, max_nodes, True, euclid=True)
 
     def keep_out_euclid_true_min_dev(self, dY, B, d_out, d_t_star=None, d_faces=None, d_dir=None, d_bound=None, d_nodes=None,
                                      d_status=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
-        self._check(self._lib.obtg_keep_out_euclid_true_min_dev(
-            self._h, _vp(dY), int(B), float(margin), float(eps_rel), int(max_nodes),
-            *[_vp(q) for q in (d_out, d_t_star, d_faces, d_dir, d_bound, d_nodes, d_status)]), "obtg_keep_out_euclid_true_min_dev")
+        self._keep_out_call_dev("obtg_keep_out_euclid_true_min_dev", (dY,), B, margin, eps_rel, max_nodes,
+                                (d_out, d_t_star, d_faces, d_dir, d_bound, d_nodes, d_status))
 
     def keep_out_euclid_true_min_jac_dev(self, dY, B, d_out, d_jac, d_t_star=None, d_faces=None, d_dir=None, d_bound=None, d_nodes=None,
                                          d_status=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
-        self._check(self._lib.obtg_keep_out_euclid_true_min_jac_dev(
-            self._h, _vp(dY), int(B), float(margin), float(eps_rel), int(max_nodes),
-            *[_vp(q) for q in (d_out, d_t_star, d_faces, d_dir, d_bound, d_nodes, d_status, d_jac)]), "obtg_keep_out_euclid_true_min_jac_dev")
+        self._keep_out_call_dev("obtg_keep_out_euclid_true_min_jac_dev", (dY,), B, margin, eps_rel, max_nodes,
+                                (d_out, d_t_star, d_faces, d_dir, d_bound, d_nodes, d_status, d_jac))
 
     def bern_keep_out_euclid(self, c, H, eps_rel=1e-9, max_nodes=100000):
         """The Euclidean clearance of free curves c[M][dim][K] from ONE convex obstacle, the raw faces H[F][dim+1]
         (obtg_bern_keep_out_euclid): dict(val[M], t_star[M], status[M])."""
-        c = _f64(c)
-        if c.ndim == 2:
-            c = c[None]
-        M, dim, K = c.shape
-        H = _f64(H).reshape(-1, dim + 1)
-        r = dict(val=np.empty(M), t_star=np.empty(M), status=np.zeros(M, np.int32))
-        self._check(self._lib.obtg_bern_keep_out_euclid(self._h, _ptr(c), M, dim, K, _ptr(H), H.shape[0], float(eps_rel), int(max_nodes),
-                                                        *[_ptr(a) for a in r.values()]), "obtg_bern_keep_out_euclid")
-        return r
+        return self._bern_keep_out("obtg_bern_keep_out_euclid", c, H, eps_rel, max_nodes)
 
     def bern_keep_out_euclid_dev(self, d_c, M, dim, K, H, d_val, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
-        H = _f64(H).reshape(-1, int(dim) + 1)
-        self._check(self._lib.obtg_bern_keep_out_euclid_dev(self._h, _vp(d_c), int(M), int(dim), int(K), _ptr(H), H.shape[0],
-                                                            float(eps_rel), int(max_nodes), _vp(d_val), _vp(d_t_star), _vp(d_status)),
-                    "obtg_bern_keep_out_euclid_dev")
+        self._bern_keep_out_dev("obtg_bern_keep_out_euclid_dev", d_c, M, dim, K, H, eps_rel, max_nodes, d_val, d_t_star, d_status)
 
     # -- moving keep-out obstacles (include/obtg.h "moving keep-out obstacles"): motion = (Q, q_off[O+1], T[O]) -- Q the
     # obstacles' [dim][m_o+1] control-point blocks one after the other, flat; q_off in control points, an empty run for an
@@ -1089,68 +1101,38 @@ class Context(object):
                 self.set_keep_out_motion(Q, q_off, T)
         return P
 
-    def _keep_out_moving_call(self, name, Y, tf, obstacles, motion, margin, eps_rel, max_nodes, jac):
-        P = self._keep_out_motion(obstacles, motion)
-        Y, B = self._rows(Y)
-        tf = np.ascontiguousarray(np.broadcast_to(_f64(tf).reshape(-1), (B,)))
-        r = dict(val=pinned_empty((B, P)), t_star=np.empty((B, P)), face=np.zeros((B, P, 2), np.int32), lam=np.empty((B, P)),
-                 bound=np.empty((B, P)), nodes=np.zeros((B, P), np.int32), status=np.zeros((B, P), np.int32),
-                 rel=np.empty((B, P, self.dim, self.deg + 1)))
-        if jac:
-            r["jac"] = pinned_empty((B, P, self.dim, self.deg + 1))
-            r["jac_tf"] = np.empty((B, P))
-        self._check(getattr(self._lib, name)(self._h, _ptr(Y), _ptr(tf), B, float(margin), float(eps_rel), int(max_nodes),
-                                             *[_ptr(a) for a in r.values()]), name)
-        return r
-
     def keep_out_moving_true_min(self, Y, tf, obstacles=None, motion=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
         """keep_out_true_min against obstacles that translate along Bezier offsets (obtg_keep_out_moving_true_min): per
         (vehicle, obstacle) item the static row of the relative curve c_v(s) - q_o(s tf), tf[B] the rows' spans.  The dict of
         keep_out_true_min and rel[B][P][dim][deg+1], the relative control points the search ran on."""
-        return self._keep_out_moving_call("obtg_keep_out_moving_true_min", Y, tf, obstacles, motion, margin, eps_rel, max_nodes, False)
+        return self._keep_out_call("obtg_keep_out_moving_true_min", self._keep_out_motion(obstacles, motion), Y, margin, eps_rel, max_nodes,
+                                   False, tf=_f64(tf), rel=True)
 
     def keep_out_moving_true_min_jac(self, Y, tf, obstacles=None, motion=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
         """keep_out_moving_true_min with its envelope Jacobian (obtg_keep_out_moving_true_min_jac): the same dict, bit for bit,
         jac[B][P][dim][deg+1] (d/d the item's own vehicle's control points) and jac_tf[B][P], the explicit d/dtf."""
-        return self._keep_out_moving_call("obtg_keep_out_moving_true_min_jac", Y, tf, obstacles, motion, margin, eps_rel, max_nodes, True)
+        return self._keep_out_call("obtg_keep_out_moving_true_min_jac", self._keep_out_motion(obstacles, motion), Y, margin, eps_rel,
+                                   max_nodes, True, tf=_f64(tf), rel=True)
 
     def keep_out_moving_true_min_dev(self, dY, d_tf, B, d_out, d_t_star=None, d_face=None, d_lam=None, d_bound=None, d_nodes=None,
                                      d_status=None, d_rel=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
-        self._check(self._lib.obtg_keep_out_moving_true_min_dev(
-            self._h, _vp(dY), _vp(d_tf), int(B), float(margin), float(eps_rel), int(max_nodes),
-            *[_vp(q) for q in (d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel)]), "obtg_keep_out_moving_true_min_dev")
+        self._keep_out_call_dev("obtg_keep_out_moving_true_min_dev", (dY, d_tf), B, margin, eps_rel, max_nodes,
+                                (d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel))
 
     def keep_out_moving_true_min_jac_dev(self, dY, d_tf, B, d_out, d_jac, d_jac_tf, d_t_star=None, d_face=None, d_lam=None, d_bound=None,
                                          d_nodes=None, d_status=None, d_rel=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
-        self._check(self._lib.obtg_keep_out_moving_true_min_jac_dev(
-            self._h, _vp(dY), _vp(d_tf), int(B), float(margin), float(eps_rel), int(max_nodes),
-            *[_vp(q) for q in (d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel, d_jac, d_jac_tf)]),
-            "obtg_keep_out_moving_true_min_jac_dev")
+        self._keep_out_call_dev("obtg_keep_out_moving_true_min_jac_dev", (dY, d_tf), B, margin, eps_rel, max_nodes,
+                                (d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel, d_jac, d_jac_tf))
 
     def bern_keep_out_moving(self, c, H, Q, r=None, eps_rel=1e-9, max_nodes=100000):
         """The clearance of free curves c[M][dim][K] from ONE convex obstacle H[F][dim+1] that moves by the offset curve
         Q[dim][Km], Km <= K; r[M]: the part [0, r] of the motion's parameter each curve spans (None: 1)
         (obtg_bern_keep_out_moving): dict(val[M], t_star[M], status[M])."""
-        c = _f64(c)
-        if c.ndim == 2:
-            c = c[None]
-        M, dim, K = c.shape
-        H = _f64(H).reshape(-1, dim + 1)
-        Q = _f64(Q).reshape(dim, -1)
-        if r is not None:
-            r = np.ascontiguousarray(np.broadcast_to(_f64(r).reshape(-1), (M,)))
-        out = dict(val=np.empty(M), t_star=np.empty(M), status=np.zeros(M, np.int32))
-        self._check(self._lib.obtg_bern_keep_out_moving(self._h, _ptr(c), M, dim, K, _ptr(H), H.shape[0], _ptr(Q), Q.shape[1],
-                                                        None if r is None else _ptr(r), float(eps_rel), int(max_nodes),
-                                                        *[_ptr(a) for a in out.values()]), "obtg_bern_keep_out_moving")
-        return out
+        return self._bern_keep_out("obtg_bern_keep_out_moving", c, H, eps_rel, max_nodes, moving=True, Q=Q, r=r)
 
     def bern_keep_out_moving_dev(self, d_c, M, dim, K, H, Q, d_val, d_r=None, d_t_star=None, d_status=None, eps_rel=1e-9, max_nodes=100000):
-        H = _f64(H).reshape(-1, int(dim) + 1)
-        Q = _f64(Q).reshape(int(dim), -1)
-        self._check(self._lib.obtg_bern_keep_out_moving_dev(self._h, _vp(d_c), int(M), int(dim), int(K), _ptr(H), H.shape[0], _ptr(Q),
-                                                            Q.shape[1], _vp(d_r), float(eps_rel), int(max_nodes), _vp(d_val),
-                                                            _vp(d_t_star), _vp(d_status)), "obtg_bern_keep_out_moving_dev")
+        self._bern_keep_out_dev("obtg_bern_keep_out_moving_dev", d_c, M, dim, K, H, eps_rel, max_nodes, d_val, d_t_star, d_status,
+                                moving=True, Q=Q, d_r=d_r)
 
     # -- polytopic vehicle-to-vehicle separation (include/obtg.h): ONE region H[F][dim+1] around the origin, the pairs i < j in
     # the order of np.triu_indices(N, 1); `region` as `obstacles` above: sent only when its bytes differ, None: what is set
@@ -1172,42 +1154,33 @@ class Context(object):
     def len_pair_keep_out(self):
         return self._lib.obtg_len_pair_keep_out(self._h)
 
-    def _pair_keep_out_call(self, name, euclid, Y, region, margin, eps_rel, max_nodes, jac):
+    def _pair_items(self, region):
         self._pair_keep_out(region)
-        P = self.n_veh * (self.n_veh - 1) // 2       # (no region: the library's call answers OBTG_ERR_ARG)
-        Y, B = self._rows(Y)
-        r = dict(val=pinned_empty((B, P)), t_star=np.empty((B, P)))
-        if euclid:
-            r.update(faces=np.zeros((B, P, 3), np.int32), dir=np.empty((B, P, self.dim)))
-        else:
-            r.update(face=np.zeros((B, P, 2), np.int32), lam=np.empty((B, P)))
-        r.update(bound=np.empty((B, P)), nodes=np.zeros((B, P), np.int32), status=np.zeros((B, P), np.int32),
-                 rel=np.empty((B, P, self.dim, self.deg + 1)))
-        if jac:
-            r["jac"] = pinned_empty((B, P, self.dim, self.deg + 1))
-        self._check(getattr(self._lib, name)(self._h, _ptr(Y), B, float(margin), float(eps_rel), int(max_nodes),
-                                             *[_ptr(a) for a in r.values()]), name)
-        return r
+        return self.n_veh * (self.n_veh - 1) // 2    # (no region: the library's call answers OBTG_ERR_ARG)
 
     def pair_keep_out_true_min(self, Y, region=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
         """Per vehicle pair i < j the separation row: the minimum over t in [0, 1] of the largest a_f . (c_i - c_j)(t) - b_f over
         the region's faces, minus margin (obtg_pair_keep_out_true_min): the dict of keep_out_true_min over the P = N (N - 1) / 2
         pairs and rel[B][P][dim][deg+1], the relative control points the search ran on."""
-        return self._pair_keep_out_call("obtg_pair_keep_out_true_min", False, Y, region, margin, eps_rel, max_nodes, False)
+        return self._keep_out_call("obtg_pair_keep_out_true_min", self._pair_items(region),
+                                   Y, margin, eps_rel, max_nodes, False, euclid=False, rel=True)
 
     def pair_keep_out_true_min_jac(self, Y, region=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
         """pair_keep_out_true_min with its envelope Jacobian (obtg_pair_keep_out_true_min_jac): the same dict, bit for bit, and
         jac[B][P][dim][deg+1], the block of the pair's FIRST vehicle; the second vehicle's is its exact negation."""
-        return self._pair_keep_out_call("obtg_pair_keep_out_true_min_jac", False, Y, region, margin, eps_rel, max_nodes, True)
+        return self._keep_out_call("obtg_pair_keep_out_true_min_jac", self._pair_items(region),
+                                   Y, margin, eps_rel, max_nodes, True, euclid=False, rel=True)
 
     def pair_keep_out_euclid_true_min(self, Y, region=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
         """pair_keep_out_true_min under the Euclidean metric (obtg_pair_keep_out_euclid_true_min): the dict of
         keep_out_euclid_true_min (faces[B][P][3], dir[B][P][dim]) and rel."""
-        return self._pair_keep_out_call("obtg_pair_keep_out_euclid_true_min", True, Y, region, margin, eps_rel, max_nodes, False)
+        return self._keep_out_call("obtg_pair_keep_out_euclid_true_min", self._pair_items(region),
+                                   Y, margin, eps_rel, max_nodes, False, euclid=True, rel=True)
 
     def pair_keep_out_euclid_true_min_jac(self, Y, region=None, margin=0.0, eps_rel=1e-9, max_nodes=100000):
         """pair_keep_out_euclid_true_min with jac[B][P][dim][deg+1] = dir[c] B_i(t_star), the first vehicle's block."""
-        return self._pair_keep_out_call("obtg_pair_keep_out_euclid_true_min_jac", True, Y, region, margin, eps_rel, max_nodes, True)
+        return self._keep_out_call("obtg_pair_keep_out_euclid_true_min_jac", self._pair_items(region),
+                                   Y, margin, eps_rel, max_nodes, True, euclid=True, rel=True)
 
     def pair_keep_out_true_min_dev(self, dY, B, d_out, d_t_star=None, d_face=None, d_lam=None, d_bound=None, d_nodes=None, d_status=None,
                                    d_rel=None, d_jac=None, euclid=False, margin=0.0, eps_rel=1e-9, max_nodes=100000):
@@ -1215,8 +1188,7 @@ class Context(object):
         form."""
         name = "obtg_pair_keep_out_%strue_min%s_dev" % ("euclid_" if euclid else "", "" if d_jac is None else "_jac")
         ptrs = [d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel] + ([] if d_jac is None else [d_jac])
-        self._check(getattr(self._lib, name)(self._h, _vp(dY), int(B), float(margin), float(eps_rel), int(max_nodes),
-                                             *[_vp(q) for q in ptrs]), name)
+        self._keep_out_call_dev(name, (dY,), B, margin, eps_rel, max_nodes, ptrs)
 
     def jerk(self, Y, tf, bound):
         """The jerk-bound rows (obtg_jerk): [B][N * (2 deg + DEG_ELEV + 1)] control points of

@@ -2305,126 +2305,6 @@ int obtg_ctx_set_keep_out(obtg_ctx* c, const double* H, const int* obs_off, int 
 
 int obtg_len_keep_out(const obtg_ctx* c) { return c ? c->ko_P : 0; }
 
-// pair: the rows of the vehicle pairs (obtg_pair_keep_out_*), which need the separation region in place of the obstacle tables
-static int keep_out_args(const obtg_ctx* c, const double* out, int B, int max_nodes, double eps_rel, double margin, bool pair = false)
-{
-    if (!check_ctx(c) || (pair ? c->pk_F : c->ko_P) <= 0 || (c->dim != 2 && c->dim != 3) || !out || B < 0 || max_nodes < 1 ||
-        !(eps_rel >= 0.0) || margin != margin)
-        return OBTG_ERR_ARG;
-    return c->deg > 31 ? OBTG_ERR_UNSUPPORTED : OBTG_OK;
-}
-
-static int keep_out_launch(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
-                           double* d_t, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status, double* d_jac)
-{
-    return launch_keep_out(c, c->dim, c->deg + 1, dY, (long)B * c->ko_P, c->n_veh, c->ko_P, c->d_ko_H.as<double>(),
-                           c->d_ko_off.as<int>(), c->d_ko_VO.as<int>(), 0, margin, eps_rel, max_nodes, d_out, d_t, d_face, d_lam,
-                           d_bound, d_nodes, d_status, d_jac, OBTG_K_SPEED);
-}
-
-// want_jac: the _jac entry points, where the blocks are not optional
-static int keep_out_true_min_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
-                                 double* d_t, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status, bool want_jac,
-                                 double* d_jac)
-{
-    if (int rc = keep_out_args(c, d_out, B, max_nodes, eps_rel, margin)) return rc;
-    if (!dY || (want_jac && !d_jac)) return OBTG_ERR_ARG;
-    (void)hipSetDevice(c->device);
-    return keep_out_launch(c, dY, B, margin, eps_rel, max_nodes, d_out, d_t, d_face, d_lam, d_bound, d_nodes, d_status, d_jac);
-}
-
-// the host body: Y up; val | t_star | lam | bound | jac in ws_out, face | nodes | status in WS_STATUS
-static int keep_out_true_min(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
-                             double* t_star, int* face, double* lam, double* bound, int* nodes, int* status, bool want_jac, double* jac)
-{
-    if (int rc = keep_out_args(c, out, B, max_nodes, eps_rel, margin)) return rc;
-    if (!Y || (want_jac && !jac)) return OBTG_ERR_ARG;
-    if (B == 0) return OBTG_OK;
-    const size_t n = (size_t)B * c->ko_P, nj = jac ? n * c->dim * (c->deg + 1) : 0;
-    HostCall h(c);
-    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
-    double* dv = h.out<double>(c->ws_out, 4 * n + nj);
-    int* di = h.out<int>(c->ws_misc[WS_STATUS], 4 * n);
-    double* dj = jac ? dv + 4 * n : nullptr;
-    h.run([&] { return keep_out_launch(c, dY, B, margin, eps_rel, max_nodes, dv, dv + n, di, dv + 2 * n, dv + 3 * n, di + 2 * n,
-                                       di + 3 * n, dj); });
-    h.fetch(t_star, dv + n, n);
-    h.fetch(lam, dv + 2 * n, n);
-    h.fetch(bound, dv + 3 * n, n);
-    h.fetch(face, di, 2 * n);
-    h.fetch(nodes, di + 2 * n, n);
-    h.fetch(status, di + 3 * n, n);
-    h.fetch(jac, dj, nj);
-    return h.finish(out, dv, n);
-}
-
-int obtg_keep_out_true_min_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
-                               double* d_t_star, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status)
-{
-    return keep_out_true_min_dev(c, dY, B, margin, eps_rel, max_nodes, d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, false,
-                                 nullptr);
-}
-
-int obtg_keep_out_true_min(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out, double* t_star,
-                           int* face, double* lam, double* bound, int* nodes, int* status)
-{
-    return keep_out_true_min(c, Y, B, margin, eps_rel, max_nodes, out, t_star, face, lam, bound, nodes, status, false, nullptr);
-}
-
-int obtg_keep_out_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
-                                   double* d_t_star, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status,
-                                   double* d_jac)
-{
-    return keep_out_true_min_dev(c, dY, B, margin, eps_rel, max_nodes, d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, true,
-                                 d_jac);
-}
-
-int obtg_keep_out_true_min_jac(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
-                               double* t_star, int* face, double* lam, double* bound, int* nodes, int* status, double* jac)
-{
-    return keep_out_true_min(c, Y, B, margin, eps_rel, max_nodes, out, t_star, face, lam, bound, nodes, status, true, jac);
-}
-
-// Free curves cv[M][dim][K] against ONE face table H[F][dim+1] (a host array in both forms), whatever the context's shape is:
-// the same kernel, one obstacle of all F faces, margin 0.  The context's own keep-out tables are not touched.
-static int bern_keep_out_args(const obtg_ctx* c, const double* cv, int M, int dim, int K, const double* H, int F, double eps_rel,
-                              int max_nodes, const double* val)
-{
-    if (!check_ctx(c) || M < 0 || (dim != 2 && dim != 3) || K < 2 || F < 1 || !H || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
-    if (K > kMdMaxCurveK || F > kKeepOutMaxFaces) return OBTG_ERR_UNSUPPORTED;
-    if (M == 0) return kNothingToDo;
-    return cv && val ? OBTG_OK : OBTG_ERR_ARG;
-}
-
-int obtg_bern_keep_out_dev(obtg_ctx* c, const double* d_c, int M, int dim, int K, const double* H, int F, double eps_rel, int max_nodes,
-                           double* d_val, double* d_t_star, int* d_status)
-{
-    if (int chk = bern_keep_out_args(c, d_c, M, dim, K, H, F, eps_rel, max_nodes, d_val)) return done(chk);
-    (void)hipSetDevice(c->device);
-    DevBuf& dH = c->ws_misc[WS_ARG_A];
-    if (int rc = upload(c, dH, H, sizeof(double) * (size_t)F * (dim + 1))) return rc;
-    return launch_keep_out(c, dim, K, d_c, M, 1, 1, dH.as<double>(), nullptr, nullptr, F, 0.0, eps_rel, max_nodes, d_val, d_t_star,
-                           nullptr, nullptr, nullptr, nullptr, d_status, nullptr, OBTG_K_SPEED);
-}
-
-int obtg_bern_keep_out(obtg_ctx* c, const double* cv, int M, int dim, int K, const double* H, int F, double eps_rel, int max_nodes,
-                       double* val, double* t_star, int* status)
-{
-    if (int chk = bern_keep_out_args(c, cv, M, dim, K, H, F, eps_rel, max_nodes, val)) return done(chk);
-    const size_t n = (size_t)M;
-    HostCall h(c);
-    DevBuf& dH = c->ws_misc[WS_ARG_A];
-    if (int rc = upload(c, dH, H, sizeof(double) * (size_t)F * (dim + 1))) return rc;
-    const double* d_c = h.in(c->ws_in, cv, n * dim * K);
-    double* dv = h.out<double>(c->ws_out, 2 * n);
-    int* ds = h.out<int>(c->ws_misc[WS_STATUS], n);
-    h.run([&] { return launch_keep_out(c, dim, K, d_c, M, 1, 1, dH.as<double>(), nullptr, nullptr, F, 0.0, eps_rel, max_nodes, dv, dv + n,
-                                       nullptr, nullptr, nullptr, nullptr, ds, nullptr, OBTG_K_SPEED); });
-    h.fetch(t_star, dv + n, n);
-    h.fetch(status, ds, n);
-    return h.finish(val, dv, n);
-}
-
 // The Euclidean metric (include/obtg.h "Euclidean keep-out clearance"; csrc/keepout_features.h): the signed Euclidean distance in
 // place of the largest face value.  The normalised faces and the feature records are host work, done once per table.
 int obtg_keep_out_features(const double* H, int F, int d, double* Hn, int* idx, double* ginv, int* n)
@@ -2446,152 +2326,6 @@ static void keep_out_pack_features(const int* idx, const double* ginv, int n, st
         std::memcpy(&slot, &pk, sizeof slot);
         rec.push_back(slot);
     }
-}
-
-// the context's tables, on the first Euclidean call after obtg_ctx_set_keep_out
-static int keep_out_euclid_tables(obtg_ctx* c)
-{
-    if (c->ko_eu_state) return c->ko_eu_state == 1 ? OBTG_OK : c->ko_eu_state;
-    const int d = c->dim, O = c->ko_O;
-    std::vector<double> Hn(c->h_ko_H.size()), rec, ginv(6 * (size_t)kKoMaxFeatures);
-    std::vector<int> foff(O + 1, 0), idx(3 * (size_t)kKoMaxFeatures);
-    for (int o = 0; o < O; ++o) {
-        const int f0 = c->h_ko_off[o], F = c->h_ko_off[o + 1] - f0;
-        keep_out_normalise(c->h_ko_H.data() + (size_t)f0 * (d + 1), F, d, Hn.data() + (size_t)f0 * (d + 1));
-        const int n = keep_out_enumerate(Hn.data() + (size_t)f0 * (d + 1), F, d, kKoMaxFeatures, idx.data(), ginv.data());
-        if (n > kKoMaxFeatures) return c->ko_eu_state = OBTG_ERR_UNSUPPORTED;
-        keep_out_pack_features(idx.data(), ginv.data(), n, rec);
-        foff[o + 1] = foff[o] + n;
-    }
-    if (rec.empty()) rec.push_back(0.0);           // (no obstacle has a feature: the buffer is never read)
-    (void)hipSetDevice(c->device);
-    int rc = upload(c, c->d_ko_Hn, Hn.data(), sizeof(double) * Hn.size());
-    if (!rc) rc = upload(c, c->d_ko_feat, rec.data(), sizeof(double) * rec.size());
-    if (!rc) rc = upload(c, c->d_ko_foff, foff.data(), sizeof(int) * foff.size());
-    if (rc) return rc;
-    c->ko_eu_state = 1;
-    return OBTG_OK;
-}
-
-static int keep_out_euclid_launch(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
-                                  double* d_t, int* d_faces, double* d_dir, double* d_bound, int* d_nodes, int* d_status, double* d_jac)
-{
-    return launch_keep_out_euclid(c, c->dim, c->deg + 1, dY, (long)B * c->ko_P, c->n_veh, c->ko_P, c->d_ko_Hn.as<double>(),
-                                  c->d_ko_off.as<int>(), c->d_ko_VO.as<int>(), 0, c->d_ko_feat.as<double>(), c->d_ko_foff.as<int>(), 0,
-                                  margin, eps_rel, max_nodes, d_out, d_t, d_faces, d_dir, d_bound, d_nodes, d_status, d_jac, OBTG_K_SPEED);
-}
-
-static int keep_out_euclid_args(obtg_ctx* c, const double* out, int B, int max_nodes, double eps_rel, double margin)
-{
-    if (int rc = keep_out_args(c, out, B, max_nodes, eps_rel, margin)) return rc;
-    if (c->ko_motion) return OBTG_ERR_UNSUPPORTED;           // moving obstacles under this metric are not built
-    return keep_out_euclid_tables(c);
-}
-
-static int keep_out_euclid_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
-                               double* d_t, int* d_faces, double* d_dir, double* d_bound, int* d_nodes, int* d_status, bool want_jac,
-                               double* d_jac)
-{
-    if (int rc = keep_out_euclid_args(c, d_out, B, max_nodes, eps_rel, margin)) return rc;
-    if (!dY || (want_jac && !d_jac)) return OBTG_ERR_ARG;
-    (void)hipSetDevice(c->device);
-    return keep_out_euclid_launch(c, dY, B, margin, eps_rel, max_nodes, d_out, d_t, d_faces, d_dir, d_bound, d_nodes, d_status, d_jac);
-}
-
-// the host body: Y up; val | t_star | bound | dir | jac in ws_out, faces | nodes | status in WS_STATUS
-static int keep_out_euclid_host(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
-                                double* t_star, int* faces, double* dir, double* bound, int* nodes, int* status, bool want_jac, double* jac)
-{
-    if (int rc = keep_out_euclid_args(c, out, B, max_nodes, eps_rel, margin)) return rc;
-    if (!Y || (want_jac && !jac)) return OBTG_ERR_ARG;
-    if (B == 0) return OBTG_OK;
-    const size_t n = (size_t)B * c->ko_P, nd = n * c->dim, nj = jac ? n * c->dim * (c->deg + 1) : 0;
-    HostCall h(c);
-    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
-    double* dv = h.out<double>(c->ws_out, 3 * n + nd + nj);
-    int* di = h.out<int>(c->ws_misc[WS_STATUS], 5 * n);
-    double* dj = jac ? dv + 3 * n + nd : nullptr;
-    h.run([&] { return keep_out_euclid_launch(c, dY, B, margin, eps_rel, max_nodes, dv, dv + n, di, dv + 3 * n, dv + 2 * n, di + 3 * n,
-                                              di + 4 * n, dj); });
-    h.fetch(t_star, dv + n, n);
-    h.fetch(bound, dv + 2 * n, n);
-    h.fetch(dir, dv + 3 * n, nd);
-    h.fetch(faces, di, 3 * n);
-    h.fetch(nodes, di + 3 * n, n);
-    h.fetch(status, di + 4 * n, n);
-    h.fetch(jac, dj, nj);
-    return h.finish(out, dv, n);
-}
-
-int obtg_keep_out_euclid_true_min_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
-                                      double* d_t_star, int* d_faces, double* d_dir, double* d_bound, int* d_nodes, int* d_status)
-{
-    return keep_out_euclid_dev(c, dY, B, margin, eps_rel, max_nodes, d_out, d_t_star, d_faces, d_dir, d_bound, d_nodes, d_status, false,
-                               nullptr);
-}
-
-int obtg_keep_out_euclid_true_min(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
-                                  double* t_star, int* faces, double* dir, double* bound, int* nodes, int* status)
-{
-    return keep_out_euclid_host(c, Y, B, margin, eps_rel, max_nodes, out, t_star, faces, dir, bound, nodes, status, false, nullptr);
-}
-
-int obtg_keep_out_euclid_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes,
-                                          double* d_out, double* d_t_star, int* d_faces, double* d_dir, double* d_bound, int* d_nodes,
-                                          int* d_status, double* d_jac)
-{
-    return keep_out_euclid_dev(c, dY, B, margin, eps_rel, max_nodes, d_out, d_t_star, d_faces, d_dir, d_bound, d_nodes, d_status, true,
-                               d_jac);
-}
-
-int obtg_keep_out_euclid_true_min_jac(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
-                                      double* t_star, int* faces, double* dir, double* bound, int* nodes, int* status, double* jac)
-{
-    return keep_out_euclid_host(c, Y, B, margin, eps_rel, max_nodes, out, t_star, faces, dir, bound, nodes, status, true, jac);
-}
-
-// Free curves against ONE obstacle under the Euclidean metric: Hn | the records in one buffer (WS_ARG_A); *nf the records
-static int bern_keep_out_euclid_tables(obtg_ctx* c, const double* H, int F, int dim, int* nf)
-{
-    std::vector<double> buf((size_t)F * (dim + 1)), ginv(6 * (size_t)kKoMaxFeatures);
-    std::vector<int> idx(3 * (size_t)kKoMaxFeatures);
-    keep_out_normalise(H, F, dim, buf.data());
-    *nf = keep_out_enumerate(buf.data(), F, dim, kKoMaxFeatures, idx.data(), ginv.data());
-    if (*nf > kKoMaxFeatures) return OBTG_ERR_UNSUPPORTED;
-    keep_out_pack_features(idx.data(), ginv.data(), *nf, buf);
-    return upload(c, c->ws_misc[WS_ARG_A], buf.data(), sizeof(double) * buf.size());
-}
-
-int obtg_bern_keep_out_euclid_dev(obtg_ctx* c, const double* d_c, int M, int dim, int K, const double* H, int F, double eps_rel,
-                                  int max_nodes, double* d_val, double* d_t_star, int* d_status)
-{
-    if (int chk = bern_keep_out_args(c, d_c, M, dim, K, H, F, eps_rel, max_nodes, d_val)) return done(chk);
-    (void)hipSetDevice(c->device);
-    int nf = 0;
-    if (int rc = bern_keep_out_euclid_tables(c, H, F, dim, &nf)) return rc;
-    const double* dH = c->ws_misc[WS_ARG_A].as<double>();
-    return launch_keep_out_euclid(c, dim, K, d_c, M, 1, 1, dH, nullptr, nullptr, F, dH + (size_t)F * (dim + 1), nullptr, nf, 0.0, eps_rel,
-                                  max_nodes, d_val, d_t_star, nullptr, nullptr, nullptr, nullptr, d_status, nullptr, OBTG_K_SPEED);
-}
-
-int obtg_bern_keep_out_euclid(obtg_ctx* c, const double* cv, int M, int dim, int K, const double* H, int F, double eps_rel, int max_nodes,
-                              double* val, double* t_star, int* status)
-{
-    if (int chk = bern_keep_out_args(c, cv, M, dim, K, H, F, eps_rel, max_nodes, val)) return done(chk);
-    const size_t n = (size_t)M;
-    HostCall h(c);
-    int nf = 0;
-    if (int rc = bern_keep_out_euclid_tables(c, H, F, dim, &nf)) return rc;
-    const double* dH = c->ws_misc[WS_ARG_A].as<double>();
-    const double* d_c = h.in(c->ws_in, cv, n * dim * K);
-    double* dv = h.out<double>(c->ws_out, 2 * n);
-    int* ds = h.out<int>(c->ws_misc[WS_STATUS], n);
-    h.run([&] { return launch_keep_out_euclid(c, dim, K, d_c, M, 1, 1, dH, nullptr, nullptr, F, dH + (size_t)F * (dim + 1), nullptr, nf, 0.0,
-                                              eps_rel, max_nodes, dv, dv + n, nullptr, nullptr, nullptr, nullptr, ds, nullptr,
-                                              OBTG_K_SPEED); });
-    h.fetch(t_star, dv + n, n);
-    h.fetch(status, ds, n);
-    return h.finish(val, dv, n);
 }
 
 // Moving keep-out obstacles (include/obtg.h "moving keep-out obstacles"): obstacle o's faces are translated by a Bezier offset
@@ -2622,145 +2356,6 @@ int obtg_ctx_set_keep_out_motion(obtg_ctx* c, const double* Q, const int* q_off,
     if (rc) return rc;
     c->ko_motion = true;
     return OBTG_OK;
-}
-
-// (the entry points below refuse a context without a motion, OBTG_ERR_ARG: that is a caller who forgot to set one, not a
-// request for the static rows)
-static int keep_out_moving_launch(obtg_ctx* c, const double* dY, const double* d_tf, int B, double margin, double eps_rel, int max_nodes,
-                                  double* d_out, double* d_t, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status,
-                                  double* d_rel, double* d_jac, double* d_jac_tf)
-{
-    KeepOutMotionArgs mo{};
-    mo.d_Q = c->d_ko_Q.as<double>(); mo.d_q_off = c->d_ko_qoff.as<int>(); mo.d_T = c->d_ko_T.as<double>(); mo.d_tf = d_tf;
-    mo.d_rel = d_rel; mo.d_jac_tf = d_jac_tf;
-    return launch_keep_out_moving(c, c->dim, c->deg + 1, dY, (long)B * c->ko_P, c->n_veh, c->ko_P, c->d_ko_H.as<double>(),
-                                  c->d_ko_off.as<int>(), c->d_ko_VO.as<int>(), 0, &mo, margin, eps_rel, max_nodes, d_out, d_t, d_face,
-                                  d_lam, d_bound, d_nodes, d_status, d_jac, OBTG_K_SPEED);
-}
-
-static int keep_out_moving_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double margin, double eps_rel, int max_nodes,
-                               double* d_out, double* d_t, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status,
-                               double* d_rel, bool want_jac, double* d_jac, double* d_jac_tf)
-{
-    if (int rc = keep_out_args(c, d_out, B, max_nodes, eps_rel, margin)) return rc;
-    if (!c->ko_motion || !dY || !d_tf || (want_jac && (!d_jac || !d_jac_tf))) return OBTG_ERR_ARG;
-    (void)hipSetDevice(c->device);
-    return keep_out_moving_launch(c, dY, d_tf, B, margin, eps_rel, max_nodes, d_out, d_t, d_face, d_lam, d_bound, d_nodes, d_status,
-                                  d_rel, d_jac, d_jac_tf);
-}
-
-// the host body: Y and tf up; val | t_star | lam | bound | jac_tf | rel | jac in ws_out, face | nodes | status in WS_STATUS
-static int keep_out_moving(obtg_ctx* c, const double* Y, const double* tf, int B, double margin, double eps_rel, int max_nodes,
-                           double* out, double* t_star, int* face, double* lam, double* bound, int* nodes, int* status, double* rel,
-                           bool want_jac, double* jac, double* jac_tf)
-{
-    if (int rc = keep_out_args(c, out, B, max_nodes, eps_rel, margin)) return rc;
-    if (!c->ko_motion || !Y || !tf || (want_jac && (!jac || !jac_tf))) return OBTG_ERR_ARG;
-    if (B == 0) return OBTG_OK;
-    const size_t n = (size_t)B * c->ko_P, nb = n * c->dim * (c->deg + 1), nr = rel ? nb : 0, nj = want_jac ? nb : 0;
-    HostCall h(c);
-    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
-    const double* d_tf = h.in(c->ws_in2, tf, (size_t)B, true);
-    double* dv = h.out<double>(c->ws_out, 5 * n + nr + nj);
-    int* di = h.out<int>(c->ws_misc[WS_STATUS], 4 * n);
-    double* dr = rel ? dv + 5 * n : nullptr;
-    double* dj = want_jac ? dv + 5 * n + nr : nullptr;
-    h.run([&] { return keep_out_moving_launch(c, dY, d_tf, B, margin, eps_rel, max_nodes, dv, dv + n, di, dv + 2 * n, dv + 3 * n, di + 2 * n,
-                                              di + 3 * n, dr, dj, want_jac ? dv + 4 * n : nullptr); });
-    h.fetch(t_star, dv + n, n);
-    h.fetch(lam, dv + 2 * n, n);
-    h.fetch(bound, dv + 3 * n, n);
-    if (want_jac) h.fetch(jac_tf, dv + 4 * n, n);
-    h.fetch(face, di, 2 * n);
-    h.fetch(nodes, di + 2 * n, n);
-    h.fetch(status, di + 3 * n, n);
-    h.fetch(rel, dr, nr);
-    if (want_jac) h.fetch(jac, dj, nj);
-    return h.finish(out, dv, n);
-}
-
-int obtg_keep_out_moving_true_min_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double margin, double eps_rel, int max_nodes,
-                                      double* d_out, double* d_t_star, int* d_face, double* d_lam, double* d_bound, int* d_nodes,
-                                      int* d_status, double* d_rel)
-{
-    return keep_out_moving_dev(c, dY, d_tf, B, margin, eps_rel, max_nodes, d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel,
-                               false, nullptr, nullptr);
-}
-
-int obtg_keep_out_moving_true_min(obtg_ctx* c, const double* Y, const double* tf, int B, double margin, double eps_rel, int max_nodes,
-                                  double* out, double* t_star, int* face, double* lam, double* bound, int* nodes, int* status, double* rel)
-{
-    return keep_out_moving(c, Y, tf, B, margin, eps_rel, max_nodes, out, t_star, face, lam, bound, nodes, status, rel, false, nullptr,
-                           nullptr);
-}
-
-int obtg_keep_out_moving_true_min_jac_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double margin, double eps_rel,
-                                          int max_nodes, double* d_out, double* d_t_star, int* d_face, double* d_lam, double* d_bound,
-                                          int* d_nodes, int* d_status, double* d_rel, double* d_jac, double* d_jac_tf)
-{
-    return keep_out_moving_dev(c, dY, d_tf, B, margin, eps_rel, max_nodes, d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel,
-                               true, d_jac, d_jac_tf);
-}
-
-int obtg_keep_out_moving_true_min_jac(obtg_ctx* c, const double* Y, const double* tf, int B, double margin, double eps_rel, int max_nodes,
-                                      double* out, double* t_star, int* face, double* lam, double* bound, int* nodes, int* status,
-                                      double* rel, double* jac, double* jac_tf)
-{
-    return keep_out_moving(c, Y, tf, B, margin, eps_rel, max_nodes, out, t_star, face, lam, bound, nodes, status, rel, true, jac, jac_tf);
-}
-
-// Free curves cv[M][dim][K] against ONE obstacle H[F][dim+1] that moves by Q[dim][Km] (H and Q host arrays in both forms); r[M]:
-// per curve the part [0, r] of the motion's parameter that the curve spans (null: 1); a host array, device memory in the _dev form.
-static int bern_keep_out_moving_args(const obtg_ctx* c, const double* cv, int M, int dim, int K, const double* H, int F, const double* Q,
-                                     int Km, double eps_rel, int max_nodes, const double* val)
-{
-    if (int chk = bern_keep_out_args(c, cv, M, dim, K, H, F, eps_rel, max_nodes, val)) {
-        if (chk != kNothingToDo) return chk;
-        return (Km < 1 || !Q) ? OBTG_ERR_ARG : Km > K ? OBTG_ERR_UNSUPPORTED : kNothingToDo;
-    }
-    if (Km < 1 || !Q) return OBTG_ERR_ARG;
-    return Km > K ? OBTG_ERR_UNSUPPORTED : OBTG_OK;
-}
-
-static int bern_keep_out_moving_launch(obtg_ctx* c, const double* d_c, int M, int dim, int K, const double* dH, int F, const double* dQ,
-                                       int Km, const double* d_r, double eps_rel, int max_nodes, double* d_val, double* d_t, int* d_status)
-{
-    KeepOutMotionArgs mo{};
-    mo.d_Q = dQ; mo.Km = Km; mo.d_r = d_r;
-    return launch_keep_out_moving(c, dim, K, d_c, M, 1, 1, dH, nullptr, nullptr, F, &mo, 0.0, eps_rel, max_nodes, d_val, d_t, nullptr,
-                                  nullptr, nullptr, nullptr, d_status, nullptr, OBTG_K_SPEED);
-}
-
-int obtg_bern_keep_out_moving_dev(obtg_ctx* c, const double* d_c, int M, int dim, int K, const double* H, int F, const double* Q, int Km,
-                                  const double* d_r, double eps_rel, int max_nodes, double* d_val, double* d_t_star, int* d_status)
-{
-    if (int chk = bern_keep_out_moving_args(c, d_c, M, dim, K, H, F, Q, Km, eps_rel, max_nodes, d_val)) return done(chk);
-    (void)hipSetDevice(c->device);
-    DevBuf &dH = c->ws_misc[WS_ARG_A], &dQ = c->ws_misc[WS_ARG_B];
-    if (int rc = upload(c, dH, H, sizeof(double) * (size_t)F * (dim + 1))) return rc;
-    if (int rc = upload(c, dQ, Q, sizeof(double) * (size_t)Km * dim)) return rc;
-    return bern_keep_out_moving_launch(c, d_c, M, dim, K, dH.as<double>(), F, dQ.as<double>(), Km, d_r, eps_rel, max_nodes, d_val, d_t_star,
-                                       d_status);
-}
-
-int obtg_bern_keep_out_moving(obtg_ctx* c, const double* cv, int M, int dim, int K, const double* H, int F, const double* Q, int Km,
-                              const double* r, double eps_rel, int max_nodes, double* val, double* t_star, int* status)
-{
-    if (int chk = bern_keep_out_moving_args(c, cv, M, dim, K, H, F, Q, Km, eps_rel, max_nodes, val)) return done(chk);
-    const size_t n = (size_t)M;
-    HostCall h(c);
-    DevBuf &dH = c->ws_misc[WS_ARG_A], &dQ = c->ws_misc[WS_ARG_B];
-    if (int rc = upload(c, dH, H, sizeof(double) * (size_t)F * (dim + 1))) return rc;
-    if (int rc = upload(c, dQ, Q, sizeof(double) * (size_t)Km * dim)) return rc;
-    const double* d_c = h.in(c->ws_in, cv, n * dim * K);
-    const double* d_r = r ? h.in(c->ws_in2, r, n) : nullptr;
-    double* dv = h.out<double>(c->ws_out, 2 * n);
-    int* ds = h.out<int>(c->ws_misc[WS_STATUS], n);
-    h.run([&] { return bern_keep_out_moving_launch(c, d_c, M, dim, K, dH.as<double>(), F, dQ.as<double>(), Km, d_r, eps_rel, max_nodes, dv,
-                                                   dv + n, ds); });
-    h.fetch(t_star, dv + n, n);
-    h.fetch(status, ds, n);
-    return h.finish(val, dv, n);
 }
 
 // Vehicle pairs against ONE separation region (include/obtg.h "polytopic vehicle-to-vehicle separation"): the keep-out kernel on
@@ -2794,143 +2389,446 @@ int obtg_ctx_set_pair_keep_out(obtg_ctx* c, const double* H, int F)
 
 int obtg_len_pair_keep_out(const obtg_ctx* c) { return c && c->pk_F > 0 ? c->n_veh * (c->n_veh - 1) / 2 : 0; }
 
-// the region's normalised faces and feature records, on the first Euclidean pair call after obtg_ctx_set_pair_keep_out
-static int pair_keep_out_euclid_tables(obtg_ctx* c)
+// ------------------------------------------------------------------ the keep-out family's one host path
+// A form is a set of these bits; KO_FREE: the free-curve calls (obtg_bern_keep_out*), whose only outputs are val, t and status
+enum : unsigned { KO_MOVING = 1, KO_EUCLID = 2, KO_PAIR = 4, KO_FREE = 8 };
+
+// The output columns of a keep-out call, in the order of the workspace -- the doubles in ws_out, the ints in WS_STATUS -- and
+// of the downloads: the per-item doubles, the ints, then the blocks, the order every keep-out call has downloaded in since
+// it was added.  val is first and is downloaded last (finish, the call's ONE synchronise).  The partition of the workspace and
+// the list of downloads both come from walking this table; a new output is a new line here and a member of KeepOutOutputs.
+constexpr int kKoPerDim = -1, kKoPerBlock = -2;       // elements per item: dim, dim K
+struct KoColumn {
+    double* KeepOutOutputs::*d;     // a column of doubles, or
+    int* KeepOutOutputs::*i;        // a column of ints
+    int per_item;                   // 1, 2, 3, kKoPerDim or kKoPerBlock
+    unsigned only, never;           // the forms that have it: one bit of `only` set (0: any form) and no bit of `never`
+    bool on_request;                // true: on the device only when the caller asked for it (a null pointer: the kernel skips the
+                                    // stores); false: always given device storage, whatever the caller's pointer is
+};
+static const KoColumn kKoColumns[] = {
+    { &KeepOutOutputs::val, nullptr, 1, 0, 0, false },
+    { &KeepOutOutputs::t, nullptr, 1, 0, 0, false },
+    { &KeepOutOutputs::lam, nullptr, 1, 0, KO_EUCLID | KO_FREE, false },
+    { &KeepOutOutputs::dir, nullptr, kKoPerDim, KO_EUCLID, KO_FREE, false },
+    { &KeepOutOutputs::bound, nullptr, 1, 0, KO_FREE, false },
+    { &KeepOutOutputs::jac_tf, nullptr, 1, KO_MOVING, KO_FREE, true },
+    { nullptr, &KeepOutOutputs::face, 2, 0, KO_EUCLID | KO_FREE, false },
+    { nullptr, &KeepOutOutputs::faces3, 3, KO_EUCLID, KO_FREE, false },
+    { nullptr, &KeepOutOutputs::nodes, 1, 0, KO_FREE, false },
+    { nullptr, &KeepOutOutputs::status, 1, 0, 0, false },
+    { &KeepOutOutputs::rel, nullptr, kKoPerBlock, KO_MOVING | KO_PAIR, KO_FREE, true },
+    { &KeepOutOutputs::jac, nullptr, kKoPerBlock, 0, KO_FREE, true },
+};
+
+// elements per item of a column in this call; 0: the call has no such column on the device (the on-request columns are doubles)
+static size_t ko_per_item(const KoColumn& col, unsigned form, int dim, int K, const KeepOutOutputs& host)
 {
-    if (c->pk_eu_state) return c->pk_eu_state == 1 ? OBTG_OK : c->pk_eu_state;
-    const int d = c->dim, F = c->pk_F;
-    std::vector<double> Hn(c->h_pk_H.size()), rec, ginv(6 * (size_t)kKoMaxFeatures);
-    std::vector<int> idx(3 * (size_t)kKoMaxFeatures);
-    keep_out_normalise(c->h_pk_H.data(), F, d, Hn.data());
-    const int n = keep_out_enumerate(Hn.data(), F, d, kKoMaxFeatures, idx.data(), ginv.data());
-    if (n > kKoMaxFeatures) return c->pk_eu_state = OBTG_ERR_UNSUPPORTED;
-    keep_out_pack_features(idx.data(), ginv.data(), n, rec);
-    if (rec.empty()) rec.push_back(0.0);           // (a region without a feature: the buffer is never read)
+    if ((col.only && !(form & col.only)) || (form & col.never) || (col.on_request && !(host.*col.d))) return 0;
+    return col.per_item == kKoPerDim ? dim : col.per_item == kKoPerBlock ? dim * K : col.per_item;
+}
+
+// the device side of a call of n items: the workspace reserved and handed out column by column
+static KeepOutOutputs keep_out_device_outputs(HostCall& h, unsigned form, int dim, int K, size_t n, const KeepOutOutputs& host)
+{
+    size_t nd = 0, ni = 0;
+    for (const KoColumn& col : kKoColumns) (col.d ? nd : ni) += n * ko_per_item(col, form, dim, K, host);
+    double* dv = h.out<double>(h.c->ws_out, nd);
+    int* di = h.out<int>(h.c->ws_misc[WS_STATUS], ni);
+    KeepOutOutputs dev{};
+    for (const KoColumn& col : kKoColumns) {
+        const size_t k = n * ko_per_item(col, form, dim, K, host);
+        if (!k) continue;
+        if (col.d) { dev.*col.d = dv; dv += k; }
+        else { dev.*col.i = di; di += k; }
+    }
+    return dev;
+}
+
+// one download per optional output the caller gave a pointer for, then val
+static int keep_out_download(HostCall& h, unsigned form, int dim, int K, size_t n, const KeepOutOutputs& host, const KeepOutOutputs& dev)
+{
+    for (const KoColumn& col : kKoColumns) {
+        const size_t k = n * ko_per_item(col, form, dim, K, host);
+        if (!k || col.d == &KeepOutOutputs::val) continue;
+        if (col.d) h.fetch(host.*col.d, dev.*col.d, k);
+        else h.fetch(host.*col.i, dev.*col.i, k);
+    }
+    return h.finish(host.val, dev.val, n);
+}
+
+// The Euclidean tables of the face ranges off[0 .. O] of H: the normalised faces and, range by range, the feature records
+// (normalise, enumerate, pack), then the upload -- Hn to d_Hn, the records to d_feat (null: behind Hn, in the same buffer), the
+// ranges' record offsets to d_foff (null: not kept); *nf: the records of the last range.  A range with more than
+// kKoMaxFeatures records: OBTG_ERR_UNSUPPORTED, nothing uploaded.
+static int keep_out_feature_tables(obtg_ctx* c, const double* H, const int* off, int O, int d, DevBuf& d_Hn, DevBuf* d_feat, DevBuf* d_foff,
+                                   int* nf)
+{
+    std::vector<double> Hn((size_t)off[O] * (d + 1)), rec, ginv(6 * (size_t)kKoMaxFeatures);
+    std::vector<int> foff(O + 1, 0), idx(3 * (size_t)kKoMaxFeatures);
+    for (int o = 0; o < O; ++o) {
+        const size_t at = (size_t)off[o] * (d + 1);
+        const int F = off[o + 1] - off[o];
+        keep_out_normalise(H + at, F, d, Hn.data() + at);
+        const int n = keep_out_enumerate(Hn.data() + at, F, d, kKoMaxFeatures, idx.data(), ginv.data());
+        if (n > kKoMaxFeatures) return OBTG_ERR_UNSUPPORTED;
+        keep_out_pack_features(idx.data(), ginv.data(), n, rec);
+        foff[o + 1] = foff[o] + n;
+    }
     (void)hipSetDevice(c->device);
-    int rc = upload(c, c->d_pk_Hn, Hn.data(), sizeof(double) * Hn.size());
-    if (!rc) rc = upload(c, c->d_pk_feat, rec.data(), sizeof(double) * rec.size());
-    if (rc) return rc;
-    c->pk_NF = n;
-    c->pk_eu_state = 1;
-    return OBTG_OK;
+    if (!d_feat) Hn.insert(Hn.end(), rec.begin(), rec.end());
+    else if (rec.empty()) rec.push_back(0.0);      // (no range has a feature: the buffer is never read)
+    int rc = upload(c, d_Hn, Hn.data(), sizeof(double) * Hn.size());
+    if (!rc && d_feat) rc = upload(c, *d_feat, rec.data(), sizeof(double) * rec.size());
+    if (!rc && d_foff) rc = upload(c, *d_foff, foff.data(), sizeof(int) * foff.size());
+    if (!rc && nf) *nf = foff[O] - foff[O - 1];
+    return rc;
 }
 
-static int pair_keep_out_args(obtg_ctx* c, const double* out, int B, int max_nodes, double eps_rel, double margin, bool euclid)
+// the context's Euclidean tables -- the obstacles', or with `pair` the region's -- made on the first Euclidean call after the
+// tables were set; a refusal is remembered (ko_eu_state / pk_eu_state) and answered again
+static int keep_out_euclid_tables(obtg_ctx* c, bool pair)
 {
-    if (int rc = keep_out_args(c, out, B, max_nodes, eps_rel, margin, true)) return rc;
-    return euclid ? pair_keep_out_euclid_tables(c) : OBTG_OK;
+    int& state = pair ? c->pk_eu_state : c->ko_eu_state;
+    if (state) return state == 1 ? OBTG_OK : state;
+    const int region[2] = {0, c->pk_F};
+    const int rc = pair ? keep_out_feature_tables(c, c->h_pk_H.data(), region, 1, c->dim, c->d_pk_Hn, &c->d_pk_feat, nullptr, &c->pk_NF)
+                        : keep_out_feature_tables(c, c->h_ko_H.data(), c->h_ko_off.data(), c->ko_O, c->dim, c->d_ko_Hn, &c->d_ko_feat,
+                                                  &c->d_ko_foff, nullptr);
+    if (rc == OBTG_OK) state = 1;
+    else if (rc == OBTG_ERR_UNSUPPORTED) state = rc;
+    return rc;
 }
 
-// d_fi | d_ld: face[.][2] | lam, under the Euclidean metric faces[.][3] | dir[.][d]
-static int pair_keep_out_launch(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, bool euclid,
-                                double* d_out, double* d_t, int* d_fi, double* d_ld, double* d_bound, int* d_nodes, int* d_status,
-                                double* d_rel, double* d_jac)
+// What an entry point of the context forms passes beside its outputs.  tf: the moving forms'; want_jac: the _jac entry points,
+// where the blocks (and the moving forms' jac_tf) are not optional
+struct KoCall {
+    unsigned form;
+    bool want_jac;
+    const double* Y;
+    const double* tf;
+    int B;
+    double margin, eps_rel;
+    int max_nodes;
+};
+
+static KoCall ko_call(unsigned form, bool want_jac, const double* Y, const double* tf, int B, double margin, double eps_rel, int max_nodes)
 {
-    const int P = obtg_len_pair_keep_out(c);
-    KeepOutPairEuclidArgs eu{c->d_pk_feat.as<double>(), c->pk_NF, d_fi, d_ld};
-    return launch_keep_out_pair(c, c->dim, c->deg + 1, dY, (long)B * P, c->n_veh, P, (euclid ? c->d_pk_Hn : c->d_pk_H).as<double>(),
-                                c->d_pk_IJ.as<int>(), c->pk_F, euclid ? &eu : nullptr, margin, eps_rel, max_nodes, d_out, d_t,
-                                euclid ? nullptr : d_fi, euclid ? nullptr : d_ld, d_bound, d_nodes, d_status, d_rel, d_jac, OBTG_K_SPEED);
+    KoCall k{};
+    k.form = form; k.want_jac = want_jac; k.Y = Y; k.tf = tf; k.B = B; k.margin = margin; k.eps_rel = eps_rel; k.max_nodes = max_nodes;
+    return k;
 }
 
-// want_jac: the _jac entry points, where the blocks are not optional
-static int pair_keep_out_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, bool euclid, double* d_out,
-                             double* d_t, int* d_fi, double* d_ld, double* d_bound, int* d_nodes, int* d_status, double* d_rel,
-                             bool want_jac, double* d_jac)
+// The refusals of the context forms, in the order a caller can observe; all before any launch
+static int keep_out_args(obtg_ctx* c, const KoCall& k, const KeepOutOutputs& o)
 {
-    if (int rc = pair_keep_out_args(c, d_out, B, max_nodes, eps_rel, margin, euclid)) return rc;
-    if (!dY || (want_jac && !d_jac)) return OBTG_ERR_ARG;
+    const bool pair = k.form & KO_PAIR;
+    if (!check_ctx(c) || (pair ? c->pk_F : c->ko_P) <= 0 || (c->dim != 2 && c->dim != 3) || !o.val || k.B < 0 || k.max_nodes < 1 ||
+        !(k.eps_rel >= 0.0) || k.margin != k.margin)
+        return OBTG_ERR_ARG;
+    if (c->deg > 31) return OBTG_ERR_UNSUPPORTED;
+    if (k.form == KO_EUCLID && c->ko_motion) return OBTG_ERR_UNSUPPORTED;       // moving obstacles under this metric are not built
+    if (k.form & KO_EUCLID)
+        if (int rc = keep_out_euclid_tables(c, pair)) return rc;
+    // (a moving call on a context without a motion is a caller who forgot to set one, not a request for the static rows)
+    if ((k.form & KO_MOVING) && (!c->ko_motion || !k.tf || (k.want_jac && !o.jac_tf))) return OBTG_ERR_ARG;
+    return !k.Y || (k.want_jac && !o.jac) ? OBTG_ERR_ARG : OBTG_OK;
+}
+
+// the launch of a context form: the context's tables by name
+static int keep_out_launch(obtg_ctx* c, const KoCall& k, const double* dY, const double* d_tf, const KeepOutOutputs& dev)
+{
+    KeepOutLaunch a{};
+    a.dim = c->dim; a.K = c->deg + 1; a.n_veh = c->n_veh;
+    a.moving = k.form & KO_MOVING; a.euclid = k.form & KO_EUCLID; a.pair = k.form & KO_PAIR;
+    a.Y = dY; a.margin = k.margin; a.eps_rel = k.eps_rel; a.max_nodes = k.max_nodes; a.out = dev;
+    if (a.pair) {
+        a.P = obtg_len_pair_keep_out(c); a.F_all = c->pk_F;
+        a.H = (a.euclid ? c->d_pk_Hn : c->d_pk_H).as<double>(); a.VO_or_IJ = c->d_pk_IJ.as<int>();
+        if (a.euclid) { a.feat = c->d_pk_feat.as<double>(); a.NF_all = c->pk_NF; }
+    } else {
+        a.P = c->ko_P;
+        a.H = (a.euclid ? c->d_ko_Hn : c->d_ko_H).as<double>(); a.off = c->d_ko_off.as<int>(); a.VO_or_IJ = c->d_ko_VO.as<int>();
+        if (a.euclid) { a.feat = c->d_ko_feat.as<double>(); a.feat_off = c->d_ko_foff.as<int>(); }
+        if (a.moving) { a.Q = c->d_ko_Q.as<double>(); a.q_off = c->d_ko_qoff.as<int>(); a.T = c->d_ko_T.as<double>(); a.tf = d_tf; }
+    }
+    a.M = (long)k.B * a.P;
+    return launch_keep_out(c, a);
+}
+
+// the _dev body: Y, tf and the outputs are the caller's device memory (an empty call is the launcher's OBTG_OK)
+static int keep_out_dev(obtg_ctx* c, const KoCall& k, const KeepOutOutputs& o)
+{
+    if (int rc = keep_out_args(c, k, o)) return rc;
     (void)hipSetDevice(c->device);
-    return pair_keep_out_launch(c, dY, B, margin, eps_rel, max_nodes, euclid, d_out, d_t, d_fi, d_ld, d_bound, d_nodes, d_status, d_rel,
-                                d_jac);
+    return keep_out_launch(c, k, k.Y, k.tf, o);
 }
 
-// the host body: Y up; val | t_star | bound | lam or dir | rel | jac in ws_out, face(s) | nodes | status in WS_STATUS
-static int pair_keep_out_host(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, bool euclid, double* out,
-                              double* t_star, int* fi, double* ld, double* bound, int* nodes, int* status, double* rel, bool want_jac,
-                              double* jac)
+// the host body: Y (and tf) up zero-copy, the columns of the table in the workspace, one download per output asked for
+static int keep_out_host(obtg_ctx* c, const KoCall& k, const KeepOutOutputs& o)
 {
-    if (int rc = pair_keep_out_args(c, out, B, max_nodes, eps_rel, margin, euclid)) return rc;
-    if (!Y || (want_jac && !jac)) return OBTG_ERR_ARG;
-    const size_t n = (size_t)B * obtg_len_pair_keep_out(c);
-    if (n == 0) return OBTG_OK;
-    const size_t nb = n * c->dim * (c->deg + 1), nl = euclid ? n * c->dim : n, nf = euclid ? 3 : 2, nr = rel ? nb : 0,
-                 nj = want_jac ? nb : 0;
+    if (int rc = keep_out_args(c, k, o)) return rc;
+    const size_t n = (size_t)k.B * ((k.form & KO_PAIR) ? obtg_len_pair_keep_out(c) : c->ko_P);
+    if (n == 0) return OBTG_OK;                // (B == 0, or a pair call on a context of one vehicle)
     HostCall h(c);
-    const double* dY = h.in(c->ws_in, Y, ysize(c) * B, true);
-    double* dv = h.out<double>(c->ws_out, 3 * n + nl + nr + nj);
-    int* di = h.out<int>(c->ws_misc[WS_STATUS], (nf + 2) * n);
-    double* dr = rel ? dv + 3 * n + nl : nullptr;
-    double* dj = want_jac ? dv + 3 * n + nl + nr : nullptr;
-    h.run([&] { return pair_keep_out_launch(c, dY, B, margin, eps_rel, max_nodes, euclid, dv, dv + n, di, dv + 3 * n, dv + 2 * n,
-                                            di + nf * n, di + (nf + 1) * n, dr, dj); });
-    h.fetch(t_star, dv + n, n);
-    h.fetch(bound, dv + 2 * n, n);
-    h.fetch(ld, dv + 3 * n, nl);
-    h.fetch(fi, di, nf * n);
-    h.fetch(nodes, di + nf * n, n);
-    h.fetch(status, di + (nf + 1) * n, n);
-    h.fetch(rel, dr, nr);
-    h.fetch(jac, dj, nj);
-    return h.finish(out, dv, n);
+    const double* dY = h.in(c->ws_in, k.Y, ysize(c) * k.B, true);
+    const double* d_tf = (k.form & KO_MOVING) ? h.in(c->ws_in2, k.tf, (size_t)k.B, true) : nullptr;
+    const KeepOutOutputs dev = keep_out_device_outputs(h, k.form, c->dim, c->deg + 1, n, o);
+    h.run([&] { return keep_out_launch(c, k, dY, d_tf, dev); });
+    return keep_out_download(h, k.form, c->dim, c->deg + 1, n, o, dev);
+}
+
+// Free curves cv[M][dim][K] against ONE face table H[F][dim+1] (a host array in both forms), whatever the context's shape is:
+// the same kernel, one obstacle of all F faces, margin 0; KO_EUCLID: under the Euclidean metric (Hn | the records in one buffer);
+// KO_MOVING: the obstacle moves by Q[dim][Km] (a host array in both forms), r[M] per curve the part [0, r] of the motion's
+// parameter that the curve spans (null: 1; device memory in the _dev forms).  The context's own keep-out tables are not touched:
+// the tables of the call go to WS_ARG_A and WS_ARG_B.  dev: cv, r and the outputs are device memory.
+static int bern_keep_out(obtg_ctx* c, unsigned form, bool dev, const double* cv, int M, int dim, int K, const double* H, int F,
+                         const double* Q, int Km, const double* r, double eps_rel, int max_nodes, double* val, double* t_star, int* status)
+{
+    if (!check_ctx(c) || M < 0 || (dim != 2 && dim != 3) || K < 2 || F < 1 || !H || max_nodes < 1 || !(eps_rel >= 0.0)) return OBTG_ERR_ARG;
+    if (K > kMdMaxCurveK || F > kKeepOutMaxFaces) return OBTG_ERR_UNSUPPORTED;
+    if (M > 0 && !(cv && val)) return OBTG_ERR_ARG;
+    if (form & KO_MOVING) {                    // (a bad motion is refused in an empty call too)
+        if (Km < 1 || !Q) return OBTG_ERR_ARG;
+        if (Km > K) return OBTG_ERR_UNSUPPORTED;
+    }
+    if (M == 0) return OBTG_OK;
+    (void)hipSetDevice(c->device);
+    DevBuf &dH = c->ws_misc[WS_ARG_A], &dQ = c->ws_misc[WS_ARG_B];
+    const int faces[2] = {0, F};
+    KeepOutLaunch a{};
+    a.dim = dim; a.K = K; a.M = M; a.n_veh = a.P = 1; a.F_all = F; a.moving = form & KO_MOVING; a.euclid = form & KO_EUCLID;
+    a.eps_rel = eps_rel; a.max_nodes = max_nodes;
+    if (int rc = a.euclid ? keep_out_feature_tables(c, H, faces, 1, dim, dH, nullptr, nullptr, &a.NF_all)
+                          : upload(c, dH, H, sizeof(double) * (size_t)F * (dim + 1)))
+        return rc;
+    a.H = dH.as<double>();
+    if (a.euclid) a.feat = a.H + (size_t)F * (dim + 1);
+    if (a.moving) {
+        if (int rc = upload(c, dQ, Q, sizeof(double) * (size_t)Km * dim)) return rc;
+        a.Q = dQ.as<double>(); a.Km = Km;
+    }
+    KeepOutOutputs o{};
+    o.val = val; o.t = t_star; o.status = status;
+    if (dev) {
+        a.Y = cv; a.r = r; a.out = o;
+        return launch_keep_out(c, a);
+    }
+    const size_t n = (size_t)M;
+    HostCall h(c);
+    a.Y = h.in(c->ws_in, cv, n * dim * K);
+    a.r = r ? h.in(c->ws_in2, r, n) : nullptr;
+    a.out = keep_out_device_outputs(h, form | KO_FREE, dim, K, n, o);
+    h.run([&] { return launch_keep_out(c, a); });
+    return keep_out_download(h, form | KO_FREE, dim, K, n, o, a.out);
+}
+
+// The entry points: each names its form and passes its pointers.  include/obtg.h has two orders of the outputs, the faces
+// metric's (face, lam) and the Euclidean metric's (faces, dir); rel, jac and jac_tf follow where the entry point has them.
+static KeepOutOutputs ko_out(double* val, double* t, int* face, double* lam, double* bound, int* nodes, int* status, double* rel = nullptr,
+                             double* jac = nullptr, double* jac_tf = nullptr)
+{
+    KeepOutOutputs o{};
+    o.val = val; o.t = t; o.face = face; o.lam = lam; o.bound = bound; o.nodes = nodes; o.status = status;
+    o.rel = rel; o.jac = jac; o.jac_tf = jac_tf;
+    return o;
+}
+
+static KeepOutOutputs ko_out_euclid(double* val, double* t, int* faces3, double* dir, double* bound, int* nodes, int* status,
+                                    double* rel = nullptr, double* jac = nullptr)
+{
+    KeepOutOutputs o{};
+    o.val = val; o.t = t; o.faces3 = faces3; o.dir = dir; o.bound = bound; o.nodes = nodes; o.status = status;
+    o.rel = rel; o.jac = jac;
+    return o;
+}
+
+int obtg_keep_out_true_min_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
+                               double* d_t_star, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status)
+{
+    return keep_out_dev(c, ko_call(0, false, dY, nullptr, B, margin, eps_rel, max_nodes),
+                        ko_out(d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status));
+}
+
+int obtg_keep_out_true_min(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out, double* t_star,
+                           int* face, double* lam, double* bound, int* nodes, int* status)
+{
+    return keep_out_host(c, ko_call(0, false, Y, nullptr, B, margin, eps_rel, max_nodes),
+                         ko_out(out, t_star, face, lam, bound, nodes, status));
+}
+
+int obtg_keep_out_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
+                                   double* d_t_star, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status,
+                                   double* d_jac)
+{
+    return keep_out_dev(c, ko_call(0, true, dY, nullptr, B, margin, eps_rel, max_nodes),
+                        ko_out(d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, nullptr, d_jac));
+}
+
+int obtg_keep_out_true_min_jac(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
+                               double* t_star, int* face, double* lam, double* bound, int* nodes, int* status, double* jac)
+{
+    return keep_out_host(c, ko_call(0, true, Y, nullptr, B, margin, eps_rel, max_nodes),
+                         ko_out(out, t_star, face, lam, bound, nodes, status, nullptr, jac));
+}
+
+int obtg_keep_out_euclid_true_min_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
+                                      double* d_t_star, int* d_faces, double* d_dir, double* d_bound, int* d_nodes, int* d_status)
+{
+    return keep_out_dev(c, ko_call(KO_EUCLID, false, dY, nullptr, B, margin, eps_rel, max_nodes),
+                        ko_out_euclid(d_out, d_t_star, d_faces, d_dir, d_bound, d_nodes, d_status));
+}
+
+int obtg_keep_out_euclid_true_min(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
+                                  double* t_star, int* faces, double* dir, double* bound, int* nodes, int* status)
+{
+    return keep_out_host(c, ko_call(KO_EUCLID, false, Y, nullptr, B, margin, eps_rel, max_nodes),
+                         ko_out_euclid(out, t_star, faces, dir, bound, nodes, status));
+}
+
+int obtg_keep_out_euclid_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes,
+                                          double* d_out, double* d_t_star, int* d_faces, double* d_dir, double* d_bound, int* d_nodes,
+                                          int* d_status, double* d_jac)
+{
+    return keep_out_dev(c, ko_call(KO_EUCLID, true, dY, nullptr, B, margin, eps_rel, max_nodes),
+                        ko_out_euclid(d_out, d_t_star, d_faces, d_dir, d_bound, d_nodes, d_status, nullptr, d_jac));
+}
+
+int obtg_keep_out_euclid_true_min_jac(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
+                                      double* t_star, int* faces, double* dir, double* bound, int* nodes, int* status, double* jac)
+{
+    return keep_out_host(c, ko_call(KO_EUCLID, true, Y, nullptr, B, margin, eps_rel, max_nodes),
+                         ko_out_euclid(out, t_star, faces, dir, bound, nodes, status, nullptr, jac));
+}
+
+int obtg_keep_out_moving_true_min_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double margin, double eps_rel, int max_nodes,
+                                      double* d_out, double* d_t_star, int* d_face, double* d_lam, double* d_bound, int* d_nodes,
+                                      int* d_status, double* d_rel)
+{
+    return keep_out_dev(c, ko_call(KO_MOVING, false, dY, d_tf, B, margin, eps_rel, max_nodes),
+                        ko_out(d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel));
+}
+
+int obtg_keep_out_moving_true_min(obtg_ctx* c, const double* Y, const double* tf, int B, double margin, double eps_rel, int max_nodes,
+                                  double* out, double* t_star, int* face, double* lam, double* bound, int* nodes, int* status, double* rel)
+{
+    return keep_out_host(c, ko_call(KO_MOVING, false, Y, tf, B, margin, eps_rel, max_nodes),
+                         ko_out(out, t_star, face, lam, bound, nodes, status, rel));
+}
+
+int obtg_keep_out_moving_true_min_jac_dev(obtg_ctx* c, const double* dY, const double* d_tf, int B, double margin, double eps_rel,
+                                          int max_nodes, double* d_out, double* d_t_star, int* d_face, double* d_lam, double* d_bound,
+                                          int* d_nodes, int* d_status, double* d_rel, double* d_jac, double* d_jac_tf)
+{
+    return keep_out_dev(c, ko_call(KO_MOVING, true, dY, d_tf, B, margin, eps_rel, max_nodes),
+                        ko_out(d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel, d_jac, d_jac_tf));
+}
+
+int obtg_keep_out_moving_true_min_jac(obtg_ctx* c, const double* Y, const double* tf, int B, double margin, double eps_rel, int max_nodes,
+                                      double* out, double* t_star, int* face, double* lam, double* bound, int* nodes, int* status,
+                                      double* rel, double* jac, double* jac_tf)
+{
+    return keep_out_host(c, ko_call(KO_MOVING, true, Y, tf, B, margin, eps_rel, max_nodes),
+                         ko_out(out, t_star, face, lam, bound, nodes, status, rel, jac, jac_tf));
 }
 
 int obtg_pair_keep_out_true_min_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
                                     double* d_t_star, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status,
                                     double* d_rel)
 {
-    return pair_keep_out_dev(c, dY, B, margin, eps_rel, max_nodes, false, d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel,
-                             false, nullptr);
+    return keep_out_dev(c, ko_call(KO_PAIR, false, dY, nullptr, B, margin, eps_rel, max_nodes),
+                        ko_out(d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel));
 }
 
 int obtg_pair_keep_out_true_min(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
                                 double* t_star, int* face, double* lam, double* bound, int* nodes, int* status, double* rel)
 {
-    return pair_keep_out_host(c, Y, B, margin, eps_rel, max_nodes, false, out, t_star, face, lam, bound, nodes, status, rel, false, nullptr);
+    return keep_out_host(c, ko_call(KO_PAIR, false, Y, nullptr, B, margin, eps_rel, max_nodes),
+                         ko_out(out, t_star, face, lam, bound, nodes, status, rel));
 }
 
 int obtg_pair_keep_out_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes, double* d_out,
                                         double* d_t_star, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status,
                                         double* d_rel, double* d_jac)
 {
-    return pair_keep_out_dev(c, dY, B, margin, eps_rel, max_nodes, false, d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel,
-                             true, d_jac);
+    return keep_out_dev(c, ko_call(KO_PAIR, true, dY, nullptr, B, margin, eps_rel, max_nodes),
+                        ko_out(d_out, d_t_star, d_face, d_lam, d_bound, d_nodes, d_status, d_rel, d_jac));
 }
 
 int obtg_pair_keep_out_true_min_jac(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
                                     double* t_star, int* face, double* lam, double* bound, int* nodes, int* status, double* rel,
                                     double* jac)
 {
-    return pair_keep_out_host(c, Y, B, margin, eps_rel, max_nodes, false, out, t_star, face, lam, bound, nodes, status, rel, true, jac);
+    return keep_out_host(c, ko_call(KO_PAIR, true, Y, nullptr, B, margin, eps_rel, max_nodes),
+                         ko_out(out, t_star, face, lam, bound, nodes, status, rel, jac));
 }
 
 int obtg_pair_keep_out_euclid_true_min_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes,
                                            double* d_out, double* d_t_star, int* d_faces, double* d_dir, double* d_bound, int* d_nodes,
                                            int* d_status, double* d_rel)
 {
-    return pair_keep_out_dev(c, dY, B, margin, eps_rel, max_nodes, true, d_out, d_t_star, d_faces, d_dir, d_bound, d_nodes, d_status, d_rel,
-                             false, nullptr);
+    return keep_out_dev(c, ko_call(KO_PAIR | KO_EUCLID, false, dY, nullptr, B, margin, eps_rel, max_nodes),
+                        ko_out_euclid(d_out, d_t_star, d_faces, d_dir, d_bound, d_nodes, d_status, d_rel));
 }
 
 int obtg_pair_keep_out_euclid_true_min(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
                                        double* t_star, int* faces, double* dir, double* bound, int* nodes, int* status, double* rel)
 {
-    return pair_keep_out_host(c, Y, B, margin, eps_rel, max_nodes, true, out, t_star, faces, dir, bound, nodes, status, rel, false, nullptr);
+    return keep_out_host(c, ko_call(KO_PAIR | KO_EUCLID, false, Y, nullptr, B, margin, eps_rel, max_nodes),
+                         ko_out_euclid(out, t_star, faces, dir, bound, nodes, status, rel));
 }
 
 int obtg_pair_keep_out_euclid_true_min_jac_dev(obtg_ctx* c, const double* dY, int B, double margin, double eps_rel, int max_nodes,
                                                double* d_out, double* d_t_star, int* d_faces, double* d_dir, double* d_bound,
                                                int* d_nodes, int* d_status, double* d_rel, double* d_jac)
 {
-    return pair_keep_out_dev(c, dY, B, margin, eps_rel, max_nodes, true, d_out, d_t_star, d_faces, d_dir, d_bound, d_nodes, d_status, d_rel,
-                             true, d_jac);
+    return keep_out_dev(c, ko_call(KO_PAIR | KO_EUCLID, true, dY, nullptr, B, margin, eps_rel, max_nodes),
+                        ko_out_euclid(d_out, d_t_star, d_faces, d_dir, d_bound, d_nodes, d_status, d_rel, d_jac));
 }
 
 int obtg_pair_keep_out_euclid_true_min_jac(obtg_ctx* c, const double* Y, int B, double margin, double eps_rel, int max_nodes, double* out,
                                            double* t_star, int* faces, double* dir, double* bound, int* nodes, int* status, double* rel,
                                            double* jac)
 {
-    return pair_keep_out_host(c, Y, B, margin, eps_rel, max_nodes, true, out, t_star, faces, dir, bound, nodes, status, rel, true, jac);
+    return keep_out_host(c, ko_call(KO_PAIR | KO_EUCLID, true, Y, nullptr, B, margin, eps_rel, max_nodes),
+                         ko_out_euclid(out, t_star, faces, dir, bound, nodes, status, rel, jac));
+}
+
+int obtg_bern_keep_out_dev(obtg_ctx* c, const double* d_c, int M, int dim, int K, const double* H, int F, double eps_rel, int max_nodes,
+                           double* d_val, double* d_t_star, int* d_status)
+{
+    return bern_keep_out(c, 0, true, d_c, M, dim, K, H, F, nullptr, 0, nullptr, eps_rel, max_nodes, d_val, d_t_star, d_status);
+}
+
+int obtg_bern_keep_out(obtg_ctx* c, const double* cv, int M, int dim, int K, const double* H, int F, double eps_rel, int max_nodes,
+                       double* val, double* t_star, int* status)
+{
+    return bern_keep_out(c, 0, false, cv, M, dim, K, H, F, nullptr, 0, nullptr, eps_rel, max_nodes, val, t_star, status);
+}
+
+int obtg_bern_keep_out_euclid_dev(obtg_ctx* c, const double* d_c, int M, int dim, int K, const double* H, int F, double eps_rel,
+                                  int max_nodes, double* d_val, double* d_t_star, int* d_status)
+{
+    return bern_keep_out(c, KO_EUCLID, true, d_c, M, dim, K, H, F, nullptr, 0, nullptr, eps_rel, max_nodes, d_val, d_t_star, d_status);
+}
+
+int obtg_bern_keep_out_euclid(obtg_ctx* c, const double* cv, int M, int dim, int K, const double* H, int F, double eps_rel, int max_nodes,
+                              double* val, double* t_star, int* status)
+{
+    return bern_keep_out(c, KO_EUCLID, false, cv, M, dim, K, H, F, nullptr, 0, nullptr, eps_rel, max_nodes, val, t_star, status);
+}
+
+int obtg_bern_keep_out_moving_dev(obtg_ctx* c, const double* d_c, int M, int dim, int K, const double* H, int F, const double* Q, int Km,
+                                  const double* d_r, double eps_rel, int max_nodes, double* d_val, double* d_t_star, int* d_status)
+{
+    return bern_keep_out(c, KO_MOVING, true, d_c, M, dim, K, H, F, Q, Km, d_r, eps_rel, max_nodes, d_val, d_t_star, d_status);
+}
+
+int obtg_bern_keep_out_moving(obtg_ctx* c, const double* cv, int M, int dim, int K, const double* H, int F, const double* Q, int Km,
+                              const double* r, double eps_rel, int max_nodes, double* val, double* t_star, int* status)
+{
+    return bern_keep_out(c, KO_MOVING, false, cv, M, dim, K, H, F, Q, Km, r, eps_rel, max_nodes, val, t_star, status);
 }
 
 // Free curves c[M][dim][K], any K from 2 to 32 whatever the context's shape is: the family's rows kernel and workspace search

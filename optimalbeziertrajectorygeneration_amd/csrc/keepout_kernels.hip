@@ -42,6 +42,11 @@
 // against ONE region around the origin, under either metric.  The prologue is one subtraction per control point; D stays in LDS
 // behind the faces (behind the records under the Euclidean metric: OBTG_KO_LDS_WAVE_DOUBLES), the root reads it from its registers and the
 // evaluation at t_star from LDS -- what the moving form does with its D.  No E, no restriction, no jac_tf.
+//
+// Launch (below the kernel): ONE launcher, launch_keep_out over KeepOutLaunch (obtg_internal.h), for all five
+// parameter types.  It refuses what the kernel is not built for, fills the common prefix of the parameters once and the form's
+// own members after it, and picks one of the ten instantiations.  A new form is a parameter struct here, its members in
+// launch_keep_out_form and a line in launch_keep_out; the host side of it is a line of capi.cpp's column table.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -480,102 +485,46 @@ __global__ __launch_bounds__(kKoWaves * kWave) void k_keep_out(const PRM p)
     }
 }
 
-// d_H | d_off | d_VO: device tables (the context's, or a free-curve call's own); VO null: free curves, one obstacle of F_all faces
-int launch_keep_out(obtg_ctx* c, int dim, int K, const double* dY, long M, int n_veh, int P, const double* d_H, const int* d_off,
-                    const int* d_VO, int F_all, double margin, double eps_rel, int max_nodes, double* d_val, double* d_t, int* d_face,
-                    double* d_lam, double* d_bound, int* d_nodes, int* d_status, double* d_jac, int kernel_id)
+// One form of the launch: the common prefix of the parameters once, then the form's own members, then one of its two kernels
+template <class PRM>
+static int launch_keep_out_form(obtg_ctx* c, const KeepOutLaunch& a)
 {
-    return launch_keep_out_moving(c, dim, K, dY, M, n_veh, P, d_H, d_off, d_VO, F_all, nullptr, margin, eps_rel, max_nodes, d_val, d_t,
-                                  d_face, d_lam, d_bound, d_nodes, d_status, d_jac, kernel_id);
-}
-
-// mo null: the static form.  mo->Q | q_off | T | tf | r: device tables; mo->rel, mo->jac_tf: nullable outputs
-int launch_keep_out_moving(obtg_ctx* c, int dim, int K, const double* dY, long M, int n_veh, int P, const double* d_H, const int* d_off,
-                           const int* d_VO, int F_all, const KeepOutMotionArgs* mo, double margin, double eps_rel, int max_nodes,
-                           double* d_val, double* d_t, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status,
-                           double* d_jac, int kernel_id)
-{
-    if (M <= 0) return OBTG_OK;
-    if ((dim != 2 && dim != 3) || K < 2 || K > kKoMaxK) return OBTG_ERR_UNSUPPORTED;
-    KeepOutMovingParams p{};
-    p.Y = dY; p.H = d_H; p.obs_off = d_off; p.VO = (const int2*)d_VO;
-    p.val = d_val; p.t = d_t; p.face = d_face; p.lam = d_lam; p.bound = d_bound; p.nodes = d_nodes; p.status = d_status; p.jac = d_jac;
-    p.M = M; p.n_veh = n_veh; p.P = P; p.K = K; p.F_all = F_all; p.max_nodes = max_nodes; p.margin = margin; p.eps_rel = eps_rel;
-    const size_t lds = ko_lds_bytes(dim, K, mo != nullptr, false, false);
-    const dim3 grid((unsigned)((M + kKoWaves - 1) / kKoWaves)), block(kKoWaves * kWave);
-    ScopedKernelTimer t(c, kernel_id);
-    if (mo) {
-        p.Q = mo->d_Q; p.q_off = mo->d_q_off; p.T = mo->d_T; p.tf = mo->d_tf; p.r = mo->d_r; p.rel = mo->d_rel; p.jac_tf = mo->d_jac_tf;
-        p.Km = mo->Km;
-        void (*const kernel)(KeepOutMovingParams) = dim == 2 ? k_keep_out<2, KeepOutMovingParams> : k_keep_out<3, KeepOutMovingParams>;
-        hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, p);
+    const KeepOutOutputs& o = a.out;
+    PRM p{};
+    p.Y = a.Y; p.H = a.H; p.obs_off = a.off; p.VO = (const int2*)a.VO_or_IJ;
+    p.val = o.val; p.t = o.t; p.bound = o.bound; p.nodes = o.nodes; p.status = o.status; p.jac = o.jac;
+    p.M = a.M; p.n_veh = a.n_veh; p.P = a.P; p.K = a.K; p.F_all = a.F_all; p.max_nodes = a.max_nodes;
+    p.margin = a.margin; p.eps_rel = a.eps_rel;
+    if constexpr (PRM::kEuclid) {              // (face and lam stay null: faces3 and dir stand in for them)
+        p.feat = a.feat; p.feat_off = a.feat_off; p.NF_all = a.NF_all; p.dir = o.dir; p.faces3 = o.faces3;
     } else {
-        void (*const kernel)(KeepOutParams) = dim == 2 ? k_keep_out<2, KeepOutParams> : k_keep_out<3, KeepOutParams>;
-        const KeepOutParams& ps = p;
-        hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, ps);
+        p.face = o.face; p.lam = o.lam;
     }
-    OBTG_HIP(c, hipGetLastError());
-    return OBTG_OK;
-}
-
-// The Euclidean metric: d_Hn the normalised faces, d_feat | d_feat_off the feature records (d_feat_off null with d_VO null: free
-// curves, records 0 .. NF_all - 1); d_dir[M][dim] and d_faces3[M][3] in place of face and lam
-int launch_keep_out_euclid(obtg_ctx* c, int dim, int K, const double* dY, long M, int n_veh, int P, const double* d_Hn, const int* d_off,
-                           const int* d_VO, int F_all, const double* d_feat, const int* d_feat_off, int NF_all, double margin,
-                           double eps_rel, int max_nodes, double* d_val, double* d_t, int* d_faces3, double* d_dir, double* d_bound,
-                           int* d_nodes, int* d_status, double* d_jac, int kernel_id)
-{
-    if (M <= 0) return OBTG_OK;
-    if ((dim != 2 && dim != 3) || K < 2 || K > kKoMaxK || NF_all > kKoMaxFeatures) return OBTG_ERR_UNSUPPORTED;
-    KeepOutEuclidParams p{};
-    p.Y = dY; p.H = d_Hn; p.obs_off = d_off; p.VO = (const int2*)d_VO;
-    p.val = d_val; p.t = d_t; p.bound = d_bound; p.nodes = d_nodes; p.status = d_status; p.jac = d_jac;
-    p.M = M; p.n_veh = n_veh; p.P = P; p.K = K; p.F_all = F_all; p.max_nodes = max_nodes; p.margin = margin; p.eps_rel = eps_rel;
-    p.feat = d_feat; p.feat_off = d_feat_off; p.dir = d_dir; p.faces3 = d_faces3; p.NF_all = NF_all;
-    const size_t lds = ko_lds_bytes(dim, K, false, true, false);
-    const dim3 grid((unsigned)((M + kKoWaves - 1) / kKoWaves)), block(kKoWaves * kWave);
-    void (*const kernel)(KeepOutEuclidParams) = dim == 2 ? k_keep_out<2, KeepOutEuclidParams> : k_keep_out<3, KeepOutEuclidParams>;
-    if (lds > 64 * 1024) OBTG_HIP(c, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ScopedKernelTimer t(c, kernel_id);
+    if constexpr (PRM::kMoving) {
+        p.Q = a.Q; p.q_off = a.q_off; p.T = a.T; p.tf = a.tf; p.r = a.r; p.Km = a.Km; p.jac_tf = o.jac_tf;
+    }
+    if constexpr (PRM::kMoving || PRM::kPair) p.rel = o.rel;
+    const size_t lds = ko_lds_bytes(a.dim, a.K, PRM::kMoving, PRM::kEuclid, PRM::kPair);
+    const dim3 grid((unsigned)((a.M + kKoWaves - 1) / kKoWaves)), block(kKoWaves * kWave);
+    void (*const kernel)(PRM) = a.dim == 2 ? k_keep_out<2, PRM> : k_keep_out<3, PRM>;
+    if (PRM::kEuclid && lds > 64 * 1024)
+        OBTG_HIP(c, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ScopedKernelTimer t(c, OBTG_K_SPEED);
     hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, p);
     OBTG_HIP(c, hipGetLastError());
     return OBTG_OK;
 }
 
-// Vehicle pairs against the ONE region d_H[F_all][dim + 1] (eu: the NORMALISED faces, with eu->d_feat[eu->NF] records): d_IJ[P]
-// the pairs' (i, j).  faces metric: d_face[M][2], d_lam[M];  Euclidean: eu->d_faces3[M][3], eu->d_dir[M][dim].  d_rel nullable.
-int launch_keep_out_pair(obtg_ctx* c, int dim, int K, const double* dY, long M, int n_veh, int P, const double* d_H, const int* d_IJ,
-                         int F_all, const KeepOutPairEuclidArgs* eu, double margin, double eps_rel, int max_nodes, double* d_val,
-                         double* d_t, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status, double* d_rel,
-                         double* d_jac, int kernel_id)
+// The ten instantiations: five parameter types (static, Euclidean, moving, pair, Euclidean pair) times two dimensions
+int launch_keep_out(obtg_ctx* c, const KeepOutLaunch& a)
 {
-    if (M <= 0) return OBTG_OK;
-    if ((dim != 2 && dim != 3) || K < 2 || K > kKoMaxK || F_all < 1 || F_all > kKoMaxFaces || (eu && eu->NF > kKoMaxFeatures))
+    if (a.M <= 0) return OBTG_OK;
+    if ((a.dim != 2 && a.dim != 3) || a.K < 2 || a.K > kKoMaxK || (a.euclid && a.NF_all > kKoMaxFeatures) ||
+        (a.pair && (a.F_all < 1 || a.F_all > kKoMaxFaces)) || (a.moving && (a.euclid || a.pair)))      // (k_keep_out's static_asserts)
         return OBTG_ERR_UNSUPPORTED;
-    KeepOutEuclidPairParams p{};
-    p.Y = dY; p.H = d_H; p.VO = (const int2*)d_IJ;
-    p.val = d_val; p.t = d_t; p.face = d_face; p.lam = d_lam; p.bound = d_bound; p.nodes = d_nodes; p.status = d_status; p.jac = d_jac;
-    p.M = M; p.n_veh = n_veh; p.P = P; p.K = K; p.F_all = F_all; p.max_nodes = max_nodes; p.margin = margin; p.eps_rel = eps_rel;
-    p.rel = d_rel;
-    const size_t lds = ko_lds_bytes(dim, K, false, eu != nullptr, true);
-    const dim3 grid((unsigned)((M + kKoWaves - 1) / kKoWaves)), block(kKoWaves * kWave);
-    if (eu) {
-        p.face = nullptr; p.lam = nullptr;
-        p.feat = eu->d_feat; p.NF_all = eu->NF; p.dir = eu->d_dir; p.faces3 = eu->d_faces3;
-        void (*const kernel)(KeepOutEuclidPairParams) = dim == 2 ? k_keep_out<2, KeepOutEuclidPairParams> : k_keep_out<3, KeepOutEuclidPairParams>;
-        if (lds > 64 * 1024) OBTG_HIP(c, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        ScopedKernelTimer t(c, kernel_id);
-        hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, p);
-    } else {
-        KeepOutPairParams pf{};
-        static_cast<KeepOutParams&>(pf) = p;
-        pf.rel = d_rel;
-        void (*const kernel)(KeepOutPairParams) = dim == 2 ? k_keep_out<2, KeepOutPairParams> : k_keep_out<3, KeepOutPairParams>;
-        ScopedKernelTimer t(c, kernel_id);
-        hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, pf);
-    }
-    OBTG_HIP(c, hipGetLastError());
-    return OBTG_OK;
+    if (a.moving) return launch_keep_out_form<KeepOutMovingParams>(c, a);
+    if (a.pair) return a.euclid ? launch_keep_out_form<KeepOutEuclidPairParams>(c, a) : launch_keep_out_form<KeepOutPairParams>(c, a);
+    return a.euclid ? launch_keep_out_form<KeepOutEuclidParams>(c, a) : launch_keep_out_form<KeepOutParams>(c, a);
 }
 
 }  // namespace obtg

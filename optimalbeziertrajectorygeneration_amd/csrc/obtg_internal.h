@@ -463,52 +463,57 @@ RowFamily ang_row_family(const obtg_ctx* c, const double* d_tf, double max_rate)
 // coefficients elevated once per row (R = 0: the family's rows_r0), degree up to 31
 RowFamily keep_in_row_family(const obtg_ctx* c);                                                      // bern_kernels.hip
 int launch_keep_in_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, int R, double* d_out);
-// The keep-out rows (keepout_kernels.hip): min over t of the max over an obstacle's faces of a_f . c(t) - b_f, per item -- a
-// (batch row, vehicle, obstacle) of the tables d_VO / d_off, or (d_VO null) free curve m of dY[M][dim][K] against faces
-// 0 .. F_all - 1 of d_H.  dim 2 or 3, 2 <= K <= 32, at most 16 faces per obstacle (the callers check the faces).  Every output
-// but d_val is nullable; d_jac null: no blocks -- the other outputs are the same bits either way.
-int launch_keep_out(obtg_ctx* c, int dim, int K, const double* dY, long M, int n_veh, int P, const double* d_H, const int* d_off,
-                    const int* d_VO, int F_all, double margin, double eps_rel, int max_nodes, double* d_val, double* d_t, int* d_face,
-                    double* d_lam, double* d_bound, int* d_nodes, int* d_status, double* d_jac, int kernel_id);
-// The same search against obstacles that move (obtg_keep_out_moving_*): mo null is launch_keep_out.  With tables (d_VO): d_Q the
-// obstacles' [dim][m_o + 1] blocks one after the other, d_q_off[O + 1] in control points (an empty run: the obstacle stands
-// still), d_T[O], d_tf[B]; free curves (d_VO null): d_Q[dim][Km], d_r[M] or null (1).  Km <= K is the callers' check.
-// d_rel[M][dim][K] and d_jac_tf[M] are nullable outputs.
-struct KeepOutMotionArgs {
-    const double* d_Q;
-    const int* d_q_off;
-    const double* d_T;
-    const double* d_tf;
-    const double* d_r;
+// The keep-out rows (keepout_kernels.hip): min over t of the max over an obstacle's faces of a_f . c(t) - b_f, per item, in
+// every form the family has -- ONE launcher over one argument struct; the host path on top of it is DESIGN.md 4.29.
+// The outputs of a call as one named set: device pointers for the launcher, host pointers for the entry points (capi.cpp's
+// column table walks it).  Every one but val is nullable; rel, jac and jac_tf null: the kernel skips those stores, the other
+// outputs are the same bits either way.
+struct KeepOutOutputs {
+    double* val;            // [M]
+    double* t;              // [M]
+    int* face;              // [M][2]: the faces metric's active faces ...
+    double* lam;            // [M]:    ... and the first one's weight
+    int* faces3;            // [M][3]: the Euclidean metric's active set, -1 padded ...
+    double* dir;            // [M][dim]: ... and the unit direction; they stand in for face and lam, which are then not written
+    double* bound;          // [M]
+    int* nodes;             // [M]
+    int* status;            // [M]
+    double* rel;            // [M][dim][K]: the relative control points (moving, pair)
+    double* jac;            // [M][dim][K]
+    double* jac_tf;         // [M] (moving)
+};
+// Items: with tables (VO_or_IJ set), item (b, k) of M = B P is batch row b of Y[B][n_veh dim][K] against entry k of the table --
+// (vehicle, obstacle), obstacle o owning faces off[o] .. off[o + 1] - 1 of H (at most 16, the callers' check), or with `pair`
+// the vehicles (i, j) against the ONE region H[F_all][dim + 1], 1 <= F_all <= 16.  Free curves (VO_or_IJ null): curve m of
+// Y[M][dim][K] against faces 0 .. F_all - 1.  dim 2 or 3, 2 <= K <= 32.
+//   euclid: H holds the NORMALISED faces, feat[.][7] the feature records, feat_off[O + 1] their ranges (pairs and free curves:
+//           feat_off null, records 0 .. NF_all - 1; at most 128 records per obstacle);
+//   moving: Q the obstacles' [dim][m_o + 1] blocks one after the other, q_off[O + 1] in control points (an empty run: the
+//           obstacle stands still), T[O], tf[B]; free curves: Q[dim][Km] (Km <= K is the callers' check), r[M] or null (1).
+// M <= 0 answers OBTG_OK; a shape out of range, or moving together with euclid or pair, OBTG_ERR_UNSUPPORTED.
+struct KeepOutLaunch {
+    int dim, K;
+    long M;
+    int n_veh, P, F_all;
+    bool moving, euclid, pair;
+    const double* Y;
+    const double* H;
+    const int* off;
+    const int* VO_or_IJ;
+    const double* feat;
+    const int* feat_off;
+    int NF_all;
+    const double* Q;
+    const int* q_off;
+    const double* T;
+    const double* tf;
+    const double* r;
     int Km;
-    double* d_rel;
-    double* d_jac_tf;
+    double margin, eps_rel;
+    int max_nodes;
+    KeepOutOutputs out;
 };
-int launch_keep_out_moving(obtg_ctx* c, int dim, int K, const double* dY, long M, int n_veh, int P, const double* d_H, const int* d_off,
-                           const int* d_VO, int F_all, const KeepOutMotionArgs* mo, double margin, double eps_rel, int max_nodes,
-                           double* d_val, double* d_t, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status,
-                           double* d_jac, int kernel_id);
-// The Euclidean metric of the static form (obtg_keep_out_euclid_*): the same kernel body over d_Hn, the NORMALISED faces, with
-// the obstacles' feature records d_feat[.][7] and their ranges d_feat_off[O + 1] (free curves, d_VO null: d_feat_off null and
-// records 0 .. NF_all - 1; at most 128 records per obstacle).  d_faces3[M][3] and d_dir[M][dim] are nullable outputs.
-int launch_keep_out_euclid(obtg_ctx* c, int dim, int K, const double* dY, long M, int n_veh, int P, const double* d_Hn, const int* d_off,
-                           const int* d_VO, int F_all, const double* d_feat, const int* d_feat_off, int NF_all, double margin,
-                           double eps_rel, int max_nodes, double* d_val, double* d_t, int* d_faces3, double* d_dir, double* d_bound,
-                           int* d_nodes, int* d_status, double* d_jac, int kernel_id);
-// Vehicle pairs against ONE region around the origin (obtg_pair_keep_out_*): the same kernel body on D = Y_i - Y_j, d_IJ[P] the
-// pairs' (i, j), d_H[F_all][dim + 1] the region (1 <= F_all <= 16).  eu null: the faces metric (d_face[M][2], d_lam[M]); eu set:
-// d_H holds the NORMALISED faces, eu->d_feat[eu->NF][7] the region's records (at most 128), and eu->d_faces3[M][3], eu->d_dir[M][dim]
-// stand in for d_face and d_lam, which are not written.  d_rel[M][dim][K] is a nullable output.
-struct KeepOutPairEuclidArgs {
-    const double* d_feat;
-    int NF;
-    int* d_faces3;
-    double* d_dir;
-};
-int launch_keep_out_pair(obtg_ctx* c, int dim, int K, const double* dY, long M, int n_veh, int P, const double* d_H, const int* d_IJ,
-                         int F_all, const KeepOutPairEuclidArgs* eu, double margin, double eps_rel, int max_nodes, double* d_val,
-                         double* d_t, int* d_face, double* d_lam, double* d_bound, int* d_nodes, int* d_status, double* d_rel,
-                         double* d_jac, int kernel_id);
+int launch_keep_out(obtg_ctx* c, const KeepOutLaunch& a);
 // the angular-rate family's polynomials [B][n_veh][2][2 deg + 1] (obtg_ang_rate_poly; its rows_r0): dim 2, degree 1 .. 31
 int launch_ang_rows(obtg_ctx* c, const RowFamily& f, const double* dY, int B, double* d_out);
 // The two curvature families, kind = ROWS_CURV (dim 2; two items, the sides, per vehicle; workspace rows num, den) or ROWS_SCURV
